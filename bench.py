@@ -20,6 +20,10 @@ for `value`): configs[3] with the vocoder, the per-GPU share of configs[2] (UniP
 latency of the caller north_star names (22_infer_tts.py), and `split_f16`: the same configs[1] step with
 every UNet GEMM on the opt-in two-fp16-term path (csrc/conv_bf3.hip; 22-bit operands, narrower than the
 reference's fp32), reported next to -- never as -- the exact-fp32 `value`.
+
+Every timed step seeds the global generator (the sampler's start noise), so the same arguments compute the same outputs run after run;
+`--dump-outputs DIR` writes those of the last timed step as DIR/mel.npy (and DIR/wav.npy where the workload has a vocoder), so two builds
+can be compared output for output.
 """
 import argparse
 import json
@@ -45,6 +49,8 @@ PEAK_HBM_TBS = 8.0               # HBM3E spec peak (same table; ~6.3 TB/s achiev
 FRAME_SEC = 512 / 44100.0        # one mel frame = hop 512 @ 44.1 kHz (reference configs/config.yaml:3,12)
 UNET_GFLOP_PER_UTT_FWD = 40.98   # SURVEY.md 8d (T=512, M=80), algorithmic
 VOCODER_GFLOP_PER_UTT = 331.9    # SURVEY.md App. B (512 frames, synthetic h)
+STEP_SEED = 20240                # torch.manual_seed(STEP_SEED + rank) before every step of run_job
+DUMP_CAP_BYTES = 64 << 20        # --dump-outputs writes at most this much in all
 
 
 def cpu_baseline(T, n_eval):
@@ -205,6 +211,26 @@ def roofline_from_profile(prof):
     return roof, {r["name"]: round(r["ms"], 3) for r in prof[:14]}
 
 
+def dump_outputs(outs, out_dir, cap_bytes=DUMP_CAP_BYTES):
+    """--dump-outputs: every array of one step's result as <out_dir>/<name>.npy in float32.  When the arrays hold more than cap_bytes in all,
+    each keeps its share of the cap as a sample at sorted flat indices drawn from a generator seeded with 0: the same shapes give the same
+    indices, so two builds' files compare element for element.  Returns {name: {"shape", "elements_written"}}."""
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(v.numel() for v in outs.values())
+    cap = cap_bytes // 4
+    written = {}
+    for name, v in sorted(outs.items()):
+        v = v.detach()
+        if total > cap:
+            n = v.numel()
+            idx = np.unique(np.random.default_rng(0).integers(0, n, size=n * cap // total))
+            v = v.reshape(-1)[torch.from_numpy(idx).to(v.device)]
+        arr = v.float().cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+        written[name] = {"shape": list(outs[name].shape), "elements_written": int(arr.size)}
+    return written
+
+
 def timed_loop(step, steps, warmup, world, sync, dist=None, dev=None):
     """W untimed warm-up steps, then exactly K steps bracketed by barrier + device sync; max over ranks."""
     def barrier():
@@ -316,16 +342,22 @@ def run_job(args, rank, world, dev, model=None, voc=None, dist=None, sync=None, 
     del full
 
     def step(gather=True):
+        # the sampler's start noise (and DDPM's per-step draws) come from the global generator: seeded per step, every step computes the same
+        # thing, and the same arguments give the same outputs from run to run (--dump-outputs)
+        torch.manual_seed(STEP_SEED + rank)
         outs = pipe.step(*local)
         if gather:
             outs = {k: shard.gather_batch(v, rank, world, sizes=[B] * world, force=force) for k, v in outs.items()}
         return outs
 
     dt, outs = timed_loop(step, args.steps, args.warmup, world, sync, dist, dev)
+    dumped = None
     if rank == 0:
         pipe.check(outs, world * B)
         if on_output is not None:
             on_output(outs["mel"])
+        if args.dump_outputs:
+            dumped = dump_outputs(outs, args.dump_outputs)
 
     frames = world * B * T * args.steps
     value = frames / dt
@@ -340,6 +372,8 @@ def run_job(args, rank, world, dev, model=None, voc=None, dist=None, sync=None, 
     }
     if rank != 0:
         return None
+    if dumped is not None:
+        res["dumped_outputs"] = {"dir": os.path.abspath(args.dump_outputs), "arrays": dumped}
     if profiler is not None:
         # roofline leg: one extra instrumented step on rank 0 ONLY, so it must not contain a collective (gather=False)
         prof = profiler.run(lambda: step(gather=False))
@@ -610,7 +644,14 @@ def parse_args(argv=None):
     ap.add_argument("--no-profile", action="store_true", help="skip the instrumented roofline step (for rocprofv3 --pmc passes)")
     ap.add_argument("--stub-cpu", action="store_true",
                     help="tests only: gloo ranks on the CPU with stand-in models (exercises the launcher / scatter / gather / JSON plumbing without a GPU)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (mel, and wav where the workload has a vocoder) as DIR/<name>.npy, "
+                         "float32, at most 64 MiB in all (a fixed, seeded sample of larger outputs)")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
     if args.vocoder and args.workload == "sampler":
         args.workload = "e2e"
     if args.batch is None:

@@ -1,6 +1,6 @@
 """Regenerate every golden fixture from the imported reference into a temporary directory and check that the result is
 bit-identical to the committed files (every array of every .npz, every manifest).  Needs /root/reference, so it runs in
-the build container only; tests/test_fixture_recipe.py calls `verify()` and is skipped elsewhere.
+the build container only, by hand; the test suite needs nothing outside the repository and does not run it.
 
     PYTHONDONTWRITEBYTECODE=1 python tests/golden/verify_fixtures.py
 """

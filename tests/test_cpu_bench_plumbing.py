@@ -106,6 +106,58 @@ def test_bench_main_spawns_its_own_ranks(workload):
     assert abs(res["value"] - 2 * 3 * 8 * 2 / (res["ms_per_step"] * 2e-3)) < 1e-6 * res["value"]
 
 
+@pytest.mark.parametrize("workload", ["sampler", "e2e"])
+def test_bench_dump_outputs_writes_the_last_step(workload, tmp_path):
+    """--dump-outputs: the timed path's last-step results as float32 .npy files, the same from run to run, and --steps counts the timed steps"""
+    import numpy as np
+    dumps = []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        p, res = _run_bench(["--gpus", "1", "--stub-cpu", "--steps", "4", "--warmup", "2", "--batch", "3", "--frames", "8", "--workload", workload,
+                             "--dump-outputs", str(d)])
+        assert p.returncode == 0, p.stderr[-2000:]
+        assert res["steps"] == 4 and res["ms_per_step"] > 0 and abs(res["value"] - 3 * 8 * 4 / (res["ms_per_step"] * 4e-3)) < 1e-6 * res["value"]
+        names = ["mel"] if workload == "sampler" else ["mel", "wav"]
+        assert sorted(f.name for f in d.iterdir()) == [n + ".npy" for n in names]
+        assert sorted(res["dumped_outputs"]["arrays"]) == names
+        dumps.append({n: np.load(d / (n + ".npy")) for n in names})
+    from bench import build_pipeline, parse_args
+    args = parse_args(["--stub-cpu", "--batch", "3", "--frames", "8", "--workload", workload])
+    _, make_inputs, _ = build_pipeline(args, torch.device("cpu"))
+    units, spk = make_inputs(3, 8)
+    want = (2.0 * units[..., :80] + spk.to(torch.float32)[:, :, None]).numpy()
+    for got in dumps:
+        assert got["mel"].dtype == np.float32 and np.array_equal(got["mel"], want)
+        if workload == "e2e":
+            assert got["wav"].dtype == np.float32 and got["wav"].shape == (3, 1, 32)
+    for n in dumps[0]:
+        assert np.array_equal(dumps[0][n], dumps[1][n])
+
+
+def test_dump_outputs_samples_above_the_cap(tmp_path):
+    """outputs above the cap are written as a seeded sample within the cap, each array its share, the same indices every time"""
+    import numpy as np
+    from bench import dump_outputs
+    outs = {"mel": torch.arange(6000, dtype=torch.float32).reshape(3, 25, 80), "wav": -torch.arange(18000, dtype=torch.float64).reshape(3, 1, 6000)}
+    info = dump_outputs(outs, str(tmp_path / "a"), cap_bytes=4096)
+    dump_outputs(outs, str(tmp_path / "b"), cap_bytes=4096)
+    total = 0
+    for n, v in outs.items():
+        a, b = np.load(tmp_path / "a" / (n + ".npy")), np.load(tmp_path / "b" / (n + ".npy"))
+        assert a.dtype == np.float32 and np.array_equal(a, b) and info[n]["elements_written"] == a.size > 0
+        assert info[n]["shape"] == list(v.shape)
+        assert np.isin(a, v.reshape(-1).float().numpy()).all() and (np.diff(np.abs(a)) > 0).all()      # distinct elements, in index order
+        total += a.nbytes
+    assert total <= 4096
+    small = dump_outputs({"mel": outs["mel"]}, str(tmp_path / "c"))
+    assert small["mel"]["elements_written"] == 6000 and np.array_equal(np.load(tmp_path / "c" / "mel.npy"), outs["mel"].numpy())
+
+
+def test_bench_refuses_zero_steps():
+    p, res = _run_bench(["--gpus", "1", "--stub-cpu", "--steps", "0", "--batch", "2", "--frames", "8"])
+    assert p.returncode != 0 and res is None and "--steps must be at least 1" in p.stderr
+
+
 def test_bench_main_refuses_a_world_size_mismatch():
     """a launcher that provides fewer ranks than --gpus asks for must fail loudly, not measure one GPU and label it N"""
     p, res = _run_bench(["--gpus", "2", "--stub-cpu", "--steps", "1", "--warmup", "0", "--batch", "2", "--frames", "8"],
