@@ -109,6 +109,12 @@ int lds_debug_set_touch_weights(int on);
  * (reference models.py:186-192, 250-259); x, acc, out dev [B][C][T], weights host [C][C][K]; lengths host int32 [B] or null */
 int lds_test_voc_pair(const float* x, const float* w1, const float* b1, const float* w2, const float* b2, int C, int T, int K, int dil,
                       const float* acc, float div, const int32_t* lengths, float* out, int B, void* stream);
+/* the VAE encoder's convolution alone (csrc/conv_down.hip; reference models.py:24-29,39-54 Conv1d with stride): x dev [B][Ci][T], w host
+ * [Co][Ci][K], b host [Co] or NULL, out dev [B][Co][To]; pad = (K - stride + 1) / 2, To = (T + 2 pad - K) / stride + 1; LeakyReLU(slope) on
+ * the input (slope 1 = none); T a multiple of stride.  tile: 0 = the product path's choice (workgroups against the device's CU count), else
+ * BM*1000+BN in {64064, 64128, 128128}; cfg_out (or NULL) receives the configuration that ran ("BM128 BN128 grid ...").  Synchronises. */
+int lds_test_conv_down(const float* x, const float* w, const float* b, int Ci, int Co, int K, int stride, int T, int B, float slope,
+                       int tile, float* out, char* cfg_out, size_t cfg_cap, void* stream);
 int lds_debug_set_split_rule(int rule);
 /* plain [B,C,T] -> K8B3 -> plain: must return the input bit for bit (the three-term split is lossless) */
 int lds_test_k8b3_roundtrip(const float* x, float* out, int B, int C, int T, void* stream);

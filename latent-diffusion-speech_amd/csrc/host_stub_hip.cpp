@@ -43,6 +43,7 @@ hipError_t hipGetDevice(int* d) {
     return hipSuccess;
 }
 hipError_t hipGetLastError(void) { return hipSuccess; }
+hipError_t hipDeviceGetAttribute(int*, hipDeviceAttribute_t, int) { return hipErrorNotSupported; }
 const char* hipGetErrorString(hipError_t) { return "host stub"; }
 hipError_t hipFuncSetAttribute(const void*, hipFuncAttribute, int) { return hipSuccess; }
 hipError_t hipLaunchKernel(const void*, dim3, dim3, void**, size_t, hipStream_t) { return hipErrorNotSupported; }

@@ -58,6 +58,20 @@ bool conv_mono_applies(const ConvArgs& a);      // one output channel, k 7: the 
 hipError_t launch_conv_mono(const ConvArgs& a, hipStream_t s);
 const char* conv_small_last_config();
 
+// conv_down (conv_down.hip): the VAE encoder's convolutions over plain tensors, x [B][Ci][L] -> out [B][Co][To] with
+// out[b,co,t] = bias[co] + sum_{ci,k} w[co][ci][k] * lrelu_slope(x[b,ci, t*stride - pad + k]) (taps outside [0, L) read zeros;
+// slope 1 = no activation); w is the unpacked device weight [Co][Ci][K].  v_mfma_f32_32x32x2_f32, exact fp32.
+struct ConvDownArgs {
+    const float* x; const float* w; const float* bias; float* out;
+    int Ci, Co, K, stride, pad, L, To, B;
+    float slope;
+    int tile;      // 0 = auto (by workgroup count against the CU count), else BM*1000+BN in {64064, 64128, 128128}
+};
+hipError_t launch_conv_down(const ConvDownArgs& a, hipStream_t s);
+const char* conv_down_last_config();
+// y [B][2C][T] (conv_post) -> out [B][T][2C] = (m, only_mean ? 0 : logs); z [B][T][C] = m + noise * exp(logs) when z (needs noise [B][C][T])
+hipError_t launch_vae_head(const float* y, const float* noise, float* out, float* z, int B, int C, int T, int only_mean, hipStream_t s);
+
 // voc_pair (voc_pair.hip): one residual step of the vocoder's ResBlock1 at 16 / 32 channels as one launch over plain [B][C][T] tensors:
 // out = (accum ? out : 0) + c2(lrelu(c1(lrelu(x)))) + x, divided by out_div; c1 dilated by `dil`, both k = KT, "same" zero padding;
 // frames at and beyond vlen[b] (device int32 [B], null = T) are outside the utterance: the intermediate reads as zero there and the

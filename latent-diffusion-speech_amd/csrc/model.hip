@@ -1733,12 +1733,16 @@ extern "C" int lds_axpby(float* out, const float* a, const float* b, float c0, f
 // Vocoder
 // ================================================================================================
 struct VocRes { std::vector<ConvW> c1, c2; int k = 3; std::vector<int> dil; };
-struct lds_vocoder {
+// What the generator (lds_vocoder) and the encoder (lds_vae_encoder) share: the config and the MRF weight sets, stage s owning
+// rbs[s * n_kernels + j] (the reference's resblocks order in both directions)
+struct VocNet {
     lds_vocoder_cfg cfg;
     Owner own;
+    std::vector<VocRes> rbs;
+};
+struct lds_vocoder : VocNet {
     ConvW pre, post;
     std::vector<ConvW> ups;
-    std::vector<VocRes> rbs;
 };
 
 // fold weight norm: w = g * v / ||v|| (norm over all dims but 0), reference hifi_vaegan.py:61
@@ -1760,6 +1764,38 @@ static bool get_folded(Tensors& T, const std::string& p, int64_t d0, int64_t res
         for (int64_t j = 0; j < rest; ++j) out[i * rest + j] = v[i * rest + j] * sc;
     }
     return true;
+}
+
+// The MRF weight sets of one stage (reference models.py:161-222): n_kernels resblocks at `ch` channels, appended to net.rbs
+static bool load_mrf_stage(Tensors& T, VocNet& net, int stage, int ch) {
+    const lds_vocoder_cfg* cfg = &net.cfg;
+    Owner& o = net.own;
+    std::vector<float> w;
+    bool ok = true;
+    for (int j = 0; j < cfg->n_kernels && ok; ++j) {
+        VocRes rb;
+        rb.k = cfg->resblock_kernel_sizes[j];
+        if (rb.k != 3 && rb.k != 7 && rb.k != 11) { T.missing = "resblock kernel size must be 3, 7 or 11"; return false; }
+        const std::string rp = "resblocks." + std::to_string(stage * cfg->n_kernels + j) + ".";
+        for (int m = 0; m < cfg->n_dil && ok; ++m) {
+            rb.dil.push_back(cfg->resblock_dilation_sizes[j][m]);
+            if (rb.dil.back() < 1 || rb.dil.back() > 5) { T.missing = "dilation must be 1..5"; return false; }
+            ConvW a, b;
+            if (cfg->resblock == 1) {
+                const std::string p1 = rp + "convs1." + std::to_string(m) + ".", p2 = rp + "convs2." + std::to_string(m) + ".";
+                ok = get_folded(T, p1, ch, (int64_t)ch * rb.k, w) && pack_conv(o, w.data(), T.get(p1 + "bias", ch), ch, ch, rb.k, a);
+                ok = ok && get_folded(T, p2, ch, (int64_t)ch * rb.k, w) && pack_conv(o, w.data(), T.get(p2 + "bias", ch), ch, ch, rb.k, b);
+                rb.c1.push_back(a);
+                rb.c2.push_back(b);
+            } else {
+                const std::string p1 = rp + "convs." + std::to_string(m) + ".";
+                ok = get_folded(T, p1, ch, (int64_t)ch * rb.k, w) && pack_conv(o, w.data(), T.get(p1 + "bias", ch), ch, ch, rb.k, a);
+                rb.c1.push_back(a);
+            }
+        }
+        net.rbs.push_back(rb);
+    }
+    return ok;
 }
 
 extern "C" int lds_vocoder_create(const lds_vocoder_cfg* cfg, int n, const char* const* names, const float* const* ptrs,
@@ -1786,29 +1822,7 @@ extern "C" int lds_vocoder_create(const lds_vocoder_cfg* cfg, int n, const char*
         ok = get_folded(T, p, cin, (int64_t)cout * k, w) && pack_convT(o, w.data(), T.get(p + "bias", cout), cin, cout, k, s, cw);
         v->ups.push_back(cw);
         ch = cout;
-        for (int j = 0; j < cfg->n_kernels && ok; ++j) {
-            VocRes rb;
-            rb.k = cfg->resblock_kernel_sizes[j];
-            if (rb.k != 3 && rb.k != 7 && rb.k != 11) { ok = false; T.missing = "resblock kernel size must be 3, 7 or 11"; break; }
-            const std::string rp = "resblocks." + std::to_string(i * cfg->n_kernels + j) + ".";
-            for (int m = 0; m < cfg->n_dil && ok; ++m) {
-                rb.dil.push_back(cfg->resblock_dilation_sizes[j][m]);
-                if (rb.dil.back() < 1 || rb.dil.back() > 5) { ok = false; T.missing = "dilation must be 1..5"; break; }
-                ConvW a, b;
-                if (cfg->resblock == 1) {
-                    const std::string p1 = rp + "convs1." + std::to_string(m) + ".", p2 = rp + "convs2." + std::to_string(m) + ".";
-                    ok = get_folded(T, p1, ch, (int64_t)ch * rb.k, w) && pack_conv(o, w.data(), T.get(p1 + "bias", ch), ch, ch, rb.k, a);
-                    ok = ok && get_folded(T, p2, ch, (int64_t)ch * rb.k, w) && pack_conv(o, w.data(), T.get(p2 + "bias", ch), ch, ch, rb.k, b);
-                    rb.c1.push_back(a);
-                    rb.c2.push_back(b);
-                } else {
-                    const std::string p1 = rp + "convs." + std::to_string(m) + ".";
-                    ok = get_folded(T, p1, ch, (int64_t)ch * rb.k, w) && pack_conv(o, w.data(), T.get(p1 + "bias", ch), ch, ch, rb.k, a);
-                    rb.c1.push_back(a);
-                }
-            }
-            v->rbs.push_back(rb);
-        }
+        ok = ok && load_mrf_stage(T, *v, i, ch);
     }
     ok = ok && get_folded(T, "conv_post.", 1, (int64_t)ch * 7, w) && pack_conv(o, w.data(), T.get("conv_post.bias", 1), 1, ch, 7, v->post);
     if (!ok) {
@@ -1828,7 +1842,7 @@ extern "C" void lds_vocoder_destroy(lds_vocoder* v) { delete v; }
 // tail) and their upsamplers stay on the register-staged conv_gemm / conv_small over plain tensors.
 constexpr int kVocPad = 32;
 struct VocWs { float *x, *xs, *ta, *ra, *rb; float *kx_raw, *kx_act, *kt_act, *ka_raw, *ka_act, *kb_raw, *kb_act, *ks, *kin; int* vlens; };
-static bool voc_dma_stage(const lds_vocoder* v, int ch) {
+static bool voc_dma_stage(const VocNet* v, int ch) {
     if (ch % 64) return false;
     for (const VocRes& rb : v->rbs)
         for (int d : rb.dil)
@@ -1869,7 +1883,7 @@ extern "C" int lds_vocoder_workspace_bytes(const lds_vocoder* v, int B, int T, s
 // MRF of one stage on the K4P / LDS-DMA path (reference models.py:161-222,250-259): x plain [B][ch][Tl] (null: the upsampler has
 // already written kx_raw / kx_act) -> mean_j resblock_j(x), to xs plain, or (xs null) as LeakyReLU(0.1)(.) to the K4P tensor kin,
 // the next upsampler's input
-static int voc_mrf_dma(const lds_vocoder* v, const VocWs& w, int stage, const float* x, float* xs, int ch, int Tl, int B, hipStream_t st, const int* vlen = nullptr) {
+static int voc_mrf_dma(const VocNet* v, const VocWs& w, int stage, const float* x, float* xs, int ch, int Tl, int B, hipStream_t st, const int* vlen = nullptr) {
     const lds_vocoder_cfg& c = v->cfg;
     const int P = kVocPad;
     if (x) HIP_TRY(launch_to_k4p_act(x, w.kx_raw, w.kx_act, 0.1f, B, ch, Tl, P, st, vlen));
@@ -1945,6 +1959,43 @@ static int run_voc_pair(const ConvW& W1, const ConvW& W2, const float* x, float*
 }
 static bool voc_pair_ok(const lds_vocoder_cfg& c, const VocRes& rb, int m, int ch) {
     return c.resblock == 1 && g_voc_pair.load(std::memory_order_relaxed) && voc_pair_applies(ch, rb.k, rb.dil[m]) && rb.c1[m].Mp == 32 && rb.c2[m].Mp == 32;
+}
+
+// MRF of one narrow stage on the register-staged kernels over plain tensors (voc_pair / conv_small / conv_gemm): x [B][ch][Tl] ->
+// xs = mean_j resblock_j(x), through the scratch tensors w.ra / w.rb / w.ta
+static int voc_mrf_plain(const VocNet* v, const VocWs& w, int stage, const float* x, float* xs, int ch, int Tl, int B, hipStream_t st,
+                         const int* vlen) {
+    const lds_vocoder_cfg& c = v->cfg;
+    for (int j = 0; j < c.n_kernels; ++j) {
+        const VocRes& rb = v->rbs[stage * c.n_kernels + j];
+        const float* cur = x;
+        float* pp[2] = {w.ra, w.rb};
+        const int nd = (int)rb.dil.size();
+        for (int m = 0; m < nd; ++m) {
+            const bool last = m == nd - 1;
+            const int d = rb.dil[m];
+            Src s1{cur, ch, nullptr, 0, Tl};
+            ConvOpt o1;
+            o1.dil = d; o1.pad = (rb.k * d - d) / 2; o1.act_in = ACT_LRELU; o1.slope = 0.1f; o1.vlen = vlen;
+            ConvOpt o2;
+            o2.res = cur; o2.vlen = vlen;
+            if (last) { o2.accum = j > 0; o2.out_div = (j == c.n_kernels - 1) ? (float)c.n_kernels : 1.0f; }
+            float* dst = last ? xs : pp[m & 1];
+            if (voc_pair_ok(c, rb, m, ch)) {
+                LDS_TRY(run_voc_pair(rb.c1[m], rb.c2[m], cur, dst, ch, Tl, d, o2.accum != 0, o2.out_div, vlen, B, st));
+            } else if (c.resblock == 1) {
+                LDS_TRY(run_conv(rb.c1[m], s1, o1, w.ta, B, st));
+                Src s2{w.ta, ch, nullptr, 0, Tl};
+                o2.pad = (rb.k - 1) / 2; o2.act_in = ACT_LRELU; o2.slope = 0.1f;
+                LDS_TRY(run_conv(rb.c2[m], s2, o2, dst, B, st));
+            } else {
+                o2.dil = d; o2.pad = o1.pad; o2.act_in = ACT_LRELU; o2.slope = 0.1f;
+                LDS_TRY(run_conv(rb.c1[m], s1, o2, dst, B, st));
+            }
+            cur = dst;
+        }
+    }
+    return LDS_OK;
 }
 
 static int vocoder_forward_impl(lds_vocoder* v, const float* z, float* wav, void* ws, size_t ws_bytes, int B, int T, void* stream, const int* lens_host);
@@ -2033,41 +2084,175 @@ static int vocoder_forward_impl(lds_vocoder* v, const float* z, float* wav, void
             { float* t = x; x = xs; xs = t; }
             continue;
         }
-        for (int j = 0; j < c.n_kernels; ++j) {
-            const VocRes& rb = v->rbs[i * c.n_kernels + j];
-            const float* cur = x;
-            float* pp[2] = {w.ra, w.rb};
-            const int nd = (int)rb.dil.size();
-            for (int m = 0; m < nd; ++m) {
-                const bool last = m == nd - 1;
-                const int d = rb.dil[m];
-                Src s1{cur, ch, nullptr, 0, Tl};
-                ConvOpt o1;
-                o1.dil = d; o1.pad = (rb.k * d - d) / 2; o1.act_in = ACT_LRELU; o1.slope = 0.1f; o1.vlen = vl[i + 1];
-                ConvOpt o2;
-                o2.res = cur; o2.vlen = vl[i + 1];
-                if (last) { o2.accum = j > 0; o2.out_div = (j == c.n_kernels - 1) ? (float)c.n_kernels : 1.0f; }
-                float* dst = last ? xs : pp[m & 1];
-                if (voc_pair_ok(c, rb, m, ch)) {
-                    LDS_TRY(run_voc_pair(rb.c1[m], rb.c2[m], cur, dst, ch, Tl, d, o2.accum != 0, o2.out_div, vl[i + 1], B, st));
-                } else if (c.resblock == 1) {
-                    LDS_TRY(run_conv(rb.c1[m], s1, o1, w.ta, B, st));
-                    Src s2{w.ta, ch, nullptr, 0, Tl};
-                    o2.pad = (rb.k - 1) / 2; o2.act_in = ACT_LRELU; o2.slope = 0.1f;
-                    LDS_TRY(run_conv(rb.c2[m], s2, o2, dst, B, st));
-                } else {
-                    o2.dil = d; o2.pad = o1.pad; o2.act_in = ACT_LRELU; o2.slope = 0.1f;
-                    LDS_TRY(run_conv(rb.c1[m], s1, o2, dst, B, st));
-                }
-                cur = dst;
-            }
-        }
+        LDS_TRY(voc_mrf_plain(v, w, i, x, xs, ch, Tl, B, st, vl[i + 1]));
         { float* t = x; x = xs; xs = t; }
     }
     Src s{x, ch, nullptr, 0, Tl};
     ConvOpt o;
     o.pad = 3; o.act_in = ACT_LRELU; o.slope = 0.01f; o.epi = EPI_TANH; o.vlen = vl[c.n_ups];
     return run_conv(v->post, s, o, wav, B, st);
+}
+
+// ================================================================================================
+// VAE encoder (audio -> latent): the generator run backwards (reference models.py:14-67, hifi_vaegan.py:32-50)
+// ================================================================================================
+// conv_pre, the downsamplers and conv_post keep the reference's unpacked [Co][Ci][K] weights: conv_down (conv_down.hip) reads them as
+// the A operand of its implicit GEMM as they are
+struct DownW { float* w = nullptr; float* bias = nullptr; int Co = 0, Ci = 0, K = 0, stride = 1, pad = 0; };
+struct lds_vae_encoder : VocNet {
+    DownW pre, post;
+    std::vector<DownW> downs;      // downs[i]: stage i, stride rates[n_ups - 1 - i]
+    int hop = 1;
+};
+
+static bool load_down(Tensors& T, Owner& o, const std::string& p, int Co, int Ci, int K, int stride, int pad, DownW& d) {
+    std::vector<float> w;
+    if (!get_folded(T, p, Co, (int64_t)Ci * K, w)) return false;      // Conv1d weight norm: over dims 1, 2 of [Co][Ci][K]
+    const float* b = T.get(p + "bias", Co);
+    if (!b) return false;
+    d.w = o.upload(w);
+    d.bias = o.upload(std::vector<float>(b, b + Co));
+    d.Co = Co; d.Ci = Ci; d.K = K; d.stride = stride; d.pad = pad;
+    return d.w && d.bias;
+}
+
+// the geometry the downsamplers support: k = 2u, u a power of two in 2 .. 16 (padding (k - u + 1) / 2 = u / 2, L -> L / u)
+static bool down_geometry_ok(int u, int k) { return u >= 2 && u <= 16 && (u & (u - 1)) == 0 && k == 2 * u; }
+
+extern "C" int lds_vae_encoder_create(const lds_vocoder_cfg* cfg, int n, const char* const* names, const float* const* ptrs,
+                                      const int64_t* numel, lds_vae_encoder** out) {
+    if (!cfg || !names || !ptrs || !numel || !out || n < 0) return fail(LDS_EINVAL, "null argument");
+    if (cfg->n_ups < 1 || cfg->n_ups > 8 || cfg->n_kernels < 1 || cfg->n_kernels > 4 || cfg->n_dil < 1 || cfg->n_dil > 4 || cfg->inter_channels < 1 ||
+        cfg->upsample_initial_channel < 1)
+        return fail(LDS_EINVAL, "encoder config out of range");
+    const int nu = cfg->n_ups, c0 = cfg->upsample_initial_channel;
+    if ((c0 >> nu) < 1 || (c0 >> nu) << nu != c0) return fail(LDS_EINVAL, "encoder: upsample_initial_channel must be divisible by 2^n_ups");
+    int hop = 1;
+    for (int i = 0; i < nu; ++i) {
+        const int u = cfg->upsample_rates[nu - 1 - i], k = cfg->upsample_kernel_sizes[nu - 1 - i], cout = c0 >> (nu - 1 - i);
+        if (!down_geometry_ok(u, k)) return fail(LDS_EINVAL, "encoder: unsupported downsample geometry (stride %d, kernel %d; needs k = 2u, u a power of two <= 16)", u, k);
+        if (cout < 16 || cout % 16) return fail(LDS_EINVAL, "encoder: unsupported stage width %d (a multiple of 16 is needed)", cout);
+        hop *= u;
+    }
+    Tensors T;
+    for (int i = 0; i < n; ++i) T.m[names[i]] = {ptrs[i], numel[i]};
+    lds_vae_encoder* e = new lds_vae_encoder();
+    e->cfg = *cfg;
+    e->hop = hop;
+    bool ok = load_down(T, e->own, "conv_pre.", c0 >> nu, 1, 7, 1, 3, e->pre);
+    for (int i = 0; i < nu && ok; ++i) {
+        const int u = cfg->upsample_rates[nu - 1 - i], k = cfg->upsample_kernel_sizes[nu - 1 - i];
+        const int cin = c0 >> (nu - i), cout = c0 >> (nu - 1 - i);
+        DownW d;
+        ok = load_down(T, e->own, "ups." + std::to_string(i) + ".", cout, cin, k, u, (k - u + 1) / 2, d);
+        e->downs.push_back(d);
+        ok = ok && load_mrf_stage(T, *e, i, cout);
+    }
+    ok = ok && load_down(T, e->own, "conv_post.", 2 * cfg->inter_channels, c0, 7, 1, 3, e->post);
+    if (!ok) {
+        std::string miss = T.missing;
+        delete e;
+        if (!miss.empty()) return fail(LDS_EMISSING, "encoder: %s", miss.c_str());
+        return fail(LDS_ENOMEM, "encoder weight upload failed");
+    }
+    *out = e;
+    return LDS_OK;
+}
+extern "C" void lds_vae_encoder_destroy(lds_vae_encoder* e) { delete e; }
+
+struct EncWs { VocWs v; float* y; };
+static bool enc_args_ok(const lds_vae_encoder* e, int B, int64_t L) {
+    return e && B > 0 && B <= 65535 && L > 0 && L % e->hop == 0 && L <= (int64_t)1 << 30;
+}
+// Stage tensors ping-pong through v.x / v.xs ([B][16][L] after conv_pre is the widest: every stage halves the width at least as often
+// as it doubles the channels); y = conv_post's [B][2C][T].  The plain MRF stages' scratch (ta, ra, rb) and the DMA-fed stages' K4P
+// tensors (sized as in plan_voc) share one region: every stage writes the scratch it reads before reading it, and the stages run one
+// after the other on the stream, so a narrow stage and a DMA stage never hold it at the same time.
+static void plan_enc(const lds_vae_encoder* e, Arena& A, int B, int64_t L, EncWs& w) {
+    size_t mx = (size_t)e->pre.Co * L, mk = 0, mp = 0;
+    int64_t Tl = L;
+    for (const DownW& d : e->downs) {
+        Tl /= d.stride;
+        mx = std::max(mx, (size_t)d.Co * Tl);
+        if (voc_dma_stage(e, d.Co)) mk = std::max(mk, (size_t)d.Co * (Tl + 2 * kVocPad));
+        else mp = std::max(mp, (size_t)d.Co * Tl);
+    }
+    VocWs& v = w.v;
+    v.x = A.f(B * mx); v.xs = A.f(B * mx);
+    auto rnd = [](size_t n) { return (n * sizeof(float) + 255) / 256 * 256 / sizeof(float); };      // Arena's slot rounding
+    const size_t plain = mp ? rnd(B * mp) : 0, k4 = mk ? rnd(B * mk + 4096) : 0;
+    float* shared = A.f(std::max(3 * plain, 8 * k4));
+    v.ta = v.ra = v.rb = nullptr;      // (planning without a buffer: every pointer stays null)
+    if (mp && shared) { v.ta = shared; v.ra = shared + plain; v.rb = shared + 2 * plain; }
+    float** kb[8] = {&v.kx_raw, &v.kx_act, &v.kt_act, &v.ka_raw, &v.ka_act, &v.kb_raw, &v.kb_act, &v.ks};
+    for (int i = 0; i < 8; ++i) *kb[i] = (mk && shared) ? shared + i * k4 : nullptr;
+    v.kin = nullptr;      // (the encoder's MRF stages always return a plain tensor)
+    v.vlens = nullptr;
+    w.y = A.f((size_t)B * e->post.Co * (L / e->hop));
+}
+extern "C" int lds_vae_encoder_workspace_bytes(const lds_vae_encoder* e, int B, int64_t L, size_t* out) {
+    if (!out || !enc_args_ok(e, B, L)) return fail(LDS_EINVAL, "bad argument (B %d, L %lld: B >= 1 and L a positive multiple of the hop)", B, (long long)L);
+    Arena A(nullptr, 0);
+    EncWs w;
+    plan_enc(e, A, B, L, w);
+    *out = A.used;
+    return LDS_OK;
+}
+
+static int run_down(const DownW& d, const float* x, int64_t L, float slope, float* out, int B, hipStream_t st, int tile = 0) {
+    ConvDownArgs a;
+    memset(&a, 0, sizeof(a));
+    a.x = x; a.w = d.w; a.bias = d.bias; a.out = out;
+    a.Ci = d.Ci; a.Co = d.Co; a.K = d.K; a.stride = d.stride; a.pad = d.pad; a.L = (int)L; a.B = B; a.slope = slope; a.tile = tile;
+    a.To = (int)((L + 2 * d.pad - d.K) / d.stride + 1);
+    const double flops = 2.0 * B * (double)a.To * d.Co * (double)d.Ci * d.K;
+    const double bytes = 4.0 * ((double)B * d.Ci * L + (double)d.Co * d.Ci * d.K + (double)B * d.Co * a.To);
+    hipError_t e;
+    {
+        ProfScope ps(st, "conv_down", flops, bytes);
+        e = launch_conv_down(a, st);
+        if (ps.on) {
+            std::string cfgs(conv_down_last_config());
+            std::string nm = "conv_down<" + cfgs.substr(0, cfgs.find(" grid")) + ">";
+            if (g_prof_level.load(std::memory_order_relaxed) >= 2) {
+                char sh[96];
+                snprintf(sh, sizeof(sh), " Ci%d Co%d K%d s%d To%d", d.Ci, d.Co, d.K, d.stride, a.To);
+                nm += sh;
+            }
+            ps.rename(nm);
+        }
+    }
+    if (e != hipSuccess)
+        return fail(LDS_EHIP, "conv_down launch failed (%s): Co %d Ci %d K %d stride %d L %lld", hipGetErrorString(e), d.Co, d.Ci, d.K, d.stride, (long long)L);
+    return LDS_OK;
+}
+
+extern "C" int lds_vae_encoder_forward(lds_vae_encoder* e, const float* audio, const float* noise, float* out, float* z, int only_mean, void* ws,
+                                       size_t ws_bytes, int B, int64_t L, void* stream) {
+    if (!audio || !out || !ws || (z && !noise) || !enc_args_ok(e, B, L)) return fail(LDS_EINVAL, "bad argument");
+    hipStream_t st = (hipStream_t)stream;
+    ProfChain chain;
+    Arena A(ws, ws_bytes);
+    EncWs w;
+    plan_enc(e, A, B, L, w);
+    if (!A.ok) return fail(LDS_ENOMEM, "encoder workspace too small: need %zu", A.used);
+    // reference models.py:39-54
+    LDS_TRY(run_down(e->pre, audio, L, 1.0f, w.v.x, B, st));
+    float* x = w.v.x;
+    float* xs = w.v.xs;
+    int64_t Tl = L;
+    for (size_t i = 0; i < e->downs.size(); ++i) {
+        const DownW& d = e->downs[i];
+        LDS_TRY(run_down(d, x, Tl, 0.1f, xs, B, st));      // x = ups[i](leaky_relu(x, 0.1))
+        { float* t = x; x = xs; xs = t; }
+        Tl /= d.stride;
+        if (voc_dma_stage(e, d.Co)) LDS_TRY(voc_mrf_dma(e, w.v, (int)i, x, xs, d.Co, (int)Tl, B, st));
+        else LDS_TRY(voc_mrf_plain(e, w.v, (int)i, x, xs, d.Co, (int)Tl, B, st, nullptr));
+        { float* t = x; x = xs; xs = t; }
+    }
+    LDS_TRY(run_down(e->post, x, Tl, 0.01f, w.y, B, st));      // conv_post(leaky_relu(x)) -> [B][2C][T]
+    HIP_TRY(launch_vae_head(w.y, noise, out, z, B, e->cfg.inter_channels, (int)Tl, only_mean, st));
+    return LDS_OK;
 }
 
 // ================================================================================================
@@ -2634,6 +2819,24 @@ extern "C" int lds_test_voc_pair(const float* x, const float* w1, const float* b
     }
     if (acc) HIP_TRY(hipMemcpyAsync(out, acc, sizeof(float) * (size_t)B * C * T, hipMemcpyDeviceToDevice, st));
     LDS_TRY(run_voc_pair(W1, W2, x, out, C, T, dil, acc != nullptr, div, vl, B, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return LDS_OK;
+}
+// The encoder's convolution alone: x dev [B][Ci][T], w host [Co][Ci][K], b host [Co] or null; out dev [B][Co][To], To = (T + 2 pad - K) / stride + 1
+// with pad = (K - stride + 1) / 2 (the reference's downsampler padding; 3 for k 7, stride 1), LeakyReLU(slope) on the input (1 = none);
+// tile 0 = the product path's choice, else forced (kernels.h ConvDownArgs::tile); cfg_out (or null) = the configuration that ran
+extern "C" int lds_test_conv_down(const float* x, const float* w, const float* b, int Ci, int Co, int K, int stride, int T, int B, float slope,
+                                  int tile, float* out, char* cfg_out, size_t cfg_cap, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    if (!x || !w || !out || Ci < 1 || Co < 1 || K < stride || stride < 1 || T < 1 || B < 1 || B > 65535 || T % stride) return fail(LDS_EINVAL, "bad argument");
+    Owner own;
+    DownW d;
+    d.w = own.upload(std::vector<float>(w, w + (size_t)Co * Ci * K));
+    if (b) d.bias = own.upload(std::vector<float>(b, b + Co));
+    if (!d.w || (b && !d.bias)) return fail(LDS_ENOMEM, "upload failed");
+    d.Co = Co; d.Ci = Ci; d.K = K; d.stride = stride; d.pad = (K - stride + 1) / 2;
+    LDS_TRY(run_down(d, x, T, slope, out, B, st, tile));
+    if (cfg_out && cfg_cap) snprintf(cfg_out, cfg_cap, "%s", conv_down_last_config());
     HIP_TRY(hipStreamSynchronize(st));
     return LDS_OK;
 }

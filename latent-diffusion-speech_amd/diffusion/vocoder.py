@@ -1,6 +1,6 @@
-"""`Vocoder` wrapper with the reference's constructor, attributes and `infer` (reference
-diffusion/vocoder.py:5-33).  `extract` (audio -> latent, the VAE encoder + torchaudio resampler)
-is preprocessing and out of scope."""
+"""`Vocoder` wrapper with the reference's constructor, attributes, `extract` and `infer` (reference
+diffusion/vocoder.py:5-33).  `extract` runs the VAE encoder; the torchaudio resampler in front of it is
+not built (see Vocoder.extract)."""
 import torch
 
 from encoder.hifi_vaegan.hifi_vaegan import Hifi_VAEGAN
@@ -22,7 +22,18 @@ class Vocoder:
         self.dimension = self.vocoder.dimension()
 
     def extract(self, audio, sample_rate, keyshift=0, **kwargs):
-        raise NotImplementedError("Vocoder.extract (audio -> latent encoder) is preprocessing, outside the sampler hot path")
+        """audio [B,L] at `sample_rate` -> latent [B,T,2C] (or z [B,T,C] with only_z=True); kwargs (only_z, only_mean) go to
+        Hifi_VAEGAN.extract (reference diffusion/vocoder.py:24-31).  Two deviations from the reference:
+          - resampling is not built: sample_rate must equal the vocoder's rate (ValueError naming both otherwise), where the
+            reference resamples with torchaudio;
+          - keyshift must be 0 (ValueError otherwise): the reference passes keyshift= to Hifi_VAEGAN.extract, which has no such
+            parameter, so its extract raises TypeError for every call; the latent of unshifted audio is what it means."""
+        if keyshift != 0:
+            raise ValueError(f"Vocoder.extract: keyshift must be 0 (got {keyshift}); the encoder takes no key shift")
+        if sample_rate != self.vocoder_sample_rate:
+            raise ValueError(f"Vocoder.extract: audio at {sample_rate} Hz, the vocoder runs at {self.vocoder_sample_rate} Hz; "
+                             "resampling is not built, resample the audio first")
+        return self.vocoder.extract(audio, **kwargs)
 
     def infer(self, mel):
         return self.vocoder(mel)

@@ -1,6 +1,7 @@
-"""`Hifi_VAEGAN` decoder wrapper (reference encoder/hifi_vaegan/hifi_vaegan.py:10-65): reads
+"""`Hifi_VAEGAN` wrapper (reference encoder/hifi_vaegan/hifi_vaegan.py:10-65): reads
 `<model_path>/decoder.pth` = {'config': h, 'model': state_dict with weight-norm pairs}, lazily
-builds the native Generator on first call and maps z [B,T,C] -> wav [B,1,T*hop]."""
+builds the native Generator on first call and maps z [B,T,C] -> wav [B,1,T*hop]; `extract` lazily
+builds the native encoder from `<model_path>/encoder.pth` (same layout) and maps audio [B,L] -> [B,T,2C]."""
 import os
 
 import torch
@@ -14,9 +15,10 @@ def load_config(model_path):
 
 
 class Hifi_VAEGAN(torch.nn.Module):
-    def __init__(self, model_path, device=None, h=None, state=None):
+    def __init__(self, model_path, device=None, h=None, state=None, *, encoder_state=None):
         """`h`/`state` (optional, not in the reference) inject a config + Generator state_dict directly,
-        for synthetic-weight runs where no decoder.pth exists."""
+        for synthetic-weight runs where no decoder.pth exists; `encoder_state` likewise an Encoder state_dict
+        (no encoder.pth)."""
         super().__init__()
         if device is None:
             device = "cuda" if torch.cuda.is_available() else "cpu"
@@ -25,6 +27,7 @@ class Hifi_VAEGAN(torch.nn.Module):
         self.encoder_model = None
         self.decoder_model = None
         self._state = state
+        self._encoder_state = encoder_state
         self.h = h if h is not None else load_config(model_path)
 
     def sample_rate(self):
@@ -36,8 +39,31 @@ class Hifi_VAEGAN(torch.nn.Module):
     def dimension(self):
         return self.h["inter_channels"]
 
-    def extract(self, audio, only_z=False, only_mean=False):
-        raise NotImplementedError("the VAE encoder is preprocessing, outside the sampler hot path")
+    @torch.no_grad()
+    def extract(self, audio, only_z=False, only_mean=False, *, noise=None):
+        """audio [B,L] -> cat(m, logs) as [B,T,2C] (logs zeroed under only_mean), or z = m + randn * exp(logs) as [B,T,C] under only_z
+        (reference hifi_vaegan.py:32-50).  L is right-padded with zeros to a multiple of the hop.  The reference draws randn_like(m)
+        inside every encoder call; so does this one (torch.randn of [B,C,T] on the device), so the torch generator advances the same.
+        `noise` (not in the reference): a [B,C,T] tensor used instead of that draw (nothing is drawn then)."""
+        if not audio.is_cuda:
+            raise RuntimeError("Hifi_VAEGAN.extract needs tensors on a HIP device (no CPU fallback)")
+        if self.encoder_model is None:
+            state = self._encoder_state
+            if state is None:
+                print("| Load Vaegan Encoder: ", self.model_path)
+                state = torch.load(os.path.join(self.model_path, "encoder.pth"), map_location="cpu", weights_only=False)["model"]
+            self.encoder_model = native.VaeEncoder(self.h, state)     # folds weight norm like remove_weight_norm()
+            self._encoder_state = None
+        audio = audio.float()
+        hop = self.hop_size()
+        if audio.shape[-1] % hop != 0:      # PAD
+            audio = torch.nn.functional.pad(audio, (0, hop - audio.shape[-1] % hop))
+        audio = audio.contiguous()
+        B, T = audio.shape[0], audio.shape[-1] // hop
+        if noise is None:
+            noise = torch.randn(B, self.dimension(), T, dtype=torch.float32, device=audio.device)      # randn_like(m)
+        out, z = self.encoder_model.forward(audio, noise.float().contiguous() if only_z else None, only_mean=only_mean)
+        return z if only_z else out
 
     @torch.no_grad()
     def forward_ragged(self, z, lengths):

@@ -215,6 +215,39 @@ def generator_param_shapes(h):
     return d
 
 
+def encoder_param_shapes(h):
+    """``Encoder.state_dict()`` before remove_weight_norm (reference encoder/hifi_vaegan/modules/models.py:14-37): the
+    generator's stages in reverse, with Conv1d downsamplers ([Cout][Cin][k], so weight_g is per output channel)."""
+    d = OrderedDict()
+
+    def wn(p, wshape, nbias):
+        d[p + "bias"] = (nbias,)
+        d[p + "weight_g"] = (wshape[0], 1, 1)
+        d[p + "weight_v"] = tuple(wshape)
+
+    c0, n = h["upsample_initial_channel"], len(h["upsample_rates"])
+    wn("conv_pre.", (c0 // 2 ** n, 1, 7), c0 // 2 ** n)
+    for i, k in enumerate(reversed(h["upsample_kernel_sizes"])):
+        cin, cout = c0 // 2 ** (n - i), c0 // 2 ** (n - i - 1)
+        wn(f"ups.{i}.", (cout, cin, k), cout)
+    nk = len(h["resblock_kernel_sizes"])
+    ch = c0
+    for i in range(n):
+        ch = c0 // 2 ** (n - 1 - i)
+        for j, (k, dil) in enumerate(zip(h["resblock_kernel_sizes"], h["resblock_dilation_sizes"])):
+            p = f"resblocks.{i * nk + j}."
+            if h["resblock"] == "1":
+                for m in range(len(dil)):
+                    wn(p + f"convs1.{m}.", (ch, ch, k), ch)
+                for m in range(len(dil)):
+                    wn(p + f"convs2.{m}.", (ch, ch, k), ch)
+            else:
+                for m in range(len(dil)):
+                    wn(p + f"convs.{m}.", (ch, ch, k), ch)
+    wn("conv_post.", (2 * h["inter_channels"], ch, 7), 2 * h["inter_channels"])
+    return d
+
+
 def get_encoder_out_channels(encoder):
     """Reference tools/tools.py:257-264 (`get_encdoer_out_channels`)."""
     table = {"whisper_large_v3": 1280, "contentvec768l12": 768, "xlsr_53_56k": 1024}

@@ -51,7 +51,8 @@ EXPORTS = [
     "lds_embed_workspace_bytes", "lds_embed_forward", "lds_transpose", "lds_gather_rows", "lds_resample_frames", "lds_axpby", "lds_vocoder_create", "lds_vocoder_destroy",
     "lds_vocoder_workspace_bytes", "lds_vocoder_forward", "lds_lm_create", "lds_lm_destroy", "lds_lm_workspace_bytes", "lds_lm_encode",
     "lds_lm_generate", "lds_prof_enable", "lds_prof_summary", "lds_unet_set_gemm_mode", "lds_unet_get_gemm_mode",
-    "lds_unet_set_latency_mode", "lds_unet_get_latency_mode", "lds_unet_forward_ragged", "lds_sampler_run_ragged", "lds_vocoder_forward_ragged"]
+    "lds_unet_set_latency_mode", "lds_unet_get_latency_mode", "lds_unet_forward_ragged", "lds_sampler_run_ragged", "lds_vocoder_forward_ragged",
+    "lds_vae_encoder_create", "lds_vae_encoder_destroy", "lds_vae_encoder_workspace_bytes", "lds_vae_encoder_forward"]
 # include/lds_test.h: single-op entry points for tests/ and tools/ (not part of the drop-in boundary)
 TEST_EXPORTS = [
     "lds_test_conv", "lds_test_dconv", "lds_bench_dconv", "lds_test_gn_apply", "lds_bench_gn_stream", "lds_test_gn_chain_k4p",
@@ -59,7 +60,8 @@ TEST_EXPORTS = [
     "lds_bench_dconv_bf3", "lds_test_k8b3_roundtrip", "lds_test_gn_apply_bf3", "lds_test_dconv_split", "lds_bench_dconv_split",
     "lds_test_split_roundtrip", "lds_test_gn_apply_split", "lds_debug_set_split_rule", "lds_test_attention_f16math",
     "lds_test_attention_latency", "lds_debug_set_gn_fold", "lds_debug_set_voc_pair", "lds_debug_set_touch_weights", "lds_test_voc_pair", "lds_test_gn_fold_k4p", "lds_bench_dconv_alt", "lds_debug_fill_u32", "lds_debug_trace",
-    "lds_debug_trace_count", "lds_debug_trace_get", "lds_debug_unet_plan", "lds_test_gn_fold_split", "lds_test_cluster_join", "lds_test_lm_sample"]
+    "lds_debug_trace_count", "lds_debug_trace_get", "lds_debug_unet_plan", "lds_test_gn_fold_split", "lds_test_cluster_join", "lds_test_lm_sample",
+    "lds_test_conv_down"]
 
 
 def lib():
@@ -72,9 +74,9 @@ def lib():
         L = C.CDLL(LIB_PATH)
         L.lds_last_error.restype = C.c_char_p
         for n in EXPORTS + TEST_EXPORTS:
-            if n not in ("lds_last_error", "lds_unet_destroy", "lds_embed_destroy", "lds_vocoder_destroy", "lds_lm_destroy"):
+            if n not in ("lds_last_error", "lds_unet_destroy", "lds_embed_destroy", "lds_vocoder_destroy", "lds_lm_destroy", "lds_vae_encoder_destroy"):
                 getattr(L, n).restype = C.c_int
-        for n in ("lds_unet_destroy", "lds_embed_destroy", "lds_vocoder_destroy", "lds_lm_destroy"):
+        for n in ("lds_unet_destroy", "lds_embed_destroy", "lds_vocoder_destroy", "lds_lm_destroy", "lds_vae_encoder_destroy"):
             getattr(L, n).restype = None
             getattr(L, n).argtypes = [C.c_void_p]
         L.lds_unet_set_gemm_mode.argtypes = [C.c_void_p, C.c_int]
@@ -367,6 +369,24 @@ def transpose(x, scale=1.0):
     return out
 
 
+def vocoder_cfg(h):
+    """lds_vocoder_cfg of a HiFi-VAEGAN config dict (shared by the decoder and the encoder)."""
+    c = VocoderCfg()
+    c.inter_channels = h["inter_channels"]
+    c.upsample_initial_channel = h["upsample_initial_channel"]
+    c.n_ups = len(h["upsample_rates"])
+    for i, (u, k) in enumerate(zip(h["upsample_rates"], h["upsample_kernel_sizes"])):
+        c.upsample_rates[i], c.upsample_kernel_sizes[i] = u, k
+    c.resblock = 1 if str(h["resblock"]) == "1" else 2
+    c.n_kernels = len(h["resblock_kernel_sizes"])
+    c.n_dil = len(h["resblock_dilation_sizes"][0])
+    for j, (k, dil) in enumerate(zip(h["resblock_kernel_sizes"], h["resblock_dilation_sizes"])):
+        c.resblock_kernel_sizes[j] = k
+        for m, d in enumerate(dil):
+            c.resblock_dilation_sizes[j][m] = d
+    return c
+
+
 class Generator:
     """HiFi-VAEGAN decoder (lds_vocoder_*)."""
 
@@ -413,6 +433,69 @@ class Generator:
         check(lib().lds_vocoder_forward(self.h, _dev(z, torch.float32), _dev(wav), _dev(ws), C.c_size_t(ws.numel()), B, T,
                                         _stream()))
         return wav
+
+
+class VaeEncoder:
+    """HiFi-VAEGAN encoder (lds_vae_encoder_*): audio [B,L] -> (out [B,T,2C], z [B,T,C] or None)."""
+
+    def __init__(self, h, state):
+        hop = int(np.prod(h["upsample_rates"]))
+        if "hop_size" in h and int(h["hop_size"]) != hop:      # extract pads to hop_size; the encoder's frames are prod(upsample_rates) samples
+            raise ValueError(f"VaeEncoder: config hop_size {h['hop_size']} != prod(upsample_rates) {hop} = {list(h['upsample_rates'])}")
+        c = vocoder_cfg(h)
+        n, names, ptrs, numel, keep = _host_tensor_table(state)
+        self.h = C.c_void_p()
+        check(lib().lds_vae_encoder_create(C.byref(c), n, names, ptrs, numel, C.byref(self.h)))
+        self.hop = int(np.prod(h["upsample_rates"]))
+        self.C = c.inter_channels
+        self.ws = Workspace()
+
+    def __del__(self):
+        if getattr(self, "h", None) and _lib is not None:
+            _lib.lds_vae_encoder_destroy(self.h)
+            self.h = None
+
+    def workspace_bytes(self, B, L):
+        nb = C.c_size_t()
+        check(lib().lds_vae_encoder_workspace_bytes(self.h, B, C.c_int64(L), C.byref(nb)))
+        return nb.value
+
+    def forward(self, audio, noise=None, only_mean=False, ws=None):
+        """audio [B,L] (L a multiple of the hop); noise [B,C,T] or None -> (out [B,T,2C], z [B,T,C] or None); `ws`: a caller's uint8
+        workspace of at least workspace_bytes(B, L) (tests poison it), else the handle's own"""
+        import torch
+        B, L = audio.shape
+        T = L // self.hop
+        if noise is not None and tuple(noise.shape) != (B, self.C, T):
+            raise ValueError(f"noise must be [B, C, T] = {[B, self.C, T]}, got {list(noise.shape)}")
+        nb = self.workspace_bytes(B, L)
+        if ws is None:
+            ws = self.ws.get(nb, audio.device)
+        out = torch.empty(B, T, 2 * self.C, dtype=torch.float32, device=audio.device)
+        z = torch.empty(B, T, self.C, dtype=torch.float32, device=audio.device) if noise is not None else None
+        check(lib().lds_vae_encoder_forward(self.h, _dev(audio, torch.float32), _dev(noise, torch.float32) if noise is not None else None,
+                                            _dev(out), _dev(z) if z is not None else None, int(bool(only_mean)), _dev(ws),
+                                            C.c_size_t(ws.numel()), B, C.c_int64(L), _stream()))
+        return out, z
+
+
+def conv_down(x, w, b, stride, slope=1.0, tile=0, cfg=None):
+    """The encoder's convolution alone (lds_test_conv_down): x [B,Ci,T] on the device, w [Co,Ci,K] / b [Co] host arrays ->
+    [B,Co,(T + 2 pad - K) // stride + 1] with pad = (K - stride + 1) // 2, LeakyReLU(slope) on the input.  tile: 0 = the product path's
+    choice, else 64064 / 64128 / 128128; cfg: a list that receives the configuration that ran."""
+    import torch
+    B, Ci, T = x.shape
+    w = np.ascontiguousarray(w, dtype=np.float32)
+    Co, _, K = w.shape
+    pad = (K - stride + 1) // 2
+    out = torch.empty(B, Co, (T + 2 * pad - K) // stride + 1, dtype=torch.float32, device=x.device)
+    bb = np.ascontiguousarray(b, dtype=np.float32) if b is not None else None
+    buf = C.create_string_buffer(128)
+    check(lib().lds_test_conv_down(_dev(x, torch.float32), C.c_void_p(w.ctypes.data), C.c_void_p(bb.ctypes.data) if bb is not None else None,
+                                   Ci, Co, K, stride, T, B, C.c_float(slope), tile, _dev(out), buf, C.c_size_t(len(buf)), _stream()))
+    if cfg is not None:
+        cfg.append(buf.value.decode())
+    return out
 
 
 class LM:
