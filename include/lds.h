@@ -179,6 +179,15 @@ int  lds_vae_encoder_workspace_bytes(const lds_vae_encoder* e, int B, int64_t L,
  * z dev [B][T][C] = m + noise * exp(logs) (the real logs, whatever only_mean) or NULL (needs noise) */
 int  lds_vae_encoder_forward(lds_vae_encoder* e, const float* audio, const float* noise, float* out, float* z,
                              int only_mean, void* ws, size_t ws_bytes, int B, int64_t L, void* stream);
+/* Ragged batch (see lds_vocoder_forward_ragged): lengths host int32 [B] (B <= 64) = every clip's own sample count inside audio [B][L],
+ * 1 <= lengths[b] <= L.  Clip b is encoded as if alone (zero-padded to ceil(lengths[b] / hop) * hop samples, T_b frames): every stage of
+ * the encoder stores zeros beyond the clip's length at that stage, which is the zero padding its convolutions see when it runs alone.
+ * Rows [T_b, T) of out and z are zeros; samples of audio beyond lengths[b] are never read as anything but zero (NaN / Inf included), nor
+ * is noise beyond T_b.  Rows [0, T_b) equal the clip encoded alone within the stated tolerance; with every length equal to L the result
+ * is lds_vae_encoder_forward's, bit for bit.  Uses lds_vae_encoder_workspace_bytes; a bad length, a null lengths or B > 64 give
+ * LDS_EINVAL naming the value, before anything is enqueued. */
+int  lds_vae_encoder_forward_ragged(lds_vae_encoder* e, const float* audio, const int32_t* lengths, const float* noise, float* out,
+                                    float* z, int only_mean, void* ws, size_t ws_bytes, int B, int64_t L, void* stream);
 
 /* ---- text2semantic: RoFormer encoder prefill + cached autoregressive decode (reference text2semantic/roformer/roformer.py:59-255
  *      over HF transformers RoFormerModel / RoFormerForCausalLM + GenerationMixin; called from 22_infer_tts.py:76-98) ------------- */

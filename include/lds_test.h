@@ -115,6 +115,11 @@ int lds_test_voc_pair(const float* x, const float* w1, const float* b1, const fl
  * BM*1000+BN in {64064, 64128, 128128}; cfg_out (or NULL) receives the configuration that ran ("BM128 BN128 grid ...").  Synchronises. */
 int lds_test_conv_down(const float* x, const float* w, const float* b, int Ci, int Co, int K, int stride, int T, int B, float slope,
                        int tile, float* out, char* cfg_out, size_t cfg_cap, void* stream);
+/* ... in a ragged batch: lengths_in / lengths_out host int32 [B] (B <= 64) = every element's valid input frames (0 .. T; x reads as zeros
+ * from there on, whatever it holds) and output frames (0 .. To; out is stored as zeros from there on) */
+int lds_test_conv_down_ragged(const float* x, const float* w, const float* b, int Ci, int Co, int K, int stride, int T, int B, float slope,
+                              const int32_t* lengths_in, const int32_t* lengths_out, int tile, float* out, char* cfg_out, size_t cfg_cap,
+                              void* stream);
 int lds_debug_set_split_rule(int rule);
 /* plain [B,C,T] -> K8B3 -> plain: must return the input bit for bit (the three-term split is lossless) */
 int lds_test_k8b3_roundtrip(const float* x, float* out, int B, int C, int T, void* stream);

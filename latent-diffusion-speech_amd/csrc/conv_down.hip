@@ -2,8 +2,10 @@
 //   conv_down   out[b,co,t] = bias[co] + sum_{ci,k} W[co][ci][k] * lrelu(x[b,ci, t*stride - pad + k]) over plain [B][Ci][L] input,
 //               as an implicit GEMM (M = co, N = t, K = (ci, k) in the weight's own [Co][Ci*K] order) on v_mfma_f32_32x32x2_f32.
 //               It runs conv_pre (1 -> 16, k 7, stride 1; slope 1 = no activation), the five strided downsamplers (k = 2u, stride u)
-//               and conv_post (slope 0.01).  Taps outside [0, L) read exact zeros.
-//   vae_head    conv_post's [B][2C][T] -> out [B][T][2C] (m, then logs or zeros) and z = m + n * exp(logs) as [B][T][C].
+//               and conv_post (slope 0.01).  Taps outside [0, L) read exact zeros; in a ragged batch, so do taps at or beyond the element's
+//               vlen_in, and frames at or beyond its vlen are stored as zeros (a workgroup wholly beyond vlen skips its reduction).
+//   vae_head    conv_post's [B][2C][T] -> out [B][T][2C] (m, then logs or zeros) and z = m + n * exp(logs) as [B][T][C]; in a ragged
+//               batch, rows beyond the element's frame count are zeros.
 // Every output element is one k-ordered fmaf chain from zero (K-steps of 32 rows, two rows per MFMA) plus the bias, whatever the tile
 // shape, so an utterance encodes to the same bits alone and inside a batch.
 #include "kernels.h"
@@ -35,6 +37,8 @@ __global__ void __launch_bounds__(256) conv_down_kernel(const ConvDownArgs p) {
     const int Kd = p.Ci * p.K;
     const int kk = tid & 31, r0 = tid >> 5;
     const float* xb = p.x + (long long)b * p.Ci * p.L;
+    const int Lin = p.vlen_in ? min(p.L, p.vlen_in[b]) : p.L;      // ragged batch: the input reads as zeros from Lin on ...
+    const int Lout = p.vlen ? min(p.To, p.vlen[b]) : p.To;         // ... and the output is zeros from Lout on
     float wv[NW], xv[NX];
     auto load = [&](int k0) {
         const int kg = k0 + kk;
@@ -51,7 +55,7 @@ __global__ void __launch_bounds__(256) conv_down_kernel(const ConvDownArgs p) {
         for (int i = 0; i < NX; ++i) {
             const int t = t0 + r0 + 8 * i;
             const long long s = (long long)t * p.stride - p.pad + tap;
-            float v = (kin && t < p.To && s >= 0 && s < p.L) ? xr[s] : 0.f;
+            float v = (kin && t < p.To && s >= 0 && s < Lin) ? xr[s] : 0.f;
             xv[i] = v >= 0.f ? v : v * p.slope;
         }
     };
@@ -62,8 +66,8 @@ __global__ void __launch_bounds__(256) conv_down_kernel(const ConvDownArgs p) {
         for (int j = 0; j < WN; ++j)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-    load(0);
-    for (int k0 = 0; k0 < Kd; k0 += kDownKC) {
+    if (t0 < Lout) load(0);
+    for (int k0 = 0; t0 < Lout && k0 < Kd; k0 += kDownKC) {      // (t0 >= Lout: every column of the tile is padding; only zeros are stored)
 #pragma unroll
         for (int i = 0; i < NW; ++i) Ws[kk * SW + r0 + 8 * i] = wv[i];
 #pragma unroll
@@ -93,7 +97,7 @@ __global__ void __launch_bounds__(256) conv_down_kernel(const ConvDownArgs p) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int co = co0 + (wm * WM + i) * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-                if (co < p.Co && t < p.To) p.out[((long long)b * p.Co + co) * p.To + t] = acc[i][j][r] + (p.bias ? p.bias[co] : 0.f);
+                if (co < p.Co && t < p.To) p.out[((long long)b * p.Co + co) * p.To + t] = t < Lout ? acc[i][j][r] + (p.bias ? p.bias[co] : 0.f) : 0.f;
             }
         }
 }
@@ -141,14 +145,20 @@ hipError_t launch_conv_down(const ConvDownArgs& a, hipStream_t s) {
 }
 
 // one thread per (b, t, c), c fastest: the [B][T][2C] / [B][T][C] stores are coalesced; z's product and sum are rounded separately,
-// like the reference's three eager ops (randn_like(m) * exp(logs), then + m)
+// like the reference's three eager ops (randn_like(m) * exp(logs), then + m); ragged batch: rows t >= tlen[b] are written as zeros
 __global__ void __launch_bounds__(256) vae_head_kernel(const float* __restrict__ y, const float* __restrict__ noise, float* __restrict__ out,
-                                                       float* __restrict__ z, int C, int T, int only_mean, long long n) {
+                                                       float* __restrict__ z, int C, int T, int only_mean, long long n, const int* __restrict__ tlen) {
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
         const int ch = (int)(i % C);
         const long long bt = i / C;
         const int t = (int)(bt % T);
         const long long b = bt / T;
+        if (tlen && t >= tlen[b]) {
+            out[bt * 2 * C + ch] = 0.f;
+            out[bt * 2 * C + C + ch] = 0.f;
+            if (z) z[bt * C + ch] = 0.f;
+            continue;
+        }
         const float m = y[(b * 2 * C + ch) * T + t];
         const float lg = y[(b * 2 * C + C + ch) * T + t];
         out[bt * 2 * C + ch] = m;
@@ -157,12 +167,12 @@ __global__ void __launch_bounds__(256) vae_head_kernel(const float* __restrict__
     }
 }
 
-hipError_t launch_vae_head(const float* y, const float* noise, float* out, float* z, int B, int C, int T, int only_mean, hipStream_t s) {
+hipError_t launch_vae_head(const float* y, const float* noise, float* out, float* z, int B, int C, int T, int only_mean, hipStream_t s, const int* tlen) {
     if (!y || !out || (z && !noise) || B < 1 || C < 1 || T < 1) return hipErrorInvalidValue;
     const long long n = (long long)B * T * C;
     const long long nb = std::min<long long>((n + 255) / 256, 65536);
     ProfScope ps(s, "vae_head", 2.0 * n, 4.0 * n * (z ? 5 : 4));
-    hipLaunchKernelGGL(vae_head_kernel, dim3((unsigned)nb), dim3(256), 0, s, y, noise, out, z, C, T, only_mean, n);
+    hipLaunchKernelGGL(vae_head_kernel, dim3((unsigned)nb), dim3(256), 0, s, y, noise, out, z, C, T, only_mean, n, tlen);
     return hipGetLastError();
 }
 

@@ -61,16 +61,21 @@ const char* conv_small_last_config();
 // conv_down (conv_down.hip): the VAE encoder's convolutions over plain tensors, x [B][Ci][L] -> out [B][Co][To] with
 // out[b,co,t] = bias[co] + sum_{ci,k} w[co][ci][k] * lrelu_slope(x[b,ci, t*stride - pad + k]) (taps outside [0, L) read zeros;
 // slope 1 = no activation); w is the unpacked device weight [Co][Ci][K].  v_mfma_f32_32x32x2_f32, exact fp32.
+// Ragged batch: vlen_in / vlen (device int32 [B], null = L / To) are each batch element's valid input / output frames; the input reads
+// as zeros from vlen_in[b] on (whatever x holds there) and the output is stored as zeros from vlen[b] on.
 struct ConvDownArgs {
     const float* x; const float* w; const float* bias; float* out;
     int Ci, Co, K, stride, pad, L, To, B;
     float slope;
     int tile;      // 0 = auto (by workgroup count against the CU count), else BM*1000+BN in {64064, 64128, 128128}
+    const int* vlen_in; const int* vlen;
 };
 hipError_t launch_conv_down(const ConvDownArgs& a, hipStream_t s);
 const char* conv_down_last_config();
-// y [B][2C][T] (conv_post) -> out [B][T][2C] = (m, only_mean ? 0 : logs); z [B][T][C] = m + noise * exp(logs) when z (needs noise [B][C][T])
-hipError_t launch_vae_head(const float* y, const float* noise, float* out, float* z, int B, int C, int T, int only_mean, hipStream_t s);
+// y [B][2C][T] (conv_post) -> out [B][T][2C] = (m, only_mean ? 0 : logs); z [B][T][C] = m + noise * exp(logs) when z (needs noise [B][C][T]);
+// tlen (device int32 [B], null = T): rows t >= tlen[b] of out and z are zeros and noise is not read there
+hipError_t launch_vae_head(const float* y, const float* noise, float* out, float* z, int B, int C, int T, int only_mean, hipStream_t s,
+                           const int* tlen = nullptr);
 
 // voc_pair (voc_pair.hip): one residual step of the vocoder's ResBlock1 at 16 / 32 channels as one launch over plain [B][C][T] tensors:
 // out = (accum ? out : 0) + c2(lrelu(c1(lrelu(x)))) + x, divided by out_div; c1 dilated by `dil`, both k = KT, "same" zero padding;

@@ -2187,8 +2187,8 @@ static void plan_enc(const lds_vae_encoder* e, Arena& A, int B, int64_t L, EncWs
     float** kb[8] = {&v.kx_raw, &v.kx_act, &v.kt_act, &v.ka_raw, &v.ka_act, &v.kb_raw, &v.kb_act, &v.ks};
     for (int i = 0; i < 8; ++i) *kb[i] = (mk && shared) ? shared + i * k4 : nullptr;
     v.kin = nullptr;      // (the encoder's MRF stages always return a plain tensor)
-    v.vlens = nullptr;
     w.y = A.f((size_t)B * e->post.Co * (L / e->hop));
+    v.vlens = (int*)A.f((e->downs.size() + 2) * 64);      // ragged batches: the sample lengths and every stage's lengths, <= 64 clips
 }
 extern "C" int lds_vae_encoder_workspace_bytes(const lds_vae_encoder* e, int B, int64_t L, size_t* out) {
     if (!out || !enc_args_ok(e, B, L)) return fail(LDS_EINVAL, "bad argument (B %d, L %lld: B >= 1 and L a positive multiple of the hop)", B, (long long)L);
@@ -2199,10 +2199,11 @@ extern "C" int lds_vae_encoder_workspace_bytes(const lds_vae_encoder* e, int B, 
     return LDS_OK;
 }
 
-static int run_down(const DownW& d, const float* x, int64_t L, float slope, float* out, int B, hipStream_t st, int tile = 0) {
+static int run_down(const DownW& d, const float* x, int64_t L, float slope, float* out, int B, hipStream_t st, int tile = 0, const int* vlen_in = nullptr,
+                    const int* vlen = nullptr) {
     ConvDownArgs a;
     memset(&a, 0, sizeof(a));
-    a.x = x; a.w = d.w; a.bias = d.bias; a.out = out;
+    a.x = x; a.w = d.w; a.bias = d.bias; a.out = out; a.vlen_in = vlen_in; a.vlen = vlen;
     a.Ci = d.Ci; a.Co = d.Co; a.K = d.K; a.stride = d.stride; a.pad = d.pad; a.L = (int)L; a.B = B; a.slope = slope; a.tile = tile;
     a.To = (int)((L + 2 * d.pad - d.K) / d.stride + 1);
     const double flops = 2.0 * B * (double)a.To * d.Co * (double)d.Ci * d.K;
@@ -2227,8 +2228,23 @@ static int run_down(const DownW& d, const float* x, int64_t L, float slope, floa
     return LDS_OK;
 }
 
+static int vae_encoder_forward_impl(lds_vae_encoder* e, const float* audio, const int32_t* lens_host, const float* noise, float* out, float* z,
+                                    int only_mean, void* ws, size_t ws_bytes, int B, int64_t L, void* stream);
 extern "C" int lds_vae_encoder_forward(lds_vae_encoder* e, const float* audio, const float* noise, float* out, float* z, int only_mean, void* ws,
                                        size_t ws_bytes, int B, int64_t L, void* stream) {
+    return vae_encoder_forward_impl(e, audio, nullptr, noise, out, z, only_mean, ws, ws_bytes, B, L, stream);
+}
+extern "C" int lds_vae_encoder_forward_ragged(lds_vae_encoder* e, const float* audio, const int32_t* lengths, const float* noise, float* out, float* z,
+                                              int only_mean, void* ws, size_t ws_bytes, int B, int64_t L, void* stream) {
+    if (!lengths) return fail(LDS_EINVAL, "bad argument: lengths is null");
+    if (B > 64) return fail(LDS_EINVAL, "per-clip lengths: at most 64 clips per call (got %d)", B);
+    if (!enc_args_ok(e, B, L)) return fail(LDS_EINVAL, "bad argument (B %d, L %lld: B >= 1 and L a positive multiple of the hop)", B, (long long)L);
+    for (int b = 0; b < B; ++b)
+        if (lengths[b] < 1 || lengths[b] > L) return fail(LDS_EINVAL, "length[%d] = %d outside 1 .. %lld", b, lengths[b], (long long)L);
+    return vae_encoder_forward_impl(e, audio, lengths, noise, out, z, only_mean, ws, ws_bytes, B, L, stream);
+}
+static int vae_encoder_forward_impl(lds_vae_encoder* e, const float* audio, const int32_t* lens_host, const float* noise, float* out, float* z,
+                                    int only_mean, void* ws, size_t ws_bytes, int B, int64_t L, void* stream) {
     if (!audio || !out || !ws || (z && !noise) || !enc_args_ok(e, B, L)) return fail(LDS_EINVAL, "bad argument");
     hipStream_t st = (hipStream_t)stream;
     ProfChain chain;
@@ -2236,22 +2252,48 @@ extern "C" int lds_vae_encoder_forward(lds_vae_encoder* e, const float* audio, c
     EncWs w;
     plan_enc(e, A, B, L, w);
     if (!A.ok) return fail(LDS_ENOMEM, "encoder workspace too small: need %zu", A.used);
+    // Ragged batch: clip b is audio[b, :len_b] encoded alone, i.e. zero-padded to Lp_b = ceil(len_b / hop) * hop samples.  vl[0] = len_b
+    // (conv_pre reads the audio as zeros from there on), vl[1] = Lp_b (conv_pre's output), vl[2 + i] = Lp_b / (u_0 ... u_i) after
+    // downsampler i (k = 2u, pad u / 2: a multiple of u maps to L / u exactly); the last is the clip's frame count T_b.  Every stage
+    // stores zeros beyond its length, which is the zero padding the clip's convolutions see when it runs alone.
+    const size_t nd = e->downs.size();
+    std::vector<const int*> vl(nd + 2, nullptr);
+    if (lens_host) {
+        std::vector<int64_t> cur(B);
+        for (int b = 0; b < B; ++b) cur[b] = lens_host[b];
+        for (size_t i = 0; i < nd + 2; ++i) {
+            float tmp[64];
+            for (int b = 0; b < B; ++b) {
+                const int v = (int)cur[b];
+                memcpy(&tmp[b], &v, sizeof(int));
+            }
+            HIP_TRY(launch_set_list((float*)(w.v.vlens + 64 * i), tmp, B, st));
+            vl[i] = w.v.vlens + 64 * i;
+            for (int b = 0; b < B; ++b) {
+                if (i == 0) cur[b] = (cur[b] + e->hop - 1) / e->hop * e->hop;
+                else if (i <= nd) cur[b] /= e->downs[i - 1].stride;
+            }
+        }
+    }
     // reference models.py:39-54
-    LDS_TRY(run_down(e->pre, audio, L, 1.0f, w.v.x, B, st));
+    LDS_TRY(run_down(e->pre, audio, L, 1.0f, w.v.x, B, st, 0, vl[0], vl[1]));
     float* x = w.v.x;
     float* xs = w.v.xs;
     int64_t Tl = L;
-    for (size_t i = 0; i < e->downs.size(); ++i) {
+    for (size_t i = 0; i < nd; ++i) {
         const DownW& d = e->downs[i];
-        LDS_TRY(run_down(d, x, Tl, 0.1f, xs, B, st));      // x = ups[i](leaky_relu(x, 0.1))
+        const int* vlen = vl[i + 2];
+        LDS_TRY(run_down(d, x, Tl, 0.1f, xs, B, st, 0, vl[i + 1], vlen));      // x = ups[i](leaky_relu(x, 0.1))
         { float* t = x; x = xs; xs = t; }
         Tl /= d.stride;
-        if (voc_dma_stage(e, d.Co)) LDS_TRY(voc_mrf_dma(e, w.v, (int)i, x, xs, d.Co, (int)Tl, B, st));
-        else LDS_TRY(voc_mrf_plain(e, w.v, (int)i, x, xs, d.Co, (int)Tl, B, st, nullptr));
+        // (ragged: the narrow stage's voc_pair masks its input window by Tl, not by vlen; it relies on conv_down above having stored
+        // zeros beyond vlen, and on each residual step doing the same for the next)
+        if (voc_dma_stage(e, d.Co)) LDS_TRY(voc_mrf_dma(e, w.v, (int)i, x, xs, d.Co, (int)Tl, B, st, vlen));
+        else LDS_TRY(voc_mrf_plain(e, w.v, (int)i, x, xs, d.Co, (int)Tl, B, st, vlen));
         { float* t = x; x = xs; xs = t; }
     }
-    LDS_TRY(run_down(e->post, x, Tl, 0.01f, w.y, B, st));      // conv_post(leaky_relu(x)) -> [B][2C][T]
-    HIP_TRY(launch_vae_head(w.y, noise, out, z, B, e->cfg.inter_channels, (int)Tl, only_mean, st));
+    LDS_TRY(run_down(e->post, x, Tl, 0.01f, w.y, B, st, 0, vl[nd + 1], vl[nd + 1]));      // conv_post(leaky_relu(x)) -> [B][2C][T]
+    HIP_TRY(launch_vae_head(w.y, noise, out, z, B, e->cfg.inter_channels, (int)Tl, only_mean, st, vl[nd + 1]));
     return LDS_OK;
 }
 
@@ -2825,20 +2867,47 @@ extern "C" int lds_test_voc_pair(const float* x, const float* w1, const float* b
 // The encoder's convolution alone: x dev [B][Ci][T], w host [Co][Ci][K], b host [Co] or null; out dev [B][Co][To], To = (T + 2 pad - K) / stride + 1
 // with pad = (K - stride + 1) / 2 (the reference's downsampler padding; 3 for k 7, stride 1), LeakyReLU(slope) on the input (1 = none);
 // tile 0 = the product path's choice, else forced (kernels.h ConvDownArgs::tile); cfg_out (or null) = the configuration that ran
-extern "C" int lds_test_conv_down(const float* x, const float* w, const float* b, int Ci, int Co, int K, int stride, int T, int B, float slope,
-                                  int tile, float* out, char* cfg_out, size_t cfg_cap, void* stream) {
+static int conv_down_test_impl(const float* x, const float* w, const float* b, int Ci, int Co, int K, int stride, int T, int B, float slope,
+                               const int32_t* lengths_in, const int32_t* lengths_out, int tile, float* out, char* cfg_out, size_t cfg_cap, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     if (!x || !w || !out || Ci < 1 || Co < 1 || K < stride || stride < 1 || T < 1 || B < 1 || B > 65535 || T % stride) return fail(LDS_EINVAL, "bad argument");
+    const int pad = (K - stride + 1) / 2, To = (T + 2 * pad - K) / stride + 1;
+    const int32_t* src[2] = {lengths_in, lengths_out};
+    const int lim[2] = {T, To};
+    for (int i = 0; i < 2 && lengths_in; ++i)
+        for (int e = 0; e < B; ++e)
+            if (src[i][e] < 0 || src[i][e] > lim[i]) return fail(LDS_EINVAL, "lengths_%s[%d] = %d outside 0 .. %d", i ? "out" : "in", e, src[i][e], lim[i]);
     Owner own;
+    TmpDev tmp;
     DownW d;
     d.w = own.upload(std::vector<float>(w, w + (size_t)Co * Ci * K));
     if (b) d.bias = own.upload(std::vector<float>(b, b + Co));
     if (!d.w || (b && !d.bias)) return fail(LDS_ENOMEM, "upload failed");
-    d.Co = Co; d.Ci = Ci; d.K = K; d.stride = stride; d.pad = (K - stride + 1) / 2;
-    LDS_TRY(run_down(d, x, T, slope, out, B, st, tile));
+    d.Co = Co; d.Ci = Ci; d.K = K; d.stride = stride; d.pad = pad;
+    int* vl[2] = {nullptr, nullptr};
+    for (int i = 0; i < 2 && lengths_in; ++i) {
+        float t4[64];
+        memcpy(t4, src[i], sizeof(int) * B);
+        vl[i] = (int*)tmp.f(64);
+        if (!vl[i]) return fail(LDS_ENOMEM, "alloc");
+        HIP_TRY(launch_set_list((float*)vl[i], t4, B, st));
+    }
+    LDS_TRY(run_down(d, x, T, slope, out, B, st, tile, vl[0], vl[1]));
     if (cfg_out && cfg_cap) snprintf(cfg_out, cfg_cap, "%s", conv_down_last_config());
     HIP_TRY(hipStreamSynchronize(st));
     return LDS_OK;
+}
+extern "C" int lds_test_conv_down(const float* x, const float* w, const float* b, int Ci, int Co, int K, int stride, int T, int B, float slope,
+                                  int tile, float* out, char* cfg_out, size_t cfg_cap, void* stream) {
+    return conv_down_test_impl(x, w, b, Ci, Co, K, stride, T, B, slope, nullptr, nullptr, tile, out, cfg_out, cfg_cap, stream);
+}
+// ... in a ragged batch: lengths_in / lengths_out host int32 [B] (B <= 64) = every element's valid input frames (0 .. T) and output frames
+// (0 .. To) (kernels.h ConvDownArgs::vlen_in / vlen)
+extern "C" int lds_test_conv_down_ragged(const float* x, const float* w, const float* b, int Ci, int Co, int K, int stride, int T, int B, float slope,
+                                         const int32_t* lengths_in, const int32_t* lengths_out, int tile, float* out, char* cfg_out, size_t cfg_cap,
+                                         void* stream) {
+    if (!lengths_in || !lengths_out || B < 1 || B > 64) return fail(LDS_EINVAL, "bad argument: lengths_in / lengths_out null or B %d outside 1 .. 64", B);
+    return conv_down_test_impl(x, w, b, Ci, Co, K, stride, T, B, slope, lengths_in, lengths_out, tile, out, cfg_out, cfg_cap, stream);
 }
 extern "C" int lds_debug_set_gn_fold(int on) {
     g_gn_fold.store(on ? 1 : 0);

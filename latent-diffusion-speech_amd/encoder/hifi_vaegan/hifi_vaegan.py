@@ -1,7 +1,8 @@
 """`Hifi_VAEGAN` wrapper (reference encoder/hifi_vaegan/hifi_vaegan.py:10-65): reads
 `<model_path>/decoder.pth` = {'config': h, 'model': state_dict with weight-norm pairs}, lazily
 builds the native Generator on first call and maps z [B,T,C] -> wav [B,1,T*hop]; `extract` lazily
-builds the native encoder from `<model_path>/encoder.pth` (same layout) and maps audio [B,L] -> [B,T,2C]."""
+builds the native encoder from `<model_path>/encoder.pth` (same layout) and maps audio [B,L] -> [B,T,2C]; `extract_ragged` does the same
+for a batch of clips of their own lengths."""
 import os
 
 import torch
@@ -47,6 +48,21 @@ class Hifi_VAEGAN(torch.nn.Module):
         `noise` (not in the reference): a [B,C,T] tensor used instead of that draw (nothing is drawn then)."""
         if not audio.is_cuda:
             raise RuntimeError("Hifi_VAEGAN.extract needs tensors on a HIP device (no CPU fallback)")
+        return self._encode(audio, only_z, only_mean, noise, None)
+
+    @torch.no_grad()
+    def extract_ragged(self, audio, lengths, only_z=False, only_mean=False, *, noise=None):
+        """Extension (not in the reference): audio [B,L] padded to the longest clip + every clip's own sample count (host ints, B <= 64,
+        1 .. L) -> [B,T,2C] (or z [B,T,C] under only_z) with every clip encoded as if alone: clip b is audio[b, :lengths[b]] right-padded
+        with zeros to T_b = ceil(lengths[b] / hop) frames, whatever the buffer holds beyond lengths[b]; rows [T_b, T) are zeros
+        (include/lds.h lds_vae_encoder_forward_ragged).  Pads L and draws the noise exactly as extract does; z uses noise[b, :, :T_b]."""
+        B, L = audio.shape[0], audio.shape[-1]
+        ln = native.VaeEncoder.lengths(lengths, B, L)      # (host-side validation first: a bad length is a ValueError on any device)
+        if not audio.is_cuda:
+            raise RuntimeError("Hifi_VAEGAN.extract_ragged needs tensors on a HIP device (no CPU fallback)")
+        return self._encode(audio, only_z, only_mean, noise, ln)
+
+    def _encode(self, audio, only_z, only_mean, noise, lengths):
         if self.encoder_model is None:
             state = self._encoder_state
             if state is None:
@@ -62,7 +78,7 @@ class Hifi_VAEGAN(torch.nn.Module):
         B, T = audio.shape[0], audio.shape[-1] // hop
         if noise is None:
             noise = torch.randn(B, self.dimension(), T, dtype=torch.float32, device=audio.device)      # randn_like(m)
-        out, z = self.encoder_model.forward(audio, noise.float().contiguous() if only_z else None, only_mean=only_mean)
+        out, z = self.encoder_model.forward(audio, noise.float().contiguous() if only_z else None, only_mean=only_mean, lengths=lengths)
         return z if only_z else out
 
     @torch.no_grad()

@@ -52,7 +52,8 @@ EXPORTS = [
     "lds_vocoder_workspace_bytes", "lds_vocoder_forward", "lds_lm_create", "lds_lm_destroy", "lds_lm_workspace_bytes", "lds_lm_encode",
     "lds_lm_generate", "lds_prof_enable", "lds_prof_summary", "lds_unet_set_gemm_mode", "lds_unet_get_gemm_mode",
     "lds_unet_set_latency_mode", "lds_unet_get_latency_mode", "lds_unet_forward_ragged", "lds_sampler_run_ragged", "lds_vocoder_forward_ragged",
-    "lds_vae_encoder_create", "lds_vae_encoder_destroy", "lds_vae_encoder_workspace_bytes", "lds_vae_encoder_forward"]
+    "lds_vae_encoder_create", "lds_vae_encoder_destroy", "lds_vae_encoder_workspace_bytes", "lds_vae_encoder_forward",
+    "lds_vae_encoder_forward_ragged"]
 # include/lds_test.h: single-op entry points for tests/ and tools/ (not part of the drop-in boundary)
 TEST_EXPORTS = [
     "lds_test_conv", "lds_test_dconv", "lds_bench_dconv", "lds_test_gn_apply", "lds_bench_gn_stream", "lds_test_gn_chain_k4p",
@@ -61,7 +62,7 @@ TEST_EXPORTS = [
     "lds_test_split_roundtrip", "lds_test_gn_apply_split", "lds_debug_set_split_rule", "lds_test_attention_f16math",
     "lds_test_attention_latency", "lds_debug_set_gn_fold", "lds_debug_set_voc_pair", "lds_debug_set_touch_weights", "lds_test_voc_pair", "lds_test_gn_fold_k4p", "lds_bench_dconv_alt", "lds_debug_fill_u32", "lds_debug_trace",
     "lds_debug_trace_count", "lds_debug_trace_get", "lds_debug_unet_plan", "lds_test_gn_fold_split", "lds_test_cluster_join", "lds_test_lm_sample",
-    "lds_test_conv_down"]
+    "lds_test_conv_down", "lds_test_conv_down_ragged"]
 
 
 def lib():
@@ -460,12 +461,21 @@ class VaeEncoder:
         check(lib().lds_vae_encoder_workspace_bytes(self.h, B, C.c_int64(L), C.byref(nb)))
         return nb.value
 
-    def forward(self, audio, noise=None, only_mean=False, ws=None):
+    @staticmethod
+    def lengths(lengths, B, L):
+        """per-clip sample counts of a ragged batch -> host int32 [B] (include/lds.h lds_vae_encoder_forward_ragged: B <= 64, 1 .. L)"""
+        if B > 64:
+            raise ValueError(f"a ragged encoder batch holds at most 64 clips (got {B})")
+        return UNet._lengths(lengths, B, L)
+
+    def forward(self, audio, noise=None, only_mean=False, ws=None, lengths=None):
         """audio [B,L] (L a multiple of the hop); noise [B,C,T] or None -> (out [B,T,2C], z [B,T,C] or None); `ws`: a caller's uint8
-        workspace of at least workspace_bytes(B, L) (tests poison it), else the handle's own"""
+        workspace of at least workspace_bytes(B, L) (tests poison it), else the handle's own; `lengths`: every clip's own sample count
+        (host ints, ragged batch: include/lds.h lds_vae_encoder_forward_ragged) or None"""
         import torch
         B, L = audio.shape
         T = L // self.hop
+        ln = self.lengths(lengths, B, L) if lengths is not None else None
         if noise is not None and tuple(noise.shape) != (B, self.C, T):
             raise ValueError(f"noise must be [B, C, T] = {[B, self.C, T]}, got {list(noise.shape)}")
         nb = self.workspace_bytes(B, L)
@@ -473,6 +483,12 @@ class VaeEncoder:
             ws = self.ws.get(nb, audio.device)
         out = torch.empty(B, T, 2 * self.C, dtype=torch.float32, device=audio.device)
         z = torch.empty(B, T, self.C, dtype=torch.float32, device=audio.device) if noise is not None else None
+        if ln is not None:
+            check(lib().lds_vae_encoder_forward_ragged(self.h, _dev(audio, torch.float32), C.c_void_p(ln.ctypes.data),
+                                                       _dev(noise, torch.float32) if noise is not None else None, _dev(out),
+                                                       _dev(z) if z is not None else None, int(bool(only_mean)), _dev(ws), C.c_size_t(ws.numel()), B,
+                                                       C.c_int64(L), _stream()))
+            return out, z
         check(lib().lds_vae_encoder_forward(self.h, _dev(audio, torch.float32), _dev(noise, torch.float32) if noise is not None else None,
                                             _dev(out), _dev(z) if z is not None else None, int(bool(only_mean)), _dev(ws),
                                             C.c_size_t(ws.numel()), B, C.c_int64(L), _stream()))
@@ -493,6 +509,28 @@ def conv_down(x, w, b, stride, slope=1.0, tile=0, cfg=None):
     buf = C.create_string_buffer(128)
     check(lib().lds_test_conv_down(_dev(x, torch.float32), C.c_void_p(w.ctypes.data), C.c_void_p(bb.ctypes.data) if bb is not None else None,
                                    Ci, Co, K, stride, T, B, C.c_float(slope), tile, _dev(out), buf, C.c_size_t(len(buf)), _stream()))
+    if cfg is not None:
+        cfg.append(buf.value.decode())
+    return out
+
+
+def conv_down_ragged(x, w, b, stride, lengths_in, lengths_out, slope=1.0, tile=0, cfg=None):
+    """conv_down over a ragged batch (lds_test_conv_down_ragged): x reads as zeros from lengths_in[b] on, the output is zeros from
+    lengths_out[b] on (host ints, B <= 64)"""
+    import torch
+    B, Ci, T = x.shape
+    w = np.ascontiguousarray(w, dtype=np.float32)
+    Co, _, K = w.shape
+    pad = (K - stride + 1) // 2
+    out = torch.empty(B, Co, (T + 2 * pad - K) // stride + 1, dtype=torch.float32, device=x.device)
+    bb = np.ascontiguousarray(b, dtype=np.float32) if b is not None else None
+    li = np.ascontiguousarray(lengths_in, dtype=np.int32)
+    lo = np.ascontiguousarray(lengths_out, dtype=np.int32)
+    assert li.shape == lo.shape == (B,)
+    buf = C.create_string_buffer(128)
+    check(lib().lds_test_conv_down_ragged(_dev(x, torch.float32), C.c_void_p(w.ctypes.data), C.c_void_p(bb.ctypes.data) if bb is not None else None,
+                                          Ci, Co, K, stride, T, B, C.c_float(slope), C.c_void_p(li.ctypes.data), C.c_void_p(lo.ctypes.data), tile,
+                                          _dev(out), buf, C.c_size_t(len(buf)), _stream()))
     if cfg is not None:
         cfg.append(buf.value.decode())
     return out

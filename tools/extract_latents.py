@@ -1,12 +1,13 @@
 """Encode a directory of float32 .npy waveforms to VAE latents (the reference's batch_proccessor/acoustic_extract.py flow).
 
-    python tools/extract_latents.py IN_DIR OUT_DIR --model pretrain/hifi-vaegan [--batch 16] [--only-mean]
+    python tools/extract_latents.py IN_DIR OUT_DIR --model pretrain/hifi-vaegan [--batch 16] [--only-mean] [--ragged]
 
 Every IN_DIR/<name>.npy (1-D float32 at the vocoder's sample rate) becomes OUT_DIR/<name>.npy of shape [ceil(len / hop), 2C]
 (m, then logs; zeros for logs with --only-mean).  Files are batched in sorted order and right-padded with zeros to the longest clip of
 their batch; each result is cropped to its own ceil(len / hop) frames afterwards.  That is the reference's own behaviour, and it means
 that a clip's last frames can depend on its batch: the encoder's receptive field reaches into the padding of the batch, so a shorter clip
-encoded with a longer one need not give the bits it gets alone (use --batch 1 for that).
+encoded with a longer one need not give what it gets alone.  With --ragged, each batch goes through Vocoder.extract_ragged with the clips'
+own lengths instead, and every clip's latent is the clip encoded alone (within float rounding), independent of its batch.
 """
 import argparse
 import math
@@ -28,6 +29,7 @@ def main():
     ap.add_argument("--model", required=True, help="directory with decoder.pth (config) and encoder.pth")
     ap.add_argument("--batch", type=int, default=16)
     ap.add_argument("--only-mean", action="store_true", help="write zeros for logs (reference extract(only_mean=True))")
+    ap.add_argument("--ragged", action="store_true", help="encode every clip as if alone (extract_ragged with the clips' own lengths)")
     a = ap.parse_args()
     voc = Vocoder("hifi-vaegan", a.model, device="cuda")
     hop = voc.vocoder_hop_size
@@ -40,7 +42,11 @@ def main():
         audio = np.zeros((len(clips), L), dtype=np.float32)
         for b, c in enumerate(clips):
             audio[b, :len(c)] = c
-        lat = voc.extract(torch.from_numpy(audio).cuda(), voc.vocoder_sample_rate, only_mean=a.only_mean).cpu().numpy()
+        x = torch.from_numpy(audio).cuda()
+        if a.ragged:
+            lat = voc.extract_ragged(x, voc.vocoder_sample_rate, [len(c) for c in clips], only_mean=a.only_mean).cpu().numpy()
+        else:
+            lat = voc.extract(x, voc.vocoder_sample_rate, only_mean=a.only_mean).cpu().numpy()
         for b, (f, c) in enumerate(zip(group, clips)):
             np.save(os.path.join(a.out_dir, f), lat[b, :math.ceil(len(c) / hop)])
         print(f"{i + len(group)} / {len(names)}")
