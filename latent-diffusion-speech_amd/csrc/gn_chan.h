@@ -1,6 +1,6 @@
-// Chan's parallel combination of (count, mean, M2) partials across a wave in a fixed order (DPP row shifts + row broadcasts): the way
-// every consumer of the GroupNorm partials [B][C/16][ceil(T/32)] combines them (gn_stream in k4p_ops.hip; the GroupNorm fold of
-// conv_dma / conv_bf3), so that all of them see the same statistics bit for bit.
+// The combination of (count, mean, M2) partials across a wave in a fixed order (DPP row shifts + row broadcasts): the way every consumer
+// of the GroupNorm partials [B][C/16][ceil(T/32)] combines them (gn_stream in k4p_ops.hip; the GroupNorm fold of conv_dma / conv_bf3),
+// so that all of them see the same statistics bit for bit.  Also LayerNorm's column statistics (ln_column_stats).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -10,35 +10,17 @@ template <int CTRL, int ROW_MASK, bool BOUND>
 static __device__ __forceinline__ float dpp_get(float v) {
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, ROW_MASK, 0xf, BOUND));
 }
-// an empty side (count 0) is the identity
-static __device__ __forceinline__ void chan(float& n, float& mean, float& m2, float nb, float mb, float qb) {
-    const float nn = n + nb;
-    const float r = (nn > 0.f) ? __builtin_amdgcn_rcpf(nn) : 0.f;      // counts are small integers: v_rcp_f32 is within 1 ulp
-    const float d = mb - mean;
-    mean += d * (nb * r);
-    m2 += qb + d * d * (n * nb * r);
-    n = nn;
-}
-template <int CTRL, int ROW_MASK, bool BOUND>
-static __device__ __forceinline__ void chan_step(float& n, float& mean, float& m2) {
-    // lanes outside ROW_MASK (and row starts with BOUND) receive zeros = an empty partial
-    // (the three values are complete, and two wait states have passed, before any lane reads them across the wave: the compiler may not weave
-    //  a step's arithmetic into the next step's cross-lane reads -- section 14 of DESIGN.md is about a schedule of this code that was not stable)
-    asm volatile("s_nop 1" : "+v"(n), "+v"(mean), "+v"(m2));
-    const float nb = dpp_get<CTRL, ROW_MASK, BOUND>(n), mb = dpp_get<CTRL, ROW_MASK, BOUND>(mean), qb = dpp_get<CTRL, ROW_MASK, BOUND>(m2);
-    chan(n, mean, m2, nb, mb, qb);
-}
-
 // (mean, variance) of group g of batch element b over all T frames, from the partials `gp` of a C-channel tensor; every lane of the
 // wave takes part, the result is wave-uniform.  cg16 = 16-channel blocks per group.  Two phases so that a caller can put other work
 // between the request and the use: gn_part_load = this lane's partial of round p0 (an empty one beyond the group's last),
-// gn_group_finish = the combination (further rounds are loaded there; P <= 64 partials -- every level of the UNet -- need none).
+// gnf_group_stats = the combination (further rounds are loaded there; P <= 64 partials -- every level of the UNet at T <= 1024 -- need none).
 struct GnPart { float n, mean, m2; };
 // Tv: valid frames of this batch element (ragged batches; = T otherwise): blocks beyond it are empty partials whatever the buffer holds.
-// The load itself is UNCONDITIONAL (an out-of-range lane reads the group's first partial, a valid address) and only the count carries the mask:
+// The load itself is UNCONDITIONAL (an out-of-range lane reads the group's first partial, a valid address) and the mask is applied to the values:
 // a load inside a divergent branch is waited for at the end of that branch, and the fold's kernels want these requests in flight across the
 // issue of their first operand tiles (round 4: the ISA of the folded proj_in showed `s_waitcnt vmcnt(0)` right behind each request).  An
-// empty partial is n = 0 with a finite (mean, M2) that every consumer multiplies by its count or masks by it.
+// empty partial is (0, 0, 0): in a ragged batch, the partials of blocks past an utterance's length were never written and hold whatever the
+// workspace held (NaN included), and 0 * NaN is NaN in every consumer's n * mean.
 static __device__ __forceinline__ GnPart gn_part_load(const float2* __restrict__ gp, int b, int C, int T, int cg16, int g, int lane, int p0, int Tv) {
     const int nT = (T + 31) >> 5, P = cg16 * nT;
     const int pi = p0 + lane;
@@ -47,30 +29,12 @@ static __device__ __forceinline__ GnPart gn_part_load(const float2* __restrict__
     const int kk = (int)(((float)pc + 0.5f) * (1.0f / (float)nT)), tb = pc - kk * nT, kb = g * cg16 + kk;      // pc / nT without the integer-division sequence
     const int nv = (Tv - tb * 32 < 32) ? Tv - tb * 32 : 32;
     const float2 pr = gp[((long long)b * (C >> 4) + kb) * nT + tb];
+    const bool ok = in && nv > 0;      // (selects on the loaded values: the load stays unconditional)
     GnPart r;
-    r.n = (in && nv > 0) ? 16.0f * (float)nv : 0.f;
-    r.mean = pr.x; r.m2 = pr.y;
+    r.n = ok ? 16.0f * (float)nv : 0.f;
+    r.mean = ok ? pr.x : 0.f; r.m2 = ok ? pr.y : 0.f;
     return r;
 }
-static __device__ __forceinline__ void gn_group_finish(const float2* __restrict__ gp, int b, int C, int T, int cg16, int g, int lane, GnPart first, float& mu, float& var, int Tv) {
-    const int nT = (T + 31) >> 5, P = cg16 * nT;
-    float n = 0.f, mean = 0.f, m2 = 0.f;
-    chan(n, mean, m2, first.n, first.mean, (first.n > 0.f) ? first.m2 : 0.f);      // (an empty partial's M2 is whatever its clamped load returned)
-    for (int p0 = 64; p0 < P; p0 += 64) {
-        const GnPart q = gn_part_load(gp, b, C, T, cg16, g, lane, p0, Tv);
-        chan(n, mean, m2, q.n, q.mean, (q.n > 0.f) ? q.m2 : 0.f);
-    }
-    chan_step<0x111, 0xf, true>(n, mean, m2);
-    chan_step<0x112, 0xf, true>(n, mean, m2);
-    chan_step<0x114, 0xf, true>(n, mean, m2);
-    chan_step<0x118, 0xf, true>(n, mean, m2);
-    chan_step<0x142, 0xa, false>(n, mean, m2);
-    chan_step<0x143, 0xc, false>(n, mean, m2);
-    mu = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, mean), 63));
-    var = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, m2), 63)) /
-          __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, n), 63));
-}
-
 // ---- the GroupNorm FOLD's statistics (conv_dma.hip / conv_bf3.hip gnf_prepare) -----------------------------------------------------------
 // The same (mean, variance) from the same partials, combined as two plain wave sums instead of a Chan tree:
 //     mean = sum_i n_i mean_i / N,      var = sum_i (M2_i + n_i (mean_i - mean)^2) / N,      N = 16 cg16 Tv  (known without a reduction)

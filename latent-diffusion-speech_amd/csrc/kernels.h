@@ -79,8 +79,8 @@ hipError_t launch_vae_head(const float* y, const float* noise, float* out, float
 
 // voc_pair (voc_pair.hip): one residual step of the vocoder's ResBlock1 at 16 / 32 channels as one launch over plain [B][C][T] tensors:
 // out = (accum ? out : 0) + c2(lrelu(c1(lrelu(x)))) + x, divided by out_div; c1 dilated by `dil`, both k = KT, "same" zero padding;
-// frames at and beyond vlen[b] (device int32 [B], null = T) are outside the utterance: the intermediate reads as zero there and the
-// output is written as zeros.  x and out must not alias (neighbouring tiles read x's halo).
+// frames at and beyond vlen[b] (device int32 [B], null = T) are outside the utterance: x and the intermediate read as zero there (whatever
+// x holds) and the output is written as zeros.  x and out must not alias (neighbouring tiles read x's halo).
 struct VocPairArgs {
     const float* x; float* out;
     const float* w1; const float* b1; int Mp1;      // packed weights [KT][C/8][2][Mp][4] and packed-row biases (model.hip pack_conv)

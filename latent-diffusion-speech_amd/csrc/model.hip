@@ -2286,8 +2286,6 @@ static int vae_encoder_forward_impl(lds_vae_encoder* e, const float* audio, cons
         LDS_TRY(run_down(d, x, Tl, 0.1f, xs, B, st, 0, vl[i + 1], vlen));      // x = ups[i](leaky_relu(x, 0.1))
         { float* t = x; x = xs; xs = t; }
         Tl /= d.stride;
-        // (ragged: the narrow stage's voc_pair masks its input window by Tl, not by vlen; it relies on conv_down above having stored
-        // zeros beyond vlen, and on each residual step doing the same for the next)
         if (voc_dma_stage(e, d.Co)) LDS_TRY(voc_mrf_dma(e, w.v, (int)i, x, xs, d.Co, (int)Tl, B, st, vlen));
         else LDS_TRY(voc_mrf_plain(e, w.v, (int)i, x, xs, d.Co, (int)Tl, B, st, vlen));
         { float* t = x; x = xs; xs = t; }

@@ -167,12 +167,14 @@ __global__ void __launch_bounds__(256, (PairCfg<C, KT, DIL>::OCC)) voc_pair_kern
         }
     }
     f32x4 xr[NCH];
-    auto fetch = [&](int tile) {          // window chunks of this thread, all issued together; zeros outside [0, T)
+    auto fetch = [&](int tile) {          // window chunks of this thread, all issued together; zeros outside [0, Tv)
         const int b = tile / nt, t0 = (tile - b * nt) * N;
         const float* xb = p.x + (long long)b * C * T;
         const int s0 = t0 - H1 - H0;
         const int s_al = (s0 >= 0) ? (s0 & ~3) : -(((-s0) + 3) & ~3);
-        const bool inner = s_al >= 0 && s_al + 4 * W4 <= T;      // (wave-uniform) the whole window is inside the row
+        // ragged batch: the input past the utterance's length is read as zeros, whatever the tensor holds there
+        const int Tv = p.vlen ? (p.vlen[b] < T ? p.vlen[b] : T) : T;
+        const bool inner = s_al >= 0 && s_al + 4 * W4 <= Tv;      // (wave-uniform) the whole window is inside the utterance
 #pragma unroll
         for (int i = 0; i < NCH; ++i) {
             int ci, c4; unsigned lo;
@@ -182,16 +184,17 @@ __global__ void __launch_bounds__(256, (PairCfg<C, KT, DIL>::OCC)) voc_pair_kern
             if constexpr (vec) {
                 if (inner) {
                     xr[i] = *reinterpret_cast<const f32x4*>(xb + (live ? ci * T + s : 0));
-                } else {
-                    const bool in = live && s >= 0 && s < T;
+                } else {      // (boundary tiles only; a chunk may straddle Tv, which need not be a multiple of 4)
+                    const bool in = live && s >= 0 && s < Tv;
                     const f32x4 v = *reinterpret_cast<const f32x4*>(xb + (in ? ci * T + s : 0));
-                    xr[i] = in ? v : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) xr[i][e] = (in && s + e < Tv) ? v[e] : 0.f;
                 }
             } else {
                 f32x4 v = {0.f, 0.f, 0.f, 0.f};
                 if (live) {
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = (s + e >= 0 && s + e < T) ? xb[ci * T + s + e] : 0.f;
+                    for (int e = 0; e < 4; ++e) v[e] = (s + e >= 0 && s + e < Tv) ? xb[ci * T + s + e] : 0.f;
                 }
                 xr[i] = v;
             }

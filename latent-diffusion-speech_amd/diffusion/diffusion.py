@@ -308,6 +308,7 @@ class GaussianDiffusion(nn.Module):
         # x.squeeze(1).transpose(1, 2) / acoustic_scale  (reference diffusion.py:342-343)
         mel = native.transpose(x, float(self.acoustic_scale))
         if lengths is not None:      # the sampler's state beyond an utterance's length is the scaled start noise: not part of the result
+            # (a select, not a product with a 0/1 mask: a caller's x_T may hold NaN or Inf there)
             ln = torch.as_tensor(lengths, device=mel.device).reshape(-1, 1)
-            mel = mel * (torch.arange(mel.shape[1], device=mel.device)[None, :] < ln)[:, :, None]
+            mel = mel.masked_fill((torch.arange(mel.shape[1], device=mel.device)[None, :] >= ln)[:, :, None], 0.0)
         return mel

@@ -417,6 +417,12 @@ class Generator:
             _lib.lds_vocoder_destroy(self.h)
             self.h = None
 
+    def workspace_tensor(self, B, T, device):
+        """the caller-owned scratch a forward of this size on the current stream will use (tests poison it)"""
+        nb = C.c_size_t()
+        check(lib().lds_vocoder_workspace_bytes(self.h, B, T, C.byref(nb)))
+        return self.ws.get(nb.value, device)
+
     def forward(self, z, lengths=None):
         """z [B,C,T] -> wav [B,1,T*hop]; lengths: the utterances' own frame counts (ragged batch, include/lds.h lds_vocoder_forward_ragged)"""
         import torch

@@ -232,7 +232,8 @@ def test_vocoder_resblock_step_dma(C, T, K, dil, mode, B):
 def test_vocoder_resblock_step_fused(C, T, K, dil, B, acc, ragged):
     """one residual step of ResBlock1 at the vocoder's 16- / 32-channel stages as ONE launch (csrc/voc_pair.hip: c1 -> LDS -> c2, frames as the
     MFMA rows) against the numpy oracle: several tiles per utterance, last tiles ragged, T not a multiple of 4 (the scalar-access instantiation),
-    T shorter than one tile, the running-sum epilogue, and per-utterance lengths (the intermediate is ZERO beyond an utterance's end, the output too)"""
+    T shorter than one tile, the running-sum epilogue, and per-utterance lengths (the intermediate is ZERO beyond an utterance's end, the output too,
+    and the input there is never read)"""
     _need_gpu()
     from lds import native
     from oracle import unet1d
@@ -259,19 +260,32 @@ def test_vocoder_resblock_step_fused(C, T, K, dil, B, acc, ragged):
     if ragged:
         for b in range(B):
             xin[b, :, lens[b]:] = 0          # (the producer of a ragged batch writes zeros beyond each utterance)
-    out = torch.full((B, C, T), float("nan"), dtype=torch.float32, device="cuda")
-    dx, dacc = dev(xin), dev(a)
-    native.check(native.lib().lds_test_voc_pair(ct.c_void_p(dx.data_ptr()), ct.c_void_p(w1.ctypes.data), ct.c_void_p(b1.ctypes.data), ct.c_void_p(w2.ctypes.data),
-                                                ct.c_void_p(b2.ctypes.data), C, T, K, dil, ct.c_void_p(dacc.data_ptr() if acc else None),
-                                                ct.c_float(3.0 if acc else 1.0), ct.c_void_p(lens.ctypes.data if ragged else None),
-                                                ct.c_void_p(out.data_ptr()), B, ct.c_void_p(torch.cuda.current_stream().cuda_stream)))
-    torch.cuda.synchronize()
-    got = out.cpu().numpy()
+    dacc = dev(a)
+
+    def run(xa):
+        out = torch.full((B, C, T), float("nan"), dtype=torch.float32, device="cuda")
+        dx = dev(xa)
+        native.check(native.lib().lds_test_voc_pair(ct.c_void_p(dx.data_ptr()), ct.c_void_p(w1.ctypes.data), ct.c_void_p(b1.ctypes.data), ct.c_void_p(w2.ctypes.data),
+                                                    ct.c_void_p(b2.ctypes.data), C, T, K, dil, ct.c_void_p(dacc.data_ptr() if acc else None),
+                                                    ct.c_float(3.0 if acc else 1.0), ct.c_void_p(lens.ctypes.data if ragged else None),
+                                                    ct.c_void_p(out.data_ptr()), B, ct.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        torch.cuda.synchronize()
+        return out.cpu().numpy()
+    got = run(xin)
     assert np.isfinite(got).all()
     if ragged:
         for b in range(B):
             assert not got[b, :, lens[b]:].any(), "frames beyond an utterance's length must be written as zeros"
     assert relmax(got, ref) < 2e-5, relmax(got, ref)
+    if ragged:      # the input beyond each length is never read: NaN, +-Inf and +-1e30 there give the zero-padded run's bits, inside and beyond
+        xp = x.copy()
+        for b in range(B):
+            g = np.where(U(tag + f".g{b}", (C, T - lens[b])) < 0, np.float32(-1e30), np.float32(1e30)).astype(np.float32).reshape(-1)
+            g[::7] = np.nan
+            g[3::11] = np.inf
+            g[5::13] = -np.inf
+            xp[b, :, lens[b]:] = g.reshape(C, T - lens[b])
+        assert np.array_equal(run(xp), got), "the input beyond an utterance's length changed the result"
 
 
 def test_vocoder_fused_steps_equal_two_launch_steps():
