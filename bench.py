@@ -15,11 +15,15 @@ itself -- a child `python -m torch.distributed.run ...` created before this proc
 checks that the line it gets back says n_gpus = N and exits non-zero otherwise: an N-GPU request can
 never silently measure one GPU.  --workload: sampler (configs[1] / [2]: the headline), e2e (configs[3]:
 + HiFi-VAEGAN decode, waveform gathered), full_tts (configs[4]: phones -> RoFormer generate -> codebook ->
-sampler -> vocoder, 8 utterances per GPU).  At N = 1 the sampler line also carries `extra` legs (untimed
-for `value`): configs[3] with the vocoder, the per-GPU share of configs[2] (UniPC, 20 NFE), the B = 1
-latency of the caller north_star names (22_infer_tts.py), and `split_f16`: the same configs[1] step with
-every UNet GEMM on the opt-in two-fp16-term path (csrc/conv_bf3.hip; 22-bit operands, narrower than the
-reference's fp32), reported next to -- never as -- the exact-fp32 `value`.
+sampler -> vocoder, 8 utterances per GPU).
+
+A plain run does only what `value` needs: set-up, the W warm-up and K timed steps, --dump-outputs, the result
+line.  `--full` adds what the headline figure does not need (full_legs): one instrumented step for `roofline`
+and `kernel_breakdown_ms`, and at N = 1 the `cpu_baseline` (numpy oracle on the host) and, for the sampler,
+the `extra` legs (untimed for `value`): configs[3] with the vocoder, the per-GPU share of configs[2] (UniPC,
+20 NFE), the B = 1 latency of the caller north_star names (22_infer_tts.py), and `split_f16`: the same
+configs[1] step with every UNet GEMM on the opt-in two-fp16-term path (csrc/conv_bf3.hip; 22-bit operands,
+narrower than the reference's fp32), reported next to -- never as -- the exact-fp32 `value`.
 
 Every timed step seeds the global generator (the sampler's start noise), so the same arguments compute the same outputs run after run;
 `--dump-outputs DIR` writes those of the last timed step as DIR/mel.npy (and DIR/wav.npy where the workload has a vocoder), so two builds
@@ -369,16 +373,16 @@ def run_job(args, rank, world, dev, model=None, voc=None, dist=None, sync=None, 
                    "parallelism": f"batch-shard x{world}", "gathered": sorted(outs.keys()) if rank == 0 else None},
         "x_realtime": value * FRAME_SEC, "rtf": 1.0 / (value * FRAME_SEC),
         "mel_frames_per_sec_per_gpu": value / world,
+        "unet_algorithmic_tflops": (UNET_GFLOP_PER_UTT_FWD * B * args.nfe * 1e9 / (dt / args.steps) / 1e12) if T == 512 else None,
     }
     if rank != 0:
         return None
     if dumped is not None:
         res["dumped_outputs"] = {"dir": os.path.abspath(args.dump_outputs), "arrays": dumped}
     if profiler is not None:
-        # roofline leg: one extra instrumented step on rank 0 ONLY, so it must not contain a collective (gather=False)
+        # roofline leg (--full): one extra instrumented step on rank 0 ONLY, so it must not contain a collective (gather=False)
         prof = profiler.run(lambda: step(gather=False))
         res["roofline"], res["kernel_breakdown_ms"] = roofline_from_profile(prof)
-        res["unet_algorithmic_tflops"] = (UNET_GFLOP_PER_UTT_FWD * B * args.nfe * 1e9 / (dt / args.steps) / 1e12) if T == 512 else None
     return res
 
 
@@ -635,13 +639,17 @@ def parse_args(argv=None):
     ap.add_argument("--frames", type=int, default=512)
     ap.add_argument("--nfe", type=int, default=50)
     ap.add_argument("--method", default="dpm-solver")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run what the headline figure does not need: the instrumented roofline step, and at N=1 "
+                         "the CPU baseline and (sampler workload) the extra legs; a plain run does none of them")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-nfe", type=int, default=8)
     ap.add_argument("--vocoder", action="store_true", help="same as --workload e2e")
-    ap.add_argument("--no-extras", action="store_true", help="skip the extra legs (split-bf16, configs[3], UniPC-20, B=1 latency, configs[4] share) at N=1")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: skip the extra legs (split-f16, configs[3], UniPC-20, B=1 latency, configs[5] share, ragged batch) at N=1")
     ap.add_argument("--rehearse-rccl", action="store_true",
                     help="N=1 only: open a single-rank RCCL process group and issue every collective of the N>1 path (scatter, gather, barrier, all-reduce)")
-    ap.add_argument("--no-profile", action="store_true", help="skip the instrumented roofline step (for rocprofv3 --pmc passes)")
+    ap.add_argument("--no-profile", action="store_true", help="with --full: skip the instrumented roofline step")
     ap.add_argument("--stub-cpu", action="store_true",
                     help="tests only: gloo ranks on the CPU with stand-in models (exercises the launcher / scatter / gather / JSON plumbing without a GPU)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
@@ -657,6 +665,22 @@ def parse_args(argv=None):
     if args.batch is None:
         args.batch = 8 if args.workload == "full_tts" else 16
     return args
+
+
+def full_legs(args, world):
+    """what this run measures beyond the timed steps: nothing without --full; with it the instrumented roofline step ("roofline"), and at N = 1
+    the CPU baseline ("cpu_baseline") and, for the sampler workload, the extra legs ("extra"), each unless its --no-* option says otherwise.
+    --stub-cpu has no device to instrument and no model for the legs: nothing."""
+    if not args.full or args.stub_cpu:
+        return set()
+    legs = set()
+    if not args.no_profile:
+        legs.add("roofline")
+    if world == 1 and not args.no_extras and args.workload == "sampler":
+        legs.add("extra")
+    if world == 1 and not args.no_cpu_baseline:
+        legs.add("cpu_baseline")
+    return legs
 
 
 def spawn_ranks(args, argv):
@@ -804,15 +828,16 @@ def main(argv=None):
         smax = torch.tensor([setup_s], device=dev, dtype=torch.float64)
         dist.all_reduce(smax, op=dist.ReduceOp.MAX)
         setup_s = float(smax.item())
-    profiler = None if (args.no_profile or args.stub_cpu) else NativeProfiler()
+    legs = full_legs(args, world)
+    profiler = NativeProfiler() if "roofline" in legs else None
     res = run_job(args, rank, world, dev, dist=dist, sync=sync, profiler=profiler, pipeline=pipe)
     if rank == 0:
         # set-up per rank (max over ranks): weights generated on rank 0 and broadcast, packed on every rank, uploaded; not part of `value`
         res["setup_s"] = setup_s
         res["weights_broadcast_bytes"] = getattr(args, "weights_broadcast_bytes", 0)
-        if world == 1 and not args.no_extras and not args.stub_cpu and args.workload == "sampler":
+        if "extra" in legs:
             res["extra"] = extra_legs(args, dev, model, make_inputs)
-        if not args.no_cpu_baseline and world == 1 and not args.stub_cpu:      # reported on rank 0 at N = 1 only
+        if "cpu_baseline" in legs:      # reported on rank 0 at N = 1 only
             res["cpu_baseline"] = cpu_baseline(args.frames, args.cpu_nfe)
         print(json.dumps(res), flush=True)
     if dist is not None:

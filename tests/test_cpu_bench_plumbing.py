@@ -164,3 +164,29 @@ def test_bench_main_refuses_a_world_size_mismatch():
                         env_extra={"WORLD_SIZE": "1", "RANK": "0", "LOCAL_RANK": "0"})
     assert p.returncode != 0 and res is None
     assert "--gpus 2 but WORLD_SIZE=1" in p.stderr
+
+
+def test_plain_run_measures_only_the_timed_steps():
+    """without --full the run adds nothing to the timed steps (no roofline step, no extra legs, no CPU baseline) for any workload or
+    world size; --full adds each at the world sizes and workloads it applies to, and each --no-* option takes its own leg away"""
+    from bench import full_legs, parse_args
+    for workload in ("sampler", "e2e", "full_tts"):
+        for world in (1, 2):
+            assert full_legs(parse_args(["--gpus", str(world), "--workload", workload]), world) == set()
+            assert full_legs(parse_args(["--gpus", str(world), "--workload", workload, "--no-profile"]), world) == set()
+    assert full_legs(parse_args(["--full"]), 1) == {"roofline", "extra", "cpu_baseline"}
+    assert full_legs(parse_args(["--full", "--workload", "e2e"]), 1) == {"roofline", "cpu_baseline"}
+    assert full_legs(parse_args(["--full", "--gpus", "2"]), 2) == {"roofline"}
+    assert full_legs(parse_args(["--full", "--no-profile"]), 1) == {"extra", "cpu_baseline"}
+    assert full_legs(parse_args(["--full", "--no-extras"]), 1) == {"roofline", "cpu_baseline"}
+    assert full_legs(parse_args(["--full", "--no-cpu-baseline"]), 1) == {"roofline", "extra"}
+    assert full_legs(parse_args(["--full", "--stub-cpu"]), 1) == set()
+
+
+def test_bench_full_stub_run_prints_one_line():
+    """--full goes through the same launcher and result line (--stub-cpu: no device leg to add)"""
+    p, res = _run_bench(["--gpus", "2", "--stub-cpu", "--full", "--steps", "2", "--warmup", "1", "--batch", "3", "--frames", "8"])
+    assert p.returncode == 0, p.stderr[-2000:]
+    assert len([ln for ln in p.stdout.splitlines() if ln.startswith("{")]) == 1
+    assert res["n_gpus"] == 2 and res["steps"] == 2 and res["value"] > 0
+    assert not {"roofline", "extra", "cpu_baseline"} & set(res)

@@ -9,7 +9,7 @@ tag=${1:-rXX}
 out=gpurun_out/prof_$tag
 mkdir -p $out
 export TMPDIR=/tmp
-common="--steps 1 --warmup 1 --no-extras --no-cpu-baseline"
+common="--full --steps 1 --warmup 1 --no-extras --no-cpu-baseline"      # --full: the instrumented roofline step too
 echo "[1/4] kernel trace" && rocprofv3 --kernel-trace --stats --output-format csv -d $out/ks -o ks -- python3 bench.py $common > $out/bench_under_rocprof.json 2> $out/ks.err || exit 1
 cp $(find $out/ks -name "*kernel_stats.csv" | head -1) $out/kernel_stats.csv
 pmc="--nfe 5 --steps 1 --warmup 0 --no-extras --no-cpu-baseline --no-profile"
