@@ -224,6 +224,30 @@ int lds_lm_generate(lds_lm* lm, const float* enc, const int32_t* enc_len, int B,
                     float temperature, float repetition_penalty, const float* uniforms, int64_t* tokens, float* logits_out, int* n_tokens_host,
                     void* ws, size_t ws_bytes, void* stream);
 
+/* Decode options of lds_lm_generate_opts (HF GenerationConfig fields of reference roformer.py:216-227).
+ *   num_beams 1: greedy (do_sample 0) or sampling as lds_lm_generate.  no_repeat_ngram_size n >= 1 adds HF's NoRepeatNGramLogitsProcessor
+ *     between the repetition penalty and the temperature: a token that would complete an n-gram already in the sequence (BOS included)
+ *     gets -inf; nothing is banned while the sequence is shorter than n.  0 = off (lds_lm_generate's kernels, bit for bit).
+ *   num_beams 2 .. 8 with do_sample 0: HF's greedy beam search (_beam_search, length_penalty 1): log_softmax -> repetition penalty (on the
+ *     log-probabilities) -> n-gram ban (each beam's own history) -> + running score -> top 2K of K * vocab (ties: the lower index beam * vocab
+ *     + token) -> running beams and finished hypotheses with HF's -1e9 masks as fp32 additions -> early-stop heuristic.  early_stopping:
+ *     1 = True (the reference's default), 0 = False, 2 = "never".  The result is each item's best finished hypothesis, cropped to the longest
+ *     of them: BOS first, EOS kept, PAD after it.  Not built (LDS_EINVAL): beam sampling (num_beams > 1 with do_sample), logits_out with
+ *     num_beams > 1.  Beam search limits: vocabularies of at most 4352 entries, max_length <= 8000.  top_k, top_p, temperature are read
+ *     only when do_sample is set. */
+typedef struct {
+    int do_sample, top_k;
+    float top_p, temperature, repetition_penalty;
+    int no_repeat_ngram_size, num_beams, early_stopping;
+} lds_lm_decode_opts;
+/* workspace of lds_lm_generate_opts: num_beams * B decode rows (the cross-attention keys / values stay one set per item) plus the beam state */
+int lds_lm_workspace_bytes_opts(const lds_lm* lm, int B, int L, int max_length, int num_beams, size_t* out);
+/* lds_lm_generate with lds_lm_decode_opts (arguments as there; enc, enc_len one row per batch item, also with beams).  A bad option gives
+ * LDS_EINVAL before anything is enqueued (the option checks come first and need no handle).  Beam search keeps the decode loop on the
+ * stream as well: the synchronisation every 8 steps reads the search's per-step flags instead of the EOS flags. */
+int lds_lm_generate_opts(lds_lm* lm, const float* enc, const int32_t* enc_len, int B, int L, int max_length, const lds_lm_decode_opts* opts,
+                         const float* uniforms, int64_t* tokens, float* logits_out, int* n_tokens_host, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- per-launch HIP-event timing for bench.py's roofline leg (off by default) ------------------
  * lds_prof_enable(1) clears and starts recording one event pair per kernel launch on the launch
  * stream; lds_prof_summary synchronises them and writes a JSON list of

@@ -131,6 +131,16 @@ int lds_test_gn_apply_bf3(const float* x1, const float* x2, int C1, int C2, int 
  * penalty looks at); uniforms [B] (dev); out [B] int64 (dev).  top_k 0 = no top-k filter (HF: None / 0), else 1 .. 64 with ties of the k-th kept. */
 int lds_test_lm_sample(const float* logits, int B, int V, int do_sample, int top_k, float top_p, float temperature, float repetition_penalty,
                        const float* uniforms, const int64_t* hist, int n_hist, int64_t* out, void* stream);
+/* ONE step of lds_lm_generate_opts' beam search on logits [B * K][V] (dev) and the state of HF's _beam_search (all dev): running sequences
+ * [B * K][max_length] int64 (the first cur_len ids are the history) and scores [B * K]; finished hypotheses [B * K][max_length], scores,
+ * is_sent_finished flags and generated lengths [B * K]; is_early_stop_heuristic_unsatisfied [B].  Writes the same state after the step,
+ * parent_out [B * K] (parent beam 0 .. K - 1 of every new running beam) and flag_out [1] (1: some item may improve, 2: some item has an
+ * unfinished hypothesis slot, 4: some candidate did not hit the stopping criteria).  2 K <= V <= 4352, 1 <= cur_len < max_length. */
+int lds_test_lm_beam_step(const float* logits, int B, int K, int V, int cur_len, int max_length, int eos, float repetition_penalty,
+                          int no_repeat_ngram_size, int early_stopping, const int64_t* run_seq, const float* run_score, const int64_t* fin_seq,
+                          const float* fin_score, const int32_t* fin_flag, const int32_t* fin_len, const int32_t* unsat, int64_t* run_seq_out,
+                          float* run_score_out, int32_t* parent_out, int64_t* fin_seq_out, float* fin_score_out, int32_t* fin_flag_out,
+                          int32_t* fin_len_out, int32_t* unsat_out, int32_t* flag_out, void* stream);
 
 /* ---- debugging aids (tests/test_gpu_poison.py, tools/diag_trace.py) ----------------------------------------------------------
  * lds_debug_fill_u32: every 32-bit word of a device buffer = pattern.  Tests fill a caller workspace with NaN patterns (0x7fc07fc0 is a NaN

@@ -27,6 +27,8 @@ def parse_args(argv=None):
     ap.add_argument("-lm", "--language_model", help="exp/lm/model_<step>.pt ({'model': Roformer.state_dict()}) with config.yaml next to it")
     ap.add_argument("-p", "--phones", help=".npy int array [2, L]: phone ids and tone ids (text_to_sequence output); tokens come from the LM")
     ap.add_argument("--max_length", type=int, default=1024)
+    ap.add_argument("--num_beams", type=int, default=1, help="> 1: greedy beam search over the semantic tokens instead of top-k sampling (2 .. 8)")
+    ap.add_argument("--no_repeat_ngram_size", type=int, default=0, help="n >= 1: no n-gram of semantic tokens repeats (HF NoRepeatNGramLogitsProcessor)")
     ap.add_argument("-o", "--output", default="output.npy")
     ap.add_argument("-id", "--spk_id", type=int, default=1)
     ap.add_argument("-s", "--speedup", type=int, default=10)
@@ -87,11 +89,13 @@ def load_lm(path, dev):
     return lm.eval()
 
 
-def text2semantic(lm, phones, tones, spk_id=1, max_length=1024):
-    """22_infer_tts.py:76-104: sample the semantic tokens (top-k 5, temperature 1) and strip BOS / EOS.  phones, tones [B,L] int64."""
+def text2semantic(lm, phones, tones, spk_id=1, max_length=1024, num_beams=1, no_repeat_ngram_size=0):
+    """22_infer_tts.py:76-104: sample the semantic tokens (top-k 5, temperature 1) and strip BOS / EOS.  phones, tones [B,L] int64.
+    num_beams > 1: greedy beam search instead of sampling; no_repeat_ngram_size n >= 1: no n-gram repeats (either decode)."""
     spk = torch.ones_like(phones) * spk_id
-    tok = lm.generate(phones, tones, attention_mask=None, use_cache=None, max_length=max_length, do_sample=True, temperature=1.0, top_k=5, top_p=1.0,
-                      repetition_penalty=1.0, num_beams=1, no_repeat_ngram_size=0, early_stopping=True, spk_id=spk, end_gate_threshold=None)
+    tok = lm.generate(phones, tones, attention_mask=None, use_cache=None, max_length=max_length, do_sample=num_beams == 1, temperature=1.0, top_k=5,
+                      top_p=1.0, repetition_penalty=1.0, num_beams=num_beams, no_repeat_ngram_size=no_repeat_ngram_size, early_stopping=True, spk_id=spk,
+                      end_gate_threshold=None)
     # reference 22_infer_tts.py:100-103 (`if semantic_token[:, -1] == eos`: written for one utterance; on a batch that line itself raises).
     # The batched counterpart: every row ending with its EOS at the same step is stripped like the single row; rows that all ran to max_length
     # come back whole; rows that ended at DIFFERENT steps (EOS / PAD ids inside the result) cannot be one rectangular tensor.
@@ -105,18 +109,20 @@ def text2semantic(lm, phones, tones, spk_id=1, max_length=1024):
     return tok[:, 1:]
 
 
-def text2semantic_rows(lm, phones, tones, spk_id=1, max_length=1024, phone_lengths=None):
+def text2semantic_rows(lm, phones, tones, spk_id=1, max_length=1024, phone_lengths=None, num_beams=1, no_repeat_ngram_size=0):
     """A batch of sentences of DIFFERENT lengths (BASELINE configs[4]: 64 sentences per call).  phones / tones [B,L] right-padded,
     phone_lengths [B] (None = all L): the padding mask goes through the encoder and the cross-attention (reference roformer.py:209-236).
     Returns one 1-D token tensor per row: BOS stripped, cut before the row's first EOS (rows that finish early are padded by generate;
-    the ids EOS = kmeans_num + 1 and PAD = kmeans_num + 2 have no codebook row and must never reach the unit lookup)."""
+    the ids EOS = kmeans_num + 1 and PAD = kmeans_num + 2 have no codebook row and must never reach the unit lookup).  num_beams and
+    no_repeat_ngram_size as in text2semantic."""
     B, L = phones.shape
     mask = None
     if phone_lengths is not None:
         mask = (torch.arange(L, device=phones.device)[None] < torch.as_tensor(phone_lengths, device=phones.device)[:, None]).to(torch.int64)
     spk = torch.ones_like(phones) * spk_id
-    tok = lm.generate(phones, tones, attention_mask=mask, use_cache=None, max_length=max_length, do_sample=True, temperature=1.0, top_k=5, top_p=1.0,
-                      repetition_penalty=1.0, num_beams=1, no_repeat_ngram_size=0, early_stopping=True, spk_id=spk, end_gate_threshold=None)
+    tok = lm.generate(phones, tones, attention_mask=mask, use_cache=None, max_length=max_length, do_sample=num_beams == 1, temperature=1.0, top_k=5,
+                      top_p=1.0, repetition_penalty=1.0, num_beams=num_beams, no_repeat_ngram_size=no_repeat_ngram_size, early_stopping=True, spk_id=spk,
+                      end_gate_threshold=None)
     tok = tok[:, 1:].cpu()
     rows = []
     for b in range(B):
@@ -305,7 +311,7 @@ def main(argv=None):
         if lm is None:
             raise SystemExit("--phones needs --language_model (or --synthetic)")
         pt = torch.from_numpy(np.load(a.phones).astype(np.int64)).to(dev)
-        tokens = text2semantic(lm, pt[0:1], pt[1:2], a.spk_id, a.max_length)
+        tokens = text2semantic(lm, pt[0:1], pt[1:2], a.spk_id, a.max_length, a.num_beams, a.no_repeat_ngram_size)
         tokens = tokens.clamp(max=codebook.shape[0] - 1)      # pad ids of finished rows (batch > 1) have no codebook row
     _, _, wav = synthesize(svc, codebook, tokens, a.spk_id, a.speedup, a.method, a.scale_factor)
     wav = wav[0, 0].cpu().numpy()

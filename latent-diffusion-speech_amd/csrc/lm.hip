@@ -295,15 +295,21 @@ __global__ void __launch_bounds__(256) lm_kv_pack_kernel(const float* __restrict
 //      the causal context, the encoder is bidirectional).  q [N][ldq] (head slice at hd*d), out [N][H].  The four waves take alternate
 //      64-key blocks; inside a wave, phase 1 has one key per lane (scores), phase 2 one output channel per lane with the two half-waves on
 //      alternate keys; the waves' (max, sum, partial output) meet through LDS in a fixed order.  d <= 32. ----
-__global__ void __launch_bounds__(256) lm_attn_kernel(const float* __restrict__ q, int ldq, const float* __restrict__ kc, const float* __restrict__ vc, int cap,
-                                                      int Lq, int Lk_all, const int* __restrict__ klen, int H, int heads, float* __restrict__ out) {
-    extern __shared__ float sc[];                      // [Lk rounded to 64] scores, then 4 x (max, sum, acc[32])
+// BEAM (lm_attn_beam_kernel, beam-search decode, Lq = 1): cache rows are beam rows.  src != null (self-attention): key p < Lk - 1 of row n
+// lives in cache row src[n * src_cap + p] (the beam's ancestry, see lm_beam_step_kernel), the last key in row n itself.  group: rows per
+// batch item of the cross-attention's keys / values and klen (b = n / group).  The source rows ride along the scores in LDS.
+template <bool BEAM>
+static __device__ __forceinline__ void lm_attn_body(const float* __restrict__ q, int ldq, const float* __restrict__ kc, const float* __restrict__ vc, int cap,
+                                                    int Lq, int Lk_all, const int* __restrict__ klen, int H, int heads, float* __restrict__ out,
+                                                    const int* __restrict__ src, int src_cap, int group) {
+    extern __shared__ float sc[];                      // [Lk rounded to 64] scores, then 4 x (max, sum, acc[32]) (BEAM: then [Lk rounded to 64] source rows)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int item = blockIdx.x;                       // (b, l, head)
     const int d = H / heads, Lkp = (Lk_all + 63) & ~63;
     const int hd = item % heads;
     const long long n = item / heads;                  // token index b * Lq + l
-    const int b = (int)(n / Lq);
+    const int b = BEAM ? (int)(n / Lq) / group : (int)(n / Lq);
+    int* srow = reinterpret_cast<int*>(sc + Lkp + 4 * 34);
     // padding mask (reference roformer.py:209-236: attention_mask on the encoder's keys, encoder_attention_mask on the cross-attention's):
     // right-padded rows, so the mask of batch row b is "keys [0, klen[b])"; masked keys get probability exactly 0 as with HF's -inf bias
     const int kl = klen ? klen[b] : Lk_all;
@@ -321,8 +327,16 @@ __global__ void __launch_bounds__(256) lm_attn_kernel(const float* __restrict__ 
         float dot = -INFINITY;
         if (key < Lk) {
             dot = 0.f;
+            const float* kbk = kb;
+            if constexpr (BEAM) {
+                if (src) {
+                    const int r = (key == Lk - 1) ? (int)n : src[n * src_cap + key];
+                    srow[key] = r;
+                    kbk = kc + ((long long)r * heads + hd) * cap * d;
+                }
+            }
             if (d == 32) {      // the key row as eight 16-byte loads (a lane per key: every load instruction gathers 64 rows)
-                const f32x4* kr = reinterpret_cast<const f32x4*>(kb + (long long)key * 32);
+                const f32x4* kr = reinterpret_cast<const f32x4*>(kbk + (long long)key * 32);
                 f32x4 kv[8];
 #pragma unroll
                 for (int e4 = 0; e4 < 8; ++e4) kv[e4] = kr[e4];
@@ -331,7 +345,7 @@ __global__ void __launch_bounds__(256) lm_attn_kernel(const float* __restrict__ 
             } else {
 #pragma unroll
                 for (int e = 0; e < 32; ++e)
-                    if (e < d) dot = fmaf(qr[e], kb[(long long)key * d + e], dot);
+                    if (e < d) dot = fmaf(qr[e], kbk[(long long)key * d + e], dot);
             }
             dot *= scale;
         }
@@ -355,8 +369,14 @@ __global__ void __launch_bounds__(256) lm_attn_kernel(const float* __restrict__ 
     if (e < d && mx > -INFINITY)
         for (int k0 = wave * 64; k0 < Lk; k0 += 256) {
             const int kend = (k0 + 64 < Lk) ? k0 + 64 : Lk;
+            if (BEAM && src) {
 #pragma unroll 8
-            for (int key = k0 + half; key < kend; key += 2) acc = fmaf(sc[key], vb[(long long)key * d + e], acc);
+                for (int key = k0 + half; key < kend; key += 2)
+                    acc = fmaf(sc[key], vc[(((long long)srow[key] * heads + hd) * cap + key) * d + e], acc);
+            } else {
+#pragma unroll 8
+                for (int key = k0 + half; key < kend; key += 2) acc = fmaf(sc[key], vb[(long long)key * d + e], acc);
+            }
         }
     acc += __shfl_xor(acc, 32, 64);
     if (lane == 0) { mrg[wave * 34] = mx; mrg[wave * 34 + 1] = sum; }
@@ -374,17 +394,38 @@ __global__ void __launch_bounds__(256) lm_attn_kernel(const float* __restrict__ 
         out[n * H + hd * d + e] = o / tot;
     }
 }
+__global__ void __launch_bounds__(256) lm_attn_kernel(const float* __restrict__ q, int ldq, const float* __restrict__ kc, const float* __restrict__ vc, int cap,
+                                                      int Lq, int Lk_all, const int* __restrict__ klen, int H, int heads, float* __restrict__ out) {
+    lm_attn_body<false>(q, ldq, kc, vc, cap, Lq, Lk_all, klen, H, heads, out, nullptr, 0, 1);
+}
+__global__ void __launch_bounds__(256) lm_attn_beam_kernel(const float* __restrict__ q, int ldq, const float* __restrict__ kc, const float* __restrict__ vc, int cap,
+                                                           int Lq, int Lk_all, const int* __restrict__ klen, int H, int heads, float* __restrict__ out,
+                                                           const int* __restrict__ src, int src_cap, int group) {
+    lm_attn_body<true>(q, ldq, kc, vc, cap, Lq, Lk_all, klen, H, heads, out, src, src_cap, group);
+}
 
 // ---- next-token choice per sequence (HF GenerationMixin._sample with RepetitionPenalty -> Temperature -> TopK -> TopP, then
 //      softmax + one draw; greedy = argmax).  The draw is the inverse-CDF rule over the vocabulary order with a caller-supplied
 //      uniform (torch.multinomial's own stream cannot be reproduced outside torch).  One workgroup per sequence, V <= 256 * 32. ----
 constexpr int kMaxTopK = 64;
-template <int NI>      // NI * 256 >= V: vocabulary slots per thread
-__global__ void __launch_bounds__(256) lm_sample_kernel(const float* __restrict__ logits, int V, int do_sample, int top_k, float top_p, float inv_temp,
-                                                        float rep_pen, const float* __restrict__ uniforms, int64_t* __restrict__ tokens, int cap_tokens,
-                                                        int step, int* __restrict__ unfinished, int eos, int pad, int* __restrict__ any_unfinished,
-                                                        const float* __restrict__ word, const float* __restrict__ type, const float* __restrict__ eg,
-                                                        const float* __restrict__ eb, float eps, int H, float* __restrict__ xnext) {
+// NoRepeatNGramLogitsProcessor (transformers generation/logits_process.py) over the history seq[0, len), BOS included: every window of n tokens
+// whose first n - 1 equal the last n - 1 tokens of the history bans its last token (n = 1: every token seen so far).  Nothing is banned while
+// len < n.  The banned ids are set as bits of ban[] (LDS, V <= 8192) by the threads [t0, t0 + nt); the caller zeroes ban and synchronises.
+static __device__ __forceinline__ void lm_ngram_mark(const int64_t* __restrict__ seq, int len, int n, int V, unsigned* ban, int t0, int nt) {
+    for (int i = t0; i + n <= len; i += nt) {
+        bool match = true;
+        for (int j = 0; j < n - 1 && match; ++j) match = seq[i + j] == seq[len - n + 1 + j];
+        const long long t = seq[i + n - 1];
+        if (match && t >= 0 && t < V) atomicOr(ban + (t >> 5), 1u << (t & 31));
+    }
+}
+
+template <int NI, bool NG>      // NI * 256 >= V: vocabulary slots per thread; NG: n-gram ban of size `ngram` after the repetition penalty
+static __device__ __forceinline__ void lm_sample_body(const float* __restrict__ logits, int V, int do_sample, int top_k, float top_p, float inv_temp,
+                                                      float rep_pen, const float* __restrict__ uniforms, int64_t* __restrict__ tokens, int cap_tokens,
+                                                      int step, int* __restrict__ unfinished, int eos, int pad, int* __restrict__ any_unfinished,
+                                                      const float* __restrict__ word, const float* __restrict__ type, const float* __restrict__ eg,
+                                                      const float* __restrict__ eb, float eps, int H, float* __restrict__ xnext, int ngram) {
     __shared__ float rv[4];
     __shared__ int ri[4];
     __shared__ int chosen;
@@ -412,6 +453,18 @@ __global__ void __launch_bounds__(256) lm_sample_kernel(const float* __restrict_
                 for (int i = 0; i < NI; ++i)
                     if (i == (t >> 8)) v[i] = (v[i] < 0.f) ? v[i] * rep_pen : v[i] / rep_pen;
             }
+        }
+    }
+    if constexpr (NG) {      // NoRepeatNGram comes after the repetition penalty and before the temperature (HF _get_logits_processor)
+        __shared__ unsigned ban[256];
+        ban[tid] = 0u;
+        __syncthreads();
+        lm_ngram_mark(seq, step + 1, ngram, V, ban, tid, 256);
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < NI; ++i) {
+            const int c = tid + 256 * i;
+            if (c < V && ((ban[c >> 5] >> (c & 31)) & 1u)) v[i] = -INFINITY;
         }
     }
     if (do_sample && inv_temp != 1.0f) {
@@ -525,17 +578,38 @@ __global__ void __launch_bounds__(256) lm_sample_kernel(const float* __restrict_
     }
 }
 
+template <int NI>
+__global__ void __launch_bounds__(256) lm_sample_kernel(const float* __restrict__ logits, int V, int do_sample, int top_k, float top_p, float inv_temp,
+                                                        float rep_pen, const float* __restrict__ uniforms, int64_t* __restrict__ tokens, int cap_tokens,
+                                                        int step, int* __restrict__ unfinished, int eos, int pad, int* __restrict__ any_unfinished,
+                                                        const float* __restrict__ word, const float* __restrict__ type, const float* __restrict__ eg,
+                                                        const float* __restrict__ eb, float eps, int H, float* __restrict__ xnext) {
+    lm_sample_body<NI, false>(logits, V, do_sample, top_k, top_p, inv_temp, rep_pen, uniforms, tokens, cap_tokens, step, unfinished, eos, pad, any_unfinished,
+                              word, type, eg, eb, eps, H, xnext, 0);
+}
+// the same with no_repeat_ngram_size = ngram >= 1
+template <int NI>
+__global__ void __launch_bounds__(256) lm_sample_ngram_kernel(const float* __restrict__ logits, int V, int do_sample, int top_k, float top_p, float inv_temp,
+                                                              float rep_pen, const float* __restrict__ uniforms, int64_t* __restrict__ tokens, int cap_tokens,
+                                                              int step, int* __restrict__ unfinished, int eos, int pad, int* __restrict__ any_unfinished,
+                                                              const float* __restrict__ word, const float* __restrict__ type, const float* __restrict__ eg,
+                                                              const float* __restrict__ eb, float eps, int H, float* __restrict__ xnext, int ngram) {
+    lm_sample_body<NI, true>(logits, V, do_sample, top_k, top_p, inv_temp, rep_pen, uniforms, tokens, cap_tokens, step, unfinished, eos, pad, any_unfinished,
+                             word, type, eg, eb, eps, H, xnext, ngram);
+}
+
 // ---- the same choice with NO top-k filter (HF: top_k = None / 0): RepetitionPenalty -> Temperature -> [TopP] -> softmax -> one draw over the whole
 //      vocabulary.  An optional path (the reference's caller passes top_k = 5): the softmax normalisation and the inverse-CDF walk are serial loops of
 //      one thread over an LDS copy of the row (~4 k adds each: tens of microseconds), in vocabulary order -- exactly what a sequential float32
 //      cumsum computes, so the oracle restates it to the bit.  TopP (modeling: sort ascending, drop while the cumulative probability stays
 //      <= 1 - top_p, always keep the largest): the cut is found as the largest probability value t with sum{p_j <= t} <= 1 - top_p by bisection
 //      over the ordered bit patterns of the probabilities (31 block reductions); probabilities tied with the cut are dropped together. ----
-__global__ void __launch_bounds__(256) lm_sample_full_kernel(const float* __restrict__ logits, int V, float top_p, float inv_temp, float rep_pen,
-                                                             const float* __restrict__ uniforms, int64_t* __restrict__ tokens, int cap_tokens, int step,
-                                                             int* __restrict__ unfinished, int eos, int pad, int* __restrict__ any_unfinished,
-                                                             const float* __restrict__ word, const float* __restrict__ type, const float* __restrict__ eg,
-                                                             const float* __restrict__ eb, float eps, int H, float* __restrict__ xnext) {
+template <bool NG>
+static __device__ __forceinline__ void lm_sample_full_body(const float* __restrict__ logits, int V, float top_p, float inv_temp, float rep_pen,
+                                                           const float* __restrict__ uniforms, int64_t* __restrict__ tokens, int cap_tokens, int step,
+                                                           int* __restrict__ unfinished, int eos, int pad, int* __restrict__ any_unfinished,
+                                                           const float* __restrict__ word, const float* __restrict__ type, const float* __restrict__ eg,
+                                                           const float* __restrict__ eb, float eps, int H, float* __restrict__ xnext, int ngram) {
     extern __shared__ float prob[];      // [V]
     __shared__ float rv[4];
     __shared__ int chosen;
@@ -554,6 +628,16 @@ __global__ void __launch_bounds__(256) lm_sample_full_kernel(const float* __rest
         }
     }
     __syncthreads();
+    if constexpr (NG) {      // the n-gram ban, between the repetition penalty and the temperature
+        __shared__ unsigned ban[256];
+        ban[tid] = 0u;
+        __syncthreads();
+        lm_ngram_mark(seq, step + 1, ngram, V, ban, tid, 256);
+        __syncthreads();
+        for (int c = tid; c < V; c += 256)
+            if ((ban[c >> 5] >> (c & 31)) & 1u) prob[c] = -INFINITY;
+        __syncthreads();
+    }
     float m = -INFINITY;
     for (int c = tid; c < V; c += 256) {
         if (inv_temp != 1.0f) prob[c] *= inv_temp;
@@ -629,6 +713,238 @@ __global__ void __launch_bounds__(256) lm_sample_full_kernel(const float* __rest
         for (int i = 0; i < 4; ++i) {
             const int c = tid + 256 * i;
             if (c < H) xnext[(long long)b * H + c] = (ev[i] - mean) * rstd * eg[c] + eb[c];
+        }
+    }
+}
+
+__global__ void __launch_bounds__(256) lm_sample_full_kernel(const float* __restrict__ logits, int V, float top_p, float inv_temp, float rep_pen,
+                                                             const float* __restrict__ uniforms, int64_t* __restrict__ tokens, int cap_tokens, int step,
+                                                             int* __restrict__ unfinished, int eos, int pad, int* __restrict__ any_unfinished,
+                                                             const float* __restrict__ word, const float* __restrict__ type, const float* __restrict__ eg,
+                                                             const float* __restrict__ eb, float eps, int H, float* __restrict__ xnext) {
+    lm_sample_full_body<false>(logits, V, top_p, inv_temp, rep_pen, uniforms, tokens, cap_tokens, step, unfinished, eos, pad, any_unfinished, word, type, eg, eb,
+                               eps, H, xnext, 0);
+}
+__global__ void __launch_bounds__(256) lm_sample_full_ngram_kernel(const float* __restrict__ logits, int V, float top_p, float inv_temp, float rep_pen,
+                                                                   const float* __restrict__ uniforms, int64_t* __restrict__ tokens, int cap_tokens, int step,
+                                                                   int* __restrict__ unfinished, int eos, int pad, int* __restrict__ any_unfinished,
+                                                                   const float* __restrict__ word, const float* __restrict__ type, const float* __restrict__ eg,
+                                                                   const float* __restrict__ eb, float eps, int H, float* __restrict__ xnext, int ngram) {
+    lm_sample_full_body<true>(logits, V, top_p, inv_temp, rep_pen, uniforms, tokens, cap_tokens, step, unfinished, eos, pad, any_unfinished, word, type, eg, eb,
+                              eps, H, xnext, ngram);
+}
+
+// ---- one step of HF's greedy beam search (transformers generation/utils.py _beam_search with _get_top_k_continuations,
+//      _get_running_beams_for_next_iteration, _update_finished_beams, _check_early_stop_heuristic, _beam_search_has_unfinished_sequences;
+//      length_penalty 1).  One workgroup per batch item b, whose K running beams are rows b * K + k of logits [B * K][V]:
+//        scores = log_softmax(logits) -> RepetitionPenalty (on the log-probabilities) -> NoRepeatNGram (each beam's own history)
+//                 + running score;  top 2K of the K * V scores (ties: the lower flat index k * V + token);
+//        a candidate hits the stopping criteria on EOS or when its length reaches max_length;
+//        next running beams = top K of (score + hit * -1e9); finished hypotheses = top K of the old ones and the new candidates
+//        (score / generated length, plus the -1e9 masks as fp32 additions, in HF's order);  then the early-stop heuristic.
+//      Each wave takes whole beam rows (K <= 8): the row sits in registers, NW = ceil(V / 64) values per lane, and the row's top 2K come
+//      out of 2K wave argmax rounds; one thread merges the K lists of 2K (the running score is constant across a row, so the global top 2K
+//      are among them) and does the O(K) bookkeeping from LDS copies of the item's state.  Sequences and the key/value ancestry table are
+//      double-buffered (_in -> _out);
+//      per-row scores and flags are read before they are rewritten, in place is allowed.  prev_flag (null at step 0): the previous step's
+//      bits; when they say the search has ended the step changes nothing.  flag_out gets (OR over the batch) 1 = some item may still
+//      improve, 2 = some item has an unfinished hypothesis slot, 4 = some candidate did not hit the stopping criteria, 8 = ended before. ----
+constexpr int kMaxBeams = 8, kMaxBeamVocab = 64 * 68;
+struct LmBeamState {
+    const int64_t* rseq_in; int64_t* rseq_out;      // running sequences [B * K][cap]
+    const float* rscore_in; float* rscore_out;      // running scores [B * K]
+    const int* tab_in; int* tab_out;                // [B * K][cap]: cache row of key p of each running beam (null: not tracked)
+    const int64_t* fseq_in; int64_t* fseq_out;      // finished hypotheses [B * K][cap]
+    const float* fscore_in; float* fscore_out;      // [B * K]
+    const int* ffin_in; int* ffin_out;              // is_sent_finished [B * K]
+    const int* flen_in; int* flen_out;              // generated tokens of each hypothesis (BOS not counted) [B * K]
+    const int* unsat_in; int* unsat_out;            // is_early_stop_heuristic_unsatisfied [B]
+    int* parent;                                    // [B * K] parent beam of each new running beam, or null
+    const int* prev_flag; int* flag_out;
+};
+static __device__ __forceinline__ bool lm_beam_running(int f, int early_stopping) {      // _beam_search_has_unfinished_sequences over the batch
+    return !(f & 8) && (f & 1) && (early_stopping != 1 || (f & 2)) && (f & 4);
+}
+template <int NW>
+__global__ void __launch_bounds__(256) lm_beam_step_kernel(const float* __restrict__ logits, int V, int K, int step, int cap, int max_length, int eos,
+                                                           float rep_pen, int ngram, int early_stopping, const LmBeamState st,
+                                                           const float* __restrict__ word, const float* __restrict__ type, const float* __restrict__ eg,
+                                                           const float* __restrict__ eb, float eps, int H, float* __restrict__ xnext) {
+    __shared__ unsigned pen_bits[4][256], ban_bits[4][256];
+    __shared__ float cv[kMaxBeams][2 * kMaxBeams], topv[2 * kMaxBeams], sel_sc[kMaxBeams], nf_sc[kMaxBeams], f_sc[kMaxBeams];
+    __shared__ int ci[kMaxBeams][2 * kMaxBeams], topb[2 * kMaxBeams], topt[2 * kMaxBeams], sel_j[kMaxBeams], nf_m[kMaxBeams], nf_fin[kMaxBeams], nf_len[kMaxBeams];
+    __shared__ int f_fin[kMaxBeams], f_len[kMaxBeams], unsat_sh;
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int cur_len = step + 1, K2 = 2 * K, base = b * K;
+    if (st.prev_flag && !lm_beam_running(*st.prev_flag, early_stopping)) {
+        if (tid == 0) atomicOr(st.flag_out, 8);
+        return;
+    }
+    // the item's finished-hypothesis state, staged for the serial bookkeeping below (its loads overlap the rows' work)
+    if (tid < K) { f_sc[tid] = st.fscore_in[base + tid]; f_fin[tid] = st.ffin_in[base + tid]; f_len[tid] = st.flen_in[base + tid]; }
+    if (tid == 64) unsat_sh = st.unsat_in[b];
+    for (int r0 = 0; r0 < K; r0 += 4) {      // (uniform trip count: the barriers below are reached by every wave)
+        const int k = r0 + wave, row = base + k;
+        const bool act = k < K;
+        for (int i = lane; i < 256; i += 64) { pen_bits[wave][i] = 0u; ban_bits[wave][i] = 0u; }
+        __syncthreads();
+        if (act) {
+            const int64_t* hist = st.rseq_in + (long long)row * cap;
+            if (rep_pen != 1.0f)
+                for (int j = lane; j < cur_len; j += 64) {
+                    const long long t = hist[j];
+                    if (t >= 0 && t < V) atomicOr(&pen_bits[wave][t >> 5], 1u << (t & 31));
+                }
+            if (ngram > 0) lm_ngram_mark(hist, cur_len, ngram, V, ban_bits[wave], lane, 64);
+        }
+        __syncthreads();
+        if (act) {
+            const float* lg = logits + (long long)row * V;
+            float v[NW];
+            float m = -INFINITY;
+#pragma unroll
+            for (int i = 0; i < NW; ++i) {
+                const int c = lane + 64 * i;
+                v[i] = (c < V) ? lg[c] : -INFINITY;
+                m = fmaxf(m, v[i]);
+            }
+            m = wave_max(m);
+            float z = 0.f;
+#pragma unroll
+            for (int i = 0; i < NW; ++i) z += (lane + 64 * i < V) ? expf(v[i] - m) : 0.f;
+            const float lse = logf(wave_sum(z));
+            const float rs = st.rscore_in[row];
+#pragma unroll
+            for (int i = 0; i < NW; ++i) {
+                const int c = lane + 64 * i;
+                float x = (v[i] - m) - lse;
+                if ((pen_bits[wave][c >> 5] >> (c & 31)) & 1u) x = (x < 0.f) ? x * rep_pen : x / rep_pen;
+                if ((ban_bits[wave][c >> 5] >> (c & 31)) & 1u) x = -INFINITY;
+                v[i] = (c < V) ? x + rs : -INFINITY;
+            }
+            for (int j = 0; j < K2; ++j) {      // the row's j-th largest score, ties to the lower token id
+                float bv = -INFINITY;
+                int bi = 0x7fffffff;
+#pragma unroll
+                for (int i = 0; i < NW; ++i)
+                    if (v[i] > bv) { bv = v[i]; bi = lane + 64 * i; }
+                const float mx = wave_max(bv);
+                bi = wave_min_i((bv == mx) ? bi : 0x7fffffff);
+                if (lane == 0) { cv[k][j] = mx; ci[k][j] = (bi < V) ? bi : 0; }
+                if ((bi & 63) == lane) {
+#pragma unroll
+                    for (int i = 0; i < NW; ++i)
+                        if (i == (bi >> 6)) v[i] = -INFINITY;
+                }
+            }
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        // _get_top_k_continuations: merge the K sorted lists (value descending, then flat index k * V + token ascending)
+        int head[kMaxBeams];
+        for (int k = 0; k < K; ++k) head[k] = 0;
+        for (int j = 0; j < K2; ++j) {
+            int bk = -1;
+            for (int k = 0; k < K; ++k) {
+                if (head[k] >= K2) continue;
+                if (bk < 0 || cv[k][head[k]] > cv[bk][head[bk]]) bk = k;      // (k ascending: an equal value keeps the lower flat index)
+            }
+            topv[j] = cv[bk][head[bk]]; topb[j] = bk; topt[j] = ci[bk][head[bk]];
+            ++head[bk];
+        }
+        bool hit[2 * kMaxBeams];
+        bool all_hit = true;
+        for (int j = 0; j < K2; ++j) { hit[j] = topt[j] == eos || cur_len + 1 >= max_length; all_hit = all_hit && hit[j]; }
+        // _get_running_beams_for_next_iteration
+        float trl[2 * kMaxBeams];
+        for (int j = 0; j < K2; ++j) trl[j] = topv[j] + (hit[j] ? -1.0e9f : -0.0f);
+        unsigned taken = 0u;
+        for (int k = 0; k < K; ++k) {
+            int bj = -1;
+            for (int j = 0; j < K2; ++j)
+                if (!((taken >> j) & 1u) && (bj < 0 || trl[j] > trl[bj])) bj = j;
+            taken |= 1u << bj;
+            sel_j[k] = bj; sel_sc[k] = trl[bj];
+        }
+        // _update_finished_beams (length_penalty 1: divide by the generated length cur_len + 1 - 1)
+        bool all_fin = true;
+        for (int k = 0; k < K; ++k) all_fin = all_fin && f_fin[k] != 0;
+        const int unsat = unsat_sh;
+        float ms[3 * kMaxBeams];
+        for (int k = 0; k < K; ++k) ms[k] = f_sc[k];
+        for (int j = 0; j < K2; ++j) {
+            const bool did = hit[j] && j < K;
+            float f = topv[j] / (float)cur_len;
+            f = f + ((all_fin && early_stopping == 1) ? -1.0e9f : -0.0f);
+            f = f + (unsat ? -0.0f : -1.0e9f);
+            f = f + (did ? -0.0f : -1.0e9f);
+            ms[K + j] = f;
+        }
+        unsigned mtaken = 0u;
+        float worst = INFINITY;
+        bool nall_fin = true;
+        for (int k = 0; k < K; ++k) {
+            int bm = -1;
+            for (int m = 0; m < K + K2; ++m)
+                if (!((mtaken >> m) & 1u) && (bm < 0 || ms[m] > ms[bm])) bm = m;
+            mtaken |= 1u << bm;
+            nf_m[k] = bm; nf_sc[k] = ms[bm];
+            nf_fin[k] = (bm < K) ? f_fin[bm] : (hit[bm - K] && bm - K < K) ? 1 : 0;
+            nf_len[k] = (bm < K) ? f_len[bm] : cur_len;
+            worst = fminf(worst, ms[bm]);
+            nall_fin = nall_fin && nf_fin[k];
+        }
+        // _check_early_stop_heuristic at cur_len + 1 (early_stopping "never" with a positive length penalty: the best length is max_length)
+        const int hyp = (early_stopping == 2) ? max_length - 1 : cur_len;
+        const float best = sel_sc[0] / (float)hyp;
+        bool improve = false;
+        for (int k = 0; k < K; ++k) improve = improve || best > (nf_fin[k] ? worst : -1.0e9f);
+        const int nunsat = (unsat && improve) ? 1 : 0;
+        st.unsat_out[b] = nunsat;
+        atomicOr(st.flag_out, (nunsat ? 1 : 0) | (nall_fin ? 0 : 2) | (all_hit ? 0 : 4));
+    }
+    __syncthreads();
+    // the new running sequences, finished hypotheses and ancestry tables: every (beam, position) pair at once
+    const int n1 = cur_len + 1;
+    for (int i = tid; i < K * n1; i += 256) {
+        const int k = i / n1, p = i - k * n1;
+        const int row = base + k, j = sel_j[k], par = base + topb[j], m = nf_m[k];
+        const int64_t* fi = (m < K) ? st.fseq_in + (long long)(base + m) * cap : st.rseq_in + (long long)(base + topb[m - K]) * cap;
+        st.rseq_out[(long long)row * cap + p] = (p < cur_len) ? st.rseq_in[(long long)par * cap + p] : (int64_t)topt[j];
+        st.fseq_out[(long long)row * cap + p] = (m >= K && p == cur_len) ? (int64_t)topt[m - K] : fi[p];
+        if (st.tab_out && p < cur_len) st.tab_out[(long long)row * cap + p] = (p < step) ? st.tab_in[(long long)par * cap + p] : par;
+    }
+    if (tid < K) {
+        const int row = base + tid;
+        st.rscore_out[row] = sel_sc[tid];
+        st.fscore_out[row] = nf_sc[tid]; st.ffin_out[row] = nf_fin[tid]; st.flen_out[row] = nf_len[tid];
+        if (st.parent) st.parent[row] = topb[sel_j[tid]];
+    }
+    // the next step's input rows, LayerNorm(word[token] + type[0]) (lm_embed_kernel's rows): wave w takes beams w, w + 4 with
+    // fixed-order wave sums (H <= 256, lds_lm_create allows 256)
+    if (xnext) {
+        for (int k = wave; k < K; k += 4) {
+            long long t = topt[sel_j[k]];
+            t = (t < 0) ? 0 : (t >= V ? V - 1 : t);
+            float ev[4];
+            float s = 0.f;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int c = lane + 64 * i;
+                ev[i] = (c < H) ? word[t * H + c] + type[c] : 0.f;
+                s += ev[i];
+            }
+            const float mean = wave_sum(s) / (float)H;
+            float q = 0.f;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) { const float dd = (lane + 64 * i < H) ? ev[i] - mean : 0.f; q += dd * dd; }
+            const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)H + eps);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int c = lane + 64 * i;
+                if (c < H) xnext[(long long)(base + k) * H + c] = (ev[i] - mean) * rstd * eg[c] + eb[c];
+            }
         }
     }
 }
@@ -768,19 +1084,28 @@ struct LmArena {
         return (float*)p;
     }
 };
-struct LmWs { float *x, *y, *z, *qkv, *ctx, *ff, *kv, *logits, *kc_tmp, *vc_tmp; int* flags; std::vector<float*> kc, vc, ckc, cvc; };
-// N = rows processed at once (B * L for the prefill, B for a decode step)
-void lm_plan(const lds_lm* lm, LmArena& A, int B, int L, int cap, LmWs& w) {
+// beam-search state (K > 1): two buffers of the running sequences, of the ancestry table and of the finished hypotheses, per-row scores / flags
+struct LmBeamWs { int64_t *rseq[2], *fseq[2]; int* tab[2]; float *rscore, *fscore; int *ffin, *flen, *unsat; };
+struct LmWs { float *x, *y, *z, *qkv, *ctx, *ff, *kv, *logits, *kc_tmp, *vc_tmp; int* flags; std::vector<float*> kc, vc, ckc, cvc; LmBeamWs beam; };
+// N = rows processed at once (B * L for the prefill, B * K for a decode step); K = beams per batch item (1: the layout of a plain decode)
+void lm_plan(const lds_lm* lm, LmArena& A, int B, int L, int cap, LmWs& w, int K = 1) {
     const lds_lm_cfg& c = lm->cfg;
-    const size_t N = (size_t)B * (L > 1 ? L : 1), H = c.hidden;
+    const size_t R = (size_t)B * K, BL = (size_t)B * (L > 1 ? L : 1), N = BL > R ? BL : R, H = c.hidden;
     w.x = A.f(N * H); w.y = A.f(N * H); w.z = A.f(N * H); w.qkv = A.f(N * 3 * H); w.ctx = A.f(N * H); w.ff = A.f(N * c.inter); w.kv = A.f(N * 2 * H);
-    w.logits = A.f((size_t)B * c.sem_vocab);
+    w.logits = A.f(R * c.sem_vocab);
     w.kc_tmp = A.f(N * H); w.vc_tmp = A.f(N * H);
-    w.flags = (int*)A.f((size_t)cap + B + 64);
+    w.flags = (int*)A.f((size_t)cap + R + 64);
     w.kc.clear(); w.vc.clear(); w.ckc.clear(); w.cvc.clear();
     for (int i = 0; i < c.dec_layers; ++i) {
-        w.kc.push_back(A.f((size_t)B * H * cap)); w.vc.push_back(A.f((size_t)B * H * cap));
+        w.kc.push_back(A.f(R * H * cap)); w.vc.push_back(A.f(R * H * cap));
         w.ckc.push_back(A.f((size_t)B * H * L)); w.cvc.push_back(A.f((size_t)B * H * L));
+    }
+    w.beam = LmBeamWs{};
+    if (K > 1) {
+        for (int i = 0; i < 2; ++i) {
+            w.beam.rseq[i] = (int64_t*)A.f(2 * R * cap); w.beam.fseq[i] = (int64_t*)A.f(2 * R * cap); w.beam.tab[i] = (int*)A.f(R * cap);
+        }
+        w.beam.rscore = A.f(R); w.beam.fscore = A.f(R); w.beam.ffin = (int*)A.f(R); w.beam.flen = (int*)A.f(R); w.beam.unsat = (int*)A.f(B);
     }
 }
 hipError_t lm_attention(const float* q, int ldq, const float* kc, const float* vc, int cap, int B, int Lq, int Lk, const int* klen, const lds_lm_cfg& c, float* out,
@@ -788,6 +1113,15 @@ hipError_t lm_attention(const float* q, int ldq, const float* kc, const float* v
     const int total = B * Lq * c.heads;
     const size_t lds = (size_t)(((Lk + 63) & ~63) + 4 * 34) * sizeof(float);
     hipLaunchKernelGGL(lm_attn_kernel, dim3(total), dim3(256), lds, st, q, ldq, kc, vc, cap, Lq, Lk, klen, c.hidden, c.heads, out);
+    return hipGetLastError();
+}
+// beam rows of a decode step (lm_attn_beam_kernel): src = ancestry table of the self-attention (null for the cross-attention), group = beams
+struct LmBeamAttn { const int* src; int K; };
+hipError_t lm_attention_beam(const float* q, int ldq, const float* kc, const float* vc, int cap, int B, int Lq, int Lk, const int* klen, const lds_lm_cfg& c,
+                             float* out, const int* src, int src_cap, int group, hipStream_t st) {
+    const int total = B * Lq * c.heads, Lkp = (Lk + 63) & ~63;
+    const size_t lds = (size_t)(Lkp + 4 * 34) * sizeof(float) + (src ? (size_t)Lkp * sizeof(int) : 0);
+    hipLaunchKernelGGL(lm_attn_beam_kernel, dim3(total), dim3(256), lds, st, q, ldq, kc, vc, cap, Lq, Lk, klen, c.hidden, c.heads, out, src, src_cap, group);
     return hipGetLastError();
 }
 // rows [N][hidden] together with the LayerNorm that is still owed to them (ln == nullptr: already normalised)
@@ -813,8 +1147,9 @@ hipError_t lm_dln(const LmLinear& W, const LmRows& X, int ldx, const LmRows* R, 
 // Every LayerNorm is deferred to the readers of its rows (lm_linear_dln_kernel): `x` comes in, and goes out, as rows + owed LayerNorm.
 // The three row buffers of the workspace rotate: input -> a (attention block) -> c (cross-attention block) -> output in the input's buffer.
 // self_klen / cross_klen: per-batch-row key counts of the padding mask (device int32 [B]) or null
+// beam (decode steps of a beam search, B = rows = items * beam->K): the self-attention follows the ancestry table, the cross-attention maps row n to item n / K
 int lm_layer(const lds_lm* lm, const LmStack& s, const LmLayer& Ly, const LmWs& w, LmRows& x, int B, int L, int pos0, float* kc, float* vc, int cap,
-             const float* ckc, const float* cvc, int Lenc, const int* self_klen, const int* cross_klen, hipStream_t st) {
+             const float* ckc, const float* cvc, int Lenc, const int* self_klen, const int* cross_klen, hipStream_t st, const LmBeamAttn* beam = nullptr) {
     const lds_lm_cfg& c = lm->cfg;
     const int H = c.hidden, N = B * L;
     if (Ly.self.o.M != H || Ly.ff2.M != H || (Ly.has_cross && (Ly.cross.o.M != H || Ly.cross.q.K != H))) return lm_fail(LDS_EINVAL, "layer shapes");
@@ -825,13 +1160,15 @@ int lm_layer(const lds_lm* lm, const LmStack& s, const LmLayer& Ly, const LmWs& 
         const LmRope rope{s.table, kc, vc, pos0, L, c.heads, cap};      // rotary embedding and cache append in the projection's epilogue
         LM_HIP(lm_dln<4>(Ly.self.qkv, x, H, nullptr, c.eps, w.qkv, 3 * H, N, st, &rope));
     }
-    LM_HIP(lm_attention(w.qkv, 3 * H, kc, vc, cap, B, L, pos0 + L, self_klen, c, w.ctx, st));
+    if (beam) LM_HIP(lm_attention_beam(w.qkv, 3 * H, kc, vc, cap, B, L, pos0 + L, self_klen, c, w.ctx, beam->src, cap, 1, st));
+    else LM_HIP(lm_attention(w.qkv, 3 * H, kc, vc, cap, B, L, pos0 + L, self_klen, c, w.ctx, st));
     const LmRows ctx{w.ctx, nullptr};
     LM_HIP(lm_dln<5>(Ly.self.o, ctx, H, &x, c.eps, free1, H, N, st));               // a = W_o ctx + LN(x)
     LmRows cur{free1, &Ly.self.ln};
     if (Ly.has_cross) {
         LM_HIP(lm_dln<0>(Ly.cross.q, cur, H, nullptr, c.eps, w.qkv, H, N, st));
-        LM_HIP(lm_attention(w.qkv, H, ckc, cvc, Lenc, B, L, Lenc, cross_klen, c, w.ctx, st));
+        if (beam) LM_HIP(lm_attention_beam(w.qkv, H, ckc, cvc, Lenc, B, L, Lenc, cross_klen, c, w.ctx, nullptr, 0, beam->K, st));
+        else LM_HIP(lm_attention(w.qkv, H, ckc, cvc, Lenc, B, L, Lenc, cross_klen, c, w.ctx, st));
         LM_HIP(lm_dln<5>(Ly.cross.o, ctx, H, &cur, c.eps, free2, H, N, st));        // c = W_o' ctx' + LN(a)
         cur = LmRows{free2, &Ly.cross.ln};
     }
@@ -882,13 +1219,83 @@ extern "C" int lds_lm_encode(lds_lm* lm, const int64_t* phone, const int64_t* to
     return LDS_OK;
 }
 
+namespace {
+// the token choice of one decode step (K = 1): the n-gram variants only when no_repeat_ngram_size > 0, so a plain decode runs today's kernels
+hipError_t lm_launch_choice(const lds_lm_decode_opts& o, int B, int V, const float* lg, float inv_temp, const float* u, int64_t* tokens, int cap, int step,
+                            int* unfinished, int eos, int pad, int* any_unf, const float* word, const float* type, const float* eg, const float* eb, float eps,
+                            int H, float* xnext, hipStream_t st) {
+    const int ds = o.do_sample, tk = ds ? o.top_k : 1, ng = o.no_repeat_ngram_size;
+    const float pen = o.repetition_penalty, tp = o.top_p;
+    if (ds && o.top_k == 0) {
+        if (ng > 0)
+            hipLaunchKernelGGL(lm_sample_full_ngram_kernel, dim3(B), dim3(256), sizeof(float) * V, st, lg, V, tp, inv_temp, pen, u, tokens, cap, step, unfinished,
+                               eos, pad, any_unf, word, type, eg, eb, eps, H, xnext, ng);
+        else
+            hipLaunchKernelGGL(lm_sample_full_kernel, dim3(B), dim3(256), sizeof(float) * V, st, lg, V, tp, inv_temp, pen, u, tokens, cap, step, unfinished,
+                               eos, pad, any_unf, word, type, eg, eb, eps, H, xnext);
+        return hipGetLastError();
+    }
+#define LM_CHOICE(NI)                                                                                                                                    \
+    do {                                                                                                                                                 \
+        if (ng > 0)                                                                                                                                      \
+            hipLaunchKernelGGL(lm_sample_ngram_kernel<NI>, dim3(B), dim3(256), 0, st, lg, V, ds, tk, tp, inv_temp, pen, u, tokens, cap, step, unfinished, \
+                               eos, pad, any_unf, word, type, eg, eb, eps, H, xnext, ng);                                                                \
+        else                                                                                                                                             \
+            hipLaunchKernelGGL(lm_sample_kernel<NI>, dim3(B), dim3(256), 0, st, lg, V, ds, tk, tp, inv_temp, pen, u, tokens, cap, step, unfinished,      \
+                               eos, pad, any_unf, word, type, eg, eb, eps, H, xnext);                                                                    \
+    } while (0)
+    if (V <= 256 * 9) LM_CHOICE(9);
+    else if (V <= 256 * 17) LM_CHOICE(17);      // (the reference's 4096-entry semantic codebook + 3 special ids)
+    else LM_CHOICE(32);
+#undef LM_CHOICE
+    return hipGetLastError();
+}
+hipError_t lm_launch_beam_step(int B, int K, int V, const float* lg, int step, int cap, int max_length, int eos, float pen, int ngram, int es,
+                               const LmBeamState& bs, const float* word, const float* type, const float* eg, const float* eb, float eps, int H, float* xnext,
+                               hipStream_t st) {
+    if (V <= 64 * 36)
+        hipLaunchKernelGGL(lm_beam_step_kernel<36>, dim3(B), dim3(256), 0, st, lg, V, K, step, cap, max_length, eos, pen, ngram, es, bs, word, type, eg, eb, eps, H, xnext);
+    else if (V <= kMaxBeamVocab)      // (4096 codes + 3 special ids; a row of 128 values per lane would spill)
+        hipLaunchKernelGGL(lm_beam_step_kernel<68>, dim3(B), dim3(256), 0, st, lg, V, K, step, cap, max_length, eos, pen, ngram, es, bs, word, type, eg, eb, eps, H, xnext);
+    else
+        return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+// the option checks that need no model (they come before every other check of lds_lm_generate_opts; no device call)
+int lm_check_opts(const lds_lm_decode_opts& o, const float* logits_out) {
+    if (o.num_beams < 1 || o.num_beams > kMaxBeams) return lm_fail(LDS_EINVAL, "num_beams %d out of range (1 .. %d)", o.num_beams, kMaxBeams);
+    if (o.no_repeat_ngram_size < 0) return lm_fail(LDS_EINVAL, "no_repeat_ngram_size %d < 0", o.no_repeat_ngram_size);
+    if (o.num_beams > 1 && o.do_sample)
+        return lm_fail(LDS_EINVAL, "beam sampling (num_beams > 1 with do_sample) is not built: only greedy beam search");
+    if (o.num_beams > 1 && (o.early_stopping < 0 || o.early_stopping > 2)) return lm_fail(LDS_EINVAL, "early_stopping must be 0 (False), 1 (True) or 2 (\"never\")");
+    if (o.num_beams > 1 && logits_out) return lm_fail(LDS_EINVAL, "logits_out is not available with num_beams > 1");
+    return LDS_OK;
+}
+}  // namespace
+
+extern "C" int lds_lm_workspace_bytes_opts(const lds_lm* lm, int B, int L, int max_length, int num_beams, size_t* out) {
+    if (num_beams < 1 || num_beams > kMaxBeams) return lm_fail(LDS_EINVAL, "num_beams %d out of range (1 .. %d)", num_beams, kMaxBeams);
+    if (!lm || !out || B <= 0 || L <= 0 || max_length < 2) return lm_fail(LDS_EINVAL, "bad argument");
+    LmArena A(nullptr, 0);
+    LmWs w;
+    lm_plan(lm, A, B, L, max_length, w, num_beams);
+    *out = A.used;
+    return LDS_OK;
+}
+
 // enc [B,L,hidden] (dev); uniforms [max_length-1][B] (dev, sampling only); tokens [B][max_length] int64 (dev): BOS then the generated ids,
 // positions past the returned length are unspecified; logits_out optional [max_length-1][B][vocab] (dev).  *n_tokens_host = sequence length incl. BOS.
-extern "C" int lds_lm_generate(lds_lm* lm, const float* enc, const int32_t* enc_len, int B, int L, int max_length, int do_sample, int top_k, float top_p,
-                               float temperature, float repetition_penalty, const float* uniforms, int64_t* tokens, float* logits_out, int* n_tokens_host,
-                               void* ws, size_t ws_bytes, void* stream) {
+extern "C" int lds_lm_generate_opts(lds_lm* lm, const float* enc, const int32_t* enc_len, int B, int L, int max_length, const lds_lm_decode_opts* opts,
+                                    const float* uniforms, int64_t* tokens, float* logits_out, int* n_tokens_host, void* ws, size_t ws_bytes, void* stream) {
+    if (!opts) return lm_fail(LDS_EINVAL, "null options");
+    const lds_lm_decode_opts o = *opts;
+    if (int r = lm_check_opts(o, logits_out)) return r;
     if (!lm || !enc || !tokens || !n_tokens_host || !ws || B <= 0 || L <= 0 || max_length < 2) return lm_fail(LDS_EINVAL, "bad argument");
     const lds_lm_cfg& c = lm->cfg;
+    const int do_sample = o.do_sample, top_k = o.top_k, K = o.num_beams;
+    const float top_p = o.top_p, temperature = o.temperature;
+    if (K > 1 && (2 * K > c.sem_vocab || c.sem_vocab > kMaxBeamVocab))
+        return lm_fail(LDS_EINVAL, "beam search is built for vocabularies of 2 * num_beams .. %d entries", kMaxBeamVocab);
     if (do_sample && (!uniforms || top_k < 0 || top_k > kMaxTopK || top_k > c.sem_vocab || !(top_p > 0.f) || !(temperature > 0.f)))
         return lm_fail(LDS_EINVAL, "sampling needs uniforms, 0 <= top_k <= %d (0 = no top-k filter), top_p > 0, temperature > 0", kMaxTopK);
     if (do_sample && top_k == 0 && (size_t)c.sem_vocab * sizeof(float) > 60 * 1024) return lm_fail(LDS_EINVAL, "top_k = 0 needs the vocabulary row in LDS (<= 15360 entries)");
@@ -896,15 +1303,18 @@ extern "C" int lds_lm_generate(lds_lm* lm, const float* enc, const int32_t* enc_
     // the encoder states come from lds_lm_encode (L <= max_pos); the cross-attention stages one score per encoder position in LDS
     if (L < 1 || L > c.max_pos || (size_t)(((L + 63) & ~63) + 4 * 34) * sizeof(float) > 64 * 1024)
         return lm_fail(LDS_EINVAL, "encoder length %d out of range (1 .. min(max_position_embeddings = %d, 16000))", L, c.max_pos);
+    // a beam decode stages one score and one source row per cached position in LDS
+    if (K > 1 && (size_t)(((max_length + 63) & ~63) * 2 + 4 * 34) * sizeof(float) > 64 * 1024)
+        return lm_fail(LDS_EINVAL, "max_length %d too long for a beam decode (<= 8000)", max_length);
     hipStream_t st = (hipStream_t)stream;
     LmArena A(ws, ws_bytes);
     LmWs w;
-    lm_plan(lm, A, B, L, max_length, w);
+    lm_plan(lm, A, B, L, max_length, w, K);
     if (!A.ok) return lm_fail(LDS_ENOMEM, "LM workspace too small: need %zu bytes", A.used);
-    const int H = c.hidden, V = c.sem_vocab;
-    int* unfinished = w.flags;                 // [B]
-    int* any_unf = w.flags + B;                // [max_length]: 1 when a sequence is still running after step s
-    // cross-attention keys / values of every decoder layer, once
+    const int H = c.hidden, V = c.sem_vocab, R = B * K;
+    int* unfinished = w.flags;                 // [R]
+    int* any_unf = w.flags + R;                // [max_length]: 1 when a sequence is still running after step s (beam search: lm_beam_step_kernel's bits)
+    // cross-attention keys / values of every decoder layer, once (one set per batch item, shared by its beams)
     for (int i = 0; i < c.dec_layers; ++i) {
         {
             const LmRows er{const_cast<float*>(enc), nullptr};
@@ -913,66 +1323,103 @@ extern "C" int lds_lm_generate(lds_lm* lm, const float* enc, const int32_t* enc_
         hipLaunchKernelGGL(lm_kv_pack_kernel, dim3((unsigned)(((long long)B * L * H + 255) / 256)), dim3(256), 0, st, w.kv, B, L, H, c.heads, w.ckc[i], w.cvc[i], L);
         LM_HIP(hipGetLastError());
     }
+    std::vector<int64_t> bos((size_t)R * max_length, (int64_t)c.sem_pad);
+    for (int r = 0; r < R; ++r) bos[(size_t)r * max_length] = c.sem_bos;
     {
-        std::vector<int> init(B + max_length, 0);
-        for (int b = 0; b < B; ++b) init[b] = 1;
-        LM_HIP(hipMemcpyAsync(unfinished, init.data(), sizeof(int) * (B + max_length), hipMemcpyHostToDevice, st));
-        std::vector<int64_t> bos((size_t)B * max_length, (int64_t)c.sem_pad);
-        for (int b = 0; b < B; ++b) bos[(size_t)b * max_length] = c.sem_bos;
-        LM_HIP(hipMemcpyAsync(tokens, bos.data(), sizeof(int64_t) * B * max_length, hipMemcpyHostToDevice, st));
-        LM_HIP(hipStreamSynchronize(st));      // the two host staging vectors go out of scope
+        std::vector<int> init(R + max_length, 0);
+        for (int b = 0; b < R; ++b) init[b] = 1;
+        LM_HIP(hipMemcpyAsync(unfinished, init.data(), sizeof(int) * (R + max_length), hipMemcpyHostToDevice, st));
+        if (K == 1) {
+            LM_HIP(hipMemcpyAsync(tokens, bos.data(), sizeof(int64_t) * B * max_length, hipMemcpyHostToDevice, st));
+        } else {      // HF _beam_search: running scores 0, -1e9, ...; finished scores -1e9; sequences BOS then PAD
+            std::vector<float> rs(R, -1.0e9f), fs(R, -1.0e9f);
+            std::vector<int> zero((size_t)R * max_length, 0), one(B, 1);
+            for (int b = 0; b < B; ++b) rs[(size_t)b * K] = 0.f;
+            for (int i = 0; i < 2; ++i) {
+                LM_HIP(hipMemcpyAsync(w.beam.rseq[i], bos.data(), sizeof(int64_t) * R * max_length, hipMemcpyHostToDevice, st));
+                LM_HIP(hipMemcpyAsync(w.beam.fseq[i], bos.data(), sizeof(int64_t) * R * max_length, hipMemcpyHostToDevice, st));
+                LM_HIP(hipMemcpyAsync(w.beam.tab[i], zero.data(), sizeof(int) * R * max_length, hipMemcpyHostToDevice, st));
+            }
+            LM_HIP(hipMemcpyAsync(w.beam.rscore, rs.data(), sizeof(float) * R, hipMemcpyHostToDevice, st));
+            LM_HIP(hipMemcpyAsync(w.beam.fscore, fs.data(), sizeof(float) * R, hipMemcpyHostToDevice, st));
+            LM_HIP(hipMemcpyAsync(w.beam.ffin, zero.data(), sizeof(int) * R, hipMemcpyHostToDevice, st));
+            LM_HIP(hipMemcpyAsync(w.beam.flen, zero.data(), sizeof(int) * R, hipMemcpyHostToDevice, st));
+            LM_HIP(hipMemcpyAsync(w.beam.unsat, one.data(), sizeof(int) * B, hipMemcpyHostToDevice, st));
+            LM_HIP(hipStreamSynchronize(st));      // (zero, one, rs, fs go out of scope)
+        }
+        LM_HIP(hipStreamSynchronize(st));      // the host staging vectors go out of scope
     }
     const float inv_temp = do_sample ? 1.0f / temperature : 1.0f;
-    int n_tokens = max_length;
+    int n_tokens = max_length, last_step = max_length - 2;
     std::vector<int> host_flags(max_length, 0);
     int checked = 0;
     for (int step = 0; step + 1 < max_length; ++step) {
+        const int cur = step & 1;
         // token at position `step` -> logits -> token at position step + 1
         if (step == 0) {      // the BOS embedding; every later step's input row is written by the previous step's token-choice kernel
-            hipLaunchKernelGGL(lm_embed_kernel, dim3(B), dim3(256), 0, st, lm->dec.word, lm->dec.type, (const float*)nullptr, lm->dec.ln_emb.g, lm->dec.ln_emb.b,
-                               (const int64_t*)tokens, max_length, (const int64_t*)nullptr, (const int64_t*)nullptr, 0, c.eps, H, c.sem_vocab, 1, 1, w.x);
+            hipLaunchKernelGGL(lm_embed_kernel, dim3(R), dim3(256), 0, st, lm->dec.word, lm->dec.type, (const float*)nullptr, lm->dec.ln_emb.g, lm->dec.ln_emb.b,
+                               (const int64_t*)(K == 1 ? tokens : w.beam.rseq[0]), max_length, (const int64_t*)nullptr, (const int64_t*)nullptr, 0, c.eps, H,
+                               c.sem_vocab, 1, 1, w.x);
             LM_HIP(hipGetLastError());
         }
         LmRows cx{w.x, nullptr};
+        const LmBeamAttn ba{w.beam.tab[cur], K};
         for (int i = 0; i < c.dec_layers; ++i) {
-            int r = lm_layer(lm, lm->dec, lm->dec.layers[i], w, cx, B, 1, step, w.kc[i], w.vc[i], max_length, w.ckc[i], w.cvc[i], L, nullptr, enc_len, st);
+            int r = lm_layer(lm, lm->dec, lm->dec.layers[i], w, cx, R, 1, step, w.kc[i], w.vc[i], max_length, w.ckc[i], w.cvc[i], L, nullptr, enc_len, st,
+                             K > 1 ? &ba : nullptr);
             if (r != LDS_OK) return r;
         }
         // LM head: h = GELU(W_t LN(x)) stored un-normalised, logits = W_d LN(h)
-        LM_HIP(lm_dln<1>(lm->head_t, cx, H, nullptr, c.eps, w.ctx, H, B, st));
+        LM_HIP(lm_dln<1>(lm->head_t, cx, H, nullptr, c.eps, w.ctx, H, R, st));
         const LmRows hrows{w.ctx, &lm->head_ln};
         float* lg = logits_out ? logits_out + (size_t)step * B * V : w.logits;
-        LM_HIP(lm_dln<0>(lm->head_d, hrows, H, nullptr, c.eps, lg, V, B, st));
-        if (do_sample && top_k == 0)
-            hipLaunchKernelGGL(lm_sample_full_kernel, dim3(B), dim3(256), sizeof(float) * V, st, lg, V, top_p, inv_temp, repetition_penalty, uniforms + (size_t)step * B,
-                               tokens, max_length, step, unfinished, c.sem_eos, c.sem_pad, any_unf, lm->dec.word, lm->dec.type, lm->dec.ln_emb.g, lm->dec.ln_emb.b,
-                               c.eps, H, w.x);
-        else if (V <= 256 * 9)
-            hipLaunchKernelGGL(lm_sample_kernel<9>, dim3(B), dim3(256), 0, st, lg, V, do_sample, do_sample ? top_k : 1, top_p, inv_temp, repetition_penalty,
-                               do_sample ? uniforms + (size_t)step * B : nullptr, tokens, max_length, step, unfinished, c.sem_eos, c.sem_pad, any_unf,
-                               lm->dec.word, lm->dec.type, lm->dec.ln_emb.g, lm->dec.ln_emb.b, c.eps, H, w.x);
-        else if (V <= 256 * 17)      // (the reference's 4096-entry semantic codebook + 3 special ids)
-            hipLaunchKernelGGL(lm_sample_kernel<17>, dim3(B), dim3(256), 0, st, lg, V, do_sample, do_sample ? top_k : 1, top_p, inv_temp, repetition_penalty,
-                               do_sample ? uniforms + (size_t)step * B : nullptr, tokens, max_length, step, unfinished, c.sem_eos, c.sem_pad, any_unf,
-                               lm->dec.word, lm->dec.type, lm->dec.ln_emb.g, lm->dec.ln_emb.b, c.eps, H, w.x);
-        else
-            hipLaunchKernelGGL(lm_sample_kernel<32>, dim3(B), dim3(256), 0, st, lg, V, do_sample, do_sample ? top_k : 1, top_p, inv_temp, repetition_penalty,
-                               do_sample ? uniforms + (size_t)step * B : nullptr, tokens, max_length, step, unfinished, c.sem_eos, c.sem_pad, any_unf,
-                               lm->dec.word, lm->dec.type, lm->dec.ln_emb.g, lm->dec.ln_emb.b, c.eps, H, w.x);
-        LM_HIP(hipGetLastError());
-        // EOS poll every 8 steps: the loop ends after the step in which the last running sequence emitted EOS
+        LM_HIP(lm_dln<0>(lm->head_d, hrows, H, nullptr, c.eps, lg, V, R, st));
+        if (K == 1) {
+            LM_HIP(lm_launch_choice(o, B, V, lg, inv_temp, do_sample ? uniforms + (size_t)step * B : nullptr, tokens, max_length, step, unfinished, c.sem_eos,
+                                    c.sem_pad, any_unf, lm->dec.word, lm->dec.type, lm->dec.ln_emb.g, lm->dec.ln_emb.b, c.eps, H, w.x, st));
+        } else {
+            const int nxt = cur ^ 1;
+            const LmBeamState bs{w.beam.rseq[cur], w.beam.rseq[nxt], w.beam.rscore, w.beam.rscore, w.beam.tab[cur], w.beam.tab[nxt], w.beam.fseq[cur],
+                                 w.beam.fseq[nxt], w.beam.fscore, w.beam.fscore, w.beam.ffin, w.beam.ffin, w.beam.flen, w.beam.flen, w.beam.unsat,
+                                 w.beam.unsat, nullptr, step ? any_unf + step - 1 : nullptr, any_unf + step};
+            LM_HIP(lm_launch_beam_step(B, K, V, lg, step, max_length, max_length, c.sem_eos, o.repetition_penalty, o.no_repeat_ngram_size, o.early_stopping, bs,
+                                       lm->dec.word, lm->dec.type, lm->dec.ln_emb.g, lm->dec.ln_emb.b, c.eps, H, w.x, st));
+        }
+        // EOS poll every 8 steps: the loop ends after the step in which the last running sequence emitted EOS (beam search: after the step
+        // at which HF's loop condition turned false; the steps enqueued after it change nothing)
         if ((step & 7) == 7 || step + 2 == max_length) {
             LM_HIP(hipMemcpyAsync(host_flags.data() + checked, any_unf + checked, sizeof(int) * (step + 1 - checked), hipMemcpyDeviceToHost, st));
             LM_HIP(hipStreamSynchronize(st));
             bool done = false;
-            for (int s = checked; s <= step; ++s)
-                if (!host_flags[s]) { n_tokens = s + 2; done = true; break; }
+            for (int s = checked; s <= step; ++s) {
+                const int f = host_flags[s];
+                const bool running = (K == 1) ? f != 0 : (!(f & 8) && (f & 1) && (o.early_stopping != 1 || (f & 2)) && (f & 4));
+                if (!running) { n_tokens = s + 2; last_step = s; done = true; break; }
+            }
             checked = step + 1;
             if (done) break;
         }
     }
+    if (K > 1) {      // the best finished hypothesis of every item (slot 0), cropped to the longest one; BOS first, EOS kept, PAD after it
+        const int64_t* best = w.beam.fseq[(last_step + 1) & 1];
+        std::vector<int> flen(R, 0);
+        LM_HIP(hipMemcpy2DAsync(tokens, sizeof(int64_t) * max_length, best, sizeof(int64_t) * max_length * K, sizeof(int64_t) * max_length, B,
+                                hipMemcpyDeviceToDevice, st));
+        LM_HIP(hipMemcpyAsync(flen.data(), w.beam.flen, sizeof(int) * R, hipMemcpyDeviceToHost, st));
+        LM_HIP(hipStreamSynchronize(st));
+        int gen = 0;
+        for (int b = 0; b < B; ++b) gen = flen[(size_t)b * K] > gen ? flen[(size_t)b * K] : gen;
+        n_tokens = 1 + gen;
+    }
     *n_tokens_host = n_tokens;
     return LDS_OK;
+}
+
+extern "C" int lds_lm_generate(lds_lm* lm, const float* enc, const int32_t* enc_len, int B, int L, int max_length, int do_sample, int top_k, float top_p,
+                               float temperature, float repetition_penalty, const float* uniforms, int64_t* tokens, float* logits_out, int* n_tokens_host,
+                               void* ws, size_t ws_bytes, void* stream) {
+    const lds_lm_decode_opts o{do_sample, top_k, top_p, temperature, repetition_penalty, 0, 1, 1};
+    return lds_lm_generate_opts(lm, enc, enc_len, B, L, max_length, &o, uniforms, tokens, logits_out, n_tokens_host, ws, ws_bytes, stream);
 }
 
 // Test entry (include/lds_test.h): ONE token choice per row of `logits` [B][V] with the generate loop's own kernels, after a history of n_hist tokens
@@ -1017,4 +1464,30 @@ extern "C" int lds_test_lm_sample(const float* logits, int B, int V, int do_samp
     (void)hipFree(seq);
     (void)hipFree(flags);
     return rc;
+}
+
+// Test entry (include/lds_test.h): ONE beam-search step (lm_beam_step_kernel) on logits [B * K][V] and the given state (all dev); the step is
+// cur_len - 1 (history = the first cur_len ids of every running sequence, sequences [B * K][max_length] int64).  Outputs as in the kernel;
+// parent_out [B * K] = parent beam (0 .. K - 1) of every new running beam; flag_out [1] = the step's bits (1 | 2 | 4, see lm_beam_step_kernel).
+extern "C" int lds_test_lm_beam_step(const float* logits, int B, int K, int V, int cur_len, int max_length, int eos, float repetition_penalty,
+                                     int no_repeat_ngram_size, int early_stopping, const int64_t* run_seq, const float* run_score, const int64_t* fin_seq,
+                                     const float* fin_score, const int32_t* fin_flag, const int32_t* fin_len, const int32_t* unsat, int64_t* run_seq_out,
+                                     float* run_score_out, int32_t* parent_out, int64_t* fin_seq_out, float* fin_score_out, int32_t* fin_flag_out,
+                                     int32_t* fin_len_out, int32_t* unsat_out, int32_t* flag_out, void* stream) {
+    if (!logits || !run_seq || !run_score || !fin_seq || !fin_score || !fin_flag || !fin_len || !unsat || !run_seq_out || !run_score_out || !parent_out ||
+        !fin_seq_out || !fin_score_out || !fin_flag_out || !fin_len_out || !unsat_out || !flag_out)
+        return lm_fail(LDS_EINVAL, "null argument");
+    if (B <= 0 || K < 1 || K > kMaxBeams || V < 2 * K || V > kMaxBeamVocab || cur_len < 1 || cur_len >= max_length || no_repeat_ngram_size < 0 ||
+        early_stopping < 0 || early_stopping > 2)
+        return lm_fail(LDS_EINVAL, "bad argument");
+    hipStream_t st = (hipStream_t)stream;
+    const LmBeamState bs{run_seq, run_seq_out, run_score, run_score_out, nullptr, nullptr, fin_seq, fin_seq_out, fin_score, fin_score_out, fin_flag, fin_flag_out,
+                         fin_len, fin_len_out, unsat, unsat_out, parent_out, nullptr, flag_out};
+    if (hipMemsetAsync(flag_out, 0, sizeof(int32_t), st) != hipSuccess) return lm_fail(LDS_EHIP, "memset");
+    const float* nf = nullptr;
+    if (lm_launch_beam_step(B, K, V, logits, cur_len - 1, max_length, max_length, eos, repetition_penalty, no_repeat_ngram_size, early_stopping, bs, nf, nf, nf, nf,
+                            0.f, 0, nullptr, st) != hipSuccess)
+        return lm_fail(LDS_EHIP, "launch");
+    if (hipStreamSynchronize(st) != hipSuccess) return lm_fail(LDS_EHIP, "sync");
+    return LDS_OK;
 }

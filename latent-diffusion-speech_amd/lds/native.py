@@ -32,6 +32,14 @@ class LMCfg(C.Structure):
                 ("eps", C.c_float), ("sem_bos", C.c_int), ("sem_eos", C.c_int), ("sem_pad", C.c_int)]
 
 
+class LMDecodeOpts(C.Structure):
+    _fields_ = [("do_sample", C.c_int), ("top_k", C.c_int), ("top_p", C.c_float), ("temperature", C.c_float), ("repetition_penalty", C.c_float),
+                ("no_repeat_ngram_size", C.c_int), ("num_beams", C.c_int), ("early_stopping", C.c_int)]
+
+
+EARLY_STOPPING = {True: 1, False: 0, "never": 2}
+
+
 class ConvTest(C.Structure):
     _fields_ = [("x1", C.c_void_p), ("x2", C.c_void_p), ("C1", C.c_int), ("C2", C.c_int), ("Tsrc", C.c_int),
                 ("w", C.c_void_p), ("bias", C.c_void_p), ("Co", C.c_int), ("K", C.c_int), ("pad", C.c_int), ("dil", C.c_int),
@@ -53,7 +61,7 @@ EXPORTS = [
     "lds_lm_generate", "lds_prof_enable", "lds_prof_summary", "lds_unet_set_gemm_mode", "lds_unet_get_gemm_mode",
     "lds_unet_set_latency_mode", "lds_unet_get_latency_mode", "lds_unet_forward_ragged", "lds_sampler_run_ragged", "lds_vocoder_forward_ragged",
     "lds_vae_encoder_create", "lds_vae_encoder_destroy", "lds_vae_encoder_workspace_bytes", "lds_vae_encoder_forward",
-    "lds_vae_encoder_forward_ragged"]
+    "lds_vae_encoder_forward_ragged", "lds_lm_workspace_bytes_opts", "lds_lm_generate_opts"]
 # include/lds_test.h: single-op entry points for tests/ and tools/ (not part of the drop-in boundary)
 TEST_EXPORTS = [
     "lds_test_conv", "lds_test_dconv", "lds_bench_dconv", "lds_test_gn_apply", "lds_bench_gn_stream", "lds_test_gn_chain_k4p",
@@ -62,7 +70,7 @@ TEST_EXPORTS = [
     "lds_test_split_roundtrip", "lds_test_gn_apply_split", "lds_debug_set_split_rule", "lds_test_attention_f16math",
     "lds_test_attention_latency", "lds_debug_set_gn_fold", "lds_debug_set_voc_pair", "lds_debug_set_touch_weights", "lds_test_voc_pair", "lds_test_gn_fold_k4p", "lds_bench_dconv_alt", "lds_debug_fill_u32", "lds_debug_trace",
     "lds_debug_trace_count", "lds_debug_trace_get", "lds_debug_unet_plan", "lds_test_gn_fold_split", "lds_test_cluster_join", "lds_test_lm_sample",
-    "lds_test_conv_down", "lds_test_conv_down_ragged"]
+    "lds_test_conv_down", "lds_test_conv_down_ragged", "lds_test_lm_beam_step"]
 
 
 def lib():
@@ -564,9 +572,12 @@ class LM:
             _lib.lds_lm_destroy(self.h)
             self.h = None
 
-    def _ws(self, B, L, max_length, device):
+    def _ws(self, B, L, max_length, device, num_beams=1):
         nb = C.c_size_t()
-        check(lib().lds_lm_workspace_bytes(self.h, B, L, max_length, C.byref(nb)))
+        if num_beams == 1:
+            check(lib().lds_lm_workspace_bytes(self.h, B, L, max_length, C.byref(nb)))
+        else:
+            check(lib().lds_lm_workspace_bytes_opts(self.h, B, L, max_length, int(num_beams), C.byref(nb)))
         return self.ws.get(nb.value, device)
 
     def encode(self, phone, tone, spk_id=None, enc_len=None):
@@ -581,17 +592,26 @@ class LM:
                                   _dev(enc_len, torch.int32) if enc_len is not None else None, _dev(enc), _dev(ws), C.c_size_t(ws.numel()), B, L, _stream()))
         return enc
 
-    def generate(self, enc, max_length, do_sample, top_k, top_p, temperature, repetition_penalty, uniforms=None, return_logits=False, enc_len=None):
+    def generate(self, enc, max_length, do_sample, top_k, top_p, temperature, repetition_penalty, uniforms=None, return_logits=False, enc_len=None,
+                 num_beams=1, no_repeat_ngram_size=0, early_stopping=True):
+        """num_beams > 1: greedy beam search (do_sample False); enc / enc_len stay one row per batch item (include/lds.h lds_lm_decode_opts)"""
         import torch
         B, L, _ = enc.shape
-        ws = self._ws(B, L, max_length, enc.device)
+        o = LMDecodeOpts(1 if do_sample else 0, int(top_k or 0), float(top_p), float(temperature), float(repetition_penalty), int(no_repeat_ngram_size),
+                         int(num_beams), EARLY_STOPPING.get(early_stopping, -1))
+        ws = self._ws(B, L, max_length, enc.device, num_beams)
         tokens = torch.empty(B, max_length, dtype=torch.int64, device=enc.device)
         logits = torch.empty(max_length - 1, B, self.cfg["sem_vocab"], dtype=torch.float32, device=enc.device) if return_logits else None
         n = C.c_int()
-        check(lib().lds_lm_generate(self.h, _dev(enc.contiguous(), torch.float32), _dev(enc_len, torch.int32) if enc_len is not None else None, B, L,
-                                    int(max_length), 1 if do_sample else 0, int(top_k or 0),
-                                    C.c_float(top_p), C.c_float(temperature), C.c_float(repetition_penalty),
-                                    _dev(uniforms.contiguous(), torch.float32) if uniforms is not None else None, _dev(tokens),
-                                    _dev(logits) if logits is not None else None, C.byref(n), _dev(ws), C.c_size_t(ws.numel()), _stream()))
+        el = _dev(enc_len, torch.int32) if enc_len is not None else None
+        u = _dev(uniforms.contiguous(), torch.float32) if uniforms is not None else None
+        lg = _dev(logits) if logits is not None else None
+        if num_beams == 1 and no_repeat_ngram_size == 0:      # the plain decode (lds_lm_generate_opts' wrapper)
+            check(lib().lds_lm_generate(self.h, _dev(enc.contiguous(), torch.float32), el, B, L, int(max_length), o.do_sample, o.top_k, C.c_float(o.top_p),
+                                        C.c_float(o.temperature), C.c_float(o.repetition_penalty), u, _dev(tokens), lg, C.byref(n), _dev(ws),
+                                        C.c_size_t(ws.numel()), _stream()))
+        else:
+            check(lib().lds_lm_generate_opts(self.h, _dev(enc.contiguous(), torch.float32), el, B, L, int(max_length), C.byref(o), u, _dev(tokens), lg,
+                                             C.byref(n), _dev(ws), C.c_size_t(ws.numel()), _stream()))
         toks = tokens[:, : n.value].contiguous()
         return toks, (logits[: n.value - 1] if logits is not None else None)

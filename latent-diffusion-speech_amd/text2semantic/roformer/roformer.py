@@ -4,7 +4,8 @@ RoFormerForCausalLM (+ cross-attention) through GenerationMixin; here the encode
 token choice run in liblds (csrc/lm.hip).  torch keeps the parameters and draws the sampling uniforms.
 
 Scope: phone mode (the 'text' mode fetches a BERT tokenizer from the hub), inference only (`forward` = teacher-forced training
-path), num_beams = 1, no n-gram blocking, no end gate, no padding mask -- what 22_infer_tts.py:83-98 uses."""
+path), right-padded batches; greedy decoding, sampling and greedy beam search (num_beams 2 .. 8), each with optional n-gram blocking.
+Not built: beam sampling and the end gate (see `generate`)."""
 import numpy as np
 import torch
 from torch import nn
@@ -123,8 +124,24 @@ class Roformer(ParamTree):
     def generate(self, phone, tone, attention_mask=None, use_cache=None, max_length=1024, do_sample=True, temperature=1.0, top_k=5, top_p=0.8,
                  repetition_penalty=1.2, num_beams=1, no_repeat_ngram_size=0, early_stopping=True, spk_id=None, end_gate_threshold=None,
                  return_logits=False, **kwargs):
-        if num_beams != 1 or no_repeat_ngram_size != 0 or end_gate_threshold is not None:
-            raise NotImplementedError("beam search, n-gram blocking and the end gate are not built (22_infer_tts.py uses none of them)")
+        if end_gate_threshold is not None:
+            # reference roformer.py:49-57 sets the WHOLE score row to +inf once softmax(scores)[eos] passes the threshold: greedy then picks
+            # token 0 and sampling makes torch.multinomial raise on NaN probabilities -- there is no coherent behaviour to restate
+            raise NotImplementedError("the end gate is not built: the reference's EndGateLogitsProcessor sets the whole score row to +inf, "
+                                      "after which greedy picks token 0 and sampling raises")
+        if isinstance(num_beams, bool) or not isinstance(num_beams, (int, np.integer)) or not 1 <= num_beams <= 8:
+            raise ValueError(f"num_beams must be an integer in 1 .. 8, got {num_beams!r}")
+        if isinstance(no_repeat_ngram_size, bool) or not isinstance(no_repeat_ngram_size, (int, np.integer)) or no_repeat_ngram_size < 0:
+            raise ValueError(f"no_repeat_ngram_size must be an integer >= 0, got {no_repeat_ngram_size!r}")
+        num_beams, no_repeat_ngram_size = int(num_beams), int(no_repeat_ngram_size)
+        if num_beams > 1 and do_sample:
+            # HF draws 2 * num_beams candidates without replacement through torch.multinomial; the inverse-CDF draw over recorded uniforms
+            # that stands in for the single-sample draw has no agreed form for more than one sample
+            raise NotImplementedError("beam sampling (num_beams > 1 with do_sample=True) is not built; pass do_sample=False for greedy beam search")
+        if num_beams > 1 and return_logits:
+            raise NotImplementedError("return_logits is not available with num_beams > 1")
+        if num_beams > 1 and early_stopping not in (True, False, "never"):
+            raise ValueError(f"early_stopping must be True, False or 'never', got {early_stopping!r}")
         # top_k as HF's TopKLogitsWarper: None / 0 = no filter (the draw runs over the whole vocabulary), k keeps the k largest scores and every
         # score tied with the k-th (22_infer_tts.py:83-98 passes top_k = 5); more than 64 survivors are not built
         top_k = 0 if top_k is None else int(top_k)
@@ -136,5 +153,7 @@ class Roformer(ParamTree):
         enc = self.native().encode(phone, tone, spk_id if self.spk_emb_enabled else None, enc_len)
         B = enc.shape[0]
         uniforms = torch.rand(max_length - 1, B, device=enc.device) if do_sample else None      # one draw per step and sequence
-        toks, logits = self.native().generate(enc, max_length, do_sample, top_k, top_p, temperature, repetition_penalty, uniforms, return_logits, enc_len)
+        # beams: enc and enc_len stay one row per item; the library maps beam row r to item r // num_beams
+        toks, logits = self.native().generate(enc, max_length, do_sample, top_k, top_p, temperature, repetition_penalty, uniforms, return_logits, enc_len,
+                                              num_beams=num_beams, no_repeat_ngram_size=no_repeat_ngram_size, early_stopping=early_stopping)
         return (toks, logits) if return_logits else toks

@@ -1,4 +1,13 @@
-"""Decode-step time of the text2semantic RoFormer (synthetic weights): 512 sampled tokens, batch 1 and 8."""
+"""Decode-step time of the text2semantic RoFormer (synthetic weights): 512 sampled tokens, batch 1 and 8.
+
+  --num_beams K        greedy beam search with K beams instead of sampling (1: sampling, or greedy with --greedy)
+  --tokens N [N ...]   decode lengths; two of them show whether the cost of a step grows with the position
+  --lib PATH           time another build of liblds.so (a previous commit: only the plain decode, which it has)
+
+With --num_beams > 1, --greedy, or more than one length the EOS logit is biased far down, so that every sequence runs to the full
+length and the time per step is that of a full decode."""
+import argparse
+import ctypes
 import os
 import sys
 import time
@@ -10,15 +19,44 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 import infer_tts  # noqa: E402
+from lds import native  # noqa: E402
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--batch", type=int, nargs="*", default=[1, 8])
+ap.add_argument("--num_beams", type=int, default=1)
+ap.add_argument("--greedy", action="store_true")
+ap.add_argument("--no_repeat_ngram_size", type=int, default=0)
+ap.add_argument("--tokens", type=int, nargs="*", default=[512])
+ap.add_argument("--lib", default=None)
+a = ap.parse_args()
+if a.lib:
+    native.LIB_PATH = os.path.abspath(a.lib)
+    have = ctypes.CDLL(native.LIB_PATH)
+    native.EXPORTS = [n for n in native.EXPORTS if hasattr(have, n)]
+    native.TEST_EXPORTS = [n for n in native.TEST_EXPORTS if hasattr(have, n)]
 
 lm = infer_tts.synthetic_lm("cuda")
-for B in (1, 8):
+if a.num_beams > 1 or a.greedy or len(a.tokens) > 1:
+    with torch.no_grad():
+        lm.semantic_decoder.cls.predictions.bias[lm.semantic_eos_token_id] -= 1.0e4
+mode = f"beam search K {a.num_beams}" if a.num_beams > 1 else "greedy" if a.greedy else "sampled"
+
+
+def decode(ph, tn, n):
+    kw = dict(attention_mask=None, use_cache=None, max_length=n + 1, temperature=1.0, top_k=5, top_p=1.0, repetition_penalty=1.0,
+              num_beams=a.num_beams, no_repeat_ngram_size=a.no_repeat_ngram_size, early_stopping=True, spk_id=torch.ones_like(ph), end_gate_threshold=None)
+    return lm.generate(ph, tn, do_sample=a.num_beams == 1 and not a.greedy, **kw)
+
+
+for B in a.batch:
     ph = torch.from_numpy((np.arange(B * 64).reshape(B, 64) * 7 % 107 + 1).astype(np.int64)).cuda()
     tn = torch.from_numpy((np.arange(B * 64).reshape(B, 64) * 5 % 12).astype(np.int64)).cuda()
-    infer_tts.text2semantic(lm, ph, tn, 1, 65)
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    tok = infer_tts.text2semantic(lm, ph, tn, 1, 513)
-    torch.cuda.synchronize()
-    dt = time.perf_counter() - t0
-    print(f"B {B}: {tuple(tok.shape)} {dt * 1e3:.1f} ms, {dt * 1e6 / 512:.1f} us/step, {B * 512 / dt:.0f} tokens/s")
+    for n in a.tokens:
+        decode(ph, tn, 64)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        tok = decode(ph, tn, n)
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        steps = tok.shape[1] - 1
+        print(f"B {B} {mode}: {tuple(tok.shape)} {dt * 1e3:.1f} ms, {dt * 1e6 / steps:.1f} us/step, {B * steps / dt:.0f} tokens/s")
