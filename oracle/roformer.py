@@ -140,11 +140,12 @@ def pick_token(logits, do_sample, top_k, u):
     return int(min(np.searchsorted(c, f32(u), side="right"), len(c) - 1))
 
 
-def pick_token_hf(logits, history, top_k, top_p, temperature, repetition_penalty, u):
+def pick_token_hf(logits, history, top_k, top_p, temperature, repetition_penalty, u, with_cdf=False):
     """One draw the way HF's GenerationMixin._sample forms it (transformers logits_process.py): RepetitionPenaltyLogitsProcessor over the distinct
     tokens of `history` -> TemperatureLogitsWarper -> TopKLogitsWarper (top_k None / 0: no filter; else scores BELOW the k-th largest are removed, so
     ties of the k-th survive) -> TopPLogitsWarper (ascending order, drop while the cumulative probability stays <= 1 - top_p, keep the largest) ->
-    softmax -> inverse-CDF draw in vocabulary order with the uniform u (float32 sequential sums, like the kernels)."""
+    softmax -> inverse-CDF draw in vocabulary order with the uniform u (float32 sequential sums, like the kernels).  with_cdf: returns
+    (token, the cumulative sums the draw walks), so that a caller can see how far u lies from the nearest step."""
     s = np.asarray(logits, dtype=f32).copy()
     if repetition_penalty != 1.0:
         for t in sorted(set(int(t) for t in history)):
@@ -177,7 +178,8 @@ def pick_token_hf(logits, history, top_k, top_p, temperature, repetition_penalty
         ids, p = ids[:kept], (p[:kept] / tot).astype(f32)
         o = np.argsort(ids)
         c = np.cumsum(p[o], dtype=f32)
-        return int(ids[o][min(int(np.searchsorted(c, f32(u), side="right")), kept - 1)])
+        tok = int(ids[o][min(int(np.searchsorted(c, f32(u), side="right")), kept - 1)])
+        return (tok, c) if with_cdf else tok
     # no top-k filter: the whole vocabulary; the nucleus cut by VALUE (probabilities equal to the last dropped one go with it)
     p = np.exp(s - s.max()).astype(f32)
     p = (p / np.cumsum(p, dtype=f32)[-1]).astype(f32)
@@ -195,7 +197,7 @@ def pick_token_hf(logits, history, top_k, top_p, temperature, repetition_penalty
     k = int(np.searchsorted(c, f32(u), side="right"))
     if k >= len(c):
         k = int(np.nonzero(p > 0)[0][-1])
-    return k
+    return (k, c) if with_cdf else k
 
 
 def generate(w, cfg, enc, max_length, do_sample=False, top_k=5, uniforms=None, enc_len=None):

@@ -1,11 +1,13 @@
 """numpy restatement of the LM decode's n-gram ban and of one step of HF's greedy beam search (transformers generation/utils.py
-_beam_search, length_penalty 1), in the state layout of lds_test_lm_beam_step (include/lds_test.h).  fp32 throughout; top-k ties go to
-the lower (flat) index, as in csrc/lm.hip.  Shared by tests/test_cpu_lm_beam.py (checked against transformers' own helpers) and
-tests/test_gpu_lm_beam.py (the kernel against it)."""
+_beam_search, length_penalty 1), in the state layout of lds_test_lm_beam_step (include/lds_test.h), and a whole beam-search decode
+driven by it over oracle.roformer's cached decoder step.  fp32 throughout; top-k ties go to the lower (flat) index, as in csrc/lm.hip.
+Shared by tests/test_cpu_lm_beam.py (checked against transformers' own helpers and the reference's tokens), tests/test_gpu_lm_beam.py
+and tests/test_gpu_lm_long.py (the kernels against it)."""
 import numpy as np
 
 MASK = np.float32(-1.0e9)
 ZERO = np.float32(-0.0)
+MASKED = -5e8      # scores carrying one of the -1e9 masks: their order among themselves never reaches the output
 
 
 def ngram_banned(hist, n):
@@ -30,11 +32,30 @@ def _top(x, k):
     return np.argsort(-x, kind="stable")[:k]
 
 
+def _gap(x, ranks):
+    """the smallest score gap between the (r)-th and (r + 1)-th largest of x over `ranks` (1-based r), leaving out masked scores
+    (make_lm_beam_fixtures.Margins.note)"""
+    m = min(len(x), max(ranks) + 1)
+    s = np.sort(np.partition(x, len(x) - m)[len(x) - m:])[::-1]
+    g = np.inf
+    for r in ranks:
+        if r < len(s) and s[r] > MASKED and np.isfinite(s[r - 1]):
+            g = min(g, float(s[r - 1]) - float(s[r]))
+    return g
+
+
+def running(bits, early_stopping):
+    """_beam_search_has_unfinished_sequences from a step's flag bits"""
+    return bool(bits & 1) and (early_stopping != 1 or bool(bits & 2)) and bool(bits & 4)
+
+
 def beam_step(logits, K, cur_len, max_length, eos, rep_pen, ngram, early_stopping, run_seq, run_score, fin_seq, fin_score, fin_flag, fin_len,
               unsat):
     """one step; early_stopping 1 = True, 0 = False, 2 = "never".  Arrays: logits [B*K, V]; run_seq, fin_seq [B*K, max_length] int64;
-    run_score, fin_score [B*K] fp32; fin_flag, fin_len [B*K] int; unsat [B] int.  Returns the new state, parent [B*K] and the step's
-    flag bits (1: some item may improve, 2: some item has an unfinished slot, 4: some candidate did not hit the stopping criteria)."""
+    run_score, fin_score [B*K] fp32; fin_flag, fin_len [B*K] int; unsat [B] int.  Returns the new state, parent [B*K], the step's
+    flag bits (1: some item may improve, 2: some item has an unfinished slot, 4: some candidate did not hit the stopping criteria) and
+    "gap", the smallest score gap at a selection of the step (top 2K of K * V: ranks 2K | 2K + 1 and K | K + 1; running beams: K | K + 1;
+    finished merge: K | K + 1 and 1 | 2)."""
     R, V = logits.shape
     B = R // K
     lp = log_softmax(logits)
@@ -48,11 +69,12 @@ def beam_step(logits, K, cur_len, max_length, eos, rep_pen, ngram, early_stoppin
     acc = (lp + run_score.astype(np.float32)[:, None]).astype(np.float32)
     out = dict(run_seq=run_seq.copy(), run_score=run_score.astype(np.float32).copy(), fin_seq=fin_seq.copy(), fin_score=fin_score.astype(np.float32).copy(),
                fin_flag=fin_flag.copy(), fin_len=fin_len.copy(), unsat=unsat.copy(), parent=np.zeros(R, np.int32))
-    bits = 0
+    bits, gap = 0, np.inf
     for b in range(B):
         rows = slice(b * K, (b + 1) * K)
         flat = acc[rows].reshape(-1)
         sel = _top(flat, 2 * K)
+        gap = min(gap, _gap(flat, [2 * K, K]))
         topv, topb, topt = flat[sel], sel // V, sel % V
         hit = (topt == eos) | (cur_len + 1 >= max_length)
         trl = np.array([topv[j] + (MASK if hit[j] else ZERO) for j in range(2 * K)], np.float32)
@@ -68,6 +90,7 @@ def beam_step(logits, K, cur_len, max_length, eos, rep_pen, ngram, early_stoppin
             f[j] = v
         ms = np.concatenate([fin_score[rows].astype(np.float32), f])
         fin_j = _top(ms, K)
+        gap = min(gap, _gap(trl, [K]), _gap(ms, [K, 1]))
         for k in range(K):
             r = b * K + k
             j = run_j[k]
@@ -93,7 +116,40 @@ def beam_step(logits, K, cur_len, max_length, eos, rep_pen, ngram, early_stoppin
         out["unsat"][b] = int(bool(unsat[b]) and improve)
         bits |= (1 if out["unsat"][b] else 0) | (0 if out["fin_flag"][rows].all() else 2) | (0 if hit.all() else 4)
     out["flags"] = bits
+    out["gap"] = gap
     return out
+
+
+def generate_beam(w, cfg, enc, K, max_length, rep_pen=1.0, ngram=0, early_stopping=1, enc_len=None):
+    """greedy beam search over oracle.roformer.decoder_step the way HF's _beam_search drives it: beam_step on every step's logits, then
+    the key/value caches reordered by parent (HF's _reorder_cache), until the step's flag bits say HF's loop ends.  enc [B, L, hidden]
+    encoder states, enc_len [B] or None.  Returns (tokens [B, n]: slot 0 of every item's finished hypotheses, BOS first, cropped to the
+    longest generated length, PAD after each one's end; the smallest decision margin of the run, as make_lm_beam_fixtures.Margins)."""
+    from oracle import roformer as R
+    B = enc.shape[0]
+    N = B * K
+    eos, bos, pad = cfg["sem_eos"], cfg["sem_bos"], cfg["sem_pad"]
+    kv = [(np.repeat(k, K, axis=0), np.repeat(v, K, axis=0)) for k, v in R.cross_kv(w, cfg, enc)]
+    el = None if enc_len is None else np.repeat(np.asarray(enc_len), K)
+    caches = [dict() for _ in range(cfg["dec_layers"])]
+    run_seq = np.full((N, max_length), pad, np.int64)
+    run_seq[:, 0] = bos
+    st = dict(run_seq=run_seq, run_score=np.tile(np.array([0.0] + [-1e9] * (K - 1), np.float32), B), fin_seq=run_seq.copy(),
+              fin_score=np.full(N, -1e9, np.float32), fin_flag=np.zeros(N, np.int32), fin_len=np.zeros(N, np.int32), unsat=np.ones(B, np.int32))
+    gap = np.inf
+    for step in range(max_length - 1):
+        lg = R.decoder_step(w, cfg, st["run_seq"][:, step], step, caches, kv, el)
+        out = beam_step(lg, K, step + 1, max_length, eos, rep_pen, ngram, early_stopping, st["run_seq"], st["run_score"], st["fin_seq"],
+                        st["fin_score"], st["fin_flag"], st["fin_len"], st["unsat"])
+        gap = min(gap, out["gap"])
+        src = np.repeat(np.arange(B) * K, K) + out["parent"]
+        for c in caches:
+            c["k"], c["v"] = c["k"][src], c["v"][src]
+        st = {k: out[k] for k in st}
+        if not running(out["flags"], early_stopping):
+            break
+    n = 1 + int(st["fin_len"][::K].max())
+    return st["fin_seq"][::K, :n].copy(), gap
 
 
 def random_state(rng, B, K, V, cur_len, max_length, bos, pad, finished=0.0):

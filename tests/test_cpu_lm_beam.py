@@ -58,10 +58,6 @@ def hf_beam_step(logits, K, cur_len, max_length, eos, rep_pen, ngram, early_stop
                 parent=parent, running=running)
 
 
-def running_from_bits(bits, early_stopping):
-    return bool(bits & 1) and (early_stopping != 1 or bool(bits & 2)) and bool(bits & 4)
-
-
 CASES = [      # (B, K, V, cur_len, max_length, rep_pen, ngram, early_stopping, finished share, EOS boost)
     (3, 4, 300, 1, 24, 1.0, 0, 1, 0.0, None),          # first step: beams 1.. carry -1e9
     (3, 4, 300, 9, 24, 1.2, 3, 1, 0.3, None),           # EOS outside the top K
@@ -98,7 +94,7 @@ def test_numpy_beam_step_matches_transformers(case):
         for k in (pre + "_seq",) + extra:
             assert np.array_equal(got[k][real], want[k][real]), (k, got[k], want[k])
         np.testing.assert_allclose(got[pre + "_score"][real], want[pre + "_score"][real], rtol=1e-6, atol=0)
-    assert running_from_bits(got["flags"], es) == want["running"]
+    assert NB.running(got["flags"], es) == want["running"]
     if boost == "top" and cur_len + 1 < max_length:      # the case does what it says: EOS candidates finish
         assert (got["fin_len"] == cur_len).any()
     if cur_len + 1 >= max_length:
@@ -123,6 +119,28 @@ def test_ngram_ban_matches_transformers(n):
 def lm():
     from text2semantic.utils import get_language_model
     return get_language_model(**yaml.safe_load(open(os.path.join(GOLDEN, "config_lm_like_reference.yaml"))))
+
+
+@pytest.mark.parametrize("tag", ["beam4", "beam4_ngram3", "beam4_eos", "beam3_ragged"])
+def test_generate_beam_reproduces_the_reference(lm, golden, tag):
+    """the numpy beam-search driver (NB.generate_beam: beam_step, then the caches reordered by parent) over oracle.roformer gives the
+    reference's own tokens for every beam case of roformer_beam.npz, and the smallest decision margin the fixture recorded"""
+    from oracle import roformer as R
+    kw = {"beam4": dict(K=4, max_length=24), "beam4_ngram3": dict(K=4, max_length=24, ngram=3, rep_pen=1.2), "beam4_eos": dict(K=4, max_length=40),
+          "beam3_ragged": dict(K=3, max_length=24)}[tag]
+    g, fx = golden("roformer.npz"), golden("roformer_beam.npz")
+    cfg = lm.cfg
+    w = {k: v.detach().cpu().numpy().copy() for k, v in lm.state_dict().items()}
+    if "eos" in tag:
+        b = w["semantic_decoder.cls.predictions.bias"].copy()
+        b[cfg["sem_eos"]] += fx["eos_bias"]
+        w["semantic_decoder.cls.predictions.bias"] = w["semantic_decoder.cls.predictions.decoder.bias"] = b
+    enc_len = fx["ragged_len"] if "ragged" in tag else None
+    enc = R.encoder_forward(w, cfg, g["phone"], g["tone"], g["spk_id"], enc_len)
+    toks, gap = NB.generate_beam(w, cfg, enc, enc_len=enc_len, **kw)
+    want = fx[tag + "_tokens"]
+    assert toks.shape == want.shape and np.array_equal(toks, want), (toks.tolist(), want.tolist())
+    assert abs(gap - float(fx[tag + "_margin"])) < 5e-5, (gap, float(fx[tag + "_margin"]))
 
 
 def test_generate_beam_search_reaches_the_device_check(lm):

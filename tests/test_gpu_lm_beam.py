@@ -116,6 +116,8 @@ STEP_CASES = [      # (B, K, V, cur_len, max_length, rep_pen, ngram, early_stopp
     (4, 2, 300, 12, 13, 1.1, 1, 1, 0.4, None),
     (2, 3, 2304, 30, 64, 1.0, 4, 2, 1.0, "top"),
     (1, 5, 1000, 70, 200, 1.3, 2, 1, 0.3, "mid"),
+    (2, 4, 4099, 500, 600, 1.2, 3, 1, 0.3, "mid"),          # long histories: the penalty marks and the n-gram scan over 500 ...
+    (1, 8, 4099, 1000, 1100, 1.2, 2, 0, 0.4, "top"),        # ... and 1000 tokens, and the copies of rows that long
 ]
 
 
