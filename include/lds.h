@@ -189,6 +189,36 @@ int  lds_vae_encoder_forward(lds_vae_encoder* e, const float* audio, const float
 int  lds_vae_encoder_forward_ragged(lds_vae_encoder* e, const float* audio, const int32_t* lengths, const float* noise, float* out,
                                     float* z, int only_mean, void* ws, size_t ws_bytes, int B, int64_t L, void* stream);
 
+/* ---- units encoder: Whisper log-mel front end + AudioEncoder, audio -> units (reference tools/tools.py:43-126 Units_Encoder /
+ *      WhisperLargeV3, encoder/whisper/audio.py:62-82, encoder/whisper/model.py:112-131) -------------------------------------------
+ * names: the reference Whisper.state_dict() keys ("encoder.conv1.weight", "encoder.blocks.N.attn.query.weight", ...,
+ * "encoder.ln_post.bias"; `key` has no bias), fp32 host arrays in the reference's layouts.  mel_filters: host [n_mels][201] (the filter
+ * bank of audio.py:55-60).  Limits (LDS_EINVAL): n_mels 80 or 128, n_state a multiple of 64 with n_state / n_head == 64, 1 <= n_layer <= 64.
+ * The sinusoid table of n_ctx rows is built at create with the reference's fp32 operation order.
+ *
+ * A call takes B clips in audio dev [B][L] (16 kHz samples, L >= 400).  lengths host int32 [B] (B <= 64), 400 <= lengths[b] <= L, or NULL
+ * (every clip has L samples).  Clip b is audio[b, :lengths[b]] ENCODED ALONE: reflect padding at its own end, F_b = lengths[b] / 160 mel
+ * frames, the dynamic-range floor from its own maximum, T_b = (F_b - 1) / 2 + 1 encoder frames, attention keys stop at T_b.  Nothing at or
+ * beyond lengths[b] is read.  F = L / 160, T = (F - 1) / 2 + 1 <= n_ctx (LDS_EINVAL otherwise).  A clip's result does not depend on the
+ * other clips of the call.  Nothing synchronises; a bad argument returns before anything is enqueued; a small workspace gives LDS_ENOMEM. */
+typedef struct lds_whisper lds_whisper;
+typedef struct { int n_mels, n_state, n_head, n_layer, n_ctx; } lds_whisper_cfg;
+int  lds_whisper_create(const lds_whisper_cfg* cfg, int n_tensors, const char* const* names, const float* const* host_ptrs, const int64_t* numel,
+                        const float* mel_filters, lds_whisper** out);
+void lds_whisper_destroy(lds_whisper* w);
+/* one size for all three calls below (lds_whisper_encode_mel: L = 160 * F) */
+int  lds_whisper_workspace_bytes(const lds_whisper* w, int B, int64_t L, size_t* out);
+/* mel dev [B][n_mels][F] plain = log_mel_spectrogram of every clip; frames at and beyond F_b are zeros */
+int  lds_whisper_logmel(lds_whisper* w, const float* audio, const int32_t* lengths, float* mel, void* ws, size_t ws_bytes, int B, int64_t L,
+                        void* stream);
+/* AudioEncoder.forward: mel dev [B][n_mels][F] plain, n_frames host int32 [B] (1 <= n_frames[b] <= F; mel beyond is read as zeros) or NULL
+ * -> units dev [B][T][n_state] frame-major; rows at and beyond T_b are zeros */
+int  lds_whisper_encode_mel(lds_whisper* w, const float* mel, const int32_t* n_frames, float* units, void* ws, size_t ws_bytes, int B, int F,
+                            void* stream);
+/* both in one call (WhisperLargeV3.__call__): the log-mel goes straight into the first convolution's input layout */
+int  lds_whisper_encode(lds_whisper* w, const float* audio, const int32_t* lengths, float* units, void* ws, size_t ws_bytes, int B, int64_t L,
+                        void* stream);
+
 /* ---- text2semantic: RoFormer encoder prefill + cached autoregressive decode (reference text2semantic/roformer/roformer.py:59-255
  *      over HF transformers RoFormerModel / RoFormerForCausalLM + GenerationMixin; called from 22_infer_tts.py:76-98) ------------- */
 typedef struct lds_lm lds_lm;

@@ -92,7 +92,7 @@ struct DmaCfg {
 };
 
 // GNF: the GroupNorm fold of DmaConvArgs::gnf_part (its own instantiations: the other launches carry none of its registers)
-template <int BM, int BN, int KT, int STRIDE, bool UPS, int BK, int NST, int DIL = 1, bool VOC = false, bool GNF = false>
+template <int BM, int BN, int KT, int STRIDE, bool UPS, int BK, int NST, int DIL = 1, bool VOC = false, bool GNF = false, bool GELU = false>
 struct DmaKernel {
     using Cfg = DmaCfg<BM, BN, KT, STRIDE, UPS, BK, NST, DIL>;
     static constexpr int TM = Cfg::TM, TN = Cfg::TN, KR = Cfg::KR, XW = Cfg::XW, WPW = Cfg::WPW, RPW = Cfg::RPW, NXI = Cfg::NXI;
@@ -462,6 +462,18 @@ struct DmaKernel {
                     acc[0][0][j][r] *= 0.5f * g * (1.0f + erf_fast(g * 0.70710678118654752440f));
                 }
         }
+        if constexpr (GELU) {      // plain GELU, exact form (the Whisper encoder's conv1 / conv2 / mlp.0, reference encoder/whisper/model.py:96,122-123):
+                                   // instantiations of its own (launch_conv_dma), so that no other launch's code changes
+#pragma unroll
+            for (int i = 0; i < TM; ++i)
+#pragma unroll
+                for (int j = 0; j < TN; ++j)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const float v = acc[0][i][j][r];
+                        acc[0][i][j][r] = 0.5f * v * (1.0f + erf_fast(v * 0.70710678118654752440f));
+                    }
+        }
     }
 
     // frame-major store of one 32x32 tile: out[b][co][n], co = c0 + local row
@@ -809,11 +821,11 @@ struct DmaKernel {
     }
 };
 
-template <int BM, int BN, int KT, int STRIDE, bool UPS, int BK, int NST, int DIL = 1, bool VOC = false, bool GNF = false>
+template <int BM, int BN, int KT, int STRIDE, bool UPS, int BK, int NST, int DIL = 1, bool VOC = false, bool GNF = false, bool GELU = false>
 // (the polyphase upsampler's scatter epilogue needs more than the 128 registers of 4 workgroups per CU: 2 per CU, no spills)
 __global__ void __launch_bounds__(256, ((VOC && KT == 2) ? 2 : DmaCfg<BM, BN, KT, STRIDE, UPS, BK, NST, DIL>::OCC)) conv_dma_kernel(const DmaConvArgs p) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    DmaKernel<BM, BN, KT, STRIDE, UPS, BK, NST, DIL, VOC, GNF> k(p, smem);
+    DmaKernel<BM, BN, KT, STRIDE, UPS, BK, NST, DIL, VOC, GNF, GELU> k(p, smem);
     k.setup();
     // ragged batch: a tile that lies wholly beyond its utterance's length has nothing to reduce -- the epilogue writes its zeros (what it
     // computes from the untouched accumulators never reaches memory: masked columns are stored as literal zeros)
@@ -861,22 +873,22 @@ __global__ void __launch_bounds__(256, (PairCfg<BM, BN, BK3, BK1, NST>::OCC)) co
 static thread_local char g_dcfg[96] = "";
 const char* conv_dma_last_config() { return g_dcfg; }
 
-template <int BM, int BN, int KT, int STRIDE, bool UPS, int BK, int NST, int DIL = 1, bool VOC = false, bool GNF = false>
+template <int BM, int BN, int KT, int STRIDE, bool UPS, int BK, int NST, int DIL = 1, bool VOC = false, bool GNF = false, bool GELU = false>
 static hipError_t launch_dma_cfg(const DmaConvArgs& a, hipStream_t s) {
     using Cfg = DmaCfg<BM, BN, KT, STRIDE, UPS, BK, NST, DIL>;
-    if (GNF != (a.gnf_part != nullptr)) return hipErrorInvalidValue;
+    if (GNF != (a.gnf_part != nullptr) || GELU != (a.epi == EPI_GELU)) return hipErrorInvalidValue;
     const size_t lds_bytes = Cfg::LDS_BYTES + (GNF ? (BM + 32) * sizeof(float) : 0);      // the fold's row constants and group statistics sit behind the ring
     const int nN = (a.To + BN - 1) / BN;
     const int S = a.ksplit > 1 ? a.ksplit : 1;
     if (S > 1 && (Cfg::TM * Cfg::TN > 2 || VOC || (a.Ci / BK) % S)) return hipErrorInvalidValue;
     dim3 grid((a.Mp / BM) * nN, a.B * S);
-    auto kern = conv_dma_kernel<BM, BN, KT, STRIDE, UPS, BK, NST, DIL, VOC, GNF>;
+    auto kern = conv_dma_kernel<BM, BN, KT, STRIDE, UPS, BK, NST, DIL, VOC, GNF, GELU>;
     if (lds_bytes > 48 * 1024) {
         static std::atomic<unsigned long long> attr_done{0};
         hipError_t e = ensure_max_dynamic_lds(reinterpret_cast<const void*>(kern), attr_done);
         if (e != hipSuccess) return e;
     }
-    const char* gtag = GNF ? " GNF" : "";
+    const char* gtag = GNF ? " GNF" : GELU ? " GELU" : "";
     if (!VOC && S > 1) snprintf(g_dcfg, sizeof(g_dcfg), "BM%d BN%d KT%d S%d U%d BK%d NST%d KS%d%s grid %ux%u lds %zu", BM, BN, KT, STRIDE, (int)UPS, BK, NST, S, gtag, grid.x, grid.y, lds_bytes);
     else if (!VOC) snprintf(g_dcfg, sizeof(g_dcfg), "BM%d BN%d KT%d S%d U%d BK%d NST%d%s grid %ux%u lds %zu", BM, BN, KT, STRIDE, (int)UPS, BK, NST, gtag, grid.x, grid.y, lds_bytes);
     else snprintf(g_dcfg, sizeof(g_dcfg), "BM%d BN%d KT%d S%d U%d BK%d NST%d D%d grid %ux%u lds %zu", BM, BN, KT, STRIDE, (int)UPS, BK, NST, DIL, grid.x, grid.y, Cfg::LDS_BYTES);
@@ -1070,6 +1082,28 @@ hipError_t launch_conv_dma(const DmaConvArgs& a_, int cfg, hipStream_t s) {
 #define GCASE(BM, BN, BK, NS) if (bm == BM && bn == BN && bk == BK && nst == NS) return launch_dma_cfg<BM, BN, 1, 1, false, BK, NS, 1, false, true>(a, s)
         GCASE(32, 64, 32, 2); GCASE(32, 64, 64, 2); GCASE(64, 64, 32, 2); GCASE(64, 64, 16, 3); GCASE(128, 64, 32, 2); GCASE(128, 64, 16, 3);
 #undef GCASE
+        return hipErrorInvalidValue;
+    }
+    if (a.epi == EPI_GELU) {
+        // Plain-GELU epilogue (the Whisper encoder's conv1, conv2, mlp.0): a template flag, so that the kernels of every other launch are
+        // compiled exactly as before, and a reduced set of tiles: the picked tile where it is one of these (it is for every shape of
+        // the large-v3 encoder), else 64 x 64.  The choice depends on the shape and the nominal batch only, like dma_pick's.
+        if (a.ups || a.plain_from < a.Cout || a.out_plain) return hipErrorInvalidValue;
+#define ECASE(BM, BN, KT, ST, BK, NS) return launch_dma_cfg<BM, BN, KT, ST, false, BK, NS, 1, false, false, true>(a, s)
+        if (a.KT == 1 && a.stride == 1) {
+            if (bm == 128 && k32) ECASE(128, 64, 1, 1, 32, 2);
+            if (k32) ECASE(64, 64, 1, 1, 32, 2);
+            ECASE(64, 64, 1, 1, 16, 2);
+        } else if (a.KT == 3 && a.stride == 1) {
+            if (bm == 128 && bn == 128) ECASE(128, 128, 3, 1, 16, 2);
+            if (bm == 128 && bn == 64) ECASE(128, 64, 3, 1, 16, 2);      // (the 128 x 128 tile's summation order: dma_pick)
+            if (k32) ECASE(64, 64, 3, 1, 32, 2);
+            ECASE(64, 64, 3, 1, 16, 2);
+        } else if (a.KT == 3 && a.stride == 2) {
+            if (k32) ECASE(64, 64, 3, 2, 32, 2);
+            ECASE(64, 64, 3, 2, 16, 2);
+        }
+#undef ECASE
         return hipErrorInvalidValue;
     }
     if (cfg == 0) a.ksplit = cluster_split(a, bm, bn, a.Ci / bk, 0, 2);

@@ -15,7 +15,7 @@ namespace lds {
 // The MFMA is v_mfma_f32_32x32x2_f32 (exact fp32); A = packed weights (M = co), B = activations (N = t).
 // ---------------------------------------------------------------------------------------------
 enum { ACT_NONE = 0, ACT_LRELU = 2 };      // activation applied to the input while staging (conv_gemm)
-enum { EPI_NONE = 0, EPI_GEGLU = 1, EPI_TANH = 2 };
+enum { EPI_NONE = 0, EPI_GEGLU = 1, EPI_TANH = 2, EPI_GELU = 3 };      // EPI_GELU (conv_dma): exact-form GELU of the biased / normalised value, before the residual
 
 struct ConvArgs {
     // input: virtual channel-concat of two sources (x2 for ci >= C1)
@@ -106,7 +106,7 @@ struct DmaConvArgs {
     const float* bias;                  // packed-row bias [Mp] or null
     int Mp, Co, Ci, KT, stride, pad, ups;
     const float* res;                   // K4P residual [B][Cout(K4P part)][To] or null
-    int epi;                            // EPI_NONE | EPI_GEGLU
+    int epi;                            // EPI_NONE | EPI_GEGLU | EPI_GELU
     float* out;                         // K4P [B][min(Cout, plain_from)][To], or plain [B][Cout][To] when out_plain
     int out_plain;
     int plain_from; float* out2;        // output channels >= plain_from go frame-major to out2 [B][Cout-plain_from][To] ...
@@ -227,6 +227,22 @@ hipError_t launch_attention_k4p(const float* qk, const float* vt, float* out, in
 hipError_t launch_attention_k4p_f16math(const float* qk, const float* vt, float* out, int B, int C, int T, int heads, hipStream_t s, int tile_batch = 0);
 hipError_t launch_attention_k4p_out_bf3(const float* qk, const float* vt, void* out, int B, int C, int T, int heads, hipStream_t s, int fmt = 0, int tile_batch = 0,
                                         const int* lens = nullptr, int lvl = 0);
+
+// ---------------------------------------------------------------------------------------------
+// Whisper units encoder: front and back end (logmel.hip)
+// ---------------------------------------------------------------------------------------------
+// audio [B][L] -> Whisper's log-mel spectrogram of every clip taken alone (reference encoder/whisper/audio.py:62-82), F_b = slen[b] / 160
+// frames of Fmax = L / 160.  slen: device int32 [B] sample counts (null = L), 400 <= slen[b] <= L; nothing at or beyond slen[b] is read.
+// basis: double [400][201][2] windowed (cos, sin); filtT [201][n_mels]; scratch logspec [B][n_mels][Fmax], pmax [B][ceil(Fmax / 16)].
+// out: K4P [B][n_mels][Fmax] (out_k4p; pads and frames beyond F_b zero) or plain [B][n_mels][Fmax] (zeros beyond F_b).
+hipError_t launch_logmel(const float* audio, const int* slen, long long L, int Fmax, const double* basis, const float* filtT, int n_mels,
+                         float* logspec, float* pmax, float* out, int out_k4p, int B, hipStream_t s);
+// x (K4P [B][C][T]) += posk (the positional table as one K4P element of n_ctx frames) on frames below ragged_len(lens, b, 1, T);
+// lnpart [B][C/32][T] = the LayerNorm partials of the sum (DmaConvArgs::lnpart_out's format)
+hipError_t launch_whisper_pos(float* x, const float* posk, int n_ctx, float2* lnpart, const int* lens, int B, int C, int T, hipStream_t s);
+// out [B][T][C] frame-major = LayerNorm(x) from the partials lnpart; rows at and beyond ragged_len(lens, b, 1, T) are zeros
+hipError_t launch_whisper_ln_post(const float* x, const float2* lnpart, const float* gamma, const float* beta, float eps, float* out, const int* lens,
+                                  int B, int C, int T, hipStream_t s);
 
 // ---------------------------------------------------------------------------------------------
 // Small dense layers with N = batch columns (time embedding path)

@@ -3,6 +3,7 @@
 // kernels on the caller's stream; no allocation or synchronisation happens after *_create.
 #include "../../include/lds.h"
 #include "../../include/lds_test.h"
+#include "k4p.h"
 #include "k8b3.h"
 #include "kernels.h"
 
@@ -2293,6 +2294,289 @@ static int vae_encoder_forward_impl(lds_vae_encoder* e, const float* audio, cons
     LDS_TRY(run_down(e->post, x, Tl, 0.01f, w.y, B, st, 0, vl[nd + 1], vl[nd + 1]));      // conv_post(leaky_relu(x)) -> [B][2C][T]
     HIP_TRY(launch_vae_head(w.y, noise, out, z, B, e->cfg.inter_channels, (int)Tl, only_mean, st, vl[nd + 1]));
     return LDS_OK;
+}
+
+// ================================================================================================
+// Whisper units encoder: log-mel front end + AudioEncoder (reference encoder/whisper/audio.py:62-82, model.py:112-131,
+// tools/tools.py:105-126).  Channel-major K4P like the UNet's transformer, and built from the same launches: every LayerNorm is
+// folded into the 1x1 convolution that reads it (pack_ln_fold), q | k | v is one convolution whose value third is stored in
+// attention's VT layout, `out` and `mlp.2` add the residual and emit the next LayerNorm's partials.  Five launches per block.
+// ================================================================================================
+struct WhisperBlockW {
+    ConvW qkv, out, fc1, fc2;
+    float *qkv_c1 = nullptr, *qkv_c2 = nullptr, *fc1_c1 = nullptr, *fc1_c2 = nullptr;
+};
+struct lds_whisper {
+    lds_whisper_cfg cfg;
+    Owner own;
+    ConvW conv1, conv2;
+    std::vector<WhisperBlockW> blocks;
+    float *post_g = nullptr, *post_b = nullptr;
+    float* posk = nullptr;        // the sinusoid table as one K4P element [n_state][n_ctx]
+    double* basis = nullptr;      // [400][201] (cos, sin) times the periodic Hann window
+    float* filtT = nullptr;       // [201][n_mels]
+};
+
+constexpr int kWhisperHop = 160, kWhisperNfft = 400, kWhisperBins = 201;
+
+static int whisper_cfg_check(const lds_whisper_cfg* c) {
+    if (!c) return fail(LDS_EINVAL, "null argument");
+    if (c->n_mels != 80 && c->n_mels != 128) return fail(LDS_EINVAL, "whisper: n_mels %d (80 or 128)", c->n_mels);
+    if (c->n_state < 64 || c->n_state % 64) return fail(LDS_EINVAL, "whisper: n_state %d must be a positive multiple of 64", c->n_state);
+    if (c->n_head < 1 || c->n_state != c->n_head * 64) return fail(LDS_EINVAL, "whisper: n_state / n_head must be 64 (got %d / %d)", c->n_state, c->n_head);
+    if (c->n_layer < 1 || c->n_layer > 64) return fail(LDS_EINVAL, "whisper: n_layer %d outside 1 .. 64", c->n_layer);
+    if (c->n_ctx < 1 || c->n_ctx > 65536) return fail(LDS_EINVAL, "whisper: n_ctx %d outside 1 .. 65536", c->n_ctx);
+    return LDS_OK;
+}
+
+extern "C" int lds_whisper_create(const lds_whisper_cfg* cfg, int n, const char* const* names, const float* const* ptrs, const int64_t* numel,
+                                  const float* mel_filters, lds_whisper** out) {
+    if (!cfg || !names || !ptrs || !numel || !mel_filters || !out || n < 0) return fail(LDS_EINVAL, "null argument");
+    LDS_TRY(whisper_cfg_check(cfg));
+    const int C = cfg->n_state, M = cfg->n_mels, NC = cfg->n_ctx;
+    Tensors T;
+    for (int i = 0; i < n; ++i) T.m[names[i]] = {ptrs[i], numel[i]};
+    lds_whisper* h = new lds_whisper();
+    h->cfg = *cfg;
+    Owner& o = h->own;
+    auto vec = [&](const std::string& k, int64_t cnt) -> float* {
+        const float* p = T.get(k, cnt);
+        return p ? o.upload(std::vector<float>(p, p + cnt)) : nullptr;
+    };
+    bool ok = true;
+    {
+        const float* w1 = T.get("encoder.conv1.weight", (int64_t)C * M * 3);
+        const float* b1 = T.get("encoder.conv1.bias", C);
+        const float* w2 = T.get("encoder.conv2.weight", (int64_t)C * C * 3);
+        const float* b2 = T.get("encoder.conv2.bias", C);
+        ok = w1 && b1 && w2 && b2 && pack_conv(o, w1, b1, C, M, 3, h->conv1) && pack_conv(o, w2, b2, C, C, 3, h->conv2);
+    }
+    h->blocks.resize(cfg->n_layer);
+    for (int l = 0; l < cfg->n_layer && ok; ++l) {
+        const std::string p = "encoder.blocks." + std::to_string(l) + ".";
+        WhisperBlockW& bw = h->blocks[l];
+        const int64_t CC = (int64_t)C * C;
+        const float *ag = T.get(p + "attn_ln.weight", C), *ab = T.get(p + "attn_ln.bias", C);
+        const float *qw = T.get(p + "attn.query.weight", CC), *qb = T.get(p + "attn.query.bias", C);
+        const float* kw = T.get(p + "attn.key.weight", CC);      // (no bias: model.py:47)
+        const float *vw = T.get(p + "attn.value.weight", CC), *vb = T.get(p + "attn.value.bias", C);
+        const float *ow = T.get(p + "attn.out.weight", CC), *ob = T.get(p + "attn.out.bias", C);
+        const float *mg = T.get(p + "mlp_ln.weight", C), *mb = T.get(p + "mlp_ln.bias", C);
+        const float *f1 = T.get(p + "mlp.0.weight", 4 * CC), *f1b = T.get(p + "mlp.0.bias", 4 * C);
+        const float *f2 = T.get(p + "mlp.2.weight", 4 * CC), *f2b = T.get(p + "mlp.2.bias", C);
+        if (!ag || !ab || !qw || !qb || !kw || !vw || !vb || !ow || !ob || !mg || !mb || !f1 || !f1b || !f2 || !f2b) { ok = false; break; }
+        std::vector<float> cat((size_t)3 * CC), cb((size_t)3 * C, 0.f);
+        memcpy(cat.data(), qw, sizeof(float) * CC);
+        memcpy(cat.data() + CC, kw, sizeof(float) * CC);
+        memcpy(cat.data() + 2 * CC, vw, sizeof(float) * CC);
+        memcpy(cb.data(), qb, sizeof(float) * C);
+        memcpy(cb.data() + 2 * C, vb, sizeof(float) * C);
+        ok = pack_ln_fold(o, cat.data(), cb.data(), ag, ab, 3 * C, C, {}, bw.qkv, bw.qkv_c1, bw.qkv_c2) && pack_conv(o, ow, ob, C, C, 1, bw.out) &&
+             pack_ln_fold(o, f1, f1b, mg, mb, 4 * C, C, {}, bw.fc1, bw.fc1_c1, bw.fc1_c2) && pack_conv(o, f2, f2b, C, 4 * C, 1, bw.fc2);
+    }
+    if (ok) {
+        h->post_g = vec("encoder.ln_post.weight", C);
+        h->post_b = vec("encoder.ln_post.bias", C);
+        ok = h->post_g && h->post_b;
+    }
+    if (ok) {
+        // sinusoids(n_ctx, n_state) (model.py:35-40) with the reference's operation order in fp32: the increment is a double that torch
+        // rounds to fp32 when it multiplies the integer range; the two products (increment x index, frame x inverse timescale) are fp32
+        // products.  exp / sin / cos of those fp32 arguments are evaluated in double and rounded once, i.e. correctly rounded fp32
+        // functions: an fp32 exp that is off by one ulp moves the table by 1500 ulp at frame 1500 (1e-4), and fp32 exp implementations
+        // differ by that (torch's CPU exp is not correctly rounded for 6 of large-v3's 640 timescales), so the table is pinned to the
+        // one definition that every platform reproduces (tests/whisper_numpy.py sinusoids is the same).
+        const int half = C / 2;
+        const float ninc = (float)(-(log(10000.0) / (double)(half - 1)));
+        std::vector<float> inv(half), pk((size_t)C * (NC + 2), 0.f);
+        for (int j = 0; j < half; ++j) inv[j] = (float)exp((double)(ninc * (float)j));
+        for (int t = 0; t < NC; ++t)
+            for (int j = 0; j < half; ++j) {
+                const float st = (float)t * inv[j];
+                pk[k4p_index(C, NC, 0, j, t)] = (float)sin((double)st);
+                pk[k4p_index(C, NC, 0, half + j, t)] = (float)cos((double)st);
+            }
+        h->posk = o.upload(pk);
+        // windowed DFT basis in double (logmel.hip): bin k of sample i of a frame; the angle is reduced exactly (k * i mod 400)
+        std::vector<double> bs((size_t)kWhisperNfft * kWhisperBins * 2);
+        const double two_pi = 6.283185307179586476925286766559;
+        for (int i = 0; i < kWhisperNfft; ++i) {
+            const double win = 0.5 - 0.5 * cos(two_pi * (double)i / kWhisperNfft);      // torch.hann_window(400): periodic
+            for (int k = 0; k < kWhisperBins; ++k) {
+                const double ang = two_pi * (double)((k * i) % kWhisperNfft) / kWhisperNfft;
+                bs[((size_t)i * kWhisperBins + k) * 2] = win * cos(ang);
+                bs[((size_t)i * kWhisperBins + k) * 2 + 1] = -win * sin(ang);
+            }
+        }
+        h->basis = (double*)o.upload_bytes(bs.data(), bs.size() * sizeof(double));
+        std::vector<float> ft((size_t)kWhisperBins * M);
+        for (int m = 0; m < M; ++m)
+            for (int k = 0; k < kWhisperBins; ++k) ft[(size_t)k * M + m] = mel_filters[(size_t)m * kWhisperBins + k];
+        h->filtT = o.upload(ft);
+        ok = h->posk && h->basis && h->filtT;
+    }
+    if (!ok) {
+        std::string miss = T.missing;
+        delete h;
+        if (!miss.empty()) return fail(LDS_EMISSING, "whisper: %s", miss.c_str());
+        return fail(LDS_ENOMEM, "whisper weight upload failed");
+    }
+    *out = h;
+    return LDS_OK;
+}
+extern "C" void lds_whisper_destroy(lds_whisper* h) { delete h; }
+
+struct WhisperWs {
+    int *slen, *flen;                      // device copies of the clips' sample / mel-frame counts (<= 64 clips)
+    float *logspec, *pmax, *melk;          // front end scratch; conv1's K4P input
+    float *big;                            // conv1's output [C][F], later mlp.0's [4C][T]
+    float *xa, *xb, *qk, *v, *att;
+    float2* lnp;
+};
+// F = mel frames per clip buffer, T = (F - 1) / 2 + 1 encoder frames
+static void plan_whisper(const lds_whisper* h, Arena& A, int B, int F, WhisperWs& w) {
+    const size_t C = h->cfg.n_state, M = h->cfg.n_mels, T = (size_t)(F - 1) / 2 + 1, Bz = B;
+    w.slen = (int*)A.f(64); w.flen = (int*)A.f(64);
+    w.logspec = A.f(Bz * M * F);
+    w.pmax = A.f(Bz * ((F + 15) / 16));
+    w.melk = A.f(Bz * M * (F + 2));
+    w.big = A.f(Bz * std::max(C * (F + 2), 4 * C * (T + 2)));
+    w.xa = A.f(Bz * C * (T + 2)); w.xb = A.f(Bz * C * (T + 2));
+    w.qk = A.f(Bz * 2 * C * (T + 2));
+    w.v = A.f(Bz * (C * ((T + 3) & ~(size_t)3) + 2048));
+    w.att = A.f(Bz * C * (T + 2));
+    w.lnp = (float2*)A.f(Bz * (C / 32) * T * 2);
+    A.f(16384);      // tail slack: ragged last tiles read (masked) entries past a tensor's end
+}
+// the limits of one call: B clips in buffers of F mel frames
+static int whisper_shape_check(const lds_whisper* h, int B, int64_t F) {
+    if (!h) return fail(LDS_EINVAL, "null handle");
+    if (B < 1 || B > 65535) return fail(LDS_EINVAL, "whisper: B %d outside 1 .. 65535", B);
+    if (F < 1) return fail(LDS_EINVAL, "whisper: no mel frame (a clip needs at least 400 samples)");
+    if ((F - 1) / 2 + 1 > h->cfg.n_ctx) return fail(LDS_EINVAL, "whisper: %lld frames exceed n_ctx %d", (long long)((F - 1) / 2 + 1), h->cfg.n_ctx);
+    return LDS_OK;
+}
+extern "C" int lds_whisper_workspace_bytes(const lds_whisper* h, int B, int64_t L, size_t* out) {
+    if (!out) return fail(LDS_EINVAL, "null argument");
+    if (L < kWhisperNfft) return fail(LDS_EINVAL, "whisper: L %lld below 400 samples", (long long)L);
+    LDS_TRY(whisper_shape_check(h, B, L / kWhisperHop));
+    Arena A(nullptr, 0);
+    WhisperWs w;
+    plan_whisper(h, A, B, (int)(L / kWhisperHop), w);
+    *out = A.used;
+    return LDS_OK;
+}
+
+static int whisper_upload(const int32_t* host, int B, int* dev, hipStream_t st) {
+    float tmp[64];
+    for (int b = 0; b < B; ++b) memcpy(&tmp[b], &host[b], sizeof(int));
+    HIP_TRY(launch_set_list((float*)dev, tmp, B, st));
+    return LDS_OK;
+}
+// audio -> (mel_plain and / or units); or mel_in (plain [B][n_mels][F]) -> units.  lens_host: samples per clip (audio) or mel frames per
+// clip (mel_in); null = the buffer's length.  Every argument has been checked by the callers.
+static int whisper_run(lds_whisper* h, const float* audio, int64_t L, const float* mel_in, int F, const int32_t* lens_host, float* mel_plain,
+                       float* units, void* ws, size_t ws_bytes, int B, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    ProfChain chain;
+    Arena A(ws, ws_bytes);
+    WhisperWs w;
+    plan_whisper(h, A, B, F, w);
+    if (!A.ok) return fail(LDS_ENOMEM, "whisper workspace too small: need %zu", A.used);
+    const int C = h->cfg.n_state, M = h->cfg.n_mels, T = (F - 1) / 2 + 1;
+    const int* slen = nullptr;
+    const int* flen = nullptr;      // mel frames per clip: "level 0" of ragged_len; the encoder's frames are its level 1
+    if (lens_host) {
+        int32_t fl[64];
+        for (int b = 0; b < B; ++b) fl[b] = audio ? lens_host[b] / kWhisperHop : lens_host[b];
+        if (audio) { LDS_TRY(whisper_upload(lens_host, B, w.slen, st)); slen = w.slen; }
+        LDS_TRY(whisper_upload(fl, B, w.flen, st));
+        flen = w.flen;
+    }
+    if (audio) {
+        if (mel_plain) HIP_TRY(launch_logmel(audio, slen, L, F, h->basis, h->filtT, M, w.logspec, w.pmax, mel_plain, 0, B, st));
+        if (units) HIP_TRY(launch_logmel(audio, slen, L, F, h->basis, h->filtT, M, w.logspec, w.pmax, w.melk, 1, B, st));
+    } else {
+        HIP_TRY(launch_to_k4p(mel_in, w.melk, B, M, F, M, 0, st, flen));
+    }
+    if (!units) return LDS_OK;
+    LensScope ls(flen);
+    TileBatchScope tb(0);      // tile rules judged at the nominal batch (16 clips): a clip's units do not depend on the batch it is in
+    {
+        DOpt o;      // gelu(conv1(mel))
+        o.pad = 1; o.epi = EPI_GELU; o.lvl_in = 0; o.lvl_out = 0;
+        LDS_TRY(run_dconv(h->conv1, w.melk, M, nullptr, 0, F, o, w.big, B, st));
+    }
+    {
+        DOpt o;      // gelu(conv2(.)), stride 2: F -> T frames, a clip's F_b -> (F_b - 1) / 2 + 1
+        o.pad = 1; o.stride = 2; o.epi = EPI_GELU; o.lvl_in = 0; o.lvl_out = 1;
+        LDS_TRY(run_dconv(h->conv2, w.big, C, nullptr, 0, F, o, w.xa, B, st));
+    }
+    HIP_TRY(launch_whisper_pos(w.xa, h->posk, h->cfg.n_ctx, w.lnp, flen, B, C, T, st));
+    float* x = w.xa;
+    float* xn = w.xb;
+    for (const WhisperBlockW& bw : h->blocks) {
+        DOpt oq;      // q | k | v of attn_ln(x)
+        oq.lvl_in = oq.lvl_out = 1;
+        oq.plain_from = 2 * C; oq.out2 = w.v; oq.vt_D = 64;
+        oq.ln_part = w.lnp; oq.ln_np = C / 32; oq.ln_c1 = bw.qkv_c1; oq.ln_c2 = bw.qkv_c2;
+        LDS_TRY(run_dconv(bw.qkv, x, C, nullptr, 0, T, oq, w.qk, B, st));
+        HIP_TRY(launch_attention_k4p(w.qk, w.v, w.att, B, C, T, h->cfg.n_head, st, 0, flen, 1));
+        DOpt oo;      // x + out(.), partials for mlp_ln
+        oo.lvl_in = oo.lvl_out = 1;
+        oo.res = x; oo.lnpart_out = w.lnp;
+        LDS_TRY(run_dconv(bw.out, w.att, C, nullptr, 0, T, oo, xn, B, st));
+        DOpt o1;      // gelu(mlp.0(mlp_ln(.)))
+        o1.lvl_in = o1.lvl_out = 1;
+        o1.epi = EPI_GELU;
+        o1.ln_part = w.lnp; o1.ln_np = C / 32; o1.ln_c1 = bw.fc1_c1; o1.ln_c2 = bw.fc1_c2;
+        LDS_TRY(run_dconv(bw.fc1, xn, C, nullptr, 0, T, o1, w.big, B, st));
+        DOpt o2;      // + mlp.2(.), partials for the next block's attn_ln / ln_post
+        o2.lvl_in = o2.lvl_out = 1;
+        o2.res = xn; o2.lnpart_out = w.lnp;
+        LDS_TRY(run_dconv(bw.fc2, w.big, 4 * C, nullptr, 0, T, o2, x, B, st));
+    }
+    HIP_TRY(launch_whisper_ln_post(x, w.lnp, h->post_g, h->post_b, 1e-5f, units, flen, B, C, T, st));
+    return LDS_OK;
+}
+
+// argument checks shared by the audio entries; *F_out = mel frames of the buffers
+static int whisper_audio_check(const lds_whisper* h, const float* audio, const int32_t* lengths, const void* ws, int B, int64_t L, int* F_out) {
+    if (!h || !audio || !ws) return fail(LDS_EINVAL, "null argument");
+    if (L < kWhisperNfft || L > ((int64_t)1 << 30)) return fail(LDS_EINVAL, "whisper: L %lld outside 400 .. 2^30 samples", (long long)L);
+    LDS_TRY(whisper_shape_check(h, B, L / kWhisperHop));
+    if (lengths) {
+        if (B > 64) return fail(LDS_EINVAL, "per-clip lengths: at most 64 clips per call (got %d)", B);
+        for (int b = 0; b < B; ++b)
+            if (lengths[b] < kWhisperNfft || lengths[b] > L) return fail(LDS_EINVAL, "length[%d] = %d outside 400 .. %lld", b, lengths[b], (long long)L);
+    }
+    *F_out = (int)(L / kWhisperHop);
+    return LDS_OK;
+}
+extern "C" int lds_whisper_logmel(lds_whisper* h, const float* audio, const int32_t* lengths, float* mel, void* ws, size_t ws_bytes, int B, int64_t L,
+                                  void* stream) {
+    int F = 0;
+    if (!mel) return fail(LDS_EINVAL, "null argument");
+    LDS_TRY(whisper_audio_check(h, audio, lengths, ws, B, L, &F));
+    return whisper_run(h, audio, L, nullptr, F, lengths, mel, nullptr, ws, ws_bytes, B, stream);
+}
+extern "C" int lds_whisper_encode(lds_whisper* h, const float* audio, const int32_t* lengths, float* units, void* ws, size_t ws_bytes, int B, int64_t L,
+                                  void* stream) {
+    int F = 0;
+    if (!units) return fail(LDS_EINVAL, "null argument");
+    LDS_TRY(whisper_audio_check(h, audio, lengths, ws, B, L, &F));
+    return whisper_run(h, audio, L, nullptr, F, lengths, nullptr, units, ws, ws_bytes, B, stream);
+}
+extern "C" int lds_whisper_encode_mel(lds_whisper* h, const float* mel, const int32_t* n_frames, float* units, void* ws, size_t ws_bytes, int B, int F,
+                                      void* stream) {
+    if (!h || !mel || !units || !ws) return fail(LDS_EINVAL, "null argument");
+    LDS_TRY(whisper_shape_check(h, B, F));
+    if (n_frames) {
+        if (B > 64) return fail(LDS_EINVAL, "per-clip lengths: at most 64 clips per call (got %d)", B);
+        for (int b = 0; b < B; ++b)
+            if (n_frames[b] < 1 || n_frames[b] > F) return fail(LDS_EINVAL, "n_frames[%d] = %d outside 1 .. %d", b, n_frames[b], F);
+    }
+    return whisper_run(h, nullptr, 0, mel, F, n_frames, nullptr, units, ws, ws_bytes, B, stream);
 }
 
 // ================================================================================================

@@ -355,3 +355,78 @@ def roformer_init_state(cfg, seed=0, init_weights=None):
     for dst, src in ROFORMER_TIED.items():
         st[dst] = st[src]
     return {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in st.items()}
+
+
+# ---- Whisper units encoder (reference encoder/whisper/model.py:10-21,112-137; tools/tools.py:105-116) ----------------------------------
+# dims of the reference's configured encoder (configs/config.yaml: whisper_large_v3); the text-side fields describe the decoder the
+# reference's Whisper(dims) never builds and are carried only because ModelDimensions has them
+WHISPER_LARGE_V3_DIMS = dict(n_mels=128, n_audio_ctx=1500, n_audio_state=1280, n_audio_head=20, n_audio_layer=32, n_vocab=51866,
+                             n_text_ctx=448, n_text_state=1280, n_text_head=20, n_text_layer=32)
+
+
+def whisper_param_shapes(n_mels, n_audio_state, n_audio_layer):
+    """`Whisper(dims).state_dict()` key -> shape: the audio encoder only (`key` has no bias, model.py:47)"""
+    d = OrderedDict()
+    c = int(n_audio_state)
+    d["encoder.conv1.weight"] = (c, int(n_mels), 3)
+    d["encoder.conv1.bias"] = (c,)
+    d["encoder.conv2.weight"] = (c, c, 3)
+    d["encoder.conv2.bias"] = (c,)
+    for i in range(int(n_audio_layer)):
+        p = f"encoder.blocks.{i}."
+        d[p + "attn.query.weight"] = (c, c)
+        d[p + "attn.query.bias"] = (c,)
+        d[p + "attn.key.weight"] = (c, c)
+        d[p + "attn.value.weight"] = (c, c)
+        d[p + "attn.value.bias"] = (c,)
+        d[p + "attn.out.weight"] = (c, c)
+        d[p + "attn.out.bias"] = (c,)
+        d[p + "attn_ln.weight"] = (c,)
+        d[p + "attn_ln.bias"] = (c,)
+        d[p + "mlp.0.weight"] = (4 * c, c)
+        d[p + "mlp.0.bias"] = (4 * c,)
+        d[p + "mlp.2.weight"] = (c, 4 * c)
+        d[p + "mlp.2.bias"] = (c,)
+        d[p + "mlp_ln.weight"] = (c,)
+        d[p + "mlp_ln.bias"] = (c,)
+    d["encoder.ln_post.weight"] = (c,)
+    d["encoder.ln_post.bias"] = (c,)
+    return d
+
+
+def whisper_init_state(n_mels, n_audio_state, n_audio_layer, seed=0, init_weights=None):
+    """Build-owned seeded weights for the units encoder (no checkpoint ships): LayerNorm gains in [0.8, 1.2), LayerNorm biases in
+    [-0.1, 0.1), everything else by lds.init_weights' role rules.  `init_weights` = that module when this file is loaded by path."""
+    if init_weights is None:
+        from . import init_weights
+    import numpy as np
+    shapes = whisper_param_shapes(n_mels, n_audio_state, n_audio_layer)
+    st = init_weights.init_state(shapes, seed)
+    for k in shapes:
+        if "_ln." in k or ".ln_post." in k:
+            st[k] = init_weights.uniform(k, shapes[k], seed, 0.8, 1.2) if k.endswith(".weight") else init_weights.uniform(k, shapes[k], seed, -0.1, 0.1)
+    return {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in st.items()}
+
+
+def whisper_mel_filters(n_mels, sr=16000, n_fft=400):
+    """The filter bank of the reference's assets/mel_filters.npz ([n_mels][201], float32), computed: librosa.filters.mel(sr=16000,
+    n_fft=400, n_mels=n_mels) -- Slaney's scale (linear below 1 kHz, logarithmic above), triangles normalised to unit area -- evaluated
+    in float64 and rounded once."""
+    import numpy as np
+    assert n_mels in (80, 128), f"Unsupported n_mels: {n_mels}"
+    fftfreqs = np.linspace(0.0, sr / 2.0, 1 + n_fft // 2)
+    f_sp, min_log_hz = 200.0 / 3.0, 1000.0
+    min_log_mel, logstep = min_log_hz / f_sp, np.log(6.4) / 27.0
+
+    def hz_to_mel(f):
+        return f / f_sp if f < min_log_hz else min_log_mel + np.log(f / min_log_hz) / logstep
+
+    mels = np.linspace(hz_to_mel(0.0), hz_to_mel(sr / 2.0), n_mels + 2)
+    mel_f = np.where(mels >= min_log_mel, min_log_hz * np.exp(logstep * (mels - min_log_mel)), f_sp * mels)
+    fdiff = np.diff(mel_f)
+    ramps = mel_f[:, None] - fftfreqs[None, :]
+    w = np.zeros((n_mels, 1 + n_fft // 2))
+    for i in range(n_mels):
+        w[i] = np.maximum(0.0, np.minimum(-ramps[i] / fdiff[i], ramps[i + 2] / fdiff[i + 1]))
+    w *= (2.0 / (mel_f[2:n_mels + 2] - mel_f[:n_mels]))[:, None]
+    return w.astype(np.float32)

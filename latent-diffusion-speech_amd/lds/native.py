@@ -37,6 +37,10 @@ class LMDecodeOpts(C.Structure):
                 ("no_repeat_ngram_size", C.c_int), ("num_beams", C.c_int), ("early_stopping", C.c_int)]
 
 
+class WhisperCfg(C.Structure):
+    _fields_ = [("n_mels", C.c_int), ("n_state", C.c_int), ("n_head", C.c_int), ("n_layer", C.c_int), ("n_ctx", C.c_int)]
+
+
 EARLY_STOPPING = {True: 1, False: 0, "never": 2}
 
 
@@ -61,7 +65,8 @@ EXPORTS = [
     "lds_lm_generate", "lds_prof_enable", "lds_prof_summary", "lds_unet_set_gemm_mode", "lds_unet_get_gemm_mode",
     "lds_unet_set_latency_mode", "lds_unet_get_latency_mode", "lds_unet_forward_ragged", "lds_sampler_run_ragged", "lds_vocoder_forward_ragged",
     "lds_vae_encoder_create", "lds_vae_encoder_destroy", "lds_vae_encoder_workspace_bytes", "lds_vae_encoder_forward",
-    "lds_vae_encoder_forward_ragged", "lds_lm_workspace_bytes_opts", "lds_lm_generate_opts"]
+    "lds_vae_encoder_forward_ragged", "lds_lm_workspace_bytes_opts", "lds_lm_generate_opts", "lds_whisper_create", "lds_whisper_destroy",
+    "lds_whisper_workspace_bytes", "lds_whisper_logmel", "lds_whisper_encode_mel", "lds_whisper_encode"]
 # include/lds_test.h: single-op entry points for tests/ and tools/ (not part of the drop-in boundary)
 TEST_EXPORTS = [
     "lds_test_conv", "lds_test_dconv", "lds_bench_dconv", "lds_test_gn_apply", "lds_bench_gn_stream", "lds_test_gn_chain_k4p",
@@ -83,9 +88,10 @@ def lib():
         L = C.CDLL(LIB_PATH)
         L.lds_last_error.restype = C.c_char_p
         for n in EXPORTS + TEST_EXPORTS:
-            if n not in ("lds_last_error", "lds_unet_destroy", "lds_embed_destroy", "lds_vocoder_destroy", "lds_lm_destroy", "lds_vae_encoder_destroy"):
+            if n not in ("lds_last_error", "lds_unet_destroy", "lds_embed_destroy", "lds_vocoder_destroy", "lds_lm_destroy", "lds_vae_encoder_destroy",
+                             "lds_whisper_destroy"):
                 getattr(L, n).restype = C.c_int
-        for n in ("lds_unet_destroy", "lds_embed_destroy", "lds_vocoder_destroy", "lds_lm_destroy", "lds_vae_encoder_destroy"):
+        for n in ("lds_unet_destroy", "lds_embed_destroy", "lds_vocoder_destroy", "lds_lm_destroy", "lds_vae_encoder_destroy", "lds_whisper_destroy"):
             getattr(L, n).restype = None
             getattr(L, n).argtypes = [C.c_void_p]
         L.lds_unet_set_gemm_mode.argtypes = [C.c_void_p, C.c_int]
@@ -507,6 +513,105 @@ class VaeEncoder:
                                             _dev(out), _dev(z) if z is not None else None, int(bool(only_mean)), _dev(ws),
                                             C.c_size_t(ws.numel()), B, C.c_int64(L), _stream()))
         return out, z
+
+
+class Whisper:
+    """Whisper units encoder (lds_whisper_*): audio [B,L] at 16 kHz -> log-mel [B,n_mels,L//160] / units [B,T,n_state], T = (L//160 - 1)//2 + 1.
+    `lengths`: every clip's own sample count (host ints, 400 .. L, at most 64 clips): each clip is encoded as if alone."""
+    HOP, N_FFT = 160, 400
+
+    def __init__(self, n_mels, n_state, n_head, n_layer, n_ctx, state, mel_filters):
+        if n_mels not in (80, 128):
+            raise ValueError(f"Whisper: n_mels {n_mels} (80 or 128)")
+        if n_state % 64 or n_head < 1 or n_state != 64 * n_head:
+            raise ValueError(f"Whisper: n_state {n_state} must be 64 * n_head ({n_head})")
+        if n_layer < 1 or n_ctx < 1:
+            raise ValueError(f"Whisper: n_layer {n_layer} and n_ctx {n_ctx} must be positive")
+        mf = np.ascontiguousarray(mel_filters, dtype=np.float32)
+        if mf.shape != (n_mels, 201):
+            raise ValueError(f"Whisper: mel_filters must be [{n_mels}, 201], got {list(mf.shape)}")
+        c = WhisperCfg(n_mels, n_state, n_head, n_layer, n_ctx)
+        n, names, ptrs, numel, keep = _host_tensor_table(state)
+        self.h = C.c_void_p()
+        check(lib().lds_whisper_create(C.byref(c), n, names, ptrs, numel, C.c_void_p(mf.ctypes.data), C.byref(self.h)))
+        self.n_mels, self.n_state, self.n_ctx = n_mels, n_state, n_ctx
+        self.ws = Workspace()
+
+    def __del__(self):
+        if getattr(self, "h", None) and _lib is not None:
+            _lib.lds_whisper_destroy(self.h)
+            self.h = None
+
+    def frames(self, n_mel_frames):
+        return (int(n_mel_frames) - 1) // 2 + 1
+
+    def _check(self, B, L):
+        if B < 1:
+            raise ValueError("Whisper: an empty batch")
+        if L < self.N_FFT:
+            raise ValueError(f"Whisper: clips need at least {self.N_FFT} samples (got {L}); pad them as Units_Encoder.encode does")
+        if self.frames(L // self.HOP) > self.n_ctx:
+            raise ValueError(f"Whisper: {L} samples give {self.frames(L // self.HOP)} frames, more than n_audio_ctx {self.n_ctx}")
+
+    def lengths(self, lengths, B, L):
+        """per-clip sample counts -> host int32 [B] (include/lds.h: B <= 64, 400 .. L)"""
+        if B > 64:
+            raise ValueError(f"a ragged units batch holds at most 64 clips (got {B})")
+        a = np.ascontiguousarray(np.asarray(lengths.cpu() if hasattr(lengths, "cpu") else lengths).reshape(-1), dtype=np.int32)
+        if a.shape != (B,) or a.min() < self.N_FFT or a.max() > L:
+            raise ValueError(f"lengths must be {B} integers in {self.N_FFT} .. {L}")
+        return a
+
+    def workspace_bytes(self, B, L):
+        nb = C.c_size_t()
+        check(lib().lds_whisper_workspace_bytes(self.h, B, C.c_int64(L), C.byref(nb)))
+        return nb.value
+
+    def _ws(self, ws, B, L, device):
+        return ws if ws is not None else self.ws.get(self.workspace_bytes(B, L), device)
+
+    def logmel(self, audio, lengths=None, ws=None):
+        """audio [B,L] -> [B,n_mels,L//160] (frames at and beyond a clip's own count are zeros)"""
+        import torch
+        B, L = audio.shape
+        self._check(B, L)
+        ln = self.lengths(lengths, B, L) if lengths is not None else None
+        ws = self._ws(ws, B, L, audio.device)
+        mel = torch.empty(B, self.n_mels, L // self.HOP, dtype=torch.float32, device=audio.device)
+        check(lib().lds_whisper_logmel(self.h, _dev(audio, torch.float32), C.c_void_p(ln.ctypes.data) if ln is not None else None, _dev(mel), _dev(ws),
+                                       C.c_size_t(ws.numel()), B, C.c_int64(L), _stream()))
+        return mel
+
+    def encode_mel(self, mel, n_frames=None, ws=None):
+        """mel [B,n_mels,F] -> units [B,T,n_state]; n_frames: every clip's own mel frame count (host ints) or None"""
+        import torch
+        B, M, F = mel.shape
+        if M != self.n_mels:
+            raise ValueError(f"Whisper: mel has {M} channels, the model {self.n_mels}")
+        if B < 1 or F < 1 or self.frames(F) > self.n_ctx:
+            raise ValueError(f"Whisper: {F} mel frames give {self.frames(F)} frames, outside 1 .. n_audio_ctx {self.n_ctx}")
+        nf = None
+        if n_frames is not None:
+            if B > 64:
+                raise ValueError(f"a ragged units batch holds at most 64 clips (got {B})")
+            nf = UNet._lengths(n_frames, B, F)
+        ws = self._ws(ws, B, max(F * self.HOP, self.N_FFT), mel.device)
+        units = torch.empty(B, self.frames(F), self.n_state, dtype=torch.float32, device=mel.device)
+        check(lib().lds_whisper_encode_mel(self.h, _dev(mel, torch.float32), C.c_void_p(nf.ctypes.data) if nf is not None else None, _dev(units), _dev(ws),
+                                           C.c_size_t(ws.numel()), B, F, _stream()))
+        return units
+
+    def encode(self, audio, lengths=None, ws=None):
+        """audio [B,L] -> units [B,T,n_state] (rows at and beyond a clip's own frame count are zeros)"""
+        import torch
+        B, L = audio.shape
+        self._check(B, L)
+        ln = self.lengths(lengths, B, L) if lengths is not None else None
+        ws = self._ws(ws, B, L, audio.device)
+        units = torch.empty(B, self.frames(L // self.HOP), self.n_state, dtype=torch.float32, device=audio.device)
+        check(lib().lds_whisper_encode(self.h, _dev(audio, torch.float32), C.c_void_p(ln.ctypes.data) if ln is not None else None, _dev(units), _dev(ws),
+                                       C.c_size_t(ws.numel()), B, C.c_int64(L), _stream()))
+        return units
 
 
 def conv_down(x, w, b, stride, slope=1.0, tile=0, cfg=None):

@@ -1,7 +1,7 @@
 """`DiffusionSVC` inference facade for the TTS path: the reference's tools/infer_tools.py:9-81 with call signatures that
 are consistent with `Unit2Mel.forward` / `Vocoder.infer` (the reference's own versions raise TypeError before any compute,
-SURVEY.md 3.1).  Only what 22_infer_tts.py uses is kept: load_model, __call__, infer, mel2wav.  The speech encoders,
-volume extractor and long-audio slicing are preprocessing / SVC features outside the sampler hot path."""
+SURVEY.md 3.1).  What 22_infer_tts.py uses is kept (load_model, __call__, infer, mel2wav), plus `encode_units` on the Whisper
+units encoder.  The volume extractor and long-audio slicing are not built."""
 import numpy as np
 import torch
 
@@ -18,14 +18,26 @@ class DiffusionSVC:
         self.units_encoder = None
         self.volume_extractor = None
 
-    def load_model(self, model_path, loaded_vocoder=None, **_ignored):
+    def load_model(self, model_path, loaded_vocoder=None, units_encoder_checkpoint=None, **_ignored):
         """reference infer_tools.py:28-30 (22_infer_tts.py passes extra f0_min/f0_max keywords that the reference's own
-        method does not accept; they are accepted and ignored here)"""
+        method does not accept; they are accepted and ignored here).  The reference builds its Units_Encoder here (infer_tools.py:31-38);
+        this one only when `units_encoder_checkpoint` names the Whisper encoder's checkpoint (large-v3_encoder.pt)."""
         self.model_path = model_path
         self.model, self.vocoder, self.args = load_model_vocoder(model_path, device=self.device, loaded_vocoder=loaded_vocoder)
+        if units_encoder_checkpoint is not None:
+            from tools.tools import Units_Encoder, WhisperLargeV3
+            data = getattr(self.args, "data", None)
+            self.units_encoder = Units_Encoder(getattr(data, "encoder", "whisper_large_v3"), getattr(data, "encoder_sample_rate", 16000),
+                                               getattr(data, "encoder_hop_size", 320), device=self.device,
+                                               units_forced_mode=getattr(data, "units_forced_mode", "nearest"),
+                                               model=WhisperLargeV3(device=self.device, checkpoint=units_encoder_checkpoint))
 
     def encode_units(self, audio, sr=44100, padding_mask=None):
-        raise NotImplementedError("speech->units encoders are preprocessing, outside the sampler hot path")
+        """reference infer_tools.py:41-44: audio at `sr` -> units [T, C] on the device (Units_Encoder.encode: `sr` must be the encoder's
+        rate, resampling is not built)"""
+        if self.units_encoder is None:
+            raise NotImplementedError("no units encoder is loaded: pass units_encoder_checkpoint= to load_model, or set .units_encoder")
+        return self.units_encoder.encode(audio, sr, padding_mask=padding_mask)
 
     @torch.no_grad()
     def mel2wav(self, mel, f0=None, start_frame=0):

@@ -1,12 +1,13 @@
-"""The pieces of reference tools/tools.py that sit on the TTS inference path: the encoder-width table and
-`units_forced_alignment` (the speech encoders, volume extractor and schedulers there are preprocessing / training and out
-of scope)."""
+"""The pieces of reference tools/tools.py that are built: the encoder-width table, `units_forced_alignment`, and the Whisper
+units encoder (`Units_Encoder` / `WhisperLargeV3`, reference tools/tools.py:43-126).  The two other speech encoders, the volume
+extractor and the schedulers there are not built."""
 import math
 
 import numpy as np
 import torch
 
-from lds import native
+from encoder.whisper.model import ModelDimensions, Whisper
+from lds import arch, native
 from lds.arch import get_encoder_out_channels
 
 
@@ -43,3 +44,104 @@ def units_forced_alignment(units, audio=None, sample_rate=None, hop_size=None, n
     else:
         raise NotImplementedError(f"units_forced_mode {units_forced_mode!r} is not used on the TTS path")
     return out.squeeze(0) if squeeze else out
+
+
+class Units_Encoder:
+    """Speech -> units (reference tools/tools.py:43-103).  Built: encoder 'whisper_large_v3' in the 'nearest' / 'left' modes.
+    Deviations from the reference, each raising instead of guessing:
+      - resampling is not built: `sample_rate` must equal `encoder_sample_rate` (ValueError naming both), where the reference
+        resamples with torchaudio;
+      - the units stay on the device (the reference moves them to the CPU); CPU tensors raise, there is no CPU fallback;
+      - 'w2v-bert' needs a transformers hub download and 'xlsr_53_56k' fairseq: NotImplementedError; the 'rfa441to512' /
+        'rfa512to441' modes need librosa's resampler: NotImplementedError.
+    `model` (not in the reference): a ready WhisperLargeV3, e.g. WhisperLargeV3.synthetic(...), instead of the checkpoint."""
+
+    def __init__(self, encoder, encoder_sample_rate=16000, encoder_hop_size=320, device=None, units_forced_mode='nearest', *, model=None):
+        if device is None:
+            device = 'cuda' if torch.cuda.is_available() else 'cpu'
+        self.device = device
+        self.encoder = encoder
+        if units_forced_mode is None:
+            units_forced_mode = 'left'
+        self.units_forced_mode = units_forced_mode
+        if encoder == 'w2v-bert':
+            raise NotImplementedError("Units_Encoder: 'w2v-bert' needs transformers' from_pretrained('facebook/w2v-bert-2.0') download; not built")
+        if encoder == 'xlsr_53_56k':
+            raise NotImplementedError("Units_Encoder: 'xlsr_53_56k' needs fairseq and its checkpoint; not built")
+        if encoder != 'whisper_large_v3':
+            raise ValueError(f"[x] Unknown units encoder: {encoder}")
+        if units_forced_mode in ('rfa441to512', 'rfa512to441'):
+            raise NotImplementedError(f"units_forced_mode {units_forced_mode!r} resamples with librosa; not built")
+        self.model = model if model is not None else WhisperLargeV3(device=device)
+        self.resample_kernel = {}
+        self.encoder_sample_rate = encoder_sample_rate
+        self.encoder_hop_size = encoder_hop_size
+
+    def _check(self, name, audio, sample_rate):
+        if sample_rate != self.encoder_sample_rate:
+            raise ValueError(f"{name}: audio at {sample_rate} Hz, the encoder runs at {self.encoder_sample_rate} Hz; "
+                             "resampling is not built, resample the audio first")
+        if not torch.is_tensor(audio) or not audio.is_cuda:
+            raise RuntimeError(f"{name} needs the audio as a tensor on a HIP device (no CPU fallback)")
+
+    def encode(self, audio, sample_rate, padding_mask=None):
+        """audio [L] or [1, L] -> units [T, C] on the device (reference tools/tools.py:76-103; padding_mask is ignored as
+        WhisperLargeV3.__call__ ignores it); a clip shorter than 400 samples is zero-padded to 400 as the reference does"""
+        self._check("Units_Encoder.encode", audio, sample_rate)
+        if audio.size(-1) < 400:
+            audio = torch.nn.functional.pad(audio, (0, 400 - audio.size(-1)))
+        units = self.model(audio, padding_mask=padding_mask)
+        if units.dim() == 3 and units.shape[0] == 1:
+            units = units.squeeze(0)
+        return units
+
+    def encode_ragged(self, audio, lengths, sample_rate=None):
+        """Extension (not in the reference): audio [B, L] padded to the longest clip + every clip's own sample count (host ints, at most 64
+        clips) -> (units [B, Tmax, C], n_frames [B] int64 on the host): every clip encoded as if alone, rows beyond its own
+        n_frames[b] = (lengths[b] // 160 - 1) // 2 + 1 are zeros.  400 <= lengths[b] <= L (ValueError otherwise: pad a shorter clip with
+        zeros to 400 samples first, as encode does)."""
+        self._check("Units_Encoder.encode_ragged", audio, self.encoder_sample_rate if sample_rate is None else sample_rate)
+        return self.model.encode_ragged(audio, lengths)
+
+
+class WhisperLargeV3(torch.nn.Module):
+    """reference tools/tools.py:105-126.  `checkpoint` (the reference hard-codes this path) holds {"dims", "model_state_dict"};
+    `dims` + `state` (not in the reference) inject them directly."""
+
+    def __init__(self, device='cuda', checkpoint='pretrain/large-v3_encoder.pt', *, dims=None, state=None):
+        super().__init__()
+        self.device = device
+        if state is None:
+            print('whisper_large_v3')
+            ck = torch.load(checkpoint, map_location="cpu", weights_only=False)
+            dims, state = ModelDimensions(**ck["dims"]), ck["model_state_dict"]
+        model = Whisper(dims)
+        model.load_state_dict({k: torch.as_tensor(v) for k, v in state.items()})
+        self.hidden_dim = dims
+        self.model = model
+        self.model.eval()
+
+    @classmethod
+    def synthetic(cls, dims=None, seed=0, device='cuda'):
+        """seeded weights (lds.arch.whisper_init_state) for `dims` (default: large-v3's) -- no checkpoint ships"""
+        if dims is None:
+            dims = ModelDimensions(**arch.WHISPER_LARGE_V3_DIMS)
+        return cls(device=device, dims=dims, state=arch.whisper_init_state(dims.n_mels, dims.n_audio_state, dims.n_audio_layer, seed))
+
+    @torch.inference_mode()
+    def __call__(self, audio, padding_mask=None):
+        """audio (any shape, flattened into ONE clip as the reference's audio.view(1, -1) does) -> units [T, C] on the device"""
+        if not audio.is_cuda:
+            raise RuntimeError("WhisperLargeV3 needs the audio on a HIP device (no CPU fallback)")
+        audio = audio.reshape(1, -1).float().contiguous()
+        return self.model.encoder.native().encode(audio).squeeze(0)
+
+    @torch.inference_mode()
+    def encode_ragged(self, audio, lengths):
+        B, L = audio.shape
+        enc = self.model.encoder.native()
+        ln = enc.lengths(lengths, B, L)      # (host-side validation first: a bad length is a ValueError on any device)
+        if not audio.is_cuda:
+            raise RuntimeError("WhisperLargeV3.encode_ragged needs the audio on a HIP device (no CPU fallback)")
+        units = enc.encode(audio.float().contiguous(), ln)
+        return units, torch.from_numpy((ln.astype(np.int64) // 160 - 1) // 2 + 1)
