@@ -278,6 +278,40 @@ int lds_lm_workspace_bytes_opts(const lds_lm* lm, int B, int L, int max_length, 
 int lds_lm_generate_opts(lds_lm* lm, const float* enc, const int32_t* enc_len, int B, int L, int max_length, const lds_lm_decode_opts* opts,
                          const float* uniforms, int64_t* tokens, float* logits_out, int* n_tokens_host, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- k-means semantic tokenizer: units -> tokens and the codebook fit (reference cluster/__init__.py:13-23 get_cluster_result /
+ *      get_cluster_center_result, cluster/kmeans.py:10-50 _kpp, :108-131 euc_sim / max_sim, :184-198 the Lloyd step; called from
+ *      17_preprocess_train_cluster.py and 19_preprocess_token.py) -------------------------------------------------------------------
+ * Stateless helpers.  X dev [N][D] and C dev [K][D] are plain row-major fp32 (units as they are at the module boundary and on disk).
+ * Limits, checked before anything is enqueued (LDS_EINVAL with a message): D a multiple of 8 in 8 .. 4096, 1 <= K <= 65,536,
+ * 1 <= N <= 2,147,483,000 (all row addressing is 64-bit), K <= N for seeding, no NULL pointer except where noted; a workspace smaller
+ * than lds_kmeans_workspace_bytes(N, K, D) gives LDS_ENOMEM.  One workspace size serves all calls of the same (N, K, D); its contents
+ * on entry do not matter.  Nothing synchronises.  No floating-point atomics: every call is bit-identical on repeat. */
+int lds_kmeans_workspace_bytes(int64_t N, int K, int D, size_t* out);
+/* h dev [K] = |c_k|^2 / 2 (once per codebook; lds_kmeans_update refreshes it) */
+int lds_kmeans_prepare(const float* C, int K, int D, float* h, void* stream);
+/* labels dev int64 [N]: label[n] = argmax_k (x_n . c_k - h_k) = the nearest centre (scikit-learn's predict; the arg-max of the reference's
+ * euc_sim), the LOWEST index among exactly equal scores; best dev [N] or NULL = the winning score (|x_n|^2 - 2 best = squared distance).
+ * Exact fp32 on the MFMA; the N x K matrix is never stored.  A row's label depends on that row and the codebook only: not on N, the row's
+ * position or the other rows (NaN / Inf there included). */
+int lds_kmeans_assign(const float* X, int64_t N, const float* C, const float* h, int K, int D, int64_t* labels, float* best, void* ws, size_t ws_bytes,
+                      void* stream);
+/* the same over a ragged batch X dev [B][T][D]: lengths host int32 [B] (B <= 64, 0 <= lengths[b] <= T); rows t >= lengths[b] get pad_id (a
+ * 32-bit value; best = 0 there) whatever they hold.  Workspace of N = B * T. */
+int lds_kmeans_assign_ragged(const float* X, int B, int T, const int32_t* lengths, int64_t pad_id, const float* C, const float* h, int K, int D,
+                             int64_t* labels, float* best, void* ws, size_t ws_bytes, void* stream);
+/* One Lloyd step given labels (kmeans.py:185-198): c_grad = per-cluster mean (an empty cluster: a zero row), *error (dev float) =
+ * sum (c_grad - C)^2, lr = 1 / num_points * 0.9 + 0.1, C = C (1 - lr) + c_grad lr in place, then num_points (dev [K]) += the counts and h
+ * refreshed.  The sums run in row order per cluster (a stable counting sort of the rows by label), the error in a fixed order.  Rows whose
+ * label is outside [0, K) are ignored. */
+int lds_kmeans_update(const float* X, const int64_t* labels, int64_t N, float* C, float* h, float* num_points, int K, int D, float* error, void* ws,
+                      size_t ws_bytes, void* stream);
+/* k-means++ seeding (kmeans.py:42-49): C[0] = X[first_index]; for i >= 1 the weight of a point is its Euclidean DISTANCE (not squared, as
+ * the reference's cdist) to the nearest centre picked so far (a running minimum, fp32), and C[i] = X[j], j = the first index whose
+ * prefix sum reaches uniforms[i - 1] * total -- the prefix in double in a fixed order -- clamped to N - 1 (the reference raises there).
+ * uniforms dev [K - 1] (may be NULL when K = 1); picked dev int64 [K] or NULL receives the indices.  K dependent steps, all on the stream. */
+int lds_kmeans_seed(const float* X, int64_t N, int D, int K, int64_t first_index, const float* uniforms, float* C, int64_t* picked, void* ws,
+                    size_t ws_bytes, void* stream);
+
 /* ---- per-launch HIP-event timing for bench.py's roofline leg (off by default) ------------------
  * lds_prof_enable(1) clears and starts recording one event pair per kernel launch on the launch
  * stream; lds_prof_summary synchronises them and writes a JSON list of

@@ -66,7 +66,8 @@ EXPORTS = [
     "lds_unet_set_latency_mode", "lds_unet_get_latency_mode", "lds_unet_forward_ragged", "lds_sampler_run_ragged", "lds_vocoder_forward_ragged",
     "lds_vae_encoder_create", "lds_vae_encoder_destroy", "lds_vae_encoder_workspace_bytes", "lds_vae_encoder_forward",
     "lds_vae_encoder_forward_ragged", "lds_lm_workspace_bytes_opts", "lds_lm_generate_opts", "lds_whisper_create", "lds_whisper_destroy",
-    "lds_whisper_workspace_bytes", "lds_whisper_logmel", "lds_whisper_encode_mel", "lds_whisper_encode"]
+    "lds_whisper_workspace_bytes", "lds_whisper_logmel", "lds_whisper_encode_mel", "lds_whisper_encode", "lds_kmeans_workspace_bytes",
+    "lds_kmeans_prepare", "lds_kmeans_assign", "lds_kmeans_assign_ragged", "lds_kmeans_update", "lds_kmeans_seed"]
 # include/lds_test.h: single-op entry points for tests/ and tools/ (not part of the drop-in boundary)
 TEST_EXPORTS = [
     "lds_test_conv", "lds_test_dconv", "lds_bench_dconv", "lds_test_gn_apply", "lds_bench_gn_stream", "lds_test_gn_chain_k4p",
@@ -98,6 +99,16 @@ def lib():
         L.lds_unet_get_gemm_mode.argtypes = [C.c_void_p]
         L.lds_unet_set_latency_mode.argtypes = [C.c_void_p, C.c_int]
         L.lds_unet_get_latency_mode.argtypes = [C.c_void_p]
+        L.lds_kmeans_workspace_bytes.argtypes = [C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_size_t)]
+        L.lds_kmeans_prepare.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.lds_kmeans_assign.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                        C.c_void_p]
+        L.lds_kmeans_assign_ragged.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.lds_kmeans_update.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                        C.c_size_t, C.c_void_p]
+        L.lds_kmeans_seed.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                      C.c_void_p]
         _lib = L
     return _lib
 
@@ -720,3 +731,81 @@ class LM:
                                              C.byref(n), _dev(ws), C.c_size_t(ws.numel()), _stream()))
         toks = tokens[:, : n.value].contiguous()
         return toks, (logits[: n.value - 1] if logits is not None else None)
+
+
+# ---- k-means semantic tokenizer (lds_kmeans_*): thin wrappers; X [N, D] and C [K, D] contiguous fp32 device tensors ----
+_kmeans_ws = Workspace()
+
+
+def kmeans_workspace_bytes(N, K, D):
+    nb = C.c_size_t()
+    check(lib().lds_kmeans_workspace_bytes(int(N), int(K), int(D), C.byref(nb)))
+    return nb.value
+
+
+def _kmeans_ws_for(ws, N, K, D, device):
+    if device.type != "cuda":
+        raise RuntimeError("liblds needs tensors on a HIP device (no CPU fallback for the hot path)")
+    return ws if ws is not None else _kmeans_ws.get(kmeans_workspace_bytes(N, K, D), device)
+
+
+def kmeans_prepare(centers):
+    """h [K] = |c_k|^2 / 2 of a codebook [K, D] (once per codebook)"""
+    import torch
+    K, D = centers.shape
+    h = torch.empty(K, dtype=torch.float32, device=centers.device)
+    check(lib().lds_kmeans_prepare(_dev(centers, torch.float32), K, D, _dev(h), _stream()))
+    return h
+
+
+def kmeans_assign(x, centers, h, return_best=False, ws=None, lengths=None, pad_id=0):
+    """x [N, D] -> labels int64 [N] (the nearest centre, lowest index among ties) and optionally the winning score x.c - h.
+    lengths (host ints [B]) with x [B, T, D]: the ragged form, labels [B, T] with pad_id at and beyond every clip's length."""
+    import torch
+    K, D = centers.shape
+    if x.shape[-1] != D or x.dim() != (3 if lengths is not None else 2):
+        raise ValueError(f"kmeans_assign: x {list(x.shape)} against a codebook {[K, D]}")
+    N = x.numel() // D
+    ws = _kmeans_ws_for(ws, N, K, D, x.device)
+    labels = torch.empty(x.shape[:-1], dtype=torch.int64, device=x.device)
+    best = torch.empty(x.shape[:-1], dtype=torch.float32, device=x.device) if return_best else None
+    if lengths is not None:
+        B, T = x.shape[:2]
+        ln = np.ascontiguousarray(np.asarray(lengths.cpu() if hasattr(lengths, "cpu") else lengths).reshape(-1), dtype=np.int32)
+        if ln.shape != (B,):
+            raise ValueError(f"kmeans_assign: lengths must be {B} integers")
+        check(lib().lds_kmeans_assign_ragged(_dev(x, torch.float32), B, T, C.c_void_p(ln.ctypes.data), int(pad_id), _dev(centers, torch.float32),
+                                             _dev(h, torch.float32), K, D, _dev(labels), _dev(best) if best is not None else None, _dev(ws),
+                                             C.c_size_t(ws.numel()), _stream()))
+    else:
+        check(lib().lds_kmeans_assign(_dev(x, torch.float32), N, _dev(centers, torch.float32), _dev(h, torch.float32), K, D, _dev(labels),
+                                      _dev(best) if best is not None else None, _dev(ws), C.c_size_t(ws.numel()), _stream()))
+    return (labels, best) if return_best else labels
+
+
+def kmeans_update(x, labels, centers, h, num_points, ws=None):
+    """one Lloyd step in place on centers / h / num_points (include/lds.h lds_kmeans_update); returns the error as a device scalar"""
+    import torch
+    K, D = centers.shape
+    N = x.shape[0]
+    if x.dim() != 2 or x.shape[1] != D or labels.shape != (N,) or num_points.shape != (K,) or h.shape != (K,):
+        raise ValueError("kmeans_update: shapes of x, labels, centers, h, num_points do not agree")
+    ws = _kmeans_ws_for(ws, N, K, D, x.device)
+    err = torch.empty((), dtype=torch.float32, device=x.device)
+    check(lib().lds_kmeans_update(_dev(x, torch.float32), _dev(labels, torch.int64), N, _dev(centers, torch.float32), _dev(h, torch.float32),
+                                  _dev(num_points, torch.float32), K, D, _dev(err), _dev(ws), C.c_size_t(ws.numel()), _stream()))
+    return err
+
+
+def kmeans_seed(x, K, first_index, uniforms, ws=None):
+    """k-means++ seeding: x [N, D], uniforms fp32 device [K - 1] -> (centers [K, D], picked int64 [K]) on the device"""
+    import torch
+    N, D = x.shape
+    ws = _kmeans_ws_for(ws, N, K, D, x.device)
+    centers = torch.empty(K, D, dtype=torch.float32, device=x.device)
+    picked = torch.empty(K, dtype=torch.int64, device=x.device)
+    if K > 1 and uniforms.numel() != K - 1:
+        raise ValueError(f"kmeans_seed: {K - 1} uniforms needed, got {uniforms.numel()}")
+    check(lib().lds_kmeans_seed(_dev(x, torch.float32), N, D, int(K), int(first_index), _dev(uniforms, torch.float32) if K > 1 else None, _dev(centers),
+                                _dev(picked), _dev(ws), C.c_size_t(ws.numel()), _stream()))
+    return centers, picked

@@ -39,6 +39,12 @@ class DiffusionSVC:
             raise NotImplementedError("no units encoder is loaded: pass units_encoder_checkpoint= to load_model, or set .units_encoder")
         return self.units_encoder.encode(audio, sr, padding_mask=padding_mask)
 
+    def encode_tokens(self, audio, sr, codebook):
+        """audio at `sr` -> semantic tokens int64 [T] on the device (Units_Encoder.encode_tokens: units, then the nearest centre of `codebook`)"""
+        if self.units_encoder is None:
+            raise NotImplementedError("no units encoder is loaded: pass units_encoder_checkpoint= to load_model, or set .units_encoder")
+        return self.units_encoder.encode_tokens(audio, sr, codebook)
+
     @torch.no_grad()
     def mel2wav(self, mel, f0=None, start_frame=0):
         """reference infer_tools.py:60-67; the vocoder takes the mel only (reference vocoder.py:32)"""

@@ -103,6 +103,18 @@ class Units_Encoder:
         self._check("Units_Encoder.encode_ragged", audio, self.encoder_sample_rate if sample_rate is None else sample_rate)
         return self.model.encode_ragged(audio, lengths)
 
+    def encode_tokens(self, audio, sample_rate, codebook):
+        """Extension: audio -> semantic tokens int64 [T] on the device = encode, then the nearest centre of `codebook` (a model from
+        cluster.get_cluster_model) by lds_kmeans_assign, without leaving the device (the reference's steps 16 + 19 go through .npy files)"""
+        import cluster
+        return cluster.get_cluster_result(codebook, self.encode(audio, sample_rate))
+
+    def encode_tokens_ragged(self, audio, lengths, codebook, pad_id, sample_rate=None):
+        """Extension: encode_ragged + tokens [B, Tmax] int64: rows at and beyond a clip's own n_frames[b] hold pad_id; returns (tokens, n_frames)"""
+        import cluster
+        units, n_frames = self.encode_ragged(audio, lengths, sample_rate)
+        return cluster.get_cluster_result(codebook, units, lengths=n_frames, pad_id=pad_id), n_frames
+
 
 class WhisperLargeV3(torch.nn.Module):
     """reference tools/tools.py:105-126.  `checkpoint` (the reference hard-codes this path) holds {"dims", "model_state_dict"};

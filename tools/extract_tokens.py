@@ -1,0 +1,88 @@
+"""Turn unit files, or 16 kHz clips, into semantic tokens (the reference's 19_preprocess_token.py, its kmeans branch).
+
+    python tools/extract_tokens.py IN_DIR [--out DIR] [--codebook pretrain/semantic_codebook.pt | --synthetic K [--seed S]] [--batch 8]
+                                   [--from-audio [--checkpoint pretrain/large-v3_encoder.pt | --synthetic-encoder [--layers N]]]
+
+IN_DIR holds .npy unit files [T, dim] (tools/extract_units.py writes them).  Every file becomes DIR/<name>.npy (default DIR:
+IN_DIR/../semantic_token) of int64 tokens [T]: the index of the nearest centre of the codebook, computed on the HIP device by
+cluster.get_cluster_result.  Files are batched in sorted order, padded to the longest of the batch and assigned in the ragged form, so
+a file's tokens do not depend on its batch.  --synthetic K uses K seeded N(0, 1) centres instead of a checkpoint.
+--from-audio: IN_DIR holds 16 kHz clips instead (.npy samples or PCM16 .wav, as tools/extract_units.py reads them); every batch goes
+through Units_Encoder.encode_tokens_ragged (Whisper units, then the nearest centre) without leaving the device.  --synthetic-encoder
+runs seeded encoder weights at large-v3's width (--layers sets the depth) where no checkpoint exists.
+"""
+import argparse
+import os
+import sys
+import types
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "latent-diffusion-speech_amd"))
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+import cluster  # noqa: E402
+
+
+def units_encoder(a):
+    from encoder.whisper.model import ModelDimensions
+    from lds import arch
+    from tools.tools import Units_Encoder, WhisperLargeV3
+    if a.synthetic_encoder:
+        model = WhisperLargeV3.synthetic(ModelDimensions(**dict(arch.WHISPER_LARGE_V3_DIMS, n_audio_layer=a.layers)), seed=a.seed, device="cuda")
+    else:
+        model = WhisperLargeV3(device="cuda", checkpoint=a.checkpoint)
+    return Units_Encoder("whisper_large_v3", device="cuda", model=model)
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("in_dir")
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--codebook", default="pretrain/semantic_codebook.pt")
+    ap.add_argument("--synthetic", type=int, default=0, metavar="K")
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--batch", type=int, default=8)
+    ap.add_argument("--from-audio", action="store_true", help="IN_DIR holds 16 kHz clips: encode them to units first")
+    ap.add_argument("--checkpoint", default="pretrain/large-v3_encoder.pt")
+    ap.add_argument("--synthetic-encoder", action="store_true", help="seeded Whisper weights instead of the checkpoint")
+    ap.add_argument("--layers", type=int, default=32)
+    a = ap.parse_args()
+    ext = (".npy", ".wav") if a.from_audio else (".npy",)
+    paths = [os.path.join(a.in_dir, f) for f in sorted(os.listdir(a.in_dir)) if f.endswith(ext)]
+    if not paths:
+        raise SystemExit(f"no {' / '.join(ext)} files in {a.in_dir}")
+    out = a.out or os.path.join(os.path.dirname(os.path.abspath(a.in_dir)), "semantic_token")
+    os.makedirs(out, exist_ok=True)
+    ue = units_encoder(a) if a.from_audio else None
+    if a.synthetic:
+        dim = ue.model.hidden_dim.n_audio_state if a.from_audio else np.load(paths[0]).shape[1]
+        model = types.SimpleNamespace(cluster_centers_=np.random.default_rng(a.seed).standard_normal((a.synthetic, dim)).astype(np.float32))
+    else:
+        model = cluster.get_cluster_model(a.codebook)
+    batch = max(1, min(a.batch, 64))
+    for i in range(0, len(paths), batch):
+        group = paths[i: i + batch]
+        if a.from_audio:
+            from extract_units import load_clip      # (tools/ is this script's own directory)
+            clips = [load_clip(p) for p in group]
+            slen = [max(len(c), 400) for c in clips]      # (a clip shorter than 400 samples is zero-padded to 400, as Units_Encoder.encode does)
+            audio = np.zeros((len(clips), max(slen)), dtype=np.float32)
+            for b, c in enumerate(clips):
+                audio[b, : len(c)] = c
+            tok, lens = ue.encode_tokens_ragged(torch.from_numpy(audio).cuda(), slen, model, pad_id=-1)
+            tok, lens = tok.cpu().numpy(), [int(n) for n in lens]
+        else:
+            units = [np.load(p).astype(np.float32) for p in group]
+            lens = [u.shape[0] for u in units]
+            x = np.zeros((len(units), max(lens), units[0].shape[1]), dtype=np.float32)
+            for b, u in enumerate(units):
+                x[b, : lens[b]] = u
+            tok = cluster.get_cluster_result(model, torch.from_numpy(x).cuda(), lengths=lens, pad_id=-1).cpu().numpy()
+        for b, p in enumerate(group):
+            np.save(os.path.join(out, os.path.splitext(os.path.basename(p))[0] + ".npy"), tok[b, : lens[b]])
+    print(f"{len(paths)} files -> {out}")
+
+
+if __name__ == "__main__":
+    main()
