@@ -57,58 +57,124 @@ class DConvTest(C.Structure):
                 ("v_split", C.c_int), ("cfg", C.c_int)]
 
 
-EXPORTS = [
-    "lds_last_error", "lds_version", "lds_unet_create", "lds_unet_destroy", "lds_unet_workspace_bytes",
-    "lds_unet_forward", "lds_sampler_run", "lds_sampler_workspace_bytes", "lds_embed_create", "lds_embed_destroy",
-    "lds_embed_workspace_bytes", "lds_embed_forward", "lds_transpose", "lds_gather_rows", "lds_resample_frames", "lds_axpby", "lds_vocoder_create", "lds_vocoder_destroy",
-    "lds_vocoder_workspace_bytes", "lds_vocoder_forward", "lds_lm_create", "lds_lm_destroy", "lds_lm_workspace_bytes", "lds_lm_encode",
-    "lds_lm_generate", "lds_prof_enable", "lds_prof_summary", "lds_unet_set_gemm_mode", "lds_unet_get_gemm_mode",
-    "lds_unet_set_latency_mode", "lds_unet_get_latency_mode", "lds_unet_forward_ragged", "lds_sampler_run_ragged", "lds_vocoder_forward_ragged",
-    "lds_vae_encoder_create", "lds_vae_encoder_destroy", "lds_vae_encoder_workspace_bytes", "lds_vae_encoder_forward",
-    "lds_vae_encoder_forward_ragged", "lds_lm_workspace_bytes_opts", "lds_lm_generate_opts", "lds_whisper_create", "lds_whisper_destroy",
-    "lds_whisper_workspace_bytes", "lds_whisper_logmel", "lds_whisper_encode_mel", "lds_whisper_encode", "lds_kmeans_workspace_bytes",
-    "lds_kmeans_prepare", "lds_kmeans_assign", "lds_kmeans_assign_ragged", "lds_kmeans_update", "lds_kmeans_seed"]
+# The C ABI, one line per entry point: name, return kind ':' argument kinds in the header's order.
+# Arguments: p pointer (any sort, c_void_p), i int, z size_t, f float, q int64_t, u uint32_t.  Returns: i int, v void, s const char*.
+_KIND = {"p": C.c_void_p, "i": C.c_int, "z": C.c_size_t, "f": C.c_float, "q": C.c_int64, "u": C.c_uint32}
+_RETURN = {"i": C.c_int, "v": None, "s": C.c_char_p}
+_PUBLIC = """
+lds_last_error                   s:
+lds_version                      i:
+lds_unet_create                  i:pipppp
+lds_unet_destroy                 v:p
+lds_unet_workspace_bytes         i:piip
+lds_unet_forward                 i:ppppppziip
+lds_sampler_run                  i:piipppppziip
+lds_sampler_workspace_bytes      i:piip
+lds_unet_forward_ragged          i:pppppppziip
+lds_sampler_run_ragged           i:piippppppziip
+lds_embed_create                 i:iiipppp
+lds_embed_destroy                v:p
+lds_embed_workspace_bytes        i:piip
+lds_embed_forward                i:pppppziip
+lds_transpose                    i:ppiiifp
+lds_gather_rows                  i:pppiiip
+lds_resample_frames              i:ppiiiifp
+lds_axpby                        i:pppffqp
+lds_vocoder_create               i:pipppp
+lds_vocoder_destroy              v:p
+lds_vocoder_workspace_bytes      i:piip
+lds_vocoder_forward              i:ppppziip
+lds_vocoder_forward_ragged       i:pppppziip
+lds_vae_encoder_create           i:pipppp
+lds_vae_encoder_destroy          v:p
+lds_vae_encoder_workspace_bytes  i:piqp
+lds_vae_encoder_forward          i:pppppipziqp
+lds_vae_encoder_forward_ragged   i:ppppppipziqp
+lds_whisper_create               i:pippppp
+lds_whisper_destroy              v:p
+lds_whisper_workspace_bytes      i:piqp
+lds_whisper_logmel               i:pppppziqp
+lds_whisper_encode_mel           i:pppppziip
+lds_whisper_encode               i:pppppziqp
+lds_lm_create                    i:pipppp
+lds_lm_destroy                   v:p
+lds_lm_workspace_bytes           i:piiip
+lds_lm_encode                    i:pppppppziip
+lds_lm_generate                  i:pppiiiiifffpppppzp
+lds_lm_workspace_bytes_opts      i:piiiip
+lds_lm_generate_opts             i:pppiiippppppzp
+lds_kmeans_workspace_bytes       i:qiip
+lds_kmeans_prepare               i:piipp
+lds_kmeans_assign                i:pqppiipppzp
+lds_kmeans_assign_ragged         i:piipqppiipppzp
+lds_kmeans_update                i:ppqpppiippzp
+lds_kmeans_seed                  i:pqiiqppppzp
+lds_prof_enable                  i:i
+lds_prof_summary                 i:pz
+lds_unet_set_gemm_mode           i:pi
+lds_unet_get_gemm_mode           i:p
+lds_unet_set_latency_mode        i:pi
+lds_unet_get_latency_mode        i:p
+"""
 # include/lds_test.h: single-op entry points for tests/ and tools/ (not part of the drop-in boundary)
-TEST_EXPORTS = [
-    "lds_test_conv", "lds_test_dconv", "lds_bench_dconv", "lds_test_gn_apply", "lds_bench_gn_stream", "lds_test_gn_chain_k4p",
-    "lds_test_ln_chain_k4p", "lds_test_attention_k4p", "lds_test_conv_transpose", "lds_test_voc_step", "lds_test_dconv_bf3",
-    "lds_bench_dconv_bf3", "lds_test_k8b3_roundtrip", "lds_test_gn_apply_bf3", "lds_test_dconv_split", "lds_bench_dconv_split",
-    "lds_test_split_roundtrip", "lds_test_gn_apply_split", "lds_debug_set_split_rule", "lds_test_attention_f16math",
-    "lds_test_attention_latency", "lds_debug_set_gn_fold", "lds_debug_set_voc_pair", "lds_debug_set_touch_weights", "lds_test_voc_pair", "lds_test_gn_fold_k4p", "lds_bench_dconv_alt", "lds_debug_fill_u32", "lds_debug_trace",
-    "lds_debug_trace_count", "lds_debug_trace_get", "lds_debug_unet_plan", "lds_test_gn_fold_split", "lds_test_cluster_join", "lds_test_lm_sample",
-    "lds_test_conv_down", "lds_test_conv_down_ragged", "lds_test_lm_beam_step"]
+_TEST = """
+lds_test_conv                    i:ppip
+lds_test_dconv                   i:pppip
+lds_bench_dconv                  i:ppiippzp
+lds_test_gn_apply                i:ppiiiifpppipip
+lds_bench_gn_stream              i:iiiiipp
+lds_test_gn_chain_k4p            i:pppppfiippiiiiip
+lds_test_ln_chain_k4p            i:pppppfppiiiip
+lds_test_attention_k4p           i:ppiiiip
+lds_test_conv_transpose          i:ppppiiiiiiifp
+lds_test_voc_step                i:pppppiiiiipfppip
+lds_test_dconv_bf3               i:pppiip
+lds_bench_dconv_bf3              i:ppiiippzp
+lds_test_k8b3_roundtrip          i:ppiiip
+lds_test_gn_apply_bf3            i:ppiiiifpppipip
+lds_test_dconv_split             i:pppiiip
+lds_bench_dconv_split            i:ppiiiippzp
+lds_test_split_roundtrip         i:ppiiiip
+lds_test_gn_apply_split          i:ppiiiifpppipiip
+lds_debug_set_split_rule         i:i
+lds_test_attention_f16math       i:ppiiiip
+lds_test_attention_latency       i:ppiiiiip
+lds_debug_set_gn_fold            i:i
+lds_debug_set_voc_pair           i:i
+lds_debug_set_touch_weights      i:i
+lds_test_voc_pair                i:pppppiiiipfppip
+lds_test_gn_fold_k4p             i:pppppfippppiiiiiiip
+lds_bench_dconv_alt              i:ppiipipp
+lds_debug_fill_u32               i:pzup
+lds_debug_trace                  i:i
+lds_debug_trace_count            i:
+lds_debug_trace_get              i:ipzpp
+lds_debug_unet_plan              i:piipz
+lds_test_gn_fold_split           i:pppppfippppiiiiiiiiip
+lds_test_cluster_join            i:ppppiiiiiiippppzp
+lds_test_lm_sample               i:piiiifffppipp
+lds_test_conv_down               i:pppiiiiiifippzp
+lds_test_conv_down_ragged        i:pppiiiiiifppippzp
+lds_test_lm_beam_step            i:piiiiiifiippppppppppppppppp
+"""
+SIGNATURES = dict(ln.split() for ln in (_PUBLIC + _TEST).splitlines() if ln)
+EXPORTS = [ln.split()[0] for ln in _PUBLIC.splitlines() if ln]
+TEST_EXPORTS = [ln.split()[0] for ln in _TEST.splitlines() if ln]
 
 
 def lib():
-    """Load liblds.so (once).  Raises if it has not been built (python __graft_entry__.py build)."""
+    """Load liblds.so (once) and declare restype / argtypes of every name in EXPORTS + TEST_EXPORTS.  Raises if it has not been built
+    (python __graft_entry__.py build)."""
     global _lib
     if _lib is None:
         if not os.path.exists(LIB_PATH):
             raise RuntimeError(f"{LIB_PATH} is missing: build it with `make -C latent-diffusion-speech_amd/csrc` "
                                "(there is no CPU fallback for the hot path)")
         L = C.CDLL(LIB_PATH)
-        L.lds_last_error.restype = C.c_char_p
         for n in EXPORTS + TEST_EXPORTS:
-            if n not in ("lds_last_error", "lds_unet_destroy", "lds_embed_destroy", "lds_vocoder_destroy", "lds_lm_destroy", "lds_vae_encoder_destroy",
-                             "lds_whisper_destroy"):
-                getattr(L, n).restype = C.c_int
-        for n in ("lds_unet_destroy", "lds_embed_destroy", "lds_vocoder_destroy", "lds_lm_destroy", "lds_vae_encoder_destroy", "lds_whisper_destroy"):
-            getattr(L, n).restype = None
-            getattr(L, n).argtypes = [C.c_void_p]
-        L.lds_unet_set_gemm_mode.argtypes = [C.c_void_p, C.c_int]
-        L.lds_unet_get_gemm_mode.argtypes = [C.c_void_p]
-        L.lds_unet_set_latency_mode.argtypes = [C.c_void_p, C.c_int]
-        L.lds_unet_get_latency_mode.argtypes = [C.c_void_p]
-        L.lds_kmeans_workspace_bytes.argtypes = [C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_size_t)]
-        L.lds_kmeans_prepare.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-        L.lds_kmeans_assign.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
-                                        C.c_void_p]
-        L.lds_kmeans_assign_ragged.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
-                                               C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-        L.lds_kmeans_update.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
-                                        C.c_size_t, C.c_void_p]
-        L.lds_kmeans_seed.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
-                                      C.c_void_p]
+            ret, _, args = SIGNATURES[n].partition(":")
+            fn = getattr(L, n)
+            fn.restype, fn.argtypes = _RETURN[ret], [_KIND[k] for k in args]
         _lib = L
     return _lib
 
@@ -167,8 +233,66 @@ class Workspace:
         return buf
 
 
-class UNet:
+def _dev_or_null(t, dtype=None):
+    return None if t is None else _dev(t, dtype)
+
+
+def _host(a):
+    """address of a host numpy array (the caller keeps it alive over the call), or NULL"""
+    return None if a is None else a.ctypes.data
+
+
+def _bytes(entry, *args):
+    """what the `*_workspace_bytes` entry answers for these arguments"""
+    nb = C.c_size_t()
+    check(getattr(lib(), entry)(*args, C.byref(nb)))
+    return nb.value
+
+
+def _host_lengths(lengths, B, lo, hi, max_B=None, what=""):
+    """the per-item counts of a ragged batch (list / array / tensor) -> host int32 [B], every one in lo .. hi; max_B: the most items (`what`
+    names them in the message) that the entry takes"""
+    if max_B is not None and B > max_B:
+        raise ValueError(f"a ragged {what} batch holds at most {max_B} clips (got {B})")
+    a = np.ascontiguousarray(np.asarray(lengths.cpu() if hasattr(lengths, "cpu") else lengths).reshape(-1), dtype=np.int32)
+    if a.shape != (B,) or a.min() < lo or a.max() > hi:
+        raise ValueError(f"lengths must be {B} integers in {lo} .. {hi}")
+    return a
+
+
+def _dense_or_ragged(name, *lengths):
+    """(the entry `name`, ()) without lengths, else (its `_ragged` twin, the host addresses of the lengths arrays -- which the caller keeps
+    alive over the call).  The C entries stay two: a ragged one refuses a null `lengths`."""
+    if lengths[0] is None:
+        return getattr(lib(), name), ()
+    return getattr(lib(), name + "_ragged"), tuple(a.ctypes.data for a in lengths)
+
+
+class _Handle:
+    """What the handle classes share: `h` from lds_<KIND>_create, destroyed with the object, and `ws`, the scratch of its calls."""
+    KIND = None
+
+    def _create(self, *args):
+        self.h, self.ws = C.c_void_p(), Workspace()
+        check(getattr(lib(), f"lds_{self.KIND}_create")(*args, C.byref(self.h)))
+
+    def _create_weights(self, cfg, state, *more):
+        n, names, ptrs, numel, keep = _host_tensor_table(state)
+        self._create(C.byref(cfg), n, names, ptrs, numel, *more)
+
+    def __del__(self):
+        if getattr(self, "h", None) and _lib is not None:
+            getattr(_lib, f"lds_{self.KIND}_destroy")(self.h)
+            self.h = None
+
+    def _workspace(self, entry, device, *dims):
+        """the buffer of the current stream, grown to what `entry` asks for a call of these dimensions"""
+        return self.ws.get(_bytes(entry, self.h, *dims), device)
+
+
+class UNet(_Handle):
     """Handle on the packed denoiser (lds_unet_*)."""
+    KIND = "unet"
 
     def __init__(self, cfg, state):
         c = UNetCfg()
@@ -178,16 +302,8 @@ class UNet:
         c.n_blocks = len(boc)
         for i, v in enumerate(boc):
             c.block_out_channels[i] = v
-        n, names, ptrs, numel, keep = _host_tensor_table(state)
-        self.h = C.c_void_p()
-        check(lib().lds_unet_create(C.byref(c), n, names, ptrs, numel, C.byref(self.h)))
+        self._create_weights(c, state)
         self.M, self.H = c.out_dims, c.n_hidden
-        self.ws = Workspace()
-
-    def __del__(self):
-        if getattr(self, "h", None) and _lib is not None:
-            _lib.lds_unet_destroy(self.h)
-            self.h = None
 
     def set_gemm_mode(self, mode):
         """0 / "f32": exact-fp32 MFMA (default); 2 / "split_f16": two fp16 terms per operand (opt-in; include/lds.h)"""
@@ -207,38 +323,28 @@ class UNet:
     @staticmethod
     def _lengths(lengths, B, T):
         """per-utterance frame counts of a ragged batch -> host int32 [B] (include/lds.h lds_sampler_run_ragged)"""
-        a = np.ascontiguousarray(np.asarray(lengths.cpu() if hasattr(lengths, "cpu") else lengths).reshape(-1), dtype=np.int32)
-        if a.shape != (B,) or a.min() < 1 or a.max() > T:
-            raise ValueError(f"lengths must be {B} integers in 1 .. {T}")
-        return a
+        return _host_lengths(lengths, B, 1, T)
 
     def workspace_tensor(self, B, T, device, sampler=False):
         """the caller-owned scratch a forward (or sampler run) of this size on the current stream will use (tests poison it)"""
-        nb = C.c_size_t()
-        check((lib().lds_sampler_workspace_bytes if sampler else lib().lds_unet_workspace_bytes)(self.h, B, T, C.byref(nb)))
-        return self.ws.get(nb.value, device)
+        return self._workspace("lds_sampler_workspace_bytes" if sampler else "lds_unet_workspace_bytes", device, B, T)
 
     def plan(self, B, T):
         """[(slot name, offset, bytes)] of the workspace of a forward of this size (include/lds_test.h lds_debug_unet_plan)"""
         buf = C.create_string_buffer(1 << 16)
-        check(lib().lds_debug_unet_plan(self.h, B, T, buf, C.c_size_t(len(buf))))
+        check(lib().lds_debug_unet_plan(self.h, B, T, buf, len(buf)))
         return [(a, int(b), int(c)) for a, b, c in (ln.split() for ln in buf.value.decode().splitlines())]
 
     def forward(self, x, cond, t, lengths=None):
         import torch
         B, M, T = x.shape
         assert M == self.M and cond.shape == (B, self.H, T) and t.shape == (B,)
-        nb = C.c_size_t()
-        check(lib().lds_unet_workspace_bytes(self.h, B, T, C.byref(nb)))
-        ws = self.ws.get(nb.value, x.device)
+        ws = self.workspace_tensor(B, T, x.device)
         eps = torch.empty_like(x)
-        if lengths is not None:
-            ln = self._lengths(lengths, B, T)
-            check(lib().lds_unet_forward_ragged(self.h, _dev(x, torch.float32), _dev(cond, torch.float32), _dev(t, torch.float32), C.c_void_p(ln.ctypes.data),
-                                                _dev(eps), _dev(ws), C.c_size_t(ws.numel()), B, T, _stream()))
-            return eps
-        check(lib().lds_unet_forward(self.h, _dev(x, torch.float32), _dev(cond, torch.float32), _dev(t, torch.float32),
-                                     _dev(eps), _dev(ws), C.c_size_t(ws.numel()), B, T, _stream()))
+        ln = None if lengths is None else self._lengths(lengths, B, T)
+        fn, ln_at = _dense_or_ragged("lds_unet_forward", ln)
+        check(fn(self.h, _dev(x, torch.float32), _dev(cond, torch.float32), _dev(t, torch.float32), *ln_at, _dev(eps), _dev(ws), ws.numel(), B, T,
+                 _stream()))
         return eps
 
     def sample(self, method, table, cond, x, noise=None, lengths=None):
@@ -248,60 +354,41 @@ class UNet:
         B, M, T = x.shape
         table = np.ascontiguousarray(table, dtype=np.float32)
         assert table.ndim == 2 and table.shape[1] == TABLE_STRIDE
-        nb = C.c_size_t()
-        check(lib().lds_sampler_workspace_bytes(self.h, B, T, C.byref(nb)))
-        ws = self.ws.get(nb.value, x.device)
-        nz = _dev(noise, torch.float32) if noise is not None else None
-        if lengths is not None:
-            ln = self._lengths(lengths, B, T)
-            check(lib().lds_sampler_run_ragged(self.h, METHODS[method], table.shape[0], C.c_void_p(table.ctypes.data), _dev(cond, torch.float32),
-                                               _dev(x, torch.float32), nz, C.c_void_p(ln.ctypes.data), _dev(ws), C.c_size_t(ws.numel()), B, T, _stream()))
-            return x
-        check(lib().lds_sampler_run(self.h, METHODS[method], table.shape[0], C.c_void_p(table.ctypes.data),
-                                    _dev(cond, torch.float32), _dev(x, torch.float32), nz, _dev(ws),
-                                    C.c_size_t(ws.numel()), B, T, _stream()))
+        ws = self.workspace_tensor(B, T, x.device, sampler=True)
+        ln = None if lengths is None else self._lengths(lengths, B, T)
+        fn, ln_at = _dense_or_ragged("lds_sampler_run", ln)
+        check(fn(self.h, METHODS[method], table.shape[0], table.ctypes.data, _dev(cond, torch.float32), _dev(x, torch.float32),
+                 _dev_or_null(noise, torch.float32), *ln_at, _dev(ws), ws.numel(), B, T, _stream()))
         return x
 
 
-class Embed:
+class Embed(_Handle):
     """unit_embed + spk_embed front end (lds_embed_*)."""
+    KIND = "embed"
 
     def __init__(self, unit_w, unit_b, spk_w=None):
         uw = np.ascontiguousarray(unit_w, dtype=np.float32)
         ub = np.ascontiguousarray(unit_b, dtype=np.float32)
         sw = None if spk_w is None else np.ascontiguousarray(spk_w, dtype=np.float32)
         self.H, self.Cin = uw.shape
-        self.h = C.c_void_p()
-        check(lib().lds_embed_create(self.Cin, self.H, 0 if sw is None else sw.shape[0], C.c_void_p(uw.ctypes.data),
-                                     C.c_void_p(ub.ctypes.data), None if sw is None else C.c_void_p(sw.ctypes.data),
-                                     C.byref(self.h)))
-        self.ws = Workspace()
-
-    def __del__(self):
-        if getattr(self, "h", None) and _lib is not None:
-            _lib.lds_embed_destroy(self.h)
-            self.h = None
+        self._create(self.Cin, self.H, 0 if sw is None else sw.shape[0], _host(uw), _host(ub), _host(sw))
 
     def forward(self, units, spk_id):
         import torch
         B, T, K = units.shape
         assert K == self.Cin
-        nb = C.c_size_t()
-        check(lib().lds_embed_workspace_bytes(self.h, B, T, C.byref(nb)))
-        ws = self.ws.get(nb.value, units.device)
+        ws = self._workspace("lds_embed_workspace_bytes", units.device, B, T)
         cond = torch.empty(B, self.H, T, dtype=torch.float32, device=units.device)
         sid = None
         if spk_id is not None:
             sid = spk_id.reshape(B, -1)[:, 0].contiguous().to(torch.int64)
-        check(lib().lds_embed_forward(self.h, _dev(units, torch.float32), _dev(sid) if sid is not None else None,
-                                      _dev(cond), _dev(ws), C.c_size_t(ws.numel()), B, T, _stream()))
+        check(lib().lds_embed_forward(self.h, _dev(units, torch.float32), _dev_or_null(sid), _dev(cond), _dev(ws), ws.numel(), B, T, _stream()))
         return cond
 
 
 def debug_fill(t, pattern):
     """every 32-bit word of a device tensor = pattern (include/lds_test.h: poisoned-workspace tests)"""
-    n = t.numel() * t.element_size() // 4
-    check(lib().lds_debug_fill_u32(_dev(t), C.c_size_t(n), C.c_uint32(pattern), _stream()))
+    check(lib().lds_debug_fill_u32(_dev(t), t.numel() * t.element_size() // 4, pattern, _stream()))
 
 
 def debug_trace(on):
@@ -314,7 +401,7 @@ def debug_trace_records():
     for i in range(lib().lds_debug_trace_count()):
         name = C.create_string_buffer(96)
         ptr, nb = C.c_void_p(), C.c_size_t()
-        check(lib().lds_debug_trace_get(i, name, C.c_size_t(len(name)), C.byref(ptr), C.byref(nb)))
+        check(lib().lds_debug_trace_get(i, name, len(name), C.byref(ptr), C.byref(nb)))
         out.append((name.value.decode(), C.string_at(ptr, nb.value)))
     return out
 
@@ -352,7 +439,7 @@ def prof_summary():
     """list of dicts {name,count,ms,flops,bytes}; synchronises the recorded events."""
     import json
     buf = C.create_string_buffer(1 << 16)
-    check(lib().lds_prof_summary(buf, C.c_size_t(len(buf))))
+    check(lib().lds_prof_summary(buf, len(buf)))
     return json.loads(buf.value.decode())
 
 
@@ -360,8 +447,7 @@ def axpby(a, b, c0, c1):
     """c0*a + c1*b on the device."""
     import torch
     out = torch.empty_like(a)
-    check(lib().lds_axpby(_dev(out), _dev(a, torch.float32), _dev(b, torch.float32), C.c_float(c0), C.c_float(c1),
-                          C.c_int64(a.numel()), _stream()))
+    check(lib().lds_axpby(_dev(out), _dev(a, torch.float32), _dev(b, torch.float32), c0, c1, a.numel(), _stream()))
     return out
 
 
@@ -382,7 +468,7 @@ def resample_frames(x, n_out, step):
     B, T, Cc = x.shape
     out = torch.empty(B, n_out, Cc, dtype=torch.float32, device=x.device)
     if n_out:
-        check(lib().lds_resample_frames(_dev(x, torch.float32), _dev(out), B, T, n_out, Cc, C.c_float(step), _stream()))
+        check(lib().lds_resample_frames(_dev(x, torch.float32), _dev(out), B, T, n_out, Cc, step, _stream()))
     return out
 
 
@@ -391,7 +477,7 @@ def transpose(x, scale=1.0):
     import torch
     B, R, Cc = x.shape
     out = torch.empty(B, Cc, R, dtype=torch.float32, device=x.device)
-    check(lib().lds_transpose(_dev(x, torch.float32), _dev(out), B, R, Cc, C.c_float(scale), _stream()))
+    check(lib().lds_transpose(_dev(x, torch.float32), _dev(out), B, R, Cc, scale, _stream()))
     return out
 
 
@@ -413,91 +499,53 @@ def vocoder_cfg(h):
     return c
 
 
-class Generator:
+class Generator(_Handle):
     """HiFi-VAEGAN decoder (lds_vocoder_*)."""
+    KIND = "vocoder"
 
     def __init__(self, h, state):
-        c = VocoderCfg()
-        c.inter_channels = h["inter_channels"]
-        c.upsample_initial_channel = h["upsample_initial_channel"]
-        c.n_ups = len(h["upsample_rates"])
-        for i, (u, k) in enumerate(zip(h["upsample_rates"], h["upsample_kernel_sizes"])):
-            c.upsample_rates[i], c.upsample_kernel_sizes[i] = u, k
-        c.resblock = 1 if str(h["resblock"]) == "1" else 2
-        c.n_kernels = len(h["resblock_kernel_sizes"])
-        c.n_dil = len(h["resblock_dilation_sizes"][0])
-        for j, (k, dil) in enumerate(zip(h["resblock_kernel_sizes"], h["resblock_dilation_sizes"])):
-            c.resblock_kernel_sizes[j] = k
-            for m, d in enumerate(dil):
-                c.resblock_dilation_sizes[j][m] = d
-        n, names, ptrs, numel, keep = _host_tensor_table(state)
-        self.h = C.c_void_p()
-        check(lib().lds_vocoder_create(C.byref(c), n, names, ptrs, numel, C.byref(self.h)))
+        c = vocoder_cfg(h)
+        self._create_weights(c, state)
         self.hop = int(np.prod(h["upsample_rates"]))
         self.C = c.inter_channels
-        self.ws = Workspace()
-
-    def __del__(self):
-        if getattr(self, "h", None) and _lib is not None:
-            _lib.lds_vocoder_destroy(self.h)
-            self.h = None
 
     def workspace_tensor(self, B, T, device):
         """the caller-owned scratch a forward of this size on the current stream will use (tests poison it)"""
-        nb = C.c_size_t()
-        check(lib().lds_vocoder_workspace_bytes(self.h, B, T, C.byref(nb)))
-        return self.ws.get(nb.value, device)
+        return self._workspace("lds_vocoder_workspace_bytes", device, B, T)
 
     def forward(self, z, lengths=None):
         """z [B,C,T] -> wav [B,1,T*hop]; lengths: the utterances' own frame counts (ragged batch, include/lds.h lds_vocoder_forward_ragged)"""
         import torch
         B, Cc, T = z.shape
         assert Cc == self.C
-        nb = C.c_size_t()
-        check(lib().lds_vocoder_workspace_bytes(self.h, B, T, C.byref(nb)))
-        ws = self.ws.get(nb.value, z.device)
+        ws = self.workspace_tensor(B, T, z.device)
         wav = torch.empty(B, 1, T * self.hop, dtype=torch.float32, device=z.device)
-        if lengths is not None:
-            ln = UNet._lengths(lengths, B, T)
-            check(lib().lds_vocoder_forward_ragged(self.h, _dev(z, torch.float32), C.c_void_p(ln.ctypes.data), _dev(wav), _dev(ws), C.c_size_t(ws.numel()),
-                                                   B, T, _stream()))
-            return wav
-        check(lib().lds_vocoder_forward(self.h, _dev(z, torch.float32), _dev(wav), _dev(ws), C.c_size_t(ws.numel()), B, T,
-                                        _stream()))
+        ln = None if lengths is None else UNet._lengths(lengths, B, T)
+        fn, ln_at = _dense_or_ragged("lds_vocoder_forward", ln)
+        check(fn(self.h, _dev(z, torch.float32), *ln_at, _dev(wav), _dev(ws), ws.numel(), B, T, _stream()))
         return wav
 
 
-class VaeEncoder:
+class VaeEncoder(_Handle):
     """HiFi-VAEGAN encoder (lds_vae_encoder_*): audio [B,L] -> (out [B,T,2C], z [B,T,C] or None)."""
+    KIND = "vae_encoder"
 
     def __init__(self, h, state):
         hop = int(np.prod(h["upsample_rates"]))
         if "hop_size" in h and int(h["hop_size"]) != hop:      # extract pads to hop_size; the encoder's frames are prod(upsample_rates) samples
             raise ValueError(f"VaeEncoder: config hop_size {h['hop_size']} != prod(upsample_rates) {hop} = {list(h['upsample_rates'])}")
         c = vocoder_cfg(h)
-        n, names, ptrs, numel, keep = _host_tensor_table(state)
-        self.h = C.c_void_p()
-        check(lib().lds_vae_encoder_create(C.byref(c), n, names, ptrs, numel, C.byref(self.h)))
-        self.hop = int(np.prod(h["upsample_rates"]))
+        self._create_weights(c, state)
+        self.hop = hop
         self.C = c.inter_channels
-        self.ws = Workspace()
-
-    def __del__(self):
-        if getattr(self, "h", None) and _lib is not None:
-            _lib.lds_vae_encoder_destroy(self.h)
-            self.h = None
 
     def workspace_bytes(self, B, L):
-        nb = C.c_size_t()
-        check(lib().lds_vae_encoder_workspace_bytes(self.h, B, C.c_int64(L), C.byref(nb)))
-        return nb.value
+        return _bytes("lds_vae_encoder_workspace_bytes", self.h, B, L)
 
     @staticmethod
     def lengths(lengths, B, L):
         """per-clip sample counts of a ragged batch -> host int32 [B] (include/lds.h lds_vae_encoder_forward_ragged: B <= 64, 1 .. L)"""
-        if B > 64:
-            raise ValueError(f"a ragged encoder batch holds at most 64 clips (got {B})")
-        return UNet._lengths(lengths, B, L)
+        return _host_lengths(lengths, B, 1, L, 64, "encoder")
 
     def forward(self, audio, noise=None, only_mean=False, ws=None, lengths=None):
         """audio [B,L] (L a multiple of the hop); noise [B,C,T] or None -> (out [B,T,2C], z [B,T,C] or None); `ws`: a caller's uint8
@@ -514,21 +562,16 @@ class VaeEncoder:
             ws = self.ws.get(nb, audio.device)
         out = torch.empty(B, T, 2 * self.C, dtype=torch.float32, device=audio.device)
         z = torch.empty(B, T, self.C, dtype=torch.float32, device=audio.device) if noise is not None else None
-        if ln is not None:
-            check(lib().lds_vae_encoder_forward_ragged(self.h, _dev(audio, torch.float32), C.c_void_p(ln.ctypes.data),
-                                                       _dev(noise, torch.float32) if noise is not None else None, _dev(out),
-                                                       _dev(z) if z is not None else None, int(bool(only_mean)), _dev(ws), C.c_size_t(ws.numel()), B,
-                                                       C.c_int64(L), _stream()))
-            return out, z
-        check(lib().lds_vae_encoder_forward(self.h, _dev(audio, torch.float32), _dev(noise, torch.float32) if noise is not None else None,
-                                            _dev(out), _dev(z) if z is not None else None, int(bool(only_mean)), _dev(ws),
-                                            C.c_size_t(ws.numel()), B, C.c_int64(L), _stream()))
+        fn, ln_at = _dense_or_ragged("lds_vae_encoder_forward", ln)
+        check(fn(self.h, _dev(audio, torch.float32), *ln_at, _dev_or_null(noise, torch.float32), _dev(out), _dev_or_null(z), int(bool(only_mean)),
+                 _dev(ws), ws.numel(), B, L, _stream()))
         return out, z
 
 
-class Whisper:
+class Whisper(_Handle):
     """Whisper units encoder (lds_whisper_*): audio [B,L] at 16 kHz -> log-mel [B,n_mels,L//160] / units [B,T,n_state], T = (L//160 - 1)//2 + 1.
     `lengths`: every clip's own sample count (host ints, 400 .. L, at most 64 clips): each clip is encoded as if alone."""
+    KIND = "whisper"
     HOP, N_FFT = 160, 400
 
     def __init__(self, n_mels, n_state, n_head, n_layer, n_ctx, state, mel_filters):
@@ -541,17 +584,8 @@ class Whisper:
         mf = np.ascontiguousarray(mel_filters, dtype=np.float32)
         if mf.shape != (n_mels, 201):
             raise ValueError(f"Whisper: mel_filters must be [{n_mels}, 201], got {list(mf.shape)}")
-        c = WhisperCfg(n_mels, n_state, n_head, n_layer, n_ctx)
-        n, names, ptrs, numel, keep = _host_tensor_table(state)
-        self.h = C.c_void_p()
-        check(lib().lds_whisper_create(C.byref(c), n, names, ptrs, numel, C.c_void_p(mf.ctypes.data), C.byref(self.h)))
+        self._create_weights(WhisperCfg(n_mels, n_state, n_head, n_layer, n_ctx), state, _host(mf))
         self.n_mels, self.n_state, self.n_ctx = n_mels, n_state, n_ctx
-        self.ws = Workspace()
-
-    def __del__(self):
-        if getattr(self, "h", None) and _lib is not None:
-            _lib.lds_whisper_destroy(self.h)
-            self.h = None
 
     def frames(self, n_mel_frames):
         return (int(n_mel_frames) - 1) // 2 + 1
@@ -566,17 +600,10 @@ class Whisper:
 
     def lengths(self, lengths, B, L):
         """per-clip sample counts -> host int32 [B] (include/lds.h: B <= 64, 400 .. L)"""
-        if B > 64:
-            raise ValueError(f"a ragged units batch holds at most 64 clips (got {B})")
-        a = np.ascontiguousarray(np.asarray(lengths.cpu() if hasattr(lengths, "cpu") else lengths).reshape(-1), dtype=np.int32)
-        if a.shape != (B,) or a.min() < self.N_FFT or a.max() > L:
-            raise ValueError(f"lengths must be {B} integers in {self.N_FFT} .. {L}")
-        return a
+        return _host_lengths(lengths, B, self.N_FFT, L, 64, "units")
 
     def workspace_bytes(self, B, L):
-        nb = C.c_size_t()
-        check(lib().lds_whisper_workspace_bytes(self.h, B, C.c_int64(L), C.byref(nb)))
-        return nb.value
+        return _bytes("lds_whisper_workspace_bytes", self.h, B, L)
 
     def _ws(self, ws, B, L, device):
         return ws if ws is not None else self.ws.get(self.workspace_bytes(B, L), device)
@@ -589,8 +616,7 @@ class Whisper:
         ln = self.lengths(lengths, B, L) if lengths is not None else None
         ws = self._ws(ws, B, L, audio.device)
         mel = torch.empty(B, self.n_mels, L // self.HOP, dtype=torch.float32, device=audio.device)
-        check(lib().lds_whisper_logmel(self.h, _dev(audio, torch.float32), C.c_void_p(ln.ctypes.data) if ln is not None else None, _dev(mel), _dev(ws),
-                                       C.c_size_t(ws.numel()), B, C.c_int64(L), _stream()))
+        check(lib().lds_whisper_logmel(self.h, _dev(audio, torch.float32), _host(ln), _dev(mel), _dev(ws), ws.numel(), B, L, _stream()))
         return mel
 
     def encode_mel(self, mel, n_frames=None, ws=None):
@@ -601,15 +627,10 @@ class Whisper:
             raise ValueError(f"Whisper: mel has {M} channels, the model {self.n_mels}")
         if B < 1 or F < 1 or self.frames(F) > self.n_ctx:
             raise ValueError(f"Whisper: {F} mel frames give {self.frames(F)} frames, outside 1 .. n_audio_ctx {self.n_ctx}")
-        nf = None
-        if n_frames is not None:
-            if B > 64:
-                raise ValueError(f"a ragged units batch holds at most 64 clips (got {B})")
-            nf = UNet._lengths(n_frames, B, F)
+        nf = _host_lengths(n_frames, B, 1, F, 64, "units") if n_frames is not None else None
         ws = self._ws(ws, B, max(F * self.HOP, self.N_FFT), mel.device)
         units = torch.empty(B, self.frames(F), self.n_state, dtype=torch.float32, device=mel.device)
-        check(lib().lds_whisper_encode_mel(self.h, _dev(mel, torch.float32), C.c_void_p(nf.ctypes.data) if nf is not None else None, _dev(units), _dev(ws),
-                                           C.c_size_t(ws.numel()), B, F, _stream()))
+        check(lib().lds_whisper_encode_mel(self.h, _dev(mel, torch.float32), _host(nf), _dev(units), _dev(ws), ws.numel(), B, F, _stream()))
         return units
 
     def encode(self, audio, lengths=None, ws=None):
@@ -620,54 +641,45 @@ class Whisper:
         ln = self.lengths(lengths, B, L) if lengths is not None else None
         ws = self._ws(ws, B, L, audio.device)
         units = torch.empty(B, self.frames(L // self.HOP), self.n_state, dtype=torch.float32, device=audio.device)
-        check(lib().lds_whisper_encode(self.h, _dev(audio, torch.float32), C.c_void_p(ln.ctypes.data) if ln is not None else None, _dev(units), _dev(ws),
-                                       C.c_size_t(ws.numel()), B, C.c_int64(L), _stream()))
+        check(lib().lds_whisper_encode(self.h, _dev(audio, torch.float32), _host(ln), _dev(units), _dev(ws), ws.numel(), B, L, _stream()))
         return units
+
+
+def _conv_down(x, w, b, stride, slope, tile, cfg, lengths_in=None, lengths_out=None):
+    import torch
+    B, Ci, T = x.shape
+    w = np.ascontiguousarray(w, dtype=np.float32)
+    Co, _, K = w.shape
+    pad = (K - stride + 1) // 2
+    out = torch.empty(B, Co, (T + 2 * pad - K) // stride + 1, dtype=torch.float32, device=x.device)
+    bb = np.ascontiguousarray(b, dtype=np.float32) if b is not None else None
+    buf = C.create_string_buffer(128)
+    fn, ln_at = _dense_or_ragged("lds_test_conv_down", lengths_in, lengths_out)
+    check(fn(_dev(x, torch.float32), _host(w), _host(bb), Ci, Co, K, stride, T, B, slope, *ln_at, tile, _dev(out), buf, len(buf), _stream()))
+    if cfg is not None:
+        cfg.append(buf.value.decode())
+    return out
 
 
 def conv_down(x, w, b, stride, slope=1.0, tile=0, cfg=None):
     """The encoder's convolution alone (lds_test_conv_down): x [B,Ci,T] on the device, w [Co,Ci,K] / b [Co] host arrays ->
     [B,Co,(T + 2 pad - K) // stride + 1] with pad = (K - stride + 1) // 2, LeakyReLU(slope) on the input.  tile: 0 = the product path's
     choice, else 64064 / 64128 / 128128; cfg: a list that receives the configuration that ran."""
-    import torch
-    B, Ci, T = x.shape
-    w = np.ascontiguousarray(w, dtype=np.float32)
-    Co, _, K = w.shape
-    pad = (K - stride + 1) // 2
-    out = torch.empty(B, Co, (T + 2 * pad - K) // stride + 1, dtype=torch.float32, device=x.device)
-    bb = np.ascontiguousarray(b, dtype=np.float32) if b is not None else None
-    buf = C.create_string_buffer(128)
-    check(lib().lds_test_conv_down(_dev(x, torch.float32), C.c_void_p(w.ctypes.data), C.c_void_p(bb.ctypes.data) if bb is not None else None,
-                                   Ci, Co, K, stride, T, B, C.c_float(slope), tile, _dev(out), buf, C.c_size_t(len(buf)), _stream()))
-    if cfg is not None:
-        cfg.append(buf.value.decode())
-    return out
+    return _conv_down(x, w, b, stride, slope, tile, cfg)
 
 
 def conv_down_ragged(x, w, b, stride, lengths_in, lengths_out, slope=1.0, tile=0, cfg=None):
     """conv_down over a ragged batch (lds_test_conv_down_ragged): x reads as zeros from lengths_in[b] on, the output is zeros from
     lengths_out[b] on (host ints, B <= 64)"""
-    import torch
-    B, Ci, T = x.shape
-    w = np.ascontiguousarray(w, dtype=np.float32)
-    Co, _, K = w.shape
-    pad = (K - stride + 1) // 2
-    out = torch.empty(B, Co, (T + 2 * pad - K) // stride + 1, dtype=torch.float32, device=x.device)
-    bb = np.ascontiguousarray(b, dtype=np.float32) if b is not None else None
     li = np.ascontiguousarray(lengths_in, dtype=np.int32)
     lo = np.ascontiguousarray(lengths_out, dtype=np.int32)
-    assert li.shape == lo.shape == (B,)
-    buf = C.create_string_buffer(128)
-    check(lib().lds_test_conv_down_ragged(_dev(x, torch.float32), C.c_void_p(w.ctypes.data), C.c_void_p(bb.ctypes.data) if bb is not None else None,
-                                          Ci, Co, K, stride, T, B, C.c_float(slope), C.c_void_p(li.ctypes.data), C.c_void_p(lo.ctypes.data), tile,
-                                          _dev(out), buf, C.c_size_t(len(buf)), _stream()))
-    if cfg is not None:
-        cfg.append(buf.value.decode())
-    return out
+    assert li.shape == lo.shape == (x.shape[0],)
+    return _conv_down(x, w, b, stride, slope, tile, cfg, li, lo)
 
 
-class LM:
+class LM(_Handle):
     """text2semantic RoFormer (lds_lm_*): encoder prefill + cached decode loop."""
+    KIND = "lm"
 
     def __init__(self, cfg, state):
         c = LMCfg()
@@ -677,24 +689,13 @@ class LM:
         c.n_spk_rows = cfg["n_spk"] + 1 if (cfg["n_spk"] is not None and cfg["n_spk"] > 1) else 0
         c.max_pos, c.eps = cfg["max_pos"], cfg["eps"]
         c.sem_bos, c.sem_eos, c.sem_pad = cfg["sem_bos"], cfg["sem_eos"], cfg["sem_pad"]
-        n, names, ptrs, numel, keep = _host_tensor_table(state)
-        self.h = C.c_void_p()
-        check(lib().lds_lm_create(C.byref(c), n, names, ptrs, numel, C.byref(self.h)))
+        self._create_weights(c, state)
         self.cfg = cfg
-        self.ws = Workspace()
-
-    def __del__(self):
-        if getattr(self, "h", None) and _lib is not None:
-            _lib.lds_lm_destroy(self.h)
-            self.h = None
 
     def _ws(self, B, L, max_length, device, num_beams=1):
-        nb = C.c_size_t()
         if num_beams == 1:
-            check(lib().lds_lm_workspace_bytes(self.h, B, L, max_length, C.byref(nb)))
-        else:
-            check(lib().lds_lm_workspace_bytes_opts(self.h, B, L, max_length, int(num_beams), C.byref(nb)))
-        return self.ws.get(nb.value, device)
+            return self._workspace("lds_lm_workspace_bytes", device, B, L, max_length)
+        return self._workspace("lds_lm_workspace_bytes_opts", device, B, L, max_length, int(num_beams))
 
     def encode(self, phone, tone, spk_id=None, enc_len=None):
         """enc_len: int32 [B] on the device (real positions per right-padded row) or None"""
@@ -704,8 +705,8 @@ class LM:
         sp = spk_id.contiguous().to(torch.int64) if spk_id is not None else None
         ws = self._ws(B, L, 2, phone.device)
         enc = torch.empty(B, L, self.cfg["hidden"], dtype=torch.float32, device=phone.device)
-        check(lib().lds_lm_encode(self.h, _dev(ph, torch.int64), _dev(tn, torch.int64), _dev(sp, torch.int64) if sp is not None else None,
-                                  _dev(enc_len, torch.int32) if enc_len is not None else None, _dev(enc), _dev(ws), C.c_size_t(ws.numel()), B, L, _stream()))
+        check(lib().lds_lm_encode(self.h, _dev(ph, torch.int64), _dev(tn, torch.int64), _dev_or_null(sp, torch.int64), _dev_or_null(enc_len, torch.int32),
+                                  _dev(enc), _dev(ws), ws.numel(), B, L, _stream()))
         return enc
 
     def generate(self, enc, max_length, do_sample, top_k, top_p, temperature, repetition_penalty, uniforms=None, return_logits=False, enc_len=None,
@@ -719,16 +720,13 @@ class LM:
         tokens = torch.empty(B, max_length, dtype=torch.int64, device=enc.device)
         logits = torch.empty(max_length - 1, B, self.cfg["sem_vocab"], dtype=torch.float32, device=enc.device) if return_logits else None
         n = C.c_int()
-        el = _dev(enc_len, torch.int32) if enc_len is not None else None
-        u = _dev(uniforms.contiguous(), torch.float32) if uniforms is not None else None
-        lg = _dev(logits) if logits is not None else None
+        enc, u = enc.contiguous(), uniforms.contiguous() if uniforms is not None else None
+        head = (self.h, _dev(enc, torch.float32), _dev_or_null(enc_len, torch.int32), B, L, int(max_length))
+        tail = (_dev_or_null(u, torch.float32), _dev(tokens), _dev_or_null(logits), C.byref(n), _dev(ws), ws.numel(), _stream())
         if num_beams == 1 and no_repeat_ngram_size == 0:      # the plain decode (lds_lm_generate_opts' wrapper)
-            check(lib().lds_lm_generate(self.h, _dev(enc.contiguous(), torch.float32), el, B, L, int(max_length), o.do_sample, o.top_k, C.c_float(o.top_p),
-                                        C.c_float(o.temperature), C.c_float(o.repetition_penalty), u, _dev(tokens), lg, C.byref(n), _dev(ws),
-                                        C.c_size_t(ws.numel()), _stream()))
+            check(lib().lds_lm_generate(*head, o.do_sample, o.top_k, o.top_p, o.temperature, o.repetition_penalty, *tail))
         else:
-            check(lib().lds_lm_generate_opts(self.h, _dev(enc.contiguous(), torch.float32), el, B, L, int(max_length), C.byref(o), u, _dev(tokens), lg,
-                                             C.byref(n), _dev(ws), C.c_size_t(ws.numel()), _stream()))
+            check(lib().lds_lm_generate_opts(*head, C.byref(o), *tail))
         toks = tokens[:, : n.value].contiguous()
         return toks, (logits[: n.value - 1] if logits is not None else None)
 
@@ -738,9 +736,7 @@ _kmeans_ws = Workspace()
 
 
 def kmeans_workspace_bytes(N, K, D):
-    nb = C.c_size_t()
-    check(lib().lds_kmeans_workspace_bytes(int(N), int(K), int(D), C.byref(nb)))
-    return nb.value
+    return _bytes("lds_kmeans_workspace_bytes", int(N), int(K), int(D))
 
 
 def _kmeans_ws_for(ws, N, K, D, device):
@@ -760,7 +756,7 @@ def kmeans_prepare(centers):
 
 def kmeans_assign(x, centers, h, return_best=False, ws=None, lengths=None, pad_id=0):
     """x [N, D] -> labels int64 [N] (the nearest centre, lowest index among ties) and optionally the winning score x.c - h.
-    lengths (host ints [B]) with x [B, T, D]: the ragged form, labels [B, T] with pad_id at and beyond every clip's length."""
+    lengths (host ints [B], 0 .. T) with x [B, T, D]: the ragged form, labels [B, T] with pad_id at and beyond every clip's length."""
     import torch
     K, D = centers.shape
     if x.shape[-1] != D or x.dim() != (3 if lengths is not None else 2):
@@ -769,17 +765,11 @@ def kmeans_assign(x, centers, h, return_best=False, ws=None, lengths=None, pad_i
     ws = _kmeans_ws_for(ws, N, K, D, x.device)
     labels = torch.empty(x.shape[:-1], dtype=torch.int64, device=x.device)
     best = torch.empty(x.shape[:-1], dtype=torch.float32, device=x.device) if return_best else None
-    if lengths is not None:
-        B, T = x.shape[:2]
-        ln = np.ascontiguousarray(np.asarray(lengths.cpu() if hasattr(lengths, "cpu") else lengths).reshape(-1), dtype=np.int32)
-        if ln.shape != (B,):
-            raise ValueError(f"kmeans_assign: lengths must be {B} integers")
-        check(lib().lds_kmeans_assign_ragged(_dev(x, torch.float32), B, T, C.c_void_p(ln.ctypes.data), int(pad_id), _dev(centers, torch.float32),
-                                             _dev(h, torch.float32), K, D, _dev(labels), _dev(best) if best is not None else None, _dev(ws),
-                                             C.c_size_t(ws.numel()), _stream()))
-    else:
-        check(lib().lds_kmeans_assign(_dev(x, torch.float32), N, _dev(centers, torch.float32), _dev(h, torch.float32), K, D, _dev(labels),
-                                      _dev(best) if best is not None else None, _dev(ws), C.c_size_t(ws.numel()), _stream()))
+    ln = None if lengths is None else _host_lengths(lengths, x.shape[0], 0, x.shape[1])
+    fn, ln_at = _dense_or_ragged("lds_kmeans_assign", ln)
+    rows = (N,) if ln is None else (x.shape[0], x.shape[1], *ln_at, int(pad_id))
+    check(fn(_dev(x, torch.float32), *rows, _dev(centers, torch.float32), _dev(h, torch.float32), K, D, _dev(labels), _dev_or_null(best), _dev(ws),
+             ws.numel(), _stream()))
     return (labels, best) if return_best else labels
 
 
@@ -793,7 +783,7 @@ def kmeans_update(x, labels, centers, h, num_points, ws=None):
     ws = _kmeans_ws_for(ws, N, K, D, x.device)
     err = torch.empty((), dtype=torch.float32, device=x.device)
     check(lib().lds_kmeans_update(_dev(x, torch.float32), _dev(labels, torch.int64), N, _dev(centers, torch.float32), _dev(h, torch.float32),
-                                  _dev(num_points, torch.float32), K, D, _dev(err), _dev(ws), C.c_size_t(ws.numel()), _stream()))
+                                  _dev(num_points, torch.float32), K, D, _dev(err), _dev(ws), ws.numel(), _stream()))
     return err
 
 
@@ -807,5 +797,5 @@ def kmeans_seed(x, K, first_index, uniforms, ws=None):
     if K > 1 and uniforms.numel() != K - 1:
         raise ValueError(f"kmeans_seed: {K - 1} uniforms needed, got {uniforms.numel()}")
     check(lib().lds_kmeans_seed(_dev(x, torch.float32), N, D, int(K), int(first_index), _dev(uniforms, torch.float32) if K > 1 else None, _dev(centers),
-                                _dev(picked), _dev(ws), C.c_size_t(ws.numel()), _stream()))
+                                _dev(picked), _dev(ws), ws.numel(), _stream()))
     return centers, picked

@@ -42,6 +42,67 @@ def test_capi_exports_every_declared_symbol(libpath):
     assert b"bad argument" in L.lds_last_error()
 
 
+def _parse_header(name):
+    """include/<name> with comments stripped -> ({function: (return type, [parameter types])}, {struct typedef: [(field, type, extents)]});
+    a type is the C spelling without qualifiers and names, any pointer is '*'"""
+    hdr = re.sub(r"/\*.*?\*/", " ", open(os.path.join(ROOT, "include", name)).read(), flags=re.S)
+    hdr = re.sub(r"^\s*#.*$", "", hdr, flags=re.M)
+
+    def ctype(decl):      # 'const float* x' -> '*', 'int64_t L' -> 'int64_t', 'const char*' (a return type) -> 'char*'
+        words = [w for w in re.findall(r"\w+", decl) if w != "const"]
+        return "*" if "*" in decl else words[0]
+    structs = {}
+    for body, tname in re.findall(r"typedef\s+struct\s*\{(.*?)\}\s*(\w+)\s*;", hdr, flags=re.S):
+        fields = []
+        for decl in filter(None, (d.strip() for d in body.split(";"))):
+            for i, piece in enumerate(decl.split(",")):      # 'int C1, C2, Tsrc' / 'int d[4][4]' / 'const float* w'
+                m = re.search(r"(\w+)\s*((?:\[\d+\])*)\s*$", piece)
+                fields.append((m.group(1), ctype(decl), tuple(int(e) for e in re.findall(r"\d+", m.group(2)))))
+                assert i == 0 or "*" not in decl, decl      # ('float *a, b' would need a per-declarator pointer rule)
+        structs[tname] = fields
+    hdr = re.sub(r"typedef\s+struct\s*\{.*?\}\s*\w+\s*;", "", hdr, flags=re.S)
+    protos = {}
+    for ret, fn, params in re.findall(r"([\w\s\*]+?)\b(lds_\w+)\s*\(([^()]*)\)\s*;", hdr):
+        ret = "char*" if "*" in ret else ret.split()[-1]
+        protos[fn] = (ret, [] if params.strip() == "void" else [ctype(p) for p in params.split(",")])
+    return protos, structs
+
+
+def test_binding_signatures_and_structures_match_the_headers(libpath):
+    """lds/native.py declares restype and argtypes of every entry point and mirrors every struct of include/lds.h and include/lds_test.h:
+    a call site then cannot hand the library a truncated pointer, size_t or int64_t, and a header edit that the binding misses fails here"""
+    import ctypes as C
+    from lds import native
+    kinds = {"*": C.c_void_p, "int": C.c_int, "size_t": C.c_size_t, "float": C.c_float, "int64_t": C.c_int64, "uint32_t": C.c_uint32}
+    returns = {"int": C.c_int, "void": None, "char*": C.c_char_p}
+    public, structs = _parse_header("lds.h")
+    test, test_structs = _parse_header("lds_test.h")
+    assert len(public) >= 53 and len(test) >= 38 and not set(public) & set(test)
+    assert set(public) == set(native.EXPORTS) and set(test) == set(native.TEST_EXPORTS)
+    assert len(native.EXPORTS) == len(public) and len(native.TEST_EXPORTS) == len(test)      # (no name twice)
+    assert native.LIB_PATH == libpath
+    L = native.lib()
+    for fn, (ret, params) in {**public, **test}.items():
+        f = getattr(L, fn)
+        assert f.argtypes is not None, fn
+        assert list(f.argtypes) == [kinds[p] for p in params], (fn, params, f.argtypes)
+        assert f.restype is returns[ret], (fn, ret, f.restype)
+    assert [fn for fn, (ret, _) in public.items() if ret == "void"] == [fn for fn in public if fn.endswith("_destroy")]
+    structs.update(test_structs)
+    mirrors = {"lds_unet_cfg": native.UNetCfg, "lds_vocoder_cfg": native.VocoderCfg, "lds_lm_cfg": native.LMCfg,
+               "lds_lm_decode_opts": native.LMDecodeOpts, "lds_whisper_cfg": native.WhisperCfg, "lds_conv_test": native.ConvTest,
+               "lds_dconv_test": native.DConvTest}
+    assert set(structs) == set(mirrors)
+    for tname, cls in mirrors.items():
+        assert [f[0] for f in cls._fields_] == [f[0] for f in structs[tname]], tname
+        for (fname, ftype), (_, ctype, extents) in zip(cls._fields_, structs[tname]):
+            got = []
+            while issubclass(ftype, C.Array):      # (c_int * 4) * 4 -> extents (4, 4) of c_int
+                got.append(ftype._length_)
+                ftype = ftype._type_
+            assert ftype is kinds[ctype] and tuple(got) == extents, (tname, fname, ftype, got, ctype, extents)
+
+
 def test_module_api_matches_reference_signatures():
     from diffusion.diffusion import GaussianDiffusion
     from diffusion.unit2mel import Unit2Mel, load_model_vocoder, load_svc_model
