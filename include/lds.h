@@ -312,6 +312,31 @@ int lds_kmeans_update(const float* X, const int64_t* labels, int64_t N, float* C
 int lds_kmeans_seed(const float* X, int64_t N, int D, int K, int64_t first_index, const float* uniforms, float* C, int64_t* picked, void* ws,
                     size_t ws_bytes, void* stream);
 
+/* ---- polyphase sinc resampler in front of the audio encoders (reference torchaudio.transforms.Resample(orig_freq, new_freq) with its
+ *      defaults sinc_interp_hann / lowpass_filter_width 6 / rolloff 0.99, i.e. torchaudio's _get_sinc_resample_kernel +
+ *      _apply_sinc_resample_kernel; called from tools/tools.py:78-84 Units_Encoder.encode, diffusion/vocoder.py:24-27 Vocoder.extract and
+ *      batch_proccessor/semantic_extract.py:49-68) ------------------------------------------------------------------------------------
+ * Stateless.  With O = orig / gcd, N = new / gcd a clip x[0 .. len) (zero outside) gives ceil(N len / O) samples
+ *   y[m] = sum_n x[n] g(n / O - m / N) = sum_{k < taps} x[(m / N) O + first[m % N] + k] bankT[k][m % N]
+ * bankT dev [taps][N] fp32 (tap-major) and first dev int32 [N] are the filter of one (orig, new, width, rolloff), evaluated in float64 on the
+ * host and rounded once (lds/arch.py resample_bank): first[i] = the first sample, relative to (m / N) O, inside the filter's support at
+ * phase i; the columns outside the support are left out (each below 1e-30).  One fmaf chain per output in tap order, all index arithmetic in
+ * integers (64-bit where m O needs it), no atomics: y[b] depends on x[b, :len] alone and is bit-identical on repeat, at any batch position
+ * and in either entry.  Nothing synchronises, no workspace.  Limits, checked before anything is enqueued (LDS_EINVAL with a message):
+ * 1 <= O, N <= 384,000; 1 <= taps <= 1024; N taps <= 2^24; 1 <= L <= 2^30; at most 2^31 - 1 output samples per clip; B <= 65,535
+ * (lds_resample) or B <= 64 (lds_resample_ragged); no NULL pointer except new_lengths.  A bank of more than 8192 entries is read from
+ * global memory instead of LDS (16000 -> 44101: 44,101 x 13); a pair whose 64 outputs need more than 8192 input samples runs a
+ * one-thread-per-output kernel (same bits). */
+/* x dev [B][L] -> y dev [B][M], M = ceil(N L / O) exactly (anything else is LDS_EINVAL) */
+int lds_resample(const float* x, float* y, const float* bankT, const int32_t* first, int O, int N, int taps, int B, int64_t L, int64_t M,
+                 void* stream);
+/* Ragged batch: lengths host int32 [B] (B <= 64, 0 <= lengths[b] <= L) = every clip's own sample count inside x [B][L].  Clip b is
+ * resampled as if alone: samples at and beyond lengths[b] are never read into a result (NaN / Inf included), y[b][m] = 0 for
+ * m >= ceil(N lengths[b] / O); M >= the largest of those is the row length of y.  new_lengths host int64 [B] or NULL receives
+ * ceil(N lengths[b] / O).  With every length equal to L and M = ceil(N L / O) the result is lds_resample's, bit for bit. */
+int lds_resample_ragged(const float* x, const int32_t* lengths, float* y, int64_t* new_lengths, const float* bankT, const int32_t* first, int O,
+                        int N, int taps, int B, int64_t L, int64_t M, void* stream);
+
 /* ---- per-launch HIP-event timing for bench.py's roofline leg (off by default) ------------------
  * lds_prof_enable(1) clears and starts recording one event pair per kernel launch on the launch
  * stream; lds_prof_summary synchronises them and writes a JSON list of

@@ -430,3 +430,45 @@ def whisper_mel_filters(n_mels, sr=16000, n_fft=400):
         w[i] = np.maximum(0.0, np.minimum(-ramps[i] / fdiff[i], ramps[i + 2] / fdiff[i + 1]))
     w *= (2.0 / (mel_f[2:n_mels + 2] - mel_f[:n_mels]))[:, None]
     return w.astype(np.float32)
+
+
+RESAMPLE_MAX_RATE, RESAMPLE_MAX_TAPS, RESAMPLE_MAX_BANK = 384000, 1024, 1 << 24      # include/lds.h lds_resample
+
+
+def resample_bank(orig_freq, new_freq, lowpass_filter_width=6, rolloff=0.99):
+    """The polyphase filter of torchaudio.transforms.Resample(orig_freq, new_freq, "sinc_interp_hann", lowpass_filter_width, rolloff) for
+    lds_resample: (O, N, taps, bankT fp32 [taps][N], first int32 [N]).  With O = orig / gcd, N = new / gcd, B = rolloff min(O, N) and the
+    integer d = j N - i O (the tap j of phase i sits at d / (O N) periods from the output):
+        g(d) = (B / O) sinc(u) cos^2(pi u / (2 w)),   u = clamp(B d / (O N), -w, +w)
+    first[i] = the smallest j with |u| < w, taps = the most columns any phase has inside the support, bankT[k][i] = g((first[i] + k) N - i O)
+    evaluated in float64 and rounded to fp32 once.  The columns left out sit at the clamp: cos^2(pi / 2) sinc(w), below 1e-30."""
+    import math
+
+    import numpy as np
+    w = int(lowpass_filter_width)
+    if w != lowpass_filter_width or w < 1:
+        raise ValueError(f"lowpass_filter_width must be an integer >= 1 (got {lowpass_filter_width})")
+    if not 0.0 < rolloff <= 1.0:
+        raise ValueError(f"rolloff must be in (0, 1] (got {rolloff})")
+    for f in (orig_freq, new_freq):
+        if int(f) != f or not 1 <= f <= RESAMPLE_MAX_RATE:
+            raise ValueError(f"sample rates must be integers in 1 .. {RESAMPLE_MAX_RATE} (got {orig_freq}, {new_freq})")
+    g = math.gcd(int(orig_freq), int(new_freq))
+    O, N = int(orig_freq) // g, int(new_freq) // g
+    base = min(O, N) * float(rolloff)
+    half = w * O * N / base                                     # the support is |d| < half
+    i = np.arange(N, dtype=np.int64)
+    j0 = np.floor((i * O - half) / N).astype(np.int64) + 1      # smallest j with j N - i O > -half, made exact against float rounding:
+    j0 += (j0 * N - i * O) <= -half
+    j0 -= ((j0 - 1) * N - i * O) > -half
+    j1 = np.ceil((i * O + half) / N).astype(np.int64) - 1       # largest j with j N - i O < half
+    j1 -= (j1 * N - i * O) >= half
+    j1 += ((j1 + 1) * N - i * O) < half
+    taps = int((j1 - j0 + 1).max())
+    if taps > RESAMPLE_MAX_TAPS or N * taps > RESAMPLE_MAX_BANK:
+        raise ValueError(f"resampling {orig_freq} -> {new_freq} needs {taps} taps x {N} phases; at most {RESAMPLE_MAX_TAPS} taps and "
+                         f"{RESAMPLE_MAX_BANK} bank entries are built")
+    d = (j0[None, :] + np.arange(taps, dtype=np.int64)[:, None]) * N - (i * O)[None, :]      # [taps][N]
+    u = np.clip(base * d / (O * N), -float(w), float(w))
+    bank = (base / O) * np.sinc(u) * np.cos(np.pi * u / (2.0 * w)) ** 2
+    return O, N, taps, np.ascontiguousarray(bank, dtype=np.float32), np.ascontiguousarray(j0, dtype=np.int32)

@@ -109,6 +109,8 @@ lds_kmeans_assign                i:pqppiipppzp
 lds_kmeans_assign_ragged         i:piipqppiipppzp
 lds_kmeans_update                i:ppqpppiippzp
 lds_kmeans_seed                  i:pqiiqppppzp
+lds_resample                     i:ppppiiiiqqp
+lds_resample_ragged              i:ppppppiiiiqqp
 lds_prof_enable                  i:i
 lds_prof_summary                 i:pz
 lds_unet_set_gemm_mode           i:pi
@@ -799,3 +801,47 @@ def kmeans_seed(x, K, first_index, uniforms, ws=None):
     check(lib().lds_kmeans_seed(_dev(x, torch.float32), N, D, int(K), int(first_index), _dev(uniforms, torch.float32) if K > 1 else None, _dev(centers),
                                 _dev(picked), _dev(ws), ws.numel(), _stream()))
     return centers, picked
+
+
+# ---- polyphase resampler (lds_resample*): the filter of one (orig, new, width, rolloff) is built once on the host (arch.resample_bank) and
+# uploaded once per device ----
+_resample_tables = {}
+
+
+def resample_tables(orig_freq, new_freq, lowpass_filter_width=6, rolloff=0.99):
+    """the cached host tables of a parameter set (no device needed): dict with O, N, taps, bankT fp32 [taps, N], first int32 [N]"""
+    key = (orig_freq, new_freq, lowpass_filter_width, float(rolloff))      # (arch.resample_bank refuses what is not an integer)
+    t = _resample_tables.get(key)
+    if t is None:
+        from . import arch
+        O, N, taps, bankT, first = arch.resample_bank(*key)
+        t = _resample_tables[key] = dict(O=O, N=N, taps=taps, bankT=bankT, first=first, dev={})
+    return t
+
+
+def resample_out_length(length, O, N):
+    return -((-int(length) * N) // O)
+
+
+def resample(x, tables, lengths=None):
+    """x [B, L] fp32 on the device, tables from resample_tables -> y [B, M] (include/lds.h lds_resample); with lengths (host ints [B], at most
+    64 clips, 0 .. L): every clip resampled as if alone, zeros beyond its own ceil(N len / O) samples; returns (y [B, Mmax], new lengths
+    int64 [B] on the host) (lds_resample_ragged)"""
+    import torch
+    if not x.is_cuda:
+        raise RuntimeError("liblds needs tensors on a HIP device (no CPU fallback for the hot path)")
+    B, L = x.shape
+    O, N = tables["O"], tables["N"]
+    dev = tables["dev"].get(str(x.device))
+    if dev is None:
+        dev = tables["dev"][str(x.device)] = (torch.from_numpy(tables["bankT"]).to(x.device), torch.from_numpy(tables["first"]).to(x.device))
+    ln = None if lengths is None else _host_lengths(lengths, B, 0, L, max_B=64, what="resampler")
+    M = resample_out_length(L if ln is None else max(int(ln.max()), 1), O, N)
+    y = torch.empty((B, M), dtype=torch.float32, device=x.device)
+    tail = (_dev(dev[0], torch.float32), _dev(dev[1], torch.int32), O, N, tables["taps"], B, L, M, _stream())
+    if ln is None:
+        check(lib().lds_resample(_dev(x, torch.float32), _dev(y), *tail))
+        return y
+    new = np.zeros(B, dtype=np.int64)
+    check(lib().lds_resample_ragged(_dev(x, torch.float32), _host(ln), _dev(y), _host(new), *tail))
+    return y, torch.from_numpy(new)

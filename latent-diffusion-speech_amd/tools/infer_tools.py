@@ -18,10 +18,11 @@ class DiffusionSVC:
         self.units_encoder = None
         self.volume_extractor = None
 
-    def load_model(self, model_path, loaded_vocoder=None, units_encoder_checkpoint=None, **_ignored):
+    def load_model(self, model_path, loaded_vocoder=None, units_encoder_checkpoint=None, *, resample=False, **_ignored):
         """reference infer_tools.py:28-30 (22_infer_tts.py passes extra f0_min/f0_max keywords that the reference's own
         method does not accept; they are accepted and ignored here).  The reference builds its Units_Encoder here (infer_tools.py:31-38);
-        this one only when `units_encoder_checkpoint` names the Whisper encoder's checkpoint (large-v3_encoder.pt)."""
+        this one only when `units_encoder_checkpoint` names the Whisper encoder's checkpoint (large-v3_encoder.pt).  `resample`
+        (keyword-only, not in the reference) goes to Units_Encoder: with True, encode_units resamples audio of another rate."""
         self.model_path = model_path
         self.model, self.vocoder, self.args = load_model_vocoder(model_path, device=self.device, loaded_vocoder=loaded_vocoder)
         if units_encoder_checkpoint is not None:
@@ -30,11 +31,11 @@ class DiffusionSVC:
             self.units_encoder = Units_Encoder(getattr(data, "encoder", "whisper_large_v3"), getattr(data, "encoder_sample_rate", 16000),
                                                getattr(data, "encoder_hop_size", 320), device=self.device,
                                                units_forced_mode=getattr(data, "units_forced_mode", "nearest"),
-                                               model=WhisperLargeV3(device=self.device, checkpoint=units_encoder_checkpoint))
+                                               model=WhisperLargeV3(device=self.device, checkpoint=units_encoder_checkpoint), resample=resample)
 
     def encode_units(self, audio, sr=44100, padding_mask=None):
         """reference infer_tools.py:41-44: audio at `sr` -> units [T, C] on the device (Units_Encoder.encode: `sr` must be the encoder's
-        rate, resampling is not built)"""
+        rate unless load_model was given resample=True)"""
         if self.units_encoder is None:
             raise NotImplementedError("no units encoder is loaded: pass units_encoder_checkpoint= to load_model, or set .units_encoder")
         return self.units_encoder.encode(audio, sr, padding_mask=padding_mask)

@@ -1,6 +1,7 @@
-"""The pieces of reference tools/tools.py that are built: the encoder-width table, `units_forced_alignment`, and the Whisper
-units encoder (`Units_Encoder` / `WhisperLargeV3`, reference tools/tools.py:43-126).  The two other speech encoders, the volume
-extractor and the schedulers there are not built."""
+"""The pieces of reference tools/tools.py that are built: the encoder-width table, `units_forced_alignment`, the Whisper
+units encoder (`Units_Encoder` / `WhisperLargeV3`, reference tools/tools.py:43-126) and `Resample`, the torchaudio transform that
+file imports (tools/tools.py:9).  The two other speech encoders, the volume extractor and the schedulers there are not built
+(SURVEY.md section 2)."""
 import math
 
 import numpy as np
@@ -46,17 +47,62 @@ def units_forced_alignment(units, audio=None, sample_rate=None, hop_size=None, n
     return out.squeeze(0) if squeeze else out
 
 
+class Resample(torch.nn.Module):
+    """torchaudio.transforms.Resample with its positional parameters and defaults (the reference imports it at tools/tools.py:9 and
+    diffusion/vocoder.py:3): waveform [..., L] on a HIP device -> [..., ceil(new L / orig)], the polyphase kernel of lds_resample
+    (include/lds.h).  orig_freq == new_freq returns the input itself.  Built: "sinc_interp_hann" with any integer
+    lowpass_filter_width >= 1 and 0 < rolloff <= 1; "sinc_interp_kaiser" raises NotImplementedError; CPU tensors raise (no CPU
+    fallback).  The filter is built once per parameter set on the host in float64 and uploaded once per device, so `.to(device)` has
+    nothing to move."""
+
+    def __init__(self, orig_freq=16000, new_freq=16000, resampling_method="sinc_interp_hann", lowpass_filter_width=6, rolloff=0.99):
+        super().__init__()
+        if resampling_method == "sinc_interp_kaiser":
+            raise NotImplementedError("Resample: the Kaiser window (sinc_interp_kaiser) is not built; sinc_interp_hann is")
+        if resampling_method != "sinc_interp_hann":
+            raise ValueError(f"Invalid resampling method: {resampling_method}")
+        self.orig_freq, self.new_freq = orig_freq, new_freq
+        self.resampling_method, self.lowpass_filter_width, self.rolloff = resampling_method, lowpass_filter_width, rolloff
+        self.tables = None if orig_freq == new_freq else native.resample_tables(orig_freq, new_freq, lowpass_filter_width, rolloff)
+
+    def _check(self, name, waveform):
+        if not torch.is_tensor(waveform) or not waveform.is_cuda:
+            raise RuntimeError(f"{name} needs the waveform as a tensor on a HIP device (no CPU fallback)")
+
+    @torch.inference_mode()
+    def forward(self, waveform):
+        if self.tables is None:
+            return waveform
+        self._check("Resample.forward", waveform)
+        x = waveform.reshape(-1, waveform.shape[-1]).float().contiguous()
+        y = torch.cat([native.resample(x[r:r + 65535], self.tables) for r in range(0, x.shape[0], 65535)])      # (the entry's batch limit)
+        return y.reshape(*waveform.shape[:-1], y.shape[-1])
+
+    @torch.inference_mode()
+    def forward_ragged(self, waveform, lengths):
+        """Extension (not in the reference): waveform [B, L] padded to the longest clip + every clip's own sample count (host ints, at
+        most 64 clips, 0 .. L) -> (out [B, Mmax], new_lengths int64 [B] on the host): every clip resampled as if alone, whatever lies
+        beyond its length (NaN included); new_lengths[b] = ceil(new lengths[b] / orig), zeros beyond; Mmax = the largest of them"""
+        if self.tables is None:
+            ln = native._host_lengths(lengths, waveform.shape[0], 0, waveform.shape[1], max_B=64, what="resampler")
+            return waveform, torch.from_numpy(ln.astype(np.int64))
+        self._check("Resample.forward_ragged", waveform)
+        return native.resample(waveform.float().contiguous(), self.tables, lengths)
+
+
 class Units_Encoder:
     """Speech -> units (reference tools/tools.py:43-103).  Built: encoder 'whisper_large_v3' in the 'nearest' / 'left' modes.
     Deviations from the reference, each raising instead of guessing:
-      - resampling is not built: `sample_rate` must equal `encoder_sample_rate` (ValueError naming both), where the reference
-        resamples with torchaudio;
+      - resampling is opt-in: by default `sample_rate` must equal `encoder_sample_rate` (ValueError naming both), where the reference
+        resamples with torchaudio; with `resample=True` (keyword-only, not in the reference) a mismatched rate goes through
+        `self.resample_kernel[str(sample_rate)]`, a `Resample(sample_rate, encoder_sample_rate)` made on first use as the reference
+        makes it (tools/tools.py:81-84), in encode, encode_ragged and the encode_tokens* forms;
       - the units stay on the device (the reference moves them to the CPU); CPU tensors raise, there is no CPU fallback;
       - 'w2v-bert' needs a transformers hub download and 'xlsr_53_56k' fairseq: NotImplementedError; the 'rfa441to512' /
         'rfa512to441' modes need librosa's resampler: NotImplementedError.
     `model` (not in the reference): a ready WhisperLargeV3, e.g. WhisperLargeV3.synthetic(...), instead of the checkpoint."""
 
-    def __init__(self, encoder, encoder_sample_rate=16000, encoder_hop_size=320, device=None, units_forced_mode='nearest', *, model=None):
+    def __init__(self, encoder, encoder_sample_rate=16000, encoder_hop_size=320, device=None, units_forced_mode='nearest', *, model=None, resample=False):
         if device is None:
             device = 'cuda' if torch.cuda.is_available() else 'cpu'
         self.device = device
@@ -74,20 +120,30 @@ class Units_Encoder:
             raise NotImplementedError(f"units_forced_mode {units_forced_mode!r} resamples with librosa; not built")
         self.model = model if model is not None else WhisperLargeV3(device=device)
         self.resample_kernel = {}
+        self.resample = bool(resample)
         self.encoder_sample_rate = encoder_sample_rate
         self.encoder_hop_size = encoder_hop_size
 
     def _check(self, name, audio, sample_rate):
-        if sample_rate != self.encoder_sample_rate:
+        """the resampler for this rate (None: the audio is at the encoder's rate already), after the checks of every entry"""
+        if sample_rate != self.encoder_sample_rate and not self.resample:
             raise ValueError(f"{name}: audio at {sample_rate} Hz, the encoder runs at {self.encoder_sample_rate} Hz; "
-                             "resampling is not built, resample the audio first")
+                             "resample the audio first, or pass resample=True / use tools.tools.Resample")
         if not torch.is_tensor(audio) or not audio.is_cuda:
             raise RuntimeError(f"{name} needs the audio as a tensor on a HIP device (no CPU fallback)")
+        if sample_rate == self.encoder_sample_rate:
+            return None
+        key_str = str(sample_rate)
+        if key_str not in self.resample_kernel:
+            self.resample_kernel[key_str] = Resample(sample_rate, self.encoder_sample_rate).to(self.device)
+        return self.resample_kernel[key_str]
 
     def encode(self, audio, sample_rate, padding_mask=None):
         """audio [L] or [1, L] -> units [T, C] on the device (reference tools/tools.py:76-103; padding_mask is ignored as
         WhisperLargeV3.__call__ ignores it); a clip shorter than 400 samples is zero-padded to 400 as the reference does"""
-        self._check("Units_Encoder.encode", audio, sample_rate)
+        rs = self._check("Units_Encoder.encode", audio, sample_rate)
+        if rs is not None:
+            audio = rs(audio)
         if audio.size(-1) < 400:
             audio = torch.nn.functional.pad(audio, (0, 400 - audio.size(-1)))
         units = self.model(audio, padding_mask=padding_mask)
@@ -99,8 +155,14 @@ class Units_Encoder:
         """Extension (not in the reference): audio [B, L] padded to the longest clip + every clip's own sample count (host ints, at most 64
         clips) -> (units [B, Tmax, C], n_frames [B] int64 on the host): every clip encoded as if alone, rows beyond its own
         n_frames[b] = (lengths[b] // 160 - 1) // 2 + 1 are zeros.  400 <= lengths[b] <= L (ValueError otherwise: pad a shorter clip with
-        zeros to 400 samples first, as encode does)."""
-        self._check("Units_Encoder.encode_ragged", audio, self.encoder_sample_rate if sample_rate is None else sample_rate)
+        zeros to 400 samples first, as encode does).  With resample=True and another `sample_rate`, audio and lengths are at that rate:
+        the batch is resampled by Resample.forward_ragged first, and the limits apply to the resampled lengths (a batch whose longest
+        resampled clip is below 400 samples is zero-padded to 400 columns)."""
+        rs = self._check("Units_Encoder.encode_ragged", audio, self.encoder_sample_rate if sample_rate is None else sample_rate)
+        if rs is not None:
+            audio, lengths = rs.forward_ragged(audio, lengths)
+            if audio.size(-1) < 400:
+                audio = torch.nn.functional.pad(audio, (0, 400 - audio.size(-1)))
         return self.model.encode_ragged(audio, lengths)
 
     def encode_tokens(self, audio, sample_rate, codebook):

@@ -1,9 +1,11 @@
 """Encode a directory of float32 .npy waveforms to VAE latents (the reference's batch_proccessor/acoustic_extract.py flow).
 
-    python tools/extract_latents.py IN_DIR OUT_DIR --model pretrain/hifi-vaegan [--batch 16] [--only-mean] [--ragged]
+    python tools/extract_latents.py IN_DIR OUT_DIR --model pretrain/hifi-vaegan [--batch 16] [--only-mean] [--ragged] [--sample-rate R]
 
-Every IN_DIR/<name>.npy (1-D float32 at the vocoder's sample rate) becomes OUT_DIR/<name>.npy of shape [ceil(len / hop), 2C]
-(m, then logs; zeros for logs with --only-mean).  Files are batched in sorted order and right-padded with zeros to the longest clip of
+Every IN_DIR/<name>.npy (1-D float32 at the vocoder's sample rate, or at --sample-rate: then every batch is resampled on the device
+first, each clip as if alone, by tools.tools.Resample.forward_ragged -- the reference's torchaudio Resample(R, vocoder rate) -- and
+len below is the resampled length) becomes OUT_DIR/<name>.npy of shape [ceil(len / hop), 2C] (m, then logs; zeros for logs with
+--only-mean).  Files are batched in sorted order and right-padded with zeros to the longest clip of
 their batch; each result is cropped to its own ceil(len / hop) frames afterwards.  That is the reference's own behaviour, and it means
 that a clip's last frames can depend on its batch: the encoder's receptive field reaches into the padding of the batch, so a shorter clip
 encoded with a longer one need not give what it gets alone.  With --ragged, each batch goes through Vocoder.extract_ragged with the clips'
@@ -20,6 +22,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from diffusion.vocoder import Vocoder  # noqa: E402
+from tools.tools import Resample  # noqa: E402
 
 
 def main():
@@ -30,9 +33,14 @@ def main():
     ap.add_argument("--batch", type=int, default=16)
     ap.add_argument("--only-mean", action="store_true", help="write zeros for logs (reference extract(only_mean=True))")
     ap.add_argument("--ragged", action="store_true", help="encode every clip as if alone (extract_ragged with the clips' own lengths)")
+    ap.add_argument("--sample-rate", type=int, default=None, help="rate of the clips (default: the vocoder's)")
     a = ap.parse_args()
     voc = Vocoder("hifi-vaegan", a.model, device="cuda")
     hop = voc.vocoder_hop_size
+    rs = None
+    if a.sample_rate not in (None, voc.vocoder_sample_rate):
+        rs = Resample(a.sample_rate, voc.vocoder_sample_rate)
+        a.batch = min(a.batch, 64)      # (the ragged resampler's batch limit)
     names = sorted(f for f in os.listdir(a.in_dir) if f.endswith(".npy"))
     os.makedirs(a.out_dir, exist_ok=True)
     for i in range(0, len(names), a.batch):
@@ -42,13 +50,16 @@ def main():
         audio = np.zeros((len(clips), L), dtype=np.float32)
         for b, c in enumerate(clips):
             audio[b, :len(c)] = c
-        x = torch.from_numpy(audio).cuda()
+        x, lens = torch.from_numpy(audio).cuda(), [len(c) for c in clips]
+        if rs is not None:
+            x, lens = rs.forward_ragged(x, lens)
+            lens = lens.tolist()
         if a.ragged:
-            lat = voc.extract_ragged(x, voc.vocoder_sample_rate, [len(c) for c in clips], only_mean=a.only_mean).cpu().numpy()
+            lat = voc.extract_ragged(x, voc.vocoder_sample_rate, lens, only_mean=a.only_mean).cpu().numpy()
         else:
             lat = voc.extract(x, voc.vocoder_sample_rate, only_mean=a.only_mean).cpu().numpy()
-        for b, (f, c) in enumerate(zip(group, clips)):
-            np.save(os.path.join(a.out_dir, f), lat[b, :math.ceil(len(c) / hop)])
+        for b, f in enumerate(group):
+            np.save(os.path.join(a.out_dir, f), lat[b, :math.ceil(lens[b] / hop)])
         print(f"{i + len(group)} / {len(names)}")
 
 

@@ -1,14 +1,16 @@
-"""Turn unit files, or 16 kHz clips, into semantic tokens (the reference's 19_preprocess_token.py, its kmeans branch).
+"""Turn unit files, or audio clips, into semantic tokens (the reference's 19_preprocess_token.py, its kmeans branch).
 
     python tools/extract_tokens.py IN_DIR [--out DIR] [--codebook pretrain/semantic_codebook.pt | --synthetic K [--seed S]] [--batch 8]
-                                   [--from-audio [--checkpoint pretrain/large-v3_encoder.pt | --synthetic-encoder [--layers N]]]
+                                   [--from-audio [--checkpoint pretrain/large-v3_encoder.pt | --synthetic-encoder [--layers N]]
+                                    [--sample-rate R]]
 
 IN_DIR holds .npy unit files [T, dim] (tools/extract_units.py writes them).  Every file becomes DIR/<name>.npy (default DIR:
 IN_DIR/../semantic_token) of int64 tokens [T]: the index of the nearest centre of the codebook, computed on the HIP device by
 cluster.get_cluster_result.  Files are batched in sorted order, padded to the longest of the batch and assigned in the ragged form, so
 a file's tokens do not depend on its batch.  --synthetic K uses K seeded N(0, 1) centres instead of a checkpoint.
---from-audio: IN_DIR holds 16 kHz clips instead (.npy samples or PCM16 .wav, as tools/extract_units.py reads them); every batch goes
-through Units_Encoder.encode_tokens_ragged (Whisper units, then the nearest centre) without leaving the device.  --synthetic-encoder
+--from-audio: IN_DIR holds clips instead (.npy samples at --sample-rate, default 16000, or PCM16 .wav of any rate, as
+tools/extract_units.py reads them; what is not at 16 kHz is resampled on the device inside its batch); every batch goes through
+Units_Encoder.encode_tokens_ragged (Whisper units, then the nearest centre) without leaving the device.  --synthetic-encoder
 runs seeded encoder weights at large-v3's width (--layers sets the depth) where no checkpoint exists.
 """
 import argparse
@@ -43,7 +45,8 @@ def main():
     ap.add_argument("--synthetic", type=int, default=0, metavar="K")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--batch", type=int, default=8)
-    ap.add_argument("--from-audio", action="store_true", help="IN_DIR holds 16 kHz clips: encode them to units first")
+    ap.add_argument("--from-audio", action="store_true", help="IN_DIR holds audio clips: encode them to units first")
+    ap.add_argument("--sample-rate", type=int, default=16000, help="--from-audio: rate of the .npy clips (a .wav carries its own)")
     ap.add_argument("--checkpoint", default="pretrain/large-v3_encoder.pt")
     ap.add_argument("--synthetic-encoder", action="store_true", help="seeded Whisper weights instead of the checkpoint")
     ap.add_argument("--layers", type=int, default=32)
@@ -64,13 +67,9 @@ def main():
     for i in range(0, len(paths), batch):
         group = paths[i: i + batch]
         if a.from_audio:
-            from extract_units import load_clip      # (tools/ is this script's own directory)
-            clips = [load_clip(p) for p in group]
-            slen = [max(len(c), 400) for c in clips]      # (a clip shorter than 400 samples is zero-padded to 400, as Units_Encoder.encode does)
-            audio = np.zeros((len(clips), max(slen)), dtype=np.float32)
-            for b, c in enumerate(clips):
-                audio[b, : len(c)] = c
-            tok, lens = ue.encode_tokens_ragged(torch.from_numpy(audio).cuda(), slen, model, pad_id=-1)
+            from extract_units import encoder_batch, load_clip      # (tools/ is this script's own directory)
+            audio, slen = encoder_batch([load_clip(p, a.sample_rate) for p in group])      # (16 kHz on the device; at least 400 samples each)
+            tok, lens = ue.encode_tokens_ragged(audio, slen, model, pad_id=-1)
             tok, lens = tok.cpu().numpy(), [int(n) for n in lens]
         else:
             units = [np.load(p).astype(np.float32) for p in group]

@@ -1,13 +1,16 @@
-"""Encode 16 kHz clips to Whisper units (the reference's 10_preprocess_train_unit.py flow; the counterpart of tools/extract_latents.py).
+"""Encode clips to Whisper units (the reference's 10_preprocess_train_unit.py flow; the counterpart of tools/extract_latents.py).
 
     python tools/extract_units.py IN [--out DIR] [--checkpoint pretrain/large-v3_encoder.pt | --synthetic [--layers N] [--seed S]] [--batch 8]
+                                     [--sample-rate R]
 
 IN is a directory (every .npy / .wav in it, sorted) or a text file listing one clip per line.  A .npy holds 1-D float32 samples at
-16 kHz; a .wav must be 16 kHz PCM16 (mono, or the first channel is taken) -- resampling is not built.  Every clip becomes
-DIR/<name>.npy (default DIR: IN's directory + /units) of shape [T, n_audio_state], T = (len // 160 - 1) // 2 + 1.  Clips are batched
-in sorted order through Units_Encoder.encode_ragged with their own lengths, so every clip's units are those of the clip encoded alone,
-whatever its batch; clips shorter than 400 samples are zero-padded to 400 as Units_Encoder.encode does; clips over 30 s (more than
-n_audio_ctx frames) are refused, as the data set's own preparation cuts them (00_del_audio_over_30s.py).
+--sample-rate (default 16000); a .wav is PCM16 of any rate, read from its header (mono, or the first channel is taken).  Clips that
+are not at 16 kHz are resampled on the device inside their batch (tools.tools.Resample.forward_ragged: every clip as if alone, the
+reference's torchaudio Resample(rate, 16000)).  Every clip becomes DIR/<name>.npy (default DIR: IN's directory + /units) of shape
+[T, n_audio_state], T = (len // 160 - 1) // 2 + 1 with len the clip's samples at 16 kHz.  Clips are batched in sorted order through
+Units_Encoder.encode_ragged with their own lengths, so every clip's units are those of the clip encoded alone, whatever its batch;
+clips shorter than 400 samples at 16 kHz are zero-padded to 400 as Units_Encoder.encode does; clips over 30 s (more than
+n_audio_ctx frames, counted at 16 kHz) are refused, as the data set's own preparation cuts them (00_del_audio_over_30s.py).
 --synthetic runs seeded weights at large-v3's width (no checkpoint needed; --layers sets the depth, default 32).
 """
 import argparse
@@ -22,17 +25,47 @@ import torch  # noqa: E402
 
 from encoder.whisper.model import ModelDimensions  # noqa: E402
 from lds import arch  # noqa: E402
-from tools.tools import Units_Encoder, WhisperLargeV3  # noqa: E402
+from tools.tools import Resample, Units_Encoder, WhisperLargeV3  # noqa: E402
+
+ENCODER_RATE = 16000
+_resamplers = {}
 
 
-def load_clip(path):
+def load_clip(path, npy_rate=ENCODER_RATE):
+    """-> (samples float32 [L], their rate): a .npy at `npy_rate`, a PCM16 .wav at its header's rate"""
     if path.endswith(".npy"):
-        return np.load(path).astype(np.float32).reshape(-1)
+        return np.load(path).astype(np.float32).reshape(-1), int(npy_rate)
     with wave.open(path, "rb") as w:
-        if w.getframerate() != 16000 or w.getsampwidth() != 2:
-            raise ValueError(f"{path}: {w.getframerate()} Hz, {8 * w.getsampwidth()} bit; 16 kHz PCM16 is needed (resampling is not built)")
+        if w.getsampwidth() != 2:
+            raise ValueError(f"{path}: {8 * w.getsampwidth()} bit; PCM16 is needed")
+        rate = w.getframerate()
         pcm = np.frombuffer(w.readframes(w.getnframes()), dtype=np.int16).reshape(-1, w.getnchannels())[:, 0]
-    return pcm.astype(np.float32) / 32768.0
+    return pcm.astype(np.float32) / 32768.0, rate
+
+
+def encoder_batch(clips):
+    """[(samples, rate)] (at most 64) -> (audio [B, Lmax] on the device at 16 kHz, lengths [B]): the clips of every other rate go through
+    one Resample.forward_ragged call per rate, each clip as if alone; a clip shorter than 400 samples counts as 400 (zeros follow it)"""
+    rows = [None] * len(clips)
+    for rate in sorted({r for _, r in clips}):
+        idx = [b for b, (_, r) in enumerate(clips) if r == rate]
+        lens = [len(clips[b][0]) for b in idx]
+        a = np.zeros((len(idx), max(lens)), dtype=np.float32)
+        for k, b in enumerate(idx):
+            a[k, :lens[k]] = clips[b][0]
+        x = torch.from_numpy(a).cuda()
+        if rate != ENCODER_RATE:
+            if rate not in _resamplers:
+                _resamplers[rate] = Resample(rate, ENCODER_RATE)
+            x, lens = _resamplers[rate].forward_ragged(x, lens)
+            lens = lens.tolist()
+        for k, b in enumerate(idx):
+            rows[b] = x[k, :lens[k]]
+    lens = [max(int(r.numel()), 400) for r in rows]
+    audio = torch.zeros((len(rows), max(lens)), dtype=torch.float32, device="cuda")
+    for b, r in enumerate(rows):
+        audio[b, :r.numel()] = r
+    return audio, lens
 
 
 def main():
@@ -44,6 +77,7 @@ def main():
     ap.add_argument("--layers", type=int, default=32)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--batch", type=int, default=8)
+    ap.add_argument("--sample-rate", type=int, default=ENCODER_RATE, help="rate of the .npy clips (a .wav carries its own)")
     a = ap.parse_args()
     if os.path.isdir(a.inp):
         base = a.inp
@@ -61,12 +95,8 @@ def main():
     batch = max(1, min(a.batch, 64))
     for i in range(0, len(paths), batch):
         group = paths[i:i + batch]
-        clips = [load_clip(p) for p in group]
-        lens = [max(len(c), 400) for c in clips]
-        audio = np.zeros((len(clips), max(lens)), dtype=np.float32)
-        for b, c in enumerate(clips):
-            audio[b, :len(c)] = c
-        units, n_frames = ue.encode_ragged(torch.from_numpy(audio).cuda(), lens)
+        audio, lens = encoder_batch([load_clip(p, a.sample_rate) for p in group])
+        units, n_frames = ue.encode_ragged(audio, lens)
         units = units.cpu().numpy()
         for b, p in enumerate(group):
             np.save(os.path.join(out, os.path.splitext(os.path.basename(p))[0] + ".npy"), units[b, :int(n_frames[b])])
