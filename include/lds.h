@@ -337,6 +337,43 @@ int lds_resample(const float* x, float* y, const float* bankT, const int32_t* fi
 int lds_resample_ragged(const float* x, const int32_t* lengths, float* y, int64_t* new_lengths, const float* bankT, const int32_t* first, int O,
                         int N, int taps, int B, int64_t L, int64_t M, void* stream);
 
+/* ---- long-audio conversion: slicing, volume mask, per-clip alignment and the cross-fading join (csrc/svc.hip) -------------------------
+ * The device side of DiffusionSVC.infer_from_long_audio (reference tools/infer_tools.py:83-117).  fp32 in and out, no atomics: a repeat
+ * gives the same bits; nothing synchronises; a bad argument is LDS_EINVAL with a message before anything is enqueued.  The two mean
+ * squares (lds_frame_rms, lds_volume_extract) are summed in fp64 and rounded to fp32 once, after the root.
+ *
+ * lds_frame_rms: librosa.feature.rms(y, frame_length, hop_length, center=True) as the slicer calls it (reference tools/slicer.py:40):
+ * rms[t] = sqrt(mean_{i < fl} xp[t hop + i]^2), xp = x padded by fl / 2 on both sides with zeros (pad_mode 0, librosa >= 0.10's
+ * default) or by reflection (pad_mode 1); n = 1 + (L + 2 (fl / 2) - fl) / hop exactly.  x dev [L] -> rms dev [n].  Every frame is summed
+ * in a fixed order; a workgroup squares its samples once, whatever the overlap of the frames. */
+int lds_frame_rms(const float* x, float* rms, int64_t L, int frame_length, int hop_length, int pad_mode, int64_t n, void* stream);
+/* Volume_Extractor.extract (reference tools/tools.py:23-33): x dev [L] -> volume dev [n], n = int(L // hop) + 1 exactly with Python's
+ * float floor division; volume[k] = sqrt(mean(x2p[int(k hop) : int((k + 1) hop)])), x2p = x^2 reflect-padded by
+ * (int(hop // 2), int((hop + 1) // 2)), the slice's end clipped to the padded length, the bounds computed in fp64 as Python does.
+ * hop_size: host pointer to the hop as a double (block_size * sr / model_sampling_rate: fractional when the rates differ), >= 1.
+ * L > int((hop + 1) // 2). */
+int lds_volume_extract(const float* x, float* volume, int64_t L, const double* hop_size, int64_t n, void* stream);
+/* get_mask_from_volume + upsample (reference tools/tools.py:35-41, 225-229): volume dev [n] -> mask dev [n * factor];
+ * m[k] = volume[k] > threshold, M[k] = max m[max(k - 4, 0) .. min(k + 4, n - 1)] (the reference's edge-replicated window of 9),
+ * mask[j] = M[i] (1 - f) + M[min(i + 1, n - 1)] f with i = j / factor, f = (j % factor) / factor. */
+int lds_volume_mask(const float* volume, float* mask, int64_t n, int factor, float threshold, void* stream);
+/* lds_resample_frames per clip (units_forced_alignment, reference tools/tools.py:193-223, on a ragged batch): in dev [B,Tin,C], host int32
+ * tin[B] (1 .. Tin) and tout[B] (0 .. Tout), B <= 64 -> out dev [B,Tout,C]: out[b,i,:] = in[b, min((int)floorf(i step_b), tin[b] - 1), :]
+ * for i < tout[b], zeros beyond; step_b = (float)tin[b] / (float)tout[b].  Rows of `in` at and beyond tin[b] are never read. */
+int lds_resample_frames_ragged(const float* in, const int32_t* tin, const int32_t* tout, float* out, int B, int Tin, int Tout, int C,
+                               void* stream);
+/* The mask product, the zero gaps and cross_fade of the reference's loop (tools/infer_tools.py:105-115, tools/tools.py:231-238) in one
+ * pass.  segs dev [segs_len]: the S segments packed; table int64 [3][S] = offset (into segs), start (in the result) and len of every
+ * segment, given twice: host_tab is validated, dev_tab (the same values on the device) is what the kernel reads.  mask dev [mask_len] or
+ * NULL; out dev [N], N = start[S-1] + len[S-1] exactly.  Defined by the sequential loop: R = the result so far,
+ * v_s = seg_s * mask[start_s : start_s + len_s]; start_s >= |R|: R is extended by zeros up to start_s, then by v_s; else with
+ * F = |R| - start_s and k_i = i / (F - 1) (0 when F = 1): R[start_s + i] = (1 - k_i) R[start_s + i] + k_i v_s[i] for i < F, and the rest
+ * of v_s is appended.  Preconditions (LDS_EINVAL naming the segment): start never decreases; F <= len_s;
+ * start_s >= start_{s-2} + len_{s-2}; offset_s + len_s <= segs_len; mask_len >= N.  At most two segments then meet at a sample, and every
+ * output sample evaluates the loop's closed form on its own. */
+int lds_overlap_assemble(const float* segs, int64_t segs_len, const int64_t* host_tab, const int64_t* dev_tab, int S, const float* mask,
+                         int64_t mask_len, float* out, int64_t N, void* stream);
+
 /* ---- per-launch HIP-event timing for bench.py's roofline leg (off by default) ------------------
  * lds_prof_enable(1) clears and starts recording one event pair per kernel launch on the launch
  * stream; lds_prof_summary synchronises them and writes a JSON list of

@@ -111,6 +111,11 @@ lds_kmeans_update                i:ppqpppiippzp
 lds_kmeans_seed                  i:pqiiqppppzp
 lds_resample                     i:ppppiiiiqqp
 lds_resample_ragged              i:ppppppiiiiqqp
+lds_frame_rms                    i:ppqiiiqp
+lds_volume_extract               i:ppqpqp
+lds_volume_mask                  i:ppqifp
+lds_resample_frames_ragged       i:ppppiiiip
+lds_overlap_assemble             i:pqppipqpqp
 lds_prof_enable                  i:i
 lds_prof_summary                 i:pz
 lds_unet_set_gemm_mode           i:pi
@@ -845,3 +850,96 @@ def resample(x, tables, lengths=None):
     new = np.zeros(B, dtype=np.int64)
     check(lib().lds_resample_ragged(_dev(x, torch.float32), _host(ln), _dev(y), _host(new), *tail))
     return y, torch.from_numpy(new)
+
+
+# ---- long-audio conversion (lds_frame_rms, lds_volume_*, lds_resample_frames_ragged, lds_overlap_assemble; csrc/svc.hip) ----
+def _wave_1d(x, what):
+    import torch
+    if not torch.is_tensor(x) or not x.is_cuda:
+        raise RuntimeError(f"{what} needs the audio as a tensor on a HIP device (no CPU fallback)")
+    if x.dim() != 1 or x.numel() < 1:
+        raise ValueError(f"{what}: a mono 1-D waveform with at least one sample is needed, got shape {list(x.shape)}")
+    return x.float().contiguous()
+
+
+def frame_rms_length(L, frame_length, hop_length):
+    return 1 + (int(L) + 2 * (frame_length // 2) - frame_length) // hop_length
+
+
+def frame_rms(x, frame_length, hop_length, pad_mode="constant"):
+    """x [L] on the device -> librosa.feature.rms(y=x, frame_length, hop_length) [n] on the device; pad_mode 'constant' (zeros) or 'reflect' """
+    import torch
+    if pad_mode not in ("constant", "reflect"):
+        raise ValueError(f"frame_rms: pad_mode {pad_mode!r} ('constant' or 'reflect')")
+    x = _wave_1d(x, "frame_rms")
+    n = frame_rms_length(x.numel(), frame_length, hop_length)
+    out = torch.empty(max(n, 0), dtype=torch.float32, device=x.device)
+    check(lib().lds_frame_rms(_dev(x, torch.float32), _dev(out), x.numel(), int(frame_length), int(hop_length), int(pad_mode == "reflect"), n, _stream()))
+    return out
+
+
+def volume_extract(x, hop):
+    """x [L] on the device -> Volume_Extractor.extract's volume [int(L // hop) + 1] on the device; hop: a float, possibly fractional"""
+    import torch
+    x = _wave_1d(x, "volume_extract")
+    hop = float(hop)
+    if not hop >= 1.0:
+        raise ValueError(f"volume_extract: hop {hop} must be at least 1")
+    n = int(x.numel() // hop) + 1
+    out = torch.empty(n, dtype=torch.float32, device=x.device)
+    h = C.c_double(hop)
+    check(lib().lds_volume_extract(_dev(x, torch.float32), _dev(out), x.numel(), C.addressof(h), n, _stream()))
+    return out
+
+
+def volume_mask(volume, factor, threshold):
+    """volume [n] on the device -> the dilated, linearly up-sampled mask [n * factor]; threshold: the linear amplitude, rounded to fp32"""
+    import torch
+    if not torch.is_tensor(volume) or not volume.is_cuda:
+        raise RuntimeError("volume_mask needs the volume as a tensor on a HIP device (no CPU fallback)")
+    v = volume.reshape(-1).float().contiguous()
+    out = torch.empty(v.numel() * int(factor), dtype=torch.float32, device=v.device)
+    check(lib().lds_volume_mask(_dev(v, torch.float32), _dev(out), v.numel(), int(factor), float(np.float32(threshold)), _stream()))
+    return out
+
+
+def resample_frames_ragged(x, tin, tout):
+    """x [B, Tin, C], every clip's own frame counts in (1 .. Tin) and out (host ints) -> [B, max(tout), C]: clip b's first tin[b] rows
+    aligned to tout[b] rows by 'nearest' as resample_frames does alone, zeros beyond"""
+    import torch
+    B, T, Cc = x.shape
+    ti = _host_lengths(tin, B, 1, T, max_B=64, what="frame alignment")
+    to = _host_lengths(tout, B, 0, 2 ** 31 - 1)
+    n_out = max(int(to.max()), 1)
+    out = torch.empty(B, n_out, Cc, dtype=torch.float32, device=x.device)
+    check(lib().lds_resample_frames_ragged(_dev(x, torch.float32), _host(ti), _host(to), _dev(out), B, T, n_out, Cc, _stream()))
+    return out
+
+
+def overlap_table(offset, start, length):
+    """the three per-segment arrays -> host int64 [3, S] (offset, start, len), as lds_overlap_assemble reads them"""
+    tab = np.ascontiguousarray(np.stack([np.asarray(a, dtype=np.int64).reshape(-1) for a in (offset, start, length)]))
+    if tab.shape[1] < 1:
+        raise ValueError("overlap_assemble: no segment")
+    return tab
+
+
+def overlap_assemble(segs, offset, start, length, mask=None):
+    """segs [n] on the device: the segments packed; offset / start / length: host ints per segment; mask [>= N] on the device or None ->
+    the joined waveform [N], N = start[-1] + length[-1] (include/lds.h lds_overlap_assemble).  The library checks the preconditions on the
+    host table before anything is enqueued; its LDS_EINVAL, which names the segment, is raised as ValueError.  The table is uploaded once."""
+    import torch
+    tab = overlap_table(offset, start, length)
+    S = tab.shape[1]
+    N = int(tab[1, -1] + tab[2, -1])
+    if not torch.is_tensor(segs) or not segs.is_cuda or (mask is not None and not mask.is_cuda):
+        raise RuntimeError("liblds needs tensors on a HIP device (no CPU fallback for the hot path)")
+    m = None if mask is None else mask.reshape(-1)
+    dtab = torch.from_numpy(tab).to(segs.device)
+    out = torch.empty(min(max(N, 0), 1 << 33), dtype=torch.float32, device=segs.device)      # (a table that gives another N is refused below)
+    rc = lib().lds_overlap_assemble(_dev(segs, torch.float32) if segs.numel() else None, segs.numel(), _host(tab), _dev(dtab, torch.int64), S,
+                                    _dev_or_null(m, torch.float32), 0 if m is None else m.numel(), _dev(out) if N > 0 else None, N, _stream())
+    if rc == -1:      # LDS_EINVAL: a precondition on the table, the mask or the buffer
+        raise ValueError(lib().lds_last_error().decode())
+    check(rc)
+    return out

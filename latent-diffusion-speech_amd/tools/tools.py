@@ -1,7 +1,7 @@
-"""The pieces of reference tools/tools.py that are built: the encoder-width table, `units_forced_alignment`, the Whisper
-units encoder (`Units_Encoder` / `WhisperLargeV3`, reference tools/tools.py:43-126) and `Resample`, the torchaudio transform that
-file imports (tools/tools.py:9).  The two other speech encoders, the volume extractor and the schedulers there are not built
-(SURVEY.md section 2)."""
+"""The pieces of reference tools/tools.py that are built: the encoder-width table, `units_forced_alignment` (and its per-clip form
+`units_forced_alignment_ragged`), the Whisper units encoder (`Units_Encoder` / `WhisperLargeV3`, reference tools/tools.py:43-126),
+`Volume_Extractor`, `upsample` and `cross_fade` (tools/tools.py:12-41, 225-238) and `Resample`, the torchaudio transform that file imports
+(tools/tools.py:9).  The two other speech encoders and the schedulers there are not built."""
 import math
 
 import numpy as np
@@ -45,6 +45,68 @@ def units_forced_alignment(units, audio=None, sample_rate=None, hop_size=None, n
     else:
         raise NotImplementedError(f"units_forced_mode {units_forced_mode!r} is not used on the TTS path")
     return out.squeeze(0) if squeeze else out
+
+
+def units_forced_alignment_ragged(units, unit_lengths, n_frames):
+    """Extension (not in the reference): units_forced_alignment(units[b, :unit_lengths[b]], n_frames=n_frames[b]) in 'nearest' mode for
+    every clip of a padded batch [B, T, C] at once (host ints, at most 64 clips) -> [B, max(n_frames), C], each clip bit for bit as if
+    aligned alone, zeros beyond its n_frames[b]; rows at and beyond unit_lengths[b] are never read (lds_resample_frames_ragged)"""
+    if isinstance(units, np.ndarray) or not units.is_cuda:
+        raise RuntimeError("units_forced_alignment_ragged needs the units on a HIP device (no CPU fallback for the hot path)")
+    return native.resample_frames_ragged(units.contiguous().float(), unit_lengths, n_frames)
+
+
+def _device_wave(name, audio, device="cuda"):
+    """numpy is moved to the device; a tensor must be there already"""
+    if isinstance(audio, np.ndarray):
+        audio = torch.from_numpy(np.ascontiguousarray(audio, dtype=np.float32)).to(device)
+    if not torch.is_tensor(audio) or not audio.is_cuda:
+        raise RuntimeError(f"{name} needs a numpy array or a tensor on a HIP device (no CPU fallback)")
+    return audio
+
+
+class Volume_Extractor:
+    """reference tools/tools.py:12-41.  `extract` returns the volume fp32 [n] on the device (the reference: float64 numpy), computed by
+    lds_volume_extract; `get_mask_from_volume` thresholds, dilates and up-samples it in one kernel (lds_volume_mask)."""
+
+    def __init__(self, hop_size=512, block_size=None, model_sampling_rate=None):
+        """hop_size alone: frames of that many samples.  block_size together with model_sampling_rate: the hop follows the rate of the
+        audio that `extract` is given, block_size * sr / model_sampling_rate (one without the other is an AssertionError)"""
+        given = [v is not None for v in (block_size, model_sampling_rate)]
+        assert all(given) or not any(given)
+        self.hop_size, self.block_size, self.model_sampling_rate = hop_size, block_size, model_sampling_rate
+        self.hop_size_follow_input = all(given)
+
+    def extract(self, audio, sr=None, device="cuda"):
+        """`device` (not in the reference): where a numpy `audio` is moved to"""
+        if sr is not None:
+            assert self.hop_size_follow_input
+            self.hop_size = self.block_size * sr / self.model_sampling_rate
+        return native.volume_extract(_device_wave("Volume_Extractor.extract", audio, device), self.hop_size)
+
+    def get_mask_from_volume(self, volume, threhold=-60.0, device='cpu'):
+        """volume [n] -> mask [1, n * block_size] on the device the volume lives on (`device` is the reference's parameter: the mask of a
+        device volume cannot be anywhere else; a numpy volume goes to `device`, which must be a HIP device)"""
+        volume = _device_wave("Volume_Extractor.get_mask_from_volume", volume, device)
+        return native.volume_mask(volume, self.block_size, 10 ** (float(threhold) / 20)).unsqueeze(0)
+
+
+def upsample(signal, factor):
+    """reference tools/tools.py:225-229: signal [B, n, C] -> [B, n * factor, C], linear interpolation with the last frame repeated:
+    out[j] = s[i] (1 - f) + s[min(i + 1, n - 1)] f, i = j // factor, f = (j % factor) / factor.  The long-audio path does not come here
+    (lds_volume_mask holds the same formula); this is the reference's helper for other callers, a gather and a lerp on the signal's device."""
+    n = signal.shape[1]
+    j = torch.arange(n * factor, device=signal.device)
+    i = j // factor
+    f = ((j % factor).float() / factor)[None, :, None]
+    return signal[:, i] * (1 - f) + signal[:, torch.clamp(i + 1, max=n - 1)] * f
+
+
+def cross_fade(a, b, idx):
+    """reference tools/tools.py:231-238: `a` up to idx, a linear fade from a to b over a's remaining len(a) - idx samples, then the rest of
+    b -> [idx + len(b)] on the device = lds_overlap_assemble with two segments and no mask (0 <= len(a) - idx <= len(b))"""
+    a, b = _device_wave("cross_fade", a).reshape(-1).float(), _device_wave("cross_fade", b).reshape(-1).float()
+    return native.overlap_assemble(torch.cat([a, b]), [0, a.numel()], [0, int(idx)], [a.numel(), b.numel()])
 
 
 class Resample(torch.nn.Module):
@@ -151,18 +213,28 @@ class Units_Encoder:
             units = units.squeeze(0)
         return units
 
-    def encode_ragged(self, audio, lengths, sample_rate=None):
+    def encode_ragged(self, audio, lengths, sample_rate=None, *, pad_short=False):
         """Extension (not in the reference): audio [B, L] padded to the longest clip + every clip's own sample count (host ints, at most 64
         clips) -> (units [B, Tmax, C], n_frames [B] int64 on the host): every clip encoded as if alone, rows beyond its own
         n_frames[b] = (lengths[b] // 160 - 1) // 2 + 1 are zeros.  400 <= lengths[b] <= L (ValueError otherwise: pad a shorter clip with
         zeros to 400 samples first, as encode does).  With resample=True and another `sample_rate`, audio and lengths are at that rate:
         the batch is resampled by Resample.forward_ragged first, and the limits apply to the resampled lengths (a batch whose longest
-        resampled clip is below 400 samples is zero-padded to 400 columns)."""
+        resampled clip is below 400 samples is zero-padded to 400 columns).  pad_short=True does encode's padding here: a clip that has
+        fewer than 400 samples at the encoder's rate (after resampling, if any) is continued with zeros to 400, whatever the buffer held
+        there."""
         rs = self._check("Units_Encoder.encode_ragged", audio, self.encoder_sample_rate if sample_rate is None else sample_rate)
         if rs is not None:
             audio, lengths = rs.forward_ragged(audio, lengths)
-            if audio.size(-1) < 400:
-                audio = torch.nn.functional.pad(audio, (0, 400 - audio.size(-1)))
+        if (rs is not None or pad_short) and audio.size(-1) < 400:
+            audio = torch.nn.functional.pad(audio, (0, 400 - audio.size(-1)))
+        if pad_short:
+            ln = native._host_lengths(lengths, audio.shape[0], 0, audio.shape[1], max_B=64, what="units")
+            if (ln < 400).any():
+                if rs is None:      # (the resampler has written zeros beyond every clip already)
+                    audio = audio.clone()
+                    for b in np.nonzero(ln < 400)[0]:
+                        audio[b, int(ln[b]):400] = 0
+                lengths = np.maximum(ln, 400)
         return self.model.encode_ragged(audio, lengths)
 
     def encode_tokens(self, audio, sample_rate, codebook):
