@@ -219,6 +219,41 @@ int  lds_whisper_encode_mel(lds_whisper* w, const float* mel, const int32_t* n_f
 int  lds_whisper_encode(lds_whisper* w, const float* audio, const int32_t* lengths, float* units, void* ws, size_t ws_bytes, int B, int64_t L,
                         void* stream);
 
+/* ---- units encoder: HuBERT-base / HuBERT-Soft / ContentVec, audio -> units (reference encoder/hubert/model.py:19-148: Hubert.encode,
+ *      HubertSoft.units) -------------------------------------------------------------------------------------------------------------------
+ * A 7-layer waveform convolution stack (conv0 k 10 stride 5 + GroupNorm per channel; conv1..4 k 3, conv5..6 k 2, all stride 2, no bias, no
+ * padding, GELU), LayerNorm + Linear (conv_dim -> n_state), a grouped positional convolution (pos_kernel taps, pos_groups groups, weight norm
+ * folded at create in double) added to its input and normalised, n_layer post-LayerNorm blocks (nn.TransformerEncoderLayer, GELU,
+ * norm_first False, eps 1e-5) and proj (n_state -> n_proj).  names: the reference Hubert.state_dict() keys ("feature_extractor.conv0.weight",
+ * "positional_embedding.conv.parametrizations.weight.original0" = g [1][1][K], "...original1" = v, "encoder.layers.N.self_attn.in_proj_weight",
+ * ..., "proj.bias"; masked_spec_embed and label_embedding.weight are not read), fp32 host arrays in the reference's layouts.
+ * HuBERT-base: {512, 768, 12, 12, 3072, 256, 128, 16, 1500}.  Limits (LDS_EINVAL): conv_dim and n_state multiples of 64 up to 1024,
+ * n_state / n_head == 64, n_ffn and n_proj multiples of 64, n_state / pos_groups in {16, 32, 48, 64}, pos_kernel even in 2 .. 128,
+ * 1 <= n_layer <= 64, 1 <= n_ctx <= 1500 (the range the attention kernel is tested in).
+ *
+ * A call takes B clips in audio dev [B][L] (16 kHz samples).  `pad` zeros are added on each side of every clip: 40 is HubertSoft.units
+ * (F.pad(wav, (40, 40)), T = L / 320 frames), 0 is Hubert.encode on a waveform as given; 0 <= pad <= 40, L + 2 pad >= 400.  The frame counts:
+ * n0 = (L + 2 pad - 10) / 5 + 1, four times n <- (n - 3) / 2 + 1, twice n <- (n - 2) / 2 + 1 = T <= n_ctx.  lengths host int32 [B] (B <= 64),
+ * 400 - 2 pad <= lengths[b] <= L, or NULL (every clip has L samples).  Clip b is audio[b, :lengths[b]] ENCODED ALONE: its own zero pad, its
+ * own GroupNorm statistics over its own n0 frames, its own zero padding in the positional convolution, attention keys that stop at its T_b.
+ * Nothing at or beyond lengths[b] is read; rows at and beyond T_b of a result are zeros.  A clip's result does not depend on the other clips
+ * of the call.  Exact fp32, no floating-point atomics: a repeat gives the same bits.  Nothing synchronises; a bad argument returns before
+ * anything is enqueued; a small workspace gives LDS_ENOMEM. */
+typedef struct lds_hubert lds_hubert;
+typedef struct lds_hubert_cfg { int conv_dim, n_state, n_head, n_layer, n_ffn, n_proj, pos_kernel, pos_groups, n_ctx; } lds_hubert_cfg;
+int  lds_hubert_create(const lds_hubert_cfg* cfg, int n_tensors, const char* const* names, const float* const* host_ptrs, const int64_t* numel,
+                       lds_hubert** out);
+void lds_hubert_destroy(lds_hubert* h);
+/* one size for both calls below */
+int  lds_hubert_workspace_bytes(const lds_hubert* h, int B, int64_t L, int pad, size_t* out);
+/* out dev [B][T][conv_dim] frame-major = the feature extractor's output (FeatureExtractor.forward, transposed) */
+int  lds_hubert_features(lds_hubert* h, const float* audio, const int32_t* lengths, float* out, void* ws, size_t ws_bytes, int B, int64_t L, int pad,
+                         void* stream);
+/* Hubert.encode(., layer = n_layers_run)[0] -> out dev [B][T][n_state]; 0 <= n_layers_run <= n_layer (0 = the output of `norm`).  want_proj
+ * (only with n_layers_run == n_layer): proj applied, out dev [B][T][n_proj] (HubertSoft.units with pad 40). */
+int  lds_hubert_encode(lds_hubert* h, const float* audio, const int32_t* lengths, float* out, int n_layers_run, int want_proj, void* ws,
+                       size_t ws_bytes, int B, int64_t L, int pad, void* stream);
+
 /* ---- text2semantic: RoFormer encoder prefill + cached autoregressive decode (reference text2semantic/roformer/roformer.py:59-255
  *      over HF transformers RoFormerModel / RoFormerForCausalLM + GenerationMixin; called from 22_infer_tts.py:76-98) ------------- */
 typedef struct lds_lm lds_lm;

@@ -24,6 +24,8 @@ def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("-dm", "--diffusion_model")
     ap.add_argument("-ue", "--units_encoder", help="large-v3_encoder.pt: {'dims', 'model_state_dict'} of the Whisper encoder")
+    ap.add_argument("--encoder", default="whisper_large_v3", choices=("whisper_large_v3", "hubertsoft", "contentvec768l12"),
+                    help="the units encoder; for a HuBERT encoder -ue names a HubertSoft state dict")
     ap.add_argument("-i", "--input", help="mono PCM16 .wav, or .npy float [L] (then --sample_rate says its rate)")
     ap.add_argument("-sr", "--sample_rate", type=int, default=44100, help="rate of a .npy input / of the generated recording")
     ap.add_argument("-o", "--output", default="output.wav", help=".wav (PCM16) or .npy")
@@ -42,26 +44,33 @@ def parse_args(argv=None):
     return ap.parse_args(argv)
 
 
-def synthetic_svc(dev, width=1280, layers=4):
+def synthetic_svc(dev, width=1280, layers=4, encoder="whisper_large_v3"):
     """DiffusionSVC with seeded random-init weights throughout (no checkpoints ship with the reference): the Unit2Mel and
-    vocoder of infer_tts.synthetic_pipeline, a Whisper encoder of `width` (large-v3's mel front end and context) with resampling on"""
+    vocoder of infer_tts.synthetic_pipeline, a Whisper encoder of `width` (large-v3's mel front end and context) with resampling on; or,
+    for encoder 'hubertsoft' / 'contentvec768l12', the HuBERT-base stack of `layers` blocks (its own width: 256 / 768)"""
     from diffusion.unit2mel import DotDict, Unit2Mel
     from diffusion.vocoder import Vocoder
     from encoder.hifi_vaegan.hifi_vaegan import Hifi_VAEGAN
     from encoder.whisper.model import ModelDimensions
     from lds import arch, init_weights
     from tools.infer_tools import DiffusionSVC
-    from tools.tools import Units_Encoder, Volume_Extractor, WhisperLargeV3
+    from tools.tools import HubertUnits, Units_Encoder, Volume_Extractor, WhisperLargeV3
     h = arch.SYNTHETIC_VOCODER_H
+    if encoder in HubertUnits.NAMES:
+        width = arch.get_encoder_out_channels(encoder)
     voc = Vocoder.__new__(Vocoder)
     voc.vocoder = Hifi_VAEGAN(None, device=dev, h=h, state=init_weights.init_state(arch.generator_param_shapes(h), 0))
     voc.vocoder_hop_size, voc.vocoder_sample_rate, voc.dimension, voc.device = h["hop_size"], h["sampling_rate"], h["inter_channels"], dev
     svc = DiffusionSVC(device=dev)
     svc.model, svc.vocoder = Unit2Mel(width, 323, h["inter_channels"]).to(dev).eval(), voc
-    svc.args = DotDict({"data": {"block_size": h["hop_size"], "sampling_rate": h["sampling_rate"], "encoder": "whisper_large_v3",
+    svc.args = DotDict({"data": {"block_size": h["hop_size"], "sampling_rate": h["sampling_rate"], "encoder": encoder,
                                  "encoder_sample_rate": 16000, "encoder_hop_size": 320}})
-    dims = ModelDimensions(**dict(arch.WHISPER_LARGE_V3_DIMS, n_audio_state=width, n_audio_head=width // 64, n_audio_layer=layers))
-    svc.units_encoder = Units_Encoder("whisper_large_v3", 16000, 320, device=dev, model=WhisperLargeV3.synthetic(dims, seed=0, device=dev), resample=True)
+    if encoder in HubertUnits.NAMES:
+        model = HubertUnits.synthetic(encoder, dict(arch.HUBERT_BASE_DIMS, n_layer=layers), seed=0, device=dev)
+    else:
+        dims = ModelDimensions(**dict(arch.WHISPER_LARGE_V3_DIMS, n_audio_state=width, n_audio_head=width // 64, n_audio_layer=layers))
+        model = WhisperLargeV3.synthetic(dims, seed=0, device=dev)
+    svc.units_encoder = Units_Encoder(encoder, 16000, 320, device=dev, model=model, resample=True)
     svc.volume_extractor = Volume_Extractor(hop_size=512, block_size=h["hop_size"], model_sampling_rate=h["sampling_rate"])
     return svc
 
@@ -98,13 +107,14 @@ def main(argv=None):
     a = parse_args(argv)
     dev = "cuda"
     if a.synthetic:
-        svc = synthetic_svc(dev, a.synthetic_width, a.synthetic_layers)
+        svc = synthetic_svc(dev, a.synthetic_width, a.synthetic_layers, a.encoder)
     else:
         if not a.diffusion_model or not a.units_encoder:
             raise SystemExit("-dm and -ue are needed (or --synthetic)")
         from tools.infer_tools import DiffusionSVC
         svc = DiffusionSVC(device=dev)
-        svc.load_model(a.diffusion_model, units_encoder_checkpoint=a.units_encoder, resample=True)
+        svc.load_model(a.diffusion_model, units_encoder_checkpoint=a.units_encoder, resample=True,
+                       encoder=None if a.encoder == "whisper_large_v3" else a.encoder)
     if a.input:
         audio, sr = read_audio(a.input, a.sample_rate)
     elif a.synthetic:

@@ -1062,7 +1062,7 @@ hipError_t launch_conv_dma(const DmaConvArgs& a_, int cfg, hipStream_t s) {
         return hipErrorInvalidValue;
     }
     if (a.dil != 1 || a.act_slope != 0.f || a.acc_in || a.out_div != 1.0f || a.ph_Tout) return hipErrorInvalidValue;      // vocoder-only features
-    if (a.KT != 1 && a.KT != 3) return hipErrorInvalidValue;
+    if (a.KT != 1 && a.KT != 3 && !(a.KT == 2 && a.stride == 2 && a.epi == EPI_GELU)) return hipErrorInvalidValue;      // (k 2: HuBERT's conv5 / conv6)
     const bool k32 = (a.Ci % 32 == 0) && (a.C1 % 32 == 0), k64 = (a.Ci % 64 == 0) && (a.C1 % 64 == 0);
     int bm, bn, bk, nst;
     dma_pick(a, cfg, bm, bn, bk, nst);
@@ -1102,6 +1102,9 @@ hipError_t launch_conv_dma(const DmaConvArgs& a_, int cfg, hipStream_t s) {
         } else if (a.KT == 3 && a.stride == 2) {
             if (k32) ECASE(64, 64, 3, 2, 32, 2);
             ECASE(64, 64, 3, 2, 16, 2);
+        } else if (a.KT == 2 && a.stride == 2) {      // the HuBERT feature extractor's last two convolutions
+            if (k32) ECASE(64, 64, 2, 2, 32, 2);
+            ECASE(64, 64, 2, 2, 16, 2);
         }
 #undef ECASE
         return hipErrorInvalidValue;

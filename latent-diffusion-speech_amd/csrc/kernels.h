@@ -245,6 +245,21 @@ hipError_t launch_whisper_ln_post(const float* x, const float2* lnpart, const fl
                                   int B, int C, int T, hipStream_t s);
 
 // ---------------------------------------------------------------------------------------------
+// HuBERT units encoder: the kernels of its own (hubert.hip); nlen / slen are device int32 [B] or null (= the buffer's length)
+// ---------------------------------------------------------------------------------------------
+// audio [B][L] -> out K4P [B][C][N0] = GELU(GroupNorm(C, C)(conv0(clip padded by `pad` zeros per side))), N0 = (L + 2 pad - 10) / 5 + 1;
+// clip b = audio[b, :slen[b]] with its own nlen[b] frames and its own statistics; w0 [C][10]; scratch part [B][ceil(N0 / 256)][C], stat [B][C]
+hipError_t launch_hubert_conv0(const float* audio, const int* slen, long long L, int pad, const float* w0, const float* gamma, const float* beta, float eps,
+                               const int* nlen, int N0, int C, float2* part, float2* stat, float* out, int B, hipStream_t s);
+// out (K4P) = x + GELU(grouped conv of x, k = K taps, padding K / 2, last frame dropped); wp packed [group][k][ci / 4][row tile][64]
+hipError_t launch_hubert_posconv(const float* x, const float* wp, const float* bias, float* out, const int* nlen, int B, int C, int T, int K, int groups,
+                                 hipStream_t s);
+// out (K4P) = LayerNorm over the channels of x (K4P), zeros beyond a clip's frames
+hipError_t launch_hubert_ln(const float* x, const float* gamma, const float* beta, float eps, float* out, const int* nlen, int B, int C, int T, hipStream_t s);
+// x (K4P [B][C][T]) -> out [B][T][C] frame-major, zero rows beyond a clip's frames
+hipError_t launch_hubert_store_frames(const float* x, float* out, const int* nlen, int B, int C, int T, hipStream_t s);
+
+// ---------------------------------------------------------------------------------------------
 // Small dense layers with N = batch columns (time embedding path)
 // out[b][m] = sum_k W[m][k] * g(in[b][k]) + bias[m];  g = identity | SiLU | sinusoid(t[b])
 // ---------------------------------------------------------------------------------------------

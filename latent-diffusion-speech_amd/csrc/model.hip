@@ -2580,6 +2580,295 @@ extern "C" int lds_whisper_encode_mel(lds_whisper* h, const float* mel, const in
 }
 
 // ================================================================================================
+// HuBERT units encoder (reference encoder/hubert/model.py:19-148: Hubert.encode / HubertSoft.units): a 7-layer waveform convolution
+// stack, a LayerNorm + Linear projection, a grouped positional convolution and post-LayerNorm transformer blocks.  K4P throughout like the
+// Whisper encoder above and built from the same launches; its own kernels are in hubert.hip.  Post-LN: a block's LayerNorm output is the
+// next residual, so it is materialised (launch_hubert_ln) and the GEMMs read it with plain weights.  Seven launches per block.
+// The frame counts do not follow ragged_len's halving rule (k 3 / k 2 convolutions without padding), so every level's per-clip counts
+// are computed on the host and the launches of a level run with that level's array as their `lens` at level 0.
+// ================================================================================================
+struct HubertBlockW {
+    ConvW qkv, out, fc1, fc2;
+    float *n1_g = nullptr, *n1_b = nullptr, *n2_g = nullptr, *n2_b = nullptr;
+};
+struct lds_hubert {
+    lds_hubert_cfg cfg;
+    Owner own;
+    float *w0 = nullptr, *gn_g = nullptr, *gn_b = nullptr;      // conv0 [conv_dim][10], norm0
+    ConvW conv[6];                                                // conv1 .. conv6
+    ConvW fproj;                                                  // feature_projection: LayerNorm folded into the Linear
+    float *fproj_c1 = nullptr, *fproj_c2 = nullptr;
+    float *pos_w = nullptr, *pos_b = nullptr;                     // weight norm folded, packed for hubert_posconv
+    float *norm_g = nullptr, *norm_b = nullptr;
+    std::vector<HubertBlockW> blocks;
+    ConvW proj;
+};
+
+constexpr int kHubertLevels = 7;      // conv0 .. conv6
+// frames after every layer of the feature extractor for a clip of n samples padded by `pad` zeros per side (model.py:99-106)
+static void hubert_levels(int64_t n, int pad, int32_t* lv) {
+    int64_t f = (n + 2 * pad - 10) / 5 + 1;
+    lv[0] = (int32_t)f;
+    for (int i = 1; i < kHubertLevels; ++i) {
+        f = (i <= 4) ? (f - 3) / 2 + 1 : (f - 2) / 2 + 1;
+        lv[i] = (int32_t)f;
+    }
+}
+
+static int hubert_cfg_check(const lds_hubert_cfg* c) {
+    if (!c) return fail(LDS_EINVAL, "null argument");
+    if (c->conv_dim < 64 || c->conv_dim % 64 || c->conv_dim > 1024) return fail(LDS_EINVAL, "hubert: conv_dim %d must be a multiple of 64 in 64 .. 1024", c->conv_dim);
+    if (c->n_state < 64 || c->n_state % 64 || c->n_state > 1024) return fail(LDS_EINVAL, "hubert: n_state %d must be a multiple of 64 in 64 .. 1024", c->n_state);
+    if (c->n_head < 1 || c->n_state != c->n_head * 64) return fail(LDS_EINVAL, "hubert: n_state / n_head must be 64 (got %d / %d)", c->n_state, c->n_head);
+    if (c->n_layer < 1 || c->n_layer > 64) return fail(LDS_EINVAL, "hubert: n_layer %d outside 1 .. 64", c->n_layer);
+    if (c->n_ffn < 64 || c->n_ffn % 64) return fail(LDS_EINVAL, "hubert: n_ffn %d must be a positive multiple of 64", c->n_ffn);
+    if (c->n_proj < 64 || c->n_proj % 64) return fail(LDS_EINVAL, "hubert: n_proj %d must be a positive multiple of 64", c->n_proj);
+    if (c->pos_kernel < 2 || c->pos_kernel > 128 || (c->pos_kernel & 1)) return fail(LDS_EINVAL, "hubert: pos_kernel %d must be even in 2 .. 128", c->pos_kernel);
+    if (c->pos_groups < 1 || c->n_state % c->pos_groups || (c->n_state / c->pos_groups) % 16 || c->n_state / c->pos_groups > 64)
+        return fail(LDS_EINVAL, "hubert: n_state / pos_groups must be 16, 32, 48 or 64 (got %d / %d)", c->n_state, c->pos_groups);
+    if (c->n_ctx < 1 || c->n_ctx > 1500) return fail(LDS_EINVAL, "hubert: n_ctx %d outside 1 .. 1500", c->n_ctx);
+    return LDS_OK;
+}
+
+// weight norm of the positional convolution folded in double (parametrizations.weight_norm(dim=2): one norm per tap, over the other two
+// axes): w[:, :, k] = g[k] v[:, :, k] / |v[:, :, k]|; then the A-operand order of hubert_posconv: [group][k][ci / 4][row tile][lane]
+static float* pack_posconv(Owner& o, const float* g, const float* v, int C, int groups, int K) {
+    const int gw = C / groups, MT = gw / 16;
+    std::vector<double> sc(K);
+    for (int k = 0; k < K; ++k) {
+        double s = 0;
+        for (int64_t i = 0; i < (int64_t)C * gw; ++i) s += (double)v[i * K + k] * (double)v[i * K + k];
+        sc[k] = (double)g[k] / sqrt(s);
+    }
+    std::vector<float> p((size_t)C * gw * K);
+    for (int gi = 0; gi < groups; ++gi)
+        for (int k = 0; k < K; ++k)
+            for (int c4 = 0; c4 < gw / 4; ++c4)
+                for (int m = 0; m < MT; ++m)
+                    for (int l = 0; l < 64; ++l) {
+                        const int co = gi * gw + m * 16 + (l & 15), ci = c4 * 4 + (l >> 4);
+                        p[((((size_t)gi * K + k) * (gw / 4) + c4) * MT + m) * 64 + l] = (float)((double)v[((size_t)co * gw + ci) * K + k] * sc[k]);
+                    }
+    return o.upload(p);
+}
+
+extern "C" int lds_hubert_create(const lds_hubert_cfg* cfg, int n, const char* const* names, const float* const* ptrs, const int64_t* numel, lds_hubert** out) {
+    if (!cfg || !names || !ptrs || !numel || !out || n < 0) return fail(LDS_EINVAL, "null argument");
+    LDS_TRY(hubert_cfg_check(cfg));
+    const int D = cfg->conv_dim, C = cfg->n_state, F = cfg->n_ffn, K = cfg->pos_kernel, gw = C / cfg->pos_groups;
+    Tensors T;
+    for (int i = 0; i < n; ++i) T.m[names[i]] = {ptrs[i], numel[i]};
+    lds_hubert* h = new lds_hubert();
+    h->cfg = *cfg;
+    Owner& o = h->own;
+    auto vec = [&](const std::string& k, int64_t cnt) -> float* {
+        const float* p = T.get(k, cnt);
+        return p ? o.upload(std::vector<float>(p, p + cnt)) : nullptr;
+    };
+    h->w0 = vec("feature_extractor.conv0.weight", (int64_t)D * 10);
+    h->gn_g = vec("feature_extractor.norm0.weight", D);
+    h->gn_b = vec("feature_extractor.norm0.bias", D);
+    bool ok = h->w0 && h->gn_g && h->gn_b;
+    for (int i = 1; i <= 6 && ok; ++i) {
+        const int k = i <= 4 ? 3 : 2;
+        const float* w = T.get("feature_extractor.conv" + std::to_string(i) + ".weight", (int64_t)D * D * k);
+        ok = w && pack_conv(o, w, nullptr, D, D, k, h->conv[i - 1]);
+    }
+    if (ok) {
+        const float *g = T.get("feature_projection.norm.weight", D), *b = T.get("feature_projection.norm.bias", D);
+        const float *w = T.get("feature_projection.projection.weight", (int64_t)C * D), *wb = T.get("feature_projection.projection.bias", C);
+        ok = g && b && w && wb && pack_ln_fold(o, w, wb, g, b, C, D, {}, h->fproj, h->fproj_c1, h->fproj_c2);
+    }
+    if (ok) {
+        const float* g = T.get("positional_embedding.conv.parametrizations.weight.original0", K);
+        const float* v = T.get("positional_embedding.conv.parametrizations.weight.original1", (int64_t)C * gw * K);
+        h->pos_b = vec("positional_embedding.conv.bias", C);
+        if (g && v) h->pos_w = pack_posconv(o, g, v, C, cfg->pos_groups, K);
+        h->norm_g = vec("norm.weight", C);
+        h->norm_b = vec("norm.bias", C);
+        ok = h->pos_w && h->pos_b && h->norm_g && h->norm_b;
+    }
+    h->blocks.resize(cfg->n_layer);
+    for (int l = 0; l < cfg->n_layer && ok; ++l) {
+        const std::string p = "encoder.layers." + std::to_string(l) + ".";
+        HubertBlockW& bw = h->blocks[l];
+        const int64_t CC = (int64_t)C * C;
+        const float *iw = T.get(p + "self_attn.in_proj_weight", 3 * CC), *ib = T.get(p + "self_attn.in_proj_bias", 3 * C);
+        const float *ow = T.get(p + "self_attn.out_proj.weight", CC), *ob = T.get(p + "self_attn.out_proj.bias", C);
+        const float *f1 = T.get(p + "linear1.weight", (int64_t)F * C), *f1b = T.get(p + "linear1.bias", F);
+        const float *f2 = T.get(p + "linear2.weight", (int64_t)F * C), *f2b = T.get(p + "linear2.bias", C);
+        if (!iw || !ib || !ow || !ob || !f1 || !f1b || !f2 || !f2b) { ok = false; break; }
+        bw.n1_g = vec(p + "norm1.weight", C); bw.n1_b = vec(p + "norm1.bias", C);
+        bw.n2_g = vec(p + "norm2.weight", C); bw.n2_b = vec(p + "norm2.bias", C);
+        ok = bw.n1_g && bw.n1_b && bw.n2_g && bw.n2_b && pack_conv(o, iw, ib, 3 * C, C, 1, bw.qkv) && pack_conv(o, ow, ob, C, C, 1, bw.out) &&
+             pack_conv(o, f1, f1b, F, C, 1, bw.fc1) && pack_conv(o, f2, f2b, C, F, 1, bw.fc2);
+    }
+    if (ok) {
+        const float *w = T.get("proj.weight", (int64_t)cfg->n_proj * C), *b = T.get("proj.bias", cfg->n_proj);
+        ok = w && b && pack_conv(o, w, b, cfg->n_proj, C, 1, h->proj);
+    }
+    if (!ok) {
+        std::string miss = T.missing;
+        delete h;
+        if (!miss.empty()) return fail(LDS_EMISSING, "hubert: %s", miss.c_str());
+        return fail(LDS_ENOMEM, "hubert weight upload failed");
+    }
+    *out = h;
+    return LDS_OK;
+}
+extern "C" void lds_hubert_destroy(lds_hubert* h) { delete h; }
+
+struct HubertWs {
+    int* slen;
+    int* nlen[kHubertLevels];      // device copies of the clips' sample counts and of their frame counts after conv0 .. conv6
+    float2 *part, *stat;           // norm0's statistics
+    float *ca, *cb;                // the feature extractor's ping-pong (conv0's output is the largest tensor of the call)
+    float2* lnp;                   // conv6's LayerNorm partials for the folded feature projection
+    float *xa, *xb, *qk, *v, *att, *big, *pj;
+};
+static void plan_hubert(const lds_hubert* h, Arena& A, int B, const int32_t* nb, HubertWs& w) {
+    const size_t D = h->cfg.conv_dim, C = h->cfg.n_state, F = h->cfg.n_ffn, P = h->cfg.n_proj, T = nb[6], Bz = B;
+    w.slen = (int*)A.f(64);
+    for (int i = 0; i < kHubertLevels; ++i) w.nlen[i] = (int*)A.f(64);
+    w.part = (float2*)A.f(Bz * (((size_t)nb[0] + 255) / 256) * D * 2);
+    w.stat = (float2*)A.f(Bz * D * 2);
+    w.ca = A.f(Bz * D * ((size_t)nb[0] + 2));
+    w.cb = A.f(Bz * D * ((size_t)nb[1] + 2));
+    w.lnp = (float2*)A.f(Bz * (D / 32) * T * 2);
+    w.xa = A.f(Bz * C * (T + 2)); w.xb = A.f(Bz * C * (T + 2));
+    w.qk = A.f(Bz * 2 * C * (T + 2));
+    w.v = A.f(Bz * (C * ((T + 3) & ~(size_t)3) + 2048));
+    w.att = A.f(Bz * C * (T + 2));
+    w.big = A.f(Bz * F * (T + 2));
+    w.pj = A.f(Bz * P * (T + 2));
+    A.f(16384);      // tail slack: ragged last tiles read (masked) entries past a tensor's end
+}
+// the limits of one call: B clips in buffers of L samples, `pad` zeros added on each side of every clip; nb = the buffers' frame counts
+static int hubert_shape_check(const lds_hubert* h, int B, int64_t L, int pad, int32_t* nb) {
+    if (!h) return fail(LDS_EINVAL, "null handle");
+    if (B < 1 || B > 65535) return fail(LDS_EINVAL, "hubert: B %d outside 1 .. 65535", B);
+    if (pad < 0 || pad > 40) return fail(LDS_EINVAL, "hubert: pad %d outside 0 .. 40", pad);
+    if (L + 2 * pad < 400 || L > ((int64_t)1 << 30)) return fail(LDS_EINVAL, "hubert: L %lld outside %d .. 2^30 samples", (long long)L, 400 - 2 * pad);
+    hubert_levels(L, pad, nb);
+    if (nb[6] > h->cfg.n_ctx) return fail(LDS_EINVAL, "hubert: %d frames exceed n_ctx %d", nb[6], h->cfg.n_ctx);
+    return LDS_OK;
+}
+extern "C" int lds_hubert_workspace_bytes(const lds_hubert* h, int B, int64_t L, int pad, size_t* out) {
+    if (!out) return fail(LDS_EINVAL, "null argument");
+    int32_t nb[kHubertLevels];
+    LDS_TRY(hubert_shape_check(h, B, L, pad, nb));
+    Arena A(nullptr, 0);
+    HubertWs w;
+    plan_hubert(h, A, B, nb, w);
+    *out = A.used;
+    return LDS_OK;
+}
+
+// audio -> feat ([B][T][conv_dim]) and / or enc ([B][T][n_state], or [B][T][n_proj] with want_proj).  Every argument has been checked.
+static int hubert_run(lds_hubert* h, const float* audio, int64_t L, int pad, const int32_t* lens_host, const int32_t* nb, float* feat, float* enc,
+                      int n_layers_run, int want_proj, void* ws, size_t ws_bytes, int B, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    ProfChain chain;
+    Arena A(ws, ws_bytes);
+    HubertWs w;
+    plan_hubert(h, A, B, nb, w);
+    if (!A.ok) return fail(LDS_ENOMEM, "hubert workspace too small: need %zu", A.used);
+    const int D = h->cfg.conv_dim, C = h->cfg.n_state, T = nb[6];
+    const int* slen = nullptr;
+    const int* nlen[kHubertLevels] = {};
+    if (lens_host) {
+        int32_t lv[kHubertLevels][64];
+        for (int b = 0; b < B; ++b) {
+            int32_t one[kHubertLevels];
+            hubert_levels(lens_host[b], pad, one);
+            for (int i = 0; i < kHubertLevels; ++i) lv[i][b] = one[i];
+        }
+        LDS_TRY(whisper_upload(lens_host, B, w.slen, st));
+        slen = w.slen;
+        for (int i = 0; i < kHubertLevels; ++i) {
+            LDS_TRY(whisper_upload(lv[i], B, w.nlen[i], st));
+            nlen[i] = w.nlen[i];
+        }
+    }
+    TileBatchScope tb(0);      // tile rules judged at the nominal batch: a clip's units do not depend on the batch it is in
+    HIP_TRY(launch_hubert_conv0(audio, slen, L, pad, h->w0, h->gn_g, h->gn_b, 1e-5f, nlen[0], nb[0], D, w.part, w.stat, w.ca, B, st));
+    float* x = w.ca;
+    float* xn = w.cb;
+    for (int i = 1; i < kHubertLevels; ++i) {      // gelu(conv_i(.)): stride 2, no padding; frames beyond a clip's count at level i are zeros
+        LensScope ls(nlen[i]);
+        DOpt o;
+        o.stride = 2; o.pad = 0; o.epi = EPI_GELU;
+        if (i == kHubertLevels - 1) o.lnpart_out = w.lnp;      // partials for feature_projection.norm
+        LDS_TRY(run_dconv(h->conv[i - 1], x, D, nullptr, 0, nb[i - 1], o, xn, B, st));
+        { float* t = x; x = xn; xn = t; }
+    }
+    const int* flen = nlen[kHubertLevels - 1];
+    if (feat) HIP_TRY(launch_hubert_store_frames(x, feat, flen, B, D, T, st));
+    if (!enc) return LDS_OK;
+    LensScope ls(flen);
+    {
+        DOpt o;      // projection(norm(.))
+        o.ln_part = w.lnp; o.ln_np = D / 32; o.ln_c1 = h->fproj_c1; o.ln_c2 = h->fproj_c2;
+        LDS_TRY(run_dconv(h->fproj, x, D, nullptr, 0, T, o, w.xa, B, st));
+    }
+    HIP_TRY(launch_hubert_posconv(w.xa, h->pos_w, h->pos_b, w.xb, flen, B, C, T, h->cfg.pos_kernel, h->cfg.pos_groups, st));
+    HIP_TRY(launch_hubert_ln(w.xb, h->norm_g, h->norm_b, 1e-5f, w.xa, flen, B, C, T, st));
+    for (int l = 0; l < n_layers_run; ++l) {
+        const HubertBlockW& bw = h->blocks[l];
+        DOpt oq;      // q | k | v
+        oq.plain_from = 2 * C; oq.out2 = w.v; oq.vt_D = 64;
+        LDS_TRY(run_dconv(bw.qkv, w.xa, C, nullptr, 0, T, oq, w.qk, B, st));
+        HIP_TRY(launch_attention_k4p(w.qk, w.v, w.att, B, C, T, h->cfg.n_head, st, 0, flen, 0));
+        DOpt oo;      // x + out_proj(.), then norm1
+        oo.res = w.xa;
+        LDS_TRY(run_dconv(bw.out, w.att, C, nullptr, 0, T, oo, w.xb, B, st));
+        HIP_TRY(launch_hubert_ln(w.xb, bw.n1_g, bw.n1_b, 1e-5f, w.xa, flen, B, C, T, st));
+        DOpt o1;      // gelu(linear1(.))
+        o1.epi = EPI_GELU;
+        LDS_TRY(run_dconv(bw.fc1, w.xa, C, nullptr, 0, T, o1, w.big, B, st));
+        DOpt o2;      // + linear2(.), then norm2
+        o2.res = w.xa;
+        LDS_TRY(run_dconv(bw.fc2, w.big, h->cfg.n_ffn, nullptr, 0, T, o2, w.xb, B, st));
+        HIP_TRY(launch_hubert_ln(w.xb, bw.n2_g, bw.n2_b, 1e-5f, w.xa, flen, B, C, T, st));
+    }
+    if (want_proj) {
+        DOpt o;
+        LDS_TRY(run_dconv(h->proj, w.xa, C, nullptr, 0, T, o, w.pj, B, st));
+        HIP_TRY(launch_hubert_store_frames(w.pj, enc, flen, B, h->cfg.n_proj, T, st));
+    } else {
+        HIP_TRY(launch_hubert_store_frames(w.xa, enc, flen, B, C, T, st));
+    }
+    return LDS_OK;
+}
+
+static int hubert_audio_check(const lds_hubert* h, const float* audio, const int32_t* lengths, const void* out, const void* ws, int B, int64_t L, int pad,
+                              int32_t* nb) {
+    if (!h || !audio || !out || !ws) return fail(LDS_EINVAL, "null argument");
+    LDS_TRY(hubert_shape_check(h, B, L, pad, nb));
+    if (lengths) {
+        if (B > 64) return fail(LDS_EINVAL, "per-clip lengths: at most 64 clips per call (got %d)", B);
+        for (int b = 0; b < B; ++b)
+            if (lengths[b] < 400 - 2 * pad || lengths[b] > L)
+                return fail(LDS_EINVAL, "length[%d] = %d outside %d .. %lld", b, lengths[b], 400 - 2 * pad, (long long)L);
+    }
+    return LDS_OK;
+}
+extern "C" int lds_hubert_features(lds_hubert* h, const float* audio, const int32_t* lengths, float* out, void* ws, size_t ws_bytes, int B, int64_t L, int pad,
+                                   void* stream) {
+    int32_t nb[kHubertLevels];
+    LDS_TRY(hubert_audio_check(h, audio, lengths, out, ws, B, L, pad, nb));
+    return hubert_run(h, audio, L, pad, lengths, nb, out, nullptr, 0, 0, ws, ws_bytes, B, stream);
+}
+extern "C" int lds_hubert_encode(lds_hubert* h, const float* audio, const int32_t* lengths, float* out, int n_layers_run, int want_proj, void* ws,
+                                 size_t ws_bytes, int B, int64_t L, int pad, void* stream) {
+    int32_t nb[kHubertLevels];
+    LDS_TRY(hubert_audio_check(h, audio, lengths, out, ws, B, L, pad, nb));
+    if (n_layers_run < 0 || n_layers_run > h->cfg.n_layer) return fail(LDS_EINVAL, "hubert: n_layers_run %d outside 0 .. %d", n_layers_run, h->cfg.n_layer);
+    if (want_proj && n_layers_run != h->cfg.n_layer) return fail(LDS_EINVAL, "hubert: proj follows the last layer (n_layers_run %d of %d)", n_layers_run, h->cfg.n_layer);
+    return hubert_run(h, audio, L, pad, lengths, nb, nullptr, out, n_layers_run, want_proj, ws, ws_bytes, B, stream);
+}
+
+// ================================================================================================
 // Single-op test entry points
 // ================================================================================================
 extern "C" int lds_test_conv(const lds_conv_test* a, float* out, int B, void* stream) {

@@ -250,7 +250,7 @@ def encoder_param_shapes(h):
 
 def get_encoder_out_channels(encoder):
     """Reference tools/tools.py:257-264 (`get_encdoer_out_channels`)."""
-    table = {"whisper_large_v3": 1280, "contentvec768l12": 768, "xlsr_53_56k": 1024}
+    table = {"whisper_large_v3": 1280, "contentvec768l12": 768, "xlsr_53_56k": 1024, "hubertsoft": 256}
     if encoder in table:
         return table[encoder]
     raise ValueError(f"[x] Unknown encoder: {encoder}")
@@ -430,6 +430,106 @@ def whisper_mel_filters(n_mels, sr=16000, n_fft=400):
         w[i] = np.maximum(0.0, np.minimum(-ramps[i] / fdiff[i], ramps[i + 2] / fdiff[i + 1]))
     w *= (2.0 / (mel_f[2:n_mels + 2] - mel_f[:n_mels]))[:, None]
     return w.astype(np.float32)
+
+
+# ---- HuBERT units encoder (reference encoder/hubert/model.py:19-148: HuBERT-base; HuBERT-Soft and ContentVec are this network) ----------
+# the fields of include/lds.h lds_hubert_cfg; n_ctx = the most frames of one call (30 s)
+HUBERT_BASE_DIMS = dict(conv_dim=512, n_state=768, n_head=12, n_layer=12, n_ffn=3072, n_proj=256, pos_kernel=128, pos_groups=16, n_ctx=1500)
+HUBERT_HOP, HUBERT_PAD, HUBERT_MIN_SAMPLES = 320, 40, 320      # HubertSoft.units: 40 zeros per side, then L // 320 frames
+
+
+def hubert_level_frames(n_samples, pad=HUBERT_PAD):
+    """Frames after conv0 .. conv6 for a clip of n_samples padded by `pad` zeros per side (model.py:99-106): conv0 k 10 stride 5,
+    conv1..4 k 3 stride 2, conv5..6 k 2 stride 2, none padded."""
+    n = [(int(n_samples) + 2 * pad - 10) // 5 + 1]
+    for i in range(1, 7):
+        n.append((n[-1] - 3) // 2 + 1 if i <= 4 else (n[-1] - 2) // 2 + 1)
+    return n
+
+
+def hubert_frames(n_samples, pad=HUBERT_PAD):
+    """Frames the feature extractor gives for the clip (the last of hubert_level_frames).  With pad 40 this is n_samples // 320."""
+    return hubert_level_frames(n_samples, pad)[-1]
+
+
+def hubert_param_shapes(cfg=None, num_label_embeddings=100):
+    """`Hubert(num_label_embeddings).state_dict()` key -> shape, in the reference's order (masked_spec_embed and label_embedding.weight,
+    which inference never reads, included: a checkpoint loads with strict=True)"""
+    c = dict(HUBERT_BASE_DIMS if cfg is None else cfg)
+    D, C, F, P, K, G = c["conv_dim"], c["n_state"], c["n_ffn"], c["n_proj"], c["pos_kernel"], c["pos_groups"]
+    d = OrderedDict()
+    d["masked_spec_embed"] = (C,)
+    d["feature_extractor.conv0.weight"] = (D, 1, 10)
+    d["feature_extractor.norm0.weight"] = (D,)
+    d["feature_extractor.norm0.bias"] = (D,)
+    for i in range(1, 7):
+        d[f"feature_extractor.conv{i}.weight"] = (D, D, 3 if i <= 4 else 2)
+    d["feature_projection.norm.weight"] = (D,)
+    d["feature_projection.norm.bias"] = (D,)
+    d["feature_projection.projection.weight"] = (C, D)
+    d["feature_projection.projection.bias"] = (C,)
+    d["positional_embedding.conv.bias"] = (C,)
+    d["positional_embedding.conv.parametrizations.weight.original0"] = (1, 1, K)
+    d["positional_embedding.conv.parametrizations.weight.original1"] = (C, C // G, K)
+    d["norm.weight"] = (C,)
+    d["norm.bias"] = (C,)
+    for i in range(c["n_layer"]):
+        p = f"encoder.layers.{i}."
+        d[p + "self_attn.in_proj_weight"] = (3 * C, C)
+        d[p + "self_attn.in_proj_bias"] = (3 * C,)
+        d[p + "self_attn.out_proj.weight"] = (C, C)
+        d[p + "self_attn.out_proj.bias"] = (C,)
+        d[p + "linear1.weight"] = (F, C)
+        d[p + "linear1.bias"] = (F,)
+        d[p + "linear2.weight"] = (C, F)
+        d[p + "linear2.bias"] = (C,)
+        d[p + "norm1.weight"] = (C,)
+        d[p + "norm1.bias"] = (C,)
+        d[p + "norm2.weight"] = (C,)
+        d[p + "norm2.bias"] = (C,)
+    d["proj.weight"] = (P, C)
+    d["proj.bias"] = (P,)
+    d["label_embedding.weight"] = (int(num_label_embeddings), P)
+    return d
+
+
+def hubert_init_state(cfg=None, seed=0, init_weights=None, num_label_embeddings=100):
+    """Build-owned seeded weights (no checkpoint ships), scaled so that every stage lives at a scale of order 1 (torch's default
+    initialisation leaves the convolution stack at 2e-3, where an error would hide behind the next LayerNorm): the feature extractor's
+    GELU convolutions get He's bound sqrt(6 / fan_in), the positional convolution's per-tap norms g lie in [1.5, 3) (a sum over 128 taps
+    of variance g^2 / 768 each), in_proj three times the default bound (attention logits of standard deviation ~3); norms and everything
+    else by lds.init_weights' role rules.  `init_weights` = that module when this file is loaded by path."""
+    if init_weights is None:
+        from . import init_weights
+    import numpy as np
+    shapes = hubert_param_shapes(cfg, num_label_embeddings)
+    st = init_weights.init_state(shapes, seed)
+    for k, shp in shapes.items():
+        fan = int(np.prod(shp[1:])) if len(shp) > 1 else 1
+        if k.startswith("feature_extractor.conv"):
+            b = float(np.sqrt(6.0 / fan))
+            st[k] = init_weights.uniform(k, shp, seed, -b, b)
+        elif k.endswith("weight.original0"):
+            st[k] = init_weights.uniform(k, shp, seed, 1.5, 3.0)
+        elif k.endswith("in_proj_weight"):
+            b = float(3.0 / np.sqrt(fan))
+            st[k] = init_weights.uniform(k, shp, seed, -b, b)
+        elif k == "norm.weight":      # (the role rules know a norm by the dot in front of its name)
+            st[k] = init_weights.uniform(k, shp, seed, 0.8, 1.2)
+        elif k == "norm.bias":
+            st[k] = init_weights.uniform(k, shp, seed, -0.1, 0.1)
+        elif k == "masked_spec_embed":
+            st[k] = init_weights.uniform(k, shp, seed, 0.0, 1.0)
+    return {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in st.items()}
+
+
+def hubert_fold_weight_norm(g, v):
+    """parametrizations.weight_norm(conv, dim=2) folded in float64: w[:, :, k] = g[k] v[:, :, k] / |v[:, :, k]|, the norm over the other
+    two axes (what lds_hubert_create does at pack time)."""
+    import numpy as np
+    v64 = np.asarray(v, dtype=np.float64)
+    n = np.sqrt((v64 * v64).sum(axis=(0, 1), keepdims=True))
+    return np.asarray(g, dtype=np.float64).reshape(1, 1, -1) * v64 / n
 
 
 RESAMPLE_MAX_RATE, RESAMPLE_MAX_TAPS, RESAMPLE_MAX_BANK = 384000, 1024, 1 << 24      # include/lds.h lds_resample

@@ -96,6 +96,11 @@ lds_whisper_workspace_bytes      i:piqp
 lds_whisper_logmel               i:pppppziqp
 lds_whisper_encode_mel           i:pppppziip
 lds_whisper_encode               i:pppppziqp
+lds_hubert_create                i:pipppp
+lds_hubert_destroy               v:p
+lds_hubert_workspace_bytes       i:piqip
+lds_hubert_features              i:pppppziqip
+lds_hubert_encode                i:ppppiipziqip
 lds_lm_create                    i:pipppp
 lds_lm_destroy                   v:p
 lds_lm_workspace_bytes           i:piiip
@@ -573,6 +578,101 @@ class VaeEncoder(_Handle):
         check(fn(self.h, _dev(audio, torch.float32), *ln_at, _dev_or_null(noise, torch.float32), _dev(out), _dev_or_null(z), int(bool(only_mean)),
                  _dev(ws), ws.numel(), B, L, _stream()))
         return out, z
+
+
+class HubertCfg(C.Structure):
+    _fields_ = [("conv_dim", C.c_int), ("n_state", C.c_int), ("n_head", C.c_int), ("n_layer", C.c_int), ("n_ffn", C.c_int), ("n_proj", C.c_int),
+                ("pos_kernel", C.c_int), ("pos_groups", C.c_int), ("n_ctx", C.c_int)]
+
+
+class Hubert(_Handle):
+    """HuBERT units encoder (lds_hubert_*): audio [B,L] at 16 kHz -> the feature extractor's output [B,T,conv_dim] / the transformer's
+    [B,T,n_state] after `layer` blocks / units [B,T,n_proj].  `pad` zeros are added on each side of every clip (40: HubertSoft.units,
+    T = L // 320).  `lengths`: every clip's own sample count (host ints, 400 - 2 pad .. L, at most 64 clips): each clip is encoded as if
+    alone.  Every limit of include/lds.h is checked here first (ValueError, before a device is touched)."""
+    KIND = "hubert"
+    FIELDS = ("conv_dim", "n_state", "n_head", "n_layer", "n_ffn", "n_proj", "pos_kernel", "pos_groups", "n_ctx")
+
+    def __init__(self, dims, state):
+        d = {k: int(dims[k]) for k in self.FIELDS}
+        self.check_dims(d)
+        self._create_weights(HubertCfg(*(d[k] for k in self.FIELDS)), state)
+        self.dims = d
+
+    @staticmethod
+    def check_dims(d):
+        for k in ("conv_dim", "n_state"):
+            if d[k] < 64 or d[k] % 64 or d[k] > 1024:
+                raise ValueError(f"Hubert: {k} {d[k]} must be a multiple of 64 in 64 .. 1024")
+        if d["n_head"] < 1 or d["n_state"] != 64 * d["n_head"]:
+            raise ValueError(f"Hubert: n_state {d['n_state']} must be 64 * n_head ({d['n_head']})")
+        for k in ("n_ffn", "n_proj"):
+            if d[k] < 64 or d[k] % 64:
+                raise ValueError(f"Hubert: {k} {d[k]} must be a positive multiple of 64")
+        if d["pos_kernel"] < 2 or d["pos_kernel"] > 128 or d["pos_kernel"] % 2:
+            raise ValueError(f"Hubert: pos_kernel {d['pos_kernel']} must be even in 2 .. 128")
+        g = d["pos_groups"]
+        if g < 1 or d["n_state"] % g or (d["n_state"] // g) % 16 or d["n_state"] // g > 64:
+            raise ValueError(f"Hubert: n_state / pos_groups must be 16, 32, 48 or 64 (got {d['n_state']} / {g})")
+        if not 1 <= d["n_layer"] <= 64:
+            raise ValueError(f"Hubert: n_layer {d['n_layer']} outside 1 .. 64")
+        if not 1 <= d["n_ctx"] <= 1500:
+            raise ValueError(f"Hubert: n_ctx {d['n_ctx']} outside 1 .. 1500")
+
+    @staticmethod
+    def frames(n_samples, pad=40):
+        """frames of a clip of n_samples padded by `pad` zeros per side (= n_samples // 320 for pad 40)"""
+        from . import arch
+        return arch.hubert_frames(n_samples, pad)
+
+    def _check(self, B, L, pad):
+        if B < 1:
+            raise ValueError("Hubert: an empty batch")
+        if not 0 <= pad <= 40:
+            raise ValueError(f"Hubert: pad {pad} outside 0 .. 40")
+        if L < 400 - 2 * pad:
+            raise ValueError(f"Hubert: clips need at least {400 - 2 * pad} samples (got {L})")
+        if self.frames(L, pad) > self.dims["n_ctx"]:
+            raise ValueError(f"Hubert: {L} samples give {self.frames(L, pad)} frames, more than n_ctx {self.dims['n_ctx']}")
+
+    @staticmethod
+    def lengths(lengths, B, L, pad=40):
+        """per-clip sample counts -> host int32 [B] (include/lds.h: B <= 64, 400 - 2 pad .. L)"""
+        return _host_lengths(lengths, B, 400 - 2 * pad, L, 64, "units")
+
+    def workspace_bytes(self, B, L, pad=40):
+        return _bytes("lds_hubert_workspace_bytes", self.h, B, L, pad)
+
+    def _args(self, audio, lengths, ws, pad):
+        if audio.dim() != 2:
+            raise ValueError(f"Hubert: audio must be [B, L], got {list(audio.shape)}")
+        B, L = audio.shape
+        self._check(B, L, pad)
+        ln = self.lengths(lengths, B, L, pad) if lengths is not None else None
+        _dev(audio, None)
+        ws = ws if ws is not None else self.ws.get(self.workspace_bytes(B, L, pad), audio.device)
+        return B, L, ln, ws
+
+    def features(self, audio, lengths=None, ws=None, pad=40):
+        import torch
+        B, L, ln, ws = self._args(audio, lengths, ws, pad)
+        out = torch.empty(B, self.frames(L, pad), self.dims["conv_dim"], dtype=torch.float32, device=audio.device)
+        check(lib().lds_hubert_features(self.h, _dev(audio, torch.float32), _host(ln), _dev(out), _dev(ws), ws.numel(), B, L, pad, _stream()))
+        return out
+
+    def encode(self, audio, lengths=None, layer=None, proj=False, ws=None, pad=40):
+        """layer: the blocks to run (None = all, 0 = the output of `norm`); proj: apply `proj` (all blocks only) -> [B,T,n_proj]"""
+        import torch
+        nl = self.dims["n_layer"] if layer is None else int(layer)
+        if not 0 <= nl <= self.dims["n_layer"]:
+            raise ValueError(f"Hubert: layer {nl} outside 0 .. {self.dims['n_layer']}")
+        if proj and nl != self.dims["n_layer"]:
+            raise ValueError(f"Hubert: proj follows the last layer (layer {nl} of {self.dims['n_layer']})")
+        B, L, ln, ws = self._args(audio, lengths, ws, pad)
+        out = torch.empty(B, self.frames(L, pad), self.dims["n_proj" if proj else "n_state"], dtype=torch.float32, device=audio.device)
+        check(lib().lds_hubert_encode(self.h, _dev(audio, torch.float32), _host(ln), _dev(out), nl, 1 if proj else 0, _dev(ws), ws.numel(), B, L, pad,
+                                      _stream()))
+        return out
 
 
 class Whisper(_Handle):

@@ -1,6 +1,6 @@
 """`DiffusionSVC` inference facade: the reference's tools/infer_tools.py:9-117 with call signatures that are consistent with
 `Unit2Mel.forward` / `Vocoder.infer` (the reference's own versions raise TypeError before any compute).  What
-22_infer_tts.py uses is kept (load_model, __call__, infer, mel2wav), plus `encode_units` on the Whisper units encoder,
+22_infer_tts.py uses is kept (load_model, __call__, infer, mel2wav), plus `encode_units` on the units encoder (Whisper or HuBERT),
 `extract_volume_and_mask` and `infer_from_long_audio`: a recording in, the converted recording out, its segments run as ragged batches.
 Not built: key shift and f0 (the reference's `extract_f0` does not exist; the TTS model takes neither)."""
 import numpy as np
@@ -19,23 +19,30 @@ class DiffusionSVC:
         self.units_encoder = None
         self.volume_extractor = None
 
-    def load_model(self, model_path, loaded_vocoder=None, units_encoder_checkpoint=None, *, resample=False, **_ignored):
+    def load_model(self, model_path, loaded_vocoder=None, units_encoder_checkpoint=None, *, resample=False, encoder=None, **_ignored):
         """reference infer_tools.py:28-30 (22_infer_tts.py passes extra f0_min/f0_max keywords that the reference's own
         method does not accept; they are accepted and ignored here).  The reference builds its Units_Encoder here (infer_tools.py:31-38);
-        this one only when `units_encoder_checkpoint` names the Whisper encoder's checkpoint (large-v3_encoder.pt).  `resample`
-        (keyword-only, not in the reference) goes to Units_Encoder: with True, encode_units resamples audio of another rate."""
+        this one only when `units_encoder_checkpoint` names the checkpoint of the encoder that args.data.encoder names: the Whisper
+        encoder's (large-v3_encoder.pt; also when no encoder is named) or, for 'hubertsoft' / 'contentvec768l12', a HubertSoft state dict
+        (tools.tools.HubertUnits).  `resample` (keyword-only, not in the reference) goes to Units_Encoder: with True, encode_units
+        resamples audio of another rate; `encoder` (keyword-only) overrides the name in args.data.encoder."""
         self.model_path = model_path
         self.model, self.vocoder, self.args = load_model_vocoder(model_path, device=self.device, loaded_vocoder=loaded_vocoder)
         from tools.tools import Volume_Extractor
         self.volume_extractor = Volume_Extractor(hop_size=512, block_size=self.args["data"]["block_size"],      # (reference infer_tools.py:39-43)
                                                  model_sampling_rate=self.args["data"]["sampling_rate"])
         if units_encoder_checkpoint is not None:
-            from tools.tools import Units_Encoder, WhisperLargeV3
+            from tools.tools import HubertUnits, Units_Encoder, WhisperLargeV3
             data = getattr(self.args, "data", None)
-            self.units_encoder = Units_Encoder(getattr(data, "encoder", "whisper_large_v3"), getattr(data, "encoder_sample_rate", 16000),
+            name = encoder if encoder is not None else getattr(data, "encoder", "whisper_large_v3")
+            if name in HubertUnits.NAMES:
+                model = HubertUnits(name, device=self.device, checkpoint=units_encoder_checkpoint)
+            else:
+                model = WhisperLargeV3(device=self.device, checkpoint=units_encoder_checkpoint)
+            self.units_encoder = Units_Encoder(name, getattr(data, "encoder_sample_rate", 16000),
                                                getattr(data, "encoder_hop_size", 320), device=self.device,
                                                units_forced_mode=getattr(data, "units_forced_mode", "nearest"),
-                                               model=WhisperLargeV3(device=self.device, checkpoint=units_encoder_checkpoint), resample=resample)
+                                               model=model, resample=resample)
 
     def encode_units(self, audio, sr=44100, padding_mask=None):
         """reference infer_tools.py:41-44: audio at `sr` -> units [T, C] on the device (Units_Encoder.encode: `sr` must be the encoder's
@@ -97,19 +104,20 @@ class DiffusionSVC:
     def _plan_long_audio(self, sr, ranges, batch_size):
         """The host-side plan of infer_from_long_audio for the segments `ranges` = [(start_frame, begin, end)] of a recording at `sr`
         (tools.slicer.split_ranges): per segment its model frames n_s = int(len // hop) + 1, and the chunks: segment numbers sorted by
-        length (stable), at most batch_size each.  ValueError naming the segment that exceeds the encoder's window."""
+        length (stable), at most batch_size each.  ValueError naming the segment that exceeds the encoder's window.  The frame rule and
+        the window are the encoder's: Whisper's (L // 160 - 1) // 2 + 1 frames of n_audio_ctx, or a HuBERT encoder's L // 320 of its n_ctx."""
         block_size, rate = self.args["data"]["block_size"], self.args["data"]["sampling_rate"]
         hop_size = block_size * sr / rate
         ue = self.units_encoder
-        enc = ue.model.model.encoder
+        enc = ue.model      # (tools.tools.WhisperLargeV3 or HubertUnits: frames_of, n_ctx, family)
         n_frames = []
         for s, (start_frame, begin, end) in enumerate(ranges):
             ln = end - begin
             n_frames.append(int(ln // hop_size) + 1)
             at_enc = -((-ln * ue.encoder_sample_rate) // sr)      # ceil(len * new / orig): what the resampler makes of it
-            if ((at_enc // 160) - 1) // 2 + 1 > enc.n_ctx:
+            if enc.frames_of(at_enc) > enc.n_ctx:
                 raise ValueError(f"infer_from_long_audio: segment {s} (samples {begin} .. {end}, {ln / sr:.1f} s) exceeds the units encoder's window of "
-                                 f"{enc.n_ctx} frames (30 s for Whisper); splitting a segment further is not built")
+                                 f"{enc.n_ctx} frames (30 s for {enc.family}); splitting a segment further is not built")
         order = sorted(range(len(ranges)), key=lambda s: ranges[s][2] - ranges[s][1])
         chunks = [order[c:c + int(batch_size)] for c in range(0, len(order), int(batch_size))]
         return dict(hop_size=hop_size, block_size=block_size, n_frames=n_frames, chunks=chunks)

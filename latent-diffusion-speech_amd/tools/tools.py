@@ -1,12 +1,14 @@
 """The pieces of reference tools/tools.py that are built: the encoder-width table, `units_forced_alignment` (and its per-clip form
-`units_forced_alignment_ragged`), the Whisper units encoder (`Units_Encoder` / `WhisperLargeV3`, reference tools/tools.py:43-126),
+`units_forced_alignment_ragged`), the units encoders (`Units_Encoder` over `WhisperLargeV3`, reference tools/tools.py:43-126, or over
+`HubertUnits`: the reference's encoder/hubert/model.py as 'hubertsoft' / 'contentvec768l12'),
 `Volume_Extractor`, `upsample` and `cross_fade` (tools/tools.py:12-41, 225-238) and `Resample`, the torchaudio transform that file imports
-(tools/tools.py:9).  The two other speech encoders and the schedulers there are not built."""
+(tools/tools.py:9).  'w2v-bert', 'xlsr_53_56k' and the schedulers there are not built."""
 import math
 
 import numpy as np
 import torch
 
+from encoder.hubert.model import HubertSoft
 from encoder.whisper.model import ModelDimensions, Whisper
 from lds import arch, native
 from lds.arch import get_encoder_out_channels
@@ -153,7 +155,10 @@ class Resample(torch.nn.Module):
 
 
 class Units_Encoder:
-    """Speech -> units (reference tools/tools.py:43-103).  Built: encoder 'whisper_large_v3' in the 'nearest' / 'left' modes.
+    """Speech -> units (reference tools/tools.py:43-103).  Built: encoder 'whisper_large_v3' in the 'nearest' / 'left' modes, and the
+    HuBERT stack (HubertUnits below) as 'hubertsoft' (256-wide soft units) and 'contentvec768l12' (its 768-wide last layer).  Frame counts
+    and the shortest clip come from the model (`frames_of`, `min_samples`): (L // 160 - 1) // 2 + 1 and 400 samples for Whisper, L // 320
+    and 320 for HuBERT.
     Deviations from the reference, each raising instead of guessing:
       - resampling is opt-in: by default `sample_rate` must equal `encoder_sample_rate` (ValueError naming both), where the reference
         resamples with torchaudio; with `resample=True` (keyword-only, not in the reference) a mismatched rate goes through
@@ -162,9 +167,10 @@ class Units_Encoder:
       - the units stay on the device (the reference moves them to the CPU); CPU tensors raise, there is no CPU fallback;
       - 'w2v-bert' needs a transformers hub download and 'xlsr_53_56k' fairseq: NotImplementedError; the 'rfa441to512' /
         'rfa512to441' modes need librosa's resampler: NotImplementedError.
-    `model` (not in the reference): a ready WhisperLargeV3, e.g. WhisperLargeV3.synthetic(...), instead of the checkpoint."""
+    `model` (not in the reference): a ready WhisperLargeV3 / HubertUnits, e.g. WhisperLargeV3.synthetic(...), instead of the checkpoint;
+    `checkpoint` (keyword-only, not in the reference): the file a HuBERT encoder loads its state dict from."""
 
-    def __init__(self, encoder, encoder_sample_rate=16000, encoder_hop_size=320, device=None, units_forced_mode='nearest', *, model=None, resample=False):
+    def __init__(self, encoder, encoder_sample_rate=16000, encoder_hop_size=320, device=None, units_forced_mode='nearest', *, model=None, resample=False, checkpoint=None):
         if device is None:
             device = 'cuda' if torch.cuda.is_available() else 'cpu'
         self.device = device
@@ -176,11 +182,19 @@ class Units_Encoder:
             raise NotImplementedError("Units_Encoder: 'w2v-bert' needs transformers' from_pretrained('facebook/w2v-bert-2.0') download; not built")
         if encoder == 'xlsr_53_56k':
             raise NotImplementedError("Units_Encoder: 'xlsr_53_56k' needs fairseq and its checkpoint; not built")
-        if encoder != 'whisper_large_v3':
+        if encoder not in ('whisper_large_v3',) + HubertUnits.NAMES:
             raise ValueError(f"[x] Unknown units encoder: {encoder}")
         if units_forced_mode in ('rfa441to512', 'rfa512to441'):
             raise NotImplementedError(f"units_forced_mode {units_forced_mode!r} resamples with librosa; not built")
-        self.model = model if model is not None else WhisperLargeV3(device=device)
+        if model is not None:
+            self.model = model
+        elif encoder in HubertUnits.NAMES:
+            if checkpoint is None:
+                raise ValueError(f"Units_Encoder: {encoder!r} needs checkpoint=PATH (a local state dict; nothing is downloaded) or model=")
+            self.model = HubertUnits(encoder, device=device, checkpoint=checkpoint)
+        else:
+            self.model = WhisperLargeV3(device=device)
+        self.min_samples = getattr(self.model, "min_samples", 400)
         self.resample_kernel = {}
         self.resample = bool(resample)
         self.encoder_sample_rate = encoder_sample_rate
@@ -206,8 +220,8 @@ class Units_Encoder:
         rs = self._check("Units_Encoder.encode", audio, sample_rate)
         if rs is not None:
             audio = rs(audio)
-        if audio.size(-1) < 400:
-            audio = torch.nn.functional.pad(audio, (0, 400 - audio.size(-1)))
+        if audio.size(-1) < self.min_samples:
+            audio = torch.nn.functional.pad(audio, (0, self.min_samples - audio.size(-1)))
         units = self.model(audio, padding_mask=padding_mask)
         if units.dim() == 3 and units.shape[0] == 1:
             units = units.squeeze(0)
@@ -225,16 +239,17 @@ class Units_Encoder:
         rs = self._check("Units_Encoder.encode_ragged", audio, self.encoder_sample_rate if sample_rate is None else sample_rate)
         if rs is not None:
             audio, lengths = rs.forward_ragged(audio, lengths)
-        if (rs is not None or pad_short) and audio.size(-1) < 400:
-            audio = torch.nn.functional.pad(audio, (0, 400 - audio.size(-1)))
+        lo = self.min_samples      # (400 with Whisper; 320 with a HuBERT encoder)
+        if (rs is not None or pad_short) and audio.size(-1) < lo:
+            audio = torch.nn.functional.pad(audio, (0, lo - audio.size(-1)))
         if pad_short:
             ln = native._host_lengths(lengths, audio.shape[0], 0, audio.shape[1], max_B=64, what="units")
-            if (ln < 400).any():
+            if (ln < lo).any():
                 if rs is None:      # (the resampler has written zeros beyond every clip already)
                     audio = audio.clone()
-                    for b in np.nonzero(ln < 400)[0]:
-                        audio[b, int(ln[b]):400] = 0
-                lengths = np.maximum(ln, 400)
+                    for b in np.nonzero(ln < lo)[0]:
+                        audio[b, int(ln[b]):lo] = 0
+                lengths = np.maximum(ln, lo)
         return self.model.encode_ragged(audio, lengths)
 
     def encode_tokens(self, audio, sample_rate, codebook):
@@ -248,6 +263,56 @@ class Units_Encoder:
         import cluster
         units, n_frames = self.encode_ragged(audio, lengths, sample_rate)
         return cluster.get_cluster_result(codebook, units, lengths=n_frames, pad_id=pad_id), n_frames
+
+
+class HubertUnits(torch.nn.Module):
+    """The HuBERT stack (encoder.hubert.model.HubertSoft) in the role WhisperLargeV3 plays for Units_Encoder.  `name`: 'hubertsoft' -> the
+    256-wide soft units (HubertSoft.units: proj of the last layer), 'contentvec768l12' -> the 768-wide output of the last layer of the same
+    stack, both of the waveform padded by 40 zeros per side, L // 320 frames.  `checkpoint`: a torch-saved state dict with the keys of the
+    reference's HubertSoft (optionally under "model_state_dict", an optional "module." prefix removed); a ContentVec checkpoint in fairseq's
+    key naming is NOT handled (rename its keys first).  `dims` + `state` (keyword-only) inject the weights directly."""
+    NAMES = ('hubertsoft', 'contentvec768l12')
+    min_samples = arch.HUBERT_MIN_SAMPLES
+    family = "HuBERT"
+
+    def __init__(self, name='hubertsoft', device='cuda', checkpoint=None, *, dims=None, state=None):
+        super().__init__()
+        if name not in self.NAMES:
+            raise ValueError(f"[x] Unknown units encoder: {name}")
+        self.name, self.device, self.proj = name, device, name == 'hubertsoft'
+        if state is None:
+            if checkpoint is None:
+                raise ValueError(f"HubertUnits: {name!r} needs checkpoint=PATH or dims= / state= (nothing is downloaded)")
+            print(name)
+            state = torch.load(checkpoint, map_location="cpu", weights_only=False)
+            state = state.get("model_state_dict", state)
+            state = {(k[len("module."):] if k.startswith("module.") else k): v for k, v in state.items()}
+        model = HubertSoft(dims=dims)
+        model.load_state_dict({k: torch.as_tensor(v) for k, v in state.items()}, strict=True)
+        self.model = model.eval()
+        self.hidden_dim = model.dims["n_proj" if self.proj else "n_state"]
+        self.n_ctx = model.dims["n_ctx"]      # the window of one call, in frames
+
+    @classmethod
+    def synthetic(cls, name='hubertsoft', dims=None, seed=0, device='cuda'):
+        """seeded weights (lds.arch.hubert_init_state) for `dims` (default: HuBERT-base) -- no checkpoint ships"""
+        dims = dict(arch.HUBERT_BASE_DIMS if dims is None else dims)
+        return cls(name, device=device, dims=dims, state=arch.hubert_init_state(dims, seed))
+
+    @staticmethod
+    def frames_of(n_samples):
+        return arch.hubert_frames(n_samples)
+
+    @torch.inference_mode()
+    def __call__(self, audio, padding_mask=None):
+        """audio (any shape, flattened into ONE clip) -> units [T, C] on the device; padding_mask is ignored as WhisperLargeV3 ignores it"""
+        if not audio.is_cuda:
+            raise RuntimeError("HubertUnits needs the audio on a HIP device (no CPU fallback)")
+        return self.model.native().encode(audio.reshape(1, -1).float().contiguous(), proj=self.proj).squeeze(0)
+
+    @torch.inference_mode()
+    def encode_ragged(self, audio, lengths):
+        return self.model.units_ragged(audio, lengths, proj=self.proj)
 
 
 class WhisperLargeV3(torch.nn.Module):
@@ -266,6 +331,18 @@ class WhisperLargeV3(torch.nn.Module):
         self.hidden_dim = dims
         self.model = model
         self.model.eval()
+
+    min_samples = 400
+    family = "Whisper"
+
+    @staticmethod
+    def frames_of(n_samples):
+        return (n_samples // 160 - 1) // 2 + 1
+
+    @property
+    def n_ctx(self):
+        """the window of one call, in frames"""
+        return self.model.encoder.n_ctx
 
     @classmethod
     def synthetic(cls, dims=None, seed=0, device='cuda'):
@@ -290,4 +367,4 @@ class WhisperLargeV3(torch.nn.Module):
         if not audio.is_cuda:
             raise RuntimeError("WhisperLargeV3.encode_ragged needs the audio on a HIP device (no CPU fallback)")
         units = enc.encode(audio.float().contiguous(), ln)
-        return units, torch.from_numpy((ln.astype(np.int64) // 160 - 1) // 2 + 1)
+        return units, torch.from_numpy(self.frames_of(ln.astype(np.int64)))

@@ -1,7 +1,7 @@
-"""Encode clips to Whisper units (the reference's 10_preprocess_train_unit.py flow; the counterpart of tools/extract_latents.py).
+"""Encode clips to units with Whisper large-v3 (default) or a HuBERT encoder (the reference's 10_preprocess_train_unit.py flow; the counterpart of tools/extract_latents.py).
 
     python tools/extract_units.py IN [--out DIR] [--checkpoint pretrain/large-v3_encoder.pt | --synthetic [--layers N] [--seed S]] [--batch 8]
-                                     [--sample-rate R]
+                                     [--sample-rate R] [--encoder {whisper_large_v3,hubertsoft,contentvec768l12}]
 
 IN is a directory (every .npy / .wav in it, sorted) or a text file listing one clip per line.  A .npy holds 1-D float32 samples at
 --sample-rate (default 16000); a .wav is PCM16 of any rate, read from its header (mono, or the first channel is taken).  Clips that
@@ -12,6 +12,8 @@ Units_Encoder.encode_ragged with their own lengths, so every clip's units are th
 clips shorter than 400 samples at 16 kHz are zero-padded to 400 as Units_Encoder.encode does; clips over 30 s (more than
 n_audio_ctx frames, counted at 16 kHz) are refused, as the data set's own preparation cuts them (00_del_audio_over_30s.py).
 --synthetic runs seeded weights at large-v3's width (no checkpoint needed; --layers sets the depth, default 32).
+--encoder hubertsoft / contentvec768l12 runs the HuBERT stack instead (tools.tools.HubertUnits): [T, 256] / [T, 768], T = len // 320, clips
+shorter than 320 samples zero-padded to 320; --checkpoint then names a HubertSoft state dict, and --synthetic's default depth is 12.
 """
 import argparse
 import os
@@ -25,7 +27,7 @@ import torch  # noqa: E402
 
 from encoder.whisper.model import ModelDimensions  # noqa: E402
 from lds import arch  # noqa: E402
-from tools.tools import Resample, Units_Encoder, WhisperLargeV3  # noqa: E402
+from tools.tools import HubertUnits, Resample, Units_Encoder, WhisperLargeV3  # noqa: E402
 
 ENCODER_RATE = 16000
 _resamplers = {}
@@ -43,9 +45,10 @@ def load_clip(path, npy_rate=ENCODER_RATE):
     return pcm.astype(np.float32) / 32768.0, rate
 
 
-def encoder_batch(clips):
+def encoder_batch(clips, min_samples=400):
     """[(samples, rate)] (at most 64) -> (audio [B, Lmax] on the device at 16 kHz, lengths [B]): the clips of every other rate go through
-    one Resample.forward_ragged call per rate, each clip as if alone; a clip shorter than 400 samples counts as 400 (zeros follow it)"""
+    one Resample.forward_ragged call per rate, each clip as if alone; a clip shorter than `min_samples` (400 for Whisper) counts as that
+    many (zeros follow it)"""
     rows = [None] * len(clips)
     for rate in sorted({r for _, r in clips}):
         idx = [b for b, (_, r) in enumerate(clips) if r == rate]
@@ -61,7 +64,7 @@ def encoder_batch(clips):
             lens = lens.tolist()
         for k, b in enumerate(idx):
             rows[b] = x[k, :lens[k]]
-    lens = [max(int(r.numel()), 400) for r in rows]
+    lens = [max(int(r.numel()), min_samples) for r in rows]
     audio = torch.zeros((len(rows), max(lens)), dtype=torch.float32, device="cuda")
     for b, r in enumerate(rows):
         audio[b, :r.numel()] = r
@@ -72,9 +75,10 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("inp", help="directory of .npy / .wav clips, or a text file listing them")
     ap.add_argument("--out", default=None)
-    ap.add_argument("--checkpoint", default="pretrain/large-v3_encoder.pt")
+    ap.add_argument("--encoder", default="whisper_large_v3", choices=("whisper_large_v3",) + HubertUnits.NAMES)
+    ap.add_argument("--checkpoint", default=None, help="default: pretrain/large-v3_encoder.pt for whisper_large_v3; required for a HuBERT encoder")
     ap.add_argument("--synthetic", action="store_true", help="seeded weights instead of the checkpoint")
-    ap.add_argument("--layers", type=int, default=32)
+    ap.add_argument("--layers", type=int, default=None, help="depth of the --synthetic model (default 32; 12 for a HuBERT encoder)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--sample-rate", type=int, default=ENCODER_RATE, help="rate of the .npy clips (a .wav carries its own)")
@@ -87,15 +91,22 @@ def main():
         paths = [ln.strip() for ln in open(a.inp) if ln.strip()]
     out = a.out or os.path.join(base, "units")
     os.makedirs(out, exist_ok=True)
-    if a.synthetic:
-        model = WhisperLargeV3.synthetic(ModelDimensions(**dict(arch.WHISPER_LARGE_V3_DIMS, n_audio_layer=a.layers)), seed=a.seed, device="cuda")
+    if a.encoder in HubertUnits.NAMES:
+        if a.synthetic:
+            model = HubertUnits.synthetic(a.encoder, dict(arch.HUBERT_BASE_DIMS, n_layer=a.layers or 12), seed=a.seed, device="cuda")
+        elif a.checkpoint is None:
+            ap.error(f"--encoder {a.encoder} needs --checkpoint (a HubertSoft state dict) or --synthetic")
+        else:
+            model = HubertUnits(a.encoder, device="cuda", checkpoint=a.checkpoint)
+    elif a.synthetic:
+        model = WhisperLargeV3.synthetic(ModelDimensions(**dict(arch.WHISPER_LARGE_V3_DIMS, n_audio_layer=a.layers or 32)), seed=a.seed, device="cuda")
     else:
-        model = WhisperLargeV3(device="cuda", checkpoint=a.checkpoint)
-    ue = Units_Encoder("whisper_large_v3", device="cuda", model=model)
+        model = WhisperLargeV3(device="cuda", checkpoint=a.checkpoint or "pretrain/large-v3_encoder.pt")
+    ue = Units_Encoder(a.encoder, device="cuda", model=model)
     batch = max(1, min(a.batch, 64))
     for i in range(0, len(paths), batch):
         group = paths[i:i + batch]
-        audio, lens = encoder_batch([load_clip(p, a.sample_rate) for p in group])
+        audio, lens = encoder_batch([load_clip(p, a.sample_rate) for p in group], ue.min_samples)
         units, n_frames = ue.encode_ragged(audio, lens)
         units = units.cpu().numpy()
         for b, p in enumerate(group):
