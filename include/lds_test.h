@@ -121,6 +121,41 @@ int lds_test_conv_down_ragged(const float* x, const float* w, const float* b, in
                               const int32_t* lengths_in, const int32_t* lengths_out, int tile, float* out, char* cfg_out, size_t cfg_cap,
                               void* stream);
 int lds_debug_set_split_rule(int rule);
+
+/* ---- conv_dma / conv_bf3 modes that the product reaches through whole models only (tests/test_gpu_conv_modes.py) ----
+ * Common to the three entries: fmt -1 = exact fp32 (K4P, conv_dma), 0 = three bf16 planes, 1 = two fp16 planes (conv_bf3), as lds_test_gn_fold_split;
+ * tile_batch as there (0 = the tile rules at the nominal batch, > 0 = the latency mode's choices at that batch, cluster split-K included); cfg_out
+ * (or NULL) receives the configuration string of the launch under test.  lengths (host int32 [B], B <= 64, or NULL = dense) are the per-utterance
+ * lengths of a ragged batch (csrc/k4p.h ragged_len): the INPUT tensors must hold zeros at and beyond an utterance's frames at their level, as every
+ * tensor of a ragged batch does; the entry does not mask them.  Output buffers are filled with NaN patterns before the launch. */
+/* the fused resnet tail (csrc/kernels.h launch_conv_dma_pair / launch_conv_bf3_pair): out [B][Co][T] = conv_k3(h [B][Cm][T]; w3 [Co][Cm][3], pad 1)
+ * + conv_1x1([x1 ; x2] [B][C1 + C2][T]; w1 [Co][C1 + C2][1]) + b3 + b1 (x2 NULL when C2 = 0; weights and biases host), gnpart [B][Co/16][ceil(T/32)][2]
+ * = the epilogue's GroupNorm partials (mean, M2) over each block's valid frames; lvl = the level of all tensors.  Shapes without a fused variant are an
+ * error: the two-launch fallback of the resnet driver is never run here. */
+int lds_test_dconv_pair(const float* h, const float* x1, const float* x2, const float* w3, const float* b3, const float* w1, const float* b1, int B,
+                        int Cm, int C1, int C2, int Co, int T, const int32_t* lengths, int lvl, int tile_batch, int fmt, float* out, float* gnpart,
+                        char* cfg_out, size_t cfg_cap, void* stream);
+typedef struct {                        /* lds_dconv_test with the encoders' epilogue and geometries and the ragged drivers' lengths */
+    const float* x1; const float* x2;   /* dev inputs [B,C1,T], [B,C2,T] (x2 NULL when C2 = 0)                                      */
+    int C1, C2, T;
+    const float* w; const float* bias;  /* host, reference layout [Co, C1+C2, K] / [Co] (or NULL)                                   */
+    int Co, K, stride, pad;             /* To = (T + 2 pad - K) / stride + 1                                                        */
+    const float* res;                   /* dev [B,Co,To] or NULL                                                                    */
+    int epilogue;                       /* 0 none, 3 exact-form GELU of the biased / normalised value, before the residual          */
+    const int32_t* lengths;             /* host [B] or NULL; the input is at level lvl_in of them, the output at lvl_out            */
+    int lvl_in, lvl_out;
+    const float* ln_gamma; const float* ln_beta;      /* host [C1], both or neither: LayerNorm over the channels of x1 folded into the (1x1) convolution;   */
+    float ln_eps;                       /* its per-frame partials come from the epilogue of an identity convolution the entry runs  */
+    int tile_batch, fmt;
+} lds_dconv_ex_test;
+/* out dev [B][Co][To]; gnpart dev [B][Co/16][ceil(To/32)][2] or NULL */
+int lds_test_dconv_ex(const lds_dconv_ex_test* a, float* out, float* gnpart, int B, char* cfg_out, size_t cfg_cap, void* stream);
+/* one vocoder upsampler on conv_dma as the generator runs it: x dev [B][Ci][T] -> LeakyReLU(0.1) K4P copy with its pad frames zeroed -> polyphase
+ * ConvTranspose1d(K = 2 stride, stride, padding (K - stride + 1) / 2; w host [Ci][Co][K], bias host [Co] or NULL) -> out (raw) and out_act
+ * (LeakyReLU(0.1) of it), both dev [B][Co][(T - 1) stride - 2 padding + K].  lengths_in / lengths_out (host int32 [B], both or neither): x is not read at
+ * and beyond lengths_in[b] frames (it counts as zeros there, whatever it holds) and both outputs are zeros at and beyond lengths_out[b]. */
+int lds_test_voc_ups(const float* x, const float* w, const float* bias, int B, int Ci, int Co, int T, int K, int stride, const int32_t* lengths_in,
+                     const int32_t* lengths_out, float* out, float* out_act, char* cfg_out, size_t cfg_cap, void* stream);
 /* plain [B,C,T] -> K8B3 -> plain: must return the input bit for bit (the three-term split is lossless) */
 int lds_test_k8b3_roundtrip(const float* x, float* out, int B, int C, int T, void* stream);
 /* GroupNorm(+scale/shift)(+SiLU) through the K8B3 streaming pass (statistics from gn_partials_bf3) */

@@ -839,8 +839,10 @@ static hipError_t launch_bf3_pair_cfg(const DmaConvArgs& a3, const DmaConvArgs& 
         hipError_t e = ensure_max_dynamic_lds(reinterpret_cast<const void*>(kern), attr_done);
         if (e != hipSuccess) return e;
     }
-    snprintf(g_bcfg, sizeof(g_bcfg), "BM%d BN%d KT3+1 S1 U0 BK%d+%d NST%d %s grid %ux%u lds %zu", BM, BN, BK3, BK1, NST, FMT == FMT_F16X2 ? "H3" : "P6", grid.x, grid.y,
-             Cfg::LDS_BYTES);
+    if (S > 1) snprintf(g_bcfg, sizeof(g_bcfg), "BM%d BN%d KT3+1 S1 U0 BK%d+%d NST%d %s KS%d grid %ux%u lds %zu", BM, BN, BK3, BK1, NST, FMT == FMT_F16X2 ? "H3" : "P6", S,
+                        grid.x, grid.y, Cfg::LDS_BYTES);
+    else snprintf(g_bcfg, sizeof(g_bcfg), "BM%d BN%d KT3+1 S1 U0 BK%d+%d NST%d %s grid %ux%u lds %zu", BM, BN, BK3, BK1, NST, FMT == FMT_F16X2 ? "H3" : "P6", grid.x, grid.y,
+                  Cfg::LDS_BYTES);
     Bf3PairArgs pp{a3, a1};
     hipEvent_t e0, e1;
     if (prof_attach_events(&e0, &e1)) hipExtLaunchKernelGGL(kern, grid, dim3(256), Cfg::LDS_BYTES, s, e0, e1, 0, pp);
@@ -909,6 +911,7 @@ static hipError_t split_dispatch(const DmaConvArgs& a_, int cfg, int nprod, hipS
     a.ksplit = 1;
     if (a.Ci % 16 || a.C1 % 16 || a.Mp % 32 || a.B <= 0 || a.To <= 0 || a.pad < 0 || a.pad > 1 || a.voc) return hipErrorInvalidValue;
     if (a.KT != 1 && a.KT != 3) return hipErrorInvalidValue;
+    if (a.epi != EPI_NONE && a.epi != EPI_GEGLU) return hipErrorInvalidValue;      // (no plain-GELU epilogue here: the encoders that use it run on conv_dma)
     int bm, bn, bk, nst;
     bf3_pick(a, cfg, bm, bn, bk, nst, FMT);
     const bool k32 = (a.Ci % 32 == 0) && (a.C1 % 32 == 0), k64 = (a.Ci % 64 == 0) && (a.C1 % 64 == 0);

@@ -3488,3 +3488,189 @@ extern "C" int lds_debug_set_split_rule(int rule) {
     conv_bf3_set_debug_rule(rule);
     return LDS_OK;
 }
+
+// ---- conv_dma / conv_bf3 modes that only whole-model runs reach otherwise (tests/test_gpu_conv_modes.py) ----
+// host int32 lengths [B] -> a device copy (B <= 64), as the ragged drivers carry them
+static int test_upload_lens(TmpDev& tmp, const int32_t* host, int B, int*& dev, hipStream_t st) {
+    dev = nullptr;
+    if (!host) return LDS_OK;
+    if (B < 1 || B > 64) return fail(LDS_EINVAL, "per-utterance lengths: 1 .. 64 batch elements (got %d)", B);
+    dev = (int*)tmp.f(64);
+    if (!dev) return fail(LDS_ENOMEM, "alloc");
+    float t4[64];
+    memcpy(t4, host, sizeof(int) * B);
+    HIP_TRY(launch_set_list((float*)dev, t4, B, st));
+    return LDS_OK;
+}
+struct TestActs {      // plain <-> the activation layout of a kernel family (fmt -1: K4P; 0 / 1: split planes)
+    int fmt, B; hipStream_t st;
+    size_t floats(int C, int T) const { return fmt < 0 ? (size_t)B * C * (T + 2) : (size_t)B * split_floats(fmt, C, T); }
+    hipError_t to(const float* src, float* dst, int C, int T) const { return fmt < 0 ? launch_to_k4p(src, dst, B, C, T, C, 0, st) : launch_to_k8b3(src, dst, B, C, T, C, 0, st, fmt); }
+    hipError_t from(const float* src, float* dst, int C, int T) const { return fmt < 0 ? launch_from_k4p(src, dst, B, C, T, st) : launch_from_k8b3(src, dst, B, C, T, st, fmt); }
+};
+
+// The fused resnet tail alone (run_resnet -> run_dconv_pair[_bf3]): out = conv_k3(h; w3) + conv_1x1([x1 ; x2]; w1) + b3 + b1 with the epilogue's
+// GroupNorm partials.  No fused variant for the shapes is an error: the two-launch fallback is never run here.
+extern "C" int lds_test_dconv_pair(const float* h, const float* x1, const float* x2, const float* w3, const float* b3, const float* w1, const float* b1, int B,
+                                   int Cm, int C1, int C2, int Co, int T, const int32_t* lengths, int lvl, int tile_batch, int fmt, float* out, float* gnpart,
+                                   char* cfg_out, size_t cfg_cap, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    if (!h || !x1 || (C2 > 0) != (x2 != nullptr) || !w3 || !b3 || !w1 || !b1 || !out || !gnpart || B < 1 || T < 1 || Cm < 8 || C1 < 8 || C2 < 0 || (Cm & 7) || (C1 & 7) ||
+        (C2 & 7) || Co < 32 || Co % 32 || lvl < 0 || tile_batch < 0 || (fmt != -1 && fmt != FMT_BF16X3 && fmt != FMT_F16X2))
+        return fail(LDS_EINVAL, "bad argument");
+    const bool f32 = fmt < 0;
+    Owner own;
+    TmpDev tmp;
+    ConvW W3, W1;
+    if (!pack_conv(own, w3, nullptr, Co, Cm, 3, W3) || !pack_conv(own, w1, nullptr, Co, C1 + C2, 1, W1)) return fail(LDS_ENOMEM, "upload failed");
+    if (!f32 && !make_split_twin_pair(own, W3, W1, fmt)) return fail(LDS_ENOMEM, "upload failed");
+    std::vector<float> bp(W3.Mp, 0.f);
+    for (int co = 0; co < Co; ++co) bp[co] = b3[co] + b1[co];
+    float* bias_pair = own.upload(bp);
+    if (!bias_pair) return fail(LDS_ENOMEM, "upload failed");
+    int* lens = nullptr;
+    LDS_TRY(test_upload_lens(tmp, lengths, B, lens, st));
+    const TestActs act{fmt, B, st};
+    const int nT = (T + 31) / 32;
+    float* kh = tmp.f(act.floats(Cm, T));
+    float* k1 = tmp.f(act.floats(C1, T));
+    float* k2 = C2 ? tmp.f(act.floats(C2, T)) : nullptr;
+    float* ko = tmp.f(act.floats(Co, T));
+    float* kpart = tile_batch ? tmp.f((size_t)kClusterPartFloats) : nullptr;
+    unsigned* kcount = tile_batch ? (unsigned*)tmp.f(kClusterCounters) : nullptr;
+    if (!kh || !k1 || (C2 && !k2) || !ko || (tile_batch && (!kpart || !kcount))) return fail(LDS_ENOMEM, "alloc");
+    if (kcount) HIP_TRY(hipMemsetAsync(kcount, 0, sizeof(unsigned) * kClusterCounters, st));
+    HIP_TRY(hipMemsetAsync(ko, 0xff, sizeof(float) * act.floats(Co, T), st));                        // NaN fill: every frame and every partial must be written
+    HIP_TRY(hipMemsetAsync(gnpart, 0xff, sizeof(float) * (size_t)B * (Co / 16) * nT * 2, st));
+    HIP_TRY(act.to(h, kh, Cm, T));
+    HIP_TRY(act.to(x1, k1, C1, T));
+    if (C2) HIP_TRY(act.to(x2, k2, C2, T));
+    int rc;
+    {
+        LensScope ls(lens);
+        TileBatchScope tbs(tile_batch, kpart, kcount);
+        rc = f32 ? run_dconv_pair(W3, kh, W1, k1, C1, k2, C2, T, bias_pair, (float2*)gnpart, ko, B, st, lvl)
+                 : run_dconv_pair_bf3(W3, kh, W1, k1, C1, k2, C2, T, bias_pair, (float2*)gnpart, ko, B, st, fmt, lvl);
+    }
+    if (rc == 1) rc = fail(LDS_EINVAL, "dconv pair: no fused variant for Cm %d C1 %d C2 %d Co %d T %d (fmt %d, tile_batch %d)", Cm, C1, C2, Co, T, fmt, tile_batch);
+    if (rc == LDS_OK) {
+        if (cfg_out && cfg_cap) snprintf(cfg_out, cfg_cap, "%s", f32 ? conv_dma_last_config() : conv_bf3_last_config());
+        HIP_TRY(act.from(ko, out, Co, T));
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    return rc;
+}
+
+// lds_test_dconv with the modes of the encoders and the ragged drivers (include/lds_test.h lds_dconv_ex_test)
+extern "C" int lds_test_dconv_ex(const lds_dconv_ex_test* a, float* out, float* gnpart, int B, char* cfg_out, size_t cfg_cap, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    if (!a || !a->x1 || !a->w || !out || B < 1 || a->T < 1 || (a->C2 > 0) != (a->x2 != nullptr) || a->C1 < 8 || (a->C1 & 7) || a->C2 < 0 || (a->C2 & 7) || a->Co < 32 ||
+        a->Co % 32 || a->K < 1 || a->stride < 1 || a->pad < 0 || (a->epilogue != EPI_NONE && a->epilogue != EPI_GELU) || a->lvl_in < 0 || a->lvl_out < 0 ||
+        a->tile_batch < 0 || (a->fmt != -1 && a->fmt != FMT_BF16X3 && a->fmt != FMT_F16X2) || (a->ln_gamma != nullptr) != (a->ln_beta != nullptr))
+        return fail(LDS_EINVAL, "bad argument");
+    const bool f32 = a->fmt < 0, ln = a->ln_gamma != nullptr;
+    const int mode = f32 ? 0 : a->fmt + 1;
+    const int Ci = a->C1 + a->C2, T = a->T;
+    const int To = (T + 2 * a->pad - (a->K - 1) - 1) / a->stride + 1;
+    if (To < 1) return fail(LDS_EINVAL, "bad argument: no output frame");
+    if (ln && (a->K != 1 || a->C2 || Ci % 32)) return fail(LDS_EINVAL, "the LayerNorm fold takes a 1x1 convolution over one source of a multiple of 32 channels");
+    Owner own;
+    TmpDev tmp;
+    ConvW W, Wid;
+    float *c1 = nullptr, *c2 = nullptr;
+    bool ok = ln ? pack_ln_fold(own, a->w, a->bias, a->ln_gamma, a->ln_beta, a->Co, Ci, {}, W, c1, c2) : pack_conv(own, a->w, a->bias, a->Co, Ci, a->K, W);
+    if (ok && ln) {      // the partials' producer: an identity 1x1 convolution, whose epilogue writes the per-frame LayerNorm partials of x itself
+        std::vector<float> eye((size_t)Ci * Ci, 0.f);
+        for (int c = 0; c < Ci; ++c) eye[(size_t)c * Ci + c] = 1.0f;
+        ok = pack_conv(own, eye.data(), nullptr, Ci, Ci, 1, Wid);
+    }
+    if (ok && !f32) ok = make_split_twin(own, W, a->fmt) && (!ln || make_split_twin(own, Wid, a->fmt));
+    if (!ok) return fail(LDS_ENOMEM, "test dconv: upload failed");
+    int* lens = nullptr;
+    LDS_TRY(test_upload_lens(tmp, a->lengths, B, lens, st));
+    const TestActs act{a->fmt, B, st};
+    float* k1 = tmp.f(act.floats(a->C1, T));
+    float* k2 = a->C2 ? tmp.f(act.floats(a->C2, T)) : nullptr;
+    float* kx = ln ? tmp.f(act.floats(Ci, T)) : nullptr;
+    float* part = ln ? tmp.f((size_t)B * (Ci / 32) * T * 2) : nullptr;
+    float* kres = a->res ? tmp.f(act.floats(a->Co, To)) : nullptr;
+    float* ko = tmp.f(act.floats(a->Co, To));
+    float* kpart = a->tile_batch ? tmp.f((size_t)kClusterPartFloats) : nullptr;
+    unsigned* kcount = a->tile_batch ? (unsigned*)tmp.f(kClusterCounters) : nullptr;
+    if (!k1 || (a->C2 && !k2) || (ln && (!kx || !part)) || (a->res && !kres) || !ko || (a->tile_batch && (!kpart || !kcount))) return fail(LDS_ENOMEM, "alloc");
+    if (kcount) HIP_TRY(hipMemsetAsync(kcount, 0, sizeof(unsigned) * kClusterCounters, st));
+    HIP_TRY(hipMemsetAsync(ko, 0xff, sizeof(float) * act.floats(a->Co, To), st));      // NaN fill: every frame and every partial must be written
+    if (gnpart) HIP_TRY(hipMemsetAsync(gnpart, 0xff, sizeof(float) * (size_t)B * (a->Co / 16) * ((To + 31) / 32) * 2, st));
+    HIP_TRY(act.to(a->x1, k1, a->C1, T));
+    if (a->C2) HIP_TRY(act.to(a->x2, k2, a->C2, T));
+    if (a->res) HIP_TRY(act.to(a->res, kres, a->Co, To));
+    int rc = LDS_OK;
+    {
+        LensScope ls(lens);
+        const float* xin = k1;
+        if (ln) {
+            DOpt oi;
+            oi.lvl_in = oi.lvl_out = a->lvl_in;
+            oi.lnpart_out = (float2*)part;
+            rc = dconv_any(mode, Wid, k1, Ci, nullptr, 0, T, oi, kx, B, st);
+            xin = kx;
+        }
+        if (rc == LDS_OK) {
+            TileBatchScope tbs(a->tile_batch, kpart, kcount);
+            DOpt o;
+            o.stride = a->stride; o.pad = a->pad; o.epi = a->epilogue; o.res = kres;
+            o.lvl_in = a->lvl_in; o.lvl_out = a->lvl_out;
+            o.gnpart_out = (float2*)gnpart;
+            if (ln) { o.ln_part = (const float2*)part; o.ln_np = Ci / 32; o.ln_eps = a->ln_eps; o.ln_c1 = c1; o.ln_c2 = c2; }
+            rc = dconv_any(mode, W, xin, a->C1, k2, a->C2, T, o, ko, B, st);
+        }
+    }
+    if (rc == LDS_OK) {
+        if (cfg_out && cfg_cap) snprintf(cfg_out, cfg_cap, "%s", f32 ? conv_dma_last_config() : conv_bf3_last_config());
+        HIP_TRY(act.from(ko, out, a->Co, To));
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    return rc;
+}
+
+// One vocoder upsampler on conv_dma, as vocoder_forward_impl runs the stages voc_dma_ups admits: plain x -> LeakyReLU(0.1) K4P copy with kVocPad
+// zero frames per side -> polyphase ConvTranspose1d(K, stride, padding (K - stride + 1) / 2) -> the raw output and its LeakyReLU(0.1)
+extern "C" int lds_test_voc_ups(const float* x, const float* w, const float* bias, int B, int Ci, int Co, int T, int K, int stride, const int32_t* lengths_in,
+                                const int32_t* lengths_out, float* out, float* out_act, char* cfg_out, size_t cfg_cap, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    int lg = 0;
+    while ((1 << lg) < stride) ++lg;
+    if (!x || !w || !out || !out_act || B < 1 || T < 1 || Ci < 16 || Ci % 16 || Co < 64 || Co % 64 || stride < 2 || stride > 16 || (1 << lg) != stride || K != 2 * stride ||
+        (lengths_in != nullptr) != (lengths_out != nullptr))
+        return fail(LDS_EINVAL, "bad argument");
+    const int P = kVocPad, tpad = (K - stride + 1) / 2, Tn = (T - 1) * stride - 2 * tpad + K;
+    for (int b = 0; b < B && lengths_in; ++b)
+        if (lengths_in[b] < 0 || lengths_in[b] > T || lengths_out[b] < 0 || lengths_out[b] > Tn)
+            return fail(LDS_EINVAL, "lengths_in[%d] = %d / lengths_out[%d] = %d outside 0 .. %d / 0 .. %d", b, lengths_in[b], b, lengths_out[b], T, Tn);
+    Owner own;
+    TmpDev tmp;
+    ConvW W;
+    if (!pack_convT(own, w, bias, Ci, Co, K, stride, W)) return fail(LDS_ENOMEM, "upload failed");
+    int *vin = nullptr, *vout = nullptr;
+    LDS_TRY(test_upload_lens(tmp, lengths_in, B, vin, st));
+    LDS_TRY(test_upload_lens(tmp, lengths_out, B, vout, st));
+    const size_t n_in = (size_t)B * Ci * (T + 2 * P), n_out = (size_t)B * Co * (Tn + 2 * P);
+    float *scratch = tmp.f(n_in), *kin = tmp.f(n_in), *o_raw = tmp.f(n_out), *o_act = tmp.f(n_out);
+    if (!scratch || !kin || !o_raw || !o_act) return fail(LDS_ENOMEM, "alloc");
+    HIP_TRY(hipMemsetAsync(kin, 0xff, n_in * sizeof(float), st));        // NaN fill: pads must be zeroed explicitly, real frames written
+    HIP_TRY(hipMemsetAsync(o_raw, 0xff, n_out * sizeof(float), st));
+    HIP_TRY(hipMemsetAsync(o_act, 0xff, n_out * sizeof(float), st));
+    HIP_TRY(launch_to_k4p_act(x, scratch, kin, 0.1f, B, Ci, T, P, st, vin));
+    HIP_TRY(launch_k4p_zero_pads(kin, B, Ci, T, P, st));
+    DOpt o;
+    o.voc = 1; o.xpad = P; o.opad = P; o.pad = 1; o.act_slope = 0.1f; o.out_act = o_act;
+    o.ph_log2 = lg; o.ph_tpad = tpad; o.ph_Tout = Tn; o.vlen = vout;
+    const int rc = run_dconv(W, kin, Ci, nullptr, 0, T, o, o_raw, B, st);
+    if (rc == LDS_OK) {
+        if (cfg_out && cfg_cap) snprintf(cfg_out, cfg_cap, "%s", conv_dma_last_config());
+        HIP_TRY(launch_from_k4p_pad(o_raw, out, B, Co, Tn, P, st));
+        HIP_TRY(launch_from_k4p_pad(o_act, out_act, B, Co, Tn, P, st));
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    return rc;
+}

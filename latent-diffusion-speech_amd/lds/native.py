@@ -57,6 +57,13 @@ class DConvTest(C.Structure):
                 ("v_split", C.c_int), ("cfg", C.c_int)]
 
 
+class DConvExTest(C.Structure):
+    _fields_ = [("x1", C.c_void_p), ("x2", C.c_void_p), ("C1", C.c_int), ("C2", C.c_int), ("T", C.c_int),
+                ("w", C.c_void_p), ("bias", C.c_void_p), ("Co", C.c_int), ("K", C.c_int), ("stride", C.c_int), ("pad", C.c_int),
+                ("res", C.c_void_p), ("epilogue", C.c_int), ("lengths", C.c_void_p), ("lvl_in", C.c_int), ("lvl_out", C.c_int),
+                ("ln_gamma", C.c_void_p), ("ln_beta", C.c_void_p), ("ln_eps", C.c_float), ("tile_batch", C.c_int), ("fmt", C.c_int)]
+
+
 # The C ABI, one line per entry point: name, return kind ':' argument kinds in the header's order.
 # Arguments: p pointer (any sort, c_void_p), i int, z size_t, f float, q int64_t, u uint32_t.  Returns: i int, v void, s const char*.
 _KIND = {"p": C.c_void_p, "i": C.c_int, "z": C.c_size_t, "f": C.c_float, "q": C.c_int64, "u": C.c_uint32}
@@ -168,6 +175,9 @@ lds_test_lm_sample               i:piiiifffppipp
 lds_test_conv_down               i:pppiiiiiifippzp
 lds_test_conv_down_ragged        i:pppiiiiiifppippzp
 lds_test_lm_beam_step            i:piiiiiifiippppppppppppppppp
+lds_test_dconv_pair              i:pppppppiiiiiipiiipppzp
+lds_test_dconv_ex                i:pppipzp
+lds_test_voc_ups                 i:pppiiiiiipppppzp
 """
 SIGNATURES = dict(ln.split() for ln in (_PUBLIC + _TEST).splitlines() if ln)
 EXPORTS = [ln.split()[0] for ln in _PUBLIC.splitlines() if ln]

@@ -91,7 +91,7 @@ def test_binding_signatures_and_structures_match_the_headers(libpath):
     structs.update(test_structs)
     mirrors = {"lds_unet_cfg": native.UNetCfg, "lds_vocoder_cfg": native.VocoderCfg, "lds_lm_cfg": native.LMCfg,
                "lds_lm_decode_opts": native.LMDecodeOpts, "lds_whisper_cfg": native.WhisperCfg, "lds_conv_test": native.ConvTest,
-               "lds_dconv_test": native.DConvTest}
+               "lds_dconv_test": native.DConvTest, "lds_dconv_ex_test": native.DConvExTest}
     assert set(structs) == set(mirrors)
     for tname, cls in mirrors.items():
         assert [f[0] for f in cls._fields_] == [f[0] for f in structs[tname]], tname
