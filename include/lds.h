@@ -254,6 +254,35 @@ int  lds_hubert_features(lds_hubert* h, const float* audio, const int32_t* lengt
 int  lds_hubert_encode(lds_hubert* h, const float* audio, const int32_t* lengths, float* out, int n_layers_run, int want_proj, void* ws,
                        size_t ws_bytes, int B, int64_t L, int pad, void* stream);
 
+/* ---- units encoder: wav2vec 2.0 in its layer-norm flavour (XLSR-53; reference tools/tools.py Audio2xlsr_53_56k = fairseq's
+ *      extract_features(source, padding_mask = all False)["x"]), audio -> units ----------------------------------------------------------
+ * Seven waveform convolutions with HuBERT's kernels and strides (conv0 k 10 stride 5; conv1..4 k 3, conv5..6 k 2, all stride 2, no
+ * padding), each with a bias, a LayerNorm over the conv_dim channels of every frame and an erf GELU; LayerNorm + Linear (conv_dim -> n_state);
+ * x + GELU(grouped positional convolution: pos_kernel taps, pos_groups groups, weight norm over the taps, padding pos_kernel / 2, last
+ * frame dropped); n_layer pre-LayerNorm transformer blocks (n_head heads of 64, feed-forward n_ffn, biases on q, k, v, out); a final
+ * LayerNorm.  The waveform is taken as it is (no normalisation, no padding).  A clip of n samples gives T = the frame rule of lds_hubert with
+ * pad 0 (400 samples -> 1 frame, 30 s -> 1499).
+ * Tensor names are fairseq's (what the reference's pretrain/xlsr_53_56k.pt holds): feature_extractor.conv_layers.{i}.0.{weight,bias},
+ * feature_extractor.conv_layers.{i}.2.1.{weight,bias} (the LayerNorm), layer_norm.*, post_extract_proj.*,
+ * encoder.pos_conv.0.{bias,weight_g,weight_v}, encoder.layers.{l}.self_attn.{q,k,v,out}_proj.*, .self_attn_layer_norm.*, .fc1.*, .fc2.*,
+ * .final_layer_norm.*, encoder.layer_norm.*; other names are ignored.  LDS_EMISSING names a missing tensor.
+ * Limits: conv_dim and n_state multiples of 64 up to 1024, n_state = 64 n_head, n_ffn a multiple of 64, pos_kernel even in 2 .. 128,
+ * n_state / pos_groups in {16, 32, 48, 64}, 1 <= n_layer <= 64, T <= n_ctx <= 1500, 400 <= L <= 2^30.
+ * audio: dev [B][L] fp32.  lengths: host int32 [B] (B <= 64, 400 <= lengths[b] <= L) or NULL: clip b is audio[b, :lengths[b]] encoded alone.
+ * Nothing at or beyond lengths[b] is read; rows at and beyond T_b of a result are zeros.  A clip's result does not depend on the other clips
+ * of the call.  Exact fp32, no floating-point atomics: a repeat gives the same bits.  Nothing synchronises; a bad argument returns before
+ * anything is enqueued; a small workspace gives LDS_ENOMEM. */
+typedef struct lds_w2v lds_w2v;
+typedef struct lds_w2v_cfg { int conv_dim, n_state, n_head, n_layer, n_ffn, pos_kernel, pos_groups, n_ctx; } lds_w2v_cfg;
+int  lds_w2v_create(const lds_w2v_cfg* cfg, int n_tensors, const char* const* names, const float* const* host_ptrs, const int64_t* numel, lds_w2v** out);
+void lds_w2v_destroy(lds_w2v* h);
+/* one size for both calls below */
+int  lds_w2v_workspace_bytes(const lds_w2v* h, int B, int64_t L, size_t* out);
+/* out dev [B][T][conv_dim] frame-major = the feature extractor's output (after the last LayerNorm + GELU) */
+int  lds_w2v_features(lds_w2v* h, const float* audio, const int32_t* lengths, float* out, void* ws, size_t ws_bytes, int B, int64_t L, void* stream);
+/* out dev [B][T][n_state] = the output of encoder.layer_norm */
+int  lds_w2v_encode(lds_w2v* h, const float* audio, const int32_t* lengths, float* out, void* ws, size_t ws_bytes, int B, int64_t L, void* stream);
+
 /* ---- text2semantic: RoFormer encoder prefill + cached autoregressive decode (reference text2semantic/roformer/roformer.py:59-255
  *      over HF transformers RoFormerModel / RoFormerForCausalLM + GenerationMixin; called from 22_infer_tts.py:76-98) ------------- */
 typedef struct lds_lm lds_lm;

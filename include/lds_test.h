@@ -177,6 +177,16 @@ int lds_test_lm_beam_step(const float* logits, int B, int K, int V, int cur_len,
                           float* run_score_out, int32_t* parent_out, int64_t* fin_seq_out, float* fin_score_out, int32_t* fin_flag_out,
                           int32_t* fin_len_out, int32_t* unsat_out, int32_t* flag_out, void* stream);
 
+/* The wav2vec 2.0 encoder's own kernels alone (csrc/w2v.hip); every pointer but the lengths is a device pointer.
+ * w2v_conv0: audio [B][L] -> out [B][C][N0], N0 = (L - 10) / 5 + 1: GELU(LayerNorm over the C channels of each frame(bias + conv0(clip)));
+ * w [C][10]; lengths (host int32 [B] or NULL): the clips' sample counts (10 .. L), frames at and beyond (lengths[b] - 10) / 5 + 1 are zeros.
+ * w2v_ln_act: x [B][C][T] -> out [B][C][T] = GELU(LayerNorm over the channels); n_frames (host int32 [B] or NULL): zeros at and beyond;
+ * part (or NULL) [B][C / 32][T][2] = (mean, M2) of every 32 channels of out.  C a multiple of 64 up to 1024, B <= 64. */
+int lds_test_w2v_conv0(const float* audio, const int32_t* lengths, const float* w, const float* bias, const float* gamma, const float* beta, float eps,
+                       float* out, int B, int C, int64_t L, void* stream);
+int lds_test_w2v_ln_act(const float* x, const int32_t* n_frames, const float* gamma, const float* beta, float eps, float* out, float* part, int B, int C,
+                        int T, void* stream);
+
 /* ---- debugging aids (tests/test_gpu_poison.py, tools/diag_trace.py) ----------------------------------------------------------
  * lds_debug_fill_u32: every 32-bit word of a device buffer = pattern.  Tests fill a caller workspace with NaN patterns (0x7fc07fc0 is a NaN
  * as fp32 and as two fp16 / bf16 halves) before a call: a kernel that reads a slot no kernel of THAT call wrote turns it into a NaN (or, behind

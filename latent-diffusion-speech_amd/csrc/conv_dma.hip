@@ -1062,7 +1062,7 @@ hipError_t launch_conv_dma(const DmaConvArgs& a_, int cfg, hipStream_t s) {
         return hipErrorInvalidValue;
     }
     if (a.dil != 1 || a.act_slope != 0.f || a.acc_in || a.out_div != 1.0f || a.ph_Tout) return hipErrorInvalidValue;      // vocoder-only features
-    if (a.KT != 1 && a.KT != 3 && !(a.KT == 2 && a.stride == 2 && a.epi == EPI_GELU)) return hipErrorInvalidValue;      // (k 2: HuBERT's conv5 / conv6)
+    if (a.KT != 1 && a.KT != 3 && !(a.KT == 2 && a.stride == 2 && (a.epi == EPI_GELU || a.epi == EPI_NONE))) return hipErrorInvalidValue;      // (k 2: HuBERT's / wav2vec 2.0's conv5 / conv6)
     const bool k32 = (a.Ci % 32 == 0) && (a.C1 % 32 == 0), k64 = (a.Ci % 64 == 0) && (a.C1 % 64 == 0);
     int bm, bn, bk, nst;
     dma_pick(a, cfg, bm, bn, bk, nst);
@@ -1163,6 +1163,9 @@ hipError_t launch_conv_dma(const DmaConvArgs& a_, int cfg, hipStream_t s) {
         if (bk == 32 && nst == 2) DCASE(64, 64, 3, 2, false, 32, 2);
         if (bk >= 16 && nst == 3) DCASE(64, 64, 3, 2, false, 16, 3);
         if (bk == 16 && nst == 2) DCASE(64, 64, 3, 2, false, 16, 2);
+    } else if (key == 220 && tk == 64064) {      // the wav2vec 2.0 feature extractor's last two convolutions (their LayerNorm + GELU follow as a pass)
+        if (bk == 32) DCASE(64, 64, 2, 2, false, 32, 2);
+        DCASE(64, 64, 2, 2, false, 16, 2);
     } else if (key == 311 && tk == 64064) {
         if (bk == 32 && nst == 2) DCASE(64, 64, 3, 1, true, 32, 2);
         if (bk >= 16 && nst == 3) DCASE(64, 64, 3, 1, true, 16, 3);

@@ -240,9 +240,10 @@ hipError_t launch_logmel(const float* audio, const int* slen, long long L, int F
 // x (K4P [B][C][T]) += posk (the positional table as one K4P element of n_ctx frames) on frames below ragged_len(lens, b, 1, T);
 // lnpart [B][C/32][T] = the LayerNorm partials of the sum (DmaConvArgs::lnpart_out's format)
 hipError_t launch_whisper_pos(float* x, const float* posk, int n_ctx, float2* lnpart, const int* lens, int B, int C, int T, hipStream_t s);
-// out [B][T][C] frame-major = LayerNorm(x) from the partials lnpart; rows at and beyond ragged_len(lens, b, 1, T) are zeros
+// out [B][T][C] frame-major = LayerNorm(x) from the partials lnpart; rows at and beyond ragged_len(lens, b, lvl, T) are zeros (lvl 1: Whisper,
+// whose lens count mel frames; lvl 0: lens are the clips' own frame counts)
 hipError_t launch_whisper_ln_post(const float* x, const float2* lnpart, const float* gamma, const float* beta, float eps, float* out, const int* lens,
-                                  int B, int C, int T, hipStream_t s);
+                                  int B, int C, int T, hipStream_t s, int lvl = 1);
 
 // ---------------------------------------------------------------------------------------------
 // HuBERT units encoder: the kernels of its own (hubert.hip); nlen / slen are device int32 [B] or null (= the buffer's length)
@@ -258,6 +259,20 @@ hipError_t launch_hubert_posconv(const float* x, const float* wp, const float* b
 hipError_t launch_hubert_ln(const float* x, const float* gamma, const float* beta, float eps, float* out, const int* nlen, int B, int C, int T, hipStream_t s);
 // x (K4P [B][C][T]) -> out [B][T][C] frame-major, zero rows beyond a clip's frames
 hipError_t launch_hubert_store_frames(const float* x, float* out, const int* nlen, int B, int C, int T, hipStream_t s);
+
+// ---------------------------------------------------------------------------------------------
+// wav2vec 2.0 (XLSR-53) units encoder: the kernels of its own (w2v.hip); nlen / slen are device int32 [B] or null (= the buffer's length)
+// ---------------------------------------------------------------------------------------------
+// audio [B][L] -> out K4P [B][C][N0] = GELU(LayerNorm over the C channels of each frame(bias + conv0(clip))), N0 = (L - 10) / 5 + 1;
+// clip b = audio[b, :slen[b]] with its own nlen[b] frames; w0 [C][10]; C a multiple of 64, at most 1024
+hipError_t launch_w2v_conv0(const float* audio, const int* slen, long long L, const float* w0, const float* bias, const float* gamma, const float* beta,
+                            float eps, const int* nlen, int N0, int C, float* out, int B, hipStream_t s);
+// out (K4P, not x) = GELU(LayerNorm over the channels of x (K4P)), zeros beyond a clip's frames; part (or null) [B][C / 32][T] = the
+// (mean, M2) partials of out in DmaConvArgs::lnpart_out's format
+hipError_t launch_w2v_ln_act(const float* x, const float* gamma, const float* beta, float eps, float* out, float2* part, const int* nlen, int B, int C, int T,
+                             hipStream_t s);
+// part [B][C / 32][T] = the (mean, M2) partials of x (K4P) in DmaConvArgs::lnpart_out's format
+hipError_t launch_w2v_lnpart(const float* x, float2* part, const int* nlen, int B, int C, int T, hipStream_t s);
 
 // ---------------------------------------------------------------------------------------------
 // Small dense layers with N = batch columns (time embedding path)

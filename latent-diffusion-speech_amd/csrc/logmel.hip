@@ -188,15 +188,17 @@ hipError_t launch_whisper_pos(float* x, const float* posk, int n_ctx, float2* ln
 }
 
 // ln_post: out[b][t][c] = (x[b][c][t] - mean_t) * rstd_t * gamma[c] + beta[c] from the last block's LayerNorm partials (the statistics
-// every folded LayerNorm of the stack uses, gn_chan.h ln_column_stats); rows t >= T_b are zeros.  grid (ceil(T / 32), C / 64, B): a
+// every folded LayerNorm of the stack uses, gn_chan.h ln_column_stats); rows t >= T_b are zeros.  LVL: the level of `lens` (1: Whisper's
+// mel frames; 0: the wav2vec 2.0 encoder's own frame counts).  grid (ceil(T / 32), C / 64, B): a
 // 64-channel x 32-frame tile goes through LDS so that both the K4P reads and the frame-major stores are whole lines.
+template <int LVL>
 __global__ void __launch_bounds__(256) whisper_ln_post_kernel(const float* __restrict__ x, const float2* __restrict__ lnpart, const float* __restrict__ gamma,
                                                               const float* __restrict__ beta, float eps, float* __restrict__ out,
                                                               const int* __restrict__ lens, int C, int T) {
     __shared__ float tile[32][65];
     __shared__ float smu[32], srs[32];
     const int tid = threadIdx.x, t0 = blockIdx.x * 32, c0 = blockIdx.y * 64, b = blockIdx.z;
-    const int Tb = ragged_len(lens, b, 1, T);
+    const int Tb = ragged_len(lens, b, LVL, T);
     if (tid < 32) {
         const int t = t0 + tid;
         const bool ok = t < Tb;
@@ -224,10 +226,12 @@ __global__ void __launch_bounds__(256) whisper_ln_post_kernel(const float* __res
 }
 
 hipError_t launch_whisper_ln_post(const float* x, const float2* lnpart, const float* gamma, const float* beta, float eps, float* out, const int* lens,
-                                  int B, int C, int T, hipStream_t s) {
-    if (B <= 0 || B > 65535 || C % 64 || T <= 0) return hipErrorInvalidValue;
+                                  int B, int C, int T, hipStream_t s, int lvl) {
+    if (B <= 0 || B > 65535 || C % 64 || T <= 0 || lvl < 0 || lvl > 1) return hipErrorInvalidValue;
     ProfScope ps(s, "whisper_ln_post", 4.0 * B * (double)C * T, 8.0 * B * (double)C * T);
-    hipLaunchKernelGGL(whisper_ln_post_kernel, dim3((T + 31) / 32, C / 64, B), dim3(256), 0, s, x, lnpart, gamma, beta, eps, out, lens, C, T);
+    const dim3 grid((T + 31) / 32, C / 64, B);
+    if (lvl) hipLaunchKernelGGL(whisper_ln_post_kernel<1>, grid, dim3(256), 0, s, x, lnpart, gamma, beta, eps, out, lens, C, T);
+    else hipLaunchKernelGGL(whisper_ln_post_kernel<0>, grid, dim3(256), 0, s, x, lnpart, gamma, beta, eps, out, lens, C, T);
     return hipGetLastError();
 }
 

@@ -2869,6 +2869,254 @@ extern "C" int lds_hubert_encode(lds_hubert* h, const float* audio, const int32_
 }
 
 // ================================================================================================
+// wav2vec 2.0 units encoder in its layer-norm flavour (XLSR-53; reference tools/tools.py Audio2xlsr_53_56k: fairseq's
+// extract_features(source, padding_mask = all False)["x"]).  HuBERT's convolution strides and frame rule (no padding of the clip), but
+// every convolution has a bias and a LayerNorm over the channels of each frame in front of its GELU (w2v.hip), the positional convolution
+// is followed by no LayerNorm, and the blocks are pre-LN: Whisper's five launches with every LayerNorm folded into the GEMM that reads it,
+// then `encoder.layer_norm` through whisper_ln_post.  Tensor names are fairseq's (what pretrain/xlsr_53_56k.pt holds).
+// ================================================================================================
+struct lds_w2v {
+    lds_w2v_cfg cfg;
+    Owner own;
+    float *w0 = nullptr, *b0 = nullptr;                            // conv0 [conv_dim][10] and its bias
+    float *ln_g[kHubertLevels] = {}, *ln_b[kHubertLevels] = {};    // the LayerNorm behind conv0 .. conv6
+    ConvW conv[6];                                                 // conv1 .. conv6, biased
+    ConvW fproj;                                                   // layer_norm folded into post_extract_proj
+    float *fproj_c1 = nullptr, *fproj_c2 = nullptr;
+    float *pos_w = nullptr, *pos_b = nullptr;                      // weight norm folded, packed for hubert_posconv
+    std::vector<WhisperBlockW> blocks;
+    float *post_g = nullptr, *post_b = nullptr;                    // encoder.layer_norm
+};
+
+static int w2v_cfg_check(const lds_w2v_cfg* c) {
+    if (!c) return fail(LDS_EINVAL, "null argument");
+    if (c->conv_dim < 64 || c->conv_dim % 64 || c->conv_dim > 1024) return fail(LDS_EINVAL, "w2v: conv_dim %d must be a multiple of 64 in 64 .. 1024", c->conv_dim);
+    if (c->n_state < 64 || c->n_state % 64 || c->n_state > 1024) return fail(LDS_EINVAL, "w2v: n_state %d must be a multiple of 64 in 64 .. 1024", c->n_state);
+    if (c->n_head < 1 || c->n_state != c->n_head * 64) return fail(LDS_EINVAL, "w2v: n_state / n_head must be 64 (got %d / %d)", c->n_state, c->n_head);
+    if (c->n_layer < 1 || c->n_layer > 64) return fail(LDS_EINVAL, "w2v: n_layer %d outside 1 .. 64", c->n_layer);
+    if (c->n_ffn < 64 || c->n_ffn % 64) return fail(LDS_EINVAL, "w2v: n_ffn %d must be a positive multiple of 64", c->n_ffn);
+    if (c->pos_kernel < 2 || c->pos_kernel > 128 || (c->pos_kernel & 1)) return fail(LDS_EINVAL, "w2v: pos_kernel %d must be even in 2 .. 128", c->pos_kernel);
+    if (c->pos_groups < 1 || c->n_state % c->pos_groups || (c->n_state / c->pos_groups) % 16 || c->n_state / c->pos_groups > 64)
+        return fail(LDS_EINVAL, "w2v: n_state / pos_groups must be 16, 32, 48 or 64 (got %d / %d)", c->n_state, c->pos_groups);
+    if (c->n_ctx < 1 || c->n_ctx > 1500) return fail(LDS_EINVAL, "w2v: n_ctx %d outside 1 .. 1500", c->n_ctx);
+    return LDS_OK;
+}
+
+extern "C" int lds_w2v_create(const lds_w2v_cfg* cfg, int n, const char* const* names, const float* const* ptrs, const int64_t* numel, lds_w2v** out) {
+    if (!cfg || !names || !ptrs || !numel || !out || n < 0) return fail(LDS_EINVAL, "null argument");
+    LDS_TRY(w2v_cfg_check(cfg));
+    const int D = cfg->conv_dim, C = cfg->n_state, F = cfg->n_ffn, K = cfg->pos_kernel, gw = C / cfg->pos_groups;
+    Tensors T;
+    for (int i = 0; i < n; ++i) T.m[names[i]] = {ptrs[i], numel[i]};
+    lds_w2v* h = new lds_w2v();
+    h->cfg = *cfg;
+    Owner& o = h->own;
+    auto vec = [&](const std::string& k, int64_t cnt) -> float* {
+        const float* p = T.get(k, cnt);
+        return p ? o.upload(std::vector<float>(p, p + cnt)) : nullptr;
+    };
+    bool ok = true;
+    for (int i = 0; i < kHubertLevels && ok; ++i) {
+        const std::string p = "feature_extractor.conv_layers." + std::to_string(i) + ".";
+        h->ln_g[i] = vec(p + "2.1.weight", D);
+        h->ln_b[i] = vec(p + "2.1.bias", D);
+        ok = h->ln_g[i] && h->ln_b[i];
+        if (!ok) break;
+        if (i == 0) {
+            h->w0 = vec(p + "0.weight", (int64_t)D * 10);
+            h->b0 = vec(p + "0.bias", D);
+            ok = h->w0 && h->b0;
+        } else {
+            const int k = i <= 4 ? 3 : 2;
+            const float *w = T.get(p + "0.weight", (int64_t)D * D * k), *b = T.get(p + "0.bias", D);
+            ok = w && b && pack_conv(o, w, b, D, D, k, h->conv[i - 1]);
+        }
+    }
+    if (ok) {
+        const float *g = T.get("layer_norm.weight", D), *b = T.get("layer_norm.bias", D);
+        const float *w = T.get("post_extract_proj.weight", (int64_t)C * D), *wb = T.get("post_extract_proj.bias", C);
+        ok = g && b && w && wb && pack_ln_fold(o, w, wb, g, b, C, D, {}, h->fproj, h->fproj_c1, h->fproj_c2);
+    }
+    if (ok) {
+        const float* g = T.get("encoder.pos_conv.0.weight_g", K);
+        const float* v = T.get("encoder.pos_conv.0.weight_v", (int64_t)C * gw * K);
+        h->pos_b = vec("encoder.pos_conv.0.bias", C);
+        if (g && v) h->pos_w = pack_posconv(o, g, v, C, cfg->pos_groups, K);
+        ok = h->pos_w && h->pos_b;
+    }
+    h->blocks.resize(cfg->n_layer);
+    for (int l = 0; l < cfg->n_layer && ok; ++l) {
+        const std::string p = "encoder.layers." + std::to_string(l) + ".";
+        WhisperBlockW& bw = h->blocks[l];
+        const int64_t CC = (int64_t)C * C;
+        const float *ag = T.get(p + "self_attn_layer_norm.weight", C), *ab = T.get(p + "self_attn_layer_norm.bias", C);
+        const float *qw = T.get(p + "self_attn.q_proj.weight", CC), *qb = T.get(p + "self_attn.q_proj.bias", C);
+        const float *kw = T.get(p + "self_attn.k_proj.weight", CC), *kb = T.get(p + "self_attn.k_proj.bias", C);
+        const float *vw = T.get(p + "self_attn.v_proj.weight", CC), *vb = T.get(p + "self_attn.v_proj.bias", C);
+        const float *ow = T.get(p + "self_attn.out_proj.weight", CC), *ob = T.get(p + "self_attn.out_proj.bias", C);
+        const float *mg = T.get(p + "final_layer_norm.weight", C), *mb = T.get(p + "final_layer_norm.bias", C);
+        const float *f1 = T.get(p + "fc1.weight", (int64_t)F * C), *f1b = T.get(p + "fc1.bias", F);
+        const float *f2 = T.get(p + "fc2.weight", (int64_t)F * C), *f2b = T.get(p + "fc2.bias", C);
+        if (!ag || !ab || !qw || !qb || !kw || !kb || !vw || !vb || !ow || !ob || !mg || !mb || !f1 || !f1b || !f2 || !f2b) { ok = false; break; }
+        std::vector<float> cat((size_t)3 * CC), cb((size_t)3 * C);
+        memcpy(cat.data(), qw, sizeof(float) * CC);
+        memcpy(cat.data() + CC, kw, sizeof(float) * CC);
+        memcpy(cat.data() + 2 * CC, vw, sizeof(float) * CC);
+        memcpy(cb.data(), qb, sizeof(float) * C);
+        memcpy(cb.data() + C, kb, sizeof(float) * C);
+        memcpy(cb.data() + 2 * C, vb, sizeof(float) * C);
+        ok = pack_ln_fold(o, cat.data(), cb.data(), ag, ab, 3 * C, C, {}, bw.qkv, bw.qkv_c1, bw.qkv_c2) && pack_conv(o, ow, ob, C, C, 1, bw.out) &&
+             pack_ln_fold(o, f1, f1b, mg, mb, F, C, {}, bw.fc1, bw.fc1_c1, bw.fc1_c2) && pack_conv(o, f2, f2b, C, F, 1, bw.fc2);
+    }
+    if (ok) {
+        h->post_g = vec("encoder.layer_norm.weight", C);
+        h->post_b = vec("encoder.layer_norm.bias", C);
+        ok = h->post_g && h->post_b;
+    }
+    if (!ok) {
+        std::string miss = T.missing;
+        delete h;
+        if (!miss.empty()) return fail(LDS_EMISSING, "w2v: %s", miss.c_str());
+        return fail(LDS_ENOMEM, "w2v weight upload failed");
+    }
+    *out = h;
+    return LDS_OK;
+}
+extern "C" void lds_w2v_destroy(lds_w2v* h) { delete h; }
+
+struct W2vWs {
+    int* slen;
+    int* nlen[kHubertLevels];      // device copies of the clips' sample counts and of their frame counts after conv0 .. conv6
+    float *ca, *cb;                // the feature extractor's two tensors: a level's LayerNorm output / its raw convolution
+    float2* lnp;                   // LayerNorm partials: the extractor's output, then the residual stream
+    float *xa, *xb, *qk, *v, *att, *big;
+};
+static void plan_w2v(const lds_w2v* h, Arena& A, int B, const int32_t* nb, W2vWs& w) {
+    const size_t D = h->cfg.conv_dim, C = h->cfg.n_state, F = h->cfg.n_ffn, T = nb[6], Bz = B;
+    w.slen = (int*)A.f(64);
+    for (int i = 0; i < kHubertLevels; ++i) w.nlen[i] = (int*)A.f(64);
+    w.ca = A.f(Bz * D * ((size_t)nb[0] + 2));
+    w.cb = A.f(Bz * D * ((size_t)nb[1] + 2));
+    w.lnp = (float2*)A.f(Bz * (std::max(D, C) / 32) * T * 2);
+    w.xa = A.f(Bz * C * (T + 2)); w.xb = A.f(Bz * C * (T + 2));
+    w.qk = A.f(Bz * 2 * C * (T + 2));
+    w.v = A.f(Bz * (C * ((T + 3) & ~(size_t)3) + 2048));
+    w.att = A.f(Bz * C * (T + 2));
+    w.big = A.f(Bz * F * (T + 2));
+    A.f(16384);      // tail slack: ragged last tiles read (masked) entries past a tensor's end
+}
+// the limits of one call: B clips in buffers of L samples; nb = the buffers' frame counts
+static int w2v_shape_check(const lds_w2v* h, int B, int64_t L, int32_t* nb) {
+    if (!h) return fail(LDS_EINVAL, "null handle");
+    if (B < 1 || B > 65535) return fail(LDS_EINVAL, "w2v: B %d outside 1 .. 65535", B);
+    if (L < 400 || L > ((int64_t)1 << 30)) return fail(LDS_EINVAL, "w2v: L %lld outside 400 .. 2^30 samples", (long long)L);
+    hubert_levels(L, 0, nb);
+    if (nb[6] > h->cfg.n_ctx) return fail(LDS_EINVAL, "w2v: %d frames exceed n_ctx %d", nb[6], h->cfg.n_ctx);
+    return LDS_OK;
+}
+extern "C" int lds_w2v_workspace_bytes(const lds_w2v* h, int B, int64_t L, size_t* out) {
+    if (!out) return fail(LDS_EINVAL, "null argument");
+    int32_t nb[kHubertLevels];
+    LDS_TRY(w2v_shape_check(h, B, L, nb));
+    Arena A(nullptr, 0);
+    W2vWs w;
+    plan_w2v(h, A, B, nb, w);
+    *out = A.used;
+    return LDS_OK;
+}
+
+// audio -> feat ([B][T][conv_dim]) or enc ([B][T][n_state]).  Every argument has been checked.
+static int w2v_run(lds_w2v* h, const float* audio, int64_t L, const int32_t* lens_host, const int32_t* nb, float* feat, float* enc, void* ws, size_t ws_bytes,
+                   int B, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    ProfChain chain;
+    Arena A(ws, ws_bytes);
+    W2vWs w;
+    plan_w2v(h, A, B, nb, w);
+    if (!A.ok) return fail(LDS_ENOMEM, "w2v workspace too small: need %zu", A.used);
+    const int D = h->cfg.conv_dim, C = h->cfg.n_state, T = nb[6];
+    const int* slen = nullptr;
+    const int* nlen[kHubertLevels] = {};
+    if (lens_host) {
+        int32_t lv[kHubertLevels][64];
+        for (int b = 0; b < B; ++b) {
+            int32_t one[kHubertLevels];
+            hubert_levels(lens_host[b], 0, one);
+            for (int i = 0; i < kHubertLevels; ++i) lv[i][b] = one[i];
+        }
+        LDS_TRY(whisper_upload(lens_host, B, w.slen, st));
+        slen = w.slen;
+        for (int i = 0; i < kHubertLevels; ++i) {
+            LDS_TRY(whisper_upload(lv[i], B, w.nlen[i], st));
+            nlen[i] = w.nlen[i];
+        }
+    }
+    TileBatchScope tb(0);      // tile rules judged at the nominal batch: a clip's units do not depend on the batch it is in
+    HIP_TRY(launch_w2v_conv0(audio, slen, L, h->w0, h->b0, h->ln_g[0], h->ln_b[0], 1e-5f, nlen[0], nb[0], D, w.ca, B, st));
+    for (int i = 1; i < kHubertLevels; ++i) {      // conv_i + bias (stride 2, no padding) into cb, GELU(LayerNorm(.)) back into ca
+        LensScope ls(nlen[i]);
+        DOpt o;
+        o.stride = 2; o.pad = 0;
+        LDS_TRY(run_dconv(h->conv[i - 1], w.ca, D, nullptr, 0, nb[i - 1], o, w.cb, B, st));
+        // the last level's partials serve the feature projection's folded layer_norm
+        HIP_TRY(launch_w2v_ln_act(w.cb, h->ln_g[i], h->ln_b[i], 1e-5f, w.ca, (i == kHubertLevels - 1 && enc) ? w.lnp : nullptr, nlen[i], B, D, nb[i], st));
+    }
+    const int* flen = nlen[kHubertLevels - 1];
+    if (feat) HIP_TRY(launch_hubert_store_frames(w.ca, feat, flen, B, D, T, st));
+    if (!enc) return LDS_OK;
+    LensScope ls(flen);
+    {
+        DOpt o;      // post_extract_proj(layer_norm(.))
+        o.ln_part = w.lnp; o.ln_np = D / 32; o.ln_c1 = h->fproj_c1; o.ln_c2 = h->fproj_c2;
+        LDS_TRY(run_dconv(h->fproj, w.ca, D, nullptr, 0, T, o, w.xa, B, st));
+    }
+    HIP_TRY(launch_hubert_posconv(w.xa, h->pos_w, h->pos_b, w.xb, flen, B, C, T, h->cfg.pos_kernel, h->cfg.pos_groups, st));
+    HIP_TRY(launch_w2v_lnpart(w.xb, w.lnp, flen, B, C, T, st));      // partials for the first block's self_attn_layer_norm
+    float* x = w.xb;
+    float* xn = w.xa;
+    for (const WhisperBlockW& bw : h->blocks) {
+        DOpt oq;      // q | k | v of self_attn_layer_norm(x)
+        oq.plain_from = 2 * C; oq.out2 = w.v; oq.vt_D = 64;
+        oq.ln_part = w.lnp; oq.ln_np = C / 32; oq.ln_c1 = bw.qkv_c1; oq.ln_c2 = bw.qkv_c2;
+        LDS_TRY(run_dconv(bw.qkv, x, C, nullptr, 0, T, oq, w.qk, B, st));
+        HIP_TRY(launch_attention_k4p(w.qk, w.v, w.att, B, C, T, h->cfg.n_head, st, 0, flen, 0));
+        DOpt oo;      // x + out_proj(.), partials for final_layer_norm
+        oo.res = x; oo.lnpart_out = w.lnp;
+        LDS_TRY(run_dconv(bw.out, w.att, C, nullptr, 0, T, oo, xn, B, st));
+        DOpt o1;      // gelu(fc1(final_layer_norm(.)))
+        o1.epi = EPI_GELU;
+        o1.ln_part = w.lnp; o1.ln_np = C / 32; o1.ln_c1 = bw.fc1_c1; o1.ln_c2 = bw.fc1_c2;
+        LDS_TRY(run_dconv(bw.fc1, xn, C, nullptr, 0, T, o1, w.big, B, st));
+        DOpt o2;      // + fc2(.), partials for the next block's self_attn_layer_norm / encoder.layer_norm
+        o2.res = xn; o2.lnpart_out = w.lnp;
+        LDS_TRY(run_dconv(bw.fc2, w.big, h->cfg.n_ffn, nullptr, 0, T, o2, x, B, st));
+    }
+    HIP_TRY(launch_whisper_ln_post(x, w.lnp, h->post_g, h->post_b, 1e-5f, enc, flen, B, C, T, st, 0));
+    return LDS_OK;
+}
+
+static int w2v_audio_check(const lds_w2v* h, const float* audio, const int32_t* lengths, const void* out, const void* ws, int B, int64_t L, int32_t* nb) {
+    if (!h || !audio || !out || !ws) return fail(LDS_EINVAL, "null argument");
+    LDS_TRY(w2v_shape_check(h, B, L, nb));
+    if (lengths) {
+        if (B > 64) return fail(LDS_EINVAL, "per-clip lengths: at most 64 clips per call (got %d)", B);
+        for (int b = 0; b < B; ++b)
+            if (lengths[b] < 400 || lengths[b] > L) return fail(LDS_EINVAL, "length[%d] = %d outside 400 .. %lld", b, lengths[b], (long long)L);
+    }
+    return LDS_OK;
+}
+extern "C" int lds_w2v_features(lds_w2v* h, const float* audio, const int32_t* lengths, float* out, void* ws, size_t ws_bytes, int B, int64_t L, void* stream) {
+    int32_t nb[kHubertLevels];
+    LDS_TRY(w2v_audio_check(h, audio, lengths, out, ws, B, L, nb));
+    return w2v_run(h, audio, L, lengths, nb, out, nullptr, ws, ws_bytes, B, stream);
+}
+extern "C" int lds_w2v_encode(lds_w2v* h, const float* audio, const int32_t* lengths, float* out, void* ws, size_t ws_bytes, int B, int64_t L, void* stream) {
+    int32_t nb[kHubertLevels];
+    LDS_TRY(w2v_audio_check(h, audio, lengths, out, ws, B, L, nb));
+    return w2v_run(h, audio, L, lengths, nb, nullptr, out, ws, ws_bytes, B, stream);
+}
+
+// ================================================================================================
 // Single-op test entry points
 // ================================================================================================
 extern "C" int lds_test_conv(const lds_conv_test* a, float* out, int B, void* stream) {
@@ -3673,4 +3921,53 @@ extern "C" int lds_test_voc_ups(const float* x, const float* w, const float* bia
     }
     HIP_TRY(hipStreamSynchronize(st));
     return rc;
+}
+
+// The wav2vec 2.0 encoder's own kernels alone (w2v.hip), plain tensors in and out; every pointer but the lengths is a device pointer.
+extern "C" int lds_test_w2v_conv0(const float* audio, const int32_t* lengths, const float* w, const float* bias, const float* gamma, const float* beta,
+                                  float eps, float* out, int B, int C, int64_t L, void* stream) {
+    if (!audio || !w || !bias || !gamma || !beta || !out || B < 1 || B > 64 || L < 10 || L > ((int64_t)1 << 30)) return fail(LDS_EINVAL, "bad argument");
+    hipStream_t st = (hipStream_t)stream;
+    TmpDev tmp;
+    const int N0 = (int)((L - 10) / 5 + 1);
+    float* ko = tmp.f((size_t)B * C * (N0 + 2));
+    int* dl = (int*)tmp.f(128);
+    if (!ko || !dl) return fail(LDS_ENOMEM, "alloc");
+    const int *slen = nullptr, *nlen = nullptr;
+    if (lengths) {
+        int32_t n0[64];
+        for (int b = 0; b < B; ++b) {
+            if (lengths[b] < 10 || lengths[b] > L) return fail(LDS_EINVAL, "length[%d] = %d outside 10 .. %lld", b, lengths[b], (long long)L);
+            n0[b] = (lengths[b] - 10) / 5 + 1;
+        }
+        LDS_TRY(whisper_upload(lengths, B, dl, st));
+        LDS_TRY(whisper_upload(n0, B, dl + 64, st));
+        slen = dl; nlen = dl + 64;
+    }
+    HIP_TRY(launch_w2v_conv0(audio, slen, L, w, bias, gamma, beta, eps, nlen, N0, C, ko, B, st));
+    HIP_TRY(launch_from_k4p(ko, out, B, C, N0, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return LDS_OK;
+}
+extern "C" int lds_test_w2v_ln_act(const float* x, const int32_t* n_frames, const float* gamma, const float* beta, float eps, float* out, float* part, int B,
+                                   int C, int T, void* stream) {
+    if (!x || !gamma || !beta || !out || B < 1 || B > 64 || T < 1 || C < 64 || C % 64) return fail(LDS_EINVAL, "bad argument");
+    hipStream_t st = (hipStream_t)stream;
+    TmpDev tmp;
+    float* kx = tmp.f((size_t)B * C * (T + 2));
+    float* ko = tmp.f((size_t)B * C * (T + 2));
+    int* dl = (int*)tmp.f(64);
+    if (!kx || !ko || !dl) return fail(LDS_ENOMEM, "alloc");
+    const int* nlen = nullptr;
+    if (n_frames) {
+        for (int b = 0; b < B; ++b)
+            if (n_frames[b] < 1 || n_frames[b] > T) return fail(LDS_EINVAL, "n_frames[%d] = %d outside 1 .. %d", b, n_frames[b], T);
+        LDS_TRY(whisper_upload(n_frames, B, dl, st));
+        nlen = dl;
+    }
+    HIP_TRY(launch_to_k4p(x, kx, B, C, T, C, 0, st));
+    HIP_TRY(launch_w2v_ln_act(kx, gamma, beta, eps, ko, (float2*)part, nlen, B, C, T, st));
+    HIP_TRY(launch_from_k4p(ko, out, B, C, T, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return LDS_OK;
 }

@@ -532,6 +532,140 @@ def hubert_fold_weight_norm(g, v):
     return np.asarray(g, dtype=np.float64).reshape(1, 1, -1) * v64 / n
 
 
+# ---- wav2vec 2.0 units encoder, layer-norm flavour (XLSR-53: reference tools/tools.py Audio2xlsr_53_56k) ------------------------------------
+# the fields of include/lds.h lds_w2v_cfg; n_ctx = the most frames of one call (30 s give 1499)
+XLSR_53_DIMS = dict(conv_dim=512, n_state=1024, n_head=16, n_layer=24, n_ffn=4096, pos_kernel=128, pos_groups=16, n_ctx=1500)
+W2V_MIN_SAMPLES = 400
+# checkpoint tensors that inference never reads (fairseq's pre-training heads; transformers' name of mask_emb)
+W2V_IGNORED_PREFIXES = ("mask_emb", "masked_spec_embed", "quantizer.", "project_q.", "final_proj.")
+
+
+def w2v_frames(n_samples):
+    """Frames of a clip of n_samples: HuBERT's level rule without padding (400 samples -> 1, 30 s -> 1499)"""
+    return hubert_level_frames(n_samples, 0)[-1]
+
+
+def w2v_param_shapes(cfg=None):
+    """fairseq's Wav2Vec2Model key -> shape for the tensors inference reads (the names lds_w2v_create looks up)"""
+    c = dict(XLSR_53_DIMS if cfg is None else cfg)
+    D, C, F, K, G = c["conv_dim"], c["n_state"], c["n_ffn"], c["pos_kernel"], c["pos_groups"]
+    d = OrderedDict()
+    for i in range(7):
+        p = f"feature_extractor.conv_layers.{i}."
+        d[p + "0.weight"] = (D, 1 if i == 0 else D, 10 if i == 0 else (3 if i <= 4 else 2))
+        d[p + "0.bias"] = (D,)
+        d[p + "2.1.weight"] = (D,)
+        d[p + "2.1.bias"] = (D,)
+    d["layer_norm.weight"] = (D,)
+    d["layer_norm.bias"] = (D,)
+    d["post_extract_proj.weight"] = (C, D)
+    d["post_extract_proj.bias"] = (C,)
+    d["encoder.pos_conv.0.bias"] = (C,)
+    d["encoder.pos_conv.0.weight_g"] = (1, 1, K)
+    d["encoder.pos_conv.0.weight_v"] = (C, C // G, K)
+    for l in range(c["n_layer"]):
+        p = f"encoder.layers.{l}."
+        for n in ("k_proj", "v_proj", "q_proj", "out_proj"):
+            d[p + f"self_attn.{n}.weight"] = (C, C)
+            d[p + f"self_attn.{n}.bias"] = (C,)
+        d[p + "self_attn_layer_norm.weight"] = (C,)
+        d[p + "self_attn_layer_norm.bias"] = (C,)
+        d[p + "fc1.weight"] = (F, C)
+        d[p + "fc1.bias"] = (F,)
+        d[p + "fc2.weight"] = (C, F)
+        d[p + "fc2.bias"] = (C,)
+        d[p + "final_layer_norm.weight"] = (C,)
+        d[p + "final_layer_norm.bias"] = (C,)
+    d["encoder.layer_norm.weight"] = (C,)
+    d["encoder.layer_norm.bias"] = (C,)
+    return d
+
+
+def w2v_key_to_transformers(k):
+    """fairseq name -> transformers.Wav2Vec2Model's state-dict name (one to one on w2v_param_shapes' keys and on mask_emb)"""
+    import re
+    m = re.match(r"feature_extractor\.conv_layers\.(\d+)\.(0|2\.1)\.(weight|bias)$", k)
+    if m:
+        return f"feature_extractor.conv_layers.{m.group(1)}.{'conv' if m.group(2) == '0' else 'layer_norm'}.{m.group(3)}"
+    if k == "mask_emb":
+        return "masked_spec_embed"
+    for a, b in (("layer_norm.", "feature_projection.layer_norm."), ("post_extract_proj.", "feature_projection.projection.")):
+        if k.startswith(a):
+            return b + k[len(a):]
+    fixed = {"encoder.pos_conv.0.bias": "encoder.pos_conv_embed.conv.bias",
+             "encoder.pos_conv.0.weight_g": "encoder.pos_conv_embed.conv.parametrizations.weight.original0",
+             "encoder.pos_conv.0.weight_v": "encoder.pos_conv_embed.conv.parametrizations.weight.original1"}
+    if k in fixed:
+        return fixed[k]
+    m = re.match(r"(encoder\.layers\.\d+\.)(.+)$", k)
+    if m:
+        rest = m.group(2)
+        for a, b in (("self_attn_layer_norm.", "layer_norm."), ("self_attn.", "attention."), ("fc1.", "feed_forward.intermediate_dense."),
+                     ("fc2.", "feed_forward.output_dense.")):
+            if rest.startswith(a):
+                return m.group(1) + b + rest[len(a):]
+        return k      # final_layer_norm keeps its name
+    return k          # encoder.layer_norm.*
+
+
+def w2v_keys_from_transformers(cfg=None):
+    """transformers name -> fairseq name, for every tensor of w2v_param_shapes(cfg) and masked_spec_embed"""
+    table = {w2v_key_to_transformers(k): k for k in w2v_param_shapes(cfg)}
+    table["masked_spec_embed"] = "mask_emb"
+    return table
+
+
+def w2v_init_state(cfg=None, seed=0, init_weights=None):
+    """Build-owned seeded weights in fairseq's names (no checkpoint ships), every stage at a scale of order 1 as in hubert_init_state, so
+    that no error hides behind the next LayerNorm: the feature extractor's convolutions get He's bound sqrt(6 / fan_in), the positional
+    convolution's per-tap norms g lie in [1.5, 3), q_proj and k_proj 1.7 times the default bound (attention logits of standard deviation
+    ~3); every LayerNorm gain in [0.8, 1.2) and bias in [-0.1, 0.1); the rest by lds.init_weights' role rules."""
+    if init_weights is None:
+        from . import init_weights
+    import numpy as np
+    shapes = w2v_param_shapes(cfg)
+    st = init_weights.init_state(shapes, seed)
+    for k, shp in shapes.items():
+        fan = int(np.prod(shp[1:])) if len(shp) > 1 else 1
+        if "layer_norm." in k or ".2.1." in k:
+            st[k] = init_weights.uniform(k, shp, seed, 0.8, 1.2) if k.endswith(".weight") else init_weights.uniform(k, shp, seed, -0.1, 0.1)
+        elif k.startswith("feature_extractor.conv_layers.") and k.endswith(".0.weight"):
+            b = float(np.sqrt(6.0 / fan))
+            st[k] = init_weights.uniform(k, shp, seed, -b, b)
+        elif k.endswith("weight_g"):
+            st[k] = init_weights.uniform(k, shp, seed, 1.5, 3.0)
+        elif k.endswith("q_proj.weight") or k.endswith("k_proj.weight"):
+            b = float(1.7 / np.sqrt(fan))
+            st[k] = init_weights.uniform(k, shp, seed, -b, b)
+    return {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in st.items()}
+
+
+def w2v_convert_state(state, cfg=None):
+    """A checkpoint's state dict in fairseq or transformers naming (an optional "module." / "w2v_encoder.w2v_model." / "wav2vec2." prefix
+    removed, the pre-training tensors dropped) -> the tensors of w2v_param_shapes(cfg) in fairseq naming.  A missing tensor is a KeyError
+    naming it; a wrong shape a ValueError."""
+    shapes = w2v_param_shapes(cfg)
+    back = w2v_keys_from_transformers(cfg)
+    got = {}
+    for k, v in state.items():
+        for pre in ("module.", "w2v_encoder.w2v_model.", "wav2vec2."):
+            if k.startswith(pre):
+                k = k[len(pre):]
+        if k.startswith(W2V_IGNORED_PREFIXES):
+            continue
+        k = k if k in shapes else back.get(k, k)
+        if k in shapes:
+            got[k] = v
+    out = OrderedDict()
+    for k, shp in shapes.items():
+        if k not in got:
+            raise KeyError(f"wav2vec 2.0 checkpoint lacks {k!r} (transformers name: {w2v_key_to_transformers(k)!r})")
+        if tuple(got[k].shape) != tuple(shp):
+            raise ValueError(f"wav2vec 2.0 checkpoint: {k!r} has shape {tuple(got[k].shape)}, expected {tuple(shp)}")
+        out[k] = got[k]
+    return out
+
+
 RESAMPLE_MAX_RATE, RESAMPLE_MAX_TAPS, RESAMPLE_MAX_BANK = 384000, 1024, 1 << 24      # include/lds.h lds_resample
 
 

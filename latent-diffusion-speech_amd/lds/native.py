@@ -108,6 +108,11 @@ lds_hubert_destroy               v:p
 lds_hubert_workspace_bytes       i:piqip
 lds_hubert_features              i:pppppziqip
 lds_hubert_encode                i:ppppiipziqip
+lds_w2v_create                   i:pipppp
+lds_w2v_destroy                  v:p
+lds_w2v_workspace_bytes          i:piqp
+lds_w2v_features                 i:pppppziqp
+lds_w2v_encode                   i:pppppziqp
 lds_lm_create                    i:pipppp
 lds_lm_destroy                   v:p
 lds_lm_workspace_bytes           i:piiip
@@ -178,6 +183,8 @@ lds_test_lm_beam_step            i:piiiiiifiippppppppppppppppp
 lds_test_dconv_pair              i:pppppppiiiiiipiiipppzp
 lds_test_dconv_ex                i:pppipzp
 lds_test_voc_ups                 i:pppiiiiiipppppzp
+lds_test_w2v_conv0               i:ppppppfpiiqp
+lds_test_w2v_ln_act              i:ppppfppiiip
 """
 SIGNATURES = dict(ln.split() for ln in (_PUBLIC + _TEST).splitlines() if ln)
 EXPORTS = [ln.split()[0] for ln in _PUBLIC.splitlines() if ln]
@@ -683,6 +690,67 @@ class Hubert(_Handle):
         check(lib().lds_hubert_encode(self.h, _dev(audio, torch.float32), _host(ln), _dev(out), nl, 1 if proj else 0, _dev(ws), ws.numel(), B, L, pad,
                                       _stream()))
         return out
+
+
+class W2vCfg(C.Structure):
+    _fields_ = [("conv_dim", C.c_int), ("n_state", C.c_int), ("n_head", C.c_int), ("n_layer", C.c_int), ("n_ffn", C.c_int),
+                ("pos_kernel", C.c_int), ("pos_groups", C.c_int), ("n_ctx", C.c_int)]
+
+
+class Wav2Vec2(_Handle):
+    """wav2vec 2.0 units encoder in its layer-norm flavour, XLSR-53 (lds_w2v_*): audio [B,L] at 16 kHz, taken as it is -> the feature
+    extractor's output [B,T,conv_dim] / the encoder's [B,T,n_state].  `state`: fairseq-named tensors (lds.arch.w2v_param_shapes).
+    `lengths`: every clip's own sample count (host ints, 400 .. L, at most 64 clips): each clip is encoded as if alone.  Every limit of
+    include/lds.h is checked here first (ValueError, before a device is touched)."""
+    KIND = "w2v"
+    FIELDS = ("conv_dim", "n_state", "n_head", "n_layer", "n_ffn", "pos_kernel", "pos_groups", "n_ctx")
+
+    def __init__(self, dims, state):
+        d = {k: int(dims[k]) for k in self.FIELDS}
+        self.check_dims(d)
+        self._create_weights(W2vCfg(*(d[k] for k in self.FIELDS)), state)
+        self.dims = d
+
+    @staticmethod
+    def check_dims(d):
+        Hubert.check_dims(dict(d, n_proj=64))      # (the limits are HuBERT's; there is no proj here)
+
+    @staticmethod
+    def frames(n_samples):
+        from . import arch
+        return arch.w2v_frames(n_samples)
+
+    @staticmethod
+    def lengths(lengths, B, L):
+        """per-clip sample counts -> host int32 [B] (include/lds.h: B <= 64, 400 .. L)"""
+        return _host_lengths(lengths, B, 400, L, 64, "units")
+
+    def workspace_bytes(self, B, L):
+        return _bytes("lds_w2v_workspace_bytes", self.h, B, L)
+
+    def _run(self, entry, width, audio, lengths, ws):
+        import torch
+        if audio.dim() != 2:
+            raise ValueError(f"Wav2Vec2: audio must be [B, L], got {list(audio.shape)}")
+        B, L = audio.shape
+        if B < 1:
+            raise ValueError("Wav2Vec2: an empty batch")
+        if L < 400:
+            raise ValueError(f"Wav2Vec2: clips need at least 400 samples (got {L})")
+        if self.frames(L) > self.dims["n_ctx"]:
+            raise ValueError(f"Wav2Vec2: {L} samples give {self.frames(L)} frames, more than n_ctx {self.dims['n_ctx']}")
+        ln = self.lengths(lengths, B, L) if lengths is not None else None
+        _dev(audio, None)
+        ws = ws if ws is not None else self.ws.get(self.workspace_bytes(B, L), audio.device)
+        out = torch.empty(B, self.frames(L), self.dims[width], dtype=torch.float32, device=audio.device)
+        check(getattr(lib(), entry)(self.h, _dev(audio, torch.float32), _host(ln), _dev(out), _dev(ws), ws.numel(), B, L, _stream()))
+        return out
+
+    def features(self, audio, lengths=None, ws=None):
+        return self._run("lds_w2v_features", "conv_dim", audio, lengths, ws)
+
+    def encode(self, audio, lengths=None, ws=None):
+        return self._run("lds_w2v_encode", "n_state", audio, lengths, ws)
 
 
 class Whisper(_Handle):

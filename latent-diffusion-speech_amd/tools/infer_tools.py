@@ -24,19 +24,21 @@ class DiffusionSVC:
         method does not accept; they are accepted and ignored here).  The reference builds its Units_Encoder here (infer_tools.py:31-38);
         this one only when `units_encoder_checkpoint` names the checkpoint of the encoder that args.data.encoder names: the Whisper
         encoder's (large-v3_encoder.pt; also when no encoder is named) or, for 'hubertsoft' / 'contentvec768l12', a HubertSoft state dict
-        (tools.tools.HubertUnits).  `resample` (keyword-only, not in the reference) goes to Units_Encoder: with True, encode_units
-        resamples audio of another rate; `encoder` (keyword-only) overrides the name in args.data.encoder."""
+        (tools.tools.HubertUnits), or for 'xlsr_53_56k' a wav2vec 2.0 state dict of plain tensors (tools.tools.Audio2xlsr_53_56k).
+        `resample` (keyword-only, not in the reference) goes to Units_Encoder: with True, encode_units resamples audio of another rate; `encoder` (keyword-only) overrides the name in args.data.encoder."""
         self.model_path = model_path
         self.model, self.vocoder, self.args = load_model_vocoder(model_path, device=self.device, loaded_vocoder=loaded_vocoder)
         from tools.tools import Volume_Extractor
         self.volume_extractor = Volume_Extractor(hop_size=512, block_size=self.args["data"]["block_size"],      # (reference infer_tools.py:39-43)
                                                  model_sampling_rate=self.args["data"]["sampling_rate"])
         if units_encoder_checkpoint is not None:
-            from tools.tools import HubertUnits, Units_Encoder, WhisperLargeV3
+            from tools.tools import Audio2xlsr_53_56k, HubertUnits, Units_Encoder, WhisperLargeV3
             data = getattr(self.args, "data", None)
             name = encoder if encoder is not None else getattr(data, "encoder", "whisper_large_v3")
             if name in HubertUnits.NAMES:
                 model = HubertUnits(name, device=self.device, checkpoint=units_encoder_checkpoint)
+            elif name == "xlsr_53_56k":
+                model = Audio2xlsr_53_56k(device=self.device, checkpoint=units_encoder_checkpoint)
             else:
                 model = WhisperLargeV3(device=self.device, checkpoint=units_encoder_checkpoint)
             self.units_encoder = Units_Encoder(name, getattr(data, "encoder_sample_rate", 16000),
@@ -105,11 +107,12 @@ class DiffusionSVC:
         """The host-side plan of infer_from_long_audio for the segments `ranges` = [(start_frame, begin, end)] of a recording at `sr`
         (tools.slicer.split_ranges): per segment its model frames n_s = int(len // hop) + 1, and the chunks: segment numbers sorted by
         length (stable), at most batch_size each.  ValueError naming the segment that exceeds the encoder's window.  The frame rule and
-        the window are the encoder's: Whisper's (L // 160 - 1) // 2 + 1 frames of n_audio_ctx, or a HuBERT encoder's L // 320 of its n_ctx."""
+        the window are the encoder's: Whisper's (L // 160 - 1) // 2 + 1 frames of n_audio_ctx, a HuBERT encoder's L // 320 of its n_ctx, or XLSR-53's
+        unpadded level rule (lds.arch.w2v_frames) of its n_ctx."""
         block_size, rate = self.args["data"]["block_size"], self.args["data"]["sampling_rate"]
         hop_size = block_size * sr / rate
         ue = self.units_encoder
-        enc = ue.model      # (tools.tools.WhisperLargeV3 or HubertUnits: frames_of, n_ctx, family)
+        enc = ue.model      # (tools.tools.WhisperLargeV3, HubertUnits or Audio2xlsr_53_56k: frames_of, n_ctx, family)
         n_frames = []
         for s, (start_frame, begin, end) in enumerate(ranges):
             ln = end - begin
