@@ -283,6 +283,46 @@ int  lds_w2v_features(lds_w2v* h, const float* audio, const int32_t* lengths, fl
 /* out dev [B][T][n_state] = the output of encoder.layer_norm */
 int  lds_w2v_encode(lds_w2v* h, const float* audio, const int32_t* lengths, float* out, void* ws, size_t ws_bytes, int B, int64_t L, void* stream);
 
+/* ---- units encoder: w2v-BERT 2.0 (reference tools/tools.py Wav2Vec2Bert: transformers' Wav2Vec2BertModel(**SeamlessM4TFeatureExtractor(audio,
+ *      sampling_rate = 16000)).last_hidden_state), audio -> units ------------------------------------------------------------------------
+ * Front end (SeamlessM4TFeatureExtractor.__call__ on one clip): the waveform times 2^15; n = 1 + (len - 400) / 160 frames of 400 samples, not
+ * centred; per frame mean removal, pre-emphasis 0.97, Povey window, 512-point power spectrum, n_mels Kaldi-scale mel triangles (20 Hz .. 8 kHz),
+ * floor 1.192092955078125e-07, natural log; per mel bin (x - mean) / sqrt(var(ddof = 1) + 1e-7) over the clip's own n frames; `stride` frames side by
+ * side per row: rows = ceil(n / stride) rows of n_mels * stride values of which valid = n / stride are unmasked.  With n odd (stride 2) the last
+ * row is the MASKED ROW: its second half is the extractor's padding (0) and its attention-mask entry is 0.
+ * Model (Wav2Vec2BertModel without adapter): LayerNorm + Linear (n_mels * stride -> n_state), masked rows set to 0; n_layer Conformer blocks:
+ * x += 0.5 ffn1(LN(x)) (Linear n_state -> n_ffn, swish, Linear back); x += attention(LN(x)) with n_head heads of 64, biases on q, k, v, out, scores
+ * (q.k + q.E[clamp(j - i, -left_max, right_max) + left_max]) / 8 with the layer's distance_embedding E, keys at and beyond `valid` excluded;
+ * x += conv_module(x): LayerNorm, masked rows -> 0, pointwise 1x1 to 2 n_state without bias, GLU, causal depthwise convolution of dw_kernel taps
+ * without bias, LayerNorm over the channels of each frame, swish, pointwise 1x1 without bias; x += 0.5 ffn2(LN(x)); x = final_layer_norm(x).
+ * The result has `rows` rows per clip, the masked row INCLUDED, as last_hidden_state has it; a caller who does not want it drops row `valid`
+ * when n is odd.  The masked row's padding never reaches another row.
+ * Tensor names are transformers': feature_projection.{layer_norm,projection}.*, encoder.layers.{l}.{ffn1_layer_norm,ffn1.intermediate_dense,
+ * ffn1.output_dense,self_attn_layer_norm,self_attn.linear_{q,k,v,out},conv_module.layer_norm,conv_module.depthwise_layer_norm,ffn2_layer_norm,
+ * ffn2.intermediate_dense,ffn2.output_dense,final_layer_norm}.{weight,bias}, .self_attn.distance_embedding.weight,
+ * .conv_module.{pointwise_conv1,depthwise_conv,pointwise_conv2}.weight; other names are ignored.  LDS_EMISSING names a missing tensor.
+ * Limits (LDS_EINVAL otherwise): n_mels 8 .. 128 and stride 1 .. 8 with n_mels * stride a multiple of 32 up to 1024; n_state a multiple of 64 in
+ * 64 .. 1024 = 64 n_head; n_ffn a multiple of 64; 1 <= n_layer <= 64; left_max + right_max + 1 <= 80; dw_kernel odd in 1 .. 31; rows <= n_ctx <= 1500;
+ * 0 < eps < 1; at most 64 clips per call; 560 <= L <= 2^30 (560 samples = two frames: one frame makes the reference's variance 0 / 0).
+ * audio: dev [B][L] fp32 at 16 kHz.  lengths: host int32 [B] (560 <= lengths[b] <= L) or NULL: clip b is audio[b, :lengths[b]] encoded alone.
+ * Nothing at or beyond lengths[b] is read; rows at and beyond rows_b of a result are zeros.  A clip's result does not depend on the other clips
+ * of the call.  The matrix products are exact fp32, the filter bank's DFT runs in double; no floating-point atomics: a repeat gives the same
+ * bits.  Nothing synchronises; a bad argument returns before anything is enqueued; a small workspace gives LDS_ENOMEM. */
+typedef struct lds_w2vbert lds_w2vbert;
+typedef struct lds_w2vbert_cfg { int n_mels, stride, n_state, n_head, n_ffn, n_layer, left_max, right_max, dw_kernel, n_ctx; float eps; } lds_w2vbert_cfg;
+int  lds_w2vbert_create(const lds_w2vbert_cfg* cfg, int n_tensors, const char* const* names, const float* const* host_ptrs, const int64_t* numel, lds_w2vbert** out);
+void lds_w2vbert_destroy(lds_w2vbert* h);
+/* one size for the three calls below; for encode_features with R rows pass L = 400 + 160 (stride R - 1) */
+int  lds_w2vbert_workspace_bytes(const lds_w2vbert* h, int B, int64_t L, size_t* out);
+/* out dev [B][Rmax][n_mels * stride] = SeamlessM4TFeatureExtractor's input_features (Rmax = the rows of L samples), zeros beyond rows_b */
+int  lds_w2vbert_fbank(lds_w2vbert* h, const float* audio, const int32_t* lengths, float* out, void* ws, size_t ws_bytes, int B, int64_t L, void* stream);
+/* feats dev [B][R][n_mels * stride] (input_features), n_frames host int32 [B] (the clips' frame counts n, max(2, stride) .. stride R) or NULL
+ * (= stride R) -> out dev [B][R][n_state] = Wav2Vec2BertModel(input_features, attention_mask).last_hidden_state; feats rows at and beyond n / stride
+ * are not read */
+int  lds_w2vbert_encode_features(lds_w2vbert* h, const float* feats, const int32_t* n_frames, float* out, void* ws, size_t ws_bytes, int B, int R, void* stream);
+/* out dev [B][Rmax][n_state]: the two calls above in one */
+int  lds_w2vbert_encode(lds_w2vbert* h, const float* audio, const int32_t* lengths, float* out, void* ws, size_t ws_bytes, int B, int64_t L, void* stream);
+
 /* ---- text2semantic: RoFormer encoder prefill + cached autoregressive decode (reference text2semantic/roformer/roformer.py:59-255
  *      over HF transformers RoFormerModel / RoFormerForCausalLM + GenerationMixin; called from 22_infer_tts.py:76-98) ------------- */
 typedef struct lds_lm lds_lm;

@@ -187,6 +187,22 @@ int lds_test_w2v_conv0(const float* audio, const int32_t* lengths, const float* 
 int lds_test_w2v_ln_act(const float* x, const int32_t* n_frames, const float* gamma, const float* beta, float eps, float* out, float* part, int B, int C,
                         int T, void* stream);
 
+/* The w2v-BERT 2.0 encoder's own kernels alone (csrc/w2vbert.hip, csrc/attention_k4p.hip); every pointer but the row / sample counts is a
+ * device pointer, B <= 64.
+ * w2vbert_fbank: audio [B][L] -> out [B][R][160] = SeamlessM4TFeatureExtractor's input_features (80 mel bins, stride 2), R = the rows of L samples;
+ *   lengths (host int32 [B] or NULL): the clips' sample counts (560 .. L), zeros beyond a clip's rows.
+ * w2vbert_attention: qkv [B][3C][T] (q, k, v; heads of 64), E [left + right + 1][64] -> out [B][C][T] = softmax((q.k + q.E[clamp(j - i, -left, right)
+ *   + left]) / 8) v; q_rows / k_rows (host int32 [B], both or neither): the clip's queries (zeros beyond) and keys, 1 <= k_rows[b] <= q_rows[b] <= T.
+ *   q and k may hold anything at and beyond q_rows[b]; v must be finite there (in the encoder its producer writes zeros).
+ * w2vbert_dwconv: x [B][C][T], w [C][K] -> out [B][C][T] = swish(LayerNorm over the channels(sum_k w[c][k] x[c][t - (K - 1) + k])); in_rows / out_rows
+ *   (host int32 [B], both or neither): input frames at and beyond in_rows[b] read as zeros, output frames at and beyond out_rows[b] are zeros,
+ *   1 <= in_rows[b] <= out_rows[b] <= T.  C a multiple of 64 up to 1024, K <= 31. */
+int lds_test_w2vbert_fbank(const float* audio, const int32_t* lengths, float* out, int B, int64_t L, void* stream);
+int lds_test_w2vbert_attention(const float* qkv, const float* E, const int32_t* q_rows, const int32_t* k_rows, float* out, int B, int C, int T, int heads,
+                               int left, int right, void* stream);
+int lds_test_w2vbert_dwconv(const float* x, const float* w, const float* gamma, const float* beta, float eps, const int32_t* in_rows, const int32_t* out_rows,
+                            float* out, int B, int C, int T, int K, void* stream);
+
 /* ---- debugging aids (tests/test_gpu_poison.py, tools/diag_trace.py) ----------------------------------------------------------
  * lds_debug_fill_u32: every 32-bit word of a device buffer = pattern.  Tests fill a caller workspace with NaN patterns (0x7fc07fc0 is a NaN
  * as fp32 and as two fp16 / bf16 halves) before a call: a kernel that reads a slot no kernel of THAT call wrote turns it into a NaN (or, behind

@@ -421,6 +421,243 @@ hipError_t launch_attention_k4p(const float* qk, const float* vt, float* out, in
 hipError_t launch_attention_k4p_out_bf3(const float* qk, const float* vt, void* out, int B, int C, int T, int heads, hipStream_t s, int fmt, int tile_batch, const int* lens, int lvl) {
     return attention_any(qk, vt, (float*)out, B, C, T, heads, fmt == FMT_F16X2 ? 2 : 1, fmt == FMT_F16X2, tile_batch, s, lens, lvl);
 }
+// ---- relative-key attention (the w2v-BERT 2.0 Conformer's self-attention, transformers Wav2Vec2BertSelfAttention with
+// position_embeddings_type "relative_key") -----------------------------------------------------------------------------------------------
+// The kernel above at D = 64, exact fp32, K4P output, as a kernel of its own so that none of the instantiations above changes:
+//   * score(i, j) = (q_i . k_j + q_i . E[clamp(j - i, -left, right) + left]) / 8.  The second term comes from the table relp
+//     [B][heads][Tbuf][kW2vbertRelStride] that w2vbert_relpos wrote in the scores' own unit (log2(e) / 8 folded in).  The clamp makes it one
+//     value per query outside the band j - i in (-left, right): a 32-key x 32-query tile wholly left / right of the band adds the query's
+//     entry 0 / left + right (two registers, loaded once); only the few tiles that meet the band gather 16 entries per lane from the table.
+//   * the queries are the clip's qlens[b] rows, the keys its first klens[b] <= qlens[b] rows (the masked last row of a clip with an odd
+//     frame count is a query and no key).
+// The tile choice depends on Tbuf and the head count only, never on the batch or a clip's own length.
+// MAINTENANCE: the body below is attention_k4p_kernel's (D = 64, F16 = false, no out_bf3 store, no KS = 4 "resident" path); a fix to the
+// DMA ring, the soft-max or the P.V product there belongs here too.  What differs, and only this:
+//   (1) Tq / Tk: two lengths instead of T (the query load and the output's `live` use Tq; nt, the `kbase >= Tk` break and the key mask use Tk);
+//   (2) rp / pL / pR and the block "the relative-key term" between the QK MFMAs' V-operand fetch and the key mask;
+//   (3) the KS = 2 join tests a share's m == -inf explicitly (a share that saw no key, possible here when Tk <= 32), instead of relying
+//       on exp2(-inf - m).
+template <int NW, int NST, int KS>
+__global__ void __launch_bounds__(NW * 64) attention_k4p_rel_kernel(const float* __restrict__ qk, const float* __restrict__ vt, const float* __restrict__ relp,
+                                                                    float* __restrict__ out, int C, int Tbuf, float scale2, const int* __restrict__ qlens,
+                                                                    const int* __restrict__ klens, int left, int right) {
+    constexpr int D = 64;
+    using Cfg = AttCfg<D, NW, NST, KS>;
+    constexpr int NWQ = NW / KS;
+    constexpr int KB = Cfg::KB, DQ = Cfg::DQ, DT = Cfg::DT, KPW = Cfg::KPW, VPW = Cfg::VPW, STAGE = Cfg::STAGE, PER_TILE = Cfg::PER_TILE;
+    static_assert(KS == 1 || KS == 2, "no latency-mode variant");
+    extern __shared__ __attribute__((aligned(16))) float smem[];      // NST x { K [row][key][4] ; V [keyquad][d][4] }
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int c = lane & 31, h = lane >> 5;
+    const int gx = gridDim.x, gy = gridDim.y, total = gx * gy * gridDim.z;
+    const int id = (blockIdx.z * gy + blockIdx.y) * gx + blockIdx.x;
+    const int per = total >> 3, rem = total & 7, xcd = id & 7;
+    const int Lid = xcd * per + (xcd < rem ? xcd : rem) + (id >> 3);
+    const int qblk = Lid % gx, hd = (Lid / gx) % gy, b = Lid / (gx * gy);
+    const int qw = wave % NWQ, ks = wave / NWQ;
+    const int q0 = qblk * (NWQ * 32) + qw * 32;      // first query of this wave
+    const int tq = q0 + c;
+    const int Tq = qlens ? (qlens[b] < Tbuf ? qlens[b] : Tbuf) : Tbuf;
+    const int Tk = klens ? (klens[b] < Tq ? klens[b] : Tq) : Tq;
+    const int Tp = Tbuf + 2, T4 = (Tbuf + 3) & ~3;
+    const float* qb = qk + ((long long)b * 2 * C + (long long)hd * D) * Tp;
+
+    f32x4 qv[DQ];
+#pragma unroll
+    for (int kq = 0; kq < DQ; ++kq) {
+        qv[kq] = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (tq < Tq) qv[kq] = *reinterpret_cast<const f32x4*>(qb + ((long long)(kq * 2 + h) * Tp + tq + 1) * 4);
+    }
+    // this query's row of the table (a query beyond the buffer reads the last row: a valid address, its result is never stored)
+    const float* rp = relp + (((long long)b * gy + hd) * Tbuf + (tq < Tbuf ? tq : Tbuf - 1)) * kW2vbertRelStride;
+    const float pL = rp[0], pR = rp[left + right];
+
+    const __amdgpu_buffer_rsrc_t rk =
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(qk + ((long long)b * 2 * C + C + (long long)hd * D) * Tp), 0, D * Tp * 4, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rv =
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(vt + ((long long)b * C + (long long)hd * D) * T4), 0, D * T4 * 4, 0x00020000);
+    int koff[KPW], voff[VPW];
+#pragma unroll
+    for (int i = 0; i < KPW; ++i) koff[i] = (((wave + NW * i) * Tp) + lane + 1) * 16;
+#pragma unroll
+    for (int i = 0; i < VPW; ++i) voff[i] = ((wave + NW * i) * 64 + lane) * 16;
+    const int nt = (qblk * (NWQ * 32) >= Tq) ? 0 : (Tk + KB - 1) / KB;
+    for (int t = 0; t < NST - 1 && t < nt; ++t) att_issue_tile<D, NW, KPW, VPW>(rk, rv, koff, voff, wave, t, smem + t * STAGE);
+#pragma unroll
+    for (int kq = 0; kq < DQ; ++kq) qv[kq] *= scale2;
+
+    f32x16 o[DT];
+#pragma unroll
+    for (int i = 0; i < DT; ++i)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) o[i][r] = 0.f;
+    float m_run = -INFINITY, l_run = 0.f;
+
+    int sc = 0, sn = NST - 1;
+    for (int kt = 0; kt < nt; ++kt) {
+        const int younger = (nt - 1 - kt < NST - 2) ? (nt - 1 - kt) : (NST - 2);
+        att_wait_younger<NST - 2, PER_TILE>(younger);
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+        if (kt + NST - 1 < nt) att_issue_tile<D, NW, KPW, VPW>(rk, rv, koff, voff, wave, kt + NST - 1, smem + sn * STAGE);
+        const float* Kc = smem + sc * STAGE;
+        const float* Vc = Kc + KB * D;
+        const int h0 = (KS == 1) ? 0 : ks;
+        const int h1 = (KS == 1) ? KB / 32 : h0 + 1;
+#pragma unroll 1
+        for (int half = h0; half < h1; ++half) {
+            const int kbase = kt * KB + half * 32;
+            if (kbase >= Tk) break;
+            f32x4 ka[DQ], va[4][DT];
+#pragma unroll
+            for (int kq = 0; kq < DQ; ++kq) ka[kq] = *reinterpret_cast<const f32x4*>(Kc + ((kq * 2 + h) * KB + half * 32 + c) * 4);
+            __builtin_amdgcn_sched_barrier(0);
+            f32x16 s;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) s[r] = 0.f;
+#pragma unroll
+            for (int kq = 0; kq < DQ; ++kq)
+#pragma unroll
+                for (int jj = 0; jj < 4; ++jj) s = __builtin_amdgcn_mfma_f32_32x32x2f32(ka[kq][jj], qv[kq][jj], s, 0, 0, 0);
+#pragma unroll
+            for (int g = 0; g < 4; ++g)
+#pragma unroll
+                for (int i = 0; i < DT; ++i) va[g][i] = *reinterpret_cast<const f32x4*>(Vc + ((half * 8 + 2 * g + h) * D + i * 32 + c) * 4);
+            __builtin_amdgcn_sched_barrier(0);
+            // the relative-key term (wave-uniform choice: j - i spans [kbase - q0 - 31, kbase + 31 - q0] over the tile)
+            if (kbase - q0 - 31 >= right) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) s[r] += pR;
+            } else if (kbase + 31 - q0 <= -left) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) s[r] += pL;
+            } else {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    int d = kbase + (r & 3) + 8 * (r >> 2) + 4 * h - tq;
+                    d = d < -left ? -left : (d > right ? right : d);
+                    s[r] += rp[d + left];
+                }
+            }
+            if (kbase + 32 > Tk) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r)
+                    if (kbase + (r & 3) + 8 * (r >> 2) + 4 * h >= Tk) s[r] = -INFINITY;
+            }
+            float mt = max3(max3(max3(s[0], s[1], s[2]), max3(s[3], s[4], s[5]), max3(s[6], s[7], s[8])),
+                            max3(max3(s[9], s[10], s[11]), max3(s[12], s[13], s[14]), s[15]), m_run);
+            {
+                const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(mt), __float_as_uint(mt), false, false);
+                mt = max3(mt, __uint_as_float(sw[0]), __uint_as_float(sw[1]));
+            }
+            const float alpha = __builtin_amdgcn_exp2f(m_run - mt);
+            m_run = mt;
+            const f32x2 mm = {mt, mt}, aa = {alpha, alpha};
+            f32x2 lsum = {0.f, 0.f};
+#pragma unroll
+            for (int r = 0; r < 16; r += 2) {
+                const f32x2 d = f32x2{s[r], s[r + 1]} - mm;
+                s[r] = __builtin_amdgcn_exp2f(d[0]);
+                s[r + 1] = __builtin_amdgcn_exp2f(d[1]);
+                lsum += f32x2{s[r], s[r + 1]};
+            }
+            l_run = fmaf(l_run, alpha, lsum[0] + lsum[1]);
+#pragma unroll
+            for (int i = 0; i < DT; ++i)
+#pragma unroll
+                for (int r = 0; r < 16; r += 2) {
+                    const f32x2 t = f32x2{o[i][r], o[i][r + 1]} * aa;
+                    o[i][r] = t[0]; o[i][r + 1] = t[1];
+                }
+#pragma unroll
+            for (int g = 0; g < 4; ++g)
+#pragma unroll
+                for (int i = 0; i < DT; ++i)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) o[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(va[g][i][e], s[4 * g + e], o[i], 0, 0, 0);
+        }
+        sc = (sc + 1 == NST) ? 0 : sc + 1;
+        sn = (sn + 1 == NST) ? 0 : sn + 1;
+    }
+    if constexpr (KS == 2) {
+        __syncthreads();
+        constexpr int RED = (2 + 16 * DT) * 64;
+        if (ks >= 1) {
+            float* red = smem + qw * RED + lane;
+            red[0] = m_run; red[64] = l_run;
+#pragma unroll
+            for (int i = 0; i < DT; ++i)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) red[(2 + i * 16 + r) * 64] = o[i][r];
+        }
+        __syncthreads();
+        if (ks >= 1) return;
+        const float* red = smem + qw * RED + lane;
+        const float m1 = red[0], l1 = red[64];
+        const float m = fmaxf(m_run, m1);
+        // (a share that saw no key carries m = -inf, l = 0: its factor is exp2(-inf) = 0 unless both are empty, which a live query never is)
+        const float a0 = (m_run == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f(m_run - m), a1 = (m1 == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f(m1 - m);
+        l_run = l_run * a0 + l1 * a1;
+#pragma unroll
+        for (int i = 0; i < DT; ++i)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) o[i][r] = o[i][r] * a0 + red[(2 + i * 16 + r) * 64] * a1;
+    }
+    float l;
+    {
+        const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(l_run), __float_as_uint(l_run), false, false);
+        l = __uint_as_float(sw[0]) + __uint_as_float(sw[1]);
+    }
+    if (tq < Tbuf) {
+        const bool live = tq < Tq;
+        const float rl = 1.0f / l;
+        float* ob = out + (long long)b * C * Tp;
+#pragma unroll
+        for (int i = 0; i < DT; ++i)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const int q = (hd * D + i * 32) / 8 + g;
+#pragma unroll
+                for (int hh = 0; hh < 2; ++hh) {
+                    const long long off = ((long long)(q * 2 + hh) * Tp + tq + 1) * 4 + 2 * h;
+                    k4p_store_wt(ob + off, live ? f32x2{o[i][4 * g + hh] * rl, o[i][4 * g + 2 + hh] * rl} : f32x2{0.f, 0.f});
+                    if (tq == 0) *reinterpret_cast<f32x2*>(ob + off - 4) = f32x2{0.f, 0.f};
+                    if (tq == Tbuf - 1) *reinterpret_cast<f32x2*>(ob + off + 4) = f32x2{0.f, 0.f};
+                }
+            }
+    }
+}
+
+template <int NW, int NST, int KS>
+static hipError_t launch_rel_cfg(const float* qk, const float* vt, const float* relp, float* out, int B, int C, int T, int heads, const int* qlens,
+                                 const int* klens, int left, int right, hipStream_t s) {
+    using Cfg = AttCfg<64, NW, NST, KS>;
+    auto kern = attention_k4p_rel_kernel<NW, NST, KS>;
+    if (Cfg::LDS_BYTES > 48 * 1024) {
+        static std::atomic<unsigned long long> attr_done{0};
+        hipError_t e = ensure_max_dynamic_lds(reinterpret_cast<const void*>(kern), attr_done);
+        if (e != hipSuccess) return e;
+    }
+    constexpr int QPB = NW / KS * 32;
+    const float scale = 1.4426950408889634f / 8.0f;      // log2(e) / sqrt(64)
+    hipEvent_t e0, e1;
+    const dim3 grid((T + QPB - 1) / QPB, heads, B);
+    if (prof_attach_events(&e0, &e1)) hipExtLaunchKernelGGL(kern, grid, dim3(NW * 64), Cfg::LDS_BYTES, s, e0, e1, 0, qk, vt, relp, out, C, T, scale, qlens, klens, left, right);
+    else hipLaunchKernelGGL(kern, grid, dim3(NW * 64), Cfg::LDS_BYTES, s, qk, vt, relp, out, C, T, scale, qlens, klens, left, right);
+    return hipGetLastError();
+}
+
+hipError_t launch_attention_k4p_rel(const float* qk, const float* vt, const float* relp, float* out, int B, int C, int T, int heads, const int* qlens,
+                                    const int* klens, int left, int right, hipStream_t s) {
+    if (B <= 0 || heads < 1 || C != heads * 64 || T <= 0 || left < 0 || right < 0 || left + right + 1 > kW2vbertRelStride) return hipErrorInvalidValue;
+    ProfScope ps(s, "attention_rel", 4.0 * B * (double)T * T * C, 4.0 * 4.0 * B * C * T, true);
+    // launch_dk's rule at the nominal batch of 16: 128 queries per workgroup when that gives every CU two workgroups, else 64 queries with
+    // each tile's keys split over two wave groups, a single 32-query wave for the shortest buffers
+    if ((long long)((T + 127) / 128) * heads * 16 >= 512) return launch_rel_cfg<4, 2, 1>(qk, vt, relp, out, B, C, T, heads, qlens, klens, left, right, s);
+    if (T > 32) return launch_rel_cfg<4, 2, 2>(qk, vt, relp, out, B, C, T, heads, qlens, klens, left, right, s);
+    return launch_rel_cfg<1, 2, 1>(qk, vt, relp, out, B, C, T, heads, qlens, klens, left, right, s);
+}
+
 // test entry: K4P fp32 in and out, the products on the fp16 pipe
 hipError_t launch_attention_k4p_f16math(const float* qk, const float* vt, float* out, int B, int C, int T, int heads, hipStream_t s, int tile_batch) {
     return attention_any(qk, vt, out, B, C, T, heads, 0, true, tile_batch, s);

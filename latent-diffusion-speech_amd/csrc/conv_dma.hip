@@ -92,7 +92,7 @@ struct DmaCfg {
 };
 
 // GNF: the GroupNorm fold of DmaConvArgs::gnf_part (its own instantiations: the other launches carry none of its registers)
-template <int BM, int BN, int KT, int STRIDE, bool UPS, int BK, int NST, int DIL = 1, bool VOC = false, bool GNF = false, bool GELU = false>
+template <int BM, int BN, int KT, int STRIDE, bool UPS, int BK, int NST, int DIL = 1, bool VOC = false, bool GNF = false, bool GELU = false, int ACT2 = 0>
 struct DmaKernel {
     using Cfg = DmaCfg<BM, BN, KT, STRIDE, UPS, BK, NST, DIL>;
     static constexpr int TM = Cfg::TM, TN = Cfg::TN, KR = Cfg::KR, XW = Cfg::XW, WPW = Cfg::WPW, RPW = Cfg::RPW, NXI = Cfg::NXI;
@@ -459,8 +459,20 @@ struct DmaKernel {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const float g = acc[0][TM - 1][j][r];
-                    acc[0][0][j][r] *= 0.5f * g * (1.0f + erf_fast(g * 0.70710678118654752440f));
+                    if constexpr (ACT2 == 2) acc[0][0][j][r] *= 1.0f / (1.0f + expf(-g));      // GLU: value * sigmoid(gate) (the Conformer's pointwise_conv1)
+                    else acc[0][0][j][r] *= 0.5f * g * (1.0f + erf_fast(g * 0.70710678118654752440f));
                 }
+        }
+        if constexpr (ACT2 == 1) {      // swish (the Conformer's feed-forwards): instantiations of its own, as for GELU below
+#pragma unroll
+            for (int i = 0; i < TM; ++i)
+#pragma unroll
+                for (int j = 0; j < TN; ++j)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const float v = acc[0][i][j][r];
+                        acc[0][i][j][r] = v / (1.0f + expf(-v));
+                    }
         }
         if constexpr (GELU) {      // plain GELU, exact form (the Whisper encoder's conv1 / conv2 / mlp.0, reference encoder/whisper/model.py:96,122-123):
                                    // instantiations of its own (launch_conv_dma), so that no other launch's code changes
@@ -755,7 +767,7 @@ struct DmaKernel {
     }
 
     __device__ __forceinline__ void epilogue() {
-        const bool geglu = (p.epi == EPI_GEGLU) && (TM == 2);
+        const bool geglu = (p.epi == EPI_GEGLU || (ACT2 == 2 && p.epi == EPI_GLU)) && (TM == 2);
         if constexpr (SPLIT) {
             if (!join_halves()) return;
         }
@@ -821,11 +833,11 @@ struct DmaKernel {
     }
 };
 
-template <int BM, int BN, int KT, int STRIDE, bool UPS, int BK, int NST, int DIL = 1, bool VOC = false, bool GNF = false, bool GELU = false>
+template <int BM, int BN, int KT, int STRIDE, bool UPS, int BK, int NST, int DIL = 1, bool VOC = false, bool GNF = false, bool GELU = false, int ACT2 = 0>
 // (the polyphase upsampler's scatter epilogue needs more than the 128 registers of 4 workgroups per CU: 2 per CU, no spills)
 __global__ void __launch_bounds__(256, ((VOC && KT == 2) ? 2 : DmaCfg<BM, BN, KT, STRIDE, UPS, BK, NST, DIL>::OCC)) conv_dma_kernel(const DmaConvArgs p) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    DmaKernel<BM, BN, KT, STRIDE, UPS, BK, NST, DIL, VOC, GNF, GELU> k(p, smem);
+    DmaKernel<BM, BN, KT, STRIDE, UPS, BK, NST, DIL, VOC, GNF, GELU, ACT2> k(p, smem);
     k.setup();
     // ragged batch: a tile that lies wholly beyond its utterance's length has nothing to reduce -- the epilogue writes its zeros (what it
     // computes from the untouched accumulators never reaches memory: masked columns are stored as literal zeros)
@@ -873,22 +885,22 @@ __global__ void __launch_bounds__(256, (PairCfg<BM, BN, BK3, BK1, NST>::OCC)) co
 static thread_local char g_dcfg[96] = "";
 const char* conv_dma_last_config() { return g_dcfg; }
 
-template <int BM, int BN, int KT, int STRIDE, bool UPS, int BK, int NST, int DIL = 1, bool VOC = false, bool GNF = false, bool GELU = false>
+template <int BM, int BN, int KT, int STRIDE, bool UPS, int BK, int NST, int DIL = 1, bool VOC = false, bool GNF = false, bool GELU = false, int ACT2 = 0>
 static hipError_t launch_dma_cfg(const DmaConvArgs& a, hipStream_t s) {
     using Cfg = DmaCfg<BM, BN, KT, STRIDE, UPS, BK, NST, DIL>;
-    if (GNF != (a.gnf_part != nullptr) || GELU != (a.epi == EPI_GELU)) return hipErrorInvalidValue;
+    if (GNF != (a.gnf_part != nullptr) || GELU != (a.epi == EPI_GELU) || (ACT2 == 1) != (a.epi == EPI_SWISH) || (ACT2 == 2) != (a.epi == EPI_GLU)) return hipErrorInvalidValue;
     const size_t lds_bytes = Cfg::LDS_BYTES + (GNF ? (BM + 32) * sizeof(float) : 0);      // the fold's row constants and group statistics sit behind the ring
     const int nN = (a.To + BN - 1) / BN;
     const int S = a.ksplit > 1 ? a.ksplit : 1;
     if (S > 1 && (Cfg::TM * Cfg::TN > 2 || VOC || (a.Ci / BK) % S)) return hipErrorInvalidValue;
     dim3 grid((a.Mp / BM) * nN, a.B * S);
-    auto kern = conv_dma_kernel<BM, BN, KT, STRIDE, UPS, BK, NST, DIL, VOC, GNF, GELU>;
+    auto kern = conv_dma_kernel<BM, BN, KT, STRIDE, UPS, BK, NST, DIL, VOC, GNF, GELU, ACT2>;
     if (lds_bytes > 48 * 1024) {
         static std::atomic<unsigned long long> attr_done{0};
         hipError_t e = ensure_max_dynamic_lds(reinterpret_cast<const void*>(kern), attr_done);
         if (e != hipSuccess) return e;
     }
-    const char* gtag = GNF ? " GNF" : GELU ? " GELU" : "";
+    const char* gtag = GNF ? " GNF" : GELU ? " GELU" : ACT2 == 1 ? " SWISH" : ACT2 == 2 ? " GLU" : "";
     if (!VOC && S > 1) snprintf(g_dcfg, sizeof(g_dcfg), "BM%d BN%d KT%d S%d U%d BK%d NST%d KS%d%s grid %ux%u lds %zu", BM, BN, KT, STRIDE, (int)UPS, BK, NST, S, gtag, grid.x, grid.y, lds_bytes);
     else if (!VOC) snprintf(g_dcfg, sizeof(g_dcfg), "BM%d BN%d KT%d S%d U%d BK%d NST%d%s grid %ux%u lds %zu", BM, BN, KT, STRIDE, (int)UPS, BK, NST, gtag, grid.x, grid.y, lds_bytes);
     else snprintf(g_dcfg, sizeof(g_dcfg), "BM%d BN%d KT%d S%d U%d BK%d NST%d D%d grid %ux%u lds %zu", BM, BN, KT, STRIDE, (int)UPS, BK, NST, DIL, grid.x, grid.y, Cfg::LDS_BYTES);
@@ -1065,8 +1077,14 @@ hipError_t launch_conv_dma(const DmaConvArgs& a_, int cfg, hipStream_t s) {
     if (a.KT != 1 && a.KT != 3 && !(a.KT == 2 && a.stride == 2 && (a.epi == EPI_GELU || a.epi == EPI_NONE))) return hipErrorInvalidValue;      // (k 2: HuBERT's / wav2vec 2.0's conv5 / conv6)
     const bool k32 = (a.Ci % 32 == 0) && (a.C1 % 32 == 0), k64 = (a.Ci % 64 == 0) && (a.C1 % 64 == 0);
     int bm, bn, bk, nst;
-    dma_pick(a, cfg, bm, bn, bk, nst);
-    if (a.epi == EPI_GEGLU && bm != 128) return hipErrorInvalidValue;
+    if (a.epi == EPI_GLU) {      // the tile rules of EPI_GEGLU (value and gate rows interleaved the same way)
+        DmaConvArgs t = a;
+        t.epi = EPI_GEGLU;
+        dma_pick(t, cfg, bm, bn, bk, nst);
+    } else {
+        dma_pick(a, cfg, bm, bn, bk, nst);
+    }
+    if ((a.epi == EPI_GEGLU || a.epi == EPI_GLU) && bm != 128) return hipErrorInvalidValue;
     if (a.Mp % bm) return hipErrorInvalidValue;
     if ((bk == 64 && !k64) || (bk == 32 && !k32)) bk = 16;
     if (a.gnf_part) {
@@ -1083,6 +1101,22 @@ hipError_t launch_conv_dma(const DmaConvArgs& a_, int cfg, hipStream_t s) {
         GCASE(32, 64, 32, 2); GCASE(32, 64, 64, 2); GCASE(64, 64, 32, 2); GCASE(64, 64, 16, 3); GCASE(128, 64, 32, 2); GCASE(128, 64, 16, 3);
 #undef GCASE
         return hipErrorInvalidValue;
+    }
+    if (a.epi == EPI_SWISH || a.epi == EPI_GLU) {
+        // The Conformer's epilogues (w2v-BERT 2.0): instantiations of their own, so that the kernels of every other launch are compiled as before.
+        // 1x1, stride 1, K4P output only.  Swish on EPI_GELU's tiles; GLU on EPI_GEGLU's (128 output rows = 64 value + 64 gate rows per workgroup).
+        if (a.KT != 1 || a.stride != 1 || a.ups || a.plain_from < a.Cout || a.out_plain || a.gnf_part) return hipErrorInvalidValue;
+#define XCASE(BM, BN, BK, NS, ACT) return launch_dma_cfg<BM, BN, 1, 1, false, BK, NS, 1, false, false, false, ACT>(a, s)
+        if (a.epi == EPI_SWISH) {
+            if (bm == 128 && k32) XCASE(128, 64, 32, 2, 1);
+            if (k32) XCASE(64, 64, 32, 2, 1);
+            XCASE(64, 64, 16, 2, 1);
+        }
+        if (bn == 128 && bk == 32) XCASE(128, 128, 32, 2, 2);
+        if (bn == 128) XCASE(128, 128, 16, 2, 2);
+        if (bk == 32) XCASE(128, 64, 32, 2, 2);
+        XCASE(128, 64, 16, 2, 2);
+#undef XCASE
     }
     if (a.epi == EPI_GELU) {
         // Plain-GELU epilogue (the Whisper encoder's conv1, conv2, mlp.0): a template flag, so that the kernels of every other launch are

@@ -15,7 +15,8 @@ namespace lds {
 // The MFMA is v_mfma_f32_32x32x2_f32 (exact fp32); A = packed weights (M = co), B = activations (N = t).
 // ---------------------------------------------------------------------------------------------
 enum { ACT_NONE = 0, ACT_LRELU = 2 };      // activation applied to the input while staging (conv_gemm)
-enum { EPI_NONE = 0, EPI_GEGLU = 1, EPI_TANH = 2, EPI_GELU = 3 };      // EPI_GELU (conv_dma): exact-form GELU of the biased / normalised value, before the residual
+enum { EPI_NONE = 0, EPI_GEGLU = 1, EPI_TANH = 2, EPI_GELU = 3, EPI_SWISH = 4, EPI_GLU = 5 };      // EPI_GELU (conv_dma): exact-form GELU of the biased / normalised value, before the residual
+// EPI_SWISH (conv_dma): v * sigmoid(v) in EPI_GELU's place; EPI_GLU (conv_dma): value * sigmoid(gate) over weights packed as for EPI_GEGLU (pack_geglu)
 
 struct ConvArgs {
     // input: virtual channel-concat of two sources (x2 for ci >= C1)
@@ -106,7 +107,7 @@ struct DmaConvArgs {
     const float* bias;                  // packed-row bias [Mp] or null
     int Mp, Co, Ci, KT, stride, pad, ups;
     const float* res;                   // K4P residual [B][Cout(K4P part)][To] or null
-    int epi;                            // EPI_NONE | EPI_GEGLU | EPI_GELU
+    int epi;                            // EPI_NONE | EPI_GEGLU | EPI_GELU | EPI_SWISH | EPI_GLU
     float* out;                         // K4P [B][min(Cout, plain_from)][To], or plain [B][Cout][To] when out_plain
     int out_plain;
     int plain_from; float* out2;        // output channels >= plain_from go frame-major to out2 [B][Cout-plain_from][To] ...
@@ -273,6 +274,31 @@ hipError_t launch_w2v_ln_act(const float* x, const float* gamma, const float* be
                              hipStream_t s);
 // part [B][C / 32][T] = the (mean, M2) partials of x (K4P) in DmaConvArgs::lnpart_out's format
 hipError_t launch_w2v_lnpart(const float* x, float2* part, const int* nlen, int B, int C, int T, hipStream_t s);
+
+// ---------------------------------------------------------------------------------------------
+// w2v-BERT 2.0 units encoder: the kernels of its own (w2vbert.hip, attention_k4p.hip); slen / nlen / vlen / qlens / klens are device int32 [B]
+// or null (= the buffer's length)
+// ---------------------------------------------------------------------------------------------
+constexpr int kW2vbertRelStride = 80;      // floats per query row of the relative-key table (left_max + right_max + 1 <= 80)
+// audio [B][L] -> out [B][Rmax][n_mels * stride] = SeamlessM4TFeatureExtractor's input_features of every clip taken alone: N_b = 1 + (slen[b] - 400) / 160
+// frames of Nmax (the same of L), log Kaldi mel powers normalised per bin over the clip's own frames, `stride` frames per row; zeros beyond a clip's
+// frames / rows.  basis: double [400][257][2] (model.hip w2vbert_basis); filtT [257][n_mels]; scratch logspec [B][n_mels][Nmax], stat [B][n_mels] (double pairs)
+hipError_t launch_w2vbert_fbank(const float* audio, const int* slen, long long L, int Nmax, int Rmax, const double* basis, const float* filtT, int n_mels,
+                                int stride, float mel_floor, float* logspec, double2* stat, float* out, int B, hipStream_t s);
+// feats [B][T][C] frame-major -> out K4P [B][C][T], part [B][C / 32][T] = its (mean, M2) partials (DmaConvArgs::ln_part's format); rows at and
+// beyond vlen[b] are not read: zeros
+hipError_t launch_w2vbert_feats_k4p(const float* feats, float* out, float2* part, const int* vlen, int B, int C, int T, hipStream_t s);
+// relp [B][heads][T][kW2vbertRelStride]: entry r < NR = log2(e) / 8 * q_t . E[r] (q = the first C channels of the K4P tensor qk [B][2C][T], heads of 64;
+// E [NR][64]); zeros for queries at and beyond qlen[b]
+hipError_t launch_w2vbert_relpos(const float* qk, const float* E, float* relp, const int* qlen, int B, int C, int T, int heads, int NR, hipStream_t s);
+// launch_attention_k4p at heads of 64 with score(i, j) += relp[i][clamp(j - i, -left, right) + left]; queries = the clip's qlens[b] rows (zeros beyond),
+// keys = its first klens[b] <= qlens[b] rows
+hipError_t launch_attention_k4p_rel(const float* qk, const float* vt, const float* relp, float* out, int B, int C, int T, int heads, const int* qlens,
+                                    const int* klens, int left, int right, hipStream_t s);
+// out (K4P, not x) = swish(LayerNorm over the channels(causal depthwise conv of x (K4P), K <= 32 taps packed wp [C / 4][K][4])); input frames at
+// and beyond vlen[b] read as zeros, output frames at and beyond nlen[b] are zeros
+hipError_t launch_w2vbert_dwconv(const float* x, const float* wp, const float* gamma, const float* beta, float eps, float* out, const int* vlen,
+                                 const int* nlen, int B, int C, int T, int K, hipStream_t s);
 
 // ---------------------------------------------------------------------------------------------
 // Small dense layers with N = batch columns (time embedding path)

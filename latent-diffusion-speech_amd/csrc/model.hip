@@ -565,7 +565,7 @@ static int fill_dconv(const ConvW& W, const float* x1, int C1, const float* x2, 
     a.w = W.w; a.bias = W.bias; a.Mp = W.Mp; a.Co = W.Co; a.Ci = W.Ci; a.KT = W.K;
     a.stride = o.stride; a.pad = o.pad; a.ups = o.ups;
     a.res = o.res; a.epi = o.epi; a.out = out; a.out_plain = o.out_plain;
-    a.Cout = (o.epi == EPI_GEGLU) ? W.Co / 2 : W.Co;
+    a.Cout = (o.epi == EPI_GEGLU || o.epi == EPI_GLU) ? W.Co / 2 : W.Co;
     a.plain_from = (o.plain_from >= 0) ? o.plain_from : a.Cout;
     a.out2 = o.out2; a.vt_D = o.vt_D; a.lnpart_out = o.lnpart_out; a.gnpart_out = o.gnpart_out;
     a.voc = o.voc; a.dil = o.dil; a.xpad = o.xpad; a.opad = o.opad; a.act_slope = o.act_slope; a.out_act = o.out_act; a.acc_in = o.acc_in; a.out_div = o.out_div;
@@ -3117,6 +3117,352 @@ extern "C" int lds_w2v_encode(lds_w2v* h, const float* audio, const int32_t* len
 }
 
 // ================================================================================================
+// w2v-BERT 2.0 units encoder (reference tools/tools.py Wav2Vec2Bert: transformers' Wav2Vec2BertModel on SeamlessM4TFeatureExtractor's
+// input_features, with its attention mask).  A Kaldi-style filter bank (w2vbert.hip), LayerNorm + Linear, then n_layer Conformer blocks:
+// half-step feed-forward, self-attention with a relative-key bias, convolution module, half-step feed-forward, LayerNorm.  The four
+// pre-LayerNorms of a block are folded into the GEMMs that read them (pack_ln_fold), the 0.5 of the half steps into output_dense, swish
+// and GLU are conv_dma epilogues, final_layer_norm is materialised because it is the next block's residual stream.
+// A clip of n frames gives rows = (n + 1) / 2 rows of which valid = n / 2 are unmasked: with n odd the last row is a query and a residual
+// row like any other, but no attention key, zero behind the feature projection and zero as the convolution module's input.
+// Launches per encode: 2 or 3 small uploads (rows, unmasked rows; the sample counts when lengths are given: launch_set_list) + 3 (filter bank)
+// + 1 (K4P + partials) + 1 (projection) + 13 per block, 12 in the last (no partials behind the last final_layer_norm) + 1 (frame-major
+// store): 319 at 24 layers without lengths, 320 with.
+// ================================================================================================
+struct W2vbertBlockW {
+    ConvW f1a, f1b, qkv, out, pw1, pw2, f2a, f2b;
+    float *f1_c1 = nullptr, *f1_c2 = nullptr, *qkv_c1 = nullptr, *qkv_c2 = nullptr, *pw1_c1 = nullptr, *pw1_c2 = nullptr, *f2_c1 = nullptr, *f2_c2 = nullptr;
+    float *E = nullptr, *dw = nullptr, *dw_g = nullptr, *dw_b = nullptr, *fin_g = nullptr, *fin_b = nullptr;
+};
+struct lds_w2vbert {
+    lds_w2vbert_cfg cfg;
+    Owner own;
+    double* basis = nullptr;      // [400][257] (cos, sin): 2^15, mean removal, pre-emphasis and the Povey window folded in
+    float* filtT = nullptr;       // [257][n_mels] Kaldi mel triangles
+    ConvW fproj;                  // feature_projection.layer_norm folded into feature_projection.projection
+    float *fproj_c1 = nullptr, *fproj_c2 = nullptr;
+    std::vector<W2vbertBlockW> blocks;
+};
+constexpr int kFbFrame = 400, kFbHop = 160, kFbFft = 512, kFbBins = 257;
+constexpr float kFbMelFloor = 1.192092955078125e-07f;
+constexpr int kW2vbertMinSamples = kFbFrame + kFbHop;      // two frames: one frame makes the ddof = 1 variance 0 / 0 in the reference
+
+// The frame's whole linear front end as one [400][257] complex matrix (audio_utils.spectrogram's order): x * 2^15, minus the frame's mean,
+// y[0] = 0.03 u[0], y[j] = u[j] - 0.97 u[j - 1], times hanning(400) ^ 0.85, zero-padded DFT of 512.
+static std::vector<double> w2vbert_basis() {
+    const double PI = 3.14159265358979323846;
+    std::vector<double> win(kFbFrame), g((size_t)kFbFrame * kFbBins * 2), out((size_t)kFbFrame * kFbBins * 2);
+    for (int i = 0; i < kFbFrame; ++i) win[i] = pow(0.5 - 0.5 * cos(2.0 * PI * i / (kFbFrame - 1)), 0.85);
+    auto e = [&](int i, int k, int part) {
+        const double a = 2.0 * PI * (double)((i * k) % kFbFft) / kFbFft;
+        return win[i] * (part ? -sin(a) : cos(a));
+    };
+    for (int k = 0; k < kFbBins; ++k)
+        for (int part = 0; part < 2; ++part) {
+            double G = 0.0;
+            for (int i = 0; i < kFbFrame; ++i) {
+                double v = e(i, k, part);
+                if (i + 1 < kFbFrame) v -= 0.97 * e(i + 1, k, part);
+                if (i == 0) v -= 0.97 * e(0, k, part);
+                g[((size_t)i * kFbBins + k) * 2 + part] = v;
+                G += v;
+            }
+            for (int i = 0; i < kFbFrame; ++i) out[((size_t)i * kFbBins + k) * 2 + part] = (g[((size_t)i * kFbBins + k) * 2 + part] - G / kFbFrame) * 32768.0;
+        }
+    return out;
+}
+// Kaldi-scale mel triangles, built in mel space (audio_utils.mel_filter_bank with mel_scale "kaldi", triangularize_in_mel_space, no norm):
+// n_mels filters between 20 Hz and 8 kHz over the 257 bins of a 512-point DFT at 16 kHz; [257][n_mels]
+static std::vector<float> w2vbert_mel_filters(int n_mels) {
+    auto mel = [](double f) { return 1127.0 * log(1.0 + f / 700.0); };
+    const double lo = mel(20.0), hi = mel(8000.0);
+    std::vector<double> c(n_mels + 2);
+    for (int i = 0; i < n_mels + 2; ++i) c[i] = lo + (hi - lo) * i / (n_mels + 1);
+    std::vector<float> f((size_t)kFbBins * n_mels);
+    for (int k = 0; k < kFbBins; ++k) {
+        const double fm = mel(16000.0 / kFbFft * k);
+        for (int m = 0; m < n_mels; ++m) {
+            const double down = (fm - c[m]) / (c[m + 1] - c[m]), up = (c[m + 2] - fm) / (c[m + 2] - c[m + 1]);
+            f[(size_t)k * n_mels + m] = (float)std::max(0.0, std::min(down, up));
+        }
+    }
+    return f;
+}
+
+static int w2vbert_cfg_check(const lds_w2vbert_cfg* c) {
+    if (!c) return fail(LDS_EINVAL, "null argument");
+    if (c->n_mels < 8 || c->n_mels > 128 || c->stride < 1 || c->stride > 8 || (c->n_mels * c->stride) % 32 || c->n_mels * c->stride > 1024)
+        return fail(LDS_EINVAL, "w2vbert: n_mels %d x stride %d must be a multiple of 32 up to 1024 (n_mels 8 .. 128, stride 1 .. 8)", c->n_mels, c->stride);
+    if (c->n_state < 64 || c->n_state % 64 || c->n_state > 1024) return fail(LDS_EINVAL, "w2vbert: n_state %d must be a multiple of 64 in 64 .. 1024", c->n_state);
+    if (c->n_head < 1 || c->n_state != c->n_head * 64) return fail(LDS_EINVAL, "w2vbert: n_state / n_head must be 64 (got %d / %d)", c->n_state, c->n_head);
+    if (c->n_ffn < 64 || c->n_ffn % 64) return fail(LDS_EINVAL, "w2vbert: n_ffn %d must be a positive multiple of 64", c->n_ffn);
+    if (c->n_layer < 1 || c->n_layer > 64) return fail(LDS_EINVAL, "w2vbert: n_layer %d outside 1 .. 64", c->n_layer);
+    if (c->left_max < 0 || c->right_max < 0 || c->left_max + c->right_max + 1 > kW2vbertRelStride)
+        return fail(LDS_EINVAL, "w2vbert: left_max %d + right_max %d + 1 distances exceed %d", c->left_max, c->right_max, kW2vbertRelStride);
+    if (c->dw_kernel < 1 || c->dw_kernel > 31 || !(c->dw_kernel & 1)) return fail(LDS_EINVAL, "w2vbert: dw_kernel %d must be odd in 1 .. 31", c->dw_kernel);
+    if (c->n_ctx < 1 || c->n_ctx > 1500) return fail(LDS_EINVAL, "w2vbert: n_ctx %d outside 1 .. 1500", c->n_ctx);
+    if (!(c->eps > 0.f) || !(c->eps < 1.f)) return fail(LDS_EINVAL, "w2vbert: eps %g outside (0, 1)", (double)c->eps);
+    return LDS_OK;
+}
+
+extern "C" int lds_w2vbert_create(const lds_w2vbert_cfg* cfg, int n, const char* const* names, const float* const* ptrs, const int64_t* numel, lds_w2vbert** out) {
+    if (!cfg || !names || !ptrs || !numel || !out || n < 0) return fail(LDS_EINVAL, "null argument");
+    LDS_TRY(w2vbert_cfg_check(cfg));
+    const int Fd = cfg->n_mels * cfg->stride, C = cfg->n_state, F = cfg->n_ffn, K = cfg->dw_kernel, NR = cfg->left_max + cfg->right_max + 1;
+    Tensors T;
+    for (int i = 0; i < n; ++i) T.m[names[i]] = {ptrs[i], numel[i]};
+    lds_w2vbert* h = new lds_w2vbert();
+    h->cfg = *cfg;
+    Owner& o = h->own;
+    auto vec = [&](const std::string& k, int64_t cnt) -> float* {
+        const float* p = T.get(k, cnt);
+        return p ? o.upload(std::vector<float>(p, p + cnt)) : nullptr;
+    };
+    bool ok = true;
+    {
+        const std::vector<double> bs = w2vbert_basis();
+        h->basis = (double*)o.upload_bytes(bs.data(), bs.size() * sizeof(double));
+        h->filtT = o.upload(w2vbert_mel_filters(cfg->n_mels));
+        ok = h->basis && h->filtT;
+    }
+    if (ok) {
+        const float *g = T.get("feature_projection.layer_norm.weight", Fd), *b = T.get("feature_projection.layer_norm.bias", Fd);
+        const float *w = T.get("feature_projection.projection.weight", (int64_t)C * Fd), *wb = T.get("feature_projection.projection.bias", C);
+        ok = g && b && w && wb && pack_ln_fold(o, w, wb, g, b, C, Fd, {}, h->fproj, h->fproj_c1, h->fproj_c2);
+    }
+    // GLU's rows: value and gate of the same channels in one wave's two MFMA row tiles (pack_geglu's interleave)
+    std::vector<int> glu_perm((size_t)2 * C);
+    for (int m = 0; m < 2 * C; ++m) glu_perm[m] = ((m % 64) / 32 ? C : 0) + 32 * (m / 64) + m % 32;
+    h->blocks.resize(cfg->n_layer);
+    for (int l = 0; l < cfg->n_layer && ok; ++l) {
+        const std::string p = "encoder.layers." + std::to_string(l) + ".";
+        W2vbertBlockW& bw = h->blocks[l];
+        const int64_t CC = (int64_t)C * C, FC = (int64_t)F * C;
+        // a half-step feed-forward: LayerNorm folded into intermediate_dense, the 0.5 into output_dense
+        auto ffn = [&](const std::string& ln, const std::string& ff, ConvW& a, float*& c1, float*& c2, ConvW& bq) -> bool {
+            const float *g = T.get(p + ln + ".weight", C), *b = T.get(p + ln + ".bias", C);
+            const float *w1 = T.get(p + ff + ".intermediate_dense.weight", FC), *b1 = T.get(p + ff + ".intermediate_dense.bias", F);
+            const float *w2 = T.get(p + ff + ".output_dense.weight", FC), *b2 = T.get(p + ff + ".output_dense.bias", C);
+            if (!g || !b || !w1 || !b1 || !w2 || !b2) return false;
+            std::vector<float> hw(w2, w2 + FC), hb(b2, b2 + C);
+            for (float& v : hw) v *= 0.5f;
+            for (float& v : hb) v *= 0.5f;
+            return pack_ln_fold(o, w1, b1, g, b, F, C, {}, a, c1, c2) && pack_conv(o, hw.data(), hb.data(), C, F, 1, bq);
+        };
+        ok = ffn("ffn1_layer_norm", "ffn1", bw.f1a, bw.f1_c1, bw.f1_c2, bw.f1b) && ffn("ffn2_layer_norm", "ffn2", bw.f2a, bw.f2_c1, bw.f2_c2, bw.f2b);
+        if (!ok) break;
+        const float *ag = T.get(p + "self_attn_layer_norm.weight", C), *ab = T.get(p + "self_attn_layer_norm.bias", C);
+        const float *qw = T.get(p + "self_attn.linear_q.weight", CC), *qb = T.get(p + "self_attn.linear_q.bias", C);
+        const float *kw = T.get(p + "self_attn.linear_k.weight", CC), *kb = T.get(p + "self_attn.linear_k.bias", C);
+        const float *vw = T.get(p + "self_attn.linear_v.weight", CC), *vb = T.get(p + "self_attn.linear_v.bias", C);
+        const float *ow = T.get(p + "self_attn.linear_out.weight", CC), *ob = T.get(p + "self_attn.linear_out.bias", C);
+        const float *cg = T.get(p + "conv_module.layer_norm.weight", C), *cbt = T.get(p + "conv_module.layer_norm.bias", C);
+        const float *p1 = T.get(p + "conv_module.pointwise_conv1.weight", 2 * CC), *p2 = T.get(p + "conv_module.pointwise_conv2.weight", CC);
+        const float* dw = T.get(p + "conv_module.depthwise_conv.weight", (int64_t)C * K);
+        if (!ag || !ab || !qw || !qb || !kw || !kb || !vw || !vb || !ow || !ob || !cg || !cbt || !p1 || !p2 || !dw) { ok = false; break; }
+        std::vector<float> cat((size_t)3 * CC), cb((size_t)3 * C);
+        memcpy(cat.data(), qw, sizeof(float) * CC);
+        memcpy(cat.data() + CC, kw, sizeof(float) * CC);
+        memcpy(cat.data() + 2 * CC, vw, sizeof(float) * CC);
+        memcpy(cb.data(), qb, sizeof(float) * C);
+        memcpy(cb.data() + C, kb, sizeof(float) * C);
+        memcpy(cb.data() + 2 * C, vb, sizeof(float) * C);
+        std::vector<float> dwp((size_t)C * K);      // [K4P row][k][4]: row = (c / 8) * 2 + (c & 1), element (c & 7) / 2
+        for (int c = 0; c < C; ++c)
+            for (int k = 0; k < K; ++k) dwp[((size_t)((c >> 3) * 2 + (c & 1)) * K + k) * 4 + ((c & 7) >> 1)] = dw[(size_t)c * K + k];
+        bw.dw = o.upload(dwp);
+        bw.E = vec(p + "self_attn.distance_embedding.weight", (int64_t)NR * 64);
+        bw.dw_g = vec(p + "conv_module.depthwise_layer_norm.weight", C);
+        bw.dw_b = vec(p + "conv_module.depthwise_layer_norm.bias", C);
+        bw.fin_g = vec(p + "final_layer_norm.weight", C);
+        bw.fin_b = vec(p + "final_layer_norm.bias", C);
+        ok = bw.dw && bw.E && bw.dw_g && bw.dw_b && bw.fin_g && bw.fin_b &&
+             pack_ln_fold(o, cat.data(), cb.data(), ag, ab, 3 * C, C, {}, bw.qkv, bw.qkv_c1, bw.qkv_c2) && pack_conv(o, ow, ob, C, C, 1, bw.out) &&
+             pack_ln_fold(o, p1, nullptr, cg, cbt, 2 * C, C, glu_perm, bw.pw1, bw.pw1_c1, bw.pw1_c2) && pack_conv(o, p2, nullptr, C, C, 1, bw.pw2);
+    }
+    if (!ok) {
+        std::string miss = T.missing;
+        delete h;
+        if (!miss.empty()) return fail(LDS_EMISSING, "w2vbert: %s", miss.c_str());
+        return fail(LDS_ENOMEM, "w2vbert weight upload failed");
+    }
+    *out = h;
+    return LDS_OK;
+}
+extern "C" void lds_w2vbert_destroy(lds_w2vbert* h) { delete h; }
+
+static int w2vbert_frames(int64_t n) { return n < kFbFrame ? 0 : (int)((n - kFbFrame) / kFbHop) + 1; }
+
+struct W2vbertWs {
+    int *slen, *rows, *valid;      // device copies: the clips' sample counts, rows and unmasked rows
+    float* logspec; double2* stat;
+    float* feats;                  // input_features when the caller does not receive them
+    float* fk; float2* lnf;        // ... as K4P, and their LayerNorm partials
+    float2* lnp;                   // LayerNorm partials of the residual stream
+    float *xa, *xb, *qk, *v, *att, *big, *relp;
+};
+static void plan_w2vbert(const lds_w2vbert* h, Arena& A, int B, int N, int R, W2vbertWs& w) {
+    const size_t M = h->cfg.n_mels, Fd = (size_t)h->cfg.n_mels * h->cfg.stride, C = h->cfg.n_state, F = h->cfg.n_ffn, T = R, Bz = B;
+    w.slen = (int*)A.f(64); w.rows = (int*)A.f(64); w.valid = (int*)A.f(64);
+    w.logspec = A.f(Bz * M * (size_t)N);
+    w.stat = (double2*)A.f(Bz * M * 4);
+    w.feats = A.f(Bz * T * Fd);
+    w.fk = A.f(Bz * Fd * (T + 2));
+    w.lnf = (float2*)A.f(Bz * (Fd / 32) * T * 2);
+    w.lnp = (float2*)A.f(Bz * (C / 32) * T * 2);
+    w.xa = A.f(Bz * C * (T + 2)); w.xb = A.f(Bz * C * (T + 2));
+    w.qk = A.f(Bz * 2 * C * (T + 2));
+    w.v = A.f(Bz * (C * ((T + 3) & ~(size_t)3) + 2048));
+    w.att = A.f(Bz * C * (T + 2));
+    w.big = A.f(Bz * F * (T + 2));
+    w.relp = A.f(Bz * h->cfg.n_head * T * kW2vbertRelStride);
+    A.f(16384);      // tail slack: ragged last tiles read (masked) entries past a tensor's end
+}
+// the limits of one call: B clips in buffers of L samples -> N frames, R rows
+static int w2vbert_shape_check(const lds_w2vbert* h, int B, int64_t L, int& N, int& R) {
+    if (!h) return fail(LDS_EINVAL, "null handle");
+    if (B < 1 || B > 64) return fail(LDS_EINVAL, "w2vbert: B %d outside 1 .. 64", B);
+    if (L < kW2vbertMinSamples || L > ((int64_t)1 << 30)) return fail(LDS_EINVAL, "w2vbert: L %lld outside %d .. 2^30 samples", (long long)L, kW2vbertMinSamples);
+    N = w2vbert_frames(L);
+    R = (N + h->cfg.stride - 1) / h->cfg.stride;
+    if (R > h->cfg.n_ctx) return fail(LDS_EINVAL, "w2vbert: %d rows exceed n_ctx %d", R, h->cfg.n_ctx);
+    return LDS_OK;
+}
+extern "C" int lds_w2vbert_workspace_bytes(const lds_w2vbert* h, int B, int64_t L, size_t* out) {
+    if (!out) return fail(LDS_EINVAL, "null argument");
+    int N, R;
+    LDS_TRY(w2vbert_shape_check(h, B, L, N, R));
+    Arena A(nullptr, 0);
+    W2vbertWs w;
+    plan_w2vbert(h, A, B, N, R, w);
+    *out = A.used;
+    return LDS_OK;
+}
+
+// audio -> feats_out ([B][R][n_mels * stride]) and / or enc ([B][R][n_state]); or feats_in -> enc.  nfr: every clip's frame count (host, [B]),
+// N / R: the buffers' frames / rows.  Every argument has been checked.
+static int w2vbert_run(lds_w2vbert* h, const float* audio, int64_t L, const int32_t* slen_host, const float* feats_in, const int32_t* nfr, int N, int R,
+                       float* feats_out, float* enc, void* ws, size_t ws_bytes, int B, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    ProfChain chain;
+    Arena A(ws, ws_bytes);
+    W2vbertWs w;
+    plan_w2vbert(h, A, B, N, R, w);
+    if (!A.ok) return fail(LDS_ENOMEM, "w2vbert workspace too small: need %zu", A.used);
+    const lds_w2vbert_cfg& c = h->cfg;
+    const int Fd = c.n_mels * c.stride, C = c.n_state, T = R;
+    int32_t rows[64], valid[64];
+    for (int b = 0; b < B; ++b) { rows[b] = (nfr[b] + c.stride - 1) / c.stride; valid[b] = nfr[b] / c.stride; }
+    LDS_TRY(whisper_upload(rows, B, w.rows, st));
+    LDS_TRY(whisper_upload(valid, B, w.valid, st));
+    const float* feats = feats_in;
+    if (audio) {
+        const int* slen = nullptr;
+        if (slen_host) {
+            LDS_TRY(whisper_upload(slen_host, B, w.slen, st));
+            slen = w.slen;
+        }
+        float* fo = feats_out ? feats_out : w.feats;
+        HIP_TRY(launch_w2vbert_fbank(audio, slen, L, N, R, h->basis, h->filtT, c.n_mels, c.stride, kFbMelFloor, w.logspec, w.stat, fo, B, st));
+        feats = fo;
+    }
+    if (!enc) return LDS_OK;
+    TileBatchScope tb(0);      // tile rules judged at the nominal batch: a clip's units do not depend on the batch it is in
+    HIP_TRY(launch_w2vbert_feats_k4p(feats, w.fk, w.lnf, w.valid, B, Fd, T, st));
+    float* x = w.xa;
+    float* xn = w.xb;
+    {
+        LensScope lv(w.valid);      // rows at and beyond `valid` are zeros behind the projection (Wav2Vec2BertEncoder.forward's masked_fill)
+        DOpt o;
+        o.ln_part = w.lnf; o.ln_np = Fd / 32; o.ln_eps = c.eps; o.ln_c1 = h->fproj_c1; o.ln_c2 = h->fproj_c2;
+        o.lnpart_out = w.lnp;
+        LDS_TRY(run_dconv(h->fproj, w.fk, Fd, nullptr, 0, T, o, x, B, st));
+    }
+    LensScope ls(w.rows);
+    float* glu = w.att;      // the convolution module's two tensors reuse attention's (both are consumed before the module starts)
+    float* dwo = w.qk;
+    for (const W2vbertBlockW& bw : h->blocks) {
+        auto ffn = [&](const ConvW& a, const float* c1, const float* c2, const ConvW& bq, float* xin, float* xout, float2* part_out) -> int {
+            DOpt o1;      // swish(intermediate_dense(layer_norm(.)))
+            o1.epi = EPI_SWISH;
+            o1.ln_part = w.lnp; o1.ln_np = C / 32; o1.ln_eps = c.eps; o1.ln_c1 = c1; o1.ln_c2 = c2;
+            LDS_TRY(run_dconv(a, xin, C, nullptr, 0, T, o1, w.big, B, st));
+            DOpt o2;      // + 0.5 output_dense(.)
+            o2.res = xin; o2.lnpart_out = part_out;
+            return run_dconv(bq, w.big, c.n_ffn, nullptr, 0, T, o2, xout, B, st);
+        };
+        LDS_TRY(ffn(bw.f1a, bw.f1_c1, bw.f1_c2, bw.f1b, x, xn, w.lnp));      // partials for self_attn_layer_norm
+        std::swap(x, xn);
+        DOpt oq;      // q | k | v of self_attn_layer_norm(x)
+        oq.plain_from = 2 * C; oq.out2 = w.v; oq.vt_D = 64;
+        oq.ln_part = w.lnp; oq.ln_np = C / 32; oq.ln_eps = c.eps; oq.ln_c1 = bw.qkv_c1; oq.ln_c2 = bw.qkv_c2;
+        LDS_TRY(run_dconv(bw.qkv, x, C, nullptr, 0, T, oq, w.qk, B, st));
+        HIP_TRY(launch_w2vbert_relpos(w.qk, bw.E, w.relp, w.rows, B, C, T, c.n_head, c.left_max + c.right_max + 1, st));
+        HIP_TRY(launch_attention_k4p_rel(w.qk, w.v, w.relp, w.att, B, C, T, c.n_head, w.rows, w.valid, c.left_max, c.right_max, st));
+        DOpt oo;      // x + linear_out(.), partials for conv_module.layer_norm
+        oo.res = x; oo.lnpart_out = w.lnp;
+        LDS_TRY(run_dconv(bw.out, w.att, C, nullptr, 0, T, oo, xn, B, st));
+        std::swap(x, xn);
+        {
+            LensScope lv(w.valid);      // the module's input is zero on the masked row: GLU(pointwise_conv1(0)) = 0, written as zeros
+            DOpt og;
+            og.epi = EPI_GLU;
+            og.ln_part = w.lnp; og.ln_np = C / 32; og.ln_eps = c.eps; og.ln_c1 = bw.pw1_c1; og.ln_c2 = bw.pw1_c2;
+            LDS_TRY(run_dconv(bw.pw1, x, C, nullptr, 0, T, og, glu, B, st));
+        }
+        HIP_TRY(launch_w2vbert_dwconv(glu, bw.dw, bw.dw_g, bw.dw_b, c.eps, dwo, w.valid, w.rows, B, C, T, c.dw_kernel, st));
+        DOpt op;      // x + pointwise_conv2(.), partials for ffn2_layer_norm
+        op.res = x; op.lnpart_out = w.lnp;
+        LDS_TRY(run_dconv(bw.pw2, dwo, C, nullptr, 0, T, op, xn, B, st));
+        std::swap(x, xn);
+        LDS_TRY(ffn(bw.f2a, bw.f2_c1, bw.f2_c2, bw.f2b, x, xn, nullptr));
+        std::swap(x, xn);
+        // final_layer_norm, materialised: it is the next block's residual stream; its partials serve the next ffn1_layer_norm
+        HIP_TRY(launch_hubert_ln(x, bw.fin_g, bw.fin_b, c.eps, xn, w.rows, B, C, T, st));
+        std::swap(x, xn);
+        if (&bw != &h->blocks.back()) { HIP_TRY(launch_w2v_lnpart(x, w.lnp, w.rows, B, C, T, st)); }
+    }
+    HIP_TRY(launch_hubert_store_frames(x, enc, w.rows, B, C, T, st));
+    return LDS_OK;
+}
+
+static int w2vbert_audio_check(const lds_w2vbert* h, const float* audio, const int32_t* lengths, const void* out, const void* ws, int B, int64_t L, int& N,
+                               int& R, int32_t* nfr) {
+    if (!h || !audio || !out || !ws) return fail(LDS_EINVAL, "null argument");
+    LDS_TRY(w2vbert_shape_check(h, B, L, N, R));
+    for (int b = 0; b < B; ++b) {
+        if (lengths && (lengths[b] < kW2vbertMinSamples || lengths[b] > L))
+            return fail(LDS_EINVAL, "length[%d] = %d outside %d .. %lld", b, lengths[b], kW2vbertMinSamples, (long long)L);
+        nfr[b] = lengths ? w2vbert_frames(lengths[b]) : N;
+    }
+    return LDS_OK;
+}
+extern "C" int lds_w2vbert_fbank(lds_w2vbert* h, const float* audio, const int32_t* lengths, float* out, void* ws, size_t ws_bytes, int B, int64_t L, void* stream) {
+    int N, R;
+    int32_t nfr[64];
+    LDS_TRY(w2vbert_audio_check(h, audio, lengths, out, ws, B, L, N, R, nfr));
+    return w2vbert_run(h, audio, L, lengths, nullptr, nfr, N, R, out, nullptr, ws, ws_bytes, B, stream);
+}
+extern "C" int lds_w2vbert_encode(lds_w2vbert* h, const float* audio, const int32_t* lengths, float* out, void* ws, size_t ws_bytes, int B, int64_t L, void* stream) {
+    int N, R;
+    int32_t nfr[64];
+    LDS_TRY(w2vbert_audio_check(h, audio, lengths, out, ws, B, L, N, R, nfr));
+    return w2vbert_run(h, audio, L, lengths, nullptr, nfr, N, R, nullptr, out, ws, ws_bytes, B, stream);
+}
+extern "C" int lds_w2vbert_encode_features(lds_w2vbert* h, const float* feats, const int32_t* n_frames, float* out, void* ws, size_t ws_bytes, int B, int R,
+                                           void* stream) {
+    if (!h || !feats || !out || !ws) return fail(LDS_EINVAL, "null argument");
+    if (B < 1 || B > 64) return fail(LDS_EINVAL, "w2vbert: B %d outside 1 .. 64", B);
+    if (R < 1 || R > h->cfg.n_ctx) return fail(LDS_EINVAL, "w2vbert: %d rows outside 1 .. n_ctx %d", R, h->cfg.n_ctx);
+    const int st = h->cfg.stride;
+    int32_t nfr[64];
+    for (int b = 0; b < B; ++b) {
+        nfr[b] = n_frames ? n_frames[b] : R * st;
+        if (nfr[b] < 2 || nfr[b] < st || (nfr[b] + st - 1) / st > R) return fail(LDS_EINVAL, "n_frames[%d] = %d outside %d .. %d", b, nfr[b], st > 2 ? st : 2, R * st);
+    }
+    return w2vbert_run(h, nullptr, 0, nullptr, feats, nfr, R * st, R, nullptr, out, ws, ws_bytes, B, stream);
+}
+
+// ================================================================================================
 // Single-op test entry points
 // ================================================================================================
 extern "C" int lds_test_conv(const lds_conv_test* a, float* out, int B, void* stream) {
@@ -3967,6 +4313,98 @@ extern "C" int lds_test_w2v_ln_act(const float* x, const int32_t* n_frames, cons
     }
     HIP_TRY(launch_to_k4p(x, kx, B, C, T, C, 0, st));
     HIP_TRY(launch_w2v_ln_act(kx, gamma, beta, eps, ko, (float2*)part, nlen, B, C, T, st));
+    HIP_TRY(launch_from_k4p(ko, out, B, C, T, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return LDS_OK;
+}
+
+// The w2v-BERT 2.0 encoder's own kernels alone (w2vbert.hip, attention_k4p.hip), plain tensors in and out; every pointer but the lengths is a
+// device pointer.
+extern "C" int lds_test_w2vbert_fbank(const float* audio, const int32_t* lengths, float* out, int B, int64_t L, void* stream) {
+    if (!audio || !out || B < 1 || B > 64 || L < kW2vbertMinSamples || L > ((int64_t)1 << 30)) return fail(LDS_EINVAL, "bad argument");
+    hipStream_t st = (hipStream_t)stream;
+    const int n_mels = 80, stride = 2, N = w2vbert_frames(L), R = (N + 1) / 2;
+    Owner own;
+    const std::vector<double> bs = w2vbert_basis();
+    double* basis = (double*)own.upload_bytes(bs.data(), bs.size() * sizeof(double));
+    float* filtT = own.upload(w2vbert_mel_filters(n_mels));
+    TmpDev tmp;
+    float* logspec = tmp.f((size_t)B * n_mels * N);
+    double2* stat = (double2*)tmp.f((size_t)B * n_mels * 4);
+    int* dl = (int*)tmp.f(64);
+    if (!basis || !filtT || !logspec || !stat || !dl) return fail(LDS_ENOMEM, "alloc");
+    const int* slen = nullptr;
+    if (lengths) {
+        for (int b = 0; b < B; ++b)
+            if (lengths[b] < kW2vbertMinSamples || lengths[b] > L) return fail(LDS_EINVAL, "length[%d] = %d outside %d .. %lld", b, lengths[b], kW2vbertMinSamples, (long long)L);
+        LDS_TRY(whisper_upload(lengths, B, dl, st));
+        slen = dl;
+    }
+    HIP_TRY(launch_w2vbert_fbank(audio, slen, L, N, R, basis, filtT, n_mels, stride, kFbMelFloor, logspec, stat, out, B, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return LDS_OK;
+}
+extern "C" int lds_test_w2vbert_attention(const float* qkv, const float* E, const int32_t* q_rows, const int32_t* k_rows, float* out, int B, int C, int T,
+                                          int heads, int left, int right, void* stream) {
+    if (!qkv || !E || !out || B < 1 || B > 64 || T < 1 || heads < 1 || C != heads * 64 || left < 0 || right < 0 || left + right + 1 > kW2vbertRelStride)
+        return fail(LDS_EINVAL, "bad argument");
+    hipStream_t st = (hipStream_t)stream;
+    TmpDev tmp;
+    float* qkp = tmp.f((size_t)B * 2 * C * T);       // plain [B][2C][T]
+    float* vpl = tmp.f((size_t)B * C * T);
+    float* vt = tmp.f((size_t)B * C * (T + 3) + 2048);
+    float* kqk = tmp.f((size_t)B * 2 * C * (T + 2));
+    float* ko = tmp.f((size_t)B * C * (T + 2));
+    float* relp = tmp.f((size_t)B * heads * T * kW2vbertRelStride);
+    int* dl = (int*)tmp.f(128);
+    if (!qkp || !vpl || !vt || !kqk || !ko || !relp || !dl) return fail(LDS_ENOMEM, "alloc");
+    const int *ql = nullptr, *kl = nullptr;
+    if (q_rows || k_rows) {
+        if (!q_rows || !k_rows) return fail(LDS_EINVAL, "q_rows and k_rows come together");
+        for (int b = 0; b < B; ++b)
+            if (q_rows[b] < 1 || q_rows[b] > T || k_rows[b] < 1 || k_rows[b] > q_rows[b]) return fail(LDS_EINVAL, "rows[%d] = (%d, %d) outside 1 .. %d", b, q_rows[b], k_rows[b], T);
+        LDS_TRY(whisper_upload(q_rows, B, dl, st));
+        LDS_TRY(whisper_upload(k_rows, B, dl + 64, st));
+        ql = dl; kl = dl + 64;
+    }
+    for (int b = 0; b < B; ++b) {
+        HIP_TRY(hipMemcpyAsync(qkp + (size_t)b * 2 * C * T, qkv + (size_t)b * 3 * C * T, sizeof(float) * 2 * C * T, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(vpl + (size_t)b * C * T, qkv + (size_t)b * 3 * C * T + (size_t)2 * C * T, sizeof(float) * C * T, hipMemcpyDeviceToDevice, st));
+    }
+    HIP_TRY(launch_to_k4p(qkp, kqk, B, 2 * C, T, 2 * C, 0, st));
+    HIP_TRY(launch_plain_to_vt(vpl, vt, B, C, T, 64, st));
+    HIP_TRY(launch_w2vbert_relpos(kqk, E, relp, ql, B, C, T, heads, left + right + 1, st));
+    HIP_TRY(launch_attention_k4p_rel(kqk, vt, relp, ko, B, C, T, heads, ql, kl, left, right, st));
+    HIP_TRY(launch_from_k4p(ko, out, B, C, T, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return LDS_OK;
+}
+extern "C" int lds_test_w2vbert_dwconv(const float* x, const float* w, const float* gamma, const float* beta, float eps, const int32_t* in_rows,
+                                       const int32_t* out_rows, float* out, int B, int C, int T, int K, void* stream) {
+    if (!x || !w || !gamma || !beta || !out || B < 1 || B > 64 || T < 1 || C < 64 || C % 64 || C > 1024 || K < 1 || K > 31) return fail(LDS_EINVAL, "bad argument");
+    hipStream_t st = (hipStream_t)stream;
+    TmpDev tmp;
+    float* kx = tmp.f((size_t)B * C * (T + 2));
+    float* ko = tmp.f((size_t)B * C * (T + 2));
+    float* wp = tmp.f((size_t)C * K);
+    int* dl = (int*)tmp.f(128);
+    if (!kx || !ko || !wp || !dl) return fail(LDS_ENOMEM, "alloc");
+    std::vector<float> hw((size_t)C * K), hp((size_t)C * K);
+    HIP_TRY(hipMemcpy(hw.data(), w, hw.size() * sizeof(float), hipMemcpyDeviceToHost));
+    for (int c = 0; c < C; ++c)
+        for (int k = 0; k < K; ++k) hp[((size_t)((c >> 3) * 2 + (c & 1)) * K + k) * 4 + ((c & 7) >> 1)] = hw[(size_t)c * K + k];
+    HIP_TRY(hipMemcpy(wp, hp.data(), hp.size() * sizeof(float), hipMemcpyHostToDevice));
+    const int *vl = nullptr, *nl = nullptr;
+    if (in_rows || out_rows) {
+        if (!in_rows || !out_rows) return fail(LDS_EINVAL, "in_rows and out_rows come together");
+        for (int b = 0; b < B; ++b)
+            if (out_rows[b] < 1 || out_rows[b] > T || in_rows[b] < 1 || in_rows[b] > out_rows[b]) return fail(LDS_EINVAL, "rows[%d] = (%d, %d) outside 1 .. %d", b, in_rows[b], out_rows[b], T);
+        LDS_TRY(whisper_upload(in_rows, B, dl, st));
+        LDS_TRY(whisper_upload(out_rows, B, dl + 64, st));
+        vl = dl; nl = dl + 64;
+    }
+    HIP_TRY(launch_to_k4p(x, kx, B, C, T, C, 0, st));
+    HIP_TRY(launch_w2vbert_dwconv(kx, wp, gamma, beta, eps, ko, vl, nl, B, C, T, K, st));
     HIP_TRY(launch_from_k4p(ko, out, B, C, T, st));
     HIP_TRY(hipStreamSynchronize(st));
     return LDS_OK;

@@ -666,6 +666,104 @@ def w2v_convert_state(state, cfg=None):
     return out
 
 
+# ---- w2v-BERT 2.0 units encoder (reference tools/tools.py Wav2Vec2Bert: transformers' Wav2Vec2BertModel on SeamlessM4TFeatureExtractor) --------
+# the fields of include/lds.h lds_w2vbert_cfg (Wav2Vec2BertConfig()'s defaults); n_ctx = the most rows of one call (30 s give 1499)
+W2V_BERT_DIMS = dict(n_mels=80, stride=2, n_state=1024, n_head=16, n_ffn=4096, n_layer=24, left_max=64, right_max=8, dw_kernel=31, n_ctx=1500,
+                     eps=1e-5)
+W2VBERT_MIN_SAMPLES = 560      # two frames: one frame makes the extractor's ddof = 1 variance 0 / 0
+# checkpoint tensors that inference never reads
+W2VBERT_IGNORED_PREFIXES = ("masked_spec_embed",)
+
+
+def w2vbert_frames(n_samples):
+    """(n, valid, rows) of a clip of n_samples at 16 kHz: n = 1 + (L - 400) // 160 frames of 400 samples, stacked in pairs into
+    rows = (n + 1) // 2 rows of which valid = n // 2 are unmasked; with n odd the last row is the masked row"""
+    n = 1 + (int(n_samples) - 400) // 160 if n_samples >= 400 else 0
+    return n, n // 2, (n + 1) // 2
+
+
+def w2vbert_param_shapes(cfg=None):
+    """transformers' Wav2Vec2BertModel key -> shape for the tensors inference reads (the names lds_w2vbert_create looks up)"""
+    c = dict(W2V_BERT_DIMS if cfg is None else cfg)
+    Fd, C, F, K, NR = c["n_mels"] * c["stride"], c["n_state"], c["n_ffn"], c["dw_kernel"], c["left_max"] + c["right_max"] + 1
+    d = OrderedDict()
+    d["feature_projection.layer_norm.weight"] = (Fd,)
+    d["feature_projection.layer_norm.bias"] = (Fd,)
+    d["feature_projection.projection.weight"] = (C, Fd)
+    d["feature_projection.projection.bias"] = (C,)
+    for l in range(c["n_layer"]):
+        p = f"encoder.layers.{l}."
+        for ff in ("ffn1", "ffn2"):
+            d[p + f"{ff}_layer_norm.weight"] = (C,)
+            d[p + f"{ff}_layer_norm.bias"] = (C,)
+            d[p + f"{ff}.intermediate_dense.weight"] = (F, C)
+            d[p + f"{ff}.intermediate_dense.bias"] = (F,)
+            d[p + f"{ff}.output_dense.weight"] = (C, F)
+            d[p + f"{ff}.output_dense.bias"] = (C,)
+        d[p + "self_attn_layer_norm.weight"] = (C,)
+        d[p + "self_attn_layer_norm.bias"] = (C,)
+        for n in ("linear_q", "linear_k", "linear_v", "linear_out"):
+            d[p + f"self_attn.{n}.weight"] = (C, C)
+            d[p + f"self_attn.{n}.bias"] = (C,)
+        d[p + "self_attn.distance_embedding.weight"] = (NR, C // c["n_head"])
+        d[p + "conv_module.layer_norm.weight"] = (C,)
+        d[p + "conv_module.layer_norm.bias"] = (C,)
+        d[p + "conv_module.pointwise_conv1.weight"] = (2 * C, C, 1)
+        d[p + "conv_module.depthwise_conv.weight"] = (C, 1, K)
+        d[p + "conv_module.depthwise_layer_norm.weight"] = (C,)
+        d[p + "conv_module.depthwise_layer_norm.bias"] = (C,)
+        d[p + "conv_module.pointwise_conv2.weight"] = (C, C, 1)
+        d[p + "final_layer_norm.weight"] = (C,)
+        d[p + "final_layer_norm.bias"] = (C,)
+    return d
+
+
+def w2vbert_init_state(cfg=None, seed=0, init_weights=None):
+    """Build-owned seeded weights in transformers' names (no checkpoint ships), every stage at a scale of order 1 as in w2v_init_state, so that
+    no error hides behind the next LayerNorm: every matrix uniform within sqrt(3 / fan_in) (unit gain), linear_q and linear_k within
+    1.7 / sqrt(fan_in) and the distance embedding within 1 (attention logits of standard deviation ~1, the relative-key term about half
+    of it), every LayerNorm gain in [0.8, 1.2), every bias in [-0.1, 0.1)."""
+    if init_weights is None:
+        from . import init_weights
+    import numpy as np
+    st = OrderedDict()
+    for k, shp in w2vbert_param_shapes(cfg).items():
+        fan = int(np.prod(shp[1:])) if len(shp) > 1 else 1
+        if k.endswith(".bias"):
+            st[k] = init_weights.uniform(k, shp, seed, -0.1, 0.1)
+        elif "layer_norm." in k:
+            st[k] = init_weights.uniform(k, shp, seed, 0.8, 1.2)
+        elif k.endswith("distance_embedding.weight"):
+            st[k] = init_weights.uniform(k, shp, seed, -1.0, 1.0)
+        else:
+            b = float((1.7 if ("linear_q." in k or "linear_k." in k) else np.sqrt(3.0)) / np.sqrt(fan))
+            st[k] = init_weights.uniform(k, shp, seed, -b, b)
+    return OrderedDict((k, np.ascontiguousarray(v, dtype=np.float32)) for k, v in st.items())
+
+
+def w2vbert_convert_state(state, cfg=None):
+    """A checkpoint's state dict in transformers naming (an optional "module." / "wav2vec2_bert." prefix removed, masked_spec_embed dropped)
+    -> the tensors of w2vbert_param_shapes(cfg).  A missing tensor is a KeyError naming it; a wrong shape a ValueError."""
+    shapes = w2vbert_param_shapes(cfg)
+    got = {}
+    for k, v in state.items():
+        for pre in ("module.", "wav2vec2_bert."):
+            if k.startswith(pre):
+                k = k[len(pre):]
+        if k.startswith(W2VBERT_IGNORED_PREFIXES):
+            continue
+        if k in shapes:
+            got[k] = v
+    out = OrderedDict()
+    for k, shp in shapes.items():
+        if k not in got:
+            raise KeyError(f"w2v-BERT checkpoint lacks {k!r}")
+        if tuple(got[k].shape) != tuple(shp):
+            raise ValueError(f"w2v-BERT checkpoint: {k!r} has shape {tuple(got[k].shape)}, expected {tuple(shp)}")
+        out[k] = got[k]
+    return out
+
+
 RESAMPLE_MAX_RATE, RESAMPLE_MAX_TAPS, RESAMPLE_MAX_BANK = 384000, 1024, 1 << 24      # include/lds.h lds_resample
 
 

@@ -113,6 +113,12 @@ lds_w2v_destroy                  v:p
 lds_w2v_workspace_bytes          i:piqp
 lds_w2v_features                 i:pppppziqp
 lds_w2v_encode                   i:pppppziqp
+lds_w2vbert_create               i:pipppp
+lds_w2vbert_destroy              v:p
+lds_w2vbert_workspace_bytes      i:piqp
+lds_w2vbert_fbank                i:pppppziqp
+lds_w2vbert_encode_features      i:pppppziip
+lds_w2vbert_encode               i:pppppziqp
 lds_lm_create                    i:pipppp
 lds_lm_destroy                   v:p
 lds_lm_workspace_bytes           i:piiip
@@ -185,6 +191,9 @@ lds_test_dconv_ex                i:pppipzp
 lds_test_voc_ups                 i:pppiiiiiipppppzp
 lds_test_w2v_conv0               i:ppppppfpiiqp
 lds_test_w2v_ln_act              i:ppppfppiiip
+lds_test_w2vbert_fbank           i:pppiqp
+lds_test_w2vbert_attention       i:pppppiiiiiip
+lds_test_w2vbert_dwconv          i:ppppfpppiiiip
 """
 SIGNATURES = dict(ln.split() for ln in (_PUBLIC + _TEST).splitlines() if ln)
 EXPORTS = [ln.split()[0] for ln in _PUBLIC.splitlines() if ln]
@@ -751,6 +760,112 @@ class Wav2Vec2(_Handle):
 
     def encode(self, audio, lengths=None, ws=None):
         return self._run("lds_w2v_encode", "n_state", audio, lengths, ws)
+
+
+class W2vBertCfg(C.Structure):
+    _fields_ = [(k, C.c_int) for k in ("n_mels", "stride", "n_state", "n_head", "n_ffn", "n_layer", "left_max", "right_max", "dw_kernel", "n_ctx")] + \
+               [("eps", C.c_float)]
+
+
+class Wav2Vec2Bert(_Handle):
+    """w2v-BERT 2.0 units encoder (lds_w2vbert_*): audio [B,L] at 16 kHz -> SeamlessM4TFeatureExtractor's input_features [B,R,n_mels*stride] /
+    Wav2Vec2BertModel's last_hidden_state [B,R,n_state], R = the rows of L samples (lds.arch.w2vbert_frames).  `state`: transformers-named
+    tensors (lds.arch.w2vbert_param_shapes).  `lengths`: every clip's own sample count (host ints, 560 .. L, at most 64 clips): each clip is
+    encoded as if alone.  A clip with an odd frame count n keeps its masked last row (row n // 2) in the result, as the reference does.
+    Every limit of include/lds.h is checked here first (ValueError, before a device is touched)."""
+    KIND = "w2vbert"
+    FIELDS = ("n_mels", "stride", "n_state", "n_head", "n_ffn", "n_layer", "left_max", "right_max", "dw_kernel", "n_ctx")
+    MIN_SAMPLES, MAX_CLIPS = 560, 64
+
+    def __init__(self, dims, state):
+        d = self.check_dims(dims)
+        self._create_weights(W2vBertCfg(*(d[k] for k in self.FIELDS), d["eps"]), state)
+        self.dims = d
+
+    @classmethod
+    def check_dims(cls, dims):
+        """include/lds.h's limits (ValueError); returns the fields as ints (eps a float)"""
+        d = {k: int(dims[k]) for k in cls.FIELDS}
+        d["eps"] = float(dims.get("eps", 1e-5))
+        fd = d["n_mels"] * d["stride"]
+        if not (8 <= d["n_mels"] <= 128 and 1 <= d["stride"] <= 8 and fd % 32 == 0 and fd <= 1024):
+            raise ValueError(f"Wav2Vec2Bert: n_mels {d['n_mels']} x stride {d['stride']} must be a multiple of 32 up to 1024")
+        if not (64 <= d["n_state"] <= 1024 and d["n_state"] % 64 == 0 and d["n_state"] == 64 * d["n_head"]):
+            raise ValueError(f"Wav2Vec2Bert: n_state {d['n_state']} must be a multiple of 64 in 64 .. 1024 and 64 x n_head ({d['n_head']})")
+        if d["n_ffn"] < 64 or d["n_ffn"] % 64:
+            raise ValueError(f"Wav2Vec2Bert: n_ffn {d['n_ffn']} must be a positive multiple of 64")
+        if not 1 <= d["n_layer"] <= 64:
+            raise ValueError(f"Wav2Vec2Bert: n_layer {d['n_layer']} outside 1 .. 64")
+        if d["left_max"] < 0 or d["right_max"] < 0 or d["left_max"] + d["right_max"] + 1 > 80:
+            raise ValueError(f"Wav2Vec2Bert: left_max {d['left_max']} + right_max {d['right_max']} + 1 distances exceed 80")
+        if not (1 <= d["dw_kernel"] <= 31 and d["dw_kernel"] % 2 == 1):
+            raise ValueError(f"Wav2Vec2Bert: dw_kernel {d['dw_kernel']} must be odd in 1 .. 31")
+        if not 1 <= d["n_ctx"] <= 1500:
+            raise ValueError(f"Wav2Vec2Bert: n_ctx {d['n_ctx']} outside 1 .. 1500")
+        if not 0.0 < d["eps"] < 1.0:
+            raise ValueError(f"Wav2Vec2Bert: eps {d['eps']} outside (0, 1)")
+        return d
+
+    def rows(self, n_samples):
+        n = 1 + (int(n_samples) - 400) // 160
+        return (n + self.dims["stride"] - 1) // self.dims["stride"]
+
+    @classmethod
+    def lengths(cls, lengths, B, L):
+        """per-clip sample counts -> host int32 [B] (include/lds.h: B <= 64, 560 .. L)"""
+        return _host_lengths(lengths, B, cls.MIN_SAMPLES, L, cls.MAX_CLIPS, "units")
+
+    def workspace_bytes(self, B, L):
+        return _bytes("lds_w2vbert_workspace_bytes", self.h, B, L)
+
+    def _check_audio(self, audio):
+        if audio.dim() != 2:
+            raise ValueError(f"Wav2Vec2Bert: audio must be [B, L], got {list(audio.shape)}")
+        B, L = audio.shape
+        if not 1 <= B <= self.MAX_CLIPS:
+            raise ValueError(f"Wav2Vec2Bert: 1 .. {self.MAX_CLIPS} clips per call (got {B})")
+        if L < self.MIN_SAMPLES:
+            raise ValueError(f"Wav2Vec2Bert: clips need at least {self.MIN_SAMPLES} samples (got {L}); pad them as Units_Encoder.encode does")
+        if self.rows(L) > self.dims["n_ctx"]:
+            raise ValueError(f"Wav2Vec2Bert: {L} samples give {self.rows(L)} rows, more than n_ctx {self.dims['n_ctx']}")
+        return B, L
+
+    def _run(self, entry, width, audio, lengths, ws):
+        import torch
+        B, L = self._check_audio(audio)
+        ln = self.lengths(lengths, B, L) if lengths is not None else None
+        _dev(audio, None)
+        ws = ws if ws is not None else self.ws.get(self.workspace_bytes(B, L), audio.device)
+        out = torch.empty(B, self.rows(L), width, dtype=torch.float32, device=audio.device)
+        check(getattr(lib(), entry)(self.h, _dev(audio, torch.float32), _host(ln), _dev(out), _dev(ws), ws.numel(), B, L, _stream()))
+        return out
+
+    def fbank(self, audio, lengths=None, ws=None):
+        return self._run("lds_w2vbert_fbank", self.dims["n_mels"] * self.dims["stride"], audio, lengths, ws)
+
+    def encode(self, audio, lengths=None, ws=None):
+        return self._run("lds_w2vbert_encode", self.dims["n_state"], audio, lengths, ws)
+
+    def encode_features(self, feats, n_frames=None, ws=None):
+        """feats [B, R, n_mels * stride] (input_features) -> [B, R, n_state]; n_frames: every clip's frame count n (host ints, 2 .. stride R;
+        rows at and beyond n // stride are masked), None = stride R"""
+        import torch
+        st, fd = self.dims["stride"], self.dims["n_mels"] * self.dims["stride"]
+        if feats.dim() != 3 or feats.shape[2] != fd:
+            raise ValueError(f"Wav2Vec2Bert: features must be [B, R, {fd}], got {list(feats.shape)}")
+        B, R = feats.shape[0], feats.shape[1]
+        if not 1 <= B <= self.MAX_CLIPS:
+            raise ValueError(f"Wav2Vec2Bert: 1 .. {self.MAX_CLIPS} clips per call (got {B})")
+        if not 1 <= R <= self.dims["n_ctx"]:
+            raise ValueError(f"Wav2Vec2Bert: {R} rows outside 1 .. n_ctx {self.dims['n_ctx']}")
+        nf = None
+        if n_frames is not None:
+            nf = _host_lengths(n_frames, B, max(2, st), st * R, self.MAX_CLIPS, "units")
+        _dev(feats, None)
+        ws = ws if ws is not None else self.ws.get(self.workspace_bytes(B, 400 + 160 * (st * R - 1)), feats.device)
+        out = torch.empty(B, R, self.dims["n_state"], dtype=torch.float32, device=feats.device)
+        check(lib().lds_w2vbert_encode_features(self.h, _dev(feats, torch.float32), _host(nf), _dev(out), _dev(ws), ws.numel(), B, R, _stream()))
+        return out
 
 
 class Whisper(_Handle):

@@ -1,8 +1,10 @@
 """The pieces of reference tools/tools.py that are built: the encoder-width table, `units_forced_alignment` (and its per-clip form
 `units_forced_alignment_ragged`), the units encoders (`Units_Encoder` over `WhisperLargeV3`, reference tools/tools.py:43-126, or over
-`HubertUnits`: the reference's encoder/hubert/model.py as 'hubertsoft' / 'contentvec768l12', or over `Audio2xlsr_53_56k`: wav2vec 2.0 XLSR-53),
+`HubertUnits`: the reference's encoder/hubert/model.py as 'hubertsoft' / 'contentvec768l12', or over `Audio2xlsr_53_56k`: wav2vec 2.0 XLSR-53,
+or over `Wav2Vec2Bert`: w2v-BERT 2.0),
 `Volume_Extractor`, `upsample` and `cross_fade` (tools/tools.py:12-41, 225-238) and `Resample`, the torchaudio transform that file imports
-(tools/tools.py:9).  'w2v-bert', 'xlsr_53_56k' loaded through fairseq (its default) and the schedulers there are not built."""
+(tools/tools.py:9).  'w2v-bert' downloaded from the hub and 'xlsr_53_56k' loaded through fairseq (the reference's defaults) and the schedulers
+there are not built."""
 import math
 
 import numpy as np
@@ -10,6 +12,7 @@ import torch
 
 from encoder.hubert.model import HubertSoft
 from encoder.wav2vec2.model import Wav2Vec2, load_checkpoint_state
+from encoder.wav2vec2_bert.model import Wav2Vec2BertModel, load_checkpoint_state as load_w2vbert_checkpoint_state
 from encoder.whisper.model import ModelDimensions, Whisper
 from lds import arch, native
 from lds.arch import get_encoder_out_channels
@@ -158,20 +161,23 @@ class Resample(torch.nn.Module):
 class Units_Encoder:
     """Speech -> units (reference tools/tools.py:43-103).  Built: encoder 'whisper_large_v3' in the 'nearest' / 'left' modes, and the
     HuBERT stack (HubertUnits below) as 'hubertsoft' (256-wide soft units) and 'contentvec768l12' (its 768-wide last layer), and
-    'xlsr_53_56k' (Audio2xlsr_53_56k below: wav2vec 2.0 XLSR-53, 1024-wide) with `model=` or `checkpoint=`.  Frame counts and the
-    shortest clip come from the model (`frames_of`, `min_samples`): (L // 160 - 1) // 2 + 1 and 400 samples for Whisper, L // 320
-    and 320 for HuBERT, the unpadded level rule (400 samples -> 1 frame) and 400 for XLSR-53.
+    'xlsr_53_56k' (Audio2xlsr_53_56k below: wav2vec 2.0 XLSR-53, 1024-wide) and 'w2v-bert' (Wav2Vec2Bert below: w2v-BERT 2.0, 1024-wide),
+    each with `model=` or `checkpoint=`.  Frame counts and the shortest clip come from the model (`frames_of`, `min_samples`):
+    (L // 160 - 1) // 2 + 1 and 400 samples for Whisper, L // 320 and 320 for HuBERT, the unpadded level rule (400 samples -> 1 frame) and
+    400 for XLSR-53, ceil((1 + (L - 400) // 160) / 2) rows and 560 for w2v-BERT (whose last row is the reference's masked row when the
+    frame count is odd: Wav2Vec2Bert's docstring).
     Deviations from the reference, each raising instead of guessing:
       - resampling is opt-in: by default `sample_rate` must equal `encoder_sample_rate` (ValueError naming both), where the reference
         resamples with torchaudio; with `resample=True` (keyword-only, not in the reference) a mismatched rate goes through
         `self.resample_kernel[str(sample_rate)]`, a `Resample(sample_rate, encoder_sample_rate)` made on first use as the reference
         makes it (tools/tools.py:81-84), in encode, encode_ragged and the encode_tokens* forms;
       - the units stay on the device (the reference moves them to the CPU); CPU tensors raise, there is no CPU fallback;
-      - 'w2v-bert' needs a transformers hub download: NotImplementedError; 'xlsr_53_56k' with neither `model=` nor `checkpoint=` is the
-        reference's fairseq load of pretrain/xlsr_53_56k.pt: NotImplementedError; the 'rfa441to512' / 'rfa512to441' modes need
-        librosa's resampler: NotImplementedError.
-    `model` (not in the reference): a ready WhisperLargeV3 / HubertUnits / Audio2xlsr_53_56k, e.g. WhisperLargeV3.synthetic(...), instead
-    of the checkpoint; `checkpoint` (keyword-only, not in the reference): the file a HuBERT or XLSR-53 encoder loads its state dict from."""
+      - 'w2v-bert' with neither `model=` nor `checkpoint=` is the reference's transformers hub download: NotImplementedError;
+        'xlsr_53_56k' with neither is the reference's fairseq load of pretrain/xlsr_53_56k.pt: NotImplementedError; the 'rfa441to512' /
+        'rfa512to441' modes need librosa's resampler: NotImplementedError.
+    `model` (not in the reference): a ready WhisperLargeV3 / HubertUnits / Audio2xlsr_53_56k / Wav2Vec2Bert, e.g.
+    WhisperLargeV3.synthetic(...), instead of the checkpoint; `checkpoint` (keyword-only, not in the reference): the file a HuBERT, XLSR-53
+    or w2v-BERT encoder loads its state dict from."""
 
     def __init__(self, encoder, encoder_sample_rate=16000, encoder_hop_size=320, device=None, units_forced_mode='nearest', *, model=None, resample=False, checkpoint=None):
         if device is None:
@@ -181,12 +187,13 @@ class Units_Encoder:
         if units_forced_mode is None:
             units_forced_mode = 'left'
         self.units_forced_mode = units_forced_mode
-        if encoder == 'w2v-bert':
-            raise NotImplementedError("Units_Encoder: 'w2v-bert' needs transformers' from_pretrained('facebook/w2v-bert-2.0') download; not built")
+        if encoder == 'w2v-bert' and model is None and checkpoint is None:
+            raise NotImplementedError("Units_Encoder: 'w2v-bert' by default downloads transformers' from_pretrained('facebook/w2v-bert-2.0'), which is "
+                                      "not built; pass checkpoint=PATH (the state dict in transformers naming, torch-saved or .safetensors) or model=")
         if encoder == 'xlsr_53_56k' and model is None and checkpoint is None:
             raise NotImplementedError("Units_Encoder: 'xlsr_53_56k' by default loads pretrain/xlsr_53_56k.pt through fairseq, which is not built; "
                                       "pass checkpoint=PATH (a state dict of plain tensors, fairseq or transformers naming) or model=")
-        if encoder not in ('whisper_large_v3', 'xlsr_53_56k') + HubertUnits.NAMES:
+        if encoder not in ('whisper_large_v3', 'xlsr_53_56k', 'w2v-bert') + HubertUnits.NAMES:
             raise ValueError(f"[x] Unknown units encoder: {encoder}")
         if units_forced_mode in ('rfa441to512', 'rfa512to441'):
             raise NotImplementedError(f"units_forced_mode {units_forced_mode!r} resamples with librosa; not built")
@@ -198,6 +205,8 @@ class Units_Encoder:
             self.model = HubertUnits(encoder, device=device, checkpoint=checkpoint)
         elif encoder == 'xlsr_53_56k':
             self.model = Audio2xlsr_53_56k(device=device, checkpoint=checkpoint)
+        elif encoder == 'w2v-bert':
+            self.model = Wav2Vec2Bert(device=device, checkpoint=checkpoint)
         else:
             self.model = WhisperLargeV3(device=device)
         self.min_samples = getattr(self.model, "min_samples", 400)
@@ -222,7 +231,8 @@ class Units_Encoder:
 
     def encode(self, audio, sample_rate, padding_mask=None):
         """audio [L] or [1, L] -> units [T, C] on the device (reference tools/tools.py:76-103; padding_mask is ignored as
-        WhisperLargeV3.__call__ ignores it); a clip shorter than 400 samples is zero-padded to 400 as the reference does"""
+        WhisperLargeV3.__call__ ignores it); a clip shorter than 400 samples (the model's `min_samples`: 560 with w2v-BERT) is zero-padded to
+        that length as the reference pads to 400"""
         rs = self._check("Units_Encoder.encode", audio, sample_rate)
         if rs is not None:
             audio = rs(audio)
@@ -245,7 +255,7 @@ class Units_Encoder:
         rs = self._check("Units_Encoder.encode_ragged", audio, self.encoder_sample_rate if sample_rate is None else sample_rate)
         if rs is not None:
             audio, lengths = rs.forward_ragged(audio, lengths)
-        lo = self.min_samples      # (400 with Whisper and XLSR-53; 320 with a HuBERT encoder)
+        lo = self.min_samples      # (400 with Whisper and XLSR-53; 320 with a HuBERT encoder; 560 with w2v-BERT)
         if (rs is not None or pad_short) and audio.size(-1) < lo:
             audio = torch.nn.functional.pad(audio, (0, lo - audio.size(-1)))
         if pad_short:
@@ -367,6 +377,63 @@ class Audio2xlsr_53_56k(torch.nn.Module):
         ln = native.Wav2Vec2.lengths(lengths, B, L)      # (host-side validation first: a bad length is a ValueError on any device)
         if not audio.is_cuda:
             raise RuntimeError("Audio2xlsr_53_56k.encode_ragged needs the audio on a HIP device (no CPU fallback)")
+        units = self.model.native().encode(audio.float().contiguous(), ln)
+        return units, torch.from_numpy(np.array([self.frames_of(int(n)) for n in ln], dtype=np.int64))
+
+
+class Wav2Vec2Bert(torch.nn.Module):
+    """reference tools/tools.py Wav2Vec2Bert: w2v-BERT 2.0, units = Wav2Vec2BertModel(**SeamlessM4TFeatureExtractor(audio,
+    sampling_rate=16000)).last_hidden_state, 1024 wide.  The reference downloads both from the hub; here `checkpoint` is a local file holding
+    the model's state dict in transformers naming (torch-saved plain tensors, or .safetensors;
+    encoder.wav2vec2_bert.model.load_checkpoint_state), or `dims` + `state` (keyword-only) inject the weights directly, and the feature
+    extractor is the native filter bank (it has no weights).  Nothing is downloaded.
+    A clip of n = 1 + (L - 400) // 160 frames gives (n + 1) // 2 rows.  With n odd the last of them is the MASKED ROW: the extractor pads the
+    frames to an even count, the model masks the padded row as an attention key and zeroes it behind the feature projection and in front of
+    the convolution module, but still returns it -- and so does this class.  A caller who does not want it drops row n // 2 when n is odd."""
+    min_samples = arch.W2VBERT_MIN_SAMPLES
+    family = "w2v-BERT"
+
+    def __init__(self, device='cuda', *, checkpoint=None, dims=None, state=None):
+        super().__init__()
+        self.device = device
+        if state is None:
+            if checkpoint is None:
+                raise NotImplementedError("Wav2Vec2Bert: the reference downloads transformers' from_pretrained('facebook/w2v-bert-2.0'), which is "
+                                          "not built; pass checkpoint=PATH or dims= / state=")
+            print('w2v-bert')
+            state = load_w2vbert_checkpoint_state(checkpoint)
+        model = Wav2Vec2BertModel(dims)
+        model.load_state_dict(state)
+        self.model = model.eval()
+        self.hidden_dim = model.dims["n_state"]
+        self.n_ctx = model.dims["n_ctx"]      # the window of one call, in rows
+
+    @classmethod
+    def synthetic(cls, dims=None, seed=0, device='cuda'):
+        """seeded weights (lds.arch.w2vbert_init_state) for `dims` (default: w2v-BERT 2.0's) -- no checkpoint ships"""
+        dims = dict(arch.W2V_BERT_DIMS if dims is None else dims)
+        return cls(device=device, dims=dims, state=arch.w2vbert_init_state(dims, seed))
+
+    @staticmethod
+    def frames_of(n_samples):
+        """rows of a clip, the masked row of an odd frame count included"""
+        return arch.w2vbert_frames(n_samples)[2]
+
+    @torch.inference_mode()
+    def __call__(self, audio, padding_mask=None):
+        """audio (any shape, flattened into ONE clip) -> units [rows, C] on the device; padding_mask is ignored (the reference ignores it)"""
+        if not torch.is_tensor(audio) or not audio.is_cuda:
+            raise RuntimeError("Wav2Vec2Bert needs the audio as a tensor on a HIP device (no CPU fallback)")
+        return self.model.native().encode(audio.reshape(1, -1).float().contiguous()).squeeze(0)
+
+    @torch.inference_mode()
+    def encode_ragged(self, audio, lengths):
+        if audio.dim() != 2:
+            raise ValueError(f"Wav2Vec2Bert.encode_ragged: audio must be [B, L], got {list(audio.shape)}")
+        B, L = audio.shape
+        ln = native.Wav2Vec2Bert.lengths(lengths, B, L)      # (host-side validation first: a bad length is a ValueError on any device)
+        if not audio.is_cuda:
+            raise RuntimeError("Wav2Vec2Bert.encode_ragged needs the audio on a HIP device (no CPU fallback)")
         units = self.model.native().encode(audio.float().contiguous(), ln)
         return units, torch.from_numpy(np.array([self.frames_of(int(n)) for n in ln], dtype=np.int64))
 

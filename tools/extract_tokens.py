@@ -2,7 +2,7 @@
 
     python tools/extract_tokens.py IN_DIR [--out DIR] [--codebook pretrain/semantic_codebook.pt | --synthetic K [--seed S]] [--batch 8]
                                    [--from-audio [--checkpoint pretrain/large-v3_encoder.pt | --synthetic-encoder [--layers N]]
-                                    [--sample-rate R] [--encoder {whisper_large_v3,hubertsoft,contentvec768l12}]]
+                                    [--sample-rate R] [--encoder {whisper_large_v3,hubertsoft,contentvec768l12,w2v-bert}]]
 
 IN_DIR holds .npy unit files [T, dim] (tools/extract_units.py writes them).  Every file becomes DIR/<name>.npy (default DIR:
 IN_DIR/../semantic_token) of int64 tokens [T]: the index of the nearest centre of the codebook, computed on the HIP device by
@@ -12,7 +12,8 @@ a file's tokens do not depend on its batch.  --synthetic K uses K seeded N(0, 1)
 tools/extract_units.py reads them; what is not at 16 kHz is resampled on the device inside its batch); every batch goes through
 Units_Encoder.encode_tokens_ragged (Whisper units, then the nearest centre) without leaving the device.  --synthetic-encoder
 runs seeded encoder weights at large-v3's width (--layers sets the depth) where no checkpoint exists.  --encoder hubertsoft /
-contentvec768l12 encodes with the HuBERT stack instead (tools.tools.HubertUnits; --checkpoint then names a HubertSoft state dict).
+contentvec768l12 encodes with the HuBERT stack instead (tools.tools.HubertUnits; --checkpoint then names a HubertSoft state dict);
+--encoder w2v-bert with w2v-BERT 2.0 (tools.tools.Wav2Vec2Bert; --checkpoint names its state dict in transformers naming).
 """
 import argparse
 import os
@@ -30,7 +31,7 @@ import cluster  # noqa: E402
 def units_encoder(a):
     from encoder.whisper.model import ModelDimensions
     from lds import arch
-    from tools.tools import HubertUnits, Units_Encoder, WhisperLargeV3
+    from tools.tools import HubertUnits, Units_Encoder, Wav2Vec2Bert, WhisperLargeV3
     if a.encoder in HubertUnits.NAMES:
         if a.synthetic_encoder:
             model = HubertUnits.synthetic(a.encoder, dict(arch.HUBERT_BASE_DIMS, n_layer=a.layers or 12), seed=a.seed, device="cuda")
@@ -38,6 +39,13 @@ def units_encoder(a):
             raise SystemExit(f"--encoder {a.encoder} needs --checkpoint (a HubertSoft state dict) or --synthetic-encoder")
         else:
             model = HubertUnits(a.encoder, device="cuda", checkpoint=a.checkpoint)
+    elif a.encoder == "w2v-bert":
+        if a.synthetic_encoder:
+            model = Wav2Vec2Bert.synthetic(dict(arch.W2V_BERT_DIMS, n_layer=a.layers or 24), seed=a.seed, device="cuda")
+        elif a.checkpoint is None:
+            raise SystemExit("--encoder w2v-bert needs --checkpoint (the model's state dict in transformers naming) or --synthetic-encoder")
+        else:
+            model = Wav2Vec2Bert(device="cuda", checkpoint=a.checkpoint)
     elif a.synthetic_encoder:
         model = WhisperLargeV3.synthetic(ModelDimensions(**dict(arch.WHISPER_LARGE_V3_DIMS, n_audio_layer=a.layers or 32)), seed=a.seed, device="cuda")
     else:
@@ -55,7 +63,7 @@ def main():
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--from-audio", action="store_true", help="IN_DIR holds audio clips: encode them to units first")
     ap.add_argument("--sample-rate", type=int, default=16000, help="--from-audio: rate of the .npy clips (a .wav carries its own)")
-    ap.add_argument("--encoder", default="whisper_large_v3", choices=("whisper_large_v3", "hubertsoft", "contentvec768l12"))
+    ap.add_argument("--encoder", default="whisper_large_v3", choices=("whisper_large_v3", "hubertsoft", "contentvec768l12", "w2v-bert"))
     ap.add_argument("--checkpoint", default=None, help="default: pretrain/large-v3_encoder.pt for whisper_large_v3")
     ap.add_argument("--synthetic-encoder", action="store_true", help="seeded encoder weights instead of the checkpoint")
     ap.add_argument("--layers", type=int, default=None, help="depth of the synthetic encoder (default 32; 12 for a HuBERT encoder)")

@@ -1,7 +1,7 @@
 """Encode clips to units with Whisper large-v3 (default) or a HuBERT encoder (the reference's 10_preprocess_train_unit.py flow; the counterpart of tools/extract_latents.py).
 
     python tools/extract_units.py IN [--out DIR] [--checkpoint pretrain/large-v3_encoder.pt | --synthetic [--layers N] [--seed S]] [--batch 8]
-                                     [--sample-rate R] [--encoder {whisper_large_v3,hubertsoft,contentvec768l12,xlsr_53_56k}]
+                                     [--sample-rate R] [--encoder {whisper_large_v3,hubertsoft,contentvec768l12,xlsr_53_56k,w2v-bert}]
 
 IN is a directory (every .npy / .wav in it, sorted) or a text file listing one clip per line.  A .npy holds 1-D float32 samples at
 --sample-rate (default 16000); a .wav is PCM16 of any rate, read from its header (mono, or the first channel is taken).  Clips that
@@ -16,6 +16,9 @@ n_audio_ctx frames, counted at 16 kHz) are refused, as the data set's own prepar
 shorter than 320 samples zero-padded to 320; --checkpoint then names a HubertSoft state dict, and --synthetic's default depth is 12.
 --encoder xlsr_53_56k runs wav2vec 2.0 XLSR-53 (tools.tools.Audio2xlsr_53_56k): [T, 1024], T by the unpadded level rule (400 samples -> 1
 frame, 16000 -> 49); --checkpoint names a state dict of plain tensors in fairseq or transformers naming; --synthetic's default depth is 24.
+--encoder w2v-bert runs w2v-BERT 2.0 (tools.tools.Wav2Vec2Bert): [rows, 1024], rows = ceil((1 + (len - 400) // 160) / 2) (16000 samples -> 49;
+the last row of a clip with an odd frame count is the reference's masked row), clips shorter than 560 samples zero-padded to 560;
+--checkpoint names the model's state dict in transformers naming (torch-saved or .safetensors); --synthetic's default depth is 24.
 """
 import argparse
 import os
@@ -29,7 +32,7 @@ import torch  # noqa: E402
 
 from encoder.whisper.model import ModelDimensions  # noqa: E402
 from lds import arch  # noqa: E402
-from tools.tools import Audio2xlsr_53_56k, HubertUnits, Resample, Units_Encoder, WhisperLargeV3  # noqa: E402
+from tools.tools import Audio2xlsr_53_56k, HubertUnits, Resample, Units_Encoder, Wav2Vec2Bert, WhisperLargeV3  # noqa: E402
 
 ENCODER_RATE = 16000
 _resamplers = {}
@@ -77,10 +80,10 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("inp", help="directory of .npy / .wav clips, or a text file listing them")
     ap.add_argument("--out", default=None)
-    ap.add_argument("--encoder", default="whisper_large_v3", choices=("whisper_large_v3",) + HubertUnits.NAMES + ("xlsr_53_56k",))
+    ap.add_argument("--encoder", default="whisper_large_v3", choices=("whisper_large_v3",) + HubertUnits.NAMES + ("xlsr_53_56k", "w2v-bert"))
     ap.add_argument("--checkpoint", default=None, help="default: pretrain/large-v3_encoder.pt for whisper_large_v3; required for a HuBERT encoder")
     ap.add_argument("--synthetic", action="store_true", help="seeded weights instead of the checkpoint")
-    ap.add_argument("--layers", type=int, default=None, help="depth of the --synthetic model (default 32; 12 for a HuBERT encoder, 24 for xlsr_53_56k)")
+    ap.add_argument("--layers", type=int, default=None, help="depth of the --synthetic model (default 32; 12 for a HuBERT encoder, 24 for xlsr_53_56k and w2v-bert)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--sample-rate", type=int, default=ENCODER_RATE, help="rate of the .npy clips (a .wav carries its own)")
@@ -107,6 +110,13 @@ def main():
             ap.error("--encoder xlsr_53_56k needs --checkpoint (a wav2vec 2.0 state dict of plain tensors) or --synthetic")
         else:
             model = Audio2xlsr_53_56k(device="cuda", checkpoint=a.checkpoint)
+    elif a.encoder == "w2v-bert":
+        if a.synthetic:
+            model = Wav2Vec2Bert.synthetic(dict(arch.W2V_BERT_DIMS, n_layer=a.layers or 24), seed=a.seed, device="cuda")
+        elif a.checkpoint is None:
+            ap.error("--encoder w2v-bert needs --checkpoint (the model's state dict in transformers naming) or --synthetic")
+        else:
+            model = Wav2Vec2Bert(device="cuda", checkpoint=a.checkpoint)
     elif a.synthetic:
         model = WhisperLargeV3.synthetic(ModelDimensions(**dict(arch.WHISPER_LARGE_V3_DIMS, n_audio_layer=a.layers or 32)), seed=a.seed, device="cuda")
     else:
