@@ -131,6 +131,38 @@ int lds_resample_frames(const float* in, float* out, int B, int Tin, int Tout, i
 /* out = c0*a + c1*b over n elements (q_sample of shallow diffusion, reference diffusion.py:169-171) */
 int lds_axpby(float* out, const float* a, const float* b, float c0, float c1, int64_t n, void* stream);
 
+/* ---- the diffusion loss of the validation pass (reference diffusion.py:169-187: q_sample with one timestep per item, the denoiser, the mean
+ *      residual; evaluated without gradients, reference solver.py:56-62) ------------------------------------------------------------------
+ * lds_q_sample_rows: out[b][i] = sqrt_ac[t[b]] * x0[b][i] + sqrt_1m_ac[t[b]] * noise[b][i] over rows of n elements; the two products are
+ * rounded separately and then added, so the result has the reference's bits.  t dev int64 [B], read on the device and clamped into
+ * [0, n_steps); the tables dev fp32 [n_steps]; t_f32 (dev [B] or NULL) receives t as fp32, the time input of lds_unet_forward.
+ * lds_loss_reduce: out[0] (dev) = mean((a - b)^2) (loss_type 2, F.mse_loss) or mean(|a - b|) (loss_type 1) over n elements.  Deterministic:
+ * fixed slices of 4096 elements per workgroup, each summed in a fixed tree in double, and one fixed-order second stage over the partial sums
+ * in ws (lds_loss_reduce_workspace_bytes(n), 8-byte aligned); no atomics. */
+int lds_q_sample_rows(float* out, const float* x0, const float* noise, const int64_t* t, const float* sqrt_ac, const float* sqrt_1m_ac,
+                      int n_steps, float* t_f32, int B, int64_t n, void* stream);
+int lds_loss_reduce_workspace_bytes(int64_t n, size_t* out);
+int lds_loss_reduce(const float* a, const float* b, int64_t n, int loss_type, float* out, void* ws, size_t ws_bytes, void* stream);
+
+/* ---- the vocoder's log-mel analysis (reference encoder/hifi_vaegan/modules/nvSTFT.py:69-118, STFT.get_mel with center = False) --------
+ * audio dev [B][L] -> out dev [B][F][n_mels] = log(max(mel_basis @ |STFT(pad(audio))|, clip_val)), frame-major, as one launch.
+ * Geometry, resolved by the caller from (keyshift, speed): n_fft_new = round(n_fft * 2^(keyshift/12)), win_new likewise from win, hop_new =
+ * round(hop * speed).  The library pads each clip as the reference does -- (win_new - hop_new) / 2 samples on the left, max((win_new - hop_new
+ * + 1) / 2, win_new - len - left) on the right, reflected when the right pad is shorter than the clip and zeros otherwise -- and takes
+ * 1 + (len + left + right - n_fft_new) / hop_new frames; nothing at or beyond a clip's length is read.
+ * basis: dev double [n_fft_new][bins][2], bins = min(n_fft_new / 2 + 1, n_fft / 2 + 1): (cos, -sin)(2 pi n k / n_fft_new) times the window
+ * (centred in n_fft_new).  mel_basisT: dev fp32 [n_fft / 2 + 1][n_mels], the transposed filter bank.  When win_new != win the magnitudes are
+ * scaled by win / win_new, and bins at and beyond `bins` count as zeros (nvSTFT.py:110-115).  The DFT sums run in double on the f64 matrix
+ * pipe, the rest in fp32.
+ * lengths: host int32 [B] (B <= 64; 1 .. L) or NULL = every clip has L samples.  Each clip's padding mode and frame count follow its own
+ * length; its rows [0, F_b) equal the clip run alone bit for bit, rows [F_b, F) are zeros.  F: the rows of out, at least the longest clip's
+ * frames.  n_mels <= 128; 15 hop_new + n_fft_new samples must fit the workgroup's LDS (LDS_EINVAL otherwise).
+ * The launch keeps the spectrum inside the workgroup, so lds_stft_mel_workspace_bytes answers 0 today and ws may be NULL. */
+int lds_stft_mel_workspace_bytes(int n_fft_new, int hop_new, int n_mels, int B, int64_t L, size_t* out);
+int lds_stft_mel(const float* audio, const int32_t* lengths, const double* basis, const float* mel_basisT, int n_fft_new, int win_new,
+                 int hop_new, int n_fft, int win, int n_mels, float clip_val, int F, float* out, void* ws, size_t ws_bytes, int B, int64_t L,
+                 void* stream);
+
 /* ---- vocoder: HiFi-VAEGAN Generator (reference encoder/hifi_vaegan/modules/models.py:224-272,
  *      hifi_vaegan.py:52-65) ------------------------------------------------------------------- */
 typedef struct {

@@ -203,6 +203,12 @@ int lds_test_w2vbert_attention(const float* qkv, const float* E, const int32_t* 
 int lds_test_w2vbert_dwconv(const float* x, const float* w, const float* gamma, const float* beta, float eps, const int32_t* in_rows, const int32_t* out_rows,
                             float* out, int B, int C, int T, int K, void* stream);
 
+/* csrc/stftmel.hip's framed DFT alone: the frames of audio [B][L] as they are (no padding; F = 1 + (L - n_fft_new) / hop_new rows) times
+ * basis [n_fft_new][n_fft_new / 2 + 1][2] -> dft dev double [B][F][n_fft_new / 2 + 1][2], the raw sums before the magnitude (an integer-valued
+ * asymmetric basis makes them exact: a swapped row / column of the f64 MFMA's C/D map shows); out dev [B][F][n_mels] as lds_stft_mel.  Synchronises. */
+int lds_test_stft_dft(const float* audio, const double* basis, const float* mel_basisT, int n_fft_new, int hop_new, int n_mels, int F, float* out,
+                      double* dft, int B, int64_t L, void* stream);
+
 /* ---- debugging aids (tests/test_gpu_poison.py, tools/diag_trace.py) ----------------------------------------------------------
  * lds_debug_fill_u32: every 32-bit word of a device buffer = pattern.  Tests fill a caller workspace with NaN patterns (0x7fc07fc0 is a NaN
  * as fp32 and as two fp16 / bf16 halves) before a call: a kernel that reads a slot no kernel of THAT call wrote turns it into a NaN (or, behind

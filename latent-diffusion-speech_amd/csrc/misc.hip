@@ -3,6 +3,7 @@
 // (reference dpm_solver_pytorch.py:433-442,547-580,796-831; uni_pc.py:547-567;
 // diffusion.py:95-167), layout transposes at the module boundary, speaker-embedding gather.
 #include "kernels.h"
+#include "../../include/lds.h"
 
 #include <math.h>
 
@@ -248,3 +249,111 @@ hipError_t launch_resample_nearest(const float* in, float* out, int B, int C, in
 }
 
 }  // namespace lds
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// The diffusion loss (reference diffusion.py:169-187, p_losses under no_grad: the validation pass)
+// ---------------------------------------------------------------------------------------------------------------------------------
+namespace lds {
+
+// q_sample with one timestep per batch row: out[b][i] = sa[t_b] x0[b][i] + s1[t_b] noise[b][i], the two products rounded on their own and then
+// added (what the reference's two multiplications and one addition give); t_b is read from the device and clamped into the tables.
+// tf (or null) receives t_b as fp32, the denoiser's time input.  grid (blocks, B).
+__global__ void __launch_bounds__(256) q_sample_rows_kernel(float* __restrict__ out, const float* __restrict__ x0, const float* __restrict__ noise,
+                                                            const long long* __restrict__ t, const float* __restrict__ sa, const float* __restrict__ s1,
+                                                            int n_steps, float* __restrict__ tf, long long n) {
+#pragma clang fp contract(off)
+    const int b = blockIdx.y;
+    long long tb = t[b];
+    tb = tb < 0 ? 0 : tb >= n_steps ? n_steps - 1 : tb;
+    const float c0 = sa[tb], c1 = s1[tb];
+    if (tf && blockIdx.x == 0 && threadIdx.x == 0) tf[b] = (float)tb;
+    const long long o = (long long)b * n;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256)
+        out[o + i] = __fadd_rn(__fmul_rn(c0, x0[o + i]), __fmul_rn(c1, noise[o + i]));
+}
+
+constexpr int LR_SLICE = 4096;      // elements per workgroup of the first stage: fixed, whatever the device
+
+// the 256 threads' sums in a fixed tree
+static __device__ __forceinline__ double block_sum_256(double v, double* red) {
+    red[threadIdx.x] = v;
+    __syncthreads();
+#pragma unroll
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+        __syncthreads();
+    }
+    return red[0];
+}
+
+// part[blk] = sum over the slice of (a - b)^2 (l2) or |a - b| (l1): the fp32 residual as the reference forms it, summed in double
+__global__ void __launch_bounds__(256) loss_partial_kernel(const float* __restrict__ a, const float* __restrict__ b, long long n, int l2,
+                                                           double* __restrict__ part) {
+    __shared__ double red[256];
+    const long long base = (long long)blockIdx.x * LR_SLICE;
+    double s = 0.0;
+#pragma unroll
+    for (int e = 0; e < LR_SLICE / 256; ++e) {
+        const long long i = base + e * 256 + threadIdx.x;
+        if (i < n) {
+            const float d = __fsub_rn(a[i], b[i]);
+            s += l2 ? (double)__fmul_rn(d, d) : (double)fabsf(d);
+        }
+    }
+    s = block_sum_256(s, red);
+    if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+
+// out[0] = (sum of part[0 .. nblk) in a fixed order) / n
+__global__ void __launch_bounds__(256) loss_finish_kernel(const double* __restrict__ part, int nblk, long long n, float* __restrict__ out) {
+    __shared__ double red[256];
+    double s = 0.0;
+    for (int i = threadIdx.x; i < nblk; i += 256) s += part[i];
+    s = block_sum_256(s, red);
+    if (threadIdx.x == 0) out[0] = (float)(s / (double)n);
+}
+
+}  // namespace lds
+
+namespace {
+constexpr long long kLossMaxN = 1LL << 40;
+long long loss_blocks(long long n) { return (n + lds::LR_SLICE - 1) / lds::LR_SLICE; }
+}  // namespace
+
+extern "C" int lds_q_sample_rows(float* out, const float* x0, const float* noise, const int64_t* t, const float* sqrt_ac, const float* sqrt_1m_ac, int n_steps,
+                                 float* t_f32, int B, int64_t n, void* stream) {
+    if (!out || !x0 || !noise || !t || !sqrt_ac || !sqrt_1m_ac) return lds::set_error(LDS_EINVAL, "lds_q_sample_rows: null pointer");
+    if (n_steps < 1 || B < 1 || B > 65535 || n < 1) return lds::set_error(LDS_EINVAL, "lds_q_sample_rows: bad argument");
+    long long blocks = (n + 255) / 256;
+    if (blocks > 1024) blocks = 1024;
+    hipStream_t s = (hipStream_t)stream;
+    lds::ProfScope ps(s, "ew", 0.0, 4.0 * 3.0 * (double)n * B);
+    hipLaunchKernelGGL(lds::q_sample_rows_kernel, dim3((unsigned)blocks, B), dim3(256), 0, s, out, x0, noise, reinterpret_cast<const long long*>(t), sqrt_ac,
+                       sqrt_1m_ac, n_steps, t_f32, (long long)n);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? LDS_OK : lds::set_error(LDS_EHIP, "lds_q_sample_rows: %s", hipGetErrorString(e));
+}
+
+extern "C" int lds_loss_reduce_workspace_bytes(int64_t n, size_t* out) {
+    if (!out || n < 1 || n > kLossMaxN) return lds::set_error(LDS_EINVAL, "lds_loss_reduce_workspace_bytes: bad argument");
+    *out = (size_t)loss_blocks(n) * sizeof(double);
+    return LDS_OK;
+}
+
+extern "C" int lds_loss_reduce(const float* a, const float* b, int64_t n, int loss_type, float* out, void* ws, size_t ws_bytes, void* stream) {
+    if (!a || !b || !out || !ws) return lds::set_error(LDS_EINVAL, "lds_loss_reduce: null pointer");
+    if (n < 1 || n > kLossMaxN) return lds::set_error(LDS_EINVAL, "lds_loss_reduce: n %lld outside 1 .. %lld", (long long)n, kLossMaxN);
+    if (loss_type != 1 && loss_type != 2) return lds::set_error(LDS_EINVAL, "lds_loss_reduce: loss_type %d (1 = l1, 2 = l2)", loss_type);
+    const long long nblk = loss_blocks(n);
+    if (ws_bytes < (size_t)nblk * sizeof(double)) return lds::set_error(LDS_ENOMEM, "lds_loss_reduce: workspace %zu < %zu bytes", ws_bytes, (size_t)nblk * sizeof(double));
+    if (((uintptr_t)ws & 7) != 0) return lds::set_error(LDS_EINVAL, "lds_loss_reduce: the workspace must be 8-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    lds::ProfScope ps(s, "loss_reduce", 3.0 * (double)n, 8.0 * (double)n);
+    hipLaunchKernelGGL(lds::loss_partial_kernel, dim3((unsigned)nblk), dim3(256), 0, s, a, b, (long long)n, loss_type == 2 ? 1 : 0, (double*)ws);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(lds::loss_finish_kernel, dim3(1), dim3(256), 0, s, (const double*)ws, (int)nblk, (long long)n, out);
+        e = hipGetLastError();
+    }
+    return e == hipSuccess ? LDS_OK : lds::set_error(LDS_EHIP, "lds_loss_reduce: %s", hipGetErrorString(e));
+}

@@ -2,7 +2,7 @@
 (reference diffusion/diffusion.py:45-343).  The sampling loops (DDPM p_sample, DDIM, PLMS,
 DPM-Solver++ 2M, UniPC-bh2) run inside liblds: this module only draws x_T / per-step noise with
 torch's generator (as the reference does), turns the noise schedule into a per-step table of fp32
-scalars, and hands both to `lds_sampler_run`.  Training (`infer=False`) is out of scope."""
+scalars, and hands both to `lds_sampler_run`.  `infer=False` evaluates the diffusion loss without gradients (the validation pass: `p_losses`); training is out of scope."""
 import math
 from collections import deque
 
@@ -245,6 +245,42 @@ class GaussianDiffusion(nn.Module):
         return native.axpby(x_start.contiguous(), noise.contiguous(), float(self._buf("sqrt_alphas_cumprod")[ti]),
                             float(self._buf("sqrt_one_minus_alphas_cumprod")[ti]))
 
+    def p_losses(self, x_start, t, cond, noise=None, loss_type="l2"):
+        """reference diffusion.py:173-187, evaluated without gradients as the validation pass does (reference solver.py:56-62):
+        x_start [B,1,M,T], t int64 [B] on the device, cond [B,H,T] -> mean((noise - eps)^2) ('l2') or mean(|noise - eps|) ('l1') as a 0-dim
+        device tensor.  q_sample gathers t on the device (no synchronisation), the denoiser is lds_unet_forward, the mean a deterministic
+        two-stage reduction (include/lds.h lds_q_sample_rows, lds_loss_reduce).  The noise, when not given, is torch.randn_like's."""
+        if loss_type not in native.LOSS_TYPES:
+            raise NotImplementedError(loss_type)
+        if not x_start.is_cuda:
+            raise RuntimeError("GaussianDiffusion.p_losses needs tensors on a HIP device (no CPU fallback)")
+        with torch.no_grad():
+            if noise is None:
+                noise = torch.randn_like(x_start)
+            b = x_start.shape[0]
+            x0 = x_start.float().reshape(b, self.out_dims, -1).contiguous()
+            nz = noise.float().reshape(b, self.out_dims, -1).contiguous()
+            if nz.shape != x0.shape:
+                raise ValueError(f"noise must have x_start's shape {tuple(x_start.shape)}, got {tuple(noise.shape)}")
+            t = t.reshape(-1).to(device=x0.device, dtype=torch.int64).contiguous()
+            x_noisy, tf = native.q_sample_rows(x0, nz, t, self.sqrt_alphas_cumprod, self.sqrt_one_minus_alphas_cumprod)
+            eps = self.denoise_fn.native().forward(x_noisy, cond.float().contiguous(), tf)
+            return native.loss_reduce(nz, eps, loss_type)
+
+    def loss(self, condition, gt_spec, k_step=None, *, t=None, noise=None, loss_type="l2"):
+        """forward(infer=False) (reference diffusion.py:193-201) with both random draws injectable: t int64 [B] instead of
+        torch.randint(0, t_max, (B,)), noise [B,1,M,T] instead of torch.randn_like -- as x_T= injects the sampler's start noise.
+        (forward itself keeps the reference's parameters, so the injection lives here.)"""
+        if not condition.is_cuda:
+            raise RuntimeError("GaussianDiffusion.forward needs tensors on a HIP device (no CPU fallback)")
+        b, device = condition.shape[0], condition.device
+        cond = native.transpose(condition.contiguous().float())                 # [B,H,T]
+        t_max = self.k_step if k_step is None else k_step
+        if t is None:
+            t = torch.randint(0, t_max, (b,), device=device).long()
+        norm_spec = native.transpose(self.norm_spec(gt_spec).contiguous().float())[:, None, :, :]      # [B,1,M,T]
+        return self.p_losses(norm_spec, t, cond=cond, noise=noise, loss_type=loss_type)
+
     def forward(self, condition, gt_spec=None, infer=True, infer_speedup=10, method="dpm-solver", k_step=None, use_tqdm=False, *, x_T=None):
         """reference diffusion.py:189 plus one optional keyword: x_T [B,1,M,T] = the start noise to use instead of drawing it (tests, seeded
         runs; the reference draws torch.randn itself, diffusion.py:201).  The samplers' other draws (DDPM: one per step) stay torch.randn."""
@@ -258,7 +294,12 @@ class GaussianDiffusion(nn.Module):
 
     def _sample(self, condition, gt_spec, infer, infer_speedup, method, k_step, lengths, x_T=None):
         if not infer:
-            raise NotImplementedError("training (p_losses) is out of scope for the MI355X sampler build")
+            if gt_spec is None:
+                raise NotImplementedError("infer=False evaluates the diffusion loss against gt_spec (the validation pass); "
+                                          "there is nothing to do without one: training is out of scope for this build")
+            if lengths is not None or x_T is not None:
+                raise ValueError("lengths and x_T apply to sampling (infer=True)")
+            return self.loss(condition, gt_spec, k_step)
         if not condition.is_cuda:
             raise RuntimeError("GaussianDiffusion.forward needs tensors on a HIP device (no CPU fallback)")
         b, device = condition.shape[0], condition.device

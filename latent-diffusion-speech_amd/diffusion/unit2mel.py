@@ -100,12 +100,17 @@ class Unit2Mel(nn.Module):
         """reference unit2mel.py:73 plus the optional x_T of GaussianDiffusion.forward (the start noise, given instead of drawn)"""
         return self._forward(units, volume, spk_id, aug_shift, gt_spec, infer, infer_speedup, method, None, x_T)
 
+    def loss(self, units, volume, spk_id=None, aug_shift=None, gt_spec=None, *, t=None, noise=None, loss_type="l2"):
+        """forward(infer=False) -- the diffusion loss of the validation pass, a 0-dim device tensor -- with the timestep and noise draws
+        injectable (GaussianDiffusion.loss)"""
+        return self._forward(units, volume, spk_id, aug_shift, gt_spec, False, None, None, None, None, loss_args=dict(t=t, noise=noise, loss_type=loss_type))
+
     def forward_ragged(self, units, lengths, spk_id=None, infer_speedup=10, method="unipc", x_T=None):
         """Extension (not in the reference): units [B, T, C] padded to the longest utterance + the utterances' own frame counts -> mel
         [B, T, M] with zeros beyond each length; every utterance as if it ran alone (GaussianDiffusion.forward_ragged)."""
         return self._forward(units, None, spk_id, None, None, True, infer_speedup, method, lengths, x_T)
 
-    def _forward(self, units, volume, spk_id, aug_shift, gt_spec, infer, infer_speedup, method, lengths, x_T=None):
+    def _forward(self, units, volume, spk_id, aug_shift, gt_spec, infer, infer_speedup, method, lengths, x_T=None, loss_args=None):
         # reference unit2mel.py:74-77: volume_embed is None, so a non-None volume cannot be embedded there either
         if volume is not None:
             raise NotImplementedError("volume_embed is None in the reference (unit2mel.py:55); pass volume=None")
@@ -126,6 +131,8 @@ class Unit2Mel(nn.Module):
         # x = unit_embed(units) + spk_embed(spk_id - 1), produced channel-major by liblds
         cond = self._native_embed().forward(units.contiguous().float(), spk_id)        # [B,H,T]
         x = native.transpose(cond)                                                     # [B,T,H] as the reference hands over
+        if loss_args is not None:
+            return self.decoder.loss(x, gt_spec, **loss_args)
         if lengths is not None:
             return self.decoder.forward_ragged(x, lengths, gt_spec=gt_spec, infer_speedup=infer_speedup, method=method, x_T=x_T)
         return self.decoder(x, gt_spec=gt_spec, infer=infer, infer_speedup=infer_speedup, method=method, use_tqdm=False, x_T=x_T)

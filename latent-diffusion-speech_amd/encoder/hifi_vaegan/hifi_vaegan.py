@@ -2,12 +2,14 @@
 `<model_path>/decoder.pth` = {'config': h, 'model': state_dict with weight-norm pairs}, lazily
 builds the native Generator on first call and maps z [B,T,C] -> wav [B,1,T*hop]; `extract` lazily
 builds the native encoder from `<model_path>/encoder.pth` (same layout) and maps audio [B,L] -> [B,T,2C]; `extract_ragged` does the same
-for a batch of clips of their own lengths."""
+for a batch of clips of their own lengths; `get_mel` is the log-mel analysis of a waveform (csrc/stftmel.hip)."""
 import os
 
 import torch
 
 from lds import native
+
+from .modules.nvSTFT import STFT
 
 
 def load_config(model_path):
@@ -30,6 +32,7 @@ class Hifi_VAEGAN(torch.nn.Module):
         self._state = state
         self._encoder_state = encoder_state
         self.h = h if h is not None else load_config(model_path)
+        self.stft = STFT(self.h["sampling_rate"], 128, 2048, 2048, 512, 40, 16000)
 
     def sample_rate(self):
         return self.h["sampling_rate"]
@@ -39,6 +42,12 @@ class Hifi_VAEGAN(torch.nn.Module):
 
     def dimension(self):
         return self.h["inter_channels"]
+
+    @torch.no_grad()
+    def get_mel(self, audio, keyshift=0):
+        """audio [B,L] -> the log-mel spectrogram [B,F,128] the validation pass compares (reference hifi_vaegan.py:67-70); stored
+        frame-major by the kernel, so no transpose runs"""
+        return self.stft.get_mel_frames(audio, keyshift=keyshift)
 
     @torch.no_grad()
     def extract(self, audio, only_z=False, only_mean=False, *, noise=None):

@@ -87,6 +87,11 @@ lds_transpose                    i:ppiiifp
 lds_gather_rows                  i:pppiiip
 lds_resample_frames              i:ppiiiifp
 lds_axpby                        i:pppffqp
+lds_q_sample_rows                i:ppppppipiqp
+lds_loss_reduce_workspace_bytes  i:qp
+lds_loss_reduce                  i:ppqippzp
+lds_stft_mel_workspace_bytes     i:iiiiqp
+lds_stft_mel                     i:ppppiiiiiifippziqp
 lds_vocoder_create               i:pipppp
 lds_vocoder_destroy              v:p
 lds_vocoder_workspace_bytes      i:piip
@@ -194,6 +199,7 @@ lds_test_w2v_ln_act              i:ppppfppiiip
 lds_test_w2vbert_fbank           i:pppiqp
 lds_test_w2vbert_attention       i:pppppiiiiiip
 lds_test_w2vbert_dwconv          i:ppppfpppiiiip
+lds_test_stft_dft                i:pppiiiippiqp
 """
 SIGNATURES = dict(ln.split() for ln in (_PUBLIC + _TEST).splitlines() if ln)
 EXPORTS = [ln.split()[0] for ln in _PUBLIC.splitlines() if ln]
@@ -487,6 +493,75 @@ def axpby(a, b, c0, c1):
     out = torch.empty_like(a)
     check(lib().lds_axpby(_dev(out), _dev(a, torch.float32), _dev(b, torch.float32), c0, c1, a.numel(), _stream()))
     return out
+
+
+def q_sample_rows(x0, noise, t, sqrt_ac, sqrt_1m_ac):
+    """x0, noise [B, ...] fp32, t int64 [B] (device), the two schedule tables fp32 [n_steps] (device) ->
+    (sqrt_ac[t_b] * x0[b] + sqrt_1m_ac[t_b] * noise[b], t as fp32 [B]); include/lds.h lds_q_sample_rows"""
+    import torch
+    B = x0.shape[0]
+    if noise.shape != x0.shape or tuple(t.shape) != (B,) or sqrt_ac.shape != sqrt_1m_ac.shape or sqrt_ac.dim() != 1:
+        raise ValueError(f"q_sample_rows: x0 {list(x0.shape)}, noise {list(noise.shape)}, t {list(t.shape)}")
+    out = torch.empty_like(x0)
+    tf = torch.empty(B, dtype=torch.float32, device=x0.device)
+    check(lib().lds_q_sample_rows(_dev(out), _dev(x0, torch.float32), _dev(noise, torch.float32), _dev(t, torch.int64), _dev(sqrt_ac, torch.float32),
+                                  _dev(sqrt_1m_ac, torch.float32), sqrt_ac.numel(), _dev(tf), B, x0.numel() // B, _stream()))
+    return out, tf
+
+
+LOSS_TYPES = {"l1": 1, "l2": 2}
+_loss_ws = Workspace()
+
+
+def loss_reduce(a, b, loss_type="l2", ws=None):
+    """mean((a - b)^2) ('l2') or mean(|a - b|) ('l1') as a 0-dim device tensor; deterministic (include/lds.h lds_loss_reduce).  `ws`: a caller's
+    uint8 workspace (tests poison it), else one kept per stream."""
+    import torch
+    if a.shape != b.shape or a.numel() < 1:
+        raise ValueError(f"loss_reduce: shapes {list(a.shape)} and {list(b.shape)}")
+    _dev(a, torch.float32)
+    nb = _bytes("lds_loss_reduce_workspace_bytes", a.numel())
+    if ws is None:
+        ws = _loss_ws.get(nb, a.device)
+    out = torch.empty(1, dtype=torch.float32, device=a.device)
+    check(lib().lds_loss_reduce(_dev(a, torch.float32), _dev(b, torch.float32), a.numel(), LOSS_TYPES[loss_type], _dev(out), _dev(ws), ws.numel(), _stream()))
+    return out.reshape(())
+
+
+def stft_mel(audio, basis, mel_basisT, n_fft_new, win_new, hop_new, n_fft, win, clip_val, F, lengths=None, ws=None):
+    """audio [B, L] -> log-mel [B, F, n_mels], frame-major, in one launch (include/lds.h lds_stft_mel).  basis: device float64
+    [n_fft_new, bins, 2]; mel_basisT: device fp32 [n_fft // 2 + 1, n_mels]; lengths: every clip's own sample count (host ints) or None;
+    F: the rows of the result (at least the longest clip's frames).  `ws`: a caller's uint8 workspace (the launch needs none today)."""
+    import torch
+    if audio.dim() != 2:
+        raise ValueError(f"stft_mel: audio must be [B, L], got {list(audio.shape)}")
+    B, L = audio.shape
+    n_mels = mel_basisT.shape[1]
+    bins = min(n_fft_new // 2 + 1, n_fft // 2 + 1)
+    if tuple(basis.shape) != (n_fft_new, bins, 2) or tuple(mel_basisT.shape) != (n_fft // 2 + 1, n_mels):
+        raise ValueError(f"stft_mel: basis {list(basis.shape)} / mel basis {list(mel_basisT.shape)} do not fit n_fft_new {n_fft_new}, n_fft {n_fft}")
+    ln = None if lengths is None else _host_lengths(lengths, B, 1, L, 64, "log-mel")
+    _dev(audio, None)
+    nb = _bytes("lds_stft_mel_workspace_bytes", n_fft_new, hop_new, n_mels, B, L)
+    if ws is not None and ws.numel() < nb:
+        raise ValueError(f"stft_mel: workspace of {ws.numel()} bytes, {nb} needed")
+    out = torch.empty(B, F, n_mels, dtype=torch.float32, device=audio.device)
+    check(lib().lds_stft_mel(_dev(audio, torch.float32), _host(ln), _dev(basis, torch.float64), _dev(mel_basisT, torch.float32), n_fft_new, win_new, hop_new,
+                             n_fft, win, n_mels, clip_val, F, _dev(out), _dev_or_null(ws), 0 if ws is None else ws.numel(), B, L, _stream()))
+    return out
+
+
+def stft_dft_probe(audio, basis, mel_basisT, n_fft_new, hop_new):
+    """the framed DFT of csrc/stftmel.hip alone: audio [B, L] -> raw (re, im) sums float64 [B, F, n_fft_new // 2 + 1, 2] (include/lds_test.h)"""
+    import torch
+    B, L = audio.shape
+    F, bins, n_mels = 1 + (L - n_fft_new) // hop_new, n_fft_new // 2 + 1, mel_basisT.shape[1]
+    assert tuple(basis.shape) == (n_fft_new, bins, 2) and tuple(mel_basisT.shape) == (bins, n_mels)
+    out = torch.empty(B, F, n_mels, dtype=torch.float32, device=audio.device)
+    dft = torch.zeros(B, F, bins, 2, dtype=torch.float64, device=audio.device)
+    check(lib().lds_test_stft_dft(_dev(audio, torch.float32), _dev(basis, torch.float64), _dev(mel_basisT, torch.float32), n_fft_new, hop_new, n_mels, F,
+                                  _dev(out), _dev(dft), B, L, _stream()))
+    return dft
 
 
 def gather_rows(table, idx):
