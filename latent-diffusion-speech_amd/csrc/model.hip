@@ -2229,6 +2229,14 @@ static int run_down(const DownW& d, const float* x, int64_t L, float slope, floa
     return LDS_OK;
 }
 
+// per-clip counts given by the caller (here and in the units encoders below): no more than 64 of them, every value in lo .. hi
+static int clip_lens_check(const char* name, const int32_t* v, int B, int64_t lo, int64_t hi) {
+    if (B > 64) return fail(LDS_EINVAL, "per-clip lengths: at most 64 clips per call (got %d)", B);
+    for (int b = 0; b < B; ++b)
+        if (v[b] < lo || v[b] > hi) return fail(LDS_EINVAL, "%s[%d] = %d outside %lld .. %lld", name, b, v[b], (long long)lo, (long long)hi);
+    return LDS_OK;
+}
+
 static int vae_encoder_forward_impl(lds_vae_encoder* e, const float* audio, const int32_t* lens_host, const float* noise, float* out, float* z,
                                     int only_mean, void* ws, size_t ws_bytes, int B, int64_t L, void* stream);
 extern "C" int lds_vae_encoder_forward(lds_vae_encoder* e, const float* audio, const float* noise, float* out, float* z, int only_mean, void* ws,
@@ -2238,10 +2246,9 @@ extern "C" int lds_vae_encoder_forward(lds_vae_encoder* e, const float* audio, c
 extern "C" int lds_vae_encoder_forward_ragged(lds_vae_encoder* e, const float* audio, const int32_t* lengths, const float* noise, float* out, float* z,
                                               int only_mean, void* ws, size_t ws_bytes, int B, int64_t L, void* stream) {
     if (!lengths) return fail(LDS_EINVAL, "bad argument: lengths is null");
-    if (B > 64) return fail(LDS_EINVAL, "per-clip lengths: at most 64 clips per call (got %d)", B);
-    if (!enc_args_ok(e, B, L)) return fail(LDS_EINVAL, "bad argument (B %d, L %lld: B >= 1 and L a positive multiple of the hop)", B, (long long)L);
-    for (int b = 0; b < B; ++b)
-        if (lengths[b] < 1 || lengths[b] > L) return fail(LDS_EINVAL, "length[%d] = %d outside 1 .. %lld", b, lengths[b], (long long)L);
+    // more than 64 clips is refused before the other arguments are judged (clip_lens_check says so), the values after them
+    if (B <= 64 && !enc_args_ok(e, B, L)) return fail(LDS_EINVAL, "bad argument (B %d, L %lld: B >= 1 and L a positive multiple of the hop)", B, (long long)L);
+    LDS_TRY(clip_lens_check("length", lengths, B, 1, L));
     return vae_encoder_forward_impl(e, audio, lengths, noise, out, z, only_mean, ws, ws_bytes, B, L, stream);
 }
 static int vae_encoder_forward_impl(lds_vae_encoder* e, const float* audio, const int32_t* lens_host, const float* noise, float* out, float* z,
@@ -2297,20 +2304,228 @@ static int vae_encoder_forward_impl(lds_vae_encoder* e, const float* audio, cons
 }
 
 // ================================================================================================
+// Units encoders: the host toolkit that Whisper, HuBERT, wav2vec 2.0 and w2v-BERT 2.0 below are written on.  Nothing here launches on its
+// own account: the four *_run functions stay the sequences of launches, these are the pieces they state in common.
+// ================================================================================================
+// The weights of a create call: the caller's name -> tensor map and the new handle's device allocations.
+struct WeightLoader {
+    Tensors T;
+    Owner& o;
+    WeightLoader(Owner& own, int n, const char* const* names, const float* const* ptrs, const int64_t* numel) : o(own) {
+        for (int i = 0; i < n; ++i) T.m[names[i]] = {ptrs[i], numel[i]};
+    }
+    const float* get(const std::string& k, int64_t cnt) { return T.get(k, cnt); }
+    float* vec(const std::string& k, int64_t cnt) {      // a tensor uploaded as it is
+        const float* p = T.get(k, cnt);
+        return p ? o.upload(std::vector<float>(p, p + cnt)) : nullptr;
+    }
+    // the end of a create: hands the handle out, or deletes it and names the first tensor that was absent or of the wrong size
+    template <class H>
+    int finish(bool ok, const char* tag, H* h, H** out) {
+        if (ok) { *out = h; return LDS_OK; }
+        delete h;
+        if (!T.missing.empty()) return fail(LDS_EMISSING, "%s: %s", tag, T.missing.c_str());
+        return fail(LDS_ENOMEM, "%s weight upload failed", tag);
+    }
+};
+
+// q | k | v as one [3C][C] weight and one [3C] bias; kb may be null (Whisper's key has no bias): zeros
+struct QkvCat { std::vector<float> w, b; };
+static QkvCat cat_qkv(const float* qw, const float* kw, const float* vw, const float* qb, const float* kb, const float* vb, int C) {
+    const size_t CC = (size_t)C * C;
+    QkvCat q{std::vector<float>(3 * CC), std::vector<float>((size_t)3 * C, 0.f)};
+    memcpy(q.w.data(), qw, sizeof(float) * CC);
+    memcpy(q.w.data() + CC, kw, sizeof(float) * CC);
+    memcpy(q.w.data() + 2 * CC, vw, sizeof(float) * CC);
+    memcpy(q.b.data(), qb, sizeof(float) * C);
+    if (kb) memcpy(q.b.data() + C, kb, sizeof(float) * C);
+    memcpy(q.b.data() + 2 * C, vb, sizeof(float) * C);
+    return q;
+}
+// The q | k | v convolution's options: q and k stay K4P, the value third goes to `v` in attention's VT layout.  With ln_part the
+// LayerNorm in front is folded in (pack_ln_fold's c1 / c2, the partials of the C input channels).
+static DOpt qkv_opt(int C, float* v, const float2* ln_part = nullptr, const float* c1 = nullptr, const float* c2 = nullptr, float ln_eps = 1e-5f) {
+    DOpt o;
+    o.plain_from = 2 * C; o.out2 = v; o.vt_D = 64;
+    if (ln_part) { o.ln_part = ln_part; o.ln_np = C / 32; o.ln_eps = ln_eps; o.ln_c1 = c1; o.ln_c2 = c2; }
+    return o;
+}
+
+// The transformer's tensors of one call, T frames of C channels per clip: the LayerNorm partials of lnw channels, the residual stream's
+// two, q | k, v (VT layout), attention's output and the feed-forward's hidden tensor (`big` floats per clip).  Returns a slot of `more`
+// floats per clip behind them (an encoder's own last tensor); the tail slack ends the workspace.
+struct TfWs {
+    float2* lnp;
+    float *xa, *xb, *qk, *v, *att, *big;
+};
+static float* plan_tf(Arena& A, size_t B, size_t C, size_t T, size_t big, size_t lnw, TfWs& w, size_t more = 0) {
+    w.lnp = (float2*)A.f(B * (lnw / 32) * T * 2);
+    w.xa = A.f(B * C * (T + 2)); w.xb = A.f(B * C * (T + 2));
+    w.qk = A.f(B * 2 * C * (T + 2));
+    w.v = A.f(B * (C * ((T + 3) & ~(size_t)3) + 2048));
+    w.att = A.f(B * C * (T + 2));
+    w.big = A.f(B * big);
+    float* last = A.f(B * more);
+    A.f(16384);      // tail slack: ragged last tiles read (masked) entries past a tensor's end
+    return last;
+}
+// A *_workspace_bytes entry: the call's limits (check), then its plan (plan) run on an arena without memory
+template <class Check, class Plan>
+static int plan_bytes(size_t* out, Check check, Plan plan) {
+    if (!out) return fail(LDS_EINVAL, "null argument");
+    LDS_TRY(check());
+    Arena A(nullptr, 0);
+    plan(A);
+    *out = A.used;
+    return LDS_OK;
+}
+
+// up to 64 per-clip ints to a device slot, carried in a kernel's arguments (launch_set_list): stream-ordered, `host` is read during the call only
+static int upload_clip_ints(const int32_t* host, int B, int* dev, hipStream_t st) {
+    float tmp[64];
+    for (int b = 0; b < B; ++b) memcpy(&tmp[b], &host[b], sizeof(int));
+    HIP_TRY(launch_set_list((float*)dev, tmp, B, st));
+    return LDS_OK;
+}
+
+// Dimension rules; `tag` is the encoder's name in the messages.
+static int range_check(const char* tag, const char* name, int v, int lo, int hi) {
+    return v < lo || v > hi ? fail(LDS_EINVAL, "%s: %s %d outside %d .. %d", tag, name, v, lo, hi) : LDS_OK;
+}
+static int width_check(const char* tag, const char* name, int v, bool capped) {      // a GEMM's channel count; capped: at most 1024
+    if (capped && (v < 64 || v % 64 || v > 1024)) return fail(LDS_EINVAL, "%s: %s %d must be a multiple of 64 in 64 .. 1024", tag, name, v);
+    if (v < 64 || v % 64) return fail(LDS_EINVAL, "%s: %s %d must be a positive multiple of 64", tag, name, v);
+    return LDS_OK;
+}
+static int heads_check(const char* tag, int n_state, int n_head) {
+    return n_head < 1 || n_state != n_head * 64 ? fail(LDS_EINVAL, "%s: n_state / n_head must be 64 (got %d / %d)", tag, n_state, n_head) : LDS_OK;
+}
+
+// A pre-LN transformer block (Whisper's, wav2vec 2.0's): both LayerNorms folded into the GEMM that reads them.
+struct PreLnBlockW {
+    ConvW qkv, out, fc1, fc2;
+    float *qkv_c1 = nullptr, *qkv_c2 = nullptr, *fc1_c1 = nullptr, *fc1_c2 = nullptr;
+};
+// the tensors of one block as the checkpoint holds them (weight, bias); kb may be null
+struct PreLnBlockSrc {
+    const float *ag, *ab, *qw, *qb, *kw, *kb, *vw, *vb, *ow, *ob, *mg, *mb, *f1, *f1b, *f2, *f2b;
+};
+static bool pack_preln_block(Owner& o, const PreLnBlockSrc& s, int C, int n_ffn, PreLnBlockW& bw) {
+    if (!s.ag || !s.ab || !s.qw || !s.qb || !s.kw || !s.vw || !s.vb || !s.ow || !s.ob || !s.mg || !s.mb || !s.f1 || !s.f1b || !s.f2 || !s.f2b) return false;
+    const QkvCat q = cat_qkv(s.qw, s.kw, s.vw, s.qb, s.kb, s.vb, C);
+    return pack_ln_fold(o, q.w.data(), q.b.data(), s.ag, s.ab, 3 * C, C, {}, bw.qkv, bw.qkv_c1, bw.qkv_c2) && pack_conv(o, s.ow, s.ob, C, C, 1, bw.out) &&
+           pack_ln_fold(o, s.f1, s.f1b, s.mg, s.mb, n_ffn, C, {}, bw.fc1, bw.fc1_c1, bw.fc1_c2) && pack_conv(o, s.f2, s.f2b, C, n_ffn, 1, bw.fc2);
+}
+// One block in five launches: x -> x (through xn).  w.lnp holds the partials of x on entry and on return; lvl: the ragged level of the
+// frames under `lens` (k4p.h ragged_len; 1: Whisper, whose lens count mel frames; 0: lens are the clips' own frame counts).
+static int run_preln_block(const PreLnBlockW& bw, float* x, float* xn, const TfWs& w, int C, int T, int n_ffn, int n_head, int lvl, const int* lens, int B,
+                           hipStream_t st) {
+    DOpt oq = qkv_opt(C, w.v, w.lnp, bw.qkv_c1, bw.qkv_c2);      // q | k | v of ln1(x)
+    oq.lvl_in = oq.lvl_out = lvl;
+    LDS_TRY(run_dconv(bw.qkv, x, C, nullptr, 0, T, oq, w.qk, B, st));
+    HIP_TRY(launch_attention_k4p(w.qk, w.v, w.att, B, C, T, n_head, st, 0, lens, lvl));
+    DOpt oo;      // x + out(.), partials for ln2
+    oo.lvl_in = oo.lvl_out = lvl;
+    oo.res = x; oo.lnpart_out = w.lnp;
+    LDS_TRY(run_dconv(bw.out, w.att, C, nullptr, 0, T, oo, xn, B, st));
+    DOpt o1;      // gelu(fc1(ln2(.)))
+    o1.lvl_in = o1.lvl_out = lvl;
+    o1.epi = EPI_GELU;
+    o1.ln_part = w.lnp; o1.ln_np = C / 32; o1.ln_c1 = bw.fc1_c1; o1.ln_c2 = bw.fc1_c2;
+    LDS_TRY(run_dconv(bw.fc1, xn, C, nullptr, 0, T, o1, w.big, B, st));
+    DOpt o2;      // + fc2(.), partials for the next block's ln1 / the final LayerNorm
+    o2.lvl_in = o2.lvl_out = lvl;
+    o2.res = xn; o2.lnpart_out = w.lnp;
+    return run_dconv(bw.fc2, w.big, n_ffn, nullptr, 0, T, o2, x, B, st);
+}
+
+// ---- the waveform convolution stack of HuBERT and wav2vec 2.0 ----
+// what HuBERT and wav2vec 2.0 hold alike: the strided convolutions behind conv0, the feature projection and the positional convolution
+struct ConvStackW {
+    ConvW conv[6];                                                // conv1 .. conv6
+    ConvW fproj;                                                  // the projection with the LayerNorm in front of it folded in
+    float *fproj_c1 = nullptr, *fproj_c2 = nullptr;
+    float *pos_w = nullptr, *pos_b = nullptr;                     // weight norm folded, packed for hubert_posconv
+};
+constexpr int kHubertLevels = 7;      // conv0 .. conv6
+// frames after every layer of the feature extractor for a clip of n samples padded by `pad` zeros per side (model.py:99-106)
+static void hubert_levels(int64_t n, int pad, int32_t* lv) {
+    int64_t f = (n + 2 * pad - 10) / 5 + 1;
+    lv[0] = (int32_t)f;
+    for (int i = 1; i < kHubertLevels; ++i) {
+        f = (i <= 4) ? (f - 3) / 2 + 1 : (f - 2) / 2 + 1;
+        lv[i] = (int32_t)f;
+    }
+}
+
+// The stack's part of a workspace: the clips' sample counts and their frame counts after conv0 .. conv6 on the device, and the two
+// tensors the levels alternate between (conv0's output is the largest tensor of the call).  slen / nlen are what the launches take:
+// null for a dense batch, the device copies once `upload` has run.
+struct ConvStackWs {
+    int* d_slen;
+    int* d_nlen[kHubertLevels];
+    float *ca, *cb;
+    const int* slen = nullptr;
+    const int* nlen[kHubertLevels] = {};
+    void plan(Arena& A, size_t B, size_t D, const int32_t* nb) {
+        d_slen = (int*)A.f(64);
+        for (int i = 0; i < kHubertLevels; ++i) d_nlen[i] = (int*)A.f(64);
+        ca = A.f(B * D * ((size_t)nb[0] + 2));
+        cb = A.f(B * D * ((size_t)nb[1] + 2));
+    }
+    int upload(const int32_t* lens_host, int pad, int B, hipStream_t st) {
+        int32_t lv[kHubertLevels][64];
+        for (int b = 0; b < B; ++b) {
+            int32_t one[kHubertLevels];
+            hubert_levels(lens_host[b], pad, one);
+            for (int i = 0; i < kHubertLevels; ++i) lv[i][b] = one[i];
+        }
+        LDS_TRY(upload_clip_ints(lens_host, B, d_slen, st));
+        slen = d_slen;
+        for (int i = 0; i < kHubertLevels; ++i) {
+            LDS_TRY(upload_clip_ints(lv[i], B, d_nlen[i], st));
+            nlen[i] = d_nlen[i];
+        }
+        return LDS_OK;
+    }
+};
+
+// the dimension rules of HuBERT and wav2vec 2.0; n_proj < 0: the encoder has no proj
+static int conv_stack_dims_check(const char* tag, int conv_dim, int n_state, int n_head, int n_layer, int n_ffn, int n_proj, int pos_kernel, int pos_groups,
+                                 int n_ctx) {
+    LDS_TRY(width_check(tag, "conv_dim", conv_dim, true));
+    LDS_TRY(width_check(tag, "n_state", n_state, true));
+    LDS_TRY(heads_check(tag, n_state, n_head));
+    LDS_TRY(range_check(tag, "n_layer", n_layer, 1, 64));
+    LDS_TRY(width_check(tag, "n_ffn", n_ffn, false));
+    if (n_proj >= 0) LDS_TRY(width_check(tag, "n_proj", n_proj, false));
+    if (pos_kernel < 2 || pos_kernel > 128 || (pos_kernel & 1)) return fail(LDS_EINVAL, "%s: pos_kernel %d must be even in 2 .. 128", tag, pos_kernel);
+    if (pos_groups < 1 || n_state % pos_groups || (n_state / pos_groups) % 16 || n_state / pos_groups > 64)
+        return fail(LDS_EINVAL, "%s: n_state / pos_groups must be 16, 32, 48 or 64 (got %d / %d)", tag, n_state, pos_groups);
+    return range_check(tag, "n_ctx", n_ctx, 1, 1500);
+}
+// the limits of one call on audio: B clips in buffers of L samples, `pad` zeros (at most max_pad) added on each side of every clip;
+// nb = the buffers' frame counts
+static int conv_stack_shape_check(const char* tag, int n_ctx, int B, int64_t L, int pad, int max_pad, int32_t* nb) {
+    LDS_TRY(range_check(tag, "B", B, 1, 65535));
+    LDS_TRY(range_check(tag, "pad", pad, 0, max_pad));
+    if (L + 2 * pad < 400 || L > ((int64_t)1 << 30)) return fail(LDS_EINVAL, "%s: L %lld outside %d .. 2^30 samples", tag, (long long)L, 400 - 2 * pad);
+    hubert_levels(L, pad, nb);
+    if (nb[6] > n_ctx) return fail(LDS_EINVAL, "%s: %d frames exceed n_ctx %d", tag, nb[6], n_ctx);
+    return LDS_OK;
+}
+
+// ================================================================================================
 // Whisper units encoder: log-mel front end + AudioEncoder (reference encoder/whisper/audio.py:62-82, model.py:112-131,
 // tools/tools.py:105-126).  Channel-major K4P like the UNet's transformer, and built from the same launches: every LayerNorm is
 // folded into the 1x1 convolution that reads it (pack_ln_fold), q | k | v is one convolution whose value third is stored in
 // attention's VT layout, `out` and `mlp.2` add the residual and emit the next LayerNorm's partials.  Five launches per block.
 // ================================================================================================
-struct WhisperBlockW {
-    ConvW qkv, out, fc1, fc2;
-    float *qkv_c1 = nullptr, *qkv_c2 = nullptr, *fc1_c1 = nullptr, *fc1_c2 = nullptr;
-};
 struct lds_whisper {
     lds_whisper_cfg cfg;
     Owner own;
     ConvW conv1, conv2;
-    std::vector<WhisperBlockW> blocks;
+    std::vector<PreLnBlockW> blocks;
     float *post_g = nullptr, *post_b = nullptr;
     float* posk = nullptr;        // the sinusoid table as one K4P element [n_state][n_ctx]
     double* basis = nullptr;      // [400][201] (cos, sin) times the periodic Hann window
@@ -2322,10 +2537,10 @@ constexpr int kWhisperHop = 160, kWhisperNfft = 400, kWhisperBins = 201;
 static int whisper_cfg_check(const lds_whisper_cfg* c) {
     if (!c) return fail(LDS_EINVAL, "null argument");
     if (c->n_mels != 80 && c->n_mels != 128) return fail(LDS_EINVAL, "whisper: n_mels %d (80 or 128)", c->n_mels);
-    if (c->n_state < 64 || c->n_state % 64) return fail(LDS_EINVAL, "whisper: n_state %d must be a positive multiple of 64", c->n_state);
-    if (c->n_head < 1 || c->n_state != c->n_head * 64) return fail(LDS_EINVAL, "whisper: n_state / n_head must be 64 (got %d / %d)", c->n_state, c->n_head);
-    if (c->n_layer < 1 || c->n_layer > 64) return fail(LDS_EINVAL, "whisper: n_layer %d outside 1 .. 64", c->n_layer);
-    if (c->n_ctx < 1 || c->n_ctx > 65536) return fail(LDS_EINVAL, "whisper: n_ctx %d outside 1 .. 65536", c->n_ctx);
+    LDS_TRY(width_check("whisper", "n_state", c->n_state, false));
+    LDS_TRY(heads_check("whisper", c->n_state, c->n_head));
+    LDS_TRY(range_check("whisper", "n_layer", c->n_layer, 1, 64));
+    LDS_TRY(range_check("whisper", "n_ctx", c->n_ctx, 1, 65536));
     return LDS_OK;
 }
 
@@ -2334,15 +2549,10 @@ extern "C" int lds_whisper_create(const lds_whisper_cfg* cfg, int n, const char*
     if (!cfg || !names || !ptrs || !numel || !mel_filters || !out || n < 0) return fail(LDS_EINVAL, "null argument");
     LDS_TRY(whisper_cfg_check(cfg));
     const int C = cfg->n_state, M = cfg->n_mels, NC = cfg->n_ctx;
-    Tensors T;
-    for (int i = 0; i < n; ++i) T.m[names[i]] = {ptrs[i], numel[i]};
     lds_whisper* h = new lds_whisper();
     h->cfg = *cfg;
+    WeightLoader T(h->own, n, names, ptrs, numel);
     Owner& o = h->own;
-    auto vec = [&](const std::string& k, int64_t cnt) -> float* {
-        const float* p = T.get(k, cnt);
-        return p ? o.upload(std::vector<float>(p, p + cnt)) : nullptr;
-    };
     bool ok = true;
     {
         const float* w1 = T.get("encoder.conv1.weight", (int64_t)C * M * 3);
@@ -2354,29 +2564,20 @@ extern "C" int lds_whisper_create(const lds_whisper_cfg* cfg, int n, const char*
     h->blocks.resize(cfg->n_layer);
     for (int l = 0; l < cfg->n_layer && ok; ++l) {
         const std::string p = "encoder.blocks." + std::to_string(l) + ".";
-        WhisperBlockW& bw = h->blocks[l];
         const int64_t CC = (int64_t)C * C;
-        const float *ag = T.get(p + "attn_ln.weight", C), *ab = T.get(p + "attn_ln.bias", C);
-        const float *qw = T.get(p + "attn.query.weight", CC), *qb = T.get(p + "attn.query.bias", C);
-        const float* kw = T.get(p + "attn.key.weight", CC);      // (no bias: model.py:47)
-        const float *vw = T.get(p + "attn.value.weight", CC), *vb = T.get(p + "attn.value.bias", C);
-        const float *ow = T.get(p + "attn.out.weight", CC), *ob = T.get(p + "attn.out.bias", C);
-        const float *mg = T.get(p + "mlp_ln.weight", C), *mb = T.get(p + "mlp_ln.bias", C);
-        const float *f1 = T.get(p + "mlp.0.weight", 4 * CC), *f1b = T.get(p + "mlp.0.bias", 4 * C);
-        const float *f2 = T.get(p + "mlp.2.weight", 4 * CC), *f2b = T.get(p + "mlp.2.bias", C);
-        if (!ag || !ab || !qw || !qb || !kw || !vw || !vb || !ow || !ob || !mg || !mb || !f1 || !f1b || !f2 || !f2b) { ok = false; break; }
-        std::vector<float> cat((size_t)3 * CC), cb((size_t)3 * C, 0.f);
-        memcpy(cat.data(), qw, sizeof(float) * CC);
-        memcpy(cat.data() + CC, kw, sizeof(float) * CC);
-        memcpy(cat.data() + 2 * CC, vw, sizeof(float) * CC);
-        memcpy(cb.data(), qb, sizeof(float) * C);
-        memcpy(cb.data() + 2 * C, vb, sizeof(float) * C);
-        ok = pack_ln_fold(o, cat.data(), cb.data(), ag, ab, 3 * C, C, {}, bw.qkv, bw.qkv_c1, bw.qkv_c2) && pack_conv(o, ow, ob, C, C, 1, bw.out) &&
-             pack_ln_fold(o, f1, f1b, mg, mb, 4 * C, C, {}, bw.fc1, bw.fc1_c1, bw.fc1_c2) && pack_conv(o, f2, f2b, C, 4 * C, 1, bw.fc2);
+        const PreLnBlockSrc s = {T.get(p + "attn_ln.weight", C),    T.get(p + "attn_ln.bias", C),
+                                 T.get(p + "attn.query.weight", CC), T.get(p + "attn.query.bias", C),
+                                 T.get(p + "attn.key.weight", CC),   nullptr,      // (no bias: model.py:47)
+                                 T.get(p + "attn.value.weight", CC), T.get(p + "attn.value.bias", C),
+                                 T.get(p + "attn.out.weight", CC),   T.get(p + "attn.out.bias", C),
+                                 T.get(p + "mlp_ln.weight", C),      T.get(p + "mlp_ln.bias", C),
+                                 T.get(p + "mlp.0.weight", 4 * CC),  T.get(p + "mlp.0.bias", 4 * C),
+                                 T.get(p + "mlp.2.weight", 4 * CC),  T.get(p + "mlp.2.bias", C)};
+        ok = pack_preln_block(o, s, C, 4 * C, h->blocks[l]);
     }
     if (ok) {
-        h->post_g = vec("encoder.ln_post.weight", C);
-        h->post_b = vec("encoder.ln_post.bias", C);
+        h->post_g = T.vec("encoder.ln_post.weight", C);
+        h->post_b = T.vec("encoder.ln_post.bias", C);
         ok = h->post_g && h->post_b;
     }
     if (ok) {
@@ -2415,23 +2616,13 @@ extern "C" int lds_whisper_create(const lds_whisper_cfg* cfg, int n, const char*
         h->filtT = o.upload(ft);
         ok = h->posk && h->basis && h->filtT;
     }
-    if (!ok) {
-        std::string miss = T.missing;
-        delete h;
-        if (!miss.empty()) return fail(LDS_EMISSING, "whisper: %s", miss.c_str());
-        return fail(LDS_ENOMEM, "whisper weight upload failed");
-    }
-    *out = h;
-    return LDS_OK;
+    return T.finish(ok, "whisper", h, out);
 }
 extern "C" void lds_whisper_destroy(lds_whisper* h) { delete h; }
 
-struct WhisperWs {
+struct WhisperWs : TfWs {                  // big: conv1's output [C][F], later mlp.0's [4C][T]
     int *slen, *flen;                      // device copies of the clips' sample / mel-frame counts (<= 64 clips)
     float *logspec, *pmax, *melk;          // front end scratch; conv1's K4P input
-    float *big;                            // conv1's output [C][F], later mlp.0's [4C][T]
-    float *xa, *xb, *qk, *v, *att;
-    float2* lnp;
 };
 // F = mel frames per clip buffer, T = (F - 1) / 2 + 1 encoder frames
 static void plan_whisper(const lds_whisper* h, Arena& A, int B, int F, WhisperWs& w) {
@@ -2440,39 +2631,26 @@ static void plan_whisper(const lds_whisper* h, Arena& A, int B, int F, WhisperWs
     w.logspec = A.f(Bz * M * F);
     w.pmax = A.f(Bz * ((F + 15) / 16));
     w.melk = A.f(Bz * M * (F + 2));
-    w.big = A.f(Bz * std::max(C * (F + 2), 4 * C * (T + 2)));
-    w.xa = A.f(Bz * C * (T + 2)); w.xb = A.f(Bz * C * (T + 2));
-    w.qk = A.f(Bz * 2 * C * (T + 2));
-    w.v = A.f(Bz * (C * ((T + 3) & ~(size_t)3) + 2048));
-    w.att = A.f(Bz * C * (T + 2));
-    w.lnp = (float2*)A.f(Bz * (C / 32) * T * 2);
-    A.f(16384);      // tail slack: ragged last tiles read (masked) entries past a tensor's end
+    plan_tf(A, Bz, C, T, std::max(C * (F + 2), 4 * C * (T + 2)), C, w);
 }
 // the limits of one call: B clips in buffers of F mel frames
 static int whisper_shape_check(const lds_whisper* h, int B, int64_t F) {
     if (!h) return fail(LDS_EINVAL, "null handle");
-    if (B < 1 || B > 65535) return fail(LDS_EINVAL, "whisper: B %d outside 1 .. 65535", B);
+    LDS_TRY(range_check("whisper", "B", B, 1, 65535));
     if (F < 1) return fail(LDS_EINVAL, "whisper: no mel frame (a clip needs at least 400 samples)");
     if ((F - 1) / 2 + 1 > h->cfg.n_ctx) return fail(LDS_EINVAL, "whisper: %lld frames exceed n_ctx %d", (long long)((F - 1) / 2 + 1), h->cfg.n_ctx);
     return LDS_OK;
 }
 extern "C" int lds_whisper_workspace_bytes(const lds_whisper* h, int B, int64_t L, size_t* out) {
-    if (!out) return fail(LDS_EINVAL, "null argument");
-    if (L < kWhisperNfft) return fail(LDS_EINVAL, "whisper: L %lld below 400 samples", (long long)L);
-    LDS_TRY(whisper_shape_check(h, B, L / kWhisperHop));
-    Arena A(nullptr, 0);
-    WhisperWs w;
-    plan_whisper(h, A, B, (int)(L / kWhisperHop), w);
-    *out = A.used;
-    return LDS_OK;
+    return plan_bytes(
+        out,
+        [&] {
+            if (L < kWhisperNfft) return fail(LDS_EINVAL, "whisper: L %lld below 400 samples", (long long)L);
+            return whisper_shape_check(h, B, L / kWhisperHop);
+        },
+        [&](Arena& A) { WhisperWs w; plan_whisper(h, A, B, (int)(L / kWhisperHop), w); });
 }
 
-static int whisper_upload(const int32_t* host, int B, int* dev, hipStream_t st) {
-    float tmp[64];
-    for (int b = 0; b < B; ++b) memcpy(&tmp[b], &host[b], sizeof(int));
-    HIP_TRY(launch_set_list((float*)dev, tmp, B, st));
-    return LDS_OK;
-}
 // audio -> (mel_plain and / or units); or mel_in (plain [B][n_mels][F]) -> units.  lens_host: samples per clip (audio) or mel frames per
 // clip (mel_in); null = the buffer's length.  Every argument has been checked by the callers.
 static int whisper_run(lds_whisper* h, const float* audio, int64_t L, const float* mel_in, int F, const int32_t* lens_host, float* mel_plain,
@@ -2489,8 +2667,8 @@ static int whisper_run(lds_whisper* h, const float* audio, int64_t L, const floa
     if (lens_host) {
         int32_t fl[64];
         for (int b = 0; b < B; ++b) fl[b] = audio ? lens_host[b] / kWhisperHop : lens_host[b];
-        if (audio) { LDS_TRY(whisper_upload(lens_host, B, w.slen, st)); slen = w.slen; }
-        LDS_TRY(whisper_upload(fl, B, w.flen, st));
+        if (audio) { LDS_TRY(upload_clip_ints(lens_host, B, w.slen, st)); slen = w.slen; }
+        LDS_TRY(upload_clip_ints(fl, B, w.flen, st));
         flen = w.flen;
     }
     if (audio) {
@@ -2515,27 +2693,7 @@ static int whisper_run(lds_whisper* h, const float* audio, int64_t L, const floa
     HIP_TRY(launch_whisper_pos(w.xa, h->posk, h->cfg.n_ctx, w.lnp, flen, B, C, T, st));
     float* x = w.xa;
     float* xn = w.xb;
-    for (const WhisperBlockW& bw : h->blocks) {
-        DOpt oq;      // q | k | v of attn_ln(x)
-        oq.lvl_in = oq.lvl_out = 1;
-        oq.plain_from = 2 * C; oq.out2 = w.v; oq.vt_D = 64;
-        oq.ln_part = w.lnp; oq.ln_np = C / 32; oq.ln_c1 = bw.qkv_c1; oq.ln_c2 = bw.qkv_c2;
-        LDS_TRY(run_dconv(bw.qkv, x, C, nullptr, 0, T, oq, w.qk, B, st));
-        HIP_TRY(launch_attention_k4p(w.qk, w.v, w.att, B, C, T, h->cfg.n_head, st, 0, flen, 1));
-        DOpt oo;      // x + out(.), partials for mlp_ln
-        oo.lvl_in = oo.lvl_out = 1;
-        oo.res = x; oo.lnpart_out = w.lnp;
-        LDS_TRY(run_dconv(bw.out, w.att, C, nullptr, 0, T, oo, xn, B, st));
-        DOpt o1;      // gelu(mlp.0(mlp_ln(.)))
-        o1.lvl_in = o1.lvl_out = 1;
-        o1.epi = EPI_GELU;
-        o1.ln_part = w.lnp; o1.ln_np = C / 32; o1.ln_c1 = bw.fc1_c1; o1.ln_c2 = bw.fc1_c2;
-        LDS_TRY(run_dconv(bw.fc1, xn, C, nullptr, 0, T, o1, w.big, B, st));
-        DOpt o2;      // + mlp.2(.), partials for the next block's attn_ln / ln_post
-        o2.lvl_in = o2.lvl_out = 1;
-        o2.res = xn; o2.lnpart_out = w.lnp;
-        LDS_TRY(run_dconv(bw.fc2, w.big, 4 * C, nullptr, 0, T, o2, x, B, st));
-    }
+    for (const PreLnBlockW& bw : h->blocks) LDS_TRY(run_preln_block(bw, x, xn, w, C, T, 4 * C, h->cfg.n_head, 1, flen, B, st));
     HIP_TRY(launch_whisper_ln_post(x, w.lnp, h->post_g, h->post_b, 1e-5f, units, flen, B, C, T, st));
     return LDS_OK;
 }
@@ -2545,11 +2703,7 @@ static int whisper_audio_check(const lds_whisper* h, const float* audio, const i
     if (!h || !audio || !ws) return fail(LDS_EINVAL, "null argument");
     if (L < kWhisperNfft || L > ((int64_t)1 << 30)) return fail(LDS_EINVAL, "whisper: L %lld outside 400 .. 2^30 samples", (long long)L);
     LDS_TRY(whisper_shape_check(h, B, L / kWhisperHop));
-    if (lengths) {
-        if (B > 64) return fail(LDS_EINVAL, "per-clip lengths: at most 64 clips per call (got %d)", B);
-        for (int b = 0; b < B; ++b)
-            if (lengths[b] < kWhisperNfft || lengths[b] > L) return fail(LDS_EINVAL, "length[%d] = %d outside 400 .. %lld", b, lengths[b], (long long)L);
-    }
+    if (lengths) LDS_TRY(clip_lens_check("length", lengths, B, kWhisperNfft, L));
     *F_out = (int)(L / kWhisperHop);
     return LDS_OK;
 }
@@ -2571,11 +2725,7 @@ extern "C" int lds_whisper_encode_mel(lds_whisper* h, const float* mel, const in
                                       void* stream) {
     if (!h || !mel || !units || !ws) return fail(LDS_EINVAL, "null argument");
     LDS_TRY(whisper_shape_check(h, B, F));
-    if (n_frames) {
-        if (B > 64) return fail(LDS_EINVAL, "per-clip lengths: at most 64 clips per call (got %d)", B);
-        for (int b = 0; b < B; ++b)
-            if (n_frames[b] < 1 || n_frames[b] > F) return fail(LDS_EINVAL, "n_frames[%d] = %d outside 1 .. %d", b, n_frames[b], F);
-    }
+    if (n_frames) LDS_TRY(clip_lens_check("n_frames", n_frames, B, 1, F));
     return whisper_run(h, nullptr, 0, mel, F, n_frames, nullptr, units, ws, ws_bytes, B, stream);
 }
 
@@ -2591,43 +2741,18 @@ struct HubertBlockW {
     ConvW qkv, out, fc1, fc2;
     float *n1_g = nullptr, *n1_b = nullptr, *n2_g = nullptr, *n2_b = nullptr;
 };
-struct lds_hubert {
+struct lds_hubert : ConvStackW {
     lds_hubert_cfg cfg;
     Owner own;
     float *w0 = nullptr, *gn_g = nullptr, *gn_b = nullptr;      // conv0 [conv_dim][10], norm0
-    ConvW conv[6];                                                // conv1 .. conv6
-    ConvW fproj;                                                  // feature_projection: LayerNorm folded into the Linear
-    float *fproj_c1 = nullptr, *fproj_c2 = nullptr;
-    float *pos_w = nullptr, *pos_b = nullptr;                     // weight norm folded, packed for hubert_posconv
     float *norm_g = nullptr, *norm_b = nullptr;
     std::vector<HubertBlockW> blocks;
     ConvW proj;
 };
 
-constexpr int kHubertLevels = 7;      // conv0 .. conv6
-// frames after every layer of the feature extractor for a clip of n samples padded by `pad` zeros per side (model.py:99-106)
-static void hubert_levels(int64_t n, int pad, int32_t* lv) {
-    int64_t f = (n + 2 * pad - 10) / 5 + 1;
-    lv[0] = (int32_t)f;
-    for (int i = 1; i < kHubertLevels; ++i) {
-        f = (i <= 4) ? (f - 3) / 2 + 1 : (f - 2) / 2 + 1;
-        lv[i] = (int32_t)f;
-    }
-}
-
 static int hubert_cfg_check(const lds_hubert_cfg* c) {
     if (!c) return fail(LDS_EINVAL, "null argument");
-    if (c->conv_dim < 64 || c->conv_dim % 64 || c->conv_dim > 1024) return fail(LDS_EINVAL, "hubert: conv_dim %d must be a multiple of 64 in 64 .. 1024", c->conv_dim);
-    if (c->n_state < 64 || c->n_state % 64 || c->n_state > 1024) return fail(LDS_EINVAL, "hubert: n_state %d must be a multiple of 64 in 64 .. 1024", c->n_state);
-    if (c->n_head < 1 || c->n_state != c->n_head * 64) return fail(LDS_EINVAL, "hubert: n_state / n_head must be 64 (got %d / %d)", c->n_state, c->n_head);
-    if (c->n_layer < 1 || c->n_layer > 64) return fail(LDS_EINVAL, "hubert: n_layer %d outside 1 .. 64", c->n_layer);
-    if (c->n_ffn < 64 || c->n_ffn % 64) return fail(LDS_EINVAL, "hubert: n_ffn %d must be a positive multiple of 64", c->n_ffn);
-    if (c->n_proj < 64 || c->n_proj % 64) return fail(LDS_EINVAL, "hubert: n_proj %d must be a positive multiple of 64", c->n_proj);
-    if (c->pos_kernel < 2 || c->pos_kernel > 128 || (c->pos_kernel & 1)) return fail(LDS_EINVAL, "hubert: pos_kernel %d must be even in 2 .. 128", c->pos_kernel);
-    if (c->pos_groups < 1 || c->n_state % c->pos_groups || (c->n_state / c->pos_groups) % 16 || c->n_state / c->pos_groups > 64)
-        return fail(LDS_EINVAL, "hubert: n_state / pos_groups must be 16, 32, 48 or 64 (got %d / %d)", c->n_state, c->pos_groups);
-    if (c->n_ctx < 1 || c->n_ctx > 1500) return fail(LDS_EINVAL, "hubert: n_ctx %d outside 1 .. 1500", c->n_ctx);
-    return LDS_OK;
+    return conv_stack_dims_check("hubert", c->conv_dim, c->n_state, c->n_head, c->n_layer, c->n_ffn, c->n_proj, c->pos_kernel, c->pos_groups, c->n_ctx);
 }
 
 // weight norm of the positional convolution folded in double (parametrizations.weight_norm(dim=2): one norm per tap, over the other two
@@ -2656,18 +2781,13 @@ extern "C" int lds_hubert_create(const lds_hubert_cfg* cfg, int n, const char* c
     if (!cfg || !names || !ptrs || !numel || !out || n < 0) return fail(LDS_EINVAL, "null argument");
     LDS_TRY(hubert_cfg_check(cfg));
     const int D = cfg->conv_dim, C = cfg->n_state, F = cfg->n_ffn, K = cfg->pos_kernel, gw = C / cfg->pos_groups;
-    Tensors T;
-    for (int i = 0; i < n; ++i) T.m[names[i]] = {ptrs[i], numel[i]};
     lds_hubert* h = new lds_hubert();
     h->cfg = *cfg;
+    WeightLoader T(h->own, n, names, ptrs, numel);
     Owner& o = h->own;
-    auto vec = [&](const std::string& k, int64_t cnt) -> float* {
-        const float* p = T.get(k, cnt);
-        return p ? o.upload(std::vector<float>(p, p + cnt)) : nullptr;
-    };
-    h->w0 = vec("feature_extractor.conv0.weight", (int64_t)D * 10);
-    h->gn_g = vec("feature_extractor.norm0.weight", D);
-    h->gn_b = vec("feature_extractor.norm0.bias", D);
+    h->w0 = T.vec("feature_extractor.conv0.weight", (int64_t)D * 10);
+    h->gn_g = T.vec("feature_extractor.norm0.weight", D);
+    h->gn_b = T.vec("feature_extractor.norm0.bias", D);
     bool ok = h->w0 && h->gn_g && h->gn_b;
     for (int i = 1; i <= 6 && ok; ++i) {
         const int k = i <= 4 ? 3 : 2;
@@ -2682,10 +2802,10 @@ extern "C" int lds_hubert_create(const lds_hubert_cfg* cfg, int n, const char* c
     if (ok) {
         const float* g = T.get("positional_embedding.conv.parametrizations.weight.original0", K);
         const float* v = T.get("positional_embedding.conv.parametrizations.weight.original1", (int64_t)C * gw * K);
-        h->pos_b = vec("positional_embedding.conv.bias", C);
+        h->pos_b = T.vec("positional_embedding.conv.bias", C);
         if (g && v) h->pos_w = pack_posconv(o, g, v, C, cfg->pos_groups, K);
-        h->norm_g = vec("norm.weight", C);
-        h->norm_b = vec("norm.bias", C);
+        h->norm_g = T.vec("norm.weight", C);
+        h->norm_b = T.vec("norm.bias", C);
         ok = h->pos_w && h->pos_b && h->norm_g && h->norm_b;
     }
     h->blocks.resize(cfg->n_layer);
@@ -2698,8 +2818,8 @@ extern "C" int lds_hubert_create(const lds_hubert_cfg* cfg, int n, const char* c
         const float *f1 = T.get(p + "linear1.weight", (int64_t)F * C), *f1b = T.get(p + "linear1.bias", F);
         const float *f2 = T.get(p + "linear2.weight", (int64_t)F * C), *f2b = T.get(p + "linear2.bias", C);
         if (!iw || !ib || !ow || !ob || !f1 || !f1b || !f2 || !f2b) { ok = false; break; }
-        bw.n1_g = vec(p + "norm1.weight", C); bw.n1_b = vec(p + "norm1.bias", C);
-        bw.n2_g = vec(p + "norm2.weight", C); bw.n2_b = vec(p + "norm2.bias", C);
+        bw.n1_g = T.vec(p + "norm1.weight", C); bw.n1_b = T.vec(p + "norm1.bias", C);
+        bw.n2_g = T.vec(p + "norm2.weight", C); bw.n2_b = T.vec(p + "norm2.bias", C);
         ok = bw.n1_g && bw.n1_b && bw.n2_g && bw.n2_b && pack_conv(o, iw, ib, 3 * C, C, 1, bw.qkv) && pack_conv(o, ow, ob, C, C, 1, bw.out) &&
              pack_conv(o, f1, f1b, F, C, 1, bw.fc1) && pack_conv(o, f2, f2b, C, F, 1, bw.fc2);
     }
@@ -2707,61 +2827,28 @@ extern "C" int lds_hubert_create(const lds_hubert_cfg* cfg, int n, const char* c
         const float *w = T.get("proj.weight", (int64_t)cfg->n_proj * C), *b = T.get("proj.bias", cfg->n_proj);
         ok = w && b && pack_conv(o, w, b, cfg->n_proj, C, 1, h->proj);
     }
-    if (!ok) {
-        std::string miss = T.missing;
-        delete h;
-        if (!miss.empty()) return fail(LDS_EMISSING, "hubert: %s", miss.c_str());
-        return fail(LDS_ENOMEM, "hubert weight upload failed");
-    }
-    *out = h;
-    return LDS_OK;
+    return T.finish(ok, "hubert", h, out);
 }
 extern "C" void lds_hubert_destroy(lds_hubert* h) { delete h; }
 
-struct HubertWs {
-    int* slen;
-    int* nlen[kHubertLevels];      // device copies of the clips' sample counts and of their frame counts after conv0 .. conv6
-    float2 *part, *stat;           // norm0's statistics
-    float *ca, *cb;                // the feature extractor's ping-pong (conv0's output is the largest tensor of the call)
-    float2* lnp;                   // conv6's LayerNorm partials for the folded feature projection
-    float *xa, *xb, *qk, *v, *att, *big, *pj;
+struct HubertWs : ConvStackWs, TfWs {      // lnp: conv6's LayerNorm partials for the folded feature projection
+    float2 *part, *stat;                   // norm0's statistics
+    float* pj;
 };
 static void plan_hubert(const lds_hubert* h, Arena& A, int B, const int32_t* nb, HubertWs& w) {
     const size_t D = h->cfg.conv_dim, C = h->cfg.n_state, F = h->cfg.n_ffn, P = h->cfg.n_proj, T = nb[6], Bz = B;
-    w.slen = (int*)A.f(64);
-    for (int i = 0; i < kHubertLevels; ++i) w.nlen[i] = (int*)A.f(64);
+    w.plan(A, Bz, D, nb);
     w.part = (float2*)A.f(Bz * (((size_t)nb[0] + 255) / 256) * D * 2);
     w.stat = (float2*)A.f(Bz * D * 2);
-    w.ca = A.f(Bz * D * ((size_t)nb[0] + 2));
-    w.cb = A.f(Bz * D * ((size_t)nb[1] + 2));
-    w.lnp = (float2*)A.f(Bz * (D / 32) * T * 2);
-    w.xa = A.f(Bz * C * (T + 2)); w.xb = A.f(Bz * C * (T + 2));
-    w.qk = A.f(Bz * 2 * C * (T + 2));
-    w.v = A.f(Bz * (C * ((T + 3) & ~(size_t)3) + 2048));
-    w.att = A.f(Bz * C * (T + 2));
-    w.big = A.f(Bz * F * (T + 2));
-    w.pj = A.f(Bz * P * (T + 2));
-    A.f(16384);      // tail slack: ragged last tiles read (masked) entries past a tensor's end
+    w.pj = plan_tf(A, Bz, C, T, F * (T + 2), D, w, P * (T + 2));
 }
-// the limits of one call: B clips in buffers of L samples, `pad` zeros added on each side of every clip; nb = the buffers' frame counts
 static int hubert_shape_check(const lds_hubert* h, int B, int64_t L, int pad, int32_t* nb) {
     if (!h) return fail(LDS_EINVAL, "null handle");
-    if (B < 1 || B > 65535) return fail(LDS_EINVAL, "hubert: B %d outside 1 .. 65535", B);
-    if (pad < 0 || pad > 40) return fail(LDS_EINVAL, "hubert: pad %d outside 0 .. 40", pad);
-    if (L + 2 * pad < 400 || L > ((int64_t)1 << 30)) return fail(LDS_EINVAL, "hubert: L %lld outside %d .. 2^30 samples", (long long)L, 400 - 2 * pad);
-    hubert_levels(L, pad, nb);
-    if (nb[6] > h->cfg.n_ctx) return fail(LDS_EINVAL, "hubert: %d frames exceed n_ctx %d", nb[6], h->cfg.n_ctx);
-    return LDS_OK;
+    return conv_stack_shape_check("hubert", h->cfg.n_ctx, B, L, pad, 40, nb);
 }
 extern "C" int lds_hubert_workspace_bytes(const lds_hubert* h, int B, int64_t L, int pad, size_t* out) {
-    if (!out) return fail(LDS_EINVAL, "null argument");
     int32_t nb[kHubertLevels];
-    LDS_TRY(hubert_shape_check(h, B, L, pad, nb));
-    Arena A(nullptr, 0);
-    HubertWs w;
-    plan_hubert(h, A, B, nb, w);
-    *out = A.used;
-    return LDS_OK;
+    return plan_bytes(out, [&] { return hubert_shape_check(h, B, L, pad, nb); }, [&](Arena& A) { HubertWs w; plan_hubert(h, A, B, nb, w); });
 }
 
 // audio -> feat ([B][T][conv_dim]) and / or enc ([B][T][n_state], or [B][T][n_proj] with want_proj).  Every argument has been checked.
@@ -2774,35 +2861,20 @@ static int hubert_run(lds_hubert* h, const float* audio, int64_t L, int pad, con
     plan_hubert(h, A, B, nb, w);
     if (!A.ok) return fail(LDS_ENOMEM, "hubert workspace too small: need %zu", A.used);
     const int D = h->cfg.conv_dim, C = h->cfg.n_state, T = nb[6];
-    const int* slen = nullptr;
-    const int* nlen[kHubertLevels] = {};
-    if (lens_host) {
-        int32_t lv[kHubertLevels][64];
-        for (int b = 0; b < B; ++b) {
-            int32_t one[kHubertLevels];
-            hubert_levels(lens_host[b], pad, one);
-            for (int i = 0; i < kHubertLevels; ++i) lv[i][b] = one[i];
-        }
-        LDS_TRY(whisper_upload(lens_host, B, w.slen, st));
-        slen = w.slen;
-        for (int i = 0; i < kHubertLevels; ++i) {
-            LDS_TRY(whisper_upload(lv[i], B, w.nlen[i], st));
-            nlen[i] = w.nlen[i];
-        }
-    }
+    if (lens_host) LDS_TRY(w.upload(lens_host, pad, B, st));
     TileBatchScope tb(0);      // tile rules judged at the nominal batch: a clip's units do not depend on the batch it is in
-    HIP_TRY(launch_hubert_conv0(audio, slen, L, pad, h->w0, h->gn_g, h->gn_b, 1e-5f, nlen[0], nb[0], D, w.part, w.stat, w.ca, B, st));
+    HIP_TRY(launch_hubert_conv0(audio, w.slen, L, pad, h->w0, h->gn_g, h->gn_b, 1e-5f, w.nlen[0], nb[0], D, w.part, w.stat, w.ca, B, st));
     float* x = w.ca;
     float* xn = w.cb;
     for (int i = 1; i < kHubertLevels; ++i) {      // gelu(conv_i(.)): stride 2, no padding; frames beyond a clip's count at level i are zeros
-        LensScope ls(nlen[i]);
+        LensScope ls(w.nlen[i]);
         DOpt o;
         o.stride = 2; o.pad = 0; o.epi = EPI_GELU;
         if (i == kHubertLevels - 1) o.lnpart_out = w.lnp;      // partials for feature_projection.norm
         LDS_TRY(run_dconv(h->conv[i - 1], x, D, nullptr, 0, nb[i - 1], o, xn, B, st));
         { float* t = x; x = xn; xn = t; }
     }
-    const int* flen = nlen[kHubertLevels - 1];
+    const int* flen = w.nlen[kHubertLevels - 1];
     if (feat) HIP_TRY(launch_hubert_store_frames(x, feat, flen, B, D, T, st));
     if (!enc) return LDS_OK;
     LensScope ls(flen);
@@ -2815,8 +2887,7 @@ static int hubert_run(lds_hubert* h, const float* audio, int64_t L, int pad, con
     HIP_TRY(launch_hubert_ln(w.xb, h->norm_g, h->norm_b, 1e-5f, w.xa, flen, B, C, T, st));
     for (int l = 0; l < n_layers_run; ++l) {
         const HubertBlockW& bw = h->blocks[l];
-        DOpt oq;      // q | k | v
-        oq.plain_from = 2 * C; oq.out2 = w.v; oq.vt_D = 64;
+        const DOpt oq = qkv_opt(C, w.v);      // q | k | v
         LDS_TRY(run_dconv(bw.qkv, w.xa, C, nullptr, 0, T, oq, w.qk, B, st));
         HIP_TRY(launch_attention_k4p(w.qk, w.v, w.att, B, C, T, h->cfg.n_head, st, 0, flen, 0));
         DOpt oo;      // x + out_proj(.), then norm1
@@ -2845,12 +2916,7 @@ static int hubert_audio_check(const lds_hubert* h, const float* audio, const int
                               int32_t* nb) {
     if (!h || !audio || !out || !ws) return fail(LDS_EINVAL, "null argument");
     LDS_TRY(hubert_shape_check(h, B, L, pad, nb));
-    if (lengths) {
-        if (B > 64) return fail(LDS_EINVAL, "per-clip lengths: at most 64 clips per call (got %d)", B);
-        for (int b = 0; b < B; ++b)
-            if (lengths[b] < 400 - 2 * pad || lengths[b] > L)
-                return fail(LDS_EINVAL, "length[%d] = %d outside %d .. %lld", b, lengths[b], 400 - 2 * pad, (long long)L);
-    }
+    if (lengths) LDS_TRY(clip_lens_check("length", lengths, B, 400 - 2 * pad, L));
     return LDS_OK;
 }
 extern "C" int lds_hubert_features(lds_hubert* h, const float* audio, const int32_t* lengths, float* out, void* ws, size_t ws_bytes, int B, int64_t L, int pad,
@@ -2875,56 +2941,38 @@ extern "C" int lds_hubert_encode(lds_hubert* h, const float* audio, const int32_
 // is followed by no LayerNorm, and the blocks are pre-LN: Whisper's five launches with every LayerNorm folded into the GEMM that reads it,
 // then `encoder.layer_norm` through whisper_ln_post.  Tensor names are fairseq's (what pretrain/xlsr_53_56k.pt holds).
 // ================================================================================================
-struct lds_w2v {
+struct lds_w2v : ConvStackW {                                      // (conv1 .. conv6 are biased here)
     lds_w2v_cfg cfg;
     Owner own;
     float *w0 = nullptr, *b0 = nullptr;                            // conv0 [conv_dim][10] and its bias
     float *ln_g[kHubertLevels] = {}, *ln_b[kHubertLevels] = {};    // the LayerNorm behind conv0 .. conv6
-    ConvW conv[6];                                                 // conv1 .. conv6, biased
-    ConvW fproj;                                                   // layer_norm folded into post_extract_proj
-    float *fproj_c1 = nullptr, *fproj_c2 = nullptr;
-    float *pos_w = nullptr, *pos_b = nullptr;                      // weight norm folded, packed for hubert_posconv
-    std::vector<WhisperBlockW> blocks;
+    std::vector<PreLnBlockW> blocks;
     float *post_g = nullptr, *post_b = nullptr;                    // encoder.layer_norm
 };
 
 static int w2v_cfg_check(const lds_w2v_cfg* c) {
     if (!c) return fail(LDS_EINVAL, "null argument");
-    if (c->conv_dim < 64 || c->conv_dim % 64 || c->conv_dim > 1024) return fail(LDS_EINVAL, "w2v: conv_dim %d must be a multiple of 64 in 64 .. 1024", c->conv_dim);
-    if (c->n_state < 64 || c->n_state % 64 || c->n_state > 1024) return fail(LDS_EINVAL, "w2v: n_state %d must be a multiple of 64 in 64 .. 1024", c->n_state);
-    if (c->n_head < 1 || c->n_state != c->n_head * 64) return fail(LDS_EINVAL, "w2v: n_state / n_head must be 64 (got %d / %d)", c->n_state, c->n_head);
-    if (c->n_layer < 1 || c->n_layer > 64) return fail(LDS_EINVAL, "w2v: n_layer %d outside 1 .. 64", c->n_layer);
-    if (c->n_ffn < 64 || c->n_ffn % 64) return fail(LDS_EINVAL, "w2v: n_ffn %d must be a positive multiple of 64", c->n_ffn);
-    if (c->pos_kernel < 2 || c->pos_kernel > 128 || (c->pos_kernel & 1)) return fail(LDS_EINVAL, "w2v: pos_kernel %d must be even in 2 .. 128", c->pos_kernel);
-    if (c->pos_groups < 1 || c->n_state % c->pos_groups || (c->n_state / c->pos_groups) % 16 || c->n_state / c->pos_groups > 64)
-        return fail(LDS_EINVAL, "w2v: n_state / pos_groups must be 16, 32, 48 or 64 (got %d / %d)", c->n_state, c->pos_groups);
-    if (c->n_ctx < 1 || c->n_ctx > 1500) return fail(LDS_EINVAL, "w2v: n_ctx %d outside 1 .. 1500", c->n_ctx);
-    return LDS_OK;
+    return conv_stack_dims_check("w2v", c->conv_dim, c->n_state, c->n_head, c->n_layer, c->n_ffn, -1, c->pos_kernel, c->pos_groups, c->n_ctx);
 }
 
 extern "C" int lds_w2v_create(const lds_w2v_cfg* cfg, int n, const char* const* names, const float* const* ptrs, const int64_t* numel, lds_w2v** out) {
     if (!cfg || !names || !ptrs || !numel || !out || n < 0) return fail(LDS_EINVAL, "null argument");
     LDS_TRY(w2v_cfg_check(cfg));
     const int D = cfg->conv_dim, C = cfg->n_state, F = cfg->n_ffn, K = cfg->pos_kernel, gw = C / cfg->pos_groups;
-    Tensors T;
-    for (int i = 0; i < n; ++i) T.m[names[i]] = {ptrs[i], numel[i]};
     lds_w2v* h = new lds_w2v();
     h->cfg = *cfg;
+    WeightLoader T(h->own, n, names, ptrs, numel);
     Owner& o = h->own;
-    auto vec = [&](const std::string& k, int64_t cnt) -> float* {
-        const float* p = T.get(k, cnt);
-        return p ? o.upload(std::vector<float>(p, p + cnt)) : nullptr;
-    };
     bool ok = true;
     for (int i = 0; i < kHubertLevels && ok; ++i) {
         const std::string p = "feature_extractor.conv_layers." + std::to_string(i) + ".";
-        h->ln_g[i] = vec(p + "2.1.weight", D);
-        h->ln_b[i] = vec(p + "2.1.bias", D);
+        h->ln_g[i] = T.vec(p + "2.1.weight", D);
+        h->ln_b[i] = T.vec(p + "2.1.bias", D);
         ok = h->ln_g[i] && h->ln_b[i];
         if (!ok) break;
         if (i == 0) {
-            h->w0 = vec(p + "0.weight", (int64_t)D * 10);
-            h->b0 = vec(p + "0.bias", D);
+            h->w0 = T.vec(p + "0.weight", (int64_t)D * 10);
+            h->b0 = T.vec(p + "0.bias", D);
             ok = h->w0 && h->b0;
         } else {
             const int k = i <= 4 ? 3 : 2;
@@ -2940,89 +2988,47 @@ extern "C" int lds_w2v_create(const lds_w2v_cfg* cfg, int n, const char* const* 
     if (ok) {
         const float* g = T.get("encoder.pos_conv.0.weight_g", K);
         const float* v = T.get("encoder.pos_conv.0.weight_v", (int64_t)C * gw * K);
-        h->pos_b = vec("encoder.pos_conv.0.bias", C);
+        h->pos_b = T.vec("encoder.pos_conv.0.bias", C);
         if (g && v) h->pos_w = pack_posconv(o, g, v, C, cfg->pos_groups, K);
         ok = h->pos_w && h->pos_b;
     }
     h->blocks.resize(cfg->n_layer);
     for (int l = 0; l < cfg->n_layer && ok; ++l) {
         const std::string p = "encoder.layers." + std::to_string(l) + ".";
-        WhisperBlockW& bw = h->blocks[l];
-        const int64_t CC = (int64_t)C * C;
-        const float *ag = T.get(p + "self_attn_layer_norm.weight", C), *ab = T.get(p + "self_attn_layer_norm.bias", C);
-        const float *qw = T.get(p + "self_attn.q_proj.weight", CC), *qb = T.get(p + "self_attn.q_proj.bias", C);
-        const float *kw = T.get(p + "self_attn.k_proj.weight", CC), *kb = T.get(p + "self_attn.k_proj.bias", C);
-        const float *vw = T.get(p + "self_attn.v_proj.weight", CC), *vb = T.get(p + "self_attn.v_proj.bias", C);
-        const float *ow = T.get(p + "self_attn.out_proj.weight", CC), *ob = T.get(p + "self_attn.out_proj.bias", C);
-        const float *mg = T.get(p + "final_layer_norm.weight", C), *mb = T.get(p + "final_layer_norm.bias", C);
-        const float *f1 = T.get(p + "fc1.weight", (int64_t)F * C), *f1b = T.get(p + "fc1.bias", F);
-        const float *f2 = T.get(p + "fc2.weight", (int64_t)F * C), *f2b = T.get(p + "fc2.bias", C);
-        if (!ag || !ab || !qw || !qb || !kw || !kb || !vw || !vb || !ow || !ob || !mg || !mb || !f1 || !f1b || !f2 || !f2b) { ok = false; break; }
-        std::vector<float> cat((size_t)3 * CC), cb((size_t)3 * C);
-        memcpy(cat.data(), qw, sizeof(float) * CC);
-        memcpy(cat.data() + CC, kw, sizeof(float) * CC);
-        memcpy(cat.data() + 2 * CC, vw, sizeof(float) * CC);
-        memcpy(cb.data(), qb, sizeof(float) * C);
-        memcpy(cb.data() + C, kb, sizeof(float) * C);
-        memcpy(cb.data() + 2 * C, vb, sizeof(float) * C);
-        ok = pack_ln_fold(o, cat.data(), cb.data(), ag, ab, 3 * C, C, {}, bw.qkv, bw.qkv_c1, bw.qkv_c2) && pack_conv(o, ow, ob, C, C, 1, bw.out) &&
-             pack_ln_fold(o, f1, f1b, mg, mb, F, C, {}, bw.fc1, bw.fc1_c1, bw.fc1_c2) && pack_conv(o, f2, f2b, C, F, 1, bw.fc2);
+        const int64_t CC = (int64_t)C * C, FC = (int64_t)F * C;
+        const PreLnBlockSrc s = {T.get(p + "self_attn_layer_norm.weight", C), T.get(p + "self_attn_layer_norm.bias", C),
+                                 T.get(p + "self_attn.q_proj.weight", CC),    T.get(p + "self_attn.q_proj.bias", C),
+                                 T.get(p + "self_attn.k_proj.weight", CC),    T.get(p + "self_attn.k_proj.bias", C),
+                                 T.get(p + "self_attn.v_proj.weight", CC),    T.get(p + "self_attn.v_proj.bias", C),
+                                 T.get(p + "self_attn.out_proj.weight", CC),  T.get(p + "self_attn.out_proj.bias", C),
+                                 T.get(p + "final_layer_norm.weight", C),     T.get(p + "final_layer_norm.bias", C),
+                                 T.get(p + "fc1.weight", FC),                 T.get(p + "fc1.bias", F),
+                                 T.get(p + "fc2.weight", FC),                 T.get(p + "fc2.bias", C)};
+        ok = s.kb && pack_preln_block(o, s, C, F, h->blocks[l]);
     }
     if (ok) {
-        h->post_g = vec("encoder.layer_norm.weight", C);
-        h->post_b = vec("encoder.layer_norm.bias", C);
+        h->post_g = T.vec("encoder.layer_norm.weight", C);
+        h->post_b = T.vec("encoder.layer_norm.bias", C);
         ok = h->post_g && h->post_b;
     }
-    if (!ok) {
-        std::string miss = T.missing;
-        delete h;
-        if (!miss.empty()) return fail(LDS_EMISSING, "w2v: %s", miss.c_str());
-        return fail(LDS_ENOMEM, "w2v weight upload failed");
-    }
-    *out = h;
-    return LDS_OK;
+    return T.finish(ok, "w2v", h, out);
 }
 extern "C" void lds_w2v_destroy(lds_w2v* h) { delete h; }
 
-struct W2vWs {
-    int* slen;
-    int* nlen[kHubertLevels];      // device copies of the clips' sample counts and of their frame counts after conv0 .. conv6
-    float *ca, *cb;                // the feature extractor's two tensors: a level's LayerNorm output / its raw convolution
-    float2* lnp;                   // LayerNorm partials: the extractor's output, then the residual stream
-    float *xa, *xb, *qk, *v, *att, *big;
-};
+// ca / cb: a level's LayerNorm output / its raw convolution; lnp: LayerNorm partials of the extractor's output, then of the residual stream
+struct W2vWs : ConvStackWs, TfWs {};
 static void plan_w2v(const lds_w2v* h, Arena& A, int B, const int32_t* nb, W2vWs& w) {
     const size_t D = h->cfg.conv_dim, C = h->cfg.n_state, F = h->cfg.n_ffn, T = nb[6], Bz = B;
-    w.slen = (int*)A.f(64);
-    for (int i = 0; i < kHubertLevels; ++i) w.nlen[i] = (int*)A.f(64);
-    w.ca = A.f(Bz * D * ((size_t)nb[0] + 2));
-    w.cb = A.f(Bz * D * ((size_t)nb[1] + 2));
-    w.lnp = (float2*)A.f(Bz * (std::max(D, C) / 32) * T * 2);
-    w.xa = A.f(Bz * C * (T + 2)); w.xb = A.f(Bz * C * (T + 2));
-    w.qk = A.f(Bz * 2 * C * (T + 2));
-    w.v = A.f(Bz * (C * ((T + 3) & ~(size_t)3) + 2048));
-    w.att = A.f(Bz * C * (T + 2));
-    w.big = A.f(Bz * F * (T + 2));
-    A.f(16384);      // tail slack: ragged last tiles read (masked) entries past a tensor's end
+    w.plan(A, Bz, D, nb);
+    plan_tf(A, Bz, C, T, F * (T + 2), std::max(D, C), w);
 }
-// the limits of one call: B clips in buffers of L samples; nb = the buffers' frame counts
 static int w2v_shape_check(const lds_w2v* h, int B, int64_t L, int32_t* nb) {
     if (!h) return fail(LDS_EINVAL, "null handle");
-    if (B < 1 || B > 65535) return fail(LDS_EINVAL, "w2v: B %d outside 1 .. 65535", B);
-    if (L < 400 || L > ((int64_t)1 << 30)) return fail(LDS_EINVAL, "w2v: L %lld outside 400 .. 2^30 samples", (long long)L);
-    hubert_levels(L, 0, nb);
-    if (nb[6] > h->cfg.n_ctx) return fail(LDS_EINVAL, "w2v: %d frames exceed n_ctx %d", nb[6], h->cfg.n_ctx);
-    return LDS_OK;
+    return conv_stack_shape_check("w2v", h->cfg.n_ctx, B, L, 0, 0, nb);
 }
 extern "C" int lds_w2v_workspace_bytes(const lds_w2v* h, int B, int64_t L, size_t* out) {
-    if (!out) return fail(LDS_EINVAL, "null argument");
     int32_t nb[kHubertLevels];
-    LDS_TRY(w2v_shape_check(h, B, L, nb));
-    Arena A(nullptr, 0);
-    W2vWs w;
-    plan_w2v(h, A, B, nb, w);
-    *out = A.used;
-    return LDS_OK;
+    return plan_bytes(out, [&] { return w2v_shape_check(h, B, L, nb); }, [&](Arena& A) { W2vWs w; plan_w2v(h, A, B, nb, w); });
 }
 
 // audio -> feat ([B][T][conv_dim]) or enc ([B][T][n_state]).  Every argument has been checked.
@@ -3035,33 +3041,18 @@ static int w2v_run(lds_w2v* h, const float* audio, int64_t L, const int32_t* len
     plan_w2v(h, A, B, nb, w);
     if (!A.ok) return fail(LDS_ENOMEM, "w2v workspace too small: need %zu", A.used);
     const int D = h->cfg.conv_dim, C = h->cfg.n_state, T = nb[6];
-    const int* slen = nullptr;
-    const int* nlen[kHubertLevels] = {};
-    if (lens_host) {
-        int32_t lv[kHubertLevels][64];
-        for (int b = 0; b < B; ++b) {
-            int32_t one[kHubertLevels];
-            hubert_levels(lens_host[b], 0, one);
-            for (int i = 0; i < kHubertLevels; ++i) lv[i][b] = one[i];
-        }
-        LDS_TRY(whisper_upload(lens_host, B, w.slen, st));
-        slen = w.slen;
-        for (int i = 0; i < kHubertLevels; ++i) {
-            LDS_TRY(whisper_upload(lv[i], B, w.nlen[i], st));
-            nlen[i] = w.nlen[i];
-        }
-    }
+    if (lens_host) LDS_TRY(w.upload(lens_host, 0, B, st));
     TileBatchScope tb(0);      // tile rules judged at the nominal batch: a clip's units do not depend on the batch it is in
-    HIP_TRY(launch_w2v_conv0(audio, slen, L, h->w0, h->b0, h->ln_g[0], h->ln_b[0], 1e-5f, nlen[0], nb[0], D, w.ca, B, st));
+    HIP_TRY(launch_w2v_conv0(audio, w.slen, L, h->w0, h->b0, h->ln_g[0], h->ln_b[0], 1e-5f, w.nlen[0], nb[0], D, w.ca, B, st));
     for (int i = 1; i < kHubertLevels; ++i) {      // conv_i + bias (stride 2, no padding) into cb, GELU(LayerNorm(.)) back into ca
-        LensScope ls(nlen[i]);
+        LensScope ls(w.nlen[i]);
         DOpt o;
         o.stride = 2; o.pad = 0;
         LDS_TRY(run_dconv(h->conv[i - 1], w.ca, D, nullptr, 0, nb[i - 1], o, w.cb, B, st));
         // the last level's partials serve the feature projection's folded layer_norm
-        HIP_TRY(launch_w2v_ln_act(w.cb, h->ln_g[i], h->ln_b[i], 1e-5f, w.ca, (i == kHubertLevels - 1 && enc) ? w.lnp : nullptr, nlen[i], B, D, nb[i], st));
+        HIP_TRY(launch_w2v_ln_act(w.cb, h->ln_g[i], h->ln_b[i], 1e-5f, w.ca, (i == kHubertLevels - 1 && enc) ? w.lnp : nullptr, w.nlen[i], B, D, nb[i], st));
     }
-    const int* flen = nlen[kHubertLevels - 1];
+    const int* flen = w.nlen[kHubertLevels - 1];
     if (feat) HIP_TRY(launch_hubert_store_frames(w.ca, feat, flen, B, D, T, st));
     if (!enc) return LDS_OK;
     LensScope ls(flen);
@@ -3074,23 +3065,7 @@ static int w2v_run(lds_w2v* h, const float* audio, int64_t L, const int32_t* len
     HIP_TRY(launch_w2v_lnpart(w.xb, w.lnp, flen, B, C, T, st));      // partials for the first block's self_attn_layer_norm
     float* x = w.xb;
     float* xn = w.xa;
-    for (const WhisperBlockW& bw : h->blocks) {
-        DOpt oq;      // q | k | v of self_attn_layer_norm(x)
-        oq.plain_from = 2 * C; oq.out2 = w.v; oq.vt_D = 64;
-        oq.ln_part = w.lnp; oq.ln_np = C / 32; oq.ln_c1 = bw.qkv_c1; oq.ln_c2 = bw.qkv_c2;
-        LDS_TRY(run_dconv(bw.qkv, x, C, nullptr, 0, T, oq, w.qk, B, st));
-        HIP_TRY(launch_attention_k4p(w.qk, w.v, w.att, B, C, T, h->cfg.n_head, st, 0, flen, 0));
-        DOpt oo;      // x + out_proj(.), partials for final_layer_norm
-        oo.res = x; oo.lnpart_out = w.lnp;
-        LDS_TRY(run_dconv(bw.out, w.att, C, nullptr, 0, T, oo, xn, B, st));
-        DOpt o1;      // gelu(fc1(final_layer_norm(.)))
-        o1.epi = EPI_GELU;
-        o1.ln_part = w.lnp; o1.ln_np = C / 32; o1.ln_c1 = bw.fc1_c1; o1.ln_c2 = bw.fc1_c2;
-        LDS_TRY(run_dconv(bw.fc1, xn, C, nullptr, 0, T, o1, w.big, B, st));
-        DOpt o2;      // + fc2(.), partials for the next block's self_attn_layer_norm / encoder.layer_norm
-        o2.res = xn; o2.lnpart_out = w.lnp;
-        LDS_TRY(run_dconv(bw.fc2, w.big, h->cfg.n_ffn, nullptr, 0, T, o2, x, B, st));
-    }
+    for (const PreLnBlockW& bw : h->blocks) LDS_TRY(run_preln_block(bw, x, xn, w, C, T, h->cfg.n_ffn, h->cfg.n_head, 0, flen, B, st));
     HIP_TRY(launch_whisper_ln_post(x, w.lnp, h->post_g, h->post_b, 1e-5f, enc, flen, B, C, T, st, 0));
     return LDS_OK;
 }
@@ -3098,11 +3073,7 @@ static int w2v_run(lds_w2v* h, const float* audio, int64_t L, const int32_t* len
 static int w2v_audio_check(const lds_w2v* h, const float* audio, const int32_t* lengths, const void* out, const void* ws, int B, int64_t L, int32_t* nb) {
     if (!h || !audio || !out || !ws) return fail(LDS_EINVAL, "null argument");
     LDS_TRY(w2v_shape_check(h, B, L, nb));
-    if (lengths) {
-        if (B > 64) return fail(LDS_EINVAL, "per-clip lengths: at most 64 clips per call (got %d)", B);
-        for (int b = 0; b < B; ++b)
-            if (lengths[b] < 400 || lengths[b] > L) return fail(LDS_EINVAL, "length[%d] = %d outside 400 .. %lld", b, lengths[b], (long long)L);
-    }
+    if (lengths) LDS_TRY(clip_lens_check("length", lengths, B, 400, L));
     return LDS_OK;
 }
 extern "C" int lds_w2v_features(lds_w2v* h, const float* audio, const int32_t* lengths, float* out, void* ws, size_t ws_bytes, int B, int64_t L, void* stream) {
@@ -3192,14 +3163,14 @@ static int w2vbert_cfg_check(const lds_w2vbert_cfg* c) {
     if (!c) return fail(LDS_EINVAL, "null argument");
     if (c->n_mels < 8 || c->n_mels > 128 || c->stride < 1 || c->stride > 8 || (c->n_mels * c->stride) % 32 || c->n_mels * c->stride > 1024)
         return fail(LDS_EINVAL, "w2vbert: n_mels %d x stride %d must be a multiple of 32 up to 1024 (n_mels 8 .. 128, stride 1 .. 8)", c->n_mels, c->stride);
-    if (c->n_state < 64 || c->n_state % 64 || c->n_state > 1024) return fail(LDS_EINVAL, "w2vbert: n_state %d must be a multiple of 64 in 64 .. 1024", c->n_state);
-    if (c->n_head < 1 || c->n_state != c->n_head * 64) return fail(LDS_EINVAL, "w2vbert: n_state / n_head must be 64 (got %d / %d)", c->n_state, c->n_head);
-    if (c->n_ffn < 64 || c->n_ffn % 64) return fail(LDS_EINVAL, "w2vbert: n_ffn %d must be a positive multiple of 64", c->n_ffn);
-    if (c->n_layer < 1 || c->n_layer > 64) return fail(LDS_EINVAL, "w2vbert: n_layer %d outside 1 .. 64", c->n_layer);
+    LDS_TRY(width_check("w2vbert", "n_state", c->n_state, true));
+    LDS_TRY(heads_check("w2vbert", c->n_state, c->n_head));
+    LDS_TRY(width_check("w2vbert", "n_ffn", c->n_ffn, false));
+    LDS_TRY(range_check("w2vbert", "n_layer", c->n_layer, 1, 64));
     if (c->left_max < 0 || c->right_max < 0 || c->left_max + c->right_max + 1 > kW2vbertRelStride)
         return fail(LDS_EINVAL, "w2vbert: left_max %d + right_max %d + 1 distances exceed %d", c->left_max, c->right_max, kW2vbertRelStride);
     if (c->dw_kernel < 1 || c->dw_kernel > 31 || !(c->dw_kernel & 1)) return fail(LDS_EINVAL, "w2vbert: dw_kernel %d must be odd in 1 .. 31", c->dw_kernel);
-    if (c->n_ctx < 1 || c->n_ctx > 1500) return fail(LDS_EINVAL, "w2vbert: n_ctx %d outside 1 .. 1500", c->n_ctx);
+    LDS_TRY(range_check("w2vbert", "n_ctx", c->n_ctx, 1, 1500));
     if (!(c->eps > 0.f) || !(c->eps < 1.f)) return fail(LDS_EINVAL, "w2vbert: eps %g outside (0, 1)", (double)c->eps);
     return LDS_OK;
 }
@@ -3208,15 +3179,10 @@ extern "C" int lds_w2vbert_create(const lds_w2vbert_cfg* cfg, int n, const char*
     if (!cfg || !names || !ptrs || !numel || !out || n < 0) return fail(LDS_EINVAL, "null argument");
     LDS_TRY(w2vbert_cfg_check(cfg));
     const int Fd = cfg->n_mels * cfg->stride, C = cfg->n_state, F = cfg->n_ffn, K = cfg->dw_kernel, NR = cfg->left_max + cfg->right_max + 1;
-    Tensors T;
-    for (int i = 0; i < n; ++i) T.m[names[i]] = {ptrs[i], numel[i]};
     lds_w2vbert* h = new lds_w2vbert();
     h->cfg = *cfg;
+    WeightLoader T(h->own, n, names, ptrs, numel);
     Owner& o = h->own;
-    auto vec = [&](const std::string& k, int64_t cnt) -> float* {
-        const float* p = T.get(k, cnt);
-        return p ? o.upload(std::vector<float>(p, p + cnt)) : nullptr;
-    };
     bool ok = true;
     {
         const std::vector<double> bs = w2vbert_basis();
@@ -3259,46 +3225,32 @@ extern "C" int lds_w2vbert_create(const lds_w2vbert_cfg* cfg, int n, const char*
         const float *p1 = T.get(p + "conv_module.pointwise_conv1.weight", 2 * CC), *p2 = T.get(p + "conv_module.pointwise_conv2.weight", CC);
         const float* dw = T.get(p + "conv_module.depthwise_conv.weight", (int64_t)C * K);
         if (!ag || !ab || !qw || !qb || !kw || !kb || !vw || !vb || !ow || !ob || !cg || !cbt || !p1 || !p2 || !dw) { ok = false; break; }
-        std::vector<float> cat((size_t)3 * CC), cb((size_t)3 * C);
-        memcpy(cat.data(), qw, sizeof(float) * CC);
-        memcpy(cat.data() + CC, kw, sizeof(float) * CC);
-        memcpy(cat.data() + 2 * CC, vw, sizeof(float) * CC);
-        memcpy(cb.data(), qb, sizeof(float) * C);
-        memcpy(cb.data() + C, kb, sizeof(float) * C);
-        memcpy(cb.data() + 2 * C, vb, sizeof(float) * C);
+        const QkvCat qkv = cat_qkv(qw, kw, vw, qb, kb, vb, C);
         std::vector<float> dwp((size_t)C * K);      // [K4P row][k][4]: row = (c / 8) * 2 + (c & 1), element (c & 7) / 2
         for (int c = 0; c < C; ++c)
             for (int k = 0; k < K; ++k) dwp[((size_t)((c >> 3) * 2 + (c & 1)) * K + k) * 4 + ((c & 7) >> 1)] = dw[(size_t)c * K + k];
         bw.dw = o.upload(dwp);
-        bw.E = vec(p + "self_attn.distance_embedding.weight", (int64_t)NR * 64);
-        bw.dw_g = vec(p + "conv_module.depthwise_layer_norm.weight", C);
-        bw.dw_b = vec(p + "conv_module.depthwise_layer_norm.bias", C);
-        bw.fin_g = vec(p + "final_layer_norm.weight", C);
-        bw.fin_b = vec(p + "final_layer_norm.bias", C);
+        bw.E = T.vec(p + "self_attn.distance_embedding.weight", (int64_t)NR * 64);
+        bw.dw_g = T.vec(p + "conv_module.depthwise_layer_norm.weight", C);
+        bw.dw_b = T.vec(p + "conv_module.depthwise_layer_norm.bias", C);
+        bw.fin_g = T.vec(p + "final_layer_norm.weight", C);
+        bw.fin_b = T.vec(p + "final_layer_norm.bias", C);
         ok = bw.dw && bw.E && bw.dw_g && bw.dw_b && bw.fin_g && bw.fin_b &&
-             pack_ln_fold(o, cat.data(), cb.data(), ag, ab, 3 * C, C, {}, bw.qkv, bw.qkv_c1, bw.qkv_c2) && pack_conv(o, ow, ob, C, C, 1, bw.out) &&
+             pack_ln_fold(o, qkv.w.data(), qkv.b.data(), ag, ab, 3 * C, C, {}, bw.qkv, bw.qkv_c1, bw.qkv_c2) && pack_conv(o, ow, ob, C, C, 1, bw.out) &&
              pack_ln_fold(o, p1, nullptr, cg, cbt, 2 * C, C, glu_perm, bw.pw1, bw.pw1_c1, bw.pw1_c2) && pack_conv(o, p2, nullptr, C, C, 1, bw.pw2);
     }
-    if (!ok) {
-        std::string miss = T.missing;
-        delete h;
-        if (!miss.empty()) return fail(LDS_EMISSING, "w2vbert: %s", miss.c_str());
-        return fail(LDS_ENOMEM, "w2vbert weight upload failed");
-    }
-    *out = h;
-    return LDS_OK;
+    return T.finish(ok, "w2vbert", h, out);
 }
 extern "C" void lds_w2vbert_destroy(lds_w2vbert* h) { delete h; }
 
 static int w2vbert_frames(int64_t n) { return n < kFbFrame ? 0 : (int)((n - kFbFrame) / kFbHop) + 1; }
 
-struct W2vbertWs {
+struct W2vbertWs : TfWs {          // lnp: LayerNorm partials of the residual stream
     int *slen, *rows, *valid;      // device copies: the clips' sample counts, rows and unmasked rows
     float* logspec; double2* stat;
     float* feats;                  // input_features when the caller does not receive them
     float* fk; float2* lnf;        // ... as K4P, and their LayerNorm partials
-    float2* lnp;                   // LayerNorm partials of the residual stream
-    float *xa, *xb, *qk, *v, *att, *big, *relp;
+    float* relp;
 };
 static void plan_w2vbert(const lds_w2vbert* h, Arena& A, int B, int N, int R, W2vbertWs& w) {
     const size_t M = h->cfg.n_mels, Fd = (size_t)h->cfg.n_mels * h->cfg.stride, C = h->cfg.n_state, F = h->cfg.n_ffn, T = R, Bz = B;
@@ -3308,19 +3260,12 @@ static void plan_w2vbert(const lds_w2vbert* h, Arena& A, int B, int N, int R, W2
     w.feats = A.f(Bz * T * Fd);
     w.fk = A.f(Bz * Fd * (T + 2));
     w.lnf = (float2*)A.f(Bz * (Fd / 32) * T * 2);
-    w.lnp = (float2*)A.f(Bz * (C / 32) * T * 2);
-    w.xa = A.f(Bz * C * (T + 2)); w.xb = A.f(Bz * C * (T + 2));
-    w.qk = A.f(Bz * 2 * C * (T + 2));
-    w.v = A.f(Bz * (C * ((T + 3) & ~(size_t)3) + 2048));
-    w.att = A.f(Bz * C * (T + 2));
-    w.big = A.f(Bz * F * (T + 2));
-    w.relp = A.f(Bz * h->cfg.n_head * T * kW2vbertRelStride);
-    A.f(16384);      // tail slack: ragged last tiles read (masked) entries past a tensor's end
+    w.relp = plan_tf(A, Bz, C, T, F * (T + 2), C, w, h->cfg.n_head * T * kW2vbertRelStride);
 }
 // the limits of one call: B clips in buffers of L samples -> N frames, R rows
 static int w2vbert_shape_check(const lds_w2vbert* h, int B, int64_t L, int& N, int& R) {
     if (!h) return fail(LDS_EINVAL, "null handle");
-    if (B < 1 || B > 64) return fail(LDS_EINVAL, "w2vbert: B %d outside 1 .. 64", B);
+    LDS_TRY(range_check("w2vbert", "B", B, 1, 64));
     if (L < kW2vbertMinSamples || L > ((int64_t)1 << 30)) return fail(LDS_EINVAL, "w2vbert: L %lld outside %d .. 2^30 samples", (long long)L, kW2vbertMinSamples);
     N = w2vbert_frames(L);
     R = (N + h->cfg.stride - 1) / h->cfg.stride;
@@ -3328,14 +3273,8 @@ static int w2vbert_shape_check(const lds_w2vbert* h, int B, int64_t L, int& N, i
     return LDS_OK;
 }
 extern "C" int lds_w2vbert_workspace_bytes(const lds_w2vbert* h, int B, int64_t L, size_t* out) {
-    if (!out) return fail(LDS_EINVAL, "null argument");
     int N, R;
-    LDS_TRY(w2vbert_shape_check(h, B, L, N, R));
-    Arena A(nullptr, 0);
-    W2vbertWs w;
-    plan_w2vbert(h, A, B, N, R, w);
-    *out = A.used;
-    return LDS_OK;
+    return plan_bytes(out, [&] { return w2vbert_shape_check(h, B, L, N, R); }, [&](Arena& A) { W2vbertWs w; plan_w2vbert(h, A, B, N, R, w); });
 }
 
 // audio -> feats_out ([B][R][n_mels * stride]) and / or enc ([B][R][n_state]); or feats_in -> enc.  nfr: every clip's frame count (host, [B]),
@@ -3352,13 +3291,13 @@ static int w2vbert_run(lds_w2vbert* h, const float* audio, int64_t L, const int3
     const int Fd = c.n_mels * c.stride, C = c.n_state, T = R;
     int32_t rows[64], valid[64];
     for (int b = 0; b < B; ++b) { rows[b] = (nfr[b] + c.stride - 1) / c.stride; valid[b] = nfr[b] / c.stride; }
-    LDS_TRY(whisper_upload(rows, B, w.rows, st));
-    LDS_TRY(whisper_upload(valid, B, w.valid, st));
+    LDS_TRY(upload_clip_ints(rows, B, w.rows, st));
+    LDS_TRY(upload_clip_ints(valid, B, w.valid, st));
     const float* feats = feats_in;
     if (audio) {
         const int* slen = nullptr;
         if (slen_host) {
-            LDS_TRY(whisper_upload(slen_host, B, w.slen, st));
+            LDS_TRY(upload_clip_ints(slen_host, B, w.slen, st));
             slen = w.slen;
         }
         float* fo = feats_out ? feats_out : w.feats;
@@ -3392,9 +3331,7 @@ static int w2vbert_run(lds_w2vbert* h, const float* audio, int64_t L, const int3
         };
         LDS_TRY(ffn(bw.f1a, bw.f1_c1, bw.f1_c2, bw.f1b, x, xn, w.lnp));      // partials for self_attn_layer_norm
         std::swap(x, xn);
-        DOpt oq;      // q | k | v of self_attn_layer_norm(x)
-        oq.plain_from = 2 * C; oq.out2 = w.v; oq.vt_D = 64;
-        oq.ln_part = w.lnp; oq.ln_np = C / 32; oq.ln_eps = c.eps; oq.ln_c1 = bw.qkv_c1; oq.ln_c2 = bw.qkv_c2;
+        const DOpt oq = qkv_opt(C, w.v, w.lnp, bw.qkv_c1, bw.qkv_c2, c.eps);      // q | k | v of self_attn_layer_norm(x)
         LDS_TRY(run_dconv(bw.qkv, x, C, nullptr, 0, T, oq, w.qk, B, st));
         HIP_TRY(launch_w2vbert_relpos(w.qk, bw.E, w.relp, w.rows, B, C, T, c.n_head, c.left_max + c.right_max + 1, st));
         HIP_TRY(launch_attention_k4p_rel(w.qk, w.v, w.relp, w.att, B, C, T, c.n_head, w.rows, w.valid, c.left_max, c.right_max, st));
@@ -3429,11 +3366,8 @@ static int w2vbert_audio_check(const lds_w2vbert* h, const float* audio, const i
                                int& R, int32_t* nfr) {
     if (!h || !audio || !out || !ws) return fail(LDS_EINVAL, "null argument");
     LDS_TRY(w2vbert_shape_check(h, B, L, N, R));
-    for (int b = 0; b < B; ++b) {
-        if (lengths && (lengths[b] < kW2vbertMinSamples || lengths[b] > L))
-            return fail(LDS_EINVAL, "length[%d] = %d outside %d .. %lld", b, lengths[b], kW2vbertMinSamples, (long long)L);
-        nfr[b] = lengths ? w2vbert_frames(lengths[b]) : N;
-    }
+    if (lengths) LDS_TRY(clip_lens_check("length", lengths, B, kW2vbertMinSamples, L));
+    for (int b = 0; b < B; ++b) nfr[b] = lengths ? w2vbert_frames(lengths[b]) : N;
     return LDS_OK;
 }
 extern "C" int lds_w2vbert_fbank(lds_w2vbert* h, const float* audio, const int32_t* lengths, float* out, void* ws, size_t ws_bytes, int B, int64_t L, void* stream) {
@@ -3451,7 +3385,7 @@ extern "C" int lds_w2vbert_encode(lds_w2vbert* h, const float* audio, const int3
 extern "C" int lds_w2vbert_encode_features(lds_w2vbert* h, const float* feats, const int32_t* n_frames, float* out, void* ws, size_t ws_bytes, int B, int R,
                                            void* stream) {
     if (!h || !feats || !out || !ws) return fail(LDS_EINVAL, "null argument");
-    if (B < 1 || B > 64) return fail(LDS_EINVAL, "w2vbert: B %d outside 1 .. 64", B);
+    LDS_TRY(range_check("w2vbert", "B", B, 1, 64));
     if (R < 1 || R > h->cfg.n_ctx) return fail(LDS_EINVAL, "w2vbert: %d rows outside 1 .. n_ctx %d", R, h->cfg.n_ctx);
     const int st = h->cfg.stride;
     int32_t nfr[64];
@@ -4286,8 +4220,8 @@ extern "C" int lds_test_w2v_conv0(const float* audio, const int32_t* lengths, co
             if (lengths[b] < 10 || lengths[b] > L) return fail(LDS_EINVAL, "length[%d] = %d outside 10 .. %lld", b, lengths[b], (long long)L);
             n0[b] = (lengths[b] - 10) / 5 + 1;
         }
-        LDS_TRY(whisper_upload(lengths, B, dl, st));
-        LDS_TRY(whisper_upload(n0, B, dl + 64, st));
+        LDS_TRY(upload_clip_ints(lengths, B, dl, st));
+        LDS_TRY(upload_clip_ints(n0, B, dl + 64, st));
         slen = dl; nlen = dl + 64;
     }
     HIP_TRY(launch_w2v_conv0(audio, slen, L, w, bias, gamma, beta, eps, nlen, N0, C, ko, B, st));
@@ -4308,7 +4242,7 @@ extern "C" int lds_test_w2v_ln_act(const float* x, const int32_t* n_frames, cons
     if (n_frames) {
         for (int b = 0; b < B; ++b)
             if (n_frames[b] < 1 || n_frames[b] > T) return fail(LDS_EINVAL, "n_frames[%d] = %d outside 1 .. %d", b, n_frames[b], T);
-        LDS_TRY(whisper_upload(n_frames, B, dl, st));
+        LDS_TRY(upload_clip_ints(n_frames, B, dl, st));
         nlen = dl;
     }
     HIP_TRY(launch_to_k4p(x, kx, B, C, T, C, 0, st));
@@ -4337,7 +4271,7 @@ extern "C" int lds_test_w2vbert_fbank(const float* audio, const int32_t* lengths
     if (lengths) {
         for (int b = 0; b < B; ++b)
             if (lengths[b] < kW2vbertMinSamples || lengths[b] > L) return fail(LDS_EINVAL, "length[%d] = %d outside %d .. %lld", b, lengths[b], kW2vbertMinSamples, (long long)L);
-        LDS_TRY(whisper_upload(lengths, B, dl, st));
+        LDS_TRY(upload_clip_ints(lengths, B, dl, st));
         slen = dl;
     }
     HIP_TRY(launch_w2vbert_fbank(audio, slen, L, N, R, basis, filtT, n_mels, stride, kFbMelFloor, logspec, stat, out, B, st));
@@ -4363,8 +4297,8 @@ extern "C" int lds_test_w2vbert_attention(const float* qkv, const float* E, cons
         if (!q_rows || !k_rows) return fail(LDS_EINVAL, "q_rows and k_rows come together");
         for (int b = 0; b < B; ++b)
             if (q_rows[b] < 1 || q_rows[b] > T || k_rows[b] < 1 || k_rows[b] > q_rows[b]) return fail(LDS_EINVAL, "rows[%d] = (%d, %d) outside 1 .. %d", b, q_rows[b], k_rows[b], T);
-        LDS_TRY(whisper_upload(q_rows, B, dl, st));
-        LDS_TRY(whisper_upload(k_rows, B, dl + 64, st));
+        LDS_TRY(upload_clip_ints(q_rows, B, dl, st));
+        LDS_TRY(upload_clip_ints(k_rows, B, dl + 64, st));
         ql = dl; kl = dl + 64;
     }
     for (int b = 0; b < B; ++b) {
@@ -4399,8 +4333,8 @@ extern "C" int lds_test_w2vbert_dwconv(const float* x, const float* w, const flo
         if (!in_rows || !out_rows) return fail(LDS_EINVAL, "in_rows and out_rows come together");
         for (int b = 0; b < B; ++b)
             if (out_rows[b] < 1 || out_rows[b] > T || in_rows[b] < 1 || in_rows[b] > out_rows[b]) return fail(LDS_EINVAL, "rows[%d] = (%d, %d) outside 1 .. %d", b, in_rows[b], out_rows[b], T);
-        LDS_TRY(whisper_upload(in_rows, B, dl, st));
-        LDS_TRY(whisper_upload(out_rows, B, dl + 64, st));
+        LDS_TRY(upload_clip_ints(in_rows, B, dl, st));
+        LDS_TRY(upload_clip_ints(out_rows, B, dl + 64, st));
         vl = dl; nl = dl + 64;
     }
     HIP_TRY(launch_to_k4p(x, kx, B, C, T, C, 0, st));

@@ -686,13 +686,89 @@ class HubertCfg(C.Structure):
                 ("pos_kernel", C.c_int), ("pos_groups", C.c_int), ("n_ctx", C.c_int)]
 
 
-class Hubert(_Handle):
+def _w2v_check_dims(d, widths):
+    """include/lds.h's limits on the dimensions that HuBERT and wav2vec 2.0 share; `widths`: the fields that are any positive multiple of 64.
+    The messages name HuBERT for both, as they always have."""
+    for k in ("conv_dim", "n_state"):
+        if d[k] < 64 or d[k] % 64 or d[k] > 1024:
+            raise ValueError(f"Hubert: {k} {d[k]} must be a multiple of 64 in 64 .. 1024")
+    if d["n_head"] < 1 or d["n_state"] != 64 * d["n_head"]:
+        raise ValueError(f"Hubert: n_state {d['n_state']} must be 64 * n_head ({d['n_head']})")
+    for k in widths:
+        if d[k] < 64 or d[k] % 64:
+            raise ValueError(f"Hubert: {k} {d[k]} must be a positive multiple of 64")
+    if d["pos_kernel"] < 2 or d["pos_kernel"] > 128 or d["pos_kernel"] % 2:
+        raise ValueError(f"Hubert: pos_kernel {d['pos_kernel']} must be even in 2 .. 128")
+    g = d["pos_groups"]
+    if g < 1 or d["n_state"] % g or (d["n_state"] // g) % 16 or d["n_state"] // g > 64:
+        raise ValueError(f"Hubert: n_state / pos_groups must be 16, 32, 48 or 64 (got {d['n_state']} / {g})")
+    if not 1 <= d["n_layer"] <= 64:
+        raise ValueError(f"Hubert: n_layer {d['n_layer']} outside 1 .. 64")
+    if not 1 <= d["n_ctx"] <= 1500:
+        raise ValueError(f"Hubert: n_ctx {d['n_ctx']} outside 1 .. 1500")
+
+
+class _UnitsEncoder(_Handle):
+    """What the four units encoders' handles share: the path of a call on audio [B, L].  Every limit of include/lds.h is checked first
+    (ValueError, before a device is touched), then the per-clip lengths, the device, the workspace, the output and the entry.  A subclass
+    states its limits below, `_units_of` (the frame rule) and, per entry, the output's shape and the entry's extra arguments."""
+    MIN_SAMPLES = 400           # of a clip without padding
+    MAX_BATCH = None            # clips per call; None = any positive count (per-clip lengths allow 64 in every encoder)
+    PAD = 0                     # the largest `pad` (zeros added on each side of every clip); 0 = the entries take no pad
+    UNIT, CTX, HINT = "frames", "n_ctx", ""      # words of the messages
+
+    @classmethod
+    def _pad(cls, pad):
+        return cls.PAD if pad is None else pad
+
+    @classmethod
+    def lengths(cls, lengths, B, L, pad=None):
+        """per-clip sample counts -> host int32 [B] (include/lds.h: B <= 64, MIN_SAMPLES - 2 pad .. L)"""
+        return _host_lengths(lengths, B, cls.MIN_SAMPLES - 2 * cls._pad(pad), L, 64, "units")
+
+    def workspace_bytes(self, B, L, pad=None):
+        return _bytes(f"lds_{self.KIND}_workspace_bytes", self.h, B, L, *((self._pad(pad),) if self.PAD else ()))
+
+    def _check(self, B, L, pad=None):
+        """the limits of a call on B clips in buffers of L samples (ValueError); returns the units (frames, rows) of L samples"""
+        name, pad, ctx = type(self).__name__, self._pad(pad), self.dims["n_ctx"]
+        if self.MAX_BATCH is None and B < 1:
+            raise ValueError(f"{name}: an empty batch")
+        if self.MAX_BATCH is not None and not 1 <= B <= self.MAX_BATCH:
+            raise ValueError(f"{name}: 1 .. {self.MAX_BATCH} clips per call (got {B})")
+        if not 0 <= pad <= self.PAD:
+            raise ValueError(f"{name}: pad {pad} outside 0 .. {self.PAD}")
+        if L < self.MIN_SAMPLES - 2 * pad:
+            raise ValueError(f"{name}: clips need at least {self.MIN_SAMPLES - 2 * pad} samples (got {L}){self.HINT}")
+        n = self._units_of(L, pad)
+        if n > ctx:
+            raise ValueError(f"{name}: {L} samples give {n} {self.UNIT}, more than {self.CTX} {ctx}")
+        return n
+
+    def _call(self, entry, audio, lengths, ws, shape, mid=(), pad=None):
+        """entry(h, audio, lengths, out, *mid, ws, ws_bytes, B, L, [pad,] stream) -> out [B, *shape(n, L)], n = the units of L samples"""
+        import torch
+        if audio.dim() != 2:
+            raise ValueError(f"{type(self).__name__}: audio must be [B, L], got {list(audio.shape)}")
+        B, L = audio.shape
+        n = self._check(B, L, pad)
+        ln = self.lengths(lengths, B, L, pad) if lengths is not None else None
+        _dev(audio, None)
+        tail = (self._pad(pad),) if self.PAD else ()
+        ws = ws if ws is not None else self.ws.get(self.workspace_bytes(B, L, pad), audio.device)
+        out = torch.empty(B, *shape(n, L), dtype=torch.float32, device=audio.device)
+        check(getattr(lib(), entry)(self.h, _dev(audio, torch.float32), _host(ln), _dev(out), *mid, _dev(ws), ws.numel(), B, L, *tail, _stream()))
+        return out
+
+
+class Hubert(_UnitsEncoder):
     """HuBERT units encoder (lds_hubert_*): audio [B,L] at 16 kHz -> the feature extractor's output [B,T,conv_dim] / the transformer's
     [B,T,n_state] after `layer` blocks / units [B,T,n_proj].  `pad` zeros are added on each side of every clip (40: HubertSoft.units,
     T = L // 320).  `lengths`: every clip's own sample count (host ints, 400 - 2 pad .. L, at most 64 clips): each clip is encoded as if
     alone.  Every limit of include/lds.h is checked here first (ValueError, before a device is touched)."""
     KIND = "hubert"
     FIELDS = ("conv_dim", "n_state", "n_head", "n_layer", "n_ffn", "n_proj", "pos_kernel", "pos_groups", "n_ctx")
+    PAD = 40
 
     def __init__(self, dims, state):
         d = {k: int(dims[k]) for k in self.FIELDS}
@@ -702,23 +778,7 @@ class Hubert(_Handle):
 
     @staticmethod
     def check_dims(d):
-        for k in ("conv_dim", "n_state"):
-            if d[k] < 64 or d[k] % 64 or d[k] > 1024:
-                raise ValueError(f"Hubert: {k} {d[k]} must be a multiple of 64 in 64 .. 1024")
-        if d["n_head"] < 1 or d["n_state"] != 64 * d["n_head"]:
-            raise ValueError(f"Hubert: n_state {d['n_state']} must be 64 * n_head ({d['n_head']})")
-        for k in ("n_ffn", "n_proj"):
-            if d[k] < 64 or d[k] % 64:
-                raise ValueError(f"Hubert: {k} {d[k]} must be a positive multiple of 64")
-        if d["pos_kernel"] < 2 or d["pos_kernel"] > 128 or d["pos_kernel"] % 2:
-            raise ValueError(f"Hubert: pos_kernel {d['pos_kernel']} must be even in 2 .. 128")
-        g = d["pos_groups"]
-        if g < 1 or d["n_state"] % g or (d["n_state"] // g) % 16 or d["n_state"] // g > 64:
-            raise ValueError(f"Hubert: n_state / pos_groups must be 16, 32, 48 or 64 (got {d['n_state']} / {g})")
-        if not 1 <= d["n_layer"] <= 64:
-            raise ValueError(f"Hubert: n_layer {d['n_layer']} outside 1 .. 64")
-        if not 1 <= d["n_ctx"] <= 1500:
-            raise ValueError(f"Hubert: n_ctx {d['n_ctx']} outside 1 .. 1500")
+        _w2v_check_dims(d, ("n_ffn", "n_proj"))
 
     @staticmethod
     def frames(n_samples, pad=40):
@@ -726,54 +786,20 @@ class Hubert(_Handle):
         from . import arch
         return arch.hubert_frames(n_samples, pad)
 
-    def _check(self, B, L, pad):
-        if B < 1:
-            raise ValueError("Hubert: an empty batch")
-        if not 0 <= pad <= 40:
-            raise ValueError(f"Hubert: pad {pad} outside 0 .. 40")
-        if L < 400 - 2 * pad:
-            raise ValueError(f"Hubert: clips need at least {400 - 2 * pad} samples (got {L})")
-        if self.frames(L, pad) > self.dims["n_ctx"]:
-            raise ValueError(f"Hubert: {L} samples give {self.frames(L, pad)} frames, more than n_ctx {self.dims['n_ctx']}")
-
-    @staticmethod
-    def lengths(lengths, B, L, pad=40):
-        """per-clip sample counts -> host int32 [B] (include/lds.h: B <= 64, 400 - 2 pad .. L)"""
-        return _host_lengths(lengths, B, 400 - 2 * pad, L, 64, "units")
-
-    def workspace_bytes(self, B, L, pad=40):
-        return _bytes("lds_hubert_workspace_bytes", self.h, B, L, pad)
-
-    def _args(self, audio, lengths, ws, pad):
-        if audio.dim() != 2:
-            raise ValueError(f"Hubert: audio must be [B, L], got {list(audio.shape)}")
-        B, L = audio.shape
-        self._check(B, L, pad)
-        ln = self.lengths(lengths, B, L, pad) if lengths is not None else None
-        _dev(audio, None)
-        ws = ws if ws is not None else self.ws.get(self.workspace_bytes(B, L, pad), audio.device)
-        return B, L, ln, ws
+    _units_of = frames
 
     def features(self, audio, lengths=None, ws=None, pad=40):
-        import torch
-        B, L, ln, ws = self._args(audio, lengths, ws, pad)
-        out = torch.empty(B, self.frames(L, pad), self.dims["conv_dim"], dtype=torch.float32, device=audio.device)
-        check(lib().lds_hubert_features(self.h, _dev(audio, torch.float32), _host(ln), _dev(out), _dev(ws), ws.numel(), B, L, pad, _stream()))
-        return out
+        return self._call("lds_hubert_features", audio, lengths, ws, lambda n, L: (n, self.dims["conv_dim"]), pad=pad)
 
     def encode(self, audio, lengths=None, layer=None, proj=False, ws=None, pad=40):
         """layer: the blocks to run (None = all, 0 = the output of `norm`); proj: apply `proj` (all blocks only) -> [B,T,n_proj]"""
-        import torch
         nl = self.dims["n_layer"] if layer is None else int(layer)
         if not 0 <= nl <= self.dims["n_layer"]:
             raise ValueError(f"Hubert: layer {nl} outside 0 .. {self.dims['n_layer']}")
         if proj and nl != self.dims["n_layer"]:
             raise ValueError(f"Hubert: proj follows the last layer (layer {nl} of {self.dims['n_layer']})")
-        B, L, ln, ws = self._args(audio, lengths, ws, pad)
-        out = torch.empty(B, self.frames(L, pad), self.dims["n_proj" if proj else "n_state"], dtype=torch.float32, device=audio.device)
-        check(lib().lds_hubert_encode(self.h, _dev(audio, torch.float32), _host(ln), _dev(out), nl, 1 if proj else 0, _dev(ws), ws.numel(), B, L, pad,
-                                      _stream()))
-        return out
+        width = self.dims["n_proj" if proj else "n_state"]
+        return self._call("lds_hubert_encode", audio, lengths, ws, lambda n, L: (n, width), mid=(nl, 1 if proj else 0), pad=pad)
 
 
 class W2vCfg(C.Structure):
@@ -781,7 +807,7 @@ class W2vCfg(C.Structure):
                 ("pos_kernel", C.c_int), ("pos_groups", C.c_int), ("n_ctx", C.c_int)]
 
 
-class Wav2Vec2(_Handle):
+class Wav2Vec2(_UnitsEncoder):
     """wav2vec 2.0 units encoder in its layer-norm flavour, XLSR-53 (lds_w2v_*): audio [B,L] at 16 kHz, taken as it is -> the feature
     extractor's output [B,T,conv_dim] / the encoder's [B,T,n_state].  `state`: fairseq-named tensors (lds.arch.w2v_param_shapes).
     `lengths`: every clip's own sample count (host ints, 400 .. L, at most 64 clips): each clip is encoded as if alone.  Every limit of
@@ -797,44 +823,21 @@ class Wav2Vec2(_Handle):
 
     @staticmethod
     def check_dims(d):
-        Hubert.check_dims(dict(d, n_proj=64))      # (the limits are HuBERT's; there is no proj here)
+        _w2v_check_dims(d, ("n_ffn",))      # (the limits are HuBERT's; there is no proj here)
 
     @staticmethod
     def frames(n_samples):
         from . import arch
         return arch.w2v_frames(n_samples)
 
-    @staticmethod
-    def lengths(lengths, B, L):
-        """per-clip sample counts -> host int32 [B] (include/lds.h: B <= 64, 400 .. L)"""
-        return _host_lengths(lengths, B, 400, L, 64, "units")
-
-    def workspace_bytes(self, B, L):
-        return _bytes("lds_w2v_workspace_bytes", self.h, B, L)
-
-    def _run(self, entry, width, audio, lengths, ws):
-        import torch
-        if audio.dim() != 2:
-            raise ValueError(f"Wav2Vec2: audio must be [B, L], got {list(audio.shape)}")
-        B, L = audio.shape
-        if B < 1:
-            raise ValueError("Wav2Vec2: an empty batch")
-        if L < 400:
-            raise ValueError(f"Wav2Vec2: clips need at least 400 samples (got {L})")
-        if self.frames(L) > self.dims["n_ctx"]:
-            raise ValueError(f"Wav2Vec2: {L} samples give {self.frames(L)} frames, more than n_ctx {self.dims['n_ctx']}")
-        ln = self.lengths(lengths, B, L) if lengths is not None else None
-        _dev(audio, None)
-        ws = ws if ws is not None else self.ws.get(self.workspace_bytes(B, L), audio.device)
-        out = torch.empty(B, self.frames(L), self.dims[width], dtype=torch.float32, device=audio.device)
-        check(getattr(lib(), entry)(self.h, _dev(audio, torch.float32), _host(ln), _dev(out), _dev(ws), ws.numel(), B, L, _stream()))
-        return out
+    def _units_of(self, n_samples, pad=0):
+        return self.frames(n_samples)
 
     def features(self, audio, lengths=None, ws=None):
-        return self._run("lds_w2v_features", "conv_dim", audio, lengths, ws)
+        return self._call("lds_w2v_features", audio, lengths, ws, lambda n, L: (n, self.dims["conv_dim"]))
 
     def encode(self, audio, lengths=None, ws=None):
-        return self._run("lds_w2v_encode", "n_state", audio, lengths, ws)
+        return self._call("lds_w2v_encode", audio, lengths, ws, lambda n, L: (n, self.dims["n_state"]))
 
 
 class W2vBertCfg(C.Structure):
@@ -842,7 +845,7 @@ class W2vBertCfg(C.Structure):
                [("eps", C.c_float)]
 
 
-class Wav2Vec2Bert(_Handle):
+class Wav2Vec2Bert(_UnitsEncoder):
     """w2v-BERT 2.0 units encoder (lds_w2vbert_*): audio [B,L] at 16 kHz -> SeamlessM4TFeatureExtractor's input_features [B,R,n_mels*stride] /
     Wav2Vec2BertModel's last_hidden_state [B,R,n_state], R = the rows of L samples (lds.arch.w2vbert_frames).  `state`: transformers-named
     tensors (lds.arch.w2vbert_param_shapes).  `lengths`: every clip's own sample count (host ints, 560 .. L, at most 64 clips): each clip is
@@ -850,7 +853,8 @@ class Wav2Vec2Bert(_Handle):
     Every limit of include/lds.h is checked here first (ValueError, before a device is touched)."""
     KIND = "w2vbert"
     FIELDS = ("n_mels", "stride", "n_state", "n_head", "n_ffn", "n_layer", "left_max", "right_max", "dw_kernel", "n_ctx")
-    MIN_SAMPLES, MAX_CLIPS = 560, 64
+    MIN_SAMPLES, MAX_BATCH = 560, 64
+    UNIT, HINT = "rows", "; pad them as Units_Encoder.encode does"
 
     def __init__(self, dims, state):
         d = self.check_dims(dims)
@@ -885,41 +889,14 @@ class Wav2Vec2Bert(_Handle):
         n = 1 + (int(n_samples) - 400) // 160
         return (n + self.dims["stride"] - 1) // self.dims["stride"]
 
-    @classmethod
-    def lengths(cls, lengths, B, L):
-        """per-clip sample counts -> host int32 [B] (include/lds.h: B <= 64, 560 .. L)"""
-        return _host_lengths(lengths, B, cls.MIN_SAMPLES, L, cls.MAX_CLIPS, "units")
-
-    def workspace_bytes(self, B, L):
-        return _bytes("lds_w2vbert_workspace_bytes", self.h, B, L)
-
-    def _check_audio(self, audio):
-        if audio.dim() != 2:
-            raise ValueError(f"Wav2Vec2Bert: audio must be [B, L], got {list(audio.shape)}")
-        B, L = audio.shape
-        if not 1 <= B <= self.MAX_CLIPS:
-            raise ValueError(f"Wav2Vec2Bert: 1 .. {self.MAX_CLIPS} clips per call (got {B})")
-        if L < self.MIN_SAMPLES:
-            raise ValueError(f"Wav2Vec2Bert: clips need at least {self.MIN_SAMPLES} samples (got {L}); pad them as Units_Encoder.encode does")
-        if self.rows(L) > self.dims["n_ctx"]:
-            raise ValueError(f"Wav2Vec2Bert: {L} samples give {self.rows(L)} rows, more than n_ctx {self.dims['n_ctx']}")
-        return B, L
-
-    def _run(self, entry, width, audio, lengths, ws):
-        import torch
-        B, L = self._check_audio(audio)
-        ln = self.lengths(lengths, B, L) if lengths is not None else None
-        _dev(audio, None)
-        ws = ws if ws is not None else self.ws.get(self.workspace_bytes(B, L), audio.device)
-        out = torch.empty(B, self.rows(L), width, dtype=torch.float32, device=audio.device)
-        check(getattr(lib(), entry)(self.h, _dev(audio, torch.float32), _host(ln), _dev(out), _dev(ws), ws.numel(), B, L, _stream()))
-        return out
+    def _units_of(self, n_samples, pad=0):
+        return self.rows(n_samples)
 
     def fbank(self, audio, lengths=None, ws=None):
-        return self._run("lds_w2vbert_fbank", self.dims["n_mels"] * self.dims["stride"], audio, lengths, ws)
+        return self._call("lds_w2vbert_fbank", audio, lengths, ws, lambda n, L: (n, self.dims["n_mels"] * self.dims["stride"]))
 
     def encode(self, audio, lengths=None, ws=None):
-        return self._run("lds_w2vbert_encode", self.dims["n_state"], audio, lengths, ws)
+        return self._call("lds_w2vbert_encode", audio, lengths, ws, lambda n, L: (n, self.dims["n_state"]))
 
     def encode_features(self, feats, n_frames=None, ws=None):
         """feats [B, R, n_mels * stride] (input_features) -> [B, R, n_state]; n_frames: every clip's frame count n (host ints, 2 .. stride R;
@@ -929,13 +906,13 @@ class Wav2Vec2Bert(_Handle):
         if feats.dim() != 3 or feats.shape[2] != fd:
             raise ValueError(f"Wav2Vec2Bert: features must be [B, R, {fd}], got {list(feats.shape)}")
         B, R = feats.shape[0], feats.shape[1]
-        if not 1 <= B <= self.MAX_CLIPS:
-            raise ValueError(f"Wav2Vec2Bert: 1 .. {self.MAX_CLIPS} clips per call (got {B})")
+        if not 1 <= B <= self.MAX_BATCH:
+            raise ValueError(f"Wav2Vec2Bert: 1 .. {self.MAX_BATCH} clips per call (got {B})")
         if not 1 <= R <= self.dims["n_ctx"]:
             raise ValueError(f"Wav2Vec2Bert: {R} rows outside 1 .. n_ctx {self.dims['n_ctx']}")
         nf = None
         if n_frames is not None:
-            nf = _host_lengths(n_frames, B, max(2, st), st * R, self.MAX_CLIPS, "units")
+            nf = _host_lengths(n_frames, B, max(2, st), st * R, self.MAX_BATCH, "units")
         _dev(feats, None)
         ws = ws if ws is not None else self.ws.get(self.workspace_bytes(B, 400 + 160 * (st * R - 1)), feats.device)
         out = torch.empty(B, R, self.dims["n_state"], dtype=torch.float32, device=feats.device)
@@ -943,11 +920,12 @@ class Wav2Vec2Bert(_Handle):
         return out
 
 
-class Whisper(_Handle):
+class Whisper(_UnitsEncoder):
     """Whisper units encoder (lds_whisper_*): audio [B,L] at 16 kHz -> log-mel [B,n_mels,L//160] / units [B,T,n_state], T = (L//160 - 1)//2 + 1.
     `lengths`: every clip's own sample count (host ints, 400 .. L, at most 64 clips): each clip is encoded as if alone."""
     KIND = "whisper"
     HOP, N_FFT = 160, 400
+    CTX, HINT = "n_audio_ctx", "; pad them as Units_Encoder.encode does"
 
     def __init__(self, n_mels, n_state, n_head, n_layer, n_ctx, state, mel_filters):
         if n_mels not in (80, 128):
@@ -961,38 +939,17 @@ class Whisper(_Handle):
             raise ValueError(f"Whisper: mel_filters must be [{n_mels}, 201], got {list(mf.shape)}")
         self._create_weights(WhisperCfg(n_mels, n_state, n_head, n_layer, n_ctx), state, _host(mf))
         self.n_mels, self.n_state, self.n_ctx = n_mels, n_state, n_ctx
+        self.dims = dict(n_mels=n_mels, n_state=n_state, n_ctx=n_ctx)
 
     def frames(self, n_mel_frames):
         return (int(n_mel_frames) - 1) // 2 + 1
 
-    def _check(self, B, L):
-        if B < 1:
-            raise ValueError("Whisper: an empty batch")
-        if L < self.N_FFT:
-            raise ValueError(f"Whisper: clips need at least {self.N_FFT} samples (got {L}); pad them as Units_Encoder.encode does")
-        if self.frames(L // self.HOP) > self.n_ctx:
-            raise ValueError(f"Whisper: {L} samples give {self.frames(L // self.HOP)} frames, more than n_audio_ctx {self.n_ctx}")
-
-    def lengths(self, lengths, B, L):
-        """per-clip sample counts -> host int32 [B] (include/lds.h: B <= 64, 400 .. L)"""
-        return _host_lengths(lengths, B, self.N_FFT, L, 64, "units")
-
-    def workspace_bytes(self, B, L):
-        return _bytes("lds_whisper_workspace_bytes", self.h, B, L)
-
-    def _ws(self, ws, B, L, device):
-        return ws if ws is not None else self.ws.get(self.workspace_bytes(B, L), device)
+    def _units_of(self, n_samples, pad=0):
+        return self.frames(n_samples // self.HOP)
 
     def logmel(self, audio, lengths=None, ws=None):
         """audio [B,L] -> [B,n_mels,L//160] (frames at and beyond a clip's own count are zeros)"""
-        import torch
-        B, L = audio.shape
-        self._check(B, L)
-        ln = self.lengths(lengths, B, L) if lengths is not None else None
-        ws = self._ws(ws, B, L, audio.device)
-        mel = torch.empty(B, self.n_mels, L // self.HOP, dtype=torch.float32, device=audio.device)
-        check(lib().lds_whisper_logmel(self.h, _dev(audio, torch.float32), _host(ln), _dev(mel), _dev(ws), ws.numel(), B, L, _stream()))
-        return mel
+        return self._call("lds_whisper_logmel", audio, lengths, ws, lambda n, L: (self.n_mels, L // self.HOP))
 
     def encode_mel(self, mel, n_frames=None, ws=None):
         """mel [B,n_mels,F] -> units [B,T,n_state]; n_frames: every clip's own mel frame count (host ints) or None"""
@@ -1003,21 +960,14 @@ class Whisper(_Handle):
         if B < 1 or F < 1 or self.frames(F) > self.n_ctx:
             raise ValueError(f"Whisper: {F} mel frames give {self.frames(F)} frames, outside 1 .. n_audio_ctx {self.n_ctx}")
         nf = _host_lengths(n_frames, B, 1, F, 64, "units") if n_frames is not None else None
-        ws = self._ws(ws, B, max(F * self.HOP, self.N_FFT), mel.device)
+        ws = ws if ws is not None else self.ws.get(self.workspace_bytes(B, max(F * self.HOP, self.N_FFT)), mel.device)
         units = torch.empty(B, self.frames(F), self.n_state, dtype=torch.float32, device=mel.device)
         check(lib().lds_whisper_encode_mel(self.h, _dev(mel, torch.float32), _host(nf), _dev(units), _dev(ws), ws.numel(), B, F, _stream()))
         return units
 
     def encode(self, audio, lengths=None, ws=None):
         """audio [B,L] -> units [B,T,n_state] (rows at and beyond a clip's own frame count are zeros)"""
-        import torch
-        B, L = audio.shape
-        self._check(B, L)
-        ln = self.lengths(lengths, B, L) if lengths is not None else None
-        ws = self._ws(ws, B, L, audio.device)
-        units = torch.empty(B, self.frames(L // self.HOP), self.n_state, dtype=torch.float32, device=audio.device)
-        check(lib().lds_whisper_encode(self.h, _dev(audio, torch.float32), _host(ln), _dev(units), _dev(ws), ws.numel(), B, L, _stream()))
-        return units
+        return self._call("lds_whisper_encode", audio, lengths, ws, lambda n, L: (n, self.n_state))
 
 
 def _conv_down(x, w, b, stride, slope, tile, cfg, lengths_in=None, lengths_out=None):
