@@ -121,6 +121,18 @@ int lds_test_conv_down_ragged(const float* x, const float* w, const float* b, in
                               const int32_t* lengths_in, const int32_t* lengths_out, int tile, float* out, char* cfg_out, size_t cfg_cap,
                               void* stream);
 int lds_debug_set_split_rule(int rule);
+/* host only (no device is touched): conv_dma's block-index decomposition without a division (csrc/kernels.h dma_magic).
+ * lds_test_dma_magic_div: out[n] = n / d for n in [0, n_count) through the launchers' multiplier / shift pair.
+ * lds_test_dma_tile_order: out[id][4] = (M-block, frame block, batch element, cluster share) of every workgroup id of a grid of
+ * nMb * nN * B * S workgroups, with the constants the launchers pass and the arithmetic the kernel runs. */
+int lds_test_dma_magic_div(uint32_t d, uint32_t n_count, uint32_t* out);
+int lds_test_dma_tile_order(int nMb, int nN, int B, int S, int32_t* out);
+/* Arm a tap on the calling thread: the next call of lds_test_dconv (fp32, K4P output), lds_test_dconv_ex / lds_test_dconv_pair (fmt -1),
+ * lds_test_ln_chain_k4p (its `out` tensor) or lds_test_attention_k4p / _f16math / _latency fills the K4P buffer its kernel writes with NaN
+ * before the launch and copies it to dst afterwards, as the kernel left it: dev [B][C/8][2][T + 2][4] (csrc/k4p.h), entry 0 and entry T + 1
+ * of every row being the pad frames.  floats must be B * C * (T + 2) of that output (an error otherwise); the tap is then disarmed.
+ * dst NULL, floats 0: disarm. */
+int lds_test_tap_k4p(float* dst, size_t floats);
 
 /* ---- conv_dma / conv_bf3 modes that the product reaches through whole models only (tests/test_gpu_conv_modes.py) ----
  * Common to the three entries: fmt -1 = exact fp32 (K4P, conv_dma), 0 = three bf16 planes, 1 = two fp16 planes (conv_bf3), as lds_test_gn_fold_split;

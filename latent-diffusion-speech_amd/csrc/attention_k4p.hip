@@ -93,6 +93,33 @@ static __device__ __forceinline__ void att_issue_tile(const __amdgpu_buffer_rsrc
                                                  kt * (64 * D * 4), 0, 0);
 }
 
+// K4P store of a wave's output tiles o[i] / l (rows = channels hd * D + 32 i + ..., column = query tq): 16-byte write-through entries
+// (k4p.h k4p_tile_entries; the swaps run with every lane active, the stores under tq < Tbuf), zeros for a query beyond its utterance's
+// length, and the two pad frames by the lanes of the first and the last query.  ob = this batch element's tensor, Tp entries per row.
+template <int D>
+static __device__ __forceinline__ void att_store_k4p(const f32x16* o, float rl, float* ob, int C, int Tp, int hd, int h, int tq, int Tbuf, bool live) {
+    constexpr int DT = (D + 31) / 32;
+    const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(ob, 0, C * Tp * 4, 0x00020000);
+#pragma unroll
+    for (int i = 0; i < DT; ++i) {
+        f32x16 v;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) v[r] = live ? o[i][r] * rl : 0.f;
+        k4p_f32x4 ent[4];
+        k4p_tile_entries(v, ent);
+        if (tq < Tbuf) {
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                if (i * 32 + 8 * g >= D) break;
+                const int off = k4p_entry_off((hd * D + i * 32) / 8 + g, h, Tp, tq + 1);
+                k4p_store16_wt(ro, off, ent[g]);
+                if (tq == 0) k4p_store16(ro, off - 16, k4p_f32x4{0.f, 0.f, 0.f, 0.f});
+                if (tq == Tbuf - 1) k4p_store16(ro, off + 16, k4p_f32x4{0.f, 0.f, 0.f, 0.f});
+            }
+        }
+    }
+}
+
 // KS = 2 (short sequences): the workgroup covers (NW/2)*32 queries and its two wave groups each take one 32-key half of every
 // staged tile, so twice as many waves share the work; the partial (max, sum, output) triples meet through LDS at the end.
 template <int D, int NW, int NST, int KS, bool F16>
@@ -339,24 +366,8 @@ __global__ void __launch_bounds__(NW * 64) attention_k4p_kernel(const float* __r
                     if (tq == Tbuf - 1) *reinterpret_cast<k8_u32x2*>(e + 16) = k8_u32x2{0u, 0u};
                 }
             }
-    } else if (tq < Tbuf) {
-        const bool live = tq < T;      // (ragged batch: queries beyond the utterance's length are written as zeros)
-        const float rl = 1.0f / l;
-        float* ob = out + (long long)b * C * Tp;
-#pragma unroll
-        for (int i = 0; i < DT; ++i)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                if (i * 32 + 8 * g >= D) break;
-                const int q = (hd * D + i * 32) / 8 + g;
-#pragma unroll
-                for (int hh = 0; hh < 2; ++hh) {
-                    const long long off = ((long long)(q * 2 + hh) * Tp + tq + 1) * 4 + 2 * h;
-                    k4p_store_wt(ob + off, live ? f32x2{o[i][4 * g + hh] * rl, o[i][4 * g + 2 + hh] * rl} : f32x2{0.f, 0.f});      // write-through (k4p.h)
-                    if (tq == 0) *reinterpret_cast<f32x2*>(ob + off - 4) = f32x2{0.f, 0.f};
-                    if (tq == Tbuf - 1) *reinterpret_cast<f32x2*>(ob + off + 4) = f32x2{0.f, 0.f};
-                }
-            }
+    } else if (!out_bf3) {
+        att_store_k4p<D>(o, 1.0f / l, out + (long long)b * C * Tp, C, Tp, hd, h, tq, Tbuf, tq < T);      // (ragged batch: queries beyond the utterance's length are written as zeros)
     }
 }
 
@@ -608,24 +619,7 @@ __global__ void __launch_bounds__(NW * 64) attention_k4p_rel_kernel(const float*
         const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(l_run), __float_as_uint(l_run), false, false);
         l = __uint_as_float(sw[0]) + __uint_as_float(sw[1]);
     }
-    if (tq < Tbuf) {
-        const bool live = tq < Tq;
-        const float rl = 1.0f / l;
-        float* ob = out + (long long)b * C * Tp;
-#pragma unroll
-        for (int i = 0; i < DT; ++i)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const int q = (hd * D + i * 32) / 8 + g;
-#pragma unroll
-                for (int hh = 0; hh < 2; ++hh) {
-                    const long long off = ((long long)(q * 2 + hh) * Tp + tq + 1) * 4 + 2 * h;
-                    k4p_store_wt(ob + off, live ? f32x2{o[i][4 * g + hh] * rl, o[i][4 * g + 2 + hh] * rl} : f32x2{0.f, 0.f});
-                    if (tq == 0) *reinterpret_cast<f32x2*>(ob + off - 4) = f32x2{0.f, 0.f};
-                    if (tq == Tbuf - 1) *reinterpret_cast<f32x2*>(ob + off + 4) = f32x2{0.f, 0.f};
-                }
-            }
-    }
+    att_store_k4p<D>(o, 1.0f / l, out + (long long)b * C * Tp, C, Tp, hd, h, tq, Tbuf, tq < Tq);
 }
 
 template <int NW, int NST, int KS>

@@ -23,6 +23,7 @@
 #include "gn_chan.h"
 #include "k4p.h"
 #include "kernels.h"
+#include "../../include/lds_test.h"
 
 #include <hip/hip_ext.h>
 
@@ -101,6 +102,14 @@ struct DmaKernel {
 
     const DmaConvArgs& p;
     float* smem;
+    // The arguments that the first DMA issue depends on.  load_hot() requests them all at kernel entry and pins them behind ONE wait
+    // (an empty asm that takes every one of them as an operand), instead of one scalar-memory round trip per branch that first uses a
+    // field; the code in front of the first issue_tile reads these copies only.  Every other field is read from `p` where it is used.
+    struct Hot {
+        const float *x1, *x2, *w;      // (used as buffer bases only; `lens` is dereferenced and stays a kernel-argument pointer: a scalar load)
+        int C1, C2, Tsrc, Mp, Ci, xpad, pad, ksplit, To, lvl_out;
+        unsigned om0, om1, om2, os, gx, gy;
+    } hp;
     int lane, wave, c, h, wm, wn, ks, b, m0, t0;
     int ksp, kc0, ctile;      // cluster split-K (DmaConvArgs::ksplit): this workgroup's share index, its first K-step, its tile's linear index
     int Lout;                 // valid output frames of this batch element (ragged batches, k4p.h ragged_len; = To otherwise)
@@ -121,12 +130,37 @@ struct DmaKernel {
     // rows have landed long before the main loop ends, so the epilogue begins without a memory round trip
     // (vocoder tiles too: their K loops run 20-40 us, the 8 residual registers per 32 x 32 tile fit beside the accumulators)
     static constexpr bool EARLY = TM * TN == 1 || VOC;
+    // ... and the UNet's and the encoders' single-tile waves request them BEHIND the first NST tiles' DMAs (late_loads): the first DMA
+    // then waits for neither their address arithmetic nor -- vmcnt completes in order -- their data.  NLATE = the vector memory operations
+    // late_loads() issues, the same number whatever the arguments are (a null residual or bias is a buffer of zero bytes, which reads as
+    // zeros): the counted waits below rely on it.  The GroupNorm fold keeps its own order (gnf_request), the vocoder the old one.
+    static constexpr bool LATE = EARLY && !VOC && !GNF;
+    static constexpr int NLATE = LATE ? TM * TN * 8 + TM * 4 : 0;
+    static_assert(PER_TILE * (NST - 1) + NLATE <= 63 || !LATE, "vmcnt is a 6-bit field");
     f32x2 rsv[EARLY ? TM * TN * 8 : 1];
     float kbv[EARLY ? TM * 16 : 1];
 
     __device__ __forceinline__ DmaKernel(const DmaConvArgs& p_, float* s_) : p(p_), smem(s_) {}
 
+    // k4p.h ragged_len / the vocoder's lengths, read through the constant address space: the lengths do not change during a launch, and so
+    // the read stays a scalar load behind load_hot()'s asm statement (which the compiler must assume to write memory)
+    typedef const __attribute__((address_space(4))) int* const_int_ptr;
+    __device__ __forceinline__ int len_at(int lvl, int T) const {
+        if (!p.lens) return T;
+        int n = ((const_int_ptr)(unsigned long long)p.lens)[b];
+        for (int i = 0; i < lvl; ++i) n = (n - 1) / 2 + 1;
+        return n < T ? n : T;
+    }
+    __device__ __forceinline__ void load_hot() {
+        hp.x1 = p.x1; hp.x2 = p.x2; hp.w = p.w;
+        hp.C1 = p.C1; hp.C2 = p.C2; hp.Tsrc = p.Tsrc; hp.Mp = p.Mp; hp.Ci = p.Ci; hp.xpad = p.xpad; hp.pad = p.pad; hp.ksplit = p.ksplit; hp.To = p.To;
+        hp.lvl_out = p.lvl_out; hp.om0 = p.ord_m[0]; hp.om1 = p.ord_m[1]; hp.om2 = p.ord_m[2]; hp.os = p.ord_s; hp.gx = gridDim.x; hp.gy = gridDim.y;
+        asm volatile("" : "+s"(hp.x1), "+s"(hp.x2), "+s"(hp.w), "+s"(hp.C1), "+s"(hp.C2), "+s"(hp.Tsrc), "+s"(hp.Mp), "+s"(hp.Ci),
+                          "+s"(hp.xpad), "+s"(hp.pad), "+s"(hp.ksplit), "+s"(hp.To), "+s"(hp.lvl_out), "+s"(hp.om0), "+s"(hp.om1), "+s"(hp.om2),
+                          "+s"(hp.os), "+s"(hp.gx), "+s"(hp.gy));
+    }
     __device__ __forceinline__ void setup_keep_acc() {      // everything but the accumulators (second phase of conv_dma_pair_kernel)
+        load_hot();
         const int tid = threadIdx.x;
         lane = tid & 63;
         wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -136,50 +170,53 @@ struct DmaKernel {
         // XCD-aware tile order.  Workgroups are dispatched in linear order, round-robin over the 8 XCDs, each with a private
         // L2.  The workgroups that read the same activation window (all M-blocks of one (batch, frame-block)) are given
         // consecutive slots of ONE XCD, so the window is fetched from the fabric once instead of once per XCD.
-        const int nMb = p.Mp / BM;
-        const int gx = gridDim.x, total = gx * gridDim.y;
+        // The three divisions (by nMb, nN and S) are multiplications by the launcher's constants (kernels.h dma_magic): exact quotients
+        // on the scalar unit, instead of a detour through the vector unit's reciprocal each.
+        const int nMb = (int)((unsigned)hp.Mp / BM), nN = (int)((unsigned)(hp.To + BN - 1) / BN);
+        const int gx = (int)hp.gx, total = gx * (int)hp.gy;
         const int id = blockIdx.y * gx + blockIdx.x;
         const int xcd = id & 7, slot = id >> 3, per = total >> 3, rem = total & 7;
-        const int L = xcd * per + (xcd < rem ? xcd : rem) + slot;
-        const int mb = L % nMb;                   // M fastest: neighbours share the activation tile
-        const int tb = L / nMb;
-        const int nN = gx / nMb;
-        const int nb = tb % nN;
-        const int by = tb / nN, S = p.ksplit > 1 ? p.ksplit : 1;      // grid.y = B * S
-        b = by / S; ksp = by - b * S;
-        kc0 = ksp * (p.Ci / BK / S);
+        const unsigned L = (unsigned)(xcd * per + (xcd < rem ? xcd : rem) + slot);
+        const unsigned tb = dma_magic_div(L, hp.om0, hp.os & 255);
+        const int mb = (int)(L - tb * nMb);       // M fastest: neighbours share the activation tile
+        const unsigned by = dma_magic_div(tb, hp.om1, (hp.os >> 8) & 255);
+        const int nb = (int)(tb - by * nN);
+        const int S = hp.ksplit > 1 ? hp.ksplit : 1;      // grid.y = B * S
+        b = (int)dma_magic_div(by, hp.om2, (hp.os >> 16) & 255); ksp = (int)by - b * S;
+        kc0 = ksp * steps_per_share();
         ctile = (b * nN + nb) * nMb + mb;
         m0 = mb * BM; t0 = nb * BN;
-        Lout = ragged_len(p.lens, b, p.lvl_out, p.To);
+        Lout = len_at(hp.lvl_out, hp.To);
 #pragma unroll
         for (int i = 0; i < WPW; ++i) {
-            const int q = (wave + 4 * i) * 64 + lane;           // chunk = (tap, k-row, m)
-            const int tap = q / (KR * BM);
-            const int rem = q - tap * (KR * BM);
-            const int rr = rem / BM, m = rem - rr * BM;
-            woff[i] = ((tap * (p.Ci / 4) + rr) * p.Mp + m0 + m) * 16;
+            const unsigned q = (unsigned)(wave + 4 * i) * 64u + (unsigned)lane;      // chunk = (tap, k-row, m)  (unsigned: shifts and masks, no sign fix-ups)
+            const unsigned tap = q / (unsigned)(KR * BM);
+            const unsigned rem = q - tap * (unsigned)(KR * BM);
+            const unsigned rr = rem / (unsigned)BM, m = rem - rr * (unsigned)BM;
+            woff[i] = (int)(((tap * ((unsigned)hp.Ci / 4u) + rr) * (unsigned)hp.Mp + (unsigned)m0 + m) * 16u);
         }
-        const int Tp = p.Tsrc + 2 * p.xpad;
-        const int e0 = UPS ? (((t0 - 1) >> 1) + p.xpad) : (t0 * STRIDE - p.pad + p.xpad);   // first window entry (entry xpad = frame 0)
+        const int Tp = hp.Tsrc + 2 * hp.xpad;
+        const int e0 = UPS ? (((t0 - 1) >> 1) + hp.xpad) : (t0 * STRIDE - hp.pad + hp.xpad);   // first window entry (entry xpad = frame 0)
 #pragma unroll
         for (int i = 0; i < NXI; ++i) {
-            const int qq = i * 64 + lane;
-            const int rl = qq / XW, col = qq - rl * XW;
-            xact[i] = qq < RPW * XW;
+            const unsigned qq = (unsigned)(i * 64 + lane);
+            const int rl = (int)(qq / (unsigned)XW), col = (int)qq - rl * XW;
+            xact[i] = (int)qq < RPW * XW;
             xoff[i] = ((wave * RPW + rl) * Tp + e0 + col) * 16;
         }
-        rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.w), 0, KT * p.Ci * p.Mp * 4, 0x00020000);
-        rx1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.x1 + (long long)b * p.C1 * Tp), 0, p.C1 * Tp * 4, 0x00020000);
-        rx2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.x2 ? p.x2 + (long long)b * p.C2 * Tp : p.x1), 0, p.C2 * Tp * 4, 0x00020000);
+        rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(hp.w), 0, KT * hp.Ci * hp.Mp * 4, 0x00020000);
+        rx1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(hp.x1 + (long long)b * hp.C1 * Tp), 0, hp.C1 * Tp * 4, 0x00020000);
+        rx2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(hp.x2 ? hp.x2 + (long long)b * hp.C2 * Tp : hp.x1), 0, hp.C2 * Tp * 4, 0x00020000);
         arow = wm * TM * 32 + c;
 #pragma unroll
         for (int j = 0; j < TN; ++j) bcol[j] = wn * TN * 32 + j * 32 + c;
     }
+    // this workgroup's K-steps: Ci / BK / S (S = the cluster split, a divisor of Ci / BK: the launchers check it)
+    __device__ __forceinline__ int steps_per_share() const { return (int)dma_magic_div((unsigned)hp.Ci / BK, hp.om2, (hp.os >> 16) & 255); }
     __device__ __forceinline__ bool dead_tile() const { return !VOC && p.lens && t0 >= Lout; }
     // the vocoder's lengths multiply per stage: given outright (kernels.h DmaConvArgs::vlen), fetched where they are used (the epilogue)
-    __device__ __forceinline__ int voc_len() const { return p.vlen[b]; }
-    __device__ __forceinline__ void setup() {
-        setup_keep_acc();
+    __device__ __forceinline__ int voc_len() const { return ((const_int_ptr)(unsigned long long)p.vlen)[b]; }
+    __device__ __forceinline__ void zero_acc() {
 #pragma unroll
         for (int a = 0; a < NACC; ++a)
 #pragma unroll
@@ -194,13 +231,13 @@ struct DmaKernel {
     // LDS-DMA: per-lane byte offsets are loop invariant (VGPR), the K-step advance is a scalar offset, so issuing a tile
     // costs no vector ALU work; reads past a source slab return zeros (hardware range check).
     __device__ __forceinline__ void issue_tile(int kc, float* st) {
-        const int ws = kc * (KR * 16) * p.Mp;                    // bytes
+        const int ws = kc * (KR * 16) * hp.Mp;                   // bytes
 #pragma unroll
         for (int i = 0; i < WPW; ++i)
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (__attribute__((address_space(3))) void*)(st + ((wave + 4 * i) * 64) * 4), 16, woff[i], ws, 0, 0);
         const int k0 = kc * BK;
-        const bool s2 = k0 >= p.C1;                              // C1 % BK == 0: a K-step reads one source only
-        const int xsoff = (s2 ? k0 - p.C1 : k0) * (p.Tsrc + 2 * p.xpad) * 4;
+        const bool s2 = k0 >= hp.C1;                             // C1 % BK == 0: a K-step reads one source only
+        const int xsoff = (s2 ? k0 - hp.C1 : k0) * (hp.Tsrc + 2 * hp.xpad) * 4;
         float* xs = st + KT * BK * BM + wave * RPW * XW * 4;
 #pragma unroll
         for (int i = 0; i < NXI; ++i)
@@ -246,15 +283,19 @@ struct DmaKernel {
     // Tile boundary, reached when the operand ring is about to read its first group of tile kc+1: this wave has issued
     // (and, after the lgkmcnt wait, completed) all its reads of tile kc.  After the barrier tile kc+1 is visible to
     // everyone and tile kc's stage is free, so it is refilled with tile kc+NST.
+    template <bool EPI>
     __device__ __forceinline__ void tile_sync(int kc, int nk, float* cur) {
         const int younger = (nk - 2 - kc < NST - 2) ? (nk - 2 - kc) : (NST - 2);     // tiles after kc+1 still in flight
-        wait_younger<NST - 2>(younger);
+        // (tile kc+1 < NST belongs to the first burst, which late_loads() follows: its NLATE operations are younger too.  A later tile
+        // was issued after them: they are older and count for nothing.)
+        if (EPI && NLATE > 0 && kc + 1 < NST) wait_younger<NST - 2, NLATE>(younger);
+        else wait_younger<NST - 2, 0>(younger);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
         if (kc + NST < nk) issue_tile(kc0 + kc + NST, cur);
     }
-    template <int g>
+    template <int g, bool EPI>
     __device__ __forceinline__ void kstep(float* cur, const float* nxt, int kc, int nk) {
         if constexpr (g < G) {
             constexpr int gp = g + NB - 1;                     // group whose operands are fetched now
@@ -262,13 +303,13 @@ struct DmaKernel {
                 load_ops<gp % NB>(cur, gp / KQW, gp % KQW);
             } else {
                 if (kc + 1 < nk) {
-                    if constexpr (gp == G) tile_sync(kc, nk, cur);
+                    if constexpr (gp == G) tile_sync<EPI>(kc, nk, cur);
                     load_ops<gp % NB>(nxt, (gp - G) / KQW, (gp - G) % KQW);
                 }
             }
             mfma_ops<g % NB>();
             __builtin_amdgcn_sched_barrier(0);     // keep the operand reads NB-1 groups ahead of their MFMAs
-            kstep<g + 1>(cur, nxt, kc, nk);
+            kstep<g + 1, EPI>(cur, nxt, kc, nk);
         }
     }
 
@@ -298,7 +339,7 @@ struct DmaKernel {
     // partials (wave w takes groups w and w + 4) and for the terms of the row constants
     __device__ __forceinline__ void gnf_request() {
         const int G_ = p.gnf_groups, gsz = p.Ci / G_;
-        const int gTv = ragged_len(p.lens, b, p.lvl_in, p.Tsrc);      // the statistics stop at the utterance's own length
+        const int gTv = len_at(p.lvl_in, p.Tsrc);      // the statistics stop at the utterance's own length
         ginv = 1.0f / (float)gsz;
         gp0 = gn_part_load(p.gnf_part, b, p.Ci, p.Tsrc, gsz >> 4, wave, lane, 0, gTv);                              // (8 groups at most: wave < G_ or an unused slot)
         gp1 = gn_part_load(p.gnf_part, b, p.Ci, p.Tsrc, gsz >> 4, (wave + 4 < G_) ? wave + 4 : wave, lane, 0, gTv);
@@ -319,7 +360,7 @@ struct DmaKernel {
             float rs = 1.f, rm = 0.f;      // (slots of absent groups: finite, they multiply zeros)
             if (g < G_) {
                 float mu, var;
-                gnf_group_stats(p.gnf_part, b, p.Ci, p.Tsrc, gsz >> 4, g, lane, e ? gp1 : gp0, mu, var, ragged_len(p.lens, b, p.lvl_in, p.Tsrc));
+                gnf_group_stats(p.gnf_part, b, p.Ci, p.Tsrc, gsz >> 4, g, lane, e ? gp1 : gp0, mu, var, len_at(p.lvl_in, p.Tsrc));
                 rs = __builtin_amdgcn_rsqf(var + p.gnf_eps); rm = rs * mu;
             }
             if (lane == 0) { tail[g] = rs; tail[8 + g] = rm; }
@@ -345,15 +386,20 @@ struct DmaKernel {
         gsn = gnf_tail()[gnf_group(k + 2)];
     }
 
-    // s_waitcnt vmcnt(y * PER_TILE) for a wave-uniform y in [0, Y]: the y younger tiles' DMAs may stay in flight
-    template <int Y>
+    // s_waitcnt vmcnt(y * PER_TILE + X) for a wave-uniform y in [0, Y]: the y younger tiles' DMAs and X further operations that are
+    // younger than the awaited tile may stay in flight.
+    // INVARIANT: the count must never exceed the number of vector memory operations this wave has ISSUED AFTER the last DMA of the tile
+    // it waits for.  vmcnt completes in order, so with N <= that number the tile has landed when the wait returns; a count that is too
+    // small only waits longer, one that is too large lets the MFMAs read LDS before the DMA has written it -- silently wrong tiles.  So X
+    // may only name operations that are issued unconditionally, by every lane mask, between the burst and the wait (late_loads()).
+    template <int Y, int X = 0>
     __device__ __forceinline__ void wait_younger(int y) {
         if constexpr (Y == 0) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(X > 63 ? 63 : X) : "memory");
         } else {
-            constexpr int N = (Y * PER_TILE > 63) ? 63 : Y * PER_TILE;      // vmcnt is a 6-bit field; a smaller count only waits longer
+            constexpr int N = (Y * PER_TILE + X > 63) ? 63 : Y * PER_TILE + X;      // vmcnt is a 6-bit field; a smaller count only waits longer
             if (y >= Y) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-            else wait_younger<Y - 1>(y);
+            else wait_younger<Y - 1, X>(y);
         }
     }
 
@@ -382,15 +428,66 @@ struct DmaKernel {
         }
     }
 
+    // The same operands through buffer loads, issued right behind the first tiles' DMAs: EXACTLY NLATE vector memory operations (8 residual
+    // entries and 4 bias quads per tile), for every argument set and by every lane -- no branch and no lane mask around them (see
+    // wait_younger).  A launch without a residual, or a tile outside it, reads a buffer of zero bytes: zeros, as before.  Frames beyond To
+    // read whatever the range check lets through; add_residual() does not use them.
+    __device__ __forceinline__ void late_loads() {
+        static_assert(TM * TN == 1, "single-tile waves");
+        const int tile0 = m0 + wm * 32, n = t0 + wn * 32 + c;
+        const int Tpo = p.To + 2 * p.opad, Ck = k4p_ck();
+        const bool rt = p.res && tile0 < p.plain_from && tile0 < p.Cout;      // (wave-uniform)
+        const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(rt ? p.res + (long long)b * Ck * Tpo : p.res), 0, rt ? Ck * Tpo * 4 : 0, 0x00020000);
+        const int vo = k4p_off(tile0, n) * 4;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) rsv[e] = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(rr, vo + e * Tpo * 16, 0, 0));
+        const bool hb = p.bias && !p.ln_part;
+        const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.bias), 0, hb ? p.Mp * 4 : 0, 0x00020000);
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const f32x4 v = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rb, (tile0 + 8 * g + 4 * h) * 4, 0, 0));      // rows 8g + 4h + (0..3) = registers 4g + (0..3)
+#pragma unroll
+            for (int k = 0; k < 4; ++k) kbv[4 * g + k] = v[k];
+        }
+    }
+
+    // EPI: this reduction is followed by the epilogue (false: the first phase of conv_dma_pair_kernel, whose epilogue operands are the second
+    // phase's -- its late loads would be dead code, and the compiler would drop them while the waits still counted them).  ZERO: clear the
+    // accumulators (behind the first DMAs, not in front of them).
+    template <bool EPI = true, bool ZERO = true>
     __device__ __forceinline__ void mainloop() {
         static_assert(G % NB == 0 && NB - 1 <= G, "ring slots must keep their phase across K-steps");
-        const int nk = p.Ci / BK / (p.ksplit > 1 ? p.ksplit : 1);      // this workgroup's K-steps: kc0 .. kc0 + nk - 1
+        constexpr int XL = EPI ? NLATE : 0;
+        const int nk = steps_per_share();      // this workgroup's K-steps: kc0 .. kc0 + nk - 1
         if constexpr (GNF) gnf_request();
-        if constexpr (EARLY) early_loads();
+        if constexpr (EARLY && !LATE) early_loads();
         for (int t = 0; t < NST && t < nk; ++t) issue_tile(kc0 + t, smem + t * STAGE);
+        if constexpr (XL > 0) {
+            // nothing of late_loads() may move in front of the burst or behind the wait: both would make the count of wait_younger too large
+            asm volatile("" ::: "memory");
+            __builtin_amdgcn_sched_barrier(0);
+            late_loads();
+            asm volatile("" ::: "memory");
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        if constexpr (ZERO) {
+            // (written as instructions so that they stay here: as plain constants the compiler materialises them in front of the burst)
+#pragma unroll
+            for (int a = 0; a < NACC; ++a)
+#pragma unroll
+                for (int i = 0; i < TM; ++i)
+#pragma unroll
+                    for (int j = 0; j < TN; ++j)
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) {
+                            float z;
+                            asm volatile("v_mov_b32 %0, 0" : "=v"(z));
+                            acc[a][i][j][r] = z;
+                        }
+        }
         if (p.ln_part) ln_columns();
         if constexpr (GNF) gnf_prepare();
-        wait_younger<NST - 1>((nk - 1 < NST - 1) ? nk - 1 : NST - 1);      // tile 0 landed (this wave's share)
+        wait_younger<NST - 1, XL>((nk - 1 < NST - 1) ? nk - 1 : NST - 1);      // tile 0 landed (this wave's share)
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
         if constexpr (GNF) gnf_rows();
@@ -398,7 +495,7 @@ struct DmaKernel {
         int sc = 0;
         for (int kc = 0; kc < nk; ++kc) {
             const int sn = (sc + 1 == NST) ? 0 : sc + 1;
-            kstep<0>(smem + sc * STAGE, smem + sn * STAGE, kc, nk);
+            kstep<0, EPI>(smem + sc * STAGE, smem + sn * STAGE, kc, nk);
             sc = sn;
             if constexpr (GNF) gnf_advance(kc);
         }
@@ -508,7 +605,9 @@ struct DmaKernel {
     }
 
     // attention's VT layout for the value channels (attention_k4p.hip): [B][head][ceil(To/4)][D][4], element = V[d] at 4
-    // consecutive frames; frames To .. ceil4(To)-1 are written as zeros (they are multiplied by zero probabilities)
+    // consecutive frames; frames To .. ceil4(To)-1 are written as zeros (they are multiplied by zero probabilities).  Plain 4-byte stores:
+    // a wave instruction writes sixteen 16-byte pieces of sixteen lines, and as write-through stores (sc1) these measured 0.9 ms per step
+    // SLOWER than left dirty for the end-of-kernel write-back
     __device__ __forceinline__ void store_vt(int c0, int i, int j, int n) {
         const int T4 = (p.To + 3) & ~3, D = p.vt_D, Cv = p.Cout - p.plain_from;
         if (n >= T4) return;
@@ -600,8 +699,28 @@ struct DmaKernel {
         const bool ok = n < p.To;
         const long long o0 = (long long)b * Ck * Tpo + k4p_off(tile0, n);
         float* ob = p.out + o0;
-        if (ok) {
-            if constexpr (VOC) {
+        if constexpr (!VOC) {
+            // 16-byte write-through entries (k4p.h k4p_tile_entries): the swaps run here, with every lane active; lane half h then
+            // owns row (q, hh = h) of each 8-channel block, pad frames included.  The statistics below read the accumulators as they were.
+            k4p_f32x4 ent[4];
+            k4p_tile_entries(acc[0][i][j], ent);
+            const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(p.out + (long long)b * Ck * Tpo, 0, Ck * Tpo * 4, 0x00020000);
+            const int e0 = k4p_entry_off(tile0 >> 3, h, Tpo, n + p.opad);
+            if (ok) {
+#pragma unroll
+                for (int g = 0; g < 4; ++g) k4p_store16_wt(ro, e0 + g * 2 * Tpo * 16, ent[g]);
+                if (p.opad == 1) {                // one pad frame per side is written with the tensor; wider pads are zeroed by k4p_zero_pads
+                    if (n == 0) {                 // left pad frame
+#pragma unroll
+                        for (int g = 0; g < 4; ++g) k4p_store16(ro, e0 + g * 2 * Tpo * 16 - 16, k4p_f32x4{0.f, 0.f, 0.f, 0.f});
+                    }
+                    if (n == p.To - 1) {          // right pad frame
+#pragma unroll
+                        for (int g = 0; g < 4; ++g) k4p_store16(ro, e0 + g * 2 * Tpo * 16 + 16, k4p_f32x4{0.f, 0.f, 0.f, 0.f});
+                    }
+                }
+            }
+        } else if (ok) {      // the vocoder's store path: its epilogue options, then 8-byte halves of the entries
             if constexpr (BN < 256) {
                 if (p.vlen && n >= voc_len()) {      // ragged batch: this stage's frames beyond the utterance's length are written as zeros
 #pragma unroll
@@ -623,7 +742,6 @@ struct DmaKernel {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) { const float v = acc[0][i][j][r]; acc[0][i][j][r] = (v >= 0.f) ? v : v * p.act_slope; }
             }
-            }      // VOC
 #pragma unroll
             for (int g = 0; g < 4; ++g)
 #pragma unroll
@@ -838,10 +956,11 @@ template <int BM, int BN, int KT, int STRIDE, bool UPS, int BK, int NST, int DIL
 __global__ void __launch_bounds__(256, ((VOC && KT == 2) ? 2 : DmaCfg<BM, BN, KT, STRIDE, UPS, BK, NST, DIL>::OCC)) conv_dma_kernel(const DmaConvArgs p) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     DmaKernel<BM, BN, KT, STRIDE, UPS, BK, NST, DIL, VOC, GNF, GELU, ACT2> k(p, smem);
-    k.setup();
+    k.setup_keep_acc();
     // ragged batch: a tile that lies wholly beyond its utterance's length has nothing to reduce -- the epilogue writes its zeros (what it
     // computes from the untouched accumulators never reaches memory: masked columns are stored as literal zeros)
     if (!k.dead_tile()) k.mainloop();
+    else k.zero_acc();
     k.epilogue();
 }
 
@@ -867,8 +986,9 @@ __global__ void __launch_bounds__(256, (PairCfg<BM, BN, BK3, BK1, NST>::OCC)) co
     K1 k1(pp.a1, smem);
     {
         K3 k3(pp.a3, smem);
-        k3.setup();
-        if (!k3.dead_tile()) k3.mainloop();
+        k3.setup_keep_acc();
+        if (!k3.dead_tile()) k3.template mainloop<false, true>();
+        else k3.zero_acc();
 #pragma unroll
         for (int a = 0; a < K3::NACC; ++a)
 #pragma unroll
@@ -878,15 +998,22 @@ __global__ void __launch_bounds__(256, (PairCfg<BM, BN, BK3, BK1, NST>::OCC)) co
     }
     __syncthreads();                // every wave is done reading the first phase's stages
     k1.setup_keep_acc();
-    if (!k1.dead_tile()) k1.mainloop();
+    if (!k1.dead_tile()) k1.template mainloop<true, false>();
     k1.epilogue();
+}
+
+// the constants of the kernel's block-index decomposition (kernels.h dma_tile_of): divisors nMb, nN, S
+static void dma_set_order(DmaConvArgs& a, int nMb, int nN, int S) {
+    const DmaMagic m0 = dma_magic((unsigned)nMb), m1 = dma_magic((unsigned)nN), m2 = dma_magic((unsigned)S);
+    a.ord_m[0] = m0.m; a.ord_m[1] = m1.m; a.ord_m[2] = m2.m;
+    a.ord_s = m0.s | (m1.s << 8) | (m2.s << 16);
 }
 
 static thread_local char g_dcfg[96] = "";
 const char* conv_dma_last_config() { return g_dcfg; }
 
 template <int BM, int BN, int KT, int STRIDE, bool UPS, int BK, int NST, int DIL = 1, bool VOC = false, bool GNF = false, bool GELU = false, int ACT2 = 0>
-static hipError_t launch_dma_cfg(const DmaConvArgs& a, hipStream_t s) {
+static hipError_t launch_dma_cfg(DmaConvArgs& a, hipStream_t s) {      // (a: the copy launch_conv_dma owns; the order constants are set in it)
     using Cfg = DmaCfg<BM, BN, KT, STRIDE, UPS, BK, NST, DIL>;
     if (GNF != (a.gnf_part != nullptr) || GELU != (a.epi == EPI_GELU) || (ACT2 == 1) != (a.epi == EPI_SWISH) || (ACT2 == 2) != (a.epi == EPI_GLU)) return hipErrorInvalidValue;
     const size_t lds_bytes = Cfg::LDS_BYTES + (GNF ? (BM + 32) * sizeof(float) : 0);      // the fold's row constants and group statistics sit behind the ring
@@ -894,6 +1021,7 @@ static hipError_t launch_dma_cfg(const DmaConvArgs& a, hipStream_t s) {
     const int S = a.ksplit > 1 ? a.ksplit : 1;
     if (S > 1 && (Cfg::TM * Cfg::TN > 2 || VOC || (a.Ci / BK) % S)) return hipErrorInvalidValue;
     dim3 grid((a.Mp / BM) * nN, a.B * S);
+    dma_set_order(a, a.Mp / BM, nN, S);
     auto kern = conv_dma_kernel<BM, BN, KT, STRIDE, UPS, BK, NST, DIL, VOC, GNF, GELU, ACT2>;
     if (lds_bytes > 48 * 1024) {
         static std::atomic<unsigned long long> attr_done{0};
@@ -991,12 +1119,14 @@ static int cluster_split(const DmaConvArgs& a, int bm, int bn, int nk, int nk2, 
 }
 
 template <int BM, int BN, int BK3, int BK1, int NST>
-static hipError_t launch_pair_cfg(const DmaConvArgs& a3, const DmaConvArgs& a1, hipStream_t s) {
+static hipError_t launch_pair_cfg(DmaConvArgs& a3, DmaConvArgs& a1, hipStream_t s) {      // (the copies launch_conv_dma_pair owns)
     using Cfg = PairCfg<BM, BN, BK3, BK1, NST>;
     const int nN = (a1.To + BN - 1) / BN;
     const int S = a1.ksplit > 1 ? a1.ksplit : 1;
     if (S > 1 && (Cfg::C1::TM * Cfg::C1::TN != 1 || a3.ksplit != a1.ksplit || (a3.Ci / BK3) % S || (a1.Ci / BK1) % S)) return hipErrorInvalidValue;
     dim3 grid((a1.Mp / BM) * nN, a1.B * S);
+    dma_set_order(a3, a1.Mp / BM, nN, S);
+    dma_set_order(a1, a1.Mp / BM, nN, S);
     auto kern = conv_dma_pair_kernel<BM, BN, BK3, BK1, NST>;
     if (Cfg::LDS_BYTES > 48 * 1024) {
         static std::atomic<unsigned long long> attr_done{0};
@@ -1209,3 +1339,22 @@ hipError_t launch_conv_dma(const DmaConvArgs& a_, int cfg, hipStream_t s) {
 }
 
 }  // namespace lds
+
+// Test entries (include/lds_test.h), host only: the launchers' division constants and the kernel's block-index decomposition
+extern "C" int lds_test_dma_magic_div(uint32_t d, uint32_t n_count, uint32_t* out) {
+    if (d < 1 || d >= (1u << 31) || n_count > (1u << 31) || !out) return (int)hipErrorInvalidValue;
+    const lds::DmaMagic m = lds::dma_magic(d);
+    for (uint32_t n = 0; n < n_count; ++n) out[n] = lds::dma_magic_div(n, m.m, m.s);
+    return 0;
+}
+extern "C" int lds_test_dma_tile_order(int nMb, int nN, int B, int S, int32_t* out) {
+    if (nMb < 1 || nN < 1 || B < 1 || S < 1 || !out || (long long)nMb * nN * B * S >= (1ll << 31)) return (int)hipErrorInvalidValue;
+    lds::DmaConvArgs a{};
+    lds::dma_set_order(a, nMb, nN, S);
+    const int total = nMb * nN * B * S;
+    for (int id = 0; id < total; ++id) {
+        const lds::DmaTile t = lds::dma_tile_of(id, total, nMb, nN, S, a.ord_m, a.ord_s);
+        out[4 * id] = t.mb; out[4 * id + 1] = t.nb; out[4 * id + 2] = t.b; out[4 * id + 3] = t.ksp;
+    }
+    return 0;
+}

@@ -158,7 +158,32 @@ struct DmaConvArgs {
     int ksplit;
     float* kpart; unsigned* kcount;
     long long kpart_cap; int kcount_cap;      // capacities (floats / counters)
+    // conv_dma only, filled by its launchers (dma_set_order): the three divisors of the block-index decomposition (M-blocks, frame blocks,
+    // cluster shares) as multiplier / shift pairs, so that the kernel finds its tile on the scalar unit alone (dma_magic below)
+    unsigned ord_m[3], ord_s;                 // ord_s = the three shifts, 8 bits each
 };
+// n / d for 0 <= n < 2^31, 1 <= d < 2^31 as (mulhi(2 n, m) >> s):  s = ceil(log2 d), m = floor(2^(31 + s) / d) + 1 < 2^32, and
+// m d - 2^(31 + s) is in (0, d] <= 2^s, which makes the quotient exact over the whole range (Granlund & Montgomery 1994, theorem 4.2)
+struct DmaMagic { unsigned m, s; };
+inline DmaMagic dma_magic(unsigned d) {
+    unsigned s = 0;
+    while ((1ull << s) < d) ++s;
+    return DmaMagic{(unsigned)((1ull << (31 + s)) / d + 1), s};
+}
+__host__ __device__ inline unsigned dma_magic_div(unsigned n, unsigned m, unsigned s) {
+    return (unsigned)(((unsigned long long)(n << 1) * m) >> 32) >> s;
+}
+// The tile of workgroup `id` of a grid of `total` = nMb * nN * B * S workgroups (conv_dma.hip, XCD-aware order): the same arithmetic on
+// the host, for the tests (lds_test_dma_tile_order)
+struct DmaTile { int mb, nb, b, ksp; };
+inline DmaTile dma_tile_of(int id, int total, int nMb, int nN, int S, const unsigned* ord_m, unsigned ord_s) {
+    const int xcd = id & 7, slot = id >> 3, per = total >> 3, rem = total & 7;
+    const unsigned L = (unsigned)(xcd * per + (xcd < rem ? xcd : rem) + slot);
+    const unsigned tb = dma_magic_div(L, ord_m[0], ord_s & 255);
+    const unsigned by = dma_magic_div(tb, ord_m[1], (ord_s >> 8) & 255);
+    const unsigned b = dma_magic_div(by, ord_m[2], (ord_s >> 16) & 255);
+    return DmaTile{(int)(L - tb * nMb), (int)(tb - by * nN), (int)b, (int)(by - b * S)};
+}
 // cfg: 0 = auto, else BM*1000000 + BN*1000 + BK*10 + NST
 hipError_t launch_conv_dma(const DmaConvArgs& a, int cfg, hipStream_t s);
 // Resnet tail in one launch (reference resnet.py:636-641): out = conv2_k3(h) + shortcut_1x1([x ; skip]) + bias.  `a3` carries the k 3

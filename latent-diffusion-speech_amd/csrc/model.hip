@@ -3422,6 +3422,26 @@ struct TmpDev {
     float* f(size_t n) { void* d = nullptr; if (hipMalloc(&d, n * sizeof(float) + 65536) != hipSuccess) return nullptr; p.push_back(d); return (float*)d; }
 };
 
+// lds_test_tap_k4p (include/lds_test.h): the raw K4P output of the next K4P test entry, pad frames included.  An armed tap makes the entry
+// fill that buffer with NaN before its launch (tap_fill) and copy it out, as it is, before converting it (tap_take).
+static thread_local float* g_tap_dst = nullptr;
+static thread_local size_t g_tap_floats = 0;
+extern "C" int lds_test_tap_k4p(float* dst, size_t floats) {
+    if ((dst != nullptr) != (floats > 0)) return fail(LDS_EINVAL, "bad argument");
+    g_tap_dst = dst; g_tap_floats = floats;
+    return LDS_OK;
+}
+static hipError_t tap_fill(float* k, size_t floats, hipStream_t st) {
+    return g_tap_dst ? hipMemsetAsync(k, 0xff, floats * sizeof(float), st) : hipSuccess;
+}
+static hipError_t tap_take(const float* k, size_t floats, hipStream_t st) {
+    if (!g_tap_dst) return hipSuccess;
+    float* dst = g_tap_dst;
+    g_tap_dst = nullptr;
+    if (floats != g_tap_floats) return hipErrorInvalidValue;      // the caller sized the buffer for another tensor
+    return hipMemcpyAsync(dst, k, floats * sizeof(float), hipMemcpyDeviceToDevice, st);
+}
+
 // bf3 = 1: the same operator through the split-bf16 kernel (K8B3 tensors, conv_bf3.hip) with `nprod` bf16 products per fp32 product
 static int dconv_test_impl(const lds_dconv_test* a, float* out, float* lnpart, int B, int iters, float* ms_out, void* stream, int bf3 = 0, int nprod = 0, int fmt = 0,
                            const int* alt_cfgs = nullptr, int n_alt = 0) {
@@ -3468,6 +3488,8 @@ static int dconv_test_impl(const lds_dconv_test* a, float* out, float* lnpart, i
         if (a->v_split > 1) o.vt_D = a->v_split;      // value third in attention's VT layout with this head dim
     }
     o.lnpart_out = (float2*)lnpart;
+    const bool tap = !bf3 && !a->plain_out;
+    if (tap) HIP_TRY(tap_fill(kout, (size_t)B * Ck * (To + 2), st));
     auto run = [&]() { return bf3 ? run_dconv_bf3(W, k1, a->C1, k2, a->C2, T, o, kout, B, st, nprod, fmt) : run_dconv(W, k1, a->C1, k2, a->C2, T, o, kout, B, st); };
     int r = run();
     if (r == LDS_OK && iters > 0 && ms_out) {
@@ -3488,6 +3510,7 @@ static int dconv_test_impl(const lds_dconv_test* a, float* out, float* lnpart, i
         (void)hipEventDestroy(e1);
     }
     auto from_out = [&](const float* src, float* dst, int C, int Tl) { return qk_f32 ? launch_from_k4p(src, dst, B, C, Tl, st) : from_act(src, dst, C, Tl); };
+    if (r == LDS_OK && tap) HIP_TRY(tap_take(kout, (size_t)B * Ck * (To + 2), st));
     if (r == LDS_OK && !a->plain_out) {
         if (a->v_split > 1) {
             // out = [B][Ck][To] plain q;k, then the raw VT buffer [B][(Cout-Ck)/D][ceil4(To)/4][D][4]
@@ -3782,12 +3805,14 @@ extern "C" int lds_test_ln_chain_k4p(const float* x, const float* w1, const floa
     float* part = tmp.f((size_t)B * (C / 32) * T * 2);
     if (!kx || !km || !ko || !part) return fail(LDS_ENOMEM, "alloc");
     HIP_TRY(launch_to_k4p(x, kx, B, C, T, C, 0, st));
+    HIP_TRY(tap_fill(ko, (size_t)B * Co * (T + 2), st));
     DOpt o1;
     o1.lnpart_out = (float2*)part;
     LDS_TRY(run_dconv(W1, kx, C, nullptr, 0, T, o1, km, B, st));
     DOpt o2;
     o2.ln_part = (const float2*)part; o2.ln_np = C / 32; o2.ln_eps = eps; o2.ln_c1 = c1; o2.ln_c2 = c2;
     LDS_TRY(run_dconv(W2, km, C, nullptr, 0, T, o2, ko, B, st));
+    HIP_TRY(tap_take(ko, (size_t)B * Co * (T + 2), st));
     HIP_TRY(launch_from_k4p(km, mid, B, C, T, st));
     HIP_TRY(launch_from_k4p(ko, out, B, Co, T, st));
     HIP_TRY(hipStreamSynchronize(st));
@@ -3865,8 +3890,10 @@ static int attention_test_impl(const float* qkv, float* out, int B, int C, int T
     }
     HIP_TRY(launch_to_k4p(qkp, kqk, B, 2 * C, T, 2 * C, 0, st));
     HIP_TRY(launch_plain_to_vt(vpl, vt, B, C, T, C / heads, st));
+    HIP_TRY(tap_fill(ko, (size_t)B * C * (T + 2), st));
     if (f16math) HIP_TRY(launch_attention_k4p_f16math(kqk, vt, ko, B, C, T, heads, st, tile_batch));
     else HIP_TRY(launch_attention_k4p(kqk, vt, ko, B, C, T, heads, st, tile_batch));
+    HIP_TRY(tap_take(ko, (size_t)B * C * (T + 2), st));
     HIP_TRY(launch_from_k4p(ko, out, B, C, T, st));
     HIP_TRY(hipStreamSynchronize(st));
     return LDS_OK;
@@ -4083,6 +4110,7 @@ extern "C" int lds_test_dconv_pair(const float* h, const float* x1, const float*
     if (rc == 1) rc = fail(LDS_EINVAL, "dconv pair: no fused variant for Cm %d C1 %d C2 %d Co %d T %d (fmt %d, tile_batch %d)", Cm, C1, C2, Co, T, fmt, tile_batch);
     if (rc == LDS_OK) {
         if (cfg_out && cfg_cap) snprintf(cfg_out, cfg_cap, "%s", f32 ? conv_dma_last_config() : conv_bf3_last_config());
+        if (f32) HIP_TRY(tap_take(ko, act.floats(Co, T), st));
         HIP_TRY(act.from(ko, out, Co, T));
     }
     HIP_TRY(hipStreamSynchronize(st));
@@ -4155,6 +4183,7 @@ extern "C" int lds_test_dconv_ex(const lds_dconv_ex_test* a, float* out, float* 
     }
     if (rc == LDS_OK) {
         if (cfg_out && cfg_cap) snprintf(cfg_out, cfg_cap, "%s", f32 ? conv_dma_last_config() : conv_bf3_last_config());
+        if (f32) HIP_TRY(tap_take(ko, act.floats(a->Co, To), st));
         HIP_TRY(act.from(ko, out, a->Co, To));
     }
     HIP_TRY(hipStreamSynchronize(st));

@@ -193,6 +193,9 @@ lds_test_conv_down_ragged        i:pppiiiiiifppippzp
 lds_test_lm_beam_step            i:piiiiiifiippppppppppppppppp
 lds_test_dconv_pair              i:pppppppiiiiiipiiipppzp
 lds_test_dconv_ex                i:pppipzp
+lds_test_dma_magic_div           i:uup
+lds_test_dma_tile_order          i:iiiip
+lds_test_tap_k4p                 i:pz
 lds_test_voc_ups                 i:pppiiiiiipppppzp
 lds_test_w2v_conv0               i:ppppppfpiiqp
 lds_test_w2v_ln_act              i:ppppfppiiip

@@ -15,7 +15,12 @@ import sys
 
 def short(name):
     m = re.match(r"(?:void )?lds::(\w+?)(?:_kernel)?(<[^>]*>)?\(", name)
-    return (m.group(1) + (m.group(2) or "")) if m else name[:60]
+    if not m:
+        return name[:60]
+    s = m.group(1) + (m.group(2) or "")
+    # conv_dma's two youngest template arguments (GELU, ACT2) at their defaults are left out: the UNet's kernels keep the ten-argument names
+    # of the earlier summaries, which is the form bench.py looks kernels up by
+    return re.sub(r"^(conv_dma<(?:[^,>]+, ){9}[^,>]+), false, 0>$", r"\1>", s)
 
 
 def main():
