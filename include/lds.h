@@ -414,6 +414,30 @@ int lds_lm_workspace_bytes_opts(const lds_lm* lm, int B, int L, int max_length, 
 int lds_lm_generate_opts(lds_lm* lm, const float* enc, const int32_t* enc_len, int B, int L, int max_length, const lds_lm_decode_opts* opts,
                          const float* uniforms, int64_t* tokens, float* logits_out, int* n_tokens_host, void* ws, size_t ws_bytes, void* stream);
 
+/* Teacher-forced scoring: the log-probability, under the LM, of given semantic tokens at every position, in one causal pass over all
+ * B * T decoder rows instead of T cached decode steps.  The logits at position t are those of the prefix semantic[:, :t + 1] -- what
+ * lds_lm_generate computes at step t, bit for bit (the rows go through the decode's own linear kernels, and the causal self-attention
+ * restates the cached step's arithmetic per row and head).
+ *   enc dev [B][L][hidden] from lds_lm_encode, enc_len dev int32 [B] or NULL as there (the cross-attention's padding mask).
+ *   semantic dev int64 [B][T], BOS first; sem_len dev int32 [B] (real tokens per right-padded row) or NULL = T everywhere;
+ *   labels dev int64 [B][T] or NULL = semantic.  Position t of row b (0 <= t <= T - 2) is counted when t + 1 < sem_len[b] and
+ *   y = labels[b][t + 1] != -100 (HF's shift and ignore index, ForCausalLMLoss); a label outside [0, sem_vocab) is ignored like -100.
+ *   logprobs dev [B][T-1]:  logit_y - logsumexp_v logit_v  (max and sum of exp in a fixed order, the log in double, rounded once); 0 where not counted
+ *   ranks dev int32 [B][T-1]:  #{v : logit_v > logit_y} + #{v < y : logit_v == logit_y}  (ties to the lowest index); -1 where not counted
+ *   loss dev [1] = -(sum of the counted logprobs) / n_counted (HF's mean reduction; NaN when nothing is counted), n_counted dev int32 [1]:
+ *     a fixed-order two-stage sum in double, no atomics -- every output is bit-identical on repeat.
+ *   logits_out dev [B][T][sem_vocab] or NULL.  Without it the head runs over chunks of 256 rows through one reused buffer, so the
+ *     workspace does not grow with B * T * sem_vocab.
+ * Token ids are clamped to [0, sem_vocab) on the way into the embedding (callers validate the ids inside the lengths; lds.native's
+ * wrapper does).  Ids, labels and logits rows at and beyond sem_len[b] have no effect on any counted output.  The contents of the
+ * workspace on entry do not matter.  Nothing synchronises and nothing is copied from the host.  Limits (LDS_EINVAL before anything is
+ * enqueued): 2 <= T <= min(max_position_embeddings, 16000), L as for lds_lm_generate_opts, B * T and B * L <= 524280.  A workspace
+ * smaller than lds_lm_score_workspace_bytes(B, L, T) gives LDS_ENOMEM with the size needed in the message. */
+int lds_lm_score_workspace_bytes(const lds_lm* lm, int B, int L, int T, size_t* out);
+int lds_lm_score(lds_lm* lm, const float* enc, const int32_t* enc_len, int B, int L, const int64_t* semantic, const int32_t* sem_len,
+                 const int64_t* labels, int T, float* logprobs, int32_t* ranks, float* loss, int32_t* n_counted, float* logits_out, void* ws,
+                 size_t ws_bytes, void* stream);
+
 /* ---- k-means semantic tokenizer: units -> tokens and the codebook fit (reference cluster/__init__.py:13-23 get_cluster_result /
  *      get_cluster_center_result, cluster/kmeans.py:10-50 _kpp, :108-131 euc_sim / max_sim, :184-198 the Lloyd step; called from
  *      17_preprocess_train_cluster.py and 19_preprocess_token.py) -------------------------------------------------------------------

@@ -29,6 +29,9 @@ def parse_args(argv=None):
     ap.add_argument("--max_length", type=int, default=1024)
     ap.add_argument("--num_beams", type=int, default=1, help="> 1: greedy beam search over the semantic tokens instead of top-k sampling (2 .. 8)")
     ap.add_argument("--no_repeat_ngram_size", type=int, default=0, help="n >= 1: no n-gram of semantic tokens repeats (HF NoRepeatNGramLogitsProcessor)")
+    ap.add_argument("--candidates", type=int, default=1,
+                    help="N > 1: sample N token sequences in one batch, score them with the LM (Roformer.score) and keep the one with the highest mean "
+                         "log-prob per generated token (sampling only: num_beams 1)")
     ap.add_argument("-o", "--output", default="output.npy")
     ap.add_argument("-id", "--spk_id", type=int, default=1)
     ap.add_argument("-s", "--speedup", type=int, default=10)
@@ -107,6 +110,36 @@ def text2semantic(lm, phones, tones, spk_id=1, max_length=1024, num_beams=1, no_
         raise ValueError("rows of a batch ended at different lengths (EOS / PAD ids in the result): use text2semantic_rows, which cuts every "
                          "row at its own EOS, and synthesize_ragged")
     return tok[:, 1:]
+
+
+def pick_candidate(lm, phones, tones, tok, spk_id=1):
+    """Rank N sampled sequences of ONE utterance with one Roformer.score call.  phones, tones [1,L]; tok [N,n] as generate returns it (BOS, the
+    tokens, then EOS and PAD in rows that finished early: a row counts up to and including its EOS).  Returns (index of the row with the highest
+    mean log-prob per generated token, those means [N], the LMScore)."""
+    N, n = tok.shape
+    stop = tok[:, 1:] == lm.semantic_eos_token_id
+    length = torch.where(stop.any(1), stop.int().argmax(1) + 2, torch.full_like(tok[:, 0], n))
+    mask = (torch.arange(n, device=tok.device)[None] < length[:, None]).to(torch.int64)
+    ph, tn = phones.expand(N, -1).contiguous(), tones.expand(N, -1).contiguous()
+    r = lm.score(ph, tn, tok, attention_mask=mask, spk_id=torch.ones_like(ph) * spk_id)
+    mean_lp = r.seq_logprob / r.ranks.ge(0).sum(1)
+    return int(mean_lp.argmax()), mean_lp, r
+
+
+def text2semantic_candidates(lm, phones, tones, spk_id=1, max_length=1024, candidates=2, no_repeat_ngram_size=0):
+    """text2semantic for one utterance with N sampled candidates decoded as one batch; the best one under the LM (pick_candidate) comes back as
+    [1, n]: BOS stripped, cut before its EOS"""
+    if phones.shape[0] != 1:
+        raise ValueError("candidates are drawn for one utterance at a time (phones [1, L])")
+    ph, tn = phones.expand(candidates, -1).contiguous(), tones.expand(candidates, -1).contiguous()
+    tok = lm.generate(ph, tn, attention_mask=None, use_cache=None, max_length=max_length, do_sample=True, temperature=1.0, top_k=5, top_p=1.0,
+                      repetition_penalty=1.0, num_beams=1, no_repeat_ngram_size=no_repeat_ngram_size, early_stopping=True, spk_id=torch.ones_like(ph) * spk_id,
+                      end_gate_threshold=None)
+    best, mean_lp, _ = pick_candidate(lm, phones, tones, tok, spk_id)
+    row = tok[best, 1:]
+    stop = (row >= lm.semantic_eos_token_id).nonzero()
+    print(f"candidates: mean log-prob per token {[round(float(v), 4) for v in mean_lp]}, kept {best}")
+    return row[None, : int(stop[0]) if stop.numel() else row.shape[0]]
 
 
 def text2semantic_rows(lm, phones, tones, spk_id=1, max_length=1024, phone_lengths=None, num_beams=1, no_repeat_ngram_size=0):
@@ -311,7 +344,12 @@ def main(argv=None):
         if lm is None:
             raise SystemExit("--phones needs --language_model (or --synthetic)")
         pt = torch.from_numpy(np.load(a.phones).astype(np.int64)).to(dev)
-        tokens = text2semantic(lm, pt[0:1], pt[1:2], a.spk_id, a.max_length, a.num_beams, a.no_repeat_ngram_size)
+        if a.candidates < 1 or (a.candidates > 1 and a.num_beams != 1):
+            raise SystemExit("--candidates needs N >= 1 and, for N > 1, sampling (--num_beams 1)")
+        if a.candidates > 1:
+            tokens = text2semantic_candidates(lm, pt[0:1], pt[1:2], a.spk_id, a.max_length, a.candidates, a.no_repeat_ngram_size)
+        else:
+            tokens = text2semantic(lm, pt[0:1], pt[1:2], a.spk_id, a.max_length, a.num_beams, a.no_repeat_ngram_size)
         tokens = tokens.clamp(max=codebook.shape[0] - 1)      # pad ids of finished rows (batch > 1) have no codebook row
     _, _, wav = synthesize(svc, codebook, tokens, a.spk_id, a.speedup, a.method, a.scale_factor)
     wav = wav[0, 0].cpu().numpy()

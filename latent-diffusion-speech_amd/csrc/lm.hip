@@ -298,7 +298,10 @@ __global__ void __launch_bounds__(256) lm_kv_pack_kernel(const float* __restrict
 // BEAM (lm_attn_beam_kernel, beam-search decode, Lq = 1): cache rows are beam rows.  src != null (self-attention): key p < Lk - 1 of row n
 // lives in cache row src[n * src_cap + p] (the beam's ancestry, see lm_beam_step_kernel), the last key in row n itself.  group: rows per
 // batch item of the cross-attention's keys / values and klen (b = n / group).  The source rows ride along the scores in LDS.
-template <bool BEAM>
+// CAUSAL (lm_attn_causal_kernel, the teacher-forced prefill of lds_lm_score, Lq = Lk_all = T, klen null): query l sees keys 0 .. l of the cache
+// that the projection of all T rows has just filled -- the Lk of the cached decode at step l, hence its key striding over the waves, its
+// block boundaries and its merge order: the row's arithmetic is the decode step's, bit for bit.
+template <bool BEAM, bool CAUSAL = false>
 static __device__ __forceinline__ void lm_attn_body(const float* __restrict__ q, int ldq, const float* __restrict__ kc, const float* __restrict__ vc, int cap,
                                                     int Lq, int Lk_all, const int* __restrict__ klen, int H, int heads, float* __restrict__ out,
                                                     const int* __restrict__ src, int src_cap, int group) {
@@ -313,7 +316,7 @@ static __device__ __forceinline__ void lm_attn_body(const float* __restrict__ q,
     // padding mask (reference roformer.py:209-236: attention_mask on the encoder's keys, encoder_attention_mask on the cross-attention's):
     // right-padded rows, so the mask of batch row b is "keys [0, klen[b])"; masked keys get probability exactly 0 as with HF's -inf bias
     const int kl = klen ? klen[b] : Lk_all;
-    const int Lk = (kl < Lk_all) ? (kl < 1 ? 1 : kl) : Lk_all;
+    const int Lk = CAUSAL ? (int)(n - (long long)b * Lq) + 1 : (kl < Lk_all) ? (kl < 1 ? 1 : kl) : Lk_all;
     float* mrg = sc + Lkp;
     float qr[32];
 #pragma unroll
@@ -402,6 +405,80 @@ __global__ void __launch_bounds__(256) lm_attn_beam_kernel(const float* __restri
                                                            int Lq, int Lk_all, const int* __restrict__ klen, int H, int heads, float* __restrict__ out,
                                                            const int* __restrict__ src, int src_cap, int group) {
     lm_attn_body<true>(q, ldq, kc, vc, cap, Lq, Lk_all, klen, H, heads, out, src, src_cap, group);
+}
+__global__ void __launch_bounds__(256) lm_attn_causal_kernel(const float* __restrict__ q, int ldq, const float* __restrict__ kc, const float* __restrict__ vc, int cap,
+                                                             int T, int H, int heads, float* __restrict__ out) {
+    lm_attn_body<false, true>(q, ldq, kc, vc, cap, T, T, nullptr, H, heads, out, nullptr, 0, 1);
+}
+
+// ---- teacher-forced scoring (lds_lm_score): the statistics of one logits row, one workgroup per row of a chunk [rows][V] whose first row is
+//      row n0 = b * T + t of the batch.  Position t is counted when t + 1 < len_b and y = labels[b][t + 1] is a vocabulary id (HF's shift,
+//      ForCausalLMLoss; -100 is the ignore index and every other id outside [0, V) is ignored with it):
+//        lp   = logit_y - logsumexp_v logit_v        max and sum of exp in a fixed order (256 strided chains, DPP wave order, waves 0 .. 3),
+//                                                     the final log in double, rounded once
+//        rank = #{v : logit_v > logit_y} + #{v < y : logit_v == logit_y}      (the library's lowest-index tie rule)
+//      Positions that are not counted get lp = 0, rank = -1; rows t = T - 1 have no label and write nothing. ----
+__global__ void __launch_bounds__(256) lm_score_rows_kernel(const float* __restrict__ logits, long long n0, int V, int T, const int64_t* __restrict__ labels,
+                                                            const int32_t* __restrict__ sem_len, float* __restrict__ lp, int32_t* __restrict__ rank) {
+    __shared__ float red[4];
+    const long long n = n0 + blockIdx.x;
+    const int tid = threadIdx.x, b = (int)(n / T), t = (int)(n - (long long)b * T);
+    if (t >= T - 1) return;
+    int len = sem_len ? sem_len[b] : T;
+    len = len > T ? T : len;
+    const long long y = (t + 1 < len) ? labels[(long long)b * T + t + 1] : -100;
+    const long long o = (long long)b * (T - 1) + t;
+    if (y < 0 || y >= V) {      // (uniform over the workgroup)
+        if (tid == 0) { lp[o] = 0.f; rank[o] = -1; }
+        return;
+    }
+    const float* lg = logits + (long long)blockIdx.x * V;
+    const float ly = lg[y];
+    float m = -INFINITY, cnt = 0.f;      // the count stays below V <= 8192: exact in fp32 in any order
+    for (int c = tid; c < V; c += 256) {
+        const float v = lg[c];
+        m = fmaxf(m, v);
+        cnt += (v > ly || (v == ly && c < y)) ? 1.f : 0.f;
+    }
+    m = wave_max(m);
+    if ((tid & 63) == 0) red[tid >> 6] = m;
+    __syncthreads();
+    m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    float s = 0.f;
+    for (int c = tid; c < V; c += 256) s += expf(lg[c] - m);
+    s = block_sum256(s, red);
+    cnt = block_sum256(cnt, red);
+    if (tid == 0) {
+        lp[o] = (float)((double)ly - ((double)m + log((double)s)));
+        rank[o] = (int)cnt;
+    }
+}
+// loss = -(sum of the counted lp) / n_counted over the whole batch (HF's mean reduction; 0 / 0 = NaN when nothing is counted), as a fixed-order
+// two-stage sum in double without atomics: one workgroup per batch row (256 strided chains, then a fixed tree), then one thread over the rows
+__global__ void __launch_bounds__(256) lm_score_rowsum_kernel(const float* __restrict__ lp, const int32_t* __restrict__ rank, int T1, double* __restrict__ psum,
+                                                              int32_t* __restrict__ pcnt) {
+    __shared__ double sh[256];
+    __shared__ int shc[256];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    double s = 0.0;
+    int c = 0;
+    for (int t = tid; t < T1; t += 256)
+        if (rank[(long long)b * T1 + t] >= 0) { s += (double)lp[(long long)b * T1 + t]; ++c; }
+    sh[tid] = s; shc[tid] = c;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if (tid < w) { sh[tid] += sh[tid + w]; shc[tid] += shc[tid + w]; }
+        __syncthreads();
+    }
+    if (tid == 0) { psum[b] = sh[0]; pcnt[b] = shc[0]; }
+}
+__global__ void lm_score_loss_kernel(const double* __restrict__ psum, const int32_t* __restrict__ pcnt, int B, float* __restrict__ loss, int32_t* __restrict__ n_counted) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    double s = 0.0;
+    int n = 0;
+    for (int b = 0; b < B; ++b) { s += psum[b]; n += pcnt[b]; }
+    *loss = (float)(-s / (double)n);
+    *n_counted = n;
 }
 
 // ---- next-token choice per sequence (HF GenerationMixin._sample with RepetitionPenalty -> Temperature -> TopK -> TopP, then
@@ -1115,6 +1192,12 @@ hipError_t lm_attention(const float* q, int ldq, const float* kc, const float* v
     hipLaunchKernelGGL(lm_attn_kernel, dim3(total), dim3(256), lds, st, q, ldq, kc, vc, cap, Lq, Lk, klen, c.hidden, c.heads, out);
     return hipGetLastError();
 }
+// the self-attention of the teacher-forced prefill (lm_attn_causal_kernel): T queries per item over the T keys just appended
+hipError_t lm_attention_causal(const float* q, int ldq, const float* kc, const float* vc, int cap, int B, int T, const lds_lm_cfg& c, float* out, hipStream_t st) {
+    const size_t lds = (size_t)(((T + 63) & ~63) + 4 * 34) * sizeof(float);
+    hipLaunchKernelGGL(lm_attn_causal_kernel, dim3((unsigned)(B * T * c.heads)), dim3(256), lds, st, q, ldq, kc, vc, cap, T, c.hidden, c.heads, out);
+    return hipGetLastError();
+}
 // beam rows of a decode step (lm_attn_beam_kernel): src = ancestry table of the self-attention (null for the cross-attention), group = beams
 struct LmBeamAttn { const int* src; int K; };
 hipError_t lm_attention_beam(const float* q, int ldq, const float* kc, const float* vc, int cap, int B, int Lq, int Lk, const int* klen, const lds_lm_cfg& c,
@@ -1148,8 +1231,9 @@ hipError_t lm_dln(const LmLinear& W, const LmRows& X, int ldx, const LmRows* R, 
 // The three row buffers of the workspace rotate: input -> a (attention block) -> c (cross-attention block) -> output in the input's buffer.
 // self_klen / cross_klen: per-batch-row key counts of the padding mask (device int32 [B]) or null
 // beam (decode steps of a beam search, B = rows = items * beam->K): the self-attention follows the ancestry table, the cross-attention maps row n to item n / K
+// causal (the teacher-forced prefill, pos0 = 0, cap >= L): query l of the self-attention sees keys 0 .. l
 int lm_layer(const lds_lm* lm, const LmStack& s, const LmLayer& Ly, const LmWs& w, LmRows& x, int B, int L, int pos0, float* kc, float* vc, int cap,
-             const float* ckc, const float* cvc, int Lenc, const int* self_klen, const int* cross_klen, hipStream_t st, const LmBeamAttn* beam = nullptr) {
+             const float* ckc, const float* cvc, int Lenc, const int* self_klen, const int* cross_klen, hipStream_t st, const LmBeamAttn* beam = nullptr, bool causal = false) {
     const lds_lm_cfg& c = lm->cfg;
     const int H = c.hidden, N = B * L;
     if (Ly.self.o.M != H || Ly.ff2.M != H || (Ly.has_cross && (Ly.cross.o.M != H || Ly.cross.q.K != H))) return lm_fail(LDS_EINVAL, "layer shapes");
@@ -1160,7 +1244,8 @@ int lm_layer(const lds_lm* lm, const LmStack& s, const LmLayer& Ly, const LmWs& 
         const LmRope rope{s.table, kc, vc, pos0, L, c.heads, cap};      // rotary embedding and cache append in the projection's epilogue
         LM_HIP(lm_dln<4>(Ly.self.qkv, x, H, nullptr, c.eps, w.qkv, 3 * H, N, st, &rope));
     }
-    if (beam) LM_HIP(lm_attention_beam(w.qkv, 3 * H, kc, vc, cap, B, L, pos0 + L, self_klen, c, w.ctx, beam->src, cap, 1, st));
+    if (causal) LM_HIP(lm_attention_causal(w.qkv, 3 * H, kc, vc, cap, B, L, c, w.ctx, st));
+    else if (beam) LM_HIP(lm_attention_beam(w.qkv, 3 * H, kc, vc, cap, B, L, pos0 + L, self_klen, c, w.ctx, beam->src, cap, 1, st));
     else LM_HIP(lm_attention(w.qkv, 3 * H, kc, vc, cap, B, L, pos0 + L, self_klen, c, w.ctx, st));
     const LmRows ctx{w.ctx, nullptr};
     LM_HIP(lm_dln<5>(Ly.self.o, ctx, H, &x, c.eps, free1, H, N, st));               // a = W_o ctx + LN(x)
@@ -1420,6 +1505,90 @@ extern "C" int lds_lm_generate(lds_lm* lm, const float* enc, const int32_t* enc_
                                void* ws, size_t ws_bytes, void* stream) {
     const lds_lm_decode_opts o{do_sample, top_k, top_p, temperature, repetition_penalty, 0, 1, 1};
     return lds_lm_generate_opts(lm, enc, enc_len, B, L, max_length, &o, uniforms, tokens, logits_out, n_tokens_host, ws, ws_bytes, stream);
+}
+
+// ---- teacher-forced scoring: the decoder stack over all B * T rows in one causal pass, then the head over row chunks of kScoreChunk rows
+//      through one reused buffer (or straight into logits_out), each chunk followed by its row statistics.  Every row goes through the
+//      kernels of the decode (lm_linear_dln_kernel's fmaf chain per row does not depend on the row count; lm_attn_causal_kernel restates the
+//      cached step), so the logits equal the decode's bit for bit. ----
+namespace {
+constexpr int kScoreChunk = 256;
+struct LmScoreWs { LmWs w; float *kc, *vc, *ckc, *cvc, *chunk; double* psum; int32_t* pcnt; };
+void lm_score_plan(const lds_lm* lm, LmArena& A, int B, int L, int T, LmScoreWs& s) {
+    const lds_lm_cfg& c = lm->cfg;
+    const size_t N = (size_t)B * T, NL = (size_t)B * L, H = c.hidden;
+    s.w = LmWs{};
+    s.w.x = A.f(N * H); s.w.y = A.f(N * H); s.w.z = A.f(N * H); s.w.qkv = A.f(N * 3 * H); s.w.ctx = A.f(N * H); s.w.ff = A.f(N * c.inter);
+    s.w.kv = A.f(NL * 2 * H);
+    s.kc = A.f(N * H); s.vc = A.f(N * H);              // one layer's self-attention keys / values at a time
+    s.ckc = A.f(NL * H); s.cvc = A.f(NL * H);          // and its cross-attention keys / values
+    s.chunk = A.f((size_t)kScoreChunk * c.sem_vocab);
+    s.psum = (double*)A.f(2 * (size_t)B);
+    s.pcnt = (int32_t*)A.f((size_t)B);
+}
+int lm_score_check(const lds_lm* lm, int B, int L, int T) {
+    if (!lm || B <= 0) return lm_fail(LDS_EINVAL, "bad argument");
+    const lds_lm_cfg& c = lm->cfg;
+    if (T < 2 || T > c.max_pos) return lm_fail(LDS_EINVAL, "sequence length %d out of range (2 .. max_position_embeddings = %d)", T, c.max_pos);
+    if (L < 1 || L > c.max_pos || (size_t)(((L + 63) & ~63) + 4 * 34) * sizeof(float) > 64 * 1024)
+        return lm_fail(LDS_EINVAL, "encoder length %d out of range (1 .. min(max_position_embeddings = %d, 16000))", L, c.max_pos);
+    // the causal self-attention stages one score per key in LDS; the linears take 8 rows per workgroup along grid.y
+    if ((size_t)(((T + 63) & ~63) + 4 * 34) * sizeof(float) > 64 * 1024) return lm_fail(LDS_EINVAL, "sequence length %d too long for scoring (<= 16000)", T);
+    if ((long long)B * T > 8 * 65535LL || (long long)B * L > 8 * 65535LL) return lm_fail(LDS_EINVAL, "batch too large for one scoring call (B * T and B * L <= 524280)");
+    return LDS_OK;
+}
+}  // namespace
+
+extern "C" int lds_lm_score_workspace_bytes(const lds_lm* lm, int B, int L, int T, size_t* out) {
+    if (!out) return lm_fail(LDS_EINVAL, "bad argument");
+    if (int r = lm_score_check(lm, B, L, T)) return r;
+    LmArena A(nullptr, 0);
+    LmScoreWs s;
+    lm_score_plan(lm, A, B, L, T, s);
+    *out = A.used;
+    return LDS_OK;
+}
+
+extern "C" int lds_lm_score(lds_lm* lm, const float* enc, const int32_t* enc_len, int B, int L, const int64_t* semantic, const int32_t* sem_len, const int64_t* labels,
+                            int T, float* logprobs, int32_t* ranks, float* loss, int32_t* n_counted, float* logits_out, void* ws, size_t ws_bytes, void* stream) {
+    if (int r = lm_score_check(lm, B, L, T)) return r;
+    if (!enc || !semantic || !logprobs || !ranks || !loss || !n_counted || !ws) return lm_fail(LDS_EINVAL, "null argument");
+    const lds_lm_cfg& c = lm->cfg;
+    hipStream_t st = (hipStream_t)stream;
+    LmArena A(ws, ws_bytes);
+    LmScoreWs s;
+    lm_score_plan(lm, A, B, L, T, s);
+    if (!A.ok) return lm_fail(LDS_ENOMEM, "LM scoring workspace too small: need %zu bytes", A.used);
+    const int H = c.hidden, V = c.sem_vocab, N = B * T;
+    if (!labels) labels = semantic;
+    // ids are clamped to the vocabulary (lm_embed_kernel); rows at and beyond a sequence's length are computed and never counted
+    hipLaunchKernelGGL(lm_embed_kernel, dim3(N), dim3(256), 0, st, lm->dec.word, lm->dec.type, (const float*)nullptr, lm->dec.ln_emb.g, lm->dec.ln_emb.b, semantic, 1,
+                       (const int64_t*)nullptr, (const int64_t*)nullptr, 0, c.eps, H, V, 1, 1, s.w.x);
+    LM_HIP(hipGetLastError());
+    LmRows cx{s.w.x, nullptr};
+    for (int i = 0; i < c.dec_layers; ++i) {
+        const LmRows er{const_cast<float*>(enc), nullptr};
+        LM_HIP(lm_dln<0>(lm->dec.layers[i].cross.kv, er, H, nullptr, c.eps, s.w.kv, 2 * H, B * L, st));
+        hipLaunchKernelGGL(lm_kv_pack_kernel, dim3((unsigned)(((long long)B * L * H + 255) / 256)), dim3(256), 0, st, s.w.kv, B, L, H, c.heads, s.ckc, s.cvc, L);
+        LM_HIP(hipGetLastError());
+        int r = lm_layer(lm, lm->dec, lm->dec.layers[i], s.w, cx, B, T, 0, s.kc, s.vc, T, s.ckc, s.cvc, L, nullptr, enc_len, st, nullptr, true);
+        if (r != LDS_OK) return r;
+    }
+    // LM head as in the decode: h = GELU(W_t LN(x)) stored un-normalised, logits = W_d LN(h), the latter chunk by chunk
+    LM_HIP(lm_dln<1>(lm->head_t, cx, H, nullptr, c.eps, s.w.ctx, H, N, st));
+    for (int r0 = 0; r0 < N; r0 += kScoreChunk) {
+        const int rows = (N - r0 < kScoreChunk) ? N - r0 : kScoreChunk;
+        const LmRows hrows{s.w.ctx + (size_t)r0 * H, &lm->head_ln};
+        float* lg = logits_out ? logits_out + (size_t)r0 * V : s.chunk;
+        LM_HIP(lm_dln<0>(lm->head_d, hrows, H, nullptr, c.eps, lg, V, rows, st));
+        hipLaunchKernelGGL(lm_score_rows_kernel, dim3(rows), dim3(256), 0, st, (const float*)lg, (long long)r0, V, T, labels, sem_len, logprobs, ranks);
+        LM_HIP(hipGetLastError());
+    }
+    hipLaunchKernelGGL(lm_score_rowsum_kernel, dim3(B), dim3(256), 0, st, (const float*)logprobs, (const int32_t*)ranks, T - 1, s.psum, s.pcnt);
+    LM_HIP(hipGetLastError());
+    hipLaunchKernelGGL(lm_score_loss_kernel, dim3(1), dim3(64), 0, st, (const double*)s.psum, (const int32_t*)s.pcnt, B, loss, n_counted);
+    LM_HIP(hipGetLastError());
+    return LDS_OK;
 }
 
 // Test entry (include/lds_test.h): ONE token choice per row of `logits` [B][V] with the generate loop's own kernels, after a history of n_hist tokens

@@ -131,6 +131,8 @@ lds_lm_encode                    i:pppppppziip
 lds_lm_generate                  i:pppiiiiifffpppppzp
 lds_lm_workspace_bytes_opts      i:piiiip
 lds_lm_generate_opts             i:pppiiippppppzp
+lds_lm_score_workspace_bytes     i:piiip
+lds_lm_score                     i:pppiipppippppppzp
 lds_kmeans_workspace_bytes       i:qiip
 lds_kmeans_prepare               i:piipp
 lds_kmeans_assign                i:pqppiipppzp
@@ -1057,6 +1059,30 @@ class LM(_Handle):
             check(lib().lds_lm_generate_opts(*head, C.byref(o), *tail))
         toks = tokens[:, : n.value].contiguous()
         return toks, (logits[: n.value - 1] if logits is not None else None)
+
+    def score(self, enc, semantic, sem_len=None, labels=None, enc_len=None, return_logits=False):
+        """Teacher-forced scoring (lds_lm_score): enc [B,L,hidden] from `encode`, semantic / labels [B,T] int64 (labels None = semantic),
+        sem_len / enc_len int32 [B] on the device or None.  Returns (logprobs [B,T-1], ranks int32 [B,T-1], loss [], n_counted int32 [],
+        logits [B,T,V] or None), all on the device; nothing synchronises."""
+        import torch
+        B, L, _ = enc.shape
+        if semantic.dim() != 2 or semantic.shape[0] != B:
+            raise ValueError(f"semantic must be [B, T] with B = {B}, got {tuple(semantic.shape)}")
+        T = int(semantic.shape[1])
+        if labels is not None and tuple(labels.shape) != (B, T):
+            raise ValueError(f"labels must have semantic's shape {(B, T)}, got {tuple(labels.shape)}")
+        enc, sem = enc.contiguous(), semantic.contiguous()
+        lab = labels.contiguous() if labels is not None else None
+        ws = self._workspace("lds_lm_score_workspace_bytes", enc.device, B, L, T)
+        lp = torch.empty(B, T - 1, dtype=torch.float32, device=enc.device)
+        ranks = torch.empty(B, T - 1, dtype=torch.int32, device=enc.device)
+        loss = torch.empty((), dtype=torch.float32, device=enc.device)
+        n = torch.empty((), dtype=torch.int32, device=enc.device)
+        logits = torch.empty(B, T, self.cfg["sem_vocab"], dtype=torch.float32, device=enc.device) if return_logits else None
+        check(lib().lds_lm_score(self.h, _dev(enc, torch.float32), _dev_or_null(enc_len, torch.int32), B, L, _dev(sem, torch.int64),
+                                 _dev_or_null(sem_len, torch.int32), _dev_or_null(lab, torch.int64), T, _dev(lp), _dev(ranks), _dev(loss), _dev(n),
+                                 _dev_or_null(logits), _dev(ws), ws.numel(), _stream()))
+        return lp, ranks, loss, n, logits
 
 
 # ---- k-means semantic tokenizer (lds_kmeans_*): thin wrappers; X [N, D] and C [K, D] contiguous fp32 device tensors ----

@@ -3,9 +3,12 @@
 RoFormerForCausalLM (+ cross-attention) through GenerationMixin; here the encoder prefill, the key/value-cached decode loop and the
 token choice run in liblds (csrc/lm.hip).  torch keeps the parameters and draws the sampling uniforms.
 
-Scope: phone mode (the 'text' mode fetches a BERT tokenizer from the hub), inference only (`forward` = teacher-forced training
-path), right-padded batches; greedy decoding, sampling and greedy beam search (num_beams 2 .. 8), each with optional n-gram blocking.
+Scope: phone mode (the 'text' mode fetches a BERT tokenizer from the hub), inference only (`forward` = the gradient-carrying
+teacher-forced training entry), right-padded batches; greedy decoding, sampling and greedy beam search (num_beams 2 .. 8), each with
+optional n-gram blocking; `score`: teacher-forced log-probs, loss and ranks of given tokens in one causal pass (no gradients).
 Not built: beam sampling and the end gate (see `generate`)."""
+from collections import namedtuple
+
 import numpy as np
 import torch
 from torch import nn
@@ -19,6 +22,11 @@ def _get(cfg, key, default=None):
     if isinstance(cfg, dict):
         return cfg.get(key, default)
     return getattr(cfg, key, default)
+
+
+# what `Roformer.score` returns: loss [] (HF's mean over the counted positions), token_logprobs [B,T-1] (0 where not counted), ranks int32
+# [B,T-1] (-1 where not counted), seq_logprob [B], n_tokens int32 [] (counted positions), logits [B,T,V] or None
+LMScore = namedtuple("LMScore", "loss token_logprobs ranks seq_logprob n_tokens logits")
 
 
 def get_model(n_spk, **kwargs):
@@ -101,7 +109,8 @@ class Roformer(ParamTree):
         return self._native
 
     def forward(self, *a, **k):
-        raise NotImplementedError("teacher-forced training forward is out of scope for the MI355X inference build")
+        raise NotImplementedError("teacher-forced training forward (with gradients) is out of scope for the MI355X inference build; "
+                                  "Roformer.score gives the teacher-forced loss, log-probs and ranks without gradients")
 
     @staticmethod
     def _mask_to_lengths(attention_mask):
@@ -157,3 +166,36 @@ class Roformer(ParamTree):
         toks, logits = self.native().generate(enc, max_length, do_sample, top_k, top_p, temperature, repetition_penalty, uniforms, return_logits, enc_len,
                                               num_beams=num_beams, no_repeat_ngram_size=no_repeat_ngram_size, early_stopping=early_stopping)
         return (toks, logits) if return_logits else toks
+
+    @torch.no_grad()
+    def score(self, phone, tone, semantic, attention_mask=None, encoder_attention_mask=None, labels=None, spk_id=None, return_logits=False):
+        """Teacher-forced scoring of `semantic` [B,T] (BOS first, as the reference's loader builds it) under the LM, all positions in one
+        causal pass.  The arguments are those of the reference's `forward` (roformer.py:138-176; `labels` defaults to `semantic` as in
+        dataloader.py:181-182); the logits at position t are those of the PREFIX semantic[:, :t + 1] -- what `generate` computes at step t,
+        bit for bit -- not those of the reference's one-call forward, which is non-causal on transformers 5.x.
+        Position t (0 <= t <= len_b - 2) is counted when labels[b, t + 1] != -100 (HF's shift); ids at and beyond a row's length have no
+        effect on any counted output.  Returns an LMScore."""
+        if semantic.dim() != 2 or semantic.shape[0] != phone.shape[0]:
+            raise ValueError(f"semantic must be [B, T] with B = {phone.shape[0]}, got {tuple(semantic.shape)}")
+        B, T = semantic.shape
+        if T < 2 or T > self.cfg["max_pos"]:
+            raise ValueError(f"semantic needs 2 <= T <= max_position_embeddings = {self.cfg['max_pos']}, got T = {T}")
+        if labels is not None and tuple(labels.shape) != (B, T):
+            raise ValueError(f"labels must have semantic's shape {(B, T)}, got {tuple(labels.shape)}")
+        if attention_mask is not None and tuple(attention_mask.shape) != (B, T):
+            raise ValueError(f"attention_mask must have semantic's shape {(B, T)}, got {tuple(attention_mask.shape)}")
+        enc_len, sem_len = self._mask_to_lengths(encoder_attention_mask), self._mask_to_lengths(attention_mask)
+        if not (phone.is_cuda and tone.is_cuda and semantic.is_cuda):
+            raise RuntimeError("Roformer.score needs tensors on a HIP device (no CPU fallback)")
+        semantic = semantic.to(torch.int64)
+        labels = labels.to(device=semantic.device, dtype=torch.int64) if labels is not None else None
+        # the library clamps ids on the way into the embedding: what it would hide is refused here (ids inside the lengths; labels may be -100)
+        V = self.cfg["sem_vocab"]
+        inside = torch.ones_like(semantic, dtype=torch.bool) if sem_len is None else torch.arange(T, device=semantic.device)[None] < sem_len[:, None]
+        if bool((inside & ((semantic < 0) | (semantic >= V))).any()):
+            raise ValueError(f"semantic ids inside the sequence lengths must lie in [0, {V})")
+        if labels is not None and bool((inside & (labels != -100) & ((labels < 0) | (labels >= V))).any()):
+            raise ValueError(f"labels inside the sequence lengths must be -100 or lie in [0, {V})")
+        enc = self.native().encode(phone, tone, spk_id if self.spk_emb_enabled else None, enc_len)
+        lp, ranks, loss, n, logits = self.native().score(enc, semantic, sem_len, labels, enc_len, return_logits)
+        return LMScore(loss, lp, ranks, lp.double().sum(-1).float(), n, logits)

@@ -8,3 +8,11 @@ def get_language_model(**args):
     else:
         raise ValueError(f" [x] Unknown Model: {model_type}")
     return get_model(args["common"]["n_spk"], **args["text2semantic"])
+
+
+def get_topk_acc(gt_token, logits, k=5):
+    """fraction of positions whose ground-truth token is among the k largest logits (reference text2semantic/utils.py get_topk_acc):
+    gt_token [N] int, logits [N, V]"""
+    import torch
+    topk = torch.topk(logits, k, dim=-1).indices
+    return float((topk == gt_token.to(topk.device)[:, None]).any(-1).float().mean())

@@ -4,8 +4,12 @@
   --tokens N [N ...]   decode lengths; two of them show whether the cost of a step grows with the position
   --lib PATH           time another build of liblds.so (a previous commit: only the plain decode, which it has)
 
-With --num_beams > 1, --greedy, or more than one length the EOS logit is biased far down, so that every sequence runs to the full
-length and the time per step is that of a full decode."""
+  --score              time one teacher-forced scoring call (Roformer.score's library call, encoder states given) over the tokens of a
+                       decode of the same length, next to that decode: the only other way to visit those positions.  Both as the
+                       time between two events on the stream (median of --reps), in the same process; --json FILE keeps the rows.
+
+With --num_beams > 1, --greedy, --score or more than one length the EOS logit is biased far down, so that every sequence runs to the
+full length and the time per step is that of a full decode."""
 import argparse
 import ctypes
 import os
@@ -28,6 +32,9 @@ ap.add_argument("--greedy", action="store_true")
 ap.add_argument("--no_repeat_ngram_size", type=int, default=0)
 ap.add_argument("--tokens", type=int, nargs="*", default=[512])
 ap.add_argument("--lib", default=None)
+ap.add_argument("--score", action="store_true")
+ap.add_argument("--reps", type=int, default=5)
+ap.add_argument("--json", default=None)
 a = ap.parse_args()
 if a.lib:
     native.LIB_PATH = os.path.abspath(a.lib)
@@ -36,7 +43,7 @@ if a.lib:
     native.TEST_EXPORTS = [n for n in native.TEST_EXPORTS if hasattr(have, n)]
 
 lm = infer_tts.synthetic_lm("cuda")
-if a.num_beams > 1 or a.greedy or len(a.tokens) > 1:
+if a.num_beams > 1 or a.greedy or a.score or len(a.tokens) > 1:
     with torch.no_grad():
         lm.semantic_decoder.cls.predictions.bias[lm.semantic_eos_token_id] -= 1.0e4
 mode = f"beam search K {a.num_beams}" if a.num_beams > 1 else "greedy" if a.greedy else "sampled"
@@ -47,6 +54,46 @@ def decode(ph, tn, n):
               num_beams=a.num_beams, no_repeat_ngram_size=a.no_repeat_ngram_size, early_stopping=True, spk_id=torch.ones_like(ph), end_gate_threshold=None)
     return lm.generate(ph, tn, do_sample=a.num_beams == 1 and not a.greedy, **kw)
 
+
+def event_ms(fn, reps):
+    """median over reps of the time between two events around fn() on the current stream, and fn's last result"""
+    out, ts = None, []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        out = fn()
+        e1.record()
+        e1.synchronize()
+        ts.append(e0.elapsed_time(e1))
+    return float(np.median(ts)), out
+
+
+def score_mode():
+    rows = []
+    for B in a.batch:
+        ph = torch.from_numpy((np.arange(B * 64).reshape(B, 64) * 7 % 107 + 1).astype(np.int64)).cuda()
+        tn = torch.from_numpy((np.arange(B * 64).reshape(B, 64) * 5 % 12).astype(np.int64)).cuda()
+        enc = lm.encode(ph, tn, torch.ones_like(ph))
+        for n in a.tokens:
+            decode(ph, tn, 64)
+            dec_ms, tok = event_ms(lambda: decode(ph, tn, n - 1), a.reps)      # n tokens incl. BOS: n - 1 decode steps = the n - 1 scored positions
+            assert tok.shape == (B, n), tok.shape
+            lm.native().score(enc, tok)
+            sc_ms, _ = event_ms(lambda: lm.native().score(enc, tok), a.reps)
+            lg_ms, _ = event_ms(lambda: lm.native().score(enc, tok, return_logits=True), a.reps)
+            rows.append({"B": B, "T": n, "positions": B * (n - 1), "decode_ms": dec_ms, "score_ms": sc_ms, "score_with_logits_ms": lg_ms,
+                         "decode_over_score": dec_ms / sc_ms, "score_us_per_position": sc_ms * 1e3 / (B * (n - 1))})
+            print(rows[-1])
+    if a.json:
+        import json
+        json.dump({"what": "one lds_lm_score call vs the cached decode of the same tokens (greedy, EOS biased down), event time on the stream, "
+                           f"median of {a.reps}", "rows": rows}, open(a.json, "w"), indent=1)
+
+
+if a.score:
+    a.greedy = True
+    score_mode()
+    sys.exit(0)
 
 for B in a.batch:
     ph = torch.from_numpy((np.arange(B * 64).reshape(B, 64) * 7 % 107 + 1).astype(np.int64)).cuda()
