@@ -414,6 +414,29 @@ int lds_lm_workspace_bytes_opts(const lds_lm* lm, int B, int L, int max_length, 
 int lds_lm_generate_opts(lds_lm* lm, const float* enc, const int32_t* enc_len, int B, int L, int max_length, const lds_lm_decode_opts* opts,
                          const float* uniforms, int64_t* tokens, float* logits_out, int* n_tokens_host, void* ws, size_t ws_bytes, void* stream);
 
+/* Prompted decode: every row continues from semantic tokens it is given (reference roformer.py:235-242 calls semantic_decoder.generate, whose
+ * HF GenerationMixin.generate takes the decoder prompt as input_ids=; the reference wrapper's **kwargs drop it).  Arguments as
+ * lds_lm_generate_opts, plus:
+ *   prompt dev int64 [B][P]: row b = BOS, s_1 .. s_{prompt_len[b]-1}, right-padded to P.  Ids are clamped to [0, sem_vocab) on the way in
+ *     (callers validate the ids inside the lengths; lds.native's caller does); ids at and beyond prompt_len[b] are never looked at.
+ *   prompt_len HOST int32 [B] (like `lengths` of the ragged sampler entries: the driver sizes the prefill and the step count from it) or
+ *     NULL = P everywhere.  1 <= prompt_len[b] <= P and prompt_len[b] < max_length: max_length is the TOTAL length, prompt included, as in HF.
+ *   tokens dev int64 [B][max_length]: the prompt, then the generated ids; EOS kept, PAD after it.  *n_tokens_host = the longest row's length.
+ *   Row b's s-th generated token is drawn with uniforms[s][b] and chosen from logits_out[s][b] (both laid out [max_length-1][B] as there; the first
+ *     max_length - min prompt_len steps are used); rows of logits_out at steps past a row's end are unspecified.  The repetition penalty and
+ *     the n-gram ban see the whole history, prompt included (HF hands the full input_ids to the processors).
+ * Each row equals that row run alone (B = 1, its own phones and prompt), tokens and logits bit for bit: a row's position, cache slot, key
+ * count and history are its own.  The prompt's positions but the last go through ONE causal pass that fills the decode's key/value caches
+ * (the arithmetic of the cached steps, as in lds_lm_score), then the decode continues step by step.  With prompt_len 1 everywhere the call
+ * IS lds_lm_generate_opts (same launches; slot 0 gets the model's BOS id).  The contents of the workspace on entry do not matter.
+ * Limits (LDS_EINVAL before anything is enqueued): B <= 64; num_beams 1 (beam search from a prompt is not built: the ancestry tables
+ * would need the prefix replicated per beam); P <= 16000 and B * P <= 524280; max_length <= 16000.  A workspace smaller than
+ * lds_lm_workspace_bytes_prompt(B, L, max_length, P) gives LDS_ENOMEM; with P = 1 that size is lds_lm_workspace_bytes_opts(.., 1, ..)'s. */
+int lds_lm_workspace_bytes_prompt(const lds_lm* lm, int B, int L, int max_length, int P, size_t* out);
+int lds_lm_generate_prompt(lds_lm* lm, const float* enc, const int32_t* enc_len, int B, int L, int max_length, const lds_lm_decode_opts* opts,
+                           const int64_t* prompt, const int32_t* prompt_len, int P, const float* uniforms, int64_t* tokens, float* logits_out,
+                           int* n_tokens_host, void* ws, size_t ws_bytes, void* stream);
+
 /* Teacher-forced scoring: the log-probability, under the LM, of given semantic tokens at every position, in one causal pass over all
  * B * T decoder rows instead of T cached decode steps.  The logits at position t are those of the prefix semantic[:, :t + 1] -- what
  * lds_lm_generate computes at step t, bit for bit (the rows go through the decode's own linear kernels, and the causal self-attention

@@ -5,6 +5,8 @@ The grapheme-to-phoneme front end (text/cleaner.py: pypinyin / jieba / g2p table
 
     python infer_tts.py -dm exp/diffusion/model_300000.pt -cb pretrain/semantic_codebook.pt -t tokens.npy -o out.wav
     python infer_tts.py --synthetic -o /tmp/demo.npy        # seeded random weights, synthetic tokens (no checkpoints exist)
+    python infer_tts.py ... -lm exp/lm/model.pt -p phones.npy --prompt_tokens ref_tokens.npy --prompt_phones ref_phones.npy
+                                                            # continue a voice / prosody prompt: the waveform is the continuation only
 """
 import argparse
 import os
@@ -32,6 +34,16 @@ def parse_args(argv=None):
     ap.add_argument("--candidates", type=int, default=1,
                     help="N > 1: sample N token sequences in one batch, score them with the LM (Roformer.score) and keep the one with the highest mean "
                          "log-prob per generated token (sampling only: num_beams 1)")
+    ap.add_argument("--prompt_tokens", help=".npy int array [Tp] of semantic token ids the LM continues from (BOS is added): a voice / prosody prompt, or "
+                                            "the tail of the previous sentence")
+    ap.add_argument("--prompt_phones", help=".npy int array [2, Lp]: the prompt's own phone and tone ids, put in front of --phones")
+    ap.add_argument("--prompt_audio", help="a clip (.wav PCM16 or .npy at --prompt_sample_rate) whose semantic tokens become the prompt: resampler -> "
+                                           "units encoder -> nearest codebook centre, as tools/extract_tokens.py --from-audio")
+    ap.add_argument("--prompt_sample_rate", type=int, default=16000)
+    ap.add_argument("--prompt_encoder", default="whisper_large_v3", choices=("whisper_large_v3", "hubertsoft", "contentvec768l12", "w2v-bert"))
+    ap.add_argument("--prompt_encoder_checkpoint", default=None)
+    ap.add_argument("--prompt_encoder_layers", type=int, default=None, help="depth of the seeded units encoder that --synthetic uses for --prompt_audio")
+    ap.add_argument("--keep_prompt", action="store_true", help="synthesise the prompt's tokens too (default: the continuation only)")
     ap.add_argument("-o", "--output", default="output.npy")
     ap.add_argument("-id", "--spk_id", type=int, default=1)
     ap.add_argument("-s", "--speedup", type=int, default=10)
@@ -92,76 +104,118 @@ def load_lm(path, dev):
     return lm.eval()
 
 
-def text2semantic(lm, phones, tones, spk_id=1, max_length=1024, num_beams=1, no_repeat_ngram_size=0):
+def with_bos(lm, prompt_tokens, rows=1):
+    """semantic ids [Tp] -> the decoder prompt [rows, 1 + Tp] that Roformer.generate takes (BOS first)"""
+    p = torch.cat([prompt_tokens.new_full((1,), lm.semantic_bos_token_id), prompt_tokens.reshape(-1)])
+    return p[None].expand(rows, -1).contiguous()
+
+
+def tokens_from_audio(a, codebook, dev):
+    """--prompt_audio: the clip's semantic tokens through the functions tools/extract_tokens.py --from-audio uses (everything on the device)"""
+    import types
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    from extract_tokens import units_encoder
+    from extract_units import encoder_batch, load_clip
+    ue = units_encoder(types.SimpleNamespace(encoder=a.prompt_encoder, synthetic_encoder=a.synthetic, checkpoint=a.prompt_encoder_checkpoint,
+                                             layers=a.prompt_encoder_layers, seed=0))
+    audio, slen = encoder_batch([load_clip(a.prompt_audio, a.prompt_sample_rate)], ue.min_samples)
+    model = types.SimpleNamespace(cluster_centers_=codebook.detach().cpu().numpy())
+    tok, lens = ue.encode_tokens_ragged(audio, slen, model, pad_id=-1)
+    return tok[0, : int(lens[0])].to(device=dev, dtype=torch.int64)
+
+
+def text2semantic(lm, phones, tones, spk_id=1, max_length=1024, num_beams=1, no_repeat_ngram_size=0, semantic_prompt=None, keep_prompt=False):
     """22_infer_tts.py:76-104: sample the semantic tokens (top-k 5, temperature 1) and strip BOS / EOS.  phones, tones [B,L] int64.
-    num_beams > 1: greedy beam search instead of sampling; no_repeat_ngram_size n >= 1: no n-gram repeats (either decode)."""
+    num_beams > 1: greedy beam search instead of sampling; no_repeat_ngram_size n >= 1: no n-gram repeats (either decode).
+    semantic_prompt [B,P] (BOS first): the decode continues it; its tokens are stripped with BOS unless keep_prompt."""
     spk = torch.ones_like(phones) * spk_id
+    P = 1 if semantic_prompt is None else semantic_prompt.shape[1]      # ids in front of the generated ones: BOS, or the prompt (BOS first)
+    first = 1 if keep_prompt else P
     tok = lm.generate(phones, tones, attention_mask=None, use_cache=None, max_length=max_length, do_sample=num_beams == 1, temperature=1.0, top_k=5,
                       top_p=1.0, repetition_penalty=1.0, num_beams=num_beams, no_repeat_ngram_size=no_repeat_ngram_size, early_stopping=True, spk_id=spk,
-                      end_gate_threshold=None)
+                      end_gate_threshold=None, **({} if semantic_prompt is None else {"semantic_prompt": semantic_prompt}))
     # reference 22_infer_tts.py:100-103 (`if semantic_token[:, -1] == eos`: written for one utterance; on a batch that line itself raises).
     # The batched counterpart: every row ending with its EOS at the same step is stripped like the single row; rows that all ran to max_length
     # come back whole; rows that ended at DIFFERENT steps (EOS / PAD ids inside the result) cannot be one rectangular tensor.
     eos = lm.semantic_eos_token_id
-    body_has_stop = bool((tok[:, 1:-1] >= eos).any()) if tok.shape[1] > 2 else False
+    body_has_stop = bool((tok[:, P:-1] >= eos).any()) if tok.shape[1] > P + 1 else False
     if not body_has_stop and bool((tok[:, -1] == eos).all()):
-        return tok[:, 1:-1]
+        return tok[:, first:-1]
     if body_has_stop or bool((tok[:, -1] >= eos).any()):
         raise ValueError("rows of a batch ended at different lengths (EOS / PAD ids in the result): use text2semantic_rows, which cuts every "
                          "row at its own EOS, and synthesize_ragged")
-    return tok[:, 1:]
+    return tok[:, first:]
 
 
-def pick_candidate(lm, phones, tones, tok, spk_id=1):
+def pick_candidate(lm, phones, tones, tok, spk_id=1, prompt_len=1):
     """Rank N sampled sequences of ONE utterance with one Roformer.score call.  phones, tones [1,L]; tok [N,n] as generate returns it (BOS, the
     tokens, then EOS and PAD in rows that finished early: a row counts up to and including its EOS).  Returns (index of the row with the highest
-    mean log-prob per generated token, those means [N], the LMScore)."""
+    mean log-prob per generated token, those means [N], the LMScore).  prompt_len > 1: the first prompt_len ids of every row are a given prompt
+    (BOS included); they are labelled -100, so only the continuation is counted."""
     N, n = tok.shape
     stop = tok[:, 1:] == lm.semantic_eos_token_id
     length = torch.where(stop.any(1), stop.int().argmax(1) + 2, torch.full_like(tok[:, 0], n))
     mask = (torch.arange(n, device=tok.device)[None] < length[:, None]).to(torch.int64)
     ph, tn = phones.expand(N, -1).contiguous(), tones.expand(N, -1).contiguous()
-    r = lm.score(ph, tn, tok, attention_mask=mask, spk_id=torch.ones_like(ph) * spk_id)
+    labels = None
+    if prompt_len > 1:
+        labels = tok.clone()
+        labels[:, :prompt_len] = -100
+    r = lm.score(ph, tn, tok, attention_mask=mask, labels=labels, spk_id=torch.ones_like(ph) * spk_id)
     mean_lp = r.seq_logprob / r.ranks.ge(0).sum(1)
     return int(mean_lp.argmax()), mean_lp, r
 
 
-def text2semantic_candidates(lm, phones, tones, spk_id=1, max_length=1024, candidates=2, no_repeat_ngram_size=0):
+def text2semantic_candidates(lm, phones, tones, spk_id=1, max_length=1024, candidates=2, no_repeat_ngram_size=0, semantic_prompt=None, keep_prompt=False):
     """text2semantic for one utterance with N sampled candidates decoded as one batch; the best one under the LM (pick_candidate) comes back as
-    [1, n]: BOS stripped, cut before its EOS"""
+    [1, n]: BOS stripped, cut before its EOS.  semantic_prompt [1,P] (BOS first): every candidate continues it, the ranking counts the
+    continuation only, and the prompt is stripped with BOS unless keep_prompt."""
     if phones.shape[0] != 1:
         raise ValueError("candidates are drawn for one utterance at a time (phones [1, L])")
     ph, tn = phones.expand(candidates, -1).contiguous(), tones.expand(candidates, -1).contiguous()
     tok = lm.generate(ph, tn, attention_mask=None, use_cache=None, max_length=max_length, do_sample=True, temperature=1.0, top_k=5, top_p=1.0,
                       repetition_penalty=1.0, num_beams=1, no_repeat_ngram_size=no_repeat_ngram_size, early_stopping=True, spk_id=torch.ones_like(ph) * spk_id,
-                      end_gate_threshold=None)
-    best, mean_lp, _ = pick_candidate(lm, phones, tones, tok, spk_id)
-    row = tok[best, 1:]
-    stop = (row >= lm.semantic_eos_token_id).nonzero()
+                      end_gate_threshold=None, **({} if semantic_prompt is None else {"semantic_prompt": semantic_prompt.expand(candidates, -1).contiguous()}))
+    P = 1 if semantic_prompt is None else semantic_prompt.shape[1]
+    best, mean_lp, _ = pick_candidate(lm, phones, tones, tok, spk_id, prompt_len=P)
+    row = tok[best]
+    stop = (row[P:] >= lm.semantic_eos_token_id).nonzero()
     print(f"candidates: mean log-prob per token {[round(float(v), 4) for v in mean_lp]}, kept {best}")
-    return row[None, : int(stop[0]) if stop.numel() else row.shape[0]]
+    return row[None, 1 if keep_prompt else P: P + int(stop[0]) if stop.numel() else row.shape[0]]
 
 
-def text2semantic_rows(lm, phones, tones, spk_id=1, max_length=1024, phone_lengths=None, num_beams=1, no_repeat_ngram_size=0):
+def text2semantic_rows(lm, phones, tones, spk_id=1, max_length=1024, phone_lengths=None, num_beams=1, no_repeat_ngram_size=0, prompt_rows=None,
+                       keep_prompt=False):
     """A batch of sentences of DIFFERENT lengths (BASELINE configs[4]: 64 sentences per call).  phones / tones [B,L] right-padded,
     phone_lengths [B] (None = all L): the padding mask goes through the encoder and the cross-attention (reference roformer.py:209-236).
     Returns one 1-D token tensor per row: BOS stripped, cut before the row's first EOS (rows that finish early are padded by generate;
     the ids EOS = kmeans_num + 1 and PAD = kmeans_num + 2 have no codebook row and must never reach the unit lookup).  num_beams and
-    no_repeat_ngram_size as in text2semantic."""
+    no_repeat_ngram_size as in text2semantic.  prompt_rows: one 1-D tensor of semantic ids per row (empty or None: no prompt; BOS is added):
+    every row continues its own prompt as if it ran alone, and comes back without it unless keep_prompt."""
     B, L = phones.shape
     mask = None
     if phone_lengths is not None:
         mask = (torch.arange(L, device=phones.device)[None] < torch.as_tensor(phone_lengths, device=phones.device)[:, None]).to(torch.int64)
     spk = torch.ones_like(phones) * spk_id
+    plen, extra = [1] * B, {}
+    if prompt_rows is not None:
+        plen = [1 + (0 if r is None else int(r.numel())) for r in prompt_rows]
+        prompt = torch.full((B, max(plen)), lm.semantic_pad_token_id, dtype=torch.int64, device=phones.device)
+        prompt[:, 0] = lm.semantic_bos_token_id
+        for b, r in enumerate(prompt_rows):
+            if plen[b] > 1:
+                prompt[b, 1:plen[b]] = r.to(phones.device)
+        pmask = (torch.arange(prompt.shape[1], device=phones.device)[None] < torch.as_tensor(plen, device=phones.device)[:, None]).to(torch.int64)
+        extra = dict(semantic_prompt=prompt, prompt_attention_mask=pmask)
     tok = lm.generate(phones, tones, attention_mask=mask, use_cache=None, max_length=max_length, do_sample=num_beams == 1, temperature=1.0, top_k=5,
                       top_p=1.0, repetition_penalty=1.0, num_beams=num_beams, no_repeat_ngram_size=no_repeat_ngram_size, early_stopping=True, spk_id=spk,
-                      end_gate_threshold=None)
-    tok = tok[:, 1:].cpu()
+                      end_gate_threshold=None, **extra)
+    tok = tok.cpu()
     rows = []
     for b in range(B):
-        stop = (tok[b] >= lm.semantic_eos_token_id).nonzero()
-        n = int(stop[0]) if stop.numel() else tok.shape[1]
-        rows.append(tok[b, :n].to(phones.device))
+        stop = (tok[b, plen[b]:] >= lm.semantic_eos_token_id).nonzero()
+        n = plen[b] + int(stop[0]) if stop.numel() else tok.shape[1]
+        rows.append(tok[b, 1 if keep_prompt else plen[b]: n].to(phones.device))
     return rows
 
 
@@ -324,6 +378,8 @@ def synthesize(svc, codebook, tokens, spk_id=1, speedup=10, method="dpm-solver",
 
 def main(argv=None):
     a = parse_args(argv)
+    if not a.phones and (a.prompt_tokens or a.prompt_phones or a.prompt_audio or a.keep_prompt):
+        raise SystemExit("--prompt_tokens / --prompt_phones / --prompt_audio / --keep_prompt prompt the LM: they need --phones")
     dev = "cuda"
     lm = None
     if a.synthetic:
@@ -346,10 +402,18 @@ def main(argv=None):
         pt = torch.from_numpy(np.load(a.phones).astype(np.int64)).to(dev)
         if a.candidates < 1 or (a.candidates > 1 and a.num_beams != 1):
             raise SystemExit("--candidates needs N >= 1 and, for N > 1, sampling (--num_beams 1)")
+        prompt = {}
+        if a.prompt_tokens and a.prompt_audio:
+            raise SystemExit("--prompt_tokens and --prompt_audio both name the prompt: give one")
+        if a.prompt_phones:
+            pt = torch.cat([torch.from_numpy(np.load(a.prompt_phones).astype(np.int64)).to(dev), pt], dim=1)
+        if a.prompt_tokens or a.prompt_audio:
+            ptok = torch.from_numpy(np.load(a.prompt_tokens).astype(np.int64)).to(dev) if a.prompt_tokens else tokens_from_audio(a, codebook, dev)
+            prompt = dict(semantic_prompt=with_bos(lm, ptok), keep_prompt=a.keep_prompt)
         if a.candidates > 1:
-            tokens = text2semantic_candidates(lm, pt[0:1], pt[1:2], a.spk_id, a.max_length, a.candidates, a.no_repeat_ngram_size)
+            tokens = text2semantic_candidates(lm, pt[0:1], pt[1:2], a.spk_id, a.max_length, a.candidates, a.no_repeat_ngram_size, **prompt)
         else:
-            tokens = text2semantic(lm, pt[0:1], pt[1:2], a.spk_id, a.max_length, a.num_beams, a.no_repeat_ngram_size)
+            tokens = text2semantic(lm, pt[0:1], pt[1:2], a.spk_id, a.max_length, a.num_beams, a.no_repeat_ngram_size, **prompt)
         tokens = tokens.clamp(max=codebook.shape[0] - 1)      # pad ids of finished rows (batch > 1) have no codebook row
     _, _, wav = synthesize(svc, codebook, tokens, a.spk_id, a.speedup, a.method, a.scale_factor)
     wav = wav[0, 0].cpu().numpy()

@@ -15,6 +15,7 @@
 
 #include <map>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 namespace lds {
@@ -129,6 +130,9 @@ __global__ void __launch_bounds__(256) lm_embed_kernel(const float* __restrict__
 // rotary embedding + cache append of the self-attention q | k | v projection (EPI 4): table row = [sin(d/2) | cos(d/2)], pairs (2p, 2p+1)
 // (modeling_roformer.py:220-245); rotated q goes to Y, rotated k and v to kc / vc [B][heads][cap][d] at slot pos0 + l (row n = b * L + l)
 struct LmRope { const float* table; float* kc; float* vc; int pos0, L, heads, cap; };
+// PROW (prompted decode, L = 1): row b sits at its own position plen[b] - 1 + pos0 (pos0 = the global step).  A row that has run past the
+// cache (position >= cap: it reached max_length at an earlier step) stores nothing.
+struct LmRopeRow : LmRope { const int32_t* plen; };
 
 // ---- Deferred LayerNorm.  A linear whose epilogue normalises complete rows needs one workgroup per row tile, i.e. ONE CU streaming the
 //      whole weight matrix (~55 GB/s: 11 us for 256 x 256, four of them per decode step).  Here the producing linear keeps its
@@ -162,11 +166,12 @@ static __device__ __forceinline__ void lm_rows_ln_inplace(float* buf, int L, con
     __syncthreads();
 }
 
-template <int EPI>
+template <int EPI, bool PROW = false>
 __global__ void __launch_bounds__(1024) lm_linear_dln_kernel(const float* __restrict__ X, int ldx, const float* __restrict__ xg, const float* __restrict__ xb,
                                                             const float* __restrict__ Wt, const float* __restrict__ bias, const float* __restrict__ R,
                                                             const float* __restrict__ rg, const float* __restrict__ rb, float eps, float* __restrict__ Y, int ldy,
-                                                            int N, int K, int M, const LmRope rope) {
+                                                            int N, int K, int M, const std::conditional_t<PROW, LmRopeRow, LmRope> rope) {
+    static_assert(!PROW || EPI == 4, "per-row positions belong to the rotary epilogue");
     constexpr int COLS = 64, KS = 16;
     extern __shared__ __attribute__((aligned(16))) float sm[];      // xs [K][8], part [KS-1][COLS][8], rs [M][8] (residual rows), red8 [16][8]
     float* xs = sm;
@@ -241,12 +246,19 @@ __global__ void __launch_bounds__(1024) lm_linear_dln_kernel(const float* __rest
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const int n = (n0 + j < N) ? n0 + j : n0;
-            const int b = n / rope.L, pos = rope.pos0 + (n - b * rope.L);
+            const int b = n / rope.L;
+            int pos = rope.pos0 + (n - b * rope.L);
+            bool live = true;
+            if constexpr (PROW) {
+                pos += rope.plen[b] - 1;
+                live = pos < rope.cap;
+                pos = live ? pos : rope.cap - 1;      // (a finished row: its table row only has to exist)
+            }
             const float sn = rope.table[(long long)pos * d + (e >> 1)], cs = rope.table[(long long)pos * d + hp + (e >> 1)];
             const float other = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, y[j]), 0xb1, 0xf, 0xf, false));   // quad_perm [1,0,3,2]
             const float rot = (e & 1) ? y[j] * cs + other * sn : y[j] * cs - other * sn;
             const long long co = (((long long)b * rope.heads + hd) * rope.cap + pos) * d + e;
-            if (ok[j]) {
+            if (ok[j] && live) {
                 if (sec == 0) Y[(long long)n * ldy + m] = rot;
                 else if (sec == 1) rope.kc[co] = rot;
                 else rope.vc[co] = y[j];
@@ -301,10 +313,13 @@ __global__ void __launch_bounds__(256) lm_kv_pack_kernel(const float* __restrict
 // CAUSAL (lm_attn_causal_kernel, the teacher-forced prefill of lds_lm_score, Lq = Lk_all = T, klen null): query l sees keys 0 .. l of the cache
 // that the projection of all T rows has just filled -- the Lk of the cached decode at step l, hence its key striding over the waves, its
 // block boundaries and its merge order: the row's arithmetic is the decode step's, bit for bit.
-template <bool BEAM, bool CAUSAL = false>
+// PROW (lm_attn_rows_kernel, prompted decode, Lq = 1): klen = the rows' prompt lengths, row b sees its own plen[b] + kadd cached keys (kadd = the
+// global step; the key the row has just appended at slot plen[b] - 1 + kadd is the last of them), at most Lk_all.  The lane blocks, the wave
+// striding and the merge order depend on that count alone, so the row's arithmetic is that of the row decoded alone.
+template <bool BEAM, bool CAUSAL = false, bool PROW = false>
 static __device__ __forceinline__ void lm_attn_body(const float* __restrict__ q, int ldq, const float* __restrict__ kc, const float* __restrict__ vc, int cap,
                                                     int Lq, int Lk_all, const int* __restrict__ klen, int H, int heads, float* __restrict__ out,
-                                                    const int* __restrict__ src, int src_cap, int group) {
+                                                    const int* __restrict__ src, int src_cap, int group, int kadd = 0) {
     extern __shared__ float sc[];                      // [Lk rounded to 64] scores, then 4 x (max, sum, acc[32]) (BEAM: then [Lk rounded to 64] source rows)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int item = blockIdx.x;                       // (b, l, head)
@@ -316,7 +331,7 @@ static __device__ __forceinline__ void lm_attn_body(const float* __restrict__ q,
     // padding mask (reference roformer.py:209-236: attention_mask on the encoder's keys, encoder_attention_mask on the cross-attention's):
     // right-padded rows, so the mask of batch row b is "keys [0, klen[b])"; masked keys get probability exactly 0 as with HF's -inf bias
     const int kl = klen ? klen[b] : Lk_all;
-    const int Lk = CAUSAL ? (int)(n - (long long)b * Lq) + 1 : (kl < Lk_all) ? (kl < 1 ? 1 : kl) : Lk_all;
+    const int Lk = CAUSAL ? (int)(n - (long long)b * Lq) + 1 : PROW ? (kl + kadd < Lk_all ? kl + kadd : Lk_all) : (kl < Lk_all) ? (kl < 1 ? 1 : kl) : Lk_all;
     float* mrg = sc + Lkp;
     float qr[32];
 #pragma unroll
@@ -411,6 +426,11 @@ __global__ void __launch_bounds__(256) lm_attn_causal_kernel(const float* __rest
     lm_attn_body<false, true>(q, ldq, kc, vc, cap, T, T, nullptr, H, heads, out, nullptr, 0, 1);
 }
 
+__global__ void __launch_bounds__(256) lm_attn_rows_kernel(const float* __restrict__ q, int ldq, const float* __restrict__ kc, const float* __restrict__ vc, int cap,
+                                                           int Lk_all, const int* __restrict__ plen, int kadd, int H, int heads, float* __restrict__ out) {
+    lm_attn_body<false, false, true>(q, ldq, kc, vc, cap, 1, Lk_all, plen, H, heads, out, nullptr, 0, 1, kadd);
+}
+
 // ---- teacher-forced scoring (lds_lm_score): the statistics of one logits row, one workgroup per row of a chunk [rows][V] whose first row is
 //      row n0 = b * T + t of the batch.  Position t is counted when t + 1 < len_b and y = labels[b][t + 1] is a vocabulary id (HF's shift,
 //      ForCausalLMLoss; -100 is the ignore index and every other id outside [0, V) is ignored with it):
@@ -497,18 +517,28 @@ static __device__ __forceinline__ void lm_ngram_mark(const int64_t* __restrict__
     }
 }
 
-template <int NI, bool NG>      // NI * 256 >= V: vocabulary slots per thread; NG: n-gram ban of size `ngram` after the repetition penalty
+// PROW (prompted decode): row b continues a prompt of plen[b] tokens, so at the global step `step` it sits at position plen[b] - 1 + step: that is
+// its history's last index, seq[that + 1] is the slot it writes, and a row whose slot would lie beyond the sequence (it reached max_length =
+// cap_tokens at an earlier step) does nothing.  A row that writes the last slot counts as finished; every finishing row records its length in
+// rowlen[b].  `step` still indexes the uniforms, the logits and the flag array.
+template <int NI, bool NG, bool PROW = false>      // NI * 256 >= V: vocabulary slots per thread; NG: n-gram ban of size `ngram` after the repetition penalty
 static __device__ __forceinline__ void lm_sample_body(const float* __restrict__ logits, int V, int do_sample, int top_k, float top_p, float inv_temp,
                                                       float rep_pen, const float* __restrict__ uniforms, int64_t* __restrict__ tokens, int cap_tokens,
                                                       int step, int* __restrict__ unfinished, int eos, int pad, int* __restrict__ any_unfinished,
                                                       const float* __restrict__ word, const float* __restrict__ type, const float* __restrict__ eg,
-                                                      const float* __restrict__ eb, float eps, int H, float* __restrict__ xnext, int ngram) {
+                                                      const float* __restrict__ eb, float eps, int H, float* __restrict__ xnext, int ngram,
+                                                      const int32_t* __restrict__ plen = nullptr, int* __restrict__ rowlen = nullptr) {
     __shared__ float rv[4];
     __shared__ int ri[4];
     __shared__ int chosen;
     __shared__ float topv[kMaxTopK], pr[kMaxTopK];
     __shared__ int topi[kMaxTopK], ord[kMaxTopK];
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int gstep = step;
+    if constexpr (PROW) {
+        step += plen[b] - 1;
+        if (step + 1 >= cap_tokens) return;      // (uniform over the workgroup)
+    }
     const float* lg = logits + (long long)b * V;
     int64_t* seq = tokens + (long long)b * cap_tokens;
     // thread 0 needs these at the very end: fetched now, their latency hides behind the top-k rounds
@@ -626,8 +656,10 @@ static __device__ __forceinline__ void lm_sample_body(const float* __restrict__ 
         if (!alive) next = pad;
         seq[step + 1] = next;
         chosen = next;
-        if (alive && next == eos) unfinished[b] = 0;
-        if (alive && next != eos) atomicOr(any_unfinished + step, 1);      // flag array indexed by step, zeroed by the host wrapper
+        const bool full = PROW && step + 2 >= cap_tokens;                  // the row has just written its last slot
+        if (alive && (next == eos || full)) unfinished[b] = 0;
+        if (alive && next != eos && !full) atomicOr(any_unfinished + gstep, 1);      // flag array indexed by step, zeroed by the host wrapper
+        if constexpr (PROW) { if (alive && (next == eos || full)) rowlen[b] = step + 2; }
     }
     // the next decode step's input row, LayerNorm(word[next] + type[0]) (what lm_embed_kernel computes), without a launch of its own
     if (xnext) {
@@ -681,17 +713,23 @@ __global__ void __launch_bounds__(256) lm_sample_ngram_kernel(const float* __res
 //      cumsum computes, so the oracle restates it to the bit.  TopP (modeling: sort ascending, drop while the cumulative probability stays
 //      <= 1 - top_p, always keep the largest): the cut is found as the largest probability value t with sum{p_j <= t} <= 1 - top_p by bisection
 //      over the ordered bit patterns of the probabilities (31 block reductions); probabilities tied with the cut are dropped together. ----
-template <bool NG>
+template <bool NG, bool PROW = false>
 static __device__ __forceinline__ void lm_sample_full_body(const float* __restrict__ logits, int V, float top_p, float inv_temp, float rep_pen,
                                                            const float* __restrict__ uniforms, int64_t* __restrict__ tokens, int cap_tokens, int step,
                                                            int* __restrict__ unfinished, int eos, int pad, int* __restrict__ any_unfinished,
                                                            const float* __restrict__ word, const float* __restrict__ type, const float* __restrict__ eg,
-                                                           const float* __restrict__ eb, float eps, int H, float* __restrict__ xnext, int ngram) {
+                                                           const float* __restrict__ eb, float eps, int H, float* __restrict__ xnext, int ngram,
+                                                           const int32_t* __restrict__ plen = nullptr, int* __restrict__ rowlen = nullptr) {
     extern __shared__ float prob[];      // [V]
     __shared__ float rv[4];
     __shared__ int chosen;
     __shared__ float sh_max, sh_z;
     const int b = blockIdx.x, tid = threadIdx.x;
+    const int gstep = step;
+    if constexpr (PROW) {      // the row's own position, as in lm_sample_body
+        step += plen[b] - 1;
+        if (step + 1 >= cap_tokens) return;
+    }
     const float* lg = logits + (long long)b * V;
     int64_t* seq = tokens + (long long)b * cap_tokens;
     for (int c = tid; c < V; c += 256) prob[c] = lg[c];
@@ -766,8 +804,10 @@ static __device__ __forceinline__ void lm_sample_full_body(const float* __restri
         if (!alive) next = pad;
         seq[step + 1] = next;
         chosen = next;
-        if (alive && next == eos) unfinished[b] = 0;
-        if (alive && next != eos) atomicOr(any_unfinished + step, 1);
+        const bool full = PROW && step + 2 >= cap_tokens;
+        if (alive && (next == eos || full)) unfinished[b] = 0;
+        if (alive && next != eos && !full) atomicOr(any_unfinished + gstep, 1);
+        if constexpr (PROW) { if (alive && (next == eos || full)) rowlen[b] = step + 2; }
     }
     if (xnext) {      // the next decode step's input row, as lm_sample_kernel writes it
         __syncthreads();
@@ -809,6 +849,47 @@ __global__ void __launch_bounds__(256) lm_sample_full_ngram_kernel(const float* 
                                                                    const float* __restrict__ eb, float eps, int H, float* __restrict__ xnext, int ngram) {
     lm_sample_full_body<true>(logits, V, top_p, inv_temp, rep_pen, uniforms, tokens, cap_tokens, step, unfinished, eos, pad, any_unfinished, word, type, eg, eb,
                               eps, H, xnext, ngram);
+}
+
+// the four choices above with per-row positions (lds_lm_generate_prompt): NG false ignores `ngram`
+template <int NI, bool NG>
+__global__ void __launch_bounds__(256) lm_sample_rows_kernel(const float* __restrict__ logits, int V, int do_sample, int top_k, float top_p, float inv_temp,
+                                                             float rep_pen, const float* __restrict__ uniforms, int64_t* __restrict__ tokens, int cap_tokens,
+                                                             int step, int* __restrict__ unfinished, int eos, int pad, int* __restrict__ any_unfinished,
+                                                             const float* __restrict__ word, const float* __restrict__ type, const float* __restrict__ eg,
+                                                             const float* __restrict__ eb, float eps, int H, float* __restrict__ xnext, int ngram,
+                                                             const int32_t* __restrict__ plen, int* __restrict__ rowlen) {
+    lm_sample_body<NI, NG, true>(logits, V, do_sample, top_k, top_p, inv_temp, rep_pen, uniforms, tokens, cap_tokens, step, unfinished, eos, pad, any_unfinished,
+                                 word, type, eg, eb, eps, H, xnext, ngram, plen, rowlen);
+}
+template <bool NG>
+__global__ void __launch_bounds__(256) lm_sample_full_rows_kernel(const float* __restrict__ logits, int V, float top_p, float inv_temp, float rep_pen,
+                                                                  const float* __restrict__ uniforms, int64_t* __restrict__ tokens, int cap_tokens, int step,
+                                                                  int* __restrict__ unfinished, int eos, int pad, int* __restrict__ any_unfinished,
+                                                                  const float* __restrict__ word, const float* __restrict__ type, const float* __restrict__ eg,
+                                                                  const float* __restrict__ eb, float eps, int H, float* __restrict__ xnext, int ngram,
+                                                                  const int32_t* __restrict__ plen, int* __restrict__ rowlen) {
+    lm_sample_full_body<NG, true>(logits, V, top_p, inv_temp, rep_pen, uniforms, tokens, cap_tokens, step, unfinished, eos, pad, any_unfinished, word, type, eg, eb,
+                                  eps, H, xnext, ngram, plen, rowlen);
+}
+
+// the start of a prompted decode, one workgroup per row: tokens[b] = the row's prompt (ids clamped to the vocabulary), PAD from plen[b] on;
+// ids [B][Pq] = the first Pq prompt positions of every row for the prefill's embedding (clamped as well; beyond plen[b] whatever the caller left there);
+// last[b] = the row's last prompt token, the first decode step's input
+__global__ void __launch_bounds__(256) lm_prompt_init_kernel(const int64_t* __restrict__ prompt, int P, const int32_t* __restrict__ plen, int V, int pad, int cap,
+                                                             int Pq, int64_t* __restrict__ tokens, int64_t* __restrict__ ids, int64_t* __restrict__ last) {
+    const int b = blockIdx.x, pl = plen[b];
+    for (int l = threadIdx.x; l < cap; l += 256) {
+        long long t = pad;
+        if (l < P) {
+            t = prompt[(long long)b * P + l];
+            t = (t < 0) ? 0 : (t >= V ? V - 1 : t);
+            if (l < Pq) ids[(long long)b * Pq + l] = t;
+            if (l == pl - 1) last[b] = t;
+            if (l >= pl) t = pad;
+        }
+        tokens[(long long)b * cap + l] = t;
+    }
 }
 
 // ---- one step of HF's greedy beam search (transformers generation/utils.py _beam_search with _get_top_k_continuations,
@@ -1163,11 +1244,14 @@ struct LmArena {
 };
 // beam-search state (K > 1): two buffers of the running sequences, of the ancestry table and of the finished hypotheses, per-row scores / flags
 struct LmBeamWs { int64_t *rseq[2], *fseq[2]; int* tab[2]; float *rscore, *fscore; int *ffin, *flen, *unsat; };
-struct LmWs { float *x, *y, *z, *qkv, *ctx, *ff, *kv, *logits, *kc_tmp, *vc_tmp; int* flags; std::vector<float*> kc, vc, ckc, cvc; LmBeamWs beam; };
+// a prompted decode (P > 1): the prefill's token ids [B][P], every row's last prompt token [B] and the prompt lengths on the device [B]
+struct LmPromptWs { int64_t *ids, *last; int32_t* plen; };
+struct LmWs { float *x, *y, *z, *qkv, *ctx, *ff, *kv, *logits, *kc_tmp, *vc_tmp; int* flags; std::vector<float*> kc, vc, ckc, cvc; LmBeamWs beam; LmPromptWs prompt; };
 // N = rows processed at once (B * L for the prefill, B * K for a decode step); K = beams per batch item (1: the layout of a plain decode)
-void lm_plan(const lds_lm* lm, LmArena& A, int B, int L, int cap, LmWs& w, int K = 1) {
+// P = the prompt's width (1: no prompt, today's layout byte for byte): the prefill runs B * P rows through the activation buffers
+void lm_plan(const lds_lm* lm, LmArena& A, int B, int L, int cap, LmWs& w, int K = 1, int P = 1) {
     const lds_lm_cfg& c = lm->cfg;
-    const size_t R = (size_t)B * K, BL = (size_t)B * (L > 1 ? L : 1), N = BL > R ? BL : R, H = c.hidden;
+    const size_t R = (size_t)B * K, BL = (size_t)B * (L > 1 ? L : 1), BP = (size_t)B * P, N0 = BL > R ? BL : R, N = N0 > BP ? N0 : BP, H = c.hidden;
     w.x = A.f(N * H); w.y = A.f(N * H); w.z = A.f(N * H); w.qkv = A.f(N * 3 * H); w.ctx = A.f(N * H); w.ff = A.f(N * c.inter); w.kv = A.f(N * 2 * H);
     w.logits = A.f(R * c.sem_vocab);
     w.kc_tmp = A.f(N * H); w.vc_tmp = A.f(N * H);
@@ -1184,6 +1268,8 @@ void lm_plan(const lds_lm* lm, LmArena& A, int B, int L, int cap, LmWs& w, int K
         }
         w.beam.rscore = A.f(R); w.beam.fscore = A.f(R); w.beam.ffin = (int*)A.f(R); w.beam.flen = (int*)A.f(R); w.beam.unsat = (int*)A.f(B);
     }
+    w.prompt = LmPromptWs{};
+    if (P > 1) { w.prompt.ids = (int64_t*)A.f(2 * BP); w.prompt.last = (int64_t*)A.f(2 * (size_t)B); w.prompt.plen = (int32_t*)A.f((size_t)B); }
 }
 hipError_t lm_attention(const float* q, int ldq, const float* kc, const float* vc, int cap, int B, int Lq, int Lk, const int* klen, const lds_lm_cfg& c, float* out,
                         hipStream_t st) {
@@ -1207,6 +1293,13 @@ hipError_t lm_attention_beam(const float* q, int ldq, const float* kc, const flo
     hipLaunchKernelGGL(lm_attn_beam_kernel, dim3(total), dim3(256), lds, st, q, ldq, kc, vc, cap, Lq, Lk, klen, c.hidden, c.heads, out, src, src_cap, group);
     return hipGetLastError();
 }
+// one query per row over the row's own plen[b] + step cached keys (lm_attn_rows_kernel); Lk_max = the longest row's count, for the LDS size
+hipError_t lm_attention_rows(const float* q, int ldq, const float* kc, const float* vc, int cap, int B, int Lk_max, const int32_t* plen, int step,
+                             const lds_lm_cfg& c, float* out, hipStream_t st) {
+    const size_t lds = (size_t)(((Lk_max + 63) & ~63) + 4 * 34) * sizeof(float);
+    hipLaunchKernelGGL(lm_attn_rows_kernel, dim3((unsigned)(B * c.heads)), dim3(256), lds, st, q, ldq, kc, vc, cap, Lk_max, plen, step, c.hidden, c.heads, out);
+    return hipGetLastError();
+}
 // rows [N][hidden] together with the LayerNorm that is still owed to them (ln == nullptr: already normalised)
 struct LmRows { float* p; const LmLN* ln; };
 
@@ -1226,25 +1319,58 @@ hipError_t lm_dln(const LmLinear& W, const LmRows& X, int ldx, const LmRows* R, 
     return hipGetLastError();
 }
 
+// the self-attention projection of a prompted decode step (EPI 4 with per-row positions, N = B rows)
+hipError_t lm_dln_rope_rows(const LmLinear& W, const LmRows& X, float eps, float* Y, int N, hipStream_t st, const LmRopeRow& rope) {
+    if (W.K % 256 || W.M % 192 || (W.M / 3 / rope.heads) % 2 || rope.L != 1 || !rope.plen) return hipErrorInvalidValue;
+    auto kern = lm_linear_dln_kernel<4, true>;
+    static std::atomic<unsigned long long> attr_done{0};
+    hipError_t e = ensure_max_dynamic_lds(reinterpret_cast<const void*>(kern), attr_done);
+    if (e != hipSuccess) return e;
+    const size_t lds = ((size_t)W.K * 8 + (size_t)15 * 64 * 8 + 16 * 8) * sizeof(float);
+    hipLaunchKernelGGL(kern, dim3((W.M + 63) / 64, (N + 7) / 8), dim3(1024), lds, st, (const float*)X.p, W.K, X.ln ? X.ln->g : nullptr, X.ln ? X.ln->b : nullptr, W.wt,
+                       W.b, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, eps, Y, W.M, N, W.K, W.M, rope);
+    return hipGetLastError();
+}
+
 // one BERT-style post-LN layer over N = B * L rows; self-attention over [pos0, pos0 + L) appended to the cache (kc, vc).
 // Every LayerNorm is deferred to the readers of its rows (lm_linear_dln_kernel): `x` comes in, and goes out, as rows + owed LayerNorm.
 // The three row buffers of the workspace rotate: input -> a (attention block) -> c (cross-attention block) -> output in the input's buffer.
 // self_klen / cross_klen: per-batch-row key counts of the padding mask (device int32 [B]) or null
-// beam (decode steps of a beam search, B = rows = items * beam->K): the self-attention follows the ancestry table, the cross-attention maps row n to item n / K
-// causal (the teacher-forced prefill, pos0 = 0, cap >= L): query l of the self-attention sees keys 0 .. l
+// mode: which self-attention the layer runs (LmLayerMode; the default is the plain one over the keys [0, pos0 + L))
+struct LmLayerMode {
+    // decode steps of a beam search (B = rows = items * beam->K): the self-attention follows the ancestry table, the cross-attention maps row n to item n / K
+    const LmBeamAttn* beam = nullptr;
+    // the teacher-forced prefill (pos0 = 0, cap >= L): query l of the self-attention sees keys 0 .. l
+    bool causal = false;
+    // a prompted decode step (L = 1, pos0 = the global step): row b sits at position plen[b] - 1 + pos0; Lk_max = the longest row's key count
+    const int32_t* plen = nullptr;
+    int Lk_max = 0;
+    static LmLayerMode beams(const LmBeamAttn* b) { LmLayerMode m; m.beam = b; return m; }
+    static LmLayerMode prefill() { LmLayerMode m; m.causal = true; return m; }
+    static LmLayerMode rows(const int32_t* plen, int Lk_max) { LmLayerMode m; m.plen = plen; m.Lk_max = Lk_max; return m; }
+};
 int lm_layer(const lds_lm* lm, const LmStack& s, const LmLayer& Ly, const LmWs& w, LmRows& x, int B, int L, int pos0, float* kc, float* vc, int cap,
-             const float* ckc, const float* cvc, int Lenc, const int* self_klen, const int* cross_klen, hipStream_t st, const LmBeamAttn* beam = nullptr, bool causal = false) {
+             const float* ckc, const float* cvc, int Lenc, const int* self_klen, const int* cross_klen, hipStream_t st, const LmLayerMode& mode = LmLayerMode()) {
+    const LmBeamAttn* beam = mode.beam;
+    const bool causal = mode.causal;
+    const int32_t* plen = mode.plen;
+    const int Lk_max = mode.Lk_max;
     const lds_lm_cfg& c = lm->cfg;
     const int H = c.hidden, N = B * L;
     if (Ly.self.o.M != H || Ly.ff2.M != H || (Ly.has_cross && (Ly.cross.o.M != H || Ly.cross.q.K != H))) return lm_fail(LDS_EINVAL, "layer shapes");
     float* free1 = (x.p == w.x) ? w.y : w.x;
     float* free2 = (x.p == w.z) ? w.y : w.z;
     if (free1 == free2) free2 = w.x;
-    {
+    if (plen) {
+        LmRopeRow rope;
+        rope.table = s.table; rope.kc = kc; rope.vc = vc; rope.pos0 = pos0; rope.L = L; rope.heads = c.heads; rope.cap = cap; rope.plen = plen;
+        LM_HIP(lm_dln_rope_rows(Ly.self.qkv, x, c.eps, w.qkv, N, st, rope));
+    } else {
         const LmRope rope{s.table, kc, vc, pos0, L, c.heads, cap};      // rotary embedding and cache append in the projection's epilogue
         LM_HIP(lm_dln<4>(Ly.self.qkv, x, H, nullptr, c.eps, w.qkv, 3 * H, N, st, &rope));
     }
-    if (causal) LM_HIP(lm_attention_causal(w.qkv, 3 * H, kc, vc, cap, B, L, c, w.ctx, st));
+    if (plen) LM_HIP(lm_attention_rows(w.qkv, 3 * H, kc, vc, cap, B, Lk_max, plen, pos0, c, w.ctx, st));
+    else if (causal) LM_HIP(lm_attention_causal(w.qkv, 3 * H, kc, vc, cap, B, L, c, w.ctx, st));
     else if (beam) LM_HIP(lm_attention_beam(w.qkv, 3 * H, kc, vc, cap, B, L, pos0 + L, self_klen, c, w.ctx, beam->src, cap, 1, st));
     else LM_HIP(lm_attention(w.qkv, 3 * H, kc, vc, cap, B, L, pos0 + L, self_klen, c, w.ctx, st));
     const LmRows ctx{w.ctx, nullptr};
@@ -1451,7 +1577,7 @@ extern "C" int lds_lm_generate_opts(lds_lm* lm, const float* enc, const int32_t*
         const LmBeamAttn ba{w.beam.tab[cur], K};
         for (int i = 0; i < c.dec_layers; ++i) {
             int r = lm_layer(lm, lm->dec, lm->dec.layers[i], w, cx, R, 1, step, w.kc[i], w.vc[i], max_length, w.ckc[i], w.cvc[i], L, nullptr, enc_len, st,
-                             K > 1 ? &ba : nullptr);
+                             LmLayerMode::beams(K > 1 ? &ba : nullptr));
             if (r != LDS_OK) return r;
         }
         // LM head: h = GELU(W_t LN(x)) stored un-normalised, logits = W_d LN(h)
@@ -1505,6 +1631,166 @@ extern "C" int lds_lm_generate(lds_lm* lm, const float* enc, const int32_t* enc_
                                void* ws, size_t ws_bytes, void* stream) {
     const lds_lm_decode_opts o{do_sample, top_k, top_p, temperature, repetition_penalty, 0, 1, 1};
     return lds_lm_generate_opts(lm, enc, enc_len, B, L, max_length, &o, uniforms, tokens, logits_out, n_tokens_host, ws, ws_bytes, stream);
+}
+
+// ---- prompted decode (lds_lm_generate_prompt): every row continues its own prompt of plen[b] tokens.
+//      Prefill: the positions 0 .. Pq - 1 (Pq = the longest prompt - 1) of all rows go through the decoder layers in ONE causal pass
+//      (lm_layer with causal = true, the pass of lds_lm_score) that appends their keys / values to the decode's own caches.  The head is skipped.
+//      Decode: global step s handles row b at position plen[b] - 1 + s -- the row's last prompt token at s = 0 -- with the per-row forms of
+//      the projection, the self-attention and the token choice.
+//      INVARIANT: the prefill also fills the cache slots plen[b] - 1 .. Pq - 1 of a shorter row, from ids the caller never meant to be read
+//      (clamped to the vocabulary).  No query ever sees them: step s of row b first overwrites slot plen[b] - 1 + s with the row's real token
+//      and then reads the slots 0 .. plen[b] - 1 + s, so every slot a query reads was written from the prompt proper or by an earlier step
+//      of the same row.  The same argument covers whatever the workspace held on entry. ----
+namespace {
+constexpr int kMaxPromptBatch = 64;      // the rows' final lengths live in the 64 spare ints behind the step flags (lm_plan)
+// the shape checks, which need no model (they come before every check that does; no device call)
+int lm_prompt_check(int B, int L, int max_length, int P) {
+    if (B <= 0 || L <= 0 || max_length < 2 || P < 1) return lm_fail(LDS_EINVAL, "bad argument");
+    if (B > kMaxPromptBatch) return lm_fail(LDS_EINVAL, "a prompted decode takes at most %d rows, got %d", kMaxPromptBatch, B);
+    // the prefill's causal self-attention stages one score per key in LDS; its linears take 8 rows per workgroup along grid.y
+    if ((size_t)(((P + 63) & ~63) + 4 * 34) * sizeof(float) > 64 * 1024 || (long long)B * P > 8 * 65535LL)
+        return lm_fail(LDS_EINVAL, "prompt width %d too large (<= 16000, B * P <= 524280)", P);
+    return LDS_OK;
+}
+hipError_t lm_launch_choice_rows(const lds_lm_decode_opts& o, int B, int V, const float* lg, float inv_temp, const float* u, int64_t* tokens, int cap, int step,
+                                 int* unfinished, int eos, int pad, int* any_unf, const float* word, const float* type, const float* eg, const float* eb, float eps,
+                                 int H, float* xnext, const int32_t* plen, int* rowlen, hipStream_t st) {
+    const int ds = o.do_sample, tk = ds ? o.top_k : 1, ng = o.no_repeat_ngram_size;
+    const float pen = o.repetition_penalty, tp = o.top_p;
+    if (ds && o.top_k == 0) {
+        auto kern = ng > 0 ? lm_sample_full_rows_kernel<true> : lm_sample_full_rows_kernel<false>;
+        hipLaunchKernelGGL(kern, dim3(B), dim3(256), sizeof(float) * V, st, lg, V, tp, inv_temp, pen, u, tokens, cap, step, unfinished, eos, pad, any_unf, word, type,
+                           eg, eb, eps, H, xnext, ng, plen, rowlen);
+        return hipGetLastError();
+    }
+    auto kern = (V <= 256 * 9)    ? (ng > 0 ? lm_sample_rows_kernel<9, true> : lm_sample_rows_kernel<9, false>)
+                : (V <= 256 * 17) ? (ng > 0 ? lm_sample_rows_kernel<17, true> : lm_sample_rows_kernel<17, false>)
+                                  : (ng > 0 ? lm_sample_rows_kernel<32, true> : lm_sample_rows_kernel<32, false>);
+    hipLaunchKernelGGL(kern, dim3(B), dim3(256), 0, st, lg, V, ds, tk, tp, inv_temp, pen, u, tokens, cap, step, unfinished, eos, pad, any_unf, word, type, eg, eb, eps,
+                       H, xnext, ng, plen, rowlen);
+    return hipGetLastError();
+}
+}  // namespace
+
+extern "C" int lds_lm_workspace_bytes_prompt(const lds_lm* lm, int B, int L, int max_length, int P, size_t* out) {
+    if (int r = lm_prompt_check(B, L, max_length, P)) return r;
+    if (!lm || !out) return lm_fail(LDS_EINVAL, "bad argument");
+    LmArena A(nullptr, 0);
+    LmWs w;
+    lm_plan(lm, A, B, L, max_length, w, 1, P);
+    *out = A.used;
+    return LDS_OK;
+}
+
+extern "C" int lds_lm_generate_prompt(lds_lm* lm, const float* enc, const int32_t* enc_len, int B, int L, int max_length, const lds_lm_decode_opts* opts,
+                                      const int64_t* prompt, const int32_t* prompt_len, int P, const float* uniforms, int64_t* tokens, float* logits_out,
+                                      int* n_tokens_host, void* ws, size_t ws_bytes, void* stream) {
+    if (!opts) return lm_fail(LDS_EINVAL, "null options");
+    const lds_lm_decode_opts o = *opts;
+    if (int r = lm_check_opts(o, logits_out)) return r;
+    if (o.num_beams > 1) return lm_fail(LDS_EINVAL, "beam search from a prompt is not built (num_beams must be 1 with a prompt)");
+    if (int r = lm_prompt_check(B, L, max_length, P)) return r;
+    int Pmax = 0, Pmin = P;
+    for (int b = 0; b < B; ++b) {
+        const int pl = prompt_len ? prompt_len[b] : P;
+        if (pl < 1 || pl > P) return lm_fail(LDS_EINVAL, "prompt_len[%d] = %d out of range (1 .. P = %d)", b, pl, P);
+        if (pl >= max_length) return lm_fail(LDS_EINVAL, "prompt_len[%d] = %d leaves no room below max_length = %d (the total length, prompt included)", b, pl, max_length);
+        Pmax = pl > Pmax ? pl : Pmax;
+        Pmin = pl < Pmin ? pl : Pmin;
+    }
+    if (!lm || !enc || !tokens || !n_tokens_host || !ws || !prompt) return lm_fail(LDS_EINVAL, "bad argument");
+    {   // the workspace is checked against the prompted plan whatever the lengths are
+        LmArena A(ws, ws_bytes);
+        LmWs w;
+        lm_plan(lm, A, B, L, max_length, w, 1, P);
+        if (!A.ok) return lm_fail(LDS_ENOMEM, "LM workspace too small: need %zu bytes", A.used);
+    }
+    // every row is BOS alone: the plain decode, through its own launches (its plan is a prefix of the prompted one when P > 1)
+    if (Pmax == 1) return lds_lm_generate_opts(lm, enc, enc_len, B, L, max_length, opts, uniforms, tokens, logits_out, n_tokens_host, ws, ws_bytes, stream);
+    const lds_lm_cfg& c = lm->cfg;
+    const int do_sample = o.do_sample, top_k = o.top_k;
+    const float top_p = o.top_p, temperature = o.temperature;
+    if (do_sample && (!uniforms || top_k < 0 || top_k > kMaxTopK || top_k > c.sem_vocab || !(top_p > 0.f) || !(temperature > 0.f)))
+        return lm_fail(LDS_EINVAL, "sampling needs uniforms, 0 <= top_k <= %d (0 = no top-k filter), top_p > 0, temperature > 0", kMaxTopK);
+    if (do_sample && top_k == 0 && (size_t)c.sem_vocab * sizeof(float) > 60 * 1024) return lm_fail(LDS_EINVAL, "top_k = 0 needs the vocabulary row in LDS (<= 15360 entries)");
+    if (max_length > c.max_pos) return lm_fail(LDS_EINVAL, "max_length exceeds max_position_embeddings");
+    if (L > c.max_pos || (size_t)(((L + 63) & ~63) + 4 * 34) * sizeof(float) > 64 * 1024)
+        return lm_fail(LDS_EINVAL, "encoder length %d out of range (1 .. min(max_position_embeddings = %d, 16000))", L, c.max_pos);
+    if ((size_t)(((max_length + 63) & ~63) + 4 * 34) * sizeof(float) > 64 * 1024) return lm_fail(LDS_EINVAL, "max_length %d too long for a prompted decode (<= 16000)", max_length);
+    hipStream_t st = (hipStream_t)stream;
+    LmArena A(ws, ws_bytes);
+    LmWs w;
+    lm_plan(lm, A, B, L, max_length, w, 1, P);
+    const int H = c.hidden, V = c.sem_vocab, Pq = Pmax - 1;
+    int* unfinished = w.flags;                       // [B]
+    int* any_unf = w.flags + B;                      // [max_length]: 1 when a row is still running after global step s
+    int* rowlen = w.flags + B + max_length;          // [B <= 64]: every row's final length, prompt included
+    for (int i = 0; i < c.dec_layers; ++i) {         // cross-attention keys / values, as in lds_lm_generate_opts
+        const LmRows er{const_cast<float*>(enc), nullptr};
+        LM_HIP(lm_dln<0>(lm->dec.layers[i].cross.kv, er, H, nullptr, c.eps, w.kv, 2 * H, B * L, st));
+        hipLaunchKernelGGL(lm_kv_pack_kernel, dim3((unsigned)(((long long)B * L * H + 255) / 256)), dim3(256), 0, st, w.kv, B, L, H, c.heads, w.ckc[i], w.cvc[i], L);
+        LM_HIP(hipGetLastError());
+    }
+    {
+        std::vector<int> init(B + max_length + kMaxPromptBatch, 0), pl(B);
+        for (int b = 0; b < B; ++b) { init[b] = 1; init[B + max_length + b] = max_length; pl[b] = prompt_len ? prompt_len[b] : P; }
+        LM_HIP(hipMemcpyAsync(unfinished, init.data(), sizeof(int) * init.size(), hipMemcpyHostToDevice, st));
+        LM_HIP(hipMemcpyAsync(w.prompt.plen, pl.data(), sizeof(int) * B, hipMemcpyHostToDevice, st));
+        LM_HIP(hipStreamSynchronize(st));      // the host staging vectors go out of scope
+    }
+    const int32_t* plen = w.prompt.plen;
+    hipLaunchKernelGGL(lm_prompt_init_kernel, dim3(B), dim3(256), 0, st, prompt, P, plen, V, c.sem_pad, max_length, Pq, tokens, w.prompt.ids, w.prompt.last);
+    LM_HIP(hipGetLastError());
+    {   // prefill: positions 0 .. Pq - 1 of every row, keys / values straight into the decode caches (see the invariant above)
+        hipLaunchKernelGGL(lm_embed_kernel, dim3(B * Pq), dim3(256), 0, st, lm->dec.word, lm->dec.type, (const float*)nullptr, lm->dec.ln_emb.g, lm->dec.ln_emb.b,
+                           (const int64_t*)w.prompt.ids, 1, (const int64_t*)nullptr, (const int64_t*)nullptr, 0, c.eps, H, V, 1, 1, w.x);
+        LM_HIP(hipGetLastError());
+        LmRows px{w.x, nullptr};
+        for (int i = 0; i < c.dec_layers; ++i) {
+            int r = lm_layer(lm, lm->dec, lm->dec.layers[i], w, px, B, Pq, 0, w.kc[i], w.vc[i], max_length, w.ckc[i], w.cvc[i], L, nullptr, enc_len, st, LmLayerMode::prefill());
+            if (r != LDS_OK) return r;
+        }
+    }
+    // the first step's input rows: every row's last prompt token; later rows come from the token choice
+    hipLaunchKernelGGL(lm_embed_kernel, dim3(B), dim3(256), 0, st, lm->dec.word, lm->dec.type, (const float*)nullptr, lm->dec.ln_emb.g, lm->dec.ln_emb.b,
+                       (const int64_t*)w.prompt.last, 1, (const int64_t*)nullptr, (const int64_t*)nullptr, 0, c.eps, H, V, 1, 1, w.x);
+    LM_HIP(hipGetLastError());
+    const float inv_temp = do_sample ? 1.0f / temperature : 1.0f;
+    const int n_steps = max_length - Pmin;      // the shortest row writes its last slot at step n_steps - 1
+    std::vector<int> host_flags(n_steps, 0);
+    int checked = 0;
+    for (int step = 0; step < n_steps; ++step) {
+        LmRows cx{w.x, nullptr};
+        const int Lk_max = (Pmax + step < max_length) ? Pmax + step : max_length;
+        for (int i = 0; i < c.dec_layers; ++i) {
+            int r = lm_layer(lm, lm->dec, lm->dec.layers[i], w, cx, B, 1, step, w.kc[i], w.vc[i], max_length, w.ckc[i], w.cvc[i], L, nullptr, enc_len, st,
+                             LmLayerMode::rows(plen, Lk_max));
+            if (r != LDS_OK) return r;
+        }
+        LM_HIP(lm_dln<1>(lm->head_t, cx, H, nullptr, c.eps, w.ctx, H, B, st));
+        const LmRows hrows{w.ctx, &lm->head_ln};
+        float* lg = logits_out ? logits_out + (size_t)step * B * V : w.logits;
+        LM_HIP(lm_dln<0>(lm->head_d, hrows, H, nullptr, c.eps, lg, V, B, st));
+        LM_HIP(lm_launch_choice_rows(o, B, V, lg, inv_temp, do_sample ? uniforms + (size_t)step * B : nullptr, tokens, max_length, step, unfinished, c.sem_eos,
+                                     c.sem_pad, any_unf, lm->dec.word, lm->dec.type, lm->dec.ln_emb.g, lm->dec.ln_emb.b, c.eps, H, w.x, plen, rowlen, st));
+        if ((step & 7) == 7 || step + 1 == n_steps) {      // the EOS poll of lds_lm_generate_opts; a row that reached max_length counts as finished
+            LM_HIP(hipMemcpyAsync(host_flags.data() + checked, any_unf + checked, sizeof(int) * (step + 1 - checked), hipMemcpyDeviceToHost, st));
+            LM_HIP(hipStreamSynchronize(st));
+            bool done = false;
+            for (int s = checked; s <= step && !done; ++s) done = host_flags[s] == 0;
+            checked = step + 1;
+            if (done) break;
+        }
+    }
+    // cropped to the longest row.  (Steps enqueued past the last running row's end only wrote PAD behind finished rows.)
+    std::vector<int> len(B, 0);
+    LM_HIP(hipMemcpyAsync(len.data(), rowlen, sizeof(int) * B, hipMemcpyDeviceToHost, st));
+    LM_HIP(hipStreamSynchronize(st));
+    int n_tokens = 0;
+    for (int b = 0; b < B; ++b) n_tokens = len[b] > n_tokens ? len[b] : n_tokens;
+    *n_tokens_host = n_tokens;
+    return LDS_OK;
 }
 
 // ---- teacher-forced scoring: the decoder stack over all B * T rows in one causal pass, then the head over row chunks of kScoreChunk rows
@@ -1571,7 +1857,7 @@ extern "C" int lds_lm_score(lds_lm* lm, const float* enc, const int32_t* enc_len
         LM_HIP(lm_dln<0>(lm->dec.layers[i].cross.kv, er, H, nullptr, c.eps, s.w.kv, 2 * H, B * L, st));
         hipLaunchKernelGGL(lm_kv_pack_kernel, dim3((unsigned)(((long long)B * L * H + 255) / 256)), dim3(256), 0, st, s.w.kv, B, L, H, c.heads, s.ckc, s.cvc, L);
         LM_HIP(hipGetLastError());
-        int r = lm_layer(lm, lm->dec, lm->dec.layers[i], s.w, cx, B, T, 0, s.kc, s.vc, T, s.ckc, s.cvc, L, nullptr, enc_len, st, nullptr, true);
+        int r = lm_layer(lm, lm->dec, lm->dec.layers[i], s.w, cx, B, T, 0, s.kc, s.vc, T, s.ckc, s.cvc, L, nullptr, enc_len, st, LmLayerMode::prefill());
         if (r != LDS_OK) return r;
     }
     // LM head as in the decode: h = GELU(W_t LN(x)) stored un-normalised, logits = W_d LN(h), the latter chunk by chunk

@@ -131,6 +131,8 @@ lds_lm_encode                    i:pppppppziip
 lds_lm_generate                  i:pppiiiiifffpppppzp
 lds_lm_workspace_bytes_opts      i:piiiip
 lds_lm_generate_opts             i:pppiiippppppzp
+lds_lm_workspace_bytes_prompt    i:piiiip
+lds_lm_generate_prompt           i:pppiiipppipppppzp
 lds_lm_score_workspace_bytes     i:piiip
 lds_lm_score                     i:pppiipppippppppzp
 lds_kmeans_workspace_bytes       i:qiip
@@ -1059,6 +1061,34 @@ class LM(_Handle):
             check(lib().lds_lm_generate_opts(*head, C.byref(o), *tail))
         toks = tokens[:, : n.value].contiguous()
         return toks, (logits[: n.value - 1] if logits is not None else None)
+
+    def generate_prompt(self, enc, prompt, prompt_len, max_length, do_sample, top_k, top_p, temperature, repetition_penalty, uniforms=None,
+                        return_logits=False, enc_len=None, no_repeat_ngram_size=0):
+        """Prompted decode (lds_lm_generate_prompt): prompt int64 [B,P] on the device (BOS first, right-padded), prompt_len a sequence of B
+        host ints or None (= P everywhere); max_length counts the prompt.  Returns (tokens [B,n] with the prompt in front, logits [steps,B,V]
+        or None): logits[s][b] chose row b's s-th generated token, and steps is the largest number of tokens any row generated (rows of the
+        library's buffer behind that were chosen by no row)."""
+        import torch
+        B, L, _ = enc.shape
+        P = int(prompt.shape[1])
+        o = LMDecodeOpts(1 if do_sample else 0, int(top_k or 0), float(top_p), float(temperature), float(repetition_penalty), int(no_repeat_ngram_size), 1, 1)
+        plen = None if prompt_len is None else (C.c_int32 * B)(*[int(v) for v in prompt_len])
+        ws = self._workspace("lds_lm_workspace_bytes_prompt", enc.device, B, L, int(max_length), P)
+        tokens = torch.empty(B, max_length, dtype=torch.int64, device=enc.device)
+        logits = torch.empty(max_length - 1, B, self.cfg["sem_vocab"], dtype=torch.float32, device=enc.device) if return_logits else None
+        n = C.c_int()
+        enc, prompt, u = enc.contiguous(), prompt.contiguous(), uniforms.contiguous() if uniforms is not None else None
+        check(lib().lds_lm_generate_prompt(self.h, _dev(enc, torch.float32), _dev_or_null(enc_len, torch.int32), B, L, int(max_length), C.byref(o),
+                                           _dev(prompt, torch.int64), C.cast(plen, C.c_void_p) if plen is not None else None, P,
+                                           _dev_or_null(u, torch.float32), _dev(tokens), _dev_or_null(logits), C.byref(n), _dev(ws), ws.numel(), _stream()))
+        toks = tokens[:, : n.value].contiguous()
+        if logits is None:
+            return toks, None
+        # every row's generated count: up to and including its EOS behind the prompt, else to the end of the returned rows
+        plen = torch.tensor([P] * B if prompt_len is None else [int(v) for v in prompt_len], device=toks.device)
+        stop = (toks == self.cfg["sem_eos"]) & (torch.arange(n.value, device=toks.device)[None] >= plen[:, None])
+        end = torch.where(stop.any(1), stop.int().argmax(1) + 1, torch.full_like(plen, n.value))
+        return toks, logits[: int((end - plen).max())]
 
     def score(self, enc, semantic, sem_len=None, labels=None, enc_len=None, return_logits=False):
         """Teacher-forced scoring (lds_lm_score): enc [B,L,hidden] from `encode`, semantic / labels [B,T] int64 (labels None = semantic),

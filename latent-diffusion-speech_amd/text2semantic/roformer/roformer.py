@@ -5,8 +5,9 @@ token choice run in liblds (csrc/lm.hip).  torch keeps the parameters and draws 
 
 Scope: phone mode (the 'text' mode fetches a BERT tokenizer from the hub), inference only (`forward` = the gradient-carrying
 teacher-forced training entry), right-padded batches; greedy decoding, sampling and greedy beam search (num_beams 2 .. 8), each with
-optional n-gram blocking; `score`: teacher-forced log-probs, loss and ranks of given tokens in one causal pass (no gradients).
-Not built: beam sampling and the end gate (see `generate`)."""
+optional n-gram blocking; greedy decoding and sampling may continue a given semantic prompt (`semantic_prompt`, one length per row);
+`score`: teacher-forced log-probs, loss and ranks of given tokens in one causal pass (no gradients).
+Not built: beam sampling, beam search from a prompt and the end gate (see `generate`)."""
 from collections import namedtuple
 
 import numpy as np
@@ -124,6 +125,31 @@ class Roformer(ParamTree):
             raise NotImplementedError("only right-padded batches are built: every attention_mask row must be ones followed by zeros")
         return n.to(torch.int32).contiguous()
 
+    def _check_prompt(self, B, semantic_prompt, prompt_attention_mask, max_length, num_beams):
+        """the checks of `generate`'s decoder prompt (no device work beyond reading the prompt itself) -> the rows' lengths as a list of ints"""
+        if num_beams > 1:
+            # the beams' key/value ancestry tables start at BOS: a prefix would have to be replicated per beam first
+            raise NotImplementedError("beam search from a prompt (num_beams > 1 with semantic_prompt) is not built")
+        if semantic_prompt.dim() != 2 or semantic_prompt.shape[0] != B or semantic_prompt.shape[1] < 1:
+            raise ValueError(f"semantic_prompt must be [B, P] with B = {B} and P >= 1, got {tuple(semantic_prompt.shape)}")
+        if B > 64:
+            raise ValueError(f"a prompted decode takes at most 64 rows, got {B}")
+        P = int(semantic_prompt.shape[1])
+        if prompt_attention_mask is not None and tuple(prompt_attention_mask.shape) != (B, P):
+            raise ValueError(f"prompt_attention_mask must have semantic_prompt's shape {(B, P)}, got {tuple(prompt_attention_mask.shape)}")
+        n = self._mask_to_lengths(prompt_attention_mask)
+        lens = [P] * B if n is None else [int(v) for v in n.tolist()]
+        sp = semantic_prompt.detach().to("cpu", torch.int64)
+        for b, pl in enumerate(lens):
+            if pl >= max_length:      # HF raises ValueError as well: max_length counts the prompt
+                raise ValueError(f"row {b}: the prompt has {pl} tokens, which leaves no room below max_length = {max_length} (the total length)")
+            if int(sp[b, 0]) != self.semantic_bos_token_id:
+                raise ValueError(f"row {b}: semantic_prompt must start with BOS ({self.semantic_bos_token_id}), got {int(sp[b, 0])}")
+            body = sp[b, 1:pl]
+            if bool(((body < 0) | (body >= self.cfg["semantic_kmeans_num"])).any()):
+                raise ValueError(f"row {b}: prompt ids after BOS and inside the length must lie in [0, {self.cfg['semantic_kmeans_num']})")
+        return lens
+
     @torch.no_grad()
     def encode(self, phone, tone, spk_id=None, attention_mask=None):
         """encoder_hidden_states [B,L,hidden] of reference roformer.py:196-214 (rows of padded positions are computed but never read)"""
@@ -132,7 +158,13 @@ class Roformer(ParamTree):
     @torch.no_grad()
     def generate(self, phone, tone, attention_mask=None, use_cache=None, max_length=1024, do_sample=True, temperature=1.0, top_k=5, top_p=0.8,
                  repetition_penalty=1.2, num_beams=1, no_repeat_ngram_size=0, early_stopping=True, spk_id=None, end_gate_threshold=None,
-                 return_logits=False, **kwargs):
+                 return_logits=False, semantic_prompt=None, prompt_attention_mask=None, uniforms=None, **kwargs):
+        """The reference's `generate` (roformer.py:179-244), plus the decoder prompt its HF call accepts as input_ids= (roformer.py:235-242):
+        semantic_prompt [B,P] int64, BOS first like `score`'s `semantic`, right-padded with prompt_attention_mask [B,P] (ones then zeros) when the
+        rows' prompts differ in length.  Every row continues its own prompt exactly as it would alone; max_length is the total length, prompt
+        included (HF); the returned rows start with the prompt; the repetition penalty and the n-gram ban see the prompt as history.
+        uniforms [max_length - 1, B] (sampling): row b's s-th generated token uses uniforms[s][b]; None draws them with torch.rand as always.
+        With return_logits, logits[s][b] are the logits that chose row b's s-th generated token."""
         if end_gate_threshold is not None:
             # reference roformer.py:49-57 sets the WHOLE score row to +inf once softmax(scores)[eos] passes the threshold: greedy then picks
             # token 0 and sampling makes torch.multinomial raise on NaN probabilities -- there is no coherent behaviour to restate
@@ -157,11 +189,31 @@ class Roformer(ParamTree):
         if do_sample and not (0 <= top_k <= 64):
             raise NotImplementedError("sampling is built for top_k = None / 0 (no filter) or 1 <= top_k <= 64")
         enc_len = self._mask_to_lengths(attention_mask)      # reference roformer.py:209-236: the encoder's mask and the cross-attention's
+        prompt_len = None
+        if semantic_prompt is None and prompt_attention_mask is not None:
+            raise ValueError("prompt_attention_mask needs semantic_prompt")
+        if semantic_prompt is not None:      # everything about the prompt is checked before any device work
+            prompt_len = self._check_prompt(phone.shape[0], semantic_prompt, prompt_attention_mask, max_length, num_beams)
         if not phone.is_cuda:
             raise RuntimeError("Roformer.generate needs tensors on a HIP device (no CPU fallback)")
         enc = self.native().encode(phone, tone, spk_id if self.spk_emb_enabled else None, enc_len)
         B = enc.shape[0]
-        uniforms = torch.rand(max_length - 1, B, device=enc.device) if do_sample else None      # one draw per step and sequence
+        if not do_sample:
+            uniforms = None
+        elif uniforms is None:
+            uniforms = torch.rand(max_length - 1, B, device=enc.device)      # one draw per step and sequence
+        else:
+            uniforms = uniforms.to(device=enc.device, dtype=torch.float32)
+            if uniforms.dim() != 2 or uniforms.shape[1] != B or uniforms.shape[0] < max_length - (min(prompt_len) if prompt_len else 1):
+                raise ValueError(f"uniforms must be [steps, B = {B}] with one row per generated position, got {tuple(uniforms.shape)}")
+            if uniforms.shape[0] < max_length - 1:      # the library's layout is [max_length - 1, B]; the rows past the last step are never read
+                uniforms = torch.cat([uniforms, uniforms.new_zeros(max_length - 1 - uniforms.shape[0], B)])
+        if prompt_len is not None:
+            P = max(prompt_len)
+            prompt = semantic_prompt[:, :P].to(device=enc.device, dtype=torch.int64)
+            toks, logits = self.native().generate_prompt(enc, prompt, prompt_len, max_length, do_sample, top_k, top_p, temperature, repetition_penalty,
+                                                         uniforms, return_logits, enc_len, no_repeat_ngram_size=no_repeat_ngram_size)
+            return (toks, logits) if return_logits else toks
         # beams: enc and enc_len stay one row per item; the library maps beam row r to item r // num_beams
         toks, logits = self.native().generate(enc, max_length, do_sample, top_k, top_p, temperature, repetition_penalty, uniforms, return_logits, enc_len,
                                               num_beams=num_beams, no_repeat_ngram_size=no_repeat_ngram_size, early_stopping=early_stopping)

@@ -8,7 +8,12 @@
                        decode of the same length, next to that decode: the only other way to visit those positions.  Both as the
                        time between two events on the stream (median of --reps), in the same process; --json FILE keeps the rows.
 
-With --num_beams > 1, --greedy, --score or more than one length the EOS logit is biased far down, so that every sequence runs to the
+  --prompt P [P ...]   time a prompted decode (Roformer.generate(semantic_prompt=...)): P prompt tokens (BOS included), then --new tokens,
+                       next to the unprompted decode to the same total length, which visits the prompt's P - 1 extra positions step by
+                       step: the difference is what the causal prefill saves.  With --batch 8 also one ragged batch whose prompt lengths
+                       run from 64 to the largest P.  Greedy; event time on the stream, median of --reps; --json FILE keeps the rows.
+
+With --num_beams > 1, --greedy, --score, --prompt or more than one length the EOS logit is biased far down, so that every sequence runs to the
 full length and the time per step is that of a full decode."""
 import argparse
 import ctypes
@@ -33,6 +38,8 @@ ap.add_argument("--no_repeat_ngram_size", type=int, default=0)
 ap.add_argument("--tokens", type=int, nargs="*", default=[512])
 ap.add_argument("--lib", default=None)
 ap.add_argument("--score", action="store_true")
+ap.add_argument("--prompt", type=int, nargs="*", default=[])
+ap.add_argument("--new", type=int, default=64)
 ap.add_argument("--reps", type=int, default=5)
 ap.add_argument("--json", default=None)
 a = ap.parse_args()
@@ -43,7 +50,7 @@ if a.lib:
     native.TEST_EXPORTS = [n for n in native.TEST_EXPORTS if hasattr(have, n)]
 
 lm = infer_tts.synthetic_lm("cuda")
-if a.num_beams > 1 or a.greedy or a.score or len(a.tokens) > 1:
+if a.num_beams > 1 or a.greedy or a.score or a.prompt or len(a.tokens) > 1:
     with torch.no_grad():
         lm.semantic_decoder.cls.predictions.bias[lm.semantic_eos_token_id] -= 1.0e4
 mode = f"beam search K {a.num_beams}" if a.num_beams > 1 else "greedy" if a.greedy else "sampled"
@@ -89,6 +96,45 @@ def score_mode():
         json.dump({"what": "one lds_lm_score call vs the cached decode of the same tokens (greedy, EOS biased down), event time on the stream, "
                            f"median of {a.reps}", "rows": rows}, open(a.json, "w"), indent=1)
 
+
+def prompt_mode():
+    rows = []
+    rng = np.random.default_rng(0)
+
+    def prompted(ph, tn, prompt, pmask, total):
+        return lm.generate(ph, tn, attention_mask=None, max_length=total, do_sample=False, temperature=1.0, top_k=5, top_p=1.0, repetition_penalty=1.0,
+                           spk_id=torch.ones_like(ph), semantic_prompt=prompt, prompt_attention_mask=pmask)
+
+    for B in a.batch:
+        ph = torch.from_numpy((np.arange(B * 64).reshape(B, 64) * 7 % 107 + 1).astype(np.int64)).cuda()
+        tn = torch.from_numpy((np.arange(B * 64).reshape(B, 64) * 5 % 12).astype(np.int64)).cuda()
+        cases = [(P, [P] * B) for P in a.prompt]
+        if B > 1 and max(a.prompt) > 64:
+            cases.append((max(a.prompt), [int(v) for v in np.linspace(64, max(a.prompt), B).round()]))
+        for P, lens in cases:
+            sem = rng.integers(0, lm.cfg["semantic_kmeans_num"], size=(B, P)).astype(np.int64)
+            sem[:, 0] = lm.semantic_bos_token_id
+            prompt = torch.from_numpy(sem).cuda()
+            pmask = (torch.arange(P).cuda()[None] < torch.tensor(lens).cuda()[:, None]).to(torch.int64)
+            total = P + a.new
+            decode(ph, tn, 64)
+            prompted(ph, tn, prompt, pmask, total)
+            pr_ms, tok = event_ms(lambda: prompted(ph, tn, prompt, pmask, total), a.reps)
+            un_ms, tok0 = event_ms(lambda: decode(ph, tn, total - 1), a.reps)
+            assert tok.shape == tok0.shape == (B, total), (tok.shape, tok0.shape)
+            rows.append({"B": B, "prompt_lengths": sorted(set(lens)), "new_tokens": a.new, "total": total, "prompted_ms": pr_ms, "unprompted_same_total_ms": un_ms,
+                         "steps_prompted": total - min(lens), "steps_unprompted": total - 1, "saved_ms": un_ms - pr_ms})
+            print(rows[-1])
+    if a.json:
+        import json
+        json.dump({"what": "a prompted greedy decode (causal prefill of the prompt, then the per-row decode steps) vs the unprompted decode to the same total "
+                           f"length, EOS biased down, event time on the stream, median of {a.reps}", "rows": rows}, open(a.json, "w"), indent=1)
+
+
+if a.prompt:
+    a.greedy = True
+    prompt_mode()
+    sys.exit(0)
 
 if a.score:
     a.greedy = True
