@@ -461,6 +461,42 @@ int lds_lm_score(lds_lm* lm, const float* enc, const int32_t* enc_len, int B, in
                  const int64_t* labels, int T, float* logprobs, int32_t* ranks, float* loss, int32_t* n_counted, float* logits_out, void* ws,
                  size_t ws_bytes, void* stream);
 
+/* ---- text2semantic, the second LM: a decoder-only Llama over one token stream (reference text2semantic/llama/llama.py:23-184 over HF transformers
+ *      LlamaForCausalLM + GenerationMixin): [phone BOS, phones, phone EOS, semantic BOS, semantic tokens ...].  RMSNorm, bias-free projections with
+ *      grouped-query attention (query head h reads kv head h / (heads / kv_heads)), rotary embedding in the half-split convention (element i pairs
+ *      with i + head_dim / 2; default rope, the angle an fp32 product of position and inv_freq), SwiGLU MLP, untied head.  Everything fp32. ------- */
+typedef struct lds_llama lds_llama;
+/* llama.py:23-65: hidden .. max_pos, eps (rms_norm_eps), rope_theta are LlamaConfig's; vocab = len(symbols) + semantic_kmeans_num + 3;
+ * first_free_id = semantic_token_shift (108): llama.py:170 bans every id below it (bad_words_ids), so the head computes the columns
+ * first_free_id .. vocab only; bos / eos / pad = the config's ids (llama.py:56-58), inside those columns. */
+typedef struct lds_llama_cfg { int hidden, heads, kv_heads, head_dim, inter, layers, vocab, max_pos; float eps, rope_theta; int first_free_id, bos, eos, pad; } lds_llama_cfg;
+/* names = the reference Llama.state_dict() keys (llama.py:65: llama.model.embed_tokens.weight, llama.model.layers.N.{self_attn.{q,k,v,o}_proj,
+ * mlp.{gate,up,down}_proj,input_layernorm,post_attention_layernorm}.weight, llama.model.norm.weight, llama.lm_head.weight), fp32 host arrays; a
+ * missing one gives LDS_EMISSING naming it.  Optional: llama.model.rotary_emb.inv_freq [head_dim / 2], HF's own inverse frequencies (absent: powf).
+ * Limits (LDS_EINVAL): head_dim a multiple of 16 in 16 .. 256; kv_heads divides heads; hidden <= 2048; inter and heads * head_dim <= 3840;
+ * vocab - first_free_id <= 8192 (the token-choice kernels' columns). */
+int  lds_llama_create(const lds_llama_cfg* cfg, int n_tensors, const char* const* names, const float* const* host_ptrs, const int64_t* numel, lds_llama** out);
+void lds_llama_destroy(lds_llama* h);
+int  lds_llama_workspace_bytes(const lds_llama* h, int B, int P, int max_length, size_t* out);
+/* Llama.generate (llama.py:121-184; the reference can only do B = 1, llama.py:148) for num_beams 1: greedy, or HF's order per step on the raw logits of
+ * the last position -- repetition penalty, n-gram ban (both over the WHOLE input_ids, phones included), the bad-word ban of the ids below
+ * first_free_id (llama.py:170), temperature, top-k, top-p, one draw -- through the token-choice kernels of lds_lm_generate_prompt.
+ *   input_ids dev int64 [B][P]: row b = its in_len[b] prompt ids (llama.py:148-152: [BOS, phones, EOS, semantic BOS]; any prefix of generated ids may
+ *     follow), right-padded to P.  Ids are clamped to [0, vocab) on the way in; ids at and beyond in_len[b] are never looked at.
+ *   in_len HOST int32 [B] or NULL = P everywhere; 1 <= in_len[b] <= P and in_len[b] < max_length (the TOTAL length, prompt included, as in HF).
+ *   opts: lds_lm_decode_opts with num_beams 1.  uniforms dev [max_length-1][B] (sampling): row b's s-th generated token uses uniforms[s][b].
+ *   tokens dev int64 [B][max_length]: the prompt, then the generated ids of the model's vocabulary (not shifted; llama.py:182 subtracts the shift), EOS
+ *     kept, PAD after it.  logits_out optional dev [max_length-1][B][vocab - first_free_id]: HF's raw logits (before any processor) of the columns
+ *     first_free_id .. vocab that chose row b's s-th generated token.  *n_tokens_host = the longest row's length.
+ * One causal pass over the prompts' positions but the last fills the key/value caches (kv_heads of them per row), then the decode continues step by
+ * step; prefill rows and decode steps run the same kernels, so a row equals that row run alone and a call continued from a longer prefix, tokens and
+ * logits bit for bit.  The workspace's contents on entry do not matter.  The call synchronises the stream every 8 steps to poll for EOS.
+ * Limits (LDS_EINVAL with a message before anything is enqueued): num_beams 1 (beam search is not built: HF's log_softmax runs over the whole
+ * vocabulary, banned columns included); B <= 64; P and max_length <= 15000; max_length <= max_pos; the lds_lm_decode_opts checks of
+ * lds_lm_generate_opts.  A workspace smaller than lds_llama_workspace_bytes(B, P, max_length) gives LDS_ENOMEM with the size needed. */
+int  lds_llama_generate(lds_llama* h, const int64_t* input_ids, const int32_t* in_len, int B, int P, int max_length, const lds_lm_decode_opts* opts,
+                        const float* uniforms, int64_t* tokens, float* logits_out, int* n_tokens_host, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- k-means semantic tokenizer: units -> tokens and the codebook fit (reference cluster/__init__.py:13-23 get_cluster_result /
  *      get_cluster_center_result, cluster/kmeans.py:10-50 _kpp, :108-131 euc_sim / max_sim, :184-198 the Lloyd step; called from
  *      17_preprocess_train_cluster.py and 19_preprocess_token.py) -------------------------------------------------------------------

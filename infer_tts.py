@@ -53,6 +53,8 @@ def parse_args(argv=None):
     ap.add_argument("--latency_mode", action="store_true",
                     help="one sentence per call: tile shapes / reduction splits from the actual batch (include/lds.h lds_unet_set_latency_mode)")
     ap.add_argument("--gemm_mode", default="f32", choices=["f32", "split_f16"], help="the UNet's GEMMs (include/lds.h lds_unet_set_gemm_mode)")
+    ap.add_argument("--lm_type", default="roformer", choices=("roformer", "llama"),
+                    help="which seeded LM --synthetic builds: the RoFormer encoder / decoder or the decoder-only Llama (a checkpoint's config.yaml names its own)")
     ap.add_argument("--synthetic", action="store_true")
     ap.add_argument("--synthetic_tokens", type=int, default=256)
     return ap.parse_args(argv)
@@ -93,6 +95,14 @@ def synthetic_lm(dev):
               max_position_embeddings=c["max_pos"], layer_norm_eps=c["eps"])
     return Roformer(dict(hf, num_hidden_layers=c["enc_layers"]), dict(hf, num_hidden_layers=c["dec_layers"]), mode="phone",
                     semantic_kmeans_num=c["semantic_kmeans_num"], codebook_path="", n_spk=c["n_spk"]).to(dev).eval()
+
+
+def synthetic_llama(dev):
+    """seeded random-init decoder-only text2semantic model: the width of the reference's own example (llama.py:186-193: hidden 768, 4 heads,
+    4 layers, intermediate 512) over the synthetic codebook's 4096 tokens"""
+    from text2semantic.llama.llama import Llama
+    return Llama(dict(hidden_size=768, num_attention_heads=4, num_hidden_layers=4, intermediate_size=512, max_position_embeddings=2048),
+                 mode="phone", semantic_kmeans_num=4096, codebook_path="").to(dev).eval()
 
 
 def load_lm(path, dev):
@@ -145,6 +155,16 @@ def text2semantic(lm, phones, tones, spk_id=1, max_length=1024, num_beams=1, no_
         raise ValueError("rows of a batch ended at different lengths (EOS / PAD ids in the result): use text2semantic_rows, which cuts every "
                          "row at its own EOS, and synthesize_ragged")
     return tok[:, first:]
+
+
+def text2semantic_llama(lm, phones, tones, spk_id=1, max_length=1024, no_repeat_ngram_size=0):
+    """`text2semantic` for the decoder-only Llama (reference llama.py:121-184): its generate returns the generated semantic ids alone (no BOS in
+    front, the shift subtracted); max_length counts the L + 3 prompt ids.  One utterance: phones, tones [1, L]."""
+    tok = lm.generate(phones, tones, attention_mask=None, use_cache=None, max_length=max_length, do_sample=True, temperature=1.0, top_k=5, top_p=1.0,
+                      repetition_penalty=1.0, num_beams=1, no_repeat_ngram_size=no_repeat_ngram_size, early_stopping=True,
+                      spk_id=torch.ones_like(phones) * spk_id, end_gate_threshold=None)
+    eos = lm.config.eos_token_id - lm.semantic_token_shift
+    return tok[:, :-1] if bool((tok[:, -1] == eos).all()) else tok
 
 
 def pick_candidate(lm, phones, tones, tok, spk_id=1, prompt_len=1):
@@ -385,7 +405,7 @@ def main(argv=None):
     if a.synthetic:
         svc, codebook, tokens = synthetic_pipeline(dev, a.synthetic_tokens)
         if a.phones:
-            lm = synthetic_lm(dev)
+            lm = synthetic_llama(dev) if a.lm_type == "llama" else synthetic_lm(dev)
     else:
         from tools.infer_tools import DiffusionSVC
         svc = DiffusionSVC(device=dev)
@@ -403,6 +423,8 @@ def main(argv=None):
         if a.candidates < 1 or (a.candidates > 1 and a.num_beams != 1):
             raise SystemExit("--candidates needs N >= 1 and, for N > 1, sampling (--num_beams 1)")
         prompt = {}
+        if hasattr(lm, "llama") and (a.prompt_tokens or a.prompt_audio or a.prompt_phones or a.candidates > 1 or a.num_beams > 1):
+            raise SystemExit("the Llama LM takes --phones alone: prompts, --candidates and --num_beams are the RoFormer's")
         if a.prompt_tokens and a.prompt_audio:
             raise SystemExit("--prompt_tokens and --prompt_audio both name the prompt: give one")
         if a.prompt_phones:
@@ -410,7 +432,9 @@ def main(argv=None):
         if a.prompt_tokens or a.prompt_audio:
             ptok = torch.from_numpy(np.load(a.prompt_tokens).astype(np.int64)).to(dev) if a.prompt_tokens else tokens_from_audio(a, codebook, dev)
             prompt = dict(semantic_prompt=with_bos(lm, ptok), keep_prompt=a.keep_prompt)
-        if a.candidates > 1:
+        if hasattr(lm, "llama"):      # the decoder-only LM: sampling from the phones alone
+            tokens = text2semantic_llama(lm, pt[0:1], pt[1:2], a.spk_id, a.max_length, a.no_repeat_ngram_size)
+        elif a.candidates > 1:
             tokens = text2semantic_candidates(lm, pt[0:1], pt[1:2], a.spk_id, a.max_length, a.candidates, a.no_repeat_ngram_size, **prompt)
         else:
             tokens = text2semantic(lm, pt[0:1], pt[1:2], a.spk_id, a.max_length, a.num_beams, a.no_repeat_ngram_size, **prompt)

@@ -1,0 +1,617 @@
+// text2semantic Llama on gfx950 (reference text2semantic/llama/llama.py:23-184 over HF transformers LlamaForCausalLM + GenerationMixin): a
+// decoder-only LM over one token stream [phone BOS, phones, phone EOS, semantic BOS, semantic tokens ...].  One causal prefill of the prompts
+// fills the key/value caches, then the cached decode continues row by row; the token choice is lm.hip's (lm_common.h).
+// Everything is fp32 and follows lm.hip's rules: one fixed-order accumulation per output that depends neither on the batch size nor on whether
+// a row is a prefill row or a decode step (both go through the SAME kernels, a row's position being the only thing that tells them apart), no
+// atomics, the whole decode loop on the stream with an EOS poll every 8 steps.
+//   RMSNorm        (x * rsqrt(mean(x^2) + eps)) * w, fused into the consuming linear: the mean of squares is a lane-strided sum + the DPP tree
+//   linear         weights transposed [K][M]; a workgroup = 64 columns x 16 K-slices over 8 rows staged in LDS; every slice is one ascending
+//                  fmaf chain, the slices meet through LDS in the order 0, 1, .. 15
+//   q | k | v      one projection; the epilogue rotates q and k in the half-split convention (element i pairs with i + d/2) at the row's own
+//                  position and writes k, v into the row's cache slot: caches are [B][kv_heads][cap][d]
+//   attention      one workgroup per (row, query head) over the keys 0 .. pos of kv head h / (heads / kv_heads)
+//   MLP            gate and up in one pass with silu(g) * u in the epilogue; down and o_proj add the residual in theirs
+//   head           the final norm fused in; only the columns first_free_id .. vocab (the bad-word ban makes the others unobservable)
+#include "../../include/lds.h"
+#include "kernels.h"
+#include "lm_common.h"
+
+#include <math.h>
+#include <stdio.h>
+#include <string.h>
+
+#include <map>
+#include <string>
+#include <vector>
+
+namespace lds {
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+// Which (batch row, position) row n of a pass is.  L > 0: the prefill, n = b * L + l at position l.  L == 0: a decode step, row b at position
+// plen[b] - 1 + step; a row that has run past the cache (it reached max_length at an earlier step) is not live and stores nothing.
+struct LlRows { const int32_t* plen; int L, step, cap; };
+static __device__ __forceinline__ void ll_row(const LlRows& r, int n, int& b, int& pos, bool& live) {
+    if (r.L > 0) {
+        b = n / r.L; pos = n - b * r.L; live = true;
+    } else {
+        b = n; pos = r.plen[b] - 1 + r.step;
+        live = pos < r.cap;
+        pos = live ? pos : r.cap - 1;      // (its table row and token slot only have to exist)
+    }
+}
+
+// the start of a decode, one workgroup per row: stok[b] = the row's ids, clamped to the vocabulary and shifted by -shift (the token-choice kernels'
+// column numbering: phone ids turn negative), PAD (shifted) from plen[b] on -- ids beyond a row's length are never looked at
+__global__ void __launch_bounds__(256) ll_init_kernel(const int64_t* __restrict__ ids, int P, const int32_t* __restrict__ plen, int vocab, int shift, int pad_s,
+                                                      int cap, int64_t* __restrict__ stok) {
+    const int b = blockIdx.x, pl = plen[b];
+    for (int l = threadIdx.x; l < cap; l += 256) {
+        long long t = pad_s;
+        if (l < pl && l < P) {
+            t = ids[(long long)b * P + l];
+            t = (t < 0) ? 0 : (t >= vocab ? vocab - 1 : t);
+            t -= shift;
+        }
+        stok[(long long)b * cap + l] = t;
+    }
+}
+// tokens = stok + shift: the ids of the model's vocabulary again
+__global__ void __launch_bounds__(256) ll_finish_kernel(const int64_t* __restrict__ stok, long long n, int shift, int64_t* __restrict__ tokens) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) tokens[i] = stok[i] + shift;
+}
+// x[n] = embed_tokens[id of row n], ids clamped
+__global__ void __launch_bounds__(256) ll_embed_kernel(const float* __restrict__ emb, const int64_t* __restrict__ stok, const LlRows rows, int shift, int vocab,
+                                                       int H, float* __restrict__ x) {
+    const int n = blockIdx.x;
+    int b, pos;
+    bool live;
+    ll_row(rows, n, b, pos, live);
+    long long t = stok[(long long)b * rows.cap + pos] + shift;
+    t = (t < 0) ? 0 : (t >= vocab ? vocab - 1 : t);
+    for (int c = threadIdx.x; c < H; c += 256) x[(long long)n * H + c] = emb[t * H + c];
+}
+
+// ---- Y[n][m] = epi(sum_k rms(X)[n][k] * Wt[k][m]) for a tile of 8 rows per workgroup (lm_linear_dln_kernel's shape: 64 columns x 16 K-slices,
+//      the staged rows normalised in LDS when nw != null).  K is arbitrary: slice s walks k in [s * ceil(K / 16), ...) ascending.
+//      LL_RESID: + R[n][m] (R may be Y).  LL_SWIGLU: Wt = gate, Wt2 = up, y = silu(g) * u.
+//      LL_ROPE: the q | k | v projection.  The first column blocks hold 32 rotation pairs each -- lane c < 32 element i of a head, lane c + 32
+//      its partner i + d/2 -- so the partner's value is one cross-lane move away whatever d is; the remaining blocks are v's plain columns. ----
+enum { LL_PLAIN = 0, LL_RESID = 1, LL_SWIGLU = 2, LL_ROPE = 3 };
+struct LlRope { const float* cs; float* kc; float* vc; int heads, kv_heads, d; LlRows rows; };      // cs [max_pos][d]: cos[d/2] | sin[d/2]
+constexpr int kLlCols = 64, kLlSlices = 16;
+
+template <int EPI>
+__global__ void __launch_bounds__(1024) ll_linear_kernel(const float* __restrict__ X, int K, const float* __restrict__ nw, float eps, const float* __restrict__ Wt,
+                                                        const float* __restrict__ Wt2, int M, const float* R, float* Y, int ldy, int N, const LlRope rope) {
+    constexpr int COLS = kLlCols, KS = kLlSlices, NP = (EPI == LL_SWIGLU) ? 2 : 1;
+    extern __shared__ __attribute__((aligned(16))) float sm[];      // xs [K][8], part [NP][KS-1][COLS][8], rstd [8]
+    float* xs = sm;
+    float* part = sm + (size_t)K * 8;
+    float* rstd_s = part + (size_t)NP * (KS - 1) * COLS * 8;
+    const int tid = threadIdx.x, col = tid % COLS, ks = tid / COLS, lane = tid & 63, wave = tid >> 6;
+    const int n0 = blockIdx.y * 8;
+    // the column this thread owns
+    int m;
+    bool valid;
+    int hq = 0, ri = 0, half = 0, npb = 0;
+    if constexpr (EPI == LL_ROPE) {
+        const int hd = rope.d >> 1, npairs = (rope.heads + rope.kv_heads) * hd;
+        npb = (npairs + 31) / 32;
+        if ((int)blockIdx.x < npb) {
+            const int p = blockIdx.x * 32 + (col & 31);
+            valid = p < npairs;
+            hq = p / hd; ri = p - hq * hd; half = col >> 5;
+            m = hq * rope.d + ri + half * hd;
+        } else {
+            const int vcol = (blockIdx.x - npb) * COLS + col;
+            valid = vcol < rope.kv_heads * rope.d;
+            m = (rope.heads + rope.kv_heads) * rope.d + vcol;
+        }
+    } else {
+        m = blockIdx.x * COLS + col;
+        valid = m < M;
+    }
+    for (int i = tid; i < K * 8; i += 1024) {
+        const int k = i >> 3, j = i & 7;
+        xs[i] = (n0 + j < N) ? X[(long long)(n0 + j) * K + k] : 0.f;
+    }
+    __syncthreads();
+    if (nw) {      // RMSNorm of the staged rows: wave j owns row j (lane-strided sum of squares, DPP tree), then every thread scales
+        if (wave < 8) {
+            float ss = 0.f;
+            for (int k = lane; k < K; k += 64) { const float v = xs[8 * k + wave]; ss = fmaf(v, v, ss); }
+            ss = wave_sum(ss);
+            if (lane == 0) rstd_s[wave] = 1.0f / sqrtf(ss / (float)K + eps);
+        }
+        __syncthreads();
+        float rs[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) rs[j] = rstd_s[j];
+        for (int k = tid; k < K; k += 1024) {
+            const float wk = nw[k];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) xs[8 * k + j] = (xs[8 * k + j] * rs[j]) * wk;
+        }
+        __syncthreads();
+    }
+    float acc[NP][8];
+#pragma unroll
+    for (int p = 0; p < NP; ++p)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) acc[p][j] = 0.f;
+    const int kq = (K + KS - 1) / KS, k0 = ks * kq, k1 = (k0 + kq < K) ? k0 + kq : K;
+    if (valid) {
+        const float* wp = Wt + m;
+        const float* wp2 = (EPI == LL_SWIGLU) ? Wt2 + m : nullptr;
+        int k = k0;
+        for (; k + 8 <= k1; k += 8) {
+            float w[NP][8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                w[0][u] = wp[(long long)(k + u) * M];
+                if constexpr (EPI == LL_SWIGLU) w[NP - 1][u] = wp2[(long long)(k + u) * M];
+            }
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const f32x4 a = *reinterpret_cast<const f32x4*>(xs + 8 * (k + u)), b = *reinterpret_cast<const f32x4*>(xs + 8 * (k + u) + 4);
+#pragma unroll
+                for (int p = 0; p < NP; ++p) {
+                    acc[p][0] = fmaf(w[p][u], a[0], acc[p][0]); acc[p][1] = fmaf(w[p][u], a[1], acc[p][1]);
+                    acc[p][2] = fmaf(w[p][u], a[2], acc[p][2]); acc[p][3] = fmaf(w[p][u], a[3], acc[p][3]);
+                    acc[p][4] = fmaf(w[p][u], b[0], acc[p][4]); acc[p][5] = fmaf(w[p][u], b[1], acc[p][5]);
+                    acc[p][6] = fmaf(w[p][u], b[2], acc[p][6]); acc[p][7] = fmaf(w[p][u], b[3], acc[p][7]);
+                }
+            }
+        }
+        for (; k < k1; ++k) {
+            const f32x4 a = *reinterpret_cast<const f32x4*>(xs + 8 * k), b = *reinterpret_cast<const f32x4*>(xs + 8 * k + 4);
+#pragma unroll
+            for (int p = 0; p < NP; ++p) {
+                const float w = (p == 0) ? wp[(long long)k * M] : wp2[(long long)k * M];
+                acc[p][0] = fmaf(w, a[0], acc[p][0]); acc[p][1] = fmaf(w, a[1], acc[p][1]); acc[p][2] = fmaf(w, a[2], acc[p][2]); acc[p][3] = fmaf(w, a[3], acc[p][3]);
+                acc[p][4] = fmaf(w, b[0], acc[p][4]); acc[p][5] = fmaf(w, b[1], acc[p][5]); acc[p][6] = fmaf(w, b[2], acc[p][6]); acc[p][7] = fmaf(w, b[3], acc[p][7]);
+            }
+        }
+    }
+    if (ks > 0) {
+#pragma unroll
+        for (int p = 0; p < NP; ++p)
+#pragma unroll
+            for (int j = 0; j < 8; ++j) part[(((size_t)p * (KS - 1) + ks - 1) * COLS + col) * 8 + j] = acc[p][j];
+    }
+    __syncthreads();
+    if (ks > 0) return;      // slice 0 is exactly wave 0
+#pragma unroll
+    for (int p = 0; p < NP; ++p)
+#pragma unroll 1
+        for (int q = 0; q < KS - 1; ++q) {
+            const float* pp = part + (((size_t)p * (KS - 1) + q) * COLS + col) * 8;
+            const f32x4 a = *reinterpret_cast<const f32x4*>(pp), b = *reinterpret_cast<const f32x4*>(pp + 4);
+            acc[p][0] += a[0]; acc[p][1] += a[1]; acc[p][2] += a[2]; acc[p][3] += a[3];
+            acc[p][4] += b[0]; acc[p][5] += b[1]; acc[p][6] += b[2]; acc[p][7] += b[3];
+        }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const int n = n0 + j;
+        const bool ok = valid && n < N;
+        float y = acc[0][j];
+        if constexpr (EPI == LL_SWIGLU) y = (y / (1.0f + expf(-y))) * acc[NP - 1][j];
+        if constexpr (EPI == LL_ROPE) {
+            int b, pos;
+            bool live;
+            ll_row(rope.rows, n < N ? n : n0, b, pos, live);
+            const float other = __shfl_xor(y, 32, 64);      // (all of wave 0 takes part; only the pair blocks use it)
+            const int d = rope.d, hd = d >> 1;
+            if ((int)blockIdx.x < npb) {
+                const float cs = valid ? rope.cs[(long long)pos * d + ri] : 0.f, sn = valid ? rope.cs[(long long)pos * d + hd + ri] : 0.f;
+                // HF apply_rotary_pos_emb: x * cos + rotate_half(x) * sin, rotate_half(x) = [-x2 | x1]
+                const float rot = half ? y * cs + other * sn : y * cs - other * sn;
+                if (ok && live) {
+                    if (hq < rope.heads) Y[(long long)n * ldy + m] = rot;
+                    else rope.kc[(((long long)b * rope.kv_heads + (hq - rope.heads)) * rope.rows.cap + pos) * d + ri + half * hd] = rot;
+                }
+            } else if (ok && live) {
+                const int vcol = m - (rope.heads + rope.kv_heads) * d, hv = vcol / d;
+                rope.vc[(((long long)b * rope.kv_heads + hv) * rope.rows.cap + pos) * d + (vcol - hv * d)] = y;
+            }
+        } else {
+            if constexpr (EPI == LL_RESID) { if (ok) y += R[(long long)n * M + m]; }
+            if (ok) Y[(long long)n * ldy + m] = y;
+        }
+    }
+}
+
+// ---- attention of one (row, query head) per workgroup: softmax(q K^T / sqrt(d)) V over the row's keys 0 .. pos, which its cache holds -- the
+//      causal context, for a prefill row and for a decode step alike, so the arithmetic depends on the position alone.  lm_attn_body's scheme
+//      for head dims up to 256: the four waves take alternate 64-key blocks; phase 1 has a key per lane, phase 2 the channels lane, lane + 64, ..
+//      over the wave's keys in ascending order; the waves' (max, sum, partial output) meet through LDS in the order 0 .. 3.
+//      q, out [N][heads * d]; query head h reads kv head h / (heads / kv_heads). ----
+constexpr int kLlMaxHeadDim = 256;
+__global__ void __launch_bounds__(256) ll_attn_kernel(const float* __restrict__ q, const float* __restrict__ kc, const float* __restrict__ vc, const LlRows rows,
+                                                      int heads, int kv_heads, int d, int Lkp, float* __restrict__ out) {
+    extern __shared__ __attribute__((aligned(16))) float sa[];      // qs [256], sc [Lkp], mrg [4][2 + 256]
+    float* qs = sa;
+    float* sc = sa + kLlMaxHeadDim;
+    float* mrg = sc + Lkp;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int h = blockIdx.x % heads, n = blockIdx.x / heads;
+    int b, pos;
+    bool live;
+    ll_row(rows, n, b, pos, live);
+    const int QD = heads * d, kvh = h / (heads / kv_heads);
+    if (!live) {      // (uniform over the workgroup) a row past its end: zeros, so that what follows in its row stays finite and depends on nothing stale
+        if (tid < d) out[(long long)n * QD + h * d + tid] = 0.f;
+        return;
+    }
+    int Lk = pos + 1;
+    Lk = Lk < Lkp ? Lk : Lkp;
+    if (tid < d) qs[tid] = q[(long long)n * QD + h * d + tid];
+    __syncthreads();
+    const float* kb = kc + ((long long)b * kv_heads + kvh) * rows.cap * d;
+    const float* vb = vc + ((long long)b * kv_heads + kvh) * rows.cap * d;
+    const float scale = 1.0f / sqrtf((float)d);
+    float mx = -INFINITY;
+    for (int k0 = wave * 64; k0 < Lk; k0 += 256) {
+        const int key = k0 + lane;
+        float dot = -INFINITY;
+        if (key < Lk) {
+            dot = 0.f;
+            const f32x4* kr = reinterpret_cast<const f32x4*>(kb + (long long)key * d);
+            const f32x4* q4 = reinterpret_cast<const f32x4*>(qs);
+            for (int e4 = 0; e4 < (d >> 2); e4 += 4) {      // d is a multiple of 16
+                f32x4 kv[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) kv[u] = kr[e4 + u];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const f32x4 qv = q4[e4 + u];
+                    dot = fmaf(qv[0], kv[u][0], dot); dot = fmaf(qv[1], kv[u][1], dot); dot = fmaf(qv[2], kv[u][2], dot); dot = fmaf(qv[3], kv[u][3], dot);
+                }
+            }
+            dot *= scale;
+            sc[key] = dot;
+        }
+        mx = fmaxf(mx, dot);
+    }
+    mx = wave_max(mx);
+    float sum = 0.f;
+    for (int k0 = wave * 64; k0 < Lk; k0 += 256) {
+        const int key = k0 + lane;
+        float p = 0.f;
+        if (key < Lk) { p = expf(sc[key] - mx); sc[key] = p; }
+        sum += p;
+    }
+    sum = wave_sum(sum);
+    __syncthreads();      // the probabilities are in LDS
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int k0 = wave * 64; k0 < Lk; k0 += 256) {
+        const int kend = (k0 + 64 < Lk) ? k0 + 64 : Lk;
+        for (int key = k0; key < kend; ++key) {
+            const float p = sc[key];
+            const float* vr = vb + (long long)key * d;
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                if (lane + 64 * i < d) acc[i] = fmaf(p, vr[lane + 64 * i], acc[i]);
+        }
+    }
+    float* mw = mrg + wave * (2 + kLlMaxHeadDim);
+    if (lane == 0) { mw[0] = mx; mw[1] = sum; }
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+        if (lane + 64 * i < d) mw[2 + lane + 64 * i] = acc[i];
+    __syncthreads();
+    if (tid < d) {
+        constexpr int S = 2 + kLlMaxHeadDim;
+        const float m = fmaxf(fmaxf(mrg[0], mrg[S]), fmaxf(mrg[2 * S], mrg[3 * S]));
+        float tot = 0.f, o = 0.f;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            const float f = (mrg[w * S] > -INFINITY) ? expf(mrg[w * S] - m) : 0.f;
+            tot += mrg[w * S + 1] * f;
+            o += mrg[w * S + 2 + tid] * f;
+        }
+        out[(long long)n * QD + h * d + tid] = o / tot;
+    }
+}
+
+}  // namespace lds
+
+using namespace lds;
+
+// ================================================================================================
+// host side
+// ================================================================================================
+#define ll_fail lds::set_error
+#define LL_HIP(expr)                                                                                                    \
+    do {                                                                                                                \
+        hipError_t e_ = (expr);                                                                                         \
+        if (e_ != hipSuccess) return ll_fail(LDS_EHIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
+    } while (0)
+
+struct LlLayer { float *nw_attn = nullptr, *wqkv = nullptr, *wo = nullptr, *nw_mlp = nullptr, *wgate = nullptr, *wup = nullptr, *wdown = nullptr; };
+struct lds_llama {
+    lds_llama_cfg cfg;
+    std::vector<void*> bufs;
+    float *embed = nullptr, *cs = nullptr, *nw_final = nullptr, *head = nullptr;
+    std::vector<LlLayer> layers;
+    ~lds_llama() { for (void* p : bufs) (void)hipFree(p); }
+    float* up(const std::vector<float>& h) {
+        void* d = nullptr;
+        if (hipMalloc(&d, h.size() * sizeof(float)) != hipSuccess) return nullptr;
+        if (hipMemcpy(d, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(d); return nullptr; }
+        bufs.push_back(d);
+        return (float*)d;
+    }
+};
+
+namespace {
+constexpr int kLlMaxBatch = 64;          // the rows' final lengths live in 64 ints behind the step flags
+constexpr int kLlMaxLength = 15000;      // the attention stages one score per key in LDS
+struct LlTensors {
+    std::map<std::string, std::pair<const float*, int64_t>> m;
+    std::string missing;
+    const float* get(const std::string& k, int64_t n) {
+        auto it = m.find(k);
+        if (it == m.end() || it->second.second != n) { if (missing.empty()) missing = k; return nullptr; }
+        return it->second.first;
+    }
+};
+// reference layout W [M][K] (rows r0 .. r0 + Mper of each) -> transposed [K][M], several matrices concatenated along M
+float* ll_linear_up(lds_llama* L, LlTensors& T, const std::vector<std::pair<std::string, int>>& mats, int K, int r0 = 0, int rows_all = -1) {
+    int M = 0;
+    for (auto& s : mats) M += s.second;
+    std::vector<float> wt((size_t)K * M);
+    int c0 = 0;
+    for (auto& s : mats) {
+        const int full = rows_all < 0 ? s.second : rows_all;
+        const float* w = T.get(s.first, (int64_t)full * K);
+        if (!w) return nullptr;
+        for (int m = 0; m < s.second; ++m)
+            for (int k = 0; k < K; ++k) wt[(size_t)k * M + c0 + m] = w[(size_t)(r0 + m) * K + k];
+        c0 += s.second;
+    }
+    return L->up(wt);
+}
+float* ll_vec_up(lds_llama* L, LlTensors& T, const std::string& k, int64_t n) {
+    const float* p = T.get(k, n);
+    return p ? L->up(std::vector<float>(p, p + n)) : nullptr;
+}
+int ll_check_cfg(const lds_llama_cfg& c) {
+    if (c.hidden < 1 || c.hidden > 2048 || c.inter < 1 || c.inter > 3840 || c.layers < 1 || c.max_pos < 2)
+        return ll_fail(LDS_EINVAL, "unsupported Llama shape (1 <= hidden <= 2048, 1 <= intermediate size <= 3840, layers >= 1, max_position_embeddings >= 2)");
+    if (c.head_dim < 16 || c.head_dim > kLlMaxHeadDim || c.head_dim % 16) return ll_fail(LDS_EINVAL, "head_dim %d must be a multiple of 16 in 16 .. %d", c.head_dim, kLlMaxHeadDim);
+    if (c.heads < 1 || c.kv_heads < 1 || c.heads % c.kv_heads) return ll_fail(LDS_EINVAL, "num_key_value_heads %d must divide num_attention_heads %d", c.kv_heads, c.heads);
+    if ((long long)c.heads * c.head_dim > 3840) return ll_fail(LDS_EINVAL, "heads * head_dim = %lld too wide (<= 3840)", (long long)c.heads * c.head_dim);
+    if (c.first_free_id < 0 || c.vocab <= c.first_free_id || c.vocab - c.first_free_id > kLmMaxChoiceVocab)
+        return ll_fail(LDS_EINVAL, "the token choice takes 1 .. %d columns (vocab %d - first_free_id %d)", kLmMaxChoiceVocab, c.vocab, c.first_free_id);
+    for (int id : {c.bos, c.eos, c.pad})
+        if (id < c.first_free_id || id >= c.vocab) return ll_fail(LDS_EINVAL, "bos / eos / pad id %d outside [first_free_id, vocab)", id);
+    if (!(c.eps > 0.f) || !(c.rope_theta > 0.f)) return ll_fail(LDS_EINVAL, "rms_norm_eps and rope_theta must be positive");
+    return LDS_OK;
+}
+}  // namespace
+
+extern "C" int lds_llama_create(const lds_llama_cfg* cfg, int n, const char* const* names, const float* const* ptrs, const int64_t* numel, lds_llama** out) {
+    if (!cfg || !names || !ptrs || !numel || !out || n < 0) return ll_fail(LDS_EINVAL, "null argument");
+    if (int r = ll_check_cfg(*cfg)) return r;
+    const lds_llama_cfg& c = *cfg;
+    LlTensors T;
+    for (int i = 0; i < n; ++i) T.m[names[i]] = {ptrs[i], numel[i]};
+    lds_llama* L = new lds_llama();
+    L->cfg = c;
+    const int H = c.hidden, d = c.head_dim, QD = c.heads * d, KD = c.kv_heads * d, hd = d / 2;
+    const std::string p = "llama.model.";
+    bool ok = (L->embed = ll_vec_up(L, T, p + "embed_tokens.weight", (int64_t)c.vocab * H)) != nullptr;
+    for (int i = 0; i < c.layers && ok; ++i) {
+        LlLayer y;
+        const std::string q = p + "layers." + std::to_string(i) + ".";
+        y.nw_attn = ll_vec_up(L, T, q + "input_layernorm.weight", H);
+        y.wqkv = ll_linear_up(L, T, {{q + "self_attn.q_proj.weight", QD}, {q + "self_attn.k_proj.weight", KD}, {q + "self_attn.v_proj.weight", KD}}, H);
+        y.wo = ll_linear_up(L, T, {{q + "self_attn.o_proj.weight", H}}, QD);
+        y.nw_mlp = ll_vec_up(L, T, q + "post_attention_layernorm.weight", H);
+        y.wgate = ll_linear_up(L, T, {{q + "mlp.gate_proj.weight", c.inter}}, H);
+        y.wup = ll_linear_up(L, T, {{q + "mlp.up_proj.weight", c.inter}}, H);
+        y.wdown = ll_linear_up(L, T, {{q + "mlp.down_proj.weight", H}}, c.inter);
+        ok = y.nw_attn && y.wqkv && y.wo && y.nw_mlp && y.wgate && y.wup && y.wdown;
+        L->layers.push_back(y);
+    }
+    ok = ok && (L->nw_final = ll_vec_up(L, T, p + "norm.weight", H)) != nullptr;
+    // the head's observable columns only: rows first_free_id .. vocab of lm_head.weight
+    ok = ok && (L->head = ll_linear_up(L, T, {{"llama.lm_head.weight", c.vocab - c.first_free_id}}, H, c.first_free_id, c.vocab)) != nullptr;
+    if (ok) {
+        // HF LlamaRotaryEmbedding (default rope): angle = fp32(position) * inv_freq as an fp32 product, cos / sin of THAT angle.  inv_freq =
+        // theta^(-2i/d) in fp32; a caller that has HF's own numbers hands them in (torch's vectorised pow is not correctly rounded, and one ulp
+        // of inv_freq is 6e-5 rad at position 1000)
+        std::vector<float> inv(hd), cs((size_t)c.max_pos * d);
+        auto it = T.m.find(p + "rotary_emb.inv_freq");
+        if (it != T.m.end() && it->second.second == hd) memcpy(inv.data(), it->second.first, sizeof(float) * hd);
+        else for (int i = 0; i < hd; ++i) inv[i] = 1.0f / powf(c.rope_theta, (float)(2 * i) / (float)d);
+        for (int pos = 0; pos < c.max_pos; ++pos)
+            for (int i = 0; i < hd; ++i) {
+                const float ang = (float)pos * inv[i];
+                cs[(size_t)pos * d + i] = (float)cos((double)ang);
+                cs[(size_t)pos * d + hd + i] = (float)sin((double)ang);
+            }
+        ok = (L->cs = L->up(cs)) != nullptr;
+    }
+    if (!ok) {
+        const std::string miss = T.missing;
+        delete L;
+        if (!miss.empty()) return ll_fail(LDS_EMISSING, "Llama weight tensor %s (absent or wrong size)", miss.c_str());
+        return ll_fail(LDS_ENOMEM, "Llama weight upload failed");
+    }
+    *out = L;
+    return LDS_OK;
+}
+extern "C" void lds_llama_destroy(lds_llama* L) { delete L; }
+
+namespace {
+struct LlArena {
+    char* base; size_t cap, used = 0; bool ok = true;
+    LlArena(void* p, size_t n) : base((char*)p), cap(n) {}
+    float* f(size_t n) {
+        const size_t bytes = (n * sizeof(float) + 255) & ~(size_t)255;
+        if (base && used + bytes > cap) ok = false;
+        char* p = base ? base + used : nullptr;
+        used += bytes;
+        return (float*)p;
+    }
+};
+struct LlWs { float *x, *q, *ctx, *ff, *logits; int* flags; int64_t* stok; int32_t* plen; std::vector<float*> kc, vc; };
+// rows of a pass: B * (P - 1) for the prefill (the prompts' positions but the last), B for a decode step
+void ll_plan(const lds_llama* L, LlArena& A, int B, int P, int cap, LlWs& w) {
+    const lds_llama_cfg& c = L->cfg;
+    const size_t N = (size_t)B * (P > 2 ? P - 1 : 1), QD = (size_t)c.heads * c.head_dim, KD = (size_t)c.kv_heads * c.head_dim;
+    w.x = A.f(N * c.hidden); w.q = A.f(N * QD); w.ctx = A.f(N * QD); w.ff = A.f(N * c.inter);
+    w.logits = A.f((size_t)B * (c.vocab - c.first_free_id));
+    w.flags = (int*)A.f((size_t)B + cap + kLlMaxBatch);
+    w.stok = (int64_t*)A.f(2 * (size_t)B * cap);
+    w.plen = (int32_t*)A.f((size_t)B);
+    w.kc.clear(); w.vc.clear();
+    for (int i = 0; i < c.layers; ++i) { w.kc.push_back(A.f((size_t)B * KD * cap)); w.vc.push_back(A.f((size_t)B * KD * cap)); }
+}
+// the shape checks, which need no model
+int ll_check_shape(int B, int P, int max_length) {
+    if (B <= 0 || P < 1 || max_length < 2) return ll_fail(LDS_EINVAL, "bad argument");
+    if (B > kLlMaxBatch) return ll_fail(LDS_EINVAL, "a Llama decode takes at most %d rows, got %d", kLlMaxBatch, B);
+    if (P > kLlMaxLength || max_length > kLlMaxLength) return ll_fail(LDS_EINVAL, "prompt width %d / max_length %d too long (<= %d)", P, max_length, kLlMaxLength);
+    return LDS_OK;
+}
+
+template <int EPI>
+hipError_t ll_linear(const float* X, int K, const float* nw, float eps, const float* Wt, const float* Wt2, int M, const float* R, float* Y, int ldy, int N,
+                     hipStream_t st, const LlRope* rope = nullptr) {
+    auto kern = ll_linear_kernel<EPI>;
+    static std::atomic<unsigned long long> attr_done{0};
+    hipError_t e = ensure_max_dynamic_lds(reinterpret_cast<const void*>(kern), attr_done);
+    if (e != hipSuccess) return e;
+    const size_t lds = ((size_t)K * 8 + (size_t)(EPI == LL_SWIGLU ? 2 : 1) * (kLlSlices - 1) * kLlCols * 8 + 8) * sizeof(float);
+    if (lds > 160 * 1024) return hipErrorInvalidValue;
+    unsigned gx = (M + kLlCols - 1) / kLlCols;
+    LlRope ro{};
+    if (EPI == LL_ROPE) {
+        if (!rope) return hipErrorInvalidValue;
+        ro = *rope;
+        gx = ((ro.heads + ro.kv_heads) * (ro.d / 2) + 31) / 32 + (ro.kv_heads * ro.d + kLlCols - 1) / kLlCols;
+    }
+    hipLaunchKernelGGL(kern, dim3(gx, (N + 7) / 8), dim3(1024), lds, st, X, K, nw, eps, Wt, Wt2, M, R, Y, ldy, N, ro);
+    return hipGetLastError();
+}
+
+// the decoder layers over N rows (a prefill pass or a decode step, told apart by `rows` alone); Lk_max = the most keys any row sees
+int ll_layers(const lds_llama* L, const LlWs& w, int N, const LlRows& rows, int Lk_max, hipStream_t st) {
+    const lds_llama_cfg& c = L->cfg;
+    const int H = c.hidden, d = c.head_dim, QD = c.heads * d, KD = c.kv_heads * d, Lkp = (Lk_max + 63) & ~63;
+    const size_t attn_lds = (size_t)(kLlMaxHeadDim + Lkp + 4 * (2 + kLlMaxHeadDim)) * sizeof(float);
+    for (int i = 0; i < c.layers; ++i) {
+        const LlLayer& y = L->layers[i];
+        const LlRope rope{L->cs, w.kc[i], w.vc[i], c.heads, c.kv_heads, d, rows};
+        LL_HIP(ll_linear<LL_ROPE>(w.x, H, y.nw_attn, c.eps, y.wqkv, nullptr, QD + 2 * KD, nullptr, w.q, QD, N, st, &rope));
+        hipLaunchKernelGGL(ll_attn_kernel, dim3((unsigned)(N * c.heads)), dim3(256), attn_lds, st, (const float*)w.q, (const float*)w.kc[i], (const float*)w.vc[i], rows,
+                           c.heads, c.kv_heads, d, Lkp, w.ctx);
+        LL_HIP(hipGetLastError());
+        LL_HIP(ll_linear<LL_RESID>(w.ctx, QD, nullptr, c.eps, y.wo, nullptr, H, w.x, w.x, H, N, st));
+        LL_HIP(ll_linear<LL_SWIGLU>(w.x, H, y.nw_mlp, c.eps, y.wgate, y.wup, c.inter, nullptr, w.ff, c.inter, N, st));
+        LL_HIP(ll_linear<LL_RESID>(w.ff, c.inter, nullptr, c.eps, y.wdown, nullptr, H, w.x, w.x, H, N, st));
+    }
+    return LDS_OK;
+}
+}  // namespace
+
+extern "C" int lds_llama_workspace_bytes(const lds_llama* L, int B, int P, int max_length, size_t* out) {
+    if (int r = ll_check_shape(B, P, max_length)) return r;
+    if (!L || !out) return ll_fail(LDS_EINVAL, "bad argument");
+    LlArena A(nullptr, 0);
+    LlWs w;
+    ll_plan(L, A, B, P, max_length, w);
+    *out = A.used;
+    return LDS_OK;
+}
+
+extern "C" int lds_llama_generate(lds_llama* L, const int64_t* input_ids, const int32_t* in_len, int B, int P, int max_length, const lds_lm_decode_opts* opts,
+                                  const float* uniforms, int64_t* tokens, float* logits_out, int* n_tokens_host, void* ws, size_t ws_bytes, void* stream) {
+    if (!opts) return ll_fail(LDS_EINVAL, "null options");
+    const lds_lm_decode_opts o = *opts;
+    if (int r = lm_check_opts(o, logits_out)) return r;
+    if (o.num_beams != 1) return ll_fail(LDS_EINVAL, "beam search is not built for Llama (num_beams must be 1): HF normalises over the whole vocabulary before the ban");
+    if (int r = ll_check_shape(B, P, max_length)) return r;
+    int Pmax = 0, Pmin = P;
+    for (int b = 0; b < B; ++b) {
+        const int pl = in_len ? in_len[b] : P;
+        if (pl < 1 || pl > P) return ll_fail(LDS_EINVAL, "in_len[%d] = %d out of range (1 .. P = %d)", b, pl, P);
+        if (pl >= max_length) return ll_fail(LDS_EINVAL, "in_len[%d] = %d leaves no room below max_length = %d (the total length, prompt included)", b, pl, max_length);
+        Pmax = pl > Pmax ? pl : Pmax;
+        Pmin = pl < Pmin ? pl : Pmin;
+    }
+    if (!L || !input_ids || !tokens || !n_tokens_host || !ws) return ll_fail(LDS_EINVAL, "bad argument");
+    const lds_llama_cfg& c = L->cfg;
+    const int H = c.hidden, V = c.vocab - c.first_free_id, shift = c.first_free_id;
+    if (o.do_sample && (!uniforms || o.top_k < 0 || o.top_k > kLmMaxTopK || o.top_k > V || !(o.top_p > 0.f) || !(o.temperature > 0.f)))
+        return ll_fail(LDS_EINVAL, "sampling needs uniforms, 0 <= top_k <= %d (0 = no top-k filter), top_p > 0, temperature > 0", kLmMaxTopK);
+    if (max_length > c.max_pos) return ll_fail(LDS_EINVAL, "max_length %d exceeds max_position_embeddings %d", max_length, c.max_pos);
+    hipStream_t st = (hipStream_t)stream;
+    LlArena A(ws, ws_bytes);
+    LlWs w;
+    ll_plan(L, A, B, P, max_length, w);
+    if (!A.ok) return ll_fail(LDS_ENOMEM, "Llama workspace too small: need %zu bytes", A.used);
+    int* unfinished = w.flags;                       // [B]
+    int* any_unf = w.flags + B;                      // [max_length]: 1 when a row is still running after global step s
+    int* rowlen = w.flags + B + max_length;          // [B <= 64]: every row's final length, prompt included
+    {
+        std::vector<int> init(B + max_length + kLlMaxBatch, 0), pl(B);
+        for (int b = 0; b < B; ++b) { init[b] = 1; init[B + max_length + b] = max_length; pl[b] = in_len ? in_len[b] : P; }
+        LL_HIP(hipMemcpyAsync(unfinished, init.data(), sizeof(int) * init.size(), hipMemcpyHostToDevice, st));
+        LL_HIP(hipMemcpyAsync(w.plen, pl.data(), sizeof(int) * B, hipMemcpyHostToDevice, st));
+        LL_HIP(hipStreamSynchronize(st));      // the host staging vectors go out of scope
+    }
+    const int32_t* plen = w.plen;
+    const int pad_s = c.pad - shift, eos_s = c.eos - shift;
+    hipLaunchKernelGGL(ll_init_kernel, dim3(B), dim3(256), 0, st, input_ids, P, plen, c.vocab, shift, pad_s, max_length, w.stok);
+    LL_HIP(hipGetLastError());
+    // Prefill: the positions 0 .. Pq - 1 (Pq = the longest prompt - 1) of every row in one causal pass that fills the decode's caches; the head is
+    // skipped.  A shorter row's slots in_len[b] - 1 .. Pq - 1 are filled from PAD; no query ever sees them: step s of row b first overwrites slot
+    // in_len[b] - 1 + s with the row's real token and then reads the slots 0 .. in_len[b] - 1 + s.  The same covers the workspace's contents on entry.
+    const int Pq = Pmax - 1;
+    if (Pq > 0) {
+        if ((long long)B * Pq > 8 * 65535LL) return ll_fail(LDS_EINVAL, "B * P too large for the prefill (<= 524280)");
+        const LlRows rows{plen, Pq, 0, max_length};
+        hipLaunchKernelGGL(ll_embed_kernel, dim3(B * Pq), dim3(256), 0, st, (const float*)L->embed, (const int64_t*)w.stok, rows, shift, c.vocab, H, w.x);
+        LL_HIP(hipGetLastError());
+        if (int r = ll_layers(L, w, B * Pq, rows, Pq, st)) return r;
+    }
+    const float inv_temp = o.do_sample ? 1.0f / o.temperature : 1.0f;
+    const int n_steps = max_length - Pmin;      // the shortest row writes its last slot at step n_steps - 1
+    std::vector<int> host_flags(n_steps, 0);
+    int checked = 0;
+    for (int step = 0; step < n_steps; ++step) {
+        const LlRows rows{plen, 0, step, max_length};
+        hipLaunchKernelGGL(ll_embed_kernel, dim3(B), dim3(256), 0, st, (const float*)L->embed, (const int64_t*)w.stok, rows, shift, c.vocab, H, w.x);
+        LL_HIP(hipGetLastError());
+        const int Lk_max = (Pmax + step < max_length) ? Pmax + step : max_length;
+        if (int r = ll_layers(L, w, B, rows, Lk_max, st)) return r;
+        float* lg = logits_out ? logits_out + (size_t)step * B * V : w.logits;
+        LL_HIP(ll_linear<LL_PLAIN>(w.x, H, L->nw_final, c.eps, L->head, nullptr, V, nullptr, lg, V, B, st));
+        LL_HIP(lm_launch_choice_rows(o, B, V, lg, inv_temp, o.do_sample ? uniforms + (size_t)step * B : nullptr, w.stok, max_length, step, unfinished, eos_s, pad_s,
+                                     any_unf, nullptr, nullptr, nullptr, nullptr, c.eps, H, nullptr, plen, rowlen, st));
+        if ((step & 7) == 7 || step + 1 == n_steps) {      // the EOS poll; a row that reached max_length counts as finished
+            LL_HIP(hipMemcpyAsync(host_flags.data() + checked, any_unf + checked, sizeof(int) * (step + 1 - checked), hipMemcpyDeviceToHost, st));
+            LL_HIP(hipStreamSynchronize(st));
+            bool done = false;
+            for (int s = checked; s <= step && !done; ++s) done = host_flags[s] == 0;
+            checked = step + 1;
+            if (done) break;
+        }
+    }
+    const long long total = (long long)B * max_length;
+    hipLaunchKernelGGL(ll_finish_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const int64_t*)w.stok, total, shift, tokens);
+    LL_HIP(hipGetLastError());
+    std::vector<int> len(B, 0);
+    LL_HIP(hipMemcpyAsync(len.data(), rowlen, sizeof(int) * B, hipMemcpyDeviceToHost, st));
+    LL_HIP(hipStreamSynchronize(st));
+    int n_tokens = 0;
+    for (int b = 0; b < B; ++b) n_tokens = len[b] > n_tokens ? len[b] : n_tokens;
+    *n_tokens_host = n_tokens;
+    return LDS_OK;
+}

@@ -7,6 +7,7 @@
 // per output, independent of the batch size.
 #include "../../include/lds.h"
 #include "kernels.h"
+#include "lm_common.h"
 
 #include <math.h>
 #include <stdarg.h>
@@ -22,60 +23,6 @@ namespace lds {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-// Wave64 reductions on the DPP path (row shifts + row broadcasts: VALU speed, no LDS crossbar), result in every lane.  A butterfly of
-// __shfl_xor is six dependent ds_bpermute round trips (~0.3 us); the decode step runs ~40 of these reductions back to back.
-template <int CTRL, int ROW_MASK, bool BOUND>
-static __device__ __forceinline__ int dpp_i(int old, int v) { return __builtin_amdgcn_update_dpp(old, v, CTRL, ROW_MASK, 0xf, BOUND); }
-template <int CTRL, int ROW_MASK, bool BOUND>
-static __device__ __forceinline__ float dpp_f(float old, float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, old), __builtin_bit_cast(int, v), CTRL, ROW_MASK, 0xf, BOUND));
-}
-static __device__ __forceinline__ float wave_sum(float v) {      // fixed order; the total forms in lane 63
-    v += dpp_f<0x111, 0xf, true>(0.f, v);      // row_shr:1
-    v += dpp_f<0x112, 0xf, true>(0.f, v);      // row_shr:2
-    v += dpp_f<0x114, 0xf, true>(0.f, v);      // row_shr:4
-    v += dpp_f<0x118, 0xf, true>(0.f, v);      // row_shr:8: lane 15 of every 16-lane row = the row's sum
-    v += dpp_f<0x142, 0xa, false>(0.f, v);     // row_bcast:15 into rows 1 and 3
-    v += dpp_f<0x143, 0xc, false>(0.f, v);     // row_bcast:31 into rows 2 and 3
-    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
-}
-static __device__ __forceinline__ float wave_max(float v) {      // lanes without a source keep their own value (old = v)
-    v = fmaxf(v, dpp_f<0x111, 0xf, false>(v, v));
-    v = fmaxf(v, dpp_f<0x112, 0xf, false>(v, v));
-    v = fmaxf(v, dpp_f<0x114, 0xf, false>(v, v));
-    v = fmaxf(v, dpp_f<0x118, 0xf, false>(v, v));
-    v = fmaxf(v, dpp_f<0x142, 0xa, false>(v, v));
-    v = fmaxf(v, dpp_f<0x143, 0xc, false>(v, v));
-    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
-}
-static __device__ __forceinline__ int wave_min_i(int v) {
-    v = min(v, dpp_i<0x111, 0xf, false>(v, v));
-    v = min(v, dpp_i<0x112, 0xf, false>(v, v));
-    v = min(v, dpp_i<0x114, 0xf, false>(v, v));
-    v = min(v, dpp_i<0x118, 0xf, false>(v, v));
-    v = min(v, dpp_i<0x142, 0xa, false>(v, v));
-    v = min(v, dpp_i<0x143, 0xc, false>(v, v));
-    return __builtin_amdgcn_readlane(v, 63);
-}
-// sum over the NT threads of a workgroup (fixed order), result in every thread; red has NT / 64 <= 16 slots
-template <int NT>
-static __device__ __forceinline__ float block_sum(float v, float* red) {
-    v = wave_sum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float t = 0.f;
-#pragma unroll
-    for (int i = 0; i < NT / 64; ++i) t += red[i];
-    return t;
-}
-static __device__ __forceinline__ float block_sum256(float v, float* red) {
-    v = wave_sum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
 static __device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
 
 // ---- embeddings: x = LN(word[tok] + type[tt]); encoder: x = LN(x + spk[spk_id] + type[0]) as well (roformer.py:196, the
@@ -504,7 +451,7 @@ __global__ void lm_score_loss_kernel(const double* __restrict__ psum, const int3
 // ---- next-token choice per sequence (HF GenerationMixin._sample with RepetitionPenalty -> Temperature -> TopK -> TopP, then
 //      softmax + one draw; greedy = argmax).  The draw is the inverse-CDF rule over the vocabulary order with a caller-supplied
 //      uniform (torch.multinomial's own stream cannot be reproduced outside torch).  One workgroup per sequence, V <= 256 * 32. ----
-constexpr int kMaxTopK = 64;
+constexpr int kMaxTopK = kLmMaxTopK;
 // NoRepeatNGramLogitsProcessor (transformers generation/logits_process.py) over the history seq[0, len), BOS included: every window of n tokens
 // whose first n - 1 equal the last n - 1 tokens of the history bans its last token (n = 1: every token seen so far).  Nothing is banned while
 // len < n.  The banned ids are set as bits of ban[] (LDS, V <= 8192) by the threads [t0, t0 + nt); the caller zeroes ban and synchronises.
@@ -554,7 +501,7 @@ static __device__ __forceinline__ void lm_sample_body(const float* __restrict__ 
         unsigned done = 0;
         for (int j = 0; j <= step; ++j) {
             const int t = (int)seq[j];
-            if ((t & 255) == tid && !((done >> (t >> 8)) & 1u)) {
+            if (t >= 0 && (t & 255) == tid && !((done >> (t >> 8)) & 1u)) {      // (negative: an id outside the columns, llama.hip's phone ids)
                 done |= 1u << (t >> 8);
 #pragma unroll
                 for (int i = 0; i < NI; ++i)
@@ -1472,8 +1419,10 @@ hipError_t lm_launch_beam_step(int B, int K, int V, const float* lg, int step, i
         return hipErrorInvalidValue;
     return hipGetLastError();
 }
+}  // namespace
+
 // the option checks that need no model (they come before every other check of lds_lm_generate_opts; no device call)
-int lm_check_opts(const lds_lm_decode_opts& o, const float* logits_out) {
+int lds::lm_check_opts(const lds_lm_decode_opts& o, const float* logits_out) {
     if (o.num_beams < 1 || o.num_beams > kMaxBeams) return lm_fail(LDS_EINVAL, "num_beams %d out of range (1 .. %d)", o.num_beams, kMaxBeams);
     if (o.no_repeat_ngram_size < 0) return lm_fail(LDS_EINVAL, "no_repeat_ngram_size %d < 0", o.no_repeat_ngram_size);
     if (o.num_beams > 1 && o.do_sample)
@@ -1482,7 +1431,6 @@ int lm_check_opts(const lds_lm_decode_opts& o, const float* logits_out) {
     if (o.num_beams > 1 && logits_out) return lm_fail(LDS_EINVAL, "logits_out is not available with num_beams > 1");
     return LDS_OK;
 }
-}  // namespace
 
 extern "C" int lds_lm_workspace_bytes_opts(const lds_lm* lm, int B, int L, int max_length, int num_beams, size_t* out) {
     if (num_beams < 1 || num_beams > kMaxBeams) return lm_fail(LDS_EINVAL, "num_beams %d out of range (1 .. %d)", num_beams, kMaxBeams);
@@ -1653,7 +1601,10 @@ int lm_prompt_check(int B, int L, int max_length, int P) {
         return lm_fail(LDS_EINVAL, "prompt width %d too large (<= 16000, B * P <= 524280)", P);
     return LDS_OK;
 }
-hipError_t lm_launch_choice_rows(const lds_lm_decode_opts& o, int B, int V, const float* lg, float inv_temp, const float* u, int64_t* tokens, int cap, int step,
+}  // namespace
+
+// (declared in lm_common.h: llama.hip's decode chooses its tokens through the same kernels)
+hipError_t lds::lm_launch_choice_rows(const lds_lm_decode_opts& o, int B, int V, const float* lg, float inv_temp, const float* u, int64_t* tokens, int cap, int step,
                                  int* unfinished, int eos, int pad, int* any_unf, const float* word, const float* type, const float* eg, const float* eb, float eps,
                                  int H, float* xnext, const int32_t* plen, int* rowlen, hipStream_t st) {
     const int ds = o.do_sample, tk = ds ? o.top_k : 1, ng = o.no_repeat_ngram_size;
@@ -1671,7 +1622,6 @@ hipError_t lm_launch_choice_rows(const lds_lm_decode_opts& o, int B, int V, cons
                        H, xnext, ng, plen, rowlen);
     return hipGetLastError();
 }
-}  // namespace
 
 extern "C" int lds_lm_workspace_bytes_prompt(const lds_lm* lm, int B, int L, int max_length, int P, size_t* out) {
     if (int r = lm_prompt_check(B, L, max_length, P)) return r;

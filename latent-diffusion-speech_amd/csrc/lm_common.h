@@ -1,0 +1,74 @@
+// What the two language models share (lm.hip: RoFormer, llama.hip: Llama): the wave64 / workgroup reductions of their kernels and the
+// launchers of the token-choice kernels, which live in lm.hip and serve both decodes.
+#pragma once
+#include "../../include/lds.h"
+#include "kernels.h"
+
+namespace lds {
+
+// Wave64 reductions on the DPP path (row shifts + row broadcasts: VALU speed, no LDS crossbar), result in every lane.  A butterfly of
+// __shfl_xor is six dependent ds_bpermute round trips (~0.3 us); the decode step runs ~40 of these reductions back to back.
+template <int CTRL, int ROW_MASK, bool BOUND>
+static __device__ __forceinline__ int dpp_i(int old, int v) { return __builtin_amdgcn_update_dpp(old, v, CTRL, ROW_MASK, 0xf, BOUND); }
+template <int CTRL, int ROW_MASK, bool BOUND>
+static __device__ __forceinline__ float dpp_f(float old, float v) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, old), __builtin_bit_cast(int, v), CTRL, ROW_MASK, 0xf, BOUND));
+}
+static __device__ __forceinline__ float wave_sum(float v) {      // fixed order; the total forms in lane 63
+    v += dpp_f<0x111, 0xf, true>(0.f, v);      // row_shr:1
+    v += dpp_f<0x112, 0xf, true>(0.f, v);      // row_shr:2
+    v += dpp_f<0x114, 0xf, true>(0.f, v);      // row_shr:4
+    v += dpp_f<0x118, 0xf, true>(0.f, v);      // row_shr:8: lane 15 of every 16-lane row = the row's sum
+    v += dpp_f<0x142, 0xa, false>(0.f, v);     // row_bcast:15 into rows 1 and 3
+    v += dpp_f<0x143, 0xc, false>(0.f, v);     // row_bcast:31 into rows 2 and 3
+    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
+}
+static __device__ __forceinline__ float wave_max(float v) {      // lanes without a source keep their own value (old = v)
+    v = fmaxf(v, dpp_f<0x111, 0xf, false>(v, v));
+    v = fmaxf(v, dpp_f<0x112, 0xf, false>(v, v));
+    v = fmaxf(v, dpp_f<0x114, 0xf, false>(v, v));
+    v = fmaxf(v, dpp_f<0x118, 0xf, false>(v, v));
+    v = fmaxf(v, dpp_f<0x142, 0xa, false>(v, v));
+    v = fmaxf(v, dpp_f<0x143, 0xc, false>(v, v));
+    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
+}
+static __device__ __forceinline__ int wave_min_i(int v) {
+    v = min(v, dpp_i<0x111, 0xf, false>(v, v));
+    v = min(v, dpp_i<0x112, 0xf, false>(v, v));
+    v = min(v, dpp_i<0x114, 0xf, false>(v, v));
+    v = min(v, dpp_i<0x118, 0xf, false>(v, v));
+    v = min(v, dpp_i<0x142, 0xa, false>(v, v));
+    v = min(v, dpp_i<0x143, 0xc, false>(v, v));
+    return __builtin_amdgcn_readlane(v, 63);
+}
+// sum over the NT threads of a workgroup (fixed order), result in every thread; red has NT / 64 <= 16 slots
+template <int NT>
+static __device__ __forceinline__ float block_sum(float v, float* red) {
+    v = wave_sum(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    float t = 0.f;
+#pragma unroll
+    for (int i = 0; i < NT / 64; ++i) t += red[i];
+    return t;
+}
+static __device__ __forceinline__ float block_sum256(float v, float* red) {
+    v = wave_sum(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return (red[0] + red[1]) + (red[2] + red[3]);
+}
+// ---- lm.hip's token choice (greedy, top-k 1..64 with ties, no filter, top-p, repetition penalty, n-gram ban) with per-row positions: row b
+//      continues a history of plen[b] tokens in tokens [B][cap] and writes slot plen[b] + step (lm_sample_body's PROW form).  word .. eb / xnext:
+//      the RoFormer's next input row, null to skip it. ----
+hipError_t lm_launch_choice_rows(const lds_lm_decode_opts& o, int B, int V, const float* lg, float inv_temp, const float* u, int64_t* tokens, int cap, int step,
+                                 int* unfinished, int eos, int pad, int* any_unf, const float* word, const float* type, const float* eg, const float* eb, float eps,
+                                 int H, float* xnext, const int32_t* plen, int* rowlen, hipStream_t st);
+// the option checks that need no model (no device call); LDS_OK or LDS_EINVAL with a message
+int lm_check_opts(const lds_lm_decode_opts& o, const float* logits_out);
+constexpr int kLmMaxTopK = 64;            // survivors of the top-k filter
+constexpr int kLmMaxChoiceVocab = 8192;   // columns the token-choice kernels take (32 per thread; the n-gram ban's bit set)
+
+}  // namespace lds

@@ -357,6 +357,56 @@ def roformer_init_state(cfg, seed=0, init_weights=None):
     return {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in st.items()}
 
 
+# ---- text2semantic Llama (reference text2semantic/llama/llama.py:23-71 over HF LlamaForCausalLM): one decoder-only stack over the stream
+# [phone BOS, phones, phone EOS, semantic BOS, semantic tokens ...] ------------------------------------------------------------------------
+def llama_config(semantic_kmeans_num=10000, hidden_size=4096, num_attention_heads=32, num_key_value_heads=None, head_dim=None,
+                 intermediate_size=11008, num_hidden_layers=32, max_position_embeddings=2048, rms_norm_eps=1e-6, rope_theta=10000.0):
+    """Shapes and ids of `Llama(config, mode="phone", semantic_kmeans_num=K)` (defaults: HF LlamaConfig's).  The phone-side BOS / EOS / PAD
+    (108, 109, 110) coincide with the shifted semantic ids 0, 1, 2: that is the reference's numbering (llama.py:39-58)."""
+    kv = num_attention_heads if num_key_value_heads is None else num_key_value_heads
+    d = hidden_size // num_attention_heads if head_dim is None else head_dim
+    s, K = PHONE_SYMBOLS, semantic_kmeans_num
+    return dict(semantic_kmeans_num=K, hidden=hidden_size, heads=num_attention_heads, kv_heads=kv, head_dim=d, inter=intermediate_size,
+                layers=num_hidden_layers, max_pos=max_position_embeddings, eps=float(rms_norm_eps), rope_theta=float(rope_theta),
+                text_bos=s, text_eos=s + 1, text_pad=s + 2, shift=s, bos=s + K, eos=s + K + 1, pad=s + K + 2, vocab=s + K + 3)
+
+
+def llama_param_shapes(cfg):
+    """`Llama.state_dict()` key -> shape (llama.py:65; tie_word_embeddings is False there, so lm_head.weight is a tensor of its own)"""
+    d = OrderedDict()
+    h, qd, kd, it = cfg["hidden"], cfg["heads"] * cfg["head_dim"], cfg["kv_heads"] * cfg["head_dim"], cfg["inter"]
+    d["llama.model.embed_tokens.weight"] = (cfg["vocab"], h)
+    for i in range(cfg["layers"]):
+        p = f"llama.model.layers.{i}."
+        d[p + "self_attn.q_proj.weight"] = (qd, h)
+        d[p + "self_attn.k_proj.weight"] = (kd, h)
+        d[p + "self_attn.v_proj.weight"] = (kd, h)
+        d[p + "self_attn.o_proj.weight"] = (h, qd)
+        d[p + "mlp.gate_proj.weight"] = (it, h)
+        d[p + "mlp.up_proj.weight"] = (it, h)
+        d[p + "mlp.down_proj.weight"] = (h, it)
+        d[p + "input_layernorm.weight"] = (h,)
+        d[p + "post_attention_layernorm.weight"] = (h,)
+    d["llama.model.norm.weight"] = (h,)
+    d["llama.lm_head.weight"] = (cfg["vocab"], h)
+    return d
+
+
+def llama_init_state(cfg, seed=0, init_weights=None):
+    """Build-owned seeded weights for the Llama LM: matrices at the familiar 1/sqrt(fan_in) scale, norm gains around 1, unit-range embeddings"""
+    if init_weights is None:
+        from . import init_weights
+    import numpy as np
+    shapes = llama_param_shapes(cfg)
+    st = init_weights.init_state(shapes, seed)
+    for k in shapes:
+        if k.endswith("layernorm.weight") or k.endswith("model.norm.weight"):
+            st[k] = init_weights.uniform(k, shapes[k], seed, 0.8, 1.2)
+        elif k.endswith("embed_tokens.weight"):
+            st[k] = init_weights.uniform(k, shapes[k], seed, -1.0, 1.0)
+    return {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in st.items()}
+
+
 # ---- Whisper units encoder (reference encoder/whisper/model.py:10-21,112-137; tools/tools.py:105-116) ----------------------------------
 # dims of the reference's configured encoder (configs/config.yaml: whisper_large_v3); the text-side fields describe the decoder the
 # reference's Whisper(dims) never builds and are carried only because ModelDimensions has them

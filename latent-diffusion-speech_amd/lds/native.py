@@ -135,6 +135,10 @@ lds_lm_workspace_bytes_prompt    i:piiiip
 lds_lm_generate_prompt           i:pppiiipppipppppzp
 lds_lm_score_workspace_bytes     i:piiip
 lds_lm_score                     i:pppiipppippppppzp
+lds_llama_create                 i:pipppp
+lds_llama_destroy                v:p
+lds_llama_workspace_bytes        i:piiip
+lds_llama_generate               i:pppiiippppppzp
 lds_kmeans_workspace_bytes       i:qiip
 lds_kmeans_prepare               i:piipp
 lds_kmeans_assign                i:pqppiipppzp
@@ -1113,6 +1117,52 @@ class LM(_Handle):
                                  _dev_or_null(sem_len, torch.int32), _dev_or_null(lab, torch.int64), T, _dev(lp), _dev(ranks), _dev(loss), _dev(n),
                                  _dev_or_null(logits), _dev(ws), ws.numel(), _stream()))
         return lp, ranks, loss, n, logits
+
+
+class LlamaCfg(C.Structure):
+    _fields_ = [("hidden", C.c_int), ("heads", C.c_int), ("kv_heads", C.c_int), ("head_dim", C.c_int), ("inter", C.c_int), ("layers", C.c_int),
+                ("vocab", C.c_int), ("max_pos", C.c_int), ("eps", C.c_float), ("rope_theta", C.c_float), ("first_free_id", C.c_int), ("bos", C.c_int),
+                ("eos", C.c_int), ("pad", C.c_int)]
+
+
+class Llama(_Handle):
+    """text2semantic Llama (lds_llama_*): causal prefill of the prompts + cached decode loop."""
+    KIND = "llama"
+
+    def __init__(self, cfg, state):
+        """cfg: arch.llama_config; state: Llama.state_dict() (+ llama.model.rotary_emb.inv_freq, HF's inverse frequencies)"""
+        c = LlamaCfg()
+        c.hidden, c.heads, c.kv_heads, c.head_dim, c.inter, c.layers = cfg["hidden"], cfg["heads"], cfg["kv_heads"], cfg["head_dim"], cfg["inter"], cfg["layers"]
+        c.vocab, c.max_pos, c.eps, c.rope_theta = cfg["vocab"], cfg["max_pos"], cfg["eps"], cfg["rope_theta"]
+        c.first_free_id, c.bos, c.eos, c.pad = cfg["shift"], cfg["bos"], cfg["eos"], cfg["pad"]
+        self._create_weights(c, state)
+        self.cfg = cfg
+
+    def generate(self, input_ids, in_len, max_length, do_sample, top_k, top_p, temperature, repetition_penalty, uniforms=None, return_logits=False,
+                 no_repeat_ngram_size=0, num_beams=1):
+        """input_ids int64 [B,P] on the device (right-padded), in_len a sequence of B host ints or None (= P everywhere); max_length counts the
+        prompt.  Returns (tokens [B,n], ids of the model's vocabulary with the prompt in front, logits [steps,B,vocab - shift] or None):
+        logits[s][b] chose row b's s-th generated token; steps is the largest number of tokens any row generated."""
+        import torch
+        B, P = input_ids.shape
+        o = LMDecodeOpts(1 if do_sample else 0, int(top_k or 0), float(top_p), float(temperature), float(repetition_penalty), int(no_repeat_ngram_size),
+                         int(num_beams), 1)
+        plen = None if in_len is None else (C.c_int32 * B)(*[int(v) for v in in_len])
+        ws = self._workspace("lds_llama_workspace_bytes", input_ids.device, B, P, int(max_length))
+        tokens = torch.empty(B, max_length, dtype=torch.int64, device=input_ids.device)
+        V = self.cfg["vocab"] - self.cfg["shift"]
+        logits = torch.empty(max_length - 1, B, V, dtype=torch.float32, device=input_ids.device) if return_logits else None
+        n = C.c_int()
+        ids, u = input_ids.contiguous(), uniforms.contiguous() if uniforms is not None else None
+        check(lib().lds_llama_generate(self.h, _dev(ids, torch.int64), C.cast(plen, C.c_void_p) if plen is not None else None, B, P, int(max_length), C.byref(o),
+                                       _dev_or_null(u, torch.float32), _dev(tokens), _dev_or_null(logits), C.byref(n), _dev(ws), ws.numel(), _stream()))
+        toks = tokens[:, : n.value].contiguous()
+        if logits is None:
+            return toks, None
+        plen = torch.tensor([P] * B if in_len is None else [int(v) for v in in_len], device=toks.device)
+        stop = (toks == self.cfg["eos"]) & (torch.arange(n.value, device=toks.device)[None] >= plen[:, None])
+        end = torch.where(stop.any(1), stop.int().argmax(1) + 1, torch.full_like(plen, n.value))
+        return toks, logits[: int((end - plen).max())]
 
 
 # ---- k-means semantic tokenizer (lds_kmeans_*): thin wrappers; X [N, D] and C [K, D] contiguous fp32 device tensors ----

@@ -5,6 +5,8 @@ def get_language_model(**args):
     model_type = args["text2semantic"]["model"]["type"]
     if model_type == "roformer":
         from text2semantic.roformer.roformer import get_model
+    elif model_type == "llama":      # (the reference's utils.py has no such branch: its Llama is only ever built by hand, llama.py:186-193)
+        from text2semantic.llama.llama import get_model
     else:
         raise ValueError(f" [x] Unknown Model: {model_type}")
     return get_model(args["common"]["n_spk"], **args["text2semantic"])

@@ -13,6 +13,12 @@
                        step: the difference is what the causal prefill saves.  With --batch 8 also one ragged batch whose prompt lengths
                        run from 64 to the largest P.  Greedy; event time on the stream, median of --reps; --json FILE keeps the rows.
 
+  --llama              the decoder-only Llama instead (Llama.generate; the shape of the reference's own example, llama.py:186-193: hidden 768,
+                       4 heads, 4 layers, intermediate 512, K 2048) with 64 phones, greedy: the prefill (a decode of one step) and the time per
+                       further decode step at --batch, event time on the stream, median of --reps; the RoFormer's step time from the same
+                       process for scale; and, where transformers imports, HF's LlamaForCausalLM.generate with the same weights on the
+                       same device.  --json FILE keeps the rows.
+
 With --num_beams > 1, --greedy, --score, --prompt or more than one length the EOS logit is biased far down, so that every sequence runs to the
 full length and the time per step is that of a full decode."""
 import argparse
@@ -42,6 +48,7 @@ ap.add_argument("--prompt", type=int, nargs="*", default=[])
 ap.add_argument("--new", type=int, default=64)
 ap.add_argument("--reps", type=int, default=5)
 ap.add_argument("--json", default=None)
+ap.add_argument("--llama", action="store_true")
 a = ap.parse_args()
 if a.lib:
     native.LIB_PATH = os.path.abspath(a.lib)
@@ -130,6 +137,68 @@ def prompt_mode():
         json.dump({"what": "a prompted greedy decode (causal prefill of the prompt, then the per-row decode steps) vs the unprompted decode to the same total "
                            f"length, EOS biased down, event time on the stream, median of {a.reps}", "rows": rows}, open(a.json, "w"), indent=1)
 
+
+def llama_mode():
+    from text2semantic.llama.llama import Llama
+    K, L, new = 2048, 64, a.new
+    conf = dict(hidden_size=768, num_attention_heads=4, num_hidden_layers=4, intermediate_size=512, max_position_embeddings=2048)
+    m = Llama(dict(conf), semantic_kmeans_num=K, codebook_path="").cuda().eval()
+    with torch.no_grad():
+        m.llama.lm_head.weight[m.cfg["eos"]] = 0.0      # an EOS logit of exactly 0 never wins here (asserted): every row runs to the full length
+    P = L + 3
+    hf = None
+    try:
+        from transformers import LlamaConfig, LlamaForCausalLM
+        hf = LlamaForCausalLM(LlamaConfig(vocab_size=m.cfg["vocab"], **conf)).cuda().eval()
+        hf.load_state_dict({k[len("llama."):]: v for k, v in m.state_dict().items()}, strict=True)
+    except ImportError:
+        print("transformers does not import here: no HF timing")
+    rows = []
+    for B in a.batch:
+        ph = torch.from_numpy((np.arange(B * L).reshape(B, L) * 7 % 107 + 1).astype(np.int64)).cuda()
+
+        def gen(n):
+            return m.generate(ph, ph, max_length=P + n, do_sample=False)
+        gen(8)
+        pre_ms, _ = event_ms(lambda: gen(1), a.reps)
+        all_ms, tok = event_ms(lambda: gen(1 + new), a.reps)
+        assert tok.shape == (B, 1 + new), tok.shape
+        row = {"B": B, "phones": L, "prompt_ids": P, "new_tokens": new, "prefill_plus_one_step_ms": pre_ms, "decode_ms": all_ms,
+               "us_per_step": (all_ms - pre_ms) * 1e3 / new}
+        if hf is not None:
+            ids, _ = m.input_ids(ph)
+
+            def hf_gen(n):
+                return hf.generate(inputs=ids, max_length=P + n, do_sample=False, use_cache=True, pad_token_id=m.cfg["pad"], eos_token_id=m.cfg["eos"],
+                                   bad_words_ids=[[i] for i in range(m.cfg["shift"])])
+            hf_gen(8)
+            h1, _ = event_ms(lambda: hf_gen(1), a.reps)
+            h2, htok = event_ms(lambda: hf_gen(1 + new), a.reps)
+            row.update(hf_prefill_plus_one_step_ms=h1, hf_decode_ms=h2, hf_us_per_step=(h2 - h1) * 1e3 / new, hf_over_native=h2 / all_ms,
+                       same_tokens=bool(htok.shape[1] == P + 1 + new and torch.equal(htok[:, P:] - m.cfg["shift"], tok)))
+        rows.append(row)
+        print(row)
+    # the RoFormer's step from the same process, for scale (greedy, EOS biased down)
+    with torch.no_grad():
+        lm.semantic_decoder.cls.predictions.bias[lm.semantic_eos_token_id] -= 1.0e4
+    a.greedy = True
+    for B in a.batch:
+        ph = torch.from_numpy((np.arange(B * L).reshape(B, L) * 7 % 107 + 1).astype(np.int64)).cuda()
+        tn = torch.from_numpy((np.arange(B * L).reshape(B, L) * 5 % 12).astype(np.int64)).cuda()
+        decode(ph, tn, 8)
+        r1, _ = event_ms(lambda: decode(ph, tn, 1), a.reps)
+        r2, _ = event_ms(lambda: decode(ph, tn, 1 + new), a.reps)
+        rows.append({"B": B, "model": "roformer", "us_per_step": (r2 - r1) * 1e3 / new})
+        print(rows[-1])
+    if a.json:
+        import json
+        json.dump({"what": "Llama.generate (greedy, 64 phones, the reference example's width): a one-step decode (the prefill) and the time per further step; "
+                           f"event time on the stream, median of {a.reps}", "rows": rows}, open(a.json, "w"), indent=1)
+
+
+if a.llama:
+    llama_mode()
+    sys.exit(0)
 
 if a.prompt:
     a.greedy = True
