@@ -497,6 +497,31 @@ int  lds_llama_workspace_bytes(const lds_llama* h, int B, int P, int max_length,
 int  lds_llama_generate(lds_llama* h, const int64_t* input_ids, const int32_t* in_len, int B, int P, int max_length, const lds_lm_decode_opts* opts,
                         const float* uniforms, int64_t* tokens, float* logits_out, int* n_tokens_host, void* ws, size_t ws_bytes, void* stream);
 
+/* Teacher-forced scoring under the Llama: what the reference's forward (llama.py:73-117) hands to LlamaForCausalLM with labels -- the logits of
+ * every position of given streams in ONE causal pass, and HF's shifted cross entropy over the WHOLE vocabulary (ids below first_free_id
+ * included: only generate bans them, llama.py:170) -- with lds_lm_score's outputs and definitions.  The rows go through the kernels of
+ * lds_llama_generate (a row's position is all that tells a scoring row from a prefill row or a decode step), so the columns first_free_id ..
+ * of the logits at position t equal what the decode computes there, bit for bit.
+ *   input_ids dev int64 [B][S]: the streams (llama.py:98-101: [phone BOS, phones, phone EOS, semantic BOS, semantic ids + shift, semantic EOS]),
+ *     right-padded; ids_len dev int32 [B] (real ids per row) or NULL = S everywhere.  Ids are clamped to [0, vocab) on the way into the
+ *     embedding (callers validate the ids inside the lengths; lds.native's callers do).
+ *   labels dev int64 [B][S] or NULL = input_ids (the loader's choice, text2semantic/llama/dataloader.py:182-183).  Position t of row b
+ *     (0 <= t <= S - 2) is counted when t + 1 < ids_len[b] and y = labels[b][t + 1] lies in [0, vocab); -100 (HF's ignore index) and every
+ *     other id outside are ignored.
+ *   logprobs dev [B][S-1]:  logit_y - logsumexp_v logit_v over v in [0, vocab)  (max and sum of exp in a fixed order, the log in double,
+ *     rounded once); 0 where not counted.   ranks dev int32 [B][S-1]:  #{v : logit_v > logit_y} + #{v < y : logit_v == logit_y}; -1 where not counted.
+ *   loss dev [1] = -(sum of the counted logprobs) / n_counted (llama.py:103-117's outputs.loss, HF's mean reduction; NaN when nothing is
+ *     counted), n_counted dev int32 [1]: a fixed-order two-stage sum in double, no atomics -- every output is bit-identical on repeat.
+ *   logits_out dev [B][S][vocab] or NULL.  Without it the head runs over chunks of 256 rows through one reused buffer, so the workspace does
+ *     not grow with B * S * vocab.
+ * Slots at and beyond ids_len[b] are filled from PAD, as in the prefill; ids, labels and logits rows there have no effect on any counted
+ * output.  The contents of the workspace on entry do not matter.  Nothing synchronises and nothing is copied from the host.  Limits
+ * (LDS_EINVAL with a message before anything is enqueued): B >= 1, 2 <= S <= min(max_position_embeddings, 15000), B * S <= 524280.  A workspace
+ * smaller than lds_llama_score_workspace_bytes(B, S) gives LDS_ENOMEM with the size needed in the message. */
+int  lds_llama_score_workspace_bytes(const lds_llama* h, int B, int S, size_t* out);
+int  lds_llama_score(lds_llama* h, const int64_t* input_ids, const int32_t* ids_len, const int64_t* labels, int B, int S, float* logprobs, int32_t* ranks,
+                     float* loss, int32_t* n_counted, float* logits_out, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- k-means semantic tokenizer: units -> tokens and the codebook fit (reference cluster/__init__.py:13-23 get_cluster_result /
  *      get_cluster_center_result, cluster/kmeans.py:10-50 _kpp, :108-131 euc_sim / max_sim, :184-198 the Lloyd step; called from
  *      17_preprocess_train_cluster.py and 19_preprocess_token.py) -------------------------------------------------------------------

@@ -32,7 +32,7 @@ def parse_args(argv=None):
     ap.add_argument("--num_beams", type=int, default=1, help="> 1: greedy beam search over the semantic tokens instead of top-k sampling (2 .. 8)")
     ap.add_argument("--no_repeat_ngram_size", type=int, default=0, help="n >= 1: no n-gram of semantic tokens repeats (HF NoRepeatNGramLogitsProcessor)")
     ap.add_argument("--candidates", type=int, default=1,
-                    help="N > 1: sample N token sequences in one batch, score them with the LM (Roformer.score) and keep the one with the highest mean "
+                    help="N > 1: sample N token sequences in one batch, score them with the LM (Roformer.score / Llama.score) and keep the one with the highest mean "
                          "log-prob per generated token (sampling only: num_beams 1)")
     ap.add_argument("--prompt_tokens", help=".npy int array [Tp] of semantic token ids the LM continues from (BOS is added): a voice / prosody prompt, or "
                                             "the tail of the previous sentence")
@@ -115,8 +115,9 @@ def load_lm(path, dev):
 
 
 def with_bos(lm, prompt_tokens, rows=1):
-    """semantic ids [Tp] -> the decoder prompt [rows, 1 + Tp] that Roformer.generate takes (BOS first)"""
-    p = torch.cat([prompt_tokens.new_full((1,), lm.semantic_bos_token_id), prompt_tokens.reshape(-1)])
+    """semantic ids [Tp] -> the decoder prompt [rows, 1 + Tp] that Roformer.generate and Llama.generate take (BOS first)"""
+    bos = lm.config.bos_token_id - lm.semantic_token_shift if hasattr(lm, "llama") else lm.semantic_bos_token_id      # (the Llama's K, in returned numbering)
+    p = torch.cat([prompt_tokens.new_full((1,), bos), prompt_tokens.reshape(-1)])
     return p[None].expand(rows, -1).contiguous()
 
 
@@ -157,14 +158,45 @@ def text2semantic(lm, phones, tones, spk_id=1, max_length=1024, num_beams=1, no_
     return tok[:, first:]
 
 
-def text2semantic_llama(lm, phones, tones, spk_id=1, max_length=1024, no_repeat_ngram_size=0):
-    """`text2semantic` for the decoder-only Llama (reference llama.py:121-184): its generate returns the generated semantic ids alone (no BOS in
-    front, the shift subtracted); max_length counts the L + 3 prompt ids.  One utterance: phones, tones [1, L]."""
+def text2semantic_llama(lm, phones, tones, spk_id=1, max_length=1024, no_repeat_ngram_size=0, semantic_prompt=None, keep_prompt=False):
+    """`text2semantic` for the decoder-only Llama (reference llama.py:121-184): its generate returns the ids behind the semantic BOS alone (no BOS
+    in front, the shift subtracted); max_length counts the L + 3 prompt ids and the prompt's tokens.  One utterance: phones, tones [1, L].
+    semantic_prompt [1,P] (BOS first): the decode continues it; its P - 1 tokens are stripped unless keep_prompt."""
     tok = lm.generate(phones, tones, attention_mask=None, use_cache=None, max_length=max_length, do_sample=True, temperature=1.0, top_k=5, top_p=1.0,
                       repetition_penalty=1.0, num_beams=1, no_repeat_ngram_size=no_repeat_ngram_size, early_stopping=True,
-                      spk_id=torch.ones_like(phones) * spk_id, end_gate_threshold=None)
+                      spk_id=torch.ones_like(phones) * spk_id, end_gate_threshold=None,
+                      **({} if semantic_prompt is None else {"semantic_prompt": semantic_prompt}))
     eos = lm.config.eos_token_id - lm.semantic_token_shift
-    return tok[:, :-1] if bool((tok[:, -1] == eos).all()) else tok
+    first = 0 if keep_prompt or semantic_prompt is None else semantic_prompt.shape[1] - 1
+    return tok[:, first:-1] if bool((tok[:, -1] == eos).all()) else tok[:, first:]
+
+
+def text2semantic_llama_candidates(lm, phones, tones, spk_id=1, max_length=1024, candidates=2, no_repeat_ngram_size=0, semantic_prompt=None,
+                                   keep_prompt=False):
+    """text2semantic_llama for one utterance with N sampled candidates decoded as one batch and ranked with ONE Llama.score call: the row with the
+    highest mean log-prob per generated token (over the full vocabulary, a row counting up to and including its EOS) comes back as [1, n], cut
+    before its EOS.  semantic_prompt [1,P] (BOS first): every candidate continues it, its tokens are labelled -100 so that only the continuation
+    is counted, and they are stripped unless keep_prompt."""
+    if phones.shape[0] != 1:
+        raise ValueError("candidates are drawn for one utterance at a time (phones [1, L])")
+    ph, tn = phones.expand(candidates, -1).contiguous(), tones.expand(candidates, -1).contiguous()
+    tok = lm.generate(ph, tn, attention_mask=None, use_cache=None, max_length=max_length, do_sample=True, temperature=1.0, top_k=5, top_p=1.0,
+                      repetition_penalty=1.0, num_beams=1, no_repeat_ngram_size=no_repeat_ngram_size, early_stopping=True, spk_id=torch.ones_like(ph) * spk_id,
+                      end_gate_threshold=None, **({} if semantic_prompt is None else {"semantic_prompt": semantic_prompt.expand(candidates, -1).contiguous()}))
+    n_prompt = 0 if semantic_prompt is None else semantic_prompt.shape[1] - 1
+    eos = lm.config.eos_token_id - lm.semantic_token_shift
+    # a row's length: up to and including its first EOS behind the prompt (an EOS or pad id inside the prompt must not end the row)
+    stop = tok[:, n_prompt:] == eos
+    length = torch.where(stop.any(1), stop.int().argmax(1) + 1 + n_prompt, torch.full_like(tok[:, 0], tok.shape[1]))
+    mask = (torch.arange(tok.shape[1], device=tok.device)[None] < length[:, None]).to(torch.int64)
+    labels = tok.clone()
+    labels[:, :n_prompt] = -100
+    r = lm.score(ph, tn, tok, semantic_attention_mask=mask, labels=labels)
+    mean_lp = r.seq_logprob / r.ranks.ge(0).sum(1)
+    best = int(mean_lp.argmax())
+    print(f"candidates: mean log-prob per token {[round(float(v), 4) for v in mean_lp]}, kept {best}")
+    end = int(length[best]) - (1 if bool(stop[best].any()) else 0)
+    return tok[best][None, 0 if keep_prompt else n_prompt: end]
 
 
 def pick_candidate(lm, phones, tones, tok, spk_id=1, prompt_len=1):
@@ -423,8 +455,8 @@ def main(argv=None):
         if a.candidates < 1 or (a.candidates > 1 and a.num_beams != 1):
             raise SystemExit("--candidates needs N >= 1 and, for N > 1, sampling (--num_beams 1)")
         prompt = {}
-        if hasattr(lm, "llama") and (a.prompt_tokens or a.prompt_audio or a.prompt_phones or a.candidates > 1 or a.num_beams > 1):
-            raise SystemExit("the Llama LM takes --phones alone: prompts, --candidates and --num_beams are the RoFormer's")
+        if hasattr(lm, "llama") and a.num_beams > 1:
+            raise SystemExit("beam search is not built for the Llama LM: --num_beams is the RoFormer's (prompts and --candidates work with both)")
         if a.prompt_tokens and a.prompt_audio:
             raise SystemExit("--prompt_tokens and --prompt_audio both name the prompt: give one")
         if a.prompt_phones:
@@ -432,8 +464,10 @@ def main(argv=None):
         if a.prompt_tokens or a.prompt_audio:
             ptok = torch.from_numpy(np.load(a.prompt_tokens).astype(np.int64)).to(dev) if a.prompt_tokens else tokens_from_audio(a, codebook, dev)
             prompt = dict(semantic_prompt=with_bos(lm, ptok), keep_prompt=a.keep_prompt)
-        if hasattr(lm, "llama"):      # the decoder-only LM: sampling from the phones alone
-            tokens = text2semantic_llama(lm, pt[0:1], pt[1:2], a.spk_id, a.max_length, a.no_repeat_ngram_size)
+        if hasattr(lm, "llama"):      # the decoder-only LM: sampling, optionally from a prompt and with ranked candidates
+            fn = text2semantic_llama if a.candidates == 1 else text2semantic_llama_candidates
+            tokens = fn(lm, pt[0:1], pt[1:2], a.spk_id, a.max_length, **({} if a.candidates == 1 else {"candidates": a.candidates}),
+                        no_repeat_ngram_size=a.no_repeat_ngram_size, **prompt)
         elif a.candidates > 1:
             tokens = text2semantic_candidates(lm, pt[0:1], pt[1:2], a.spk_id, a.max_length, a.candidates, a.no_repeat_ngram_size, **prompt)
         else:

@@ -12,6 +12,9 @@
 //   attention      one workgroup per (row, query head) over the keys 0 .. pos of kv head h / (heads / kv_heads)
 //   MLP            gate and up in one pass with silu(g) * u in the epilogue; down and o_proj add the residual in theirs
 //   head           the final norm fused in; only the columns first_free_id .. vocab (the bad-word ban makes the others unobservable)
+//   scoring        lds_llama_score: ONE causal pass over all B * S rows of given streams through the same kernels (a row's position is all that
+//                  tells it from a decode step), then the head over the WHOLE vocabulary -- the low columns from a second packed matrix, the
+//                  columns first_free_id .. by the decode's own launch at another column address -- and lm.hip's row statistics and loss
 #include "../../include/lds.h"
 #include "kernels.h"
 #include "lm_common.h"
@@ -54,6 +57,20 @@ __global__ void __launch_bounds__(256) ll_init_kernel(const int64_t* __restrict_
             t -= shift;
         }
         stok[(long long)b * cap + l] = t;
+    }
+}
+// the start of a scoring pass, one workgroup per row: the same shifted ids over cap = S slots, len null = S everywhere (no host copy feeds it)
+__global__ void __launch_bounds__(256) ll_score_init_kernel(const int64_t* __restrict__ ids, int S, const int32_t* __restrict__ len, int vocab, int shift, int pad_s,
+                                                            int64_t* __restrict__ stok) {
+    const int b = blockIdx.x, n = len ? len[b] : S;
+    for (int l = threadIdx.x; l < S; l += 256) {
+        long long t = pad_s;
+        if (l < n) {
+            t = ids[(long long)b * S + l];
+            t = (t < 0) ? 0 : (t >= vocab ? vocab - 1 : t);
+            t -= shift;
+        }
+        stok[(long long)b * S + l] = t;
     }
 }
 // tokens = stok + shift: the ids of the model's vocabulary again
@@ -334,7 +351,7 @@ struct LlLayer { float *nw_attn = nullptr, *wqkv = nullptr, *wo = nullptr, *nw_m
 struct lds_llama {
     lds_llama_cfg cfg;
     std::vector<void*> bufs;
-    float *embed = nullptr, *cs = nullptr, *nw_final = nullptr, *head = nullptr;
+    float *embed = nullptr, *cs = nullptr, *nw_final = nullptr, *head = nullptr, *head_lo = nullptr;
     std::vector<LlLayer> layers;
     ~lds_llama() { for (void* p : bufs) (void)hipFree(p); }
     float* up(const std::vector<float>& h) {
@@ -420,6 +437,8 @@ extern "C" int lds_llama_create(const lds_llama_cfg* cfg, int n, const char* con
     ok = ok && (L->nw_final = ll_vec_up(L, T, p + "norm.weight", H)) != nullptr;
     // the head's observable columns only: rows first_free_id .. vocab of lm_head.weight
     ok = ok && (L->head = ll_linear_up(L, T, {{"llama.lm_head.weight", c.vocab - c.first_free_id}}, H, c.first_free_id, c.vocab)) != nullptr;
+    // and the columns below, which only scoring looks at (HF's log_softmax runs over the whole vocabulary): rows 0 .. first_free_id, a matrix of its own
+    if (c.first_free_id > 0) ok = ok && (L->head_lo = ll_linear_up(L, T, {{"llama.lm_head.weight", c.first_free_id}}, H, 0, c.vocab)) != nullptr;
     if (ok) {
         // HF LlamaRotaryEmbedding (default rope): angle = fp32(position) * inv_freq as an fp32 product, cos / sin of THAT angle.  inv_freq =
         // theta^(-2i/d) in fp32; a caller that has HF's own numbers hands them in (torch's vectorised pow is not correctly rounded, and one ulp
@@ -613,5 +632,80 @@ extern "C" int lds_llama_generate(lds_llama* L, const int64_t* input_ids, const 
     int n_tokens = 0;
     for (int b = 0; b < B; ++b) n_tokens = len[b] > n_tokens ? len[b] : n_tokens;
     *n_tokens_host = n_tokens;
+    return LDS_OK;
+}
+
+// ---- teacher-forced scoring: the decoder layers over all B * S rows in one causal pass (LlRows with L = S: row n = b * S + l at position l, its
+//      keys the slots 0 .. l of a cache of S slots), then the head over row chunks of kLlScoreChunk rows through one reused buffer (or straight
+//      into logits_out), each chunk followed by its row statistics.  One layer's cache at a time: layer i's keys are dead once its rows are done. ----
+namespace {
+constexpr int kLlScoreChunk = 256;
+struct LlScoreWs { LlWs w; float* chunk; double* psum; int32_t* pcnt; };
+void ll_score_plan(const lds_llama* L, LlArena& A, int B, int S, LlScoreWs& s) {
+    const lds_llama_cfg& c = L->cfg;
+    const size_t N = (size_t)B * S, QD = (size_t)c.heads * c.head_dim, KD = (size_t)c.kv_heads * c.head_dim;
+    LlWs& w = s.w;
+    w.x = A.f(N * c.hidden); w.q = A.f(N * QD); w.ctx = A.f(N * QD); w.ff = A.f(N * c.inter);
+    w.logits = nullptr; w.flags = nullptr; w.plen = nullptr;
+    w.stok = (int64_t*)A.f(2 * N);
+    float *kc = A.f(N * KD), *vc = A.f(N * KD);
+    w.kc.assign(c.layers, kc); w.vc.assign(c.layers, vc);
+    s.chunk = A.f((size_t)kLlScoreChunk * c.vocab);
+    s.psum = (double*)A.f(2 * (size_t)B);
+    s.pcnt = (int32_t*)A.f((size_t)B);
+}
+// the shape checks that need no model, then the model's
+int ll_score_check(const lds_llama* L, int B, int S) {
+    if (B < 1) return ll_fail(LDS_EINVAL, "scoring needs B >= 1, got %d", B);
+    if (S < 2 || S > kLlMaxLength) return ll_fail(LDS_EINVAL, "stream length %d out of range for scoring (2 .. %d)", S, kLlMaxLength);
+    // the linears take 8 rows per workgroup along grid.y
+    if ((long long)B * S > 8 * 65535LL) return ll_fail(LDS_EINVAL, "batch too large for one scoring call (B * S <= 524280, got %lld)", (long long)B * S);
+    if (!L) return ll_fail(LDS_EINVAL, "null handle");
+    if (S > L->cfg.max_pos) return ll_fail(LDS_EINVAL, "stream length %d exceeds max_position_embeddings %d", S, L->cfg.max_pos);
+    return LDS_OK;
+}
+}  // namespace
+
+extern "C" int lds_llama_score_workspace_bytes(const lds_llama* L, int B, int S, size_t* out) {
+    if (int r = ll_score_check(L, B, S)) return r;
+    if (!out) return ll_fail(LDS_EINVAL, "bad argument");
+    LlArena A(nullptr, 0);
+    LlScoreWs s;
+    ll_score_plan(L, A, B, S, s);
+    *out = A.used;
+    return LDS_OK;
+}
+
+extern "C" int lds_llama_score(lds_llama* L, const int64_t* input_ids, const int32_t* ids_len, const int64_t* labels, int B, int S, float* logprobs, int32_t* ranks,
+                               float* loss, int32_t* n_counted, float* logits_out, void* ws, size_t ws_bytes, void* stream) {
+    if (int r = ll_score_check(L, B, S)) return r;
+    if (!input_ids || !logprobs || !ranks || !loss || !n_counted || !ws) return ll_fail(LDS_EINVAL, "null argument");
+    const lds_llama_cfg& c = L->cfg;
+    hipStream_t st = (hipStream_t)stream;
+    LlArena A(ws, ws_bytes);
+    LlScoreWs s;
+    ll_score_plan(L, A, B, S, s);
+    if (!A.ok) return ll_fail(LDS_ENOMEM, "Llama scoring workspace too small: need %zu bytes", A.used);
+    const int H = c.hidden, V = c.vocab, lo = c.first_free_id, N = B * S;
+    if (!labels) labels = input_ids;      // the loader's choice (dataloader.py:182-183)
+    // slots at and beyond a row's length are filled from PAD, as in the prefill: their rows are computed and never counted, and no counted
+    // row's query sees their keys (row l reads the slots 0 .. l)
+    hipLaunchKernelGGL(ll_score_init_kernel, dim3(B), dim3(256), 0, st, input_ids, S, ids_len, c.vocab, lo, c.pad - lo, s.w.stok);
+    LL_HIP(hipGetLastError());
+    const LlRows rows{nullptr, S, 0, S};
+    hipLaunchKernelGGL(ll_embed_kernel, dim3(N), dim3(256), 0, st, (const float*)L->embed, (const int64_t*)s.w.stok, rows, lo, c.vocab, H, s.w.x);
+    LL_HIP(hipGetLastError());
+    if (int r = ll_layers(L, s.w, N, rows, S, st)) return r;
+    for (int r0 = 0; r0 < N; r0 += kLlScoreChunk) {
+        const int nr = (N - r0 < kLlScoreChunk) ? N - r0 : kLlScoreChunk;
+        const float* x = s.w.x + (size_t)r0 * H;
+        float* lg = logits_out ? logits_out + (size_t)r0 * V : s.chunk;
+        // rows of width vocab: the low columns from their own matrix, the columns first_free_id .. by the decode's launch -- the same fmaf chain per
+        // output, only the column's address differs
+        if (lo > 0) LL_HIP(ll_linear<LL_PLAIN>(x, H, L->nw_final, c.eps, L->head_lo, nullptr, lo, nullptr, lg, V, nr, st));
+        LL_HIP(ll_linear<LL_PLAIN>(x, H, L->nw_final, c.eps, L->head, nullptr, V - lo, nullptr, lg + lo, V, nr, st));
+        LL_HIP(lm_launch_score_rows(lg, r0, nr, V, S, labels, ids_len, logprobs, ranks, st));
+    }
+    LL_HIP(lm_launch_score_loss(logprobs, ranks, B, S - 1, s.psum, s.pcnt, loss, n_counted, st));
     return LDS_OK;
 }

@@ -401,7 +401,7 @@ __global__ void __launch_bounds__(256) lm_score_rows_kernel(const float* __restr
     }
     const float* lg = logits + (long long)blockIdx.x * V;
     const float ly = lg[y];
-    float m = -INFINITY, cnt = 0.f;      // the count stays below V <= 8192: exact in fp32 in any order
+    float m = -INFINITY, cnt = 0.f;      // the count stays below V (<= 8300 for the Llama's whole vocabulary), far below 2^24: exact in fp32 in any order
     for (int c = tid; c < V; c += 256) {
         const float v = lg[c];
         m = fmaxf(m, v);
@@ -1817,14 +1817,24 @@ extern "C" int lds_lm_score(lds_lm* lm, const float* enc, const int32_t* enc_len
         const LmRows hrows{s.w.ctx + (size_t)r0 * H, &lm->head_ln};
         float* lg = logits_out ? logits_out + (size_t)r0 * V : s.chunk;
         LM_HIP(lm_dln<0>(lm->head_d, hrows, H, nullptr, c.eps, lg, V, rows, st));
-        hipLaunchKernelGGL(lm_score_rows_kernel, dim3(rows), dim3(256), 0, st, (const float*)lg, (long long)r0, V, T, labels, sem_len, logprobs, ranks);
-        LM_HIP(hipGetLastError());
+        LM_HIP(lm_launch_score_rows(lg, r0, rows, V, T, labels, sem_len, logprobs, ranks, st));
     }
-    hipLaunchKernelGGL(lm_score_rowsum_kernel, dim3(B), dim3(256), 0, st, (const float*)logprobs, (const int32_t*)ranks, T - 1, s.psum, s.pcnt);
-    LM_HIP(hipGetLastError());
-    hipLaunchKernelGGL(lm_score_loss_kernel, dim3(1), dim3(64), 0, st, (const double*)s.psum, (const int32_t*)s.pcnt, B, loss, n_counted);
-    LM_HIP(hipGetLastError());
+    LM_HIP(lm_launch_score_loss(logprobs, ranks, B, T - 1, s.psum, s.pcnt, loss, n_counted, st));
     return LDS_OK;
+}
+
+// (declared in lm_common.h: llama.hip's scoring takes its row statistics and its loss from the same kernels)
+hipError_t lds::lm_launch_score_rows(const float* logits, long long n0, int rows, int V, int T, const int64_t* labels, const int32_t* len, float* lp, int32_t* rank,
+                                     hipStream_t st) {
+    hipLaunchKernelGGL(lm_score_rows_kernel, dim3(rows), dim3(256), 0, st, logits, n0, V, T, labels, len, lp, rank);
+    return hipGetLastError();
+}
+hipError_t lds::lm_launch_score_loss(const float* lp, const int32_t* rank, int B, int T1, double* psum, int32_t* pcnt, float* loss, int32_t* n_counted, hipStream_t st) {
+    hipLaunchKernelGGL(lm_score_rowsum_kernel, dim3(B), dim3(256), 0, st, lp, rank, T1, psum, pcnt);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(lm_score_loss_kernel, dim3(1), dim3(64), 0, st, (const double*)psum, (const int32_t*)pcnt, B, loss, n_counted);
+    return hipGetLastError();
 }
 
 // Test entry (include/lds_test.h): ONE token choice per row of `logits` [B][V] with the generate loop's own kernels, after a history of n_hist tokens

@@ -66,6 +66,13 @@ static __device__ __forceinline__ float block_sum256(float v, float* red) {
 hipError_t lm_launch_choice_rows(const lds_lm_decode_opts& o, int B, int V, const float* lg, float inv_temp, const float* u, int64_t* tokens, int cap, int step,
                                  int* unfinished, int eos, int pad, int* any_unf, const float* word, const float* type, const float* eg, const float* eb, float eps,
                                  int H, float* xnext, const int32_t* plen, int* rowlen, hipStream_t st);
+// ---- lm.hip's teacher-forced row statistics (lds_lm_score's definitions; lds_llama_score counts over its whole vocabulary with them).
+//      lm_launch_score_rows: `rows` logits rows [rows][V], the first being row n0 = b * T + t of the batch -> lp / rank [B][T-1] at the counted
+//      positions (t + 1 < len[b], labels[b][t + 1] in [0, V)), 0 / -1 elsewhere.  lm_launch_score_loss: the fixed-order double sum over the
+//      counted positions -> loss [1] = -sum / n, n_counted [1]; psum [B] doubles and pcnt [B] ints are scratch. ----
+hipError_t lm_launch_score_rows(const float* logits, long long n0, int rows, int V, int T, const int64_t* labels, const int32_t* len, float* lp, int32_t* rank,
+                                hipStream_t st);
+hipError_t lm_launch_score_loss(const float* lp, const int32_t* rank, int B, int T1, double* psum, int32_t* pcnt, float* loss, int32_t* n_counted, hipStream_t st);
 // the option checks that need no model (no device call); LDS_OK or LDS_EINVAL with a message
 int lm_check_opts(const lds_lm_decode_opts& o, const float* logits_out);
 constexpr int kLmMaxTopK = 64;            // survivors of the top-k filter

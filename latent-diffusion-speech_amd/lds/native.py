@@ -139,6 +139,8 @@ lds_llama_create                 i:pipppp
 lds_llama_destroy                v:p
 lds_llama_workspace_bytes        i:piiip
 lds_llama_generate               i:pppiiippppppzp
+lds_llama_score_workspace_bytes  i:piip
+lds_llama_score                  i:ppppiippppppzp
 lds_kmeans_workspace_bytes       i:qiip
 lds_kmeans_prepare               i:piipp
 lds_kmeans_assign                i:pqppiipppzp
@@ -1163,6 +1165,28 @@ class Llama(_Handle):
         stop = (toks == self.cfg["eos"]) & (torch.arange(n.value, device=toks.device)[None] >= plen[:, None])
         end = torch.where(stop.any(1), stop.int().argmax(1) + 1, torch.full_like(plen, n.value))
         return toks, logits[: int((end - plen).max())]
+
+    def score(self, input_ids, ids_len=None, labels=None, return_logits=False):
+        """Teacher-forced scoring (lds_llama_score): input_ids / labels int64 [B,S] on the device (labels None = input_ids), ids_len int32 [B]
+        on the device or None.  Returns (logprobs [B,S-1], ranks int32 [B,S-1], loss [], n_counted int32 [], logits [B,S,vocab] or None), all
+        on the device; nothing synchronises."""
+        import torch
+        if input_ids.dim() != 2:
+            raise ValueError(f"input_ids must be [B, S], got {tuple(input_ids.shape)}")
+        B, S = (int(v) for v in input_ids.shape)
+        if labels is not None and tuple(labels.shape) != (B, S):
+            raise ValueError(f"labels must have input_ids' shape {(B, S)}, got {tuple(labels.shape)}")
+        ids = input_ids.contiguous()
+        lab = labels.contiguous() if labels is not None else None
+        ws = self._workspace("lds_llama_score_workspace_bytes", ids.device, B, S)
+        lp = torch.empty(B, S - 1, dtype=torch.float32, device=ids.device)
+        ranks = torch.empty(B, S - 1, dtype=torch.int32, device=ids.device)
+        loss = torch.empty((), dtype=torch.float32, device=ids.device)
+        n = torch.empty((), dtype=torch.int32, device=ids.device)
+        logits = torch.empty(B, S, self.cfg["vocab"], dtype=torch.float32, device=ids.device) if return_logits else None
+        check(lib().lds_llama_score(self.h, _dev(ids, torch.int64), _dev_or_null(ids_len, torch.int32), _dev_or_null(lab, torch.int64), B, S, _dev(lp),
+                                    _dev(ranks), _dev(loss), _dev(n), _dev_or_null(logits), _dev(ws), ws.numel(), _stream()))
+        return lp, ranks, loss, n, logits
 
 
 # ---- k-means semantic tokenizer (lds_kmeans_*): thin wrappers; X [N, D] and C [K, D] contiguous fp32 device tensors ----

@@ -10,7 +10,9 @@ bans every id below 108 (llama.py:170), returns the generated ids minus 108 with
 to HF's processors: with a repetition penalty the semantic tokens 0 and 1 are penalised from the first step on (ids 108 and 109 are in every
 prompt), and the prompt's n-grams count for the n-gram ban.
 
-Scope: phone mode, inference, num_beams 1 (greedy and sampling, each with the repetition penalty and n-gram blocking).
+Scope: phone mode, inference, num_beams 1 (greedy and sampling, each with the repetition penalty and n-gram blocking), each optionally
+continuing a semantic prompt (`semantic_prompt`, one length per row); `score` / `score_ids`: teacher-forced log-probs, loss and ranks over
+the whole vocabulary in one causal pass (the reference `forward`'s numbers, no gradients).
 Not built (each raises): mode 'text', the end gate, beam search, `forward` (training), attention_bias / mlp_bias, a rope type other than
 default, hidden_act other than silu."""
 import numpy as np
@@ -18,7 +20,7 @@ import torch
 
 from lds import arch, native
 from lds.paramtree import ParamTree
-from text2semantic.roformer.roformer import _get
+from text2semantic.roformer.roformer import LMScore, _get
 
 
 def get_model(n_spk, **kwargs):
@@ -144,10 +146,178 @@ class Llama(ParamTree):
             ids[b, n + 3:] = self.cfg["pad"]
         return ids, [n + 3 for n in lens]
 
+    @staticmethod
+    def _mask_to_lengths(mask, shape, name):
+        """a right-padded HF mask [B, N] (ones then zeros; rows of zeros allowed) -> the rows' lengths as a list of ints; None = N everywhere"""
+        if mask is None:
+            return [int(shape[1])] * int(shape[0])
+        if tuple(mask.shape) != tuple(shape):
+            raise ValueError(f"{name} must have the shape {tuple(shape)}, got {tuple(mask.shape)}")
+        m = mask.to(torch.int64)
+        n = m.sum(-1)
+        if not bool(((torch.arange(m.shape[1], device=m.device)[None] < n[:, None]).to(torch.int64) == m).all()):
+            raise NotImplementedError(f"only right-padded batches are built: every {name} row must be ones followed by zeros")
+        return [int(v) for v in n.tolist()]
+
+    def _streams(self, phone, attention_mask, tails):
+        """rows [108, phones_b, 109, tails[b] ...] (tails: one 1-D int64 tensor of model ids per row), right-padded with the config's pad id
+        -> (ids [B, S] int64 on phone's device, the rows' lengths, the rows' phone counts)"""
+        head, hl = self.input_ids(phone, attention_mask)
+        nph = [n - 3 for n in hl]
+        lens = [n + 2 + int(t.numel()) for n, t in zip(nph, tails)]
+        ids = torch.full((len(lens), max(lens)), self.cfg["pad"], dtype=torch.int64, device=phone.device)
+        for b, (n, t) in enumerate(zip(nph, tails)):
+            ids[b, :n + 2] = head[b, :n + 2]
+            ids[b, n + 2:lens[b]] = t.to(device=phone.device, dtype=torch.int64)
+        return ids, lens, nph
+
+    def _check_prompt(self, B, semantic_prompt, prompt_attention_mask):
+        """the checks of `generate`'s semantic prompt -> one 1-D tensor of SHIFTED (model) ids per row, the semantic BOS first"""
+        K = self.cfg["semantic_kmeans_num"]
+        if semantic_prompt.dim() != 2 or semantic_prompt.shape[0] != B or semantic_prompt.shape[1] < 1:
+            raise ValueError(f"semantic_prompt must be [B, P] with B = {B} and P >= 1, got {tuple(semantic_prompt.shape)}")
+        lens = self._mask_to_lengths(prompt_attention_mask, semantic_prompt.shape, "prompt_attention_mask")
+        sp = semantic_prompt.detach().to("cpu", torch.int64)
+        tails = []
+        for b, pl in enumerate(lens):
+            if pl < 1 or int(sp[b, 0]) != K:
+                raise ValueError(f"row {b}: semantic_prompt must start with the semantic BOS ({K})" + (f", got {int(sp[b, 0])}" if pl >= 1 else ""))
+            body = sp[b, :pl]
+            if bool(((body < 0) | (body > K + 2)).any()):
+                raise ValueError(f"row {b}: prompt ids inside the length must lie in 0 .. {K + 2}")
+            tails.append(body + self.semantic_token_shift)
+        return tails
+
+    @torch.no_grad()
+    def score_ids(self, input_ids, attention_mask=None, labels=None, return_logits=False):
+        """The `input_ids=` path of the reference's `forward` (llama.py:73-117, 103-114) without gradients: input_ids [B, S] of the model's
+        vocabulary, right-padded with attention_mask [B, S] (ones then zeros); labels [B, S] default to input_ids (dataloader.py:182-183), -100
+        is HF's ignore index.  One causal pass; position t of row b is counted when t + 1 lies inside the row and labels[b, t + 1] != -100
+        (HF's shift); log-probabilities and ranks are taken over the whole vocabulary, phone ids included, as HF's loss does.  Returns an
+        LMScore: loss [], token_logprobs [B, S - 1] (0 where not counted), ranks int32 [B, S - 1] (-1 where not counted), seq_logprob [B],
+        n_tokens int32 [], logits [B, S, vocab] or None."""
+        if input_ids.dim() != 2:
+            raise ValueError(f"input_ids must be [B, S], got {tuple(input_ids.shape)}")
+        B, S = input_ids.shape
+        if S < 2 or S > self.cfg["max_pos"]:
+            raise ValueError(f"input_ids needs 2 <= S <= max_position_embeddings = {self.cfg['max_pos']}, got S = {S}")
+        if labels is not None and tuple(labels.shape) != (B, S):
+            raise ValueError(f"labels must have input_ids' shape {(B, S)}, got {tuple(labels.shape)}")
+        lens = None if attention_mask is None else self._mask_to_lengths(attention_mask, (B, S), "attention_mask")
+        ids = input_ids.to(torch.int64)
+        labels = labels.to(device=ids.device, dtype=torch.int64) if labels is not None else None
+        ids_len = None if lens is None else torch.tensor(lens, dtype=torch.int32, device=ids.device)
+        # the library clamps ids on the way into the embedding: what it would hide is refused here (ids inside the lengths; labels may be -100)
+        V = self.cfg["vocab"]
+        inside = torch.ones_like(ids, dtype=torch.bool) if ids_len is None else torch.arange(S, device=ids.device)[None] < ids_len[:, None]
+        if bool((inside & ((ids < 0) | (ids >= V))).any()):
+            raise ValueError(f"input_ids inside the sequence lengths must lie in [0, {V})")
+        if labels is not None and bool((inside & (labels != -100) & ((labels < 0) | (labels >= V))).any()):
+            raise ValueError(f"labels inside the sequence lengths must be -100 or lie in [0, {V})")
+        if not input_ids.is_cuda:
+            raise RuntimeError("Llama.score_ids needs tensors on a HIP device (no CPU fallback)")
+        lp, ranks, loss, n, logits = self.native().score(ids, ids_len, labels, return_logits)
+        return LMScore(loss, lp, ranks, lp.double().sum(-1).float(), n, logits)
+
+    def semantic_lengths(self, semantic, semantic_attention_mask=None):
+        """the rows' token counts of `semantic` [B, T] in the numbering `generate` returns: a row ends behind its first K + 1 (EOS, kept) or
+        before its first K + 2 (pad), whichever comes first; a semantic_attention_mask (ones then zeros) decides instead"""
+        if semantic_attention_mask is not None:
+            return self._mask_to_lengths(semantic_attention_mask, semantic.shape, "semantic_attention_mask")
+        K = self.cfg["semantic_kmeans_num"]
+        out = []
+        for row in semantic.detach().to("cpu", torch.int64).tolist():
+            n = len(row)
+            for j, t in enumerate(row):
+                if t == K + 1 or t == K + 2:
+                    n = j + 1 if t == K + 1 else j
+                    break
+            out.append(n)
+        return out
+
+    def score_streams(self, phone, semantic, attention_mask=None, semantic_attention_mask=None, labels=None, append_eos=False):
+        """The id arithmetic of `score` (no device work beyond the caller's tensors): -> (ids [B, S] the right-padded streams, their lengths as a
+        list, labels [B, S] for lds_llama_score or None = ids, at [B, T (+ 1)] the stream position that predicts semantic token j, valid
+        [B, T (+ 1)] whether row b has a token j)"""
+        K, shift = self.cfg["semantic_kmeans_num"], self.semantic_token_shift
+        if semantic.dim() != 2 or semantic.shape[0] != phone.shape[0] or semantic.shape[1] < 1:
+            raise ValueError(f"semantic must be [B, T] with B = {phone.shape[0]} and T >= 1, got {tuple(semantic.shape)}")
+        B, T = semantic.shape
+        stream_labels = isinstance(labels, str)
+        if stream_labels and labels != "stream":
+            raise ValueError(f"labels must be None, 'stream' or a [B, T] tensor, got {labels!r}")
+        if labels is not None and not stream_labels and tuple(labels.shape) != (B, T):
+            raise ValueError(f"labels must have semantic's shape {(B, T)}, got {tuple(labels.shape)}")
+        sl = self.semantic_lengths(semantic, semantic_attention_mask)
+        sem = semantic.detach().to("cpu", torch.int64)
+        tails, tl = [], []
+        for b, n in enumerate(sl):
+            body = sem[b, :n]
+            if bool(((body < 0) | (body > K + 2)).any()):
+                raise ValueError(f"row {b}: semantic ids inside the length must lie in 0 .. {K + 2}")
+            tail = [torch.tensor([self.cfg["bos"]]), body + shift] + ([torch.tensor([self.cfg["eos"]])] if append_eos else [])
+            tails.append(torch.cat(tail))
+            tl.append(n + (1 if append_eos else 0))
+            if tl[-1] < 1:
+                raise ValueError(f"row {b}: no semantic token to score")
+        ids, lens, nph = self._streams(phone, attention_mask, tails)
+        S, Tout = ids.shape[1], T + (1 if append_eos else 0)
+        if S > self.cfg["max_pos"]:
+            raise ValueError(f"the longest stream has {S} ids, max_position_embeddings is {self.cfg['max_pos']}")
+        dev = ids.device
+        # token j of row b is id nph[b] + 3 + j of the stream, predicted at position nph[b] + 2 + j
+        first = torch.tensor(nph, device=dev)[:, None] + 2
+        j = torch.arange(Tout, device=dev)[None]
+        valid = j < torch.tensor(tl, device=dev)[:, None]
+        at = torch.where(valid, first + j, torch.zeros_like(j))      # [B, Tout] indices into [B, S - 1]
+        if stream_labels:
+            lab = None      # = input_ids
+        else:
+            lab = torch.full_like(ids, -100)
+            tgt = ids.gather(1, at + 1)
+            if labels is not None:
+                given = labels.to(device=dev, dtype=torch.int64)
+                if bool((valid[:, :T] & (given != -100) & ((given < 0) | (given > K + 2))).any()):
+                    raise ValueError(f"labels inside the lengths must be -100 or lie in 0 .. {K + 2}")
+                keep = torch.ones_like(valid)
+                keep[:, :T] = given != -100
+                tgt = tgt.clone()
+                tgt[:, :T] = torch.where(given != -100, given + shift, tgt[:, :T])
+                tgt = torch.where(keep, tgt, torch.full_like(tgt, -100))
+            lab.scatter_(1, torch.where(valid, at + 1, torch.zeros_like(at)), torch.where(valid, tgt, lab[:, :1].expand_as(tgt)))
+            lab[:, 0] = -100      # (the slot the rows behind their ends were pointed at; position 0 is never a target)
+        return ids, lens, lab, at, valid
+
+    @torch.no_grad()
+    def score(self, phone, tone, semantic, attention_mask=None, semantic_attention_mask=None, labels=None, append_eos=False, return_logits=False):
+        """Teacher-forced scoring of the semantic part of the stream.  semantic [B, T] is in the numbering `generate` returns (token t, EOS =
+        K + 1, pad = K + 2; no BOS); row b's stream is [108, phones_b, 109, 108 + K, semantic_b + 108] with the semantic EOS appended when
+        append_eos -- the reference `forward`'s stream (llama.py:98-101).  A row's tokens end as `semantic_lengths` says.  `tone` has no
+        effect, as in `generate`.
+        Returns an LMScore whose arrays run per semantic token, [B, T] ([B, T + 1] with append_eos): entry j is the log-probability and the
+        rank, over the full vocabulary, of token j given everything before it (0 / -1 behind a row's end and where the label is -100);
+        seq_logprob [B] their sums.  labels: None = the semantic targets only (loss = their mean negative log-probability: reranking);
+        "stream" = every id of the stream, phones included (loss = the reference's training loss, labels = input_ids); a [B, T] tensor in
+        semantic's numbering with -100 holes (an appended EOS stays a target).  With return_logits, logits [B, T (+ 1), K + 3] are the raw logits
+        of the ids 108 .. vocab that predict token j: `generate(..., return_logits=True)`'s, bit for bit, for tokens that `generate` produced."""
+        ids, lens, lab, at, valid = self.score_streams(phone, semantic, attention_mask, semantic_attention_mask, labels, append_eos)
+        if not (phone.is_cuda and semantic.is_cuda):
+            raise RuntimeError("Llama.score needs tensors on a HIP device (no CPU fallback)")
+        B, dev, shift = ids.shape[0], ids.device, self.semantic_token_shift
+        ids_len = torch.tensor(lens, dtype=torch.int32, device=dev)
+        lp, ranks, loss, n, logits = self.native().score(ids, ids_len, lab, return_logits)
+        tok_lp = torch.where(valid, lp.gather(1, at), torch.zeros_like(lp[:, :1]))
+        tok_rk = torch.where(valid, ranks.gather(1, at), torch.full_like(ranks[:, :1], -1))
+        out_logits = None
+        if return_logits:
+            picked = logits[torch.arange(B, device=dev)[:, None], at][:, :, shift:]
+            out_logits = torch.where(valid[:, :, None], picked, torch.zeros_like(picked))
+        return LMScore(loss, tok_lp, tok_rk, tok_lp.double().sum(-1).float(), n, out_logits)
+
     @torch.no_grad()
     def generate(self, phone, tone, attention_mask=None, use_cache=None, max_length=1024, do_sample=True, temperature=1.0, top_k=5, top_p=1.0,
                  repetition_penalty=1.0, num_beams=1, no_repeat_ngram_size=0, early_stopping=True, spk_id=None, end_gate_threshold=None,
-                 return_logits=False, uniforms=None, **kwargs):
+                 return_logits=False, uniforms=None, semantic_prompt=None, prompt_attention_mask=None, **kwargs):
         """The reference's `generate` (llama.py:121-184): phone [1, L] -> the generated semantic ids [1, n] (shift subtracted, EOS = K + 1 kept);
         max_length is the total length, the L + 3 prompt ids included.  tone, spk_id, use_cache and early_stopping (forced off with one beam,
         llama.py:154) have no effect, as there.
@@ -155,7 +325,12 @@ class Llama(ParamTree):
         nothing that reads it): row b is [108, phones_b, 109, 108 + K] with its own length and decodes exactly as it would alone; returned rows
         are cropped to the longest and padded with K + 2.  return_logits: also logits [steps, B, K + 3], logits[s][b] = HF's raw logits (before
         any processor) of the ids 108 .. vocab that chose row b's s-th generated token.  uniforms [max_length - 1, B] (sampling): row b's s-th
-        generated token uses uniforms[s][b]; None draws them with torch.rand."""
+        generated token uses uniforms[s][b]; None draws them with torch.rand.
+        semantic_prompt [B, P] int64 in the returned numbering, the semantic BOS (K) first like Roformer.generate's, right-padded with
+        prompt_attention_mask [B, P] (ones then zeros) when the rows' prompts differ in length: row b's stream is [108, phones_b, 109,
+        semantic_prompt_b + 108] and the decode continues it -- a voice or prosody prompt, or the previous sentence's tail.  The returned rows
+        stay "the ids behind the semantic BOS, minus 108": they begin with the prompt's tokens.  max_length counts everything; the repetition
+        penalty and the n-gram ban see the prompt, as HF would; logits[s][b] chose row b's s-th GENERATED token."""
         if end_gate_threshold is not None:
             # reference llama.py:11-20 sets the WHOLE score row to +inf once softmax(scores)[eos] passes the threshold: greedy then picks
             # id 0 and sampling makes torch.multinomial raise on NaN probabilities -- there is no coherent behaviour to restate
@@ -171,13 +346,22 @@ class Llama(ParamTree):
         top_k = 0 if top_k is None else int(top_k)
         if do_sample and not (0 <= top_k <= 64):
             raise NotImplementedError("sampling is built for top_k = None / 0 (no filter) or 1 <= top_k <= 64")
-        ids, lens = self.input_ids(phone, attention_mask)
+        if semantic_prompt is None and prompt_attention_mask is not None:
+            raise ValueError("prompt_attention_mask needs semantic_prompt")
+        if semantic_prompt is None:
+            ids, lens = self.input_ids(phone, attention_mask)
+            first = lens      # where each row's returned ids begin: behind the semantic BOS
+        else:      # everything about the prompt is checked before any device work
+            tails = self._check_prompt(phone.shape[0], semantic_prompt, prompt_attention_mask)
+            ids, lens, nph = self._streams(phone, attention_mask, tails)
+            first = [n + 3 for n in nph]
         B = ids.shape[0]
         if B > 64:
             raise ValueError(f"a Llama decode takes at most 64 rows, got {B}")
         for b, n in enumerate(lens):
             if n >= max_length:      # HF raises ValueError as well: max_length counts the prompt
-                raise ValueError(f"row {b}: the prompt has {n} ids (phones + 3), which leaves no room below max_length = {max_length} (the total length)")
+                raise ValueError(f"row {b}: the prompt has {n} ids (phones + 3" + (f" + {n - first[b]} prompt tokens" if n > first[b] else "") +
+                                 f"), which leaves no room below max_length = {max_length} (the total length)")
         if max_length > self.cfg["max_pos"]:
             raise ValueError(f"max_length = {max_length} exceeds max_position_embeddings = {self.cfg['max_pos']}")
         if not phone.is_cuda:
@@ -200,8 +384,8 @@ class Llama(ParamTree):
         for b, n in enumerate(lens):      # a row ends with its first EOS behind the prompt, else with the returned rows
             hit = (host[b, n:] == self.cfg["eos"]).nonzero()
             ends.append(n + int(hit[0]) + 1 if hit.numel() else toks.shape[1])
-        out = torch.full((B, max(e - n for e, n in zip(ends, lens))), self.cfg["pad"], dtype=torch.int64, device=toks.device)
-        for b, (e, n) in enumerate(zip(ends, lens)):
+        out = torch.full((B, max(e - n for e, n in zip(ends, first))), self.cfg["pad"], dtype=torch.int64, device=toks.device)
+        for b, (e, n) in enumerate(zip(ends, first)):
             out[b, : e - n] = toks[b, n:e]
         out = out - self.semantic_token_shift
         return (out, logits) if return_logits else out

@@ -18,6 +18,11 @@
                        further decode step at --batch, event time on the stream, median of --reps; the RoFormer's step time from the same
                        process for scale; and, where transformers imports, HF's LlamaForCausalLM.generate with the same weights on the
                        same device.  --json FILE keeps the rows.
+  --llama --score      one teacher-forced scoring call (lds_llama_score through lds.native, without and with the logits) over the stream of a
+                       greedy decode to S = 67 + N ids for every N of --tokens, next to that decode -- the only other way to visit those
+                       positions; event time on the stream, median of --reps, same process.  (--lib: the decode alone, for a build without it.)
+  --llama --prompt P.. Llama.generate(semantic_prompt=...) with P prompt tokens (BOS included) and --new tokens, next to the unprompted decode to
+                       the same total length, which visits the prompt's positions step by step.
 
 With --num_beams > 1, --greedy, --score, --prompt or more than one length the EOS logit is biased far down, so that every sequence runs to the
 full length and the time per step is that of a full decode."""
@@ -148,12 +153,50 @@ def llama_mode():
     P = L + 3
     hf = None
     try:
+        if a.score or a.prompt:
+            raise ImportError      # (those modes compare the library with itself)
         from transformers import LlamaConfig, LlamaForCausalLM
         hf = LlamaForCausalLM(LlamaConfig(vocab_size=m.cfg["vocab"], **conf)).cuda().eval()
         hf.load_state_dict({k[len("llama."):]: v for k, v in m.state_dict().items()}, strict=True)
     except ImportError:
-        print("transformers does not import here: no HF timing")
+        if not (a.score or a.prompt):
+            print("transformers does not import here: no HF timing")
     rows = []
+    if a.score or a.prompt:
+        for B in a.batch:
+            ph = torch.from_numpy((np.arange(B * L).reshape(B, L) * 7 % 107 + 1).astype(np.int64)).cuda()
+            m.generate(ph, ph, max_length=P + 8, do_sample=False)
+            for n in (a.tokens if a.score else a.prompt):
+                if a.score:      # the stream of a decode of n tokens: S = P + n ids, S - 1 scored positions, n decode steps
+                    dec_ms, tok = event_ms(lambda: m.generate(ph, ph, max_length=P + n, do_sample=False), a.reps)
+                    assert tok.shape == (B, n), tok.shape
+                    row = {"B": B, "S": P + n, "decode_steps": n, "decode_ms": dec_ms, "decode_us_per_step": dec_ms * 1e3 / n}
+                    if hasattr(m.native(), "score") and "lds_llama_score" in native.EXPORTS:
+                        ids = torch.cat([m.input_ids(ph)[0], tok + m.cfg["shift"]], dim=1)
+                        m.native().score(ids)
+                        sc_ms, _ = event_ms(lambda: m.native().score(ids), a.reps)
+                        lg_ms, _ = event_ms(lambda: m.native().score(ids, return_logits=True), a.reps)
+                        row.update(positions=B * (P + n - 1), score_ms=sc_ms, score_with_logits_ms=lg_ms, decode_over_score=dec_ms / sc_ms,
+                                   score_us_per_position=sc_ms * 1e3 / (B * (P + n - 1)))
+                else:      # n prompt tokens (BOS included), then --new generated ones
+                    sem = torch.from_numpy(np.random.default_rng(0).integers(0, K, size=(B, n)).astype(np.int64)).cuda()
+                    sem[:, 0] = K
+                    total = P - 1 + n + new
+                    m.generate(ph, ph, max_length=total, do_sample=False, semantic_prompt=sem)
+                    pr_ms, tok = event_ms(lambda: m.generate(ph, ph, max_length=total, do_sample=False, semantic_prompt=sem), a.reps)
+                    un_ms, tok0 = event_ms(lambda: m.generate(ph, ph, max_length=total, do_sample=False), a.reps)
+                    assert tok.shape == tok0.shape == (B, n - 1 + new), (tok.shape, tok0.shape)
+                    row = {"B": B, "prompt_tokens": n, "new_tokens": new, "total": total, "prompted_ms": pr_ms, "unprompted_same_total_ms": un_ms,
+                           "steps_prompted": new, "steps_unprompted": n - 1 + new, "saved_ms": un_ms - pr_ms}
+                rows.append(row)
+                print(row)
+        if a.json:
+            import json
+            what = ("one lds_llama_score call vs the cached greedy decode of the same stream" if a.score else
+                    "a prompted greedy Llama decode vs the unprompted decode to the same total length")
+            json.dump({"what": what + f" (64 phones, the reference example's width, EOS never wins); event time on the stream, median of {a.reps}", "rows": rows},
+                      open(a.json, "w"), indent=1)
+        return
     for B in a.batch:
         ph = torch.from_numpy((np.arange(B * L).reshape(B, L) * 7 % 107 + 1).astype(np.int64)).cuda()
 

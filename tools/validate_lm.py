@@ -11,7 +11,12 @@ loader does, labels = tokens, batch size 1.  The speaker id of every item is --s
 its loader meets their directories).  --synthetic scores seeded items under seeded weights (no checkpoint ships).
 
 The logits behind the numbers are the causal (prefix) ones that `generate` computes, not those of the reference's one-call forward on
-transformers 5.x, which sees the future tokens: on real weights the loss is the causal cross-entropy."""
+transformers 5.x, which sees the future tokens: on real weights the loss is the causal cross-entropy.
+
+--lm_type llama (or a checkpoint whose config.yaml names the Llama): Llama.score over the stream [108, phones, 109, 108 + K, tokens + 108, EOS]
+(reference llama.py:98-101).  "loss" and the accuracy are then those of labels = input_ids -- every id of the stream, phones included, over the
+full vocabulary: the reference's training loss (text2semantic/llama/dataloader.py:182-183; its forward is causal) -- and
+"semantic_loss" / "semantic_top<k>_acc" next to them count the semantic tokens and the EOS only."""
 import argparse
 import json
 import os
@@ -32,6 +37,7 @@ def parse_args(argv=None):
     ap.add_argument("-id", "--spk_id", type=int, default=1)
     ap.add_argument("-k", "--topk", type=int, default=5)
     ap.add_argument("--synthetic", action="store_true")
+    ap.add_argument("--lm_type", default="roformer", choices=("roformer", "llama"), help="which seeded LM --synthetic builds (a checkpoint's config.yaml names its own)")
     ap.add_argument("--synthetic_items", type=int, default=4)
     ap.add_argument("--synthetic_tokens", type=int, default=64)
     a = ap.parse_args(argv)
@@ -58,8 +64,32 @@ def load_items(path):
 
 
 @torch.no_grad()
+def validate_llama(lm, items, k=5):
+    """`validate` for the decoder-only Llama: per item the stream loss / accuracy (labels = input_ids) and the semantic-only ones, both from one
+    Llama.score call each; then the means over the items"""
+    dev = next(lm.parameters()).device
+    key = f"top{k}_acc"
+    rows = []
+    for name, phones, tones, tokens in items:
+        ph, tn = (torch.from_numpy(np.asarray(v).astype(np.int64))[None].to(dev) for v in (phones, tones))
+        sem = torch.from_numpy(np.asarray(tokens).astype(np.int64))[None].to(dev)
+        mask = torch.ones_like(sem)      # every given token counts, whatever its id
+        ids, lens, _, _, _ = lm.score_streams(ph, sem, semantic_attention_mask=mask, append_eos=True)
+        full = lm.score_ids(ids)      # labels = input_ids: the reference's training loss
+        part = lm.score(ph, tn, sem, semantic_attention_mask=mask, append_eos=True)
+        rows.append({"name": name, "tokens": int(full.n_tokens), "loss": float(full.loss), key: float((full.ranks[full.ranks >= 0] < k).float().mean()),
+                     "semantic_tokens": int(part.n_tokens), "semantic_loss": float(part.loss),
+                     "semantic_" + key: float((part.ranks[part.ranks >= 0] < k).float().mean())})
+    if not rows:
+        raise SystemExit("no items")
+    return dict({"items": rows}, **{f: float(np.mean([r[f] for r in rows])) for f in ("loss", key, "semantic_loss", "semantic_" + key)})
+
+
+@torch.no_grad()
 def validate(lm, items, spk_id=1, k=5):
     """-> {"items": [{"name", "tokens", "loss", "top<k>_acc"}], "loss", "top<k>_acc"}: the means over the items, as the reference's loop forms them"""
+    if hasattr(lm, "llama"):
+        return validate_llama(lm, items, k)
     dev = next(lm.parameters()).device
     key = f"top{k}_acc"
     rows = []
@@ -78,7 +108,8 @@ def main(argv=None):
     a = parse_args(argv)
     import infer_tts
     if a.synthetic:
-        lm, items = infer_tts.synthetic_lm("cuda"), synthetic_items(a.synthetic_items, a.synthetic_tokens)
+        lm = infer_tts.synthetic_llama("cuda") if a.lm_type == "llama" else infer_tts.synthetic_lm("cuda")
+        items = synthetic_items(a.synthetic_items, a.synthetic_tokens)
     else:
         lm, items = infer_tts.load_lm(a.model, "cuda"), load_items(a.data)
     res = validate(lm, items, a.spk_id, a.topk)
