@@ -159,8 +159,11 @@ typedef struct {                        /* lds_dconv_test with the encoders' epi
     const float* ln_gamma; const float* ln_beta;      /* host [C1], both or neither: LayerNorm over the channels of x1 folded into the (1x1) convolution;   */
     float ln_eps;                       /* its per-frame partials come from the epilogue of an identity convolution the entry runs  */
     int tile_batch, fmt;
+    int v_split;                        /* 0, or > 1 (fp32, 1x1): the QKV projection -- the last third of the rows in attention's VT layout, head dim v_split */
+    int cfg;                            /* 0 auto, else BM*1000000 + BN*1000 + BK*10 + NST                                           */
 } lds_dconv_ex_test;
-/* out dev [B][Co][To]; gnpart dev [B][Co/16][ceil(To/32)][2] or NULL */
+/* epilogue 1 (GEGLU; fp32 with the LayerNorm fold only): the transformer's FF1, Co = 2 x the output channels, out dev [B][Co/2][To].
+ * out dev [B][Co][To] (v_split: [B][2 Co/3][To] followed by the raw VT buffer [B][Co/3/D][ceil4(To)/4][D][4]); gnpart dev [B][Co/16][ceil(To/32)][2] or NULL */
 int lds_test_dconv_ex(const lds_dconv_ex_test* a, float* out, float* gnpart, int B, char* cfg_out, size_t cfg_cap, void* stream);
 /* one vocoder upsampler on conv_dma as the generator runs it: x dev [B][Ci][T] -> LeakyReLU(0.1) K4P copy with its pad frames zeroed -> polyphase
  * ConvTranspose1d(K = 2 stride, stride, padding (K - stride + 1) / 2; w host [Ci][Co][K], bias host [Co] or NULL) -> out (raw) and out_act

@@ -139,7 +139,6 @@ struct DmaKernel {
     static_assert(PER_TILE * (NST - 1) + NLATE <= 63 || !LATE, "vmcnt is a 6-bit field");
     f32x2 rsv[EARLY ? TM * TN * 8 : 1];
     float kbv[EARLY ? TM * 16 : 1];
-
     __device__ __forceinline__ DmaKernel(const DmaConvArgs& p_, float* s_) : p(p_), smem(s_) {}
 
     // k4p.h ragged_len / the vocoder's lengths, read through the constant address space: the lengths do not change during a launch, and so
@@ -432,17 +431,28 @@ struct DmaKernel {
     // entries and 4 bias quads per tile), for every argument set and by every lane -- no branch and no lane mask around them (see
     // wait_younger).  A launch without a residual, or a tile outside it, reads a buffer of zero bytes: zeros, as before.  Frames beyond To
     // read whatever the range check lets through; add_residual() does not use them.
+    // A LayerNorm-fold launch without a residual (the QKV projections) has no use for either: its slots fetch the fold's row constants
+    // instead, ln_c1 through the eight residual slots (8 bytes each: rows 8g + 4h + 2k + 0..1) and ln_c2 through the four bias quads, so
+    // they too have landed before the K loop ends (row_consts).  The choice is scalar: buffer base, size and steps; the loads are the same.
+    // (wave-uniform) a LayerNorm-fold launch without a residual: late_loads() fetches ln_c1 through the residual slots, ln_c2 through the bias slots
+    __device__ __forceinline__ bool ln_late() const { return LATE && KT == 1 && p.ln_part && !p.res; }      // (the fold belongs to 1x1 convolutions: the other kernels compile the choice out)
+    template <bool FOLD>      // (false: the fused pair's second phase, which never carries a LayerNorm fold -- its code stays as it was)
     __device__ __forceinline__ void late_loads() {
         static_assert(TM * TN == 1, "single-tile waves");
         const int tile0 = m0 + wm * 32, n = t0 + wn * 32 + c;
         const int Tpo = p.To + 2 * p.opad, Ck = k4p_ck();
         const bool rt = p.res && tile0 < p.plain_from && tile0 < p.Cout;      // (wave-uniform)
-        const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(rt ? p.res + (long long)b * Ck * Tpo : p.res), 0, rt ? Ck * Tpo * 4 : 0, 0x00020000);
-        const int vo = k4p_off(tile0, n) * 4;
+        const bool lnf = FOLD && ln_late();                                          // (wave-uniform) the slots carry the LayerNorm fold's row constants
+        const float* rbase = lnf ? p.ln_c1 : (rt ? p.res + (long long)b * Ck * Tpo : p.res);
+        const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(rbase), 0, lnf ? p.Mp * 4 : (rt ? Ck * Tpo * 4 : 0), 0x00020000);
+        const int vo = lnf ? (tile0 + 4 * h) * 4 : k4p_off(tile0, n) * 4;
 #pragma unroll
-        for (int e = 0; e < 8; ++e) rsv[e] = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(rr, vo + e * Tpo * 16, 0, 0));
-        const bool hb = p.bias && !p.ln_part;
-        const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.bias), 0, hb ? p.Mp * 4 : 0, 0x00020000);
+        for (int e = 0; e < 8; ++e) {      // fold: rows 8g + 4h + 2k + (0, 1) = registers 4g + 2k + (0, 1), slot e = 2g + k (a scalar step either way)
+            const int step = lnf ? (e >> 1) * 32 + (e & 1) * 8 : e * Tpo * 16;
+            rsv[e] = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(rr, vo + step, 0, 0));
+        }
+        const bool hb = (p.bias && !p.ln_part) || lnf;
+        const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(lnf ? p.ln_c2 : p.bias), 0, hb ? p.Mp * 4 : 0, 0x00020000);
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
             const f32x4 v = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rb, (tile0 + 8 * g + 4 * h) * 4, 0, 0));      // rows 8g + 4h + (0..3) = registers 4g + (0..3)
@@ -466,7 +476,7 @@ struct DmaKernel {
             // nothing of late_loads() may move in front of the burst or behind the wait: both would make the count of wait_younger too large
             asm volatile("" ::: "memory");
             __builtin_amdgcn_sched_barrier(0);
-            late_loads();
+            late_loads<ZERO>();
             asm volatile("" ::: "memory");
             __builtin_amdgcn_sched_barrier(0);
         }
@@ -501,10 +511,69 @@ struct DmaKernel {
         }
         if constexpr (GNF) __syncthreads();      // (the row constants are read in finalize: a one-K-step launch has met no barrier since)
     }
+    // The row constants of tile row i in the accumulators' plain layout (register 4g + k = packed weight row 8g + 4h + k): k1 = ln_c1 (the
+    // LayerNorm fold only), k2 = ln_c2 or the bias.  Single-tile waves hold them since late_loads() / early_loads(); the others (and a fold
+    // with a residual, whose slots carry the residual) fetch them here as four 16-byte loads per array -- the rows of a register quad
+    // are contiguous -- from one address per array with immediate offsets.  Global loads, not buffer loads: the register buffer loads
+    // of these kernels are the counted late loads and nothing else.
+    // (HELD is the caller's branch: each source gets its own copy of the code that uses the values)
+    template <bool HELD>
+    __device__ __forceinline__ void row_consts(int i, bool ln, float* k1, float* k2) const {
+        if constexpr (HELD) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                k2[r] = kbv[i * 16 + r];
+                if constexpr (LATE) k1[r] = ln ? rsv[r >> 1][r & 1] : 0.f;
+                else k1[r] = 0.f;
+            }
+        } else {
+            // (scalar base + one unsigned 32-bit lane offset + immediates: no 64-bit vector address arithmetic)
+            const unsigned ro = (unsigned)(m0 + wm * TM * 32 + i * 32 + 4 * h) * 4u;
+            const char* a2 = reinterpret_cast<const char*>(ln ? p.ln_c2 : p.bias);      // (not null: the callers come here with a fold or a bias only)
+            f32x4 q1[4], q2[4];
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                q1[g] = f32x4{0.f, 0.f, 0.f, 0.f};
+                q2[g] = *reinterpret_cast<const f32x4*>(a2 + ro + 32 * g);
+            }
+            if (ln) {
+                const char* a1 = reinterpret_cast<const char*>(p.ln_c1);
+#pragma unroll
+                for (int g = 0; g < 4; ++g) q1[g] = *reinterpret_cast<const f32x4*>(a1 + ro + 32 * g);
+            }
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) { k1[4 * g + k] = q1[g][k]; k2[4 * g + k] = q2[g][k]; }
+            }
+        }
+    }
+
+    template <bool HELD>
+    __device__ __forceinline__ void apply_rows(bool ln) {
+        float k1[TM][16], k2[TM][16];
+#pragma unroll
+        for (int i = 0; i < TM; ++i) row_consts<HELD>(i, ln, k1[i], k2[i]);
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+#pragma unroll
+            for (int j = 0; j < TN; ++j)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const float v = acc[0][i][j][r];
+                    // rstd * (v - mean * k1) + k2 with its roundings spelled out, so that they do not hang on how the compiler contracts the
+                    // expression: two fused multiply-adds in single-tile kernels, and
+                    // fma, multiply, add in the multi-tile ones -- what either kind has always computed
+                    const float t = fmaf(-lmu[j], k1[i][r], v);
+                    if constexpr (EARLY) acc[0][i][j][r] = ln ? fmaf(lrs[j], t, k2[i][r]) : v + k2[i][r];
+                    else acc[0][i][j][r] = ln ? __fadd_rn(__fmul_rn(lrs[j], t), k2[i][r]) : v + k2[i][r];
+                }
+    }
 
     // Epilogue, phase 1: accumulators -> output values in place (acc[0]).  All loads of a phase are issued before their
     // first use and before any store: a load placed after a store cannot be moved above it (possible aliasing), and a
     // load -> wait -> store chain costs one memory round trip per element.
+    template <bool FOLD>
     __device__ __forceinline__ void finalize(bool geglu) {
         if constexpr (NACC == 2) {
 #pragma unroll
@@ -512,7 +581,7 @@ struct DmaKernel {
 #pragma unroll
                 for (int j = 0; j < TN; ++j) acc[0][i][j] += acc[1][i][j];
         }
-        const bool ln = p.ln_part != nullptr;
+        const bool ln = FOLD && KT == 1 && p.ln_part != nullptr;      // (the fold belongs to 1x1 convolutions: launch_conv_dma; never to the fused pair)
         if (EARLY && !ln) {
 #pragma unroll
             for (int i = 0; i < TM; ++i)
@@ -521,24 +590,8 @@ struct DmaKernel {
 #pragma unroll
                     for (int r = 0; r < 16; ++r) acc[0][i][j][r] += kbv[i * 16 + r];
         } else if (ln || p.bias) {
-            float k1[TM][16], k2[TM][16];
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int m = m0 + wm * TM * 32 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;      // packed weight row
-                    k1[i][r] = ln ? p.ln_c1[m] : 0.f;
-                    k2[i][r] = ln ? p.ln_c2[m] : p.bias[m];
-                }
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const float v = acc[0][i][j][r];
-                        acc[0][i][j][r] = ln ? lrs[j] * (v - lmu[j] * k1[i][r]) + k2[i][r] : v + k2[i][r];
-                    }
+            if (LATE && ln_late()) apply_rows<LATE>(ln);
+            else apply_rows<false>(ln);
         }
         if constexpr (GNF) {
 #pragma unroll
@@ -605,9 +658,10 @@ struct DmaKernel {
     }
 
     // attention's VT layout for the value channels (attention_k4p.hip): [B][head][ceil(To/4)][D][4], element = V[d] at 4
-    // consecutive frames; frames To .. ceil4(To)-1 are written as zeros (they are multiplied by zero probabilities).  Plain 4-byte stores:
-    // a wave instruction writes sixteen 16-byte pieces of sixteen lines, and as write-through stores (sc1) these measured 0.9 ms per step
-    // SLOWER than left dirty for the end-of-kernel write-back
+    // consecutive frames; frames To .. ceil4(To)-1 are written as zeros (they are multiplied by zero probabilities).
+    // Sixteen predicated 4-byte stores per lane: a VT entry is one channel at four frames, and a lane of the MFMA's output holds one frame.
+    // Whole 16-byte entries from a transposed tile (operands exchanged) were built and measured 0.46 ms per step, inside the A/B's spread:
+    // taken out again.  As write-through stores (sc1) these measured 0.9 ms per step SLOWER than left dirty
     __device__ __forceinline__ void store_vt(int c0, int i, int j, int n) {
         const int T4 = (p.To + 3) & ~3, D = p.vt_D, Cv = p.Cout - p.plain_from;
         if (n >= T4) return;
@@ -884,6 +938,7 @@ struct DmaKernel {
         return true;
     }
 
+    template <bool FOLD = true>      // (false: the fused pair, whose launcher admits no LayerNorm fold -- its epilogue carries none of the fold's code)
     __device__ __forceinline__ void epilogue() {
         const bool geglu = (p.epi == EPI_GEGLU || (ACT2 == 2 && p.epi == EPI_GLU)) && (TM == 2);
         if constexpr (SPLIT) {
@@ -894,7 +949,7 @@ struct DmaKernel {
                 if (!cluster_join()) return;
             }
         }
-        finalize(geglu);
+        finalize<FOLD>(geglu);
         const int ni = geglu ? 1 : TM;
         if (p.res) {
 #pragma unroll
@@ -999,7 +1054,7 @@ __global__ void __launch_bounds__(256, (PairCfg<BM, BN, BK3, BK1, NST>::OCC)) co
     __syncthreads();                // every wave is done reading the first phase's stages
     k1.setup_keep_acc();
     if (!k1.dead_tile()) k1.template mainloop<true, false>();
-    k1.epilogue();
+    k1.template epilogue<false>();
 }
 
 // the constants of the kernel's block-index decomposition (kernels.h dma_tile_of): divisors nMb, nN, S
@@ -1181,6 +1236,7 @@ hipError_t launch_conv_dma(const DmaConvArgs& a_, int cfg, hipStream_t s) {
     DmaConvArgs a = a_;
     a.ksplit = 1;
     if (a.Ci % 16 || a.C1 % 16 || a.Mp % 64 || a.B <= 0 || a.To <= 0 || a.xpad < 1 || a.opad < 1 || a.pad < 0 || a.pad > a.xpad) return hipErrorInvalidValue;
+    if (a.ln_part && a.KT != 1) return hipErrorInvalidValue;      // the LayerNorm fold's epilogue exists in the 1x1 kernels only
     if (a.voc) {
         // vocoder resblock convolutions (k 3 / 7 / 11, dilation 1 / 3 / 5; LeakyReLU / running-sum epilogues): one 64 x 128 tile shape,
         // BK 16 (a K-step = 16 channels x all taps: 6 / 14 / 22 MFMA groups of 8 per wave), 2 stages (the weight tile of k 11 is 45 KB per stage)

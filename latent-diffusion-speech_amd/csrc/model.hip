@@ -4121,10 +4121,15 @@ extern "C" int lds_test_dconv_pair(const float* h, const float* x1, const float*
 extern "C" int lds_test_dconv_ex(const lds_dconv_ex_test* a, float* out, float* gnpart, int B, char* cfg_out, size_t cfg_cap, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     if (!a || !a->x1 || !a->w || !out || B < 1 || a->T < 1 || (a->C2 > 0) != (a->x2 != nullptr) || a->C1 < 8 || (a->C1 & 7) || a->C2 < 0 || (a->C2 & 7) || a->Co < 32 ||
-        a->Co % 32 || a->K < 1 || a->stride < 1 || a->pad < 0 || (a->epilogue != EPI_NONE && a->epilogue != EPI_GELU) || a->lvl_in < 0 || a->lvl_out < 0 ||
-        a->tile_batch < 0 || (a->fmt != -1 && a->fmt != FMT_BF16X3 && a->fmt != FMT_F16X2) || (a->ln_gamma != nullptr) != (a->ln_beta != nullptr))
+        a->Co % 32 || a->K < 1 || a->stride < 1 || a->pad < 0 || (a->epilogue != EPI_NONE && a->epilogue != EPI_GELU && a->epilogue != EPI_GEGLU) || a->lvl_in < 0 ||
+        a->lvl_out < 0 || a->tile_batch < 0 || (a->fmt != -1 && a->fmt != FMT_BF16X3 && a->fmt != FMT_F16X2) || (a->ln_gamma != nullptr) != (a->ln_beta != nullptr) ||
+        a->v_split < 0 || a->v_split == 1 || a->cfg < 0)
         return fail(LDS_EINVAL, "bad argument");
-    const bool f32 = a->fmt < 0, ln = a->ln_gamma != nullptr;
+    const bool f32 = a->fmt < 0, ln = a->ln_gamma != nullptr, geglu = a->epilogue == EPI_GEGLU;
+    // the transformer's two folded projections as the UNet runs them: FF1 (GEGLU rows interleaved as pack_geglu does) and QKV (value third in VT layout)
+    if (geglu && (!ln || !f32 || a->Co % 128 || a->res || gnpart || a->v_split)) return fail(LDS_EINVAL, "GEGLU here is the folded FF1: fp32, LayerNorm fold, Co a multiple of 128");
+    if (a->v_split && (!f32 || a->Co % 3 || (a->Co / 3) % a->v_split || ((a->Co / 3) * 2) % 8 || a->res || gnpart || a->K != 1 || a->stride != 1))
+        return fail(LDS_EINVAL, "v_split is the fp32 QKV projection: 1x1, Co = 3 C, C a multiple of the head dim");
     const int mode = f32 ? 0 : a->fmt + 1;
     const int Ci = a->C1 + a->C2, T = a->T;
     const int To = (T + 2 * a->pad - (a->K - 1) - 1) / a->stride + 1;
@@ -4134,7 +4139,12 @@ extern "C" int lds_test_dconv_ex(const lds_dconv_ex_test* a, float* out, float* 
     TmpDev tmp;
     ConvW W, Wid;
     float *c1 = nullptr, *c2 = nullptr;
-    bool ok = ln ? pack_ln_fold(own, a->w, a->bias, a->ln_gamma, a->ln_beta, a->Co, Ci, {}, W, c1, c2) : pack_conv(own, a->w, a->bias, a->Co, Ci, a->K, W);
+    std::vector<int> perm;
+    if (geglu) {
+        perm.resize(a->Co);
+        for (int mm = 0; mm < a->Co; ++mm) perm[mm] = ((mm % 64) / 32 == 0 ? 0 : a->Co / 2) + 32 * (mm / 64) + mm % 32;
+    }
+    bool ok = ln ? pack_ln_fold(own, a->w, a->bias, a->ln_gamma, a->ln_beta, a->Co, Ci, perm, W, c1, c2) : pack_conv(own, a->w, a->bias, a->Co, Ci, a->K, W);
     if (ok && ln) {      // the partials' producer: an identity 1x1 convolution, whose epilogue writes the per-frame LayerNorm partials of x itself
         std::vector<float> eye((size_t)Ci * Ci, 0.f);
         for (int c = 0; c < Ci; ++c) eye[(size_t)c * Ci + c] = 1.0f;
@@ -4150,12 +4160,15 @@ extern "C" int lds_test_dconv_ex(const lds_dconv_ex_test* a, float* out, float* 
     float* kx = ln ? tmp.f(act.floats(Ci, T)) : nullptr;
     float* part = ln ? tmp.f((size_t)B * (Ci / 32) * T * 2) : nullptr;
     float* kres = a->res ? tmp.f(act.floats(a->Co, To)) : nullptr;
-    float* ko = tmp.f(act.floats(a->Co, To));
+    const int Cout = geglu ? a->Co / 2 : a->Co, Ck = a->v_split ? (Cout / 3) * 2 : Cout, To4 = (To + 3) & ~3;      // (K4P channels; the rest is the VT third)
+    float* ko = tmp.f(act.floats(Ck, To));
+    float* vout = a->v_split ? tmp.f((size_t)B * (Cout - Ck) * To4) : nullptr;
     float* kpart = a->tile_batch ? tmp.f((size_t)kClusterPartFloats) : nullptr;
     unsigned* kcount = a->tile_batch ? (unsigned*)tmp.f(kClusterCounters) : nullptr;
-    if (!k1 || (a->C2 && !k2) || (ln && (!kx || !part)) || (a->res && !kres) || !ko || (a->tile_batch && (!kpart || !kcount))) return fail(LDS_ENOMEM, "alloc");
+    if (!k1 || (a->C2 && !k2) || (ln && (!kx || !part)) || (a->res && !kres) || !ko || (a->v_split && !vout) || (a->tile_batch && (!kpart || !kcount))) return fail(LDS_ENOMEM, "alloc");
     if (kcount) HIP_TRY(hipMemsetAsync(kcount, 0, sizeof(unsigned) * kClusterCounters, st));
-    HIP_TRY(hipMemsetAsync(ko, 0xff, sizeof(float) * act.floats(a->Co, To), st));      // NaN fill: every frame and every partial must be written
+    HIP_TRY(hipMemsetAsync(ko, 0xff, sizeof(float) * act.floats(Ck, To), st));      // NaN fill: every frame and every partial must be written
+    if (vout) HIP_TRY(hipMemsetAsync(vout, 0xff, sizeof(float) * (size_t)B * (Cout - Ck) * To4, st));      // (the VT tail too)
     if (gnpart) HIP_TRY(hipMemsetAsync(gnpart, 0xff, sizeof(float) * (size_t)B * (a->Co / 16) * ((To + 31) / 32) * 2, st));
     HIP_TRY(act.to(a->x1, k1, a->C1, T));
     if (a->C2) HIP_TRY(act.to(a->x2, k2, a->C2, T));
@@ -4174,8 +4187,9 @@ extern "C" int lds_test_dconv_ex(const lds_dconv_ex_test* a, float* out, float* 
         if (rc == LDS_OK) {
             TileBatchScope tbs(a->tile_batch, kpart, kcount);
             DOpt o;
-            o.stride = a->stride; o.pad = a->pad; o.epi = a->epilogue; o.res = kres;
+            o.stride = a->stride; o.pad = a->pad; o.epi = a->epilogue; o.res = kres; o.cfg = a->cfg;
             o.lvl_in = a->lvl_in; o.lvl_out = a->lvl_out;
+            if (a->v_split) { o.plain_from = Ck; o.out2 = vout; o.vt_D = a->v_split; }
             o.gnpart_out = (float2*)gnpart;
             if (ln) { o.ln_part = (const float2*)part; o.ln_np = Ci / 32; o.ln_eps = a->ln_eps; o.ln_c1 = c1; o.ln_c2 = c2; }
             rc = dconv_any(mode, W, xin, a->C1, k2, a->C2, T, o, ko, B, st);
@@ -4183,8 +4197,9 @@ extern "C" int lds_test_dconv_ex(const lds_dconv_ex_test* a, float* out, float* 
     }
     if (rc == LDS_OK) {
         if (cfg_out && cfg_cap) snprintf(cfg_out, cfg_cap, "%s", f32 ? conv_dma_last_config() : conv_bf3_last_config());
-        if (f32) HIP_TRY(tap_take(ko, act.floats(a->Co, To), st));
-        HIP_TRY(act.from(ko, out, a->Co, To));
+        if (f32) HIP_TRY(tap_take(ko, act.floats(Ck, To), st));
+        HIP_TRY(act.from(ko, out, Ck, To));      // out = [B][Ck][To], then (v_split) the raw VT buffer [B][(Cout - Ck) / D][ceil4(To) / 4][D][4]
+        if (vout) HIP_TRY(hipMemcpyAsync(out + (size_t)B * Ck * To, vout, sizeof(float) * (size_t)B * (Cout - Ck) * To4, hipMemcpyDeviceToDevice, st));
     }
     HIP_TRY(hipStreamSynchronize(st));
     return rc;

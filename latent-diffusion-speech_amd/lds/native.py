@@ -61,7 +61,8 @@ class DConvExTest(C.Structure):
     _fields_ = [("x1", C.c_void_p), ("x2", C.c_void_p), ("C1", C.c_int), ("C2", C.c_int), ("T", C.c_int),
                 ("w", C.c_void_p), ("bias", C.c_void_p), ("Co", C.c_int), ("K", C.c_int), ("stride", C.c_int), ("pad", C.c_int),
                 ("res", C.c_void_p), ("epilogue", C.c_int), ("lengths", C.c_void_p), ("lvl_in", C.c_int), ("lvl_out", C.c_int),
-                ("ln_gamma", C.c_void_p), ("ln_beta", C.c_void_p), ("ln_eps", C.c_float), ("tile_batch", C.c_int), ("fmt", C.c_int)]
+                ("ln_gamma", C.c_void_p), ("ln_beta", C.c_void_p), ("ln_eps", C.c_float), ("tile_batch", C.c_int), ("fmt", C.c_int),
+                ("v_split", C.c_int), ("cfg", C.c_int)]
 
 
 # The C ABI, one line per entry point: name, return kind ':' argument kinds in the header's order.
