@@ -77,6 +77,10 @@ int lds_test_attention_k4p(const float* qkv, float* out, int B, int C, int T, in
 int lds_test_attention_f16math(const float* qkv, float* out, int B, int C, int T, int heads, void* stream);
 /* the latency mode's configuration choice (judged at the actual batch: 32-query workgroups whose four waves share the keys); f16math 0 / 1 */
 int lds_test_attention_latency(const float* qkv, float* out, int B, int C, int T, int heads, int f16math, void* stream);
+/* the same three on a ragged batch: lens = HOST int32 [B], 1 <= lens[b] <= T.  q and k reach the kernel as given (the caller may fill the frames
+ * beyond a clip's length with NaN); v is zeroed there, as the QKV convolution writes it; the K4P output buffer starts as NaN.  out [B,C,T]:
+ * frames at and beyond lens[b] are zeros.  f16math 0 / 1; latency 1 = the latency mode's configuration choice */
+int lds_test_attention_ragged(const float* qkv, const int* lens, float* out, int B, int C, int T, int heads, int f16math, int latency, void* stream);
 int lds_test_conv_transpose(const float* x, const float* w /*host [Ci,Co,K]*/, const float* bias,
                             float* out, int B, int Ci, int Co, int T, int K, int stride, int pad,
                             float in_slope, void* stream);

@@ -124,39 +124,61 @@ static __device__ __forceinline__ void att_store_k4p(const f32x16* o, float rl, 
 // staged tile, so twice as many waves share the work; the partial (max, sum, output) triples meet through LDS at the end.
 template <int D, int NW, int NST, int KS, bool F16>
 __global__ void __launch_bounds__(NW * 64) attention_k4p_kernel(const float* __restrict__ qk, const float* __restrict__ vt, float* __restrict__ out,
-                                                                int C, int Tbuf, float scale2, int out_bf3, const int* __restrict__ lens, int lvl) {
+                                                                int C, int Tbuf, float scale2, int out_bf3, const int* __restrict__ lens, int lvl,
+                                                                unsigned om0, unsigned om1, unsigned os) {
     using Cfg = AttCfg<D, NW, NST, KS>;
     constexpr int NWQ = NW / KS;
     constexpr int KB = Cfg::KB, DQ = Cfg::DQ, DT = Cfg::DT, KPW = Cfg::KPW, VPW = Cfg::VPW, STAGE = Cfg::STAGE, PER_TILE = Cfg::PER_TILE;
     extern __shared__ __attribute__((aligned(16))) float smem[];      // NST x { K [row][key][4] ; V [keyquad][d][4] }
+    // The arguments the first DMA depends on, requested in one burst behind one wait (conv_dma.hip load_hot): copies pinned by one empty
+    // asm that names them all.  qk / vt serve as buffer bases only; `lens` is dereferenced and stays the kernel argument.
+    struct { const float *qk, *vt; int C, Tbuf, lvl; unsigned om0, om1, os, gx, gy, gz; } hp = {qk, vt, C, Tbuf, lvl, om0, om1, os, gridDim.x, gridDim.y, gridDim.z};
+    asm volatile("" : "+s"(hp.qk), "+s"(hp.vt), "+s"(hp.C), "+s"(hp.Tbuf), "+s"(hp.lvl), "+s"(hp.om0), "+s"(hp.om1), "+s"(hp.os), "+s"(hp.gx), "+s"(hp.gy), "+s"(hp.gz));
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int c = lane & 31, h = lane >> 5;
     // XCD-aware order: the query blocks of one (batch, head) share K and V, so they take consecutive slots of one XCD
-    // (workgroups are dispatched round-robin over the 8 XCDs, each with its own L2)
-    const int gx = gridDim.x, gy = gridDim.y, total = gx * gy * gridDim.z;
+    // (workgroups are dispatched round-robin over the 8 XCDs, each with its own L2).  The two divisions (by the query blocks and by the
+    // heads) are multiplications by the launcher's constants (kernels.h dma_magic): exact quotients on the scalar unit.
+    const int gx = (int)hp.gx, gy = (int)hp.gy, total = gx * gy * (int)hp.gz;
     const int id = (blockIdx.z * gy + blockIdx.y) * gx + blockIdx.x;
     const int per = total >> 3, rem = total & 7, xcd = id & 7;
-    const int L = xcd * per + (xcd < rem ? xcd : rem) + (id >> 3);
-    const int qblk = L % gx, hd = (L / gx) % gy, b = L / (gx * gy);
+    const unsigned L = (unsigned)(xcd * per + (xcd < rem ? xcd : rem) + (id >> 3));
+    const unsigned bh = dma_magic_div(L, hp.om0, hp.os & 255);
+    const int qblk = (int)(L - bh * (unsigned)gx);
+    const int b = (int)dma_magic_div(bh, hp.om1, (hp.os >> 8) & 255), hd = (int)bh - b * gy;
     const int qw = wave % NWQ, ks = wave / NWQ;       // query tile of this wave; which 32-key half of each tile it takes
     const int tq = qblk * (NWQ * 32) + qw * 32 + c;
     // T = this utterance's own length (ragged batches: keys stop there, queries beyond it are written as zeros); the strides are the buffer's
-    const int T = ragged_len(lens, b, lvl, Tbuf);
-    const int Tp = Tbuf + 2, T4 = (Tbuf + 3) & ~3;
-    const float* qb = qk + ((long long)b * 2 * C + (long long)hd * D) * Tp;            // q rows of this head
+    // (read through the constant address space: it stays a scalar load behind the asm statements, as conv_dma.hip len_at)
+    const int Tbuf_ = hp.Tbuf, C_ = hp.C;
+    int T = Tbuf_;
+    if (lens) {
+        int n = ((const __attribute__((address_space(4))) int*)(unsigned long long)lens)[b];
+        asm volatile("" : "+s"(n));      // (one wait here, none inside the loop)
+        for (int i = 0; i < hp.lvl; ++i) n = (n - 1) / 2 + 1;
+        T = n < Tbuf_ ? n : Tbuf_;
+    }
+    const int Tp = Tbuf_ + 2, T4 = (Tbuf_ + 3) & ~3;
 
-    // queries: B operands, pre-multiplied by log2(e)/sqrt(d) so the scores come out in log2 units
+    // queries (B operands): requested UNCONDITIONALLY in front of the first K/V tile, as buffer loads written in asm so that the compiler
+    // neither wraps each in an exec-masked branch that ends with `s_waitcnt vmcnt(0)` nor puts a wait of its own (which would not count the
+    // LDS-DMAs behind them) in front of their first use.  vmcnt completes in order: they have landed when tile 0 has, which is what the
+    // counted wait in front of the loop waits for (att_wait_younger still sees only tile DMAs younger than the awaited tile).  A query at or
+    // beyond the buffer's length reads the row's last frame (a valid address of this head's rows); the `tq < T` zero is a select below.
+    const __amdgpu_buffer_rsrc_t rq =
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(hp.qk + ((long long)b * 2 * C_ + (long long)hd * D) * Tp), 0, D * Tp * 4, 0x00020000);
     f32x4 qv[DQ];
+    {
+        const int qoff = (h * Tp + (tq < Tbuf_ ? tq : Tbuf_ - 1) + 1) * 16;
 #pragma unroll
-    for (int kq = 0; kq < DQ; ++kq) {
-        qv[kq] = f32x4{0.f, 0.f, 0.f, 0.f};
-        if (tq < T) qv[kq] = *reinterpret_cast<const f32x4*>(qb + ((long long)(kq * 2 + h) * Tp + tq + 1) * 4);
+        for (int kq = 0; kq < DQ; ++kq) asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen" : "=v"(qv[kq]) : "v"(qoff), "s"(rq), "s"(kq * 2 * Tp * 16));
+        // (descriptor and offsets are scalar-unit results, kernel arguments and the block index alone: no VALU-written SGPR feeds these loads)
     }
 
     const __amdgpu_buffer_rsrc_t rk =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(qk + ((long long)b * 2 * C + C + (long long)hd * D) * Tp), 0, D * Tp * 4, 0x00020000);
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(hp.qk + ((long long)b * 2 * C_ + C_ + (long long)hd * D) * Tp), 0, D * Tp * 4, 0x00020000);
     const __amdgpu_buffer_rsrc_t rv =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(vt + ((long long)b * C + (long long)hd * D) * T4), 0, D * T4 * 4, 0x00020000);
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(hp.vt + ((long long)b * C_ + (long long)hd * D) * T4), 0, D * T4 * 4, 0x00020000);
     // loop-invariant per-lane byte offsets of this wave's DMA shares
     int koff[KPW], voff[VPW];
 #pragma unroll
@@ -166,8 +188,23 @@ __global__ void __launch_bounds__(NW * 64) attention_k4p_kernel(const float* __r
     // (ragged batch: a query block wholly beyond the utterance's length attends to nothing; its zeros are written below)
     const int nt = (qblk * (NWQ * 32) >= T) ? 0 : (T + KB - 1) / KB;
     for (int t = 0; t < NST - 1 && t < nt; ++t) att_issue_tile<D, NW, KPW, VPW>(rk, rv, koff, voff, wave, t, smem + t * STAGE);
+
+    // KS = 4 (latency mode) with the whole sequence resident in the ring: one wait for everything and one barrier, then every wave
+    // runs through its own chunks without meeting the others (a per-tile barrier would make the four waves take turns: chunk j of
+    // tile kt belongs to one wave only)
+    const bool resident = (KS == 4) && nt <= NST - 1;
+    // The wait of tile 0 (the loop's first one finds it done), which covers the older query loads; nt = 0 waits for the queries alone: no
+    // load may be in flight when the registers are reused.  The empty asm makes the landed values the compiler's from here on.
+    if (resident) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    else att_wait_younger<NST - 2, PER_TILE>((nt - 1 < NST - 2) ? nt - 1 : NST - 2);
 #pragma unroll
-    for (int kq = 0; kq < DQ; ++kq) qv[kq] *= scale2;
+    for (int kq = 0; kq < DQ; ++kq) asm volatile("" : "+v"(qv[kq]));
+    // pre-multiplied by log2(e)/sqrt(d) so the scores come out in log2 units; zeros for a query at or beyond its utterance's length
+#pragma unroll
+    for (int kq = 0; kq < DQ; ++kq) {
+        if (!(tq < T)) qv[kq] = f32x4{0.f, 0.f, 0.f, 0.f};
+        qv[kq] *= scale2;
+    }
     att_u32x4 qh1[F16 ? DQ / 2 : 1], qh2[F16 ? DQ / 2 : 1];      // F16: the query fragments, split once
     if constexpr (F16) {
 #pragma unroll
@@ -181,12 +218,7 @@ __global__ void __launch_bounds__(NW * 64) attention_k4p_kernel(const float* __r
         for (int r = 0; r < 16; ++r) o[i][r] = 0.f;
     float m_run = -INFINITY, l_run = 0.f;
 
-    // KS = 4 (latency mode) with the whole sequence resident in the ring: one wait for everything and one barrier, then every wave
-    // runs through its own chunks without meeting the others (a per-tile barrier would make the four waves take turns: chunk j of
-    // tile kt belongs to one wave only)
-    const bool resident = (KS == 4) && nt <= NST - 1;
     if (resident) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
     }
@@ -381,9 +413,13 @@ static hipError_t launch_cfg(const float* qk, const float* vt, float* out, int B
         if (e != hipSuccess) return e;
     }
     constexpr int QPB = NW / KS * 32;       // queries per workgroup
+    // the block-index decomposition's two divisors (query blocks, heads) as multiplier / shift pairs (kernels.h dma_magic)
+    const int gx = (T + QPB - 1) / QPB;
+    const DmaMagic m0 = dma_magic((unsigned)gx), m1 = dma_magic((unsigned)heads);
+    const unsigned os = m0.s | (m1.s << 8);
     hipEvent_t e0, e1;
-    if (prof_attach_events(&e0, &e1)) hipExtLaunchKernelGGL(kern, dim3((T + QPB - 1) / QPB, heads, B), dim3(NW * 64), Cfg::LDS_BYTES, s, e0, e1, 0, qk, vt, out, C, T, scale, out_bf3, lens, lvl);
-    else hipLaunchKernelGGL(kern, dim3((T + QPB - 1) / QPB, heads, B), dim3(NW * 64), Cfg::LDS_BYTES, s, qk, vt, out, C, T, scale, out_bf3, lens, lvl);
+    if (prof_attach_events(&e0, &e1)) hipExtLaunchKernelGGL(kern, dim3(gx, heads, B), dim3(NW * 64), Cfg::LDS_BYTES, s, e0, e1, 0, qk, vt, out, C, T, scale, out_bf3, lens, lvl, m0.m, m1.m, os);
+    else hipLaunchKernelGGL(kern, dim3(gx, heads, B), dim3(NW * 64), Cfg::LDS_BYTES, s, qk, vt, out, C, T, scale, out_bf3, lens, lvl, m0.m, m1.m, os);
     return hipGetLastError();
 }
 
@@ -653,8 +689,8 @@ hipError_t launch_attention_k4p_rel(const float* qk, const float* vt, const floa
 }
 
 // test entry: K4P fp32 in and out, the products on the fp16 pipe
-hipError_t launch_attention_k4p_f16math(const float* qk, const float* vt, float* out, int B, int C, int T, int heads, hipStream_t s, int tile_batch) {
-    return attention_any(qk, vt, out, B, C, T, heads, 0, true, tile_batch, s);
+hipError_t launch_attention_k4p_f16math(const float* qk, const float* vt, float* out, int B, int C, int T, int heads, hipStream_t s, int tile_batch, const int* lens) {
+    return attention_any(qk, vt, out, B, C, T, heads, 0, true, tile_batch, s, lens, 0);
 }
 
 }  // namespace lds

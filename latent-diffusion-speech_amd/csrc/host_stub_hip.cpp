@@ -29,6 +29,10 @@ hipError_t hipMemsetAsync(void* d, int v, size_t n, hipStream_t) {
     memset(d, v, n);
     return hipSuccess;
 }
+hipError_t hipMemset2DAsync(void* d, size_t pitch, int v, size_t width, size_t height, hipStream_t) {
+    for (size_t r = 0; r < height; ++r) memset((char*)d + r * pitch, v, width);
+    return hipSuccess;
+}
 hipError_t hipMemcpy2DAsync(void* d, size_t dpitch, const void* s_, size_t spitch, size_t width, size_t height, hipMemcpyKind, hipStream_t) {
     for (size_t r = 0; r < height; ++r) memcpy((char*)d + r * dpitch, (const char*)s_ + r * spitch, width);
     return hipSuccess;

@@ -181,109 +181,133 @@ hipError_t launch_gn_partials(const float* x, int C, int T, float2* gp, int B, h
     return hipGetLastError();
 }
 
-// One workgroup per (batch, 8-channel block): E x 256 entries of 16 bytes are requested first, the group's statistics are
-// combined from the partials while those loads are in flight (every wave does it redundantly: no LDS, no barrier), then
-// normalise + affine (+scale/shift) (+SiLU) and store; the pad frames are written as zeros.
+// One workgroup per (batch, 8-channel block).  Everything the launch needs is requested at its top, unconditionally, and waited for once:
+// the group's first two rounds of partials, E x 256 entries of 16 bytes of the tensor, and the block's eight gamma / beta / scale / shift
+// values as four 32-byte scalar loads (the eight channels of a block are contiguous in each array).  A load inside a branch is waited for at
+// the end of that branch, so the masks are selects on the loaded values.  The statistics are combined while the tensor's entries are in
+// flight (every wave does it redundantly: no LDS, no barrier), then normalise + affine (+scale/shift) (+SiLU) and store; the pad frames
+// are written as zeros.  cg16 = 16-channel blocks per group, (gm, gsh) = kernels.h dma_magic of the 8-channel blocks per group,
+// inv_nT = 1 / ceil(T / 32): the launcher's, so that no division stands in front of the first load.
+typedef float gn_f32x8 __attribute__((ext_vector_type(8)));
+typedef float gn_f32x2 __attribute__((ext_vector_type(2)));
+typedef gn_f32x8 gn_f32x8_a4 __attribute__((aligned(4)));
+// eight consecutive floats as ONE scalar load (dword alignment is all the scalar unit asks for), through the constant address space: the
+// arrays do not change during a launch, and so the read stays scalar behind the asm statement that pins the arguments
+static __device__ __forceinline__ gn_f32x8 gn_load8(const float* p) {
+    return *(const __attribute__((address_space(4))) gn_f32x8_a4*)(unsigned long long)p;
+}
 template <int E>
 __global__ void __launch_bounds__(256) gn_stream_kernel(const float* __restrict__ x1, const float* __restrict__ x2, int C1, int C2, int T,
-                                                        int groups, float eps, const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                        int cg16, unsigned gm, unsigned gsh, float inv_nT, float eps,
+                                                        const float* __restrict__ gamma, const float* __restrict__ beta,
                                                         const float* __restrict__ ss, int ss_stride, int ss_off, int silu,
                                                         const float2* __restrict__ gp1, const float2* __restrict__ gp2, float* __restrict__ y,
                                                         const int* __restrict__ lens, int lvl) {
+    // the arguments in one burst behind one wait (conv_dma.hip load_hot): one empty asm that names them all
+    asm volatile("" : "+s"(x1), "+s"(x2), "+s"(C1), "+s"(C2), "+s"(T), "+s"(cg16), "+s"(gm), "+s"(gsh), "+s"(inv_nT), "+s"(eps), "+s"(gamma), "+s"(beta),
+                      "+s"(ss), "+s"(ss_stride), "+s"(ss_off), "+s"(silu), "+s"(gp1), "+s"(gp2), "+s"(y), "+s"(lens), "+s"(lvl));
     const int q = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, lane = tid & 63;
-    const int Tv = ragged_len(lens, b, lvl, T);      // ragged batch: statistics over, and output for, the utterance's own frames; zeros beyond
     const int C = C1 + C2, Tp = T + 2, nq1 = C1 >> 3, nq = C >> 3;
+    // ---- 1. the scalar requests: the block's eight gamma / beta / scale / shift values (channels 8q .. 8q + 7 of each array; without
+    // scale/shift the two extra loads re-read gamma) and the utterance's length ----
+    const float* sp = ss ? ss + (long long)b * ss_stride + ss_off + q * 8 : gamma + q * 8;
+    const gn_f32x8 g8 = gn_load8(gamma + q * 8), b8 = gn_load8(beta + q * 8), sc8 = gn_load8(sp), sh8 = gn_load8(ss ? sp + C : sp);
+    int Tv = T;      // ragged batch (k4p.h ragged_len): statistics over, and output for, the utterance's own frames; zeros beyond
+    if (lens) {
+        int n = ((const __attribute__((address_space(4))) int*)(unsigned long long)lens)[b];
+        asm volatile("" : "+s"(n));
+        for (int i = 0; i < lvl; ++i) n = (n - 1) / 2 + 1;
+        Tv = n < T ? n : T;
+    }
     const float* xb = (q < nq1) ? x1 + (((long long)b * nq1 + q) * 2) * Tp * 4 : x2 + (((long long)b * (C2 >> 3) + (q - nq1)) * 2) * Tp * 4;
     float* yb = y + (((long long)b * nq + q) * 2) * Tp * 4;
+    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(xb), 0, 2 * Tp * 16, 0x00020000);
     const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(yb, 0, 2 * Tp * 16, 0x00020000);
     const int total = 2 * T;                          // real entries of this block: (row hh, frame t) -> idx = hh * T + t
-    // ---- 1. request the first chunk ----
+    // ---- 2. request the partials of the first two rounds (<= 128: every shape of the UNet at T <= 1024), in front of the tensor's entries:
+    // vmcnt completes in order, and the statistics are the launch's critical path ----
+    const int g = (int)dma_magic_div((unsigned)q, gm, gsh);      // the block's group: q / (2 cg16)
+    const int nT = (T + 31) >> 5, P = cg16 * nT, nk1 = C1 >> 4;
+    // an empty partial (beyond the group's last, or a block beyond the utterance's length, whose partials were never written) is (0, 0, 0);
+    // its load reads the group's first partial, a valid address (gn_chan.h gn_part_load)
+    auto request = [&](int p0, float& nb, bool& ok) {      // the load, this lane's count and whether the partial takes part
+        const int pi = p0 + lane;
+        const bool in = pi < P;
+        const int pc = in ? pi : 0;
+        const int kk = (int)(((float)pc + 0.5f) * inv_nT), tb = pc - kk * nT, kb = g * cg16 + kk;      // pc / nT without the integer-division sequence
+        const int nv = (Tv - tb * 32 < 32) ? Tv - tb * 32 : 32;
+        const bool f1 = kb < nk1;      // which source's partials (selects of scalars; global pointers again behind the asm above)
+        const int off = ((f1 ? b * nk1 : b * (C2 >> 4) - nk1) + kb) * nT + tb;
+        ok = in && nv > 0;
+        nb = ok ? 16.0f * (float)nv : 0.f;
+        return ((const __attribute__((address_space(1))) gn_f32x2*)(unsigned long long)(f1 ? gp1 : gp2))[off];
+    };
+    auto part = [&](int p0, float& nb, float& mb, float& qb) {
+        bool ok;
+        const gn_f32x2 pr = request(p0, nb, ok);
+        mb = ok ? pr.x : 0.f; qb = ok ? pr.y : 0.f;
+    };
+    float n0, n1;
+    bool ok0, ok1;
+    gn_f32x2 pr0 = request(0, n0, ok0), pr1 = request(64, n1, ok1);
+    // ---- 3. request the first chunk (an entry beyond the block reads the pad frame or, by the buffer's range check, nothing) ----
+    auto entry = [&](int idx) {
+        const int hh = idx >= T, t = idx - hh * T;
+        return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rx, (hh * Tp + t + 1) * 16, 0, 0));
+    };
     f32x4 v[E];
 #pragma unroll
-    for (int i = 0; i < E; ++i) {
-        const int idx = tid + 256 * i;
-        if (idx < total) {
-            const int hh = idx >= T, t = idx - hh * T;
-            v[i] = *reinterpret_cast<const f32x4*>(xb + ((long long)hh * Tp + t + 1) * 4);
-        }
-    }
-    // ---- 2. per-channel affine terms ----
+    for (int i = 0; i < E; ++i) v[i] = entry(tid + 256 * i);
+    asm volatile("" : "+v"(pr0), "+v"(pr1));      // both rounds behind one counted wait (the entries stay in flight)
+    const float m0 = ok0 ? pr0.x : 0.f, q0 = ok0 ? pr0.y : 0.f, m1 = ok1 ? pr1.x : 0.f, q1 = ok1 ? pr1.y : 0.f;
     float ga[2][4], be[2][4];
 #pragma unroll
     for (int hh = 0; hh < 2; ++hh)
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const int ci = q * 8 + 2 * j + hh;
-            float g_ = gamma[ci], b_ = beta[ci];
+            float g_ = g8[2 * j + hh], b_ = b8[2 * j + hh];
             if (ss) {
-                const float sc = 1.0f + ss[(long long)b * ss_stride + ss_off + ci];
-                const float sh = ss[(long long)b * ss_stride + ss_off + C + ci];
+                const float sc = 1.0f + sc8[2 * j + hh];
                 g_ *= sc;
-                b_ = b_ * sc + sh;
+                b_ = fmaf(b_, sc, sh8[2 * j + hh]);      // (the roundings are spelled out where the compiler had contracted: results stay bit for bit)
             }
             ga[hh][j] = g_; be[hh][j] = b_;
         }
-    // ---- 3. group statistics from the partials ----
-    const int cg16 = (C / groups) >> 4;               // 16-channel blocks per group
-    const int g = (q * 8) / (C / groups);
-    const int nT = (T + 31) >> 5, P = cg16 * nT, nk1 = C1 >> 4;
-    const float inv_nT = 1.0f / (float)nT;
+    // ---- 4. group statistics from the partials ----
     // two plain sums in a fixed order (gn_chan.h gnf_wave_sum): mean = sum(n_i mean_i) / N, var = sum(M2_i + n_i (mean_i - mean)^2) / N with
     // N = 16 cg16 Tv known outright -- a dependent chain of 2 x 6 additions where the Chan tree had 6 steps of a dozen operations with a
     // reciprocal each, on the critical path of a launch that is latency-bound (DESIGN.md sections 3.10, 14.10).  The partials of the first
-    // two rounds (<= 128: every shape of the UNet at T <= 1024) stay in registers between the sums; further rounds are read twice.
-    auto part = [&](int p0, float& nb, float& mb, float& qb) {
-        const int pi = p0 + lane;
-        nb = 0.f; mb = 0.f; qb = 0.f;
-        if (pi < P) {
-            const int kk = (int)(((float)pi + 0.5f) * inv_nT), tb = pi - kk * nT, kb = g * cg16 + kk;      // pi / nT without the integer-division sequence
-            const int nv = (Tv - tb * 32 < 32) ? Tv - tb * 32 : 32;
-            if (nv > 0) {
-                const float2 pr = (kb < nk1) ? gp1[((long long)b * nk1 + kb) * nT + tb] : gp2[((long long)b * (C2 >> 4) + (kb - nk1)) * nT + tb];
-                nb = 16.0f * (float)nv; mb = pr.x; qb = pr.y;
-            }
-        }
-    };
-    float n0, m0, q0, n1 = 0.f, m1 = 0.f, q1 = 0.f;
-    part(0, n0, m0, q0);
-    if (P > 64) part(64, n1, m1, q1);
-    float s1 = fmaf(n1, m1, n0 * m0);
+    // two rounds stay in registers between the sums; further rounds are read twice, each with its own wait.
+    float s1 = fmaf(n1, m1, __fmul_rn(n0, m0));
     for (int p0 = 128; p0 < P; p0 += 64) {
         float nb, mb, qb;
         part(p0, nb, mb, qb);
         s1 = fmaf(nb, mb, s1);
     }
     const float rN = __builtin_amdgcn_rcpf(16.0f * (float)cg16 * (float)Tv);
-    const float mu = gnf_wave_sum(s1) * rN;
-    float d0 = m0 - mu, d1 = m1 - mu;
-    float s2 = fmaf(n0 * d0, d0, q0) + fmaf(n1 * d1, d1, q1);      // (an empty partial carries n = 0, mean = 0, M2 = 0)
+    const float mu = __fmul_rn(gnf_wave_sum(s1), rN);
+    const float d0 = __fsub_rn(m0, mu), d1 = __fsub_rn(m1, mu);
+    float s2 = __fadd_rn(fmaf(__fmul_rn(n0, d0), d0, q0), fmaf(__fmul_rn(n1, d1), d1, q1));      // (an empty partial carries n = 0, mean = 0, M2 = 0)
     for (int p0 = 128; p0 < P; p0 += 64) {
         float nb, mb, qb;
         part(p0, nb, mb, qb);
-        const float d = mb - mu;
-        s2 += fmaf(nb * d, d, qb);
+        const float d = __fsub_rn(mb, mu);
+        s2 = __fadd_rn(s2, fmaf(__fmul_rn(nb, d), d, qb));
     }
-    const float var = gnf_wave_sum(s2) * rN;
-    const float rstd = __builtin_amdgcn_rsqf(var + eps);
+    const float rstd = __builtin_amdgcn_rsqf(fmaf(gnf_wave_sum(s2), rN, eps));      // var = sum * rN, + eps in one rounding
 #pragma unroll
     for (int hh = 0; hh < 2; ++hh)
 #pragma unroll
         for (int j = 0; j < 4; ++j) ga[hh][j] *= rstd;
-    // ---- 4. normalise and store ----
+    // ---- 5. normalise and store ----
     if (tid < 4) {                                    // the four pad entries (frames -1 and T of both rows)
         const int hh = tid >> 1, e = (tid & 1) ? T + 1 : 0;
-        *reinterpret_cast<f32x4*>(yb + ((long long)hh * Tp + e) * 4) = f32x4{0.f, 0.f, 0.f, 0.f};
+        k4p_store16(ry, (hh * Tp + e) * 16, k4p_f32x4{0.f, 0.f, 0.f, 0.f});
     }
     for (int base = 0; base < total; base += 256 * E) {
         if (base > 0) {
 #pragma unroll
-            for (int i = 0; i < E; ++i) {
-                const int idx = base + tid + 256 * i;
-                if (idx < total) {
-                    const int hh = idx >= T, t = idx - hh * T;
-                    v[i] = *reinterpret_cast<const f32x4*>(xb + ((long long)hh * Tp + t + 1) * 4);
-                }
-            }
+            for (int i = 0; i < E; ++i) v[i] = entry(base + tid + 256 * i);
         }
 #pragma unroll
         for (int i = 0; i < E; ++i) {
@@ -293,7 +317,7 @@ __global__ void __launch_bounds__(256) gn_stream_kernel(const float* __restrict_
                 f32x4 o;
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    float r = (v[i][j] - mu) * (hh ? ga[1][j] : ga[0][j]) + (hh ? be[1][j] : be[0][j]);
+                    float r = fmaf(v[i][j] - mu, hh ? ga[1][j] : ga[0][j], hh ? be[1][j] : be[0][j]);
                     if (silu) r = r * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(r * -1.4426950408889634f));
                     o[j] = (t < Tv) ? r : 0.f;
                 }
@@ -312,7 +336,12 @@ hipError_t launch_gn_stream(const float* x1, const float* x2, int C1, int C2, in
     ProfScope ps(s, "gn_stream", 0.0, 4.0 * 2.0 * B * (double)C * T, true);
     const dim3 grid(C / 8, B), blk(256);
     const int need = (2 * T + 255) / 256;
-#define GN_ARGS x1, x2 ? x2 : x1, C1, C2, T, groups, eps, gamma, beta, ss, ss_stride, ss_off, silu, gp1, gp2 ? gp2 : gp1, y, lens, lvl
+    // channels per group and the group of a block, for the kernel's scalar unit: 16-channel blocks per group, and the divisor "8-channel
+    // blocks per group" as a multiplier / shift pair (kernels.h dma_magic); 1 / ceil(T / 32) for its partial-index arithmetic
+    const int cg16 = (C / groups) >> 4;
+    const DmaMagic gmg = dma_magic((unsigned)(2 * cg16));
+    const float inv_nT = 1.0f / (float)((T + 31) >> 5);
+#define GN_ARGS x1, x2 ? x2 : x1, C1, C2, T, cg16, gmg.m, gmg.s, inv_nT, eps, gamma, beta, ss, ss_stride, ss_off, silu, gp1, gp2 ? gp2 : gp1, y, lens, lvl
     hipEvent_t e0, e1;
     if (prof_attach_events(&e0, &e1)) {      // bench.py's instrumented step: the events ride in the dispatch
         if (need <= 1) hipExtLaunchKernelGGL(gn_stream_kernel<1>, grid, blk, 0, s, e0, e1, 0, GN_ARGS);

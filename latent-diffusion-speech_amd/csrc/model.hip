@@ -3865,7 +3865,7 @@ extern "C" int lds_test_voc_step(const float* x, const float* w1, const float* b
     return LDS_OK;
 }
 
-static int attention_test_impl(const float* qkv, float* out, int B, int C, int T, int heads, int f16math, void* stream, int tile_batch = 0);
+static int attention_test_impl(const float* qkv, float* out, int B, int C, int T, int heads, int f16math, void* stream, int tile_batch = 0, const int* lens_host = nullptr);
 extern "C" int lds_test_attention_k4p(const float* qkv, float* out, int B, int C, int T, int heads, void* stream) {
     return attention_test_impl(qkv, out, B, C, T, heads, 0, stream);
 }
@@ -3875,9 +3875,22 @@ extern "C" int lds_test_attention_f16math(const float* qkv, float* out, int B, i
 extern "C" int lds_test_attention_latency(const float* qkv, float* out, int B, int C, int T, int heads, int f16math, void* stream) {
     return attention_test_impl(qkv, out, B, C, T, heads, f16math, stream, B);      // the latency mode's choice (tile_batch = the actual batch)
 }
-static int attention_test_impl(const float* qkv, float* out, int B, int C, int T, int heads, int f16math, void* stream, int tile_batch) {
+// ragged batch (include/lds_test.h): lens = host int32 [B], the clips' lengths at the buffer's resolution
+extern "C" int lds_test_attention_ragged(const float* qkv, const int* lens, float* out, int B, int C, int T, int heads, int f16math, int latency, void* stream) {
+    if (!lens) return fail(LDS_EINVAL, "lens is null");
+    for (int b = 0; b < B; ++b)
+        if (lens[b] < 1 || lens[b] > T) return fail(LDS_EINVAL, "length out of range");
+    return attention_test_impl(qkv, out, B, C, T, heads, f16math, stream, latency ? B : 0, lens);
+}
+static int attention_test_impl(const float* qkv, float* out, int B, int C, int T, int heads, int f16math, void* stream, int tile_batch, const int* lens_host) {
     hipStream_t st = (hipStream_t)stream;
     TmpDev tmp;
+    int* dlens = nullptr;
+    if (lens_host) {
+        dlens = (int*)tmp.f((size_t)B);
+        if (!dlens) return fail(LDS_ENOMEM, "alloc");
+        HIP_TRY(hipMemcpyAsync(dlens, lens_host, sizeof(int) * B, hipMemcpyHostToDevice, st));
+    }
     float* qkp = tmp.f((size_t)B * 2 * C * T);       // plain [B][2C][T]
     float* vpl = tmp.f((size_t)B * C * T);
     float* vt = tmp.f((size_t)B * C * (T + 3));
@@ -3888,11 +3901,20 @@ static int attention_test_impl(const float* qkv, float* out, int B, int C, int T
         HIP_TRY(hipMemcpyAsync(qkp + (size_t)b * 2 * C * T, qkv + (size_t)b * 3 * C * T, sizeof(float) * 2 * C * T, hipMemcpyDeviceToDevice, st));
         HIP_TRY(hipMemcpyAsync(vpl + (size_t)b * C * T, qkv + (size_t)b * 3 * C * T + (size_t)2 * C * T, sizeof(float) * C * T, hipMemcpyDeviceToDevice, st));
     }
+    // ragged: q and k keep whatever the caller put beyond a clip's length; the value rows are zeros there, as the QKV convolution's epilogue
+    // writes them (attention_k4p.hip: a masked key's probability is 0, and 0 * V must be 0); the output buffer starts as NaN
+    if (lens_host) {
+        for (int b = 0; b < B; ++b)
+            if (lens_host[b] < T)
+                HIP_TRY(hipMemset2DAsync(vpl + (size_t)b * C * T + lens_host[b], sizeof(float) * T, 0, sizeof(float) * (T - lens_host[b]), C, st));
+        HIP_TRY(hipMemsetAsync(ko, 0xff, (size_t)B * C * (T + 2) * sizeof(float), st));
+    }
     HIP_TRY(launch_to_k4p(qkp, kqk, B, 2 * C, T, 2 * C, 0, st));
     HIP_TRY(launch_plain_to_vt(vpl, vt, B, C, T, C / heads, st));
     HIP_TRY(tap_fill(ko, (size_t)B * C * (T + 2), st));
-    if (f16math) HIP_TRY(launch_attention_k4p_f16math(kqk, vt, ko, B, C, T, heads, st, tile_batch));
-    else HIP_TRY(launch_attention_k4p(kqk, vt, ko, B, C, T, heads, st, tile_batch));
+    if (lens_host && f16math) HIP_TRY(launch_attention_k4p_f16math(kqk, vt, ko, B, C, T, heads, st, tile_batch, dlens));
+    else if (f16math) HIP_TRY(launch_attention_k4p_f16math(kqk, vt, ko, B, C, T, heads, st, tile_batch));
+    else HIP_TRY(launch_attention_k4p(kqk, vt, ko, B, C, T, heads, st, tile_batch, dlens, 0));
     HIP_TRY(tap_take(ko, (size_t)B * C * (T + 2), st));
     HIP_TRY(launch_from_k4p(ko, out, B, C, T, st));
     HIP_TRY(hipStreamSynchronize(st));

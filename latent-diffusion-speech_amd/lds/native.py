@@ -185,6 +185,7 @@ lds_test_gn_apply_split          i:ppiiiifpppipiip
 lds_debug_set_split_rule         i:i
 lds_test_attention_f16math       i:ppiiiip
 lds_test_attention_latency       i:ppiiiiip
+lds_test_attention_ragged        i:pppiiiiiip
 lds_debug_set_gn_fold            i:i
 lds_debug_set_voc_pair           i:i
 lds_debug_set_touch_weights      i:i
