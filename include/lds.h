@@ -556,6 +556,38 @@ int lds_kmeans_update(const float* X, const int64_t* labels, int64_t N, float* C
 int lds_kmeans_seed(const float* X, int64_t N, int D, int K, int64_t first_index, const float* uniforms, float* C, int64_t* picked, void* ws,
                     size_t ws_bytes, void* stream);
 
+/* ---- units retrieval: exact k-NN over a speaker's unit pool and the blend of the nearest rows (csrc/knn.hip) -----------------------------
+ * The reference has no retrieval step; this replaces the host-side approximate faiss index ("units index", index.search + the inverse-square
+ * weighting of the squared distances) that the Diffusion-SVC / RVC tool chains the reference was forked from run on the units before
+ * Unit2Mel (reference tools/infer_tools.py:83-117 is where the units pass; 22_infer_tts.py:43-52,106 the codebook gather they follow in TTS).
+ * Here the search is exact and on the device.  Stateless helpers: X dev [N][D] queries and P dev [M][D] the pool, plain row-major fp32,
+ * 16-byte aligned.
+ *   score(n, m) = x_n . p_m - h_m, h_m = |p_m|^2 / 2: lds_kmeans_assign's score on the fp32 MFMA (its arg-max is the arg-min of the squared
+ *   distance).  Every score of a query row is the same fmaf chain whatever N, the row's position, the slab or the split: duplicated pool rows
+ *   tie exactly, and a row's neighbours depend on that row and the pool only.  The k best come in descending score order, the LOWER pool
+ *   index first among equal scores.  The N x M matrix is never stored.
+ * Limits, checked before anything is enqueued (LDS_EINVAL with a message): D a multiple of 8 in 8 .. 4096, 1 <= k <= 8 and k <= M,
+ * 1 <= M <= 16,777,216 (indices are int32; the pool is addressed in slabs of at most 2^31 bytes), 1 <= N <= 2,147,483,000, ratio in [0, 1]
+ * and not NaN, no NULL pointer except where noted; a workspace smaller than lds_knn_workspace_bytes(N, M, D, k) gives LDS_ENOMEM.  The
+ * contents of the workspace on entry do not matter.  Nothing synchronises.  No floating-point atomics: every call is bit-identical on repeat. */
+/* h dev [M] = |p_m|^2 / 2 (once per pool) */
+int lds_knn_prepare(const float* P, int64_t M, int D, float* h, void* stream);
+int lds_knn_workspace_bytes(int64_t N, int64_t M, int D, int k, size_t* out);
+/* idx dev int32 [N][k] = the k nearest pool rows of every query, nearest first; score dev [N][k] or NULL = their scores
+ * (|x_n|^2 - 2 score = squared distance).  A query without k comparable scores (a NaN row) gets -1 in the missing places. */
+int lds_knn_search(const float* X, int64_t N, const float* P, const float* h, int64_t M, int D, int k, int32_t* idx, float* score, void* ws,
+                   size_t ws_bytes, void* stream);
+/* Y dev [N][D]: the search, then for the k winners d_j = sum_c (x_c - p_jc)^2 recomputed directly (not from |x|^2 - 2 score) in fp32 in one
+ * fixed order, d_j = max(d_j, 1e-12), w_j = (1 / d_j)^2 normalised by their sum taken for j ascending, z = sum_j w_j p_j (fmaf, j ascending),
+ * y_n = (1 - ratio) x_n + ratio z.  ratio = 0 gives x bit for bit, ratio = 1 with k = 1 the pool row bit for bit.  idx dev int32 [N][k] and
+ * dist dev [N][k] (the floored d_j), either may be NULL.  Every gathered index is clamped into [0, M) before it forms an address. */
+int lds_knn_retrieve(const float* X, int64_t N, const float* P, const float* h, int64_t M, int D, int k, float ratio, float* Y, int32_t* idx,
+                     float* dist, void* ws, size_t ws_bytes, void* stream);
+/* the same over a ragged batch X dev [B][T][D]: lengths host int32 [B] (B <= 64, 0 <= lengths[b] <= T); rows t >= lengths[b] get y = 0,
+ * idx = -1 and dist = 0 whatever they hold.  Workspace of N = B * T. */
+int lds_knn_retrieve_ragged(const float* X, int B, int T, const int32_t* lengths, const float* P, const float* h, int64_t M, int D, int k,
+                            float ratio, float* Y, int32_t* idx, float* dist, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- polyphase sinc resampler in front of the audio encoders (reference torchaudio.transforms.Resample(orig_freq, new_freq) with its
  *      defaults sinc_interp_hann / lowpass_filter_width 6 / rolloff 0.99, i.e. torchaudio's _get_sinc_resample_kernel +
  *      _apply_sinc_resample_kernel; called from tools/tools.py:78-84 Units_Encoder.encode, diffusion/vocoder.py:24-27 Vocoder.extract and

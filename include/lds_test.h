@@ -228,6 +228,13 @@ int lds_test_w2vbert_dwconv(const float* x, const float* w, const float* gamma, 
 int lds_test_stft_dft(const float* audio, const double* basis, const float* mel_basisT, int n_fft_new, int hop_new, int n_mels, int F, float* out,
                       double* dft, int B, int64_t L, void* stream);
 
+/* lds_knn_search (include/lds.h, csrc/knn.hip) with the pool's cut forced by the caller, so that the slab and split paths run at toy sizes:
+ * slab_rows (a multiple of 128 that one buffer descriptor holds) pool rows per descriptor, `splits` (1 .. 64) ranges of 128-row pool blocks,
+ * each walked by its own workgroups.  The workspace holds min(splits, pool blocks) * N * (k rounded up to 1, 2, 4, 8) * 8 bytes or more
+ * (each of the two halves rounded up to 256); LDS_ENOMEM below that. */
+int lds_test_knn_search(const float* X, int64_t N, const float* P, const float* h, int64_t M, int D, int k, int slab_rows, int splits, int32_t* idx,
+                        float* score, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- debugging aids (tests/test_gpu_poison.py, tools/diag_trace.py) ----------------------------------------------------------
  * lds_debug_fill_u32: every 32-bit word of a device buffer = pattern.  Tests fill a caller workspace with NaN patterns (0x7fc07fc0 is a NaN
  * as fp32 and as two fp16 / bf16 halves) before a call: a kernel that reads a slot no kernel of THAT call wrote turns it into a NaN (or, behind

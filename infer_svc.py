@@ -5,6 +5,7 @@ vocoder as ragged batches, and one kernel joins them under the volume mask.
     python infer_svc.py -dm exp/diffusion/model_300000.pt -ue pretrain/large-v3_encoder.pt -i in.wav -o out.wav
     python infer_svc.py --synthetic -i in.wav -o out.wav          # seeded random weights (no checkpoints exist)
     python infer_svc.py --synthetic -o out.wav                    # ... and a generated recording of --synthetic_seconds
+    python infer_svc.py ... --index units_index.pt --index_ratio 0.5 --index_k 8      # units retrieval over the target speaker's pool
 """
 import argparse
 import os
@@ -38,6 +39,10 @@ def parse_args(argv=None):
     ap.add_argument("--min_len", type=int, default=5000, help="shortest piece the slicer cuts, ms")
     ap.add_argument("--batch_size", type=int, default=16, help="segments per ragged batch (1 .. 64; 1 = the reference's loop shape)")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--index", help="units_index.pt (tools/train_units_index.py): every units frame is blended with its nearest rows of this pool "
+                                    "before the diffusion model (units retrieval, exact and on the device)")
+    ap.add_argument("--index_ratio", type=float, default=0.5, help="0 .. 1: the share of the retrieved units in the blend")
+    ap.add_argument("--index_k", type=int, default=8, help="1 .. 8 nearest pool rows per frame")
     ap.add_argument("--synthetic", action="store_true")
     ap.add_argument("--synthetic_width", type=int, default=1280, help="width of the synthetic units encoder (a multiple of 64)")
     ap.add_argument("--synthetic_layers", type=int, default=4)
@@ -128,9 +133,14 @@ def main(argv=None):
         audio, sr = synthetic_recording(a.synthetic_seconds, a.sample_rate), a.sample_rate
     else:
         raise SystemExit("-i is needed")
+    index = None
+    if a.index:
+        from cluster.index import UnitsIndex
+        index = UnitsIndex.load(a.index)
     torch.manual_seed(a.seed)
     wav, rate = svc.infer_from_long_audio(audio, sr=sr, spk_id=a.spk_id, infer_speedup=a.speedup, method=a.method, threhold=a.threhold,
-                                          threhold_for_split=a.threhold_for_split, min_len=a.min_len, batch_size=a.batch_size)
+                                          threhold_for_split=a.threhold_for_split, min_len=a.min_len, batch_size=a.batch_size, index=index,
+                                          index_ratio=a.index_ratio, index_k=a.index_k)
     wav = wav.cpu().numpy()
     if a.output.endswith(".wav"):
         with wave.open(a.output, "wb") as f:

@@ -55,6 +55,10 @@ def parse_args(argv=None):
     ap.add_argument("--gemm_mode", default="f32", choices=["f32", "split_f16"], help="the UNet's GEMMs (include/lds.h lds_unet_set_gemm_mode)")
     ap.add_argument("--lm_type", default="roformer", choices=("roformer", "llama"),
                     help="which seeded LM --synthetic builds: the RoFormer encoder / decoder or the decoder-only Llama (a checkpoint's config.yaml names its own)")
+    ap.add_argument("--index", help="units_index.pt (tools/train_units_index.py): the codebook centres of the tokens are blended with their nearest "
+                                    "rows of this pool of the speaker's units before the alignment (units retrieval, exact and on the device)")
+    ap.add_argument("--index_ratio", type=float, default=0.5, help="0 .. 1: the share of the retrieved units in the blend")
+    ap.add_argument("--index_k", type=int, default=8, help="1 .. 8 nearest pool rows per frame")
     ap.add_argument("--synthetic", action="store_true")
     ap.add_argument("--synthetic_tokens", type=int, default=256)
     return ap.parse_args(argv)
@@ -415,12 +419,15 @@ def synthesize_ragged(svc, codebook, token_rows, spk_id=1, speedup=10, method="d
     return out
 
 
-def synthesize(svc, codebook, tokens, spk_id=1, speedup=10, method="dpm-solver", scale_factor=None):
-    """tokens [T] (or [B,T]) int64 on the device -> (units [B,T',C], mel [B,T',M], wav [B,1,T'*hop])"""
+def synthesize(svc, codebook, tokens, spk_id=1, speedup=10, method="dpm-solver", scale_factor=None, *, index=None, index_ratio=0.5, index_k=8):
+    """tokens [T] (or [B,T]) int64 on the device -> (units [B,T',C], mel [B,T',M], wav [B,1,T'*hop]); index (cluster.index.UnitsIndex): the
+    gathered centres are blended with their index_k nearest pool rows at index_ratio before the alignment"""
     from lds import native
     from tools.tools import units_forced_alignment
     tok = tokens if tokens.dim() == 2 else tokens[None]
     units = native.gather_rows(codebook, tok)                                  # semantic_embedding(semantic_token), 22_infer_tts.py:106
+    if index is not None:
+        units = index.retrieve(units, k=index_k, ratio=index_ratio)
     if scale_factor is not None:
         units = units_forced_alignment(units, scale_factor=scale_factor)
     mel = svc(units, f0=None, volume=None, spk_id=spk_id, infer_speedup=speedup, method=method)
@@ -473,7 +480,11 @@ def main(argv=None):
         else:
             tokens = text2semantic(lm, pt[0:1], pt[1:2], a.spk_id, a.max_length, a.num_beams, a.no_repeat_ngram_size, **prompt)
         tokens = tokens.clamp(max=codebook.shape[0] - 1)      # pad ids of finished rows (batch > 1) have no codebook row
-    _, _, wav = synthesize(svc, codebook, tokens, a.spk_id, a.speedup, a.method, a.scale_factor)
+    index = None
+    if a.index:
+        from cluster.index import UnitsIndex
+        index = UnitsIndex.load(a.index)
+    _, _, wav = synthesize(svc, codebook, tokens, a.spk_id, a.speedup, a.method, a.scale_factor, index=index, index_ratio=a.index_ratio, index_k=a.index_k)
     wav = wav[0, 0].cpu().numpy()
     if a.output.endswith(".wav"):
         import wave

@@ -1,0 +1,487 @@
+// Units retrieval (the "units index" of the Diffusion-SVC / RVC tool chains, there an approximate faiss index on the host): exact k-NN of
+// every query frame over a speaker's unit pool and the inverse-square blend of the k nearest pool rows, fp32, gfx950.
+//   search   score of pool row m for query n = x_n . p_m - h_m, h_m = |p_m|^2 / 2 (kmeans.hip's assign score: its arg-max is the arg-min of the
+//            squared distance); the k best in descending score order, the lower pool index first among equal scores.  kmeans_assign_kernel's
+//            tiling (128 x 128 tiles, both operands by LDS-DMA with the source-side swizzle, v_mfma_f32_32x32x2_f32), so every score of a query
+//            row is the same fmaf chain whatever N, the row's position, the slab or the split; the N x M matrix is never stored.  Each lane
+//            keeps a sorted list of KT (score, index) pairs for each of its two query columns in registers (KT = k rounded up to 1, 2, 4, 8).
+//   slabs    a buffer descriptor addresses 2^31 bytes: the pool is cut into slabs of whole 128-row blocks, each with its own descriptor base.
+//   splits   a workgroup walks a contiguous range of pool blocks; the per-split lists go to the workspace as [split][N][KT].
+//   blend    one wave per query row merges the splits' lists in split order, recomputes the k distances directly as sum (x - p)^2, forms
+//            w = (1 / max(d, 1e-12))^2, normalises and writes y = (1 - ratio) x + ratio sum w_j p_j.
+// No floating-point atomics; every slot of the workspace that is read was written by the same call.
+#include "../../include/lds.h"
+#include "../../include/lds_test.h"
+#include "kernels.h"
+
+#include <math.h>
+
+namespace lds {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int kKnB = 128;                  // query rows / pool rows per tile
+constexpr int kKnBK = 32;                  // d per K-step: one 128-byte line of every row
+constexpr int kKnTile = kKnB * kKnBK;      // floats per operand tile
+constexpr int kKnOob = 0x7fff0000;         // a buffer offset beyond every slab (slabs are cut below it): the DMA stores zeros
+constexpr int kKnNone = 0x7fffffff;        // the index of an empty list entry (score -inf): sorts behind every pool row
+constexpr int kKnMaxK = 8;
+
+struct KnLens { int n, T; int v[64]; };    // ragged form: B = n clips of T rows, v[b] valid rows; n = 0: plain
+
+// (score, index) order of the lists: higher score first, the lower index among equal scores
+static __device__ __forceinline__ bool kn_before(float v, int i, float w, int j) { return v > w || (v == w && i < j); }
+
+// 256 threads = 2 x 2 waves; wave (wm, wn) owns pool rows wm*64 .. +64 (MFMA rows, spread over the accumulator registers) and queries
+// wn*64 .. +64 (MFMA columns, one per lane) of a 128 x 128 tile.  grid (query row blocks, splits).  The LDS image of a tile and the swizzle
+// on the source address are kmeans_assign_kernel's.  Pool block b (128 rows) lies in slab b / slab_blocks; a block never straddles two slabs.
+// A lane meets the pool rows of a query column in increasing index order, so inserting on a strictly greater score keeps the lower index first.
+template <int KT>
+__global__ void __launch_bounds__(256) knn_topk_kernel(const float* __restrict__ X, long long N, const float* __restrict__ P, const float* __restrict__ hh,
+                                                       int M, int D, int slab_blocks, int pb_per_split, float* __restrict__ lval, int* __restrict__ lidx) {
+    __shared__ __attribute__((aligned(16))) float smem[4 * kKnTile];      // 2 stages x (X tile, P tile) = 64 KB
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int c = lane & 31, h = lane >> 5, wm = wave >> 1, wn = wave & 1;
+    const long long n0 = (long long)blockIdx.x * kKnB;
+    const int rows = (int)((N - n0) < kKnB ? (N - n0) : kKnB);
+    const int nPB = (M + kKnB - 1) / kKnB;
+    const int pb0 = blockIdx.y * pb_per_split;
+    const int pb1 = pb0 + pb_per_split < nPB ? pb0 + pb_per_split : nPB;
+    const int nk = (D + kKnBK - 1) / kKnBK;
+    const int slab_rows = slab_blocks * kKnB;
+    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(X + n0 * D), 0, rows * D * 4, 0x00020000);
+    int xoff[4], crow[4], kch[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int row = (wave * 4 + i) * 8 + (lane >> 3);
+        const int ch = (lane & 7) ^ ((row >> 1) & 7);
+        crow[i] = row;
+        kch[i] = ch * 4;
+        xoff[i] = (row < rows ? row : rows - 1) * D * 4 + ch * 16;      // rows beyond N read the last row (their lists are not stored)
+    }
+    auto issue = [&](int pb, int ks, float* st) {
+        const int k0 = ks * kKnBK;
+        const bool tail = k0 + kKnBK > D;
+        const int slab = pb / slab_blocks;                                     // wave-uniform: the descriptor lives in scalar registers
+        const int r0 = slab * slab_rows;                                       // the slab's first pool row; it holds srows of them
+        const int srows = M - r0 < slab_rows ? M - r0 : slab_rows;
+        const __amdgpu_buffer_rsrc_t rp = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(P + (long long)r0 * D), 0, srows * D * 4, 0x00020000);
+        const int b0 = pb * kKnB - r0;                                         // the block's first row inside the slab
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            int pr = b0 + crow[i];
+            pr = pr < srows ? pr : srows - 1;                                  // pool rows beyond M read the last one (masked in the epilogue)
+            int vx = xoff[i], vp = pr * D * 4 + kch[i] * 4;
+            if (tail && k0 + kch[i] >= D) vx = vp = kKnOob;                     // d beyond D: zeros for both operands
+            float* dst = st + (wave * 4 + i) * 256;
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (__attribute__((address_space(3))) void*)dst, 16, vx, k0 * 4, 0, 0);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rp, (__attribute__((address_space(3))) void*)(dst + kKnTile), 16, vp, k0 * 4, 0, 0);
+        }
+    };
+    int pos[4];
+#pragma unroll
+    for (int g = 0; g < 4; ++g) pos[g] = ((2 * g + h) ^ ((c >> 1) & 7)) * 4;
+    f32x16 acc[2][2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    float lv[2][KT];
+    int li[2][KT];
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int p = 0; p < KT; ++p) { lv[j][p] = -INFINITY; li[j][p] = kKnNone; }
+
+    const int total = (pb1 - pb0) * nk;
+    int pb = pb0, ks = 0;           // the tile being computed
+    int ipb = pb0, iks = 0;         // the tile being fetched
+    issue(ipb, iks, smem);
+    for (int s = 0; s < total; ++s) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();            // tile s has landed for everyone; everyone has finished reading tile s - 1
+        if (s + 1 < total) {
+            if (++iks == nk) { iks = 0; ++ipb; }
+            issue(ipb, iks, smem + ((s + 1) & 1) * 2 * kKnTile);
+        }
+        const float* xs = smem + (s & 1) * 2 * kKnTile + (wn * 64 + c) * kKnBK;
+        const float* ps = smem + (s & 1) * 2 * kKnTile + kKnTile + (wm * 64 + c) * kKnBK;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            f32x4 a[2], b[2];
+#pragma unroll
+            for (int i = 0; i < 2; ++i) a[i] = *reinterpret_cast<const f32x4*>(ps + i * 32 * kKnBK + pos[g]);
+#pragma unroll
+            for (int j = 0; j < 2; ++j) b[j] = *reinterpret_cast<const f32x4*>(xs + j * 32 * kKnBK + pos[g]);
+#pragma unroll
+            for (int jj = 0; jj < 4; ++jj)
+#pragma unroll
+                for (int i = 0; i < 2; ++i)
+#pragma unroll
+                    for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i][jj], b[j][jj], acc[i][j], 0, 0, 0);
+        }
+        if (++ks == nk) {           // a pool block is complete: scores into the lists, in increasing pool index
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int m = pb * kKnB + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                    const float hv = m < M ? hh[m] : INFINITY;
+#pragma unroll
+                    for (int j = 0; j < 2; ++j) {
+                        const float v = acc[i][j][r] - hv;
+                        acc[i][j][r] = 0.f;
+                        if (v > lv[j][KT - 1]) {      // (a NaN score, or -inf beyond M, never enters)
+#pragma unroll
+                            for (int p = KT - 1; p >= 0; --p) {
+                                const bool up = p > 0 && v > lv[j][p > 0 ? p - 1 : 0];      // the entry above moves down into p
+                                const bool here = v > lv[j][p];
+                                lv[j][p] = up ? lv[j][p > 0 ? p - 1 : 0] : (here ? v : lv[j][p]);
+                                li[j][p] = up ? li[j][p > 0 ? p - 1 : 0] : (here ? m : li[j][p]);
+                            }
+                        }
+                    }
+                }
+            ks = 0;
+            ++pb;
+        }
+    }
+    __syncthreads();
+    // the four lists of a query (two wm waves x two half-waves) meet in LDS: [list q][entry p][query], 4 * KT * 128 values and as many indices
+    float* rv = smem;
+    int* ri = reinterpret_cast<int*>(smem + 4 * KT * kKnB);
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int p = 0; p < KT; ++p) {
+            rv[((wm * 2 + h) * KT + p) * kKnB + wn * 64 + j * 32 + c] = lv[j][p];
+            ri[((wm * 2 + h) * KT + p) * kKnB + wn * 64 + j * 32 + c] = li[j][p];
+        }
+    __syncthreads();
+    if (tid < rows) {
+        int at[4] = {0, 0, 0, 0};
+        const long long o = ((long long)blockIdx.y * N + n0 + tid) * KT;
+        for (int p = 0; p < KT; ++p) {
+            float bv = -INFINITY;
+            int bi = kKnNone, bq = 0;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int a = at[q] < KT ? at[q] : KT - 1;
+                const float v = at[q] < KT ? rv[(q * KT + a) * kKnB + tid] : -INFINITY;
+                const int i = at[q] < KT ? ri[(q * KT + a) * kKnB + tid] : kKnNone;
+                if (kn_before(v, i, bv, bi)) { bv = v; bi = i; bq = q; }
+            }
+#pragma unroll
+            for (int q = 0; q < 4; ++q) at[q] += (q == bq && bi != kKnNone) ? 1 : 0;
+            lval[o + p] = bv;
+            lidx[o + p] = bi;
+        }
+    }
+}
+
+// the final list of a query row: the splits' lists merged in split order under the same rule.  Entries whose index is not a pool row (the
+// empty entries of a split that holds fewer than KT rows) are dropped.  bv / bi: 8 entries, (-inf, kKnNone) where fewer than 8 exist.
+static __device__ __forceinline__ void kn_merge(const float* __restrict__ lval, const int* __restrict__ lidx, int S, int KT, long long N, long long n, int M,
+                                                float (&bv)[kKnMaxK], int (&bi)[kKnMaxK]) {
+#pragma unroll
+    for (int q = 0; q < kKnMaxK; ++q) { bv[q] = -INFINITY; bi[q] = kKnNone; }
+    for (int s = 0; s < S; ++s) {
+        const long long o = ((long long)s * N + n) * KT;
+        for (int p = 0; p < KT; ++p) {
+            const float v = lval[o + p];
+            const int i = lidx[o + p];
+            if (i < 0 || i >= M) break;                                        // the list is sorted: only empty entries follow
+            if (!kn_before(v, i, bv[kKnMaxK - 1], bi[kKnMaxK - 1])) break;     // nor can a later entry of this list enter
+#pragma unroll
+            for (int q = kKnMaxK - 1; q >= 0; --q) {
+                const bool up = q > 0 && kn_before(v, i, bv[q > 0 ? q - 1 : 0], bi[q > 0 ? q - 1 : 0]);
+                const bool here = kn_before(v, i, bv[q], bi[q]);
+                bv[q] = up ? bv[q > 0 ? q - 1 : 0] : (here ? v : bv[q]);
+                bi[q] = up ? bi[q > 0 ? q - 1 : 0] : (here ? i : bi[q]);
+            }
+        }
+    }
+}
+
+// search only: one thread per query row writes idx [N][k] (-1 where the row has fewer than k comparable scores: a NaN query) and the scores
+__global__ void __launch_bounds__(256) knn_select_kernel(const float* __restrict__ lval, const int* __restrict__ lidx, int S, int KT, long long N, int M, int k,
+                                                         int* __restrict__ idx, float* __restrict__ score) {
+    const long long n = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (n >= N) return;
+    float bv[kKnMaxK];
+    int bi[kKnMaxK];
+    kn_merge(lval, lidx, S, KT, N, n, M, bv, bi);
+#pragma unroll
+    for (int q = 0; q < kKnMaxK; ++q)
+        if (q < k) {
+            idx[n * k + q] = bi[q] == kKnNone ? -1 : bi[q];
+            if (score) score[n * k + q] = bv[q];
+        }
+}
+
+// One wave per query row (4 rows per workgroup).  Every lane merges the row's lists (the same addresses in all lanes); lane l then takes the
+// columns 4 (l + 64 t) .. + 4 of x and of the k pool rows: d_j = sum (x - p_j)^2 by one fmaf chain per lane in ascending column order and
+// a fixed butterfly over the lanes, d_j = max(d_j, 1e-12), w_j = (1 / d_j)^2, normalised by their sum taken for j ascending;
+// z = w_0 p_0, then fmaf for j ascending; y = x at ratio 0, z at ratio 1, fmaf(ratio, z, (1 - ratio) x) between.  Every pool index is clamped
+// into [0, M) before it forms an address; an entry that is no pool row has weight 0.  Rows at and beyond a clip's length: y = 0, idx = -1, dist = 0.
+__global__ void __launch_bounds__(256) knn_blend_kernel(const float* __restrict__ X, long long N, const float* __restrict__ P, int M, int D,
+                                                        const float* __restrict__ lval, const int* __restrict__ lidx, int S, int KT, int k, float ratio,
+                                                        float* __restrict__ Y, int* __restrict__ idx, float* __restrict__ dist, const KnLens lens) {
+    const int lane = threadIdx.x & 63;
+    const long long n = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (n >= N) return;
+    const int D4 = D >> 2;
+    f32x4* y = reinterpret_cast<f32x4*>(Y + n * D);
+    if (lens.n > 0 && (int)(n % lens.T) >= lens.v[n / lens.T]) {
+        const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+        for (int t = lane; t < D4; t += 64) y[t] = zero;
+        if (lane < k) {
+            if (idx) idx[n * k + lane] = -1;
+            if (dist) dist[n * k + lane] = 0.f;
+        }
+        return;
+    }
+    float bv[kKnMaxK];
+    int bi[kKnMaxK];
+    kn_merge(lval, lidx, S, KT, N, n, M, bv, bi);
+    const f32x4* x = reinterpret_cast<const f32x4*>(X + n * D);
+    const f32x4* pr[kKnMaxK];
+    bool ok[kKnMaxK];
+#pragma unroll
+    for (int j = 0; j < kKnMaxK; ++j) {
+        ok[j] = j < k && bi[j] >= 0 && bi[j] < M;
+        const int m = bi[j] < 0 ? 0 : (bi[j] >= M ? M - 1 : bi[j]);
+        pr[j] = reinterpret_cast<const f32x4*>(P + (long long)m * D);
+    }
+    float d[kKnMaxK];
+#pragma unroll
+    for (int j = 0; j < kKnMaxK; ++j) d[j] = 0.f;
+    for (int t = lane; t < D4; t += 64) {
+        const f32x4 xv = x[t];
+#pragma unroll
+        for (int j = 0; j < kKnMaxK; ++j)
+            if (j < k) {
+                const f32x4 pv = pr[j][t];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const float u = xv[e] - pv[e];
+                    d[j] = fmaf(u, u, d[j]);
+                }
+            }
+    }
+    float w[kKnMaxK], sum = 0.f;
+#pragma unroll
+    for (int j = 0; j < kKnMaxK; ++j) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) d[j] += __shfl_xor(d[j], o, 64);
+        d[j] = fmaxf(d[j], 1e-12f);
+        const float r = __fdiv_rn(1.0f, d[j]);
+        w[j] = ok[j] ? __fmul_rn(r, r) : 0.f;
+        if (j < k) sum = __fadd_rn(sum, w[j]);
+    }
+#pragma unroll
+    for (int j = 0; j < kKnMaxK; ++j) w[j] = __fdiv_rn(w[j], sum);
+    const float keep = 1.0f - ratio;
+    for (int t = lane; t < D4; t += 64) {
+        const f32x4 xv = x[t];
+        f32x4 z;
+        {
+            const f32x4 pv = pr[0][t];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) z[e] = __fmul_rn(w[0], pv[e]);
+        }
+#pragma unroll
+        for (int j = 1; j < kKnMaxK; ++j)
+            if (j < k) {
+                const f32x4 pv = pr[j][t];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) z[e] = fmaf(w[j], pv[e], z[e]);
+            }
+        f32x4 out;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) out[e] = ratio == 0.f ? xv[e] : (ratio == 1.f ? z[e] : fmaf(ratio, z[e], __fmul_rn(keep, xv[e])));
+        y[t] = out;
+    }
+#pragma unroll
+    for (int j = 0; j < kKnMaxK; ++j)
+        if (j < k && lane == j) {
+            if (idx) idx[n * k + j] = ok[j] ? bi[j] : -1;
+            if (dist) dist[n * k + j] = d[j];
+        }
+}
+
+// h[m] = |p_m|^2 / 2: one wave per pool row, lanes stride the columns, fixed butterfly (a duplicated row gets the same h)
+__global__ void __launch_bounds__(256) knn_prepare_kernel(const float* __restrict__ P, long long M, int D, float* __restrict__ hh) {
+    const int lane = threadIdx.x & 63;
+    const long long m = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (m >= M) return;
+    const float* r = P + m * D;
+    float s = 0.f;
+    for (int d = lane; d < D; d += 64) s = fmaf(r[d], r[d], s);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    if (lane == 0) hh[m] = 0.5f * s;
+}
+
+}  // namespace lds
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// C ABI (include/lds.h, include/lds_test.h)
+// ---------------------------------------------------------------------------------------------------------------------------------
+namespace {
+
+using lds::set_error;
+
+constexpr long long kKnMaxM = 16777216LL;
+constexpr long long kKnMaxN = 2147483000LL;
+constexpr int kKnMaxSplits = 64;
+
+struct KnPlan {
+    int KT;                     // the list length: k rounded up to 1, 2, 4, 8
+    int slab_blocks;            // 128-row pool blocks per slab
+    int S, pbps;                // splits, pool blocks per split
+    size_t o_val, o_idx, bytes;
+};
+
+int kn_check_dims(const char* fn, long long N, long long M, int D, int k) {
+    if (D < 8 || D > 4096 || D % 8) return set_error(LDS_EINVAL, "%s: D %d must be a multiple of 8 in 8 .. 4096", fn, D);
+    if (M < 1 || M > kKnMaxM) return set_error(LDS_EINVAL, "%s: M %lld outside 1 .. 16777216", fn, M);
+    if (k < 1 || k > lds::kKnMaxK || k > M) return set_error(LDS_EINVAL, "%s: k %d outside 1 .. min(8, M = %lld)", fn, k, M);
+    if (N < 1 || N > kKnMaxN) return set_error(LDS_EINVAL, "%s: N %lld outside 1 .. 2147483000", fn, N);
+    return LDS_OK;
+}
+
+// the most pool rows one buffer descriptor takes: whole 128-row blocks below the out-of-range offset the DMA tail uses (itself below 2^31 - 1)
+int kn_slab_rows(int D) {
+    const long long r = ((long long)lds::kKnOob / (4LL * D)) / lds::kKnB * lds::kKnB;
+    return (int)(r < kKnMaxM ? r : kKnMaxM);
+}
+
+// slab_rows / splits 0: the library's choice
+KnPlan kn_plan(long long N, long long M, int D, int k, int slab_rows, int splits) {
+    KnPlan p;
+    p.KT = k <= 1 ? 1 : k <= 2 ? 2 : k <= 4 ? 4 : 8;
+    p.slab_blocks = (slab_rows > 0 ? slab_rows : kn_slab_rows(D)) / lds::kKnB;
+    const long long rb = (N + lds::kKnB - 1) / lds::kKnB;
+    const int nPB = (int)((M + lds::kKnB - 1) / lds::kKnB);
+    long long s = splits > 0 ? splits : (rb >= 512 ? 1 : 512 / rb);      // enough workgroups for two per CU when the row blocks alone do not give them
+    if (s > kKnMaxSplits) s = kKnMaxSplits;
+    if (s > nPB) s = nPB;
+    p.pbps = (int)((nPB + s - 1) / s);
+    p.S = (nPB + p.pbps - 1) / p.pbps;
+    size_t o = 0;
+    auto take = [&](size_t n) { const size_t at = o; o += (n + 255) & ~(size_t)255; return at; };
+    p.o_val = take((size_t)p.S * (size_t)N * p.KT * 4);
+    p.o_idx = take((size_t)p.S * (size_t)N * p.KT * 4);
+    p.bytes = o;
+    return p;
+}
+
+int kn_launched(const char* fn) {
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? LDS_OK : set_error(LDS_EHIP, "%s: %s", fn, hipGetErrorString(e));
+}
+
+bool kn_misaligned(const void* p) { return ((uintptr_t)p & 15) != 0; }
+
+void kn_topk(const KnPlan& p, const float* X, long long N, const float* P, const float* h, int M, int D, float* lval, int* lidx, hipStream_t s) {
+    lds::ProfScope ps(s, "knn_topk", 2.0 * (double)N * M * D, 4.0 * ((double)N * D + (double)M * D * ((N + 127) / 128)));
+    const dim3 grid((unsigned)((N + lds::kKnB - 1) / lds::kKnB), p.S);
+    switch (p.KT) {
+        case 1: hipLaunchKernelGGL(lds::knn_topk_kernel<1>, grid, dim3(256), 0, s, X, N, P, h, M, D, p.slab_blocks, p.pbps, lval, lidx); break;
+        case 2: hipLaunchKernelGGL(lds::knn_topk_kernel<2>, grid, dim3(256), 0, s, X, N, P, h, M, D, p.slab_blocks, p.pbps, lval, lidx); break;
+        case 4: hipLaunchKernelGGL(lds::knn_topk_kernel<4>, grid, dim3(256), 0, s, X, N, P, h, M, D, p.slab_blocks, p.pbps, lval, lidx); break;
+        default: hipLaunchKernelGGL(lds::knn_topk_kernel<8>, grid, dim3(256), 0, s, X, N, P, h, M, D, p.slab_blocks, p.pbps, lval, lidx); break;
+    }
+}
+
+int kn_search(const char* fn, const float* X, long long N, const float* P, const float* h, long long M, int D, int k, int slab_rows, int splits,
+              int32_t* idx, float* score, void* ws, size_t ws_bytes, hipStream_t s) {
+    if (int rc = kn_check_dims(fn, N, M, D, k)) return rc;
+    if (!X || !P || !h || !idx || !ws) return set_error(LDS_EINVAL, "%s: null pointer", fn);
+    if (kn_misaligned(X) || kn_misaligned(P)) return set_error(LDS_EINVAL, "%s: X and P must be 16-byte aligned", fn);
+    const KnPlan p = kn_plan(N, M, D, k, slab_rows, splits);
+    if (ws_bytes < p.bytes) return set_error(LDS_ENOMEM, "%s: workspace %zu < %zu bytes", fn, ws_bytes, p.bytes);
+    float* lval = (float*)((char*)ws + p.o_val);
+    int* lidx = (int*)((char*)ws + p.o_idx);
+    kn_topk(p, X, N, P, h, (int)M, D, lval, lidx, s);
+    hipLaunchKernelGGL(lds::knn_select_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, lval, lidx, p.S, p.KT, N, (int)M, k, (int*)idx, score);
+    return kn_launched(fn);
+}
+
+int kn_retrieve(const char* fn, const float* X, long long N, const float* P, const float* h, long long M, int D, int k, float ratio, float* Y, int32_t* idx,
+                float* dist, void* ws, size_t ws_bytes, const lds::KnLens& lens, hipStream_t s) {
+    if (int rc = kn_check_dims(fn, N, M, D, k)) return rc;
+    if (!(ratio >= 0.f && ratio <= 1.f)) return set_error(LDS_EINVAL, "%s: ratio %g outside 0 .. 1", fn, (double)ratio);
+    if (!X || !P || !h || !Y || !ws) return set_error(LDS_EINVAL, "%s: null pointer", fn);
+    if (kn_misaligned(X) || kn_misaligned(P) || kn_misaligned(Y)) return set_error(LDS_EINVAL, "%s: X, P and Y must be 16-byte aligned", fn);
+    const KnPlan p = kn_plan(N, M, D, k, 0, 0);
+    if (ws_bytes < p.bytes) return set_error(LDS_ENOMEM, "%s: workspace %zu < %zu bytes", fn, ws_bytes, p.bytes);
+    float* lval = (float*)((char*)ws + p.o_val);
+    int* lidx = (int*)((char*)ws + p.o_idx);
+    kn_topk(p, X, N, P, h, (int)M, D, lval, lidx, s);
+    {
+        lds::ProfScope ps(s, "knn_blend", 5.0 * (double)N * k * D, 4.0 * (double)N * D * (2.0 * k + 3.0));
+        hipLaunchKernelGGL(lds::knn_blend_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, s, X, N, P, (int)M, D, lval, lidx, p.S, p.KT, k, ratio, Y,
+                           (int*)idx, dist, lens);
+    }
+    return kn_launched(fn);
+}
+
+lds::KnLens kn_plain() {
+    lds::KnLens lens;
+    lens.n = 0; lens.T = 1;
+    for (int i = 0; i < 64; ++i) lens.v[i] = 0;
+    return lens;
+}
+
+}  // namespace
+
+extern "C" int lds_knn_prepare(const float* P, int64_t M, int D, float* h, void* stream) {
+    if (int rc = kn_check_dims("lds_knn_prepare", 1, M, D, 1)) return rc;
+    if (!P || !h) return set_error(LDS_EINVAL, "lds_knn_prepare: null pointer");
+    hipLaunchKernelGGL(lds::knn_prepare_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, (hipStream_t)stream, P, (long long)M, D, h);
+    return kn_launched("lds_knn_prepare");
+}
+
+extern "C" int lds_knn_workspace_bytes(int64_t N, int64_t M, int D, int k, size_t* out) {
+    if (!out) return set_error(LDS_EINVAL, "lds_knn_workspace_bytes: null out");
+    if (int rc = kn_check_dims("lds_knn_workspace_bytes", N, M, D, k)) return rc;
+    *out = kn_plan(N, M, D, k, 0, 0).bytes;
+    return LDS_OK;
+}
+
+extern "C" int lds_knn_search(const float* X, int64_t N, const float* P, const float* h, int64_t M, int D, int k, int32_t* idx, float* score, void* ws,
+                              size_t ws_bytes, void* stream) {
+    return kn_search("lds_knn_search", X, N, P, h, M, D, k, 0, 0, idx, score, ws, ws_bytes, (hipStream_t)stream);
+}
+
+extern "C" int lds_knn_retrieve(const float* X, int64_t N, const float* P, const float* h, int64_t M, int D, int k, float ratio, float* Y, int32_t* idx,
+                                float* dist, void* ws, size_t ws_bytes, void* stream) {
+    return kn_retrieve("lds_knn_retrieve", X, N, P, h, M, D, k, ratio, Y, idx, dist, ws, ws_bytes, kn_plain(), (hipStream_t)stream);
+}
+
+extern "C" int lds_knn_retrieve_ragged(const float* X, int B, int T, const int32_t* lengths, const float* P, const float* h, int64_t M, int D, int k,
+                                       float ratio, float* Y, int32_t* idx, float* dist, void* ws, size_t ws_bytes, void* stream) {
+    if (B < 1 || B > 64 || T < 1) return set_error(LDS_EINVAL, "lds_knn_retrieve_ragged: B %d outside 1 .. 64 or T %d < 1", B, T);
+    if (!lengths) return set_error(LDS_EINVAL, "lds_knn_retrieve_ragged: null lengths");
+    lds::KnLens lens = kn_plain();
+    lens.n = B; lens.T = T;
+    for (int b = 0; b < B; ++b) {
+        if (lengths[b] < 0 || lengths[b] > T) return set_error(LDS_EINVAL, "lds_knn_retrieve_ragged: lengths[%d] = %d outside 0 .. %d", b, lengths[b], T);
+        lens.v[b] = lengths[b];
+    }
+    return kn_retrieve("lds_knn_retrieve_ragged", X, (long long)B * T, P, h, M, D, k, ratio, Y, idx, dist, ws, ws_bytes, lens, (hipStream_t)stream);
+}
+
+extern "C" int lds_test_knn_search(const float* X, int64_t N, const float* P, const float* h, int64_t M, int D, int k, int slab_rows, int splits, int32_t* idx,
+                                   float* score, void* ws, size_t ws_bytes, void* stream) {
+    if (slab_rows < lds::kKnB || slab_rows % lds::kKnB || (D >= 8 && D <= 4096 && slab_rows > kn_slab_rows(D)))
+        return set_error(LDS_EINVAL, "lds_test_knn_search: slab_rows %d must be a multiple of 128 that one descriptor holds", slab_rows);
+    if (splits < 1 || splits > kKnMaxSplits) return set_error(LDS_EINVAL, "lds_test_knn_search: splits %d outside 1 .. %d", splits, kKnMaxSplits);
+    return kn_search("lds_test_knn_search", X, N, P, h, M, D, k, slab_rows, splits, idx, score, ws, ws_bytes, (hipStream_t)stream);
+}

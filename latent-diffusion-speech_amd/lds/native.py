@@ -148,6 +148,11 @@ lds_kmeans_assign                i:pqppiipppzp
 lds_kmeans_assign_ragged         i:piipqppiipppzp
 lds_kmeans_update                i:ppqpppiippzp
 lds_kmeans_seed                  i:pqiiqppppzp
+lds_knn_prepare                  i:pqipp
+lds_knn_workspace_bytes          i:qqiip
+lds_knn_search                   i:pqppqiipppzp
+lds_knn_retrieve                 i:pqppqiifppppzp
+lds_knn_retrieve_ragged          i:piipppqiifppppzp
 lds_resample                     i:ppppiiiiqqp
 lds_resample_ragged              i:ppppppiiiiqqp
 lds_frame_rms                    i:ppqiiiqp
@@ -215,6 +220,7 @@ lds_test_w2vbert_fbank           i:pppiqp
 lds_test_w2vbert_attention       i:pppppiiiiiip
 lds_test_w2vbert_dwconv          i:ppppfpppiiiip
 lds_test_stft_dft                i:pppiiiippiqp
+lds_test_knn_search              i:pqppqiiiipppzp
 """
 SIGNATURES = dict(ln.split() for ln in (_PUBLIC + _TEST).splitlines() if ln)
 EXPORTS = [ln.split()[0] for ln in _PUBLIC.splitlines() if ln]
@@ -1259,6 +1265,68 @@ def kmeans_seed(x, K, first_index, uniforms, ws=None):
     check(lib().lds_kmeans_seed(_dev(x, torch.float32), N, D, int(K), int(first_index), _dev(uniforms, torch.float32) if K > 1 else None, _dev(centers),
                                 _dev(picked), _dev(ws), ws.numel(), _stream()))
     return centers, picked
+
+
+# ---- units retrieval (lds_knn_*): thin wrappers; x [N, D] (or [B, T, D] with lengths) and pool [M, D] contiguous fp32 device tensors ----
+_knn_ws = Workspace()
+
+
+def knn_workspace_bytes(N, M, D, k):
+    return _bytes("lds_knn_workspace_bytes", int(N), int(M), int(D), int(k))
+
+
+def _knn_ws_for(ws, N, M, D, k, device):
+    if device.type != "cuda":
+        raise RuntimeError("liblds needs tensors on a HIP device (no CPU fallback for the hot path)")
+    return ws if ws is not None else _knn_ws.get(knn_workspace_bytes(N, M, D, k), device)
+
+
+def knn_prepare(pool):
+    """h [M] = |p_m|^2 / 2 of a pool [M, D] (once per pool)"""
+    import torch
+    M, D = pool.shape
+    h = torch.empty(M, dtype=torch.float32, device=pool.device)
+    check(lib().lds_knn_prepare(_dev(pool, torch.float32), M, D, _dev(h), _stream()))
+    return h
+
+
+def knn_search(x, pool, h, k, ws=None, slab_rows=None, splits=None):
+    """x [N, D] -> (idx int32 [N, k], score [N, k]): the k nearest pool rows, nearest first, the lower index among equal scores.
+    slab_rows / splits (both or neither): the pool's cut forced through lds_test_knn_search; `ws` must then be given"""
+    import torch
+    M, D = pool.shape
+    if x.dim() != 2 or x.shape[1] != D:
+        raise ValueError(f"knn_search: x {list(x.shape)} against a pool {[M, D]}")
+    N = x.shape[0]
+    idx = torch.empty(N, k, dtype=torch.int32, device=x.device)
+    score = torch.empty(N, k, dtype=torch.float32, device=x.device)
+    head = (_dev(x, torch.float32), N, _dev(pool, torch.float32), _dev(h, torch.float32), M, D, int(k))
+    if slab_rows is None:
+        ws = _knn_ws_for(ws, N, M, D, k, x.device)
+        check(lib().lds_knn_search(*head, _dev(idx), _dev(score), _dev(ws), ws.numel(), _stream()))
+    else:
+        check(lib().lds_test_knn_search(*head, int(slab_rows), int(splits), _dev(idx), _dev(score), _dev(ws), ws.numel(), _stream()))
+    return idx, score
+
+
+def knn_retrieve(x, pool, h, k, ratio, lengths=None, ws=None):
+    """x [N, D], or [B, T, D] with lengths (host ints [B], 0 .. T) -> (y like x, idx int32 [.., k], dist [.., k]): every row blended with its
+    k nearest pool rows (include/lds.h lds_knn_retrieve); rows at and beyond a clip's length: y = 0, idx = -1, dist = 0"""
+    import torch
+    M, D = pool.shape
+    if x.shape[-1] != D or x.dim() != (3 if lengths is not None else 2):
+        raise ValueError(f"knn_retrieve: x {list(x.shape)} against a pool {[M, D]}")
+    N = x.numel() // D
+    ws = _knn_ws_for(ws, N, M, D, k, x.device)
+    y = torch.empty_like(x)
+    idx = torch.empty(*x.shape[:-1], k, dtype=torch.int32, device=x.device)
+    dist = torch.empty(*x.shape[:-1], k, dtype=torch.float32, device=x.device)
+    ln = None if lengths is None else _host_lengths(lengths, x.shape[0], 0, x.shape[1], max_B=64, what="retrieval")
+    fn, ln_at = _dense_or_ragged("lds_knn_retrieve", ln)
+    rows = (N,) if ln is None else (x.shape[0], x.shape[1], *ln_at)
+    check(fn(_dev(x, torch.float32), *rows, _dev(pool, torch.float32), _dev(h, torch.float32), M, D, int(k), float(ratio), _dev(y), _dev(idx), _dev(dist),
+             _dev(ws), ws.numel(), _stream()))
+    return y, idx, dist
 
 
 # ---- polyphase resampler (lds_resample*): the filter of one (orig, new, width, rolloff) is built once on the host (arch.resample_bank) and
