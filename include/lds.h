@@ -429,8 +429,8 @@ int lds_lm_generate_opts(lds_lm* lm, const float* enc, const int32_t* enc_len, i
  * count and history are its own.  The prompt's positions but the last go through ONE causal pass that fills the decode's key/value caches
  * (the arithmetic of the cached steps, as in lds_lm_score), then the decode continues step by step.  With prompt_len 1 everywhere the call
  * IS lds_lm_generate_opts (same launches; slot 0 gets the model's BOS id).  The contents of the workspace on entry do not matter.
- * Limits (LDS_EINVAL before anything is enqueued): B <= 64; num_beams 1 (beam search from a prompt is not built: the ancestry tables
- * would need the prefix replicated per beam); P <= 16000 and B * P <= 524280; max_length <= 16000.  A workspace smaller than
+ * Limits (LDS_EINVAL before anything is enqueued): B <= 64; num_beams 1 (beam search from a prompt is not built here: the ancestry tables
+ * would need the prefix replicated per beam, or lds_llama_generate_beam's shared-prefix scheme); P <= 16000 and B * P <= 524280; max_length <= 16000.  A workspace smaller than
  * lds_lm_workspace_bytes_prompt(B, L, max_length, P) gives LDS_ENOMEM; with P = 1 that size is lds_lm_workspace_bytes_opts(.., 1, ..)'s. */
 int lds_lm_workspace_bytes_prompt(const lds_lm* lm, int B, int L, int max_length, int P, size_t* out);
 int lds_lm_generate_prompt(lds_lm* lm, const float* enc, const int32_t* enc_len, int B, int L, int max_length, const lds_lm_decode_opts* opts,
@@ -491,11 +491,31 @@ int  lds_llama_workspace_bytes(const lds_llama* h, int B, int P, int max_length,
  * One causal pass over the prompts' positions but the last fills the key/value caches (kv_heads of them per row), then the decode continues step by
  * step; prefill rows and decode steps run the same kernels, so a row equals that row run alone and a call continued from a longer prefix, tokens and
  * logits bit for bit.  The workspace's contents on entry do not matter.  The call synchronises the stream every 8 steps to poll for EOS.
- * Limits (LDS_EINVAL with a message before anything is enqueued): num_beams 1 (beam search is not built: HF's log_softmax runs over the whole
- * vocabulary, banned columns included); B <= 64; P and max_length <= 15000; max_length <= max_pos; the lds_lm_decode_opts checks of
- * lds_lm_generate_opts.  A workspace smaller than lds_llama_workspace_bytes(B, P, max_length) gives LDS_ENOMEM with the size needed. */
+ * Limits (LDS_EINVAL with a message before anything is enqueued): num_beams 1 (beam search is lds_llama_generate_beam: HF's log_softmax runs
+ * over the whole vocabulary, banned columns included, which this entry's head does not form); B <= 64; P and max_length <= 15000; max_length <=
+ * max_pos; the lds_lm_decode_opts checks of lds_lm_generate_opts.  A workspace smaller than lds_llama_workspace_bytes(B, P, max_length) gives
+ * LDS_ENOMEM with the size needed. */
 int  lds_llama_generate(lds_llama* h, const int64_t* input_ids, const int32_t* in_len, int B, int P, int max_length, const lds_lm_decode_opts* opts,
                         const float* uniforms, int64_t* tokens, float* logits_out, int* n_tokens_host, void* ws, size_t ws_bytes, void* stream);
+/* Llama.generate with num_beams 2 .. 8 and do_sample 0: HF's greedy beam search (_beam_search, length_penalty 1) as lds_lm_decode_opts states it,
+ * from a decoder prompt.  Row b's decoder_prompt_len is in_len[b] -- [BOS, phones, EOS, semantic BOS] plus any semantic prompt -- so a finished
+ * hypothesis scores  sum / (length - in_len[b]),  the early-stop heuristic divides by the generated length (early_stopping 2, "never": by
+ * max_length - in_len[b]) and max_length is the total length.  Per step and beam: log_softmax over the WHOLE vocabulary (the head's low
+ * columns included, as in lds_llama_score) -> repetition penalty -> n-gram ban (both over the whole ids, phones included) -> -inf for every id
+ * below first_free_id -> + the running score; ties go to the lower index beam * vocab + token.  early_stopping is the caller's (1 / 0 / 2).
+ *   input_ids, in_len, B, P, max_length: as lds_llama_generate, one row per ITEM (not per beam).
+ *   tokens dev int64 [B][max_length]: the prompt, then the item's best finished hypothesis, EOS kept, PAD after it.  *n_tokens_host = the longest row.
+ * The prefill runs the B prompts once: all num_beams beams of an item read the positions below in_len[b] from the item's one prefilled cache row,
+ * and an ancestry table over the generated positions tells the attention which beam row holds each later key.  Every item equals that item run
+ * alone (B = 1), token for token: items reach max_length and the end of HF's loop at steps of their own, and an item whose loop has ended is
+ * frozen.  The loop stays on the stream; every 8 steps the step's flag bits are polled, and the result does not depend on that interval.  The
+ * workspace's contents on entry do not matter.
+ * Limits (LDS_EINVAL with a message before anything is enqueued): the lds_lm_decode_opts checks; num_beams 2 .. 8; do_sample 0; B <= 64 and
+ * B * num_beams <= 256; P <= 15000; max_length <= 7488 and <= max_pos; in_len as for lds_llama_generate; vocab <= 4352 and vocab - first_free_id
+ * >= 2 * num_beams.  A workspace smaller than lds_llama_beam_workspace_bytes(B, P, max_length, num_beams) gives LDS_ENOMEM with the size needed. */
+int  lds_llama_beam_workspace_bytes(const lds_llama* h, int B, int P, int max_length, int num_beams, size_t* out);
+int  lds_llama_generate_beam(lds_llama* h, const int64_t* input_ids, const int32_t* in_len, int B, int P, int max_length, const lds_lm_decode_opts* opts,
+                             int64_t* tokens, int* n_tokens_host, void* ws, size_t ws_bytes, void* stream);
 
 /* Teacher-forced scoring under the Llama: what the reference's forward (llama.py:73-117) hands to LlamaForCausalLM with labels -- the logits of
  * every position of given streams in ONE causal pass, and HF's shifted cross entropy over the WHOLE vocabulary (ids below first_free_id

@@ -195,6 +195,27 @@ int lds_test_lm_beam_step(const float* logits, int B, int K, int V, int cur_len,
                           const float* fin_score, const int32_t* fin_flag, const int32_t* fin_len, const int32_t* unsat, int64_t* run_seq_out,
                           float* run_score_out, int32_t* parent_out, int64_t* fin_seq_out, float* fin_score_out, int32_t* fin_flag_out,
                           int32_t* fin_len_out, int32_t* unsat_out, int32_t* flag_out, void* stream);
+/* ONE step of lds_llama_generate_beam's beam search: lds_test_lm_beam_step with per-item prompts.  Item b continues a prompt of prompt_len[b]
+ * ids (HOST int32 [B]) and is at cur_len = prompt_len[b] + step: its histories are the first cur_len ids of its running sequences, and fin_len
+ * counts generated tokens.  Ids below first_free_id are banned after the n-gram ban.  ended (HOST int32 [B]): an item whose own loop has ended
+ * comes back unchanged (parent_out = 0 .. K - 1) and adds nothing to flag_out; ended_out dev int32 [B] = 2 for it (its state now stands in both
+ * buffers; an item handed in with 2 is not touched at all) and 1 for every item whose loop ends with this step.  flag_out [1]: the bits of lds_test_lm_beam_step over the items that ran, plus 16 = some item still runs.
+ * vocab <= 4352, V - first_free_id >= 2 K, prompt_len[b] + step < max_length for every item that runs. */
+int lds_test_llama_beam_step(const float* logits, int B, int K, int V, int step, int max_length, int eos, float repetition_penalty,
+                             int no_repeat_ngram_size, int early_stopping, int first_free_id, const int32_t* prompt_len, const int32_t* ended,
+                             const int64_t* run_seq, const float* run_score, const int64_t* fin_seq, const float* fin_score, const int32_t* fin_flag,
+                             const int32_t* fin_len, const int32_t* unsat, int64_t* run_seq_out, float* run_score_out, int32_t* parent_out,
+                             int64_t* fin_seq_out, float* fin_score_out, int32_t* fin_flag_out, int32_t* fin_len_out, int32_t* unsat_out,
+                             int32_t* ended_out, int32_t* flag_out, void* stream);
+/* ONE attention call of the Llama decode at step `step`: q, out dev [R][heads * d]; kc, vc dev [R][kv_heads][cap][d]; row n of item n / K is at
+ * position prompt_len[n / K] - 1 + step (prompt_len HOST int32 [R / K]).  tab dev int32 [R][tcap]: the beam attention -- key p of row n comes
+ * from cache row (n / K) * K for p < prompt_len, from row n for the last key, from tab[n][p - prompt_len] otherwise.  tab NULL (K = 1): the
+ * plain attention of lds_llama_generate, every row on its own cache row. */
+int lds_test_llama_beam_attn(const float* q, const float* kc, const float* vc, const int32_t* tab, const int32_t* prompt_len, int R, int K, int heads,
+                             int kv_heads, int d, int cap, int tcap, int step, float* out, void* stream);
+/* lds_llama_generate_beam with `poll` steps (>= 1) between two polls of the flag bits in place of its own 8: the result must not depend on it. */
+int lds_test_llama_generate_beam_poll(lds_llama* h, const int64_t* input_ids, const int32_t* in_len, int B, int P, int max_length,
+                                      const lds_lm_decode_opts* opts, int64_t* tokens, int* n_tokens_host, void* ws, size_t ws_bytes, void* stream, int poll);
 
 /* The wav2vec 2.0 encoder's own kernels alone (csrc/w2v.hip); every pointer but the lengths is a device pointer.
  * w2v_conv0: audio [B][L] -> out [B][C][N0], N0 = (L - 10) / 5 + 1: GELU(LayerNorm over the C channels of each frame(bias + conv0(clip)));

@@ -15,6 +15,9 @@
 //   scoring        lds_llama_score: ONE causal pass over all B * S rows of given streams through the same kernels (a row's position is all that
 //                  tells it from a decode step), then the head over the WHOLE vocabulary -- the low columns from a second packed matrix, the
 //                  columns first_free_id .. by the decode's own launch at another column address -- and lm.hip's row statistics and loss
+//   beam search    lds_llama_generate_beam: B * K beam rows behind ONE prefill row per item; ll_attn_beam_kernel reads generated keys through the
+//                  beams' ancestry table and prompt keys from the item's prefilled cache row; the head over the whole vocabulary as in scoring;
+//                  lm.hip's beam step in its per-row form (lm_common.h)
 #include "../../include/lds.h"
 #include "kernels.h"
 #include "lm_common.h"
@@ -33,6 +36,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // Which (batch row, position) row n of a pass is.  L > 0: the prefill, n = b * L + l at position l.  L == 0: a decode step, row b at position
 // plen[b] - 1 + step; a row that has run past the cache (it reached max_length at an earlier step) is not live and stores nothing.
+// (A beam decode's step has a row per beam: plen then has one entry per BEAM row, its item's length.)
 struct LlRows { const int32_t* plen; int L, step, cap; };
 static __device__ __forceinline__ void ll_row(const LlRows& r, int n, int& b, int& pos, bool& live) {
     if (r.L > 0) {
@@ -245,7 +249,13 @@ __global__ void __launch_bounds__(1024) ll_linear_kernel(const float* __restrict
 //      for head dims up to 256: the four waves take alternate 64-key blocks; phase 1 has a key per lane, phase 2 the channels lane, lane + 64, ..
 //      over the wave's keys in ascending order; the waves' (max, sum, partial output) meet through LDS in the order 0 .. 3.
 //      q, out [N][heads * d]; query head h reads kv head h / (heads / kv_heads). ----
+//      ll_attn_beam_kernel (a beam decode's step; ba.K beams per item) is the same arithmetic in the same order, written out a second time so
+//      that the plain decode runs the very kernel it ran before beams existed; there key p lives in cache
+//      row  item * K  for p < plen[item] (the ONE row the item's prefill filled: no look-up),  n itself for p = pos,  tab[n][p - plen[item]]
+//      otherwise -- the beam's ancestry over generated positions (lm_beam_step_kernel's table).  The source row of every key is kept beside its score
+//      in LDS for the value pass.  ended[item] != 0: the item's search is over, its rows give zeros like a row past its end. ----
 constexpr int kLlMaxHeadDim = 256;
+struct LlBeamAttn { const int* tab; const int* ended; int tcap, K; };
 __global__ void __launch_bounds__(256) ll_attn_kernel(const float* __restrict__ q, const float* __restrict__ kc, const float* __restrict__ vc, const LlRows rows,
                                                       int heads, int kv_heads, int d, int Lkp, float* __restrict__ out) {
     extern __shared__ __attribute__((aligned(16))) float sa[];      // qs [256], sc [Lkp], mrg [4][2 + 256]
@@ -331,6 +341,143 @@ __global__ void __launch_bounds__(256) ll_attn_kernel(const float* __restrict__ 
         }
         out[(long long)n * QD + h * d + tid] = o / tot;
     }
+}
+// the beam decode's sibling: ll_attn_kernel line for line, but for where a key's row comes from (above); a change to either belongs in both --
+// tests/test_gpu_llama_beam.py holds the two bit for bit
+__global__ void __launch_bounds__(256) ll_attn_beam_kernel(const float* __restrict__ q, const float* __restrict__ kc, const float* __restrict__ vc, const LlRows rows,
+                                                           int heads, int kv_heads, int d, int Lkp, float* __restrict__ out, const LlBeamAttn ba) {
+    extern __shared__ __attribute__((aligned(16))) float sa[];      // qs [256], sc [Lkp], mrg [4][2 + 256], src [Lkp]
+    float* qs = sa;
+    float* sc = sa + kLlMaxHeadDim;
+    float* mrg = sc + Lkp;
+    int* src = reinterpret_cast<int*>(mrg + 4 * (2 + kLlMaxHeadDim));
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int h = blockIdx.x % heads, n = blockIdx.x / heads;
+    int b, pos;
+    bool live;
+    ll_row(rows, n, b, pos, live);
+    const int QD = heads * d, kvh = h / (heads / kv_heads);
+    const int item = n / ba.K, row0 = item * ba.K, pl = rows.plen[n];
+    if (ba.ended && ba.ended[item]) live = false;
+    if (!live) {      // (uniform over the workgroup) a row past its end: zeros, so that what follows in its row stays finite and depends on nothing stale
+        if (tid < d) out[(long long)n * QD + h * d + tid] = 0.f;
+        return;
+    }
+    int Lk = pos + 1;
+    Lk = Lk < Lkp ? Lk : Lkp;
+    if (tid < d) qs[tid] = q[(long long)n * QD + h * d + tid];
+    __syncthreads();
+    const float scale = 1.0f / sqrtf((float)d);
+    float mx = -INFINITY;
+    for (int k0 = wave * 64; k0 < Lk; k0 += 256) {
+        const int key = k0 + lane;
+        float dot = -INFINITY;
+        if (key < Lk) {
+            dot = 0.f;
+            int r = row0;
+            if (key >= pl) {
+                r = (key == pos) ? n : ba.tab[(long long)n * ba.tcap + key - pl];
+                r = r < row0 ? row0 : (r >= row0 + ba.K ? row0 + ba.K - 1 : r);      // (a row of the item's, whatever the table holds)
+            }
+            src[key] = r;
+            const f32x4* kr = reinterpret_cast<const f32x4*>(kc + (((long long)r * kv_heads + kvh) * rows.cap + key) * d);
+            const f32x4* q4 = reinterpret_cast<const f32x4*>(qs);
+            for (int e4 = 0; e4 < (d >> 2); e4 += 4) {      // d is a multiple of 16
+                f32x4 kv[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) kv[u] = kr[e4 + u];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const f32x4 qv = q4[e4 + u];
+                    dot = fmaf(qv[0], kv[u][0], dot); dot = fmaf(qv[1], kv[u][1], dot); dot = fmaf(qv[2], kv[u][2], dot); dot = fmaf(qv[3], kv[u][3], dot);
+                }
+            }
+            dot *= scale;
+            sc[key] = dot;
+        }
+        mx = fmaxf(mx, dot);
+    }
+    mx = wave_max(mx);
+    float sum = 0.f;
+    for (int k0 = wave * 64; k0 < Lk; k0 += 256) {
+        const int key = k0 + lane;
+        float p = 0.f;
+        if (key < Lk) { p = expf(sc[key] - mx); sc[key] = p; }
+        sum += p;
+    }
+    sum = wave_sum(sum);
+    __syncthreads();      // the probabilities are in LDS
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int k0 = wave * 64; k0 < Lk; k0 += 256) {
+        const int kend = (k0 + 64 < Lk) ? k0 + 64 : Lk;
+        for (int key = k0; key < kend; ++key) {
+            const float p = sc[key];
+            const float* vr = vc + (((long long)src[key] * kv_heads + kvh) * rows.cap + key) * d;
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                if (lane + 64 * i < d) acc[i] = fmaf(p, vr[lane + 64 * i], acc[i]);
+        }
+    }
+    float* mw = mrg + wave * (2 + kLlMaxHeadDim);
+    if (lane == 0) { mw[0] = mx; mw[1] = sum; }
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+        if (lane + 64 * i < d) mw[2 + lane + 64 * i] = acc[i];
+    __syncthreads();
+    if (tid < d) {
+        constexpr int S = 2 + kLlMaxHeadDim;
+        const float m = fmaxf(fmaxf(mrg[0], mrg[S]), fmaxf(mrg[2 * S], mrg[3 * S]));
+        float tot = 0.f, o = 0.f;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            const float f = (mrg[w * S] > -INFINITY) ? expf(mrg[w * S] - m) : 0.f;
+            tot += mrg[w * S + 1] * f;
+            o += mrg[w * S + 2 + tid] * f;
+        }
+        out[(long long)n * QD + h * d + tid] = o / tot;
+    }
+}
+
+// the start of a beam decode, one workgroup per beam row r of item r / K: the item's prompt ids (clamped, not shifted), PAD from plen on, into both
+// buffers of the running sequences and of the finished hypotheses; HF's initial scores (running 0, -1e9, ..; finished -1e9) and flags
+__global__ void __launch_bounds__(256) ll_beam_init_kernel(const int64_t* __restrict__ ids, int P, const int32_t* __restrict__ plen, int vocab, int pad, int cap, int K,
+                                                           int64_t* __restrict__ r0, int64_t* __restrict__ r1, int64_t* __restrict__ f0, int64_t* __restrict__ f1,
+                                                           float* __restrict__ rscore, float* __restrict__ fscore, int* __restrict__ ffin, int* __restrict__ flen,
+                                                           int* __restrict__ unsat, int* __restrict__ ended) {
+    const int r = blockIdx.x, item = r / K, pl = plen[item];
+    for (int l = threadIdx.x; l < cap; l += 256) {
+        long long t = pad;
+        if (l < pl && l < P) {
+            t = ids[(long long)item * P + l];
+            t = (t < 0) ? 0 : (t >= vocab ? vocab - 1 : t);
+        }
+        const long long a = (long long)r * cap + l;
+        r0[a] = t; r1[a] = t; f0[a] = t; f1[a] = t;
+    }
+    if (threadIdx.x == 0) {
+        const bool first = r == item * K;
+        rscore[r] = first ? 0.f : -1.0e9f; fscore[r] = -1.0e9f; ffin[r] = 0; flen[r] = 0;
+        if (first) { unsat[item] = 1; ended[item] = 0; }
+    }
+}
+// after a beam decode's prefill, which filled cache rows 0 .. B - 1 like any prefill: item b's positions 0 .. Pq - 1 move to cache row b * K, the
+// first of its K beam rows.  A thread owns ONE (kv head, position, channel) of a cache (blockIdx.y: keys, values) and walks the items downwards:
+// b * K > b, so no row is overwritten before it has been moved, and no two threads touch the same float.
+__global__ void __launch_bounds__(256) ll_beam_spread_kernel(float* __restrict__ kc, float* __restrict__ vc, int B, int K, int kv_heads, int cap, int d, int Pq) {
+    float* c = blockIdx.y ? vc : kc;
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x, per = (long long)Pq * d;
+    if (e >= kv_heads * per) return;
+    const long long off = (e / per) * cap * d + e % per, row = (long long)kv_heads * cap * d;
+    for (int b = B - 1; b >= 1; --b) c[(long long)b * K * row + off] = c[b * row + off];
+}
+// the end of a beam decode, one workgroup per item: its best finished hypothesis (slot 0) up to its end, PAD after it; rowlen[b] = its length
+__global__ void __launch_bounds__(256) ll_beam_finish_kernel(const int64_t* __restrict__ fseq, const int* __restrict__ flen, const int32_t* __restrict__ plen, int K,
+                                                             int cap, int pad, int64_t* __restrict__ tokens, int* __restrict__ rowlen) {
+    const int b = blockIdx.x;
+    int n = plen[b] + flen[b * K];
+    n = n < cap ? n : cap;
+    for (int l = threadIdx.x; l < cap; l += 256) tokens[(long long)b * cap + l] = (l < n) ? fseq[(long long)b * K * cap + l] : (int64_t)pad;
+    if (threadIdx.x == 0) rowlen[b] = n;
 }
 
 }  // namespace lds
@@ -498,6 +645,18 @@ int ll_check_shape(int B, int P, int max_length) {
     if (P > kLlMaxLength || max_length > kLlMaxLength) return ll_fail(LDS_EINVAL, "prompt width %d / max_length %d too long (<= %d)", P, max_length, kLlMaxLength);
     return LDS_OK;
 }
+// the rows' prompt lengths (host): each inside 1 .. P and below max_length -> the longest and the shortest
+int ll_check_lens(const int32_t* in_len, int B, int P, int max_length, int& Pmax, int& Pmin) {
+    Pmax = 0; Pmin = P;
+    for (int b = 0; b < B; ++b) {
+        const int pl = in_len ? in_len[b] : P;
+        if (pl < 1 || pl > P) return ll_fail(LDS_EINVAL, "in_len[%d] = %d out of range (1 .. P = %d)", b, pl, P);
+        if (pl >= max_length) return ll_fail(LDS_EINVAL, "in_len[%d] = %d leaves no room below max_length = %d (the total length, prompt included)", b, pl, max_length);
+        Pmax = pl > Pmax ? pl : Pmax;
+        Pmin = pl < Pmin ? pl : Pmin;
+    }
+    return LDS_OK;
+}
 
 template <int EPI>
 hipError_t ll_linear(const float* X, int K, const float* nw, float eps, const float* Wt, const float* Wt2, int M, const float* R, float* Y, int ldy, int N,
@@ -520,7 +679,7 @@ hipError_t ll_linear(const float* X, int K, const float* nw, float eps, const fl
 }
 
 // the decoder layers over N rows (a prefill pass or a decode step, told apart by `rows` alone); Lk_max = the most keys any row sees
-int ll_layers(const lds_llama* L, const LlWs& w, int N, const LlRows& rows, int Lk_max, hipStream_t st) {
+int ll_layers(const lds_llama* L, const LlWs& w, int N, const LlRows& rows, int Lk_max, hipStream_t st, const LlBeamAttn* beam = nullptr) {
     const lds_llama_cfg& c = L->cfg;
     const int H = c.hidden, d = c.head_dim, QD = c.heads * d, KD = c.kv_heads * d, Lkp = (Lk_max + 63) & ~63;
     const size_t attn_lds = (size_t)(kLlMaxHeadDim + Lkp + 4 * (2 + kLlMaxHeadDim)) * sizeof(float);
@@ -528,8 +687,12 @@ int ll_layers(const lds_llama* L, const LlWs& w, int N, const LlRows& rows, int 
         const LlLayer& y = L->layers[i];
         const LlRope rope{L->cs, w.kc[i], w.vc[i], c.heads, c.kv_heads, d, rows};
         LL_HIP(ll_linear<LL_ROPE>(w.x, H, y.nw_attn, c.eps, y.wqkv, nullptr, QD + 2 * KD, nullptr, w.q, QD, N, st, &rope));
-        hipLaunchKernelGGL(ll_attn_kernel, dim3((unsigned)(N * c.heads)), dim3(256), attn_lds, st, (const float*)w.q, (const float*)w.kc[i], (const float*)w.vc[i], rows,
-                           c.heads, c.kv_heads, d, Lkp, w.ctx);
+        if (beam)      // (one more int per key in LDS: the key's source row)
+            hipLaunchKernelGGL(ll_attn_beam_kernel, dim3((unsigned)(N * c.heads)), dim3(256), attn_lds + (size_t)Lkp * sizeof(int), st, (const float*)w.q,
+                               (const float*)w.kc[i], (const float*)w.vc[i], rows, c.heads, c.kv_heads, d, Lkp, w.ctx, *beam);
+        else
+            hipLaunchKernelGGL(ll_attn_kernel, dim3((unsigned)(N * c.heads)), dim3(256), attn_lds, st, (const float*)w.q, (const float*)w.kc[i], (const float*)w.vc[i], rows,
+                               c.heads, c.kv_heads, d, Lkp, w.ctx);
         LL_HIP(hipGetLastError());
         LL_HIP(ll_linear<LL_RESID>(w.ctx, QD, nullptr, c.eps, y.wo, nullptr, H, w.x, w.x, H, N, st));
         LL_HIP(ll_linear<LL_SWIGLU>(w.x, H, y.nw_mlp, c.eps, y.wgate, y.wup, c.inter, nullptr, w.ff, c.inter, N, st));
@@ -554,16 +717,10 @@ extern "C" int lds_llama_generate(lds_llama* L, const int64_t* input_ids, const 
     if (!opts) return ll_fail(LDS_EINVAL, "null options");
     const lds_lm_decode_opts o = *opts;
     if (int r = lm_check_opts(o, logits_out)) return r;
-    if (o.num_beams != 1) return ll_fail(LDS_EINVAL, "beam search is not built for Llama (num_beams must be 1): HF normalises over the whole vocabulary before the ban");
+    if (o.num_beams != 1) return ll_fail(LDS_EINVAL, "lds_llama_generate takes num_beams 1; beam search over the whole vocabulary is lds_llama_generate_beam");
     if (int r = ll_check_shape(B, P, max_length)) return r;
     int Pmax = 0, Pmin = P;
-    for (int b = 0; b < B; ++b) {
-        const int pl = in_len ? in_len[b] : P;
-        if (pl < 1 || pl > P) return ll_fail(LDS_EINVAL, "in_len[%d] = %d out of range (1 .. P = %d)", b, pl, P);
-        if (pl >= max_length) return ll_fail(LDS_EINVAL, "in_len[%d] = %d leaves no room below max_length = %d (the total length, prompt included)", b, pl, max_length);
-        Pmax = pl > Pmax ? pl : Pmax;
-        Pmin = pl < Pmin ? pl : Pmin;
-    }
+    if (int r = ll_check_lens(in_len, B, P, max_length, Pmax, Pmin)) return r;
     if (!L || !input_ids || !tokens || !n_tokens_host || !ws) return ll_fail(LDS_EINVAL, "bad argument");
     const lds_llama_cfg& c = L->cfg;
     const int H = c.hidden, V = c.vocab - c.first_free_id, shift = c.first_free_id;
@@ -708,4 +865,233 @@ extern "C" int lds_llama_score(lds_llama* L, const int64_t* input_ids, const int
     }
     LL_HIP(lm_launch_score_loss(logprobs, ranks, B, S - 1, s.psum, s.pcnt, loss, n_counted, st));
     return LDS_OK;
+}
+
+// ---- greedy beam search (lds_llama_generate_beam): HF's _beam_search over B * K beam rows, every item from its own prompt.
+//      Prefill: ONE row per item (B rows, not B * K), the plain decode's own, then moved into the item's first cache row; every beam reads the
+//      positions below the item's prompt length from there.  Step s handles beam row n of item n / K at position plen[item] - 1 + s: the row's token comes from the running
+//      sequences (ll_embed_kernel), its key / value go into cache row n, ll_attn_beam_kernel follows the ancestry table over the generated
+//      positions, the head runs over the WHOLE vocabulary (scoring's two launches: HF's log_softmax sees the banned columns), and lm.hip's
+//      per-row beam step selects.  An item whose own loop has ended freezes (lm_beam_step_kernel), so every item equals its stand-alone run and the
+//      result does not depend on when the poll notices that all have ended. ----
+namespace {
+constexpr int kLlMaxBeamRows = 256;        // B * num_beams
+constexpr int kLlMaxBeamLength = 7488;     // the beam attention stages a score and a source row per key in LDS
+constexpr int kLlBeamPoll = 8;             // steps between two polls of the flag bits
+struct LlBeamWs { LlWs w; int64_t *rseq[2], *fseq[2]; int* tab[2]; float *rscore, *fscore; int *ffin, *flen, *unsat, *ended, *flags, *rowlen; int32_t* plen_rows; };
+void ll_beam_plan(const lds_llama* L, LlArena& A, int B, int P, int cap, int K, LlBeamWs& s) {
+    const lds_llama_cfg& c = L->cfg;
+    const size_t R = (size_t)B * K, Npre = (size_t)B * (P > 2 ? P - 1 : 1), N = Npre > R ? Npre : R;
+    const size_t QD = (size_t)c.heads * c.head_dim, KD = (size_t)c.kv_heads * c.head_dim;
+    LlWs& w = s.w;
+    w.x = A.f(N * c.hidden); w.q = A.f(N * QD); w.ctx = A.f(N * QD); w.ff = A.f(N * c.inter);
+    w.logits = A.f(R * c.vocab);
+    w.flags = nullptr; w.stok = nullptr;
+    w.plen = (int32_t*)A.f((size_t)B);      // per item (the beam step, the init and finish kernels)
+    s.plen_rows = (int32_t*)A.f(R);         // per beam row (LlRows)
+    w.kc.clear(); w.vc.clear();
+    for (int i = 0; i < c.layers; ++i) { w.kc.push_back(A.f(R * KD * cap)); w.vc.push_back(A.f(R * KD * cap)); }
+    for (int i = 0; i < 2; ++i) { s.rseq[i] = (int64_t*)A.f(2 * R * cap); s.fseq[i] = (int64_t*)A.f(2 * R * cap); s.tab[i] = (int*)A.f(R * cap); }
+    s.rscore = A.f(R); s.fscore = A.f(R); s.ffin = (int*)A.f(R); s.flen = (int*)A.f(R);
+    s.unsat = (int*)A.f((size_t)B); s.ended = (int*)A.f((size_t)B); s.rowlen = (int*)A.f((size_t)B);
+    s.flags = (int*)A.f((size_t)cap);
+}
+// the checks that need no model
+int ll_beam_check_shape(int B, int P, int max_length, int K) {
+    if (K < 2 || K > kMaxBeams) return ll_fail(LDS_EINVAL, "num_beams %d out of range for a beam decode (2 .. %d)", K, kMaxBeams);
+    if (int r = ll_check_shape(B, P, max_length)) return r;
+    if ((long long)B * K > kLlMaxBeamRows) return ll_fail(LDS_EINVAL, "a Llama beam decode takes at most %d beam rows, got B * num_beams = %d", kLlMaxBeamRows, B * K);
+    if (max_length > kLlMaxBeamLength) return ll_fail(LDS_EINVAL, "max_length %d too long for a beam decode (<= %d)", max_length, kLlMaxBeamLength);
+    return LDS_OK;
+}
+int ll_beam_check_model(const lds_llama* L, int K, int max_length) {
+    const lds_llama_cfg& c = L->cfg;
+    if (c.vocab > kMaxBeamVocab) return ll_fail(LDS_EINVAL, "beam search is built for vocabularies of at most %d entries, got %d", kMaxBeamVocab, c.vocab);
+    if (c.vocab - c.first_free_id < 2 * K) return ll_fail(LDS_EINVAL, "beam search needs 2 * num_beams = %d ids that are not banned, got %d", 2 * K, c.vocab - c.first_free_id);
+    if (max_length > c.max_pos) return ll_fail(LDS_EINVAL, "max_length %d exceeds max_position_embeddings %d", max_length, c.max_pos);
+    return LDS_OK;
+}
+}  // namespace
+
+extern "C" int lds_llama_beam_workspace_bytes(const lds_llama* L, int B, int P, int max_length, int num_beams, size_t* out) {
+    if (int r = ll_beam_check_shape(B, P, max_length, num_beams)) return r;
+    if (!L || !out) return ll_fail(LDS_EINVAL, "bad argument");
+    LlArena A(nullptr, 0);
+    LlBeamWs s;
+    ll_beam_plan(L, A, B, P, max_length, num_beams, s);
+    *out = A.used;
+    return LDS_OK;
+}
+
+namespace {
+// the decode; poll = the steps between two polls (the public entry's is fixed; a test entry varies it to show that the result does not depend on it)
+int ll_generate_beam(lds_llama* L, const int64_t* input_ids, const int32_t* in_len, int B, int P, int max_length, const lds_lm_decode_opts* opts, int64_t* tokens,
+                     int* n_tokens_host, void* ws, size_t ws_bytes, void* stream, int poll) {
+    if (!opts) return ll_fail(LDS_EINVAL, "null options");
+    const lds_lm_decode_opts o = *opts;
+    if (int r = lm_check_opts(o, nullptr)) return r;
+    if (o.do_sample) return ll_fail(LDS_EINVAL, "beam sampling (do_sample with beams) is not built: only greedy beam search");
+    const int K = o.num_beams;
+    if (int r = ll_beam_check_shape(B, P, max_length, K)) return r;
+    int Pmax = 0, Pmin = P;
+    if (int r = ll_check_lens(in_len, B, P, max_length, Pmax, Pmin)) return r;
+    if (!L || !input_ids || !tokens || !n_tokens_host || !ws) return ll_fail(LDS_EINVAL, "bad argument");
+    if (int r = ll_beam_check_model(L, K, max_length)) return r;
+    const lds_llama_cfg& c = L->cfg;
+    const int H = c.hidden, V = c.vocab, lo = c.first_free_id, R = B * K, cap = max_length;
+    const int Pq = Pmax - 1;
+    if ((long long)B * Pq > 8 * 65535LL) return ll_fail(LDS_EINVAL, "B * P too large for the prefill (<= 524280)");
+    hipStream_t st = (hipStream_t)stream;
+    LlArena A(ws, ws_bytes);
+    LlBeamWs s;
+    ll_beam_plan(L, A, B, P, max_length, K, s);
+    if (!A.ok) return ll_fail(LDS_ENOMEM, "Llama beam workspace too small: need %zu bytes", A.used);
+    const LlWs& w = s.w;
+    {
+        std::vector<int> pl(B), plr(R);
+        for (int b = 0; b < B; ++b) pl[b] = in_len ? in_len[b] : P;
+        for (int r = 0; r < R; ++r) plr[r] = pl[r / K];
+        LL_HIP(hipMemcpyAsync(w.plen, pl.data(), sizeof(int) * B, hipMemcpyHostToDevice, st));
+        LL_HIP(hipMemcpyAsync(s.plen_rows, plr.data(), sizeof(int) * R, hipMemcpyHostToDevice, st));
+        LL_HIP(hipStreamSynchronize(st));      // the host staging vectors go out of scope
+    }
+    const int32_t* plen = w.plen;
+    LL_HIP(hipMemsetAsync(s.flags, 0, sizeof(int) * cap, st));
+    // Prefill: lds_llama_generate's own, B rows into cache rows 0 .. B - 1 (the ids, not shifted, wait in the first B rows of a sequence buffer
+    // that the init kernel below fills afterwards); then item b's keys and values move to cache row b * K.  A shorter row's slots in_len[b] - 1 ..
+    // Pq - 1 are filled from PAD and overwritten by the item's first beam row (which IS cache row b * K) before any query reads them.
+    if (Pq > 0) {
+        hipLaunchKernelGGL(ll_init_kernel, dim3(B), dim3(256), 0, st, input_ids, P, plen, V, 0, c.pad, cap, s.rseq[1]);
+        LL_HIP(hipGetLastError());
+        const LlRows rows{plen, Pq, 0, cap};
+        hipLaunchKernelGGL(ll_embed_kernel, dim3(B * Pq), dim3(256), 0, st, (const float*)L->embed, (const int64_t*)s.rseq[1], rows, 0, V, H, w.x);
+        LL_HIP(hipGetLastError());
+        if (int r = ll_layers(L, w, B * Pq, rows, Pq, st)) return r;
+        if (B > 1) {
+            const long long elems = (long long)c.kv_heads * Pq * c.head_dim;
+            for (int i = 0; i < c.layers; ++i)
+                hipLaunchKernelGGL(ll_beam_spread_kernel, dim3((unsigned)((elems + 255) / 256), 2), dim3(256), 0, st, w.kc[i], w.vc[i], B, K, c.kv_heads, cap,
+                                   c.head_dim, Pq);
+            LL_HIP(hipGetLastError());
+        }
+    }
+    hipLaunchKernelGGL(ll_beam_init_kernel, dim3(R), dim3(256), 0, st, input_ids, P, plen, V, c.pad, cap, K, s.rseq[0], s.rseq[1], s.fseq[0], s.fseq[1], s.rscore,
+                       s.fscore, s.ffin, s.flen, s.unsat, s.ended);
+    LL_HIP(hipGetLastError());
+    const int n_steps = max_length - Pmin;      // the shortest row's candidates all hit max_length at step n_steps - 1
+    std::vector<int> host_flags(n_steps, 0);
+    int checked = 0, last = 0;
+    for (int step = 0; step < n_steps; ++step) {
+        const int cur = step & 1, nxt = cur ^ 1;
+        last = step;
+        const LlRows rows{s.plen_rows, 0, step, cap};
+        hipLaunchKernelGGL(ll_embed_kernel, dim3(R), dim3(256), 0, st, (const float*)L->embed, (const int64_t*)s.rseq[cur], rows, 0, V, H, w.x);
+        LL_HIP(hipGetLastError());
+        const int Lk_max = (Pmax + step < max_length) ? Pmax + step : max_length;
+        const LlBeamAttn ba{s.tab[cur], s.ended, cap, K};
+        if (int r = ll_layers(L, w, R, rows, Lk_max, st, &ba)) return r;
+        // rows of width vocab, as lds_llama_score forms them: the low columns from their own matrix, the others by the decode's launch
+        if (lo > 0) LL_HIP(ll_linear<LL_PLAIN>(w.x, H, L->nw_final, c.eps, L->head_lo, nullptr, lo, nullptr, w.logits, V, R, st));
+        LL_HIP(ll_linear<LL_PLAIN>(w.x, H, L->nw_final, c.eps, L->head, nullptr, V - lo, nullptr, w.logits + lo, V, R, st));
+        const LmBeamState bs{s.rseq[cur], s.rseq[nxt], s.rscore, s.rscore, s.tab[cur], s.tab[nxt], s.fseq[cur], s.fseq[nxt], s.fscore, s.fscore, s.ffin, s.ffin,
+                             s.flen, s.flen, s.unsat, s.unsat, nullptr, nullptr, s.flags + step};
+        const LmBeamRows rw{plen, lo, s.ended, s.ended, cap};
+        LL_HIP(lm_launch_beam_rows(B, K, V, w.logits, step, cap, max_length, c.eos, o.repetition_penalty, o.no_repeat_ngram_size, o.early_stopping, bs, rw, st));
+        if ((step + 1) % poll == 0 || step + 1 == n_steps) {      // the poll: bit 16 = some item's own loop still runs
+            LL_HIP(hipMemcpyAsync(host_flags.data() + checked, s.flags + checked, sizeof(int) * (step + 1 - checked), hipMemcpyDeviceToHost, st));
+            LL_HIP(hipStreamSynchronize(st));
+            bool done = false;
+            for (int q = checked; q <= step && !done; ++q) done = !(host_flags[q] & 16);
+            checked = step + 1;
+            if (done) break;
+        }
+    }
+    // every item is frozen in both buffers from the step after its end on; the last step run wrote buffer (last + 1) & 1
+    hipLaunchKernelGGL(ll_beam_finish_kernel, dim3(B), dim3(256), 0, st, (const int64_t*)s.fseq[(last + 1) & 1], (const int*)s.flen, plen, K, cap, c.pad, tokens, s.rowlen);
+    LL_HIP(hipGetLastError());
+    std::vector<int> len(B, 0);
+    LL_HIP(hipMemcpyAsync(len.data(), s.rowlen, sizeof(int) * B, hipMemcpyDeviceToHost, st));
+    LL_HIP(hipStreamSynchronize(st));
+    int n_tokens = 0;
+    for (int b = 0; b < B; ++b) n_tokens = len[b] > n_tokens ? len[b] : n_tokens;
+    *n_tokens_host = n_tokens;
+    return LDS_OK;
+}
+}  // namespace
+
+extern "C" int lds_llama_generate_beam(lds_llama* L, const int64_t* input_ids, const int32_t* in_len, int B, int P, int max_length, const lds_lm_decode_opts* opts,
+                                       int64_t* tokens, int* n_tokens_host, void* ws, size_t ws_bytes, void* stream) {
+    return ll_generate_beam(L, input_ids, in_len, B, P, max_length, opts, tokens, n_tokens_host, ws, ws_bytes, stream, kLlBeamPoll);
+}
+
+// Test entries (include/lds_test.h).  lds_test_llama_generate_beam_poll: lds_llama_generate_beam with a poll interval of the caller's.
+// lds_test_llama_beam_step: ONE step of the per-row beam step (lm_beam_step_kernel<NW, true>) on logits [B * K][V] and the
+// given state; item b is at cur_len = prompt_len[b] + step.  lds_test_llama_beam_attn: ONE attention call over given q and caches.
+extern "C" int lds_test_llama_generate_beam_poll(lds_llama* L, const int64_t* input_ids, const int32_t* in_len, int B, int P, int max_length,
+                                                 const lds_lm_decode_opts* opts, int64_t* tokens, int* n_tokens_host, void* ws, size_t ws_bytes, void* stream, int poll) {
+    if (poll < 1) return ll_fail(LDS_EINVAL, "poll interval %d (>= 1)", poll);
+    return ll_generate_beam(L, input_ids, in_len, B, P, max_length, opts, tokens, n_tokens_host, ws, ws_bytes, stream, poll);
+}
+extern "C" int lds_test_llama_beam_step(const float* logits, int B, int K, int V, int step, int max_length, int eos, float repetition_penalty,
+                                        int no_repeat_ngram_size, int early_stopping, int first_free_id, const int32_t* prompt_len, const int32_t* ended,
+                                        const int64_t* run_seq, const float* run_score, const int64_t* fin_seq, const float* fin_score, const int32_t* fin_flag,
+                                        const int32_t* fin_len, const int32_t* unsat, int64_t* run_seq_out, float* run_score_out, int32_t* parent_out,
+                                        int64_t* fin_seq_out, float* fin_score_out, int32_t* fin_flag_out, int32_t* fin_len_out, int32_t* unsat_out,
+                                        int32_t* ended_out, int32_t* flag_out, void* stream) {
+    if (!logits || !prompt_len || !ended || !run_seq || !run_score || !fin_seq || !fin_score || !fin_flag || !fin_len || !unsat || !run_seq_out || !run_score_out ||
+        !parent_out || !fin_seq_out || !fin_score_out || !fin_flag_out || !fin_len_out || !unsat_out || !ended_out || !flag_out)
+        return ll_fail(LDS_EINVAL, "null argument");
+    if (B <= 0 || B > kLlMaxBeamRows || K < 1 || K > kMaxBeams || V > kMaxBeamVocab || first_free_id < 0 || V - first_free_id < 2 * K || step < 0 ||
+        no_repeat_ngram_size < 0 || early_stopping < 0 || early_stopping > 2)
+        return ll_fail(LDS_EINVAL, "bad argument");
+    for (int b = 0; b < B; ++b)      // a running item writes slot prompt_len[b] + step
+        if (prompt_len[b] < 1 || (!ended[b] && prompt_len[b] + step >= max_length)) return ll_fail(LDS_EINVAL, "prompt_len[%d] + step outside the sequences", b);
+    hipStream_t st = (hipStream_t)stream;
+    int* dev = nullptr;      // prompt_len [B] | ended [B]
+    if (hipMalloc((void**)&dev, sizeof(int) * 2 * B) != hipSuccess) return ll_fail(LDS_ENOMEM, "hipMalloc");
+    int rc = LDS_OK;
+    const LmBeamState bs{run_seq, run_seq_out, run_score, run_score_out, nullptr, nullptr, fin_seq, fin_seq_out, fin_score, fin_score_out, fin_flag, fin_flag_out,
+                         fin_len, fin_len_out, unsat, unsat_out, parent_out, nullptr, flag_out};
+    const LmBeamRows rw{dev, first_free_id, dev + B, ended_out, max_length};
+    if (hipMemcpyAsync(dev, prompt_len, sizeof(int) * B, hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipMemcpyAsync(dev + B, ended, sizeof(int) * B, hipMemcpyHostToDevice, st) != hipSuccess || hipMemsetAsync(flag_out, 0, sizeof(int32_t), st) != hipSuccess ||
+        lm_launch_beam_rows(B, K, V, logits, step, max_length, max_length, eos, repetition_penalty, no_repeat_ngram_size, early_stopping, bs, rw, st) != hipSuccess)
+        rc = ll_fail(LDS_EHIP, "launch");
+    if (hipStreamSynchronize(st) != hipSuccess) rc = ll_fail(LDS_EHIP, "sync");
+    (void)hipFree(dev);
+    return rc;
+}
+extern "C" int lds_test_llama_beam_attn(const float* q, const float* kc, const float* vc, const int32_t* tab, const int32_t* prompt_len, int R, int K, int heads,
+                                        int kv_heads, int d, int cap, int tcap, int step, float* out, void* stream) {
+    if (!q || !kc || !vc || !prompt_len || !out) return ll_fail(LDS_EINVAL, "null argument");
+    if (R < 1 || R > 4096 || K < 1 || K > kMaxBeams || R % K || heads < 1 || kv_heads < 1 || heads % kv_heads || d < 16 || d > kLlMaxHeadDim || d % 16 || cap < 1 ||
+        cap > kLlMaxBeamLength || step < 0 || (tab && tcap < step) || (!tab && K != 1))
+        return ll_fail(LDS_EINVAL, "bad argument");
+    int pos_max = 0;
+    for (int i = 0; i < R / K; ++i) {
+        const int pos = prompt_len[i] - 1 + step;
+        if (prompt_len[i] < 1 || pos >= cap) return ll_fail(LDS_EINVAL, "prompt_len[%d] - 1 + step outside the cache", i);
+        pos_max = pos > pos_max ? pos : pos_max;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    int* dev = nullptr;      // the lengths per row
+    if (hipMalloc((void**)&dev, sizeof(int) * R) != hipSuccess) return ll_fail(LDS_ENOMEM, "hipMalloc");
+    std::vector<int> plr(R);
+    for (int r = 0; r < R; ++r) plr[r] = prompt_len[r / K];
+    int rc = LDS_OK;
+    const int Lkp = (pos_max + 1 + 63) & ~63;
+    const size_t lds = (size_t)(kLlMaxHeadDim + Lkp + 4 * (2 + kLlMaxHeadDim)) * sizeof(float);
+    const LlRows rows{dev, 0, step, cap};
+    if (hipMemcpyAsync(dev, plr.data(), sizeof(int) * R, hipMemcpyHostToDevice, st) != hipSuccess) rc = ll_fail(LDS_EHIP, "copy");
+    if (rc == LDS_OK) {
+        if (tab)
+            hipLaunchKernelGGL(ll_attn_beam_kernel, dim3((unsigned)(R * heads)), dim3(256), lds + (size_t)Lkp * sizeof(int), st, q, kc, vc, rows, heads, kv_heads, d, Lkp,
+                               out, LlBeamAttn{tab, nullptr, tcap, K});
+        else      // the plain kernel: K is 1, every row has its own prompt length and cache row
+            hipLaunchKernelGGL(ll_attn_kernel, dim3((unsigned)(R * heads)), dim3(256), lds, st, q, kc, vc, rows, heads, kv_heads, d, Lkp, out);
+        if (hipGetLastError() != hipSuccess) rc = ll_fail(LDS_EHIP, "launch");
+    }
+    if (hipStreamSynchronize(st) != hipSuccess) rc = ll_fail(LDS_EHIP, "sync");
+    (void)hipFree(dev);
+    return rc;
 }

@@ -853,35 +853,54 @@ __global__ void __launch_bounds__(256) lm_prompt_init_kernel(const int64_t* __re
 //      double-buffered (_in -> _out);
 //      per-row scores and flags are read before they are rewritten, in place is allowed.  prev_flag (null at step 0): the previous step's
 //      bits; when they say the search has ended the step changes nothing.  flag_out gets (OR over the batch) 1 = some item may still
-//      improve, 2 = some item has an unfinished hypothesis slot, 4 = some candidate did not hit the stopping criteria, 8 = ended before. ----
-constexpr int kMaxBeams = 8, kMaxBeamVocab = 64 * 68;
-struct LmBeamState {
-    const int64_t* rseq_in; int64_t* rseq_out;      // running sequences [B * K][cap]
-    const float* rscore_in; float* rscore_out;      // running scores [B * K]
-    const int* tab_in; int* tab_out;                // [B * K][cap]: cache row of key p of each running beam (null: not tracked)
-    const int64_t* fseq_in; int64_t* fseq_out;      // finished hypotheses [B * K][cap]
-    const float* fscore_in; float* fscore_out;      // [B * K]
-    const int* ffin_in; int* ffin_out;              // is_sent_finished [B * K]
-    const int* flen_in; int* flen_out;              // generated tokens of each hypothesis (BOS not counted) [B * K]
-    const int* unsat_in; int* unsat_out;            // is_early_stop_heuristic_unsatisfied [B]
-    int* parent;                                    // [B * K] parent beam of each new running beam, or null
-    const int* prev_flag; int* flag_out;
-};
+//      improve, 2 = some item has an unfinished hypothesis slot, 4 = some candidate did not hit the stopping criteria, 8 = ended before.
+//      ROWS (lm_beam_step_kernel<NW, true>, the Llama's decode: LmBeamRows in lm_common.h): every item continues a prompt of its own length plen[b], so
+//      cur_len = plen[b] + step, the finished score divides by cur_len + 1 - plen[b] and the heuristic by that or by max_length - plen[b]; the
+//      ids below first_free get -inf after the n-gram ban (HF's bad-word ban); the table holds generated positions only (entry p - plen[b]);
+//      an item whose own loop has ended (ended_in 1) copies its state through ONCE, after which both buffers hold it (ended 2: the step does
+//      nothing for it), and leaves the flag bits alone; flag_out gets 16 = some item still runs after this step.  No input row is written: the next step's embedding reads the token from the running sequence. ----
 static __device__ __forceinline__ bool lm_beam_running(int f, int early_stopping) {      // _beam_search_has_unfinished_sequences over the batch
     return !(f & 8) && (f & 1) && (early_stopping != 1 || (f & 2)) && (f & 4);
 }
-template <int NW>
+// (The RoFormer's instantiation takes an empty struct last, where the per-row form takes LmBeamRows: its arguments lie where they lay before
+// the per-row form existed, and the compiler gives it the code it had then.)
+struct LmNoRows { static constexpr const int32_t* plen = nullptr; static constexpr int first_free = 0, tcap = 0; };
+template <int NW, bool ROWS>
 __global__ void __launch_bounds__(256) lm_beam_step_kernel(const float* __restrict__ logits, int V, int K, int step, int cap, int max_length, int eos,
                                                            float rep_pen, int ngram, int early_stopping, const LmBeamState st,
                                                            const float* __restrict__ word, const float* __restrict__ type, const float* __restrict__ eg,
-                                                           const float* __restrict__ eb, float eps, int H, float* __restrict__ xnext) {
+                                                           const float* __restrict__ eb, float eps, int H, float* __restrict__ xnext,
+                                                           const std::conditional_t<ROWS, LmBeamRows, LmNoRows> rw) {
     __shared__ unsigned pen_bits[4][256], ban_bits[4][256];
     __shared__ float cv[kMaxBeams][2 * kMaxBeams], topv[2 * kMaxBeams], sel_sc[kMaxBeams], nf_sc[kMaxBeams], f_sc[kMaxBeams];
     __shared__ int ci[kMaxBeams][2 * kMaxBeams], topb[2 * kMaxBeams], topt[2 * kMaxBeams], sel_j[kMaxBeams], nf_m[kMaxBeams], nf_fin[kMaxBeams], nf_len[kMaxBeams];
     __shared__ int f_fin[kMaxBeams], f_len[kMaxBeams], unsat_sh;
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int cur_len = step + 1, K2 = 2 * K, base = b * K;
-    if (st.prev_flag && !lm_beam_running(*st.prev_flag, early_stopping)) {
+    const int K2 = 2 * K, base = b * K;
+    const int pl = ROWS ? rw.plen[b] : 1, cur_len = ROWS ? pl + step : step + 1;
+    const int gen = ROWS ? cur_len + 1 - pl : cur_len;      // generated tokens of a hypothesis that ends at this step
+    const int tp0 = ROWS ? pl : 0, tcap = ROWS ? rw.tcap : cap;      // the position of the table's entry 0, and its row stride
+    if constexpr (ROWS) {
+        const int was_ended = rw.ended_in[b];
+        if (was_ended > 1) return;      // (uniform over the workgroup) frozen, and an earlier step has already left both buffers alike
+        if (was_ended) {      // frozen: the state goes through as it is, once (ended 1 -> 2), the flag bits are not touched
+            for (int i = tid; i < K * cap; i += 256) {
+                const long long a = (long long)base * cap + i;
+                st.rseq_out[a] = st.rseq_in[a]; st.fseq_out[a] = st.fseq_in[a];
+            }
+            if (st.tab_out)
+                for (int i = tid; i < K * tcap; i += 256) st.tab_out[(long long)base * tcap + i] = st.tab_in[(long long)base * tcap + i];
+            if (tid < K) {
+                const int row = base + tid;
+                const float rs = st.rscore_in[row], fs = st.fscore_in[row];
+                const int ff = st.ffin_in[row], fl = st.flen_in[row];
+                st.rscore_out[row] = rs; st.fscore_out[row] = fs; st.ffin_out[row] = ff; st.flen_out[row] = fl;
+                if (st.parent) st.parent[row] = tid;
+            }
+            if (tid == 64) { const int u = st.unsat_in[b]; st.unsat_out[b] = u; rw.ended_out[b] = 2; }
+            return;
+        }
+    } else if (st.prev_flag && !lm_beam_running(*st.prev_flag, early_stopping)) {
         if (tid == 0) atomicOr(st.flag_out, 8);
         return;
     }
@@ -925,6 +944,7 @@ __global__ void __launch_bounds__(256) lm_beam_step_kernel(const float* __restri
                 float x = (v[i] - m) - lse;
                 if ((pen_bits[wave][c >> 5] >> (c & 31)) & 1u) x = (x < 0.f) ? x * rep_pen : x / rep_pen;
                 if ((ban_bits[wave][c >> 5] >> (c & 31)) & 1u) x = -INFINITY;
+                if (ROWS && c < rw.first_free) x = -INFINITY;
                 v[i] = (c < V) ? x + rs : -INFINITY;
             }
             for (int j = 0; j < K2; ++j) {      // the row's j-th largest score, ties to the lower token id
@@ -972,7 +992,7 @@ __global__ void __launch_bounds__(256) lm_beam_step_kernel(const float* __restri
             taken |= 1u << bj;
             sel_j[k] = bj; sel_sc[k] = trl[bj];
         }
-        // _update_finished_beams (length_penalty 1: divide by the generated length cur_len + 1 - 1)
+        // _update_finished_beams (length_penalty 1: divide by the generated length cur_len + 1 - decoder_prompt_len)
         bool all_fin = true;
         for (int k = 0; k < K; ++k) all_fin = all_fin && f_fin[k] != 0;
         const int unsat = unsat_sh;
@@ -980,7 +1000,7 @@ __global__ void __launch_bounds__(256) lm_beam_step_kernel(const float* __restri
         for (int k = 0; k < K; ++k) ms[k] = f_sc[k];
         for (int j = 0; j < K2; ++j) {
             const bool did = hit[j] && j < K;
-            float f = topv[j] / (float)cur_len;
+            float f = topv[j] / (float)gen;
             f = f + ((all_fin && early_stopping == 1) ? -1.0e9f : -0.0f);
             f = f + (unsat ? -0.0f : -1.0e9f);
             f = f + (did ? -0.0f : -1.0e9f);
@@ -996,18 +1016,24 @@ __global__ void __launch_bounds__(256) lm_beam_step_kernel(const float* __restri
             mtaken |= 1u << bm;
             nf_m[k] = bm; nf_sc[k] = ms[bm];
             nf_fin[k] = (bm < K) ? f_fin[bm] : (hit[bm - K] && bm - K < K) ? 1 : 0;
-            nf_len[k] = (bm < K) ? f_len[bm] : cur_len;
+            nf_len[k] = (bm < K) ? f_len[bm] : gen;
             worst = fminf(worst, ms[bm]);
             nall_fin = nall_fin && nf_fin[k];
         }
         // _check_early_stop_heuristic at cur_len + 1 (early_stopping "never" with a positive length penalty: the best length is max_length)
-        const int hyp = (early_stopping == 2) ? max_length - 1 : cur_len;
+        const int hyp = (early_stopping == 2) ? max_length - pl : gen;
         const float best = sel_sc[0] / (float)hyp;
         bool improve = false;
         for (int k = 0; k < K; ++k) improve = improve || best > (nf_fin[k] ? worst : -1.0e9f);
         const int nunsat = (unsat && improve) ? 1 : 0;
         st.unsat_out[b] = nunsat;
-        atomicOr(st.flag_out, (nunsat ? 1 : 0) | (nall_fin ? 0 : 2) | (all_hit ? 0 : 4));
+        int bits = (nunsat ? 1 : 0) | (nall_fin ? 0 : 2) | (all_hit ? 0 : 4);
+        if constexpr (ROWS) {      // the item's own loop condition: the batch's OR would let a longer row keep a finished one running
+            const bool run = nunsat && (early_stopping != 1 || !nall_fin) && !all_hit;
+            rw.ended_out[b] = run ? 0 : 1;
+            bits |= run ? 16 : 0;
+        }
+        atomicOr(st.flag_out, bits);
     }
     __syncthreads();
     // the new running sequences, finished hypotheses and ancestry tables: every (beam, position) pair at once
@@ -1018,7 +1044,7 @@ __global__ void __launch_bounds__(256) lm_beam_step_kernel(const float* __restri
         const int64_t* fi = (m < K) ? st.fseq_in + (long long)(base + m) * cap : st.rseq_in + (long long)(base + topb[m - K]) * cap;
         st.rseq_out[(long long)row * cap + p] = (p < cur_len) ? st.rseq_in[(long long)par * cap + p] : (int64_t)topt[j];
         st.fseq_out[(long long)row * cap + p] = (m >= K && p == cur_len) ? (int64_t)topt[m - K] : fi[p];
-        if (st.tab_out && p < cur_len) st.tab_out[(long long)row * cap + p] = (p < step) ? st.tab_in[(long long)par * cap + p] : par;
+        if (st.tab_out && (!ROWS || p >= tp0) && p < cur_len) st.tab_out[(long long)row * tcap + p - tp0] = (p < cur_len - 1) ? st.tab_in[(long long)par * tcap + p - tp0] : par;
     }
     if (tid < K) {
         const int row = base + tid;
@@ -1028,7 +1054,7 @@ __global__ void __launch_bounds__(256) lm_beam_step_kernel(const float* __restri
     }
     // the next step's input rows, LayerNorm(word[token] + type[0]) (lm_embed_kernel's rows): wave w takes beams w, w + 4 with
     // fixed-order wave sums (H <= 256, lds_lm_create allows 256)
-    if (xnext) {
+    if (!ROWS && xnext) {
         for (int k = wave; k < K; k += 4) {
             long long t = topt[sel_j[k]];
             t = (t < 0) ? 0 : (t >= V ? V - 1 : t);
@@ -1412,14 +1438,25 @@ hipError_t lm_launch_beam_step(int B, int K, int V, const float* lg, int step, i
                                const LmBeamState& bs, const float* word, const float* type, const float* eg, const float* eb, float eps, int H, float* xnext,
                                hipStream_t st) {
     if (V <= 64 * 36)
-        hipLaunchKernelGGL(lm_beam_step_kernel<36>, dim3(B), dim3(256), 0, st, lg, V, K, step, cap, max_length, eos, pen, ngram, es, bs, word, type, eg, eb, eps, H, xnext);
+        hipLaunchKernelGGL((lm_beam_step_kernel<36, false>), dim3(B), dim3(256), 0, st, lg, V, K, step, cap, max_length, eos, pen, ngram, es, bs, word, type, eg, eb, eps, H, xnext, LmNoRows{});
     else if (V <= kMaxBeamVocab)      // (4096 codes + 3 special ids; a row of 128 values per lane would spill)
-        hipLaunchKernelGGL(lm_beam_step_kernel<68>, dim3(B), dim3(256), 0, st, lg, V, K, step, cap, max_length, eos, pen, ngram, es, bs, word, type, eg, eb, eps, H, xnext);
+        hipLaunchKernelGGL((lm_beam_step_kernel<68, false>), dim3(B), dim3(256), 0, st, lg, V, K, step, cap, max_length, eos, pen, ngram, es, bs, word, type, eg, eb, eps, H, xnext, LmNoRows{});
     else
         return hipErrorInvalidValue;
     return hipGetLastError();
 }
 }  // namespace
+
+hipError_t lds::lm_launch_beam_rows(int B, int K, int V, const float* lg, int step, int cap, int max_length, int eos, float pen, int ngram, int es,
+                                    const LmBeamState& bs, const LmBeamRows& rw, hipStream_t st) {
+    const float* nf = nullptr;      // (no input row is written)
+    if (V <= 64 * 36)
+        hipLaunchKernelGGL((lm_beam_step_kernel<36, true>), dim3(B), dim3(256), 0, st, lg, V, K, step, cap, max_length, eos, pen, ngram, es, bs, nf, nf, nf, nf, 0.f, 0, (float*)nullptr, rw);
+    else if (V <= kMaxBeamVocab)
+        hipLaunchKernelGGL((lm_beam_step_kernel<68, true>), dim3(B), dim3(256), 0, st, lg, V, K, step, cap, max_length, eos, pen, ngram, es, bs, nf, nf, nf, nf, 0.f, 0, (float*)nullptr, rw);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
 
 // the option checks that need no model (they come before every other check of lds_lm_generate_opts; no device call)
 int lds::lm_check_opts(const lds_lm_decode_opts& o, const float* logits_out) {

@@ -73,6 +73,29 @@ hipError_t lm_launch_choice_rows(const lds_lm_decode_opts& o, int B, int V, cons
 hipError_t lm_launch_score_rows(const float* logits, long long n0, int rows, int V, int T, const int64_t* labels, const int32_t* len, float* lp, int32_t* rank,
                                 hipStream_t st);
 hipError_t lm_launch_score_loss(const float* lp, const int32_t* rank, int B, int T1, double* psum, int32_t* pcnt, float* loss, int32_t* n_counted, hipStream_t st);
+// ---- lm.hip's beam-search step (lm_beam_step_kernel: one step of HF's _beam_search per batch item), its state, and its per-row form for a decode
+//      whose items continue prompts of their own lengths (the Llama's: lm_beam_step_kernel<NW, true>) ----
+constexpr int kMaxBeams = 8, kMaxBeamVocab = 64 * 68;
+struct LmBeamState {
+    const int64_t* rseq_in; int64_t* rseq_out;      // running sequences [B * K][cap]
+    const float* rscore_in; float* rscore_out;      // running scores [B * K]
+    const int* tab_in; int* tab_out;                // [B * K][cap]: cache row of key p of each running beam (null: not tracked)
+    const int64_t* fseq_in; int64_t* fseq_out;      // finished hypotheses [B * K][cap]
+    const float* fscore_in; float* fscore_out;      // [B * K]
+    const int* ffin_in; int* ffin_out;              // is_sent_finished [B * K]
+    const int* flen_in; int* flen_out;              // generated tokens of each hypothesis (the prompt / BOS not counted) [B * K]
+    const int* unsat_in; int* unsat_out;            // is_early_stop_heuristic_unsatisfied [B]
+    int* parent;                                    // [B * K] parent beam of each new running beam, or null
+    const int* prev_flag; int* flag_out;
+};
+// The per-row form.  plen [B]: every item's decoder_prompt_len; the item is at cur_len = plen[b] + step.  first_free: ids below it are banned
+// (-inf) after the n-gram ban.  ended_in / ended_out [B] (may alias): 1 once the item's own loop condition has turned false; such an item's
+// state goes through unchanged and it adds nothing to the flag bits, whose bit 16 says that some item still runs after the step.  The step that
+// finds 1 copies the state into the other buffers and writes 2; one that finds 2 touches nothing of the item's (both buffers already agree).  The
+// ancestry table is [B * K][tcap] over generated positions only: entry e is the cache row of the key at position plen[b] + e.
+struct LmBeamRows { const int32_t* plen; int first_free; const int* ended_in; int* ended_out; int tcap; };
+hipError_t lm_launch_beam_rows(int B, int K, int V, const float* lg, int step, int cap, int max_length, int eos, float pen, int ngram, int es,
+                               const LmBeamState& bs, const LmBeamRows& rw, hipStream_t st);
 // the option checks that need no model (no device call); LDS_OK or LDS_EINVAL with a message
 int lm_check_opts(const lds_lm_decode_opts& o, const float* logits_out);
 constexpr int kLmMaxTopK = 64;            // survivors of the top-k filter

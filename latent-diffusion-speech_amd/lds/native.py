@@ -140,6 +140,8 @@ lds_llama_create                 i:pipppp
 lds_llama_destroy                v:p
 lds_llama_workspace_bytes        i:piiip
 lds_llama_generate               i:pppiiippppppzp
+lds_llama_beam_workspace_bytes   i:piiiip
+lds_llama_generate_beam          i:pppiiippppzp
 lds_llama_score_workspace_bytes  i:piip
 lds_llama_score                  i:ppppiippppppzp
 lds_kmeans_workspace_bytes       i:qiip
@@ -208,6 +210,9 @@ lds_test_lm_sample               i:piiiifffppipp
 lds_test_conv_down               i:pppiiiiiifippzp
 lds_test_conv_down_ragged        i:pppiiiiiifppippzp
 lds_test_lm_beam_step            i:piiiiiifiippppppppppppppppp
+lds_test_llama_beam_step         i:piiiiiifiiipppppppppppppppppppp
+lds_test_llama_beam_attn         i:pppppiiiiiiiipp
+lds_test_llama_generate_beam_poll i:pppiiippppzpi
 lds_test_dconv_pair              i:pppppppiiiiiipiiipppzp
 lds_test_dconv_ex                i:pppipzp
 lds_test_dma_magic_div           i:uup
@@ -1173,6 +1178,21 @@ class Llama(_Handle):
         stop = (toks == self.cfg["eos"]) & (torch.arange(n.value, device=toks.device)[None] >= plen[:, None])
         end = torch.where(stop.any(1), stop.int().argmax(1) + 1, torch.full_like(plen, n.value))
         return toks, logits[: int((end - plen).max())]
+
+    def generate_beam(self, input_ids, in_len, max_length, num_beams, repetition_penalty=1.0, no_repeat_ngram_size=0, early_stopping=True):
+        """Greedy beam search (lds_llama_generate_beam): input_ids / in_len / max_length as `generate`, one row per item; early_stopping True,
+        False or "never".  Returns tokens [B,n]: every item's prompt and best finished hypothesis (EOS kept, PAD after it), n the longest row."""
+        import torch
+        B, P = input_ids.shape
+        o = LMDecodeOpts(0, 0, 1.0, 1.0, float(repetition_penalty), int(no_repeat_ngram_size), int(num_beams), EARLY_STOPPING.get(early_stopping, -1))
+        plen = None if in_len is None else (C.c_int32 * B)(*[int(v) for v in in_len])
+        ws = self._workspace("lds_llama_beam_workspace_bytes", input_ids.device, B, P, int(max_length), int(num_beams))
+        tokens = torch.empty(B, max_length, dtype=torch.int64, device=input_ids.device)
+        n = C.c_int()
+        ids = input_ids.contiguous()
+        check(lib().lds_llama_generate_beam(self.h, _dev(ids, torch.int64), C.cast(plen, C.c_void_p) if plen is not None else None, B, P, int(max_length),
+                                            C.byref(o), _dev(tokens), C.byref(n), _dev(ws), ws.numel(), _stream()))
+        return tokens[:, : n.value].contiguous()
 
     def score(self, input_ids, ids_len=None, labels=None, return_logits=False):
         """Teacher-forced scoring (lds_llama_score): input_ids / labels int64 [B,S] on the device (labels None = input_ids), ids_len int32 [B]

@@ -319,8 +319,12 @@ class Llama(ParamTree):
                  repetition_penalty=1.0, num_beams=1, no_repeat_ngram_size=0, early_stopping=True, spk_id=None, end_gate_threshold=None,
                  return_logits=False, uniforms=None, semantic_prompt=None, prompt_attention_mask=None, **kwargs):
         """The reference's `generate` (llama.py:121-184): phone [1, L] -> the generated semantic ids [1, n] (shift subtracted, EOS = K + 1 kept);
-        max_length is the total length, the L + 3 prompt ids included.  tone, spk_id, use_cache and early_stopping (forced off with one beam,
-        llama.py:154) have no effect, as there.
+        max_length is the total length, the L + 3 prompt ids included.  tone, spk_id and use_cache have no effect, as there; early_stopping is forced off with one
+        beam (llama.py:154).
+        num_beams 2 .. 8 with do_sample=False: HF's greedy beam search (length_penalty 1) with the caller's early_stopping (True, False or "never"):
+        log_softmax over the whole vocabulary, then the repetition penalty, the n-gram ban and the ban of the ids below 108; a row's
+        decoder_prompt_len is its own stream length, semantic prompt included.  Rows of a batch equal the rows alone.  Not built: beam sampling
+        (do_sample=True, the default), return_logits with beams.
         Extensions: phone [B, L] with a right-padded attention_mask [B, L] (ones then zeros; the reference can only do B = 1 and hands its mask to
         nothing that reads it): row b is [108, phones_b, 109, 108 + K] with its own length and decodes exactly as it would alone; returned rows
         are cropped to the longest and padded with K + 2.  return_logits: also logits [steps, B, K + 3], logits[s][b] = HF's raw logits (before
@@ -336,11 +340,17 @@ class Llama(ParamTree):
             # id 0 and sampling makes torch.multinomial raise on NaN probabilities -- there is no coherent behaviour to restate
             raise NotImplementedError("the end gate is not built: the reference's EndGateLogitsProcessor sets the whole score row to +inf, "
                                       "after which greedy picks token 0 and sampling raises")
-        if isinstance(num_beams, bool) or not isinstance(num_beams, (int, np.integer)) or num_beams < 1:
-            raise ValueError(f"num_beams must be an integer >= 1, got {num_beams!r}")
+        if isinstance(num_beams, bool) or not isinstance(num_beams, (int, np.integer)) or not 1 <= num_beams <= 8:
+            raise ValueError(f"num_beams must be an integer in 1 .. 8, got {num_beams!r}")
         if num_beams > 1:
-            # HF normalises with log_softmax over the whole vocabulary before the processors: the head would have to give the banned columns' share
-            raise NotImplementedError("beam search (num_beams > 1) is not built for Llama; Roformer.generate has greedy beam search")
+            if do_sample:
+                raise NotImplementedError("beam sampling (num_beams > 1 with do_sample=True, the default) is not built: greedy beam search takes do_sample=False")
+            if return_logits:
+                raise NotImplementedError("return_logits is not available with beam search (num_beams > 1)")
+            if not (early_stopping is True or early_stopping is False or early_stopping == "never"):
+                raise ValueError(f"early_stopping must be True, False or 'never', got {early_stopping!r}")
+            if self.cfg["vocab"] > 4352:
+                raise NotImplementedError(f"beam search is built for vocabularies of at most 4352 ids (K <= 4241), got {self.cfg['vocab']}")
         if isinstance(no_repeat_ngram_size, bool) or not isinstance(no_repeat_ngram_size, (int, np.integer)) or no_repeat_ngram_size < 0:
             raise ValueError(f"no_repeat_ngram_size must be an integer >= 0, got {no_repeat_ngram_size!r}")
         top_k = 0 if top_k is None else int(top_k)
@@ -358,6 +368,10 @@ class Llama(ParamTree):
         B = ids.shape[0]
         if B > 64:
             raise ValueError(f"a Llama decode takes at most 64 rows, got {B}")
+        if num_beams > 1 and B * num_beams > 256:
+            raise ValueError(f"a Llama beam decode takes at most 256 beam rows, got B * num_beams = {B * num_beams}")
+        if num_beams > 1 and max_length > 7488:
+            raise ValueError(f"a Llama beam decode takes max_length <= 7488, got {max_length}")
         for b, n in enumerate(lens):
             if n >= max_length:      # HF raises ValueError as well: max_length counts the prompt
                 raise ValueError(f"row {b}: the prompt has {n} ids (phones + 3" + (f" + {n - first[b]} prompt tokens" if n > first[b] else "") +
@@ -376,8 +390,11 @@ class Llama(ParamTree):
                 raise ValueError(f"uniforms must be [steps, B = {B}] with one row per generated position, got {tuple(uniforms.shape)}")
             if uniforms.shape[0] < max_length - 1:      # the library's layout is [max_length - 1, B]; the rows past the last step are never read
                 uniforms = torch.cat([uniforms, uniforms.new_zeros(max_length - 1 - uniforms.shape[0], B)])
-        toks, logits = self.native().generate(ids, lens, max_length, do_sample, top_k, top_p, temperature, repetition_penalty, uniforms, return_logits,
-                                              no_repeat_ngram_size=int(no_repeat_ngram_size))
+        if num_beams > 1:      # every item's prompt and best finished hypothesis: EOS kept (a hypothesis without one ends at max_length), pad after it
+            toks, logits = self.native().generate_beam(ids, lens, max_length, int(num_beams), repetition_penalty, int(no_repeat_ngram_size), early_stopping), None
+        else:
+            toks, logits = self.native().generate(ids, lens, max_length, do_sample, top_k, top_p, temperature, repetition_penalty, uniforms, return_logits,
+                                                  no_repeat_ngram_size=int(no_repeat_ngram_size))
         # llama.py:182 for every row: the ids behind the row's own prompt, cropped to the longest row, padded with the pad id; then the shift
         host = toks.cpu()
         ends = []

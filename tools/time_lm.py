@@ -18,6 +18,8 @@
                        further decode step at --batch, event time on the stream, median of --reps; the RoFormer's step time from the same
                        process for scale; and, where transformers imports, HF's LlamaForCausalLM.generate with the same weights on the
                        same device.  --json FILE keeps the rows.
+  --llama --num_beams K  Llama.generate with K beams (early_stopping False, so that the search runs to the full length) next to the greedy decode of
+                       the same B items and of B * K rows -- the rows a beam step runs: us per step at --batch.
   --llama --score      one teacher-forced scoring call (lds_llama_score through lds.native, without and with the logits) over the stream of a
                        greedy decode to S = 67 + N ids for every N of --tokens, next to that decode -- the only other way to visit those
                        positions; event time on the stream, median of --reps, same process.  (--lib: the decode alone, for a build without it.)
@@ -153,13 +155,13 @@ def llama_mode():
     P = L + 3
     hf = None
     try:
-        if a.score or a.prompt:
+        if a.score or a.prompt or a.num_beams > 1:
             raise ImportError      # (those modes compare the library with itself)
         from transformers import LlamaConfig, LlamaForCausalLM
         hf = LlamaForCausalLM(LlamaConfig(vocab_size=m.cfg["vocab"], **conf)).cuda().eval()
         hf.load_state_dict({k[len("llama."):]: v for k, v in m.state_dict().items()}, strict=True)
     except ImportError:
-        if not (a.score or a.prompt):
+        if not (a.score or a.prompt or a.num_beams > 1):
             print("transformers does not import here: no HF timing")
     rows = []
     if a.score or a.prompt:
@@ -219,8 +221,30 @@ def llama_mode():
             h2, htok = event_ms(lambda: hf_gen(1 + new), a.reps)
             row.update(hf_prefill_plus_one_step_ms=h1, hf_decode_ms=h2, hf_us_per_step=(h2 - h1) * 1e3 / new, hf_over_native=h2 / all_ms,
                        same_tokens=bool(htok.shape[1] == P + 1 + new and torch.equal(htok[:, P:] - m.cfg["shift"], tok)))
+        if a.num_beams > 1:      # the beam decode of the same B items, and greedy over as many rows as it has beam rows
+            Kb = a.num_beams
+
+            def beam(n):
+                return m.generate(ph, ph, max_length=P + n, do_sample=False, num_beams=Kb, early_stopping=False)
+            beam(8)
+            b1, _ = event_ms(lambda: beam(1), a.reps)
+            b2, btok = event_ms(lambda: beam(1 + new), a.reps)
+            assert btok.shape == (B, 1 + new), btok.shape      # (no hypothesis finished early: every step ran)
+            row.update(num_beams=Kb, beam_prefill_plus_one_step_ms=b1, beam_decode_ms=b2, beam_us_per_step=(b2 - b1) * 1e3 / new)
+            if B * Kb <= 64:
+                phk = ph.repeat(Kb, 1)
+                m.generate(phk, phk, max_length=P + 8, do_sample=False)
+                g1, _ = event_ms(lambda: m.generate(phk, phk, max_length=P + 1, do_sample=False), a.reps)
+                g2, _ = event_ms(lambda: m.generate(phk, phk, max_length=P + 1 + new, do_sample=False), a.reps)
+                row.update(greedy_rows=B * Kb, greedy_same_rows_us_per_step=(g2 - g1) * 1e3 / new)
         rows.append(row)
         print(row)
+    if a.num_beams > 1:
+        if a.json:
+            import json
+            json.dump({"what": f"Llama.generate with {a.num_beams} beams (early_stopping False, 64 phones, the reference example's width, EOS never wins) next to "
+                               f"greedy over B and over B * num_beams rows; event time on the stream, median of {a.reps}", "rows": rows}, open(a.json, "w"), indent=1)
+        return
     # the RoFormer's step from the same process, for scale (greedy, EOS biased down)
     with torch.no_grad():
         lm.semantic_decoder.cls.predictions.bias[lm.semantic_eos_token_id] -= 1.0e4
