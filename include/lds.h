@@ -315,6 +315,50 @@ int  lds_w2v_features(lds_w2v* h, const float* audio, const int32_t* lengths, fl
 /* out dev [B][T][n_state] = the output of encoder.layer_norm */
 int  lds_w2v_encode(lds_w2v* h, const float* audio, const int32_t* lengths, float* out, void* ws, size_t ws_bytes, int B, int64_t L, void* stream);
 
+/* ---- units encoder: WavLM (transformers' WavLMModel: so-vits-svc's wavlmbase+, kNN-VC's WavLM-Large), audio -> units ----------------
+ * Two flavours of one network, chosen by stable_layer_norm:
+ *   0 (Base / Base+; feat_extract_norm "group", do_stable_layer_norm False): lds_hubert's skeleton -- seven bias-free waveform convolutions, a
+ *     GroupNorm per channel behind conv0, LayerNorm + Linear (conv_dim -> n_state), x + GELU(grouped positional convolution), encoder.layer_norm,
+ *     post-LayerNorm blocks.  WavLM-Base+: {512, 768, 12, 12, 3072, 128, 16, 320, 800, 0, 1500}.
+ *   1 (Large; feat_extract_norm "layer", do_stable_layer_norm True): lds_w2v's skeleton with zero convolution biases -- a LayerNorm + GELU behind
+ *     every convolution, pre-LayerNorm blocks, a final encoder.layer_norm.  WavLM-Large: {512, 1024, 16, 24, 4096, 128, 16, 320, 800, 1, 1500}.
+ * conv_bias is False in both; eps 1e-5.  The self-attention of every block (n_head heads of 64), x its input [T][n_state]:
+ *   p = gru_rel_pos_linear(x viewed as [n_head][T][64]) -> [n_head][T][8]; (a, b) = sigmoid of the sums of p[..., 0:4] and p[..., 4:8];
+ *   gate[h][i] = a (b gru_rel_pos_const[h] - 1) + 2;   score(i, j) = q_i . k_j / 8 + gate[h][i] bias[h][j - i], soft-max over the clip's own keys;
+ *   bias[h][d] = layer 0's rel_attn_embed.weight[bucket(d)][h] for every layer, bucket = WavLMAttention._relative_positions_bucket with
+ *   nb = num_buckets / 2, me = nb / 2: (d > 0) nb + (|d| < me ? |d| : min(me + trunc(log(|d| / me) / log(max_distance / me) (nb - me)), nb - 1)),
+ *   the logarithm branch in float32 as torch runs it.  The bias is kept as a table [n_head][2 n_ctx - 1] built at create; nothing of size
+ *   T x T is stored.
+ * Tensor names are the keys of WavLMModel.state_dict(): feature_extractor.conv_layers.{i}.conv.weight, .{i}.layer_norm.* (i = 0; every i in
+ * the stable flavour), feature_projection.{layer_norm,projection}.*, encoder.pos_conv_embed.conv.{bias,parametrizations.weight.original0,
+ * parametrizations.weight.original1} (weight norm folded at create in double), encoder.layer_norm.*, encoder.layers.{l}.attention.{q,k,v,out}_proj.*,
+ * .attention.gru_rel_pos_linear.*, .attention.gru_rel_pos_const, encoder.layers.0.attention.rel_attn_embed.weight, .layer_norm.*,
+ * .feed_forward.{intermediate_dense,output_dense}.*, .final_layer_norm.*; masked_spec_embed and other names are not read.  LDS_EMISSING names a
+ * missing tensor.
+ * Limits (LDS_EINVAL otherwise): conv_dim and n_state multiples of 64 up to 1024, n_state = 64 n_head, n_ffn a multiple of 64, pos_kernel even
+ * in 2 .. 128, n_state / pos_groups in {16, 32, 48, 64}, 1 <= n_layer <= 64, num_buckets a multiple of 4 in 4 .. 4096,
+ * num_buckets / 4 < max_distance <= 2^20, stable_layer_norm 0 or 1, T <= n_ctx <= 1500, 1 <= B <= 64, 400 <= L <= 2^30.
+ * audio: dev [B][L] fp32 at 16 kHz.  A clip of n samples gives T = the frame rule of lds_hubert with pad 0 (400 samples -> 1 frame, 16,000 -> 49,
+ * 30 s -> 1499).  lengths: host int32 [B] (400 <= lengths[b] <= L) or NULL: clip b is audio[b, :lengths[b]] encoded alone.  normalize (0 or 1):
+ * with 1 every clip becomes (x - mean) / sqrt(var + 1e-7) over its own samples first (what Wav2Vec2FeatureExtractor(do_normalize=True) does in
+ * front of WavLM-Large), statistics in double.
+ * Nothing at or beyond lengths[b] is read; rows at and beyond T_b of a result are zeros.  A clip's result does not depend on the other clips
+ * of the call.  Exact fp32, no floating-point atomics: a repeat gives the same bits.  Nothing synchronises; a bad argument returns before
+ * anything is enqueued; a small workspace gives LDS_ENOMEM naming the size. */
+typedef struct lds_wavlm lds_wavlm;
+typedef struct lds_wavlm_cfg { int conv_dim, n_state, n_head, n_layer, n_ffn, pos_kernel, pos_groups, num_buckets, max_distance, stable_layer_norm, n_ctx; } lds_wavlm_cfg;
+int  lds_wavlm_create(const lds_wavlm_cfg* cfg, int n_tensors, const char* const* names, const float* const* host_ptrs, const int64_t* numel, lds_wavlm** out);
+void lds_wavlm_destroy(lds_wavlm* h);
+/* one size for both calls below, with or without normalize */
+int  lds_wavlm_workspace_bytes(const lds_wavlm* h, int B, int64_t L, size_t* out);
+/* out dev [B][T][conv_dim] frame-major = feature_extractor(audio) transposed (before the projection's LayerNorm) */
+int  lds_wavlm_features(lds_wavlm* h, const float* audio, const int32_t* lengths, float* out, int normalize, void* ws, size_t ws_bytes, int B, int64_t L,
+                        void* stream);
+/* out dev [B][T][n_state] = WavLMModel(audio, output_hidden_states=True).hidden_states[n_layers_run], 0 <= n_layers_run <= n_layer;
+ * n_layers_run == n_layer gives last_hidden_state */
+int  lds_wavlm_encode(lds_wavlm* h, const float* audio, const int32_t* lengths, float* out, int n_layers_run, int normalize, void* ws, size_t ws_bytes,
+                      int B, int64_t L, void* stream);
+
 /* ---- units encoder: w2v-BERT 2.0 (reference tools/tools.py Wav2Vec2Bert: transformers' Wav2Vec2BertModel(**SeamlessM4TFeatureExtractor(audio,
  *      sampling_rate = 16000)).last_hidden_state), audio -> units ------------------------------------------------------------------------
  * Front end (SeamlessM4TFeatureExtractor.__call__ on one clip): the waveform times 2^15; n = 1 + (len - 400) / 160 frames of 400 samples, not

@@ -243,6 +243,17 @@ int lds_test_w2vbert_attention(const float* qkv, const float* E, const int32_t* 
 int lds_test_w2vbert_dwconv(const float* x, const float* w, const float* gamma, const float* beta, float eps, const int32_t* in_rows, const int32_t* out_rows,
                             float* out, int B, int C, int T, int K, void* stream);
 
+/* The WavLM encoder's gated-bias attention alone (csrc/attention_k4p.hip attention_k4p_bias); every pointer but `lengths` is a device
+ * pointer, B <= 64, T <= n_ctx <= 1500.  qkv [B][3C][T] (q, k, v; heads of 64), gate [B][heads][T], toep [heads][2 n_ctx - 1] (the bias of distance
+ * d = key - query at index d + n_ctx - 1) -> out [B][C][T] = softmax(q.k / 8 + gate[i] toep[j - i]) v; lengths (host int32 [B] or NULL): the
+ * clip's queries (zeros beyond) and keys, 1 <= lengths[b] <= T.  q, k, v and gate may hold anything at and beyond lengths[b] (the entry zeroes
+ * the value rows there, as the encoder's q | k | v convolution writes them).  Synchronises.
+ * wavlm_buckets (host only, no device): out host int32 [2 n - 1] = WavLMAttention._relative_positions_bucket of the distances -(n - 1) .. n - 1,
+ * the table lds_wavlm_create builds its bias from. */
+int lds_test_wavlm_attention(const float* qkv, const float* gate, const float* toep, const int32_t* lengths, float* out, int B, int C, int T, int heads,
+                             int n_ctx, void* stream);
+int lds_test_wavlm_buckets(int num_buckets, int max_distance, int n, int32_t* out);
+
 /* csrc/stftmel.hip's framed DFT alone: the frames of audio [B][L] as they are (no padding; F = 1 + (L - n_fft_new) / hop_new rows) times
  * basis [n_fft_new][n_fft_new / 2 + 1][2] -> dft dev double [B][F][n_fft_new / 2 + 1][2], the raw sums before the magnitude (an integer-valued
  * asymmetric basis makes them exact: a swapped row / column of the f64 MFMA's C/D map shows); out dev [B][F][n_mels] as lds_stft_mel.  Synchronises. */

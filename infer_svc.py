@@ -25,9 +25,9 @@ def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("-dm", "--diffusion_model")
     ap.add_argument("-ue", "--units_encoder", help="large-v3_encoder.pt: {'dims', 'model_state_dict'} of the Whisper encoder")
-    ap.add_argument("--encoder", default="whisper_large_v3", choices=("whisper_large_v3", "hubertsoft", "contentvec768l12", "xlsr_53_56k"),
+    ap.add_argument("--encoder", default="whisper_large_v3", choices=("whisper_large_v3", "hubertsoft", "contentvec768l12", "xlsr_53_56k", "wavlmbase+", "wavlmlarge"),
                     help="the units encoder; for a HuBERT encoder -ue names a HubertSoft state dict, for xlsr_53_56k a wav2vec 2.0 state dict of "
-                         "plain tensors (fairseq or transformers naming)")
+                         "plain tensors (fairseq or transformers naming), for a WavLM encoder its state dict in transformers naming")
     ap.add_argument("-i", "--input", help="mono PCM16 .wav, or .npy float [L] (then --sample_rate says its rate)")
     ap.add_argument("-sr", "--sample_rate", type=int, default=44100, help="rate of a .npy input / of the generated recording")
     ap.add_argument("-o", "--output", default="output.wav", help=".wav (PCM16) or .npy")
@@ -54,19 +54,24 @@ def synthetic_svc(dev, width=1280, layers=4, encoder="whisper_large_v3", encoder
     """DiffusionSVC with seeded random-init weights throughout (no checkpoints ship with the reference): the Unit2Mel and
     vocoder of infer_tts.synthetic_pipeline, a Whisper encoder of `width` (large-v3's mel front end and context) with resampling on; or,
     for encoder 'hubertsoft' / 'contentvec768l12', the HuBERT-base stack of `layers` blocks (its own width: 256 / 768); or, for
-    'xlsr_53_56k', the XLSR-53 network of `layers` blocks (1024 wide), or of `encoder_dims` (lds.arch.XLSR_53_DIMS' fields) when given"""
+    'xlsr_53_56k', the XLSR-53 network of `layers` blocks (1024 wide), or of `encoder_dims` (lds.arch.XLSR_53_DIMS' fields) when given; or,
+    for 'wavlmbase+' / 'wavlmlarge', that WavLM of `layers` blocks (768 / 1024 wide), or of `encoder_dims` (lds_wavlm_cfg's fields)"""
     from diffusion.unit2mel import DotDict, Unit2Mel
     from diffusion.vocoder import Vocoder
     from encoder.hifi_vaegan.hifi_vaegan import Hifi_VAEGAN
     from encoder.whisper.model import ModelDimensions
     from lds import arch, init_weights
     from tools.infer_tools import DiffusionSVC
-    from tools.tools import Audio2xlsr_53_56k, HubertUnits, Units_Encoder, Volume_Extractor, WhisperLargeV3
+    from tools.tools import Audio2xlsr_53_56k, HubertUnits, Units_Encoder, Volume_Extractor, WavLMUnits, WhisperLargeV3
     h = arch.SYNTHETIC_VOCODER_H
     if encoder in HubertUnits.NAMES:
         width = arch.get_encoder_out_channels(encoder)
     if encoder == "xlsr_53_56k":
         encoder_dims = dict(arch.XLSR_53_DIMS, n_layer=layers) if encoder_dims is None else dict(encoder_dims)
+        width = encoder_dims["n_state"]
+    if encoder in WavLMUnits.NAMES:
+        base = arch.wavlm_dims("large" if encoder == "wavlmlarge" else "base+")
+        encoder_dims = dict(base, n_layer=layers) if encoder_dims is None else dict(encoder_dims)
         width = encoder_dims["n_state"]
     voc = Vocoder.__new__(Vocoder)
     voc.vocoder = Hifi_VAEGAN(None, device=dev, h=h, state=init_weights.init_state(arch.generator_param_shapes(h), 0))
@@ -79,6 +84,8 @@ def synthetic_svc(dev, width=1280, layers=4, encoder="whisper_large_v3", encoder
         model = HubertUnits.synthetic(encoder, dict(arch.HUBERT_BASE_DIMS, n_layer=layers), seed=0, device=dev)
     elif encoder == "xlsr_53_56k":
         model = Audio2xlsr_53_56k.synthetic(encoder_dims, seed=0, device=dev)
+    elif encoder in WavLMUnits.NAMES:
+        model = WavLMUnits.synthetic(encoder, encoder_dims, seed=0, device=dev)
     else:
         dims = ModelDimensions(**dict(arch.WHISPER_LARGE_V3_DIMS, n_audio_state=width, n_audio_head=width // 64, n_audio_layer=layers))
         model = WhisperLargeV3.synthetic(dims, seed=0, device=dev)

@@ -688,6 +688,223 @@ hipError_t launch_attention_k4p_rel(const float* qk, const float* vt, const floa
     return launch_rel_cfg<1, 2, 1>(qk, vt, relp, out, B, C, T, heads, qlens, klens, left, right, s);
 }
 
+// ---- gated relative-bias attention (WavLM's self-attention, transformers WavLMAttention) -----------------------------------------------
+// attention_k4p at D = 64, exact fp32, K4P output, as a kernel of its own so that none of the instantiations above changes:
+//   score(i, j) = q_i . k_j / 8 + gate[b][h][i] * toep[h][j - i + n_ctx - 1], soft-max over the clip's own lens[b] keys.
+// toep [heads][2 n_ctx - 1] is the relative position bias as a function of j - i (natural units; the kernel multiplies the query's gate
+// by log2(e) once, so the product arrives in the scores' base-2 unit); gate [B][heads][Tbuf].  With an all-zero table every score gets
+// + 0 and the result equals attention_k4p's on the same inputs bit for bit (same tile rule, same order).
+// The tile choice depends on Tbuf and the head count only, never on the batch or a clip's own length.
+// MAINTENANCE: the body below is attention_k4p_rel_kernel's with Tq = Tk = T; a fix there belongs here too.  What differs, and only this:
+//   (1) one length T instead of Tq / Tk;
+//   (2) g2 / tb and the block "the gated bias" in the place of rp / pL / pR and "the relative-key term".  A tile whose keys and queries all
+//       lie inside the clip has |j - i| < T <= n_ctx, every index inside the table; a tile at the clip's end (masked keys, dead queries)
+//       clamps its indices into the table, and what it reads there is masked or never stored.
+template <int NW, int NST, int KS>
+__global__ void __launch_bounds__(NW * 64) attention_k4p_bias_kernel(const float* __restrict__ qk, const float* __restrict__ vt, const float* __restrict__ gate,
+                                                                     const float* __restrict__ toep, float* __restrict__ out, int C, int Tbuf, float scale2,
+                                                                     const int* __restrict__ lens, int n_ctx) {
+    constexpr int D = 64;
+    using Cfg = AttCfg<D, NW, NST, KS>;
+    constexpr int NWQ = NW / KS;
+    constexpr int KB = Cfg::KB, DQ = Cfg::DQ, DT = Cfg::DT, KPW = Cfg::KPW, VPW = Cfg::VPW, STAGE = Cfg::STAGE, PER_TILE = Cfg::PER_TILE;
+    static_assert(KS == 1 || KS == 2, "no latency-mode variant");
+    extern __shared__ __attribute__((aligned(16))) float smem[];      // NST x { K [row][key][4] ; V [keyquad][d][4] }
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int c = lane & 31, h = lane >> 5;
+    const int gx = gridDim.x, gy = gridDim.y, total = gx * gy * gridDim.z;
+    const int id = (blockIdx.z * gy + blockIdx.y) * gx + blockIdx.x;
+    const int per = total >> 3, rem = total & 7, xcd = id & 7;
+    const int Lid = xcd * per + (xcd < rem ? xcd : rem) + (id >> 3);
+    const int qblk = Lid % gx, hd = (Lid / gx) % gy, b = Lid / (gx * gy);
+    const int qw = wave % NWQ, ks = wave / NWQ;
+    const int q0 = qblk * (NWQ * 32) + qw * 32;      // first query of this wave
+    const int tq = q0 + c;
+    const int T = lens ? (lens[b] < Tbuf ? lens[b] : Tbuf) : Tbuf;
+    const int Tp = Tbuf + 2, T4 = (Tbuf + 3) & ~3;
+    const float* qb = qk + ((long long)b * 2 * C + (long long)hd * D) * Tp;
+
+    f32x4 qv[DQ];
+#pragma unroll
+    for (int kq = 0; kq < DQ; ++kq) {
+        qv[kq] = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (tq < T) qv[kq] = *reinterpret_cast<const f32x4*>(qb + ((long long)(kq * 2 + h) * Tp + tq + 1) * 4);
+    }
+    // this query's gate in the scores' unit (0 for a query beyond the clip: whatever the gate buffer holds there is not read) and this
+    // head's row of the table
+    const float g2 = (tq < T) ? gate[((long long)b * gy + hd) * Tbuf + tq] * 1.4426950408889634f : 0.f;
+    const float* tb = toep + (long long)hd * (2 * n_ctx - 1);
+    const int imax = 2 * n_ctx - 2;
+
+    const __amdgpu_buffer_rsrc_t rk =
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(qk + ((long long)b * 2 * C + C + (long long)hd * D) * Tp), 0, D * Tp * 4, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rv =
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(vt + ((long long)b * C + (long long)hd * D) * T4), 0, D * T4 * 4, 0x00020000);
+    int koff[KPW], voff[VPW];
+#pragma unroll
+    for (int i = 0; i < KPW; ++i) koff[i] = (((wave + NW * i) * Tp) + lane + 1) * 16;
+#pragma unroll
+    for (int i = 0; i < VPW; ++i) voff[i] = ((wave + NW * i) * 64 + lane) * 16;
+    const int nt = (qblk * (NWQ * 32) >= T) ? 0 : (T + KB - 1) / KB;
+    for (int t = 0; t < NST - 1 && t < nt; ++t) att_issue_tile<D, NW, KPW, VPW>(rk, rv, koff, voff, wave, t, smem + t * STAGE);
+#pragma unroll
+    for (int kq = 0; kq < DQ; ++kq) qv[kq] *= scale2;
+
+    f32x16 o[DT];
+#pragma unroll
+    for (int i = 0; i < DT; ++i)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) o[i][r] = 0.f;
+    float m_run = -INFINITY, l_run = 0.f;
+
+    int sc = 0, sn = NST - 1;
+    for (int kt = 0; kt < nt; ++kt) {
+        const int younger = (nt - 1 - kt < NST - 2) ? (nt - 1 - kt) : (NST - 2);
+        att_wait_younger<NST - 2, PER_TILE>(younger);
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+        if (kt + NST - 1 < nt) att_issue_tile<D, NW, KPW, VPW>(rk, rv, koff, voff, wave, kt + NST - 1, smem + sn * STAGE);
+        const float* Kc = smem + sc * STAGE;
+        const float* Vc = Kc + KB * D;
+        const int h0 = (KS == 1) ? 0 : ks;
+        const int h1 = (KS == 1) ? KB / 32 : h0 + 1;
+#pragma unroll 1
+        for (int half = h0; half < h1; ++half) {
+            const int kbase = kt * KB + half * 32;
+            if (kbase >= T) break;
+            f32x4 ka[DQ], va[4][DT];
+#pragma unroll
+            for (int kq = 0; kq < DQ; ++kq) ka[kq] = *reinterpret_cast<const f32x4*>(Kc + ((kq * 2 + h) * KB + half * 32 + c) * 4);
+            __builtin_amdgcn_sched_barrier(0);
+            f32x16 s;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) s[r] = 0.f;
+#pragma unroll
+            for (int kq = 0; kq < DQ; ++kq)
+#pragma unroll
+                for (int jj = 0; jj < 4; ++jj) s = __builtin_amdgcn_mfma_f32_32x32x2f32(ka[kq][jj], qv[kq][jj], s, 0, 0, 0);
+#pragma unroll
+            for (int g = 0; g < 4; ++g)
+#pragma unroll
+                for (int i = 0; i < DT; ++i) va[g][i] = *reinterpret_cast<const f32x4*>(Vc + ((half * 8 + 2 * g + h) * D + i * 32 + c) * 4);
+            __builtin_amdgcn_sched_barrier(0);
+            // the gated bias (wave-uniform choice: a tile wholly inside the clip needs no clamp); key j = kbase + 4 h + (r & 3) + 8 (r >> 2)
+            {
+                const int i0 = kbase + 4 * h - tq + n_ctx - 1;
+                if (kbase + 32 <= T && q0 + 32 <= T) {
+                    const float* tp = tb + i0;
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) s[r] = fmaf(g2, tp[(r & 3) + 8 * (r >> 2)], s[r]);
+                } else {
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        int i = i0 + (r & 3) + 8 * (r >> 2);
+                        i = i < 0 ? 0 : (i > imax ? imax : i);
+                        s[r] = fmaf(g2, tb[i], s[r]);
+                    }
+                }
+            }
+            if (kbase + 32 > T) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r)
+                    if (kbase + (r & 3) + 8 * (r >> 2) + 4 * h >= T) s[r] = -INFINITY;
+            }
+            float mt = max3(max3(max3(s[0], s[1], s[2]), max3(s[3], s[4], s[5]), max3(s[6], s[7], s[8])),
+                            max3(max3(s[9], s[10], s[11]), max3(s[12], s[13], s[14]), s[15]), m_run);
+            {
+                const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(mt), __float_as_uint(mt), false, false);
+                mt = max3(mt, __uint_as_float(sw[0]), __uint_as_float(sw[1]));
+            }
+            const float alpha = __builtin_amdgcn_exp2f(m_run - mt);
+            m_run = mt;
+            const f32x2 mm = {mt, mt}, aa = {alpha, alpha};
+            f32x2 lsum = {0.f, 0.f};
+#pragma unroll
+            for (int r = 0; r < 16; r += 2) {
+                const f32x2 d = f32x2{s[r], s[r + 1]} - mm;
+                s[r] = __builtin_amdgcn_exp2f(d[0]);
+                s[r + 1] = __builtin_amdgcn_exp2f(d[1]);
+                lsum += f32x2{s[r], s[r + 1]};
+            }
+            l_run = fmaf(l_run, alpha, lsum[0] + lsum[1]);
+#pragma unroll
+            for (int i = 0; i < DT; ++i)
+#pragma unroll
+                for (int r = 0; r < 16; r += 2) {
+                    const f32x2 t = f32x2{o[i][r], o[i][r + 1]} * aa;
+                    o[i][r] = t[0]; o[i][r + 1] = t[1];
+                }
+#pragma unroll
+            for (int g = 0; g < 4; ++g)
+#pragma unroll
+                for (int i = 0; i < DT; ++i)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) o[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(va[g][i][e], s[4 * g + e], o[i], 0, 0, 0);
+        }
+        sc = (sc + 1 == NST) ? 0 : sc + 1;
+        sn = (sn + 1 == NST) ? 0 : sn + 1;
+    }
+    if constexpr (KS == 2) {
+        __syncthreads();
+        constexpr int RED = (2 + 16 * DT) * 64;
+        if (ks >= 1) {
+            float* red = smem + qw * RED + lane;
+            red[0] = m_run; red[64] = l_run;
+#pragma unroll
+            for (int i = 0; i < DT; ++i)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) red[(2 + i * 16 + r) * 64] = o[i][r];
+        }
+        __syncthreads();
+        if (ks >= 1) return;
+        const float* red = smem + qw * RED + lane;
+        const float m1 = red[0], l1 = red[64];
+        const float m = fmaxf(m_run, m1);
+        // (a share that saw no key carries m = -inf, l = 0: its factor is exp2(-inf) = 0 unless both are empty, which a live query never is)
+        const float a0 = (m_run == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f(m_run - m), a1 = (m1 == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f(m1 - m);
+        l_run = l_run * a0 + l1 * a1;
+#pragma unroll
+        for (int i = 0; i < DT; ++i)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) o[i][r] = o[i][r] * a0 + red[(2 + i * 16 + r) * 64] * a1;
+    }
+    float l;
+    {
+        const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(l_run), __float_as_uint(l_run), false, false);
+        l = __uint_as_float(sw[0]) + __uint_as_float(sw[1]);
+    }
+    att_store_k4p<D>(o, 1.0f / l, out + (long long)b * C * Tp, C, Tp, hd, h, tq, Tbuf, tq < T);
+}
+
+template <int NW, int NST, int KS>
+static hipError_t launch_bias_cfg(const float* qk, const float* vt, const float* gate, const float* toep, float* out, int B, int C, int T, int heads,
+                                  const int* lens, int n_ctx, hipStream_t s) {
+    using Cfg = AttCfg<64, NW, NST, KS>;
+    auto kern = attention_k4p_bias_kernel<NW, NST, KS>;
+    if (Cfg::LDS_BYTES > 48 * 1024) {
+        static std::atomic<unsigned long long> attr_done{0};
+        hipError_t e = ensure_max_dynamic_lds(reinterpret_cast<const void*>(kern), attr_done);
+        if (e != hipSuccess) return e;
+    }
+    constexpr int QPB = NW / KS * 32;
+    const float scale = 1.4426950408889634f / 8.0f;      // log2(e) / sqrt(64)
+    hipEvent_t e0, e1;
+    const dim3 grid((T + QPB - 1) / QPB, heads, B);
+    if (prof_attach_events(&e0, &e1)) hipExtLaunchKernelGGL(kern, grid, dim3(NW * 64), Cfg::LDS_BYTES, s, e0, e1, 0, qk, vt, gate, toep, out, C, T, scale, lens, n_ctx);
+    else hipLaunchKernelGGL(kern, grid, dim3(NW * 64), Cfg::LDS_BYTES, s, qk, vt, gate, toep, out, C, T, scale, lens, n_ctx);
+    return hipGetLastError();
+}
+
+hipError_t launch_attention_k4p_bias(const float* qk, const float* vt, const float* gate, const float* toep, float* out, int B, int C, int T, int heads,
+                                     const int* lens, int n_ctx, hipStream_t s) {
+    if (B <= 0 || B > 65535 || heads < 1 || heads > 65535 || C != heads * 64 || T <= 0 || T > n_ctx) return hipErrorInvalidValue;
+    ProfScope ps(s, "attention_bias", 4.0 * B * (double)T * T * C, 4.0 * 4.0 * B * C * T, true);
+    // launch_dk's rule at the nominal batch of 16 (launch_attention_k4p_rel's)
+    if ((long long)((T + 127) / 128) * heads * 16 >= 512) return launch_bias_cfg<4, 2, 1>(qk, vt, gate, toep, out, B, C, T, heads, lens, n_ctx, s);
+    if (T > 32) return launch_bias_cfg<4, 2, 2>(qk, vt, gate, toep, out, B, C, T, heads, lens, n_ctx, s);
+    return launch_bias_cfg<1, 2, 1>(qk, vt, gate, toep, out, B, C, T, heads, lens, n_ctx, s);
+}
+
 // test entry: K4P fp32 in and out, the products on the fp16 pipe
 hipError_t launch_attention_k4p_f16math(const float* qk, const float* vt, float* out, int B, int C, int T, int heads, hipStream_t s, int tile_batch, const int* lens) {
     return attention_any(qk, vt, out, B, C, T, heads, 0, true, tile_batch, s, lens, 0);

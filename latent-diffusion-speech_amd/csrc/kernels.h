@@ -326,6 +326,22 @@ hipError_t launch_w2vbert_dwconv(const float* x, const float* wp, const float* g
                                  const int* nlen, int B, int C, int T, int K, hipStream_t s);
 
 // ---------------------------------------------------------------------------------------------
+// WavLM units encoder: the kernels of its own (wavlm.hip, attention_k4p.hip); slen / nlen / lens are device int32 [B] or null (= the
+// buffer's length)
+// ---------------------------------------------------------------------------------------------
+// gate [B][heads][T] = a (b cst[head] - 1) + 2 with (a, b) = the sigmoids of the two sums of four of w [8][64] x + bias [8] over the 64
+// channels of the head at frame t of x (K4P [B][C][T]); 0 at and beyond nlen[b] (nothing is read there)
+hipError_t launch_wavlm_gate(const float* x, const float* w, const float* bias, const float* cst, float* gate, const int* nlen, int B, int C, int T, int heads,
+                             hipStream_t s);
+// out [B][L] = (audio - mean_b) / sqrt(var_b + 1e-7) over clip b's own slen[b] samples (statistics in double; scratch stat [B]); samples at
+// and beyond slen[b] are neither read nor written
+hipError_t launch_wavlm_wave_norm(const float* audio, const int* slen, long long L, double2* stat, float* out, int B, hipStream_t s);
+// launch_attention_k4p at heads of 64 with score(i, j) += gate[b][head][i] * toep[head][j - i + n_ctx - 1] (toep [heads][2 n_ctx - 1] in
+// natural units); queries and keys = the clip's lens[b] rows (zeros beyond); T <= n_ctx
+hipError_t launch_attention_k4p_bias(const float* qk, const float* vt, const float* gate, const float* toep, float* out, int B, int C, int T, int heads,
+                                     const int* lens, int n_ctx, hipStream_t s);
+
+// ---------------------------------------------------------------------------------------------
 // Small dense layers with N = batch columns (time embedding path)
 // out[b][m] = sum_k W[m][k] * g(in[b][k]) + bias[m];  g = identity | SiLU | sinusoid(t[b])
 // ---------------------------------------------------------------------------------------------

@@ -3088,6 +3088,285 @@ extern "C" int lds_w2v_encode(lds_w2v* h, const float* audio, const int32_t* len
 }
 
 // ================================================================================================
+// WavLM units encoder (transformers' WavLMModel; so-vits-svc's wavlmbase+, kNN-VC's WavLM-Large).  Two flavours of one network:
+//   stable_layer_norm 0 (Base / Base+): HuBERT's skeleton above with pad 0 -- bias-free convolutions, a GroupNorm behind conv0, post-LN blocks;
+//   stable_layer_norm 1 (Large): wav2vec 2.0's skeleton above with zero convolution biases -- a LayerNorm behind every convolution, pre-LN
+//   blocks, a final encoder.layer_norm.
+// What neither has: every block's self-attention adds gate[h][i] * bias[h][j - i] to its scores.  The bias is layer 0's rel_attn_embed
+// looked up at the bucket of j - i, a Toeplitz table [heads][2 n_ctx - 1] built once at create; the gate [B][heads][T] comes from the
+// block's attention input in one small launch (wavlm.hip) that runs beside the q | k | v convolution's, and attention_k4p_bias applies both.
+// In the stable flavour the attention's LayerNorm is therefore materialised (launch_hubert_ln: the gate reads it too) instead of folded
+// into the q | k | v convolution; the feed-forward's stays folded.  Tensor names are WavLMModel.state_dict()'s.
+// ================================================================================================
+struct WavlmBlockW {
+    ConvW qkv, out, fc1, fc2;
+    float *n1_g = nullptr, *n1_b = nullptr, *n2_g = nullptr, *n2_b = nullptr;      // layer_norm, final_layer_norm (n2: post-LN flavour only)
+    float *fc1_c1 = nullptr, *fc1_c2 = nullptr;                                    // stable flavour: final_layer_norm folded into fc1
+    float *gate_w = nullptr, *gate_b = nullptr, *gate_c = nullptr;                 // gru_rel_pos_linear [8][64], [8]; gru_rel_pos_const [heads]
+};
+struct lds_wavlm : ConvStackW {
+    lds_wavlm_cfg cfg;
+    Owner own;
+    float *w0 = nullptr, *b0 = nullptr;                            // conv0 [conv_dim][10]; zeros (the stable flavour's conv0 kernel takes a bias)
+    float *ln_g[kHubertLevels] = {}, *ln_b[kHubertLevels] = {};    // the norm behind conv0 (both flavours) .. conv6 (stable flavour)
+    float *norm_g = nullptr, *norm_b = nullptr;                    // encoder.layer_norm
+    float* toep = nullptr;                                         // [n_head][2 n_ctx - 1]
+    std::vector<WavlmBlockW> blocks;
+};
+
+// WavLMAttention._relative_positions_bucket for one distance d = key - query, its large branch in float32 as torch runs it
+static int wavlm_bucket(int d, int num_buckets, int max_distance) {
+    const int nb = num_buckets / 2, me = nb / 2, a = d < 0 ? -d : d;
+    int v = a;
+    if (a >= me) {
+        float x = logf((float)a / (float)me);
+        x = x / (float)log((double)max_distance / (double)me);
+        x = x * (float)(nb - me);
+        const long long big = (long long)((float)me + x);
+        v = big < nb - 1 ? (int)big : nb - 1;
+    }
+    return (d > 0 ? nb : 0) + v;
+}
+static int wavlm_bucket_check(int num_buckets, int max_distance) {
+    if (num_buckets < 4 || num_buckets % 4 || num_buckets > 4096) return fail(LDS_EINVAL, "wavlm: num_buckets %d must be a multiple of 4 in 4 .. 4096", num_buckets);
+    if (max_distance <= num_buckets / 4 || max_distance > (1 << 20))
+        return fail(LDS_EINVAL, "wavlm: max_distance %d outside num_buckets / 4 + 1 = %d .. 2^20", max_distance, num_buckets / 4 + 1);
+    return LDS_OK;
+}
+static int wavlm_cfg_check(const lds_wavlm_cfg* c) {
+    if (!c) return fail(LDS_EINVAL, "null argument");
+    LDS_TRY(conv_stack_dims_check("wavlm", c->conv_dim, c->n_state, c->n_head, c->n_layer, c->n_ffn, -1, c->pos_kernel, c->pos_groups, c->n_ctx));
+    LDS_TRY(wavlm_bucket_check(c->num_buckets, c->max_distance));
+    if (c->stable_layer_norm != 0 && c->stable_layer_norm != 1) return fail(LDS_EINVAL, "wavlm: stable_layer_norm %d (0 or 1)", c->stable_layer_norm);
+    return LDS_OK;
+}
+
+extern "C" int lds_wavlm_create(const lds_wavlm_cfg* cfg, int n, const char* const* names, const float* const* ptrs, const int64_t* numel, lds_wavlm** out) {
+    if (!cfg || !names || !ptrs || !numel || !out || n < 0) return fail(LDS_EINVAL, "null argument");
+    LDS_TRY(wavlm_cfg_check(cfg));
+    const int D = cfg->conv_dim, C = cfg->n_state, F = cfg->n_ffn, K = cfg->pos_kernel, gw = C / cfg->pos_groups, H = cfg->n_head;
+    const bool stable = cfg->stable_layer_norm != 0;
+    lds_wavlm* h = new lds_wavlm();
+    h->cfg = *cfg;
+    WeightLoader T(h->own, n, names, ptrs, numel);
+    Owner& o = h->own;
+    bool ok = true;
+    for (int i = 0; i < kHubertLevels && ok; ++i) {
+        const std::string p = "feature_extractor.conv_layers." + std::to_string(i) + ".";
+        if (i == 0 || stable) {      // GroupNorm(C, C) behind conv0 (Base) / a LayerNorm behind every convolution (Large)
+            h->ln_g[i] = T.vec(p + "layer_norm.weight", D);
+            h->ln_b[i] = T.vec(p + "layer_norm.bias", D);
+            ok = h->ln_g[i] && h->ln_b[i];
+            if (!ok) break;
+        }
+        if (i == 0) {
+            h->w0 = T.vec(p + "conv.weight", (int64_t)D * 10);
+            h->b0 = o.upload(std::vector<float>(D, 0.f));
+            ok = h->w0 && h->b0;
+        } else {
+            const int k = i <= 4 ? 3 : 2;
+            const float* w = T.get(p + "conv.weight", (int64_t)D * D * k);
+            ok = w && pack_conv(o, w, nullptr, D, D, k, h->conv[i - 1]);
+        }
+    }
+    if (ok) {
+        const float *g = T.get("feature_projection.layer_norm.weight", D), *b = T.get("feature_projection.layer_norm.bias", D);
+        const float *w = T.get("feature_projection.projection.weight", (int64_t)C * D), *wb = T.get("feature_projection.projection.bias", C);
+        ok = g && b && w && wb && pack_ln_fold(o, w, wb, g, b, C, D, {}, h->fproj, h->fproj_c1, h->fproj_c2);
+    }
+    if (ok) {
+        const float* g = T.get("encoder.pos_conv_embed.conv.parametrizations.weight.original0", K);
+        const float* v = T.get("encoder.pos_conv_embed.conv.parametrizations.weight.original1", (int64_t)C * gw * K);
+        h->pos_b = T.vec("encoder.pos_conv_embed.conv.bias", C);
+        if (g && v) h->pos_w = pack_posconv(o, g, v, C, cfg->pos_groups, K);
+        h->norm_g = T.vec("encoder.layer_norm.weight", C);
+        h->norm_b = T.vec("encoder.layer_norm.bias", C);
+        ok = h->pos_w && h->pos_b && h->norm_g && h->norm_b;
+    }
+    if (ok) {      // the bias of every layer: layer 0's embedding at the bucket of every distance
+        const int NB = cfg->num_buckets, W = 2 * cfg->n_ctx - 1;
+        const float* e = T.get("encoder.layers.0.attention.rel_attn_embed.weight", (int64_t)NB * H);
+        if (e) {
+            std::vector<float> tp((size_t)H * W);
+            for (int d = -(cfg->n_ctx - 1); d < cfg->n_ctx; ++d) {
+                const int bk = wavlm_bucket(d, NB, cfg->max_distance);
+                for (int hd = 0; hd < H; ++hd) tp[(size_t)hd * W + d + cfg->n_ctx - 1] = e[(size_t)bk * H + hd];
+            }
+            h->toep = o.upload(tp);
+        }
+        ok = h->toep != nullptr;
+    }
+    h->blocks.resize(cfg->n_layer);
+    for (int l = 0; l < cfg->n_layer && ok; ++l) {
+        const std::string p = "encoder.layers." + std::to_string(l) + ".";
+        WavlmBlockW& bw = h->blocks[l];
+        const int64_t CC = (int64_t)C * C, FC = (int64_t)F * C;
+        const float *qw = T.get(p + "attention.q_proj.weight", CC), *qb = T.get(p + "attention.q_proj.bias", C);
+        const float *kw = T.get(p + "attention.k_proj.weight", CC), *kb = T.get(p + "attention.k_proj.bias", C);
+        const float *vw = T.get(p + "attention.v_proj.weight", CC), *vb = T.get(p + "attention.v_proj.bias", C);
+        const float *ow = T.get(p + "attention.out_proj.weight", CC), *ob = T.get(p + "attention.out_proj.bias", C);
+        const float *g2 = T.get(p + "final_layer_norm.weight", C), *b2 = T.get(p + "final_layer_norm.bias", C);
+        const float *f1 = T.get(p + "feed_forward.intermediate_dense.weight", FC), *f1b = T.get(p + "feed_forward.intermediate_dense.bias", F);
+        const float *f2 = T.get(p + "feed_forward.output_dense.weight", FC), *f2b = T.get(p + "feed_forward.output_dense.bias", C);
+        if (!qw || !qb || !kw || !kb || !vw || !vb || !ow || !ob || !g2 || !b2 || !f1 || !f1b || !f2 || !f2b) { ok = false; break; }
+        bw.n1_g = T.vec(p + "layer_norm.weight", C); bw.n1_b = T.vec(p + "layer_norm.bias", C);
+        bw.gate_w = T.vec(p + "attention.gru_rel_pos_linear.weight", 8 * 64);
+        bw.gate_b = T.vec(p + "attention.gru_rel_pos_linear.bias", 8);
+        bw.gate_c = T.vec(p + "attention.gru_rel_pos_const", H);
+        const QkvCat q = cat_qkv(qw, kw, vw, qb, kb, vb, C);
+        ok = bw.n1_g && bw.n1_b && bw.gate_w && bw.gate_b && bw.gate_c && pack_conv(o, q.w.data(), q.b.data(), 3 * C, C, 1, bw.qkv) &&
+             pack_conv(o, ow, ob, C, C, 1, bw.out) && pack_conv(o, f2, f2b, C, F, 1, bw.fc2);
+        if (!ok) break;
+        if (stable) {
+            ok = pack_ln_fold(o, f1, f1b, g2, b2, F, C, {}, bw.fc1, bw.fc1_c1, bw.fc1_c2);
+        } else {
+            bw.n2_g = o.upload(std::vector<float>(g2, g2 + C)); bw.n2_b = o.upload(std::vector<float>(b2, b2 + C));
+            ok = bw.n2_g && bw.n2_b && pack_conv(o, f1, f1b, F, C, 1, bw.fc1);
+        }
+    }
+    return T.finish(ok, "wavlm", h, out);
+}
+extern "C" void lds_wavlm_destroy(lds_wavlm* h) { delete h; }
+
+struct WavlmWs : ConvStackWs, TfWs {
+    float2 *part, *stat;      // Base: norm0's statistics
+    double2* wstat;           // the clips' waveform statistics
+    float *wave, *gate;       // the normalised waveform [B][L]; the block's gate [B][n_head][T]
+};
+static void plan_wavlm(const lds_wavlm* h, Arena& A, int B, int64_t L, const int32_t* nb, WavlmWs& w) {
+    const size_t D = h->cfg.conv_dim, C = h->cfg.n_state, F = h->cfg.n_ffn, T = nb[6], Bz = B;
+    w.plan(A, Bz, D, nb);
+    w.part = (float2*)A.f(Bz * (((size_t)nb[0] + 255) / 256) * D * 2);
+    w.stat = (float2*)A.f(Bz * D * 2);
+    w.wstat = (double2*)A.f(Bz * 4);
+    w.wave = A.f(Bz * (size_t)L);
+    w.gate = plan_tf(A, Bz, C, T, F * (T + 2), std::max(D, C), w, (size_t)h->cfg.n_head * T);
+}
+static int wavlm_shape_check(const lds_wavlm* h, int B, int64_t L, int32_t* nb) {
+    if (!h) return fail(LDS_EINVAL, "null handle");
+    LDS_TRY(range_check("wavlm", "B", B, 1, 64));
+    return conv_stack_shape_check("wavlm", h->cfg.n_ctx, B, L, 0, 0, nb);
+}
+extern "C" int lds_wavlm_workspace_bytes(const lds_wavlm* h, int B, int64_t L, size_t* out) {
+    int32_t nb[kHubertLevels];
+    return plan_bytes(out, [&] { return wavlm_shape_check(h, B, L, nb); }, [&](Arena& A) { WavlmWs w; plan_wavlm(h, A, B, L, nb, w); });
+}
+
+// audio -> feat ([B][T][conv_dim]) or enc ([B][T][n_state] = hidden_states[n_layers_run]).  Every argument has been checked.
+static int wavlm_run(lds_wavlm* h, const float* audio, int64_t L, const int32_t* lens_host, const int32_t* nb, float* feat, float* enc, int n_layers_run,
+                     int normalize, void* ws, size_t ws_bytes, int B, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    ProfChain chain;
+    Arena A(ws, ws_bytes);
+    WavlmWs w;
+    plan_wavlm(h, A, B, L, nb, w);
+    if (!A.ok) return fail(LDS_ENOMEM, "wavlm workspace too small: need %zu", A.used);
+    const int D = h->cfg.conv_dim, C = h->cfg.n_state, T = nb[6], H = h->cfg.n_head, F = h->cfg.n_ffn;
+    const bool stable = h->cfg.stable_layer_norm != 0;
+    if (lens_host) LDS_TRY(w.upload(lens_host, 0, B, st));
+    TileBatchScope tb(0);      // tile rules judged at the nominal batch: a clip's units do not depend on the batch it is in
+    if (normalize) {
+        HIP_TRY(launch_wavlm_wave_norm(audio, w.slen, L, w.wstat, w.wave, B, st));
+        audio = w.wave;
+    }
+    float* x = w.ca;
+    if (stable) {      // w2v_run's stack: conv_i into cb, GELU(LayerNorm(.)) back into ca
+        HIP_TRY(launch_w2v_conv0(audio, w.slen, L, h->w0, h->b0, h->ln_g[0], h->ln_b[0], 1e-5f, w.nlen[0], nb[0], D, w.ca, B, st));
+        for (int i = 1; i < kHubertLevels; ++i) {
+            LensScope ls(w.nlen[i]);
+            DOpt o;
+            o.stride = 2; o.pad = 0;
+            LDS_TRY(run_dconv(h->conv[i - 1], w.ca, D, nullptr, 0, nb[i - 1], o, w.cb, B, st));
+            HIP_TRY(launch_w2v_ln_act(w.cb, h->ln_g[i], h->ln_b[i], 1e-5f, w.ca, (i == kHubertLevels - 1 && enc) ? w.lnp : nullptr, w.nlen[i], B, D, nb[i], st));
+        }
+    } else {           // hubert_run's stack with pad 0: gelu(conv_i(.)), the levels alternating between ca and cb
+        HIP_TRY(launch_hubert_conv0(audio, w.slen, L, 0, h->w0, h->ln_g[0], h->ln_b[0], 1e-5f, w.nlen[0], nb[0], D, w.part, w.stat, w.ca, B, st));
+        float* xn = w.cb;
+        for (int i = 1; i < kHubertLevels; ++i) {
+            LensScope ls(w.nlen[i]);
+            DOpt o;
+            o.stride = 2; o.pad = 0; o.epi = EPI_GELU;
+            if (i == kHubertLevels - 1) o.lnpart_out = w.lnp;
+            LDS_TRY(run_dconv(h->conv[i - 1], x, D, nullptr, 0, nb[i - 1], o, xn, B, st));
+            { float* t = x; x = xn; xn = t; }
+        }
+    }
+    const int* flen = w.nlen[kHubertLevels - 1];
+    if (feat) HIP_TRY(launch_hubert_store_frames(x, feat, flen, B, D, T, st));
+    if (!enc) return LDS_OK;
+    LensScope ls(flen);
+    {
+        DOpt o;      // projection(layer_norm(.))
+        o.ln_part = w.lnp; o.ln_np = D / 32; o.ln_c1 = h->fproj_c1; o.ln_c2 = h->fproj_c2;
+        LDS_TRY(run_dconv(h->fproj, x, D, nullptr, 0, T, o, w.xa, B, st));
+    }
+    HIP_TRY(launch_hubert_posconv(w.xa, h->pos_w, h->pos_b, w.xb, flen, B, C, T, h->cfg.pos_kernel, h->cfg.pos_groups, st));
+    // the residual stream is w.xb in the stable flavour (w.xa holds a block's layer_norm output), w.xa in the post-LN flavour
+    if (!stable) HIP_TRY(launch_hubert_ln(w.xb, h->norm_g, h->norm_b, 1e-5f, w.xa, flen, B, C, T, st));
+    for (int l = 0; l < n_layers_run; ++l) {
+        const WavlmBlockW& bw = h->blocks[l];
+        if (stable) HIP_TRY(launch_hubert_ln(w.xb, bw.n1_g, bw.n1_b, 1e-5f, w.xa, flen, B, C, T, st));
+        const DOpt oq = qkv_opt(C, w.v);      // q | k | v and the gate of the attention input w.xa
+        LDS_TRY(run_dconv(bw.qkv, w.xa, C, nullptr, 0, T, oq, w.qk, B, st));
+        HIP_TRY(launch_wavlm_gate(w.xa, bw.gate_w, bw.gate_b, bw.gate_c, w.gate, flen, B, C, T, H, st));
+        HIP_TRY(launch_attention_k4p_bias(w.qk, w.v, w.gate, h->toep, w.att, B, C, T, H, flen, h->cfg.n_ctx, st));
+        if (stable) {
+            DOpt oo;      // x + out_proj(.), partials for final_layer_norm
+            oo.res = w.xb; oo.lnpart_out = w.lnp;
+            LDS_TRY(run_dconv(bw.out, w.att, C, nullptr, 0, T, oo, w.xa, B, st));
+            DOpt o1;      // gelu(intermediate_dense(final_layer_norm(.)))
+            o1.epi = EPI_GELU;
+            o1.ln_part = w.lnp; o1.ln_np = C / 32; o1.ln_c1 = bw.fc1_c1; o1.ln_c2 = bw.fc1_c2;
+            LDS_TRY(run_dconv(bw.fc1, w.xa, C, nullptr, 0, T, o1, w.big, B, st));
+            DOpt o2;      // + output_dense(.)
+            o2.res = w.xa;
+            LDS_TRY(run_dconv(bw.fc2, w.big, F, nullptr, 0, T, o2, w.xb, B, st));
+        } else {
+            DOpt oo;      // x + out_proj(.), then layer_norm
+            oo.res = w.xa;
+            LDS_TRY(run_dconv(bw.out, w.att, C, nullptr, 0, T, oo, w.xb, B, st));
+            HIP_TRY(launch_hubert_ln(w.xb, bw.n1_g, bw.n1_b, 1e-5f, w.xa, flen, B, C, T, st));
+            DOpt o1;      // gelu(intermediate_dense(.))
+            o1.epi = EPI_GELU;
+            LDS_TRY(run_dconv(bw.fc1, w.xa, C, nullptr, 0, T, o1, w.big, B, st));
+            DOpt o2;      // + output_dense(.), then final_layer_norm
+            o2.res = w.xa;
+            LDS_TRY(run_dconv(bw.fc2, w.big, F, nullptr, 0, T, o2, w.xb, B, st));
+            HIP_TRY(launch_hubert_ln(w.xb, bw.n2_g, bw.n2_b, 1e-5f, w.xa, flen, B, C, T, st));
+        }
+    }
+    if (stable && n_layers_run == h->cfg.n_layer) {      // hidden_states[n_layer] is behind encoder.layer_norm, the earlier ones are not
+        HIP_TRY(launch_hubert_ln(w.xb, h->norm_g, h->norm_b, 1e-5f, w.xa, flen, B, C, T, st));
+        HIP_TRY(launch_hubert_store_frames(w.xa, enc, flen, B, C, T, st));
+    } else {
+        HIP_TRY(launch_hubert_store_frames(stable ? w.xb : w.xa, enc, flen, B, C, T, st));
+    }
+    return LDS_OK;
+}
+
+static int wavlm_audio_check(const lds_wavlm* h, const float* audio, const int32_t* lengths, const void* out, const void* ws, int B, int64_t L, int normalize,
+                             int32_t* nb) {
+    if (!h || !audio || !out || !ws) return fail(LDS_EINVAL, "null argument");
+    LDS_TRY(wavlm_shape_check(h, B, L, nb));
+    if (normalize != 0 && normalize != 1) return fail(LDS_EINVAL, "wavlm: normalize %d (0 or 1)", normalize);
+    if (lengths) LDS_TRY(clip_lens_check("length", lengths, B, 400, L));
+    return LDS_OK;
+}
+extern "C" int lds_wavlm_features(lds_wavlm* h, const float* audio, const int32_t* lengths, float* out, int normalize, void* ws, size_t ws_bytes, int B,
+                                  int64_t L, void* stream) {
+    int32_t nb[kHubertLevels];
+    LDS_TRY(wavlm_audio_check(h, audio, lengths, out, ws, B, L, normalize, nb));
+    return wavlm_run(h, audio, L, lengths, nb, out, nullptr, 0, normalize, ws, ws_bytes, B, stream);
+}
+extern "C" int lds_wavlm_encode(lds_wavlm* h, const float* audio, const int32_t* lengths, float* out, int n_layers_run, int normalize, void* ws,
+                                size_t ws_bytes, int B, int64_t L, void* stream) {
+    int32_t nb[kHubertLevels];
+    LDS_TRY(wavlm_audio_check(h, audio, lengths, out, ws, B, L, normalize, nb));
+    if (n_layers_run < 0 || n_layers_run > h->cfg.n_layer) return fail(LDS_EINVAL, "wavlm: n_layers_run %d outside 0 .. %d", n_layers_run, h->cfg.n_layer);
+    return wavlm_run(h, audio, L, lengths, nb, nullptr, out, n_layers_run, normalize, ws, ws_bytes, B, stream);
+}
+
+// ================================================================================================
 // w2v-BERT 2.0 units encoder (reference tools/tools.py Wav2Vec2Bert: transformers' Wav2Vec2BertModel on SeamlessM4TFeatureExtractor's
 // input_features, with its attention mask).  A Kaldi-style filter bank (w2vbert.hip), LayerNorm + Linear, then n_layer Conformer blocks:
 // half-step feed-forward, self-attention with a relative-key bias, convolution module, half-step feed-forward, LayerNorm.  The four
@@ -4407,5 +4686,47 @@ extern "C" int lds_test_w2vbert_dwconv(const float* x, const float* w, const flo
     HIP_TRY(launch_w2vbert_dwconv(kx, wp, gamma, beta, eps, ko, vl, nl, B, C, T, K, st));
     HIP_TRY(launch_from_k4p(ko, out, B, C, T, st));
     HIP_TRY(hipStreamSynchronize(st));
+    return LDS_OK;
+}
+
+// The WavLM encoder's gated-bias attention alone (attention_k4p.hip), plain tensors in and out; every pointer but the lengths is a device
+// pointer.  wavlm_buckets touches no device.
+extern "C" int lds_test_wavlm_attention(const float* qkv, const float* gate, const float* toep, const int32_t* lengths, float* out, int B, int C, int T,
+                                        int heads, int n_ctx, void* stream) {
+    if (!qkv || !gate || !toep || !out || B < 1 || B > 64 || T < 1 || heads < 1 || C != heads * 64 || n_ctx < T || n_ctx > 1500) return fail(LDS_EINVAL, "bad argument");
+    hipStream_t st = (hipStream_t)stream;
+    TmpDev tmp;
+    float* qkp = tmp.f((size_t)B * 2 * C * T);       // plain [B][2C][T]
+    float* vpl = tmp.f((size_t)B * C * T);
+    float* vt = tmp.f((size_t)B * C * (T + 3) + 2048);
+    float* kqk = tmp.f((size_t)B * 2 * C * (T + 2));
+    float* ko = tmp.f((size_t)B * C * (T + 2));
+    int* dl = (int*)tmp.f(64);
+    if (!qkp || !vpl || !vt || !kqk || !ko || !dl) return fail(LDS_ENOMEM, "alloc");
+    const int* ln = nullptr;
+    if (lengths) {
+        for (int b = 0; b < B; ++b)
+            if (lengths[b] < 1 || lengths[b] > T) return fail(LDS_EINVAL, "lengths[%d] = %d outside 1 .. %d", b, lengths[b], T);
+        LDS_TRY(upload_clip_ints(lengths, B, dl, st));
+        ln = dl;
+    }
+    for (int b = 0; b < B; ++b) {
+        HIP_TRY(hipMemcpyAsync(qkp + (size_t)b * 2 * C * T, qkv + (size_t)b * 3 * C * T, sizeof(float) * 2 * C * T, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(vpl + (size_t)b * C * T, qkv + (size_t)b * 3 * C * T + (size_t)2 * C * T, sizeof(float) * C * T, hipMemcpyDeviceToDevice, st));
+        if (lengths && lengths[b] < T)
+            HIP_TRY(hipMemset2DAsync(vpl + (size_t)b * C * T + lengths[b], sizeof(float) * T, 0, sizeof(float) * (T - lengths[b]), C, st));
+    }
+    HIP_TRY(hipMemsetAsync(ko, 0xff, (size_t)B * C * (T + 2) * sizeof(float), st));
+    HIP_TRY(launch_to_k4p(qkp, kqk, B, 2 * C, T, 2 * C, 0, st));
+    HIP_TRY(launch_plain_to_vt(vpl, vt, B, C, T, 64, st));
+    HIP_TRY(launch_attention_k4p_bias(kqk, vt, gate, toep, ko, B, C, T, heads, ln, n_ctx, st));
+    HIP_TRY(launch_from_k4p(ko, out, B, C, T, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return LDS_OK;
+}
+extern "C" int lds_test_wavlm_buckets(int num_buckets, int max_distance, int n, int32_t* out) {
+    if (!out || n < 1 || n > (1 << 20)) return fail(LDS_EINVAL, "bad argument");
+    LDS_TRY(wavlm_bucket_check(num_buckets, max_distance));
+    for (int d = -(n - 1); d < n; ++d) out[d + n - 1] = wavlm_bucket(d, num_buckets, max_distance);
     return LDS_OK;
 }

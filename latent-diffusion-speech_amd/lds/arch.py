@@ -250,7 +250,7 @@ def encoder_param_shapes(h):
 
 def get_encoder_out_channels(encoder):
     """Reference tools/tools.py:257-264 (`get_encdoer_out_channels`)."""
-    table = {"whisper_large_v3": 1280, "contentvec768l12": 768, "xlsr_53_56k": 1024, "hubertsoft": 256}
+    table = {"whisper_large_v3": 1280, "contentvec768l12": 768, "xlsr_53_56k": 1024, "hubertsoft": 256, "wavlmbase+": 768, "wavlmlarge": 1024}
     if encoder in table:
         return table[encoder]
     raise ValueError(f"[x] Unknown encoder: {encoder}")
@@ -812,6 +812,141 @@ def w2vbert_convert_state(state, cfg=None):
             raise ValueError(f"w2v-BERT checkpoint: {k!r} has shape {tuple(got[k].shape)}, expected {tuple(shp)}")
         out[k] = got[k]
     return out
+
+
+# ---- WavLM units encoder (transformers' WavLMModel: so-vits-svc's wavlmbase+, kNN-VC's WavLM-Large) ------------------------------------------
+# the fields of include/lds.h lds_wavlm_cfg; stable_layer_norm 0 = Base / Base+ (group-norm extractor, post-LN blocks), 1 = Large (layer-norm
+# extractor, pre-LN blocks); n_ctx = the most frames of one call (30 s give 1499)
+WAVLM_BASE_PLUS_DIMS = dict(conv_dim=512, n_state=768, n_head=12, n_layer=12, n_ffn=3072, pos_kernel=128, pos_groups=16, num_buckets=320,
+                            max_distance=800, stable_layer_norm=0, n_ctx=1500)
+WAVLM_LARGE_DIMS = dict(conv_dim=512, n_state=1024, n_head=16, n_layer=24, n_ffn=4096, pos_kernel=128, pos_groups=16, num_buckets=320,
+                        max_distance=800, stable_layer_norm=1, n_ctx=1500)
+WAVLM_MIN_SAMPLES = 400
+# checkpoint tensors that inference never reads (the masking embedding; the heads of the ForCTC / ForXVector / ... wrappers)
+WAVLM_IGNORED_PREFIXES = ("masked_spec_embed", "lm_head.", "projector.", "classifier.", "feature_extractor_xvector.", "tdnn.", "objective.",
+                          "layer_weights")
+
+
+def wavlm_dims(name):
+    """'base+' (also 'base': the same network) or 'large' -> a copy of the fields of lds_wavlm_cfg"""
+    table = {"base": WAVLM_BASE_PLUS_DIMS, "base+": WAVLM_BASE_PLUS_DIMS, "large": WAVLM_LARGE_DIMS}
+    if name not in table:
+        raise ValueError(f"wavlm_dims: {name!r} (one of {sorted(table)})")
+    return dict(table[name])
+
+
+def wavlm_frames(n_samples):
+    """Frames of a clip of n_samples: HuBERT's level rule without padding (400 samples -> 1, 16,000 -> 49, 30 s -> 1499)"""
+    return hubert_level_frames(n_samples, 0)[-1]
+
+
+def wavlm_param_shapes(cfg=None):
+    """WavLMModel.state_dict() key -> shape for the tensors inference reads (the names lds_wavlm_create looks up), in the model's order"""
+    c = dict(WAVLM_BASE_PLUS_DIMS if cfg is None else cfg)
+    D, C, F, K, G, H, NB = c["conv_dim"], c["n_state"], c["n_ffn"], c["pos_kernel"], c["pos_groups"], c["n_head"], c["num_buckets"]
+    d = OrderedDict()
+    for i in range(7):
+        p = f"feature_extractor.conv_layers.{i}."
+        d[p + "conv.weight"] = (D, 1 if i == 0 else D, 10 if i == 0 else (3 if i <= 4 else 2))
+        if i == 0 or c["stable_layer_norm"]:
+            d[p + "layer_norm.weight"] = (D,)
+            d[p + "layer_norm.bias"] = (D,)
+    d["feature_projection.layer_norm.weight"] = (D,)
+    d["feature_projection.layer_norm.bias"] = (D,)
+    d["feature_projection.projection.weight"] = (C, D)
+    d["feature_projection.projection.bias"] = (C,)
+    d["encoder.pos_conv_embed.conv.bias"] = (C,)
+    d["encoder.pos_conv_embed.conv.parametrizations.weight.original0"] = (1, 1, K)
+    d["encoder.pos_conv_embed.conv.parametrizations.weight.original1"] = (C, C // G, K)
+    d["encoder.layer_norm.weight"] = (C,)
+    d["encoder.layer_norm.bias"] = (C,)
+    for l in range(c["n_layer"]):
+        p = f"encoder.layers.{l}."
+        d[p + "attention.gru_rel_pos_const"] = (1, H, 1, 1)
+        for n in ("k_proj", "v_proj", "q_proj", "out_proj"):
+            d[p + f"attention.{n}.weight"] = (C, C)
+            d[p + f"attention.{n}.bias"] = (C,)
+        d[p + "attention.gru_rel_pos_linear.weight"] = (8, C // H)
+        d[p + "attention.gru_rel_pos_linear.bias"] = (8,)
+        if l == 0:
+            d[p + "attention.rel_attn_embed.weight"] = (NB, H)
+        d[p + "layer_norm.weight"] = (C,)
+        d[p + "layer_norm.bias"] = (C,)
+        d[p + "feed_forward.intermediate_dense.weight"] = (F, C)
+        d[p + "feed_forward.intermediate_dense.bias"] = (F,)
+        d[p + "feed_forward.output_dense.weight"] = (C, F)
+        d[p + "feed_forward.output_dense.bias"] = (C,)
+        d[p + "final_layer_norm.weight"] = (C,)
+        d[p + "final_layer_norm.bias"] = (C,)
+    return d
+
+
+def wavlm_init_state(cfg=None, seed=0, init_weights=None):
+    """Build-owned seeded weights in transformers' names (no checkpoint ships), every stage at a scale of order 1 as in w2v_init_state: the
+    feature extractor's convolutions get He's bound sqrt(6 / fan_in), the positional convolution's per-tap norms g lie in [1.5, 3), q_proj and
+    k_proj 1.7 times the default bound (attention logits of standard deviation ~3), every norm gain in [0.8, 1.2) and bias in [-0.1, 0.1).
+    The relative position bias gets enough weight to matter next to those logits: rel_attn_embed uniform in [-2, 2), gru_rel_pos_linear twice
+    the default bound (the two sigmoid arguments have standard deviation ~2.3, so the gate covers most of (1, 2)), gru_rel_pos_const in
+    [0.5, 1.5) where the model initialises it to 1; the rest by lds.init_weights' role rules."""
+    if init_weights is None:
+        from . import init_weights
+    import numpy as np
+    shapes = wavlm_param_shapes(cfg)
+    st = init_weights.init_state(shapes, seed)
+    for k, shp in shapes.items():
+        fan = int(np.prod(shp[1:])) if len(shp) > 1 else 1
+        if "layer_norm." in k:
+            st[k] = init_weights.uniform(k, shp, seed, 0.8, 1.2) if k.endswith(".weight") else init_weights.uniform(k, shp, seed, -0.1, 0.1)
+        elif k.startswith("feature_extractor.conv_layers.") and k.endswith("conv.weight"):
+            b = float(np.sqrt(6.0 / fan))
+            st[k] = init_weights.uniform(k, shp, seed, -b, b)
+        elif k.endswith("weight.original0"):
+            st[k] = init_weights.uniform(k, shp, seed, 1.5, 3.0)
+        elif k.endswith("q_proj.weight") or k.endswith("k_proj.weight"):
+            b = float(1.7 / np.sqrt(fan))
+            st[k] = init_weights.uniform(k, shp, seed, -b, b)
+        elif k.endswith("rel_attn_embed.weight"):
+            st[k] = init_weights.uniform(k, shp, seed, -2.0, 2.0)
+        elif k.endswith("gru_rel_pos_linear.weight"):
+            b = float(2.0 / np.sqrt(fan))
+            st[k] = init_weights.uniform(k, shp, seed, -b, b)
+        elif k.endswith("gru_rel_pos_const"):
+            st[k] = init_weights.uniform(k, shp, seed, 0.5, 1.5)
+    return OrderedDict((k, np.ascontiguousarray(v, dtype=np.float32)) for k, v in st.items())
+
+
+def wavlm_convert_state(state, cfg=None):
+    """A checkpoint's state dict in transformers naming (an optional "module." / "wavlm." prefix removed, masked_spec_embed and the task
+    heads dropped) -> the tensors of wavlm_param_shapes(cfg).  A missing tensor is a KeyError naming it; a wrong shape a ValueError."""
+    shapes = wavlm_param_shapes(cfg)
+    got = {}
+    for k, v in state.items():
+        for pre in ("module.", "wavlm."):
+            if k.startswith(pre):
+                k = k[len(pre):]
+        if k.startswith(WAVLM_IGNORED_PREFIXES):
+            continue
+        if k in shapes:
+            got[k] = v
+    out = OrderedDict()
+    for k, shp in shapes.items():
+        if k not in got:
+            raise KeyError(f"WavLM checkpoint lacks {k!r}")
+        if tuple(got[k].shape) != tuple(shp):
+            raise ValueError(f"WavLM checkpoint: {k!r} has shape {tuple(got[k].shape)}, expected {tuple(shp)}")
+        out[k] = got[k]
+    return out
+
+
+def wavlm_buckets(num_buckets, max_distance, n):
+    """WavLMAttention._relative_positions_bucket of the distances -(n - 1) .. n - 1 (key minus query) -> int64 [2 n - 1], the logarithm
+    branch in float32 as torch runs it (what lds_wavlm_create builds its bias table from; tests hold the library's table against this)"""
+    import numpy as np
+    nb, d = num_buckets // 2, np.arange(-(n - 1), n, dtype=np.int64)
+    me, a = nb // 2, np.abs(d)
+    x = np.log(np.maximum(a, 1).astype(np.float32) / np.float32(me)) / np.float32(np.log(max_distance / me))      # (|d| = 0 takes the small branch)
+    big = np.minimum((np.float32(me) + x.astype(np.float32) * np.float32(nb - me)).astype(np.int64), nb - 1)
+    return (d > 0) * nb + np.where(a < me, a, big)
 
 
 RESAMPLE_MAX_RATE, RESAMPLE_MAX_TAPS, RESAMPLE_MAX_BANK = 384000, 1024, 1 << 24      # include/lds.h lds_resample

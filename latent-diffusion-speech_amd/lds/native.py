@@ -119,6 +119,11 @@ lds_w2v_destroy                  v:p
 lds_w2v_workspace_bytes          i:piqp
 lds_w2v_features                 i:pppppziqp
 lds_w2v_encode                   i:pppppziqp
+lds_wavlm_create                 i:pipppp
+lds_wavlm_destroy                v:p
+lds_wavlm_workspace_bytes        i:piqp
+lds_wavlm_features               i:ppppipziqp
+lds_wavlm_encode                 i:ppppiipziqp
 lds_w2vbert_create               i:pipppp
 lds_w2vbert_destroy              v:p
 lds_w2vbert_workspace_bytes      i:piqp
@@ -224,6 +229,8 @@ lds_test_w2v_ln_act              i:ppppfppiiip
 lds_test_w2vbert_fbank           i:pppiqp
 lds_test_w2vbert_attention       i:pppppiiiiiip
 lds_test_w2vbert_dwconv          i:ppppfpppiiiip
+lds_test_wavlm_attention         i:pppppiiiiip
+lds_test_wavlm_buckets           i:iiip
 lds_test_stft_dft                i:pppiiiippiqp
 lds_test_knn_search              i:pqppqiiiipppzp
 """
@@ -864,6 +871,57 @@ class Wav2Vec2(_UnitsEncoder):
 
     def encode(self, audio, lengths=None, ws=None):
         return self._call("lds_w2v_encode", audio, lengths, ws, lambda n, L: (n, self.dims["n_state"]))
+
+
+class WavlmCfg(C.Structure):
+    _fields_ = [(k, C.c_int) for k in ("conv_dim", "n_state", "n_head", "n_layer", "n_ffn", "pos_kernel", "pos_groups", "num_buckets", "max_distance",
+                                       "stable_layer_norm", "n_ctx")]
+
+
+class WavLM(_UnitsEncoder):
+    """WavLM units encoder (lds_wavlm_*): audio [B,L] at 16 kHz -> the feature extractor's output [B,T,conv_dim] / WavLMModel's
+    hidden_states[layer] [B,T,n_state] (layer None = last_hidden_state).  `state`: transformers-named tensors (lds.arch.wavlm_param_shapes).
+    `normalize`: every clip is set to zero mean and unit variance over its own samples first (WavLM-Large's feature extractor).  `lengths`:
+    every clip's own sample count (host ints, 400 .. L): each clip is encoded as if alone.  At most 64 clips per call.  Every limit of
+    include/lds.h is checked here first (ValueError, before a device is touched)."""
+    KIND = "wavlm"
+    FIELDS = ("conv_dim", "n_state", "n_head", "n_layer", "n_ffn", "pos_kernel", "pos_groups", "num_buckets", "max_distance", "stable_layer_norm", "n_ctx")
+    MAX_BATCH = 64
+
+    def __init__(self, dims, state):
+        d = {k: int(dims[k]) for k in self.FIELDS}
+        self.check_dims(d)
+        self._create_weights(WavlmCfg(*(d[k] for k in self.FIELDS)), state)
+        self.dims = d
+
+    @staticmethod
+    def check_dims(d):
+        _w2v_check_dims(d, ("n_ffn",))      # (the skeleton's limits are HuBERT's)
+        nb, md = d["num_buckets"], d["max_distance"]
+        if nb < 4 or nb % 4 or nb > 4096:
+            raise ValueError(f"WavLM: num_buckets {nb} must be a multiple of 4 in 4 .. 4096")
+        if not nb // 4 < md <= 1 << 20:
+            raise ValueError(f"WavLM: max_distance {md} outside num_buckets / 4 + 1 = {nb // 4 + 1} .. 2^20")
+        if d["stable_layer_norm"] not in (0, 1):
+            raise ValueError(f"WavLM: stable_layer_norm {d['stable_layer_norm']} (0 or 1)")
+
+    @staticmethod
+    def frames(n_samples):
+        from . import arch
+        return arch.wavlm_frames(n_samples)
+
+    def _units_of(self, n_samples, pad=0):
+        return self.frames(n_samples)
+
+    def features(self, audio, lengths=None, normalize=False, ws=None):
+        return self._call("lds_wavlm_features", audio, lengths, ws, lambda n, L: (n, self.dims["conv_dim"]), mid=(1 if normalize else 0,))
+
+    def encode(self, audio, lengths=None, layer=None, normalize=False, ws=None):
+        """layer: the blocks to run = the index into WavLMModel's hidden_states (None = all: last_hidden_state)"""
+        nl = self.dims["n_layer"] if layer is None else int(layer)
+        if not 0 <= nl <= self.dims["n_layer"]:
+            raise ValueError(f"WavLM: layer {nl} outside 0 .. {self.dims['n_layer']}")
+        return self._call("lds_wavlm_encode", audio, lengths, ws, lambda n, L: (n, self.dims["n_state"]), mid=(nl, 1 if normalize else 0))
 
 
 class W2vBertCfg(C.Structure):

@@ -24,7 +24,8 @@ class DiffusionSVC:
         method does not accept; they are accepted and ignored here).  The reference builds its Units_Encoder here (infer_tools.py:31-38);
         this one only when `units_encoder_checkpoint` names the checkpoint of the encoder that args.data.encoder names: the Whisper
         encoder's (large-v3_encoder.pt; also when no encoder is named) or, for 'hubertsoft' / 'contentvec768l12', a HubertSoft state dict
-        (tools.tools.HubertUnits), or for 'xlsr_53_56k' a wav2vec 2.0 state dict of plain tensors (tools.tools.Audio2xlsr_53_56k).
+        (tools.tools.HubertUnits), or for 'xlsr_53_56k' a wav2vec 2.0 state dict of plain tensors (tools.tools.Audio2xlsr_53_56k), or for
+        'wavlmbase+' / 'wavlmlarge' the WavLM state dict in transformers naming (tools.tools.WavLMUnits).
         `resample` (keyword-only, not in the reference) goes to Units_Encoder: with True, encode_units resamples audio of another rate; `encoder` (keyword-only) overrides the name in args.data.encoder."""
         self.model_path = model_path
         self.model, self.vocoder, self.args = load_model_vocoder(model_path, device=self.device, loaded_vocoder=loaded_vocoder)
@@ -32,13 +33,15 @@ class DiffusionSVC:
         self.volume_extractor = Volume_Extractor(hop_size=512, block_size=self.args["data"]["block_size"],      # (reference infer_tools.py:39-43)
                                                  model_sampling_rate=self.args["data"]["sampling_rate"])
         if units_encoder_checkpoint is not None:
-            from tools.tools import Audio2xlsr_53_56k, HubertUnits, Units_Encoder, WhisperLargeV3
+            from tools.tools import Audio2xlsr_53_56k, HubertUnits, Units_Encoder, WavLMUnits, WhisperLargeV3
             data = getattr(self.args, "data", None)
             name = encoder if encoder is not None else getattr(data, "encoder", "whisper_large_v3")
             if name in HubertUnits.NAMES:
                 model = HubertUnits(name, device=self.device, checkpoint=units_encoder_checkpoint)
             elif name == "xlsr_53_56k":
                 model = Audio2xlsr_53_56k(device=self.device, checkpoint=units_encoder_checkpoint)
+            elif name in WavLMUnits.NAMES:
+                model = WavLMUnits(name, device=self.device, checkpoint=units_encoder_checkpoint)
             else:
                 model = WhisperLargeV3(device=self.device, checkpoint=units_encoder_checkpoint)
             self.units_encoder = Units_Encoder(name, getattr(data, "encoder_sample_rate", 16000),

@@ -1,7 +1,7 @@
 """The pieces of reference tools/tools.py that are built: the encoder-width table, `units_forced_alignment` (and its per-clip form
 `units_forced_alignment_ragged`), the units encoders (`Units_Encoder` over `WhisperLargeV3`, reference tools/tools.py:43-126, or over
 `HubertUnits`: the reference's encoder/hubert/model.py as 'hubertsoft' / 'contentvec768l12', or over `Audio2xlsr_53_56k`: wav2vec 2.0 XLSR-53,
-or over `Wav2Vec2Bert`: w2v-BERT 2.0),
+or over `Wav2Vec2Bert`: w2v-BERT 2.0, or over `WavLMUnits`: WavLM as 'wavlmbase+' / 'wavlmlarge'),
 `Volume_Extractor`, `upsample` and `cross_fade` (tools/tools.py:12-41, 225-238) and `Resample`, the torchaudio transform that file imports
 (tools/tools.py:9).  'w2v-bert' downloaded from the hub and 'xlsr_53_56k' loaded through fairseq (the reference's defaults) and the schedulers
 there are not built."""
@@ -13,6 +13,7 @@ import torch
 from encoder.hubert.model import HubertSoft
 from encoder.wav2vec2.model import Wav2Vec2, load_checkpoint_state
 from encoder.wav2vec2_bert.model import Wav2Vec2BertModel, load_checkpoint_state as load_w2vbert_checkpoint_state
+from encoder.wavlm.model import WavLM
 from encoder.whisper.model import ModelDimensions, Whisper
 from lds import arch, native
 from lds.arch import get_encoder_out_channels
@@ -162,7 +163,8 @@ class Units_Encoder:
     """Speech -> units (reference tools/tools.py:43-103).  Built: encoder 'whisper_large_v3' in the 'nearest' / 'left' modes, and the
     HuBERT stack (HubertUnits below) as 'hubertsoft' (256-wide soft units) and 'contentvec768l12' (its 768-wide last layer), and
     'xlsr_53_56k' (Audio2xlsr_53_56k below: wav2vec 2.0 XLSR-53, 1024-wide) and 'w2v-bert' (Wav2Vec2Bert below: w2v-BERT 2.0, 1024-wide),
-    each with `model=` or `checkpoint=`.  Frame counts and the shortest clip come from the model (`frames_of`, `min_samples`):
+    and 'wavlmbase+' / 'wavlmlarge' (WavLMUnits below: WavLM-Base+ 768-wide, WavLM-Large 1024-wide; `units_layer=` picks the hidden state,
+    default the last), each with `model=` or `checkpoint=`.  Frame counts and the shortest clip come from the model (`frames_of`, `min_samples`):
     (L // 160 - 1) // 2 + 1 and 400 samples for Whisper, L // 320 and 320 for HuBERT, the unpadded level rule (400 samples -> 1 frame) and
     400 for XLSR-53, ceil((1 + (L - 400) // 160) / 2) rows and 560 for w2v-BERT (whose last row is the reference's masked row when the
     frame count is odd: Wav2Vec2Bert's docstring).
@@ -173,13 +175,15 @@ class Units_Encoder:
         makes it (tools/tools.py:81-84), in encode, encode_ragged and the encode_tokens* forms;
       - the units stay on the device (the reference moves them to the CPU); CPU tensors raise, there is no CPU fallback;
       - 'w2v-bert' with neither `model=` nor `checkpoint=` is the reference's transformers hub download: NotImplementedError;
-        'xlsr_53_56k' with neither is the reference's fairseq load of pretrain/xlsr_53_56k.pt: NotImplementedError; the 'rfa441to512' /
-        'rfa512to441' modes need librosa's resampler: NotImplementedError.
+        'xlsr_53_56k' with neither is the reference's fairseq load of pretrain/xlsr_53_56k.pt: NotImplementedError;
+        'wavlmbase+' / 'wavlmlarge' with neither would be a hub download too: NotImplementedError; the 'rfa441to512' / 'rfa512to441' modes
+        need librosa's resampler: NotImplementedError.
     `model` (not in the reference): a ready WhisperLargeV3 / HubertUnits / Audio2xlsr_53_56k / Wav2Vec2Bert, e.g.
     WhisperLargeV3.synthetic(...), instead of the checkpoint; `checkpoint` (keyword-only, not in the reference): the file a HuBERT, XLSR-53
     or w2v-BERT encoder loads its state dict from."""
 
-    def __init__(self, encoder, encoder_sample_rate=16000, encoder_hop_size=320, device=None, units_forced_mode='nearest', *, model=None, resample=False, checkpoint=None):
+    def __init__(self, encoder, encoder_sample_rate=16000, encoder_hop_size=320, device=None, units_forced_mode='nearest', *, model=None, resample=False, checkpoint=None,
+                 units_layer=None):
         if device is None:
             device = 'cuda' if torch.cuda.is_available() else 'cpu'
         self.device = device
@@ -193,12 +197,21 @@ class Units_Encoder:
         if encoder == 'xlsr_53_56k' and model is None and checkpoint is None:
             raise NotImplementedError("Units_Encoder: 'xlsr_53_56k' by default loads pretrain/xlsr_53_56k.pt through fairseq, which is not built; "
                                       "pass checkpoint=PATH (a state dict of plain tensors, fairseq or transformers naming) or model=")
-        if encoder not in ('whisper_large_v3', 'xlsr_53_56k', 'w2v-bert') + HubertUnits.NAMES:
+        if encoder in WavLMUnits.NAMES and model is None and checkpoint is None:
+            raise NotImplementedError(f"Units_Encoder: {encoder!r} without local weights would be a hub download (microsoft/wavlm-*), which is not "
+                                      "built; pass checkpoint=PATH (the state dict in transformers naming, torch-saved or .safetensors) or model=")
+        if units_layer is not None and encoder not in WavLMUnits.NAMES:
+            raise ValueError(f"Units_Encoder: units_layer= belongs to {WavLMUnits.NAMES}, not to {encoder!r}")
+        if encoder not in ('whisper_large_v3', 'xlsr_53_56k', 'w2v-bert') + HubertUnits.NAMES + WavLMUnits.NAMES:
             raise ValueError(f"[x] Unknown units encoder: {encoder}")
         if units_forced_mode in ('rfa441to512', 'rfa512to441'):
             raise NotImplementedError(f"units_forced_mode {units_forced_mode!r} resamples with librosa; not built")
         if model is not None:
             self.model = model
+            if units_layer is not None:
+                self.model.set_units_layer(units_layer)
+        elif encoder in WavLMUnits.NAMES:
+            self.model = WavLMUnits(encoder, device=device, checkpoint=checkpoint, units_layer=units_layer)
         elif encoder in HubertUnits.NAMES:
             if checkpoint is None:
                 raise ValueError(f"Units_Encoder: {encoder!r} needs checkpoint=PATH (a local state dict; nothing is downloaded) or model=")
@@ -435,6 +448,72 @@ class Wav2Vec2Bert(torch.nn.Module):
         if not audio.is_cuda:
             raise RuntimeError("Wav2Vec2Bert.encode_ragged needs the audio on a HIP device (no CPU fallback)")
         units = self.model.native().encode(audio.float().contiguous(), ln)
+        return units, torch.from_numpy(np.array([self.frames_of(int(n)) for n in ln], dtype=np.int64))
+
+
+class WavLMUnits(torch.nn.Module):
+    """WavLM (encoder.wavlm.model.WavLM) in the role WhisperLargeV3 plays for Units_Encoder.  `name`: 'wavlmbase+' -> WavLM-Base+ (768 wide,
+    the waveform as it is: so-vits-svc's encoder), 'wavlmlarge' -> WavLM-Large (1024 wide, every clip normalised to zero mean and unit
+    variance first, as its feature extractor does: kNN-VC's encoder).  units = hidden_states[units_layer], default the last layer (kNN-VC:
+    units_layer=6).  `checkpoint`: a local file holding the state dict in transformers naming (torch-saved plain tensors, or .safetensors),
+    or `dims` + `state` (keyword-only) inject the weights directly.  Nothing is downloaded."""
+    NAMES = ('wavlmbase+', 'wavlmlarge')
+    min_samples = arch.WAVLM_MIN_SAMPLES
+    family = "WavLM"
+
+    def __init__(self, name='wavlmbase+', device='cuda', checkpoint=None, *, dims=None, state=None, units_layer=None):
+        super().__init__()
+        if name not in self.NAMES:
+            raise ValueError(f"[x] Unknown units encoder: {name}")
+        self.name, self.device = name, device
+        if dims is None:
+            dims = arch.wavlm_dims("large" if name == 'wavlmlarge' else "base+")
+        if state is None:
+            if checkpoint is None:
+                raise NotImplementedError(f"WavLMUnits: {name!r} without local weights would be a hub download, which is not built; pass "
+                                          "checkpoint=PATH or dims= / state=")
+            print(name)
+            self.model = WavLM(dims, checkpoint=checkpoint, normalize=name == 'wavlmlarge')
+        else:
+            self.model = WavLM(dims, state=state, normalize=name == 'wavlmlarge')
+        self.hidden_dim = self.model.dims["n_state"]
+        self.n_ctx = self.model.dims["n_ctx"]      # the window of one call, in frames
+        self.set_units_layer(units_layer)
+
+    def set_units_layer(self, units_layer):
+        n = self.model.dims["n_layer"]
+        self.units_layer = n if units_layer is None else int(units_layer)
+        if not 0 <= self.units_layer <= n:
+            raise ValueError(f"WavLMUnits: units_layer {units_layer} outside 0 .. {n}")
+
+    @classmethod
+    def synthetic(cls, name='wavlmbase+', dims=None, seed=0, device='cuda', units_layer=None):
+        """seeded weights (lds.arch.wavlm_init_state) for `dims` (default: the named model's) -- no checkpoint ships"""
+        dims = dict(arch.wavlm_dims("large" if name == 'wavlmlarge' else "base+") if dims is None else dims)
+        return cls(name, device=device, dims=dims, state=arch.wavlm_init_state(dims, seed), units_layer=units_layer)
+
+    @staticmethod
+    def frames_of(n_samples):
+        return arch.wavlm_frames(n_samples)
+
+    @torch.inference_mode()
+    def __call__(self, audio, padding_mask=None):
+        """audio (any shape, flattened into ONE clip) -> units [T, C] on the device; padding_mask is ignored as WhisperLargeV3 ignores it"""
+        if not torch.is_tensor(audio) or not audio.is_cuda:
+            raise RuntimeError("WavLMUnits needs the audio as a tensor on a HIP device (no CPU fallback)")
+        return self.model.encode(audio.reshape(1, -1), layer=self.units_layer).squeeze(0)
+
+    encode = __call__
+
+    @torch.inference_mode()
+    def encode_ragged(self, audio, lengths):
+        if audio.dim() != 2:
+            raise ValueError(f"WavLMUnits.encode_ragged: audio must be [B, L], got {list(audio.shape)}")
+        B, L = audio.shape
+        ln = native.WavLM.lengths(lengths, B, L)      # (host-side validation first: a bad length is a ValueError on any device)
+        if not audio.is_cuda:
+            raise RuntimeError("WavLMUnits.encode_ragged needs the audio on a HIP device (no CPU fallback)")
+        units = self.model.encode(audio, ln, layer=self.units_layer)
         return units, torch.from_numpy(np.array([self.frames_of(int(n)) for n in ln], dtype=np.int64))
 
 

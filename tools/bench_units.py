@@ -4,6 +4,10 @@ rounds; one JSON line.  `--stages` adds the per-launch split of one B = 8 encode
 included.  `--layers N` runs a shallower stack (the per-layer cost is constant; the FLOP count follows).
 
     python tools/bench_units.py [--iters 3] [--warmup 1] [--rounds 3] [--layers 32] [--stages]
+    python tools/bench_units.py --encoder wavlmbase+ | wavlmlarge | contentvec768l12 [--layers N] [--stages]
+--encoder wavlmbase+ / wavlmlarge times the WavLM encoder instead (B = 8 and B = 1 clips of 30 s, seeded weights) and, in the same process and
+in alternating rounds, the HuBERT-base stack (contentvec768l12: WavLM-Base+'s size without the gated position bias) on the same audio; the
+difference is the price of the gate and the bias.  --encoder contentvec768l12 times that stack alone.
 The per-kernel table comes from a rocprofv3 --kernel-trace --stats run of this script on its own (the front end's kernels are
 logmel_power_kernel and logmel_finish_kernel)."""
 import argparse
@@ -40,14 +44,76 @@ def timed(fn, iters):
     return e0.elapsed_time(e1) / iters
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
+    ap.add_argument("--encoder", default="whisper_large_v3", choices=("whisper_large_v3", "contentvec768l12", "wavlmbase+", "wavlmlarge"))
     ap.add_argument("--iters", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--rounds", type=int, default=3)
-    ap.add_argument("--layers", type=int, default=32)
+    ap.add_argument("--layers", type=int, default=None, help="default: the model's own depth (32 / 12 / 12 / 24)")
     ap.add_argument("--stages", action="store_true")
-    a = ap.parse_args()
+    return ap.parse_args(argv)
+
+
+def print_stages(title, fn):
+    native.prof_enable(2)
+    fn()
+    torch.cuda.synchronize()
+    prof = native.prof_summary()
+    native.prof_enable(0)
+    tot = sum(r["ms"] for r in prof)
+    print(f"{title}, profiled: {tot:.2f} ms", file=sys.stderr)
+    for r in sorted(prof, key=lambda r: -r["ms"]):
+        tf = r["flops"] / (r["ms"] * 1e-3) / 1e12 if r["flops"] else 0
+        print(f"{r['name']:80s} n={r['count']:3d} {r['ms']:8.3f} ms {100 * r['ms'] / tot:5.1f}% {tf:6.1f} TF", file=sys.stderr)
+
+
+def bench_conv_stack(a):
+    """WavLM and / or the HuBERT-base stack on 8 clips and one clip of 30 s"""
+    L = 480000
+    audio = torch.from_numpy(init_weights.uniform("bench.units.audio", (8, L), 5, -0.5, 0.5)).cuda()
+    legs = {}
+    if a.encoder != "contentvec768l12":
+        dims = arch.wavlm_dims("large" if a.encoder == "wavlmlarge" else "base+")
+        dims["n_layer"] = a.layers or dims["n_layer"]
+        w = native.WavLM(dims, arch.wavlm_init_state(dims, 0))
+        norm = a.encoder == "wavlmlarge"
+        legs["wavlm_b8"] = lambda: w.encode(audio, normalize=norm)
+        legs["wavlm_b1"] = lambda: w.encode(audio[:1], normalize=norm)
+    if a.encoder != "wavlmlarge":
+        hd = dict(arch.HUBERT_BASE_DIMS, n_layer=a.layers or 12)
+        hb = native.Hubert(hd, arch.hubert_init_state(hd, 0))
+        legs["hubert_b8"] = lambda: hb.encode(audio, pad=0)
+        legs["hubert_b1"] = lambda: hb.encode(audio[:1], pad=0)
+    for _ in range(a.warmup):
+        for fn in legs.values():
+            fn()
+    torch.cuda.synchronize()
+    t = {k: [] for k in legs}
+    for _ in range(a.rounds):      # alternating: every leg sees the same clocks and the same neighbours
+        for k, fn in legs.items():
+            t[k].append(timed(fn, a.iters))
+    ms = {k: min(v) for k, v in t.items()}
+    if a.stages:
+        for k in ("wavlm_b8", "hubert_b8"):
+            if k in legs:
+                print_stages(k, legs[k])
+    own = 24 if a.encoder == "wavlmlarge" else 12
+    out = {"encoder": a.encoder, "layers": a.layers or own, "frames": arch.wavlm_frames(L), **{k + "_ms": round(v, 3) for k, v in ms.items()},
+           "rounds_ms": {k: [round(x, 3) for x in v] for k, v in t.items()}}
+    if "wavlm_b8" in ms and "hubert_b8" in ms:
+        nl = a.layers or 12
+        out["gate_bias_ms_per_layer_b8"] = round((ms["wavlm_b8"] - ms["hubert_b8"]) / nl, 4)
+        out["gate_bias_ms_per_layer_b1"] = round((ms["wavlm_b1"] - ms["hubert_b1"]) / nl, 4)
+        out["wavlm_over_hubert_b8"] = round(ms["wavlm_b8"] / ms["hubert_b8"], 4)
+    print(json.dumps(out))
+
+
+def main():
+    a = parse_args()
+    if a.encoder != "whisper_large_v3":
+        return bench_conv_stack(a)
+    a.layers = a.layers or 32
     h = native.Whisper(N_MELS, C, HEADS, a.layers, N_CTX, arch.whisper_init_state(N_MELS, C, a.layers, 0), arch.whisper_mel_filters(N_MELS))
     L = 480000
     audio = torch.from_numpy(init_weights.uniform("bench.units.audio", (8, L), 5, -0.5, 0.5)).cuda()
@@ -68,16 +134,7 @@ def main():
     ms = {k: min(v) for k, v in t.items()}
     f1, f8, fr = flop(L, a.layers), 8 * flop(L, a.layers), sum(flop(n, a.layers) for n in lens)
     if a.stages:
-        native.prof_enable(2)
-        b8()
-        torch.cuda.synchronize()
-        prof = native.prof_summary()
-        native.prof_enable(0)
-        tot = sum(r["ms"] for r in prof)
-        print(f"B = 8 encode, profiled: {tot:.2f} ms", file=sys.stderr)
-        for r in sorted(prof, key=lambda r: -r["ms"]):
-            tf = r["flops"] / (r["ms"] * 1e-3) / 1e12 if r["flops"] else 0
-            print(f"{r['name']:80s} n={r['count']:3d} {r['ms']:8.3f} ms {100 * r['ms'] / tot:5.1f}% {tf:6.1f} TF", file=sys.stderr)
+        print_stages("B = 8 encode", b8)
     print(json.dumps({
         "layers": a.layers, "b1_ms": round(ms["b1"], 3), "b8_ms": round(ms["b8"], 3), "ragged8_ms": round(ms["rag"], 3), "per_clip8_ms": round(ms["seq"], 3),
         "logmel8_ms": round(ms["mel8"], 3), "front_end_share_b8": round(ms["mel8"] / ms["b8"], 4),

@@ -1,7 +1,7 @@
 """Encode clips to units with Whisper large-v3 (default) or a HuBERT encoder (the reference's 10_preprocess_train_unit.py flow; the counterpart of tools/extract_latents.py).
 
     python tools/extract_units.py IN [--out DIR] [--checkpoint pretrain/large-v3_encoder.pt | --synthetic [--layers N] [--seed S]] [--batch 8]
-                                     [--sample-rate R] [--encoder {whisper_large_v3,hubertsoft,contentvec768l12,xlsr_53_56k,w2v-bert}]
+                                     [--sample-rate R] [--encoder {whisper_large_v3,hubertsoft,contentvec768l12,xlsr_53_56k,w2v-bert,wavlmbase+,wavlmlarge}] [--units_layer N]
 
 IN is a directory (every .npy / .wav in it, sorted) or a text file listing one clip per line.  A .npy holds 1-D float32 samples at
 --sample-rate (default 16000); a .wav is PCM16 of any rate, read from its header (mono, or the first channel is taken).  Clips that
@@ -32,7 +32,7 @@ import torch  # noqa: E402
 
 from encoder.whisper.model import ModelDimensions  # noqa: E402
 from lds import arch  # noqa: E402
-from tools.tools import Audio2xlsr_53_56k, HubertUnits, Resample, Units_Encoder, Wav2Vec2Bert, WhisperLargeV3  # noqa: E402
+from tools.tools import Audio2xlsr_53_56k, HubertUnits, Resample, Units_Encoder, WavLMUnits, Wav2Vec2Bert, WhisperLargeV3  # noqa: E402
 
 ENCODER_RATE = 16000
 _resamplers = {}
@@ -76,18 +76,26 @@ def encoder_batch(clips, min_samples=400):
     return audio, lens
 
 
-def main():
+def build_parser():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("inp", help="directory of .npy / .wav clips, or a text file listing them")
     ap.add_argument("--out", default=None)
-    ap.add_argument("--encoder", default="whisper_large_v3", choices=("whisper_large_v3",) + HubertUnits.NAMES + ("xlsr_53_56k", "w2v-bert"))
+    ap.add_argument("--encoder", default="whisper_large_v3", choices=("whisper_large_v3",) + HubertUnits.NAMES + ("xlsr_53_56k", "w2v-bert") + WavLMUnits.NAMES)
     ap.add_argument("--checkpoint", default=None, help="default: pretrain/large-v3_encoder.pt for whisper_large_v3; required for a HuBERT encoder")
     ap.add_argument("--synthetic", action="store_true", help="seeded weights instead of the checkpoint")
-    ap.add_argument("--layers", type=int, default=None, help="depth of the --synthetic model (default 32; 12 for a HuBERT encoder, 24 for xlsr_53_56k and w2v-bert)")
+    ap.add_argument("--layers", type=int, default=None, help="depth of the --synthetic model (default 32; 12 for a HuBERT encoder, 24 for xlsr_53_56k, w2v-bert and wavlmlarge, 12 for wavlmbase+)")
+    ap.add_argument("--units_layer", type=int, default=None, help="WavLM: the hidden state to store, 0 .. depth (default: the last layer; kNN-VC uses 6 of WavLM-Large)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--sample-rate", type=int, default=ENCODER_RATE, help="rate of the .npy clips (a .wav carries its own)")
+    return ap
+
+
+def main():
+    ap = build_parser()
     a = ap.parse_args()
+    if a.units_layer is not None and a.encoder not in WavLMUnits.NAMES:
+        ap.error("--units_layer belongs to the WavLM encoders")
     if os.path.isdir(a.inp):
         base = a.inp
         paths = [os.path.join(a.inp, f) for f in sorted(os.listdir(a.inp)) if f.endswith((".npy", ".wav"))]
@@ -117,6 +125,14 @@ def main():
             ap.error("--encoder w2v-bert needs --checkpoint (the model's state dict in transformers naming) or --synthetic")
         else:
             model = Wav2Vec2Bert(device="cuda", checkpoint=a.checkpoint)
+    elif a.encoder in WavLMUnits.NAMES:
+        if a.synthetic:
+            dims = arch.wavlm_dims("large" if a.encoder == "wavlmlarge" else "base+")
+            model = WavLMUnits.synthetic(a.encoder, dict(dims, n_layer=a.layers or dims["n_layer"]), seed=a.seed, device="cuda", units_layer=a.units_layer)
+        elif a.checkpoint is None:
+            ap.error(f"--encoder {a.encoder} needs --checkpoint (the model's state dict in transformers naming) or --synthetic")
+        else:
+            model = WavLMUnits(a.encoder, device="cuda", checkpoint=a.checkpoint, units_layer=a.units_layer)
     elif a.synthetic:
         model = WhisperLargeV3.synthetic(ModelDimensions(**dict(arch.WHISPER_LARGE_V3_DIMS, n_audio_layer=a.layers or 32)), seed=a.seed, device="cuda")
     else:
