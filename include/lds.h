@@ -652,6 +652,45 @@ int lds_knn_retrieve(const float* X, int64_t N, const float* P, const float* h, 
 int lds_knn_retrieve_ragged(const float* X, int B, int T, const int32_t* lengths, const float* P, const float* h, int64_t M, int D, int k,
                             float ratio, float* Y, int32_t* idx, float* dist, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- units retrieval through an IVF coarse index: probe nprobe lists, not the pool (csrc/knn.hip) ------------------
+ * What faiss IndexIVFFlat is to the RVC / Diffusion-SVC tool chains (index.nprobe = 1 .. 16 there; IndexIVFFlat::train / add build the
+ * lists, IndexIVFFlat::search probes them): the pool's rows are grouped by their nearest coarse centre and a query is scored against the
+ * rows of its nprobe best centres only.  Each entry takes the arguments of its lds_knn_* counterpart and adds the index:
+ *   C dev [nlist][D], hc dev [nlist] = lds_knn_prepare(C): the coarse centres, 1 <= nlist <= 65,536 (lds_kmeans_assign's codebook limit;
+ *     pool row m belongs to the list lds_kmeans_assign gives it).  faiss: the quantizer of IndexIVFFlat.
+ *   offsets dev int64 [nlist + 1], order dev int32 [M]: list l holds the pool rows order[offsets[l] .. offsets[l + 1]), in ascending original
+ *     index; offsets[0] = 0, offsets[nlist] = M.  faiss: the inverted lists' ids.
+ *   PL dev [copy_rows][D], hl dev [copy_rows]: the pool and its h in list order, every list padded to whole 128-row blocks (list l starts
+ *     at row 128 sum_{j < l} ceil(len_j / 128); what the padding rows hold does not matter), copy_rows = 128 sum_l ceil(len_l / 128): at
+ *     most M + 127 nlist rows, one more pool.  faiss: the inverted lists' codes.  The original P stays: the blend reads it by original index.
+ *   nprobe in 1 .. min(8, nlist).
+ * A query's probed lists are lds_knn_search(X, C, hc, k = nprobe), its candidates the rows of those lists, its result the k best candidates
+ * by lds_knn_search's score and order (every score is the same fmaf chain as there), the lower ORIGINAL index first among equal scores;
+ * indices are original pool indices.  A query with fewer than k candidates gets -1 / -inf in the missing places of the search; the blend
+ * gives such places the weight 0 and normalises over the ones found.  Distances, weights, blend and the ragged form are lds_knn_retrieve's.
+ * lds_ivf_search does not read P and h (they may be NULL); lds_ivf_retrieve* do not read h.
+ * Limits as for lds_knn_* (LDS_EINVAL with a message before anything is enqueued), and: nlist <= M; copy_rows a multiple of 128 in
+ * M .. M + 127 nlist; N D 4 <= 2,147,418,112 bytes (the gathered query operand sits behind one buffer descriptor: split longer inputs);
+ * C and PL 16-byte aligned.  A workspace smaller than lds_ivf_workspace_bytes gives LDS_ENOMEM naming the size.  On the device the offsets
+ * are checked (start at 0, never decrease, end at M, and pad to exactly copy_rows rows): a table that fails gives every query -1
+ * everywhere; every value read from `order` is clamped into [0, M) -- nothing a corrupt table holds leads outside the buffers.  The (query,
+ * list) pairs are grouped by list with integer atomics; no result depends on the slot a pair lands in, there are no floating-point atomics
+ * and every call is bit-identical on repeat.  The contents of the workspace on entry do not matter.  Nothing synchronises.  A long list is
+ * walked in up to 8 block ranges by separate workgroups; the workspace holds 8 nprobe result lists per query. */
+int lds_ivf_workspace_bytes(int64_t N, int64_t M, int D, int k, int nlist, int nprobe, size_t* out);
+/* replaces IndexIVFFlat::search */
+int lds_ivf_search(const float* X, int64_t N, const float* P, const float* h, int64_t M, int D, int k, const float* C, const float* hc, int nlist,
+                   const int64_t* offsets, const int32_t* order, const float* PL, const float* hl, int64_t copy_rows, int nprobe, int32_t* idx,
+                   float* score, void* ws, size_t ws_bytes, void* stream);
+/* replaces IndexIVFFlat::search + the tool chains' inverse-square weighting of the rows it returns */
+int lds_ivf_retrieve(const float* X, int64_t N, const float* P, const float* h, int64_t M, int D, int k, const float* C, const float* hc, int nlist,
+                     const int64_t* offsets, const int32_t* order, const float* PL, const float* hl, int64_t copy_rows, int nprobe, float ratio,
+                     float* Y, int32_t* idx, float* dist, void* ws, size_t ws_bytes, void* stream);
+int lds_ivf_retrieve_ragged(const float* X, int B, int T, const int32_t* lengths, const float* P, const float* h, int64_t M, int D, int k,
+                            const float* C, const float* hc, int nlist, const int64_t* offsets, const int32_t* order, const float* PL,
+                            const float* hl, int64_t copy_rows, int nprobe, float ratio, float* Y, int32_t* idx, float* dist, void* ws,
+                            size_t ws_bytes, void* stream);
+
 /* ---- polyphase sinc resampler in front of the audio encoders (reference torchaudio.transforms.Resample(orig_freq, new_freq) with its
  *      defaults sinc_interp_hann / lowpass_filter_width 6 / rolloff 0.99, i.e. torchaudio's _get_sinc_resample_kernel +
  *      _apply_sinc_resample_kernel; called from tools/tools.py:78-84 Units_Encoder.encode, diffusion/vocoder.py:24-27 Vocoder.extract and

@@ -6,6 +6,7 @@ vocoder as ragged batches, and one kernel joins them under the volume mask.
     python infer_svc.py --synthetic -i in.wav -o out.wav          # seeded random weights (no checkpoints exist)
     python infer_svc.py --synthetic -o out.wav                    # ... and a generated recording of --synthetic_seconds
     python infer_svc.py ... --index units_index.pt --index_ratio 0.5 --index_k 8      # units retrieval over the target speaker's pool
+    python infer_svc.py ... --index units_index.pt --index_nprobe 8                   # ... through the file's IVF (train_units_index.py --nlist)
 """
 import argparse
 import os
@@ -43,6 +44,7 @@ def parse_args(argv=None):
                                     "before the diffusion model (units retrieval, exact and on the device)")
     ap.add_argument("--index_ratio", type=float, default=0.5, help="0 .. 1: the share of the retrieved units in the blend")
     ap.add_argument("--index_k", type=int, default=8, help="1 .. 8 nearest pool rows per frame")
+    ap.add_argument("--index_nprobe", type=int, default=None, help="1 .. 8: search only the rows of a frame's N best lists (an index written with --nlist)")
     ap.add_argument("--synthetic", action="store_true")
     ap.add_argument("--synthetic_width", type=int, default=1280, help="width of the synthetic units encoder (a multiple of 64)")
     ap.add_argument("--synthetic_layers", type=int, default=4)
@@ -147,7 +149,7 @@ def main(argv=None):
     torch.manual_seed(a.seed)
     wav, rate = svc.infer_from_long_audio(audio, sr=sr, spk_id=a.spk_id, infer_speedup=a.speedup, method=a.method, threhold=a.threhold,
                                           threhold_for_split=a.threhold_for_split, min_len=a.min_len, batch_size=a.batch_size, index=index,
-                                          index_ratio=a.index_ratio, index_k=a.index_k)
+                                          index_ratio=a.index_ratio, index_k=a.index_k, index_nprobe=a.index_nprobe)
     wav = wav.cpu().numpy()
     if a.output.endswith(".wav"):
         with wave.open(a.output, "wb") as f:

@@ -485,3 +485,496 @@ extern "C" int lds_test_knn_search(const float* X, int64_t N, const float* P, co
     if (splits < 1 || splits > kKnMaxSplits) return set_error(LDS_EINVAL, "lds_test_knn_search: splits %d outside 1 .. %d", splits, kKnMaxSplits);
     return kn_search("lds_test_knn_search", X, N, P, h, M, D, k, slab_rows, splits, idx, score, ws, ws_bytes, (hipStream_t)stream);
 }
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// IVF coarse index (faiss IndexIVFFlat's role in the RVC / Diffusion-SVC tool chains): probe nprobe lists, not the pool.
+//   index    coarse centres C [nlist][D]; pool row m belongs to the list of its best centre; offsets [nlist + 1] / order [M] give every
+//            list's rows in ascending original index; PL [Mp][D] is the pool in list order with every list padded to whole 128-row blocks
+//            (list l starts at block sum_{j < l} ceil(len_j / 128)), hl its h in the same order.  A block belongs to one list and, as the
+//            slabs are cut at whole blocks, to one slab.
+//   coarse   the exact search above over the centres with k = nprobe, unchanged: probe [N][nprobe].
+//   buckets  the N x nprobe (query, list) pairs grouped by list: count (integer atomics), one scan, fill (integer atomics).  The slot a
+//            pair lands in decides which tile column scores it, and a column's scores do not depend on the column: no result depends on it.
+//   scan     knn_topk_kernel's tile with the query operand GATHERED -- tile row i is the X row that bucket entry i names, by the per-lane
+//            source address of the LDS-DMA -- over the pool blocks of one list.  A workgroup takes one list and up to 128 of its bucket's
+//            queries; a list of more than kIvfSegBlocks blocks is cut into up to kIvfSegs block ranges ("segments"), each walked by workgroups
+//            of its own, so that the longest list is not one workgroup's serial walk.  List rows are numbered 0 .. len - 1 inside the kernel (ascending original index, so the insertion rule keeps the
+//            lower original index first) and translated through `order` on the way out: the lists go to the workspace as
+//            [probe slot * kIvfSegs + segment][N][KT] (empty where a list has fewer segments), the layout kn_merge reads with
+//            S = nprobe * kIvfSegs, and knn_select_kernel / knn_blend_kernel run as they are.
+// No floating-point atomics; every slot of the workspace that is read was written by the same call.
+// ---------------------------------------------------------------------------------------------------------------------------------
+namespace lds {
+
+constexpr int kIvfSegs = 8;          // the most block ranges a list is cut into
+constexpr int kIvfSegBlocks = 4;     // the fewest 128-row blocks in a range (but the last)
+
+// the blocks per segment of a list of nblk blocks, and its segments (1 for an empty list: its workgroups still write empty result lists)
+static __host__ __device__ __forceinline__ int ivf_seg_blocks(int nblk) {
+    const int per = (nblk + kIvfSegs - 1) / kIvfSegs;
+    return per > kIvfSegBlocks ? per : kIvfSegBlocks;
+}
+static __host__ __device__ __forceinline__ int ivf_segs(int nblk) {
+    const int n = (nblk + ivf_seg_blocks(nblk) - 1) / ivf_seg_blocks(nblk);
+    return n > 0 ? n : 1;
+}
+
+// one thread per (query, probe slot) pair: the list's count, or -- a slot without a list (a NaN query) -- the pair's empty result list
+__global__ void __launch_bounds__(256) ivf_count_kernel(const int* __restrict__ probe, long long pairs, long long N, int nprobe, int nlist, int KT,
+                                                        int* __restrict__ cnt, float* __restrict__ lval, int* __restrict__ lidx) {
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= pairs) return;
+    const int l = probe[t];
+    if (l >= 0 && l < nlist) {
+        atomicAdd(&cnt[l], 1);
+        return;
+    }
+    for (int g = 0; g < kIvfSegs; ++g) {
+        const long long o = (((t % nprobe) * kIvfSegs + g) * N + t / nprobe) * KT;
+        for (int p = 0; p < KT; ++p) { lval[o + p] = -INFINITY; lidx[o + p] = kKnNone; }
+    }
+}
+
+// One workgroup.  Checks the offsets table (starts at 0, never decreases, ends at M, and its lists padded to whole blocks fill exactly the
+// Mp rows of the copy); a table that fails gives every list the length 0, so that every query comes back without neighbours and no address
+// is formed from it.  Then three exclusive scans over the lists: pool blocks (lblk), bucket entries (bstart), workgroups of the scan (wstart:
+// one per 128 entries of a bucket and segment of the list); cnt is zeroed again to serve the fill as cursors.
+__global__ void __launch_bounds__(1024) ivf_plan_kernel(const long long* __restrict__ offsets, int nlist, long long M, long long Mp, int* __restrict__ cnt,
+                                                        int* __restrict__ llen, int* __restrict__ lrow, int* __restrict__ lblk,
+                                                        long long* __restrict__ bstart, int* __restrict__ wstart) {
+    __shared__ long long sa[1024], sb[1024], sc[1024];      // per thread: pool blocks, bucket entries, workgroups of its lists
+    __shared__ int bad;
+    const int t = threadIdx.x;
+    const int per = (nlist + 1023) / 1024;
+    const int l0 = t * per < nlist ? t * per : nlist, l1 = l0 + per < nlist ? l0 + per : nlist;
+    if (t == 0) bad = (offsets[0] != 0 || offsets[nlist] != M) ? 1 : 0;
+    __syncthreads();
+    long long a = 0, b = 0;
+    bool mybad = false;
+    for (int l = l0; l < l1; ++l) {
+        const long long o0 = offsets[l], o1 = offsets[l + 1];
+        if (o0 < 0 || o1 < o0 || o1 > M) mybad = true;
+        const long long len = mybad ? 0 : o1 - o0;
+        a += (len + kKnB - 1) / kKnB;
+        b += cnt[l];
+    }
+    if (mybad) bad = 1;
+    sa[t] = a; sb[t] = b;
+    __syncthreads();
+    if (t == 0) {
+        long long ra = 0, rb = 0;
+        for (int i = 0; i < 1024; ++i) {
+            const long long va = sa[i], vb = sb[i];
+            sa[i] = ra; sb[i] = rb;
+            ra += va; rb += vb;
+        }
+        if (ra * kKnB != Mp) bad = 1;
+        bstart[nlist] = rb;
+    }
+    __syncthreads();
+    const bool ok = bad == 0;      // known to all: the workgroups of a list depend on its length as it will be used
+    long long c = 0;
+    for (int l = l0; l < l1; ++l) {
+        const long long len = ok ? offsets[l + 1] - offsets[l] : 0;
+        c += (long long)((cnt[l] + kKnB - 1) / kKnB) * ivf_segs((int)((len + kKnB - 1) / kKnB));
+    }
+    sc[t] = c;
+    __syncthreads();
+    if (t == 0) {
+        long long rc = 0;
+        for (int i = 0; i < 1024; ++i) {
+            const long long vc = sc[i];
+            sc[i] = rc;
+            rc += vc;
+        }
+        wstart[nlist] = (int)rc;
+    }
+    __syncthreads();
+    a = sa[t]; b = sb[t]; c = sc[t];
+    for (int l = l0; l < l1; ++l) {
+        const long long o0 = offsets[l], o1 = offsets[l + 1];
+        const long long len = ok ? o1 - o0 : 0;
+        const int n = cnt[l];
+        llen[l] = (int)len;
+        lrow[l] = ok ? (int)o0 : 0;
+        lblk[l] = ok ? (int)a : 0;
+        bstart[l] = b;
+        wstart[l] = (int)c;
+        cnt[l] = 0;
+        a += (len + kKnB - 1) / kKnB;
+        b += n;
+        c += (long long)((n + kKnB - 1) / kKnB) * ivf_segs((int)((len + kKnB - 1) / kKnB));
+    }
+}
+
+// one thread per pair again: the pair takes the next slot of its list's bucket (which one does not matter to any result)
+__global__ void __launch_bounds__(256) ivf_fill_kernel(const int* __restrict__ probe, long long pairs, int nprobe, int nlist,
+                                                       const long long* __restrict__ bstart, int* __restrict__ cursor, long long* __restrict__ bq) {
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= pairs) return;
+    const int l = probe[t];
+    if (l < 0 || l >= nlist) return;
+    const int slot = atomicAdd(&cursor[l], 1);
+    bq[bstart[l] + slot] = (t / nprobe) * 8 + t % nprobe;      // query * 8 + probe slot
+}
+
+// knn_topk_kernel's tile, waves, LDS image, swizzle, MFMA order and lists; workgroup w takes entries chunk * 128 .. + 128 of list l's bucket
+// and segment seg of the list (wstart[l] <= w < wstart[l + 1], w - wstart[l] = chunk * segments + seg) and walks that segment's pool blocks in
+// PL; the workgroup of segment 0 also writes the empty lists of the segments the list does not have.  The X descriptor spans all of X
+// (N D 4 <= kKnOob bytes, checked by the driver) and a lane's offset is its bucket entry's row: the gather.  Tile columns beyond the bucket
+// repeat its last entry and are not stored; tile rows beyond the list's length score -inf and never enter a list.
+template <int KT>
+__global__ void __launch_bounds__(256) ivf_scan_kernel(const float* __restrict__ X, long long N, const float* __restrict__ PL, const float* __restrict__ hl,
+                                                       int Mp, int D, int slab_blocks, const int* __restrict__ order, int M,
+                                                       const int* __restrict__ llen, const int* __restrict__ lrow, const int* __restrict__ lblk,
+                                                       const long long* __restrict__ bstart, const int* __restrict__ wstart, int nlist,
+                                                       const long long* __restrict__ bq, float* __restrict__ lval, int* __restrict__ lidx) {
+    __shared__ __attribute__((aligned(16))) float smem[4 * kKnTile];      // 2 stages x (X tile, P tile) = 64 KB
+    const int w = blockIdx.x;
+    if (w >= wstart[nlist]) return;                                        // (the grid is the host's upper bound)
+    int l = 0;
+    for (int hi = nlist; l < hi;) {                                        // the first list whose workgroups end beyond w
+        const int mid = (l + hi) >> 1;
+        if (wstart[mid + 1] > w) hi = mid; else l = mid + 1;
+    }
+    const int len = llen[l], row0 = lrow[l];
+    const int nblk = (len + kKnB - 1) / kKnB, nseg = ivf_segs(nblk), segb = ivf_seg_blocks(nblk);
+    const int seg = (w - wstart[l]) % nseg;
+    const long long qbase = bstart[l] + (long long)((w - wstart[l]) / nseg) * kKnB;
+    const long long qleft = bstart[l + 1] - qbase;
+    const int cols = (int)(qleft < kKnB ? qleft : kKnB);                   // >= 1
+    const int lb0 = lblk[l];                                                // the list's first block: rows are numbered from it
+    const int pb0 = lb0 + seg * segb, pb1 = lb0 + ((seg + 1) * segb < nblk ? (seg + 1) * segb : nblk);
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int c = lane & 31, h = lane >> 5, wm = wave >> 1, wn = wave & 1;
+    const int nk = (D + kKnBK - 1) / kKnBK;
+    const int slab_rows = slab_blocks * kKnB;
+    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(X), 0, (int)(N * D * 4), 0x00020000);
+    int xoff[4], crow[4], kch[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int row = (wave * 4 + i) * 8 + (lane >> 3);
+        const int ch = (lane & 7) ^ ((row >> 1) & 7);
+        crow[i] = row;
+        kch[i] = ch * 4;
+        const long long q = bq[qbase + (row < cols ? row : cols - 1)] >> 3;      // columns beyond the bucket read its last query (not stored)
+        xoff[i] = (int)(q * D * 4) + ch * 16;
+    }
+    auto issue = [&](int pb, int ks, float* st) {
+        const int k0 = ks * kKnBK;
+        const bool tail = k0 + kKnBK > D;
+        const int slab = pb / slab_blocks;                                     // wave-uniform: the descriptor lives in scalar registers
+        const int r0 = slab * slab_rows;
+        const int srows = Mp - r0 < slab_rows ? Mp - r0 : slab_rows;
+        const __amdgpu_buffer_rsrc_t rp = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(PL + (long long)r0 * D), 0, srows * D * 4, 0x00020000);
+        const int b0 = pb * kKnB - r0;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            int pr = b0 + crow[i];
+            pr = pr < srows ? pr : srows - 1;
+            int vx = xoff[i], vp = pr * D * 4 + kch[i] * 4;
+            if (tail && k0 + kch[i] >= D) vx = vp = kKnOob;                     // d beyond D: zeros for both operands
+            float* dst = st + (wave * 4 + i) * 256;
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (__attribute__((address_space(3))) void*)dst, 16, vx, k0 * 4, 0, 0);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rp, (__attribute__((address_space(3))) void*)(dst + kKnTile), 16, vp, k0 * 4, 0, 0);
+        }
+    };
+    int pos[4];
+#pragma unroll
+    for (int g = 0; g < 4; ++g) pos[g] = ((2 * g + h) ^ ((c >> 1) & 7)) * 4;
+    f32x16 acc[2][2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    float lv[2][KT];
+    int li[2][KT];
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int p = 0; p < KT; ++p) { lv[j][p] = -INFINITY; li[j][p] = kKnNone; }
+
+    const int total = (pb1 - pb0) * nk;
+    int pb = pb0, ks = 0;           // the tile being computed
+    int ipb = pb0, iks = 0;         // the tile being fetched
+    if (total > 0) issue(ipb, iks, smem);
+    for (int s = 0; s < total; ++s) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();            // tile s has landed for everyone; everyone has finished reading tile s - 1
+        if (s + 1 < total) {
+            if (++iks == nk) { iks = 0; ++ipb; }
+            issue(ipb, iks, smem + ((s + 1) & 1) * 2 * kKnTile);
+        }
+        const float* xs = smem + (s & 1) * 2 * kKnTile + (wn * 64 + c) * kKnBK;
+        const float* ps = smem + (s & 1) * 2 * kKnTile + kKnTile + (wm * 64 + c) * kKnBK;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            f32x4 a[2], b[2];
+#pragma unroll
+            for (int i = 0; i < 2; ++i) a[i] = *reinterpret_cast<const f32x4*>(ps + i * 32 * kKnBK + pos[g]);
+#pragma unroll
+            for (int j = 0; j < 2; ++j) b[j] = *reinterpret_cast<const f32x4*>(xs + j * 32 * kKnBK + pos[g]);
+#pragma unroll
+            for (int jj = 0; jj < 4; ++jj)
+#pragma unroll
+                for (int i = 0; i < 2; ++i)
+#pragma unroll
+                    for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i][jj], b[j][jj], acc[i][j], 0, 0, 0);
+        }
+        if (++ks == nk) {           // a pool block is complete: scores into the lists, in increasing row of the list
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int t = wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;      // the row inside the block
+                    const int m = (pb - lb0) * kKnB + t;                                   // the row inside the list
+                    const float hv = m < len ? hl[(long long)pb * kKnB + t] : INFINITY;
+#pragma unroll
+                    for (int j = 0; j < 2; ++j) {
+                        const float v = acc[i][j][r] - hv;
+                        acc[i][j][r] = 0.f;
+                        if (v > lv[j][KT - 1]) {      // (a NaN score, or -inf beyond the list, never enters)
+#pragma unroll
+                            for (int p = KT - 1; p >= 0; --p) {
+                                const bool up = p > 0 && v > lv[j][p > 0 ? p - 1 : 0];
+                                const bool here = v > lv[j][p];
+                                lv[j][p] = up ? lv[j][p > 0 ? p - 1 : 0] : (here ? v : lv[j][p]);
+                                li[j][p] = up ? li[j][p > 0 ? p - 1 : 0] : (here ? m : li[j][p]);
+                            }
+                        }
+                    }
+                }
+            ks = 0;
+            ++pb;
+        }
+    }
+    __syncthreads();
+    // the four lists of a query (two wm waves x two half-waves) meet in LDS: [list q][entry p][query], 4 * KT * 128 values and as many indices
+    float* rv = smem;
+    int* ri = reinterpret_cast<int*>(smem + 4 * KT * kKnB);
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int p = 0; p < KT; ++p) {
+            rv[((wm * 2 + h) * KT + p) * kKnB + wn * 64 + j * 32 + c] = lv[j][p];
+            ri[((wm * 2 + h) * KT + p) * kKnB + wn * 64 + j * 32 + c] = li[j][p];
+        }
+    __syncthreads();
+    if (tid < cols) {
+        int at[4] = {0, 0, 0, 0};
+        const long long pair = bq[qbase + tid];
+        const long long o = (((pair & 7) * kIvfSegs + seg) * N + (pair >> 3)) * KT;
+        if (seg == 0)
+            for (int g = nseg; g < kIvfSegs; ++g) {
+                const long long e = (((pair & 7) * kIvfSegs + g) * N + (pair >> 3)) * KT;
+                for (int p = 0; p < KT; ++p) { lval[e + p] = -INFINITY; lidx[e + p] = kKnNone; }
+            }
+        for (int p = 0; p < KT; ++p) {
+            float bv = -INFINITY;
+            int bi = kKnNone, bq_ = 0;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int a = at[q] < KT ? at[q] : KT - 1;
+                const float v = at[q] < KT ? rv[(q * KT + a) * kKnB + tid] : -INFINITY;
+                const int i = at[q] < KT ? ri[(q * KT + a) * kKnB + tid] : kKnNone;
+                if (kn_before(v, i, bv, bi)) { bv = v; bi = i; bq_ = q; }
+            }
+#pragma unroll
+            for (int q = 0; q < 4; ++q) at[q] += (q == bq_ && bi != kKnNone) ? 1 : 0;
+            int oi = kKnNone;
+            if (bi != kKnNone) {      // the list's row -> the original pool index; both clamped before they are used
+                const int at_ = row0 + bi;
+                oi = order[at_ < M ? at_ : M - 1];
+                oi = oi < 0 ? 0 : (oi < M ? oi : M - 1);
+            }
+            lval[o + p] = bv;
+            lidx[o + p] = oi;
+        }
+    }
+}
+
+}  // namespace lds
+
+namespace {
+
+constexpr int kIvfMaxLists = 65536;
+
+struct IvfPlan {
+    KnPlan coarse;              // the exact search over the centres, k = nprobe
+    int KT, slab_blocks;
+    long long pairs;
+    unsigned wmax;              // an upper bound of the scan's workgroups: one per 128 bucket entries (rounded up per list) and segment
+    size_t o_probe, o_cnt, o_llen, o_lrow, o_lblk, o_bstart, o_wstart, o_bq, o_val, o_idx, bytes;
+};
+
+int ivf_check_dims(const char* fn, long long N, long long M, int D, int k, int nlist, int nprobe) {
+    if (int rc = kn_check_dims(fn, N, M, D, k)) return rc;
+    if (nlist < 1 || nlist > kIvfMaxLists || nlist > M) return set_error(LDS_EINVAL, "%s: nlist %d outside 1 .. min(65536, M = %lld)", fn, nlist, M);
+    if (nprobe < 1 || nprobe > lds::kKnMaxK || nprobe > nlist) return set_error(LDS_EINVAL, "%s: nprobe %d outside 1 .. min(8, nlist = %d)", fn, nprobe, nlist);
+    if (N * D * 4 > (long long)lds::kKnOob)
+        return set_error(LDS_EINVAL, "%s: N %lld rows of D %d exceed the %d bytes one descriptor of the gathered query operand holds", fn, N, D, lds::kKnOob);
+    return LDS_OK;
+}
+
+IvfPlan ivf_plan(long long N, int D, int k, int nlist, int nprobe, int slab_rows) {
+    IvfPlan p;
+    p.coarse = kn_plan(N, nlist, D, nprobe, 0, 0);
+    p.KT = k <= 1 ? 1 : k <= 2 ? 2 : k <= 4 ? 4 : 8;
+    p.slab_blocks = (slab_rows > 0 ? slab_rows : kn_slab_rows(D)) / lds::kKnB;
+    p.pairs = N * nprobe;
+    const long long full = p.pairs / lds::kKnB + nlist;
+    p.wmax = (unsigned)((full < p.pairs ? full : p.pairs) * lds::kIvfSegs);
+    size_t o = (p.coarse.bytes + 255) & ~(size_t)255;
+    auto take = [&](size_t n) { const size_t at = o; o += (n + 255) & ~(size_t)255; return at; };
+    p.o_probe = take((size_t)p.pairs * 4);
+    p.o_cnt = take((size_t)nlist * 4);
+    p.o_llen = take((size_t)nlist * 4);
+    p.o_lrow = take((size_t)nlist * 4);
+    p.o_lblk = take((size_t)nlist * 4);
+    p.o_bstart = take(((size_t)nlist + 1) * 8);
+    p.o_wstart = take(((size_t)nlist + 1) * 4);
+    p.o_bq = take((size_t)p.pairs * 8);
+    p.o_val = take((size_t)nprobe * lds::kIvfSegs * (size_t)N * p.KT * 4);
+    p.o_idx = take((size_t)nprobe * lds::kIvfSegs * (size_t)N * p.KT * 4);
+    p.bytes = o;
+    return p;
+}
+
+struct IvfIndex {               // the arguments every lds_ivf_* entry adds
+    const float *C, *hc;
+    int nlist;
+    const int64_t* offsets;
+    const int32_t* order;
+    const float *PL, *hl;
+    long long Mp;
+    int nprobe;
+};
+
+int ivf_check_index(const char* fn, const IvfIndex& ix, long long M) {
+    if (!ix.C || !ix.hc || !ix.offsets || !ix.order || !ix.PL || !ix.hl) return set_error(LDS_EINVAL, "%s: null pointer in the index", fn);
+    if (kn_misaligned(ix.C) || kn_misaligned(ix.PL)) return set_error(LDS_EINVAL, "%s: the centres and the list-ordered copy must be 16-byte aligned", fn);
+    if (ix.Mp < M || ix.Mp % lds::kKnB || ix.Mp > M + (long long)(lds::kKnB - 1) * ix.nlist)
+        return set_error(LDS_EINVAL, "%s: copy_rows %lld must be a multiple of 128 in M .. M + 127 nlist (M %lld, nlist %d)", fn, ix.Mp, M, ix.nlist);
+    return LDS_OK;
+}
+
+// coarse search, buckets and the list scan: the per-(query, probe slot, segment) lists [nprobe * kIvfSegs][N][KT] are in the workspace afterwards
+void ivf_lists(const IvfPlan& p, const float* X, long long N, long long M, int D, const IvfIndex& ix, void* ws, hipStream_t s) {
+    char* w = (char*)ws;
+    int* probe = (int*)(w + p.o_probe);
+    int* cnt = (int*)(w + p.o_cnt);
+    int *llen = (int*)(w + p.o_llen), *lrow = (int*)(w + p.o_lrow), *lblk = (int*)(w + p.o_lblk), *wstart = (int*)(w + p.o_wstart);
+    long long *bstart = (long long*)(w + p.o_bstart), *bq = (long long*)(w + p.o_bq);
+    float* lval = (float*)(w + p.o_val);
+    int* lidx = (int*)(w + p.o_idx);
+    {
+        float* cval = (float*)(w + p.coarse.o_val);
+        int* cidx = (int*)(w + p.coarse.o_idx);
+        kn_topk(p.coarse, X, N, ix.C, ix.hc, ix.nlist, D, cval, cidx, s);
+        hipLaunchKernelGGL(lds::knn_select_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, cval, cidx, p.coarse.S, p.coarse.KT, N, ix.nlist, ix.nprobe,
+                           probe, (float*)nullptr);
+    }
+    const dim3 pg((unsigned)((p.pairs + 255) / 256));
+    (void)hipMemsetAsync(cnt, 0, (size_t)ix.nlist * 4, s);
+    hipLaunchKernelGGL(lds::ivf_count_kernel, pg, dim3(256), 0, s, probe, p.pairs, N, ix.nprobe, ix.nlist, p.KT, cnt, lval, lidx);
+    hipLaunchKernelGGL(lds::ivf_plan_kernel, dim3(1), dim3(1024), 0, s, (const long long*)ix.offsets, ix.nlist, M, ix.Mp, cnt, llen, lrow, lblk, bstart, wstart);
+    hipLaunchKernelGGL(lds::ivf_fill_kernel, pg, dim3(256), 0, s, probe, p.pairs, ix.nprobe, ix.nlist, bstart, cnt, bq);
+    lds::ProfScope ps(s, "ivf_scan", 2.0 * (double)N * ix.nprobe * ((double)M / ix.nlist) * D, 4.0 * ((double)N * ix.nprobe * D + (double)ix.Mp * D));
+#define LDS_IVF_SCAN(KT_)                                                                                                                             \
+    hipLaunchKernelGGL(lds::ivf_scan_kernel<KT_>, dim3(p.wmax), dim3(256), 0, s, X, N, ix.PL, ix.hl, (int)ix.Mp, D, p.slab_blocks, (const int*)ix.order, \
+                       (int)M, llen, lrow, lblk, bstart, wstart, ix.nlist, bq, lval, lidx)
+    switch (p.KT) {
+        case 1: LDS_IVF_SCAN(1); break;
+        case 2: LDS_IVF_SCAN(2); break;
+        case 4: LDS_IVF_SCAN(4); break;
+        default: LDS_IVF_SCAN(8); break;
+    }
+#undef LDS_IVF_SCAN
+}
+
+int ivf_search(const char* fn, const float* X, long long N, long long M, int D, int k, const IvfIndex& ix, int slab_rows, int32_t* idx, float* score, void* ws,
+               size_t ws_bytes, hipStream_t s) {
+    if (int rc = ivf_check_dims(fn, N, M, D, k, ix.nlist, ix.nprobe)) return rc;
+    if (!X || !idx || !ws) return set_error(LDS_EINVAL, "%s: null pointer", fn);
+    if (int rc = ivf_check_index(fn, ix, M)) return rc;
+    if (kn_misaligned(X)) return set_error(LDS_EINVAL, "%s: X must be 16-byte aligned", fn);
+    const IvfPlan p = ivf_plan(N, D, k, ix.nlist, ix.nprobe, slab_rows);
+    if (ws_bytes < p.bytes) return set_error(LDS_ENOMEM, "%s: workspace %zu < %zu bytes", fn, ws_bytes, p.bytes);
+    ivf_lists(p, X, N, M, D, ix, ws, s);
+    hipLaunchKernelGGL(lds::knn_select_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, (const float*)((char*)ws + p.o_val),
+                       (const int*)((char*)ws + p.o_idx), ix.nprobe * lds::kIvfSegs, p.KT, N, (int)M, k, (int*)idx, score);
+    return kn_launched(fn);
+}
+
+int ivf_retrieve(const char* fn, const float* X, long long N, const float* P, long long M, int D, int k, const IvfIndex& ix, float ratio, float* Y, int32_t* idx,
+                 float* dist, void* ws, size_t ws_bytes, const lds::KnLens& lens, hipStream_t s) {
+    if (int rc = ivf_check_dims(fn, N, M, D, k, ix.nlist, ix.nprobe)) return rc;
+    if (!(ratio >= 0.f && ratio <= 1.f)) return set_error(LDS_EINVAL, "%s: ratio %g outside 0 .. 1", fn, (double)ratio);
+    if (!X || !P || !Y || !ws) return set_error(LDS_EINVAL, "%s: null pointer", fn);
+    if (int rc = ivf_check_index(fn, ix, M)) return rc;
+    if (kn_misaligned(X) || kn_misaligned(P) || kn_misaligned(Y)) return set_error(LDS_EINVAL, "%s: X, P and Y must be 16-byte aligned", fn);
+    const IvfPlan p = ivf_plan(N, D, k, ix.nlist, ix.nprobe, 0);
+    if (ws_bytes < p.bytes) return set_error(LDS_ENOMEM, "%s: workspace %zu < %zu bytes", fn, ws_bytes, p.bytes);
+    ivf_lists(p, X, N, M, D, ix, ws, s);
+    {
+        lds::ProfScope ps(s, "knn_blend", 5.0 * (double)N * k * D, 4.0 * (double)N * D * (2.0 * k + 3.0));
+        hipLaunchKernelGGL(lds::knn_blend_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, s, X, N, P, (int)M, D, (const float*)((char*)ws + p.o_val),
+                           (const int*)((char*)ws + p.o_idx), ix.nprobe * lds::kIvfSegs, p.KT, k, ratio, Y, (int*)idx, dist, lens);
+    }
+    return kn_launched(fn);
+}
+
+}  // namespace
+
+extern "C" int lds_ivf_workspace_bytes(int64_t N, int64_t M, int D, int k, int nlist, int nprobe, size_t* out) {
+    if (!out) return set_error(LDS_EINVAL, "lds_ivf_workspace_bytes: null out");
+    if (int rc = ivf_check_dims("lds_ivf_workspace_bytes", N, M, D, k, nlist, nprobe)) return rc;
+    *out = ivf_plan(N, D, k, nlist, nprobe, 0).bytes;
+    return LDS_OK;
+}
+
+extern "C" int lds_ivf_search(const float* X, int64_t N, const float* P, const float* h, int64_t M, int D, int k, const float* C, const float* hc, int nlist,
+                              const int64_t* offsets, const int32_t* order, const float* PL, const float* hl, int64_t copy_rows, int nprobe, int32_t* idx,
+                              float* score, void* ws, size_t ws_bytes, void* stream) {
+    (void)P; (void)h;      // the search scores the list-ordered copy
+    const IvfIndex ix = {C, hc, nlist, offsets, order, PL, hl, copy_rows, nprobe};
+    return ivf_search("lds_ivf_search", X, N, M, D, k, ix, 0, idx, score, ws, ws_bytes, (hipStream_t)stream);
+}
+
+extern "C" int lds_ivf_retrieve(const float* X, int64_t N, const float* P, const float* h, int64_t M, int D, int k, const float* C, const float* hc, int nlist,
+                                const int64_t* offsets, const int32_t* order, const float* PL, const float* hl, int64_t copy_rows, int nprobe, float ratio,
+                                float* Y, int32_t* idx, float* dist, void* ws, size_t ws_bytes, void* stream) {
+    (void)h;
+    const IvfIndex ix = {C, hc, nlist, offsets, order, PL, hl, copy_rows, nprobe};
+    return ivf_retrieve("lds_ivf_retrieve", X, N, P, M, D, k, ix, ratio, Y, idx, dist, ws, ws_bytes, kn_plain(), (hipStream_t)stream);
+}
+
+extern "C" int lds_ivf_retrieve_ragged(const float* X, int B, int T, const int32_t* lengths, const float* P, const float* h, int64_t M, int D, int k,
+                                       const float* C, const float* hc, int nlist, const int64_t* offsets, const int32_t* order, const float* PL,
+                                       const float* hl, int64_t copy_rows, int nprobe, float ratio, float* Y, int32_t* idx, float* dist, void* ws,
+                                       size_t ws_bytes, void* stream) {
+    (void)h;
+    if (B < 1 || B > 64 || T < 1) return set_error(LDS_EINVAL, "lds_ivf_retrieve_ragged: B %d outside 1 .. 64 or T %d < 1", B, T);
+    if (!lengths) return set_error(LDS_EINVAL, "lds_ivf_retrieve_ragged: null lengths");
+    lds::KnLens lens = kn_plain();
+    lens.n = B; lens.T = T;
+    for (int b = 0; b < B; ++b) {
+        if (lengths[b] < 0 || lengths[b] > T) return set_error(LDS_EINVAL, "lds_ivf_retrieve_ragged: lengths[%d] = %d outside 0 .. %d", b, lengths[b], T);
+        lens.v[b] = lengths[b];
+    }
+    const IvfIndex ix = {C, hc, nlist, offsets, order, PL, hl, copy_rows, nprobe};
+    return ivf_retrieve("lds_ivf_retrieve_ragged", X, (long long)B * T, P, M, D, k, ix, ratio, Y, idx, dist, ws, ws_bytes, lens, (hipStream_t)stream);
+}
+
+extern "C" int lds_test_ivf_search(const float* X, int64_t N, const float* P, const float* h, int64_t M, int D, int k, const float* C, const float* hc,
+                                   int nlist, const int64_t* offsets, const int32_t* order, const float* PL, const float* hl, int64_t copy_rows, int nprobe,
+                                   int slab_rows, int32_t* idx, float* score, void* ws, size_t ws_bytes, void* stream) {
+    (void)P; (void)h;
+    if (slab_rows < lds::kKnB || slab_rows % lds::kKnB || (D >= 8 && D <= 4096 && slab_rows > kn_slab_rows(D)))
+        return set_error(LDS_EINVAL, "lds_test_ivf_search: slab_rows %d must be a multiple of 128 that one descriptor holds", slab_rows);
+    const IvfIndex ix = {C, hc, nlist, offsets, order, PL, hl, copy_rows, nprobe};
+    return ivf_search("lds_test_ivf_search", X, N, M, D, k, ix, slab_rows, idx, score, ws, ws_bytes, (hipStream_t)stream);
+}

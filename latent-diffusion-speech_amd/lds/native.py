@@ -160,6 +160,10 @@ lds_knn_workspace_bytes          i:qqiip
 lds_knn_search                   i:pqppqiipppzp
 lds_knn_retrieve                 i:pqppqiifppppzp
 lds_knn_retrieve_ragged          i:piipppqiifppppzp
+lds_ivf_workspace_bytes          i:qqiiiip
+lds_ivf_search                   i:pqppqiippippppqipppzp
+lds_ivf_retrieve                 i:pqppqiippippppqifppppzp
+lds_ivf_retrieve_ragged          i:piipppqiippippppqifppppzp
 lds_resample                     i:ppppiiiiqqp
 lds_resample_ragged              i:ppppppiiiiqqp
 lds_frame_rms                    i:ppqiiiqp
@@ -233,6 +237,7 @@ lds_test_wavlm_attention         i:pppppiiiiip
 lds_test_wavlm_buckets           i:iiip
 lds_test_stft_dft                i:pppiiiippiqp
 lds_test_knn_search              i:pqppqiiiipppzp
+lds_test_ivf_search              i:pqppqiippippppqiipppzp
 """
 SIGNATURES = dict(ln.split() for ln in (_PUBLIC + _TEST).splitlines() if ln)
 EXPORTS = [ln.split()[0] for ln in _PUBLIC.splitlines() if ln]
@@ -1404,6 +1409,68 @@ def knn_retrieve(x, pool, h, k, ratio, lengths=None, ws=None):
     rows = (N,) if ln is None else (x.shape[0], x.shape[1], *ln_at)
     check(fn(_dev(x, torch.float32), *rows, _dev(pool, torch.float32), _dev(h, torch.float32), M, D, int(k), float(ratio), _dev(y), _dev(idx), _dev(dist),
              _dev(ws), ws.numel(), _stream()))
+    return y, idx, dist
+
+
+# ---- units retrieval through an IVF coarse index (lds_ivf_*): `ivf` is the tuple (centres [nlist, D], hc [nlist], offsets int64 [nlist + 1],
+# order int32 [M], copy [copy_rows, D], hl [copy_rows]) on the device (cluster.index.UnitsIndex.build_ivf makes it) ----
+_ivf_ws = Workspace()
+
+
+def ivf_workspace_bytes(N, M, D, k, nlist, nprobe):
+    return _bytes("lds_ivf_workspace_bytes", int(N), int(M), int(D), int(k), int(nlist), int(nprobe))
+
+
+def _ivf_args(ivf, nprobe):
+    import torch
+    centres, hc, offsets, order, copy, hl = ivf
+    return (_dev(centres, torch.float32), _dev(hc, torch.float32), centres.shape[0], _dev(offsets, torch.int64), _dev(order, torch.int32),
+            _dev(copy, torch.float32), _dev(hl, torch.float32), copy.shape[0], int(nprobe))
+
+
+def _ivf_ws_for(ws, N, M, D, k, ivf, nprobe, device):
+    if device.type != "cuda":
+        raise RuntimeError("liblds needs tensors on a HIP device (no CPU fallback for the hot path)")
+    return ws if ws is not None else _ivf_ws.get(ivf_workspace_bytes(N, M, D, k, ivf[0].shape[0], nprobe), device)
+
+
+def ivf_search(x, pool, h, k, ivf, nprobe, ws=None, slab_rows=None):
+    """x [N, D] -> (idx int32 [N, k], score [N, k]): the k best rows among the query's nprobe probed lists (include/lds.h lds_ivf_search);
+    -1 / -inf where the lists hold fewer than k rows.  slab_rows: the copy's cut forced through lds_test_ivf_search"""
+    import torch
+    M, D = pool.shape
+    if x.dim() != 2 or x.shape[1] != D:
+        raise ValueError(f"ivf_search: x {list(x.shape)} against a pool {[M, D]}")
+    N = x.shape[0]
+    ws = _ivf_ws_for(ws, N, M, D, k, ivf, nprobe, x.device)
+    idx = torch.empty(N, k, dtype=torch.int32, device=x.device)
+    score = torch.empty(N, k, dtype=torch.float32, device=x.device)
+    head = (_dev(x, torch.float32), N, _dev(pool, torch.float32), _dev(h, torch.float32), M, D, int(k), *_ivf_args(ivf, nprobe))
+    tail = (_dev(idx), _dev(score), _dev(ws), ws.numel(), _stream())
+    if slab_rows is None:
+        check(lib().lds_ivf_search(*head, *tail))
+    else:
+        check(lib().lds_test_ivf_search(*head, int(slab_rows), *tail))
+    return idx, score
+
+
+def ivf_retrieve(x, pool, h, k, ratio, ivf, nprobe, lengths=None, ws=None):
+    """knn_retrieve over the rows of every query's nprobe probed lists (include/lds.h lds_ivf_retrieve); idx = -1 (weight 0) where the
+    lists hold fewer than k rows"""
+    import torch
+    M, D = pool.shape
+    if x.shape[-1] != D or x.dim() != (3 if lengths is not None else 2):
+        raise ValueError(f"ivf_retrieve: x {list(x.shape)} against a pool {[M, D]}")
+    N = x.numel() // D
+    ws = _ivf_ws_for(ws, N, M, D, k, ivf, nprobe, x.device)
+    y = torch.empty_like(x)
+    idx = torch.empty(*x.shape[:-1], k, dtype=torch.int32, device=x.device)
+    dist = torch.empty(*x.shape[:-1], k, dtype=torch.float32, device=x.device)
+    ln = None if lengths is None else _host_lengths(lengths, x.shape[0], 0, x.shape[1], max_B=64, what="retrieval")
+    fn, ln_at = _dense_or_ragged("lds_ivf_retrieve", ln)
+    rows = (N,) if ln is None else (x.shape[0], x.shape[1], *ln_at)
+    check(fn(_dev(x, torch.float32), *rows, _dev(pool, torch.float32), _dev(h, torch.float32), M, D, int(k), *_ivf_args(ivf, nprobe), float(ratio), _dev(y),
+             _dev(idx), _dev(dist), _dev(ws), ws.numel(), _stream()))
     return y, idx, dist
 
 

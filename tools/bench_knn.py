@@ -7,12 +7,21 @@ Event time on the stream around one whole call after a warm-up call, the median 
 call (search, merge, gather and blend), to set beside the assign's kernel figures (tools/bench_kmeans.py).  The baseline is the same
 computation in torch on the same device: x @ p.T - h in chunks of pool rows with a running topk, then the gather, the distances, the
 weights and the blend.  A measurement, not a gate.
+
+    python tools/bench_knn.py --nlist 256 1024 --nprobe 1 8 [--mixture 256] [--no_torch] [--out profiles/r23_ivf_bench.json]
+
+--nlist / --nprobe: the IVF coarse index (UnitsIndex.build_ivf, retrieve(nprobe=)) beside the exact call of the same session.  Pool and
+queries then come from one seeded Gaussian mixture of --mixture components (unit-variance noise around N(0, 4) centres: a plain Gaussian has
+no neighbours worth finding at this width).  Per (pool, nlist): the build's wall time (fit + assignment + the list-ordered copy); per nprobe:
+the call's median, its ratio to the exact call, the kernels' shares of one profiled call (ivf_scan, the coarse knn_topk, knn_blend) and
+recall@8 against the exact call's lists.  exact_ms_spread is (max - min) of the exact call's --reps timings.
 """
 import argparse
 import json
 import os
 import statistics
 import sys
+import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "latent-diffusion-speech_amd"))
@@ -35,7 +44,45 @@ def median_ms(fn, reps):
         e1.record()
         torch.cuda.synchronize()
         t.append(e0.elapsed_time(e1))
+    median_ms.last = t
     return statistics.median(t)
+
+
+def mixture(n, d, comps, centres_seed, seed):
+    """n rows around `comps` seeded centres (the same centres for every seed)"""
+    c = torch.randn(comps, d, device="cuda", generator=torch.Generator(device="cuda").manual_seed(centres_seed)) * 2.0
+    g = torch.Generator(device="cuda").manual_seed(seed)
+    out = torch.randn(n, d, device="cuda", generator=g)
+    for r in range(0, n, 1 << 18):      # (in pieces: the gathered centres of a million rows are one more pool)
+        out[r:r + (1 << 18)] += c[torch.randint(0, comps, (min(1 << 18, n - r),), device="cuda", generator=g)]
+    return out
+
+
+def ivf_figures(ix, x, exact_ms, exact_idx, nlists, nprobes, reps):
+    from lds import native
+    out = {}
+    for nlist in nlists:
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        ix.build_ivf(nlist)
+        ix._device_ivf(x.device)
+        torch.cuda.synchronize()
+        lens = ix.ivf["offsets"][1:] - ix.ivf["offsets"][:-1]
+        res = {"build_s": round(time.perf_counter() - t0, 2), "lists_left": ix.nlist, "copy_rows": int(ix._device_ivf(x.device)[4].shape[0]),
+               "list_rows_mean_max": [round(float(lens.mean()), 1), int(lens.max())]}
+        for nprobe in nprobes:
+            ms = median_ms(lambda: ix.retrieve(x, k=K, ratio=0.5, nprobe=nprobe), reps)
+            native.prof_enable(1)
+            _, idx, _ = ix.retrieve(x, k=K, ratio=0.5, return_neighbours=True, nprobe=nprobe)
+            prof = {r["name"]: r["ms"] for r in native.prof_summary()}
+            native.prof_enable(0)
+            hit = (idx[:, :, None] == exact_idx[:, None, :]).any(2).float().mean()
+            per_list = torch.bincount(ix.probe_lists(x, nprobe).reshape(-1), minlength=ix.nlist)
+            res[f"nprobe_{nprobe}"] = {"ms": round(ms, 3), "speedup_over_exact": round(exact_ms / ms, 2), "recall_at_8": round(float(hit), 4),
+                                       "queries_per_list_mean_max": [round(float(per_list.float().mean()), 1), int(per_list.max())],
+                                       "profiled_ms": {k: round(v, 3) for k, v in prof.items()}}
+        out[f"nlist_{nlist}"] = res
+    return out
 
 
 def torch_retrieve(x, p, h, k, ratio, chunk=65536):
@@ -60,24 +107,38 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--pools", type=int, nargs="+", default=[100000, 1000000])
     ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r20_knn_bench.json"))
+    ap.add_argument("--out", default=None, help="default: profiles/r20_knn_bench.json, with --nlist profiles/r23_ivf_bench.json")
+    ap.add_argument("--nlist", type=int, nargs="+", default=[])
+    ap.add_argument("--nprobe", type=int, nargs="+", default=[1, 8])
+    ap.add_argument("--mixture", type=int, default=256)
+    ap.add_argument("--no_torch", action="store_true", help="leave the torch baseline out")
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "r23_ivf_bench.json" if a.nlist else "r20_knn_bench.json")
     g = torch.Generator(device="cuda").manual_seed(0)
-    x = torch.randn(N, D, device="cuda", generator=g)
+    x = mixture(N, D, a.mixture, 1, 2) if a.nlist else torch.randn(N, D, device="cuda", generator=g)
     res = {"N": N, "D": D, "k": K, "ratio": 0.5, "reps": a.reps, "peak_tflops": PEAK_TFLOPS}
+    if a.nlist:
+        res["mixture"] = a.mixture
     for M in a.pools:
-        p = torch.randn(M, D, device="cuda", generator=g)
+        p = mixture(M, D, a.mixture, 1, 3) if a.nlist else torch.randn(M, D, device="cuda", generator=g)
         ix = UnitsIndex(p)
         h = ix._device(p.device)[1]
         ms = median_ms(lambda: ix.retrieve(x, k=K, ratio=0.5), a.reps)
-        tms = median_ms(lambda: torch_retrieve(x, p, h, K, 0.5), a.reps)
+        spread = max(median_ms.last) - min(median_ms.last)
         y, idx, _ = ix.retrieve(x, k=K, ratio=0.5, return_neighbours=True)
-        ty, tidx = torch_retrieve(x, p, h, K, 0.5)
         fl = 2.0 * N * M * D
-        res[f"retrieve_{M}"] = {"ms": round(ms, 3), "tflops": round(fl / ms / 1e9, 1), "frac_peak": round(fl / ms / 1e9 / PEAK_TFLOPS, 3),
-                                "torch_ms": round(tms, 3), "torch_tflops": round(fl / tms / 1e9, 1), "speedup_over_torch": round(tms / ms, 2),
-                                "rows_with_torchs_neighbours": round(float((idx == tidx).all(1).float().mean()), 5),
-                                "max_abs_y_minus_torch": float((y - ty).abs().max())}
+        res[f"retrieve_{M}"] = {"ms": round(ms, 3), "tflops": round(fl / ms / 1e9, 1), "frac_peak": round(fl / ms / 1e9 / PEAK_TFLOPS, 3)}
+        if not a.no_torch:
+            tms = median_ms(lambda: torch_retrieve(x, p, h, K, 0.5), a.reps)
+            ty, tidx = torch_retrieve(x, p, h, K, 0.5)
+            res[f"retrieve_{M}"].update({"torch_ms": round(tms, 3), "torch_tflops": round(fl / tms / 1e9, 1), "speedup_over_torch": round(tms / ms, 2),
+                                         "rows_with_torchs_neighbours": round(float((idx == tidx).all(1).float().mean()), 5),
+                                         "max_abs_y_minus_torch": float((y - ty).abs().max())})
+            del ty, tidx
+        if a.nlist:
+            res[f"retrieve_{M}"]["exact_ms_spread"] = round(spread, 3)
+            res[f"ivf_{M}"] = ivf_figures(ix, x, ms, idx, a.nlist, a.nprobe, a.reps)
         del p, ix, h
     line = json.dumps(res)
     print(line)

@@ -1,14 +1,18 @@
 """Build a units index: the pool of a target speaker's unit frames that cluster.index.UnitsIndex searches (infer_svc.py / infer_tts.py --index).
 
     python tools/train_units_index.py UNITS_DIR -o units_index.pt [--max_rows 200000] [--reduce_to 10000] [--max_files 30000] [--seed 0]
-                                      [--max_iter 100] [--tol 1e-2] [--synthetic M]
+                                      [--max_iter 100] [--tol 1e-2] [--synthetic M] [--nlist 0] [--nlist_iter 25]
 
 UNITS_DIR holds .npy unit files [T, dim] (tools/extract_units.py writes them), searched recursively and read as tools/train_codebook.py
 reads them: up to --max_files of them, shuffled with --seed, concatenated.  Up to --max_rows frames the pool is the frames themselves
 (the search is exact at any size; 16,777,216 rows at the most).  Above --max_rows the pool is reduced to --reduce_to k-means centres of
 the frames by cluster.train_cluster (the codebook fit, on the HIP device) -- what the faiss-based tool chains do with a large speaker.
 --synthetic M: M seeded Gaussian rows of the files' width instead of the frames (a stand-in pool for smoke runs).
-The file is a torch-saved dict {"pool": float32 [M, D], "n_features_in_": D, "source_rows": the frames read, "reduced": bool}.
+--nlist N (default 0: none): an IVF coarse index over the pool as well -- N k-means centres of the pool (cluster.train_cluster, --nlist_iter
+iterations) and every row's list (UnitsIndex.build_ivf), so that --index_nprobe searches a few lists instead of the pool and a large speaker
+keeps its frames: raise --max_rows with it.
+The file is a torch-saved dict {"pool": float32 [M, D], "n_features_in_": D, "source_rows": the frames read, "reduced": bool}, with --nlist
+also "ivf": {"centres", "offsets", "order"}.
 """
 import argparse
 import glob
@@ -47,6 +51,8 @@ def main(argv=None):
     ap.add_argument("--max_iter", type=int, default=100)
     ap.add_argument("--tol", type=float, default=1e-2)
     ap.add_argument("--synthetic", type=int, default=0, metavar="M")
+    ap.add_argument("--nlist", type=int, default=0, help="lists of an IVF coarse index over the pool (0: none)")
+    ap.add_argument("--nlist_iter", type=int, default=25)
     a = ap.parse_args(argv)
     paths = sorted(glob.glob(os.path.join(a.units_dir, "**", "*.npy"), recursive=True))
     if not paths:
@@ -58,9 +64,16 @@ def main(argv=None):
     else:
         pool, reduced = build_pool(feats, a.max_rows, a.reduce_to, a.seed, a.max_iter, a.tol)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    UnitsIndex(pool, source_rows=feats.shape[0], reduced=reduced).save(a.out)
+    index = UnitsIndex(pool, source_rows=feats.shape[0], reduced=reduced)
+    if a.nlist:
+        if not 1 <= a.nlist <= min(65536, pool.shape[0]):
+            raise SystemExit(f"--nlist {a.nlist} outside 1 .. min(65536, the pool's {pool.shape[0]} rows)")
+        torch.manual_seed(a.seed)
+        ck = cluster.train_cluster(pool, a.nlist, max_iter=a.nlist_iter, tol=a.tol)
+        index.build_ivf(a.nlist, centres=np.asarray(ck["cluster_centers_"], dtype=np.float32))
+    index.save(a.out)
     print(f"{a.out}: {pool.shape[0]} rows of {pool.shape[1]} floats ({'k-means centres of' if reduced else 'the frames of' if not a.synthetic else 'synthetic, beside'} "
-          f"{feats.shape[0]} frames of {min(len(paths), a.max_files)} files)")
+          f"{feats.shape[0]} frames of {min(len(paths), a.max_files)} files)" + (f", {index.nlist} IVF lists" if a.nlist else ""))
 
 
 if __name__ == "__main__":
