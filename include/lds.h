@@ -595,24 +595,57 @@ int  lds_llama_score(lds_llama* h, const int64_t* input_ids, const int32_t* ids_
  * than lds_kmeans_workspace_bytes(N, K, D) gives LDS_ENOMEM.  One workspace size serves all calls of the same (N, K, D); its contents
  * on entry do not matter.  Nothing synchronises.  No floating-point atomics: every call is bit-identical on repeat. */
 int lds_kmeans_workspace_bytes(int64_t N, int K, int D, size_t* out);
+/* The metric of the lds_kmeans_*_metric, lds_knn_*_metric and lds_ivf_*_metric entries (any other value: LDS_EINVAL).  Each of those entries is its
+ * namesake with `int metric` added (and `int weights` where a blend follows); with LDS_METRIC_L2 (and LDS_WEIGHTS_INVERSE_SQUARE) it IS its
+ * namesake, bit for bit -- the namesakes forward.  LDS_METRIC_COSINE, all fp32:
+ *   row constant  r(v) = 1 / max(sqrt(s), 1e-12), s = the fp32 sum of squares of the row in one fixed order (lanes of a wave stride the columns,
+ *                 one fmaf chain per lane, a fixed butterfly), square root and reciprocal correctly rounded: F.normalize's eps.  s = 4, 16, 64
+ *                 give exactly 1/2, 1/4, 1/8.  A zero row has r = 1e12 and scores 0 against everything; nothing gives NaN for finite rows.
+ *                 LIMIT: a row whose s overflows fp32 (|v| beyond about 1.8e19) is outside the contract (r = 0: it scores 0 or NaN).
+ *   score         (x_n . p_m) r_m: the dot product is the L2 score's fmaf chain, the per-row array `h` holds r_m where it holds |p_m|^2 / 2
+ *                 for L2.  Order: descending score, the lower index among exactly equal scores (rows that are scaled copies by powers of
+ *                 two tie exactly).  The value REPORTED (search's score, assign's best) is that score times r(x_n), multiplied after the
+ *                 order is decided: the cosine similarity.
+ *   distance      of a chosen neighbour, recomputed directly: d_j = 1/2 sum_c (x_c r_x - p_jc r_j)^2 (= 1 - cos) in one fixed order,
+ *                 floored at 1e-12.
+ * No second copy of any pool is made; no floating-point atomics; every call is bit-identical on repeat whatever the workspace held. */
+#define LDS_METRIC_L2 0
+#define LDS_METRIC_COSINE 1
+/* the weights of a blend: (1 / d_j)^2 normalised for j ascending (the RVC / Diffusion-SVC tool chains), or w_j = 1 / found over the
+ * neighbours actually present (kNN-VC's plain mean of the matched rows) */
+#define LDS_WEIGHTS_INVERSE_SQUARE 0
+#define LDS_WEIGHTS_UNIFORM 1
 /* h dev [K] = |c_k|^2 / 2 (once per codebook; lds_kmeans_update refreshes it) */
 int lds_kmeans_prepare(const float* C, int K, int D, float* h, void* stream);
+/* cosine: h dev [K] = r(c_k).  Replaces the b side of the reference's cos_sim (kmeans.py:96-105 normalize(b, dim=-1)) without a normalised copy */
+int lds_kmeans_prepare_metric(const float* C, int K, int D, int metric, float* h, void* stream);
 /* labels dev int64 [N]: label[n] = argmax_k (x_n . c_k - h_k) = the nearest centre (scikit-learn's predict; the arg-max of the reference's
  * euc_sim), the LOWEST index among exactly equal scores; best dev [N] or NULL = the winning score (|x_n|^2 - 2 best = squared distance).
  * Exact fp32 on the MFMA; the N x K matrix is never stored.  A row's label depends on that row and the codebook only: not on N, the row's
  * position or the other rows (NaN / Inf there included). */
 int lds_kmeans_assign(const float* X, int64_t N, const float* C, const float* h, int K, int D, int64_t* labels, float* best, void* ws, size_t ws_bytes,
                       void* stream);
+/* cosine: label[n] = argmax_k (x_n . c_k) r_k, best = the cosine similarity.  Replaces KMeansGPU(mode='cosine').max_sim (kmeans.py:117-131 over
+ * cos_sim :96-105) */
+int lds_kmeans_assign_metric(const float* X, int64_t N, const float* C, const float* h, int K, int D, int metric, int64_t* labels, float* best, void* ws,
+                             size_t ws_bytes, void* stream);
 /* the same over a ragged batch X dev [B][T][D]: lengths host int32 [B] (B <= 64, 0 <= lengths[b] <= T); rows t >= lengths[b] get pad_id (a
  * 32-bit value; best = 0 there) whatever they hold.  Workspace of N = B * T. */
 int lds_kmeans_assign_ragged(const float* X, int B, int T, const int32_t* lengths, int64_t pad_id, const float* C, const float* h, int K, int D,
                              int64_t* labels, float* best, void* ws, size_t ws_bytes, void* stream);
+/* the ragged form of lds_kmeans_assign_metric (max_sim per clip; padded rows: pad_id, best = 0, whatever they hold) */
+int lds_kmeans_assign_ragged_metric(const float* X, int B, int T, const int32_t* lengths, int64_t pad_id, const float* C, const float* h, int K, int D,
+                                    int metric, int64_t* labels, float* best, void* ws, size_t ws_bytes, void* stream);
 /* One Lloyd step given labels (kmeans.py:185-198): c_grad = per-cluster mean (an empty cluster: a zero row), *error (dev float) =
  * sum (c_grad - C)^2, lr = 1 / num_points * 0.9 + 0.1, C = C (1 - lr) + c_grad lr in place, then num_points (dev [K]) += the counts and h
  * refreshed.  The sums run in row order per cluster (a stable counting sort of the rows by label), the error in a fixed order.  Rows whose
  * label is outside [0, K) are ignored. */
 int lds_kmeans_update(const float* X, const int64_t* labels, int64_t N, float* C, float* h, float* num_points, int K, int D, float* error, void* ws,
                       size_t ws_bytes, void* stream);
+/* the same step -- the reference's Lloyd step (kmeans.py:185-198) is the plain mean and the same lr in both modes -- refreshing h as
+ * lds_kmeans_prepare_metric(metric) of the new centres, bit for bit */
+int lds_kmeans_update_metric(const float* X, const int64_t* labels, int64_t N, float* C, float* h, float* num_points, int K, int D, int metric,
+                             float* error, void* ws, size_t ws_bytes, void* stream);
 /* k-means++ seeding (kmeans.py:42-49): C[0] = X[first_index]; for i >= 1 the weight of a point is its Euclidean DISTANCE (not squared, as
  * the reference's cdist) to the nearest centre picked so far (a running minimum, fp32), and C[i] = X[j], j = the first index whose
  * prefix sum reaches uniforms[i - 1] * total -- the prefix in double in a fixed order -- clamped to N - 1 (the reference raises there).
@@ -636,21 +669,35 @@ int lds_kmeans_seed(const float* X, int64_t N, int D, int K, int64_t first_index
  * contents of the workspace on entry do not matter.  Nothing synchronises.  No floating-point atomics: every call is bit-identical on repeat. */
 /* h dev [M] = |p_m|^2 / 2 (once per pool) */
 int lds_knn_prepare(const float* P, int64_t M, int D, float* h, void* stream);
+/* cosine: h dev [M] = r(p_m).  Replaces kNN-VC's normalised copy of the matching set (its fast_cosine_dist's norms) */
+int lds_knn_prepare_metric(const float* P, int64_t M, int D, int metric, float* h, void* stream);
 int lds_knn_workspace_bytes(int64_t N, int64_t M, int D, int k, size_t* out);
 /* idx dev int32 [N][k] = the k nearest pool rows of every query, nearest first; score dev [N][k] or NULL = their scores
  * (|x_n|^2 - 2 score = squared distance).  A query without k comparable scores (a NaN row) gets -1 in the missing places. */
 int lds_knn_search(const float* X, int64_t N, const float* P, const float* h, int64_t M, int D, int k, int32_t* idx, float* score, void* ws,
                    size_t ws_bytes, void* stream);
+/* cosine: the k rows of highest cosine similarity, score = the similarities (-inf in a missing place).  Replaces kNN-VC's
+ * fast_cosine_dist(...).topk(k, largest=False) */
+int lds_knn_search_metric(const float* X, int64_t N, const float* P, const float* h, int64_t M, int D, int k, int metric, int32_t* idx, float* score,
+                          void* ws, size_t ws_bytes, void* stream);
 /* Y dev [N][D]: the search, then for the k winners d_j = sum_c (x_c - p_jc)^2 recomputed directly (not from |x|^2 - 2 score) in fp32 in one
  * fixed order, d_j = max(d_j, 1e-12), w_j = (1 / d_j)^2 normalised by their sum taken for j ascending, z = sum_j w_j p_j (fmaf, j ascending),
  * y_n = (1 - ratio) x_n + ratio z.  ratio = 0 gives x bit for bit, ratio = 1 with k = 1 the pool row bit for bit.  idx dev int32 [N][k] and
  * dist dev [N][k] (the floored d_j), either may be NULL.  Every gathered index is clamped into [0, M) before it forms an address. */
 int lds_knn_retrieve(const float* X, int64_t N, const float* P, const float* h, int64_t M, int D, int k, float ratio, float* Y, int32_t* idx,
                      float* dist, void* ws, size_t ws_bytes, void* stream);
+/* the search by `metric`, the distances by `metric` (cosine: 1 - cos as above; h is then read by the blend too), the weights by `weights`, and
+ * the unchanged blend y = (1 - ratio) x + ratio sum_j w_j p_j over the ORIGINAL pool rows, j ascending, with fmaf.  A query without
+ * neighbours (a NaN row) has found = 0.  cosine + uniform + ratio 1 + k 4 replaces kNN-VC's match (the mean of the matched rows) */
+int lds_knn_retrieve_metric(const float* X, int64_t N, const float* P, const float* h, int64_t M, int D, int k, int metric, int weights, float ratio,
+                            float* Y, int32_t* idx, float* dist, void* ws, size_t ws_bytes, void* stream);
 /* the same over a ragged batch X dev [B][T][D]: lengths host int32 [B] (B <= 64, 0 <= lengths[b] <= T); rows t >= lengths[b] get y = 0,
  * idx = -1 and dist = 0 whatever they hold.  Workspace of N = B * T. */
 int lds_knn_retrieve_ragged(const float* X, int B, int T, const int32_t* lengths, const float* P, const float* h, int64_t M, int D, int k,
                             float ratio, float* Y, int32_t* idx, float* dist, void* ws, size_t ws_bytes, void* stream);
+/* the ragged form of lds_knn_retrieve_metric (kNN-VC's match per clip) */
+int lds_knn_retrieve_ragged_metric(const float* X, int B, int T, const int32_t* lengths, const float* P, const float* h, int64_t M, int D, int k,
+                                   int metric, int weights, float ratio, float* Y, int32_t* idx, float* dist, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- units retrieval through an IVF coarse index: probe nprobe lists, not the pool (csrc/knn.hip) ------------------
  * What faiss IndexIVFFlat is to the RVC / Diffusion-SVC tool chains (index.nprobe = 1 .. 16 there; IndexIVFFlat::train / add build the
@@ -690,6 +737,20 @@ int lds_ivf_retrieve_ragged(const float* X, int B, int T, const int32_t* lengths
                             const float* C, const float* hc, int nlist, const int64_t* offsets, const int32_t* order, const float* PL,
                             const float* hl, int64_t copy_rows, int nprobe, float ratio, float* Y, int32_t* idx, float* dist, void* ws,
                             size_t ws_bytes, void* stream);
+/* The same three with the metric (and the weights): C / hc, PL / hl and P / h are then one index built for that metric -- hc, hl and h from
+ * lds_knn_prepare_metric, the lists assigned by lds_kmeans_assign_metric.  In cosine mode lds_ivf_retrieve*_metric READ h (the blend's r_j).
+ * replaces IndexIVFFlat::search over an inner-product quantizer on normalised rows (faiss METRIC_INNER_PRODUCT), without the normalised copy */
+int lds_ivf_search_metric(const float* X, int64_t N, const float* P, const float* h, int64_t M, int D, int k, const float* C, const float* hc, int nlist,
+                          const int64_t* offsets, const int32_t* order, const float* PL, const float* hl, int64_t copy_rows, int nprobe, int metric,
+                          int32_t* idx, float* score, void* ws, size_t ws_bytes, void* stream);
+/* replaces that search + kNN-VC's mean (or the tool chains' inverse-square weighting) of the rows it returns */
+int lds_ivf_retrieve_metric(const float* X, int64_t N, const float* P, const float* h, int64_t M, int D, int k, const float* C, const float* hc, int nlist,
+                            const int64_t* offsets, const int32_t* order, const float* PL, const float* hl, int64_t copy_rows, int nprobe, int metric,
+                            int weights, float ratio, float* Y, int32_t* idx, float* dist, void* ws, size_t ws_bytes, void* stream);
+int lds_ivf_retrieve_ragged_metric(const float* X, int B, int T, const int32_t* lengths, const float* P, const float* h, int64_t M, int D, int k,
+                                   const float* C, const float* hc, int nlist, const int64_t* offsets, const int32_t* order, const float* PL,
+                                   const float* hl, int64_t copy_rows, int nprobe, int metric, int weights, float ratio, float* Y, int32_t* idx,
+                                   float* dist, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- polyphase sinc resampler in front of the audio encoders (reference torchaudio.transforms.Resample(orig_freq, new_freq) with its
  *      defaults sinc_interp_hann / lowpass_filter_width 6 / rolloff 0.99, i.e. torchaudio's _get_sinc_resample_kernel +

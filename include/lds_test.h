@@ -266,12 +266,19 @@ int lds_test_stft_dft(const float* audio, const double* basis, const float* mel_
  * (each of the two halves rounded up to 256); LDS_ENOMEM below that. */
 int lds_test_knn_search(const float* X, int64_t N, const float* P, const float* h, int64_t M, int D, int k, int slab_rows, int splits, int32_t* idx,
                         float* score, void* ws, size_t ws_bytes, void* stream);
+/* the same probe of lds_knn_search_metric (replaces nothing in the reference: a test entry) */
+int lds_test_knn_search_metric(const float* X, int64_t N, const float* P, const float* h, int64_t M, int D, int k, int metric, int slab_rows, int splits,
+                               int32_t* idx, float* score, void* ws, size_t ws_bytes, void* stream);
 
 /* lds_ivf_search (include/lds.h) with the list-ordered copy cut into slabs of slab_rows rows (a multiple of 128 that one buffer descriptor
  * holds), so that lists in different slabs are walked at toy sizes.  The workspace is lds_ivf_workspace_bytes'. */
 int lds_test_ivf_search(const float* X, int64_t N, const float* P, const float* h, int64_t M, int D, int k, const float* C, const float* hc, int nlist,
                         const int64_t* offsets, const int32_t* order, const float* PL, const float* hl, int64_t copy_rows, int nprobe, int slab_rows,
                         int32_t* idx, float* score, void* ws, size_t ws_bytes, void* stream);
+/* the same probe of lds_ivf_search_metric */
+int lds_test_ivf_search_metric(const float* X, int64_t N, const float* P, const float* h, int64_t M, int D, int k, const float* C, const float* hc, int nlist,
+                               const int64_t* offsets, const int32_t* order, const float* PL, const float* hl, int64_t copy_rows, int nprobe, int metric,
+                               int slab_rows, int32_t* idx, float* score, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- debugging aids (tests/test_gpu_poison.py, tools/diag_trace.py) ----------------------------------------------------------
  * lds_debug_fill_u32: every 32-bit word of a device buffer = pattern.  Tests fill a caller workspace with NaN patterns (0x7fc07fc0 is a NaN

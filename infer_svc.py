@@ -45,6 +45,9 @@ def parse_args(argv=None):
     ap.add_argument("--index_ratio", type=float, default=0.5, help="0 .. 1: the share of the retrieved units in the blend")
     ap.add_argument("--index_k", type=int, default=8, help="1 .. 8 nearest pool rows per frame")
     ap.add_argument("--index_nprobe", type=int, default=None, help="1 .. 8: search only the rows of a frame's N best lists (an index written with --nlist)")
+    ap.add_argument("--index_weights", default="inverse_square", choices=("inverse_square", "uniform"),
+                    help="the blend's weights: 1 / d^2 over the distances, or the plain mean of the rows found (kNN-VC: --index_k 4 --index_ratio 1.0 "
+                         "over an index written with --metric cosine; the metric comes from the index file)")
     ap.add_argument("--synthetic", action="store_true")
     ap.add_argument("--synthetic_width", type=int, default=1280, help="width of the synthetic units encoder (a multiple of 64)")
     ap.add_argument("--synthetic_layers", type=int, default=4)
@@ -149,7 +152,7 @@ def main(argv=None):
     torch.manual_seed(a.seed)
     wav, rate = svc.infer_from_long_audio(audio, sr=sr, spk_id=a.spk_id, infer_speedup=a.speedup, method=a.method, threhold=a.threhold,
                                           threhold_for_split=a.threhold_for_split, min_len=a.min_len, batch_size=a.batch_size, index=index,
-                                          index_ratio=a.index_ratio, index_k=a.index_k, index_nprobe=a.index_nprobe)
+                                          index_ratio=a.index_ratio, index_k=a.index_k, index_nprobe=a.index_nprobe, index_weights=a.index_weights)
     wav = wav.cpu().numpy()
     if a.output.endswith(".wav"):
         with wave.open(a.output, "wb") as f:

@@ -60,6 +60,8 @@ def parse_args(argv=None):
     ap.add_argument("--index_ratio", type=float, default=0.5, help="0 .. 1: the share of the retrieved units in the blend")
     ap.add_argument("--index_k", type=int, default=8, help="1 .. 8 nearest pool rows per frame")
     ap.add_argument("--index_nprobe", type=int, default=None, help="1 .. 8: search only the rows of a frame's N best lists (an index written with --nlist)")
+    ap.add_argument("--index_weights", default="inverse_square", choices=("inverse_square", "uniform"),
+                    help="the blend's weights: 1 / d^2 over the distances, or the plain mean of the rows found (the metric comes from the index file)")
     ap.add_argument("--synthetic", action="store_true")
     ap.add_argument("--synthetic_tokens", type=int, default=256)
     return ap.parse_args(argv)
@@ -420,7 +422,8 @@ def synthesize_ragged(svc, codebook, token_rows, spk_id=1, speedup=10, method="d
     return out
 
 
-def synthesize(svc, codebook, tokens, spk_id=1, speedup=10, method="dpm-solver", scale_factor=None, *, index=None, index_ratio=0.5, index_k=8, index_nprobe=None):
+def synthesize(svc, codebook, tokens, spk_id=1, speedup=10, method="dpm-solver", scale_factor=None, *, index=None, index_ratio=0.5, index_k=8, index_nprobe=None,
+               index_weights="inverse_square"):
     """tokens [T] (or [B,T]) int64 on the device -> (units [B,T',C], mel [B,T',M], wav [B,1,T'*hop]); index (cluster.index.UnitsIndex): the
     gathered centres are blended with their index_k nearest pool rows at index_ratio before the alignment (index_nprobe: through the index's IVF)"""
     from lds import native
@@ -428,7 +431,7 @@ def synthesize(svc, codebook, tokens, spk_id=1, speedup=10, method="dpm-solver",
     tok = tokens if tokens.dim() == 2 else tokens[None]
     units = native.gather_rows(codebook, tok)                                  # semantic_embedding(semantic_token), 22_infer_tts.py:106
     if index is not None:
-        units = index.retrieve(units, k=index_k, ratio=index_ratio, nprobe=index_nprobe)
+        units = index.retrieve(units, k=index_k, ratio=index_ratio, nprobe=index_nprobe, weights=index_weights)
     if scale_factor is not None:
         units = units_forced_alignment(units, scale_factor=scale_factor)
     mel = svc(units, f0=None, volume=None, spk_id=spk_id, infer_speedup=speedup, method=method)
@@ -486,7 +489,7 @@ def main(argv=None):
         from cluster.index import UnitsIndex
         index = UnitsIndex.load(a.index)
     _, _, wav = synthesize(svc, codebook, tokens, a.spk_id, a.speedup, a.method, a.scale_factor, index=index, index_ratio=a.index_ratio, index_k=a.index_k,
-                           index_nprobe=a.index_nprobe)
+                           index_nprobe=a.index_nprobe, index_weights=a.index_weights)
     wav = wav[0, 0].cpu().numpy()
     if a.output.endswith(".wav"):
         import wave

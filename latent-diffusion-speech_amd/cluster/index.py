@@ -7,7 +7,11 @@ in a pool of the target speaker's units: y = (1 - ratio) x + ratio sum_j w_j p_j
 
 An IVF coarse index (`build_ivf`; include/lds.h lds_ivf_*, faiss IndexIVFFlat's role in those tool chains) groups the pool's rows by their
 nearest of `nlist` coarse centres; `search` / `retrieve` with `nprobe=` then score a frame against the rows of its nprobe best centres only.
-The file then carries one more key, "ivf": {"centres": float32 [nlist, D], "offsets": int64 [nlist + 1], "order": int32 [M]}."""
+The file then carries one more key, "ivf": {"centres": float32 [nlist, D], "offsets": int64 [nlist + 1], "order": int32 [M]}.
+
+metric="cosine" is kNN-VC's matching: neighbours by cosine similarity (score (x . p) / max(|p|, 1e-12), one constant per pool row -- no
+normalised copy of the pool), distances 1 - cos; `retrieve(weights="uniform")` is its plain mean of the matched ORIGINAL rows.  The file
+carries "metric": "cosine" (an l2 index writes no such key, and a file without it is l2); an IVF belongs to the metric it was built under."""
 import numpy as np
 import torch
 
@@ -15,32 +19,38 @@ MAX_K = 8
 MAX_ROWS = 16777216
 MAX_NPROBE = 8
 MAX_NLIST = 65536
+METRICS = ("l2", "cosine")
+WEIGHTS = ("inverse_square", "uniform")
 BLOCK = 128      # the list-ordered copy pads every list to whole blocks of this many rows
 
 
-def _assign_lists(pool, centres, device):
-    """labels int64 numpy [M]: every pool row's best centre by lds_kmeans_assign (score p.c - |c|^2 / 2, the lower centre among equal scores)"""
+def _assign_lists(pool, centres, device, metric="l2"):
+    """labels int64 numpy [M]: every pool row's best centre by lds_kmeans_assign (score p.c - |c|^2 / 2, or the cosine score (p.c) / |c|; the
+    lower centre among equal scores)"""
     from lds import native
     if torch.device(device).type != "cuda":
         raise RuntimeError("UnitsIndex.build_ivf needs a HIP device (no CPU fallback for the assignment)")
     p = (pool if isinstance(pool, torch.Tensor) else torch.from_numpy(pool)).to(device).contiguous()
     c = torch.as_tensor(centres, dtype=torch.float32).to(device).contiguous()
-    return native.kmeans_assign(p, c, native.kmeans_prepare(c)).cpu().numpy()
+    return native.kmeans_assign(p, c, native.kmeans_prepare(c, metric), metric=metric).cpu().numpy()
 
 
-def _fit_centres(pool, nlist, max_iter, seed, device):
-    """nlist k-means centres of the pool by the project's KMeansGPU (seeded)"""
-    from .kmeans import KMeansGPU
+def _fit_centres(pool, nlist, max_iter, seed, device, metric="l2"):
+    """nlist k-means centres of the pool by the project's KMeansGPU (seeded), in the index's metric"""
+    from .kmeans import KMeansCosineGPU, KMeansGPU
     torch.manual_seed(seed)
-    km = KMeansGPU(n_clusters=nlist, max_iter=max_iter, device=torch.device(device))
+    km = (KMeansCosineGPU if metric == "cosine" else KMeansGPU)(n_clusters=nlist, max_iter=max_iter, device=torch.device(device))
     km.fit_predict(pool if isinstance(pool, torch.Tensor) else torch.from_numpy(pool))
     return km.centroids.cpu().numpy()
 
 
 class UnitsIndex:
-    def __init__(self, pool, source_rows=None, reduced=False):
+    def __init__(self, pool, source_rows=None, reduced=False, metric="l2"):
         """pool: numpy or tensor [M, D] (D a multiple of 8 in 8 .. 4096, M <= 16,777,216); a device tensor is used where it is, anything
-        else is uploaded on first use on a device"""
+        else is uploaded on first use on a device.  metric: "l2" or "cosine" -- what search, retrieve, probe_lists and build_ivf go by"""
+        if not isinstance(metric, str) or metric not in METRICS:
+            raise ValueError(f"UnitsIndex: metric must be one of {list(METRICS)} (got {metric!r})")
+        self.metric = metric
         if isinstance(pool, torch.Tensor):
             pool = pool.detach().to(torch.float32).contiguous()
         else:
@@ -69,7 +79,7 @@ class UnitsIndex:
                 raise RuntimeError("UnitsIndex needs tensors on a HIP device (no CPU fallback for the hot path)")
             p = self.pool if isinstance(self.pool, torch.Tensor) else torch.from_numpy(self.pool)
             p = p.to(device).contiguous()
-            self._on[key] = (p, native.knn_prepare(p))
+            self._on[key] = (p, native.knn_prepare(p, self.metric))
         return self._on[key]
 
     @property
@@ -82,14 +92,15 @@ class UnitsIndex:
         their centre (self.nlist is what is left); inside a list the rows keep ascending original index.  Returns self."""
         if isinstance(nlist, bool) or not isinstance(nlist, (int, np.integer)) or not 1 <= nlist <= min(MAX_NLIST, len(self)):
             raise ValueError(f"UnitsIndex: nlist must be an integer in 1 .. min({MAX_NLIST}, the pool's {len(self)} rows) (got {nlist!r})")
+        how = {} if self.metric == "l2" else {"metric": self.metric}      # (the l2 calls are the ones that were always made)
         if centres is None:
-            centres = _fit_centres(self.pool, int(nlist), max_iter, seed, device)
+            centres = _fit_centres(self.pool, int(nlist), max_iter, seed, device, **how)
         else:
             centres = centres.detach().cpu().numpy() if isinstance(centres, torch.Tensor) else np.asarray(centres)
         centres = np.ascontiguousarray(centres, dtype=np.float32)
         if centres.shape != (nlist, self.n_features_in_):
             raise ValueError(f"UnitsIndex: centres {list(centres.shape)} must be [{nlist}, {self.n_features_in_}]")
-        labels = np.asarray(_assign_lists(self.pool, centres, device)).reshape(-1)
+        labels = np.asarray(_assign_lists(self.pool, centres, device, **how)).reshape(-1)
         counts = np.bincount(labels, minlength=nlist)
         keep = np.flatnonzero(counts)
         self._set_ivf({"centres": centres[keep], "offsets": np.concatenate([[0], np.cumsum(counts[keep])]),
@@ -126,7 +137,7 @@ class UnitsIndex:
             copy[at] = pool[od.long()]
             hl[at] = h[od.long()]
             centres = torch.from_numpy(self.ivf["centres"]).to(device)
-            self._ivf_on[key] = (centres, native.knn_prepare(centres), torch.from_numpy(offsets).to(device), od, copy, hl)
+            self._ivf_on[key] = (centres, native.knn_prepare(centres, self.metric), torch.from_numpy(offsets).to(device), od, copy, hl)
         return self._ivf_on[key]
 
     def _check_nprobe(self, nprobe):
@@ -146,7 +157,7 @@ class UnitsIndex:
             raise ValueError(f"UnitsIndex: x {list(x.shape)} against a pool of width {self.n_features_in_}")
         x = self._on_device(x)
         centres, hc = self._device_ivf(x.device)[:2]
-        return native.knn_search(x.reshape(-1, x.shape[-1]), centres, hc, nprobe)[0].to(torch.int64).reshape(*x.shape[:-1], nprobe)
+        return native.knn_search(x.reshape(-1, x.shape[-1]), centres, hc, nprobe, metric=self.metric)[0].to(torch.int64).reshape(*x.shape[:-1], nprobe)
 
     def _check(self, x, k, dims):
         """the argument checks of search / retrieve, the ValueErrors first: they do not depend on where x lives"""
@@ -166,7 +177,8 @@ class UnitsIndex:
 
     def search(self, x, k=8, nprobe=None):
         """x [.., D] on the device -> (idx int64 [.., k], score [.., k]): the k nearest pool rows of every frame, nearest first, the lower
-        index among exactly equal scores; score = x.p - |p|^2 / 2 (|x|^2 - 2 score is the squared distance).  nprobe (needs build_ivf): only
+        index among exactly equal scores; score = x.p - |p|^2 / 2 (|x|^2 - 2 score is the squared distance), or the cosine similarity of a
+        cosine index.  nprobe (needs build_ivf): only
         the rows of the frame's nprobe best lists are scored; -1 / -inf where they hold fewer than k rows"""
         from lds import native
         k = self._check(x, k, (1, 2, 3))
@@ -175,17 +187,21 @@ class UnitsIndex:
         x = self._on_device(x)
         pool, h = self._device(x.device)
         if nprobe is None:
-            idx, score = native.knn_search(x.reshape(-1, x.shape[-1]), pool, h, k)
+            idx, score = native.knn_search(x.reshape(-1, x.shape[-1]), pool, h, k, metric=self.metric)
         else:
-            idx, score = native.ivf_search(x.reshape(-1, x.shape[-1]), pool, h, k, self._device_ivf(x.device), nprobe)
+            idx, score = native.ivf_search(x.reshape(-1, x.shape[-1]), pool, h, k, self._device_ivf(x.device), nprobe, metric=self.metric)
         return idx.to(torch.int64).reshape(*x.shape[:-1], k), score.reshape(*x.shape[:-1], k)
 
-    def retrieve(self, x, k=8, ratio=0.5, lengths=None, return_neighbours=False, nprobe=None):
+    def retrieve(self, x, k=8, ratio=0.5, lengths=None, return_neighbours=False, nprobe=None, weights="inverse_square"):
         """x [N, D] or [B, T, D] on the device -> y of the same shape; lengths ([B] ints, 0 .. T; needs [B, T, D], B <= 64): rows at and
         beyond a clip's length come back as zeros.  return_neighbours: (y, idx int64 [.., k], dist [.., k]) with the squared distances
         (floored at 1e-12) that the weights were formed from; idx = -1 beyond a clip's length.  nprobe (needs build_ivf): the neighbours come
-        from the frame's nprobe best lists; where those hold fewer than k rows idx = -1 and the blend is over the rows found"""
+        from the frame's nprobe best lists; where those hold fewer than k rows idx = -1 and the blend is over the rows found.
+        weights: "inverse_square" (w_j ~ 1 / d_j^2) or "uniform" (the plain mean of the rows found: kNN-VC's).  A cosine index reports
+        dist = 1 - cos; the blend is over the pool's original rows whatever the metric"""
         from lds import native
+        if not isinstance(weights, str) or weights not in WEIGHTS:
+            raise ValueError(f"UnitsIndex: weights must be one of {list(WEIGHTS)} (got {weights!r})")
         k = self._check(x, k, (2, 3))
         if nprobe is not None:
             nprobe = self._check_nprobe(nprobe)
@@ -198,10 +214,10 @@ class UnitsIndex:
         x = self._on_device(x)
         pool, h = self._device(x.device)
         if nprobe is None:
-            run = lambda x, **kw: native.knn_retrieve(x, pool, h, k, ratio, **kw)      # noqa: E731
+            run = lambda x, **kw: native.knn_retrieve(x, pool, h, k, ratio, metric=self.metric, weights=weights, **kw)      # noqa: E731
         else:
             ivf = self._device_ivf(x.device)
-            run = lambda x, **kw: native.ivf_retrieve(x, pool, h, k, ratio, ivf, nprobe, **kw)      # noqa: E731
+            run = lambda x, **kw: native.ivf_retrieve(x, pool, h, k, ratio, ivf, nprobe, metric=self.metric, weights=weights, **kw)      # noqa: E731
         if lengths is None:
             y, idx, dist = run(x.reshape(-1, x.shape[-1]))
             y, idx, dist = y.reshape(x.shape), idx.reshape(*x.shape[:-1], k), dist.reshape(*x.shape[:-1], k)
@@ -213,6 +229,8 @@ class UnitsIndex:
         pool = self.pool.cpu().numpy() if isinstance(self.pool, torch.Tensor) else self.pool
         st = {"pool": np.ascontiguousarray(pool, dtype=np.float32), "n_features_in_": self.n_features_in_, "source_rows": self.source_rows,
               "reduced": self.reduced}
+        if self.metric != "l2":      # (an l2 index writes the file it always wrote; a file without the key is l2)
+            st["metric"] = self.metric
         if self.ivf is not None:
             st["ivf"] = dict(self.ivf)
         return st
@@ -223,7 +241,7 @@ class UnitsIndex:
     @classmethod
     def load(cls, path):
         ck = torch.load(path, map_location="cpu", weights_only=False)      # a numpy array inside: not a weights-only file
-        ix = cls(ck["pool"], source_rows=ck.get("source_rows"), reduced=ck.get("reduced", False))
+        ix = cls(ck["pool"], source_rows=ck.get("source_rows"), reduced=ck.get("reduced", False), metric=ck.get("metric", "l2"))
         if int(ck.get("n_features_in_", ix.n_features_in_)) != ix.n_features_in_:
             raise ValueError(f"{path}: n_features_in_ {ck['n_features_in_']} against a pool of width {ix.n_features_in_}")
         if ck.get("ivf") is not None:

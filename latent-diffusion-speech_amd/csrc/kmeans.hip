@@ -9,6 +9,8 @@
 //   update   one Lloyd step in the reference's form (kmeans.py:184-198): stable counting sort of the row indices by label (integer
 //            atomics only for the per-row-block histograms), one workgroup per (cluster, 256 columns) summing its rows in index
 //            order, error by a fixed-order reduction.  No floating-point atomics: every result is independent of scheduling.
+//   cosine   (KMeansGPU mode='cosine', kmeans.py:96-105 cos_sim) the same tile with another epilogue: score = (x_n . c_k) r_k, r_k = 1 / max(|c_k|,
+//            1e-12) in the per-centre array that holds h_k otherwise; `best` is multiplied by r(x_n) after the arg-max is decided.
 //   seed     k-means++ (_kpp, kmeans.py:10-50) with a running minimum distance and a double-precision prefix; the picks stay on the device.
 #include "../../include/lds.h"
 #include "kernels.h"
@@ -27,6 +29,10 @@ constexpr int kKmOob = 0x7fff0000;         // a buffer offset beyond every slab:
 
 struct KmLens { int n, T, pad; int v[64]; };      // ragged form: B = n clips of T rows, v[b] valid rows, `pad` written beyond; n = 0: plain
 
+// the cosine row constant of a row whose fp32 sum of squares is s: 1 / max(sqrt(s), 1e-12), both operations correctly rounded
+// (F.normalize's eps; s = 4, 16, 64 give exactly 1/2, 1/4, 1/8; a zero row gets 1e12 and scores 0 against everything)
+static __device__ __forceinline__ float km_row_const(float s) { return __frcp_rn(fmaxf(__fsqrt_rn(s), 1e-12f)); }
+
 // (value, index) maximum with the lowest index among equal values: associative and commutative, so any combination order agrees
 static __device__ __forceinline__ void km_take(float v, int i, float& bv, int& bi) {
     if (v > bv || (v == bv && i < bi)) { bv = v; bi = i; }
@@ -36,7 +42,8 @@ static __device__ __forceinline__ void km_take(float v, int i, float& bv, int& b
 // wn*64 .. +64 (MFMA columns, one per lane) of a 128 x 128 tile.  grid (row blocks, centre splits).
 // LDS image of a tile: row r is 128 bytes = 8 chunks of 16; chunk q sits at position q ^ ((r >> 1) & 7), which makes the ds_read_b128 of
 // 32 consecutive rows at one chunk conflict-free.  LDS-DMA stores lane-linearly, so the swizzle is applied to the SOURCE address: one
-// wave instruction fetches 8 whole lines (8 rows x 128 bytes).
+// wave instruction fetches 8 whole lines (8 rows x 128 bytes).  MET (LDS_METRIC_*) selects the epilogue only: acc - h_k, or acc * r_k.
+template <int MET>
 __global__ void __launch_bounds__(256) kmeans_assign_kernel(const float* __restrict__ X, long long N, const float* __restrict__ Cc, const float* __restrict__ hh, int K,
                                                             int D, int cb_per_split, long long* __restrict__ labels, float* __restrict__ best_out,
                                                             float* __restrict__ pval, int* __restrict__ pidx, const KmLens lens) {
@@ -121,10 +128,12 @@ __global__ void __launch_bounds__(256) kmeans_assign_kernel(const float* __restr
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int kidx = cb * kKmB + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-                    const float hv = kidx < K ? hh[kidx] : INFINITY;
+                    const float hv = kidx < K ? hh[kidx] : (MET == LDS_METRIC_COSINE ? 0.f : INFINITY);
 #pragma unroll
                     for (int j = 0; j < 2; ++j) {
-                        const float v = acc[i][j][r] - hv;
+                        float v;
+                        if constexpr (MET == LDS_METRIC_COSINE) v = kidx < K ? acc[i][j][r] * hv : -INFINITY;
+                        else v = acc[i][j][r] - hv;
                         if (v > best[j]) { best[j] = v; bidx[j] = kidx; }
                         acc[i][j][r] = 0.f;
                     }
@@ -187,8 +196,23 @@ static __device__ __forceinline__ T km_block_sum(T v, T* sh) {
     return r;
 }
 
-// h[k] = |c_k|^2 / 2: one wave per centre, lanes stride the columns, fixed butterfly
-__global__ void __launch_bounds__(256) kmeans_prepare_kernel(const float* __restrict__ Cc, int K, int D, float* __restrict__ hh) {
+// cosine only: best[n] *= r(x_n), after the arg-max is decided.  One wave per row: the sum of squares in kmeans_prepare_kernel's order.
+// Rows at and beyond a clip's length keep their 0.
+__global__ void __launch_bounds__(256) kmeans_cos_best_kernel(const float* __restrict__ X, long long N, int D, float* __restrict__ best, const KmLens lens) {
+    const int lane = threadIdx.x & 63;
+    const long long n = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (n >= N) return;
+    if (lens.n > 0 && (int)(n % lens.T) >= lens.v[n / lens.T]) return;
+    const float* r = X + n * D;
+    float s = 0.f;
+    for (int d = lane; d < D; d += 64) s = fmaf(r[d], r[d], s);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    if (lane == 0) best[n] = __fmul_rn(best[n], km_row_const(s));
+}
+
+// h[k] = |c_k|^2 / 2 (metric L2) or r_k = 1 / max(|c_k|, 1e-12) (cosine): one wave per centre, lanes stride the columns, fixed butterfly
+__global__ void __launch_bounds__(256) kmeans_prepare_kernel(const float* __restrict__ Cc, int K, int D, float* __restrict__ hh, int metric) {
     const int lane = threadIdx.x & 63;
     const int k = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (k >= K) return;
@@ -197,7 +221,7 @@ __global__ void __launch_bounds__(256) kmeans_prepare_kernel(const float* __rest
     for (int d = lane; d < D; d += 64) s = fmaf(r[d], r[d], s);
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-    if (lane == 0) hh[k] = 0.5f * s;
+    if (lane == 0) hh[k] = metric == LDS_METRIC_COSINE ? km_row_const(s) : 0.5f * s;
 }
 
 // ---- update: stable counting sort by label, then per-cluster sums in row order ----
@@ -456,8 +480,14 @@ int km_launched(const char* fn) {
     return e == hipSuccess ? LDS_OK : set_error(LDS_EHIP, "%s: %s", fn, hipGetErrorString(e));
 }
 
-int km_assign(const char* fn, const float* X, long long N, const float* C, const float* h, int K, int D, int64_t* labels, float* best, void* ws,
+int km_check_metric(const char* fn, int metric) {
+    if (metric != LDS_METRIC_L2 && metric != LDS_METRIC_COSINE) return set_error(LDS_EINVAL, "%s: metric %d is neither LDS_METRIC_L2 nor LDS_METRIC_COSINE", fn, metric);
+    return LDS_OK;
+}
+
+int km_assign(const char* fn, int metric, const float* X, long long N, const float* C, const float* h, int K, int D, int64_t* labels, float* best, void* ws,
               size_t ws_bytes, const lds::KmLens& lens, hipStream_t s) {
+    if (int rc = km_check_metric(fn, metric)) return rc;
     if (!X || !C || !h || !labels || !ws) return set_error(LDS_EINVAL, "%s: null pointer", fn);
     const KmPlan p = km_plan(N, K, D);
     if (ws_bytes < p.bytes) return set_error(LDS_ENOMEM, "%s: workspace %zu < %zu bytes", fn, ws_bytes, p.bytes);
@@ -466,11 +496,16 @@ int km_assign(const char* fn, const float* X, long long N, const float* C, const
     int* pidx = p.KS > 1 ? (int*)(w + p.o_pidx) : nullptr;
     {
         lds::ProfScope ps(s, "kmeans_assign", 2.0 * (double)N * K * D, 4.0 * ((double)N * D + (double)K * D * ((N + 127) / 128)));
-        hipLaunchKernelGGL(lds::kmeans_assign_kernel, dim3((unsigned)((N + lds::kKmB - 1) / lds::kKmB), p.KS), dim3(256), 0, s, X, N, C, h, K, D, p.cbps,
-                           (long long*)labels, best, pval, pidx, lens);
+        const dim3 grid((unsigned)((N + lds::kKmB - 1) / lds::kKmB), p.KS);
+        if (metric == LDS_METRIC_COSINE)
+            hipLaunchKernelGGL(lds::kmeans_assign_kernel<LDS_METRIC_COSINE>, grid, dim3(256), 0, s, X, N, C, h, K, D, p.cbps, (long long*)labels, best, pval, pidx, lens);
+        else
+            hipLaunchKernelGGL(lds::kmeans_assign_kernel<LDS_METRIC_L2>, grid, dim3(256), 0, s, X, N, C, h, K, D, p.cbps, (long long*)labels, best, pval, pidx, lens);
     }
     if (p.KS > 1)
         hipLaunchKernelGGL(lds::kmeans_join_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, pval, pidx, p.KS, N, (long long*)labels, best, lens);
+    if (metric == LDS_METRIC_COSINE && best)
+        hipLaunchKernelGGL(lds::kmeans_cos_best_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, s, X, N, D, best, lens);
     return km_launched(fn);
 }
 
@@ -483,44 +518,78 @@ extern "C" int lds_kmeans_workspace_bytes(int64_t N, int K, int D, size_t* out) 
     return LDS_OK;
 }
 
+namespace {
+int km_prepare(const char* fn, int metric, const float* C, int K, int D, float* h, void* stream) {
+    if (int rc = km_check_metric(fn, metric)) return rc;
+    if (int rc = km_check_dims(fn, 1, K, D)) return rc;
+    if (!C || !h) return set_error(LDS_EINVAL, "%s: null pointer", fn);
+    hipLaunchKernelGGL(lds::kmeans_prepare_kernel, dim3((K + 3) / 4), dim3(256), 0, (hipStream_t)stream, C, K, D, h, metric);
+    return km_launched(fn);
+}
+}  // namespace
+
 extern "C" int lds_kmeans_prepare(const float* C, int K, int D, float* h, void* stream) {
-    if (int rc = km_check_dims("lds_kmeans_prepare", 1, K, D)) return rc;
-    if (!C || !h) return set_error(LDS_EINVAL, "lds_kmeans_prepare: null pointer");
-    hipLaunchKernelGGL(lds::kmeans_prepare_kernel, dim3((K + 3) / 4), dim3(256), 0, (hipStream_t)stream, C, K, D, h);
-    return km_launched("lds_kmeans_prepare");
+    return km_prepare("lds_kmeans_prepare", LDS_METRIC_L2, C, K, D, h, stream);
+}
+extern "C" int lds_kmeans_prepare_metric(const float* C, int K, int D, int metric, float* h, void* stream) {
+    return km_prepare("lds_kmeans_prepare_metric", metric, C, K, D, h, stream);
 }
 
-extern "C" int lds_kmeans_assign(const float* X, int64_t N, const float* C, const float* h, int K, int D, int64_t* labels, float* best, void* ws,
-                                 size_t ws_bytes, void* stream) {
-    if (int rc = km_check_dims("lds_kmeans_assign", N, K, D)) return rc;
+namespace {
+int km_assign_plain(const char* fn, int metric, const float* X, int64_t N, const float* C, const float* h, int K, int D, int64_t* labels, float* best, void* ws,
+                    size_t ws_bytes, void* stream) {
+    if (int rc = km_check_dims(fn, N, K, D)) return rc;
     lds::KmLens lens;
     lens.n = 0; lens.T = 1; lens.pad = 0;
     for (int i = 0; i < 64; ++i) lens.v[i] = 0;
-    return km_assign("lds_kmeans_assign", X, N, C, h, K, D, labels, best, ws, ws_bytes, lens, (hipStream_t)stream);
+    return km_assign(fn, metric, X, N, C, h, K, D, labels, best, ws, ws_bytes, lens, (hipStream_t)stream);
+}
+}  // namespace
+
+extern "C" int lds_kmeans_assign(const float* X, int64_t N, const float* C, const float* h, int K, int D, int64_t* labels, float* best, void* ws,
+                                 size_t ws_bytes, void* stream) {
+    return km_assign_plain("lds_kmeans_assign", LDS_METRIC_L2, X, N, C, h, K, D, labels, best, ws, ws_bytes, stream);
+}
+extern "C" int lds_kmeans_assign_metric(const float* X, int64_t N, const float* C, const float* h, int K, int D, int metric, int64_t* labels, float* best,
+                                        void* ws, size_t ws_bytes, void* stream) {
+    return km_assign_plain("lds_kmeans_assign_metric", metric, X, N, C, h, K, D, labels, best, ws, ws_bytes, stream);
 }
 
-extern "C" int lds_kmeans_assign_ragged(const float* X, int B, int T, const int32_t* lengths, int64_t pad_id, const float* C, const float* h, int K, int D,
-                                        int64_t* labels, float* best, void* ws, size_t ws_bytes, void* stream) {
-    if (B < 1 || B > 64 || T < 1) return set_error(LDS_EINVAL, "lds_kmeans_assign_ragged: B %d outside 1 .. 64 or T %d < 1", B, T);
-    if (!lengths) return set_error(LDS_EINVAL, "lds_kmeans_assign_ragged: null lengths");
-    if (pad_id < -2147483647LL || pad_id > 2147483647LL) return set_error(LDS_EINVAL, "lds_kmeans_assign_ragged: pad_id %lld does not fit 32 bits", (long long)pad_id);
-    if (int rc = km_check_dims("lds_kmeans_assign_ragged", (long long)B * T, K, D)) return rc;
+namespace {
+int km_assign_ragged(const char* fn, int metric, const float* X, int B, int T, const int32_t* lengths, int64_t pad_id, const float* C, const float* h, int K, int D,
+                     int64_t* labels, float* best, void* ws, size_t ws_bytes, void* stream) {
+    if (B < 1 || B > 64 || T < 1) return set_error(LDS_EINVAL, "%s: B %d outside 1 .. 64 or T %d < 1", fn, B, T);
+    if (!lengths) return set_error(LDS_EINVAL, "%s: null lengths", fn);
+    if (pad_id < -2147483647LL || pad_id > 2147483647LL) return set_error(LDS_EINVAL, "%s: pad_id %lld does not fit 32 bits", fn, (long long)pad_id);
+    if (int rc = km_check_dims(fn, (long long)B * T, K, D)) return rc;
     lds::KmLens lens;
     lens.n = B; lens.T = T; lens.pad = (int)pad_id;
     for (int i = 0; i < 64; ++i) lens.v[i] = 0;
     for (int b = 0; b < B; ++b) {
-        if (lengths[b] < 0 || lengths[b] > T) return set_error(LDS_EINVAL, "lds_kmeans_assign_ragged: lengths[%d] = %d outside 0 .. %d", b, lengths[b], T);
+        if (lengths[b] < 0 || lengths[b] > T) return set_error(LDS_EINVAL, "%s: lengths[%d] = %d outside 0 .. %d", fn, b, lengths[b], T);
         lens.v[b] = lengths[b];
     }
-    return km_assign("lds_kmeans_assign_ragged", X, (long long)B * T, C, h, K, D, labels, best, ws, ws_bytes, lens, (hipStream_t)stream);
+    return km_assign(fn, metric, X, (long long)B * T, C, h, K, D, labels, best, ws, ws_bytes, lens, (hipStream_t)stream);
+}
+}  // namespace
+
+extern "C" int lds_kmeans_assign_ragged(const float* X, int B, int T, const int32_t* lengths, int64_t pad_id, const float* C, const float* h, int K, int D,
+                                        int64_t* labels, float* best, void* ws, size_t ws_bytes, void* stream) {
+    return km_assign_ragged("lds_kmeans_assign_ragged", LDS_METRIC_L2, X, B, T, lengths, pad_id, C, h, K, D, labels, best, ws, ws_bytes, stream);
+}
+extern "C" int lds_kmeans_assign_ragged_metric(const float* X, int B, int T, const int32_t* lengths, int64_t pad_id, const float* C, const float* h, int K,
+                                               int D, int metric, int64_t* labels, float* best, void* ws, size_t ws_bytes, void* stream) {
+    return km_assign_ragged("lds_kmeans_assign_ragged_metric", metric, X, B, T, lengths, pad_id, C, h, K, D, labels, best, ws, ws_bytes, stream);
 }
 
-extern "C" int lds_kmeans_update(const float* X, const int64_t* labels, int64_t N, float* C, float* h, float* num_points, int K, int D, float* error,
-                                 void* ws, size_t ws_bytes, void* stream) {
-    if (int rc = km_check_dims("lds_kmeans_update", N, K, D)) return rc;
-    if (!X || !labels || !C || !h || !num_points || !error || !ws) return set_error(LDS_EINVAL, "lds_kmeans_update: null pointer");
+namespace {
+int km_update(const char* fn, int metric, const float* X, const int64_t* labels, int64_t N, float* C, float* h, float* num_points, int K, int D, float* error,
+              void* ws, size_t ws_bytes, void* stream) {
+    if (int rc = km_check_metric(fn, metric)) return rc;
+    if (int rc = km_check_dims(fn, N, K, D)) return rc;
+    if (!X || !labels || !C || !h || !num_points || !error || !ws) return set_error(LDS_EINVAL, "%s: null pointer", fn);
     const KmPlan p = km_plan(N, K, D);
-    if (ws_bytes < p.bytes) return set_error(LDS_ENOMEM, "lds_kmeans_update: workspace %zu < %zu bytes", ws_bytes, p.bytes);
+    if (ws_bytes < p.bytes) return set_error(LDS_ENOMEM, "%s: workspace %zu < %zu bytes", fn, ws_bytes, p.bytes);
     hipStream_t s = (hipStream_t)stream;
     char* w = (char*)ws;
     int* hist = (int*)(w + p.o_hist);
@@ -529,7 +598,7 @@ extern "C" int lds_kmeans_update(const float* X, const int64_t* labels, int64_t 
     int* sorted = (int*)(w + p.o_sorted);
     float* errpart = (float*)(w + p.o_err);
     const int ncb = (D + 255) / 256;
-    if (hipMemsetAsync(hist, 0, (size_t)p.NB * K * 4, s) != hipSuccess) return set_error(LDS_EHIP, "lds_kmeans_update: hipMemsetAsync failed");
+    if (hipMemsetAsync(hist, 0, (size_t)p.NB * K * 4, s) != hipSuccess) return set_error(LDS_EHIP, "%s: hipMemsetAsync failed", fn);
     hipLaunchKernelGGL(lds::kmeans_hist_kernel, dim3(p.NB), dim3(256), 0, s, (const long long*)labels, (long long)N, K, p.per, hist);
     hipLaunchKernelGGL(lds::kmeans_colscan_kernel, dim3((K + 255) / 256), dim3(256), 0, s, hist, p.NB, K, counts);
     hipLaunchKernelGGL(lds::kmeans_offsets_kernel, dim3(1), dim3(256), 0, s, counts, K, offsets);
@@ -539,8 +608,18 @@ extern "C" int lds_kmeans_update(const float* X, const int64_t* labels, int64_t 
         hipLaunchKernelGGL(lds::kmeans_sum_kernel, dim3(K, ncb), dim3(256), 0, s, X, sorted, offsets, counts, C, num_points, D, errpart);
     }
     hipLaunchKernelGGL(lds::kmeans_finish_kernel, dim3(1), dim3(256), 0, s, errpart, (long long)K * ncb, counts, K, num_points, error);
-    hipLaunchKernelGGL(lds::kmeans_prepare_kernel, dim3((K + 3) / 4), dim3(256), 0, s, C, K, D, h);
-    return km_launched("lds_kmeans_update");
+    hipLaunchKernelGGL(lds::kmeans_prepare_kernel, dim3((K + 3) / 4), dim3(256), 0, s, C, K, D, h, metric);
+    return km_launched(fn);
+}
+}  // namespace
+
+extern "C" int lds_kmeans_update(const float* X, const int64_t* labels, int64_t N, float* C, float* h, float* num_points, int K, int D, float* error,
+                                 void* ws, size_t ws_bytes, void* stream) {
+    return km_update("lds_kmeans_update", LDS_METRIC_L2, X, labels, N, C, h, num_points, K, D, error, ws, ws_bytes, stream);
+}
+extern "C" int lds_kmeans_update_metric(const float* X, const int64_t* labels, int64_t N, float* C, float* h, float* num_points, int K, int D, int metric,
+                                        float* error, void* ws, size_t ws_bytes, void* stream) {
+    return km_update("lds_kmeans_update_metric", metric, X, labels, N, C, h, num_points, K, D, error, ws, ws_bytes, stream);
 }
 
 extern "C" int lds_kmeans_seed(const float* X, int64_t N, int D, int K, int64_t first_index, const float* uniforms, float* C, int64_t* picked, void* ws,

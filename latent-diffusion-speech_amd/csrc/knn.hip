@@ -9,6 +9,10 @@
 //   splits   a workgroup walks a contiguous range of pool blocks; the per-split lists go to the workspace as [split][N][KT].
 //   blend    one wave per query row merges the splits' lists in split order, recomputes the k distances directly as sum (x - p)^2, forms
 //            w = (1 / max(d, 1e-12))^2, normalises and writes y = (1 - ratio) x + ratio sum w_j p_j.
+//   cosine   (kNN-VC's matching) the same tiles with another epilogue: score = (x_n . p_m) r_m, r_m = 1 / max(|p_m|, 1e-12) in the per-row array
+//            that holds h_m otherwise; the reported score is multiplied by r(x_n) after the order is decided (the cosine similarity); the
+//            blend's distance is 1/2 sum (x r_x - p_j r_j)^2 = 1 - cos, recomputed directly, and its weights are the inverse squares of the
+//            distances or uniform (kNN-VC's plain mean) -- over the ORIGINAL pool rows in both cases.
 // No floating-point atomics; every slot of the workspace that is read was written by the same call.
 #include "../../include/lds.h"
 #include "../../include/lds_test.h"
@@ -30,6 +34,18 @@ constexpr int kKnMaxK = 8;
 
 struct KnLens { int n, T; int v[64]; };    // ragged form: B = n clips of T rows, v[b] valid rows; n = 0: plain
 
+// the cosine row constant of a row whose fp32 sum of squares is s (kmeans.hip km_row_const; include/lds.h): 1 / max(sqrt(s), 1e-12)
+static __device__ __forceinline__ float kn_row_const(float s) { return __frcp_rn(fmaxf(__fsqrt_rn(s), 1e-12f)); }
+// a row's sum of squares by one wave: lanes stride the columns, one fmaf chain per lane, fixed butterfly (knn_prepare_kernel's order,
+// so that a query equal to a pool row gets that row's constant)
+static __device__ __forceinline__ float kn_row_sumsq(const float* __restrict__ r, int D, int lane) {
+    float s = 0.f;
+    for (int d = lane; d < D; d += 64) s = fmaf(r[d], r[d], s);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    return s;
+}
+
 // (score, index) order of the lists: higher score first, the lower index among equal scores
 static __device__ __forceinline__ bool kn_before(float v, int i, float w, int j) { return v > w || (v == w && i < j); }
 
@@ -37,7 +53,8 @@ static __device__ __forceinline__ bool kn_before(float v, int i, float w, int j)
 // wn*64 .. +64 (MFMA columns, one per lane) of a 128 x 128 tile.  grid (query row blocks, splits).  The LDS image of a tile and the swizzle
 // on the source address are kmeans_assign_kernel's.  Pool block b (128 rows) lies in slab b / slab_blocks; a block never straddles two slabs.
 // A lane meets the pool rows of a query column in increasing index order, so inserting on a strictly greater score keeps the lower index first.
-template <int KT>
+// MET (LDS_METRIC_*) selects the epilogue only: acc - h_m, or acc * r_m.
+template <int KT, int MET>
 __global__ void __launch_bounds__(256) knn_topk_kernel(const float* __restrict__ X, long long N, const float* __restrict__ P, const float* __restrict__ hh,
                                                        int M, int D, int slab_blocks, int pb_per_split, float* __restrict__ lval, int* __restrict__ lidx) {
     __shared__ __attribute__((aligned(16))) float smem[4 * kKnTile];      // 2 stages x (X tile, P tile) = 64 KB
@@ -130,10 +147,12 @@ __global__ void __launch_bounds__(256) knn_topk_kernel(const float* __restrict__
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int m = pb * kKnB + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-                    const float hv = m < M ? hh[m] : INFINITY;
+                    const float hv = m < M ? hh[m] : (MET == LDS_METRIC_COSINE ? 0.f : INFINITY);
 #pragma unroll
                     for (int j = 0; j < 2; ++j) {
-                        const float v = acc[i][j][r] - hv;
+                        float v;
+                        if constexpr (MET == LDS_METRIC_COSINE) v = m < M ? acc[i][j][r] * hv : -INFINITY;
+                        else v = acc[i][j][r] - hv;
                         acc[i][j][r] = 0.f;
                         if (v > lv[j][KT - 1]) {      // (a NaN score, or -inf beyond M, never enters)
 #pragma unroll
@@ -223,12 +242,34 @@ __global__ void __launch_bounds__(256) knn_select_kernel(const float* __restrict
         }
 }
 
+// the cosine search's select: one wave per query row (4 rows per workgroup), every lane merges the row's lists; the scores leave multiplied
+// by r(x_n) -- after the order is decided -- so that they are cosine similarities.  A missing place keeps -1 / -inf.
+__global__ void __launch_bounds__(256) knn_select_cos_kernel(const float* __restrict__ X, int D, const float* __restrict__ lval, const int* __restrict__ lidx, int S,
+                                                             int KT, long long N, int M, int k, int* __restrict__ idx, float* __restrict__ score) {
+    const int lane = threadIdx.x & 63;
+    const long long n = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (n >= N) return;
+    float bv[kKnMaxK];
+    int bi[kKnMaxK];
+    kn_merge(lval, lidx, S, KT, N, n, M, bv, bi);
+    const float rx = kn_row_const(kn_row_sumsq(X + n * D, D, lane));
+#pragma unroll
+    for (int q = 0; q < kKnMaxK; ++q)
+        if (q < k && lane == q) {
+            idx[n * k + q] = bi[q] == kKnNone ? -1 : bi[q];
+            if (score) score[n * k + q] = bi[q] == kKnNone ? -INFINITY : __fmul_rn(bv[q], rx);
+        }
+}
+
 // One wave per query row (4 rows per workgroup).  Every lane merges the row's lists (the same addresses in all lanes); lane l then takes the
 // columns 4 (l + 64 t) .. + 4 of x and of the k pool rows: d_j = sum (x - p_j)^2 by one fmaf chain per lane in ascending column order and
 // a fixed butterfly over the lanes, d_j = max(d_j, 1e-12), w_j = (1 / d_j)^2, normalised by their sum taken for j ascending;
 // z = w_0 p_0, then fmaf for j ascending; y = x at ratio 0, z at ratio 1, fmaf(ratio, z, (1 - ratio) x) between.  Every pool index is clamped
 // into [0, M) before it forms an address; an entry that is no pool row has weight 0.  Rows at and beyond a clip's length: y = 0, idx = -1, dist = 0.
-__global__ void __launch_bounds__(256) knn_blend_kernel(const float* __restrict__ X, long long N, const float* __restrict__ P, int M, int D,
+// MET = cosine: r_x = the row constant of x formed by this wave, r_j = hh[index] (lds_knn_prepare_metric's, original pool order),
+// d_j = 1/2 sum (x r_x - p_j r_j)^2 in the same order, floored alike.  WTS = uniform: w_j = 1 / found over the entries that are pool rows.
+template <int MET, int WTS>
+__global__ void __launch_bounds__(256) knn_blend_kernel(const float* __restrict__ X, long long N, const float* __restrict__ P, const float* __restrict__ hh, int M, int D,
                                                         const float* __restrict__ lval, const int* __restrict__ lidx, int S, int KT, int k, float ratio,
                                                         float* __restrict__ Y, int* __restrict__ idx, float* __restrict__ dist, const KnLens lens) {
     const int lane = threadIdx.x & 63;
@@ -260,31 +301,60 @@ __global__ void __launch_bounds__(256) knn_blend_kernel(const float* __restrict_
     float d[kKnMaxK];
 #pragma unroll
     for (int j = 0; j < kKnMaxK; ++j) d[j] = 0.f;
-    for (int t = lane; t < D4; t += 64) {
-        const f32x4 xv = x[t];
+    if constexpr (MET == LDS_METRIC_COSINE) {
+        const float rx = kn_row_const(kn_row_sumsq(X + n * D, D, lane));
+        float rj[kKnMaxK];
 #pragma unroll
-        for (int j = 0; j < kKnMaxK; ++j)
-            if (j < k) {
-                const f32x4 pv = pr[j][t];
+        for (int j = 0; j < kKnMaxK; ++j) rj[j] = ok[j] ? hh[bi[j]] : 0.f;
+        for (int t = lane; t < D4; t += 64) {
+            const f32x4 xv = x[t];
 #pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float u = xv[e] - pv[e];
-                    d[j] = fmaf(u, u, d[j]);
+            for (int j = 0; j < kKnMaxK; ++j)
+                if (j < k) {
+                    const f32x4 pv = pr[j][t];
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const float u = __fsub_rn(__fmul_rn(xv[e], rx), __fmul_rn(pv[e], rj[j]));
+                        d[j] = fmaf(u, u, d[j]);
+                    }
                 }
-            }
+        }
+    } else {
+        for (int t = lane; t < D4; t += 64) {
+            const f32x4 xv = x[t];
+#pragma unroll
+            for (int j = 0; j < kKnMaxK; ++j)
+                if (j < k) {
+                    const f32x4 pv = pr[j][t];
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const float u = xv[e] - pv[e];
+                        d[j] = fmaf(u, u, d[j]);
+                    }
+                }
+        }
     }
     float w[kKnMaxK], sum = 0.f;
+    int found = 0;
 #pragma unroll
     for (int j = 0; j < kKnMaxK; ++j) {
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) d[j] += __shfl_xor(d[j], o, 64);
+        if constexpr (MET == LDS_METRIC_COSINE) d[j] = __fmul_rn(0.5f, d[j]);
         d[j] = fmaxf(d[j], 1e-12f);
         const float r = __fdiv_rn(1.0f, d[j]);
         w[j] = ok[j] ? __fmul_rn(r, r) : 0.f;
         if (j < k) sum = __fadd_rn(sum, w[j]);
+        found += ok[j] ? 1 : 0;
     }
+    if constexpr (WTS == LDS_WEIGHTS_UNIFORM) {
+        const float u = __fdiv_rn(1.0f, (float)(found > 0 ? found : 1));
 #pragma unroll
-    for (int j = 0; j < kKnMaxK; ++j) w[j] = __fdiv_rn(w[j], sum);
+        for (int j = 0; j < kKnMaxK; ++j) w[j] = ok[j] ? u : 0.f;
+    } else {
+#pragma unroll
+        for (int j = 0; j < kKnMaxK; ++j) w[j] = __fdiv_rn(w[j], sum);
+    }
     const float keep = 1.0f - ratio;
     for (int t = lane; t < D4; t += 64) {
         const f32x4 xv = x[t];
@@ -314,8 +384,9 @@ __global__ void __launch_bounds__(256) knn_blend_kernel(const float* __restrict_
         }
 }
 
-// h[m] = |p_m|^2 / 2: one wave per pool row, lanes stride the columns, fixed butterfly (a duplicated row gets the same h)
-__global__ void __launch_bounds__(256) knn_prepare_kernel(const float* __restrict__ P, long long M, int D, float* __restrict__ hh) {
+// h[m] = |p_m|^2 / 2 (metric L2) or r_m = 1 / max(|p_m|, 1e-12) (cosine): one wave per pool row, lanes stride the columns, fixed butterfly
+// (a duplicated row gets the same value)
+__global__ void __launch_bounds__(256) knn_prepare_kernel(const float* __restrict__ P, long long M, int D, float* __restrict__ hh, int metric) {
     const int lane = threadIdx.x & 63;
     const long long m = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (m >= M) return;
@@ -324,7 +395,7 @@ __global__ void __launch_bounds__(256) knn_prepare_kernel(const float* __restric
     for (int d = lane; d < D; d += 64) s = fmaf(r[d], r[d], s);
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-    if (lane == 0) hh[m] = 0.5f * s;
+    if (lane == 0) hh[m] = metric == LDS_METRIC_COSINE ? kn_row_const(s) : 0.5f * s;
 }
 
 }  // namespace lds
@@ -388,19 +459,58 @@ int kn_launched(const char* fn) {
 
 bool kn_misaligned(const void* p) { return ((uintptr_t)p & 15) != 0; }
 
-void kn_topk(const KnPlan& p, const float* X, long long N, const float* P, const float* h, int M, int D, float* lval, int* lidx, hipStream_t s) {
-    lds::ProfScope ps(s, "knn_topk", 2.0 * (double)N * M * D, 4.0 * ((double)N * D + (double)M * D * ((N + 127) / 128)));
-    const dim3 grid((unsigned)((N + lds::kKnB - 1) / lds::kKnB), p.S);
-    switch (p.KT) {
-        case 1: hipLaunchKernelGGL(lds::knn_topk_kernel<1>, grid, dim3(256), 0, s, X, N, P, h, M, D, p.slab_blocks, p.pbps, lval, lidx); break;
-        case 2: hipLaunchKernelGGL(lds::knn_topk_kernel<2>, grid, dim3(256), 0, s, X, N, P, h, M, D, p.slab_blocks, p.pbps, lval, lidx); break;
-        case 4: hipLaunchKernelGGL(lds::knn_topk_kernel<4>, grid, dim3(256), 0, s, X, N, P, h, M, D, p.slab_blocks, p.pbps, lval, lidx); break;
-        default: hipLaunchKernelGGL(lds::knn_topk_kernel<8>, grid, dim3(256), 0, s, X, N, P, h, M, D, p.slab_blocks, p.pbps, lval, lidx); break;
-    }
+int kn_check_metric(const char* fn, int metric, int weights) {
+    if (metric != LDS_METRIC_L2 && metric != LDS_METRIC_COSINE) return set_error(LDS_EINVAL, "%s: metric %d is neither LDS_METRIC_L2 nor LDS_METRIC_COSINE", fn, metric);
+    if (weights != LDS_WEIGHTS_INVERSE_SQUARE && weights != LDS_WEIGHTS_UNIFORM)
+        return set_error(LDS_EINVAL, "%s: weights %d is neither LDS_WEIGHTS_INVERSE_SQUARE nor LDS_WEIGHTS_UNIFORM", fn, weights);
+    return LDS_OK;
 }
 
-int kn_search(const char* fn, const float* X, long long N, const float* P, const float* h, long long M, int D, int k, int slab_rows, int splits,
+void kn_topk(const KnPlan& p, int metric, const float* X, long long N, const float* P, const float* h, int M, int D, float* lval, int* lidx, hipStream_t s) {
+    lds::ProfScope ps(s, "knn_topk", 2.0 * (double)N * M * D, 4.0 * ((double)N * D + (double)M * D * ((N + 127) / 128)));
+    const dim3 grid((unsigned)((N + lds::kKnB - 1) / lds::kKnB), p.S);
+#define LDS_KNN_TOPK(KT_)                                                                                                                              \
+    if (metric == LDS_METRIC_COSINE)                                                                                                                   \
+        hipLaunchKernelGGL((lds::knn_topk_kernel<KT_, LDS_METRIC_COSINE>), grid, dim3(256), 0, s, X, N, P, h, M, D, p.slab_blocks, p.pbps, lval, lidx); \
+    else                                                                                                                                               \
+        hipLaunchKernelGGL((lds::knn_topk_kernel<KT_, LDS_METRIC_L2>), grid, dim3(256), 0, s, X, N, P, h, M, D, p.slab_blocks, p.pbps, lval, lidx)
+    switch (p.KT) {
+        case 1: LDS_KNN_TOPK(1); break;
+        case 2: LDS_KNN_TOPK(2); break;
+        case 4: LDS_KNN_TOPK(4); break;
+        default: LDS_KNN_TOPK(8); break;
+    }
+#undef LDS_KNN_TOPK
+}
+
+// the search's last step: the merged lists as idx / score; the cosine scores leave as similarities
+void kn_select(int metric, const float* X, int D, const float* lval, const int* lidx, int S, int KT, long long N, int M, int k, int32_t* idx, float* score, hipStream_t s) {
+    if (metric == LDS_METRIC_COSINE)
+        hipLaunchKernelGGL(lds::knn_select_cos_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, s, X, D, lval, lidx, S, KT, N, M, k, (int*)idx, score);
+    else
+        hipLaunchKernelGGL(lds::knn_select_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, lval, lidx, S, KT, N, M, k, (int*)idx, score);
+}
+
+// h: the per-row array of the ORIGINAL pool (read in cosine mode only)
+void kn_blend(int metric, int weights, const float* X, long long N, const float* P, const float* h, int M, int D, const float* lval, const int* lidx, int S, int KT,
+              int k, float ratio, float* Y, int32_t* idx, float* dist, const lds::KnLens& lens, hipStream_t s) {
+    lds::ProfScope ps(s, "knn_blend", 5.0 * (double)N * k * D, 4.0 * (double)N * D * (2.0 * k + 3.0));
+    const dim3 grid((unsigned)((N + 3) / 4));
+#define LDS_KNN_BLEND(MET_, WTS_) \
+    hipLaunchKernelGGL((lds::knn_blend_kernel<MET_, WTS_>), grid, dim3(256), 0, s, X, N, P, h, M, D, lval, lidx, S, KT, k, ratio, Y, (int*)idx, dist, lens)
+    if (metric == LDS_METRIC_COSINE) {
+        if (weights == LDS_WEIGHTS_UNIFORM) LDS_KNN_BLEND(LDS_METRIC_COSINE, LDS_WEIGHTS_UNIFORM);
+        else LDS_KNN_BLEND(LDS_METRIC_COSINE, LDS_WEIGHTS_INVERSE_SQUARE);
+    } else {
+        if (weights == LDS_WEIGHTS_UNIFORM) LDS_KNN_BLEND(LDS_METRIC_L2, LDS_WEIGHTS_UNIFORM);
+        else LDS_KNN_BLEND(LDS_METRIC_L2, LDS_WEIGHTS_INVERSE_SQUARE);
+    }
+#undef LDS_KNN_BLEND
+}
+
+int kn_search(const char* fn, int metric, const float* X, long long N, const float* P, const float* h, long long M, int D, int k, int slab_rows, int splits,
               int32_t* idx, float* score, void* ws, size_t ws_bytes, hipStream_t s) {
+    if (int rc = kn_check_metric(fn, metric, LDS_WEIGHTS_INVERSE_SQUARE)) return rc;
     if (int rc = kn_check_dims(fn, N, M, D, k)) return rc;
     if (!X || !P || !h || !idx || !ws) return set_error(LDS_EINVAL, "%s: null pointer", fn);
     if (kn_misaligned(X) || kn_misaligned(P)) return set_error(LDS_EINVAL, "%s: X and P must be 16-byte aligned", fn);
@@ -408,13 +518,14 @@ int kn_search(const char* fn, const float* X, long long N, const float* P, const
     if (ws_bytes < p.bytes) return set_error(LDS_ENOMEM, "%s: workspace %zu < %zu bytes", fn, ws_bytes, p.bytes);
     float* lval = (float*)((char*)ws + p.o_val);
     int* lidx = (int*)((char*)ws + p.o_idx);
-    kn_topk(p, X, N, P, h, (int)M, D, lval, lidx, s);
-    hipLaunchKernelGGL(lds::knn_select_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, lval, lidx, p.S, p.KT, N, (int)M, k, (int*)idx, score);
+    kn_topk(p, metric, X, N, P, h, (int)M, D, lval, lidx, s);
+    kn_select(metric, X, D, lval, lidx, p.S, p.KT, N, (int)M, k, idx, score, s);
     return kn_launched(fn);
 }
 
-int kn_retrieve(const char* fn, const float* X, long long N, const float* P, const float* h, long long M, int D, int k, float ratio, float* Y, int32_t* idx,
-                float* dist, void* ws, size_t ws_bytes, const lds::KnLens& lens, hipStream_t s) {
+int kn_retrieve(const char* fn, int metric, int weights, const float* X, long long N, const float* P, const float* h, long long M, int D, int k, float ratio,
+                float* Y, int32_t* idx, float* dist, void* ws, size_t ws_bytes, const lds::KnLens& lens, hipStream_t s) {
+    if (int rc = kn_check_metric(fn, metric, weights)) return rc;
     if (int rc = kn_check_dims(fn, N, M, D, k)) return rc;
     if (!(ratio >= 0.f && ratio <= 1.f)) return set_error(LDS_EINVAL, "%s: ratio %g outside 0 .. 1", fn, (double)ratio);
     if (!X || !P || !h || !Y || !ws) return set_error(LDS_EINVAL, "%s: null pointer", fn);
@@ -423,12 +534,8 @@ int kn_retrieve(const char* fn, const float* X, long long N, const float* P, con
     if (ws_bytes < p.bytes) return set_error(LDS_ENOMEM, "%s: workspace %zu < %zu bytes", fn, ws_bytes, p.bytes);
     float* lval = (float*)((char*)ws + p.o_val);
     int* lidx = (int*)((char*)ws + p.o_idx);
-    kn_topk(p, X, N, P, h, (int)M, D, lval, lidx, s);
-    {
-        lds::ProfScope ps(s, "knn_blend", 5.0 * (double)N * k * D, 4.0 * (double)N * D * (2.0 * k + 3.0));
-        hipLaunchKernelGGL(lds::knn_blend_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, s, X, N, P, (int)M, D, lval, lidx, p.S, p.KT, k, ratio, Y,
-                           (int*)idx, dist, lens);
-    }
+    kn_topk(p, metric, X, N, P, h, (int)M, D, lval, lidx, s);
+    kn_blend(metric, weights, X, N, P, h, (int)M, D, lval, lidx, p.S, p.KT, k, ratio, Y, idx, dist, lens, s);
     return kn_launched(fn);
 }
 
@@ -441,11 +548,33 @@ lds::KnLens kn_plain() {
 
 }  // namespace
 
+namespace {
+int kn_prepare(const char* fn, int metric, const float* P, int64_t M, int D, float* h, void* stream) {
+    if (int rc = kn_check_metric(fn, metric, LDS_WEIGHTS_INVERSE_SQUARE)) return rc;
+    if (int rc = kn_check_dims(fn, 1, M, D, 1)) return rc;
+    if (!P || !h) return set_error(LDS_EINVAL, "%s: null pointer", fn);
+    hipLaunchKernelGGL(lds::knn_prepare_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, (hipStream_t)stream, P, (long long)M, D, h, metric);
+    return kn_launched(fn);
+}
+
+int kn_ragged_lens(const char* fn, int B, int T, const int32_t* lengths, lds::KnLens& lens) {
+    if (B < 1 || B > 64 || T < 1) return set_error(LDS_EINVAL, "%s: B %d outside 1 .. 64 or T %d < 1", fn, B, T);
+    if (!lengths) return set_error(LDS_EINVAL, "%s: null lengths", fn);
+    lens = kn_plain();
+    lens.n = B; lens.T = T;
+    for (int b = 0; b < B; ++b) {
+        if (lengths[b] < 0 || lengths[b] > T) return set_error(LDS_EINVAL, "%s: lengths[%d] = %d outside 0 .. %d", fn, b, lengths[b], T);
+        lens.v[b] = lengths[b];
+    }
+    return LDS_OK;
+}
+}  // namespace
+
 extern "C" int lds_knn_prepare(const float* P, int64_t M, int D, float* h, void* stream) {
-    if (int rc = kn_check_dims("lds_knn_prepare", 1, M, D, 1)) return rc;
-    if (!P || !h) return set_error(LDS_EINVAL, "lds_knn_prepare: null pointer");
-    hipLaunchKernelGGL(lds::knn_prepare_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, (hipStream_t)stream, P, (long long)M, D, h);
-    return kn_launched("lds_knn_prepare");
+    return kn_prepare("lds_knn_prepare", LDS_METRIC_L2, P, M, D, h, stream);
+}
+extern "C" int lds_knn_prepare_metric(const float* P, int64_t M, int D, int metric, float* h, void* stream) {
+    return kn_prepare("lds_knn_prepare_metric", metric, P, M, D, h, stream);
 }
 
 extern "C" int lds_knn_workspace_bytes(int64_t N, int64_t M, int D, int k, size_t* out) {
@@ -457,33 +586,56 @@ extern "C" int lds_knn_workspace_bytes(int64_t N, int64_t M, int D, int k, size_
 
 extern "C" int lds_knn_search(const float* X, int64_t N, const float* P, const float* h, int64_t M, int D, int k, int32_t* idx, float* score, void* ws,
                               size_t ws_bytes, void* stream) {
-    return kn_search("lds_knn_search", X, N, P, h, M, D, k, 0, 0, idx, score, ws, ws_bytes, (hipStream_t)stream);
+    return kn_search("lds_knn_search", LDS_METRIC_L2, X, N, P, h, M, D, k, 0, 0, idx, score, ws, ws_bytes, (hipStream_t)stream);
+}
+extern "C" int lds_knn_search_metric(const float* X, int64_t N, const float* P, const float* h, int64_t M, int D, int k, int metric, int32_t* idx, float* score,
+                                     void* ws, size_t ws_bytes, void* stream) {
+    return kn_search("lds_knn_search_metric", metric, X, N, P, h, M, D, k, 0, 0, idx, score, ws, ws_bytes, (hipStream_t)stream);
 }
 
 extern "C" int lds_knn_retrieve(const float* X, int64_t N, const float* P, const float* h, int64_t M, int D, int k, float ratio, float* Y, int32_t* idx,
                                 float* dist, void* ws, size_t ws_bytes, void* stream) {
-    return kn_retrieve("lds_knn_retrieve", X, N, P, h, M, D, k, ratio, Y, idx, dist, ws, ws_bytes, kn_plain(), (hipStream_t)stream);
+    return kn_retrieve("lds_knn_retrieve", LDS_METRIC_L2, LDS_WEIGHTS_INVERSE_SQUARE, X, N, P, h, M, D, k, ratio, Y, idx, dist, ws, ws_bytes, kn_plain(),
+                       (hipStream_t)stream);
+}
+extern "C" int lds_knn_retrieve_metric(const float* X, int64_t N, const float* P, const float* h, int64_t M, int D, int k, int metric, int weights, float ratio,
+                                       float* Y, int32_t* idx, float* dist, void* ws, size_t ws_bytes, void* stream) {
+    return kn_retrieve("lds_knn_retrieve_metric", metric, weights, X, N, P, h, M, D, k, ratio, Y, idx, dist, ws, ws_bytes, kn_plain(), (hipStream_t)stream);
 }
 
 extern "C" int lds_knn_retrieve_ragged(const float* X, int B, int T, const int32_t* lengths, const float* P, const float* h, int64_t M, int D, int k,
                                        float ratio, float* Y, int32_t* idx, float* dist, void* ws, size_t ws_bytes, void* stream) {
-    if (B < 1 || B > 64 || T < 1) return set_error(LDS_EINVAL, "lds_knn_retrieve_ragged: B %d outside 1 .. 64 or T %d < 1", B, T);
-    if (!lengths) return set_error(LDS_EINVAL, "lds_knn_retrieve_ragged: null lengths");
-    lds::KnLens lens = kn_plain();
-    lens.n = B; lens.T = T;
-    for (int b = 0; b < B; ++b) {
-        if (lengths[b] < 0 || lengths[b] > T) return set_error(LDS_EINVAL, "lds_knn_retrieve_ragged: lengths[%d] = %d outside 0 .. %d", b, lengths[b], T);
-        lens.v[b] = lengths[b];
-    }
-    return kn_retrieve("lds_knn_retrieve_ragged", X, (long long)B * T, P, h, M, D, k, ratio, Y, idx, dist, ws, ws_bytes, lens, (hipStream_t)stream);
+    lds::KnLens lens;
+    if (int rc = kn_ragged_lens("lds_knn_retrieve_ragged", B, T, lengths, lens)) return rc;
+    return kn_retrieve("lds_knn_retrieve_ragged", LDS_METRIC_L2, LDS_WEIGHTS_INVERSE_SQUARE, X, (long long)B * T, P, h, M, D, k, ratio, Y, idx, dist, ws, ws_bytes,
+                       lens, (hipStream_t)stream);
 }
+extern "C" int lds_knn_retrieve_ragged_metric(const float* X, int B, int T, const int32_t* lengths, const float* P, const float* h, int64_t M, int D, int k,
+                                              int metric, int weights, float ratio, float* Y, int32_t* idx, float* dist, void* ws, size_t ws_bytes,
+                                              void* stream) {
+    lds::KnLens lens;
+    if (int rc = kn_ragged_lens("lds_knn_retrieve_ragged_metric", B, T, lengths, lens)) return rc;
+    return kn_retrieve("lds_knn_retrieve_ragged_metric", metric, weights, X, (long long)B * T, P, h, M, D, k, ratio, Y, idx, dist, ws, ws_bytes, lens,
+                       (hipStream_t)stream);
+}
+
+namespace {
+int kn_test_search(const char* fn, int metric, const float* X, int64_t N, const float* P, const float* h, int64_t M, int D, int k, int slab_rows, int splits,
+                   int32_t* idx, float* score, void* ws, size_t ws_bytes, void* stream) {
+    if (slab_rows < lds::kKnB || slab_rows % lds::kKnB || (D >= 8 && D <= 4096 && slab_rows > kn_slab_rows(D)))
+        return set_error(LDS_EINVAL, "%s: slab_rows %d must be a multiple of 128 that one descriptor holds", fn, slab_rows);
+    if (splits < 1 || splits > kKnMaxSplits) return set_error(LDS_EINVAL, "%s: splits %d outside 1 .. %d", fn, splits, kKnMaxSplits);
+    return kn_search(fn, metric, X, N, P, h, M, D, k, slab_rows, splits, idx, score, ws, ws_bytes, (hipStream_t)stream);
+}
+}  // namespace
 
 extern "C" int lds_test_knn_search(const float* X, int64_t N, const float* P, const float* h, int64_t M, int D, int k, int slab_rows, int splits, int32_t* idx,
                                    float* score, void* ws, size_t ws_bytes, void* stream) {
-    if (slab_rows < lds::kKnB || slab_rows % lds::kKnB || (D >= 8 && D <= 4096 && slab_rows > kn_slab_rows(D)))
-        return set_error(LDS_EINVAL, "lds_test_knn_search: slab_rows %d must be a multiple of 128 that one descriptor holds", slab_rows);
-    if (splits < 1 || splits > kKnMaxSplits) return set_error(LDS_EINVAL, "lds_test_knn_search: splits %d outside 1 .. %d", splits, kKnMaxSplits);
-    return kn_search("lds_test_knn_search", X, N, P, h, M, D, k, slab_rows, splits, idx, score, ws, ws_bytes, (hipStream_t)stream);
+    return kn_test_search("lds_test_knn_search", LDS_METRIC_L2, X, N, P, h, M, D, k, slab_rows, splits, idx, score, ws, ws_bytes, stream);
+}
+extern "C" int lds_test_knn_search_metric(const float* X, int64_t N, const float* P, const float* h, int64_t M, int D, int k, int metric, int slab_rows, int splits,
+                                          int32_t* idx, float* score, void* ws, size_t ws_bytes, void* stream) {
+    return kn_test_search("lds_test_knn_search_metric", metric, X, N, P, h, M, D, k, slab_rows, splits, idx, score, ws, ws_bytes, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -622,8 +774,8 @@ __global__ void __launch_bounds__(256) ivf_fill_kernel(const int* __restrict__ p
 // and segment seg of the list (wstart[l] <= w < wstart[l + 1], w - wstart[l] = chunk * segments + seg) and walks that segment's pool blocks in
 // PL; the workgroup of segment 0 also writes the empty lists of the segments the list does not have.  The X descriptor spans all of X
 // (N D 4 <= kKnOob bytes, checked by the driver) and a lane's offset is its bucket entry's row: the gather.  Tile columns beyond the bucket
-// repeat its last entry and are not stored; tile rows beyond the list's length score -inf and never enter a list.
-template <int KT>
+// repeat its last entry and are not stored; tile rows beyond the list's length score -inf and never enter a list.  MET as in knn_topk_kernel.
+template <int KT, int MET>
 __global__ void __launch_bounds__(256) ivf_scan_kernel(const float* __restrict__ X, long long N, const float* __restrict__ PL, const float* __restrict__ hl,
                                                        int Mp, int D, int slab_blocks, const int* __restrict__ order, int M,
                                                        const int* __restrict__ llen, const int* __restrict__ lrow, const int* __restrict__ lblk,
@@ -731,10 +883,12 @@ __global__ void __launch_bounds__(256) ivf_scan_kernel(const float* __restrict__
                 for (int r = 0; r < 16; ++r) {
                     const int t = wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;      // the row inside the block
                     const int m = (pb - lb0) * kKnB + t;                                   // the row inside the list
-                    const float hv = m < len ? hl[(long long)pb * kKnB + t] : INFINITY;
+                    const float hv = m < len ? hl[(long long)pb * kKnB + t] : (MET == LDS_METRIC_COSINE ? 0.f : INFINITY);
 #pragma unroll
                     for (int j = 0; j < 2; ++j) {
-                        const float v = acc[i][j][r] - hv;
+                        float v;
+                        if constexpr (MET == LDS_METRIC_COSINE) v = m < len ? acc[i][j][r] * hv : -INFINITY;
+                        else v = acc[i][j][r] - hv;
                         acc[i][j][r] = 0.f;
                         if (v > lv[j][KT - 1]) {      // (a NaN score, or -inf beyond the list, never enters)
 #pragma unroll
@@ -851,6 +1005,7 @@ struct IvfIndex {               // the arguments every lds_ivf_* entry adds
     const float *PL, *hl;
     long long Mp;
     int nprobe;
+    int metric;                 // LDS_METRIC_*: hc / hl (and the original pool's h, for the blend) hold h or r accordingly
 };
 
 int ivf_check_index(const char* fn, const IvfIndex& ix, long long M) {
@@ -873,7 +1028,7 @@ void ivf_lists(const IvfPlan& p, const float* X, long long N, long long M, int D
     {
         float* cval = (float*)(w + p.coarse.o_val);
         int* cidx = (int*)(w + p.coarse.o_idx);
-        kn_topk(p.coarse, X, N, ix.C, ix.hc, ix.nlist, D, cval, cidx, s);
+        kn_topk(p.coarse, ix.metric, X, N, ix.C, ix.hc, ix.nlist, D, cval, cidx, s);
         hipLaunchKernelGGL(lds::knn_select_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, cval, cidx, p.coarse.S, p.coarse.KT, N, ix.nlist, ix.nprobe,
                            probe, (float*)nullptr);
     }
@@ -883,9 +1038,10 @@ void ivf_lists(const IvfPlan& p, const float* X, long long N, long long M, int D
     hipLaunchKernelGGL(lds::ivf_plan_kernel, dim3(1), dim3(1024), 0, s, (const long long*)ix.offsets, ix.nlist, M, ix.Mp, cnt, llen, lrow, lblk, bstart, wstart);
     hipLaunchKernelGGL(lds::ivf_fill_kernel, pg, dim3(256), 0, s, probe, p.pairs, ix.nprobe, ix.nlist, bstart, cnt, bq);
     lds::ProfScope ps(s, "ivf_scan", 2.0 * (double)N * ix.nprobe * ((double)M / ix.nlist) * D, 4.0 * ((double)N * ix.nprobe * D + (double)ix.Mp * D));
-#define LDS_IVF_SCAN(KT_)                                                                                                                             \
-    hipLaunchKernelGGL(lds::ivf_scan_kernel<KT_>, dim3(p.wmax), dim3(256), 0, s, X, N, ix.PL, ix.hl, (int)ix.Mp, D, p.slab_blocks, (const int*)ix.order, \
-                       (int)M, llen, lrow, lblk, bstart, wstart, ix.nlist, bq, lval, lidx)
+#define LDS_IVF_SCAN_ARGS dim3(p.wmax), dim3(256), 0, s, X, N, ix.PL, ix.hl, (int)ix.Mp, D, p.slab_blocks, (const int*)ix.order, (int)M, llen, lrow, lblk, bstart, wstart, ix.nlist, bq, lval, lidx
+#define LDS_IVF_SCAN(KT_)                                                                                                 \
+    if (ix.metric == LDS_METRIC_COSINE) hipLaunchKernelGGL((lds::ivf_scan_kernel<KT_, LDS_METRIC_COSINE>), LDS_IVF_SCAN_ARGS); \
+    else hipLaunchKernelGGL((lds::ivf_scan_kernel<KT_, LDS_METRIC_L2>), LDS_IVF_SCAN_ARGS)
     switch (p.KT) {
         case 1: LDS_IVF_SCAN(1); break;
         case 2: LDS_IVF_SCAN(2); break;
@@ -893,10 +1049,12 @@ void ivf_lists(const IvfPlan& p, const float* X, long long N, long long M, int D
         default: LDS_IVF_SCAN(8); break;
     }
 #undef LDS_IVF_SCAN
+#undef LDS_IVF_SCAN_ARGS
 }
 
 int ivf_search(const char* fn, const float* X, long long N, long long M, int D, int k, const IvfIndex& ix, int slab_rows, int32_t* idx, float* score, void* ws,
                size_t ws_bytes, hipStream_t s) {
+    if (int rc = kn_check_metric(fn, ix.metric, LDS_WEIGHTS_INVERSE_SQUARE)) return rc;
     if (int rc = ivf_check_dims(fn, N, M, D, k, ix.nlist, ix.nprobe)) return rc;
     if (!X || !idx || !ws) return set_error(LDS_EINVAL, "%s: null pointer", fn);
     if (int rc = ivf_check_index(fn, ix, M)) return rc;
@@ -904,14 +1062,15 @@ int ivf_search(const char* fn, const float* X, long long N, long long M, int D, 
     const IvfPlan p = ivf_plan(N, D, k, ix.nlist, ix.nprobe, slab_rows);
     if (ws_bytes < p.bytes) return set_error(LDS_ENOMEM, "%s: workspace %zu < %zu bytes", fn, ws_bytes, p.bytes);
     ivf_lists(p, X, N, M, D, ix, ws, s);
-    hipLaunchKernelGGL(lds::knn_select_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, (const float*)((char*)ws + p.o_val),
-                       (const int*)((char*)ws + p.o_idx), ix.nprobe * lds::kIvfSegs, p.KT, N, (int)M, k, (int*)idx, score);
+    kn_select(ix.metric, X, D, (const float*)((char*)ws + p.o_val), (const int*)((char*)ws + p.o_idx), ix.nprobe * lds::kIvfSegs, p.KT, N, (int)M, k, idx, score, s);
     return kn_launched(fn);
 }
 
-int ivf_retrieve(const char* fn, const float* X, long long N, const float* P, long long M, int D, int k, const IvfIndex& ix, float ratio, float* Y, int32_t* idx,
-                 float* dist, void* ws, size_t ws_bytes, const lds::KnLens& lens, hipStream_t s) {
+int ivf_retrieve(const char* fn, int weights, const float* X, long long N, const float* P, const float* h, long long M, int D, int k, const IvfIndex& ix, float ratio,
+                 float* Y, int32_t* idx, float* dist, void* ws, size_t ws_bytes, const lds::KnLens& lens, hipStream_t s) {
+    if (int rc = kn_check_metric(fn, ix.metric, weights)) return rc;
     if (int rc = ivf_check_dims(fn, N, M, D, k, ix.nlist, ix.nprobe)) return rc;
+    if (ix.metric == LDS_METRIC_COSINE && !h) return set_error(LDS_EINVAL, "%s: null h (the cosine blend reads the pool's row constants)", fn);
     if (!(ratio >= 0.f && ratio <= 1.f)) return set_error(LDS_EINVAL, "%s: ratio %g outside 0 .. 1", fn, (double)ratio);
     if (!X || !P || !Y || !ws) return set_error(LDS_EINVAL, "%s: null pointer", fn);
     if (int rc = ivf_check_index(fn, ix, M)) return rc;
@@ -919,11 +1078,8 @@ int ivf_retrieve(const char* fn, const float* X, long long N, const float* P, lo
     const IvfPlan p = ivf_plan(N, D, k, ix.nlist, ix.nprobe, 0);
     if (ws_bytes < p.bytes) return set_error(LDS_ENOMEM, "%s: workspace %zu < %zu bytes", fn, ws_bytes, p.bytes);
     ivf_lists(p, X, N, M, D, ix, ws, s);
-    {
-        lds::ProfScope ps(s, "knn_blend", 5.0 * (double)N * k * D, 4.0 * (double)N * D * (2.0 * k + 3.0));
-        hipLaunchKernelGGL(lds::knn_blend_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, s, X, N, P, (int)M, D, (const float*)((char*)ws + p.o_val),
-                           (const int*)((char*)ws + p.o_idx), ix.nprobe * lds::kIvfSegs, p.KT, k, ratio, Y, (int*)idx, dist, lens);
-    }
+    kn_blend(ix.metric, weights, X, N, P, h, (int)M, D, (const float*)((char*)ws + p.o_val), (const int*)((char*)ws + p.o_idx), ix.nprobe * lds::kIvfSegs, p.KT, k,
+             ratio, Y, idx, dist, lens, s);
     return kn_launched(fn);
 }
 
@@ -936,45 +1092,70 @@ extern "C" int lds_ivf_workspace_bytes(int64_t N, int64_t M, int D, int k, int n
     return LDS_OK;
 }
 
-extern "C" int lds_ivf_search(const float* X, int64_t N, const float* P, const float* h, int64_t M, int D, int k, const float* C, const float* hc, int nlist,
-                              const int64_t* offsets, const int32_t* order, const float* PL, const float* hl, int64_t copy_rows, int nprobe, int32_t* idx,
+#define LDS_IVF_INDEX_PARAMS const float* C, const float* hc, int nlist, const int64_t* offsets, const int32_t* order, const float* PL, const float* hl, int64_t copy_rows, int nprobe
+
+extern "C" int lds_ivf_search(const float* X, int64_t N, const float* P, const float* h, int64_t M, int D, int k, LDS_IVF_INDEX_PARAMS, int32_t* idx,
                               float* score, void* ws, size_t ws_bytes, void* stream) {
     (void)P; (void)h;      // the search scores the list-ordered copy
-    const IvfIndex ix = {C, hc, nlist, offsets, order, PL, hl, copy_rows, nprobe};
+    const IvfIndex ix = {C, hc, nlist, offsets, order, PL, hl, copy_rows, nprobe, LDS_METRIC_L2};
     return ivf_search("lds_ivf_search", X, N, M, D, k, ix, 0, idx, score, ws, ws_bytes, (hipStream_t)stream);
 }
+extern "C" int lds_ivf_search_metric(const float* X, int64_t N, const float* P, const float* h, int64_t M, int D, int k, LDS_IVF_INDEX_PARAMS, int metric,
+                                     int32_t* idx, float* score, void* ws, size_t ws_bytes, void* stream) {
+    (void)P; (void)h;
+    const IvfIndex ix = {C, hc, nlist, offsets, order, PL, hl, copy_rows, nprobe, metric};
+    return ivf_search("lds_ivf_search_metric", X, N, M, D, k, ix, 0, idx, score, ws, ws_bytes, (hipStream_t)stream);
+}
 
-extern "C" int lds_ivf_retrieve(const float* X, int64_t N, const float* P, const float* h, int64_t M, int D, int k, const float* C, const float* hc, int nlist,
-                                const int64_t* offsets, const int32_t* order, const float* PL, const float* hl, int64_t copy_rows, int nprobe, float ratio,
+extern "C" int lds_ivf_retrieve(const float* X, int64_t N, const float* P, const float* h, int64_t M, int D, int k, LDS_IVF_INDEX_PARAMS, float ratio,
                                 float* Y, int32_t* idx, float* dist, void* ws, size_t ws_bytes, void* stream) {
-    (void)h;
-    const IvfIndex ix = {C, hc, nlist, offsets, order, PL, hl, copy_rows, nprobe};
-    return ivf_retrieve("lds_ivf_retrieve", X, N, P, M, D, k, ix, ratio, Y, idx, dist, ws, ws_bytes, kn_plain(), (hipStream_t)stream);
+    const IvfIndex ix = {C, hc, nlist, offsets, order, PL, hl, copy_rows, nprobe, LDS_METRIC_L2};
+    return ivf_retrieve("lds_ivf_retrieve", LDS_WEIGHTS_INVERSE_SQUARE, X, N, P, h, M, D, k, ix, ratio, Y, idx, dist, ws, ws_bytes, kn_plain(), (hipStream_t)stream);
+}
+extern "C" int lds_ivf_retrieve_metric(const float* X, int64_t N, const float* P, const float* h, int64_t M, int D, int k, LDS_IVF_INDEX_PARAMS, int metric,
+                                       int weights, float ratio, float* Y, int32_t* idx, float* dist, void* ws, size_t ws_bytes, void* stream) {
+    const IvfIndex ix = {C, hc, nlist, offsets, order, PL, hl, copy_rows, nprobe, metric};
+    return ivf_retrieve("lds_ivf_retrieve_metric", weights, X, N, P, h, M, D, k, ix, ratio, Y, idx, dist, ws, ws_bytes, kn_plain(), (hipStream_t)stream);
 }
 
 extern "C" int lds_ivf_retrieve_ragged(const float* X, int B, int T, const int32_t* lengths, const float* P, const float* h, int64_t M, int D, int k,
-                                       const float* C, const float* hc, int nlist, const int64_t* offsets, const int32_t* order, const float* PL,
-                                       const float* hl, int64_t copy_rows, int nprobe, float ratio, float* Y, int32_t* idx, float* dist, void* ws,
-                                       size_t ws_bytes, void* stream) {
-    (void)h;
-    if (B < 1 || B > 64 || T < 1) return set_error(LDS_EINVAL, "lds_ivf_retrieve_ragged: B %d outside 1 .. 64 or T %d < 1", B, T);
-    if (!lengths) return set_error(LDS_EINVAL, "lds_ivf_retrieve_ragged: null lengths");
-    lds::KnLens lens = kn_plain();
-    lens.n = B; lens.T = T;
-    for (int b = 0; b < B; ++b) {
-        if (lengths[b] < 0 || lengths[b] > T) return set_error(LDS_EINVAL, "lds_ivf_retrieve_ragged: lengths[%d] = %d outside 0 .. %d", b, lengths[b], T);
-        lens.v[b] = lengths[b];
-    }
-    const IvfIndex ix = {C, hc, nlist, offsets, order, PL, hl, copy_rows, nprobe};
-    return ivf_retrieve("lds_ivf_retrieve_ragged", X, (long long)B * T, P, M, D, k, ix, ratio, Y, idx, dist, ws, ws_bytes, lens, (hipStream_t)stream);
+                                       LDS_IVF_INDEX_PARAMS, float ratio, float* Y, int32_t* idx, float* dist, void* ws, size_t ws_bytes, void* stream) {
+    lds::KnLens lens;
+    if (int rc = kn_ragged_lens("lds_ivf_retrieve_ragged", B, T, lengths, lens)) return rc;
+    const IvfIndex ix = {C, hc, nlist, offsets, order, PL, hl, copy_rows, nprobe, LDS_METRIC_L2};
+    return ivf_retrieve("lds_ivf_retrieve_ragged", LDS_WEIGHTS_INVERSE_SQUARE, X, (long long)B * T, P, h, M, D, k, ix, ratio, Y, idx, dist, ws, ws_bytes, lens,
+                        (hipStream_t)stream);
+}
+extern "C" int lds_ivf_retrieve_ragged_metric(const float* X, int B, int T, const int32_t* lengths, const float* P, const float* h, int64_t M, int D, int k,
+                                              LDS_IVF_INDEX_PARAMS, int metric, int weights, float ratio, float* Y, int32_t* idx, float* dist, void* ws,
+                                              size_t ws_bytes, void* stream) {
+    lds::KnLens lens;
+    if (int rc = kn_ragged_lens("lds_ivf_retrieve_ragged_metric", B, T, lengths, lens)) return rc;
+    const IvfIndex ix = {C, hc, nlist, offsets, order, PL, hl, copy_rows, nprobe, metric};
+    return ivf_retrieve("lds_ivf_retrieve_ragged_metric", weights, X, (long long)B * T, P, h, M, D, k, ix, ratio, Y, idx, dist, ws, ws_bytes, lens,
+                        (hipStream_t)stream);
 }
 
-extern "C" int lds_test_ivf_search(const float* X, int64_t N, const float* P, const float* h, int64_t M, int D, int k, const float* C, const float* hc,
-                                   int nlist, const int64_t* offsets, const int32_t* order, const float* PL, const float* hl, int64_t copy_rows, int nprobe,
-                                   int slab_rows, int32_t* idx, float* score, void* ws, size_t ws_bytes, void* stream) {
-    (void)P; (void)h;
+namespace {
+int ivf_test_search(const char* fn, int metric, const float* X, int64_t N, int64_t M, int D, int k, LDS_IVF_INDEX_PARAMS, int slab_rows, int32_t* idx, float* score,
+                    void* ws, size_t ws_bytes, void* stream) {
     if (slab_rows < lds::kKnB || slab_rows % lds::kKnB || (D >= 8 && D <= 4096 && slab_rows > kn_slab_rows(D)))
-        return set_error(LDS_EINVAL, "lds_test_ivf_search: slab_rows %d must be a multiple of 128 that one descriptor holds", slab_rows);
-    const IvfIndex ix = {C, hc, nlist, offsets, order, PL, hl, copy_rows, nprobe};
-    return ivf_search("lds_test_ivf_search", X, N, M, D, k, ix, slab_rows, idx, score, ws, ws_bytes, (hipStream_t)stream);
+        return set_error(LDS_EINVAL, "%s: slab_rows %d must be a multiple of 128 that one descriptor holds", fn, slab_rows);
+    const IvfIndex ix = {C, hc, nlist, offsets, order, PL, hl, copy_rows, nprobe, metric};
+    return ivf_search(fn, X, N, M, D, k, ix, slab_rows, idx, score, ws, ws_bytes, (hipStream_t)stream);
 }
+}  // namespace
+
+extern "C" int lds_test_ivf_search(const float* X, int64_t N, const float* P, const float* h, int64_t M, int D, int k, LDS_IVF_INDEX_PARAMS, int slab_rows,
+                                   int32_t* idx, float* score, void* ws, size_t ws_bytes, void* stream) {
+    (void)P; (void)h;
+    return ivf_test_search("lds_test_ivf_search", LDS_METRIC_L2, X, N, M, D, k, C, hc, nlist, offsets, order, PL, hl, copy_rows, nprobe, slab_rows, idx, score, ws,
+                           ws_bytes, stream);
+}
+extern "C" int lds_test_ivf_search_metric(const float* X, int64_t N, const float* P, const float* h, int64_t M, int D, int k, LDS_IVF_INDEX_PARAMS, int metric,
+                                          int slab_rows, int32_t* idx, float* score, void* ws, size_t ws_bytes, void* stream) {
+    (void)P; (void)h;
+    return ivf_test_search("lds_test_ivf_search_metric", metric, X, N, M, D, k, C, hc, nlist, offsets, order, PL, hl, copy_rows, nprobe, slab_rows, idx, score, ws,
+                           ws_bytes, stream);
+}
+#undef LDS_IVF_INDEX_PARAMS

@@ -151,19 +151,30 @@ lds_llama_score_workspace_bytes  i:piip
 lds_llama_score                  i:ppppiippppppzp
 lds_kmeans_workspace_bytes       i:qiip
 lds_kmeans_prepare               i:piipp
+lds_kmeans_prepare_metric        i:piiipp
 lds_kmeans_assign                i:pqppiipppzp
+lds_kmeans_assign_metric         i:pqppiiipppzp
 lds_kmeans_assign_ragged         i:piipqppiipppzp
+lds_kmeans_assign_ragged_metric  i:piipqppiiipppzp
 lds_kmeans_update                i:ppqpppiippzp
+lds_kmeans_update_metric         i:ppqpppiiippzp
 lds_kmeans_seed                  i:pqiiqppppzp
 lds_knn_prepare                  i:pqipp
+lds_knn_prepare_metric           i:pqiipp
 lds_knn_workspace_bytes          i:qqiip
 lds_knn_search                   i:pqppqiipppzp
+lds_knn_search_metric            i:pqppqiiipppzp
 lds_knn_retrieve                 i:pqppqiifppppzp
+lds_knn_retrieve_metric          i:pqppqiiiifppppzp
 lds_knn_retrieve_ragged          i:piipppqiifppppzp
+lds_knn_retrieve_ragged_metric   i:piipppqiiiifppppzp
 lds_ivf_workspace_bytes          i:qqiiiip
 lds_ivf_search                   i:pqppqiippippppqipppzp
+lds_ivf_search_metric            i:pqppqiippippppqiipppzp
 lds_ivf_retrieve                 i:pqppqiippippppqifppppzp
+lds_ivf_retrieve_metric          i:pqppqiippippppqiiifppppzp
 lds_ivf_retrieve_ragged          i:piipppqiippippppqifppppzp
+lds_ivf_retrieve_ragged_metric   i:piipppqiippippppqiiifppppzp
 lds_resample                     i:ppppiiiiqqp
 lds_resample_ragged              i:ppppppiiiiqqp
 lds_frame_rms                    i:ppqiiiqp
@@ -237,7 +248,9 @@ lds_test_wavlm_attention         i:pppppiiiiip
 lds_test_wavlm_buckets           i:iiip
 lds_test_stft_dft                i:pppiiiippiqp
 lds_test_knn_search              i:pqppqiiiipppzp
+lds_test_knn_search_metric       i:pqppqiiiiipppzp
 lds_test_ivf_search              i:pqppqiippippppqiipppzp
+lds_test_ivf_search_metric       i:pqppqiippippppqiiipppzp
 """
 SIGNATURES = dict(ln.split() for ln in (_PUBLIC + _TEST).splitlines() if ln)
 EXPORTS = [ln.split()[0] for ln in _PUBLIC.splitlines() if ln]
@@ -342,12 +355,25 @@ def _host_lengths(lengths, B, lo, hi, max_B=None, what=""):
     return a
 
 
-def _dense_or_ragged(name, *lengths):
+def _dense_or_ragged(name, *lengths, suffix=""):
     """(the entry `name`, ()) without lengths, else (its `_ragged` twin, the host addresses of the lengths arrays -- which the caller keeps
-    alive over the call).  The C entries stay two: a ragged one refuses a null `lengths`."""
+    alive over the call).  The C entries stay two: a ragged one refuses a null `lengths`.  suffix: what follows `_ragged` in the name."""
     if lengths[0] is None:
-        return getattr(lib(), name), ()
-    return getattr(lib(), name + "_ragged"), tuple(a.ctypes.data for a in lengths)
+        return getattr(lib(), name + suffix), ()
+    return getattr(lib(), name + "_ragged" + suffix), tuple(a.ctypes.data for a in lengths)
+
+
+# the metric / weights choices of the clustering stack (include/lds.h LDS_METRIC_*, LDS_WEIGHTS_*)
+METRICS = {"l2": 0, "cosine": 1}
+WEIGHTS = {"inverse_square": 0, "uniform": 1}
+
+
+def metric_code(metric, what="metric", table=None):
+    """the C value of a metric (or, with table=WEIGHTS, a weights) name; anything else is a ValueError -- before any device work"""
+    table = METRICS if table is None else table
+    if not isinstance(metric, str) or metric not in table:
+        raise ValueError(f"{what} must be one of {sorted(table)} (got {metric!r})")
+    return table[metric]
 
 
 class _Handle:
@@ -1294,19 +1320,25 @@ def _kmeans_ws_for(ws, N, K, D, device):
     return ws if ws is not None else _kmeans_ws.get(kmeans_workspace_bytes(N, K, D), device)
 
 
-def kmeans_prepare(centers):
-    """h [K] = |c_k|^2 / 2 of a codebook [K, D] (once per codebook)"""
+def kmeans_prepare(centers, metric="l2"):
+    """h [K] = |c_k|^2 / 2 of a codebook [K, D] (once per codebook); metric="cosine": the row constants 1 / max(|c_k|, 1e-12)"""
     import torch
+    m = metric_code(metric)
     K, D = centers.shape
     h = torch.empty(K, dtype=torch.float32, device=centers.device)
-    check(lib().lds_kmeans_prepare(_dev(centers, torch.float32), K, D, _dev(h), _stream()))
+    if m == 0:
+        check(lib().lds_kmeans_prepare(_dev(centers, torch.float32), K, D, _dev(h), _stream()))
+    else:
+        check(lib().lds_kmeans_prepare_metric(_dev(centers, torch.float32), K, D, m, _dev(h), _stream()))
     return h
 
 
-def kmeans_assign(x, centers, h, return_best=False, ws=None, lengths=None, pad_id=0):
+def kmeans_assign(x, centers, h, return_best=False, ws=None, lengths=None, pad_id=0, metric="l2"):
     """x [N, D] -> labels int64 [N] (the nearest centre, lowest index among ties) and optionally the winning score x.c - h.
-    lengths (host ints [B], 0 .. T) with x [B, T, D]: the ragged form, labels [B, T] with pad_id at and beyond every clip's length."""
+    lengths (host ints [B], 0 .. T) with x [B, T, D]: the ragged form, labels [B, T] with pad_id at and beyond every clip's length.
+    metric="cosine" (h from kmeans_prepare(.., "cosine")): the centre of highest cosine similarity, and that similarity as the score."""
     import torch
+    m = metric_code(metric)
     K, D = centers.shape
     if x.shape[-1] != D or x.dim() != (3 if lengths is not None else 2):
         raise ValueError(f"kmeans_assign: x {list(x.shape)} against a codebook {[K, D]}")
@@ -1315,24 +1347,27 @@ def kmeans_assign(x, centers, h, return_best=False, ws=None, lengths=None, pad_i
     labels = torch.empty(x.shape[:-1], dtype=torch.int64, device=x.device)
     best = torch.empty(x.shape[:-1], dtype=torch.float32, device=x.device) if return_best else None
     ln = None if lengths is None else _host_lengths(lengths, x.shape[0], 0, x.shape[1])
-    fn, ln_at = _dense_or_ragged("lds_kmeans_assign", ln)
+    fn, ln_at = _dense_or_ragged("lds_kmeans_assign", ln, suffix="_metric" if m else "")
     rows = (N,) if ln is None else (x.shape[0], x.shape[1], *ln_at, int(pad_id))
-    check(fn(_dev(x, torch.float32), *rows, _dev(centers, torch.float32), _dev(h, torch.float32), K, D, _dev(labels), _dev_or_null(best), _dev(ws),
-             ws.numel(), _stream()))
+    check(fn(_dev(x, torch.float32), *rows, _dev(centers, torch.float32), _dev(h, torch.float32), K, D, *((m,) if m else ()), _dev(labels),
+             _dev_or_null(best), _dev(ws), ws.numel(), _stream()))
     return (labels, best) if return_best else labels
 
 
-def kmeans_update(x, labels, centers, h, num_points, ws=None):
-    """one Lloyd step in place on centers / h / num_points (include/lds.h lds_kmeans_update); returns the error as a device scalar"""
+def kmeans_update(x, labels, centers, h, num_points, ws=None, metric="l2"):
+    """one Lloyd step in place on centers / h / num_points (include/lds.h lds_kmeans_update); returns the error as a device scalar.
+    metric decides only what h is refreshed to (kmeans_prepare's)"""
     import torch
+    m = metric_code(metric)
     K, D = centers.shape
     N = x.shape[0]
     if x.dim() != 2 or x.shape[1] != D or labels.shape != (N,) or num_points.shape != (K,) or h.shape != (K,):
         raise ValueError("kmeans_update: shapes of x, labels, centers, h, num_points do not agree")
     ws = _kmeans_ws_for(ws, N, K, D, x.device)
     err = torch.empty((), dtype=torch.float32, device=x.device)
-    check(lib().lds_kmeans_update(_dev(x, torch.float32), _dev(labels, torch.int64), N, _dev(centers, torch.float32), _dev(h, torch.float32),
-                                  _dev(num_points, torch.float32), K, D, _dev(err), _dev(ws), ws.numel(), _stream()))
+    fn = lib().lds_kmeans_update_metric if m else lib().lds_kmeans_update
+    check(fn(_dev(x, torch.float32), _dev(labels, torch.int64), N, _dev(centers, torch.float32), _dev(h, torch.float32), _dev(num_points, torch.float32),
+             K, D, *((m,) if m else ()), _dev(err), _dev(ws), ws.numel(), _stream()))
     return err
 
 
@@ -1364,19 +1399,26 @@ def _knn_ws_for(ws, N, M, D, k, device):
     return ws if ws is not None else _knn_ws.get(knn_workspace_bytes(N, M, D, k), device)
 
 
-def knn_prepare(pool):
-    """h [M] = |p_m|^2 / 2 of a pool [M, D] (once per pool)"""
+def knn_prepare(pool, metric="l2"):
+    """h [M] = |p_m|^2 / 2 of a pool [M, D] (once per pool); metric="cosine": the row constants 1 / max(|p_m|, 1e-12)"""
     import torch
+    m = metric_code(metric)
     M, D = pool.shape
     h = torch.empty(M, dtype=torch.float32, device=pool.device)
-    check(lib().lds_knn_prepare(_dev(pool, torch.float32), M, D, _dev(h), _stream()))
+    if m == 0:
+        check(lib().lds_knn_prepare(_dev(pool, torch.float32), M, D, _dev(h), _stream()))
+    else:
+        check(lib().lds_knn_prepare_metric(_dev(pool, torch.float32), M, D, m, _dev(h), _stream()))
     return h
 
 
-def knn_search(x, pool, h, k, ws=None, slab_rows=None, splits=None):
+def knn_search(x, pool, h, k, ws=None, slab_rows=None, splits=None, metric="l2"):
     """x [N, D] -> (idx int32 [N, k], score [N, k]): the k nearest pool rows, nearest first, the lower index among equal scores.
-    slab_rows / splits (both or neither): the pool's cut forced through lds_test_knn_search; `ws` must then be given"""
+    slab_rows / splits (both or neither): the pool's cut forced through lds_test_knn_search; `ws` must then be given.
+    metric="cosine" (h from knn_prepare(.., "cosine")): by cosine similarity, which is then the score"""
     import torch
+    m = metric_code(metric)
+    mm, sfx = ((m,) if m else ()), ("_metric" if m else "")
     M, D = pool.shape
     if x.dim() != 2 or x.shape[1] != D:
         raise ValueError(f"knn_search: x {list(x.shape)} against a pool {[M, D]}")
@@ -1386,16 +1428,24 @@ def knn_search(x, pool, h, k, ws=None, slab_rows=None, splits=None):
     head = (_dev(x, torch.float32), N, _dev(pool, torch.float32), _dev(h, torch.float32), M, D, int(k))
     if slab_rows is None:
         ws = _knn_ws_for(ws, N, M, D, k, x.device)
-        check(lib().lds_knn_search(*head, _dev(idx), _dev(score), _dev(ws), ws.numel(), _stream()))
+        check(getattr(lib(), "lds_knn_search" + sfx)(*head, *mm, _dev(idx), _dev(score), _dev(ws), ws.numel(), _stream()))
     else:
-        check(lib().lds_test_knn_search(*head, int(slab_rows), int(splits), _dev(idx), _dev(score), _dev(ws), ws.numel(), _stream()))
+        check(getattr(lib(), "lds_test_knn_search" + sfx)(*head, *mm, int(slab_rows), int(splits), _dev(idx), _dev(score), _dev(ws), ws.numel(), _stream()))
     return idx, score
 
 
-def knn_retrieve(x, pool, h, k, ratio, lengths=None, ws=None):
+def _metric_args(metric, weights):
+    """((metric, weights) codes for a *_metric entry or () for its namesake, the entry's suffix): l2 with inverse_square is the namesake"""
+    m, w = metric_code(metric), metric_code(weights, "weights", WEIGHTS)
+    return ((m, w), "_metric") if (m or w) else ((), "")
+
+
+def knn_retrieve(x, pool, h, k, ratio, lengths=None, ws=None, metric="l2", weights="inverse_square"):
     """x [N, D], or [B, T, D] with lengths (host ints [B], 0 .. T) -> (y like x, idx int32 [.., k], dist [.., k]): every row blended with its
-    k nearest pool rows (include/lds.h lds_knn_retrieve); rows at and beyond a clip's length: y = 0, idx = -1, dist = 0"""
+    k nearest pool rows (include/lds.h lds_knn_retrieve); rows at and beyond a clip's length: y = 0, idx = -1, dist = 0.
+    metric / weights: include/lds.h lds_knn_retrieve_metric (cosine: dist = 1 - cos; uniform: the plain mean of the rows found)"""
     import torch
+    mw, sfx = _metric_args(metric, weights)
     M, D = pool.shape
     if x.shape[-1] != D or x.dim() != (3 if lengths is not None else 2):
         raise ValueError(f"knn_retrieve: x {list(x.shape)} against a pool {[M, D]}")
@@ -1405,10 +1455,10 @@ def knn_retrieve(x, pool, h, k, ratio, lengths=None, ws=None):
     idx = torch.empty(*x.shape[:-1], k, dtype=torch.int32, device=x.device)
     dist = torch.empty(*x.shape[:-1], k, dtype=torch.float32, device=x.device)
     ln = None if lengths is None else _host_lengths(lengths, x.shape[0], 0, x.shape[1], max_B=64, what="retrieval")
-    fn, ln_at = _dense_or_ragged("lds_knn_retrieve", ln)
+    fn, ln_at = _dense_or_ragged("lds_knn_retrieve", ln, suffix=sfx)
     rows = (N,) if ln is None else (x.shape[0], x.shape[1], *ln_at)
-    check(fn(_dev(x, torch.float32), *rows, _dev(pool, torch.float32), _dev(h, torch.float32), M, D, int(k), float(ratio), _dev(y), _dev(idx), _dev(dist),
-             _dev(ws), ws.numel(), _stream()))
+    check(fn(_dev(x, torch.float32), *rows, _dev(pool, torch.float32), _dev(h, torch.float32), M, D, int(k), *mw, float(ratio), _dev(y), _dev(idx),
+             _dev(dist), _dev(ws), ws.numel(), _stream()))
     return y, idx, dist
 
 
@@ -1434,10 +1484,13 @@ def _ivf_ws_for(ws, N, M, D, k, ivf, nprobe, device):
     return ws if ws is not None else _ivf_ws.get(ivf_workspace_bytes(N, M, D, k, ivf[0].shape[0], nprobe), device)
 
 
-def ivf_search(x, pool, h, k, ivf, nprobe, ws=None, slab_rows=None):
+def ivf_search(x, pool, h, k, ivf, nprobe, ws=None, slab_rows=None, metric="l2"):
     """x [N, D] -> (idx int32 [N, k], score [N, k]): the k best rows among the query's nprobe probed lists (include/lds.h lds_ivf_search);
-    -1 / -inf where the lists hold fewer than k rows.  slab_rows: the copy's cut forced through lds_test_ivf_search"""
+    -1 / -inf where the lists hold fewer than k rows.  slab_rows: the copy's cut forced through lds_test_ivf_search.
+    metric: the one the whole index (h, hc, hl, the lists) was built for"""
     import torch
+    m = metric_code(metric)
+    mm, sfx = ((m,) if m else ()), ("_metric" if m else "")
     M, D = pool.shape
     if x.dim() != 2 or x.shape[1] != D:
         raise ValueError(f"ivf_search: x {list(x.shape)} against a pool {[M, D]}")
@@ -1448,16 +1501,17 @@ def ivf_search(x, pool, h, k, ivf, nprobe, ws=None, slab_rows=None):
     head = (_dev(x, torch.float32), N, _dev(pool, torch.float32), _dev(h, torch.float32), M, D, int(k), *_ivf_args(ivf, nprobe))
     tail = (_dev(idx), _dev(score), _dev(ws), ws.numel(), _stream())
     if slab_rows is None:
-        check(lib().lds_ivf_search(*head, *tail))
+        check(getattr(lib(), "lds_ivf_search" + sfx)(*head, *mm, *tail))
     else:
-        check(lib().lds_test_ivf_search(*head, int(slab_rows), *tail))
+        check(getattr(lib(), "lds_test_ivf_search" + sfx)(*head, *mm, int(slab_rows), *tail))
     return idx, score
 
 
-def ivf_retrieve(x, pool, h, k, ratio, ivf, nprobe, lengths=None, ws=None):
+def ivf_retrieve(x, pool, h, k, ratio, ivf, nprobe, lengths=None, ws=None, metric="l2", weights="inverse_square"):
     """knn_retrieve over the rows of every query's nprobe probed lists (include/lds.h lds_ivf_retrieve); idx = -1 (weight 0) where the
-    lists hold fewer than k rows"""
+    lists hold fewer than k rows.  metric (the index's) / weights: include/lds.h lds_ivf_retrieve_metric"""
     import torch
+    mw, sfx = _metric_args(metric, weights)
     M, D = pool.shape
     if x.shape[-1] != D or x.dim() != (3 if lengths is not None else 2):
         raise ValueError(f"ivf_retrieve: x {list(x.shape)} against a pool {[M, D]}")
@@ -1467,10 +1521,10 @@ def ivf_retrieve(x, pool, h, k, ratio, ivf, nprobe, lengths=None, ws=None):
     idx = torch.empty(*x.shape[:-1], k, dtype=torch.int32, device=x.device)
     dist = torch.empty(*x.shape[:-1], k, dtype=torch.float32, device=x.device)
     ln = None if lengths is None else _host_lengths(lengths, x.shape[0], 0, x.shape[1], max_B=64, what="retrieval")
-    fn, ln_at = _dense_or_ragged("lds_ivf_retrieve", ln)
+    fn, ln_at = _dense_or_ragged("lds_ivf_retrieve", ln, suffix=sfx)
     rows = (N,) if ln is None else (x.shape[0], x.shape[1], *ln_at)
-    check(fn(_dev(x, torch.float32), *rows, _dev(pool, torch.float32), _dev(h, torch.float32), M, D, int(k), *_ivf_args(ivf, nprobe), float(ratio), _dev(y),
-             _dev(idx), _dev(dist), _dev(ws), ws.numel(), _stream()))
+    check(fn(_dev(x, torch.float32), *rows, _dev(pool, torch.float32), _dev(h, torch.float32), M, D, int(k), *_ivf_args(ivf, nprobe), *mw, float(ratio),
+             _dev(y), _dev(idx), _dev(dist), _dev(ws), ws.numel(), _stream()))
     return y, idx, dist
 
 

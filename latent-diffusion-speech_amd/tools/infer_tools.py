@@ -130,7 +130,8 @@ class DiffusionSVC:
 
     @torch.no_grad()
     def infer_from_long_audio(self, audio, sr=44100, key=0, spk_id=1, aug_shift=0, infer_speedup=10, method="unipc", use_tqdm=True, threhold=-60,
-                              threhold_for_split=-40, min_len=5000, *, batch_size=16, x_T=None, index=None, index_ratio=0.5, index_k=8, index_nprobe=None):
+                              threhold_for_split=-40, min_len=5000, *, batch_size=16, x_T=None, index=None, index_ratio=0.5, index_k=8, index_nprobe=None,
+                              index_weights="inverse_square"):
         """reference infer_tools.py:83-117: a mono recording [L] at `sr` (numpy, or a tensor on the device) -> (the converted recording fp32
         [N] on the device, the model's sampling rate).  The recording is cut at its silences (tools.slicer.split_ranges), the volume mask is
         taken from the whole clip, and where the reference loops over the segments -- one encoder call, one sampler run, one vocoder call
@@ -148,6 +149,7 @@ class DiffusionSVC:
         index (a cluster.index.UnitsIndex; keyword-only, not in the reference): units retrieval -- every chunk's encoder frames are blended
         with their index_k nearest rows of the index's pool at index_ratio (UnitsIndex.retrieve, per-clip lengths) before the alignment;
         index_nprobe (needs an index built with an IVF, UnitsIndex.build_ivf): only the rows of a frame's index_nprobe best lists are searched;
+        index_weights ("inverse_square" or "uniform": UnitsIndex.retrieve's weights; the metric is the index's own);
         without an index nothing changes, bit for bit."""
         if key != 0:
             raise NotImplementedError("infer_from_long_audio: key shift needs the f0 path, which is not built (the reference's extract_f0 does not exist); key must be 0")
@@ -182,7 +184,7 @@ class DiffusionSVC:
                 batch[j, :ranges[s][2] - ranges[s][1]] = audio[ranges[s][1]:ranges[s][2]]
             units, unit_frames = self.units_encoder.encode_ragged(batch, lens, sample_rate=sr, pad_short=True)
             if index is not None:
-                units = index.retrieve(units, k=index_k, ratio=index_ratio, lengths=unit_frames, nprobe=index_nprobe)
+                units = index.retrieve(units, k=index_k, ratio=index_ratio, lengths=unit_frames, nprobe=index_nprobe, weights=index_weights)
             nf = [n_frames[s] for s in idx]
             units = units_forced_alignment_ragged(units, unit_frames, nf)
             noise = torch.zeros(len(idx), 1, M, max(nf), device=audio.device)

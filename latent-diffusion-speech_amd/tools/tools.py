@@ -281,17 +281,22 @@ class Units_Encoder:
                 lengths = np.maximum(ln, lo)
         return self.model.encode_ragged(audio, lengths)
 
-    def encode_tokens(self, audio, sample_rate, codebook):
+    def encode_tokens(self, audio, sample_rate, codebook, metric="l2"):
         """Extension: audio -> semantic tokens int64 [T] on the device = encode, then the nearest centre of `codebook` (a model from
-        cluster.get_cluster_model) by lds_kmeans_assign, without leaving the device (the reference's steps 16 + 19 go through .npy files)"""
+        cluster.get_cluster_model) by lds_kmeans_assign, without leaving the device (the reference's steps 16 + 19 go through .npy files);
+        metric="cosine": the centre of highest cosine similarity (a codebook fitted by train_cluster(mode="cosine"))"""
         import cluster
-        return cluster.get_cluster_result(codebook, self.encode(audio, sample_rate))
+        from lds.native import metric_code
+        metric_code(metric)      # (a bad metric fails before the encoder runs)
+        return cluster.get_cluster_result(codebook, self.encode(audio, sample_rate), metric=metric)
 
-    def encode_tokens_ragged(self, audio, lengths, codebook, pad_id, sample_rate=None):
+    def encode_tokens_ragged(self, audio, lengths, codebook, pad_id, sample_rate=None, metric="l2"):
         """Extension: encode_ragged + tokens [B, Tmax] int64: rows at and beyond a clip's own n_frames[b] hold pad_id; returns (tokens, n_frames)"""
         import cluster
+        from lds.native import metric_code
+        metric_code(metric)
         units, n_frames = self.encode_ragged(audio, lengths, sample_rate)
-        return cluster.get_cluster_result(codebook, units, lengths=n_frames, pad_id=pad_id), n_frames
+        return cluster.get_cluster_result(codebook, units, lengths=n_frames, pad_id=pad_id, metric=metric), n_frames
 
 
 class HubertUnits(torch.nn.Module):

@@ -1,7 +1,7 @@
 """The k-means tokenizer's kernels at the reference's configuration (K 4096 centres of 1280 floats), one process, device events around whole
 calls after warm-up, alternating rounds, the minimum of the rounds; one JSON line.
 
-    python tools/bench_kmeans.py [--rounds 3] [--iters 3] [--big 1000000] [--no-tokens] [--no-fit]
+    python tools/bench_kmeans.py [--rounds 3] [--iters 3] [--big 1000000] [--no-tokens] [--no-fit] [--metric cosine]
 
   assign    N = 1500, 12,000 and --big rows: time and 2 N K D / time (a kernel figure), next to the same product (M 4096, K 1280, N columns) as a
             plain conv_dma 1x1 launch that STORES the N x K result (include/lds_test.h lds_bench_dconv, the mechanism of tools/bench_dconv.py)
@@ -10,6 +10,8 @@ calls after warm-up, alternating rounds, the minimum of the rounds; one JSON lin
   fit       one iteration (assign + update) at --big rows; KMeansGPU.fit_predict on a seeded blob corpus of that size (max_iter 5), the
             seeding timed separately
   tokens    assign of 8 x 1500 frames on top of an 8-clip, 30 s Whisper encode (large-v3 dims, seeded weights)
+  --metric cosine   the cosine assign (with its similarities) and the cosine Lloyd step join the same alternating rounds as legs of their
+            own: "cosine_ms" beside "ms", with the (max - min) of both legs' rounds; the fit then runs KMeansCosineGPU
 """
 import argparse
 import ctypes as ct
@@ -47,6 +49,7 @@ def rounds(legs, n_rounds, iters):
     for _ in range(n_rounds):
         for k, fn in legs.items():
             t[k].append(timed(fn, iters))
+    rounds.spread = {k: max(v) - min(v) for k, v in t.items()}
     return {k: min(v) for k, v in t.items()}
 
 
@@ -71,11 +74,14 @@ def main():
     ap.add_argument("--big", type=int, default=1000000)
     ap.add_argument("--no-tokens", action="store_true")
     ap.add_argument("--no-fit", action="store_true")
+    ap.add_argument("--metric", default="l2", choices=("l2", "cosine"))
     a = ap.parse_args()
+    cos = a.metric == "cosine"
     res = {"K": K, "D": D, "peak_tflops": PEAK_TFLOPS}
     g = torch.Generator(device="cuda").manual_seed(0)
     C = torch.randn(K, D, device="cuda", generator=g)
     h = native.kmeans_prepare(C)
+    hr = native.kmeans_prepare(C, "cosine") if cos else None
     lab_true = torch.randint(0, K, (a.big,), device="cuda", generator=g)
     Xbig = C[lab_true] + 0.5 * torch.randn(a.big, D, device="cuda", generator=g)
     w = np.ascontiguousarray(C.cpu().numpy().reshape(K, D, 1))
@@ -88,7 +94,10 @@ def main():
                 x = X[r0:r0 + 65536]
                 (2 * x @ C.T - (x ** 2).sum(1)[:, None] - (C ** 2).sum(1)[None, :]).max(-1)
 
-        ms = rounds({"assign": lambda: native.kmeans_assign(X, C, h), "torch": torch_ref}, a.rounds, a.iters)
+        legs = {"assign": lambda: native.kmeans_assign(X, C, h), "torch": torch_ref}
+        if cos:
+            legs["assign_cosine"] = lambda: native.kmeans_assign(X, C, hr, return_best=True, metric="cosine")
+        ms = rounds(legs, a.rounds, a.iters)
         B, T = shapes[N]
         try:
             dms = [dconv_ms(B, T, w, a.iters) for _ in range(a.rounds)]
@@ -102,6 +111,9 @@ def main():
                               "conv_dma_cfg": dms[0][1], "conv_dma_columns": B * T,
                               "assign_over_conv_dma_per_flop": round((ms["assign"] / fl) / (min(m for m, _ in dms) / dfl), 3),
                               "torch_ms": round(ms["torch"], 4)}
+        if cos:
+            res[f"assign_{N}"].update({"cosine_ms": round(ms["assign_cosine"], 4), "spread_ms": round(rounds.spread["assign"], 4),
+                                       "cosine_spread_ms": round(rounds.spread["assign_cosine"], 4)})
     # the Lloyd step and one fit iteration at --big rows
     N = a.big
     labels = native.kmeans_assign(Xbig, C, h)
@@ -109,13 +121,20 @@ def main():
     C2, h2 = C.clone(), h.clone()
     step = lambda: native.kmeans_update(Xbig, labels, C2, h2, npnt)      # noqa: E731
     it = lambda: native.kmeans_update(Xbig, native.kmeans_assign(Xbig, C2, h2), C2, h2, npnt)      # noqa: E731
-    ms = rounds({"update": step, "iteration": it}, a.rounds, a.iters)
+    legs = {"update": step, "iteration": it}
+    if cos:
+        C3, h3 = C.clone(), hr.clone()
+        legs["iteration_cosine"] = lambda: native.kmeans_update(Xbig, native.kmeans_assign(Xbig, C3, h3, metric="cosine"), C3, h3, npnt, metric="cosine")
+    ms = rounds(legs, a.rounds, a.iters)
     res[f"update_{N}"] = {"ms": round(ms["update"], 4), "x_bytes_per_s_TB": round(N * D * 4 / ms["update"] / 1e9, 3)}
     res[f"iteration_{N}"] = {"ms": round(ms["iteration"], 4)}
+    if cos:
+        res[f"iteration_{N}"].update({"cosine_ms": round(ms["iteration_cosine"], 4), "spread_ms": round(rounds.spread["iteration"], 4),
+                                      "cosine_spread_ms": round(rounds.spread["iteration_cosine"], 4)})
     if not a.no_fit:
-        from cluster.kmeans import KMeansGPU, _kpp
+        from cluster.kmeans import KMeansCosineGPU, KMeansGPU, _kpp
         torch.manual_seed(0)
-        km = KMeansGPU(K, max_iter=5, tol=0.0)
+        km = (KMeansCosineGPU if cos else KMeansGPU)(K, max_iter=5, tol=0.0)
         t0 = time.perf_counter()
         km.fit_predict(Xbig)
         torch.cuda.synchronize()

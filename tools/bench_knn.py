@@ -15,6 +15,13 @@ queries then come from one seeded Gaussian mixture of --mixture components (unit
 no neighbours worth finding at this width).  Per (pool, nlist): the build's wall time (fit + assignment + the list-ordered copy); per nprobe:
 the call's median, its ratio to the exact call, the kernels' shares of one profiled call (ivf_scan, the coarse knn_topk, knn_blend) and
 recall@8 against the exact call's lists.  exact_ms_spread is (max - min) of the exact call's --reps timings.
+
+    python tools/bench_knn.py --metric l2 cosine [--nlist 1024 --nprobe 8] [--out profiles/r24_cosine_knn_bench.json]
+
+--metric (default l2: everything above, unchanged): one metric runs the figures above on an index of that metric (the torch baseline is
+Euclidean and is left out for cosine); two metrics are timed against each other in ALTERNATING rounds in one process -- round r times one
+call of each metric in turn, on indexes over the same device pool -- and reported as median and (max - min) per metric, for the exact call and
+for every (nlist, nprobe).
 """
 import argparse
 import json
@@ -85,6 +92,45 @@ def ivf_figures(ix, x, exact_ms, exact_idx, nlists, nprobes, reps):
     return out
 
 
+def one_ms(fn):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1)
+
+
+def alternating(calls, reps):
+    """calls {name: fn}: one warm-up call each, then `reps` rounds of one timed call of each in turn -> {name: {"ms", "spread_ms", "all_ms"}}"""
+    for fn in calls.values():
+        fn()
+    torch.cuda.synchronize()
+    t = {name: [] for name in calls}
+    for _ in range(reps):
+        for name, fn in calls.items():
+            t[name].append(one_ms(fn))
+    return {name: {"ms": round(statistics.median(v), 3), "spread_ms": round(max(v) - min(v), 3), "all_ms": [round(q, 3) for q in v]} for name, v in t.items()}
+
+
+def metric_rounds(a, x, res):
+    """--metric with two metrics: the exact call and every (nlist, nprobe) of each metric in alternating rounds over one device pool"""
+    for M in a.pools:
+        p = mixture(M, D, a.mixture, 1, 3) if a.nlist else torch.randn(M, D, device="cuda", generator=torch.Generator(device="cuda").manual_seed(M))
+        ixs = {m: UnitsIndex(p, metric=m) for m in a.metric}
+        res[f"retrieve_{M}"] = alternating({m: (lambda ix=ix: ix.retrieve(x, k=K, ratio=0.5)) for m, ix in ixs.items()}, a.reps)
+        for nlist in a.nlist:
+            for ix in ixs.values():
+                ix.build_ivf(nlist)
+                ix._device_ivf(x.device)
+            for nprobe in a.nprobe:
+                res.setdefault(f"ivf_{M}", {})[f"nlist_{nlist}_nprobe_{nprobe}"] = alternating(
+                    {m: (lambda ix=ix: ix.retrieve(x, k=K, ratio=0.5, nprobe=nprobe)) for m, ix in ixs.items()}, a.reps)
+            for ix in ixs.values():
+                ix._ivf_on = {}
+        del p, ixs
+
+
 def torch_retrieve(x, p, h, k, ratio, chunk=65536):
     best_v = best_i = None
     for m0 in range(0, p.shape[0], chunk):
@@ -112,17 +158,27 @@ def main():
     ap.add_argument("--nprobe", type=int, nargs="+", default=[1, 8])
     ap.add_argument("--mixture", type=int, default=256)
     ap.add_argument("--no_torch", action="store_true", help="leave the torch baseline out")
+    ap.add_argument("--metric", nargs="+", default=["l2"], choices=("l2", "cosine"), help="one: the index's metric; two: alternating rounds of both")
     a = ap.parse_args()
+    if len(a.metric) > 2 or len(set(a.metric)) != len(a.metric):
+        raise SystemExit("--metric takes one metric, or l2 and cosine once each")
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "r23_ivf_bench.json" if a.nlist else "r20_knn_bench.json")
+        a.out = os.path.join(ROOT, "profiles", "r24_cosine_knn_bench.json" if a.metric != ["l2"] else "r23_ivf_bench.json" if a.nlist else "r20_knn_bench.json")
+    if a.metric == ["cosine"]:
+        a.no_torch = True
     g = torch.Generator(device="cuda").manual_seed(0)
     x = mixture(N, D, a.mixture, 1, 2) if a.nlist else torch.randn(N, D, device="cuda", generator=g)
     res = {"N": N, "D": D, "k": K, "ratio": 0.5, "reps": a.reps, "peak_tflops": PEAK_TFLOPS}
     if a.nlist:
         res["mixture"] = a.mixture
+    if a.metric != ["l2"]:
+        res["metric"] = a.metric
+    if len(a.metric) == 2:
+        metric_rounds(a, x, res)
+        a.pools = []
     for M in a.pools:
         p = mixture(M, D, a.mixture, 1, 3) if a.nlist else torch.randn(M, D, device="cuda", generator=g)
-        ix = UnitsIndex(p)
+        ix = UnitsIndex(p, metric=a.metric[0])
         h = ix._device(p.device)[1]
         ms = median_ms(lambda: ix.retrieve(x, k=K, ratio=0.5), a.reps)
         spread = max(median_ms.last) - min(median_ms.last)

@@ -61,6 +61,8 @@ def main():
     ap.add_argument("--synthetic", type=int, default=0, metavar="K")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--batch", type=int, default=8)
+    ap.add_argument("--metric", default="l2", choices=("l2", "cosine"), help="cosine: the centre of highest cosine similarity (a codebook from "
+                    "train_codebook.py --mode cosine)")
     ap.add_argument("--from-audio", action="store_true", help="IN_DIR holds audio clips: encode them to units first")
     ap.add_argument("--sample-rate", type=int, default=16000, help="--from-audio: rate of the .npy clips (a .wav carries its own)")
     ap.add_argument("--encoder", default="whisper_large_v3", choices=("whisper_large_v3", "hubertsoft", "contentvec768l12", "w2v-bert"))
@@ -86,7 +88,7 @@ def main():
         if a.from_audio:
             from extract_units import encoder_batch, load_clip      # (tools/ is this script's own directory)
             audio, slen = encoder_batch([load_clip(p, a.sample_rate) for p in group], ue.min_samples)      # (16 kHz on the device; at least the encoder's shortest clip each)
-            tok, lens = ue.encode_tokens_ragged(audio, slen, model, pad_id=-1)
+            tok, lens = ue.encode_tokens_ragged(audio, slen, model, pad_id=-1, metric=a.metric)
             tok, lens = tok.cpu().numpy(), [int(n) for n in lens]
         else:
             units = [np.load(p).astype(np.float32) for p in group]
@@ -94,7 +96,7 @@ def main():
             x = np.zeros((len(units), max(lens), units[0].shape[1]), dtype=np.float32)
             for b, u in enumerate(units):
                 x[b, : lens[b]] = u
-            tok = cluster.get_cluster_result(model, torch.from_numpy(x).cuda(), lengths=lens, pad_id=-1).cpu().numpy()
+            tok = cluster.get_cluster_result(model, torch.from_numpy(x).cuda(), lengths=lens, pad_id=-1, metric=a.metric).cpu().numpy()
         for b, p in enumerate(group):
             np.save(os.path.join(out, os.path.splitext(os.path.basename(p))[0] + ".npy"), tok[b, : lens[b]])
     print(f"{len(paths)} files -> {out}")

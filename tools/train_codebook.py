@@ -31,6 +31,8 @@ def main():
     ap.add_argument("--max_iter", type=int, default=500)
     ap.add_argument("--tol", type=float, default=1e-2)
     ap.add_argument("--minibatch", type=int, default=None)
+    ap.add_argument("--mode", default="euclidean", choices=("euclidean", "cosine"), help="KMeansGPU's distance measure (extract_tokens.py --metric cosine "
+                    "assigns by a cosine codebook)")
     a = ap.parse_args()
     paths = sorted(glob.glob(os.path.join(a.units_dir, "**", "*.npy"), recursive=True))
     if not paths:
@@ -39,6 +41,8 @@ def main():
     feats = np.concatenate([np.load(p).astype(np.float32) for p in paths[: a.max_files]], axis=0)
     torch.manual_seed(a.seed)
     kw = {} if a.minibatch is None else {"minibatch": a.minibatch}
+    if a.mode != "euclidean":
+        kw["mode"] = a.mode
     ck = cluster.train_cluster(feats, a.n_clusters, max_iter=a.max_iter, tol=a.tol, **kw)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     torch.save(ck, a.out)

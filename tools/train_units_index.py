@@ -29,14 +29,20 @@ import cluster  # noqa: E402
 from cluster.index import UnitsIndex  # noqa: E402
 
 
-def build_pool(feats, max_rows, reduce_to, seed=0, max_iter=100, tol=1e-2):
-    """feats [n, dim] -> (pool, reduced): the frames themselves up to max_rows, else reduce_to k-means centres of them"""
+def _mode(metric):
+    """train_cluster's extra arguments for an index metric: none for l2 (the call that was always made), mode="cosine" for cosine"""
+    return {} if metric == "l2" else {"mode": "cosine"}
+
+
+def build_pool(feats, max_rows, reduce_to, seed=0, max_iter=100, tol=1e-2, metric="l2"):
+    """feats [n, dim] -> (pool, reduced): the frames themselves up to max_rows, else reduce_to k-means centres of them (cosine k-means
+    for a cosine index)"""
     if feats.shape[0] <= max_rows:
         return np.ascontiguousarray(feats, dtype=np.float32), False
     if not 1 <= reduce_to <= max_rows:
         raise ValueError(f"--reduce_to {reduce_to} outside 1 .. --max_rows {max_rows}")
     torch.manual_seed(seed)
-    ck = cluster.train_cluster(feats, reduce_to, max_iter=max_iter, tol=tol)
+    ck = cluster.train_cluster(feats, reduce_to, max_iter=max_iter, tol=tol, **_mode(metric))
     return np.ascontiguousarray(ck["cluster_centers_"], dtype=np.float32), True
 
 
@@ -53,6 +59,8 @@ def main(argv=None):
     ap.add_argument("--synthetic", type=int, default=0, metavar="M")
     ap.add_argument("--nlist", type=int, default=0, help="lists of an IVF coarse index over the pool (0: none)")
     ap.add_argument("--nlist_iter", type=int, default=25)
+    ap.add_argument("--metric", default="l2", choices=("l2", "cosine"), help="cosine: kNN-VC's matching (the reduction and the IVF then use cosine k-means); "
+                    "the file records it and infer_svc.py / infer_tts.py follow it")
     a = ap.parse_args(argv)
     paths = sorted(glob.glob(os.path.join(a.units_dir, "**", "*.npy"), recursive=True))
     if not paths:
@@ -62,18 +70,18 @@ def main(argv=None):
     if a.synthetic:
         pool, reduced = np.random.default_rng(a.seed).standard_normal((a.synthetic, feats.shape[1])).astype(np.float32), False
     else:
-        pool, reduced = build_pool(feats, a.max_rows, a.reduce_to, a.seed, a.max_iter, a.tol)
+        pool, reduced = build_pool(feats, a.max_rows, a.reduce_to, a.seed, a.max_iter, a.tol, **({} if a.metric == "l2" else {"metric": a.metric}))
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    index = UnitsIndex(pool, source_rows=feats.shape[0], reduced=reduced)
+    index = UnitsIndex(pool, source_rows=feats.shape[0], reduced=reduced, metric=a.metric)
     if a.nlist:
         if not 1 <= a.nlist <= min(65536, pool.shape[0]):
             raise SystemExit(f"--nlist {a.nlist} outside 1 .. min(65536, the pool's {pool.shape[0]} rows)")
         torch.manual_seed(a.seed)
-        ck = cluster.train_cluster(pool, a.nlist, max_iter=a.nlist_iter, tol=a.tol)
+        ck = cluster.train_cluster(pool, a.nlist, max_iter=a.nlist_iter, tol=a.tol, **_mode(a.metric))
         index.build_ivf(a.nlist, centres=np.asarray(ck["cluster_centers_"], dtype=np.float32))
     index.save(a.out)
     print(f"{a.out}: {pool.shape[0]} rows of {pool.shape[1]} floats ({'k-means centres of' if reduced else 'the frames of' if not a.synthetic else 'synthetic, beside'} "
-          f"{feats.shape[0]} frames of {min(len(paths), a.max_files)} files)" + (f", {index.nlist} IVF lists" if a.nlist else ""))
+          f"{feats.shape[0]} frames of {min(len(paths), a.max_files)} files)" + (f", {index.nlist} IVF lists" if a.nlist else "") + (f", metric {a.metric}" if a.metric != "l2" else ""))
 
 
 if __name__ == "__main__":
