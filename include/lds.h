@@ -814,6 +814,52 @@ int lds_resample_frames_ragged(const float* in, const int32_t* tin, const int32_
 int lds_overlap_assemble(const float* segs, int64_t segs_len, const int64_t* host_tab, const int64_t* dev_tab, int S, const float* mask,
                          int64_t mask_len, float* out, int64_t N, void* stream);
 
+/* ---- CTC heads on the speech encoders: transcribe, score, align (csrc/ctc.hip; tests/ctc_numpy.py is the float64 restatement) -----------
+ * The reference has no CTC code; this replaces transformers' Wav2Vec2ForCTC / HubertForCTC / WavLMForCTC head (lm_head over the last hidden
+ * state, .logits / .loss), torch.nn.functional.ctc_loss, the greedy collapse of Wav2Vec2CTCTokenizer and torchaudio-style forced alignment.
+ * Stateless helpers, all fp32:
+ *   X dev [B][T][D]: units in the encode_ragged layout; n_frames host int32 [B], B <= 64, 0 <= n_frames[b] <= T.  Rows t >= n_frames[b]
+ *     are never read, whatever they hold (NaN included).
+ *   W dev [V][D], bias dev [V]: HF's lm_head.weight / lm_head.bias; blank in [0, V): HF's config.pad_token_id.
+ * Limits, checked before anything is enqueued (LDS_EINVAL with a message): D a multiple of 8 in 8 .. 4096, 2 <= V <= 65,536, 1 <= T,
+ * B * T <= 2^31 - 1000, 1 <= Lmax <= 511 (a batch of empty transcripts passes Lmax = 1), no NULL pointer except where noted; a workspace
+ * smaller than the entry's *_workspace_bytes gives LDS_ENOMEM with the size needed in the message.  Nothing synchronises.  No
+ * floating-point atomics: every call is bit-identical on repeat whatever the workspace held.
+ *   head    z[n][v] = x_n . w_v + b_v, exact fp32 on the MFMA (one fmaf chain per (n, v), the same for all).  Per valid frame:
+ *           arg = the argmax over v, the LOWEST id among exactly equal logits; m = z[arg]; lse = m + log sum_v exp(z_v - m).  exp never
+ *           sees a positive argument; the (max, rescaled sum) pairs of column tiles and column splits merge in one fixed order that
+ *           depends on V alone, so a frame's outputs depend on that frame and the head only: not on B, T, its position or other rows.
+ *           Padded rows: arg = -1, m = lse = 0.  The N x V matrix is never stored unless logprobs_out (dev [B][T][V]) is given: then
+ *           z - lse is also written, zeros in padded rows.
+ *   greedy  collapse runs of equal arg, drop blank.  Per clip: tokens int64 [T] padded with pad_id, n_tokens, and per emitted token
+ *           start (first frame of its run), length (run length), logprob (the mean of m - lse over the run, summed in double); beyond
+ *           n_tokens: start = -1, length = 0, logprob = 0.  It reads lds_ctc_head's outputs and needs no workspace.
+ *   score   labels dev int64 [B][Lmax], label_len host int32 [B] (0 <= label_len[b] <= Lmax): nll[b] = -log p(labels_b | X_b) by the CTC
+ *           forward recursion in log space = F.ctc_loss(log_probs, .., blank, reduction='none', zero_infinity=False).  Infeasible
+ *           (n_frames < L + the number of adjacent equal labels): +inf.  L = 0: -sum_t logp(blank).  n_frames = 0: 0 if L = 0, else +inf.
+ *           A label outside [0, V) or equal to blank: that clip's nll is +inf and nothing outside W is read.  The emissions are computed
+ *           for the clip's L + 1 distinct columns only (W's rows gathered by label).
+ *   align   the Viterbi path of the same trellis (states 0 .. 2 L: blank, label 0, blank, ..; a path starts in state 0 or 1 and ends in
+ *           state 2 L or 2 L - 1).  Ties between predecessors: prefer STAY, then STEP (from the state below), then SKIP (from two below,
+ *           allowed into a label that differs from the label before); equal final states: the blank.  path_score[b] = the path's
+ *           log-probability (-inf if infeasible or a bad label); frame_label int32 [B][T] = index into the clip's labels, -1 on blank
+ *           frames and beyond n_frames; segments int32 [B][Lmax][2] = (first frame, one past the last frame) of each label's non-blank
+ *           frames, (-1, -1) if infeasible or beyond label_len; label_logprob [B][Lmax] = the mean emission over those frames (0 where
+ *           there are none). */
+int lds_ctc_head_workspace_bytes(int B, int T, int V, int D, size_t* out);
+int lds_ctc_head(const float* X, int B, int T, const int32_t* n_frames, const float* W, const float* bias, int V, int D, int32_t* arg, float* m, float* lse,
+                 float* logprobs_out, void* ws, size_t ws_bytes, void* stream);
+/* arg, m, lse dev [B][T]: lds_ctc_head's outputs (any int32 ids in general); every output dev [B][T] but n_tokens dev int32 [B] */
+int lds_ctc_greedy(const int32_t* arg, const float* m, const float* lse, int B, int T, const int32_t* n_frames, int blank, int64_t pad_id, int64_t* tokens,
+                   int32_t* n_tokens, int32_t* start, int32_t* length, float* logprob, void* stream);
+int lds_ctc_score_workspace_bytes(int B, int T, int V, int D, int Lmax, size_t* out);
+int lds_ctc_score(const float* X, int B, int T, const int32_t* n_frames, const float* W, const float* bias, int V, int D, int blank, const int64_t* labels,
+                  const int32_t* label_len, int Lmax, float* nll, void* ws, size_t ws_bytes, void* stream);
+int lds_ctc_align_workspace_bytes(int B, int T, int V, int D, int Lmax, size_t* out);
+int lds_ctc_align(const float* X, int B, int T, const int32_t* n_frames, const float* W, const float* bias, int V, int D, int blank, const int64_t* labels,
+                  const int32_t* label_len, int Lmax, float* path_score, int32_t* frame_label, int32_t* segments, float* label_logprob, void* ws,
+                  size_t ws_bytes, void* stream);
+
 /* ---- per-launch HIP-event timing for bench.py's roofline leg (off by default) ------------------
  * lds_prof_enable(1) clears and starts recording one event pair per kernel launch on the launch
  * stream; lds_prof_summary synchronises them and writes a JSON list of

@@ -280,6 +280,14 @@ int lds_test_ivf_search_metric(const float* X, int64_t N, const float* P, const 
                                const int64_t* offsets, const int32_t* order, const float* PL, const float* hl, int64_t copy_rows, int nprobe, int metric,
                                int slab_rows, int32_t* idx, float* score, void* ws, size_t ws_bytes, void* stream);
 
+/* The two CTC recursions of csrc/ctc.hip on ready emissions E dev [B][T][Lmax + 1] (column 0 the blank's log-prob, column j that of label
+ * j - 1 of the clip), so that they are tested apart from the head: lds_ctc_score's nll and lds_ctc_align's four outputs (include/lds.h).
+ * labels dev int64 [B][Lmax] are read for their repeats only.  The Viterbi workspace holds B * T * 256 bytes of back-pointers or more. */
+int lds_test_ctc_forward(const float* E, int B, int T, const int32_t* n_frames, const int64_t* labels, const int32_t* label_len, int Lmax, float* nll,
+                         void* stream);
+int lds_test_ctc_viterbi(const float* E, int B, int T, const int32_t* n_frames, const int64_t* labels, const int32_t* label_len, int Lmax, float* path_score,
+                         int32_t* frame_label, int32_t* segments, float* label_logprob, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- debugging aids (tests/test_gpu_poison.py, tools/diag_trace.py) ----------------------------------------------------------
  * lds_debug_fill_u32: every 32-bit word of a device buffer = pattern.  Tests fill a caller workspace with NaN patterns (0x7fc07fc0 is a NaN
  * as fp32 and as two fp16 / bf16 halves) before a call: a kernel that reads a slot no kernel of THAT call wrote turns it into a NaN (or, behind

@@ -175,6 +175,13 @@ lds_ivf_retrieve                 i:pqppqiippippppqifppppzp
 lds_ivf_retrieve_metric          i:pqppqiippippppqiiifppppzp
 lds_ivf_retrieve_ragged          i:piipppqiippippppqifppppzp
 lds_ivf_retrieve_ragged_metric   i:piipppqiippippppqiiifppppzp
+lds_ctc_head_workspace_bytes     i:iiiip
+lds_ctc_head                     i:piipppiipppppzp
+lds_ctc_greedy                   i:pppiipiqpppppp
+lds_ctc_score_workspace_bytes    i:iiiiip
+lds_ctc_score                    i:piipppiiippippzp
+lds_ctc_align_workspace_bytes    i:iiiiip
+lds_ctc_align                    i:piipppiiippipppppzp
 lds_resample                     i:ppppiiiiqqp
 lds_resample_ragged              i:ppppppiiiiqqp
 lds_frame_rms                    i:ppqiiiqp
@@ -251,6 +258,8 @@ lds_test_knn_search              i:pqppqiiiipppzp
 lds_test_knn_search_metric       i:pqppqiiiiipppzp
 lds_test_ivf_search              i:pqppqiippippppqiipppzp
 lds_test_ivf_search_metric       i:pqppqiippippppqiiipppzp
+lds_test_ctc_forward             i:piipppipp
+lds_test_ctc_viterbi             i:piipppipppppzp
 """
 SIGNATURES = dict(ln.split() for ln in (_PUBLIC + _TEST).splitlines() if ln)
 EXPORTS = [ln.split()[0] for ln in _PUBLIC.splitlines() if ln]
@@ -1531,6 +1540,130 @@ def ivf_retrieve(x, pool, h, k, ratio, ivf, nprobe, lengths=None, ws=None, metri
 # ---- polyphase resampler (lds_resample*): the filter of one (orig, new, width, rolloff) is built once on the host (arch.resample_bank) and
 # uploaded once per device ----
 _resample_tables = {}
+
+
+# ---- CTC heads (lds_ctc_*): thin wrappers; units [B, T, D], weight [V, D], bias [V] contiguous fp32 device tensors ----
+_ctc_ws = Workspace()
+CTC_MAX_LABELS = 511
+
+
+def _ctc_ws_for(ws, entry, dims, device):
+    if device.type != "cuda":
+        raise RuntimeError("liblds needs tensors on a HIP device (no CPU fallback for the hot path)")
+    nb = _bytes(entry, *dims)
+    if ws is not None and ws.numel() < nb:
+        raise ValueError(f"{entry[:-16]}: workspace of {ws.numel()} bytes, {nb} needed")
+    return ws if ws is not None else _ctc_ws.get(nb, device)
+
+
+def _ctc_units(units, n_frames, weight):
+    if units.dim() != 3 or weight.dim() != 2 or units.shape[-1] != weight.shape[1]:
+        raise ValueError(f"ctc: units {list(units.shape)} against a head {list(weight.shape)}")
+    B, T, D = units.shape
+    if T < 1:
+        raise ValueError("ctc: no frames")
+    return B, T, D, weight.shape[0], _host_lengths(n_frames, B, 0, T, 64, "CTC")
+
+
+def ctc_head(units, n_frames, weight, bias, return_logprobs=False, ws=None):
+    """units [B, T, D], n_frames (host ints [B], 0 .. T) -> (arg int32 [B, T], m, lse fp32 [B, T][, log-probs [B, T, V]]): per valid frame
+    the arg-max of the logits (lowest id among ties), its logit and the log-sum-exp (include/lds.h lds_ctc_head)"""
+    import torch
+    B, T, D, V, nf = _ctc_units(units, n_frames, weight)
+    ws = _ctc_ws_for(ws, "lds_ctc_head_workspace_bytes", (B, T, V, D), units.device)
+    arg = torch.empty(B, T, dtype=torch.int32, device=units.device)
+    m, lse = torch.empty(B, T, dtype=torch.float32, device=units.device), torch.empty(B, T, dtype=torch.float32, device=units.device)
+    lp = torch.empty(B, T, V, dtype=torch.float32, device=units.device) if return_logprobs else None
+    check(lib().lds_ctc_head(_dev(units, torch.float32), B, T, _host(nf), _dev(weight, torch.float32), _dev(bias, torch.float32), V, D, _dev(arg), _dev(m),
+                             _dev(lse), _dev_or_null(lp), _dev(ws), ws.numel(), _stream()))
+    return (arg, m, lse, lp) if return_logprobs else (arg, m, lse)
+
+
+def ctc_greedy(arg, m, lse, n_frames, blank, pad_id=-1):
+    """ctc_head's outputs -> (tokens int64 [B, T], n_tokens int32 [B], start, length int32 [B, T], logprob fp32 [B, T]): runs of equal arg
+    collapsed, blank dropped (include/lds.h lds_ctc_greedy)"""
+    import torch
+    B, T = arg.shape
+    nf = _host_lengths(n_frames, B, 0, T, 64, "CTC")
+    dev = arg.device
+    tokens = torch.empty(B, T, dtype=torch.int64, device=dev)
+    n_tokens = torch.empty(B, dtype=torch.int32, device=dev)
+    start, length = torch.empty(B, T, dtype=torch.int32, device=dev), torch.empty(B, T, dtype=torch.int32, device=dev)
+    logprob = torch.empty(B, T, dtype=torch.float32, device=dev)
+    check(lib().lds_ctc_greedy(_dev(arg, torch.int32), _dev(m, torch.float32), _dev(lse, torch.float32), B, T, _host(nf), int(blank), int(pad_id), _dev(tokens),
+                               _dev(n_tokens), _dev(start), _dev(length), _dev(logprob), _stream()))
+    return tokens, n_tokens, start, length, logprob
+
+
+def _ctc_labels(labels, label_len, B):
+    """labels int64 [B, Lmax] (device), label_len host ints -> (labels, host int32 [B], Lmax); an empty label matrix becomes one unused column"""
+    import torch
+    if labels.dim() != 2 or labels.shape[0] != B:
+        raise ValueError(f"ctc: labels {list(labels.shape)} for {B} clips")
+    if labels.shape[1] > CTC_MAX_LABELS:
+        raise ValueError(f"ctc: at most {CTC_MAX_LABELS} labels per clip (got {labels.shape[1]})")
+    ll = _host_lengths(label_len, B, 0, labels.shape[1])
+    if labels.shape[1] == 0:
+        labels = torch.zeros(B, 1, dtype=torch.int64, device=labels.device)
+    return labels, ll, labels.shape[1]
+
+
+def ctc_score(units, n_frames, weight, bias, blank, labels, label_len, ws=None):
+    """nll fp32 [B] = -log p(labels_b | units_b) by the CTC forward recursion (include/lds.h lds_ctc_score)"""
+    import torch
+    B, T, D, V, nf = _ctc_units(units, n_frames, weight)
+    labels, ll, Lmax = _ctc_labels(labels, label_len, B)
+    ws = _ctc_ws_for(ws, "lds_ctc_score_workspace_bytes", (B, T, V, D, Lmax), units.device)
+    nll = torch.empty(B, dtype=torch.float32, device=units.device)
+    check(lib().lds_ctc_score(_dev(units, torch.float32), B, T, _host(nf), _dev(weight, torch.float32), _dev(bias, torch.float32), V, D, int(blank),
+                              _dev(labels, torch.int64), _host(ll), Lmax, _dev(nll), _dev(ws), ws.numel(), _stream()))
+    return nll
+
+
+def _ctc_align_outputs(B, T, Lmax, device):
+    import torch
+    return (torch.empty(B, dtype=torch.float32, device=device), torch.empty(B, T, dtype=torch.int32, device=device),
+            torch.empty(B, Lmax, 2, dtype=torch.int32, device=device), torch.empty(B, Lmax, dtype=torch.float32, device=device))
+
+
+def ctc_align(units, n_frames, weight, bias, blank, labels, label_len, ws=None):
+    """the Viterbi alignment: (path_score [B], frame_label int32 [B, T], segments int32 [B, Lmax, 2], label_logprob [B, Lmax])
+    (include/lds.h lds_ctc_align)"""
+    import torch
+    B, T, D, V, nf = _ctc_units(units, n_frames, weight)
+    labels, ll, Lmax = _ctc_labels(labels, label_len, B)
+    ws = _ctc_ws_for(ws, "lds_ctc_align_workspace_bytes", (B, T, V, D, Lmax), units.device)
+    ps, fl, seg, llp = _ctc_align_outputs(B, T, Lmax, units.device)
+    check(lib().lds_ctc_align(_dev(units, torch.float32), B, T, _host(nf), _dev(weight, torch.float32), _dev(bias, torch.float32), V, D, int(blank),
+                              _dev(labels, torch.int64), _host(ll), Lmax, _dev(ps), _dev(fl), _dev(seg), _dev(llp), _dev(ws), ws.numel(), _stream()))
+    return ps, fl, seg, llp
+
+
+def ctc_test_forward(E, n_frames, labels, label_len):
+    """the forward recursion alone on ready emissions E [B, T, Lmax + 1] (include/lds_test.h)"""
+    import torch
+    B, T, W1 = E.shape
+    nf = _host_lengths(n_frames, B, 0, T, 64, "CTC")
+    ll = _host_lengths(label_len, B, 0, W1 - 1)
+    assert tuple(labels.shape) == (B, W1 - 1)
+    nll = torch.empty(B, dtype=torch.float32, device=E.device)
+    check(lib().lds_test_ctc_forward(_dev(E, torch.float32), B, T, _host(nf), _dev(labels, torch.int64), _host(ll), W1 - 1, _dev(nll), _stream()))
+    return nll
+
+
+def ctc_test_viterbi(E, n_frames, labels, label_len, ws=None):
+    """the Viterbi recursion and backtrace alone on ready emissions E [B, T, Lmax + 1] (include/lds_test.h)"""
+    import torch
+    B, T, W1 = E.shape
+    nf = _host_lengths(n_frames, B, 0, T, 64, "CTC")
+    ll = _host_lengths(label_len, B, 0, W1 - 1)
+    assert tuple(labels.shape) == (B, W1 - 1)
+    if ws is None:
+        ws = _ctc_ws.get(B * T * 256, E.device)
+    ps, fl, seg, llp = _ctc_align_outputs(B, T, W1 - 1, E.device)
+    check(lib().lds_test_ctc_viterbi(_dev(E, torch.float32), B, T, _host(nf), _dev(labels, torch.int64), _host(ll), W1 - 1, _dev(ps), _dev(fl), _dev(seg),
+                                     _dev(llp), _dev(ws), ws.numel(), _stream()))
+    return ps, fl, seg, llp
 
 
 def resample_tables(orig_freq, new_freq, lowpass_filter_width=6, rolloff=0.99):
