@@ -288,6 +288,28 @@ int lds_test_ctc_forward(const float* E, int B, int T, const int32_t* n_frames, 
 int lds_test_ctc_viterbi(const float* E, int B, int T, const int32_t* n_frames, const int64_t* labels, const int32_t* label_len, int Lmax, float* path_score,
                          int32_t* frame_label, int32_t* segments, float* label_logprob, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- the resnets' k 3 convolution in the Winograd form F(2,3) (csrc/conv_wino.hip) ----------------------------------------------
+ * lds_test_wino_pack (host only): g [Co][Ci][3] -> U [4][Co][Ci], U0 = g0, U1 = (g0 + g1 + g2) / 2, U2 = (g0 - g1 + g2) / 2, U3 = g2, computed in
+ * double and rounded once.
+ * lds_test_wino_conv: out = conv_k3(act(GroupNorm([x1 ; x2]) (* (1 + scale) + shift))) + bias (+ res) as the UNet's routed resnet convolutions
+ * run it: GroupNorm partials of the sources, the transform pass (gn_wino_kernel), conv_wino.  Planes, K4P output and partial buffers start as
+ * NaN.  out dev [B,Co,T]; vplanes (or NULL) dev [B][Ci/8][2][4][ceil(T/2)][4], the raw planes; gnpart (or NULL) dev [B][Co/16][ceil(T/32)][2],
+ * the epilogue's (mean, M2) of every (16 channels x 32 frames) block inside a length.  lengths: frames at and beyond lengths[b] are outside
+ * utterance b (zeros in x and res as the kernels see them, zeros in out).  poison 1: the sources' pad frames and their frames beyond the
+ * lengths hold NaN / Inf when the transform pass reads them.  An armed lds_test_tap_k4p receives the raw K4P output.
+ * lds_bench_wino: the direct pair (gn_stream + conv_dma) against the Winograd pair on the same inputs, alternating in blocks of `iters`
+ * passes, `reps` times; ms_direct / ms_wino [reps] = a block's device time per pass (events on the stream around each block). */
+int lds_test_wino_pack(const float* g, int Co, int Ci, float* U);
+/* x1 / x2 dev [B,C1,T] / [B,C2,T] (x2 may be NULL); gamma / beta host [C1+C2]; scale_shift dev [B, 2 (C1+C2)] (scales, then shifts) or NULL;
+ * w / bias host, reference layout [Co, C1+C2, 3] / [Co] or NULL; res dev [B,Co,T] or NULL; lengths HOST int32 [B], 1 <= lengths[b] <= T, or
+ * NULL; cfg 0 = the launcher's choice, else BK * 10 + NST in {322, 162} */
+int lds_test_wino_conv(const float* x1, const float* x2, int C1, int C2, int T, const float* gamma, const float* beta, const float* scale_shift,
+                       int groups, int silu, const float* w, const float* bias, int Co, const float* res, const int32_t* lengths, int poison, int cfg,
+                       float* out, float* vplanes, float* gnpart, int B, void* stream);
+int lds_bench_wino(const float* x1, const float* x2, int C1, int C2, int T, const float* gamma, const float* beta, const float* scale_shift,
+                   int groups, int silu, const float* w, const float* bias, int Co, const float* res, int cfg, int B, int iters, int reps,
+                   float* ms_direct, float* ms_wino, char* cfg_out, size_t cfg_cap, void* stream);
+
 /* ---- debugging aids (tests/test_gpu_poison.py, tools/diag_trace.py) ----------------------------------------------------------
  * lds_debug_fill_u32: every 32-bit word of a device buffer = pattern.  Tests fill a caller workspace with NaN patterns (0x7fc07fc0 is a NaN
  * as fp32 and as two fp16 / bf16 halves) before a call: a kernel that reads a slot no kernel of THAT call wrote turns it into a NaN (or, behind

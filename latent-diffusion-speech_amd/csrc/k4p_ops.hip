@@ -85,6 +85,22 @@ hipError_t launch_k4p_zero_pads(float* x, int B, int C, int T, int pad, hipStrea
     return hipGetLastError();
 }
 
+// test support (lds_test_wino_conv): NaN / Inf into both pad frames of every row and into the frames at and beyond the utterance's length
+__global__ void __launch_bounds__(256) k4p_poison_kernel(float* __restrict__ x, int T, const int* __restrict__ lens) {
+    const int Tp = T + 2, Tv = ragged_len(lens, blockIdx.y, 0, T);
+    float* xb = x + ((long long)blockIdx.y * gridDim.x + blockIdx.x) * 2 * Tp * 4;
+    const float nan = __builtin_nanf(""), inf = __builtin_inff();
+    for (int idx = threadIdx.x; idx < 2 * Tp; idx += 256) {
+        const int hh = idx / Tp, e = idx - hh * Tp;
+        if (e == 0 || e > Tv) *reinterpret_cast<f32x4*>(xb + (long long)idx * 4) = f32x4{nan, inf, -inf, nan};
+    }
+}
+hipError_t launch_k4p_poison(float* x, int B, int C, int T, const int* lens, hipStream_t s) {
+    if (C & 7) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k4p_poison_kernel, dim3(C / 8, B), dim3(256), 0, s, x, T, lens);
+    return hipGetLastError();
+}
+
 __global__ void __launch_bounds__(256) from_k4p_kernel(const float* __restrict__ in, float* __restrict__ out, int C, int T) {
     const int q = blockIdx.x, b = blockIdx.y;
     const int Tp = T + 2;
@@ -150,12 +166,12 @@ static __device__ __forceinline__ float wave_sum_to_lane63(float v) {
     return v;
 }
 // one wave per (16-channel block, 32-frame block)
-__global__ void __launch_bounds__(64) gn_partials_kernel(const float* __restrict__ x, int C, int T, float2* __restrict__ gp) {
+__global__ void __launch_bounds__(64) gn_partials_kernel(const float* __restrict__ x, int C, int T, float2* __restrict__ gp, const int* __restrict__ lens, int lvl) {
     const int nT = (T + 31) >> 5, kb = blockIdx.x / nT, tb = blockIdx.x - kb * nT, b = blockIdx.y, lane = threadIdx.x;
-    const int Tp = T + 2;
+    const int Tp = T + 2, Tv = ragged_len(lens, b, lvl, T);      // (ragged batch: statistics over the utterance's own frames, as the convolutions' epilogues write them)
     const float* xb = x + (((long long)b * (C >> 3) + 2 * kb) * 2) * Tp * 4;      // 4 rows: (q = 2kb, 2kb+1) x (hh = 0, 1)
     const int t = tb * 32 + (lane & 31), half = lane >> 5;                          // each lane: two rows of one frame
-    const bool ok = t < T;
+    const bool ok = t < Tv;
     const float k = xb[(long long)(tb * 32 + 1) * 4];                               // element (row 0, first frame of the block, j = 0)
     float s1 = 0.f, s2 = 0.f;
 #pragma unroll
@@ -168,16 +184,16 @@ __global__ void __launch_bounds__(64) gn_partials_kernel(const float* __restrict
     }
     s1 = wave_sum_to_lane63(s1);
     s2 = wave_sum_to_lane63(s2);
-    const int nv = (T - tb * 32 < 32) ? T - tb * 32 : 32;
-    if (lane == 63) {
+    const int nv = (Tv - tb * 32 < 32) ? Tv - tb * 32 : 32;
+    if (lane == 63 && nv > 0) {      // (a block beyond the utterance's length has no partial: its slot is never read)
         const float cnt = 16.0f * (float)nv, rc = 1.0f / cnt;
         gp[((long long)b * (C >> 4) + kb) * nT + tb] = make_float2(k + s1 * rc, fmaxf(s2 - s1 * s1 * rc, 0.f));
     }
 }
-hipError_t launch_gn_partials(const float* x, int C, int T, float2* gp, int B, hipStream_t s) {
+hipError_t launch_gn_partials(const float* x, int C, int T, float2* gp, int B, hipStream_t s, const int* lens, int lvl) {
     if (C & 15) return hipErrorInvalidValue;
     ProfScope ps(s, "gn_partials", 0.0, 4.0 * B * (double)C * T);
-    hipLaunchKernelGGL(gn_partials_kernel, dim3((C / 16) * ((T + 31) / 32), B), dim3(64), 0, s, x, C, T, gp);
+    hipLaunchKernelGGL(gn_partials_kernel, dim3((C / 16) * ((T + 31) / 32), B), dim3(64), 0, s, x, C, T, gp, lens, lvl);
     return hipGetLastError();
 }
 
@@ -350,6 +366,164 @@ hipError_t launch_gn_stream(const float* x1, const float* x2, int C1, int C2, in
     } else if (need <= 1) hipLaunchKernelGGL(gn_stream_kernel<1>, grid, blk, 0, s, GN_ARGS);
     else if (need <= 2) hipLaunchKernelGGL(gn_stream_kernel<2>, grid, blk, 0, s, GN_ARGS);
     else hipLaunchKernelGGL(gn_stream_kernel<4>, grid, blk, 0, s, GN_ARGS);
+#undef GN_ARGS
+    return hipGetLastError();
+}
+
+// gn_stream_kernel with the Winograd F(2,3) input transform behind it (conv_wino.hip; kernels.h launch_gn_wino).  The prologue -- scalar
+// requests, partials, statistics -- is gn_stream_kernel's, statement for statement, and so is the arithmetic of d = act(GroupNorm(x)): the
+// values that enter the transform are bit for bit what gn_stream writes.  A work item is one frame pair i of one row: it loads the row's
+// entries of frames 2i-1 .. 2i+2 (the padded input d[2i .. 2i+3]: four 16-byte loads where gn_stream has two per pair, no second pass and
+// no exchange across waves), forms d at the four frames -- zero outside [0, Tv) by selects on the computed values, so whatever the pad frames or the frames beyond an
+// utterance's length hold never reaches a plane -- and stores one 16-byte entry into each plane:
+//   V0 = d[2i] - d[2i+2], V1 = d[2i+1] + d[2i+2], V2 = d[2i+2] - d[2i+1], V3 = d[2i+1] - d[2i+3]      y: [B][C/8][2][4][P][4], P = ceil(T / 2)
+template <int E>
+__global__ void __launch_bounds__(256) gn_wino_kernel(const float* __restrict__ x1, const float* __restrict__ x2, int C1, int C2, int T,
+                                                      int cg16, unsigned gm, unsigned gsh, float inv_nT, float eps,
+                                                      const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                      const float* __restrict__ ss, int ss_stride, int ss_off, int silu,
+                                                      const float2* __restrict__ gp1, const float2* __restrict__ gp2, float* __restrict__ y,
+                                                      const int* __restrict__ lens, int lvl) {
+    asm volatile("" : "+s"(x1), "+s"(x2), "+s"(C1), "+s"(C2), "+s"(T), "+s"(cg16), "+s"(gm), "+s"(gsh), "+s"(inv_nT), "+s"(eps), "+s"(gamma), "+s"(beta),
+                      "+s"(ss), "+s"(ss_stride), "+s"(ss_off), "+s"(silu), "+s"(gp1), "+s"(gp2), "+s"(y), "+s"(lens), "+s"(lvl));
+    const int q = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, lane = tid & 63;
+    const int C = C1 + C2, Tp = T + 2, nq1 = C1 >> 3, nq = C >> 3, Pn = (T + 1) >> 1;
+    const float* sp = ss ? ss + (long long)b * ss_stride + ss_off + q * 8 : gamma + q * 8;
+    const gn_f32x8 g8 = gn_load8(gamma + q * 8), b8 = gn_load8(beta + q * 8), sc8 = gn_load8(sp), sh8 = gn_load8(ss ? sp + C : sp);
+    int Tv = T;
+    if (lens) {
+        int n = ((const __attribute__((address_space(4))) int*)(unsigned long long)lens)[b];
+        asm volatile("" : "+s"(n));
+        for (int i = 0; i < lvl; ++i) n = (n - 1) / 2 + 1;
+        Tv = n < T ? n : T;
+    }
+    const float* xb = (q < nq1) ? x1 + (((long long)b * nq1 + q) * 2) * Tp * 4 : x2 + (((long long)b * (C2 >> 3) + (q - nq1)) * 2) * Tp * 4;
+    float* yb = y + (((long long)b * nq + q) * 2) * 4 * Pn * 4;
+    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(xb), 0, 2 * Tp * 16, 0x00020000);
+    const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(yb, 0, 2 * 4 * Pn * 16, 0x00020000);
+    const int total = 2 * Pn;                         // work items of this block: (row hh, pair i) -> idx = hh * Pn + i
+    const int g = (int)dma_magic_div((unsigned)q, gm, gsh);
+    const int nT = (T + 31) >> 5, P = cg16 * nT, nk1 = C1 >> 4;
+    auto request = [&](int p0, float& nb, bool& ok) {
+        const int pi = p0 + lane;
+        const bool in = pi < P;
+        const int pc = in ? pi : 0;
+        const int kk = (int)(((float)pc + 0.5f) * inv_nT), tb = pc - kk * nT, kb = g * cg16 + kk;
+        const int nv = (Tv - tb * 32 < 32) ? Tv - tb * 32 : 32;
+        const bool f1 = kb < nk1;
+        const int off = ((f1 ? b * nk1 : b * (C2 >> 4) - nk1) + kb) * nT + tb;
+        ok = in && nv > 0;
+        nb = ok ? 16.0f * (float)nv : 0.f;
+        return ((const __attribute__((address_space(1))) gn_f32x2*)(unsigned long long)(f1 ? gp1 : gp2))[off];
+    };
+    auto part = [&](int p0, float& nb, float& mb, float& qb) {
+        bool ok;
+        const gn_f32x2 pr = request(p0, nb, ok);
+        mb = ok ? pr.x : 0.f; qb = ok ? pr.y : 0.f;
+    };
+    float n0, n1;
+    bool ok0, ok1;
+    gn_f32x2 pr0 = request(0, n0, ok0), pr1 = request(64, n1, ok1);
+    // entry of frame 2i - 1 + f of the item's row = entry 2i + f of the padded row (frame -1 is the left pad frame; a frame beyond the row
+    // reads the right pad frame or the next row: the selects below never let such a value through)
+    auto entry = [&](int idx, int f) {
+        const int hh = idx >= Pn, i = idx - hh * Pn;
+        return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rx, (hh * Tp + 2 * i + f) * 16, 0, 0));
+    };
+    f32x4 v[E][4];
+#pragma unroll
+    for (int i = 0; i < E; ++i)
+#pragma unroll
+        for (int f = 0; f < 4; ++f) v[i][f] = entry(tid + 256 * i, f);
+    asm volatile("" : "+v"(pr0), "+v"(pr1));
+    const float m0 = ok0 ? pr0.x : 0.f, q0 = ok0 ? pr0.y : 0.f, m1 = ok1 ? pr1.x : 0.f, q1 = ok1 ? pr1.y : 0.f;
+    float ga[2][4], be[2][4];
+#pragma unroll
+    for (int hh = 0; hh < 2; ++hh)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float g_ = g8[2 * j + hh], b_ = b8[2 * j + hh];
+            if (ss) {
+                const float sc = 1.0f + sc8[2 * j + hh];
+                g_ *= sc;
+                b_ = fmaf(b_, sc, sh8[2 * j + hh]);
+            }
+            ga[hh][j] = g_; be[hh][j] = b_;
+        }
+    float s1 = fmaf(n1, m1, __fmul_rn(n0, m0));
+    for (int p0 = 128; p0 < P; p0 += 64) {
+        float nb, mb, qb;
+        part(p0, nb, mb, qb);
+        s1 = fmaf(nb, mb, s1);
+    }
+    const float rN = __builtin_amdgcn_rcpf(16.0f * (float)cg16 * (float)Tv);
+    const float mu = __fmul_rn(gnf_wave_sum(s1), rN);
+    const float d0 = __fsub_rn(m0, mu), d1 = __fsub_rn(m1, mu);
+    float s2 = __fadd_rn(fmaf(__fmul_rn(n0, d0), d0, q0), fmaf(__fmul_rn(n1, d1), d1, q1));
+    for (int p0 = 128; p0 < P; p0 += 64) {
+        float nb, mb, qb;
+        part(p0, nb, mb, qb);
+        const float d = __fsub_rn(mb, mu);
+        s2 = __fadd_rn(s2, fmaf(__fmul_rn(nb, d), d, qb));
+    }
+    const float rstd = __builtin_amdgcn_rsqf(fmaf(gnf_wave_sum(s2), rN, eps));
+#pragma unroll
+    for (int hh = 0; hh < 2; ++hh)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) ga[hh][j] *= rstd;
+    for (int base = 0; base < total; base += 256 * E) {
+        if (base > 0) {
+#pragma unroll
+            for (int i = 0; i < E; ++i)
+#pragma unroll
+                for (int f = 0; f < 4; ++f) v[i][f] = entry(base + tid + 256 * i, f);
+        }
+#pragma unroll
+        for (int i = 0; i < E; ++i) {
+            const int idx = base + tid + 256 * i;
+            if (idx < total) {
+                const int hh = idx >= Pn, pi = idx - hh * Pn;
+                f32x4 d[4];
+#pragma unroll
+                for (int f = 0; f < 4; ++f) {
+                    const int t = 2 * pi - 1 + f;
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        float r = fmaf(v[i][f][j] - mu, hh ? ga[1][j] : ga[0][j], hh ? be[1][j] : be[0][j]);
+                        if (silu) r = r * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(r * -1.4426950408889634f));
+                        d[f][j] = (t >= 0 && t < Tv) ? r : 0.f;
+                    }
+                }
+                const f32x4 pl[4] = {d[0] - d[2], d[1] + d[2], d[2] - d[1], d[1] - d[3]};
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, pl[j]), ry, ((hh * 4 + j) * Pn + pi) * 16, 0, 16);
+            }
+        }
+    }
+}
+
+hipError_t launch_gn_wino(const float* x1, const float* x2, int C1, int C2, int T, int groups, float eps, const float* gamma, const float* beta,
+                          const float* ss, int ss_stride, int ss_off, int silu, const float2* gp1, const float2* gp2, float* y, int B, hipStream_t s,
+                          const int* lens, int lvl) {
+    const int C = C1 + C2;
+    if ((C1 & 15) || (C2 & 15) || groups <= 0 || C % groups || (C / groups) % 16 || !gp1 || (C2 && !gp2)) return hipErrorInvalidValue;
+    const int Pn = (T + 1) / 2;
+    ProfScope ps(s, "gn_wino", 0.0, 4.0 * B * (double)C * (T + 4.0 * Pn), true);
+    const dim3 grid(C / 8, B), blk(256);
+    const int need = (2 * Pn + 255) / 256;
+    const int cg16 = (C / groups) >> 4;
+    const DmaMagic gmg = dma_magic((unsigned)(2 * cg16));
+    const float inv_nT = 1.0f / (float)((T + 31) >> 5);
+#define GN_ARGS x1, x2 ? x2 : x1, C1, C2, T, cg16, gmg.m, gmg.s, inv_nT, eps, gamma, beta, ss, ss_stride, ss_off, silu, gp1, gp2 ? gp2 : gp1, y, lens, lvl
+    hipEvent_t e0, e1;
+    if (prof_attach_events(&e0, &e1)) {
+        if (need <= 1) hipExtLaunchKernelGGL(gn_wino_kernel<1>, grid, blk, 0, s, e0, e1, 0, GN_ARGS);
+        else if (need <= 2) hipExtLaunchKernelGGL(gn_wino_kernel<2>, grid, blk, 0, s, e0, e1, 0, GN_ARGS);
+        else hipExtLaunchKernelGGL(gn_wino_kernel<4>, grid, blk, 0, s, e0, e1, 0, GN_ARGS);
+    } else if (need <= 1) hipLaunchKernelGGL(gn_wino_kernel<1>, grid, blk, 0, s, GN_ARGS);
+    else if (need <= 2) hipLaunchKernelGGL(gn_wino_kernel<2>, grid, blk, 0, s, GN_ARGS);
+    else hipLaunchKernelGGL(gn_wino_kernel<4>, grid, blk, 0, s, GN_ARGS);
 #undef GN_ARGS
     return hipGetLastError();
 }

@@ -196,6 +196,32 @@ bool conv_dma_pair_applies(const DmaConvArgs& a3, const DmaConvArgs& a1);
 const char* conv_dma_last_config();
 
 // ---------------------------------------------------------------------------------------------
+// conv_wino: the resnets' k 3 / stride 1 / pad 1 convolution in the 1-D Winograd form F(2,3) (conv_wino.hip): two output frames from
+// four products instead of six.  The input is not a K4P tensor but the four planes V0..V3 that launch_gn_wino writes over P = ceil(T / 2)
+// frame pairs, [B][Ci/8][2][4][P][4] (row (q, h) of K4P, then plane, then pair; no pad entries); the weights are the four taps U0..U3 in
+// conv_dma's packed layout [4][Ci/8][2][Mp][4].  Output: K4P (pads written), + bias, + residual, GroupNorm partials as DmaConvArgs.
+// ---------------------------------------------------------------------------------------------
+struct WinoConvArgs {
+    const float* v; const float* u;
+    const float* bias;            // [Mp] or null
+    const float* res;             // K4P [B][Co][T] or null
+    float* out;                   // K4P [B][Co][T]
+    float2* gnpart_out;           // [B][Co/16][ceil(T/32)] (mean, M2) or null
+    const int* lens; int lvl;     // ragged batches (k4p.h ragged_len): this tensor's level; null = every utterance has T frames
+    int B, Ci, Mp, Co, T;
+    unsigned ord_m[2], ord_s;     // filled by the launcher: the divisors (M-blocks, pair blocks) of the block-index decomposition (dma_magic)
+};
+// cfg = BK * 10 + NST in {322, 162} (0 = by the grid at the nominal batch); Ci % BK == 0, Mp % 32 == 0, Co % 16 == 0
+hipError_t launch_conv_wino(const WinoConvArgs& a, int cfg, hipStream_t s);
+const char* conv_wino_last_config();
+// launch_gn_stream's pass with the Winograd input transform behind it: d = act(GroupNorm(...)) exactly as launch_gn_stream computes it (frames
+// outside [0, ragged length) are zero), then V0 = d[2i] - d[2i+2], V1 = d[2i+1] + d[2i+2], V2 = d[2i+2] - d[2i+1], V3 = d[2i+1] - d[2i+3]
+// into the planes of WinoConvArgs::v (y: B * (C1 + C2) * 4 * ceil(T / 2) floats)
+hipError_t launch_gn_wino(const float* x1, const float* x2, int C1, int C2, int T, int groups, float eps, const float* gamma, const float* beta,
+                          const float* scale_shift, int ss_stride, int ss_off, int silu, const float2* gp1, const float2* gp2, float* y, int B,
+                          hipStream_t s, const int* lens = nullptr, int lvl = 0);
+
+// ---------------------------------------------------------------------------------------------
 // conv_bf3: the same operator on the bf16 matrix pipe with fp32-equivalent split operands (conv_bf3.hip, k8b3.h).  Same argument
 // struct; activations (x1, x2, res, out) are K8B3 tensors, weights packed [KT][Ci/8][3][Mp][8] bf16 (pack_conv_bf3, model.hip).
 // nprod: bf16 products per fp32 product (6 = product path; 3 / 9 exist for tools/split_bf16_probe.py's error study only).
@@ -236,7 +262,10 @@ hipError_t launch_gn_stream(const float* x1, const float* x2, int C1, int C2, in
                             const float* gamma, const float* beta, const float* scale_shift, int ss_stride, int ss_off,
                             int silu, const float2* gp1, const float2* gp2, float* y, int B, hipStream_t s, const int* lens = nullptr, int lvl = 0);
 // the same partials computed from a K4P tensor by a stand-alone pass (tensors not produced by conv_dma; test entry points)
-hipError_t launch_gn_partials(const float* x, int C, int T, float2* gp, int B, hipStream_t s);
+// (lens: the ragged batch's per-utterance lengths, k4p.h ragged_len at level lvl -- the statistics stop there, and blocks wholly beyond get no partial)
+hipError_t launch_gn_partials(const float* x, int C, int T, float2* gp, int B, hipStream_t s, const int* lens = nullptr, int lvl = 0);
+// test support: NaN / Inf into the pad frames and the frames at and beyond each utterance's length (level 0) of a K4P tensor
+hipError_t launch_k4p_poison(float* x, int B, int C, int T, const int* lens, hipStream_t s);
 // nearest-neighbour resample along frames (K4P -> K4P), reference F.interpolate(size=Tout)
 // plain [B][C][T] -> K4P with `pad` zero frames per side: raw copy and (slope != 0) LeakyReLU copy (either output may be null)
 hipError_t launch_to_k4p_act(const float* in, float* raw, float* act, float slope, int B, int C, int T, int pad, hipStream_t s, const int* vlen = nullptr);

@@ -228,6 +228,7 @@ struct ConvW {
     void* w3 = nullptr;      // the same weights as three bf16 planes [KT][Ci/8][3][Mp][8] (split-bf16 path, conv_bf3.hip)
     void* wh = nullptr;      // ... as two fp16 planes [KT][Ci/8][2][Mp][8] of (w * 2^k); wh_inv = 2^-k undoes the scale in the epilogue
     float wh_inv = 1.0f;
+    float* wu = nullptr;     // a k 3 convolution's Winograd F(2,3) taps U0..U3, packed [4][Ci][Mp] like w (pack_wino; conv_wino.hip)
 };
 
 static int round_mp(int Co) { return Co <= 32 ? 32 : (Co + 63) / 64 * 64; }
@@ -297,6 +298,32 @@ static bool pack_conv(Owner& o, const float* w, const float* b, int Co, int Ci, 
     out.bias = b ? o.upload(pb) : nullptr;
     out.Co = Co; out.Ci = Ci; out.K = K; out.Mp = Mp;
     return out.w && (!b || out.bias);
+}
+
+// Winograd F(2,3) taps of a k 3 convolution (conv_wino.hip), reference layout g[Co][Ci][3] -> U[4][Co][Ci]:
+// U0 = g0, U1 = (g0 + g1 + g2) / 2, U2 = (g0 - g1 + g2) / 2, U3 = g2, computed in double and rounded once to fp32
+static void wino_taps(const float* g, int Co, int Ci, std::vector<float>& U) {
+    const size_t n = (size_t)Co * Ci;
+    U.assign(4 * n, 0.f);
+    for (size_t i = 0; i < n; ++i) {
+        const double g0 = g[3 * i], g1 = g[3 * i + 1], g2 = g[3 * i + 2];
+        U[i] = (float)g0;
+        U[n + i] = (float)((g0 + g1 + g2) * 0.5);
+        U[2 * n + i] = (float)((g0 - g1 + g2) * 0.5);
+        U[3 * n + i] = (float)g2;
+    }
+}
+// ... packed next to the direct weights of `out` (which stay: latency mode, the split modes and the shapes that are not routed use them)
+static bool pack_wino(Owner& o, const float* w, int Co, int Ci, ConvW& out) {
+    std::vector<float> U;
+    wino_taps(w, Co, Ci, U);
+    const int Mp = out.Mp;
+    std::vector<float> p((size_t)4 * Ci * Mp, 0.f);
+    for (int j = 0; j < 4; ++j)
+        for (int co = 0; co < Co; ++co)
+            for (int ci = 0; ci < Ci; ++ci) p[widx(j, ci, co, Ci, Mp)] = U[((size_t)j * Co + co) * Ci + ci];
+    out.wu = o.upload(p);
+    return out.wu != nullptr;
 }
 
 // GEGLU projection (reference attention.py:280-301): rows [0,4C) are the value half, [4C,8C) the gate.
@@ -725,6 +752,54 @@ static int run_dconv_pair_bf3(const ConvW& W3, const void* h, const ConvW& W1, c
     return LDS_OK;
 }
 
+// Which resnet k 3 convolutions run in the Winograd form (conv_wino.hip) in exact-fp32 mode.  The choice depends on the shape (Ci, Co, T at
+// this level) alone -- never on the actual batch, so an utterance's result stays bit-identical for any batch split.  The table names the
+// (Ci, Co) of the UNet's resnets with the shortest T at which tools/bench_wino.py measured the Winograd pair (gn_wino + conv_wino) faster
+// than the direct pair (gn_stream + conv_dma) at the nominal batch of 16 by more than the larger of the two spreads; every longer T that
+// was measured won by more (profiles/r26_wino_shapes.json).  Shapes that were not measured keep the direct path.
+static int wino_min_T(int Ci, int Co) {
+    static const int kTable[][3] = {
+        {256, 256, 64},  {512, 256, 64},  {640, 256, 130}, {256, 384, 256}, {384, 384, 256}, {640, 384, 256},
+        {768, 384, 256}, {896, 384, 256}, {384, 512, 128}, {512, 512, 64},  {896, 512, 128}, {1024, 512, 64},
+    };
+    for (const auto& s : kTable)
+        if (s[0] == Ci && s[1] == Co) return s[2];
+    return 0;
+}
+static bool wino_routed(int Ci, int Co, int T) {
+    const int Tmin = wino_min_T(Ci, Co);
+    return Tmin > 0 && T >= Tmin;
+}
+static bool wino_routed_any_T(int Ci, int Co) { return wino_min_T(Ci, Co) > 0; }      // (load time: T is not known yet)
+// A resnet's k 3 convolution over the planes `v` that launch_gn_wino wrote (W.wu: its packed taps).  The profiler's record carries the
+// algorithmic FLOP of the convolution it replaces, 2 B T Co Ci 3 -- the figure every other family reports -- not the two thirds it executes.
+static int run_wconv(const ConvW& W, const float* v, int T, const float* res, float2* gnpart_out, float* out, int B, hipStream_t st, int lvl, int cfg = 0) {
+    if (!W.wu || W.K != 3) return fail(LDS_EINVAL, "wconv: the Winograd taps were not packed for this layer");
+    WinoConvArgs a{};
+    a.v = v; a.u = W.wu; a.bias = W.bias; a.res = res; a.out = out; a.gnpart_out = gnpart_out;
+    a.lens = tl_lens; a.lvl = lvl;
+    a.B = B; a.Ci = W.Ci; a.Mp = W.Mp; a.Co = W.Co; a.T = T;
+    const double flops = 2.0 * B * (double)T * (double)W.Co * (double)W.Ci * 3.0;
+    const double bytes = 4.0 * ((double)B * W.Ci * 4.0 * ((T + 1) / 2) + 4.0 * W.Ci * W.Co + (double)B * W.Co * T * (res ? 2.0 : 1.0));
+    hipError_t e;
+    {
+        ProfScope ps(st, "conv_wino", flops, bytes, true);
+        e = launch_conv_wino(a, cfg, st);
+        if (ps.on) {
+            std::string cfgs(conv_wino_last_config());
+            std::string nm = "conv_wino<" + cfgs.substr(0, cfgs.find(" grid")) + ">";
+            if (g_prof_level.load(std::memory_order_relaxed) >= 2) {
+                char sh[96];
+                snprintf(sh, sizeof(sh), " Ci%d Co%d K3 To%d%s", W.Ci, W.Co, T, res ? " +res" : "");
+                nm += sh;
+            }
+            ps.rename(nm);
+        }
+    }
+    if (e != hipSuccess) return fail(LDS_EHIP, "conv_wino launch failed (%s): Co %d Ci %d T %d cfg %d", hipGetErrorString(e), W.Co, W.Ci, T, cfg);
+    return LDS_OK;
+}
+
 // The UNet's plan is the same in both GEMM modes; these pick the kernel family.  In LDS_GEMM_SPLIT_BF16 mode every activation buffer
 // holds a K8B3 tensor (k8b3.h) instead of a K4P one -- except q / k / v, which stay fp32 for the attention kernel.
 // mode = lds_unet::gemm_mode: 0 exact fp32 (K4P tensors); 1 / 2 split planes, format mode - 1 (k8b3.h)
@@ -812,6 +887,9 @@ static bool load_resnet(lds_unet* u, Tensors& T, const std::string& p, int cin, 
     if (!pack_conv(o, w1, c1b, cout, cin, 3, r.conv1)) return false;
     if (!pack_conv(o, w2, c2b, cout, cout, 3, r.conv2)) return false;
     r.has_sc = cin != cout;
+    // the Winograd taps of conv1 and of a conv2 without shortcut, where some level routes the shape to conv_wino (the direct pack stays)
+    if (wino_routed_any_T(cin, cout) && !pack_wino(o, w1, cout, cin, r.conv1)) return false;
+    if (!r.has_sc && wino_routed_any_T(cout, cout) && !pack_wino(o, w2, cout, cout, r.conv2)) return false;
     if (r.has_sc) {
         const float* ws = T.get(p + "conv_shortcut.weight", (int64_t)cout * cin);
         const float* bs = T.get(p + "conv_shortcut.bias", cout);
@@ -1167,6 +1245,22 @@ static void plan_ws(const lds_unet* u, Arena& A, int B, int T, UnetWs& w) {
             prev = co;
         }
     }
+    // a resnet convolution routed to conv_wino reads the four Winograd planes from `gno`, 4 C ceil(T / 2) floats per utterance (twice the
+    // direct K4P tensor).  Only the exact-fp32 default mode routes, but the slot is sized alike in every mode: a handle's workspace then
+    // never shrinks when it is switched to a split mode or to latency mode.
+    {
+        auto planes = [&](const ResnetW& r, int Tl) {
+            const size_t P = (size_t)(Tl + 1) / 2;
+            if (r.conv1.wu && wino_routed(r.cin, r.cout, Tl)) maxgn = std::max(maxgn, 4 * (size_t)r.cin * P);
+            if (r.conv2.wu && wino_routed(r.cout, r.cout, Tl)) maxgn = std::max(maxgn, 4 * (size_t)r.cout * P);
+        };
+        for (int i = 0; i < nb; ++i) {
+            for (const ResnetW& r : u->down[i].res) planes(r, Ts[i]);
+            for (const ResnetW& r : u->up[i].res) planes(r, Ts[nb - 1 - i]);
+        }
+        planes(u->mid_r0, Ts[nb - 1]);
+        planes(u->mid_r1, Ts[nb - 1]);
+    }
     auto scratch = [&](const char* nm) {                       // a maximum-sized activation buffer + its partials
         float* p = A.f(B * maxct, nm);
         w.gpart[p] = (float2*)A.f(B * maxgp, (std::string(nm) + ".gnpart").c_str());
@@ -1229,13 +1323,25 @@ static int run_resnet(const lds_unet* u, const ResnetW& r, const UnetWs& w, cons
     // GroupNorm(+scale/shift)+SiLU is materialised once per tensor by a streaming pass (gn_stream) so the convolutions stay
     // VALU-free; its statistics come from the partials the producers of x1 / x2 / h1 wrote in their epilogues.
     const int bf3 = u->gemm_mode;      // 0 = fp32; else split planes, format bf3 - 1
-    HIP_TRY(gn_any(bf3, x1, x2, C1, C2, T, u->G, 1e-5f, r.g1, r.b1, nullptr, 0, 0, 1, w.gp(x1), x2 ? w.gp(x2) : nullptr, w.gno, B, st, lvl));
-    DOpt o1;
-    o1.lvl_in = o1.lvl_out = lvl;
-    o1.pad = 1; o1.gnpart_out = w.gp(w.h1);
-    TRACE_ACT("gn1", w.gno, C1 + C2, T);
-    LDS_TRY(dconv_any(bf3, r.conv1, w.gno, C1 + C2, nullptr, 0, T, o1, w.h1, B, st));
+    // exact-fp32 mode, shapes of wino_routed's table: the GroupNorm pass writes the Winograd planes instead of the K4P tensor and conv_wino
+    // reads them (the debug trace records K4P tensors: a traced run keeps the direct path)
+    const bool wino_ok = !bf3 && !u->latency_mode && !g_trace_on.load(std::memory_order_relaxed);
+    if (wino_ok && r.conv1.wu && wino_routed(C1 + C2, r.cout, T)) {
+        HIP_TRY(launch_gn_wino(x1, x2, C1, C2, T, u->G, 1e-5f, r.g1, r.b1, nullptr, 0, 0, 1, w.gp(x1), x2 ? w.gp(x2) : nullptr, w.gno, B, st, tl_lens, lvl));
+        LDS_TRY(run_wconv(r.conv1, w.gno, T, nullptr, w.gp(w.h1), w.h1, B, st, lvl));
+    } else {
+        HIP_TRY(gn_any(bf3, x1, x2, C1, C2, T, u->G, 1e-5f, r.g1, r.b1, nullptr, 0, 0, 1, w.gp(x1), x2 ? w.gp(x2) : nullptr, w.gno, B, st, lvl));
+        DOpt o1;
+        o1.lvl_in = o1.lvl_out = lvl;
+        o1.pad = 1; o1.gnpart_out = w.gp(w.h1);
+        TRACE_ACT("gn1", w.gno, C1 + C2, T);
+        LDS_TRY(dconv_any(bf3, r.conv1, w.gno, C1 + C2, nullptr, 0, T, o1, w.h1, B, st));
+    }
     TRACE_ACT("conv1", w.h1, r.cout, T);
+    if (wino_ok && !r.has_sc && C2 == 0 && r.conv2.wu && wino_routed(r.cout, r.cout, T)) {
+        HIP_TRY(launch_gn_wino(w.h1, nullptr, r.cout, 0, T, u->G, 1e-5f, r.g2, r.b2, w.tproj, w.ss_stride, r.temb_off, 1, w.gp(w.h1), nullptr, w.gno, B, st, tl_lens, lvl));
+        return run_wconv(r.conv2, w.gno, T, x1, w.gp(out), out, B, st, lvl);
+    }
     HIP_TRY(gn_any(bf3, w.h1, nullptr, r.cout, 0, T, u->G, 1e-5f, r.g2, r.b2, w.tproj, w.ss_stride, r.temb_off, 1, w.gp(w.h1), nullptr, w.gno, B, st, lvl));
     TRACE_ACT("gn2", w.gno, r.cout, T);
     const float* res = x1;
@@ -4502,6 +4608,136 @@ extern "C" int lds_test_dconv_ex(const lds_dconv_ex_test* a, float* out, float* 
         HIP_TRY(act.from(ko, out, Ck, To));      // out = [B][Ck][To], then (v_split) the raw VT buffer [B][(Cout - Ck) / D][ceil4(To) / 4][D][4]
         if (vout) HIP_TRY(hipMemcpyAsync(out + (size_t)B * Ck * To, vout, sizeof(float) * (size_t)B * (Cout - Ck) * To4, hipMemcpyDeviceToDevice, st));
     }
+    HIP_TRY(hipStreamSynchronize(st));
+    return rc;
+}
+
+// ---- conv_wino (include/lds_test.h) ----
+extern "C" int lds_test_wino_pack(const float* g, int Co, int Ci, float* U) {
+    if (!g || !U || Co < 1 || Ci < 1) return fail(LDS_EINVAL, "bad argument");
+    std::vector<float> u;
+    wino_taps(g, Co, Ci, u);
+    memcpy(U, u.data(), u.size() * sizeof(float));
+    return LDS_OK;
+}
+struct lds_wino_test {      // (the entries' arguments, gathered)
+    const float *x1, *x2; int C1, C2, T;
+    const float *gamma, *beta, *scale_shift; int groups, silu;
+    const float *w, *bias; int Co;
+    const float* res; const int32_t* lengths; int poison, cfg;
+};
+// the device state both entries share: packed weights, K4P sources with their partials, residual, the planes / K4P scratch, the output
+struct WinoTestState {
+    Owner own; TmpDev tmp; ConvW W;
+    float *gamma = nullptr, *beta = nullptr, *k1 = nullptr, *k2 = nullptr, *kres = nullptr, *planes = nullptr, *ko = nullptr;
+    float2 *gp1 = nullptr, *gp2 = nullptr;
+    int* lens = nullptr;
+    int Ci = 0, P = 0;
+    size_t plane_floats = 0, out_floats = 0;
+};
+static int wino_test_setup(const lds_wino_test* a, int B, hipStream_t st, WinoTestState& s) {
+    if (!a || !a->x1 || !a->w || !a->gamma || !a->beta || B < 1 || a->T < 1 || (a->C2 > 0) != (a->x2 != nullptr) || a->C1 < 16 || (a->C1 & 15) || a->C2 < 0 || (a->C2 & 15) ||
+        a->Co < 16 || (a->Co & 15) || a->groups < 1 || (a->C1 + a->C2) % a->groups || ((a->C1 + a->C2) / a->groups) % 16 || a->cfg < 0)
+        return fail(LDS_EINVAL, "bad argument");
+    const int Ci = a->C1 + a->C2, T = a->T, nT = (T + 31) / 32;
+    s.Ci = Ci; s.P = (T + 1) / 2;
+    for (int b = 0; b < B && a->lengths; ++b)
+        if (a->lengths[b] < 1 || a->lengths[b] > T) return fail(LDS_EINVAL, "lengths[%d] = %d outside 1 .. %d", b, a->lengths[b], T);
+    if (!pack_conv(s.own, a->w, a->bias, a->Co, Ci, 3, s.W) || !pack_wino(s.own, a->w, a->Co, Ci, s.W)) return fail(LDS_ENOMEM, "upload failed");
+    s.gamma = up_vec(s.own, a->gamma, Ci); s.beta = up_vec(s.own, a->beta, Ci);
+    LDS_TRY(test_upload_lens(s.tmp, a->lengths, B, s.lens, st));
+    s.plane_floats = (size_t)B * Ci * 4 * s.P; s.out_floats = (size_t)B * a->Co * (T + 2);
+    s.k1 = s.tmp.f((size_t)B * a->C1 * (T + 2));
+    s.k2 = a->C2 ? s.tmp.f((size_t)B * a->C2 * (T + 2)) : nullptr;
+    s.gp1 = (float2*)s.tmp.f((size_t)B * (a->C1 / 16) * nT * 2);
+    s.gp2 = a->C2 ? (float2*)s.tmp.f((size_t)B * (a->C2 / 16) * nT * 2) : nullptr;
+    s.kres = a->res ? s.tmp.f(s.out_floats) : nullptr;
+    s.planes = s.tmp.f(std::max(s.plane_floats, (size_t)B * Ci * (T + 2)));      // (the direct path's K4P tensor in lds_bench_wino)
+    s.ko = s.tmp.f(s.out_floats);
+    if (!s.gamma || !s.beta || !s.k1 || (a->C2 && (!s.k2 || !s.gp2)) || !s.gp1 || (a->res && !s.kres) || !s.planes || !s.ko) return fail(LDS_ENOMEM, "alloc");
+    HIP_TRY(hipMemsetAsync(s.gp1, 0xff, sizeof(float2) * (size_t)B * (a->C1 / 16) * nT, st));      // (NaN: a partial beyond a length is never read)
+    if (a->C2) HIP_TRY(hipMemsetAsync(s.gp2, 0xff, sizeof(float2) * (size_t)B * (a->C2 / 16) * nT, st));
+    HIP_TRY(launch_to_k4p(a->x1, s.k1, B, a->C1, T, a->C1, 0, st, s.lens));
+    if (a->C2) HIP_TRY(launch_to_k4p(a->x2, s.k2, B, a->C2, T, a->C2, 0, st, s.lens));
+    if (a->res) HIP_TRY(launch_to_k4p(a->res, s.kres, B, a->Co, T, a->Co, 0, st, s.lens));
+    if (a->poison) {      // NaN / Inf in the sources' pad frames and beyond the lengths: nothing of it may reach a plane
+        HIP_TRY(launch_k4p_poison(s.k1, B, a->C1, T, s.lens, st));
+        if (a->C2) HIP_TRY(launch_k4p_poison(s.k2, B, a->C2, T, s.lens, st));
+    }
+    HIP_TRY(launch_gn_partials(s.k1, a->C1, T, s.gp1, B, st, s.lens, 0));
+    if (a->C2) HIP_TRY(launch_gn_partials(s.k2, a->C2, T, s.gp2, B, st, s.lens, 0));
+    return LDS_OK;
+}
+static int wino_test_run(const lds_wino_test* a, WinoTestState& s, float2* gnpart, int B, hipStream_t st) {
+    HIP_TRY(launch_gn_wino(s.k1, s.k2, a->C1, a->C2, a->T, a->groups, 1e-5f, s.gamma, s.beta, a->scale_shift, 2 * s.Ci, 0, a->silu, s.gp1, s.gp2, s.planes, B, st, s.lens, 0));
+    return run_wconv(s.W, s.planes, a->T, s.kres, gnpart, s.ko, B, st, 0, a->cfg);
+}
+extern "C" int lds_test_wino_conv(const float* x1, const float* x2, int C1, int C2, int T, const float* gamma, const float* beta, const float* scale_shift,
+                                  int groups, int silu, const float* w, const float* bias, int Co, const float* res, const int32_t* lengths, int poison, int cfg,
+                                  float* out, float* vplanes, float* gnpart, int B, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    if (!out) return fail(LDS_EINVAL, "bad argument");
+    const lds_wino_test args{x1, x2, C1, C2, T, gamma, beta, scale_shift, groups, silu, w, bias, Co, res, lengths, poison, cfg};
+    const lds_wino_test* a = &args;
+    WinoTestState s;
+    LDS_TRY(wino_test_setup(a, B, st, s));
+    // NaN fill: every plane entry, every output frame (pads included) and every partial of a block inside a length must be written
+    HIP_TRY(hipMemsetAsync(s.planes, 0xff, sizeof(float) * s.plane_floats, st));
+    HIP_TRY(hipMemsetAsync(s.ko, 0xff, sizeof(float) * s.out_floats, st));
+    if (gnpart) HIP_TRY(hipMemsetAsync(gnpart, 0xff, sizeof(float) * (size_t)B * (a->Co / 16) * ((a->T + 31) / 32) * 2, st));
+    int rc;
+    {
+        LensScope ls(s.lens);
+        rc = wino_test_run(a, s, (float2*)gnpart, B, st);
+    }
+    if (rc == LDS_OK) {
+        HIP_TRY(tap_take(s.ko, s.out_floats, st));
+        HIP_TRY(launch_from_k4p(s.ko, out, B, a->Co, a->T, st));
+        if (vplanes) HIP_TRY(hipMemcpyAsync(vplanes, s.planes, sizeof(float) * s.plane_floats, hipMemcpyDeviceToDevice, st));
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    return rc;
+}
+// direct (gn_stream + conv_dma) against Winograd (gn_wino + conv_wino) on one shape, alternating: `reps` times a block of `iters` direct
+// passes, then a block of `iters` Winograd passes, each block between two events on the stream; ms_direct / ms_wino [reps] = a block's time per pass
+extern "C" int lds_bench_wino(const float* x1, const float* x2, int C1, int C2, int T, const float* gamma, const float* beta, const float* scale_shift,
+                              int groups, int silu, const float* w, const float* bias, int Co, const float* res, int cfg, int B, int iters, int reps,
+                              float* ms_direct, float* ms_wino, char* cfg_out, size_t cfg_cap, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    if (!ms_direct || !ms_wino || iters < 1 || reps < 1) return fail(LDS_EINVAL, "bad argument");
+    const lds_wino_test args{x1, x2, C1, C2, T, gamma, beta, scale_shift, groups, silu, w, bias, Co, res, nullptr, 0, cfg};
+    const lds_wino_test* a = &args;
+    WinoTestState s;
+    LDS_TRY(wino_test_setup(a, B, st, s));
+    float2* gnpart = (float2*)s.tmp.f((size_t)B * (a->Co / 16) * ((a->T + 31) / 32) * 2);
+    if (!gnpart) return fail(LDS_ENOMEM, "alloc");
+    DOpt o;
+    o.pad = 1; o.res = s.kres; o.gnpart_out = gnpart;
+    auto direct = [&]() -> int {
+        HIP_TRY(launch_gn_stream(s.k1, s.k2, a->C1, a->C2, a->T, a->groups, 1e-5f, s.gamma, s.beta, a->scale_shift, 2 * s.Ci, 0, a->silu, s.gp1, s.gp2, s.planes, B, st));
+        return run_dconv(s.W, s.planes, s.Ci, nullptr, 0, a->T, o, s.ko, B, st);
+    };
+    LDS_TRY(direct());
+    std::string cfgs = std::string("direct ") + conv_dma_last_config();
+    LDS_TRY(wino_test_run(a, s, gnpart, B, st));
+    cfgs += std::string(" | wino ") + conv_wino_last_config();
+    if (cfg_out && cfg_cap) snprintf(cfg_out, cfg_cap, "%s", cfgs.c_str());
+    hipEvent_t ev[3];
+    for (auto& e : ev) HIP_TRY(hipEventCreate(&e));
+    int rc = LDS_OK;
+    for (int r = 0; r < reps && rc == LDS_OK; ++r) {
+        HIP_TRY(hipEventRecord(ev[0], st));
+        for (int i = 0; i < iters && rc == LDS_OK; ++i) rc = direct();
+        HIP_TRY(hipEventRecord(ev[1], st));
+        for (int i = 0; i < iters && rc == LDS_OK; ++i) rc = wino_test_run(a, s, gnpart, B, st);
+        HIP_TRY(hipEventRecord(ev[2], st));
+        HIP_TRY(hipEventSynchronize(ev[2]));
+        float d = 0.f, w = 0.f;
+        HIP_TRY(hipEventElapsedTime(&d, ev[0], ev[1]));
+        HIP_TRY(hipEventElapsedTime(&w, ev[1], ev[2]));
+        ms_direct[r] = d / iters; ms_wino[r] = w / iters;
+    }
+    for (auto& e : ev) (void)hipEventDestroy(e);
     HIP_TRY(hipStreamSynchronize(st));
     return rc;
 }

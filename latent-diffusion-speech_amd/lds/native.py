@@ -260,6 +260,9 @@ lds_test_ivf_search              i:pqppqiippippppqiipppzp
 lds_test_ivf_search_metric       i:pqppqiippippppqiiipppzp
 lds_test_ctc_forward             i:piipppipp
 lds_test_ctc_viterbi             i:piipppipppppzp
+lds_test_wino_pack               i:piip
+lds_test_wino_conv               i:ppiiipppiippippiipppip
+lds_bench_wino                   i:ppiiipppiippipiiiipppzp
 """
 SIGNATURES = dict(ln.split() for ln in (_PUBLIC + _TEST).splitlines() if ln)
 EXPORTS = [ln.split()[0] for ln in _PUBLIC.splitlines() if ln]
