@@ -309,6 +309,16 @@ int lds_test_wino_conv(const float* x1, const float* x2, int C1, int C2, int T, 
 int lds_bench_wino(const float* x1, const float* x2, int C1, int C2, int T, const float* gamma, const float* beta, const float* scale_shift,
                    int groups, int silu, const float* w, const float* bias, int Co, const float* res, int cfg, int B, int iters, int reps,
                    float* ms_direct, float* ms_wino, char* cfg_out, size_t cfg_cap, void* stream);
+/* lds_test_wino_conv at level lvl of a ragged batch, as the UNet's resnets run below the first level: lengths are the LEVEL-0 lengths, T is the
+ * tensors' length at level lvl, and every length reduced lvl times by (n - 1) / 2 + 1 lies in 1 .. T.  The sources, the residual, the poison
+ * and the sources' partials are staged with the reduced lengths; both kernels receive the level-0 lengths and lvl and reduce them themselves.
+ * lvl 0 is lds_test_wino_conv. */
+int lds_test_wino_conv_lvl(const float* x1, const float* x2, int C1, int C2, int T, const float* gamma, const float* beta, const float* scale_shift,
+                           int groups, int silu, const float* w, const float* bias, int Co, const float* res, const int32_t* lengths, int poison, int cfg,
+                           int lvl, float* out, float* vplanes, float* gnpart, int B, void* stream);
+/* the routing table of the UNet's resnets (csrc/model.hip wino_min_T): the shortest T at which a k 3 convolution Ci -> Co runs on conv_wino in
+ * exact-fp32 mode, 0 = never.  Host only; returns the value, not a status. */
+int lds_test_wino_min_T(int Ci, int Co);
 
 /* ---- debugging aids (tests/test_gpu_poison.py, tools/diag_trace.py) ----------------------------------------------------------
  * lds_debug_fill_u32: every 32-bit word of a device buffer = pattern.  Tests fill a caller workspace with NaN patterns (0x7fc07fc0 is a NaN

@@ -4625,27 +4625,34 @@ struct lds_wino_test {      // (the entries' arguments, gathered)
     const float *gamma, *beta, *scale_shift; int groups, silu;
     const float *w, *bias; int Co;
     const float* res; const int32_t* lengths; int poison, cfg;
+    int lvl;      // `lengths` are level-0 lengths and T is the tensor's length at this level (run_resnet's lvl)
 };
 // the device state both entries share: packed weights, K4P sources with their partials, residual, the planes / K4P scratch, the output
 struct WinoTestState {
     Owner own; TmpDev tmp; ConvW W;
     float *gamma = nullptr, *beta = nullptr, *k1 = nullptr, *k2 = nullptr, *kres = nullptr, *planes = nullptr, *ko = nullptr;
     float2 *gp1 = nullptr, *gp2 = nullptr;
-    int* lens = nullptr;
+    int *lens = nullptr, *lens_lvl = nullptr;      // the level-0 lengths the kernels receive; the same reduced to the level, for the staging
     int Ci = 0, P = 0;
     size_t plane_floats = 0, out_floats = 0;
 };
 static int wino_test_setup(const lds_wino_test* a, int B, hipStream_t st, WinoTestState& s) {
     if (!a || !a->x1 || !a->w || !a->gamma || !a->beta || B < 1 || a->T < 1 || (a->C2 > 0) != (a->x2 != nullptr) || a->C1 < 16 || (a->C1 & 15) || a->C2 < 0 || (a->C2 & 15) ||
-        a->Co < 16 || (a->Co & 15) || a->groups < 1 || (a->C1 + a->C2) % a->groups || ((a->C1 + a->C2) / a->groups) % 16 || a->cfg < 0)
+        a->Co < 16 || (a->Co & 15) || a->groups < 1 || (a->C1 + a->C2) % a->groups || ((a->C1 + a->C2) / a->groups) % 16 || a->cfg < 0 || a->lvl < 0 || a->lvl > 30)
         return fail(LDS_EINVAL, "bad argument");
     const int Ci = a->C1 + a->C2, T = a->T, nT = (T + 31) / 32;
     s.Ci = Ci; s.P = (T + 1) / 2;
-    for (int b = 0; b < B && a->lengths; ++b)
-        if (a->lengths[b] < 1 || a->lengths[b] > T) return fail(LDS_EINVAL, "lengths[%d] = %d outside 1 .. %d", b, a->lengths[b], T);
+    int32_t reduced[64];      // the lengths at level lvl, as the kernels reduce them: (n - 1) / 2 + 1 per level
+    for (int b = 0; b < B && b < 64 && a->lengths; ++b) {
+        int n = a->lengths[b];
+        for (int i = 0; i < a->lvl && n >= 1; ++i) n = (n - 1) / 2 + 1;
+        if (n < 1 || n > T) return fail(LDS_EINVAL, "lengths[%d] = %d (%d at level %d) outside 1 .. %d", b, a->lengths[b], n, a->lvl, T);
+        reduced[b] = n;
+    }
     if (!pack_conv(s.own, a->w, a->bias, a->Co, Ci, 3, s.W) || !pack_wino(s.own, a->w, a->Co, Ci, s.W)) return fail(LDS_ENOMEM, "upload failed");
     s.gamma = up_vec(s.own, a->gamma, Ci); s.beta = up_vec(s.own, a->beta, Ci);
     LDS_TRY(test_upload_lens(s.tmp, a->lengths, B, s.lens, st));
+    LDS_TRY(test_upload_lens(s.tmp, a->lengths ? reduced : nullptr, B, s.lens_lvl, st));
     s.plane_floats = (size_t)B * Ci * 4 * s.P; s.out_floats = (size_t)B * a->Co * (T + 2);
     s.k1 = s.tmp.f((size_t)B * a->C1 * (T + 2));
     s.k2 = a->C2 ? s.tmp.f((size_t)B * a->C2 * (T + 2)) : nullptr;
@@ -4657,28 +4664,23 @@ static int wino_test_setup(const lds_wino_test* a, int B, hipStream_t st, WinoTe
     if (!s.gamma || !s.beta || !s.k1 || (a->C2 && (!s.k2 || !s.gp2)) || !s.gp1 || (a->res && !s.kres) || !s.planes || !s.ko) return fail(LDS_ENOMEM, "alloc");
     HIP_TRY(hipMemsetAsync(s.gp1, 0xff, sizeof(float2) * (size_t)B * (a->C1 / 16) * nT, st));      // (NaN: a partial beyond a length is never read)
     if (a->C2) HIP_TRY(hipMemsetAsync(s.gp2, 0xff, sizeof(float2) * (size_t)B * (a->C2 / 16) * nT, st));
-    HIP_TRY(launch_to_k4p(a->x1, s.k1, B, a->C1, T, a->C1, 0, st, s.lens));
-    if (a->C2) HIP_TRY(launch_to_k4p(a->x2, s.k2, B, a->C2, T, a->C2, 0, st, s.lens));
-    if (a->res) HIP_TRY(launch_to_k4p(a->res, s.kres, B, a->Co, T, a->Co, 0, st, s.lens));
+    HIP_TRY(launch_to_k4p(a->x1, s.k1, B, a->C1, T, a->C1, 0, st, s.lens_lvl));
+    if (a->C2) HIP_TRY(launch_to_k4p(a->x2, s.k2, B, a->C2, T, a->C2, 0, st, s.lens_lvl));
+    if (a->res) HIP_TRY(launch_to_k4p(a->res, s.kres, B, a->Co, T, a->Co, 0, st, s.lens_lvl));
     if (a->poison) {      // NaN / Inf in the sources' pad frames and beyond the lengths: nothing of it may reach a plane
-        HIP_TRY(launch_k4p_poison(s.k1, B, a->C1, T, s.lens, st));
-        if (a->C2) HIP_TRY(launch_k4p_poison(s.k2, B, a->C2, T, s.lens, st));
+        HIP_TRY(launch_k4p_poison(s.k1, B, a->C1, T, s.lens_lvl, st));
+        if (a->C2) HIP_TRY(launch_k4p_poison(s.k2, B, a->C2, T, s.lens_lvl, st));
     }
-    HIP_TRY(launch_gn_partials(s.k1, a->C1, T, s.gp1, B, st, s.lens, 0));
-    if (a->C2) HIP_TRY(launch_gn_partials(s.k2, a->C2, T, s.gp2, B, st, s.lens, 0));
+    HIP_TRY(launch_gn_partials(s.k1, a->C1, T, s.gp1, B, st, s.lens_lvl, 0));
+    if (a->C2) HIP_TRY(launch_gn_partials(s.k2, a->C2, T, s.gp2, B, st, s.lens_lvl, 0));
     return LDS_OK;
 }
 static int wino_test_run(const lds_wino_test* a, WinoTestState& s, float2* gnpart, int B, hipStream_t st) {
-    HIP_TRY(launch_gn_wino(s.k1, s.k2, a->C1, a->C2, a->T, a->groups, 1e-5f, s.gamma, s.beta, a->scale_shift, 2 * s.Ci, 0, a->silu, s.gp1, s.gp2, s.planes, B, st, s.lens, 0));
-    return run_wconv(s.W, s.planes, a->T, s.kres, gnpart, s.ko, B, st, 0, a->cfg);
+    HIP_TRY(launch_gn_wino(s.k1, s.k2, a->C1, a->C2, a->T, a->groups, 1e-5f, s.gamma, s.beta, a->scale_shift, 2 * s.Ci, 0, a->silu, s.gp1, s.gp2, s.planes, B, st, s.lens, a->lvl));
+    return run_wconv(s.W, s.planes, a->T, s.kres, gnpart, s.ko, B, st, a->lvl, a->cfg);
 }
-extern "C" int lds_test_wino_conv(const float* x1, const float* x2, int C1, int C2, int T, const float* gamma, const float* beta, const float* scale_shift,
-                                  int groups, int silu, const float* w, const float* bias, int Co, const float* res, const int32_t* lengths, int poison, int cfg,
-                                  float* out, float* vplanes, float* gnpart, int B, void* stream) {
-    hipStream_t st = (hipStream_t)stream;
+static int wino_conv_test(const lds_wino_test* a, float* out, float* vplanes, float* gnpart, int B, hipStream_t st) {
     if (!out) return fail(LDS_EINVAL, "bad argument");
-    const lds_wino_test args{x1, x2, C1, C2, T, gamma, beta, scale_shift, groups, silu, w, bias, Co, res, lengths, poison, cfg};
-    const lds_wino_test* a = &args;
     WinoTestState s;
     LDS_TRY(wino_test_setup(a, B, st, s));
     // NaN fill: every plane entry, every output frame (pads included) and every partial of a block inside a length must be written
@@ -4698,6 +4700,19 @@ extern "C" int lds_test_wino_conv(const float* x1, const float* x2, int C1, int 
     HIP_TRY(hipStreamSynchronize(st));
     return rc;
 }
+extern "C" int lds_test_wino_conv(const float* x1, const float* x2, int C1, int C2, int T, const float* gamma, const float* beta, const float* scale_shift,
+                                  int groups, int silu, const float* w, const float* bias, int Co, const float* res, const int32_t* lengths, int poison, int cfg,
+                                  float* out, float* vplanes, float* gnpart, int B, void* stream) {
+    const lds_wino_test args{x1, x2, C1, C2, T, gamma, beta, scale_shift, groups, silu, w, bias, Co, res, lengths, poison, cfg, 0};
+    return wino_conv_test(&args, out, vplanes, gnpart, B, (hipStream_t)stream);
+}
+extern "C" int lds_test_wino_conv_lvl(const float* x1, const float* x2, int C1, int C2, int T, const float* gamma, const float* beta, const float* scale_shift,
+                                      int groups, int silu, const float* w, const float* bias, int Co, const float* res, const int32_t* lengths, int poison, int cfg,
+                                      int lvl, float* out, float* vplanes, float* gnpart, int B, void* stream) {
+    const lds_wino_test args{x1, x2, C1, C2, T, gamma, beta, scale_shift, groups, silu, w, bias, Co, res, lengths, poison, cfg, lvl};
+    return wino_conv_test(&args, out, vplanes, gnpart, B, (hipStream_t)stream);
+}
+extern "C" int lds_test_wino_min_T(int Ci, int Co) { return wino_min_T(Ci, Co); }
 // direct (gn_stream + conv_dma) against Winograd (gn_wino + conv_wino) on one shape, alternating: `reps` times a block of `iters` direct
 // passes, then a block of `iters` Winograd passes, each block between two events on the stream; ms_direct / ms_wino [reps] = a block's time per pass
 extern "C" int lds_bench_wino(const float* x1, const float* x2, int C1, int C2, int T, const float* gamma, const float* beta, const float* scale_shift,
@@ -4705,7 +4720,7 @@ extern "C" int lds_bench_wino(const float* x1, const float* x2, int C1, int C2, 
                               float* ms_direct, float* ms_wino, char* cfg_out, size_t cfg_cap, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     if (!ms_direct || !ms_wino || iters < 1 || reps < 1) return fail(LDS_EINVAL, "bad argument");
-    const lds_wino_test args{x1, x2, C1, C2, T, gamma, beta, scale_shift, groups, silu, w, bias, Co, res, nullptr, 0, cfg};
+    const lds_wino_test args{x1, x2, C1, C2, T, gamma, beta, scale_shift, groups, silu, w, bias, Co, res, nullptr, 0, cfg, 0};
     const lds_wino_test* a = &args;
     WinoTestState s;
     LDS_TRY(wino_test_setup(a, B, st, s));

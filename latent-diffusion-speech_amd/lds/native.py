@@ -263,6 +263,8 @@ lds_test_ctc_viterbi             i:piipppipppppzp
 lds_test_wino_pack               i:piip
 lds_test_wino_conv               i:ppiiipppiippippiipppip
 lds_bench_wino                   i:ppiiipppiippipiiiipppzp
+lds_test_wino_conv_lvl           i:ppiiipppiippippiiipppip
+lds_test_wino_min_T              i:ii
 """
 SIGNATURES = dict(ln.split() for ln in (_PUBLIC + _TEST).splitlines() if ln)
 EXPORTS = [ln.split()[0] for ln in _PUBLIC.splitlines() if ln]

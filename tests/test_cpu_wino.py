@@ -1,6 +1,7 @@
 """Winograd F(2,3) for the resnets' k 3 convolutions (csrc/conv_wino.hip), the parts that need no GPU: the restatement of
 tests/wino_numpy.py against the direct convolution in float64, its zero rules for odd lengths and ragged utterances, and the host-side
-weight transform of the library (lds_test_wino_pack) against the float64 transform rounded once."""
+weight transform of the library (lds_test_wino_pack) against the float64 transform rounded once; the level reduction of lengths and the
+ragged per-utterance reference that tests/test_gpu_wino_modes.py compares the kernels with."""
 import ctypes as ct
 
 import numpy as np
@@ -58,6 +59,46 @@ def test_ragged_zero_rule(T, length):
     assert np.isfinite(got).all()
     assert np.abs(got[:, :length] - alone).max() <= 1e-12 * max(1.0, np.abs(alone).max())
     assert not got[:, length:].any()
+
+
+def test_level_len_is_repeated_ceil_halving():
+    """the kernels' (n - 1) / 2 + 1 per level against ceil(n / 2) applied lvl times, and against ceil(n / 2^lvl) outright"""
+    import math
+    for n in list(range(1, 1100)) + [2047, 2048, 2049, 4097, 2 ** 20 + 1]:
+        want = n
+        for lvl in range(6):
+            assert W.level_len(n, lvl) == want == -(-n // 2 ** lvl), (n, lvl)
+            want = math.ceil(want / 2)
+    assert [W.level_len(n, 2) for n in (520, 37, 259)] == [130, 10, 65]
+    assert [W.level_len(n, 3) for n in (130, 37, 1, 129)] == [17, 5, 1, 17]
+
+
+@pytest.mark.parametrize("lvl,T,lengths", [(0, 70, [70, 33, 1]), (1, 65, [130, 37, 1, 129]), (2, 130, [520, 37, 259]), (3, 17, [130, 37, 1, 129])])
+def test_ragged_reference_at_a_level(lvl, T, lengths):
+    """every utterance equals its own cut tensor run alone as a dense batch of one; whatever the tensor holds beyond a reduced length
+    (NaN, Inf) changes nothing; zeros beyond; the normalised tensor has the group statistics GroupNorm promises"""
+    B, Ci, Co, groups = len(lengths), 32, 16, 2
+    tag = f"lv{lvl}.{T}"
+    x, res = U(tag + ".x", (B, Ci, T), -2, 2) + np.float32(0.3), U(tag + ".res", (B, Co, T))
+    gamma, beta, ss = U(tag + ".g", (Ci,), 0.5, 1.5), U(tag + ".b", (Ci,), -0.5, 0.5), U(tag + ".ss", (B, 2 * Ci), -0.5, 0.5)
+    g, bias = U(tag + ".w", (Co, Ci, 3)) / np.float32(np.sqrt(3 * Ci)), U(tag + ".bias", (Co,))
+    d, Y, L = W.ragged_reference(x, lengths, lvl, gamma, beta, groups, g, bias, ss, res)
+    assert L == [-(-n // 2 ** lvl) for n in lengths] and d.dtype == Y.dtype == np.float64
+    bad = x.copy()
+    for b, n in enumerate(L):
+        bad[b, :, n:] = np.nan
+        bad[b, :, n + 1:] = np.inf
+    d2, Y2, _ = W.ragged_reference(bad, lengths, lvl, gamma, beta, groups, g, bias, ss, res)
+    assert np.array_equal(d, d2) and np.array_equal(Y, Y2)
+    for b, n in enumerate(L):
+        assert not d[b, :, n:].any() and not Y[b, :, n:].any()
+        da, Ya, La = W.ragged_reference(x[b:b + 1, :, :n], None, 0, gamma, beta, groups, g, bias, ss[b:b + 1], res[b:b + 1, :, :n])
+        assert La == [n] and np.array_equal(da[0], d[b, :, :n]) and np.array_equal(Ya[0], Y[b, :, :n])
+        # the convolution of the reference is the F(2,3) form of the same tensor
+        assert np.abs(W.conv(d[b], g, n)[:, :n] + bias[:, None] + res[b, :, :n] - Y[b, :, :n]).max() < 1e-12
+        plain = W.gn_act(x[b, :, :n], np.ones(Ci), np.zeros(Ci), groups, act=False).reshape(groups, -1)
+        assert np.abs(plain.mean(1)).max() < 1e-12
+        assert np.abs(plain.var(1) - 1.0).max() < 1e-3      # (var / (var + eps), 16 channels x n frames per group)
 
 
 def test_device_plane_layout_roundtrip():
