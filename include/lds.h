@@ -358,6 +358,13 @@ int  lds_wavlm_features(lds_wavlm* h, const float* audio, const int32_t* lengths
  * n_layers_run == n_layer gives last_hidden_state */
 int  lds_wavlm_encode(lds_wavlm* h, const float* audio, const int32_t* lengths, float* out, int n_layers_run, int normalize, void* ws, size_t ws_bytes,
                       int B, int64_t L, void* stream);
+/* out dev [B][T][n_state] = sum_l layer_w[l] hidden_states[l] over all n_layer + 1 hidden states, hidden_states[0] included: the weighted layer
+ * sum of WavLMForXVector.forward under config.use_weighted_layer_sum (transformers 5.15 modeling_wavlm.py 1591-1596, "hidden_states = torch.stack(...);
+ * norm_weights = softmax(self.layer_weights); hidden_states = (hidden_states * norm_weights.view(-1, 1, 1)).sum(dim=1)").  layer_w: HOST
+ * float[n_layer + 1], finite, already soft-maxed.  One encode: each hidden state is added where it exists, out = (l == 0 ? 0 : out) + layer_w[l] h_l
+ * (one fmaf) with l ascending, so the sum's order is fixed; no hidden state is stored.  Same workspace, limits and guarantees as lds_wavlm_encode. */
+int  lds_wavlm_encode_layersum(lds_wavlm* h, const float* audio, const int32_t* lengths, const float* layer_w, float* out, int normalize, void* ws,
+                               size_t ws_bytes, int B, int64_t L, void* stream);
 
 /* ---- units encoder: w2v-BERT 2.0 (reference tools/tools.py Wav2Vec2Bert: transformers' Wav2Vec2BertModel(**SeamlessM4TFeatureExtractor(audio,
  *      sampling_rate = 16000)).last_hidden_state), audio -> units ------------------------------------------------------------------------
@@ -859,6 +866,43 @@ int lds_ctc_align_workspace_bytes(int B, int T, int V, int D, int Lmax, size_t* 
 int lds_ctc_align(const float* X, int B, int T, const int32_t* n_frames, const float* W, const float* bias, int V, int D, int blank, const int64_t* labels,
                   const int32_t* label_len, int Lmax, float* path_score, int32_t* frame_label, int32_t* segments, float* label_logprob, void* ws,
                   size_t ws_bytes, void* stream);
+
+/* ---- x-vector speaker embeddings (csrc/xvector.hip; tests/xvector_numpy.py is the float64 restatement) -------------------------------------
+ * The reference has no speaker-verification code; this replaces the head of transformers' WavLMForXVector / Wav2Vec2ForXVector (transformers
+ * 5.15 modeling_wavlm.py: TDNNLayer.forward 1491-1498; WavLMForXVector.forward 1591-1621 -- projector and the tdnn loop 1599-1602, the
+ * statistics pooling without an attention_mask 1605-1607, feature_extractor and classifier 1620-1621; _get_tdnn_output_lengths 1541-1554 is the
+ * masked path that is not reproduced) and torch.nn.functional.cosine_similarity.  The AM-softmax objective (AMSoftmaxLoss, 1446) is training: not built.
+ *   X dev [B][T][d_in]: hidden states in the encode_ragged layout (the last hidden state, or lds_wavlm_encode_layersum's output when the
+ *     checkpoint has use_weighted_layer_sum); n_frames host int32 [B], B <= 64, n_frames[b] <= T <= 32,768.  Rows t >= n_frames[b] are never
+ *     read, whatever they hold (NaN included).  Every clip is treated as if given alone with attention_mask = None.  HF's batched masked path
+ *     is NOT reproduced: its _get_tdnn_output_lengths ignores the dilations, so it pools T - 8 frames of a tensor that holds T - 14 valid ones.
+ *   projector   x = h W^T + b, Linear(d_in -> tdnn_dim[0]), no activation.
+ *   tdnn.{i}    y[t][o] = relu(b[o] + sum_{j < ks} sum_{c < Cin} x[t + j d][c] W[o][j Cin + c]), W = tdnn.{i}.kernel.weight [out][ks Cin] as
+ *               stored; valid convolution: T_out = T_in - (ks - 1) d.  (TDNNLayer.forward: conv1d of the transposed, viewed weight.)
+ *   pooling     per channel the mean and the unbiased standard deviation (torch.std, ddof 1) over the clip's T_out frames of the last layer,
+ *               concatenated [2 tdnn_dim[-1]].  The last layer's output is never stored: every 64-frame run becomes (mean, M2) in frame
+ *               order and the runs are combined in order by Chan's update.  A clip needs T_out >= 2 (16 frames with the default geometry,
+ *               5,200 samples): fewer is LDS_EINVAL naming the count, never a NaN.  A constant channel has a standard deviation of exactly 0.
+ *   tail        emb = feature_extractor(stats) [xvector_dim]; logits = classifier(emb) [n_labels = numel(classifier.bias)].
+ *   cosine      out[i][j] = a_i . b_j / (max(|a_i|, 1e-8) max(|b_j|, 1e-8)), a dev [N][dim], b dev [M][dim], out dev [N][M].
+ * Every GEMM is exact fp32 on the MFMA, one fmaf chain per output in k order; no floating-point atomics.  A clip's embedding is bit-identical
+ * alone, at any batch position, with any other clips, for any T and on repeat, whatever the workspace held.
+ * Tensor names are the head's keys in *ForXVector.state_dict(): projector.{weight,bias}, tdnn.{i}.kernel.{weight,bias},
+ * feature_extractor.{weight,bias} (top level: not the encoder's <prefix>.feature_extractor.conv_layers.*), classifier.{weight,bias}; objective.* and
+ * other names are not read.  LDS_EMISSING names a missing tensor.
+ * Limits, checked before anything is enqueued (LDS_EINVAL with a message): 1 <= n_tdnn <= 8; d_in and every layer's input width a multiple of
+ * 32 (the K-step: a K-block may not span two taps) up to 4096; every tdnn_dim and xvector_dim a multiple of 4 up to 4096; kernels and
+ * dilations in 1 .. 8; no NULL pointer except logits.  A workspace smaller than lds_xvector_workspace_bytes gives LDS_ENOMEM naming the size.
+ * Nothing synchronises. */
+typedef struct lds_xvector lds_xvector;
+typedef struct lds_xvector_cfg { int d_in, n_tdnn, tdnn_dim[8], tdnn_kernel[8], tdnn_dilation[8], xvector_dim; } lds_xvector_cfg;
+int  lds_xvector_create(const lds_xvector_cfg* cfg, int n_tensors, const char* const* names, const float* const* host_ptrs, const int64_t* numel, lds_xvector** out);
+void lds_xvector_destroy(lds_xvector* h);
+int  lds_xvector_n_labels(const lds_xvector* h);
+int  lds_xvector_workspace_bytes(const lds_xvector* h, int B, int T, size_t* out);
+/* emb dev [B][xvector_dim]; logits dev [B][n_labels] or NULL */
+int  lds_xvector_embed(lds_xvector* h, const float* X, const int32_t* n_frames, float* emb, float* logits, void* ws, size_t ws_bytes, int B, int T, void* stream);
+int  lds_xvector_cosine(const float* a, int N, const float* b, int M, int dim, float* out, void* stream);
 
 /* ---- per-launch HIP-event timing for bench.py's roofline leg (off by default) ------------------
  * lds_prof_enable(1) clears and starts recording one event pair per kernel launch on the launch

@@ -320,7 +320,18 @@ int lds_test_wino_conv_lvl(const float* x1, const float* x2, int C1, int C2, int
  * exact-fp32 mode, 0 = never.  Host only; returns the value, not a status. */
 int lds_test_wino_min_T(int Ci, int Co);
 
-/* ---- debugging aids (tests/test_gpu_poison.py, tools/diag_trace.py) ----------------------------------------------------------
+/* ---- x-vector head, one layer at a time (csrc/xvector.hip; limits as lds_xvector_*) -----------------------------------------------------------
+ * lds_test_xvector_tdnn: X dev [B][T][Cin], n_frames host [B] (0 .. T), W dev [Cout][ks Cin], bias dev [Cout] -> Y dev [B][T][Cout]: rows below
+ * T_out = n_frames[b] - (ks - 1) d hold the layer (relu 0 / 1), the rows from there to T zeros.  ks 1 without relu is the projector.
+ * lds_test_xvector_pool: the layer with ReLU and the pooling in its epilogue -> stats dev [B][2 Cout] (means, then unbiased standard deviations);
+ * every clip needs T_out >= 2.  Y (dev [B][T][Cout] or NULL): the unfused layer's output as well, bit for bit what was pooled. */
+int lds_test_xvector_tdnn(const float* X, int B, int T, const int32_t* n_frames, const float* W, const float* bias, int Cin, int Cout, int ks, int dil, int relu,
+                          float* Y, void* stream);
+int lds_test_xvector_pool_workspace_bytes(int B, int T, int Cout, size_t* out);
+int lds_test_xvector_pool(const float* X, int B, int T, const int32_t* n_frames, const float* W, const float* bias, int Cin, int Cout, int ks, int dil,
+                          float* stats, float* Y, void* ws, size_t ws_bytes, void* stream);
+
+/* ---- debugging aids (tests/test_gpu_poison.py, tools/diag_trace.py)----------------------------------------------------------
  * lds_debug_fill_u32: every 32-bit word of a device buffer = pattern.  Tests fill a caller workspace with NaN patterns (0x7fc07fc0 is a NaN
  * as fp32 and as two fp16 / bf16 halves) before a call: a kernel that reads a slot no kernel of THAT call wrote turns it into a NaN (or, behind
  * a select, into a result that differs from the zero-filled run's).

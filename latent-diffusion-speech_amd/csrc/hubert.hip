@@ -368,4 +368,41 @@ hipError_t launch_hubert_store_frames(const float* x, float* out, const int* nle
     return hipGetLastError();
 }
 
+// ---- K4P -> frame-major, accumulated: the weighted layer sum of the *ForXVector / *ForSequenceClassification heads ------------------------
+// out[b][t][c] = (first ? 0 : out[b][t][c]) + w x[b][c][t] for t < T_b (one fmaf), zeros beyond: hubert_store_frames_kernel's tile with the
+// running sum read back where the plain store overwrites.  The caller runs the hidden states in ascending order, so the order of a sum's
+// terms is fixed.
+__global__ void __launch_bounds__(256) hubert_store_frames_acc_kernel(const float* __restrict__ x, float* __restrict__ out, const int* __restrict__ nlen, int C,
+                                                                      int T, float w, int first) {
+    __shared__ float tile[32][65];
+    const int tid = threadIdx.x, t0 = blockIdx.x * 32, c0 = blockIdx.y * 64, b = blockIdx.z;
+    const int Tb = nlen ? (nlen[b] < T ? nlen[b] : T) : T;
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+        const int idx = tid + 256 * e, row = idx >> 5, tl = idx & 31;
+        const int t = t0 + tl;
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (t < Tb) v = *reinterpret_cast<const float4*>(x + (((long long)b * (C >> 2) + (c0 >> 2) + row) * (T + 2) + t + 1) * 4);
+        const int cl = 8 * (row >> 1) + (row & 1);
+        tile[tl][cl] = v.x; tile[tl][cl + 2] = v.y; tile[tl][cl + 4] = v.z; tile[tl][cl + 6] = v.w;
+    }
+    __syncthreads();
+    const int c = tid & 63;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const int tl = (tid >> 6) + 4 * e, t = t0 + tl;
+        if (t < T) {
+            float* o = out + ((long long)b * T + t) * C + c0 + c;
+            *o = t < Tb ? fmaf(w, tile[tl][c], first ? 0.f : *o) : 0.f;
+        }
+    }
+}
+
+hipError_t launch_hubert_store_frames_acc(const float* x, float* out, const int* nlen, float w, int first, int B, int C, int T, hipStream_t s) {
+    if (B <= 0 || B > 65535 || C % 64 || T <= 0) return hipErrorInvalidValue;
+    ProfScope ps(s, "hubert_store_frames_acc", 2.0 * B * (double)C * T, 12.0 * B * (double)C * T);
+    hipLaunchKernelGGL(hubert_store_frames_acc_kernel, dim3((T + 31) / 32, C / 64, B), dim3(256), 0, s, x, out, nlen, C, T, w, first);
+    return hipGetLastError();
+}
+
 }  // namespace lds

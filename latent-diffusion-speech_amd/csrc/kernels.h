@@ -314,6 +314,8 @@ hipError_t launch_hubert_posconv(const float* x, const float* wp, const float* b
 hipError_t launch_hubert_ln(const float* x, const float* gamma, const float* beta, float eps, float* out, const int* nlen, int B, int C, int T, hipStream_t s);
 // x (K4P [B][C][T]) -> out [B][T][C] frame-major, zero rows beyond a clip's frames
 hipError_t launch_hubert_store_frames(const float* x, float* out, const int* nlen, int B, int C, int T, hipStream_t s);
+// out = (first ? 0 : out) + w * x in the same layout: one term of a weighted sum of hidden states
+hipError_t launch_hubert_store_frames_acc(const float* x, float* out, const int* nlen, float w, int first, int B, int C, int T, hipStream_t s);
 
 // ---------------------------------------------------------------------------------------------
 // wav2vec 2.0 (XLSR-53) units encoder: the kernels of its own (w2v.hip); nlen / slen are device int32 [B] or null (= the buffer's length)

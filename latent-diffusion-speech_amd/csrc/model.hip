@@ -3359,8 +3359,10 @@ extern "C" int lds_wavlm_workspace_bytes(const lds_wavlm* h, int B, int64_t L, s
 }
 
 // audio -> feat ([B][T][conv_dim]) or enc ([B][T][n_state] = hidden_states[n_layers_run]).  Every argument has been checked.
+// layer_w (host float[n_layer + 1], with n_layers_run = n_layer) or NULL: enc = sum_l layer_w[l] hidden_states[l] instead, each hidden state added
+// where it exists, l ascending (launch_hubert_store_frames_acc); with NULL the launches are the plain encode's.
 static int wavlm_run(lds_wavlm* h, const float* audio, int64_t L, const int32_t* lens_host, const int32_t* nb, float* feat, float* enc, int n_layers_run,
-                     int normalize, void* ws, size_t ws_bytes, int B, void* stream) {
+                     int normalize, void* ws, size_t ws_bytes, int B, void* stream, const float* layer_w = nullptr) {
     hipStream_t st = (hipStream_t)stream;
     ProfChain chain;
     Arena A(ws, ws_bytes);
@@ -3411,6 +3413,7 @@ static int wavlm_run(lds_wavlm* h, const float* audio, int64_t L, const int32_t*
     if (!stable) HIP_TRY(launch_hubert_ln(w.xb, h->norm_g, h->norm_b, 1e-5f, w.xa, flen, B, C, T, st));
     for (int l = 0; l < n_layers_run; ++l) {
         const WavlmBlockW& bw = h->blocks[l];
+        if (layer_w) HIP_TRY(launch_hubert_store_frames_acc(stable ? w.xb : w.xa, enc, flen, layer_w[l], l == 0, B, C, T, st));
         if (stable) HIP_TRY(launch_hubert_ln(w.xb, bw.n1_g, bw.n1_b, 1e-5f, w.xa, flen, B, C, T, st));
         const DOpt oq = qkv_opt(C, w.v);      // q | k | v and the gate of the attention input w.xa
         LDS_TRY(run_dconv(bw.qkv, w.xa, C, nullptr, 0, T, oq, w.qk, B, st));
@@ -3443,7 +3446,10 @@ static int wavlm_run(lds_wavlm* h, const float* audio, int64_t L, const int32_t*
     }
     if (stable && n_layers_run == h->cfg.n_layer) {      // hidden_states[n_layer] is behind encoder.layer_norm, the earlier ones are not
         HIP_TRY(launch_hubert_ln(w.xb, h->norm_g, h->norm_b, 1e-5f, w.xa, flen, B, C, T, st));
-        HIP_TRY(launch_hubert_store_frames(w.xa, enc, flen, B, C, T, st));
+        if (layer_w) HIP_TRY(launch_hubert_store_frames_acc(w.xa, enc, flen, layer_w[n_layers_run], 0, B, C, T, st));
+        else HIP_TRY(launch_hubert_store_frames(w.xa, enc, flen, B, C, T, st));
+    } else if (layer_w) {
+        HIP_TRY(launch_hubert_store_frames_acc(w.xa, enc, flen, layer_w[n_layers_run], 0, B, C, T, st));
     } else {
         HIP_TRY(launch_hubert_store_frames(stable ? w.xb : w.xa, enc, flen, B, C, T, st));
     }
@@ -3470,6 +3476,15 @@ extern "C" int lds_wavlm_encode(lds_wavlm* h, const float* audio, const int32_t*
     LDS_TRY(wavlm_audio_check(h, audio, lengths, out, ws, B, L, normalize, nb));
     if (n_layers_run < 0 || n_layers_run > h->cfg.n_layer) return fail(LDS_EINVAL, "wavlm: n_layers_run %d outside 0 .. %d", n_layers_run, h->cfg.n_layer);
     return wavlm_run(h, audio, L, lengths, nb, nullptr, out, n_layers_run, normalize, ws, ws_bytes, B, stream);
+}
+extern "C" int lds_wavlm_encode_layersum(lds_wavlm* h, const float* audio, const int32_t* lengths, const float* layer_w, float* out, int normalize, void* ws,
+                                         size_t ws_bytes, int B, int64_t L, void* stream) {
+    int32_t nb[kHubertLevels];
+    LDS_TRY(wavlm_audio_check(h, audio, lengths, out, ws, B, L, normalize, nb));
+    if (!layer_w) return fail(LDS_EINVAL, "wavlm: null layer_w");
+    for (int l = 0; l <= h->cfg.n_layer; ++l)
+        if (!std::isfinite(layer_w[l])) return fail(LDS_EINVAL, "wavlm: layer_w[%d] is not finite", l);
+    return wavlm_run(h, audio, L, lengths, nb, nullptr, out, h->cfg.n_layer, normalize, ws, ws_bytes, B, stream, layer_w);
 }
 
 // ================================================================================================

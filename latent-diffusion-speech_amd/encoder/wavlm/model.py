@@ -62,11 +62,12 @@ class WavLM(nn.Module):
         return x.float().contiguous()
 
     @torch.no_grad()
-    def encode(self, wave, lengths=None, layer=None):
+    def encode(self, wave, lengths=None, layer=None, layer_weights=None):
         """wave [B, L] at 16 kHz on a HIP device -> hidden_states[layer] [B, T, n_state] (None = last_hidden_state); `lengths`: every
-        clip's own sample count, each clip encoded as if alone"""
+        clip's own sample count, each clip encoded as if alone.  layer_weights (n_layer + 1 soft-maxed numbers): the weighted sum of all
+        hidden states in one encode, what a *ForXVector head with use_weighted_layer_sum reads"""
         wave = self._wave("WavLM.encode", wave)      # (judged before a handle is built)
-        return self.native().encode(wave, lengths, layer=layer, normalize=self.normalize)
+        return self.native().encode(wave, lengths, layer=layer, normalize=self.normalize, layer_weights=layer_weights)
 
     @torch.no_grad()
     def extract_features(self, wave, lengths=None):

@@ -915,6 +915,35 @@ def wavlm_init_state(cfg=None, seed=0, init_weights=None):
     return OrderedDict((k, np.ascontiguousarray(v, dtype=np.float32)) for k, v in st.items())
 
 
+XVECTOR_GEOMETRY = dict(tdnn_dim=(512, 512, 512, 512, 1500), tdnn_kernel=(5, 3, 3, 1, 1), tdnn_dilation=(1, 2, 3, 1, 1), xvector_output_dim=512)
+
+
+def xvector_init_state(D, seed=0, n_layer=None, n_labels=None, geometry=None, init_weights=None):
+    """Build-owned seeded weights of an x-vector head (transformers' *ForXVector) over D-wide hidden states, in transformers' names: every
+    Linear uniform in +- 1 / sqrt(fan_in) (torch.nn.Linear's default), and with n_layer the raw `layer_weights` of n_layer + 1 hidden states
+    uniform in [-1, 1) (non-uniform once soft-maxed).  n_labels: the classifier's outputs, None = xvector_output_dim as in transformers
+    (whose config.num_labels sizes the training objective only)."""
+    if init_weights is None:
+        from . import init_weights
+    import numpy as np
+    g = dict(XVECTOR_GEOMETRY, **(geometry or {}))
+    dims = g["tdnn_dim"]
+    st = OrderedDict()
+
+    def lin(name, out, fan_in):
+        k = float(1.0 / np.sqrt(fan_in))
+        st[f"{name}.weight"] = init_weights.uniform(f"xvector.{name}.weight", (out, fan_in), seed, -k, k)
+        st[f"{name}.bias"] = init_weights.uniform(f"xvector.{name}.bias", (out,), seed, -k, k)
+    if n_layer is not None:
+        st["layer_weights"] = init_weights.uniform("xvector.layer_weights", (n_layer + 1,), seed, -1.0, 1.0)
+    lin("projector", dims[0], D)
+    for i in range(len(dims)):
+        lin(f"tdnn.{i}.kernel", dims[i], (dims[i - 1] if i else dims[0]) * g["tdnn_kernel"][i])
+    lin("feature_extractor", g["xvector_output_dim"], 2 * dims[-1])
+    lin("classifier", g["xvector_output_dim"] if n_labels is None else n_labels, g["xvector_output_dim"])
+    return OrderedDict((k, np.ascontiguousarray(v, dtype=np.float32)) for k, v in st.items())
+
+
 def wavlm_convert_state(state, cfg=None):
     """A checkpoint's state dict in transformers naming (an optional "module." / "wavlm." prefix removed, masked_spec_embed and the task
     heads dropped) -> the tensors of wavlm_param_shapes(cfg).  A missing tensor is a KeyError naming it; a wrong shape a ValueError."""

@@ -182,6 +182,13 @@ lds_ctc_score_workspace_bytes    i:iiiiip
 lds_ctc_score                    i:piipppiiippippzp
 lds_ctc_align_workspace_bytes    i:iiiiip
 lds_ctc_align                    i:piipppiiippipppppzp
+lds_wavlm_encode_layersum        i:pppppipziqp
+lds_xvector_create               i:pipppp
+lds_xvector_destroy              v:p
+lds_xvector_n_labels             i:p
+lds_xvector_workspace_bytes      i:piip
+lds_xvector_embed                i:ppppppziip
+lds_xvector_cosine               i:pipiipp
 lds_resample                     i:ppppiiiiqqp
 lds_resample_ragged              i:ppppppiiiiqqp
 lds_frame_rms                    i:ppqiiiqp
@@ -260,6 +267,9 @@ lds_test_ivf_search              i:pqppqiippippppqiipppzp
 lds_test_ivf_search_metric       i:pqppqiippippppqiiipppzp
 lds_test_ctc_forward             i:piipppipp
 lds_test_ctc_viterbi             i:piipppipppppzp
+lds_test_xvector_tdnn            i:piipppiiiiipp
+lds_test_xvector_pool_workspace_bytes i:iiip
+lds_test_xvector_pool            i:piipppiiiipppzp
 lds_test_wino_pack               i:piip
 lds_test_wino_conv               i:ppiiipppiippippiipppip
 lds_bench_wino                   i:ppiiipppiippipiiiipppzp
@@ -823,8 +833,8 @@ class _UnitsEncoder(_Handle):
             raise ValueError(f"{name}: {L} samples give {n} {self.UNIT}, more than {self.CTX} {ctx}")
         return n
 
-    def _call(self, entry, audio, lengths, ws, shape, mid=(), pad=None):
-        """entry(h, audio, lengths, out, *mid, ws, ws_bytes, B, L, [pad,] stream) -> out [B, *shape(n, L)], n = the units of L samples"""
+    def _call(self, entry, audio, lengths, ws, shape, mid=(), pad=None, pre=()):
+        """entry(h, audio, lengths, *pre, out, *mid, ws, ws_bytes, B, L, [pad,] stream) -> out [B, *shape(n, L)], n = the units of L samples"""
         import torch
         if audio.dim() != 2:
             raise ValueError(f"{type(self).__name__}: audio must be [B, L], got {list(audio.shape)}")
@@ -835,7 +845,7 @@ class _UnitsEncoder(_Handle):
         tail = (self._pad(pad),) if self.PAD else ()
         ws = ws if ws is not None else self.ws.get(self.workspace_bytes(B, L, pad), audio.device)
         out = torch.empty(B, *shape(n, L), dtype=torch.float32, device=audio.device)
-        check(getattr(lib(), entry)(self.h, _dev(audio, torch.float32), _host(ln), _dev(out), *mid, _dev(ws), ws.numel(), B, L, *tail, _stream()))
+        check(getattr(lib(), entry)(self.h, _dev(audio, torch.float32), _host(ln), *pre, _dev(out), *mid, _dev(ws), ws.numel(), B, L, *tail, _stream()))
         return out
 
 
@@ -961,8 +971,16 @@ class WavLM(_UnitsEncoder):
     def features(self, audio, lengths=None, normalize=False, ws=None):
         return self._call("lds_wavlm_features", audio, lengths, ws, lambda n, L: (n, self.dims["conv_dim"]), mid=(1 if normalize else 0,))
 
-    def encode(self, audio, lengths=None, layer=None, normalize=False, ws=None):
-        """layer: the blocks to run = the index into WavLMModel's hidden_states (None = all: last_hidden_state)"""
+    def encode(self, audio, lengths=None, layer=None, normalize=False, ws=None, layer_weights=None):
+        """layer: the blocks to run = the index into WavLMModel's hidden_states (None = all: last_hidden_state).  layer_weights (n_layer + 1
+        finite host floats, already soft-maxed; not with `layer`): the weighted sum of all hidden states instead (lds_wavlm_encode_layersum)"""
+        if layer_weights is not None:
+            if layer is not None:
+                raise ValueError("WavLM: layer_weights sums every hidden state; it does not go with layer=")
+            lw = np.ascontiguousarray(np.asarray(layer_weights.detach().cpu() if hasattr(layer_weights, "detach") else layer_weights, dtype=np.float32).reshape(-1))
+            if lw.shape != (self.dims["n_layer"] + 1,) or not np.isfinite(lw).all():
+                raise ValueError(f"WavLM: layer_weights must be {self.dims['n_layer'] + 1} finite numbers (one per hidden state)")
+            return self._call("lds_wavlm_encode_layersum", audio, lengths, ws, lambda n, L: (n, self.dims["n_state"]), mid=(1 if normalize else 0,), pre=(_host(lw),))
         nl = self.dims["n_layer"] if layer is None else int(layer)
         if not 0 <= nl <= self.dims["n_layer"]:
             raise ValueError(f"WavLM: layer {nl} outside 0 .. {self.dims['n_layer']}")
@@ -1669,6 +1687,108 @@ def ctc_test_viterbi(E, n_frames, labels, label_len, ws=None):
     check(lib().lds_test_ctc_viterbi(_dev(E, torch.float32), B, T, _host(nf), _dev(labels, torch.int64), _host(ll), W1 - 1, _dev(ps), _dev(fl), _dev(seg),
                                      _dev(llp), _dev(ws), ws.numel(), _stream()))
     return ps, fl, seg, llp
+
+
+# ---- x-vector speaker head (lds_xvector_*): hidden states [B, T, d_in] contiguous fp32 device tensors, per-clip frame counts on the host ----
+XVECTOR_K_STEP = 32       # every layer's input width is a multiple of it (a K-block of the TDNN GEMM may not span two taps)
+XVECTOR_MAX_T = 32768
+
+
+class XVectorCfg(C.Structure):
+    _fields_ = [("d_in", C.c_int), ("n_tdnn", C.c_int), ("tdnn_dim", C.c_int * 8), ("tdnn_kernel", C.c_int * 8), ("tdnn_dilation", C.c_int * 8),
+                ("xvector_dim", C.c_int)]
+
+
+def xvector_check_layer(Cin, Cout, ks, dil, what="xvector"):
+    """the limits of one TDNN / linear layer (include/lds.h), as ValueErrors before a device is touched"""
+    if Cin < XVECTOR_K_STEP or Cin > 4096 or Cin % XVECTOR_K_STEP:
+        raise ValueError(f"{what}: input width {Cin} must be a multiple of the K-step {XVECTOR_K_STEP} in {XVECTOR_K_STEP} .. 4096")
+    if Cout < 4 or Cout > 4096 or Cout % 4:
+        raise ValueError(f"{what}: output width {Cout} must be a multiple of 4 in 4 .. 4096")
+    if not 1 <= ks <= 8 or not 1 <= dil <= 8:
+        raise ValueError(f"{what}: kernel {ks} / dilation {dil} outside 1 .. 8")
+
+
+class XVector(_Handle):
+    """Handle on an x-vector head (lds_xvector_*).  d_in: the hidden width; tdnn_dim / tdnn_kernel / tdnn_dilation: HF's config keys;
+    `state`: the head's tensors under their transformers names (projector.*, tdnn.{i}.kernel.*, feature_extractor.*, classifier.*)."""
+    KIND = "xvector"
+
+    def __init__(self, d_in, tdnn_dim, tdnn_kernel, tdnn_dilation, xvector_dim, state):
+        dim, ker, dil = [int(v) for v in tdnn_dim], [int(v) for v in tdnn_kernel], [int(v) for v in tdnn_dilation]
+        if not 1 <= len(dim) <= 8 or len(ker) != len(dim) or len(dil) != len(dim):
+            raise ValueError(f"xvector: 1 .. 8 TDNN layers with one kernel and one dilation each (got {len(dim)}, {len(ker)}, {len(dil)})")
+        xvector_check_layer(int(d_in), dim[0], 1, 1, "xvector projector")
+        for i in range(len(dim)):
+            xvector_check_layer(dim[i - 1] if i else dim[0], dim[i], ker[i], dil[i], f"xvector tdnn.{i}")
+        if xvector_dim < 4 or xvector_dim > 4096 or xvector_dim % 4:
+            raise ValueError(f"xvector: xvector_dim {xvector_dim} must be a multiple of 4 in 4 .. 4096")
+        pad = [0] * (8 - len(dim))
+        cfg = XVectorCfg(int(d_in), len(dim), (C.c_int * 8)(*dim, *pad), (C.c_int * 8)(*ker, *pad), (C.c_int * 8)(*dil, *pad), int(xvector_dim))
+        self._create_weights(cfg, state)
+        self.d_in, self.xvector_dim, self.span = int(d_in), int(xvector_dim), sum((k - 1) * d for k, d in zip(ker, dil))
+        self.n_labels = lib().lds_xvector_n_labels(self.h)
+
+    def embed(self, hidden, n_frames, return_logits=True, ws=None):
+        """hidden [B, T, d_in], n_frames (host ints [B]; every clip needs span + 2 frames) -> (embeddings [B, xvector_dim], logits [B, n_labels] or None)"""
+        import torch
+        if hidden.dim() != 3 or hidden.shape[-1] != self.d_in:
+            raise ValueError(f"xvector: hidden states {list(hidden.shape)} against a head over {self.d_in}-wide ones")
+        B, T, _ = hidden.shape
+        if not 1 <= T <= XVECTOR_MAX_T:
+            raise ValueError(f"xvector: T {T} outside 1 .. {XVECTOR_MAX_T}")
+        nf = _host_lengths(n_frames, B, 0, T, 64, "x-vector")
+        if nf.min() < self.span + 2:
+            raise ValueError(f"xvector: a clip of {int(nf.min())} frames leaves {max(int(nf.min()) - self.span, 0)} frames to pool; the unbiased standard "
+                             f"deviation needs 2, i.e. at least {self.span + 2} frames")
+        _dev(hidden, None)
+        if ws is None:
+            ws = self._workspace("lds_xvector_workspace_bytes", hidden.device, B, T)
+        emb = torch.empty(B, self.xvector_dim, dtype=torch.float32, device=hidden.device)
+        logits = torch.empty(B, self.n_labels, dtype=torch.float32, device=hidden.device) if return_logits else None
+        check(lib().lds_xvector_embed(self.h, _dev(hidden, torch.float32), _host(nf), _dev(emb), _dev_or_null(logits), _dev(ws), ws.numel(), B, T, _stream()))
+        return emb, logits
+
+
+def xvector_cosine(a, b):
+    """a [N, dim], b [M, dim] -> [N, M]: torch.nn.functional.cosine_similarity of every pair (include/lds.h lds_xvector_cosine)"""
+    import torch
+    if a.dim() != 2 or b.dim() != 2 or a.shape[1] != b.shape[1] or not a.shape[0] or not b.shape[0]:
+        raise ValueError(f"xvector_cosine: {list(a.shape)} against {list(b.shape)} are not [N, dim] and [M, dim]")
+    _dev(a, None)
+    out = torch.empty(a.shape[0], b.shape[0], dtype=torch.float32, device=a.device)
+    check(lib().lds_xvector_cosine(_dev(a, torch.float32), a.shape[0], _dev(b, torch.float32), b.shape[0], a.shape[1], _dev(out), _stream()))
+    return out
+
+
+def _xvector_layer_args(X, n_frames, W, bias, ks):
+    B, T, Cin = X.shape
+    Cout = W.shape[0]
+    assert tuple(W.shape) == (Cout, ks * Cin) and tuple(bias.shape) == (Cout,)
+    return B, T, Cin, Cout, _host_lengths(n_frames, B, 0, T, 64, "x-vector")
+
+
+def xvector_test_tdnn(X, n_frames, W, bias, ks, dil, relu=True, out=None):
+    """one layer (include/lds_test.h lds_test_xvector_tdnn) -> Y [B, T, Cout]; `out`: a preallocated Y (tests put guards behind it)"""
+    import torch
+    B, T, Cin, Cout, nf = _xvector_layer_args(X, n_frames, W, bias, ks)
+    Y = torch.empty(B, T, Cout, dtype=torch.float32, device=X.device) if out is None else out
+    check(lib().lds_test_xvector_tdnn(_dev(X, torch.float32), B, T, _host(nf), _dev(W, torch.float32), _dev(bias, torch.float32), Cin, Cout, int(ks), int(dil),
+                                      1 if relu else 0, _dev(Y), _stream()))
+    return Y
+
+
+def xvector_test_pool(X, n_frames, W, bias, ks, dil, return_y=False, ws=None):
+    """the last layer with the pooling in its epilogue (include/lds_test.h lds_test_xvector_pool) -> stats [B, 2 Cout][, the unfused Y]"""
+    import torch
+    B, T, Cin, Cout, nf = _xvector_layer_args(X, n_frames, W, bias, ks)
+    if ws is None:
+        ws = _ctc_ws.get(_bytes("lds_test_xvector_pool_workspace_bytes", B, T, Cout), X.device)
+    stats = torch.empty(B, 2 * Cout, dtype=torch.float32, device=X.device)
+    Y = torch.empty(B, T, Cout, dtype=torch.float32, device=X.device) if return_y else None
+    check(lib().lds_test_xvector_pool(_dev(X, torch.float32), B, T, _host(nf), _dev(W, torch.float32), _dev(bias, torch.float32), Cin, Cout, int(ks), int(dil),
+                                      _dev(stats), _dev_or_null(Y), _dev(ws), ws.numel(), _stream()))
+    return (stats, Y) if return_y else stats
 
 
 def resample_tables(orig_freq, new_freq, lowpass_filter_width=6, rolloff=0.99):
