@@ -17,6 +17,7 @@
 #include "../../include/lds.h"
 #include "../../include/lds_test.h"
 #include "kernels.h"
+#include "host.h"
 
 #include <math.h>
 
@@ -549,20 +550,17 @@ struct CtcPlan {
     size_t o_part, o_arg, o_m, o_lse, o_E, o_bad, o_bp, bytes;
 };
 
-int ctc_check_dims(const char* fn, int B, int T, int V, int D) {
-    if (D < 8 || D > 4096 || D % 8) return set_error(LDS_EINVAL, "%s: D %d must be a multiple of 8 in 8 .. 4096", fn, D);
-    if (V < 2 || V > 65536) return set_error(LDS_EINVAL, "%s: V %d outside 2 .. 65536", fn, V);
-    if (B < 1 || B > 64) return set_error(LDS_EINVAL, "%s: B %d outside 1 .. 64", fn, B);
+int ctc_check_bt(const char* fn, int B, int T) {
+    LDS_TRY(range_check(fn, "B", B, 1, 64));
     if (T < 1) return set_error(LDS_EINVAL, "%s: T %d < 1", fn, T);
     if ((long long)B * T > 2147482648LL) return set_error(LDS_EINVAL, "%s: B * T = %lld beyond 2^31 - 1000", fn, (long long)B * T);
     return LDS_OK;
 }
 
-int ctc_check_bt(const char* fn, int B, int T) {
-    if (B < 1 || B > 64) return set_error(LDS_EINVAL, "%s: B %d outside 1 .. 64", fn, B);
-    if (T < 1) return set_error(LDS_EINVAL, "%s: T %d < 1", fn, T);
-    if ((long long)B * T > 2147482648LL) return set_error(LDS_EINVAL, "%s: B * T = %lld beyond 2^31 - 1000", fn, (long long)B * T);
-    return LDS_OK;
+int ctc_check_dims(const char* fn, int B, int T, int V, int D) {
+    if (D < 8 || D > 4096 || D % 8) return set_error(LDS_EINVAL, "%s: D %d must be a multiple of 8 in 8 .. 4096", fn, D);
+    LDS_TRY(range_check(fn, "V", V, 2, 65536));
+    return ctc_check_bt(fn, B, T);
 }
 
 int ctc_check_lmax(const char* fn, int Lmax) {
@@ -571,25 +569,13 @@ int ctc_check_lmax(const char* fn, int Lmax) {
 }
 
 int ctc_lens(const char* fn, int B, int T, const int32_t* n_frames, lds::CtcLens& lens) {
-    if (!n_frames) return set_error(LDS_EINVAL, "%s: null n_frames", fn);
     lens.B = B; lens.T = T;
-    for (int i = 0; i < 64; ++i) lens.v[i] = 0;
-    for (int b = 0; b < B; ++b) {
-        if (n_frames[b] < 0 || n_frames[b] > T) return set_error(LDS_EINVAL, "%s: n_frames[%d] = %d outside 0 .. %d", fn, b, n_frames[b], T);
-        lens.v[b] = n_frames[b];
-    }
-    return LDS_OK;
+    return clip_lens_fill(fn, "n_frames", B, T, n_frames, lens.v);
 }
 
 int ctc_labs(const char* fn, int B, int Lmax, int blank, int V, const int32_t* label_len, lds::CtcLabs& labs) {
-    if (!label_len) return set_error(LDS_EINVAL, "%s: null label_len", fn);
     labs.Lmax = Lmax; labs.blank = blank; labs.V = V;
-    for (int i = 0; i < 64; ++i) labs.len[i] = 0;
-    for (int b = 0; b < B; ++b) {
-        if (label_len[b] < 0 || label_len[b] > Lmax) return set_error(LDS_EINVAL, "%s: label_len[%d] = %d outside 0 .. %d", fn, b, label_len[b], Lmax);
-        labs.len[b] = label_len[b];
-    }
-    return LDS_OK;
+    return clip_lens_fill(fn, "label_len", B, Lmax, label_len, labs.len);
 }
 
 // Lmax = 0: the head alone; align: also the back-pointers
@@ -598,22 +584,16 @@ CtcPlan ctc_plan(int B, int T, int V, int Lmax, bool align) {
     const size_t N = (size_t)B * T;
     const int nCB = (V + lds::kCtcB - 1) / lds::kCtcB;
     p.KS = (nCB + lds::kCtcCbps - 1) / lds::kCtcCbps;
-    size_t o = 0;
-    auto take = [&](size_t n) { const size_t at = o; o += (n + 255) & ~(size_t)255; return at; };
-    p.o_part = take(p.KS > 1 ? (size_t)p.KS * N * 12 : 0);
-    p.o_arg = take(Lmax ? N * 4 : 0);
-    p.o_m = take(Lmax ? N * 4 : 0);
-    p.o_lse = take(Lmax ? N * 4 : 0);
-    p.o_E = take(Lmax ? N * (size_t)(Lmax + 1) * 4 : 0);
-    p.o_bad = take(Lmax ? 256 : 0);
-    p.o_bp = take(align ? N * 256 : 0);
-    p.bytes = o > 256 ? o : 256;
+    Slots S;
+    p.o_part = S.take(p.KS > 1 ? (size_t)p.KS * N * 12 : 0);
+    p.o_arg = S.take(Lmax ? N * 4 : 0);
+    p.o_m = S.take(Lmax ? N * 4 : 0);
+    p.o_lse = S.take(Lmax ? N * 4 : 0);
+    p.o_E = S.take(Lmax ? N * (size_t)(Lmax + 1) * 4 : 0);
+    p.o_bad = S.take(Lmax ? 256 : 0);
+    p.o_bp = S.take(align ? N * 256 : 0);
+    p.bytes = S.o > 256 ? S.o : 256;
     return p;
-}
-
-int ctc_launched(const char* fn) {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? LDS_OK : set_error(LDS_EHIP, "%s: %s", fn, hipGetErrorString(e));
 }
 
 // the statistics of every frame into (arg, m, lse); logprobs may be NULL
@@ -672,7 +652,7 @@ int ctc_score_align(const char* fn, bool align, const float* X, int B, int T, co
     else
         hipLaunchKernelGGL(lds::ctc_trellis_kernel<false>, dim3(B), dim3(64), 0, s, E, (const long long*)labels, bad, score, (unsigned*)nullptr, (int*)nullptr,
                            (int*)nullptr, (float*)nullptr, lens, labs);
-    return ctc_launched(fn);
+    return launched(fn);
 }
 
 }  // namespace
@@ -694,7 +674,7 @@ extern "C" int lds_ctc_head(const float* X, int B, int T, const int32_t* n_frame
     const CtcPlan p = ctc_plan(B, T, V, 0, false);
     if (ws_bytes < p.bytes) return set_error(LDS_ENOMEM, "%s: workspace %zu < %zu bytes", fn, ws_bytes, p.bytes);
     ctc_head_launch(X, W, bias, V, D, arg, m, lse, logprobs_out, (char*)ws, p, lens, (hipStream_t)stream);
-    return ctc_launched(fn);
+    return launched(fn);
 }
 
 extern "C" int lds_ctc_greedy(const int32_t* arg, const float* m, const float* lse, int B, int T, const int32_t* n_frames, int blank, int64_t pad_id,
@@ -707,7 +687,7 @@ extern "C" int lds_ctc_greedy(const int32_t* arg, const float* m, const float* l
     if (!arg || !m || !lse || !tokens || !n_tokens || !start || !length || !logprob) return set_error(LDS_EINVAL, "%s: null pointer", fn);
     hipLaunchKernelGGL(lds::ctc_collapse_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, (const int*)arg, m, lse, blank, (long long)pad_id, (long long*)tokens,
                        (int*)n_tokens, (int*)start, (int*)length, logprob, lens);
-    return ctc_launched(fn);
+    return launched(fn);
 }
 
 extern "C" int lds_ctc_score_workspace_bytes(int B, int T, int V, int D, int Lmax, size_t* out) {
@@ -759,7 +739,7 @@ extern "C" int lds_test_ctc_forward(const float* E, int B, int T, const int32_t*
     if (!E || !labels || !nll) return set_error(LDS_EINVAL, "%s: null pointer", fn);
     hipLaunchKernelGGL(lds::ctc_trellis_kernel<false>, dim3(B), dim3(64), 0, (hipStream_t)stream, E, (const long long*)labels, (const int*)nullptr, nll,
                        (unsigned*)nullptr, (int*)nullptr, (int*)nullptr, (float*)nullptr, lens, labs);
-    return ctc_launched(fn);
+    return launched(fn);
 }
 
 extern "C" int lds_test_ctc_viterbi(const float* E, int B, int T, const int32_t* n_frames, const int64_t* labels, const int32_t* label_len, int Lmax,
@@ -773,5 +753,5 @@ extern "C" int lds_test_ctc_viterbi(const float* E, int B, int T, const int32_t*
     if (ws_bytes < need) return set_error(LDS_ENOMEM, "%s: workspace %zu < %zu bytes", fn, ws_bytes, need);
     hipLaunchKernelGGL(lds::ctc_trellis_kernel<true>, dim3(B), dim3(64), 0, (hipStream_t)stream, E, (const long long*)labels, (const int*)nullptr, path_score,
                        (unsigned*)ws, (int*)frame_label, (int*)segments, label_logprob, lens, labs);
-    return ctc_launched(fn);
+    return launched(fn);
 }

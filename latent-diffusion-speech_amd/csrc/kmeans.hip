@@ -14,6 +14,7 @@
 //   seed     k-means++ (_kpp, kmeans.py:10-50) with a running minimum distance and a double-precision prefix; the picks stay on the device.
 #include "../../include/lds.h"
 #include "kernels.h"
+#include "host.h"
 
 #include <math.h>
 
@@ -459,25 +460,19 @@ KmPlan km_plan(long long N, int K, int D) {
     p.NB = (int)nb;
     p.per = (N + nb - 1) / nb;
     p.nblk = (N + 255) / 256;
-    size_t o = 0;
-    auto take = [&](size_t n) { const size_t at = o; o += (n + 255) & ~(size_t)255; return at; };
-    p.o_pval = take(p.KS > 1 ? (size_t)p.KS * N * 4 : 0);
-    p.o_pidx = take(p.KS > 1 ? (size_t)p.KS * N * 4 : 0);
-    p.o_hist = take((size_t)p.NB * K * 4);
-    p.o_counts = take((size_t)K * 4);
-    p.o_offsets = take((size_t)K * 4);
-    p.o_sorted = take((size_t)N * 4);
-    p.o_err = take((size_t)K * ((D + 255) / 256) * 4);
-    p.o_mind = take((size_t)N * 4);
-    p.o_bsum = take((size_t)p.nblk * 8);
-    p.o_picked = take((size_t)K * 8);
-    p.bytes = o;
+    Slots S;
+    p.o_pval = S.take(p.KS > 1 ? (size_t)p.KS * N * 4 : 0);
+    p.o_pidx = S.take(p.KS > 1 ? (size_t)p.KS * N * 4 : 0);
+    p.o_hist = S.take((size_t)p.NB * K * 4);
+    p.o_counts = S.take((size_t)K * 4);
+    p.o_offsets = S.take((size_t)K * 4);
+    p.o_sorted = S.take((size_t)N * 4);
+    p.o_err = S.take((size_t)K * ((D + 255) / 256) * 4);
+    p.o_mind = S.take((size_t)N * 4);
+    p.o_bsum = S.take((size_t)p.nblk * 8);
+    p.o_picked = S.take((size_t)K * 8);
+    p.bytes = S.o;
     return p;
-}
-
-int km_launched(const char* fn) {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? LDS_OK : set_error(LDS_EHIP, "%s: %s", fn, hipGetErrorString(e));
 }
 
 int km_check_metric(const char* fn, int metric) {
@@ -506,7 +501,7 @@ int km_assign(const char* fn, int metric, const float* X, long long N, const flo
         hipLaunchKernelGGL(lds::kmeans_join_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, pval, pidx, p.KS, N, (long long*)labels, best, lens);
     if (metric == LDS_METRIC_COSINE && best)
         hipLaunchKernelGGL(lds::kmeans_cos_best_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, s, X, N, D, best, lens);
-    return km_launched(fn);
+    return launched(fn);
 }
 
 }  // namespace
@@ -524,7 +519,7 @@ int km_prepare(const char* fn, int metric, const float* C, int K, int D, float* 
     if (int rc = km_check_dims(fn, 1, K, D)) return rc;
     if (!C || !h) return set_error(LDS_EINVAL, "%s: null pointer", fn);
     hipLaunchKernelGGL(lds::kmeans_prepare_kernel, dim3((K + 3) / 4), dim3(256), 0, (hipStream_t)stream, C, K, D, h, metric);
-    return km_launched(fn);
+    return launched(fn);
 }
 }  // namespace
 
@@ -609,7 +604,7 @@ int km_update(const char* fn, int metric, const float* X, const int64_t* labels,
     }
     hipLaunchKernelGGL(lds::kmeans_finish_kernel, dim3(1), dim3(256), 0, s, errpart, (long long)K * ncb, counts, K, num_points, error);
     hipLaunchKernelGGL(lds::kmeans_prepare_kernel, dim3((K + 3) / 4), dim3(256), 0, s, C, K, D, h, metric);
-    return km_launched(fn);
+    return launched(fn);
 }
 }  // namespace
 
@@ -640,5 +635,5 @@ extern "C" int lds_kmeans_seed(const float* X, int64_t N, int D, int K, int64_t 
         hipLaunchKernelGGL(lds::kmeans_seed_dist_kernel, dim3((unsigned)p.nblk), dim3(256), 0, s, X, (long long)N, D, C + (size_t)(i - 1) * D, i == 1 ? 1 : 0, mind, bsum);
         hipLaunchKernelGGL(lds::kmeans_seed_pick_kernel, dim3(1), dim3(256), 0, s, X, (long long)N, D, mind, bsum, p.nblk, uniforms + (i - 1), -1LL, C + (size_t)i * D, pk + i);
     }
-    return km_launched("lds_kmeans_seed");
+    return launched("lds_kmeans_seed");
 }

@@ -17,6 +17,7 @@
 #include "../../include/lds.h"
 #include "../../include/lds_test.h"
 #include "kernels.h"
+#include "host.h"
 
 #include <math.h>
 
@@ -444,17 +445,11 @@ KnPlan kn_plan(long long N, long long M, int D, int k, int slab_rows, int splits
     if (s > nPB) s = nPB;
     p.pbps = (int)((nPB + s - 1) / s);
     p.S = (nPB + p.pbps - 1) / p.pbps;
-    size_t o = 0;
-    auto take = [&](size_t n) { const size_t at = o; o += (n + 255) & ~(size_t)255; return at; };
-    p.o_val = take((size_t)p.S * (size_t)N * p.KT * 4);
-    p.o_idx = take((size_t)p.S * (size_t)N * p.KT * 4);
-    p.bytes = o;
+    Slots S;
+    p.o_val = S.take((size_t)p.S * (size_t)N * p.KT * 4);
+    p.o_idx = S.take((size_t)p.S * (size_t)N * p.KT * 4);
+    p.bytes = S.o;
     return p;
-}
-
-int kn_launched(const char* fn) {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? LDS_OK : set_error(LDS_EHIP, "%s: %s", fn, hipGetErrorString(e));
 }
 
 bool kn_misaligned(const void* p) { return ((uintptr_t)p & 15) != 0; }
@@ -520,7 +515,7 @@ int kn_search(const char* fn, int metric, const float* X, long long N, const flo
     int* lidx = (int*)((char*)ws + p.o_idx);
     kn_topk(p, metric, X, N, P, h, (int)M, D, lval, lidx, s);
     kn_select(metric, X, D, lval, lidx, p.S, p.KT, N, (int)M, k, idx, score, s);
-    return kn_launched(fn);
+    return launched(fn);
 }
 
 int kn_retrieve(const char* fn, int metric, int weights, const float* X, long long N, const float* P, const float* h, long long M, int D, int k, float ratio,
@@ -536,7 +531,7 @@ int kn_retrieve(const char* fn, int metric, int weights, const float* X, long lo
     int* lidx = (int*)((char*)ws + p.o_idx);
     kn_topk(p, metric, X, N, P, h, (int)M, D, lval, lidx, s);
     kn_blend(metric, weights, X, N, P, h, (int)M, D, lval, lidx, p.S, p.KT, k, ratio, Y, idx, dist, lens, s);
-    return kn_launched(fn);
+    return launched(fn);
 }
 
 lds::KnLens kn_plain() {
@@ -554,19 +549,13 @@ int kn_prepare(const char* fn, int metric, const float* P, int64_t M, int D, flo
     if (int rc = kn_check_dims(fn, 1, M, D, 1)) return rc;
     if (!P || !h) return set_error(LDS_EINVAL, "%s: null pointer", fn);
     hipLaunchKernelGGL(lds::knn_prepare_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, (hipStream_t)stream, P, (long long)M, D, h, metric);
-    return kn_launched(fn);
+    return launched(fn);
 }
 
 int kn_ragged_lens(const char* fn, int B, int T, const int32_t* lengths, lds::KnLens& lens) {
     if (B < 1 || B > 64 || T < 1) return set_error(LDS_EINVAL, "%s: B %d outside 1 .. 64 or T %d < 1", fn, B, T);
-    if (!lengths) return set_error(LDS_EINVAL, "%s: null lengths", fn);
-    lens = kn_plain();
     lens.n = B; lens.T = T;
-    for (int b = 0; b < B; ++b) {
-        if (lengths[b] < 0 || lengths[b] > T) return set_error(LDS_EINVAL, "%s: lengths[%d] = %d outside 0 .. %d", fn, b, lengths[b], T);
-        lens.v[b] = lengths[b];
-    }
-    return LDS_OK;
+    return clip_lens_fill(fn, "lengths", B, T, lengths, lens.v);
 }
 }  // namespace
 
@@ -981,19 +970,18 @@ IvfPlan ivf_plan(long long N, int D, int k, int nlist, int nprobe, int slab_rows
     p.pairs = N * nprobe;
     const long long full = p.pairs / lds::kKnB + nlist;
     p.wmax = (unsigned)((full < p.pairs ? full : p.pairs) * lds::kIvfSegs);
-    size_t o = (p.coarse.bytes + 255) & ~(size_t)255;
-    auto take = [&](size_t n) { const size_t at = o; o += (n + 255) & ~(size_t)255; return at; };
-    p.o_probe = take((size_t)p.pairs * 4);
-    p.o_cnt = take((size_t)nlist * 4);
-    p.o_llen = take((size_t)nlist * 4);
-    p.o_lrow = take((size_t)nlist * 4);
-    p.o_lblk = take((size_t)nlist * 4);
-    p.o_bstart = take(((size_t)nlist + 1) * 8);
-    p.o_wstart = take(((size_t)nlist + 1) * 4);
-    p.o_bq = take((size_t)p.pairs * 8);
-    p.o_val = take((size_t)nprobe * lds::kIvfSegs * (size_t)N * p.KT * 4);
-    p.o_idx = take((size_t)nprobe * lds::kIvfSegs * (size_t)N * p.KT * 4);
-    p.bytes = o;
+    Slots S{Slots::round(p.coarse.bytes)};
+    p.o_probe = S.take((size_t)p.pairs * 4);
+    p.o_cnt = S.take((size_t)nlist * 4);
+    p.o_llen = S.take((size_t)nlist * 4);
+    p.o_lrow = S.take((size_t)nlist * 4);
+    p.o_lblk = S.take((size_t)nlist * 4);
+    p.o_bstart = S.take(((size_t)nlist + 1) * 8);
+    p.o_wstart = S.take(((size_t)nlist + 1) * 4);
+    p.o_bq = S.take((size_t)p.pairs * 8);
+    p.o_val = S.take((size_t)nprobe * lds::kIvfSegs * (size_t)N * p.KT * 4);
+    p.o_idx = S.take((size_t)nprobe * lds::kIvfSegs * (size_t)N * p.KT * 4);
+    p.bytes = S.o;
     return p;
 }
 
@@ -1063,7 +1051,7 @@ int ivf_search(const char* fn, const float* X, long long N, long long M, int D, 
     if (ws_bytes < p.bytes) return set_error(LDS_ENOMEM, "%s: workspace %zu < %zu bytes", fn, ws_bytes, p.bytes);
     ivf_lists(p, X, N, M, D, ix, ws, s);
     kn_select(ix.metric, X, D, (const float*)((char*)ws + p.o_val), (const int*)((char*)ws + p.o_idx), ix.nprobe * lds::kIvfSegs, p.KT, N, (int)M, k, idx, score, s);
-    return kn_launched(fn);
+    return launched(fn);
 }
 
 int ivf_retrieve(const char* fn, int weights, const float* X, long long N, const float* P, const float* h, long long M, int D, int k, const IvfIndex& ix, float ratio,
@@ -1080,7 +1068,7 @@ int ivf_retrieve(const char* fn, int weights, const float* X, long long N, const
     ivf_lists(p, X, N, M, D, ix, ws, s);
     kn_blend(ix.metric, weights, X, N, P, h, (int)M, D, (const float*)((char*)ws + p.o_val), (const int*)((char*)ws + p.o_idx), ix.nprobe * lds::kIvfSegs, p.KT, k,
              ratio, Y, idx, dist, lens, s);
-    return kn_launched(fn);
+    return launched(fn);
 }
 
 }  // namespace

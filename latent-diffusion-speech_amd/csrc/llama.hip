@@ -20,13 +20,13 @@
 //                  lm.hip's beam step in its per-row form (lm_common.h)
 #include "../../include/lds.h"
 #include "kernels.h"
+#include "host.h"
 #include "lm_common.h"
 
 #include <math.h>
 #include <stdio.h>
 #include <string.h>
 
-#include <map>
 #include <string>
 #include <vector>
 
@@ -487,43 +487,19 @@ using namespace lds;
 // ================================================================================================
 // host side
 // ================================================================================================
-#define ll_fail lds::set_error
-#define LL_HIP(expr)                                                                                                    \
-    do {                                                                                                                \
-        hipError_t e_ = (expr);                                                                                         \
-        if (e_ != hipSuccess) return ll_fail(LDS_EHIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
-
 struct LlLayer { float *nw_attn = nullptr, *wqkv = nullptr, *wo = nullptr, *nw_mlp = nullptr, *wgate = nullptr, *wup = nullptr, *wdown = nullptr; };
 struct lds_llama {
     lds_llama_cfg cfg;
-    std::vector<void*> bufs;
+    Owner own;
     float *embed = nullptr, *cs = nullptr, *nw_final = nullptr, *head = nullptr, *head_lo = nullptr;
     std::vector<LlLayer> layers;
-    ~lds_llama() { for (void* p : bufs) (void)hipFree(p); }
-    float* up(const std::vector<float>& h) {
-        void* d = nullptr;
-        if (hipMalloc(&d, h.size() * sizeof(float)) != hipSuccess) return nullptr;
-        if (hipMemcpy(d, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(d); return nullptr; }
-        bufs.push_back(d);
-        return (float*)d;
-    }
 };
 
 namespace {
 constexpr int kLlMaxBatch = 64;          // the rows' final lengths live in 64 ints behind the step flags
 constexpr int kLlMaxLength = 15000;      // the attention stages one score per key in LDS
-struct LlTensors {
-    std::map<std::string, std::pair<const float*, int64_t>> m;
-    std::string missing;
-    const float* get(const std::string& k, int64_t n) {
-        auto it = m.find(k);
-        if (it == m.end() || it->second.second != n) { if (missing.empty()) missing = k; return nullptr; }
-        return it->second.first;
-    }
-};
 // reference layout W [M][K] (rows r0 .. r0 + Mper of each) -> transposed [K][M], several matrices concatenated along M
-float* ll_linear_up(lds_llama* L, LlTensors& T, const std::vector<std::pair<std::string, int>>& mats, int K, int r0 = 0, int rows_all = -1) {
+float* ll_linear_up(WeightLoader& T, const std::vector<std::pair<std::string, int>>& mats, int K, int r0 = 0, int rows_all = -1) {
     int M = 0;
     for (auto& s : mats) M += s.second;
     std::vector<float> wt((size_t)K * M);
@@ -536,63 +512,57 @@ float* ll_linear_up(lds_llama* L, LlTensors& T, const std::vector<std::pair<std:
             for (int k = 0; k < K; ++k) wt[(size_t)k * M + c0 + m] = w[(size_t)(r0 + m) * K + k];
         c0 += s.second;
     }
-    return L->up(wt);
-}
-float* ll_vec_up(lds_llama* L, LlTensors& T, const std::string& k, int64_t n) {
-    const float* p = T.get(k, n);
-    return p ? L->up(std::vector<float>(p, p + n)) : nullptr;
+    return T.o.upload(wt);
 }
 int ll_check_cfg(const lds_llama_cfg& c) {
     if (c.hidden < 1 || c.hidden > 2048 || c.inter < 1 || c.inter > 3840 || c.layers < 1 || c.max_pos < 2)
-        return ll_fail(LDS_EINVAL, "unsupported Llama shape (1 <= hidden <= 2048, 1 <= intermediate size <= 3840, layers >= 1, max_position_embeddings >= 2)");
-    if (c.head_dim < 16 || c.head_dim > kLlMaxHeadDim || c.head_dim % 16) return ll_fail(LDS_EINVAL, "head_dim %d must be a multiple of 16 in 16 .. %d", c.head_dim, kLlMaxHeadDim);
-    if (c.heads < 1 || c.kv_heads < 1 || c.heads % c.kv_heads) return ll_fail(LDS_EINVAL, "num_key_value_heads %d must divide num_attention_heads %d", c.kv_heads, c.heads);
-    if ((long long)c.heads * c.head_dim > 3840) return ll_fail(LDS_EINVAL, "heads * head_dim = %lld too wide (<= 3840)", (long long)c.heads * c.head_dim);
+        return set_error(LDS_EINVAL, "unsupported Llama shape (1 <= hidden <= 2048, 1 <= intermediate size <= 3840, layers >= 1, max_position_embeddings >= 2)");
+    if (c.head_dim < 16 || c.head_dim > kLlMaxHeadDim || c.head_dim % 16) return set_error(LDS_EINVAL, "head_dim %d must be a multiple of 16 in 16 .. %d", c.head_dim, kLlMaxHeadDim);
+    if (c.heads < 1 || c.kv_heads < 1 || c.heads % c.kv_heads) return set_error(LDS_EINVAL, "num_key_value_heads %d must divide num_attention_heads %d", c.kv_heads, c.heads);
+    if ((long long)c.heads * c.head_dim > 3840) return set_error(LDS_EINVAL, "heads * head_dim = %lld too wide (<= 3840)", (long long)c.heads * c.head_dim);
     if (c.first_free_id < 0 || c.vocab <= c.first_free_id || c.vocab - c.first_free_id > kLmMaxChoiceVocab)
-        return ll_fail(LDS_EINVAL, "the token choice takes 1 .. %d columns (vocab %d - first_free_id %d)", kLmMaxChoiceVocab, c.vocab, c.first_free_id);
+        return set_error(LDS_EINVAL, "the token choice takes 1 .. %d columns (vocab %d - first_free_id %d)", kLmMaxChoiceVocab, c.vocab, c.first_free_id);
     for (int id : {c.bos, c.eos, c.pad})
-        if (id < c.first_free_id || id >= c.vocab) return ll_fail(LDS_EINVAL, "bos / eos / pad id %d outside [first_free_id, vocab)", id);
-    if (!(c.eps > 0.f) || !(c.rope_theta > 0.f)) return ll_fail(LDS_EINVAL, "rms_norm_eps and rope_theta must be positive");
+        if (id < c.first_free_id || id >= c.vocab) return set_error(LDS_EINVAL, "bos / eos / pad id %d outside [first_free_id, vocab)", id);
+    if (!(c.eps > 0.f) || !(c.rope_theta > 0.f)) return set_error(LDS_EINVAL, "rms_norm_eps and rope_theta must be positive");
     return LDS_OK;
 }
 }  // namespace
 
 extern "C" int lds_llama_create(const lds_llama_cfg* cfg, int n, const char* const* names, const float* const* ptrs, const int64_t* numel, lds_llama** out) {
-    if (!cfg || !names || !ptrs || !numel || !out || n < 0) return ll_fail(LDS_EINVAL, "null argument");
+    if (!cfg || !names || !ptrs || !numel || !out || n < 0) return set_error(LDS_EINVAL, "null argument");
     if (int r = ll_check_cfg(*cfg)) return r;
     const lds_llama_cfg& c = *cfg;
-    LlTensors T;
-    for (int i = 0; i < n; ++i) T.m[names[i]] = {ptrs[i], numel[i]};
     lds_llama* L = new lds_llama();
     L->cfg = c;
+    WeightLoader T(L->own, n, names, ptrs, numel);
     const int H = c.hidden, d = c.head_dim, QD = c.heads * d, KD = c.kv_heads * d, hd = d / 2;
     const std::string p = "llama.model.";
-    bool ok = (L->embed = ll_vec_up(L, T, p + "embed_tokens.weight", (int64_t)c.vocab * H)) != nullptr;
+    bool ok = (L->embed = T.vec(p + "embed_tokens.weight", (int64_t)c.vocab * H)) != nullptr;
     for (int i = 0; i < c.layers && ok; ++i) {
         LlLayer y;
         const std::string q = p + "layers." + std::to_string(i) + ".";
-        y.nw_attn = ll_vec_up(L, T, q + "input_layernorm.weight", H);
-        y.wqkv = ll_linear_up(L, T, {{q + "self_attn.q_proj.weight", QD}, {q + "self_attn.k_proj.weight", KD}, {q + "self_attn.v_proj.weight", KD}}, H);
-        y.wo = ll_linear_up(L, T, {{q + "self_attn.o_proj.weight", H}}, QD);
-        y.nw_mlp = ll_vec_up(L, T, q + "post_attention_layernorm.weight", H);
-        y.wgate = ll_linear_up(L, T, {{q + "mlp.gate_proj.weight", c.inter}}, H);
-        y.wup = ll_linear_up(L, T, {{q + "mlp.up_proj.weight", c.inter}}, H);
-        y.wdown = ll_linear_up(L, T, {{q + "mlp.down_proj.weight", H}}, c.inter);
+        y.nw_attn = T.vec(q + "input_layernorm.weight", H);
+        y.wqkv = ll_linear_up(T, {{q + "self_attn.q_proj.weight", QD}, {q + "self_attn.k_proj.weight", KD}, {q + "self_attn.v_proj.weight", KD}}, H);
+        y.wo = ll_linear_up(T, {{q + "self_attn.o_proj.weight", H}}, QD);
+        y.nw_mlp = T.vec(q + "post_attention_layernorm.weight", H);
+        y.wgate = ll_linear_up(T, {{q + "mlp.gate_proj.weight", c.inter}}, H);
+        y.wup = ll_linear_up(T, {{q + "mlp.up_proj.weight", c.inter}}, H);
+        y.wdown = ll_linear_up(T, {{q + "mlp.down_proj.weight", H}}, c.inter);
         ok = y.nw_attn && y.wqkv && y.wo && y.nw_mlp && y.wgate && y.wup && y.wdown;
         L->layers.push_back(y);
     }
-    ok = ok && (L->nw_final = ll_vec_up(L, T, p + "norm.weight", H)) != nullptr;
+    ok = ok && (L->nw_final = T.vec(p + "norm.weight", H)) != nullptr;
     // the head's observable columns only: rows first_free_id .. vocab of lm_head.weight
-    ok = ok && (L->head = ll_linear_up(L, T, {{"llama.lm_head.weight", c.vocab - c.first_free_id}}, H, c.first_free_id, c.vocab)) != nullptr;
+    ok = ok && (L->head = ll_linear_up(T, {{"llama.lm_head.weight", c.vocab - c.first_free_id}}, H, c.first_free_id, c.vocab)) != nullptr;
     // and the columns below, which only scoring looks at (HF's log_softmax runs over the whole vocabulary): rows 0 .. first_free_id, a matrix of its own
-    if (c.first_free_id > 0) ok = ok && (L->head_lo = ll_linear_up(L, T, {{"llama.lm_head.weight", c.first_free_id}}, H, 0, c.vocab)) != nullptr;
+    if (c.first_free_id > 0) ok = ok && (L->head_lo = ll_linear_up(T, {{"llama.lm_head.weight", c.first_free_id}}, H, 0, c.vocab)) != nullptr;
     if (ok) {
         // HF LlamaRotaryEmbedding (default rope): angle = fp32(position) * inv_freq as an fp32 product, cos / sin of THAT angle.  inv_freq =
         // theta^(-2i/d) in fp32; a caller that has HF's own numbers hands them in (torch's vectorised pow is not correctly rounded, and one ulp
         // of inv_freq is 6e-5 rad at position 1000)
         std::vector<float> inv(hd), cs((size_t)c.max_pos * d);
-        auto it = T.m.find(p + "rotary_emb.inv_freq");
-        if (it != T.m.end() && it->second.second == hd) memcpy(inv.data(), it->second.first, sizeof(float) * hd);
+        if (const float* given = T.opt(p + "rotary_emb.inv_freq", hd)) memcpy(inv.data(), given, sizeof(float) * hd);
         else for (int i = 0; i < hd; ++i) inv[i] = 1.0f / powf(c.rope_theta, (float)(2 * i) / (float)d);
         for (int pos = 0; pos < c.max_pos; ++pos)
             for (int i = 0; i < hd; ++i) {
@@ -600,34 +570,16 @@ extern "C" int lds_llama_create(const lds_llama_cfg* cfg, int n, const char* con
                 cs[(size_t)pos * d + i] = (float)cos((double)ang);
                 cs[(size_t)pos * d + hd + i] = (float)sin((double)ang);
             }
-        ok = (L->cs = L->up(cs)) != nullptr;
+        ok = (L->cs = T.o.upload(cs)) != nullptr;
     }
-    if (!ok) {
-        const std::string miss = T.missing;
-        delete L;
-        if (!miss.empty()) return ll_fail(LDS_EMISSING, "Llama weight tensor %s (absent or wrong size)", miss.c_str());
-        return ll_fail(LDS_ENOMEM, "Llama weight upload failed");
-    }
-    *out = L;
-    return LDS_OK;
+    return T.finish(ok, "Llama", L, out, "Llama weight tensor");
 }
 extern "C" void lds_llama_destroy(lds_llama* L) { delete L; }
 
 namespace {
-struct LlArena {
-    char* base; size_t cap, used = 0; bool ok = true;
-    LlArena(void* p, size_t n) : base((char*)p), cap(n) {}
-    float* f(size_t n) {
-        const size_t bytes = (n * sizeof(float) + 255) & ~(size_t)255;
-        if (base && used + bytes > cap) ok = false;
-        char* p = base ? base + used : nullptr;
-        used += bytes;
-        return (float*)p;
-    }
-};
 struct LlWs { float *x, *q, *ctx, *ff, *logits; int* flags; int64_t* stok; int32_t* plen; std::vector<float*> kc, vc; };
 // rows of a pass: B * (P - 1) for the prefill (the prompts' positions but the last), B for a decode step
-void ll_plan(const lds_llama* L, LlArena& A, int B, int P, int cap, LlWs& w) {
+void ll_plan(const lds_llama* L, Arena& A, int B, int P, int cap, LlWs& w) {
     const lds_llama_cfg& c = L->cfg;
     const size_t N = (size_t)B * (P > 2 ? P - 1 : 1), QD = (size_t)c.heads * c.head_dim, KD = (size_t)c.kv_heads * c.head_dim;
     w.x = A.f(N * c.hidden); w.q = A.f(N * QD); w.ctx = A.f(N * QD); w.ff = A.f(N * c.inter);
@@ -640,9 +592,9 @@ void ll_plan(const lds_llama* L, LlArena& A, int B, int P, int cap, LlWs& w) {
 }
 // the shape checks, which need no model
 int ll_check_shape(int B, int P, int max_length) {
-    if (B <= 0 || P < 1 || max_length < 2) return ll_fail(LDS_EINVAL, "bad argument");
-    if (B > kLlMaxBatch) return ll_fail(LDS_EINVAL, "a Llama decode takes at most %d rows, got %d", kLlMaxBatch, B);
-    if (P > kLlMaxLength || max_length > kLlMaxLength) return ll_fail(LDS_EINVAL, "prompt width %d / max_length %d too long (<= %d)", P, max_length, kLlMaxLength);
+    if (B <= 0 || P < 1 || max_length < 2) return set_error(LDS_EINVAL, "bad argument");
+    if (B > kLlMaxBatch) return set_error(LDS_EINVAL, "a Llama decode takes at most %d rows, got %d", kLlMaxBatch, B);
+    if (P > kLlMaxLength || max_length > kLlMaxLength) return set_error(LDS_EINVAL, "prompt width %d / max_length %d too long (<= %d)", P, max_length, kLlMaxLength);
     return LDS_OK;
 }
 // the rows' prompt lengths (host): each inside 1 .. P and below max_length -> the longest and the shortest
@@ -650,8 +602,8 @@ int ll_check_lens(const int32_t* in_len, int B, int P, int max_length, int& Pmax
     Pmax = 0; Pmin = P;
     for (int b = 0; b < B; ++b) {
         const int pl = in_len ? in_len[b] : P;
-        if (pl < 1 || pl > P) return ll_fail(LDS_EINVAL, "in_len[%d] = %d out of range (1 .. P = %d)", b, pl, P);
-        if (pl >= max_length) return ll_fail(LDS_EINVAL, "in_len[%d] = %d leaves no room below max_length = %d (the total length, prompt included)", b, pl, max_length);
+        if (pl < 1 || pl > P) return set_error(LDS_EINVAL, "in_len[%d] = %d out of range (1 .. P = %d)", b, pl, P);
+        if (pl >= max_length) return set_error(LDS_EINVAL, "in_len[%d] = %d leaves no room below max_length = %d (the total length, prompt included)", b, pl, max_length);
         Pmax = pl > Pmax ? pl : Pmax;
         Pmin = pl < Pmin ? pl : Pmin;
     }
@@ -686,17 +638,17 @@ int ll_layers(const lds_llama* L, const LlWs& w, int N, const LlRows& rows, int 
     for (int i = 0; i < c.layers; ++i) {
         const LlLayer& y = L->layers[i];
         const LlRope rope{L->cs, w.kc[i], w.vc[i], c.heads, c.kv_heads, d, rows};
-        LL_HIP(ll_linear<LL_ROPE>(w.x, H, y.nw_attn, c.eps, y.wqkv, nullptr, QD + 2 * KD, nullptr, w.q, QD, N, st, &rope));
+        HIP_TRY(ll_linear<LL_ROPE>(w.x, H, y.nw_attn, c.eps, y.wqkv, nullptr, QD + 2 * KD, nullptr, w.q, QD, N, st, &rope));
         if (beam)      // (one more int per key in LDS: the key's source row)
             hipLaunchKernelGGL(ll_attn_beam_kernel, dim3((unsigned)(N * c.heads)), dim3(256), attn_lds + (size_t)Lkp * sizeof(int), st, (const float*)w.q,
                                (const float*)w.kc[i], (const float*)w.vc[i], rows, c.heads, c.kv_heads, d, Lkp, w.ctx, *beam);
         else
             hipLaunchKernelGGL(ll_attn_kernel, dim3((unsigned)(N * c.heads)), dim3(256), attn_lds, st, (const float*)w.q, (const float*)w.kc[i], (const float*)w.vc[i], rows,
                                c.heads, c.kv_heads, d, Lkp, w.ctx);
-        LL_HIP(hipGetLastError());
-        LL_HIP(ll_linear<LL_RESID>(w.ctx, QD, nullptr, c.eps, y.wo, nullptr, H, w.x, w.x, H, N, st));
-        LL_HIP(ll_linear<LL_SWIGLU>(w.x, H, y.nw_mlp, c.eps, y.wgate, y.wup, c.inter, nullptr, w.ff, c.inter, N, st));
-        LL_HIP(ll_linear<LL_RESID>(w.ff, c.inter, nullptr, c.eps, y.wdown, nullptr, H, w.x, w.x, H, N, st));
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(ll_linear<LL_RESID>(w.ctx, QD, nullptr, c.eps, y.wo, nullptr, H, w.x, w.x, H, N, st));
+        HIP_TRY(ll_linear<LL_SWIGLU>(w.x, H, y.nw_mlp, c.eps, y.wgate, y.wup, c.inter, nullptr, w.ff, c.inter, N, st));
+        HIP_TRY(ll_linear<LL_RESID>(w.ff, c.inter, nullptr, c.eps, y.wdown, nullptr, H, w.x, w.x, H, N, st));
     }
     return LDS_OK;
 }
@@ -704,8 +656,8 @@ int ll_layers(const lds_llama* L, const LlWs& w, int N, const LlRows& rows, int 
 
 extern "C" int lds_llama_workspace_bytes(const lds_llama* L, int B, int P, int max_length, size_t* out) {
     if (int r = ll_check_shape(B, P, max_length)) return r;
-    if (!L || !out) return ll_fail(LDS_EINVAL, "bad argument");
-    LlArena A(nullptr, 0);
+    if (!L || !out) return set_error(LDS_EINVAL, "bad argument");
+    Arena A(nullptr, 0);
     LlWs w;
     ll_plan(L, A, B, P, max_length, w);
     *out = A.used;
@@ -714,47 +666,47 @@ extern "C" int lds_llama_workspace_bytes(const lds_llama* L, int B, int P, int m
 
 extern "C" int lds_llama_generate(lds_llama* L, const int64_t* input_ids, const int32_t* in_len, int B, int P, int max_length, const lds_lm_decode_opts* opts,
                                   const float* uniforms, int64_t* tokens, float* logits_out, int* n_tokens_host, void* ws, size_t ws_bytes, void* stream) {
-    if (!opts) return ll_fail(LDS_EINVAL, "null options");
+    if (!opts) return set_error(LDS_EINVAL, "null options");
     const lds_lm_decode_opts o = *opts;
     if (int r = lm_check_opts(o, logits_out)) return r;
-    if (o.num_beams != 1) return ll_fail(LDS_EINVAL, "lds_llama_generate takes num_beams 1; beam search over the whole vocabulary is lds_llama_generate_beam");
+    if (o.num_beams != 1) return set_error(LDS_EINVAL, "lds_llama_generate takes num_beams 1; beam search over the whole vocabulary is lds_llama_generate_beam");
     if (int r = ll_check_shape(B, P, max_length)) return r;
     int Pmax = 0, Pmin = P;
     if (int r = ll_check_lens(in_len, B, P, max_length, Pmax, Pmin)) return r;
-    if (!L || !input_ids || !tokens || !n_tokens_host || !ws) return ll_fail(LDS_EINVAL, "bad argument");
+    if (!L || !input_ids || !tokens || !n_tokens_host || !ws) return set_error(LDS_EINVAL, "bad argument");
     const lds_llama_cfg& c = L->cfg;
     const int H = c.hidden, V = c.vocab - c.first_free_id, shift = c.first_free_id;
     if (o.do_sample && (!uniforms || o.top_k < 0 || o.top_k > kLmMaxTopK || o.top_k > V || !(o.top_p > 0.f) || !(o.temperature > 0.f)))
-        return ll_fail(LDS_EINVAL, "sampling needs uniforms, 0 <= top_k <= %d (0 = no top-k filter), top_p > 0, temperature > 0", kLmMaxTopK);
-    if (max_length > c.max_pos) return ll_fail(LDS_EINVAL, "max_length %d exceeds max_position_embeddings %d", max_length, c.max_pos);
+        return set_error(LDS_EINVAL, "sampling needs uniforms, 0 <= top_k <= %d (0 = no top-k filter), top_p > 0, temperature > 0", kLmMaxTopK);
+    if (max_length > c.max_pos) return set_error(LDS_EINVAL, "max_length %d exceeds max_position_embeddings %d", max_length, c.max_pos);
     hipStream_t st = (hipStream_t)stream;
-    LlArena A(ws, ws_bytes);
+    Arena A(ws, ws_bytes);
     LlWs w;
     ll_plan(L, A, B, P, max_length, w);
-    if (!A.ok) return ll_fail(LDS_ENOMEM, "Llama workspace too small: need %zu bytes", A.used);
+    if (!A.ok) return set_error(LDS_ENOMEM, "Llama workspace too small: need %zu bytes", A.used);
     int* unfinished = w.flags;                       // [B]
     int* any_unf = w.flags + B;                      // [max_length]: 1 when a row is still running after global step s
     int* rowlen = w.flags + B + max_length;          // [B <= 64]: every row's final length, prompt included
     {
         std::vector<int> init(B + max_length + kLlMaxBatch, 0), pl(B);
         for (int b = 0; b < B; ++b) { init[b] = 1; init[B + max_length + b] = max_length; pl[b] = in_len ? in_len[b] : P; }
-        LL_HIP(hipMemcpyAsync(unfinished, init.data(), sizeof(int) * init.size(), hipMemcpyHostToDevice, st));
-        LL_HIP(hipMemcpyAsync(w.plen, pl.data(), sizeof(int) * B, hipMemcpyHostToDevice, st));
-        LL_HIP(hipStreamSynchronize(st));      // the host staging vectors go out of scope
+        HIP_TRY(hipMemcpyAsync(unfinished, init.data(), sizeof(int) * init.size(), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(w.plen, pl.data(), sizeof(int) * B, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipStreamSynchronize(st));      // the host staging vectors go out of scope
     }
     const int32_t* plen = w.plen;
     const int pad_s = c.pad - shift, eos_s = c.eos - shift;
     hipLaunchKernelGGL(ll_init_kernel, dim3(B), dim3(256), 0, st, input_ids, P, plen, c.vocab, shift, pad_s, max_length, w.stok);
-    LL_HIP(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     // Prefill: the positions 0 .. Pq - 1 (Pq = the longest prompt - 1) of every row in one causal pass that fills the decode's caches; the head is
     // skipped.  A shorter row's slots in_len[b] - 1 .. Pq - 1 are filled from PAD; no query ever sees them: step s of row b first overwrites slot
     // in_len[b] - 1 + s with the row's real token and then reads the slots 0 .. in_len[b] - 1 + s.  The same covers the workspace's contents on entry.
     const int Pq = Pmax - 1;
     if (Pq > 0) {
-        if ((long long)B * Pq > 8 * 65535LL) return ll_fail(LDS_EINVAL, "B * P too large for the prefill (<= 524280)");
+        if ((long long)B * Pq > 8 * 65535LL) return set_error(LDS_EINVAL, "B * P too large for the prefill (<= 524280)");
         const LlRows rows{plen, Pq, 0, max_length};
         hipLaunchKernelGGL(ll_embed_kernel, dim3(B * Pq), dim3(256), 0, st, (const float*)L->embed, (const int64_t*)w.stok, rows, shift, c.vocab, H, w.x);
-        LL_HIP(hipGetLastError());
+        HIP_TRY(hipGetLastError());
         if (int r = ll_layers(L, w, B * Pq, rows, Pq, st)) return r;
     }
     const float inv_temp = o.do_sample ? 1.0f / o.temperature : 1.0f;
@@ -764,16 +716,16 @@ extern "C" int lds_llama_generate(lds_llama* L, const int64_t* input_ids, const 
     for (int step = 0; step < n_steps; ++step) {
         const LlRows rows{plen, 0, step, max_length};
         hipLaunchKernelGGL(ll_embed_kernel, dim3(B), dim3(256), 0, st, (const float*)L->embed, (const int64_t*)w.stok, rows, shift, c.vocab, H, w.x);
-        LL_HIP(hipGetLastError());
+        HIP_TRY(hipGetLastError());
         const int Lk_max = (Pmax + step < max_length) ? Pmax + step : max_length;
         if (int r = ll_layers(L, w, B, rows, Lk_max, st)) return r;
         float* lg = logits_out ? logits_out + (size_t)step * B * V : w.logits;
-        LL_HIP(ll_linear<LL_PLAIN>(w.x, H, L->nw_final, c.eps, L->head, nullptr, V, nullptr, lg, V, B, st));
-        LL_HIP(lm_launch_choice_rows(o, B, V, lg, inv_temp, o.do_sample ? uniforms + (size_t)step * B : nullptr, w.stok, max_length, step, unfinished, eos_s, pad_s,
+        HIP_TRY(ll_linear<LL_PLAIN>(w.x, H, L->nw_final, c.eps, L->head, nullptr, V, nullptr, lg, V, B, st));
+        HIP_TRY(lm_launch_choice_rows(o, B, V, lg, inv_temp, o.do_sample ? uniforms + (size_t)step * B : nullptr, w.stok, max_length, step, unfinished, eos_s, pad_s,
                                      any_unf, nullptr, nullptr, nullptr, nullptr, c.eps, H, nullptr, plen, rowlen, st));
         if ((step & 7) == 7 || step + 1 == n_steps) {      // the EOS poll; a row that reached max_length counts as finished
-            LL_HIP(hipMemcpyAsync(host_flags.data() + checked, any_unf + checked, sizeof(int) * (step + 1 - checked), hipMemcpyDeviceToHost, st));
-            LL_HIP(hipStreamSynchronize(st));
+            HIP_TRY(hipMemcpyAsync(host_flags.data() + checked, any_unf + checked, sizeof(int) * (step + 1 - checked), hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
             bool done = false;
             for (int s = checked; s <= step && !done; ++s) done = host_flags[s] == 0;
             checked = step + 1;
@@ -782,10 +734,10 @@ extern "C" int lds_llama_generate(lds_llama* L, const int64_t* input_ids, const 
     }
     const long long total = (long long)B * max_length;
     hipLaunchKernelGGL(ll_finish_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const int64_t*)w.stok, total, shift, tokens);
-    LL_HIP(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     std::vector<int> len(B, 0);
-    LL_HIP(hipMemcpyAsync(len.data(), rowlen, sizeof(int) * B, hipMemcpyDeviceToHost, st));
-    LL_HIP(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpyAsync(len.data(), rowlen, sizeof(int) * B, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     int n_tokens = 0;
     for (int b = 0; b < B; ++b) n_tokens = len[b] > n_tokens ? len[b] : n_tokens;
     *n_tokens_host = n_tokens;
@@ -798,7 +750,7 @@ extern "C" int lds_llama_generate(lds_llama* L, const int64_t* input_ids, const 
 namespace {
 constexpr int kLlScoreChunk = 256;
 struct LlScoreWs { LlWs w; float* chunk; double* psum; int32_t* pcnt; };
-void ll_score_plan(const lds_llama* L, LlArena& A, int B, int S, LlScoreWs& s) {
+void ll_score_plan(const lds_llama* L, Arena& A, int B, int S, LlScoreWs& s) {
     const lds_llama_cfg& c = L->cfg;
     const size_t N = (size_t)B * S, QD = (size_t)c.heads * c.head_dim, KD = (size_t)c.kv_heads * c.head_dim;
     LlWs& w = s.w;
@@ -813,20 +765,20 @@ void ll_score_plan(const lds_llama* L, LlArena& A, int B, int S, LlScoreWs& s) {
 }
 // the shape checks that need no model, then the model's
 int ll_score_check(const lds_llama* L, int B, int S) {
-    if (B < 1) return ll_fail(LDS_EINVAL, "scoring needs B >= 1, got %d", B);
-    if (S < 2 || S > kLlMaxLength) return ll_fail(LDS_EINVAL, "stream length %d out of range for scoring (2 .. %d)", S, kLlMaxLength);
+    if (B < 1) return set_error(LDS_EINVAL, "scoring needs B >= 1, got %d", B);
+    if (S < 2 || S > kLlMaxLength) return set_error(LDS_EINVAL, "stream length %d out of range for scoring (2 .. %d)", S, kLlMaxLength);
     // the linears take 8 rows per workgroup along grid.y
-    if ((long long)B * S > 8 * 65535LL) return ll_fail(LDS_EINVAL, "batch too large for one scoring call (B * S <= 524280, got %lld)", (long long)B * S);
-    if (!L) return ll_fail(LDS_EINVAL, "null handle");
-    if (S > L->cfg.max_pos) return ll_fail(LDS_EINVAL, "stream length %d exceeds max_position_embeddings %d", S, L->cfg.max_pos);
+    if ((long long)B * S > 8 * 65535LL) return set_error(LDS_EINVAL, "batch too large for one scoring call (B * S <= 524280, got %lld)", (long long)B * S);
+    if (!L) return set_error(LDS_EINVAL, "null handle");
+    if (S > L->cfg.max_pos) return set_error(LDS_EINVAL, "stream length %d exceeds max_position_embeddings %d", S, L->cfg.max_pos);
     return LDS_OK;
 }
 }  // namespace
 
 extern "C" int lds_llama_score_workspace_bytes(const lds_llama* L, int B, int S, size_t* out) {
     if (int r = ll_score_check(L, B, S)) return r;
-    if (!out) return ll_fail(LDS_EINVAL, "bad argument");
-    LlArena A(nullptr, 0);
+    if (!out) return set_error(LDS_EINVAL, "bad argument");
+    Arena A(nullptr, 0);
     LlScoreWs s;
     ll_score_plan(L, A, B, S, s);
     *out = A.used;
@@ -836,22 +788,22 @@ extern "C" int lds_llama_score_workspace_bytes(const lds_llama* L, int B, int S,
 extern "C" int lds_llama_score(lds_llama* L, const int64_t* input_ids, const int32_t* ids_len, const int64_t* labels, int B, int S, float* logprobs, int32_t* ranks,
                                float* loss, int32_t* n_counted, float* logits_out, void* ws, size_t ws_bytes, void* stream) {
     if (int r = ll_score_check(L, B, S)) return r;
-    if (!input_ids || !logprobs || !ranks || !loss || !n_counted || !ws) return ll_fail(LDS_EINVAL, "null argument");
+    if (!input_ids || !logprobs || !ranks || !loss || !n_counted || !ws) return set_error(LDS_EINVAL, "null argument");
     const lds_llama_cfg& c = L->cfg;
     hipStream_t st = (hipStream_t)stream;
-    LlArena A(ws, ws_bytes);
+    Arena A(ws, ws_bytes);
     LlScoreWs s;
     ll_score_plan(L, A, B, S, s);
-    if (!A.ok) return ll_fail(LDS_ENOMEM, "Llama scoring workspace too small: need %zu bytes", A.used);
+    if (!A.ok) return set_error(LDS_ENOMEM, "Llama scoring workspace too small: need %zu bytes", A.used);
     const int H = c.hidden, V = c.vocab, lo = c.first_free_id, N = B * S;
     if (!labels) labels = input_ids;      // the loader's choice (dataloader.py:182-183)
     // slots at and beyond a row's length are filled from PAD, as in the prefill: their rows are computed and never counted, and no counted
     // row's query sees their keys (row l reads the slots 0 .. l)
     hipLaunchKernelGGL(ll_score_init_kernel, dim3(B), dim3(256), 0, st, input_ids, S, ids_len, c.vocab, lo, c.pad - lo, s.w.stok);
-    LL_HIP(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     const LlRows rows{nullptr, S, 0, S};
     hipLaunchKernelGGL(ll_embed_kernel, dim3(N), dim3(256), 0, st, (const float*)L->embed, (const int64_t*)s.w.stok, rows, lo, c.vocab, H, s.w.x);
-    LL_HIP(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     if (int r = ll_layers(L, s.w, N, rows, S, st)) return r;
     for (int r0 = 0; r0 < N; r0 += kLlScoreChunk) {
         const int nr = (N - r0 < kLlScoreChunk) ? N - r0 : kLlScoreChunk;
@@ -859,11 +811,11 @@ extern "C" int lds_llama_score(lds_llama* L, const int64_t* input_ids, const int
         float* lg = logits_out ? logits_out + (size_t)r0 * V : s.chunk;
         // rows of width vocab: the low columns from their own matrix, the columns first_free_id .. by the decode's launch -- the same fmaf chain per
         // output, only the column's address differs
-        if (lo > 0) LL_HIP(ll_linear<LL_PLAIN>(x, H, L->nw_final, c.eps, L->head_lo, nullptr, lo, nullptr, lg, V, nr, st));
-        LL_HIP(ll_linear<LL_PLAIN>(x, H, L->nw_final, c.eps, L->head, nullptr, V - lo, nullptr, lg + lo, V, nr, st));
-        LL_HIP(lm_launch_score_rows(lg, r0, nr, V, S, labels, ids_len, logprobs, ranks, st));
+        if (lo > 0) HIP_TRY(ll_linear<LL_PLAIN>(x, H, L->nw_final, c.eps, L->head_lo, nullptr, lo, nullptr, lg, V, nr, st));
+        HIP_TRY(ll_linear<LL_PLAIN>(x, H, L->nw_final, c.eps, L->head, nullptr, V - lo, nullptr, lg + lo, V, nr, st));
+        HIP_TRY(lm_launch_score_rows(lg, r0, nr, V, S, labels, ids_len, logprobs, ranks, st));
     }
-    LL_HIP(lm_launch_score_loss(logprobs, ranks, B, S - 1, s.psum, s.pcnt, loss, n_counted, st));
+    HIP_TRY(lm_launch_score_loss(logprobs, ranks, B, S - 1, s.psum, s.pcnt, loss, n_counted, st));
     return LDS_OK;
 }
 
@@ -879,7 +831,7 @@ constexpr int kLlMaxBeamRows = 256;        // B * num_beams
 constexpr int kLlMaxBeamLength = 7488;     // the beam attention stages a score and a source row per key in LDS
 constexpr int kLlBeamPoll = 8;             // steps between two polls of the flag bits
 struct LlBeamWs { LlWs w; int64_t *rseq[2], *fseq[2]; int* tab[2]; float *rscore, *fscore; int *ffin, *flen, *unsat, *ended, *flags, *rowlen; int32_t* plen_rows; };
-void ll_beam_plan(const lds_llama* L, LlArena& A, int B, int P, int cap, int K, LlBeamWs& s) {
+void ll_beam_plan(const lds_llama* L, Arena& A, int B, int P, int cap, int K, LlBeamWs& s) {
     const lds_llama_cfg& c = L->cfg;
     const size_t R = (size_t)B * K, Npre = (size_t)B * (P > 2 ? P - 1 : 1), N = Npre > R ? Npre : R;
     const size_t QD = (size_t)c.heads * c.head_dim, KD = (size_t)c.kv_heads * c.head_dim;
@@ -898,25 +850,25 @@ void ll_beam_plan(const lds_llama* L, LlArena& A, int B, int P, int cap, int K, 
 }
 // the checks that need no model
 int ll_beam_check_shape(int B, int P, int max_length, int K) {
-    if (K < 2 || K > kMaxBeams) return ll_fail(LDS_EINVAL, "num_beams %d out of range for a beam decode (2 .. %d)", K, kMaxBeams);
+    if (K < 2 || K > kMaxBeams) return set_error(LDS_EINVAL, "num_beams %d out of range for a beam decode (2 .. %d)", K, kMaxBeams);
     if (int r = ll_check_shape(B, P, max_length)) return r;
-    if ((long long)B * K > kLlMaxBeamRows) return ll_fail(LDS_EINVAL, "a Llama beam decode takes at most %d beam rows, got B * num_beams = %d", kLlMaxBeamRows, B * K);
-    if (max_length > kLlMaxBeamLength) return ll_fail(LDS_EINVAL, "max_length %d too long for a beam decode (<= %d)", max_length, kLlMaxBeamLength);
+    if ((long long)B * K > kLlMaxBeamRows) return set_error(LDS_EINVAL, "a Llama beam decode takes at most %d beam rows, got B * num_beams = %d", kLlMaxBeamRows, B * K);
+    if (max_length > kLlMaxBeamLength) return set_error(LDS_EINVAL, "max_length %d too long for a beam decode (<= %d)", max_length, kLlMaxBeamLength);
     return LDS_OK;
 }
 int ll_beam_check_model(const lds_llama* L, int K, int max_length) {
     const lds_llama_cfg& c = L->cfg;
-    if (c.vocab > kMaxBeamVocab) return ll_fail(LDS_EINVAL, "beam search is built for vocabularies of at most %d entries, got %d", kMaxBeamVocab, c.vocab);
-    if (c.vocab - c.first_free_id < 2 * K) return ll_fail(LDS_EINVAL, "beam search needs 2 * num_beams = %d ids that are not banned, got %d", 2 * K, c.vocab - c.first_free_id);
-    if (max_length > c.max_pos) return ll_fail(LDS_EINVAL, "max_length %d exceeds max_position_embeddings %d", max_length, c.max_pos);
+    if (c.vocab > kMaxBeamVocab) return set_error(LDS_EINVAL, "beam search is built for vocabularies of at most %d entries, got %d", kMaxBeamVocab, c.vocab);
+    if (c.vocab - c.first_free_id < 2 * K) return set_error(LDS_EINVAL, "beam search needs 2 * num_beams = %d ids that are not banned, got %d", 2 * K, c.vocab - c.first_free_id);
+    if (max_length > c.max_pos) return set_error(LDS_EINVAL, "max_length %d exceeds max_position_embeddings %d", max_length, c.max_pos);
     return LDS_OK;
 }
 }  // namespace
 
 extern "C" int lds_llama_beam_workspace_bytes(const lds_llama* L, int B, int P, int max_length, int num_beams, size_t* out) {
     if (int r = ll_beam_check_shape(B, P, max_length, num_beams)) return r;
-    if (!L || !out) return ll_fail(LDS_EINVAL, "bad argument");
-    LlArena A(nullptr, 0);
+    if (!L || !out) return set_error(LDS_EINVAL, "bad argument");
+    Arena A(nullptr, 0);
     LlBeamWs s;
     ll_beam_plan(L, A, B, P, max_length, num_beams, s);
     *out = A.used;
@@ -927,57 +879,57 @@ namespace {
 // the decode; poll = the steps between two polls (the public entry's is fixed; a test entry varies it to show that the result does not depend on it)
 int ll_generate_beam(lds_llama* L, const int64_t* input_ids, const int32_t* in_len, int B, int P, int max_length, const lds_lm_decode_opts* opts, int64_t* tokens,
                      int* n_tokens_host, void* ws, size_t ws_bytes, void* stream, int poll) {
-    if (!opts) return ll_fail(LDS_EINVAL, "null options");
+    if (!opts) return set_error(LDS_EINVAL, "null options");
     const lds_lm_decode_opts o = *opts;
     if (int r = lm_check_opts(o, nullptr)) return r;
-    if (o.do_sample) return ll_fail(LDS_EINVAL, "beam sampling (do_sample with beams) is not built: only greedy beam search");
+    if (o.do_sample) return set_error(LDS_EINVAL, "beam sampling (do_sample with beams) is not built: only greedy beam search");
     const int K = o.num_beams;
     if (int r = ll_beam_check_shape(B, P, max_length, K)) return r;
     int Pmax = 0, Pmin = P;
     if (int r = ll_check_lens(in_len, B, P, max_length, Pmax, Pmin)) return r;
-    if (!L || !input_ids || !tokens || !n_tokens_host || !ws) return ll_fail(LDS_EINVAL, "bad argument");
+    if (!L || !input_ids || !tokens || !n_tokens_host || !ws) return set_error(LDS_EINVAL, "bad argument");
     if (int r = ll_beam_check_model(L, K, max_length)) return r;
     const lds_llama_cfg& c = L->cfg;
     const int H = c.hidden, V = c.vocab, lo = c.first_free_id, R = B * K, cap = max_length;
     const int Pq = Pmax - 1;
-    if ((long long)B * Pq > 8 * 65535LL) return ll_fail(LDS_EINVAL, "B * P too large for the prefill (<= 524280)");
+    if ((long long)B * Pq > 8 * 65535LL) return set_error(LDS_EINVAL, "B * P too large for the prefill (<= 524280)");
     hipStream_t st = (hipStream_t)stream;
-    LlArena A(ws, ws_bytes);
+    Arena A(ws, ws_bytes);
     LlBeamWs s;
     ll_beam_plan(L, A, B, P, max_length, K, s);
-    if (!A.ok) return ll_fail(LDS_ENOMEM, "Llama beam workspace too small: need %zu bytes", A.used);
+    if (!A.ok) return set_error(LDS_ENOMEM, "Llama beam workspace too small: need %zu bytes", A.used);
     const LlWs& w = s.w;
     {
         std::vector<int> pl(B), plr(R);
         for (int b = 0; b < B; ++b) pl[b] = in_len ? in_len[b] : P;
         for (int r = 0; r < R; ++r) plr[r] = pl[r / K];
-        LL_HIP(hipMemcpyAsync(w.plen, pl.data(), sizeof(int) * B, hipMemcpyHostToDevice, st));
-        LL_HIP(hipMemcpyAsync(s.plen_rows, plr.data(), sizeof(int) * R, hipMemcpyHostToDevice, st));
-        LL_HIP(hipStreamSynchronize(st));      // the host staging vectors go out of scope
+        HIP_TRY(hipMemcpyAsync(w.plen, pl.data(), sizeof(int) * B, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(s.plen_rows, plr.data(), sizeof(int) * R, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipStreamSynchronize(st));      // the host staging vectors go out of scope
     }
     const int32_t* plen = w.plen;
-    LL_HIP(hipMemsetAsync(s.flags, 0, sizeof(int) * cap, st));
+    HIP_TRY(hipMemsetAsync(s.flags, 0, sizeof(int) * cap, st));
     // Prefill: lds_llama_generate's own, B rows into cache rows 0 .. B - 1 (the ids, not shifted, wait in the first B rows of a sequence buffer
     // that the init kernel below fills afterwards); then item b's keys and values move to cache row b * K.  A shorter row's slots in_len[b] - 1 ..
     // Pq - 1 are filled from PAD and overwritten by the item's first beam row (which IS cache row b * K) before any query reads them.
     if (Pq > 0) {
         hipLaunchKernelGGL(ll_init_kernel, dim3(B), dim3(256), 0, st, input_ids, P, plen, V, 0, c.pad, cap, s.rseq[1]);
-        LL_HIP(hipGetLastError());
+        HIP_TRY(hipGetLastError());
         const LlRows rows{plen, Pq, 0, cap};
         hipLaunchKernelGGL(ll_embed_kernel, dim3(B * Pq), dim3(256), 0, st, (const float*)L->embed, (const int64_t*)s.rseq[1], rows, 0, V, H, w.x);
-        LL_HIP(hipGetLastError());
+        HIP_TRY(hipGetLastError());
         if (int r = ll_layers(L, w, B * Pq, rows, Pq, st)) return r;
         if (B > 1) {
             const long long elems = (long long)c.kv_heads * Pq * c.head_dim;
             for (int i = 0; i < c.layers; ++i)
                 hipLaunchKernelGGL(ll_beam_spread_kernel, dim3((unsigned)((elems + 255) / 256), 2), dim3(256), 0, st, w.kc[i], w.vc[i], B, K, c.kv_heads, cap,
                                    c.head_dim, Pq);
-            LL_HIP(hipGetLastError());
+            HIP_TRY(hipGetLastError());
         }
     }
     hipLaunchKernelGGL(ll_beam_init_kernel, dim3(R), dim3(256), 0, st, input_ids, P, plen, V, c.pad, cap, K, s.rseq[0], s.rseq[1], s.fseq[0], s.fseq[1], s.rscore,
                        s.fscore, s.ffin, s.flen, s.unsat, s.ended);
-    LL_HIP(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     const int n_steps = max_length - Pmin;      // the shortest row's candidates all hit max_length at step n_steps - 1
     std::vector<int> host_flags(n_steps, 0);
     int checked = 0, last = 0;
@@ -986,20 +938,20 @@ int ll_generate_beam(lds_llama* L, const int64_t* input_ids, const int32_t* in_l
         last = step;
         const LlRows rows{s.plen_rows, 0, step, cap};
         hipLaunchKernelGGL(ll_embed_kernel, dim3(R), dim3(256), 0, st, (const float*)L->embed, (const int64_t*)s.rseq[cur], rows, 0, V, H, w.x);
-        LL_HIP(hipGetLastError());
+        HIP_TRY(hipGetLastError());
         const int Lk_max = (Pmax + step < max_length) ? Pmax + step : max_length;
         const LlBeamAttn ba{s.tab[cur], s.ended, cap, K};
         if (int r = ll_layers(L, w, R, rows, Lk_max, st, &ba)) return r;
         // rows of width vocab, as lds_llama_score forms them: the low columns from their own matrix, the others by the decode's launch
-        if (lo > 0) LL_HIP(ll_linear<LL_PLAIN>(w.x, H, L->nw_final, c.eps, L->head_lo, nullptr, lo, nullptr, w.logits, V, R, st));
-        LL_HIP(ll_linear<LL_PLAIN>(w.x, H, L->nw_final, c.eps, L->head, nullptr, V - lo, nullptr, w.logits + lo, V, R, st));
+        if (lo > 0) HIP_TRY(ll_linear<LL_PLAIN>(w.x, H, L->nw_final, c.eps, L->head_lo, nullptr, lo, nullptr, w.logits, V, R, st));
+        HIP_TRY(ll_linear<LL_PLAIN>(w.x, H, L->nw_final, c.eps, L->head, nullptr, V - lo, nullptr, w.logits + lo, V, R, st));
         const LmBeamState bs{s.rseq[cur], s.rseq[nxt], s.rscore, s.rscore, s.tab[cur], s.tab[nxt], s.fseq[cur], s.fseq[nxt], s.fscore, s.fscore, s.ffin, s.ffin,
                              s.flen, s.flen, s.unsat, s.unsat, nullptr, nullptr, s.flags + step};
         const LmBeamRows rw{plen, lo, s.ended, s.ended, cap};
-        LL_HIP(lm_launch_beam_rows(B, K, V, w.logits, step, cap, max_length, c.eos, o.repetition_penalty, o.no_repeat_ngram_size, o.early_stopping, bs, rw, st));
+        HIP_TRY(lm_launch_beam_rows(B, K, V, w.logits, step, cap, max_length, c.eos, o.repetition_penalty, o.no_repeat_ngram_size, o.early_stopping, bs, rw, st));
         if ((step + 1) % poll == 0 || step + 1 == n_steps) {      // the poll: bit 16 = some item's own loop still runs
-            LL_HIP(hipMemcpyAsync(host_flags.data() + checked, s.flags + checked, sizeof(int) * (step + 1 - checked), hipMemcpyDeviceToHost, st));
-            LL_HIP(hipStreamSynchronize(st));
+            HIP_TRY(hipMemcpyAsync(host_flags.data() + checked, s.flags + checked, sizeof(int) * (step + 1 - checked), hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
             bool done = false;
             for (int q = checked; q <= step && !done; ++q) done = !(host_flags[q] & 16);
             checked = step + 1;
@@ -1008,10 +960,10 @@ int ll_generate_beam(lds_llama* L, const int64_t* input_ids, const int32_t* in_l
     }
     // every item is frozen in both buffers from the step after its end on; the last step run wrote buffer (last + 1) & 1
     hipLaunchKernelGGL(ll_beam_finish_kernel, dim3(B), dim3(256), 0, st, (const int64_t*)s.fseq[(last + 1) & 1], (const int*)s.flen, plen, K, cap, c.pad, tokens, s.rowlen);
-    LL_HIP(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     std::vector<int> len(B, 0);
-    LL_HIP(hipMemcpyAsync(len.data(), s.rowlen, sizeof(int) * B, hipMemcpyDeviceToHost, st));
-    LL_HIP(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpyAsync(len.data(), s.rowlen, sizeof(int) * B, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     int n_tokens = 0;
     for (int b = 0; b < B; ++b) n_tokens = len[b] > n_tokens ? len[b] : n_tokens;
     *n_tokens_host = n_tokens;
@@ -1029,7 +981,7 @@ extern "C" int lds_llama_generate_beam(lds_llama* L, const int64_t* input_ids, c
 // given state; item b is at cur_len = prompt_len[b] + step.  lds_test_llama_beam_attn: ONE attention call over given q and caches.
 extern "C" int lds_test_llama_generate_beam_poll(lds_llama* L, const int64_t* input_ids, const int32_t* in_len, int B, int P, int max_length,
                                                  const lds_lm_decode_opts* opts, int64_t* tokens, int* n_tokens_host, void* ws, size_t ws_bytes, void* stream, int poll) {
-    if (poll < 1) return ll_fail(LDS_EINVAL, "poll interval %d (>= 1)", poll);
+    if (poll < 1) return set_error(LDS_EINVAL, "poll interval %d (>= 1)", poll);
     return ll_generate_beam(L, input_ids, in_len, B, P, max_length, opts, tokens, n_tokens_host, ws, ws_bytes, stream, poll);
 }
 extern "C" int lds_test_llama_beam_step(const float* logits, int B, int K, int V, int step, int max_length, int eos, float repetition_penalty,
@@ -1040,15 +992,15 @@ extern "C" int lds_test_llama_beam_step(const float* logits, int B, int K, int V
                                         int32_t* ended_out, int32_t* flag_out, void* stream) {
     if (!logits || !prompt_len || !ended || !run_seq || !run_score || !fin_seq || !fin_score || !fin_flag || !fin_len || !unsat || !run_seq_out || !run_score_out ||
         !parent_out || !fin_seq_out || !fin_score_out || !fin_flag_out || !fin_len_out || !unsat_out || !ended_out || !flag_out)
-        return ll_fail(LDS_EINVAL, "null argument");
+        return set_error(LDS_EINVAL, "null argument");
     if (B <= 0 || B > kLlMaxBeamRows || K < 1 || K > kMaxBeams || V > kMaxBeamVocab || first_free_id < 0 || V - first_free_id < 2 * K || step < 0 ||
         no_repeat_ngram_size < 0 || early_stopping < 0 || early_stopping > 2)
-        return ll_fail(LDS_EINVAL, "bad argument");
+        return set_error(LDS_EINVAL, "bad argument");
     for (int b = 0; b < B; ++b)      // a running item writes slot prompt_len[b] + step
-        if (prompt_len[b] < 1 || (!ended[b] && prompt_len[b] + step >= max_length)) return ll_fail(LDS_EINVAL, "prompt_len[%d] + step outside the sequences", b);
+        if (prompt_len[b] < 1 || (!ended[b] && prompt_len[b] + step >= max_length)) return set_error(LDS_EINVAL, "prompt_len[%d] + step outside the sequences", b);
     hipStream_t st = (hipStream_t)stream;
     int* dev = nullptr;      // prompt_len [B] | ended [B]
-    if (hipMalloc((void**)&dev, sizeof(int) * 2 * B) != hipSuccess) return ll_fail(LDS_ENOMEM, "hipMalloc");
+    if (hipMalloc((void**)&dev, sizeof(int) * 2 * B) != hipSuccess) return set_error(LDS_ENOMEM, "hipMalloc");
     int rc = LDS_OK;
     const LmBeamState bs{run_seq, run_seq_out, run_score, run_score_out, nullptr, nullptr, fin_seq, fin_seq_out, fin_score, fin_score_out, fin_flag, fin_flag_out,
                          fin_len, fin_len_out, unsat, unsat_out, parent_out, nullptr, flag_out};
@@ -1056,42 +1008,42 @@ extern "C" int lds_test_llama_beam_step(const float* logits, int B, int K, int V
     if (hipMemcpyAsync(dev, prompt_len, sizeof(int) * B, hipMemcpyHostToDevice, st) != hipSuccess ||
         hipMemcpyAsync(dev + B, ended, sizeof(int) * B, hipMemcpyHostToDevice, st) != hipSuccess || hipMemsetAsync(flag_out, 0, sizeof(int32_t), st) != hipSuccess ||
         lm_launch_beam_rows(B, K, V, logits, step, max_length, max_length, eos, repetition_penalty, no_repeat_ngram_size, early_stopping, bs, rw, st) != hipSuccess)
-        rc = ll_fail(LDS_EHIP, "launch");
-    if (hipStreamSynchronize(st) != hipSuccess) rc = ll_fail(LDS_EHIP, "sync");
+        rc = set_error(LDS_EHIP, "launch");
+    if (hipStreamSynchronize(st) != hipSuccess) rc = set_error(LDS_EHIP, "sync");
     (void)hipFree(dev);
     return rc;
 }
 extern "C" int lds_test_llama_beam_attn(const float* q, const float* kc, const float* vc, const int32_t* tab, const int32_t* prompt_len, int R, int K, int heads,
                                         int kv_heads, int d, int cap, int tcap, int step, float* out, void* stream) {
-    if (!q || !kc || !vc || !prompt_len || !out) return ll_fail(LDS_EINVAL, "null argument");
+    if (!q || !kc || !vc || !prompt_len || !out) return set_error(LDS_EINVAL, "null argument");
     if (R < 1 || R > 4096 || K < 1 || K > kMaxBeams || R % K || heads < 1 || kv_heads < 1 || heads % kv_heads || d < 16 || d > kLlMaxHeadDim || d % 16 || cap < 1 ||
         cap > kLlMaxBeamLength || step < 0 || (tab && tcap < step) || (!tab && K != 1))
-        return ll_fail(LDS_EINVAL, "bad argument");
+        return set_error(LDS_EINVAL, "bad argument");
     int pos_max = 0;
     for (int i = 0; i < R / K; ++i) {
         const int pos = prompt_len[i] - 1 + step;
-        if (prompt_len[i] < 1 || pos >= cap) return ll_fail(LDS_EINVAL, "prompt_len[%d] - 1 + step outside the cache", i);
+        if (prompt_len[i] < 1 || pos >= cap) return set_error(LDS_EINVAL, "prompt_len[%d] - 1 + step outside the cache", i);
         pos_max = pos > pos_max ? pos : pos_max;
     }
     hipStream_t st = (hipStream_t)stream;
     int* dev = nullptr;      // the lengths per row
-    if (hipMalloc((void**)&dev, sizeof(int) * R) != hipSuccess) return ll_fail(LDS_ENOMEM, "hipMalloc");
+    if (hipMalloc((void**)&dev, sizeof(int) * R) != hipSuccess) return set_error(LDS_ENOMEM, "hipMalloc");
     std::vector<int> plr(R);
     for (int r = 0; r < R; ++r) plr[r] = prompt_len[r / K];
     int rc = LDS_OK;
     const int Lkp = (pos_max + 1 + 63) & ~63;
     const size_t lds = (size_t)(kLlMaxHeadDim + Lkp + 4 * (2 + kLlMaxHeadDim)) * sizeof(float);
     const LlRows rows{dev, 0, step, cap};
-    if (hipMemcpyAsync(dev, plr.data(), sizeof(int) * R, hipMemcpyHostToDevice, st) != hipSuccess) rc = ll_fail(LDS_EHIP, "copy");
+    if (hipMemcpyAsync(dev, plr.data(), sizeof(int) * R, hipMemcpyHostToDevice, st) != hipSuccess) rc = set_error(LDS_EHIP, "copy");
     if (rc == LDS_OK) {
         if (tab)
             hipLaunchKernelGGL(ll_attn_beam_kernel, dim3((unsigned)(R * heads)), dim3(256), lds + (size_t)Lkp * sizeof(int), st, q, kc, vc, rows, heads, kv_heads, d, Lkp,
                                out, LlBeamAttn{tab, nullptr, tcap, K});
         else      // the plain kernel: K is 1, every row has its own prompt length and cache row
             hipLaunchKernelGGL(ll_attn_kernel, dim3((unsigned)(R * heads)), dim3(256), lds, st, q, kc, vc, rows, heads, kv_heads, d, Lkp, out);
-        if (hipGetLastError() != hipSuccess) rc = ll_fail(LDS_EHIP, "launch");
+        if (hipGetLastError() != hipSuccess) rc = set_error(LDS_EHIP, "launch");
     }
-    if (hipStreamSynchronize(st) != hipSuccess) rc = ll_fail(LDS_EHIP, "sync");
+    if (hipStreamSynchronize(st) != hipSuccess) rc = set_error(LDS_EHIP, "sync");
     (void)hipFree(dev);
     return rc;
 }

@@ -7,6 +7,7 @@
 // per output, independent of the batch size.
 #include "../../include/lds.h"
 #include "kernels.h"
+#include "host.h"
 #include "lm_common.h"
 
 #include <math.h>
@@ -14,7 +15,6 @@
 #include <stdio.h>
 #include <string.h>
 
-#include <map>
 #include <string>
 #include <type_traits>
 #include <vector>
@@ -1087,14 +1087,6 @@ using namespace lds;
 // ================================================================================================
 // host side
 // ================================================================================================
-#define lm_fail lds::set_error
-
-#define LM_HIP(expr)                                                                                                    \
-    do {                                                                                                                \
-        hipError_t e_ = (expr);                                                                                         \
-        if (e_ != hipSuccess) return lm_fail(LDS_EHIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
-
 struct LmLinear { float* wt = nullptr; float* b = nullptr; int K = 0, M = 0; };
 struct LmLN { float* g = nullptr; float* b = nullptr; };
 struct LmAttn { LmLinear qkv, q, kv, o; LmLN ln; };      // self: qkv fused; cross: q and kv separately
@@ -1103,33 +1095,16 @@ struct LmStack { float *word = nullptr, *type = nullptr, *table = nullptr; LmLN 
 
 struct lds_lm {
     lds_lm_cfg cfg;
-    std::vector<void*> bufs;
+    Owner own;
     LmStack enc, dec;
     float* spk = nullptr;
     LmLinear head_t, head_d;
     LmLN head_ln;
-    ~lds_lm() { for (void* p : bufs) (void)hipFree(p); }
-    float* up(const std::vector<float>& h) {
-        void* d = nullptr;
-        if (hipMalloc(&d, h.size() * sizeof(float)) != hipSuccess) return nullptr;
-        if (hipMemcpy(d, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(d); return nullptr; }
-        bufs.push_back(d);
-        return (float*)d;
-    }
 };
 
 namespace {
-struct LmTensors {
-    std::map<std::string, std::pair<const float*, int64_t>> m;
-    std::string missing;
-    const float* get(const std::string& k, int64_t n) {
-        auto it = m.find(k);
-        if (it == m.end() || it->second.second != n) { if (missing.empty()) missing = k; return nullptr; }
-        return it->second.first;
-    }
-};
 // reference layout W [M][K] -> transposed [K][M] (several matrices may be concatenated along M)
-bool lm_linear(lds_lm* lm, LmTensors& T, const std::vector<std::string>& prefixes, int K, int Mper, LmLinear& out) {
+bool lm_linear(WeightLoader& T, const std::vector<std::string>& prefixes, int K, int Mper, LmLinear& out) {
     const int M = Mper * (int)prefixes.size();
     std::vector<float> wt((size_t)K * M), b(M);
     for (size_t s = 0; s < prefixes.size(); ++s) {
@@ -1141,35 +1116,33 @@ bool lm_linear(lds_lm* lm, LmTensors& T, const std::vector<std::string>& prefixe
             b[s * Mper + m] = bb[m];
         }
     }
-    out.wt = lm->up(wt); out.b = lm->up(b); out.K = K; out.M = M;
+    out.wt = T.o.upload(wt); out.b = T.o.upload(b); out.K = K; out.M = M;
     return out.wt && out.b;
 }
-bool lm_vec(lds_lm* lm, LmTensors& T, const std::string& k, int64_t n, float*& out) {
-    const float* p = T.get(k, n);
-    if (!p) return false;
-    out = lm->up(std::vector<float>(p, p + n));
+bool lm_vec(WeightLoader& T, const std::string& k, int64_t n, float*& out) {
+    out = T.vec(k, n);
     return out != nullptr;
 }
-bool lm_ln(lds_lm* lm, LmTensors& T, const std::string& p, int H, LmLN& out) { return lm_vec(lm, T, p + "weight", H, out.g) && lm_vec(lm, T, p + "bias", H, out.b); }
-bool lm_attn(lds_lm* lm, LmTensors& T, const std::string& p, int H, bool cross, LmAttn& a) {
+bool lm_ln(WeightLoader& T, const std::string& p, int H, LmLN& out) { return lm_vec(T, p + "weight", H, out.g) && lm_vec(T, p + "bias", H, out.b); }
+bool lm_attn(WeightLoader& T, const std::string& p, int H, bool cross, LmAttn& a) {
     bool ok = true;
-    if (cross) ok = lm_linear(lm, T, {p + "self.query."}, H, H, a.q) && lm_linear(lm, T, {p + "self.key.", p + "self.value."}, H, H, a.kv);
-    else ok = lm_linear(lm, T, {p + "self.query.", p + "self.key.", p + "self.value."}, H, H, a.qkv);
-    return ok && lm_linear(lm, T, {p + "output.dense."}, H, H, a.o) && lm_ln(lm, T, p + "output.LayerNorm.", H, a.ln);
+    if (cross) ok = lm_linear(T, {p + "self.query."}, H, H, a.q) && lm_linear(T, {p + "self.key.", p + "self.value."}, H, H, a.kv);
+    else ok = lm_linear(T, {p + "self.query.", p + "self.key.", p + "self.value."}, H, H, a.qkv);
+    return ok && lm_linear(T, {p + "output.dense."}, H, H, a.o) && lm_ln(T, p + "output.LayerNorm.", H, a.ln);
 }
-bool lm_stack(lds_lm* lm, LmTensors& T, const std::string& p, int vocab, int type_vocab, int n_layers, bool cross, LmStack& s) {
+bool lm_stack(lds_lm* lm, WeightLoader& T, const std::string& p, int vocab, int type_vocab, int n_layers, bool cross, LmStack& s) {
     const lds_lm_cfg& c = lm->cfg;
     const int H = c.hidden, d = H / c.heads;
-    bool ok = lm_vec(lm, T, p + "embeddings.word_embeddings.weight", (int64_t)vocab * H, s.word) &&
-              lm_vec(lm, T, p + "embeddings.token_type_embeddings.weight", (int64_t)type_vocab * H, s.type) &&
-              lm_ln(lm, T, p + "embeddings.LayerNorm.", H, s.ln_emb) && lm_vec(lm, T, p + "encoder.embed_positions.weight", (int64_t)c.max_pos * d, s.table);
+    bool ok = lm_vec(T, p + "embeddings.word_embeddings.weight", (int64_t)vocab * H, s.word) &&
+              lm_vec(T, p + "embeddings.token_type_embeddings.weight", (int64_t)type_vocab * H, s.type) &&
+              lm_ln(T, p + "embeddings.LayerNorm.", H, s.ln_emb) && lm_vec(T, p + "encoder.embed_positions.weight", (int64_t)c.max_pos * d, s.table);
     for (int i = 0; i < n_layers && ok; ++i) {
         LmLayer L;
         const std::string q = p + "encoder.layer." + std::to_string(i) + ".";
         L.has_cross = cross;
-        ok = lm_attn(lm, T, q + "attention.", H, false, L.self) && (!cross || lm_attn(lm, T, q + "crossattention.", H, true, L.cross)) &&
-             lm_linear(lm, T, {q + "intermediate.dense."}, H, c.inter, L.ff1) && lm_linear(lm, T, {q + "output.dense."}, c.inter, H, L.ff2) &&
-             lm_ln(lm, T, q + "output.LayerNorm.", H, L.ln_ff);
+        ok = lm_attn(T, q + "attention.", H, false, L.self) && (!cross || lm_attn(T, q + "crossattention.", H, true, L.cross)) &&
+             lm_linear(T, {q + "intermediate.dense."}, H, c.inter, L.ff1) && lm_linear(T, {q + "output.dense."}, c.inter, H, L.ff2) &&
+             lm_ln(T, q + "output.LayerNorm.", H, L.ln_ff);
         s.layers.push_back(L);
     }
     return ok;
@@ -1177,44 +1150,25 @@ bool lm_stack(lds_lm* lm, LmTensors& T, const std::string& p, int vocab, int typ
 }  // namespace
 
 extern "C" int lds_lm_create(const lds_lm_cfg* cfg, int n, const char* const* names, const float* const* ptrs, const int64_t* numel, lds_lm** out) {
-    if (!cfg || !names || !ptrs || !numel || !out) return lm_fail(LDS_EINVAL, "null argument");
+    if (!cfg || !names || !ptrs || !numel || !out) return set_error(LDS_EINVAL, "null argument");
     if (cfg->hidden != 256 || cfg->heads <= 0 || cfg->hidden % cfg->heads || cfg->hidden / cfg->heads > 32 || (cfg->hidden / cfg->heads) % 2 ||
         cfg->sem_vocab > 256 * 32 || cfg->inter <= 0 || cfg->inter % 256 || cfg->inter > 3840)      // (inter: the staged rows of ff2 must fit in LDS)
-        return lm_fail(LDS_EINVAL, "unsupported LM shape (hidden must be 256, head dim even and <= 32, vocabulary <= 8192, intermediate size a multiple of 256 <= 3840)");
-    LmTensors T;
-    for (int i = 0; i < n; ++i) T.m[names[i]] = {ptrs[i], numel[i]};
+        return set_error(LDS_EINVAL, "unsupported LM shape (hidden must be 256, head dim even and <= 32, vocabulary <= 8192, intermediate size a multiple of 256 <= 3840)");
     lds_lm* lm = new lds_lm();
     lm->cfg = *cfg;
+    WeightLoader T(lm->own, n, names, ptrs, numel);
     const int H = cfg->hidden;
     bool ok = lm_stack(lm, T, "text_encoder.", cfg->text_vocab, cfg->type_vocab, cfg->enc_layers, false, lm->enc) &&
               lm_stack(lm, T, "semantic_decoder.roformer.", cfg->sem_vocab, 1, cfg->dec_layers, true, lm->dec);
     const std::string c = "semantic_decoder.cls.predictions.";
-    ok = ok && lm_linear(lm, T, {c + "transform.dense."}, H, H, lm->head_t) && lm_ln(lm, T, c + "transform.LayerNorm.", H, lm->head_ln) &&
-         lm_linear(lm, T, {c + "decoder."}, H, cfg->sem_vocab, lm->head_d);
-    if (ok && cfg->n_spk_rows > 0) ok = lm_vec(lm, T, "spk_emb.weight", (int64_t)cfg->n_spk_rows * H, lm->spk);
-    if (!ok) {
-        const std::string miss = T.missing;
-        delete lm;
-        if (!miss.empty()) return lm_fail(LDS_EMISSING, "LM weight tensor %s (absent or wrong size)", miss.c_str());
-        return lm_fail(LDS_ENOMEM, "LM weight upload failed");
-    }
-    *out = lm;
-    return LDS_OK;
+    ok = ok && lm_linear(T, {c + "transform.dense."}, H, H, lm->head_t) && lm_ln(T, c + "transform.LayerNorm.", H, lm->head_ln) &&
+         lm_linear(T, {c + "decoder."}, H, cfg->sem_vocab, lm->head_d);
+    if (ok && cfg->n_spk_rows > 0) ok = lm_vec(T, "spk_emb.weight", (int64_t)cfg->n_spk_rows * H, lm->spk);
+    return T.finish(ok, "LM", lm, out, "LM weight tensor");
 }
 extern "C" void lds_lm_destroy(lds_lm* lm) { delete lm; }
 
 namespace {
-struct LmArena {
-    char* base; size_t cap, used = 0; bool ok = true;
-    LmArena(void* p, size_t n) : base((char*)p), cap(n) {}
-    float* f(size_t n) {
-        const size_t bytes = (n * sizeof(float) + 255) & ~(size_t)255;
-        if (base && used + bytes > cap) ok = false;
-        char* p = base ? base + used : nullptr;
-        used += bytes;
-        return (float*)p;
-    }
-};
 // beam-search state (K > 1): two buffers of the running sequences, of the ancestry table and of the finished hypotheses, per-row scores / flags
 struct LmBeamWs { int64_t *rseq[2], *fseq[2]; int* tab[2]; float *rscore, *fscore; int *ffin, *flen, *unsat; };
 // a prompted decode (P > 1): the prefill's token ids [B][P], every row's last prompt token [B] and the prompt lengths on the device [B]
@@ -1222,7 +1176,7 @@ struct LmPromptWs { int64_t *ids, *last; int32_t* plen; };
 struct LmWs { float *x, *y, *z, *qkv, *ctx, *ff, *kv, *logits, *kc_tmp, *vc_tmp; int* flags; std::vector<float*> kc, vc, ckc, cvc; LmBeamWs beam; LmPromptWs prompt; };
 // N = rows processed at once (B * L for the prefill, B * K for a decode step); K = beams per batch item (1: the layout of a plain decode)
 // P = the prompt's width (1: no prompt, today's layout byte for byte): the prefill runs B * P rows through the activation buffers
-void lm_plan(const lds_lm* lm, LmArena& A, int B, int L, int cap, LmWs& w, int K = 1, int P = 1) {
+void lm_plan(const lds_lm* lm, Arena& A, int B, int L, int cap, LmWs& w, int K = 1, int P = 1) {
     const lds_lm_cfg& c = lm->cfg;
     const size_t R = (size_t)B * K, BL = (size_t)B * (L > 1 ? L : 1), BP = (size_t)B * P, N0 = BL > R ? BL : R, N = N0 > BP ? N0 : BP, H = c.hidden;
     w.x = A.f(N * H); w.y = A.f(N * H); w.z = A.f(N * H); w.qkv = A.f(N * 3 * H); w.ctx = A.f(N * H); w.ff = A.f(N * c.inter); w.kv = A.f(N * 2 * H);
@@ -1330,43 +1284,43 @@ int lm_layer(const lds_lm* lm, const LmStack& s, const LmLayer& Ly, const LmWs& 
     const int Lk_max = mode.Lk_max;
     const lds_lm_cfg& c = lm->cfg;
     const int H = c.hidden, N = B * L;
-    if (Ly.self.o.M != H || Ly.ff2.M != H || (Ly.has_cross && (Ly.cross.o.M != H || Ly.cross.q.K != H))) return lm_fail(LDS_EINVAL, "layer shapes");
+    if (Ly.self.o.M != H || Ly.ff2.M != H || (Ly.has_cross && (Ly.cross.o.M != H || Ly.cross.q.K != H))) return set_error(LDS_EINVAL, "layer shapes");
     float* free1 = (x.p == w.x) ? w.y : w.x;
     float* free2 = (x.p == w.z) ? w.y : w.z;
     if (free1 == free2) free2 = w.x;
     if (plen) {
         LmRopeRow rope;
         rope.table = s.table; rope.kc = kc; rope.vc = vc; rope.pos0 = pos0; rope.L = L; rope.heads = c.heads; rope.cap = cap; rope.plen = plen;
-        LM_HIP(lm_dln_rope_rows(Ly.self.qkv, x, c.eps, w.qkv, N, st, rope));
+        HIP_TRY(lm_dln_rope_rows(Ly.self.qkv, x, c.eps, w.qkv, N, st, rope));
     } else {
         const LmRope rope{s.table, kc, vc, pos0, L, c.heads, cap};      // rotary embedding and cache append in the projection's epilogue
-        LM_HIP(lm_dln<4>(Ly.self.qkv, x, H, nullptr, c.eps, w.qkv, 3 * H, N, st, &rope));
+        HIP_TRY(lm_dln<4>(Ly.self.qkv, x, H, nullptr, c.eps, w.qkv, 3 * H, N, st, &rope));
     }
-    if (plen) LM_HIP(lm_attention_rows(w.qkv, 3 * H, kc, vc, cap, B, Lk_max, plen, pos0, c, w.ctx, st));
-    else if (causal) LM_HIP(lm_attention_causal(w.qkv, 3 * H, kc, vc, cap, B, L, c, w.ctx, st));
-    else if (beam) LM_HIP(lm_attention_beam(w.qkv, 3 * H, kc, vc, cap, B, L, pos0 + L, self_klen, c, w.ctx, beam->src, cap, 1, st));
-    else LM_HIP(lm_attention(w.qkv, 3 * H, kc, vc, cap, B, L, pos0 + L, self_klen, c, w.ctx, st));
+    if (plen) HIP_TRY(lm_attention_rows(w.qkv, 3 * H, kc, vc, cap, B, Lk_max, plen, pos0, c, w.ctx, st));
+    else if (causal) HIP_TRY(lm_attention_causal(w.qkv, 3 * H, kc, vc, cap, B, L, c, w.ctx, st));
+    else if (beam) HIP_TRY(lm_attention_beam(w.qkv, 3 * H, kc, vc, cap, B, L, pos0 + L, self_klen, c, w.ctx, beam->src, cap, 1, st));
+    else HIP_TRY(lm_attention(w.qkv, 3 * H, kc, vc, cap, B, L, pos0 + L, self_klen, c, w.ctx, st));
     const LmRows ctx{w.ctx, nullptr};
-    LM_HIP(lm_dln<5>(Ly.self.o, ctx, H, &x, c.eps, free1, H, N, st));               // a = W_o ctx + LN(x)
+    HIP_TRY(lm_dln<5>(Ly.self.o, ctx, H, &x, c.eps, free1, H, N, st));               // a = W_o ctx + LN(x)
     LmRows cur{free1, &Ly.self.ln};
     if (Ly.has_cross) {
-        LM_HIP(lm_dln<0>(Ly.cross.q, cur, H, nullptr, c.eps, w.qkv, H, N, st));
-        if (beam) LM_HIP(lm_attention_beam(w.qkv, H, ckc, cvc, Lenc, B, L, Lenc, cross_klen, c, w.ctx, nullptr, 0, beam->K, st));
-        else LM_HIP(lm_attention(w.qkv, H, ckc, cvc, Lenc, B, L, Lenc, cross_klen, c, w.ctx, st));
-        LM_HIP(lm_dln<5>(Ly.cross.o, ctx, H, &cur, c.eps, free2, H, N, st));        // c = W_o' ctx' + LN(a)
+        HIP_TRY(lm_dln<0>(Ly.cross.q, cur, H, nullptr, c.eps, w.qkv, H, N, st));
+        if (beam) HIP_TRY(lm_attention_beam(w.qkv, H, ckc, cvc, Lenc, B, L, Lenc, cross_klen, c, w.ctx, nullptr, 0, beam->K, st));
+        else HIP_TRY(lm_attention(w.qkv, H, ckc, cvc, Lenc, B, L, Lenc, cross_klen, c, w.ctx, st));
+        HIP_TRY(lm_dln<5>(Ly.cross.o, ctx, H, &cur, c.eps, free2, H, N, st));        // c = W_o' ctx' + LN(a)
         cur = LmRows{free2, &Ly.cross.ln};
     }
-    LM_HIP(lm_dln<1>(Ly.ff1, cur, H, nullptr, c.eps, w.ff, c.inter, N, st));
+    HIP_TRY(lm_dln<1>(Ly.ff1, cur, H, nullptr, c.eps, w.ff, c.inter, N, st));
     const LmRows ff{w.ff, nullptr};
-    LM_HIP(lm_dln<5>(Ly.ff2, ff, c.inter, &cur, c.eps, x.p, H, N, st));              // g = W_2 f + LN(cur), into the input's buffer (no longer read)
+    HIP_TRY(lm_dln<5>(Ly.ff2, ff, c.inter, &cur, c.eps, x.p, H, N, st));              // g = W_2 f + LN(cur), into the input's buffer (no longer read)
     x.ln = &Ly.ln_ff;
     return LDS_OK;
 }
 }  // namespace
 
 extern "C" int lds_lm_workspace_bytes(const lds_lm* lm, int B, int L, int max_length, size_t* out) {
-    if (!lm || !out || B <= 0 || L <= 0 || max_length < 2) return lm_fail(LDS_EINVAL, "bad argument");
-    LmArena A(nullptr, 0);
+    if (!lm || !out || B <= 0 || L <= 0 || max_length < 2) return set_error(LDS_EINVAL, "bad argument");
+    Arena A(nullptr, 0);
     LmWs w;
     lm_plan(lm, A, B, L, max_length, w);
     *out = A.used;
@@ -1376,18 +1330,18 @@ extern "C" int lds_lm_workspace_bytes(const lds_lm* lm, int B, int L, int max_le
 // phone, tone [B,L] int64 (dev), spk_id [B,L] int64 or NULL, enc_len [B] int32 (dev) or NULL = the padding mask's key counts -> enc [B,L,hidden] (dev)
 extern "C" int lds_lm_encode(lds_lm* lm, const int64_t* phone, const int64_t* tone, const int64_t* spk_id, const int32_t* enc_len, float* enc, void* ws,
                              size_t ws_bytes, int B, int L, void* stream) {
-    if (!lm || !phone || !tone || !enc || !ws || B <= 0 || L <= 0) return lm_fail(LDS_EINVAL, "bad argument");
+    if (!lm || !phone || !tone || !enc || !ws || B <= 0 || L <= 0) return set_error(LDS_EINVAL, "bad argument");
     const lds_lm_cfg& c = lm->cfg;
-    if (L > c.max_pos) return lm_fail(LDS_EINVAL, "sequence longer than max_position_embeddings");
+    if (L > c.max_pos) return set_error(LDS_EINVAL, "sequence longer than max_position_embeddings");
     hipStream_t st = (hipStream_t)stream;
-    LmArena A(ws, ws_bytes);
+    Arena A(ws, ws_bytes);
     LmWs w;
     lm_plan(lm, A, B, L, 2, w);
-    if (!A.ok) return lm_fail(LDS_ENOMEM, "LM workspace too small: need %zu bytes", A.used);
+    if (!A.ok) return set_error(LDS_ENOMEM, "LM workspace too small: need %zu bytes", A.used);
     const int N = B * L, H = c.hidden;
     hipLaunchKernelGGL(lm_embed_kernel, dim3(N), dim3(256), 0, st, lm->enc.word, lm->enc.type, lm->spk, lm->enc.ln_emb.g, lm->enc.ln_emb.b, phone, 1, tone,
                        lm->spk ? spk_id : nullptr, 1, c.eps, H, c.text_vocab, c.type_vocab, c.n_spk_rows > 0 ? c.n_spk_rows : 1, w.x);
-    LM_HIP(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     LmRows cx{w.x, nullptr};
     for (const LmLayer& Ly : lm->enc.layers) {
         // the encoder's "cache" is just this layer's keys / values for all L positions
@@ -1396,9 +1350,9 @@ extern "C" int lds_lm_encode(lds_lm* lm, const int64_t* phone, const int64_t* to
     }
     if (cx.ln) {      // the states leave the library normalised
         hipLaunchKernelGGL(lm_ln_rows_kernel, dim3(N), dim3(256), 0, st, (const float*)cx.p, cx.ln->g, cx.ln->b, c.eps, H, enc);
-        LM_HIP(hipGetLastError());
+        HIP_TRY(hipGetLastError());
     } else {
-        LM_HIP(hipMemcpyAsync(enc, cx.p, sizeof(float) * N * H, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(enc, cx.p, sizeof(float) * N * H, hipMemcpyDeviceToDevice, st));
     }
     return LDS_OK;
 }
@@ -1460,19 +1414,19 @@ hipError_t lds::lm_launch_beam_rows(int B, int K, int V, const float* lg, int st
 
 // the option checks that need no model (they come before every other check of lds_lm_generate_opts; no device call)
 int lds::lm_check_opts(const lds_lm_decode_opts& o, const float* logits_out) {
-    if (o.num_beams < 1 || o.num_beams > kMaxBeams) return lm_fail(LDS_EINVAL, "num_beams %d out of range (1 .. %d)", o.num_beams, kMaxBeams);
-    if (o.no_repeat_ngram_size < 0) return lm_fail(LDS_EINVAL, "no_repeat_ngram_size %d < 0", o.no_repeat_ngram_size);
+    if (o.num_beams < 1 || o.num_beams > kMaxBeams) return set_error(LDS_EINVAL, "num_beams %d out of range (1 .. %d)", o.num_beams, kMaxBeams);
+    if (o.no_repeat_ngram_size < 0) return set_error(LDS_EINVAL, "no_repeat_ngram_size %d < 0", o.no_repeat_ngram_size);
     if (o.num_beams > 1 && o.do_sample)
-        return lm_fail(LDS_EINVAL, "beam sampling (num_beams > 1 with do_sample) is not built: only greedy beam search");
-    if (o.num_beams > 1 && (o.early_stopping < 0 || o.early_stopping > 2)) return lm_fail(LDS_EINVAL, "early_stopping must be 0 (False), 1 (True) or 2 (\"never\")");
-    if (o.num_beams > 1 && logits_out) return lm_fail(LDS_EINVAL, "logits_out is not available with num_beams > 1");
+        return set_error(LDS_EINVAL, "beam sampling (num_beams > 1 with do_sample) is not built: only greedy beam search");
+    if (o.num_beams > 1 && (o.early_stopping < 0 || o.early_stopping > 2)) return set_error(LDS_EINVAL, "early_stopping must be 0 (False), 1 (True) or 2 (\"never\")");
+    if (o.num_beams > 1 && logits_out) return set_error(LDS_EINVAL, "logits_out is not available with num_beams > 1");
     return LDS_OK;
 }
 
 extern "C" int lds_lm_workspace_bytes_opts(const lds_lm* lm, int B, int L, int max_length, int num_beams, size_t* out) {
-    if (num_beams < 1 || num_beams > kMaxBeams) return lm_fail(LDS_EINVAL, "num_beams %d out of range (1 .. %d)", num_beams, kMaxBeams);
-    if (!lm || !out || B <= 0 || L <= 0 || max_length < 2) return lm_fail(LDS_EINVAL, "bad argument");
-    LmArena A(nullptr, 0);
+    if (num_beams < 1 || num_beams > kMaxBeams) return set_error(LDS_EINVAL, "num_beams %d out of range (1 .. %d)", num_beams, kMaxBeams);
+    if (!lm || !out || B <= 0 || L <= 0 || max_length < 2) return set_error(LDS_EINVAL, "bad argument");
+    Arena A(nullptr, 0);
     LmWs w;
     lm_plan(lm, A, B, L, max_length, w, num_beams);
     *out = A.used;
@@ -1483,30 +1437,30 @@ extern "C" int lds_lm_workspace_bytes_opts(const lds_lm* lm, int B, int L, int m
 // positions past the returned length are unspecified; logits_out optional [max_length-1][B][vocab] (dev).  *n_tokens_host = sequence length incl. BOS.
 extern "C" int lds_lm_generate_opts(lds_lm* lm, const float* enc, const int32_t* enc_len, int B, int L, int max_length, const lds_lm_decode_opts* opts,
                                     const float* uniforms, int64_t* tokens, float* logits_out, int* n_tokens_host, void* ws, size_t ws_bytes, void* stream) {
-    if (!opts) return lm_fail(LDS_EINVAL, "null options");
+    if (!opts) return set_error(LDS_EINVAL, "null options");
     const lds_lm_decode_opts o = *opts;
     if (int r = lm_check_opts(o, logits_out)) return r;
-    if (!lm || !enc || !tokens || !n_tokens_host || !ws || B <= 0 || L <= 0 || max_length < 2) return lm_fail(LDS_EINVAL, "bad argument");
+    if (!lm || !enc || !tokens || !n_tokens_host || !ws || B <= 0 || L <= 0 || max_length < 2) return set_error(LDS_EINVAL, "bad argument");
     const lds_lm_cfg& c = lm->cfg;
     const int do_sample = o.do_sample, top_k = o.top_k, K = o.num_beams;
     const float top_p = o.top_p, temperature = o.temperature;
     if (K > 1 && (2 * K > c.sem_vocab || c.sem_vocab > kMaxBeamVocab))
-        return lm_fail(LDS_EINVAL, "beam search is built for vocabularies of 2 * num_beams .. %d entries", kMaxBeamVocab);
+        return set_error(LDS_EINVAL, "beam search is built for vocabularies of 2 * num_beams .. %d entries", kMaxBeamVocab);
     if (do_sample && (!uniforms || top_k < 0 || top_k > kMaxTopK || top_k > c.sem_vocab || !(top_p > 0.f) || !(temperature > 0.f)))
-        return lm_fail(LDS_EINVAL, "sampling needs uniforms, 0 <= top_k <= %d (0 = no top-k filter), top_p > 0, temperature > 0", kMaxTopK);
-    if (do_sample && top_k == 0 && (size_t)c.sem_vocab * sizeof(float) > 60 * 1024) return lm_fail(LDS_EINVAL, "top_k = 0 needs the vocabulary row in LDS (<= 15360 entries)");
-    if (max_length > c.max_pos) return lm_fail(LDS_EINVAL, "max_length exceeds max_position_embeddings");
+        return set_error(LDS_EINVAL, "sampling needs uniforms, 0 <= top_k <= %d (0 = no top-k filter), top_p > 0, temperature > 0", kMaxTopK);
+    if (do_sample && top_k == 0 && (size_t)c.sem_vocab * sizeof(float) > 60 * 1024) return set_error(LDS_EINVAL, "top_k = 0 needs the vocabulary row in LDS (<= 15360 entries)");
+    if (max_length > c.max_pos) return set_error(LDS_EINVAL, "max_length exceeds max_position_embeddings");
     // the encoder states come from lds_lm_encode (L <= max_pos); the cross-attention stages one score per encoder position in LDS
     if (L < 1 || L > c.max_pos || (size_t)(((L + 63) & ~63) + 4 * 34) * sizeof(float) > 64 * 1024)
-        return lm_fail(LDS_EINVAL, "encoder length %d out of range (1 .. min(max_position_embeddings = %d, 16000))", L, c.max_pos);
+        return set_error(LDS_EINVAL, "encoder length %d out of range (1 .. min(max_position_embeddings = %d, 16000))", L, c.max_pos);
     // a beam decode stages one score and one source row per cached position in LDS
     if (K > 1 && (size_t)(((max_length + 63) & ~63) * 2 + 4 * 34) * sizeof(float) > 64 * 1024)
-        return lm_fail(LDS_EINVAL, "max_length %d too long for a beam decode (<= 8000)", max_length);
+        return set_error(LDS_EINVAL, "max_length %d too long for a beam decode (<= 8000)", max_length);
     hipStream_t st = (hipStream_t)stream;
-    LmArena A(ws, ws_bytes);
+    Arena A(ws, ws_bytes);
     LmWs w;
     lm_plan(lm, A, B, L, max_length, w, K);
-    if (!A.ok) return lm_fail(LDS_ENOMEM, "LM workspace too small: need %zu bytes", A.used);
+    if (!A.ok) return set_error(LDS_ENOMEM, "LM workspace too small: need %zu bytes", A.used);
     const int H = c.hidden, V = c.sem_vocab, R = B * K;
     int* unfinished = w.flags;                 // [R]
     int* any_unf = w.flags + R;                // [max_length]: 1 when a sequence is still running after step s (beam search: lm_beam_step_kernel's bits)
@@ -1514,36 +1468,36 @@ extern "C" int lds_lm_generate_opts(lds_lm* lm, const float* enc, const int32_t*
     for (int i = 0; i < c.dec_layers; ++i) {
         {
             const LmRows er{const_cast<float*>(enc), nullptr};
-            LM_HIP(lm_dln<0>(lm->dec.layers[i].cross.kv, er, H, nullptr, c.eps, w.kv, 2 * H, B * L, st));
+            HIP_TRY(lm_dln<0>(lm->dec.layers[i].cross.kv, er, H, nullptr, c.eps, w.kv, 2 * H, B * L, st));
         }
         hipLaunchKernelGGL(lm_kv_pack_kernel, dim3((unsigned)(((long long)B * L * H + 255) / 256)), dim3(256), 0, st, w.kv, B, L, H, c.heads, w.ckc[i], w.cvc[i], L);
-        LM_HIP(hipGetLastError());
+        HIP_TRY(hipGetLastError());
     }
     std::vector<int64_t> bos((size_t)R * max_length, (int64_t)c.sem_pad);
     for (int r = 0; r < R; ++r) bos[(size_t)r * max_length] = c.sem_bos;
     {
         std::vector<int> init(R + max_length, 0);
         for (int b = 0; b < R; ++b) init[b] = 1;
-        LM_HIP(hipMemcpyAsync(unfinished, init.data(), sizeof(int) * (R + max_length), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(unfinished, init.data(), sizeof(int) * (R + max_length), hipMemcpyHostToDevice, st));
         if (K == 1) {
-            LM_HIP(hipMemcpyAsync(tokens, bos.data(), sizeof(int64_t) * B * max_length, hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(tokens, bos.data(), sizeof(int64_t) * B * max_length, hipMemcpyHostToDevice, st));
         } else {      // HF _beam_search: running scores 0, -1e9, ...; finished scores -1e9; sequences BOS then PAD
             std::vector<float> rs(R, -1.0e9f), fs(R, -1.0e9f);
             std::vector<int> zero((size_t)R * max_length, 0), one(B, 1);
             for (int b = 0; b < B; ++b) rs[(size_t)b * K] = 0.f;
             for (int i = 0; i < 2; ++i) {
-                LM_HIP(hipMemcpyAsync(w.beam.rseq[i], bos.data(), sizeof(int64_t) * R * max_length, hipMemcpyHostToDevice, st));
-                LM_HIP(hipMemcpyAsync(w.beam.fseq[i], bos.data(), sizeof(int64_t) * R * max_length, hipMemcpyHostToDevice, st));
-                LM_HIP(hipMemcpyAsync(w.beam.tab[i], zero.data(), sizeof(int) * R * max_length, hipMemcpyHostToDevice, st));
+                HIP_TRY(hipMemcpyAsync(w.beam.rseq[i], bos.data(), sizeof(int64_t) * R * max_length, hipMemcpyHostToDevice, st));
+                HIP_TRY(hipMemcpyAsync(w.beam.fseq[i], bos.data(), sizeof(int64_t) * R * max_length, hipMemcpyHostToDevice, st));
+                HIP_TRY(hipMemcpyAsync(w.beam.tab[i], zero.data(), sizeof(int) * R * max_length, hipMemcpyHostToDevice, st));
             }
-            LM_HIP(hipMemcpyAsync(w.beam.rscore, rs.data(), sizeof(float) * R, hipMemcpyHostToDevice, st));
-            LM_HIP(hipMemcpyAsync(w.beam.fscore, fs.data(), sizeof(float) * R, hipMemcpyHostToDevice, st));
-            LM_HIP(hipMemcpyAsync(w.beam.ffin, zero.data(), sizeof(int) * R, hipMemcpyHostToDevice, st));
-            LM_HIP(hipMemcpyAsync(w.beam.flen, zero.data(), sizeof(int) * R, hipMemcpyHostToDevice, st));
-            LM_HIP(hipMemcpyAsync(w.beam.unsat, one.data(), sizeof(int) * B, hipMemcpyHostToDevice, st));
-            LM_HIP(hipStreamSynchronize(st));      // (zero, one, rs, fs go out of scope)
+            HIP_TRY(hipMemcpyAsync(w.beam.rscore, rs.data(), sizeof(float) * R, hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(w.beam.fscore, fs.data(), sizeof(float) * R, hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(w.beam.ffin, zero.data(), sizeof(int) * R, hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(w.beam.flen, zero.data(), sizeof(int) * R, hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(w.beam.unsat, one.data(), sizeof(int) * B, hipMemcpyHostToDevice, st));
+            HIP_TRY(hipStreamSynchronize(st));      // (zero, one, rs, fs go out of scope)
         }
-        LM_HIP(hipStreamSynchronize(st));      // the host staging vectors go out of scope
+        HIP_TRY(hipStreamSynchronize(st));      // the host staging vectors go out of scope
     }
     const float inv_temp = do_sample ? 1.0f / temperature : 1.0f;
     int n_tokens = max_length, last_step = max_length - 2;
@@ -1556,7 +1510,7 @@ extern "C" int lds_lm_generate_opts(lds_lm* lm, const float* enc, const int32_t*
             hipLaunchKernelGGL(lm_embed_kernel, dim3(R), dim3(256), 0, st, lm->dec.word, lm->dec.type, (const float*)nullptr, lm->dec.ln_emb.g, lm->dec.ln_emb.b,
                                (const int64_t*)(K == 1 ? tokens : w.beam.rseq[0]), max_length, (const int64_t*)nullptr, (const int64_t*)nullptr, 0, c.eps, H,
                                c.sem_vocab, 1, 1, w.x);
-            LM_HIP(hipGetLastError());
+            HIP_TRY(hipGetLastError());
         }
         LmRows cx{w.x, nullptr};
         const LmBeamAttn ba{w.beam.tab[cur], K};
@@ -1566,26 +1520,26 @@ extern "C" int lds_lm_generate_opts(lds_lm* lm, const float* enc, const int32_t*
             if (r != LDS_OK) return r;
         }
         // LM head: h = GELU(W_t LN(x)) stored un-normalised, logits = W_d LN(h)
-        LM_HIP(lm_dln<1>(lm->head_t, cx, H, nullptr, c.eps, w.ctx, H, R, st));
+        HIP_TRY(lm_dln<1>(lm->head_t, cx, H, nullptr, c.eps, w.ctx, H, R, st));
         const LmRows hrows{w.ctx, &lm->head_ln};
         float* lg = logits_out ? logits_out + (size_t)step * B * V : w.logits;
-        LM_HIP(lm_dln<0>(lm->head_d, hrows, H, nullptr, c.eps, lg, V, R, st));
+        HIP_TRY(lm_dln<0>(lm->head_d, hrows, H, nullptr, c.eps, lg, V, R, st));
         if (K == 1) {
-            LM_HIP(lm_launch_choice(o, B, V, lg, inv_temp, do_sample ? uniforms + (size_t)step * B : nullptr, tokens, max_length, step, unfinished, c.sem_eos,
+            HIP_TRY(lm_launch_choice(o, B, V, lg, inv_temp, do_sample ? uniforms + (size_t)step * B : nullptr, tokens, max_length, step, unfinished, c.sem_eos,
                                     c.sem_pad, any_unf, lm->dec.word, lm->dec.type, lm->dec.ln_emb.g, lm->dec.ln_emb.b, c.eps, H, w.x, st));
         } else {
             const int nxt = cur ^ 1;
             const LmBeamState bs{w.beam.rseq[cur], w.beam.rseq[nxt], w.beam.rscore, w.beam.rscore, w.beam.tab[cur], w.beam.tab[nxt], w.beam.fseq[cur],
                                  w.beam.fseq[nxt], w.beam.fscore, w.beam.fscore, w.beam.ffin, w.beam.ffin, w.beam.flen, w.beam.flen, w.beam.unsat,
                                  w.beam.unsat, nullptr, step ? any_unf + step - 1 : nullptr, any_unf + step};
-            LM_HIP(lm_launch_beam_step(B, K, V, lg, step, max_length, max_length, c.sem_eos, o.repetition_penalty, o.no_repeat_ngram_size, o.early_stopping, bs,
+            HIP_TRY(lm_launch_beam_step(B, K, V, lg, step, max_length, max_length, c.sem_eos, o.repetition_penalty, o.no_repeat_ngram_size, o.early_stopping, bs,
                                        lm->dec.word, lm->dec.type, lm->dec.ln_emb.g, lm->dec.ln_emb.b, c.eps, H, w.x, st));
         }
         // EOS poll every 8 steps: the loop ends after the step in which the last running sequence emitted EOS (beam search: after the step
         // at which HF's loop condition turned false; the steps enqueued after it change nothing)
         if ((step & 7) == 7 || step + 2 == max_length) {
-            LM_HIP(hipMemcpyAsync(host_flags.data() + checked, any_unf + checked, sizeof(int) * (step + 1 - checked), hipMemcpyDeviceToHost, st));
-            LM_HIP(hipStreamSynchronize(st));
+            HIP_TRY(hipMemcpyAsync(host_flags.data() + checked, any_unf + checked, sizeof(int) * (step + 1 - checked), hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
             bool done = false;
             for (int s = checked; s <= step; ++s) {
                 const int f = host_flags[s];
@@ -1599,10 +1553,10 @@ extern "C" int lds_lm_generate_opts(lds_lm* lm, const float* enc, const int32_t*
     if (K > 1) {      // the best finished hypothesis of every item (slot 0), cropped to the longest one; BOS first, EOS kept, PAD after it
         const int64_t* best = w.beam.fseq[(last_step + 1) & 1];
         std::vector<int> flen(R, 0);
-        LM_HIP(hipMemcpy2DAsync(tokens, sizeof(int64_t) * max_length, best, sizeof(int64_t) * max_length * K, sizeof(int64_t) * max_length, B,
+        HIP_TRY(hipMemcpy2DAsync(tokens, sizeof(int64_t) * max_length, best, sizeof(int64_t) * max_length * K, sizeof(int64_t) * max_length, B,
                                 hipMemcpyDeviceToDevice, st));
-        LM_HIP(hipMemcpyAsync(flen.data(), w.beam.flen, sizeof(int) * R, hipMemcpyDeviceToHost, st));
-        LM_HIP(hipStreamSynchronize(st));
+        HIP_TRY(hipMemcpyAsync(flen.data(), w.beam.flen, sizeof(int) * R, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
         int gen = 0;
         for (int b = 0; b < B; ++b) gen = flen[(size_t)b * K] > gen ? flen[(size_t)b * K] : gen;
         n_tokens = 1 + gen;
@@ -1631,11 +1585,11 @@ namespace {
 constexpr int kMaxPromptBatch = 64;      // the rows' final lengths live in the 64 spare ints behind the step flags (lm_plan)
 // the shape checks, which need no model (they come before every check that does; no device call)
 int lm_prompt_check(int B, int L, int max_length, int P) {
-    if (B <= 0 || L <= 0 || max_length < 2 || P < 1) return lm_fail(LDS_EINVAL, "bad argument");
-    if (B > kMaxPromptBatch) return lm_fail(LDS_EINVAL, "a prompted decode takes at most %d rows, got %d", kMaxPromptBatch, B);
+    if (B <= 0 || L <= 0 || max_length < 2 || P < 1) return set_error(LDS_EINVAL, "bad argument");
+    if (B > kMaxPromptBatch) return set_error(LDS_EINVAL, "a prompted decode takes at most %d rows, got %d", kMaxPromptBatch, B);
     // the prefill's causal self-attention stages one score per key in LDS; its linears take 8 rows per workgroup along grid.y
     if ((size_t)(((P + 63) & ~63) + 4 * 34) * sizeof(float) > 64 * 1024 || (long long)B * P > 8 * 65535LL)
-        return lm_fail(LDS_EINVAL, "prompt width %d too large (<= 16000, B * P <= 524280)", P);
+        return set_error(LDS_EINVAL, "prompt width %d too large (<= 16000, B * P <= 524280)", P);
     return LDS_OK;
 }
 }  // namespace
@@ -1662,8 +1616,8 @@ hipError_t lds::lm_launch_choice_rows(const lds_lm_decode_opts& o, int B, int V,
 
 extern "C" int lds_lm_workspace_bytes_prompt(const lds_lm* lm, int B, int L, int max_length, int P, size_t* out) {
     if (int r = lm_prompt_check(B, L, max_length, P)) return r;
-    if (!lm || !out) return lm_fail(LDS_EINVAL, "bad argument");
-    LmArena A(nullptr, 0);
+    if (!lm || !out) return set_error(LDS_EINVAL, "bad argument");
+    Arena A(nullptr, 0);
     LmWs w;
     lm_plan(lm, A, B, L, max_length, w, 1, P);
     *out = A.used;
@@ -1673,25 +1627,25 @@ extern "C" int lds_lm_workspace_bytes_prompt(const lds_lm* lm, int B, int L, int
 extern "C" int lds_lm_generate_prompt(lds_lm* lm, const float* enc, const int32_t* enc_len, int B, int L, int max_length, const lds_lm_decode_opts* opts,
                                       const int64_t* prompt, const int32_t* prompt_len, int P, const float* uniforms, int64_t* tokens, float* logits_out,
                                       int* n_tokens_host, void* ws, size_t ws_bytes, void* stream) {
-    if (!opts) return lm_fail(LDS_EINVAL, "null options");
+    if (!opts) return set_error(LDS_EINVAL, "null options");
     const lds_lm_decode_opts o = *opts;
     if (int r = lm_check_opts(o, logits_out)) return r;
-    if (o.num_beams > 1) return lm_fail(LDS_EINVAL, "beam search from a prompt is not built (num_beams must be 1 with a prompt)");
+    if (o.num_beams > 1) return set_error(LDS_EINVAL, "beam search from a prompt is not built (num_beams must be 1 with a prompt)");
     if (int r = lm_prompt_check(B, L, max_length, P)) return r;
     int Pmax = 0, Pmin = P;
     for (int b = 0; b < B; ++b) {
         const int pl = prompt_len ? prompt_len[b] : P;
-        if (pl < 1 || pl > P) return lm_fail(LDS_EINVAL, "prompt_len[%d] = %d out of range (1 .. P = %d)", b, pl, P);
-        if (pl >= max_length) return lm_fail(LDS_EINVAL, "prompt_len[%d] = %d leaves no room below max_length = %d (the total length, prompt included)", b, pl, max_length);
+        if (pl < 1 || pl > P) return set_error(LDS_EINVAL, "prompt_len[%d] = %d out of range (1 .. P = %d)", b, pl, P);
+        if (pl >= max_length) return set_error(LDS_EINVAL, "prompt_len[%d] = %d leaves no room below max_length = %d (the total length, prompt included)", b, pl, max_length);
         Pmax = pl > Pmax ? pl : Pmax;
         Pmin = pl < Pmin ? pl : Pmin;
     }
-    if (!lm || !enc || !tokens || !n_tokens_host || !ws || !prompt) return lm_fail(LDS_EINVAL, "bad argument");
+    if (!lm || !enc || !tokens || !n_tokens_host || !ws || !prompt) return set_error(LDS_EINVAL, "bad argument");
     {   // the workspace is checked against the prompted plan whatever the lengths are
-        LmArena A(ws, ws_bytes);
+        Arena A(ws, ws_bytes);
         LmWs w;
         lm_plan(lm, A, B, L, max_length, w, 1, P);
-        if (!A.ok) return lm_fail(LDS_ENOMEM, "LM workspace too small: need %zu bytes", A.used);
+        if (!A.ok) return set_error(LDS_ENOMEM, "LM workspace too small: need %zu bytes", A.used);
     }
     // every row is BOS alone: the plain decode, through its own launches (its plan is a prefix of the prompted one when P > 1)
     if (Pmax == 1) return lds_lm_generate_opts(lm, enc, enc_len, B, L, max_length, opts, uniforms, tokens, logits_out, n_tokens_host, ws, ws_bytes, stream);
@@ -1699,14 +1653,14 @@ extern "C" int lds_lm_generate_prompt(lds_lm* lm, const float* enc, const int32_
     const int do_sample = o.do_sample, top_k = o.top_k;
     const float top_p = o.top_p, temperature = o.temperature;
     if (do_sample && (!uniforms || top_k < 0 || top_k > kMaxTopK || top_k > c.sem_vocab || !(top_p > 0.f) || !(temperature > 0.f)))
-        return lm_fail(LDS_EINVAL, "sampling needs uniforms, 0 <= top_k <= %d (0 = no top-k filter), top_p > 0, temperature > 0", kMaxTopK);
-    if (do_sample && top_k == 0 && (size_t)c.sem_vocab * sizeof(float) > 60 * 1024) return lm_fail(LDS_EINVAL, "top_k = 0 needs the vocabulary row in LDS (<= 15360 entries)");
-    if (max_length > c.max_pos) return lm_fail(LDS_EINVAL, "max_length exceeds max_position_embeddings");
+        return set_error(LDS_EINVAL, "sampling needs uniforms, 0 <= top_k <= %d (0 = no top-k filter), top_p > 0, temperature > 0", kMaxTopK);
+    if (do_sample && top_k == 0 && (size_t)c.sem_vocab * sizeof(float) > 60 * 1024) return set_error(LDS_EINVAL, "top_k = 0 needs the vocabulary row in LDS (<= 15360 entries)");
+    if (max_length > c.max_pos) return set_error(LDS_EINVAL, "max_length exceeds max_position_embeddings");
     if (L > c.max_pos || (size_t)(((L + 63) & ~63) + 4 * 34) * sizeof(float) > 64 * 1024)
-        return lm_fail(LDS_EINVAL, "encoder length %d out of range (1 .. min(max_position_embeddings = %d, 16000))", L, c.max_pos);
-    if ((size_t)(((max_length + 63) & ~63) + 4 * 34) * sizeof(float) > 64 * 1024) return lm_fail(LDS_EINVAL, "max_length %d too long for a prompted decode (<= 16000)", max_length);
+        return set_error(LDS_EINVAL, "encoder length %d out of range (1 .. min(max_position_embeddings = %d, 16000))", L, c.max_pos);
+    if ((size_t)(((max_length + 63) & ~63) + 4 * 34) * sizeof(float) > 64 * 1024) return set_error(LDS_EINVAL, "max_length %d too long for a prompted decode (<= 16000)", max_length);
     hipStream_t st = (hipStream_t)stream;
-    LmArena A(ws, ws_bytes);
+    Arena A(ws, ws_bytes);
     LmWs w;
     lm_plan(lm, A, B, L, max_length, w, 1, P);
     const int H = c.hidden, V = c.sem_vocab, Pq = Pmax - 1;
@@ -1715,24 +1669,24 @@ extern "C" int lds_lm_generate_prompt(lds_lm* lm, const float* enc, const int32_
     int* rowlen = w.flags + B + max_length;          // [B <= 64]: every row's final length, prompt included
     for (int i = 0; i < c.dec_layers; ++i) {         // cross-attention keys / values, as in lds_lm_generate_opts
         const LmRows er{const_cast<float*>(enc), nullptr};
-        LM_HIP(lm_dln<0>(lm->dec.layers[i].cross.kv, er, H, nullptr, c.eps, w.kv, 2 * H, B * L, st));
+        HIP_TRY(lm_dln<0>(lm->dec.layers[i].cross.kv, er, H, nullptr, c.eps, w.kv, 2 * H, B * L, st));
         hipLaunchKernelGGL(lm_kv_pack_kernel, dim3((unsigned)(((long long)B * L * H + 255) / 256)), dim3(256), 0, st, w.kv, B, L, H, c.heads, w.ckc[i], w.cvc[i], L);
-        LM_HIP(hipGetLastError());
+        HIP_TRY(hipGetLastError());
     }
     {
         std::vector<int> init(B + max_length + kMaxPromptBatch, 0), pl(B);
         for (int b = 0; b < B; ++b) { init[b] = 1; init[B + max_length + b] = max_length; pl[b] = prompt_len ? prompt_len[b] : P; }
-        LM_HIP(hipMemcpyAsync(unfinished, init.data(), sizeof(int) * init.size(), hipMemcpyHostToDevice, st));
-        LM_HIP(hipMemcpyAsync(w.prompt.plen, pl.data(), sizeof(int) * B, hipMemcpyHostToDevice, st));
-        LM_HIP(hipStreamSynchronize(st));      // the host staging vectors go out of scope
+        HIP_TRY(hipMemcpyAsync(unfinished, init.data(), sizeof(int) * init.size(), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(w.prompt.plen, pl.data(), sizeof(int) * B, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipStreamSynchronize(st));      // the host staging vectors go out of scope
     }
     const int32_t* plen = w.prompt.plen;
     hipLaunchKernelGGL(lm_prompt_init_kernel, dim3(B), dim3(256), 0, st, prompt, P, plen, V, c.sem_pad, max_length, Pq, tokens, w.prompt.ids, w.prompt.last);
-    LM_HIP(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     {   // prefill: positions 0 .. Pq - 1 of every row, keys / values straight into the decode caches (see the invariant above)
         hipLaunchKernelGGL(lm_embed_kernel, dim3(B * Pq), dim3(256), 0, st, lm->dec.word, lm->dec.type, (const float*)nullptr, lm->dec.ln_emb.g, lm->dec.ln_emb.b,
                            (const int64_t*)w.prompt.ids, 1, (const int64_t*)nullptr, (const int64_t*)nullptr, 0, c.eps, H, V, 1, 1, w.x);
-        LM_HIP(hipGetLastError());
+        HIP_TRY(hipGetLastError());
         LmRows px{w.x, nullptr};
         for (int i = 0; i < c.dec_layers; ++i) {
             int r = lm_layer(lm, lm->dec, lm->dec.layers[i], w, px, B, Pq, 0, w.kc[i], w.vc[i], max_length, w.ckc[i], w.cvc[i], L, nullptr, enc_len, st, LmLayerMode::prefill());
@@ -1742,7 +1696,7 @@ extern "C" int lds_lm_generate_prompt(lds_lm* lm, const float* enc, const int32_
     // the first step's input rows: every row's last prompt token; later rows come from the token choice
     hipLaunchKernelGGL(lm_embed_kernel, dim3(B), dim3(256), 0, st, lm->dec.word, lm->dec.type, (const float*)nullptr, lm->dec.ln_emb.g, lm->dec.ln_emb.b,
                        (const int64_t*)w.prompt.last, 1, (const int64_t*)nullptr, (const int64_t*)nullptr, 0, c.eps, H, V, 1, 1, w.x);
-    LM_HIP(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     const float inv_temp = do_sample ? 1.0f / temperature : 1.0f;
     const int n_steps = max_length - Pmin;      // the shortest row writes its last slot at step n_steps - 1
     std::vector<int> host_flags(n_steps, 0);
@@ -1755,15 +1709,15 @@ extern "C" int lds_lm_generate_prompt(lds_lm* lm, const float* enc, const int32_
                              LmLayerMode::rows(plen, Lk_max));
             if (r != LDS_OK) return r;
         }
-        LM_HIP(lm_dln<1>(lm->head_t, cx, H, nullptr, c.eps, w.ctx, H, B, st));
+        HIP_TRY(lm_dln<1>(lm->head_t, cx, H, nullptr, c.eps, w.ctx, H, B, st));
         const LmRows hrows{w.ctx, &lm->head_ln};
         float* lg = logits_out ? logits_out + (size_t)step * B * V : w.logits;
-        LM_HIP(lm_dln<0>(lm->head_d, hrows, H, nullptr, c.eps, lg, V, B, st));
-        LM_HIP(lm_launch_choice_rows(o, B, V, lg, inv_temp, do_sample ? uniforms + (size_t)step * B : nullptr, tokens, max_length, step, unfinished, c.sem_eos,
+        HIP_TRY(lm_dln<0>(lm->head_d, hrows, H, nullptr, c.eps, lg, V, B, st));
+        HIP_TRY(lm_launch_choice_rows(o, B, V, lg, inv_temp, do_sample ? uniforms + (size_t)step * B : nullptr, tokens, max_length, step, unfinished, c.sem_eos,
                                      c.sem_pad, any_unf, lm->dec.word, lm->dec.type, lm->dec.ln_emb.g, lm->dec.ln_emb.b, c.eps, H, w.x, plen, rowlen, st));
         if ((step & 7) == 7 || step + 1 == n_steps) {      // the EOS poll of lds_lm_generate_opts; a row that reached max_length counts as finished
-            LM_HIP(hipMemcpyAsync(host_flags.data() + checked, any_unf + checked, sizeof(int) * (step + 1 - checked), hipMemcpyDeviceToHost, st));
-            LM_HIP(hipStreamSynchronize(st));
+            HIP_TRY(hipMemcpyAsync(host_flags.data() + checked, any_unf + checked, sizeof(int) * (step + 1 - checked), hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
             bool done = false;
             for (int s = checked; s <= step && !done; ++s) done = host_flags[s] == 0;
             checked = step + 1;
@@ -1772,8 +1726,8 @@ extern "C" int lds_lm_generate_prompt(lds_lm* lm, const float* enc, const int32_
     }
     // cropped to the longest row.  (Steps enqueued past the last running row's end only wrote PAD behind finished rows.)
     std::vector<int> len(B, 0);
-    LM_HIP(hipMemcpyAsync(len.data(), rowlen, sizeof(int) * B, hipMemcpyDeviceToHost, st));
-    LM_HIP(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpyAsync(len.data(), rowlen, sizeof(int) * B, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     int n_tokens = 0;
     for (int b = 0; b < B; ++b) n_tokens = len[b] > n_tokens ? len[b] : n_tokens;
     *n_tokens_host = n_tokens;
@@ -1787,7 +1741,7 @@ extern "C" int lds_lm_generate_prompt(lds_lm* lm, const float* enc, const int32_
 namespace {
 constexpr int kScoreChunk = 256;
 struct LmScoreWs { LmWs w; float *kc, *vc, *ckc, *cvc, *chunk; double* psum; int32_t* pcnt; };
-void lm_score_plan(const lds_lm* lm, LmArena& A, int B, int L, int T, LmScoreWs& s) {
+void lm_score_plan(const lds_lm* lm, Arena& A, int B, int L, int T, LmScoreWs& s) {
     const lds_lm_cfg& c = lm->cfg;
     const size_t N = (size_t)B * T, NL = (size_t)B * L, H = c.hidden;
     s.w = LmWs{};
@@ -1800,22 +1754,22 @@ void lm_score_plan(const lds_lm* lm, LmArena& A, int B, int L, int T, LmScoreWs&
     s.pcnt = (int32_t*)A.f((size_t)B);
 }
 int lm_score_check(const lds_lm* lm, int B, int L, int T) {
-    if (!lm || B <= 0) return lm_fail(LDS_EINVAL, "bad argument");
+    if (!lm || B <= 0) return set_error(LDS_EINVAL, "bad argument");
     const lds_lm_cfg& c = lm->cfg;
-    if (T < 2 || T > c.max_pos) return lm_fail(LDS_EINVAL, "sequence length %d out of range (2 .. max_position_embeddings = %d)", T, c.max_pos);
+    if (T < 2 || T > c.max_pos) return set_error(LDS_EINVAL, "sequence length %d out of range (2 .. max_position_embeddings = %d)", T, c.max_pos);
     if (L < 1 || L > c.max_pos || (size_t)(((L + 63) & ~63) + 4 * 34) * sizeof(float) > 64 * 1024)
-        return lm_fail(LDS_EINVAL, "encoder length %d out of range (1 .. min(max_position_embeddings = %d, 16000))", L, c.max_pos);
+        return set_error(LDS_EINVAL, "encoder length %d out of range (1 .. min(max_position_embeddings = %d, 16000))", L, c.max_pos);
     // the causal self-attention stages one score per key in LDS; the linears take 8 rows per workgroup along grid.y
-    if ((size_t)(((T + 63) & ~63) + 4 * 34) * sizeof(float) > 64 * 1024) return lm_fail(LDS_EINVAL, "sequence length %d too long for scoring (<= 16000)", T);
-    if ((long long)B * T > 8 * 65535LL || (long long)B * L > 8 * 65535LL) return lm_fail(LDS_EINVAL, "batch too large for one scoring call (B * T and B * L <= 524280)");
+    if ((size_t)(((T + 63) & ~63) + 4 * 34) * sizeof(float) > 64 * 1024) return set_error(LDS_EINVAL, "sequence length %d too long for scoring (<= 16000)", T);
+    if ((long long)B * T > 8 * 65535LL || (long long)B * L > 8 * 65535LL) return set_error(LDS_EINVAL, "batch too large for one scoring call (B * T and B * L <= 524280)");
     return LDS_OK;
 }
 }  // namespace
 
 extern "C" int lds_lm_score_workspace_bytes(const lds_lm* lm, int B, int L, int T, size_t* out) {
-    if (!out) return lm_fail(LDS_EINVAL, "bad argument");
+    if (!out) return set_error(LDS_EINVAL, "bad argument");
     if (int r = lm_score_check(lm, B, L, T)) return r;
-    LmArena A(nullptr, 0);
+    Arena A(nullptr, 0);
     LmScoreWs s;
     lm_score_plan(lm, A, B, L, T, s);
     *out = A.used;
@@ -1825,38 +1779,38 @@ extern "C" int lds_lm_score_workspace_bytes(const lds_lm* lm, int B, int L, int 
 extern "C" int lds_lm_score(lds_lm* lm, const float* enc, const int32_t* enc_len, int B, int L, const int64_t* semantic, const int32_t* sem_len, const int64_t* labels,
                             int T, float* logprobs, int32_t* ranks, float* loss, int32_t* n_counted, float* logits_out, void* ws, size_t ws_bytes, void* stream) {
     if (int r = lm_score_check(lm, B, L, T)) return r;
-    if (!enc || !semantic || !logprobs || !ranks || !loss || !n_counted || !ws) return lm_fail(LDS_EINVAL, "null argument");
+    if (!enc || !semantic || !logprobs || !ranks || !loss || !n_counted || !ws) return set_error(LDS_EINVAL, "null argument");
     const lds_lm_cfg& c = lm->cfg;
     hipStream_t st = (hipStream_t)stream;
-    LmArena A(ws, ws_bytes);
+    Arena A(ws, ws_bytes);
     LmScoreWs s;
     lm_score_plan(lm, A, B, L, T, s);
-    if (!A.ok) return lm_fail(LDS_ENOMEM, "LM scoring workspace too small: need %zu bytes", A.used);
+    if (!A.ok) return set_error(LDS_ENOMEM, "LM scoring workspace too small: need %zu bytes", A.used);
     const int H = c.hidden, V = c.sem_vocab, N = B * T;
     if (!labels) labels = semantic;
     // ids are clamped to the vocabulary (lm_embed_kernel); rows at and beyond a sequence's length are computed and never counted
     hipLaunchKernelGGL(lm_embed_kernel, dim3(N), dim3(256), 0, st, lm->dec.word, lm->dec.type, (const float*)nullptr, lm->dec.ln_emb.g, lm->dec.ln_emb.b, semantic, 1,
                        (const int64_t*)nullptr, (const int64_t*)nullptr, 0, c.eps, H, V, 1, 1, s.w.x);
-    LM_HIP(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     LmRows cx{s.w.x, nullptr};
     for (int i = 0; i < c.dec_layers; ++i) {
         const LmRows er{const_cast<float*>(enc), nullptr};
-        LM_HIP(lm_dln<0>(lm->dec.layers[i].cross.kv, er, H, nullptr, c.eps, s.w.kv, 2 * H, B * L, st));
+        HIP_TRY(lm_dln<0>(lm->dec.layers[i].cross.kv, er, H, nullptr, c.eps, s.w.kv, 2 * H, B * L, st));
         hipLaunchKernelGGL(lm_kv_pack_kernel, dim3((unsigned)(((long long)B * L * H + 255) / 256)), dim3(256), 0, st, s.w.kv, B, L, H, c.heads, s.ckc, s.cvc, L);
-        LM_HIP(hipGetLastError());
+        HIP_TRY(hipGetLastError());
         int r = lm_layer(lm, lm->dec, lm->dec.layers[i], s.w, cx, B, T, 0, s.kc, s.vc, T, s.ckc, s.cvc, L, nullptr, enc_len, st, LmLayerMode::prefill());
         if (r != LDS_OK) return r;
     }
     // LM head as in the decode: h = GELU(W_t LN(x)) stored un-normalised, logits = W_d LN(h), the latter chunk by chunk
-    LM_HIP(lm_dln<1>(lm->head_t, cx, H, nullptr, c.eps, s.w.ctx, H, N, st));
+    HIP_TRY(lm_dln<1>(lm->head_t, cx, H, nullptr, c.eps, s.w.ctx, H, N, st));
     for (int r0 = 0; r0 < N; r0 += kScoreChunk) {
         const int rows = (N - r0 < kScoreChunk) ? N - r0 : kScoreChunk;
         const LmRows hrows{s.w.ctx + (size_t)r0 * H, &lm->head_ln};
         float* lg = logits_out ? logits_out + (size_t)r0 * V : s.chunk;
-        LM_HIP(lm_dln<0>(lm->head_d, hrows, H, nullptr, c.eps, lg, V, rows, st));
-        LM_HIP(lm_launch_score_rows(lg, r0, rows, V, T, labels, sem_len, logprobs, ranks, st));
+        HIP_TRY(lm_dln<0>(lm->head_d, hrows, H, nullptr, c.eps, lg, V, rows, st));
+        HIP_TRY(lm_launch_score_rows(lg, r0, rows, V, T, labels, sem_len, logprobs, ranks, st));
     }
-    LM_HIP(lm_launch_score_loss(logprobs, ranks, B, T - 1, s.psum, s.pcnt, loss, n_counted, st));
+    HIP_TRY(lm_launch_score_loss(logprobs, ranks, B, T - 1, s.psum, s.pcnt, loss, n_counted, st));
     return LDS_OK;
 }
 
@@ -1878,19 +1832,19 @@ hipError_t lds::lm_launch_score_loss(const float* lp, const int32_t* rank, int B
 // per row (hist [B][n_hist] int64, dev; what the repetition penalty looks at).  out [B] int64 (dev).  top_k 0 = no top-k filter.
 extern "C" int lds_test_lm_sample(const float* logits, int B, int V, int do_sample, int top_k, float top_p, float temperature, float repetition_penalty,
                                   const float* uniforms, const int64_t* hist, int n_hist, int64_t* out, void* stream) {
-    if (!logits || !out || B <= 0 || V <= 0 || V > 256 * 32 || n_hist < 1 || !hist || (do_sample && !uniforms) || top_k < 0 || top_k > kMaxTopK) return lm_fail(LDS_EINVAL, "bad argument");
+    if (!logits || !out || B <= 0 || V <= 0 || V > 256 * 32 || n_hist < 1 || !hist || (do_sample && !uniforms) || top_k < 0 || top_k > kMaxTopK) return set_error(LDS_EINVAL, "bad argument");
     hipStream_t st = (hipStream_t)stream;
     const int cap = n_hist + 1;
     int64_t* seq = nullptr;
     int* flags = nullptr;
-    if (hipMalloc(&seq, sizeof(int64_t) * B * cap) != hipSuccess || hipMalloc(&flags, sizeof(int) * (B + cap)) != hipSuccess) return lm_fail(LDS_ENOMEM, "alloc");
+    if (hipMalloc(&seq, sizeof(int64_t) * B * cap) != hipSuccess || hipMalloc(&flags, sizeof(int) * (B + cap)) != hipSuccess) return set_error(LDS_ENOMEM, "alloc");
     std::vector<int> init(B + cap, 0);
     for (int b = 0; b < B; ++b) init[b] = 1;
     int rc = LDS_OK;
     do {
-        if (hipMemcpy(flags, init.data(), sizeof(int) * (B + cap), hipMemcpyHostToDevice) != hipSuccess) { rc = lm_fail(LDS_EHIP, "copy"); break; }
+        if (hipMemcpy(flags, init.data(), sizeof(int) * (B + cap), hipMemcpyHostToDevice) != hipSuccess) { rc = set_error(LDS_EHIP, "copy"); break; }
         if (hipMemcpy2DAsync(seq, sizeof(int64_t) * cap, hist, sizeof(int64_t) * n_hist, sizeof(int64_t) * n_hist, B, hipMemcpyDeviceToDevice, st) != hipSuccess) {
-            rc = lm_fail(LDS_EHIP, "copy"); break;
+            rc = set_error(LDS_EHIP, "copy"); break;
         }
         const float inv_temp = do_sample ? 1.0f / temperature : 1.0f;
         const int step = n_hist - 1;
@@ -1907,11 +1861,11 @@ extern "C" int lds_test_lm_sample(const float* logits, int B, int V, int do_samp
         else
             hipLaunchKernelGGL(lm_sample_kernel<32>, dim3(B), dim3(256), 0, st, logits, V, do_sample, do_sample ? top_k : 1, top_p, inv_temp, repetition_penalty, uniforms, seq, cap,
                                step, flags, -1, -1, flags + B, nf, nf, nf, nf, 0.f, 0, (float*)nullptr);
-        if (hipGetLastError() != hipSuccess) { rc = lm_fail(LDS_EHIP, "launch"); break; }
+        if (hipGetLastError() != hipSuccess) { rc = set_error(LDS_EHIP, "launch"); break; }
         if (hipMemcpy2DAsync(out, sizeof(int64_t), seq + n_hist, sizeof(int64_t) * cap, sizeof(int64_t), B, hipMemcpyDeviceToDevice, st) != hipSuccess) {
-            rc = lm_fail(LDS_EHIP, "copy"); break;
+            rc = set_error(LDS_EHIP, "copy"); break;
         }
-        if (hipStreamSynchronize(st) != hipSuccess) rc = lm_fail(LDS_EHIP, "sync");
+        if (hipStreamSynchronize(st) != hipSuccess) rc = set_error(LDS_EHIP, "sync");
     } while (0);
     (void)hipFree(seq);
     (void)hipFree(flags);
@@ -1928,18 +1882,18 @@ extern "C" int lds_test_lm_beam_step(const float* logits, int B, int K, int V, i
                                      int32_t* fin_len_out, int32_t* unsat_out, int32_t* flag_out, void* stream) {
     if (!logits || !run_seq || !run_score || !fin_seq || !fin_score || !fin_flag || !fin_len || !unsat || !run_seq_out || !run_score_out || !parent_out ||
         !fin_seq_out || !fin_score_out || !fin_flag_out || !fin_len_out || !unsat_out || !flag_out)
-        return lm_fail(LDS_EINVAL, "null argument");
+        return set_error(LDS_EINVAL, "null argument");
     if (B <= 0 || K < 1 || K > kMaxBeams || V < 2 * K || V > kMaxBeamVocab || cur_len < 1 || cur_len >= max_length || no_repeat_ngram_size < 0 ||
         early_stopping < 0 || early_stopping > 2)
-        return lm_fail(LDS_EINVAL, "bad argument");
+        return set_error(LDS_EINVAL, "bad argument");
     hipStream_t st = (hipStream_t)stream;
     const LmBeamState bs{run_seq, run_seq_out, run_score, run_score_out, nullptr, nullptr, fin_seq, fin_seq_out, fin_score, fin_score_out, fin_flag, fin_flag_out,
                          fin_len, fin_len_out, unsat, unsat_out, parent_out, nullptr, flag_out};
-    if (hipMemsetAsync(flag_out, 0, sizeof(int32_t), st) != hipSuccess) return lm_fail(LDS_EHIP, "memset");
+    if (hipMemsetAsync(flag_out, 0, sizeof(int32_t), st) != hipSuccess) return set_error(LDS_EHIP, "memset");
     const float* nf = nullptr;
     if (lm_launch_beam_step(B, K, V, logits, cur_len - 1, max_length, max_length, eos, repetition_penalty, no_repeat_ngram_size, early_stopping, bs, nf, nf, nf, nf,
                             0.f, 0, nullptr, st) != hipSuccess)
-        return lm_fail(LDS_EHIP, "launch");
-    if (hipStreamSynchronize(st) != hipSuccess) return lm_fail(LDS_EHIP, "sync");
+        return set_error(LDS_EHIP, "launch");
+    if (hipStreamSynchronize(st) != hipSuccess) return set_error(LDS_EHIP, "sync");
     return LDS_OK;
 }

@@ -6,6 +6,7 @@
 #include "k4p.h"
 #include "k8b3.h"
 #include "kernels.h"
+#include "host.h"
 
 #include <math.h>
 #include <stdarg.h>
@@ -26,13 +27,6 @@ using namespace lds;
 // errors
 // ------------------------------------------------------------------------------------------------
 static thread_local char g_err[512] = "";
-static int fail(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
 int lds::set_error(int code, const char* fmt, ...) {
     va_list ap;
     va_start(ap, fmt);
@@ -42,17 +36,6 @@ int lds::set_error(int code, const char* fmt, ...) {
 }
 extern "C" const char* lds_last_error(void) { return g_err; }
 extern "C" int lds_version(void) { return 1; }
-
-#define HIP_TRY(expr)                                                                              \
-    do {                                                                                           \
-        hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess) return fail(LDS_EHIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
-#define LDS_TRY(expr)                    \
-    do {                                 \
-        int r_ = (expr);                 \
-        if (r_ != LDS_OK) return r_;     \
-    } while (0)
 
 // ------------------------------------------------------------------------------------------------
 // event profiler (off by default; bench.py turns it on for one instrumented pass)
@@ -157,7 +140,7 @@ extern "C" int lds_prof_summary(char* buf, size_t cap) {
         float ms = 0.f;
         if (r.ia < 0 && r.ib < 0) continue;      // an attachable scope whose launcher did not take the events (nothing was launched)
         if (r.ib < 0 || hipEventSynchronize(g_prof_ev[r.ib]) != hipSuccess || hipEventElapsedTime(&ms, g_prof_ev[r.ia], g_prof_ev[r.ib]) != hipSuccess)
-            return fail(LDS_EHIP, "profiler event read failed");
+            return set_error(LDS_EHIP, "profiler event read failed");
         Agg& a = agg[r.name];
         a.n++; a.ms += ms; a.fl += r.flops; a.by += r.bytes;
     }
@@ -171,55 +154,14 @@ extern "C" int lds_prof_summary(char* buf, size_t cap) {
         first = false;
     }
     out += "]";
-    if (out.size() + 1 > cap) return fail(LDS_ENOMEM, "profile summary needs %zu bytes", out.size() + 1);
+    if (out.size() + 1 > cap) return set_error(LDS_ENOMEM, "profile summary needs %zu bytes", out.size() + 1);
     memcpy(buf, out.c_str(), out.size() + 1);
     return LDS_OK;
 }
 
 // ------------------------------------------------------------------------------------------------
-// device allocations owned by a handle
+// weight packing (Owner, Tensors: host.h)
 // ------------------------------------------------------------------------------------------------
-struct Owner {
-    std::vector<void*> ptrs;
-    ~Owner() {
-        for (void* p : ptrs) (void)hipFree(p);
-    }
-    float* upload(const std::vector<float>& h) {
-        void* d = nullptr;
-        if (hipMalloc(&d, h.size() * sizeof(float)) != hipSuccess) return nullptr;
-        if (hipMemcpy(d, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
-            (void)hipFree(d);
-            return nullptr;
-        }
-        ptrs.push_back(d);
-        return (float*)d;
-    }
-    void* upload_bytes(const void* h, size_t n) {
-        void* d = nullptr;
-        if (hipMalloc(&d, n) != hipSuccess) return nullptr;
-        if (hipMemcpy(d, h, n, hipMemcpyHostToDevice) != hipSuccess) {
-            (void)hipFree(d);
-            return nullptr;
-        }
-        ptrs.push_back(d);
-        return d;
-    }
-};
-
-struct Tensors {
-    std::map<std::string, std::pair<const float*, int64_t>> m;
-    std::string missing;
-    const float* get(const std::string& k, int64_t numel) {
-        auto it = m.find(k);
-        if (it == m.end() || it->second.second != numel) {
-            if (missing.empty()) missing = k + (it == m.end() ? " (absent)" : " (wrong size)");
-            return nullptr;
-        }
-        return it->second.first;
-    }
-    bool has(const std::string& k) const { return m.count(k) != 0; }
-};
-
 // packed conv / linear weights: [KT][Ci][Mp] + bias[Mp]
 struct ConvW {
     float* w = nullptr;
@@ -415,23 +357,6 @@ static bool pack_convT(Owner& o, const float* w, const float* b, int Ci, int Co,
 }
 
 // ------------------------------------------------------------------------------------------------
-// workspace bump allocator (caller-owned memory)
-// ------------------------------------------------------------------------------------------------
-struct Arena {
-    char* base; size_t cap; size_t used = 0; bool ok = true;
-    std::vector<std::pair<std::string, std::pair<size_t, size_t>>>* log = nullptr;      // (name, (offset, bytes)) of every slot: lds_debug_unet_plan
-    Arena(void* p, size_t n) : base((char*)p), cap(n) {}
-    float* f(size_t n_floats, const char* name = nullptr) {
-        size_t bytes = (n_floats * sizeof(float) + 255) & ~(size_t)255;
-        if (base && used + bytes > cap) ok = false;
-        char* p = base ? base + used : nullptr;
-        if (log) log->push_back({name ? name : "slot" + std::to_string(log->size()), {used, bytes}});
-        used += bytes;
-        return (float*)p;
-    }
-};
-
-// ------------------------------------------------------------------------------------------------
 // conv helper
 // ------------------------------------------------------------------------------------------------
 struct Src {
@@ -458,7 +383,7 @@ static int run_conv(const ConvW& W, const Src& s, const ConvOpt& o, float* out, 
     a.act_in = o.act_in; a.slope = o.slope;
     a.bias = W.bias; a.bias_bc = o.bias_bc; a.res = o.res; a.epi = o.epi; a.accum = o.accum; a.out_div = o.out_div;
     a.out = out;
-    if (s.C1 + s.C2 != W.Ci) return fail(LDS_EINVAL, "conv: input channels %d+%d != %d", s.C1, s.C2, W.Ci);
+    if (s.C1 + s.C2 != W.Ci) return set_error(LDS_EINVAL, "conv: input channels %d+%d != %d", s.C1, s.C2, W.Ci);
     const int To_nat = (a.Tin + 2 * o.pad - o.dil * (W.K - 1) - 1) / o.stride + 1;
     a.To = o.To > 0 ? o.To : To_nat;
     a.Tout = o.Tout > 0 ? o.Tout : a.To;
@@ -487,7 +412,7 @@ static int run_conv(const ConvW& W, const Src& s, const ConvOpt& o, float* out, 
         }
     }
     if (e != hipSuccess)
-        return fail(LDS_EHIP, "conv_gemm launch failed (%s): Co %d Ci %d K %d stride %d dil %d ups %d To %d", hipGetErrorString(e), W.Co,
+        return set_error(LDS_EHIP, "conv_gemm launch failed (%s): Co %d Ci %d K %d stride %d dil %d ups %d To %d", hipGetErrorString(e), W.Co,
                     W.Ci, W.K, o.stride, o.dil, o.ups, a.To);
     return LDS_OK;
 }
@@ -568,7 +493,7 @@ extern "C" int lds_debug_trace_count(void) {
 }
 extern "C" int lds_debug_trace_get(int i, char* name, size_t name_cap, const void** data, size_t* bytes) {
     std::lock_guard<std::mutex> lk(g_trace_mu);
-    if (i < 0 || i >= (int)g_trace.size() || !name || !data || !bytes || name_cap == 0) return fail(LDS_EINVAL, "bad argument");
+    if (i < 0 || i >= (int)g_trace.size() || !name || !data || !bytes || name_cap == 0) return set_error(LDS_EINVAL, "bad argument");
     snprintf(name, name_cap, "%s", g_trace[i].name.c_str());
     *data = g_trace[i].bytes.data();
     *bytes = g_trace[i].bytes.size();
@@ -576,7 +501,7 @@ extern "C" int lds_debug_trace_get(int i, char* name, size_t name_cap, const voi
 }
 // every 32-bit word of a device buffer = pattern (tests poison a workspace with NaN patterns: a kernel that reads what no kernel of the call wrote shows)
 extern "C" int lds_debug_fill_u32(void* dev, size_t n_words, uint32_t pattern, void* stream) {
-    if (!dev) return fail(LDS_EINVAL, "bad argument");
+    if (!dev) return set_error(LDS_EINVAL, "bad argument");
     HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)dev, (int)pattern, n_words, (hipStream_t)stream));
     return LDS_OK;
 }
@@ -587,7 +512,7 @@ static int fill_dconv(const ConvW& W, const float* x1, int C1, const float* x2, 
     a.lens = tl_lens; a.lvl_in = o.lvl_in; a.lvl_out = o.lvl_out;
     a.vlen = o.vlen;
     a.kpart = tl_kpart; a.kcount = tl_kcount; a.kpart_cap = kClusterPartFloats; a.kcount_cap = kClusterCounters;
-    if (C1 + C2 != W.Ci) return fail(LDS_EINVAL, "dconv: input channels %d+%d != %d", C1, C2, W.Ci);
+    if (C1 + C2 != W.Ci) return set_error(LDS_EINVAL, "dconv: input channels %d+%d != %d", C1, C2, W.Ci);
     a.x1 = x1; a.x2 = x2 ? x2 : x1; a.C1 = C1; a.C2 = C2; a.Tsrc = Tsrc;
     a.w = W.w; a.bias = W.bias; a.Mp = W.Mp; a.Co = W.Co; a.Ci = W.Ci; a.KT = W.K;
     a.stride = o.stride; a.pad = o.pad; a.ups = o.ups;
@@ -628,7 +553,7 @@ static int run_dconv(const ConvW& W, const float* x1, int C1, const float* x2, i
         }
     }
     if (e != hipSuccess)
-        return fail(LDS_EHIP, "conv_dma launch failed (%s): Co %d Ci %d K %d stride %d ups %d To %d", hipGetErrorString(e), W.Co, W.Ci, W.K,
+        return set_error(LDS_EHIP, "conv_dma launch failed (%s): Co %d Ci %d K %d stride %d ups %d To %d", hipGetErrorString(e), W.Co, W.Ci, W.K,
                     o.stride, o.ups, a.To);
     return LDS_OK;
 }
@@ -639,7 +564,7 @@ static int run_dconv_bf3(const ConvW& W, const void* x1, int C1, const void* x2,
     int rc = fill_dconv(W, (const float*)x1, C1, (const float*)x2, C2, Tsrc, o, (float*)out, B, a);
     if (rc != LDS_OK) return rc;
     const void* wsp = (fmt == FMT_F16X2) ? W.wh : W.w3;
-    if (!wsp) return fail(LDS_EINVAL, "split weights were not packed for this layer");
+    if (!wsp) return set_error(LDS_EINVAL, "split weights were not packed for this layer");
     a.w = (const float*)wsp;
     a.x2 = (const float*)x2;      // null = one source (fill_dconv aliases x1 for the fp32 kernel)
     a.out_f32 = o.out_f32;
@@ -662,7 +587,7 @@ static int run_dconv_bf3(const ConvW& W, const void* x1, int C1, const void* x2,
         }
     }
     if (e != hipSuccess)
-        return fail(LDS_EHIP, "conv_bf3 launch failed (%s): Co %d Ci %d K %d stride %d ups %d To %d cfg %d", hipGetErrorString(e), W.Co, W.Ci, W.K, o.stride,
+        return set_error(LDS_EHIP, "conv_bf3 launch failed (%s): Co %d Ci %d K %d stride %d ups %d To %d cfg %d", hipGetErrorString(e), W.Co, W.Ci, W.K, o.stride,
                     o.ups, a.To, o.cfg);
     return LDS_OK;
 }
@@ -705,7 +630,7 @@ static int run_dconv_pair(const ConvW& W3, const float* h, const ConvW& W1, cons
             ps.rename(nm);
         }
     }
-    if (e != hipSuccess) return fail(LDS_EHIP, "conv_dma pair launch failed (%s): Co %d Ci %d+%d To %d", hipGetErrorString(e), W3.Co, W3.Ci, W1.Ci, a1.To);
+    if (e != hipSuccess) return set_error(LDS_EHIP, "conv_dma pair launch failed (%s): Co %d Ci %d+%d To %d", hipGetErrorString(e), W3.Co, W3.Ci, W1.Ci, a1.To);
     return LDS_OK;
 }
 
@@ -723,8 +648,8 @@ static int run_dconv_pair_bf3(const ConvW& W3, const void* h, const ConvW& W1, c
     rc = fill_dconv(W1, (const float*)x1, C1, (const float*)x2, C2, T, o1, (float*)out, B, a1);
     if (rc != LDS_OK) return rc;
     const void *w3p = (fmt == FMT_F16X2) ? W3.wh : W3.w3, *w1p = (fmt == FMT_F16X2) ? W1.wh : W1.w3;
-    if (!w3p || !w1p) return fail(LDS_EINVAL, "split weights were not packed for this layer");
-    if (fmt == FMT_F16X2 && W3.wh_inv != W1.wh_inv) return fail(LDS_EINVAL, "internal: the pair's fp16 weight scales differ");
+    if (!w3p || !w1p) return set_error(LDS_EINVAL, "split weights were not packed for this layer");
+    if (fmt == FMT_F16X2 && W3.wh_inv != W1.wh_inv) return set_error(LDS_EINVAL, "internal: the pair's fp16 weight scales differ");
     a3.w = (const float*)w3p; a1.w = (const float*)w1p;
     a3.acc_scale = a1.acc_scale = (fmt == FMT_F16X2) ? W1.wh_inv : 0.f;
     a3.x2 = nullptr; a1.x2 = (const float*)x2;
@@ -748,7 +673,7 @@ static int run_dconv_pair_bf3(const ConvW& W3, const void* h, const ConvW& W1, c
             ps.rename(nm);
         }
     }
-    if (e != hipSuccess) return fail(LDS_EHIP, "conv_bf3 pair launch failed (%s): Co %d Ci %d+%d To %d", hipGetErrorString(e), W3.Co, W3.Ci, W1.Ci, a1.To);
+    if (e != hipSuccess) return set_error(LDS_EHIP, "conv_bf3 pair launch failed (%s): Co %d Ci %d+%d To %d", hipGetErrorString(e), W3.Co, W3.Ci, W1.Ci, a1.To);
     return LDS_OK;
 }
 
@@ -774,7 +699,7 @@ static bool wino_routed_any_T(int Ci, int Co) { return wino_min_T(Ci, Co) > 0; }
 // A resnet's k 3 convolution over the planes `v` that launch_gn_wino wrote (W.wu: its packed taps).  The profiler's record carries the
 // algorithmic FLOP of the convolution it replaces, 2 B T Co Ci 3 -- the figure every other family reports -- not the two thirds it executes.
 static int run_wconv(const ConvW& W, const float* v, int T, const float* res, float2* gnpart_out, float* out, int B, hipStream_t st, int lvl, int cfg = 0) {
-    if (!W.wu || W.K != 3) return fail(LDS_EINVAL, "wconv: the Winograd taps were not packed for this layer");
+    if (!W.wu || W.K != 3) return set_error(LDS_EINVAL, "wconv: the Winograd taps were not packed for this layer");
     WinoConvArgs a{};
     a.v = v; a.u = W.wu; a.bias = W.bias; a.res = res; a.out = out; a.gnpart_out = gnpart_out;
     a.lens = tl_lens; a.lvl = lvl;
@@ -796,7 +721,7 @@ static int run_wconv(const ConvW& W, const float* v, int T, const float* res, fl
             ps.rename(nm);
         }
     }
-    if (e != hipSuccess) return fail(LDS_EHIP, "conv_wino launch failed (%s): Co %d Ci %d T %d cfg %d", hipGetErrorString(e), W.Co, W.Ci, T, cfg);
+    if (e != hipSuccess) return set_error(LDS_EHIP, "conv_wino launch failed (%s): Co %d Ci %d T %d cfg %d", hipGetErrorString(e), W.Co, W.Ci, T, cfg);
     return LDS_OK;
 }
 
@@ -983,8 +908,8 @@ static bool load_tfm(lds_unet* u, Tensors& T, const std::string& p, int C, TfmW&
 
 extern "C" int lds_unet_create(const lds_unet_cfg* cfg, int n, const char* const* names, const float* const* ptrs,
                                const int64_t* numel, lds_unet** out) {
-    if (!cfg || !names || !ptrs || !numel || !out) return fail(LDS_EINVAL, "null argument");
-    if (cfg->n_blocks < 2 || cfg->n_blocks > 8) return fail(LDS_EINVAL, "n_blocks %d unsupported", cfg->n_blocks);
+    if (!cfg || !names || !ptrs || !numel || !out) return set_error(LDS_EINVAL, "null argument");
+    if (cfg->n_blocks < 2 || cfg->n_blocks > 8) return set_error(LDS_EINVAL, "n_blocks %d unsupported", cfg->n_blocks);
     Tensors T;
     for (int i = 0; i < n; ++i) T.m[names[i]] = {ptrs[i], numel[i]};
     lds_unet* u = new lds_unet();
@@ -999,10 +924,10 @@ extern "C" int lds_unet_create(const lds_unet_cfg* cfg, int n, const char* const
         // 16 * groups: GroupNorm statistics travel as 16-channel partials, and a skip-concat's groups must be made of whole ones
         if (boc[i] % 64 != 0 || cfg->norm_groups <= 0 || boc[i] % (16 * cfg->norm_groups) != 0 || (hd != 32 && hd != 48 && hd != 64)) {
             delete u;
-            return fail(LDS_EINVAL, "block_out_channels[%d]=%d unsupported (need a multiple of 64 and of 16*norm_groups, head dim 32/48/64)", i, boc[i]);
+            return set_error(LDS_EINVAL, "block_out_channels[%d]=%d unsupported (need a multiple of 64 and of 16*norm_groups, head dim 32/48/64)", i, boc[i]);
         }
     }
-    if ((u->M % 16) || (u->H % 16)) { delete u; return fail(LDS_EINVAL, "out_dims and n_hidden must be multiples of 16"); }
+    if ((u->M % 16) || (u->H % 16)) { delete u; return set_error(LDS_EINVAL, "out_dims and n_hidden must be multiples of 16"); }
     Owner& o = u->own;
     bool ok = true;
     std::vector<float> tpw, tpb;
@@ -1116,8 +1041,8 @@ extern "C" int lds_unet_create(const lds_unet_cfg* cfg, int n, const char* const
     if (!ok) {
         std::string miss = T.missing;
         delete u;
-        if (!miss.empty()) return fail(LDS_EMISSING, "weight tensor %s", miss.c_str());
-        return fail(LDS_ENOMEM, "device allocation / upload failed while packing weights");
+        if (!miss.empty()) return set_error(LDS_EMISSING, "weight tensor %s", miss.c_str());
+        return set_error(LDS_ENOMEM, "device allocation / upload failed while packing weights");
     }
     *out = u;
     return LDS_OK;
@@ -1152,12 +1077,12 @@ static bool unet_pack_split(lds_unet* u, int fmt) {
 }
 extern "C" int lds_unet_set_gemm_mode(lds_unet* u, int mode) {
     if (u && mode == LDS_GEMM_SPLIT_BF16)
-        return fail(LDS_EINVAL, "the split-bf16 UNet mode was removed in round 4: lossless but no faster than exact fp32 (DESIGN 10.1); the kernel format remains (lds_test_dconv_split)");
-    if (!u || (mode != LDS_GEMM_F32 && mode != LDS_GEMM_SPLIT_F16)) return fail(LDS_EINVAL, "bad argument");
-    if (u->in_calls.load(std::memory_order_acquire) > 0) return fail(LDS_EBUSY, "a forward / sampler call of this handle is in progress on another thread");
+        return set_error(LDS_EINVAL, "the split-bf16 UNet mode was removed in round 4: lossless but no faster than exact fp32 (DESIGN 10.1); the kernel format remains (lds_test_dconv_split)");
+    if (!u || (mode != LDS_GEMM_F32 && mode != LDS_GEMM_SPLIT_F16)) return set_error(LDS_EINVAL, "bad argument");
+    if (u->in_calls.load(std::memory_order_acquire) > 0) return set_error(LDS_EBUSY, "a forward / sampler call of this handle is in progress on another thread");
     if (mode != LDS_GEMM_F32 && !u->split_packed[mode - 1]) {
-        if (u->M % 16 || u->H % 16) return fail(LDS_EINVAL, "split GEMM modes need out_dims and n_hidden to be multiples of 16");
-        if (!unet_pack_split(u, mode - 1)) return fail(LDS_ENOMEM, "packing the split weights failed");
+        if (u->M % 16 || u->H % 16) return set_error(LDS_EINVAL, "split GEMM modes need out_dims and n_hidden to be multiples of 16");
+        if (!unet_pack_split(u, mode - 1)) return set_error(LDS_ENOMEM, "packing the split weights failed");
         u->split_packed[mode - 1] = true;
     }
     u->gemm_mode = mode;
@@ -1165,8 +1090,8 @@ extern "C" int lds_unet_set_gemm_mode(lds_unet* u, int mode) {
 }
 extern "C" int lds_unet_get_gemm_mode(const lds_unet* u) { return u ? u->gemm_mode : LDS_EINVAL; }
 extern "C" int lds_unet_set_latency_mode(lds_unet* u, int on) {
-    if (!u || (on != 0 && on != 1)) return fail(LDS_EINVAL, "bad argument");
-    if (u->in_calls.load(std::memory_order_acquire) > 0) return fail(LDS_EBUSY, "a forward / sampler call of this handle is in progress on another thread");
+    if (!u || (on != 0 && on != 1)) return set_error(LDS_EINVAL, "bad argument");
+    if (u->in_calls.load(std::memory_order_acquire) > 0) return set_error(LDS_EBUSY, "a forward / sampler call of this handle is in progress on another thread");
     u->latency_mode = on;
     return LDS_OK;
 }
@@ -1280,7 +1205,7 @@ static void plan_ws(const lds_unet* u, Arena& A, int B, int T, UnetWs& w) {
 
 // the workspace plan of a forward as text, one slot per line: "name offset bytes" (tools/diag_poison.py fills one slot at a time)
 extern "C" int lds_debug_unet_plan(const lds_unet* u, int B, int T, char* buf, size_t cap) {
-    if (!u || !buf || B <= 0 || T <= 0) return fail(LDS_EINVAL, "bad argument");
+    if (!u || !buf || B <= 0 || T <= 0) return set_error(LDS_EINVAL, "bad argument");
     std::vector<std::pair<std::string, std::pair<size_t, size_t>>> log;
     Arena A(nullptr, 0);
     A.log = &log;
@@ -1288,13 +1213,13 @@ extern "C" int lds_debug_unet_plan(const lds_unet* u, int B, int T, char* buf, s
     plan_ws(u, A, B, T, w);
     std::string out;
     for (auto& e : log) out += e.first + " " + std::to_string(e.second.first) + " " + std::to_string(e.second.second) + "\n";
-    if (out.size() + 1 > cap) return fail(LDS_ENOMEM, "plan needs %zu bytes", out.size() + 1);
+    if (out.size() + 1 > cap) return set_error(LDS_ENOMEM, "plan needs %zu bytes", out.size() + 1);
     memcpy(buf, out.c_str(), out.size() + 1);
     return LDS_OK;
 }
 
 extern "C" int lds_unet_workspace_bytes(const lds_unet* u, int B, int T, size_t* out) {
-    if (!u || !out || B <= 0 || T <= 0) return fail(LDS_EINVAL, "bad argument");
+    if (!u || !out || B <= 0 || T <= 0) return set_error(LDS_EINVAL, "bad argument");
     Arena A(nullptr, 0);
     UnetWs w;
     plan_ws(u, A, B, T, w);
@@ -1422,10 +1347,10 @@ static int run_tfm(const lds_unet* u, const TfmW& t, const UnetWs& w, const floa
 // kernel arguments (<= 64 utterances).
 static int ragged_len_host(int n, int lvl) { for (int i = 0; i < lvl; ++i) n = (n - 1) / 2 + 1; return n; }
 static int upload_lens(const lds_unet* u, const int* lens_host, int B, int T, int* dev, hipStream_t st) {
-    if (B > 64) return fail(LDS_EINVAL, "per-utterance lengths: at most 64 utterances per call (got %d)", B);
+    if (B > 64) return set_error(LDS_EINVAL, "per-utterance lengths: at most 64 utterances per call (got %d)", B);
     float tmp[64];
     for (int b = 0; b < B; ++b) {
-        if (lens_host[b] < 1 || lens_host[b] > T) return fail(LDS_EINVAL, "length[%d] = %d outside 1 .. %d", b, lens_host[b], T);
+        if (lens_host[b] < 1 || lens_host[b] > T) return set_error(LDS_EINVAL, "length[%d] = %d outside 1 .. %d", b, lens_host[b], T);
         memcpy(&tmp[b], &lens_host[b], sizeof(int));
     }
     HIP_TRY(launch_set_list((float*)dev, tmp, B, st));
@@ -1447,7 +1372,7 @@ static int unet_stage_cond(lds_unet* u, const float* cond, void* ws, size_t ws_b
     Arena A(ws, ws_bytes);
     UnetWs w;
     plan_ws(u, A, B, T, w);
-    if (!A.ok) return fail(LDS_ENOMEM, "unet workspace too small: need %zu bytes, got %zu", A.used, ws_bytes);
+    if (!A.ok) return set_error(LDS_ENOMEM, "unet workspace too small: need %zu bytes, got %zu", A.used, ws_bytes);
     if (lens_host) LDS_TRY(upload_lens(u, lens_host, B, T, w.lens_dev, st));
     LensScope lsc(lens_host ? w.lens_dev : nullptr);
     TileBatchScope tbs(u->latency_mode ? B : 0, w.kpart, w.kcount);
@@ -1471,7 +1396,7 @@ static int unet_forward_impl(lds_unet* u, const float* x, const float* cond, con
     Arena A(ws, ws_bytes);
     UnetWs w;
     plan_ws(u, A, B, T, w);
-    if (!A.ok) return fail(LDS_ENOMEM, "unet workspace too small: need %zu bytes, got %zu", A.used, ws_bytes);
+    if (!A.ok) return set_error(LDS_ENOMEM, "unet workspace too small: need %zu bytes, got %zu", A.used, ws_bytes);
     // ragged batch: the lengths reach the device once per call (per run when the sampler staged them with the condition)
     if (lens_host && !cond_staged) LDS_TRY(upload_lens(u, lens_host, B, T, w.lens_dev, st));
     LensScope lsc(lens_host ? w.lens_dev : nullptr);
@@ -1551,7 +1476,7 @@ static int unet_forward_impl(lds_unet* u, const float* x, const float* cond, con
         for (size_t j = 0; j < b.res.size(); ++j) {
             --si;
             const float* skip = w.skips[si];
-            if (skipT[si] != Tl) return fail(LDS_EINVAL, "internal: skip length mismatch");
+            if (skipT[si] != Tl) return set_error(LDS_EINVAL, "internal: skip length mismatch");
             const int hin = b.res[j].cin - b.skip_ch[j];
             const bool att = !b.att.empty();
             float* dst = w.cur[ci ^ 1];
@@ -1603,12 +1528,12 @@ static int unet_forward_impl(lds_unet* u, const float* x, const float* cond, con
 
 extern "C" int lds_unet_forward(lds_unet* u, const float* x, const float* cond, const float* t, float* eps, void* ws, size_t ws_bytes,
                                 int B, int T, void* stream) {
-    if (!u || !x || !cond || !t || !eps || !ws || B <= 0 || T <= 0) return fail(LDS_EINVAL, "bad argument");
+    if (!u || !x || !cond || !t || !eps || !ws || B <= 0 || T <= 0) return set_error(LDS_EINVAL, "bad argument");
     return unet_forward_impl(u, x, cond, t, eps, ws, ws_bytes, B, T, (hipStream_t)stream);
 }
 extern "C" int lds_unet_forward_ragged(lds_unet* u, const float* x, const float* cond, const float* t, const int32_t* lengths, float* eps, void* ws,
                                        size_t ws_bytes, int B, int T, void* stream) {
-    if (!u || !x || !cond || !t || !lengths || !eps || !ws || B <= 0 || T <= 0) return fail(LDS_EINVAL, "bad argument");
+    if (!u || !x || !cond || !t || !lengths || !eps || !ws || B <= 0 || T <= 0) return set_error(LDS_EINVAL, "bad argument");
     return unet_forward_impl(u, x, cond, t, eps, ws, ws_bytes, B, T, (hipStream_t)stream, false, nullptr, false, lengths);
 }
 
@@ -1628,7 +1553,7 @@ static void plan_samp(const lds_unet* u, Arena& A, int B, int T, SampWs& s) {
 }
 
 extern "C" int lds_sampler_workspace_bytes(const lds_unet* u, int B, int T, size_t* out) {
-    if (!u || !out || B <= 0 || T <= 0) return fail(LDS_EINVAL, "bad argument");
+    if (!u || !out || B <= 0 || T <= 0) return set_error(LDS_EINVAL, "bad argument");
     Arena A(nullptr, 0);
     SampWs s;
     plan_samp(u, A, B, T, s);
@@ -1646,19 +1571,19 @@ extern "C" int lds_sampler_run(lds_unet* u, int method, int n_rows, const float*
 }
 extern "C" int lds_sampler_run_ragged(lds_unet* u, int method, int n_rows, const float* table, const float* cond, float* x, const float* noise,
                                       const int32_t* lengths, void* ws, size_t ws_bytes, int B, int T, void* stream) {
-    if (!lengths) return fail(LDS_EINVAL, "bad argument");
+    if (!lengths) return set_error(LDS_EINVAL, "bad argument");
     return sampler_run_impl(u, method, n_rows, table, cond, x, noise, ws, ws_bytes, B, T, stream, lengths);
 }
 static int sampler_run_impl(lds_unet* u, int method, int n_rows, const float* table, const float* cond, float* x, const float* noise, void* ws, size_t ws_bytes,
                             int B, int T, void* stream, const int* lens) {
-    if (!u || !table || !cond || !x || !ws || n_rows <= 0 || B <= 0 || T <= 0) return fail(LDS_EINVAL, "bad argument");
+    if (!u || !table || !cond || !x || !ws || n_rows <= 0 || B <= 0 || T <= 0) return set_error(LDS_EINVAL, "bad argument");
     UnetCallScope in_call(u);
     hipStream_t st = (hipStream_t)stream;
     ProfChain chain;
     Arena A(ws, ws_bytes);
     SampWs s;
     plan_samp(u, A, B, T, s);
-    if (!A.ok || A.used > ws_bytes) return fail(LDS_ENOMEM, "sampler workspace too small");
+    if (!A.ok || A.used > ws_bytes) return set_error(LDS_ENOMEM, "sampler workspace too small");
     void* uws = (char*)ws + s.unet_off;
     const size_t uws_bytes = ws_bytes - s.unet_off;
     const long long n = (long long)B * u->M * T;
@@ -1719,7 +1644,7 @@ static int sampler_run_impl(lds_unet* u, int method, int n_rows, const float* ta
         }
     } else if (method == LDS_METHOD_DDPM) {
         // row n: {t, sqrt_recip_ac, sqrt_recipm1_ac, coef1, coef2, mask*exp(0.5*logvar)}
-        if (!noise) return fail(LDS_EINVAL, "DDPM needs per-step noise");
+        if (!noise) return set_error(LDS_EINVAL, "DDPM needs per-step noise");
         for (int i = 0; i < n_rows; ++i) {
             const float* r = table + (size_t)i * S;
             LDS_TRY(model(x, r[0]));
@@ -1758,7 +1683,7 @@ static int sampler_run_impl(lds_unet* u, int method, int n_rows, const float* ta
             if (nh < 3) ++nh;
         }
     } else {
-        return fail(LDS_EINVAL, "unknown sampler method %d", method);
+        return set_error(LDS_EINVAL, "unknown sampler method %d", method);
     }
     return LDS_OK;
 }
@@ -1775,18 +1700,18 @@ struct lds_embed {
 
 extern "C" int lds_embed_create(int input_channel, int n_hidden, int n_spk, const float* unit_w, const float* unit_b,
                                 const float* spk_w, lds_embed** out) {
-    if (!unit_w || !unit_b || !out || input_channel % 16 || n_hidden <= 0) return fail(LDS_EINVAL, "bad argument");
+    if (!unit_w || !unit_b || !out || input_channel % 16 || n_hidden <= 0) return set_error(LDS_EINVAL, "bad argument");
     lds_embed* e = new lds_embed();
     e->Cin = input_channel; e->H = n_hidden; e->n_spk = (spk_w && n_spk > 1) ? n_spk : 0;
     bool ok = pack_conv(e->own, unit_w, unit_b, n_hidden, input_channel, 1, e->lin);
     if (ok && e->n_spk) { e->spk = up_vec(e->own, spk_w, (int64_t)n_spk * n_hidden); ok = e->spk != nullptr; }
-    if (!ok) { delete e; return fail(LDS_ENOMEM, "embed upload failed"); }
+    if (!ok) { delete e; return set_error(LDS_ENOMEM, "embed upload failed"); }
     *out = e;
     return LDS_OK;
 }
 extern "C" void lds_embed_destroy(lds_embed* e) { delete e; }
 extern "C" int lds_embed_workspace_bytes(const lds_embed* e, int B, int T, size_t* out) {
-    if (!e || !out) return fail(LDS_EINVAL, "bad argument");
+    if (!e || !out) return set_error(LDS_EINVAL, "bad argument");
     Arena A(nullptr, 0);
     A.f((size_t)B * e->Cin * T);
     A.f((size_t)B * e->H);
@@ -1795,16 +1720,16 @@ extern "C" int lds_embed_workspace_bytes(const lds_embed* e, int B, int T, size_
 }
 extern "C" int lds_embed_forward(lds_embed* e, const float* units, const int64_t* spk_id, float* cond, void* ws, size_t ws_bytes,
                                  int B, int T, void* stream) {
-    if (!e || !units || !cond || !ws) return fail(LDS_EINVAL, "bad argument");
+    if (!e || !units || !cond || !ws) return set_error(LDS_EINVAL, "bad argument");
     hipStream_t st = (hipStream_t)stream;
     Arena A(ws, ws_bytes);
     float* ut = A.f((size_t)B * e->Cin * T);
     float* sb = A.f((size_t)B * e->H);
-    if (!A.ok) return fail(LDS_ENOMEM, "embed workspace too small");
+    if (!A.ok) return set_error(LDS_ENOMEM, "embed workspace too small");
     HIP_TRY(launch_transpose(units, ut, B, T, e->Cin, 1.0f, st));          // [B,T,K] -> [B,K,T]
     ConvOpt o;
     if (e->n_spk) {
-        if (!spk_id) return fail(LDS_EINVAL, "spk_id required");
+        if (!spk_id) return set_error(LDS_EINVAL, "spk_id required");
         HIP_TRY(launch_gather_rows(e->spk, spk_id, -1, sb, B, e->H, e->n_spk, st));
         o.bias_bc = sb;
     }
@@ -1813,25 +1738,25 @@ extern "C" int lds_embed_forward(lds_embed* e, const float* units, const int64_t
 }
 
 extern "C" int lds_transpose(const float* in, float* out, int B, int R, int C, float scale, void* stream) {
-    if (!in || !out) return fail(LDS_EINVAL, "bad argument");
+    if (!in || !out) return set_error(LDS_EINVAL, "bad argument");
     HIP_TRY(launch_transpose(in, out, B, R, C, scale, (hipStream_t)stream));
     return LDS_OK;
 }
 
 extern "C" int lds_gather_rows(const float* table, const int64_t* idx, float* out, int n_idx, int C, int n_rows, void* stream) {
-    if (!table || !idx || !out || n_idx <= 0 || C <= 0 || n_rows <= 0) return fail(LDS_EINVAL, "bad argument");
+    if (!table || !idx || !out || n_idx <= 0 || C <= 0 || n_rows <= 0) return set_error(LDS_EINVAL, "bad argument");
     HIP_TRY(launch_gather_rows(table, idx, 0, out, n_idx, C, n_rows, (hipStream_t)stream));
     return LDS_OK;
 }
 
 extern "C" int lds_resample_frames(const float* in, float* out, int B, int Tin, int Tout, int C, float step, void* stream) {
-    if (!in || !out) return fail(LDS_EINVAL, "bad argument");
+    if (!in || !out) return set_error(LDS_EINVAL, "bad argument");
     HIP_TRY(launch_resample_frames(in, out, B, Tin, Tout, C, step, (hipStream_t)stream));
     return LDS_OK;
 }
 
 extern "C" int lds_axpby(float* out, const float* a, const float* b, float c0, float c1, int64_t n, void* stream) {
-    if (!out || !a || !b || n <= 0) return fail(LDS_EINVAL, "bad argument");
+    if (!out || !a || !b || n <= 0) return set_error(LDS_EINVAL, "bad argument");
     HIP_TRY(launch_ew(EW_AXPBY, out, a, b, nullptr, nullptr, c0, -c1, 0, 0, 0, n, (hipStream_t)stream));
     return LDS_OK;
 }
@@ -1907,9 +1832,9 @@ static bool load_mrf_stage(Tensors& T, VocNet& net, int stage, int ch) {
 
 extern "C" int lds_vocoder_create(const lds_vocoder_cfg* cfg, int n, const char* const* names, const float* const* ptrs,
                                   const int64_t* numel, lds_vocoder** out) {
-    if (!cfg || !names || !ptrs || !numel || !out) return fail(LDS_EINVAL, "null argument");
+    if (!cfg || !names || !ptrs || !numel || !out) return set_error(LDS_EINVAL, "null argument");
     if (cfg->n_ups < 1 || cfg->n_ups > 8 || cfg->n_kernels < 1 || cfg->n_kernels > 4 || cfg->n_dil < 1 || cfg->n_dil > 4)
-        return fail(LDS_EINVAL, "vocoder config out of range");
+        return set_error(LDS_EINVAL, "vocoder config out of range");
     Tensors T;
     for (int i = 0; i < n; ++i) T.m[names[i]] = {ptrs[i], numel[i]};
     lds_vocoder* v = new lds_vocoder();
@@ -1918,7 +1843,7 @@ extern "C" int lds_vocoder_create(const lds_vocoder_cfg* cfg, int n, const char*
     bool ok = true;
     std::vector<float> w;
     const int c0 = cfg->upsample_initial_channel, ci = cfg->inter_channels;
-    if (ci % 16) { delete v; return fail(LDS_EINVAL, "inter_channels must be a multiple of 16"); }
+    if (ci % 16) { delete v; return set_error(LDS_EINVAL, "inter_channels must be a multiple of 16"); }
     ok = get_folded(T, "conv_pre.", c0, (int64_t)ci * 7, w) && pack_conv(o, w.data(), T.get("conv_pre.bias", c0), c0, ci, 7, v->pre);
     int ch = c0;
     for (int i = 0; i < cfg->n_ups && ok; ++i) {
@@ -1935,8 +1860,8 @@ extern "C" int lds_vocoder_create(const lds_vocoder_cfg* cfg, int n, const char*
     if (!ok) {
         std::string miss = T.missing;
         delete v;
-        if (!miss.empty()) return fail(LDS_EMISSING, "vocoder: %s", miss.c_str());
-        return fail(LDS_ENOMEM, "vocoder weight upload failed");
+        if (!miss.empty()) return set_error(LDS_EMISSING, "vocoder: %s", miss.c_str());
+        return set_error(LDS_ENOMEM, "vocoder weight upload failed");
     }
     *out = v;
     return LDS_OK;
@@ -1979,7 +1904,7 @@ static void plan_voc(const lds_vocoder* v, Arena& A, int B, int T, VocWs& w) {
     w.vlens = (int*)A.f(9 * 64);      // ragged batches: per-stage valid lengths of <= 64 utterances
 }
 extern "C" int lds_vocoder_workspace_bytes(const lds_vocoder* v, int B, int T, size_t* out) {
-    if (!v || !out || B <= 0 || T <= 0) return fail(LDS_EINVAL, "bad argument");
+    if (!v || !out || B <= 0 || T <= 0) return set_error(LDS_EINVAL, "bad argument");
     Arena A(nullptr, 0);
     VocWs w;
     plan_voc(v, A, B, T, w);
@@ -2061,7 +1986,7 @@ static int run_voc_pair(const ConvW& W1, const ConvW& W2, const float* x, float*
             ps.rename(nm);
         }
     }
-    if (e != hipSuccess) return fail(LDS_EHIP, "voc_pair launch failed (%s): C %d K %d dil %d T %d", hipGetErrorString(e), ch, W1.K, dil, Tl);
+    if (e != hipSuccess) return set_error(LDS_EHIP, "voc_pair launch failed (%s): C %d K %d dil %d T %d", hipGetErrorString(e), ch, W1.K, dil, Tl);
     return LDS_OK;
 }
 static bool voc_pair_ok(const lds_vocoder_cfg& c, const VocRes& rb, int m, int ch) {
@@ -2110,29 +2035,29 @@ extern "C" int lds_vocoder_forward(lds_vocoder* v, const float* z, float* wav, v
     return vocoder_forward_impl(v, z, wav, ws, ws_bytes, B, T, stream, nullptr);
 }
 extern "C" int lds_vocoder_forward_ragged(lds_vocoder* v, const float* z, const int32_t* lengths, float* wav, void* ws, size_t ws_bytes, int B, int T, void* stream) {
-    if (!lengths) return fail(LDS_EINVAL, "bad argument");
+    if (!lengths) return set_error(LDS_EINVAL, "bad argument");
     return vocoder_forward_impl(v, z, wav, ws, ws_bytes, B, T, stream, lengths);
 }
 static int vocoder_forward_impl(lds_vocoder* v, const float* z, float* wav, void* ws, size_t ws_bytes, int B, int T, void* stream, const int* lens_host) {
-    if (!v || !z || !wav || !ws || B <= 0 || T <= 0) return fail(LDS_EINVAL, "bad argument");
+    if (!v || !z || !wav || !ws || B <= 0 || T <= 0) return set_error(LDS_EINVAL, "bad argument");
     hipStream_t st = (hipStream_t)stream;
     ProfChain chain;
     Arena A(ws, ws_bytes);
     VocWs w;
     plan_voc(v, A, B, T, w);
-    if (!A.ok) return fail(LDS_ENOMEM, "vocoder workspace too small: need %zu", A.used);
+    if (!A.ok) return set_error(LDS_ENOMEM, "vocoder workspace too small: need %zu", A.used);
     const lds_vocoder_cfg& c = v->cfg;
     // Ragged batch: stage s of utterance b has vl[s][b] valid frames (the transposed convolutions' own length formula applied to the
     // utterance's length); every stage writes zeros beyond them, which is the zero padding the utterance's convolutions see when it runs
     // alone.  The lists travel in kernel arguments (<= 64 utterances).
     std::vector<const int*> vl(c.n_ups + 1, nullptr);
     if (lens_host) {
-        if (B > 64) return fail(LDS_EINVAL, "per-utterance lengths: at most 64 utterances per call (got %d)", B);
+        if (B > 64) return set_error(LDS_EINVAL, "per-utterance lengths: at most 64 utterances per call (got %d)", B);
         std::vector<int> cur(lens_host, lens_host + B);
         for (int i = 0; i <= c.n_ups; ++i) {
             float tmp[64];
             for (int b = 0; b < B; ++b) {
-                if (i == 0 && (cur[b] < 1 || cur[b] > T)) return fail(LDS_EINVAL, "length[%d] = %d outside 1 .. %d", b, cur[b], T);
+                if (i == 0 && (cur[b] < 1 || cur[b] > T)) return set_error(LDS_EINVAL, "length[%d] = %d outside 1 .. %d", b, cur[b], T);
                 memcpy(&tmp[b], &cur[b], sizeof(int));
             }
             HIP_TRY(launch_set_list((float*)(w.vlens + 64 * i), tmp, B, st));
@@ -2228,17 +2153,17 @@ static bool down_geometry_ok(int u, int k) { return u >= 2 && u <= 16 && (u & (u
 
 extern "C" int lds_vae_encoder_create(const lds_vocoder_cfg* cfg, int n, const char* const* names, const float* const* ptrs,
                                       const int64_t* numel, lds_vae_encoder** out) {
-    if (!cfg || !names || !ptrs || !numel || !out || n < 0) return fail(LDS_EINVAL, "null argument");
+    if (!cfg || !names || !ptrs || !numel || !out || n < 0) return set_error(LDS_EINVAL, "null argument");
     if (cfg->n_ups < 1 || cfg->n_ups > 8 || cfg->n_kernels < 1 || cfg->n_kernels > 4 || cfg->n_dil < 1 || cfg->n_dil > 4 || cfg->inter_channels < 1 ||
         cfg->upsample_initial_channel < 1)
-        return fail(LDS_EINVAL, "encoder config out of range");
+        return set_error(LDS_EINVAL, "encoder config out of range");
     const int nu = cfg->n_ups, c0 = cfg->upsample_initial_channel;
-    if ((c0 >> nu) < 1 || (c0 >> nu) << nu != c0) return fail(LDS_EINVAL, "encoder: upsample_initial_channel must be divisible by 2^n_ups");
+    if ((c0 >> nu) < 1 || (c0 >> nu) << nu != c0) return set_error(LDS_EINVAL, "encoder: upsample_initial_channel must be divisible by 2^n_ups");
     int hop = 1;
     for (int i = 0; i < nu; ++i) {
         const int u = cfg->upsample_rates[nu - 1 - i], k = cfg->upsample_kernel_sizes[nu - 1 - i], cout = c0 >> (nu - 1 - i);
-        if (!down_geometry_ok(u, k)) return fail(LDS_EINVAL, "encoder: unsupported downsample geometry (stride %d, kernel %d; needs k = 2u, u a power of two <= 16)", u, k);
-        if (cout < 16 || cout % 16) return fail(LDS_EINVAL, "encoder: unsupported stage width %d (a multiple of 16 is needed)", cout);
+        if (!down_geometry_ok(u, k)) return set_error(LDS_EINVAL, "encoder: unsupported downsample geometry (stride %d, kernel %d; needs k = 2u, u a power of two <= 16)", u, k);
+        if (cout < 16 || cout % 16) return set_error(LDS_EINVAL, "encoder: unsupported stage width %d (a multiple of 16 is needed)", cout);
         hop *= u;
     }
     Tensors T;
@@ -2259,8 +2184,8 @@ extern "C" int lds_vae_encoder_create(const lds_vocoder_cfg* cfg, int n, const c
     if (!ok) {
         std::string miss = T.missing;
         delete e;
-        if (!miss.empty()) return fail(LDS_EMISSING, "encoder: %s", miss.c_str());
-        return fail(LDS_ENOMEM, "encoder weight upload failed");
+        if (!miss.empty()) return set_error(LDS_EMISSING, "encoder: %s", miss.c_str());
+        return set_error(LDS_ENOMEM, "encoder weight upload failed");
     }
     *out = e;
     return LDS_OK;
@@ -2298,7 +2223,7 @@ static void plan_enc(const lds_vae_encoder* e, Arena& A, int B, int64_t L, EncWs
     v.vlens = (int*)A.f((e->downs.size() + 2) * 64);      // ragged batches: the sample lengths and every stage's lengths, <= 64 clips
 }
 extern "C" int lds_vae_encoder_workspace_bytes(const lds_vae_encoder* e, int B, int64_t L, size_t* out) {
-    if (!out || !enc_args_ok(e, B, L)) return fail(LDS_EINVAL, "bad argument (B %d, L %lld: B >= 1 and L a positive multiple of the hop)", B, (long long)L);
+    if (!out || !enc_args_ok(e, B, L)) return set_error(LDS_EINVAL, "bad argument (B %d, L %lld: B >= 1 and L a positive multiple of the hop)", B, (long long)L);
     Arena A(nullptr, 0);
     EncWs w;
     plan_enc(e, A, B, L, w);
@@ -2331,15 +2256,7 @@ static int run_down(const DownW& d, const float* x, int64_t L, float slope, floa
         }
     }
     if (e != hipSuccess)
-        return fail(LDS_EHIP, "conv_down launch failed (%s): Co %d Ci %d K %d stride %d L %lld", hipGetErrorString(e), d.Co, d.Ci, d.K, d.stride, (long long)L);
-    return LDS_OK;
-}
-
-// per-clip counts given by the caller (here and in the units encoders below): no more than 64 of them, every value in lo .. hi
-static int clip_lens_check(const char* name, const int32_t* v, int B, int64_t lo, int64_t hi) {
-    if (B > 64) return fail(LDS_EINVAL, "per-clip lengths: at most 64 clips per call (got %d)", B);
-    for (int b = 0; b < B; ++b)
-        if (v[b] < lo || v[b] > hi) return fail(LDS_EINVAL, "%s[%d] = %d outside %lld .. %lld", name, b, v[b], (long long)lo, (long long)hi);
+        return set_error(LDS_EHIP, "conv_down launch failed (%s): Co %d Ci %d K %d stride %d L %lld", hipGetErrorString(e), d.Co, d.Ci, d.K, d.stride, (long long)L);
     return LDS_OK;
 }
 
@@ -2351,21 +2268,21 @@ extern "C" int lds_vae_encoder_forward(lds_vae_encoder* e, const float* audio, c
 }
 extern "C" int lds_vae_encoder_forward_ragged(lds_vae_encoder* e, const float* audio, const int32_t* lengths, const float* noise, float* out, float* z,
                                               int only_mean, void* ws, size_t ws_bytes, int B, int64_t L, void* stream) {
-    if (!lengths) return fail(LDS_EINVAL, "bad argument: lengths is null");
+    if (!lengths) return set_error(LDS_EINVAL, "bad argument: lengths is null");
     // more than 64 clips is refused before the other arguments are judged (clip_lens_check says so), the values after them
-    if (B <= 64 && !enc_args_ok(e, B, L)) return fail(LDS_EINVAL, "bad argument (B %d, L %lld: B >= 1 and L a positive multiple of the hop)", B, (long long)L);
+    if (B <= 64 && !enc_args_ok(e, B, L)) return set_error(LDS_EINVAL, "bad argument (B %d, L %lld: B >= 1 and L a positive multiple of the hop)", B, (long long)L);
     LDS_TRY(clip_lens_check("length", lengths, B, 1, L));
     return vae_encoder_forward_impl(e, audio, lengths, noise, out, z, only_mean, ws, ws_bytes, B, L, stream);
 }
 static int vae_encoder_forward_impl(lds_vae_encoder* e, const float* audio, const int32_t* lens_host, const float* noise, float* out, float* z,
                                     int only_mean, void* ws, size_t ws_bytes, int B, int64_t L, void* stream) {
-    if (!audio || !out || !ws || (z && !noise) || !enc_args_ok(e, B, L)) return fail(LDS_EINVAL, "bad argument");
+    if (!audio || !out || !ws || (z && !noise) || !enc_args_ok(e, B, L)) return set_error(LDS_EINVAL, "bad argument");
     hipStream_t st = (hipStream_t)stream;
     ProfChain chain;
     Arena A(ws, ws_bytes);
     EncWs w;
     plan_enc(e, A, B, L, w);
-    if (!A.ok) return fail(LDS_ENOMEM, "encoder workspace too small: need %zu", A.used);
+    if (!A.ok) return set_error(LDS_ENOMEM, "encoder workspace too small: need %zu", A.used);
     // Ragged batch: clip b is audio[b, :len_b] encoded alone, i.e. zero-padded to Lp_b = ceil(len_b / hop) * hop samples.  vl[0] = len_b
     // (conv_pre reads the audio as zeros from there on), vl[1] = Lp_b (conv_pre's output), vl[2 + i] = Lp_b / (u_0 ... u_i) after
     // downsampler i (k = 2u, pad u / 2: a multiple of u maps to L / u exactly); the last is the clip's frame count T_b.  Every stage
@@ -2410,31 +2327,9 @@ static int vae_encoder_forward_impl(lds_vae_encoder* e, const float* audio, cons
 }
 
 // ================================================================================================
-// Units encoders: the host toolkit that Whisper, HuBERT, wav2vec 2.0 and w2v-BERT 2.0 below are written on.  Nothing here launches on its
-// own account: the four *_run functions stay the sequences of launches, these are the pieces they state in common.
+// Units encoders: what Whisper, HuBERT, wav2vec 2.0 and w2v-BERT 2.0 below state in common on top of host.h (WeightLoader, plan_bytes,
+// upload_clip_ints, the dimension rules).  Nothing here launches on its own account: the four *_run functions stay the sequences of launches.
 // ================================================================================================
-// The weights of a create call: the caller's name -> tensor map and the new handle's device allocations.
-struct WeightLoader {
-    Tensors T;
-    Owner& o;
-    WeightLoader(Owner& own, int n, const char* const* names, const float* const* ptrs, const int64_t* numel) : o(own) {
-        for (int i = 0; i < n; ++i) T.m[names[i]] = {ptrs[i], numel[i]};
-    }
-    const float* get(const std::string& k, int64_t cnt) { return T.get(k, cnt); }
-    float* vec(const std::string& k, int64_t cnt) {      // a tensor uploaded as it is
-        const float* p = T.get(k, cnt);
-        return p ? o.upload(std::vector<float>(p, p + cnt)) : nullptr;
-    }
-    // the end of a create: hands the handle out, or deletes it and names the first tensor that was absent or of the wrong size
-    template <class H>
-    int finish(bool ok, const char* tag, H* h, H** out) {
-        if (ok) { *out = h; return LDS_OK; }
-        delete h;
-        if (!T.missing.empty()) return fail(LDS_EMISSING, "%s: %s", tag, T.missing.c_str());
-        return fail(LDS_ENOMEM, "%s weight upload failed", tag);
-    }
-};
-
 // q | k | v as one [3C][C] weight and one [3C] bias; kb may be null (Whisper's key has no bias): zeros
 struct QkvCat { std::vector<float> w, b; };
 static QkvCat cat_qkv(const float* qw, const float* kw, const float* vw, const float* qb, const float* kb, const float* vb, int C) {
@@ -2474,37 +2369,6 @@ static float* plan_tf(Arena& A, size_t B, size_t C, size_t T, size_t big, size_t
     float* last = A.f(B * more);
     A.f(16384);      // tail slack: ragged last tiles read (masked) entries past a tensor's end
     return last;
-}
-// A *_workspace_bytes entry: the call's limits (check), then its plan (plan) run on an arena without memory
-template <class Check, class Plan>
-static int plan_bytes(size_t* out, Check check, Plan plan) {
-    if (!out) return fail(LDS_EINVAL, "null argument");
-    LDS_TRY(check());
-    Arena A(nullptr, 0);
-    plan(A);
-    *out = A.used;
-    return LDS_OK;
-}
-
-// up to 64 per-clip ints to a device slot, carried in a kernel's arguments (launch_set_list): stream-ordered, `host` is read during the call only
-static int upload_clip_ints(const int32_t* host, int B, int* dev, hipStream_t st) {
-    float tmp[64];
-    for (int b = 0; b < B; ++b) memcpy(&tmp[b], &host[b], sizeof(int));
-    HIP_TRY(launch_set_list((float*)dev, tmp, B, st));
-    return LDS_OK;
-}
-
-// Dimension rules; `tag` is the encoder's name in the messages.
-static int range_check(const char* tag, const char* name, int v, int lo, int hi) {
-    return v < lo || v > hi ? fail(LDS_EINVAL, "%s: %s %d outside %d .. %d", tag, name, v, lo, hi) : LDS_OK;
-}
-static int width_check(const char* tag, const char* name, int v, bool capped) {      // a GEMM's channel count; capped: at most 1024
-    if (capped && (v < 64 || v % 64 || v > 1024)) return fail(LDS_EINVAL, "%s: %s %d must be a multiple of 64 in 64 .. 1024", tag, name, v);
-    if (v < 64 || v % 64) return fail(LDS_EINVAL, "%s: %s %d must be a positive multiple of 64", tag, name, v);
-    return LDS_OK;
-}
-static int heads_check(const char* tag, int n_state, int n_head) {
-    return n_head < 1 || n_state != n_head * 64 ? fail(LDS_EINVAL, "%s: n_state / n_head must be 64 (got %d / %d)", tag, n_state, n_head) : LDS_OK;
 }
 
 // A pre-LN transformer block (Whisper's, wav2vec 2.0's): both LayerNorms folded into the GEMM that reads them.
@@ -2605,9 +2469,9 @@ static int conv_stack_dims_check(const char* tag, int conv_dim, int n_state, int
     LDS_TRY(range_check(tag, "n_layer", n_layer, 1, 64));
     LDS_TRY(width_check(tag, "n_ffn", n_ffn, false));
     if (n_proj >= 0) LDS_TRY(width_check(tag, "n_proj", n_proj, false));
-    if (pos_kernel < 2 || pos_kernel > 128 || (pos_kernel & 1)) return fail(LDS_EINVAL, "%s: pos_kernel %d must be even in 2 .. 128", tag, pos_kernel);
+    if (pos_kernel < 2 || pos_kernel > 128 || (pos_kernel & 1)) return set_error(LDS_EINVAL, "%s: pos_kernel %d must be even in 2 .. 128", tag, pos_kernel);
     if (pos_groups < 1 || n_state % pos_groups || (n_state / pos_groups) % 16 || n_state / pos_groups > 64)
-        return fail(LDS_EINVAL, "%s: n_state / pos_groups must be 16, 32, 48 or 64 (got %d / %d)", tag, n_state, pos_groups);
+        return set_error(LDS_EINVAL, "%s: n_state / pos_groups must be 16, 32, 48 or 64 (got %d / %d)", tag, n_state, pos_groups);
     return range_check(tag, "n_ctx", n_ctx, 1, 1500);
 }
 // the limits of one call on audio: B clips in buffers of L samples, `pad` zeros (at most max_pad) added on each side of every clip;
@@ -2615,9 +2479,9 @@ static int conv_stack_dims_check(const char* tag, int conv_dim, int n_state, int
 static int conv_stack_shape_check(const char* tag, int n_ctx, int B, int64_t L, int pad, int max_pad, int32_t* nb) {
     LDS_TRY(range_check(tag, "B", B, 1, 65535));
     LDS_TRY(range_check(tag, "pad", pad, 0, max_pad));
-    if (L + 2 * pad < 400 || L > ((int64_t)1 << 30)) return fail(LDS_EINVAL, "%s: L %lld outside %d .. 2^30 samples", tag, (long long)L, 400 - 2 * pad);
+    if (L + 2 * pad < 400 || L > ((int64_t)1 << 30)) return set_error(LDS_EINVAL, "%s: L %lld outside %d .. 2^30 samples", tag, (long long)L, 400 - 2 * pad);
     hubert_levels(L, pad, nb);
-    if (nb[6] > n_ctx) return fail(LDS_EINVAL, "%s: %d frames exceed n_ctx %d", tag, nb[6], n_ctx);
+    if (nb[6] > n_ctx) return set_error(LDS_EINVAL, "%s: %d frames exceed n_ctx %d", tag, nb[6], n_ctx);
     return LDS_OK;
 }
 
@@ -2641,8 +2505,8 @@ struct lds_whisper {
 constexpr int kWhisperHop = 160, kWhisperNfft = 400, kWhisperBins = 201;
 
 static int whisper_cfg_check(const lds_whisper_cfg* c) {
-    if (!c) return fail(LDS_EINVAL, "null argument");
-    if (c->n_mels != 80 && c->n_mels != 128) return fail(LDS_EINVAL, "whisper: n_mels %d (80 or 128)", c->n_mels);
+    if (!c) return set_error(LDS_EINVAL, "null argument");
+    if (c->n_mels != 80 && c->n_mels != 128) return set_error(LDS_EINVAL, "whisper: n_mels %d (80 or 128)", c->n_mels);
     LDS_TRY(width_check("whisper", "n_state", c->n_state, false));
     LDS_TRY(heads_check("whisper", c->n_state, c->n_head));
     LDS_TRY(range_check("whisper", "n_layer", c->n_layer, 1, 64));
@@ -2652,7 +2516,7 @@ static int whisper_cfg_check(const lds_whisper_cfg* c) {
 
 extern "C" int lds_whisper_create(const lds_whisper_cfg* cfg, int n, const char* const* names, const float* const* ptrs, const int64_t* numel,
                                   const float* mel_filters, lds_whisper** out) {
-    if (!cfg || !names || !ptrs || !numel || !mel_filters || !out || n < 0) return fail(LDS_EINVAL, "null argument");
+    if (!cfg || !names || !ptrs || !numel || !mel_filters || !out || n < 0) return set_error(LDS_EINVAL, "null argument");
     LDS_TRY(whisper_cfg_check(cfg));
     const int C = cfg->n_state, M = cfg->n_mels, NC = cfg->n_ctx;
     lds_whisper* h = new lds_whisper();
@@ -2741,17 +2605,17 @@ static void plan_whisper(const lds_whisper* h, Arena& A, int B, int F, WhisperWs
 }
 // the limits of one call: B clips in buffers of F mel frames
 static int whisper_shape_check(const lds_whisper* h, int B, int64_t F) {
-    if (!h) return fail(LDS_EINVAL, "null handle");
+    if (!h) return set_error(LDS_EINVAL, "null handle");
     LDS_TRY(range_check("whisper", "B", B, 1, 65535));
-    if (F < 1) return fail(LDS_EINVAL, "whisper: no mel frame (a clip needs at least 400 samples)");
-    if ((F - 1) / 2 + 1 > h->cfg.n_ctx) return fail(LDS_EINVAL, "whisper: %lld frames exceed n_ctx %d", (long long)((F - 1) / 2 + 1), h->cfg.n_ctx);
+    if (F < 1) return set_error(LDS_EINVAL, "whisper: no mel frame (a clip needs at least 400 samples)");
+    if ((F - 1) / 2 + 1 > h->cfg.n_ctx) return set_error(LDS_EINVAL, "whisper: %lld frames exceed n_ctx %d", (long long)((F - 1) / 2 + 1), h->cfg.n_ctx);
     return LDS_OK;
 }
 extern "C" int lds_whisper_workspace_bytes(const lds_whisper* h, int B, int64_t L, size_t* out) {
     return plan_bytes(
         out,
         [&] {
-            if (L < kWhisperNfft) return fail(LDS_EINVAL, "whisper: L %lld below 400 samples", (long long)L);
+            if (L < kWhisperNfft) return set_error(LDS_EINVAL, "whisper: L %lld below 400 samples", (long long)L);
             return whisper_shape_check(h, B, L / kWhisperHop);
         },
         [&](Arena& A) { WhisperWs w; plan_whisper(h, A, B, (int)(L / kWhisperHop), w); });
@@ -2766,7 +2630,7 @@ static int whisper_run(lds_whisper* h, const float* audio, int64_t L, const floa
     Arena A(ws, ws_bytes);
     WhisperWs w;
     plan_whisper(h, A, B, F, w);
-    if (!A.ok) return fail(LDS_ENOMEM, "whisper workspace too small: need %zu", A.used);
+    if (!A.ok) return set_error(LDS_ENOMEM, "whisper workspace too small: need %zu", A.used);
     const int C = h->cfg.n_state, M = h->cfg.n_mels, T = (F - 1) / 2 + 1;
     const int* slen = nullptr;
     const int* flen = nullptr;      // mel frames per clip: "level 0" of ragged_len; the encoder's frames are its level 1
@@ -2806,8 +2670,8 @@ static int whisper_run(lds_whisper* h, const float* audio, int64_t L, const floa
 
 // argument checks shared by the audio entries; *F_out = mel frames of the buffers
 static int whisper_audio_check(const lds_whisper* h, const float* audio, const int32_t* lengths, const void* ws, int B, int64_t L, int* F_out) {
-    if (!h || !audio || !ws) return fail(LDS_EINVAL, "null argument");
-    if (L < kWhisperNfft || L > ((int64_t)1 << 30)) return fail(LDS_EINVAL, "whisper: L %lld outside 400 .. 2^30 samples", (long long)L);
+    if (!h || !audio || !ws) return set_error(LDS_EINVAL, "null argument");
+    if (L < kWhisperNfft || L > ((int64_t)1 << 30)) return set_error(LDS_EINVAL, "whisper: L %lld outside 400 .. 2^30 samples", (long long)L);
     LDS_TRY(whisper_shape_check(h, B, L / kWhisperHop));
     if (lengths) LDS_TRY(clip_lens_check("length", lengths, B, kWhisperNfft, L));
     *F_out = (int)(L / kWhisperHop);
@@ -2816,20 +2680,20 @@ static int whisper_audio_check(const lds_whisper* h, const float* audio, const i
 extern "C" int lds_whisper_logmel(lds_whisper* h, const float* audio, const int32_t* lengths, float* mel, void* ws, size_t ws_bytes, int B, int64_t L,
                                   void* stream) {
     int F = 0;
-    if (!mel) return fail(LDS_EINVAL, "null argument");
+    if (!mel) return set_error(LDS_EINVAL, "null argument");
     LDS_TRY(whisper_audio_check(h, audio, lengths, ws, B, L, &F));
     return whisper_run(h, audio, L, nullptr, F, lengths, mel, nullptr, ws, ws_bytes, B, stream);
 }
 extern "C" int lds_whisper_encode(lds_whisper* h, const float* audio, const int32_t* lengths, float* units, void* ws, size_t ws_bytes, int B, int64_t L,
                                   void* stream) {
     int F = 0;
-    if (!units) return fail(LDS_EINVAL, "null argument");
+    if (!units) return set_error(LDS_EINVAL, "null argument");
     LDS_TRY(whisper_audio_check(h, audio, lengths, ws, B, L, &F));
     return whisper_run(h, audio, L, nullptr, F, lengths, nullptr, units, ws, ws_bytes, B, stream);
 }
 extern "C" int lds_whisper_encode_mel(lds_whisper* h, const float* mel, const int32_t* n_frames, float* units, void* ws, size_t ws_bytes, int B, int F,
                                       void* stream) {
-    if (!h || !mel || !units || !ws) return fail(LDS_EINVAL, "null argument");
+    if (!h || !mel || !units || !ws) return set_error(LDS_EINVAL, "null argument");
     LDS_TRY(whisper_shape_check(h, B, F));
     if (n_frames) LDS_TRY(clip_lens_check("n_frames", n_frames, B, 1, F));
     return whisper_run(h, nullptr, 0, mel, F, n_frames, nullptr, units, ws, ws_bytes, B, stream);
@@ -2857,7 +2721,7 @@ struct lds_hubert : ConvStackW {
 };
 
 static int hubert_cfg_check(const lds_hubert_cfg* c) {
-    if (!c) return fail(LDS_EINVAL, "null argument");
+    if (!c) return set_error(LDS_EINVAL, "null argument");
     return conv_stack_dims_check("hubert", c->conv_dim, c->n_state, c->n_head, c->n_layer, c->n_ffn, c->n_proj, c->pos_kernel, c->pos_groups, c->n_ctx);
 }
 
@@ -2884,7 +2748,7 @@ static float* pack_posconv(Owner& o, const float* g, const float* v, int C, int 
 }
 
 extern "C" int lds_hubert_create(const lds_hubert_cfg* cfg, int n, const char* const* names, const float* const* ptrs, const int64_t* numel, lds_hubert** out) {
-    if (!cfg || !names || !ptrs || !numel || !out || n < 0) return fail(LDS_EINVAL, "null argument");
+    if (!cfg || !names || !ptrs || !numel || !out || n < 0) return set_error(LDS_EINVAL, "null argument");
     LDS_TRY(hubert_cfg_check(cfg));
     const int D = cfg->conv_dim, C = cfg->n_state, F = cfg->n_ffn, K = cfg->pos_kernel, gw = C / cfg->pos_groups;
     lds_hubert* h = new lds_hubert();
@@ -2949,7 +2813,7 @@ static void plan_hubert(const lds_hubert* h, Arena& A, int B, const int32_t* nb,
     w.pj = plan_tf(A, Bz, C, T, F * (T + 2), D, w, P * (T + 2));
 }
 static int hubert_shape_check(const lds_hubert* h, int B, int64_t L, int pad, int32_t* nb) {
-    if (!h) return fail(LDS_EINVAL, "null handle");
+    if (!h) return set_error(LDS_EINVAL, "null handle");
     return conv_stack_shape_check("hubert", h->cfg.n_ctx, B, L, pad, 40, nb);
 }
 extern "C" int lds_hubert_workspace_bytes(const lds_hubert* h, int B, int64_t L, int pad, size_t* out) {
@@ -2965,7 +2829,7 @@ static int hubert_run(lds_hubert* h, const float* audio, int64_t L, int pad, con
     Arena A(ws, ws_bytes);
     HubertWs w;
     plan_hubert(h, A, B, nb, w);
-    if (!A.ok) return fail(LDS_ENOMEM, "hubert workspace too small: need %zu", A.used);
+    if (!A.ok) return set_error(LDS_ENOMEM, "hubert workspace too small: need %zu", A.used);
     const int D = h->cfg.conv_dim, C = h->cfg.n_state, T = nb[6];
     if (lens_host) LDS_TRY(w.upload(lens_host, pad, B, st));
     TileBatchScope tb(0);      // tile rules judged at the nominal batch: a clip's units do not depend on the batch it is in
@@ -3020,7 +2884,7 @@ static int hubert_run(lds_hubert* h, const float* audio, int64_t L, int pad, con
 
 static int hubert_audio_check(const lds_hubert* h, const float* audio, const int32_t* lengths, const void* out, const void* ws, int B, int64_t L, int pad,
                               int32_t* nb) {
-    if (!h || !audio || !out || !ws) return fail(LDS_EINVAL, "null argument");
+    if (!h || !audio || !out || !ws) return set_error(LDS_EINVAL, "null argument");
     LDS_TRY(hubert_shape_check(h, B, L, pad, nb));
     if (lengths) LDS_TRY(clip_lens_check("length", lengths, B, 400 - 2 * pad, L));
     return LDS_OK;
@@ -3035,8 +2899,8 @@ extern "C" int lds_hubert_encode(lds_hubert* h, const float* audio, const int32_
                                  size_t ws_bytes, int B, int64_t L, int pad, void* stream) {
     int32_t nb[kHubertLevels];
     LDS_TRY(hubert_audio_check(h, audio, lengths, out, ws, B, L, pad, nb));
-    if (n_layers_run < 0 || n_layers_run > h->cfg.n_layer) return fail(LDS_EINVAL, "hubert: n_layers_run %d outside 0 .. %d", n_layers_run, h->cfg.n_layer);
-    if (want_proj && n_layers_run != h->cfg.n_layer) return fail(LDS_EINVAL, "hubert: proj follows the last layer (n_layers_run %d of %d)", n_layers_run, h->cfg.n_layer);
+    if (n_layers_run < 0 || n_layers_run > h->cfg.n_layer) return set_error(LDS_EINVAL, "hubert: n_layers_run %d outside 0 .. %d", n_layers_run, h->cfg.n_layer);
+    if (want_proj && n_layers_run != h->cfg.n_layer) return set_error(LDS_EINVAL, "hubert: proj follows the last layer (n_layers_run %d of %d)", n_layers_run, h->cfg.n_layer);
     return hubert_run(h, audio, L, pad, lengths, nb, nullptr, out, n_layers_run, want_proj, ws, ws_bytes, B, stream);
 }
 
@@ -3057,12 +2921,12 @@ struct lds_w2v : ConvStackW {                                      // (conv1 .. 
 };
 
 static int w2v_cfg_check(const lds_w2v_cfg* c) {
-    if (!c) return fail(LDS_EINVAL, "null argument");
+    if (!c) return set_error(LDS_EINVAL, "null argument");
     return conv_stack_dims_check("w2v", c->conv_dim, c->n_state, c->n_head, c->n_layer, c->n_ffn, -1, c->pos_kernel, c->pos_groups, c->n_ctx);
 }
 
 extern "C" int lds_w2v_create(const lds_w2v_cfg* cfg, int n, const char* const* names, const float* const* ptrs, const int64_t* numel, lds_w2v** out) {
-    if (!cfg || !names || !ptrs || !numel || !out || n < 0) return fail(LDS_EINVAL, "null argument");
+    if (!cfg || !names || !ptrs || !numel || !out || n < 0) return set_error(LDS_EINVAL, "null argument");
     LDS_TRY(w2v_cfg_check(cfg));
     const int D = cfg->conv_dim, C = cfg->n_state, F = cfg->n_ffn, K = cfg->pos_kernel, gw = C / cfg->pos_groups;
     lds_w2v* h = new lds_w2v();
@@ -3129,7 +2993,7 @@ static void plan_w2v(const lds_w2v* h, Arena& A, int B, const int32_t* nb, W2vWs
     plan_tf(A, Bz, C, T, F * (T + 2), std::max(D, C), w);
 }
 static int w2v_shape_check(const lds_w2v* h, int B, int64_t L, int32_t* nb) {
-    if (!h) return fail(LDS_EINVAL, "null handle");
+    if (!h) return set_error(LDS_EINVAL, "null handle");
     return conv_stack_shape_check("w2v", h->cfg.n_ctx, B, L, 0, 0, nb);
 }
 extern "C" int lds_w2v_workspace_bytes(const lds_w2v* h, int B, int64_t L, size_t* out) {
@@ -3145,7 +3009,7 @@ static int w2v_run(lds_w2v* h, const float* audio, int64_t L, const int32_t* len
     Arena A(ws, ws_bytes);
     W2vWs w;
     plan_w2v(h, A, B, nb, w);
-    if (!A.ok) return fail(LDS_ENOMEM, "w2v workspace too small: need %zu", A.used);
+    if (!A.ok) return set_error(LDS_ENOMEM, "w2v workspace too small: need %zu", A.used);
     const int D = h->cfg.conv_dim, C = h->cfg.n_state, T = nb[6];
     if (lens_host) LDS_TRY(w.upload(lens_host, 0, B, st));
     TileBatchScope tb(0);      // tile rules judged at the nominal batch: a clip's units do not depend on the batch it is in
@@ -3177,7 +3041,7 @@ static int w2v_run(lds_w2v* h, const float* audio, int64_t L, const int32_t* len
 }
 
 static int w2v_audio_check(const lds_w2v* h, const float* audio, const int32_t* lengths, const void* out, const void* ws, int B, int64_t L, int32_t* nb) {
-    if (!h || !audio || !out || !ws) return fail(LDS_EINVAL, "null argument");
+    if (!h || !audio || !out || !ws) return set_error(LDS_EINVAL, "null argument");
     LDS_TRY(w2v_shape_check(h, B, L, nb));
     if (lengths) LDS_TRY(clip_lens_check("length", lengths, B, 400, L));
     return LDS_OK;
@@ -3234,21 +3098,21 @@ static int wavlm_bucket(int d, int num_buckets, int max_distance) {
     return (d > 0 ? nb : 0) + v;
 }
 static int wavlm_bucket_check(int num_buckets, int max_distance) {
-    if (num_buckets < 4 || num_buckets % 4 || num_buckets > 4096) return fail(LDS_EINVAL, "wavlm: num_buckets %d must be a multiple of 4 in 4 .. 4096", num_buckets);
+    if (num_buckets < 4 || num_buckets % 4 || num_buckets > 4096) return set_error(LDS_EINVAL, "wavlm: num_buckets %d must be a multiple of 4 in 4 .. 4096", num_buckets);
     if (max_distance <= num_buckets / 4 || max_distance > (1 << 20))
-        return fail(LDS_EINVAL, "wavlm: max_distance %d outside num_buckets / 4 + 1 = %d .. 2^20", max_distance, num_buckets / 4 + 1);
+        return set_error(LDS_EINVAL, "wavlm: max_distance %d outside num_buckets / 4 + 1 = %d .. 2^20", max_distance, num_buckets / 4 + 1);
     return LDS_OK;
 }
 static int wavlm_cfg_check(const lds_wavlm_cfg* c) {
-    if (!c) return fail(LDS_EINVAL, "null argument");
+    if (!c) return set_error(LDS_EINVAL, "null argument");
     LDS_TRY(conv_stack_dims_check("wavlm", c->conv_dim, c->n_state, c->n_head, c->n_layer, c->n_ffn, -1, c->pos_kernel, c->pos_groups, c->n_ctx));
     LDS_TRY(wavlm_bucket_check(c->num_buckets, c->max_distance));
-    if (c->stable_layer_norm != 0 && c->stable_layer_norm != 1) return fail(LDS_EINVAL, "wavlm: stable_layer_norm %d (0 or 1)", c->stable_layer_norm);
+    if (c->stable_layer_norm != 0 && c->stable_layer_norm != 1) return set_error(LDS_EINVAL, "wavlm: stable_layer_norm %d (0 or 1)", c->stable_layer_norm);
     return LDS_OK;
 }
 
 extern "C" int lds_wavlm_create(const lds_wavlm_cfg* cfg, int n, const char* const* names, const float* const* ptrs, const int64_t* numel, lds_wavlm** out) {
-    if (!cfg || !names || !ptrs || !numel || !out || n < 0) return fail(LDS_EINVAL, "null argument");
+    if (!cfg || !names || !ptrs || !numel || !out || n < 0) return set_error(LDS_EINVAL, "null argument");
     LDS_TRY(wavlm_cfg_check(cfg));
     const int D = cfg->conv_dim, C = cfg->n_state, F = cfg->n_ffn, K = cfg->pos_kernel, gw = C / cfg->pos_groups, H = cfg->n_head;
     const bool stable = cfg->stable_layer_norm != 0;
@@ -3349,7 +3213,7 @@ static void plan_wavlm(const lds_wavlm* h, Arena& A, int B, int64_t L, const int
     w.gate = plan_tf(A, Bz, C, T, F * (T + 2), std::max(D, C), w, (size_t)h->cfg.n_head * T);
 }
 static int wavlm_shape_check(const lds_wavlm* h, int B, int64_t L, int32_t* nb) {
-    if (!h) return fail(LDS_EINVAL, "null handle");
+    if (!h) return set_error(LDS_EINVAL, "null handle");
     LDS_TRY(range_check("wavlm", "B", B, 1, 64));
     return conv_stack_shape_check("wavlm", h->cfg.n_ctx, B, L, 0, 0, nb);
 }
@@ -3368,7 +3232,7 @@ static int wavlm_run(lds_wavlm* h, const float* audio, int64_t L, const int32_t*
     Arena A(ws, ws_bytes);
     WavlmWs w;
     plan_wavlm(h, A, B, L, nb, w);
-    if (!A.ok) return fail(LDS_ENOMEM, "wavlm workspace too small: need %zu", A.used);
+    if (!A.ok) return set_error(LDS_ENOMEM, "wavlm workspace too small: need %zu", A.used);
     const int D = h->cfg.conv_dim, C = h->cfg.n_state, T = nb[6], H = h->cfg.n_head, F = h->cfg.n_ffn;
     const bool stable = h->cfg.stable_layer_norm != 0;
     if (lens_host) LDS_TRY(w.upload(lens_host, 0, B, st));
@@ -3458,9 +3322,9 @@ static int wavlm_run(lds_wavlm* h, const float* audio, int64_t L, const int32_t*
 
 static int wavlm_audio_check(const lds_wavlm* h, const float* audio, const int32_t* lengths, const void* out, const void* ws, int B, int64_t L, int normalize,
                              int32_t* nb) {
-    if (!h || !audio || !out || !ws) return fail(LDS_EINVAL, "null argument");
+    if (!h || !audio || !out || !ws) return set_error(LDS_EINVAL, "null argument");
     LDS_TRY(wavlm_shape_check(h, B, L, nb));
-    if (normalize != 0 && normalize != 1) return fail(LDS_EINVAL, "wavlm: normalize %d (0 or 1)", normalize);
+    if (normalize != 0 && normalize != 1) return set_error(LDS_EINVAL, "wavlm: normalize %d (0 or 1)", normalize);
     if (lengths) LDS_TRY(clip_lens_check("length", lengths, B, 400, L));
     return LDS_OK;
 }
@@ -3474,16 +3338,16 @@ extern "C" int lds_wavlm_encode(lds_wavlm* h, const float* audio, const int32_t*
                                 size_t ws_bytes, int B, int64_t L, void* stream) {
     int32_t nb[kHubertLevels];
     LDS_TRY(wavlm_audio_check(h, audio, lengths, out, ws, B, L, normalize, nb));
-    if (n_layers_run < 0 || n_layers_run > h->cfg.n_layer) return fail(LDS_EINVAL, "wavlm: n_layers_run %d outside 0 .. %d", n_layers_run, h->cfg.n_layer);
+    if (n_layers_run < 0 || n_layers_run > h->cfg.n_layer) return set_error(LDS_EINVAL, "wavlm: n_layers_run %d outside 0 .. %d", n_layers_run, h->cfg.n_layer);
     return wavlm_run(h, audio, L, lengths, nb, nullptr, out, n_layers_run, normalize, ws, ws_bytes, B, stream);
 }
 extern "C" int lds_wavlm_encode_layersum(lds_wavlm* h, const float* audio, const int32_t* lengths, const float* layer_w, float* out, int normalize, void* ws,
                                          size_t ws_bytes, int B, int64_t L, void* stream) {
     int32_t nb[kHubertLevels];
     LDS_TRY(wavlm_audio_check(h, audio, lengths, out, ws, B, L, normalize, nb));
-    if (!layer_w) return fail(LDS_EINVAL, "wavlm: null layer_w");
+    if (!layer_w) return set_error(LDS_EINVAL, "wavlm: null layer_w");
     for (int l = 0; l <= h->cfg.n_layer; ++l)
-        if (!std::isfinite(layer_w[l])) return fail(LDS_EINVAL, "wavlm: layer_w[%d] is not finite", l);
+        if (!std::isfinite(layer_w[l])) return set_error(LDS_EINVAL, "wavlm: layer_w[%d] is not finite", l);
     return wavlm_run(h, audio, L, lengths, nb, nullptr, out, h->cfg.n_layer, normalize, ws, ws_bytes, B, stream, layer_w);
 }
 
@@ -3560,23 +3424,23 @@ static std::vector<float> w2vbert_mel_filters(int n_mels) {
 }
 
 static int w2vbert_cfg_check(const lds_w2vbert_cfg* c) {
-    if (!c) return fail(LDS_EINVAL, "null argument");
+    if (!c) return set_error(LDS_EINVAL, "null argument");
     if (c->n_mels < 8 || c->n_mels > 128 || c->stride < 1 || c->stride > 8 || (c->n_mels * c->stride) % 32 || c->n_mels * c->stride > 1024)
-        return fail(LDS_EINVAL, "w2vbert: n_mels %d x stride %d must be a multiple of 32 up to 1024 (n_mels 8 .. 128, stride 1 .. 8)", c->n_mels, c->stride);
+        return set_error(LDS_EINVAL, "w2vbert: n_mels %d x stride %d must be a multiple of 32 up to 1024 (n_mels 8 .. 128, stride 1 .. 8)", c->n_mels, c->stride);
     LDS_TRY(width_check("w2vbert", "n_state", c->n_state, true));
     LDS_TRY(heads_check("w2vbert", c->n_state, c->n_head));
     LDS_TRY(width_check("w2vbert", "n_ffn", c->n_ffn, false));
     LDS_TRY(range_check("w2vbert", "n_layer", c->n_layer, 1, 64));
     if (c->left_max < 0 || c->right_max < 0 || c->left_max + c->right_max + 1 > kW2vbertRelStride)
-        return fail(LDS_EINVAL, "w2vbert: left_max %d + right_max %d + 1 distances exceed %d", c->left_max, c->right_max, kW2vbertRelStride);
-    if (c->dw_kernel < 1 || c->dw_kernel > 31 || !(c->dw_kernel & 1)) return fail(LDS_EINVAL, "w2vbert: dw_kernel %d must be odd in 1 .. 31", c->dw_kernel);
+        return set_error(LDS_EINVAL, "w2vbert: left_max %d + right_max %d + 1 distances exceed %d", c->left_max, c->right_max, kW2vbertRelStride);
+    if (c->dw_kernel < 1 || c->dw_kernel > 31 || !(c->dw_kernel & 1)) return set_error(LDS_EINVAL, "w2vbert: dw_kernel %d must be odd in 1 .. 31", c->dw_kernel);
     LDS_TRY(range_check("w2vbert", "n_ctx", c->n_ctx, 1, 1500));
-    if (!(c->eps > 0.f) || !(c->eps < 1.f)) return fail(LDS_EINVAL, "w2vbert: eps %g outside (0, 1)", (double)c->eps);
+    if (!(c->eps > 0.f) || !(c->eps < 1.f)) return set_error(LDS_EINVAL, "w2vbert: eps %g outside (0, 1)", (double)c->eps);
     return LDS_OK;
 }
 
 extern "C" int lds_w2vbert_create(const lds_w2vbert_cfg* cfg, int n, const char* const* names, const float* const* ptrs, const int64_t* numel, lds_w2vbert** out) {
-    if (!cfg || !names || !ptrs || !numel || !out || n < 0) return fail(LDS_EINVAL, "null argument");
+    if (!cfg || !names || !ptrs || !numel || !out || n < 0) return set_error(LDS_EINVAL, "null argument");
     LDS_TRY(w2vbert_cfg_check(cfg));
     const int Fd = cfg->n_mels * cfg->stride, C = cfg->n_state, F = cfg->n_ffn, K = cfg->dw_kernel, NR = cfg->left_max + cfg->right_max + 1;
     lds_w2vbert* h = new lds_w2vbert();
@@ -3664,12 +3528,12 @@ static void plan_w2vbert(const lds_w2vbert* h, Arena& A, int B, int N, int R, W2
 }
 // the limits of one call: B clips in buffers of L samples -> N frames, R rows
 static int w2vbert_shape_check(const lds_w2vbert* h, int B, int64_t L, int& N, int& R) {
-    if (!h) return fail(LDS_EINVAL, "null handle");
+    if (!h) return set_error(LDS_EINVAL, "null handle");
     LDS_TRY(range_check("w2vbert", "B", B, 1, 64));
-    if (L < kW2vbertMinSamples || L > ((int64_t)1 << 30)) return fail(LDS_EINVAL, "w2vbert: L %lld outside %d .. 2^30 samples", (long long)L, kW2vbertMinSamples);
+    if (L < kW2vbertMinSamples || L > ((int64_t)1 << 30)) return set_error(LDS_EINVAL, "w2vbert: L %lld outside %d .. 2^30 samples", (long long)L, kW2vbertMinSamples);
     N = w2vbert_frames(L);
     R = (N + h->cfg.stride - 1) / h->cfg.stride;
-    if (R > h->cfg.n_ctx) return fail(LDS_EINVAL, "w2vbert: %d rows exceed n_ctx %d", R, h->cfg.n_ctx);
+    if (R > h->cfg.n_ctx) return set_error(LDS_EINVAL, "w2vbert: %d rows exceed n_ctx %d", R, h->cfg.n_ctx);
     return LDS_OK;
 }
 extern "C" int lds_w2vbert_workspace_bytes(const lds_w2vbert* h, int B, int64_t L, size_t* out) {
@@ -3686,7 +3550,7 @@ static int w2vbert_run(lds_w2vbert* h, const float* audio, int64_t L, const int3
     Arena A(ws, ws_bytes);
     W2vbertWs w;
     plan_w2vbert(h, A, B, N, R, w);
-    if (!A.ok) return fail(LDS_ENOMEM, "w2vbert workspace too small: need %zu", A.used);
+    if (!A.ok) return set_error(LDS_ENOMEM, "w2vbert workspace too small: need %zu", A.used);
     const lds_w2vbert_cfg& c = h->cfg;
     const int Fd = c.n_mels * c.stride, C = c.n_state, T = R;
     int32_t rows[64], valid[64];
@@ -3764,7 +3628,7 @@ static int w2vbert_run(lds_w2vbert* h, const float* audio, int64_t L, const int3
 
 static int w2vbert_audio_check(const lds_w2vbert* h, const float* audio, const int32_t* lengths, const void* out, const void* ws, int B, int64_t L, int& N,
                                int& R, int32_t* nfr) {
-    if (!h || !audio || !out || !ws) return fail(LDS_EINVAL, "null argument");
+    if (!h || !audio || !out || !ws) return set_error(LDS_EINVAL, "null argument");
     LDS_TRY(w2vbert_shape_check(h, B, L, N, R));
     if (lengths) LDS_TRY(clip_lens_check("length", lengths, B, kW2vbertMinSamples, L));
     for (int b = 0; b < B; ++b) nfr[b] = lengths ? w2vbert_frames(lengths[b]) : N;
@@ -3784,14 +3648,14 @@ extern "C" int lds_w2vbert_encode(lds_w2vbert* h, const float* audio, const int3
 }
 extern "C" int lds_w2vbert_encode_features(lds_w2vbert* h, const float* feats, const int32_t* n_frames, float* out, void* ws, size_t ws_bytes, int B, int R,
                                            void* stream) {
-    if (!h || !feats || !out || !ws) return fail(LDS_EINVAL, "null argument");
+    if (!h || !feats || !out || !ws) return set_error(LDS_EINVAL, "null argument");
     LDS_TRY(range_check("w2vbert", "B", B, 1, 64));
-    if (R < 1 || R > h->cfg.n_ctx) return fail(LDS_EINVAL, "w2vbert: %d rows outside 1 .. n_ctx %d", R, h->cfg.n_ctx);
+    if (R < 1 || R > h->cfg.n_ctx) return set_error(LDS_EINVAL, "w2vbert: %d rows outside 1 .. n_ctx %d", R, h->cfg.n_ctx);
     const int st = h->cfg.stride;
     int32_t nfr[64];
     for (int b = 0; b < B; ++b) {
         nfr[b] = n_frames ? n_frames[b] : R * st;
-        if (nfr[b] < 2 || nfr[b] < st || (nfr[b] + st - 1) / st > R) return fail(LDS_EINVAL, "n_frames[%d] = %d outside %d .. %d", b, nfr[b], st > 2 ? st : 2, R * st);
+        if (nfr[b] < 2 || nfr[b] < st || (nfr[b] + st - 1) / st > R) return set_error(LDS_EINVAL, "n_frames[%d] = %d outside %d .. %d", b, nfr[b], st > 2 ? st : 2, R * st);
     }
     return w2vbert_run(h, nullptr, 0, nullptr, feats, nfr, R * st, R, nullptr, out, ws, ws_bytes, B, stream);
 }
@@ -3800,12 +3664,12 @@ extern "C" int lds_w2vbert_encode_features(lds_w2vbert* h, const float* feats, c
 // Single-op test entry points
 // ================================================================================================
 extern "C" int lds_test_conv(const lds_conv_test* a, float* out, int B, void* stream) {
-    if (!a || !out) return fail(LDS_EINVAL, "bad argument");
+    if (!a || !out) return set_error(LDS_EINVAL, "bad argument");
     hipStream_t st = (hipStream_t)stream;
     Owner own;
     ConvW W;
     const int Ci = a->C1 + a->C2;
-    if (!pack_conv(own, a->w, a->bias, a->Co, Ci, a->K, W)) return fail(LDS_ENOMEM, "test conv: upload failed");
+    if (!pack_conv(own, a->w, a->bias, a->Co, Ci, a->K, W)) return set_error(LDS_ENOMEM, "test conv: upload failed");
     ConvOpt o;
     o.pad = a->pad; o.dil = a->dil;
     o.act_in = a->act_in; o.slope = a->slope; o.res = a->res; o.epi = a->epilogue; o.tile = a->tile;
@@ -3827,7 +3691,7 @@ struct TmpDev {
 static thread_local float* g_tap_dst = nullptr;
 static thread_local size_t g_tap_floats = 0;
 extern "C" int lds_test_tap_k4p(float* dst, size_t floats) {
-    if ((dst != nullptr) != (floats > 0)) return fail(LDS_EINVAL, "bad argument");
+    if ((dst != nullptr) != (floats > 0)) return set_error(LDS_EINVAL, "bad argument");
     g_tap_dst = dst; g_tap_floats = floats;
     return LDS_OK;
 }
@@ -3852,13 +3716,13 @@ static int dconv_test_impl(const lds_dconv_test* a, float* out, float* lnpart, i
     const int Ci = a->C1 + a->C2, T = a->T;
     bool ok = (a->epilogue == EPI_GEGLU) ? pack_geglu(own, a->w, a->bias, a->Co, Ci, W) : pack_conv(own, a->w, a->bias, a->Co, Ci, a->K, W);
     if (ok && bf3) ok = make_split_twin(own, W, fmt);
-    if (!ok) return fail(LDS_ENOMEM, "test dconv: upload failed");
+    if (!ok) return set_error(LDS_ENOMEM, "test dconv: upload failed");
     auto act_floats = [&](int C, int Tl) { return bf3 ? (size_t)B * split_floats(fmt, C, Tl) : (size_t)B * C * (Tl + 2); };
     auto to_act = [&](const float* src, float* dst, int C, int Tl) { return bf3 ? launch_to_k8b3(src, dst, B, C, Tl, C, 0, st, fmt) : launch_to_k4p(src, dst, B, C, Tl, C, 0, st); };
     auto from_act = [&](const float* src, float* dst, int C, int Tl) { return bf3 ? launch_from_k8b3(src, dst, B, C, Tl, st, fmt) : launch_from_k4p(src, dst, B, C, Tl, st); };
     float* k1 = tmp.f(act_floats(a->C1, T));
     float* k2 = a->C2 ? tmp.f(act_floats(a->C2, T)) : nullptr;
-    if (!k1 || (a->C2 && !k2)) return fail(LDS_ENOMEM, "test dconv: alloc failed");
+    if (!k1 || (a->C2 && !k2)) return set_error(LDS_ENOMEM, "test dconv: alloc failed");
     HIP_TRY(to_act(a->x1, k1, a->C1, T));
     if (a->C2) HIP_TRY(to_act(a->x2, k2, a->C2, T));
     const int Cout = (a->epilogue == EPI_GEGLU) ? a->Co / 2 : a->Co;
@@ -3872,17 +3736,17 @@ static int dconv_test_impl(const lds_dconv_test* a, float* out, float* lnpart, i
     float* kres = nullptr;
     if (a->res) {
         kres = tmp.f(act_floats(Ck, To));
-        if (!kres) return fail(LDS_ENOMEM, "alloc");
+        if (!kres) return set_error(LDS_ENOMEM, "alloc");
         HIP_TRY(to_act(a->res, kres, Ck, To));
         o.res = kres;
     }
     float* kout = a->plain_out ? out : tmp.f(qk_f32 ? (size_t)B * Ck * (To + 2) : act_floats(Ck, To));
     float* vout = nullptr;
-    if (!kout) return fail(LDS_ENOMEM, "alloc");
+    if (!kout) return set_error(LDS_ENOMEM, "alloc");
     const int To4 = (To + 3) & ~3;
     if (a->v_split) {
         vout = tmp.f((size_t)B * (Cout - Ck) * To4);
-        if (!vout) return fail(LDS_ENOMEM, "alloc");
+        if (!vout) return set_error(LDS_ENOMEM, "alloc");
         HIP_TRY(hipMemsetAsync(vout, 0xff, sizeof(float) * B * (Cout - Ck) * To4, st));      // NaN fill: the zero tail must be written
         o.plain_from = Ck; o.out2 = vout;
         if (a->v_split > 1) o.vt_D = a->v_split;      // value third in attention's VT layout with this head dim
@@ -3919,7 +3783,7 @@ static int dconv_test_impl(const lds_dconv_test* a, float* out, float* lnpart, i
         } else if (a->v_split) {
             // out = [q;k] back to plain (first 2/3 of the channels) followed by the already-plain v third
             float* tmpo = tmp.f((size_t)B * Ck * To);
-            if (!tmpo) return fail(LDS_ENOMEM, "alloc");
+            if (!tmpo) return set_error(LDS_ENOMEM, "alloc");
             HIP_TRY(from_out(kout, tmpo, Ck, To));
             for (int b = 0; b < B; ++b) {
                 HIP_TRY(hipMemcpyAsync(out + (size_t)b * Cout * To, tmpo + (size_t)b * Ck * To, sizeof(float) * Ck * To, hipMemcpyDeviceToDevice, st));
@@ -3934,11 +3798,11 @@ static int dconv_test_impl(const lds_dconv_test* a, float* out, float* lnpart, i
     return r;
 }
 extern "C" int lds_test_dconv(const lds_dconv_test* a, float* out, float* lnpart, int B, void* stream) {
-    if (!a || !out) return fail(LDS_EINVAL, "bad argument");
+    if (!a || !out) return set_error(LDS_EINVAL, "bad argument");
     return dconv_test_impl(a, out, lnpart, B, 0, nullptr, stream);
 }
 extern "C" int lds_bench_dconv(const lds_dconv_test* a, float* out, int B, int iters, float* ms_out, char* cfg_out, size_t cfg_cap, void* stream) {
-    if (!a || !out || !ms_out || iters <= 0) return fail(LDS_EINVAL, "bad argument");
+    if (!a || !out || !ms_out || iters <= 0) return set_error(LDS_EINVAL, "bad argument");
     int r = dconv_test_impl(a, out, nullptr, B, iters, ms_out, stream);
     if (cfg_out && cfg_cap) snprintf(cfg_out, cfg_cap, "%s", conv_dma_last_config());
     return r;
@@ -3946,11 +3810,11 @@ extern "C" int lds_bench_dconv(const lds_dconv_test* a, float* out, int B, int i
 // the same launch `iters` times, rotating through the tile configurations cfgs[0 .. n) (instantiations of the same operator): what does a
 // launch cost when the previous launch ran other code?  (tools/bench_icache.py)
 extern "C" int lds_bench_dconv_alt(const lds_dconv_test* a, float* out, int B, int iters, const int* cfgs, int n, float* ms_out, void* stream) {
-    if (!a || !out || !cfgs || n < 1 || !ms_out) return fail(LDS_EINVAL, "bad argument");
+    if (!a || !out || !cfgs || n < 1 || !ms_out) return set_error(LDS_EINVAL, "bad argument");
     return dconv_test_impl(a, out, nullptr, B, iters, ms_out, stream, 0, 0, 0, cfgs, n);
 }
 extern "C" int lds_test_dconv_split(const lds_dconv_test* a, float* out, float* lnpart, int B, int nprod, int fmt, void* stream) {
-    if (!a || !out || (fmt != FMT_BF16X3 && fmt != FMT_F16X2)) return fail(LDS_EINVAL, "bad argument");
+    if (!a || !out || (fmt != FMT_BF16X3 && fmt != FMT_F16X2)) return set_error(LDS_EINVAL, "bad argument");
     return dconv_test_impl(a, out, lnpart, B, 0, nullptr, stream, 1, nprod, fmt);
 }
 extern "C" int lds_test_dconv_bf3(const lds_dconv_test* a, float* out, float* lnpart, int B, int nprod, void* stream) {
@@ -3958,13 +3822,13 @@ extern "C" int lds_test_dconv_bf3(const lds_dconv_test* a, float* out, float* ln
 }
 extern "C" int lds_bench_dconv_split(const lds_dconv_test* a, float* out, int B, int iters, int nprod, int fmt, float* ms_out, char* cfg_out, size_t cfg_cap,
                                      void* stream) {
-    if (!a || !out || !ms_out || iters <= 0 || (fmt != FMT_BF16X3 && fmt != FMT_F16X2)) return fail(LDS_EINVAL, "bad argument");
+    if (!a || !out || !ms_out || iters <= 0 || (fmt != FMT_BF16X3 && fmt != FMT_F16X2)) return set_error(LDS_EINVAL, "bad argument");
     int r = dconv_test_impl(a, out, nullptr, B, iters, ms_out, stream, 1, nprod, fmt);
     if (cfg_out && cfg_cap) snprintf(cfg_out, cfg_cap, "%s", conv_bf3_last_config());
     return r;
 }
 extern "C" int lds_bench_dconv_bf3(const lds_dconv_test* a, float* out, int B, int iters, int nprod, float* ms_out, char* cfg_out, size_t cfg_cap, void* stream) {
-    if (!a || !out || !ms_out || iters <= 0) return fail(LDS_EINVAL, "bad argument");
+    if (!a || !out || !ms_out || iters <= 0) return set_error(LDS_EINVAL, "bad argument");
     int r = dconv_test_impl(a, out, nullptr, B, iters, ms_out, stream, 1, nprod, FMT_BF16X3);
     if (cfg_out && cfg_cap) snprintf(cfg_out, cfg_cap, "%s", conv_bf3_last_config());
     return r;
@@ -3983,7 +3847,7 @@ extern "C" int lds_test_gn_apply(const float* x1, const float* x2, int C1, int C
     float* ky = tmp.f((size_t)B * C * (T + 2));
     float* p1 = tmp.f((size_t)B * (C1 / 16) * nT * 2);
     float* p2 = C2 ? tmp.f((size_t)B * (C2 / 16) * nT * 2) : nullptr;
-    if (!g || !be || !k1 || (C2 && (!k2 || !p2)) || !ky || !p1) return fail(LDS_ENOMEM, "alloc");
+    if (!g || !be || !k1 || (C2 && (!k2 || !p2)) || !ky || !p1) return set_error(LDS_ENOMEM, "alloc");
     HIP_TRY(launch_to_k4p(x1, k1, B, C1, T, C1, 0, st));
     HIP_TRY(launch_gn_partials(k1, C1, T, (float2*)p1, B, st));
     if (C2) {
@@ -4007,7 +3871,7 @@ extern "C" int lds_bench_gn_stream(int C1, int C2, int T, int B, int iters, floa
     float* p1 = tmp.f((size_t)B * (C1 / 16) * nT * 2);
     float* p2 = C2 ? tmp.f((size_t)B * (C2 / 16) * nT * 2) : nullptr;
     float* gb = tmp.f(2 * C);
-    if (!k1 || (C2 && (!k2 || !p2)) || !ky || !p1 || !gb || iters <= 0 || !ms_out) return fail(LDS_ENOMEM, "alloc");
+    if (!k1 || (C2 && (!k2 || !p2)) || !ky || !p1 || !gb || iters <= 0 || !ms_out) return set_error(LDS_ENOMEM, "alloc");
     HIP_TRY(hipMemsetAsync(k1, 0, sizeof(float) * B * C1 * (T + 2), st));
     if (C2) HIP_TRY(hipMemsetAsync(k2, 0, sizeof(float) * B * C2 * (T + 2), st));
     HIP_TRY(hipMemsetAsync(gb, 0, sizeof(float) * 2 * C, st));
@@ -4039,7 +3903,7 @@ extern "C" int lds_test_gn_chain_k4p(const float* x, const float* w1, const floa
     Owner own;
     TmpDev tmp;
     ConvW W1;
-    if (!pack_conv(own, w1, bias1, Co, C, 1, W1)) return fail(LDS_ENOMEM, "upload failed");
+    if (!pack_conv(own, w1, bias1, Co, C, 1, W1)) return set_error(LDS_ENOMEM, "upload failed");
     float* g = up_vec(own, gamma, Co);
     float* be = up_vec(own, beta, Co);
     const int nT = (T + 31) / 32;
@@ -4047,7 +3911,7 @@ extern "C" int lds_test_gn_chain_k4p(const float* x, const float* w1, const floa
     float* km = tmp.f((size_t)B * Co * (T + 2));
     float* ko = tmp.f((size_t)B * Co * (T + 2));
     float* gp = tmp.f((size_t)B * (Co / 16) * nT * 2);
-    if (!g || !be || !kx || !km || !ko || !gp) return fail(LDS_ENOMEM, "alloc");
+    if (!g || !be || !kx || !km || !ko || !gp) return set_error(LDS_ENOMEM, "alloc");
     HIP_TRY(hipMemsetAsync(gp, 0xff, sizeof(float) * B * (Co / 16) * nT * 2, st));      // NaN fill: every partial must be written
     HIP_TRY(launch_to_k4p(x, kx, B, C, T, C, 0, st));
     DOpt o1;
@@ -4070,7 +3934,7 @@ extern "C" int lds_test_gn_fold_k4p(const float* x, const float* w1, const float
     TmpDev tmp;
     ConvW W1, W2;
     float *cg = nullptr, *c2 = nullptr;
-    if (!pack_conv(own, w1, bias1, Cm, C, 1, W1) || !pack_gn_fold(own, w2, bias2, gamma, beta, Co, Cm, groups, W2, cg, c2)) return fail(LDS_ENOMEM, "upload failed");
+    if (!pack_conv(own, w1, bias1, Cm, C, 1, W1) || !pack_gn_fold(own, w2, bias2, gamma, beta, Co, Cm, groups, W2, cg, c2)) return set_error(LDS_ENOMEM, "upload failed");
     const int nT = (T + 31) / 32;
     float* kx = tmp.f((size_t)B * C * (T + 2));
     float* km = tmp.f((size_t)B * Cm * (T + 2));
@@ -4078,7 +3942,7 @@ extern "C" int lds_test_gn_fold_k4p(const float* x, const float* w1, const float
     float* gp = tmp.f((size_t)B * (Cm / 16) * nT * 2);
     float* kpart = tmp.f((size_t)kClusterPartFloats);
     unsigned* kcount = (unsigned*)tmp.f(kClusterCounters);
-    if (!kx || !km || !ko || !gp || !kpart || !kcount) return fail(LDS_ENOMEM, "alloc");
+    if (!kx || !km || !ko || !gp || !kpart || !kcount) return set_error(LDS_ENOMEM, "alloc");
     HIP_TRY(hipMemsetAsync(kcount, 0, sizeof(unsigned) * kClusterCounters, st));
     HIP_TRY(launch_to_k4p(x, kx, B, C, T, C, 0, st));
     DOpt o1;
@@ -4104,14 +3968,14 @@ extern "C" int lds_test_gn_fold_split(const float* x, const float* w1, const flo
                                       const float* w2, const float* bias2, float* mid, float* out, int B, int C, int Cm, int Co, int T, int cfg, int tile_batch,
                                       int fmt, int reps, void* stream) {
     hipStream_t st = (hipStream_t)stream;
-    if (!x || !w1 || !w2 || !mid || !out || (fmt != -1 && fmt != FMT_BF16X3 && fmt != FMT_F16X2) || reps < 1) return fail(LDS_EINVAL, "bad argument");
+    if (!x || !w1 || !w2 || !mid || !out || (fmt != -1 && fmt != FMT_BF16X3 && fmt != FMT_F16X2) || reps < 1) return set_error(LDS_EINVAL, "bad argument");
     const bool f32 = fmt < 0;
     Owner own;
     TmpDev tmp;
     ConvW W1, W2;
     float *cg = nullptr, *c2 = nullptr;
-    if (!pack_conv(own, w1, bias1, Cm, C, 1, W1) || !pack_gn_fold(own, w2, bias2, gamma, beta, Co, Cm, groups, W2, cg, c2)) return fail(LDS_ENOMEM, "upload failed");
-    if (!f32 && (!make_split_twin(own, W1, fmt) || !make_split_twin(own, W2, fmt))) return fail(LDS_ENOMEM, "upload failed");
+    if (!pack_conv(own, w1, bias1, Cm, C, 1, W1) || !pack_gn_fold(own, w2, bias2, gamma, beta, Co, Cm, groups, W2, cg, c2)) return set_error(LDS_ENOMEM, "upload failed");
+    if (!f32 && (!make_split_twin(own, W1, fmt) || !make_split_twin(own, W2, fmt))) return set_error(LDS_ENOMEM, "upload failed");
     const int nT = (T + 31) / 32;
     auto act = [&](int Cc) { return f32 ? (size_t)Cc * (T + 2) : split_floats(fmt, Cc, T); };
     float* kx = tmp.f((size_t)B * act(C));
@@ -4120,7 +3984,7 @@ extern "C" int lds_test_gn_fold_split(const float* x, const float* w1, const flo
     float* gp = tmp.f((size_t)B * (Cm / 16) * nT * 2);
     float* kpart = tmp.f((size_t)kClusterPartFloats);
     unsigned* kcount = (unsigned*)tmp.f(kClusterCounters);
-    if (!kx || !km || !ko || !gp || !kpart || !kcount) return fail(LDS_ENOMEM, "alloc");
+    if (!kx || !km || !ko || !gp || !kpart || !kcount) return set_error(LDS_ENOMEM, "alloc");
     HIP_TRY(hipMemsetAsync(kcount, 0, sizeof(unsigned) * kClusterCounters, st));
     HIP_TRY(to_act_any(f32 ? 0 : fmt + 1, x, kx, B, C, T, C, 0, st));
     DOpt o1;
@@ -4152,20 +4016,20 @@ extern "C" int lds_test_gn_fold_split(const float* x, const float* w1, const flo
 extern "C" int lds_test_cluster_join(const float* xa, const float* xb, const float* w, const float* bias, int Ci, int Co, int K, int T, int B, int fmt, int reps,
                                      float* out, float* ref_a, float* ref_b, char* cfg_out, size_t cfg_cap, void* stream) {
     hipStream_t st = (hipStream_t)stream;
-    if (!xa || !xb || !w || !out || !ref_a || !ref_b || reps < 1 || (K != 1 && K != 3) || (fmt != -1 && fmt != FMT_BF16X3 && fmt != FMT_F16X2)) return fail(LDS_EINVAL, "bad argument");
+    if (!xa || !xb || !w || !out || !ref_a || !ref_b || reps < 1 || (K != 1 && K != 3) || (fmt != -1 && fmt != FMT_BF16X3 && fmt != FMT_F16X2)) return set_error(LDS_EINVAL, "bad argument");
     const bool f32 = fmt < 0;
     const int mode = f32 ? 0 : fmt + 1;
     Owner own;
     TmpDev tmp;
     ConvW W;
-    if (!pack_conv(own, w, bias, Co, Ci, K, W) || (!f32 && !make_split_twin(own, W, fmt))) return fail(LDS_ENOMEM, "upload failed");
+    if (!pack_conv(own, w, bias, Co, Ci, K, W) || (!f32 && !make_split_twin(own, W, fmt))) return set_error(LDS_ENOMEM, "upload failed");
     auto act = [&](int Cc) { return f32 ? (size_t)Cc * (T + 2) : split_floats(fmt, Cc, T); };
     float* ka = tmp.f((size_t)B * act(Ci));
     float* kb = tmp.f((size_t)B * act(Ci));
     float* ko = tmp.f((size_t)B * act(Co));
     float* kpart = tmp.f((size_t)kClusterPartFloats);
     unsigned* kcount = (unsigned*)tmp.f(kClusterCounters);
-    if (!ka || !kb || !ko || !kpart || !kcount) return fail(LDS_ENOMEM, "alloc");
+    if (!ka || !kb || !ko || !kpart || !kcount) return set_error(LDS_ENOMEM, "alloc");
     HIP_TRY(hipMemsetAsync(kcount, 0, sizeof(unsigned) * kClusterCounters, st));
     HIP_TRY(to_act_any(mode, xa, ka, B, Ci, T, Ci, 0, st));
     HIP_TRY(to_act_any(mode, xb, kb, B, Ci, T, Ci, 0, st));
@@ -4198,12 +4062,12 @@ extern "C" int lds_test_ln_chain_k4p(const float* x, const float* w1, const floa
     TmpDev tmp;
     ConvW W1, W2;
     float *c1 = nullptr, *c2 = nullptr;
-    if (!pack_conv(own, w1, nullptr, C, C, 1, W1) || !pack_ln_fold(own, w2, nullptr, gamma, beta, Co, C, {}, W2, c1, c2)) return fail(LDS_ENOMEM, "upload failed");
+    if (!pack_conv(own, w1, nullptr, C, C, 1, W1) || !pack_ln_fold(own, w2, nullptr, gamma, beta, Co, C, {}, W2, c1, c2)) return set_error(LDS_ENOMEM, "upload failed");
     float* kx = tmp.f((size_t)B * C * (T + 2));
     float* km = tmp.f((size_t)B * C * (T + 2));
     float* ko = tmp.f((size_t)B * Co * (T + 2));
     float* part = tmp.f((size_t)B * (C / 32) * T * 2);
-    if (!kx || !km || !ko || !part) return fail(LDS_ENOMEM, "alloc");
+    if (!kx || !km || !ko || !part) return set_error(LDS_ENOMEM, "alloc");
     HIP_TRY(launch_to_k4p(x, kx, B, C, T, C, 0, st));
     HIP_TRY(tap_fill(ko, (size_t)B * Co * (T + 2), st));
     DOpt o1;
@@ -4227,15 +4091,15 @@ extern "C" int lds_test_ln_chain_k4p(const float* x, const float* w1, const floa
 extern "C" int lds_test_voc_step(const float* x, const float* w1, const float* b1, const float* w2, const float* b2, int C, int T, int K, int dil, int mode,
                                  const float* acc, float div, float* out, float* out_act, int B, void* stream) {
     hipStream_t st = (hipStream_t)stream;
-    if (!x || !w1 || !w2 || !out || C % 64 || (K != 3 && K != 7 && K != 11)) return fail(LDS_EINVAL, "bad argument");
+    if (!x || !w1 || !w2 || !out || C % 64 || (K != 3 && K != 7 && K != 11)) return set_error(LDS_EINVAL, "bad argument");
     Owner own;
     TmpDev tmp;
     ConvW W1, W2;
-    if (!pack_conv(own, w1, b1, C, C, K, W1) || !pack_conv(own, w2, b2, C, C, K, W2)) return fail(LDS_ENOMEM, "upload failed");
+    if (!pack_conv(own, w1, b1, C, C, K, W1) || !pack_conv(own, w2, b2, C, C, K, W2)) return set_error(LDS_ENOMEM, "upload failed");
     const int P = kVocPad;
     const size_t n = (size_t)B * C * (T + 2 * P) + 4096;
     float *raw = tmp.f(n), *act = tmp.f(n), *mid = tmp.f(n), *o_raw = tmp.f(n), *o_act = tmp.f(n), *kacc = tmp.f(n);
-    if (!raw || !act || !mid || !o_raw || !o_act || !kacc) return fail(LDS_ENOMEM, "alloc");
+    if (!raw || !act || !mid || !o_raw || !o_act || !kacc) return set_error(LDS_ENOMEM, "alloc");
     HIP_TRY(hipMemsetAsync(mid, 0xff, n * sizeof(float), st));      // NaN fill: pads must be zeroed explicitly, real frames written
     HIP_TRY(hipMemsetAsync(act, 0xff, n * sizeof(float), st));
     HIP_TRY(launch_to_k4p_act(x, raw, act, 0.1f, B, C, T, P, st));
@@ -4256,7 +4120,7 @@ extern "C" int lds_test_voc_step(const float* x, const float* w1, const float* b
         HIP_TRY(launch_from_k4p_pad(o_raw, out, B, C, T, P, st));
         if (out_act) HIP_TRY(launch_from_k4p_pad(o_act, out_act, B, C, T, P, st));
     } else {
-        if (!acc) return fail(LDS_EINVAL, "mode 2 needs acc");
+        if (!acc) return set_error(LDS_EINVAL, "mode 2 needs acc");
         HIP_TRY(launch_to_k4p_act(acc, kacc, nullptr, 0.f, B, C, T, P, st));
         o2.acc_in = kacc; o2.out_div = div; o2.out_plain = 1;
         LDS_TRY(run_dconv(W2, mid, C, nullptr, 0, T, o2, out, B, st));
@@ -4277,9 +4141,9 @@ extern "C" int lds_test_attention_latency(const float* qkv, float* out, int B, i
 }
 // ragged batch (include/lds_test.h): lens = host int32 [B], the clips' lengths at the buffer's resolution
 extern "C" int lds_test_attention_ragged(const float* qkv, const int* lens, float* out, int B, int C, int T, int heads, int f16math, int latency, void* stream) {
-    if (!lens) return fail(LDS_EINVAL, "lens is null");
+    if (!lens) return set_error(LDS_EINVAL, "lens is null");
     for (int b = 0; b < B; ++b)
-        if (lens[b] < 1 || lens[b] > T) return fail(LDS_EINVAL, "length out of range");
+        if (lens[b] < 1 || lens[b] > T) return set_error(LDS_EINVAL, "length out of range");
     return attention_test_impl(qkv, out, B, C, T, heads, f16math, stream, latency ? B : 0, lens);
 }
 static int attention_test_impl(const float* qkv, float* out, int B, int C, int T, int heads, int f16math, void* stream, int tile_batch, const int* lens_host) {
@@ -4288,7 +4152,7 @@ static int attention_test_impl(const float* qkv, float* out, int B, int C, int T
     int* dlens = nullptr;
     if (lens_host) {
         dlens = (int*)tmp.f((size_t)B);
-        if (!dlens) return fail(LDS_ENOMEM, "alloc");
+        if (!dlens) return set_error(LDS_ENOMEM, "alloc");
         HIP_TRY(hipMemcpyAsync(dlens, lens_host, sizeof(int) * B, hipMemcpyHostToDevice, st));
     }
     float* qkp = tmp.f((size_t)B * 2 * C * T);       // plain [B][2C][T]
@@ -4296,7 +4160,7 @@ static int attention_test_impl(const float* qkv, float* out, int B, int C, int T
     float* vt = tmp.f((size_t)B * C * (T + 3));
     float* kqk = tmp.f((size_t)B * 2 * C * (T + 2));
     float* ko = tmp.f((size_t)B * C * (T + 2));
-    if (!qkp || !vpl || !vt || !kqk || !ko) return fail(LDS_ENOMEM, "alloc");
+    if (!qkp || !vpl || !vt || !kqk || !ko) return set_error(LDS_ENOMEM, "alloc");
     for (int b = 0; b < B; ++b) {
         HIP_TRY(hipMemcpyAsync(qkp + (size_t)b * 2 * C * T, qkv + (size_t)b * 3 * C * T, sizeof(float) * 2 * C * T, hipMemcpyDeviceToDevice, st));
         HIP_TRY(hipMemcpyAsync(vpl + (size_t)b * C * T, qkv + (size_t)b * 3 * C * T + (size_t)2 * C * T, sizeof(float) * C * T, hipMemcpyDeviceToDevice, st));
@@ -4324,10 +4188,10 @@ static int attention_test_impl(const float* qkv, float* out, int B, int C, int T
 extern "C" int lds_test_conv_transpose(const float* x, const float* w, const float* bias, float* out, int B, int Ci, int Co, int T, int K,
                                        int stride, int pad, float in_slope, void* stream) {
     hipStream_t st = (hipStream_t)stream;
-    if (K % stride || pad != (K - stride + 1) / 2) return fail(LDS_EINVAL, "unsupported transposed-conv geometry");
+    if (K % stride || pad != (K - stride + 1) / 2) return set_error(LDS_EINVAL, "unsupported transposed-conv geometry");
     Owner own;
     ConvW W;
-    if (!pack_convT(own, w, bias, Ci, Co, K, stride, W)) return fail(LDS_ENOMEM, "upload failed");
+    if (!pack_convT(own, w, bias, Ci, Co, K, stride, W)) return set_error(LDS_ENOMEM, "upload failed");
     Src s{x, Ci, nullptr, 0, T};
     ConvOpt o;
     o.pad = W.K - 1; o.phases = stride; o.tpad = pad; o.To = T + 1; o.Tout = (T - 1) * stride - 2 * pad + K; o.Cout = Co;
@@ -4339,10 +4203,10 @@ extern "C" int lds_test_conv_transpose(const float* x, const float* w, const flo
 
 extern "C" int lds_test_split_roundtrip(const float* x, float* out, int B, int C, int T, int fmt, void* stream) {
     hipStream_t st = (hipStream_t)stream;
-    if (!x || !out || (C & 7) || (fmt != FMT_BF16X3 && fmt != FMT_F16X2)) return fail(LDS_EINVAL, "bad argument");
+    if (!x || !out || (C & 7) || (fmt != FMT_BF16X3 && fmt != FMT_F16X2)) return set_error(LDS_EINVAL, "bad argument");
     TmpDev tmp;
     float* k = tmp.f((size_t)B * split_floats(fmt, C, T));
-    if (!k) return fail(LDS_ENOMEM, "alloc");
+    if (!k) return set_error(LDS_ENOMEM, "alloc");
     HIP_TRY(launch_to_k8b3(x, k, B, C, T, C, 0, st, fmt));
     HIP_TRY(launch_from_k8b3(k, out, B, C, T, st, fmt));
     HIP_TRY(hipStreamSynchronize(st));
@@ -4357,7 +4221,7 @@ extern "C" int lds_test_gn_apply_bf3(const float* x1, const float* x2, int C1, i
 extern "C" int lds_test_gn_apply_split(const float* x1, const float* x2, int C1, int C2, int T, int groups, float eps, const float* gamma,
                                        const float* beta, const float* scale_shift, int silu, float* out, int B, int fmt, void* stream) {
     hipStream_t st = (hipStream_t)stream;
-    if (fmt != FMT_BF16X3 && fmt != FMT_F16X2) return fail(LDS_EINVAL, "bad argument");
+    if (fmt != FMT_BF16X3 && fmt != FMT_F16X2) return set_error(LDS_EINVAL, "bad argument");
     Owner own;
     TmpDev tmp;
     const int C = C1 + C2, nT = (T + 31) / 32;
@@ -4368,7 +4232,7 @@ extern "C" int lds_test_gn_apply_split(const float* x1, const float* x2, int C1,
     float* ky = tmp.f((size_t)B * split_floats(fmt, C, T));
     float* p1 = tmp.f((size_t)B * (C1 / 16) * nT * 2);
     float* p2 = C2 ? tmp.f((size_t)B * (C2 / 16) * nT * 2) : nullptr;
-    if (!g || !be || !k1 || (C2 && (!k2 || !p2)) || !ky || !p1) return fail(LDS_ENOMEM, "alloc");
+    if (!g || !be || !k1 || (C2 && (!k2 || !p2)) || !ky || !p1) return set_error(LDS_ENOMEM, "alloc");
     HIP_TRY(launch_to_k8b3(x1, k1, B, C1, T, C1, 0, st, fmt));
     HIP_TRY(launch_gn_partials_bf3(k1, C1, T, (float2*)p1, B, st, fmt));
     if (C2) {
@@ -4394,15 +4258,15 @@ extern "C" int lds_debug_set_voc_pair(int on) {
 extern "C" int lds_test_voc_pair(const float* x, const float* w1, const float* b1, const float* w2, const float* b2, int C, int T, int K, int dil,
                                  const float* acc, float div, const int32_t* lengths, float* out, int B, void* stream) {
     hipStream_t st = (hipStream_t)stream;
-    if (!x || !w1 || !w2 || !out || !voc_pair_applies(C, K, dil) || B < 1 || B > 64) return fail(LDS_EINVAL, "bad argument");
+    if (!x || !w1 || !w2 || !out || !voc_pair_applies(C, K, dil) || B < 1 || B > 64) return set_error(LDS_EINVAL, "bad argument");
     Owner own;
     TmpDev tmp;
     ConvW W1, W2;
-    if (!pack_conv(own, w1, b1, C, C, K, W1) || !pack_conv(own, w2, b2, C, C, K, W2)) return fail(LDS_ENOMEM, "upload failed");
+    if (!pack_conv(own, w1, b1, C, C, K, W1) || !pack_conv(own, w2, b2, C, C, K, W2)) return set_error(LDS_ENOMEM, "upload failed");
     int* vl = nullptr;
     if (lengths) {
         vl = (int*)tmp.f(64);
-        if (!vl) return fail(LDS_ENOMEM, "alloc");
+        if (!vl) return set_error(LDS_ENOMEM, "alloc");
         float t4[64];
         memcpy(t4, lengths, sizeof(int) * B);
         HIP_TRY(launch_set_list((float*)vl, t4, B, st));
@@ -4418,26 +4282,26 @@ extern "C" int lds_test_voc_pair(const float* x, const float* w1, const float* b
 static int conv_down_test_impl(const float* x, const float* w, const float* b, int Ci, int Co, int K, int stride, int T, int B, float slope,
                                const int32_t* lengths_in, const int32_t* lengths_out, int tile, float* out, char* cfg_out, size_t cfg_cap, void* stream) {
     hipStream_t st = (hipStream_t)stream;
-    if (!x || !w || !out || Ci < 1 || Co < 1 || K < stride || stride < 1 || T < 1 || B < 1 || B > 65535 || T % stride) return fail(LDS_EINVAL, "bad argument");
+    if (!x || !w || !out || Ci < 1 || Co < 1 || K < stride || stride < 1 || T < 1 || B < 1 || B > 65535 || T % stride) return set_error(LDS_EINVAL, "bad argument");
     const int pad = (K - stride + 1) / 2, To = (T + 2 * pad - K) / stride + 1;
     const int32_t* src[2] = {lengths_in, lengths_out};
     const int lim[2] = {T, To};
     for (int i = 0; i < 2 && lengths_in; ++i)
         for (int e = 0; e < B; ++e)
-            if (src[i][e] < 0 || src[i][e] > lim[i]) return fail(LDS_EINVAL, "lengths_%s[%d] = %d outside 0 .. %d", i ? "out" : "in", e, src[i][e], lim[i]);
+            if (src[i][e] < 0 || src[i][e] > lim[i]) return set_error(LDS_EINVAL, "lengths_%s[%d] = %d outside 0 .. %d", i ? "out" : "in", e, src[i][e], lim[i]);
     Owner own;
     TmpDev tmp;
     DownW d;
     d.w = own.upload(std::vector<float>(w, w + (size_t)Co * Ci * K));
     if (b) d.bias = own.upload(std::vector<float>(b, b + Co));
-    if (!d.w || (b && !d.bias)) return fail(LDS_ENOMEM, "upload failed");
+    if (!d.w || (b && !d.bias)) return set_error(LDS_ENOMEM, "upload failed");
     d.Co = Co; d.Ci = Ci; d.K = K; d.stride = stride; d.pad = pad;
     int* vl[2] = {nullptr, nullptr};
     for (int i = 0; i < 2 && lengths_in; ++i) {
         float t4[64];
         memcpy(t4, src[i], sizeof(int) * B);
         vl[i] = (int*)tmp.f(64);
-        if (!vl[i]) return fail(LDS_ENOMEM, "alloc");
+        if (!vl[i]) return set_error(LDS_ENOMEM, "alloc");
         HIP_TRY(launch_set_list((float*)vl[i], t4, B, st));
     }
     LDS_TRY(run_down(d, x, T, slope, out, B, st, tile, vl[0], vl[1]));
@@ -4454,7 +4318,7 @@ extern "C" int lds_test_conv_down(const float* x, const float* w, const float* b
 extern "C" int lds_test_conv_down_ragged(const float* x, const float* w, const float* b, int Ci, int Co, int K, int stride, int T, int B, float slope,
                                          const int32_t* lengths_in, const int32_t* lengths_out, int tile, float* out, char* cfg_out, size_t cfg_cap,
                                          void* stream) {
-    if (!lengths_in || !lengths_out || B < 1 || B > 64) return fail(LDS_EINVAL, "bad argument: lengths_in / lengths_out null or B %d outside 1 .. 64", B);
+    if (!lengths_in || !lengths_out || B < 1 || B > 64) return set_error(LDS_EINVAL, "bad argument: lengths_in / lengths_out null or B %d outside 1 .. 64", B);
     return conv_down_test_impl(x, w, b, Ci, Co, K, stride, T, B, slope, lengths_in, lengths_out, tile, out, cfg_out, cfg_cap, stream);
 }
 extern "C" int lds_debug_set_gn_fold(int on) {
@@ -4471,9 +4335,9 @@ extern "C" int lds_debug_set_split_rule(int rule) {
 static int test_upload_lens(TmpDev& tmp, const int32_t* host, int B, int*& dev, hipStream_t st) {
     dev = nullptr;
     if (!host) return LDS_OK;
-    if (B < 1 || B > 64) return fail(LDS_EINVAL, "per-utterance lengths: 1 .. 64 batch elements (got %d)", B);
+    if (B < 1 || B > 64) return set_error(LDS_EINVAL, "per-utterance lengths: 1 .. 64 batch elements (got %d)", B);
     dev = (int*)tmp.f(64);
-    if (!dev) return fail(LDS_ENOMEM, "alloc");
+    if (!dev) return set_error(LDS_ENOMEM, "alloc");
     float t4[64];
     memcpy(t4, host, sizeof(int) * B);
     HIP_TRY(launch_set_list((float*)dev, t4, B, st));
@@ -4494,17 +4358,17 @@ extern "C" int lds_test_dconv_pair(const float* h, const float* x1, const float*
     hipStream_t st = (hipStream_t)stream;
     if (!h || !x1 || (C2 > 0) != (x2 != nullptr) || !w3 || !b3 || !w1 || !b1 || !out || !gnpart || B < 1 || T < 1 || Cm < 8 || C1 < 8 || C2 < 0 || (Cm & 7) || (C1 & 7) ||
         (C2 & 7) || Co < 32 || Co % 32 || lvl < 0 || tile_batch < 0 || (fmt != -1 && fmt != FMT_BF16X3 && fmt != FMT_F16X2))
-        return fail(LDS_EINVAL, "bad argument");
+        return set_error(LDS_EINVAL, "bad argument");
     const bool f32 = fmt < 0;
     Owner own;
     TmpDev tmp;
     ConvW W3, W1;
-    if (!pack_conv(own, w3, nullptr, Co, Cm, 3, W3) || !pack_conv(own, w1, nullptr, Co, C1 + C2, 1, W1)) return fail(LDS_ENOMEM, "upload failed");
-    if (!f32 && !make_split_twin_pair(own, W3, W1, fmt)) return fail(LDS_ENOMEM, "upload failed");
+    if (!pack_conv(own, w3, nullptr, Co, Cm, 3, W3) || !pack_conv(own, w1, nullptr, Co, C1 + C2, 1, W1)) return set_error(LDS_ENOMEM, "upload failed");
+    if (!f32 && !make_split_twin_pair(own, W3, W1, fmt)) return set_error(LDS_ENOMEM, "upload failed");
     std::vector<float> bp(W3.Mp, 0.f);
     for (int co = 0; co < Co; ++co) bp[co] = b3[co] + b1[co];
     float* bias_pair = own.upload(bp);
-    if (!bias_pair) return fail(LDS_ENOMEM, "upload failed");
+    if (!bias_pair) return set_error(LDS_ENOMEM, "upload failed");
     int* lens = nullptr;
     LDS_TRY(test_upload_lens(tmp, lengths, B, lens, st));
     const TestActs act{fmt, B, st};
@@ -4515,7 +4379,7 @@ extern "C" int lds_test_dconv_pair(const float* h, const float* x1, const float*
     float* ko = tmp.f(act.floats(Co, T));
     float* kpart = tile_batch ? tmp.f((size_t)kClusterPartFloats) : nullptr;
     unsigned* kcount = tile_batch ? (unsigned*)tmp.f(kClusterCounters) : nullptr;
-    if (!kh || !k1 || (C2 && !k2) || !ko || (tile_batch && (!kpart || !kcount))) return fail(LDS_ENOMEM, "alloc");
+    if (!kh || !k1 || (C2 && !k2) || !ko || (tile_batch && (!kpart || !kcount))) return set_error(LDS_ENOMEM, "alloc");
     if (kcount) HIP_TRY(hipMemsetAsync(kcount, 0, sizeof(unsigned) * kClusterCounters, st));
     HIP_TRY(hipMemsetAsync(ko, 0xff, sizeof(float) * act.floats(Co, T), st));                        // NaN fill: every frame and every partial must be written
     HIP_TRY(hipMemsetAsync(gnpart, 0xff, sizeof(float) * (size_t)B * (Co / 16) * nT * 2, st));
@@ -4529,7 +4393,7 @@ extern "C" int lds_test_dconv_pair(const float* h, const float* x1, const float*
         rc = f32 ? run_dconv_pair(W3, kh, W1, k1, C1, k2, C2, T, bias_pair, (float2*)gnpart, ko, B, st, lvl)
                  : run_dconv_pair_bf3(W3, kh, W1, k1, C1, k2, C2, T, bias_pair, (float2*)gnpart, ko, B, st, fmt, lvl);
     }
-    if (rc == 1) rc = fail(LDS_EINVAL, "dconv pair: no fused variant for Cm %d C1 %d C2 %d Co %d T %d (fmt %d, tile_batch %d)", Cm, C1, C2, Co, T, fmt, tile_batch);
+    if (rc == 1) rc = set_error(LDS_EINVAL, "dconv pair: no fused variant for Cm %d C1 %d C2 %d Co %d T %d (fmt %d, tile_batch %d)", Cm, C1, C2, Co, T, fmt, tile_batch);
     if (rc == LDS_OK) {
         if (cfg_out && cfg_cap) snprintf(cfg_out, cfg_cap, "%s", f32 ? conv_dma_last_config() : conv_bf3_last_config());
         if (f32) HIP_TRY(tap_take(ko, act.floats(Co, T), st));
@@ -4546,17 +4410,17 @@ extern "C" int lds_test_dconv_ex(const lds_dconv_ex_test* a, float* out, float* 
         a->Co % 32 || a->K < 1 || a->stride < 1 || a->pad < 0 || (a->epilogue != EPI_NONE && a->epilogue != EPI_GELU && a->epilogue != EPI_GEGLU) || a->lvl_in < 0 ||
         a->lvl_out < 0 || a->tile_batch < 0 || (a->fmt != -1 && a->fmt != FMT_BF16X3 && a->fmt != FMT_F16X2) || (a->ln_gamma != nullptr) != (a->ln_beta != nullptr) ||
         a->v_split < 0 || a->v_split == 1 || a->cfg < 0)
-        return fail(LDS_EINVAL, "bad argument");
+        return set_error(LDS_EINVAL, "bad argument");
     const bool f32 = a->fmt < 0, ln = a->ln_gamma != nullptr, geglu = a->epilogue == EPI_GEGLU;
     // the transformer's two folded projections as the UNet runs them: FF1 (GEGLU rows interleaved as pack_geglu does) and QKV (value third in VT layout)
-    if (geglu && (!ln || !f32 || a->Co % 128 || a->res || gnpart || a->v_split)) return fail(LDS_EINVAL, "GEGLU here is the folded FF1: fp32, LayerNorm fold, Co a multiple of 128");
+    if (geglu && (!ln || !f32 || a->Co % 128 || a->res || gnpart || a->v_split)) return set_error(LDS_EINVAL, "GEGLU here is the folded FF1: fp32, LayerNorm fold, Co a multiple of 128");
     if (a->v_split && (!f32 || a->Co % 3 || (a->Co / 3) % a->v_split || ((a->Co / 3) * 2) % 8 || a->res || gnpart || a->K != 1 || a->stride != 1))
-        return fail(LDS_EINVAL, "v_split is the fp32 QKV projection: 1x1, Co = 3 C, C a multiple of the head dim");
+        return set_error(LDS_EINVAL, "v_split is the fp32 QKV projection: 1x1, Co = 3 C, C a multiple of the head dim");
     const int mode = f32 ? 0 : a->fmt + 1;
     const int Ci = a->C1 + a->C2, T = a->T;
     const int To = (T + 2 * a->pad - (a->K - 1) - 1) / a->stride + 1;
-    if (To < 1) return fail(LDS_EINVAL, "bad argument: no output frame");
-    if (ln && (a->K != 1 || a->C2 || Ci % 32)) return fail(LDS_EINVAL, "the LayerNorm fold takes a 1x1 convolution over one source of a multiple of 32 channels");
+    if (To < 1) return set_error(LDS_EINVAL, "bad argument: no output frame");
+    if (ln && (a->K != 1 || a->C2 || Ci % 32)) return set_error(LDS_EINVAL, "the LayerNorm fold takes a 1x1 convolution over one source of a multiple of 32 channels");
     Owner own;
     TmpDev tmp;
     ConvW W, Wid;
@@ -4573,7 +4437,7 @@ extern "C" int lds_test_dconv_ex(const lds_dconv_ex_test* a, float* out, float* 
         ok = pack_conv(own, eye.data(), nullptr, Ci, Ci, 1, Wid);
     }
     if (ok && !f32) ok = make_split_twin(own, W, a->fmt) && (!ln || make_split_twin(own, Wid, a->fmt));
-    if (!ok) return fail(LDS_ENOMEM, "test dconv: upload failed");
+    if (!ok) return set_error(LDS_ENOMEM, "test dconv: upload failed");
     int* lens = nullptr;
     LDS_TRY(test_upload_lens(tmp, a->lengths, B, lens, st));
     const TestActs act{a->fmt, B, st};
@@ -4587,7 +4451,7 @@ extern "C" int lds_test_dconv_ex(const lds_dconv_ex_test* a, float* out, float* 
     float* vout = a->v_split ? tmp.f((size_t)B * (Cout - Ck) * To4) : nullptr;
     float* kpart = a->tile_batch ? tmp.f((size_t)kClusterPartFloats) : nullptr;
     unsigned* kcount = a->tile_batch ? (unsigned*)tmp.f(kClusterCounters) : nullptr;
-    if (!k1 || (a->C2 && !k2) || (ln && (!kx || !part)) || (a->res && !kres) || !ko || (a->v_split && !vout) || (a->tile_batch && (!kpart || !kcount))) return fail(LDS_ENOMEM, "alloc");
+    if (!k1 || (a->C2 && !k2) || (ln && (!kx || !part)) || (a->res && !kres) || !ko || (a->v_split && !vout) || (a->tile_batch && (!kpart || !kcount))) return set_error(LDS_ENOMEM, "alloc");
     if (kcount) HIP_TRY(hipMemsetAsync(kcount, 0, sizeof(unsigned) * kClusterCounters, st));
     HIP_TRY(hipMemsetAsync(ko, 0xff, sizeof(float) * act.floats(Ck, To), st));      // NaN fill: every frame and every partial must be written
     if (vout) HIP_TRY(hipMemsetAsync(vout, 0xff, sizeof(float) * (size_t)B * (Cout - Ck) * To4, st));      // (the VT tail too)
@@ -4629,7 +4493,7 @@ extern "C" int lds_test_dconv_ex(const lds_dconv_ex_test* a, float* out, float* 
 
 // ---- conv_wino (include/lds_test.h) ----
 extern "C" int lds_test_wino_pack(const float* g, int Co, int Ci, float* U) {
-    if (!g || !U || Co < 1 || Ci < 1) return fail(LDS_EINVAL, "bad argument");
+    if (!g || !U || Co < 1 || Ci < 1) return set_error(LDS_EINVAL, "bad argument");
     std::vector<float> u;
     wino_taps(g, Co, Ci, u);
     memcpy(U, u.data(), u.size() * sizeof(float));
@@ -4654,17 +4518,17 @@ struct WinoTestState {
 static int wino_test_setup(const lds_wino_test* a, int B, hipStream_t st, WinoTestState& s) {
     if (!a || !a->x1 || !a->w || !a->gamma || !a->beta || B < 1 || a->T < 1 || (a->C2 > 0) != (a->x2 != nullptr) || a->C1 < 16 || (a->C1 & 15) || a->C2 < 0 || (a->C2 & 15) ||
         a->Co < 16 || (a->Co & 15) || a->groups < 1 || (a->C1 + a->C2) % a->groups || ((a->C1 + a->C2) / a->groups) % 16 || a->cfg < 0 || a->lvl < 0 || a->lvl > 30)
-        return fail(LDS_EINVAL, "bad argument");
+        return set_error(LDS_EINVAL, "bad argument");
     const int Ci = a->C1 + a->C2, T = a->T, nT = (T + 31) / 32;
     s.Ci = Ci; s.P = (T + 1) / 2;
     int32_t reduced[64];      // the lengths at level lvl, as the kernels reduce them: (n - 1) / 2 + 1 per level
     for (int b = 0; b < B && b < 64 && a->lengths; ++b) {
         int n = a->lengths[b];
         for (int i = 0; i < a->lvl && n >= 1; ++i) n = (n - 1) / 2 + 1;
-        if (n < 1 || n > T) return fail(LDS_EINVAL, "lengths[%d] = %d (%d at level %d) outside 1 .. %d", b, a->lengths[b], n, a->lvl, T);
+        if (n < 1 || n > T) return set_error(LDS_EINVAL, "lengths[%d] = %d (%d at level %d) outside 1 .. %d", b, a->lengths[b], n, a->lvl, T);
         reduced[b] = n;
     }
-    if (!pack_conv(s.own, a->w, a->bias, a->Co, Ci, 3, s.W) || !pack_wino(s.own, a->w, a->Co, Ci, s.W)) return fail(LDS_ENOMEM, "upload failed");
+    if (!pack_conv(s.own, a->w, a->bias, a->Co, Ci, 3, s.W) || !pack_wino(s.own, a->w, a->Co, Ci, s.W)) return set_error(LDS_ENOMEM, "upload failed");
     s.gamma = up_vec(s.own, a->gamma, Ci); s.beta = up_vec(s.own, a->beta, Ci);
     LDS_TRY(test_upload_lens(s.tmp, a->lengths, B, s.lens, st));
     LDS_TRY(test_upload_lens(s.tmp, a->lengths ? reduced : nullptr, B, s.lens_lvl, st));
@@ -4676,7 +4540,7 @@ static int wino_test_setup(const lds_wino_test* a, int B, hipStream_t st, WinoTe
     s.kres = a->res ? s.tmp.f(s.out_floats) : nullptr;
     s.planes = s.tmp.f(std::max(s.plane_floats, (size_t)B * Ci * (T + 2)));      // (the direct path's K4P tensor in lds_bench_wino)
     s.ko = s.tmp.f(s.out_floats);
-    if (!s.gamma || !s.beta || !s.k1 || (a->C2 && (!s.k2 || !s.gp2)) || !s.gp1 || (a->res && !s.kres) || !s.planes || !s.ko) return fail(LDS_ENOMEM, "alloc");
+    if (!s.gamma || !s.beta || !s.k1 || (a->C2 && (!s.k2 || !s.gp2)) || !s.gp1 || (a->res && !s.kres) || !s.planes || !s.ko) return set_error(LDS_ENOMEM, "alloc");
     HIP_TRY(hipMemsetAsync(s.gp1, 0xff, sizeof(float2) * (size_t)B * (a->C1 / 16) * nT, st));      // (NaN: a partial beyond a length is never read)
     if (a->C2) HIP_TRY(hipMemsetAsync(s.gp2, 0xff, sizeof(float2) * (size_t)B * (a->C2 / 16) * nT, st));
     HIP_TRY(launch_to_k4p(a->x1, s.k1, B, a->C1, T, a->C1, 0, st, s.lens_lvl));
@@ -4695,7 +4559,7 @@ static int wino_test_run(const lds_wino_test* a, WinoTestState& s, float2* gnpar
     return run_wconv(s.W, s.planes, a->T, s.kres, gnpart, s.ko, B, st, a->lvl, a->cfg);
 }
 static int wino_conv_test(const lds_wino_test* a, float* out, float* vplanes, float* gnpart, int B, hipStream_t st) {
-    if (!out) return fail(LDS_EINVAL, "bad argument");
+    if (!out) return set_error(LDS_EINVAL, "bad argument");
     WinoTestState s;
     LDS_TRY(wino_test_setup(a, B, st, s));
     // NaN fill: every plane entry, every output frame (pads included) and every partial of a block inside a length must be written
@@ -4734,13 +4598,13 @@ extern "C" int lds_bench_wino(const float* x1, const float* x2, int C1, int C2, 
                               int groups, int silu, const float* w, const float* bias, int Co, const float* res, int cfg, int B, int iters, int reps,
                               float* ms_direct, float* ms_wino, char* cfg_out, size_t cfg_cap, void* stream) {
     hipStream_t st = (hipStream_t)stream;
-    if (!ms_direct || !ms_wino || iters < 1 || reps < 1) return fail(LDS_EINVAL, "bad argument");
+    if (!ms_direct || !ms_wino || iters < 1 || reps < 1) return set_error(LDS_EINVAL, "bad argument");
     const lds_wino_test args{x1, x2, C1, C2, T, gamma, beta, scale_shift, groups, silu, w, bias, Co, res, nullptr, 0, cfg, 0};
     const lds_wino_test* a = &args;
     WinoTestState s;
     LDS_TRY(wino_test_setup(a, B, st, s));
     float2* gnpart = (float2*)s.tmp.f((size_t)B * (a->Co / 16) * ((a->T + 31) / 32) * 2);
-    if (!gnpart) return fail(LDS_ENOMEM, "alloc");
+    if (!gnpart) return set_error(LDS_ENOMEM, "alloc");
     DOpt o;
     o.pad = 1; o.res = s.kres; o.gnpart_out = gnpart;
     auto direct = [&]() -> int {
@@ -4781,21 +4645,21 @@ extern "C" int lds_test_voc_ups(const float* x, const float* w, const float* bia
     while ((1 << lg) < stride) ++lg;
     if (!x || !w || !out || !out_act || B < 1 || T < 1 || Ci < 16 || Ci % 16 || Co < 64 || Co % 64 || stride < 2 || stride > 16 || (1 << lg) != stride || K != 2 * stride ||
         (lengths_in != nullptr) != (lengths_out != nullptr))
-        return fail(LDS_EINVAL, "bad argument");
+        return set_error(LDS_EINVAL, "bad argument");
     const int P = kVocPad, tpad = (K - stride + 1) / 2, Tn = (T - 1) * stride - 2 * tpad + K;
     for (int b = 0; b < B && lengths_in; ++b)
         if (lengths_in[b] < 0 || lengths_in[b] > T || lengths_out[b] < 0 || lengths_out[b] > Tn)
-            return fail(LDS_EINVAL, "lengths_in[%d] = %d / lengths_out[%d] = %d outside 0 .. %d / 0 .. %d", b, lengths_in[b], b, lengths_out[b], T, Tn);
+            return set_error(LDS_EINVAL, "lengths_in[%d] = %d / lengths_out[%d] = %d outside 0 .. %d / 0 .. %d", b, lengths_in[b], b, lengths_out[b], T, Tn);
     Owner own;
     TmpDev tmp;
     ConvW W;
-    if (!pack_convT(own, w, bias, Ci, Co, K, stride, W)) return fail(LDS_ENOMEM, "upload failed");
+    if (!pack_convT(own, w, bias, Ci, Co, K, stride, W)) return set_error(LDS_ENOMEM, "upload failed");
     int *vin = nullptr, *vout = nullptr;
     LDS_TRY(test_upload_lens(tmp, lengths_in, B, vin, st));
     LDS_TRY(test_upload_lens(tmp, lengths_out, B, vout, st));
     const size_t n_in = (size_t)B * Ci * (T + 2 * P), n_out = (size_t)B * Co * (Tn + 2 * P);
     float *scratch = tmp.f(n_in), *kin = tmp.f(n_in), *o_raw = tmp.f(n_out), *o_act = tmp.f(n_out);
-    if (!scratch || !kin || !o_raw || !o_act) return fail(LDS_ENOMEM, "alloc");
+    if (!scratch || !kin || !o_raw || !o_act) return set_error(LDS_ENOMEM, "alloc");
     HIP_TRY(hipMemsetAsync(kin, 0xff, n_in * sizeof(float), st));        // NaN fill: pads must be zeroed explicitly, real frames written
     HIP_TRY(hipMemsetAsync(o_raw, 0xff, n_out * sizeof(float), st));
     HIP_TRY(hipMemsetAsync(o_act, 0xff, n_out * sizeof(float), st));
@@ -4817,18 +4681,18 @@ extern "C" int lds_test_voc_ups(const float* x, const float* w, const float* bia
 // The wav2vec 2.0 encoder's own kernels alone (w2v.hip), plain tensors in and out; every pointer but the lengths is a device pointer.
 extern "C" int lds_test_w2v_conv0(const float* audio, const int32_t* lengths, const float* w, const float* bias, const float* gamma, const float* beta,
                                   float eps, float* out, int B, int C, int64_t L, void* stream) {
-    if (!audio || !w || !bias || !gamma || !beta || !out || B < 1 || B > 64 || L < 10 || L > ((int64_t)1 << 30)) return fail(LDS_EINVAL, "bad argument");
+    if (!audio || !w || !bias || !gamma || !beta || !out || B < 1 || B > 64 || L < 10 || L > ((int64_t)1 << 30)) return set_error(LDS_EINVAL, "bad argument");
     hipStream_t st = (hipStream_t)stream;
     TmpDev tmp;
     const int N0 = (int)((L - 10) / 5 + 1);
     float* ko = tmp.f((size_t)B * C * (N0 + 2));
     int* dl = (int*)tmp.f(128);
-    if (!ko || !dl) return fail(LDS_ENOMEM, "alloc");
+    if (!ko || !dl) return set_error(LDS_ENOMEM, "alloc");
     const int *slen = nullptr, *nlen = nullptr;
     if (lengths) {
         int32_t n0[64];
         for (int b = 0; b < B; ++b) {
-            if (lengths[b] < 10 || lengths[b] > L) return fail(LDS_EINVAL, "length[%d] = %d outside 10 .. %lld", b, lengths[b], (long long)L);
+            if (lengths[b] < 10 || lengths[b] > L) return set_error(LDS_EINVAL, "length[%d] = %d outside 10 .. %lld", b, lengths[b], (long long)L);
             n0[b] = (lengths[b] - 10) / 5 + 1;
         }
         LDS_TRY(upload_clip_ints(lengths, B, dl, st));
@@ -4842,17 +4706,17 @@ extern "C" int lds_test_w2v_conv0(const float* audio, const int32_t* lengths, co
 }
 extern "C" int lds_test_w2v_ln_act(const float* x, const int32_t* n_frames, const float* gamma, const float* beta, float eps, float* out, float* part, int B,
                                    int C, int T, void* stream) {
-    if (!x || !gamma || !beta || !out || B < 1 || B > 64 || T < 1 || C < 64 || C % 64) return fail(LDS_EINVAL, "bad argument");
+    if (!x || !gamma || !beta || !out || B < 1 || B > 64 || T < 1 || C < 64 || C % 64) return set_error(LDS_EINVAL, "bad argument");
     hipStream_t st = (hipStream_t)stream;
     TmpDev tmp;
     float* kx = tmp.f((size_t)B * C * (T + 2));
     float* ko = tmp.f((size_t)B * C * (T + 2));
     int* dl = (int*)tmp.f(64);
-    if (!kx || !ko || !dl) return fail(LDS_ENOMEM, "alloc");
+    if (!kx || !ko || !dl) return set_error(LDS_ENOMEM, "alloc");
     const int* nlen = nullptr;
     if (n_frames) {
         for (int b = 0; b < B; ++b)
-            if (n_frames[b] < 1 || n_frames[b] > T) return fail(LDS_EINVAL, "n_frames[%d] = %d outside 1 .. %d", b, n_frames[b], T);
+            if (n_frames[b] < 1 || n_frames[b] > T) return set_error(LDS_EINVAL, "n_frames[%d] = %d outside 1 .. %d", b, n_frames[b], T);
         LDS_TRY(upload_clip_ints(n_frames, B, dl, st));
         nlen = dl;
     }
@@ -4866,7 +4730,7 @@ extern "C" int lds_test_w2v_ln_act(const float* x, const int32_t* n_frames, cons
 // The w2v-BERT 2.0 encoder's own kernels alone (w2vbert.hip, attention_k4p.hip), plain tensors in and out; every pointer but the lengths is a
 // device pointer.
 extern "C" int lds_test_w2vbert_fbank(const float* audio, const int32_t* lengths, float* out, int B, int64_t L, void* stream) {
-    if (!audio || !out || B < 1 || B > 64 || L < kW2vbertMinSamples || L > ((int64_t)1 << 30)) return fail(LDS_EINVAL, "bad argument");
+    if (!audio || !out || B < 1 || B > 64 || L < kW2vbertMinSamples || L > ((int64_t)1 << 30)) return set_error(LDS_EINVAL, "bad argument");
     hipStream_t st = (hipStream_t)stream;
     const int n_mels = 80, stride = 2, N = w2vbert_frames(L), R = (N + 1) / 2;
     Owner own;
@@ -4877,11 +4741,11 @@ extern "C" int lds_test_w2vbert_fbank(const float* audio, const int32_t* lengths
     float* logspec = tmp.f((size_t)B * n_mels * N);
     double2* stat = (double2*)tmp.f((size_t)B * n_mels * 4);
     int* dl = (int*)tmp.f(64);
-    if (!basis || !filtT || !logspec || !stat || !dl) return fail(LDS_ENOMEM, "alloc");
+    if (!basis || !filtT || !logspec || !stat || !dl) return set_error(LDS_ENOMEM, "alloc");
     const int* slen = nullptr;
     if (lengths) {
         for (int b = 0; b < B; ++b)
-            if (lengths[b] < kW2vbertMinSamples || lengths[b] > L) return fail(LDS_EINVAL, "length[%d] = %d outside %d .. %lld", b, lengths[b], kW2vbertMinSamples, (long long)L);
+            if (lengths[b] < kW2vbertMinSamples || lengths[b] > L) return set_error(LDS_EINVAL, "length[%d] = %d outside %d .. %lld", b, lengths[b], kW2vbertMinSamples, (long long)L);
         LDS_TRY(upload_clip_ints(lengths, B, dl, st));
         slen = dl;
     }
@@ -4892,7 +4756,7 @@ extern "C" int lds_test_w2vbert_fbank(const float* audio, const int32_t* lengths
 extern "C" int lds_test_w2vbert_attention(const float* qkv, const float* E, const int32_t* q_rows, const int32_t* k_rows, float* out, int B, int C, int T,
                                           int heads, int left, int right, void* stream) {
     if (!qkv || !E || !out || B < 1 || B > 64 || T < 1 || heads < 1 || C != heads * 64 || left < 0 || right < 0 || left + right + 1 > kW2vbertRelStride)
-        return fail(LDS_EINVAL, "bad argument");
+        return set_error(LDS_EINVAL, "bad argument");
     hipStream_t st = (hipStream_t)stream;
     TmpDev tmp;
     float* qkp = tmp.f((size_t)B * 2 * C * T);       // plain [B][2C][T]
@@ -4902,12 +4766,12 @@ extern "C" int lds_test_w2vbert_attention(const float* qkv, const float* E, cons
     float* ko = tmp.f((size_t)B * C * (T + 2));
     float* relp = tmp.f((size_t)B * heads * T * kW2vbertRelStride);
     int* dl = (int*)tmp.f(128);
-    if (!qkp || !vpl || !vt || !kqk || !ko || !relp || !dl) return fail(LDS_ENOMEM, "alloc");
+    if (!qkp || !vpl || !vt || !kqk || !ko || !relp || !dl) return set_error(LDS_ENOMEM, "alloc");
     const int *ql = nullptr, *kl = nullptr;
     if (q_rows || k_rows) {
-        if (!q_rows || !k_rows) return fail(LDS_EINVAL, "q_rows and k_rows come together");
+        if (!q_rows || !k_rows) return set_error(LDS_EINVAL, "q_rows and k_rows come together");
         for (int b = 0; b < B; ++b)
-            if (q_rows[b] < 1 || q_rows[b] > T || k_rows[b] < 1 || k_rows[b] > q_rows[b]) return fail(LDS_EINVAL, "rows[%d] = (%d, %d) outside 1 .. %d", b, q_rows[b], k_rows[b], T);
+            if (q_rows[b] < 1 || q_rows[b] > T || k_rows[b] < 1 || k_rows[b] > q_rows[b]) return set_error(LDS_EINVAL, "rows[%d] = (%d, %d) outside 1 .. %d", b, q_rows[b], k_rows[b], T);
         LDS_TRY(upload_clip_ints(q_rows, B, dl, st));
         LDS_TRY(upload_clip_ints(k_rows, B, dl + 64, st));
         ql = dl; kl = dl + 64;
@@ -4926,14 +4790,14 @@ extern "C" int lds_test_w2vbert_attention(const float* qkv, const float* E, cons
 }
 extern "C" int lds_test_w2vbert_dwconv(const float* x, const float* w, const float* gamma, const float* beta, float eps, const int32_t* in_rows,
                                        const int32_t* out_rows, float* out, int B, int C, int T, int K, void* stream) {
-    if (!x || !w || !gamma || !beta || !out || B < 1 || B > 64 || T < 1 || C < 64 || C % 64 || C > 1024 || K < 1 || K > 31) return fail(LDS_EINVAL, "bad argument");
+    if (!x || !w || !gamma || !beta || !out || B < 1 || B > 64 || T < 1 || C < 64 || C % 64 || C > 1024 || K < 1 || K > 31) return set_error(LDS_EINVAL, "bad argument");
     hipStream_t st = (hipStream_t)stream;
     TmpDev tmp;
     float* kx = tmp.f((size_t)B * C * (T + 2));
     float* ko = tmp.f((size_t)B * C * (T + 2));
     float* wp = tmp.f((size_t)C * K);
     int* dl = (int*)tmp.f(128);
-    if (!kx || !ko || !wp || !dl) return fail(LDS_ENOMEM, "alloc");
+    if (!kx || !ko || !wp || !dl) return set_error(LDS_ENOMEM, "alloc");
     std::vector<float> hw((size_t)C * K), hp((size_t)C * K);
     HIP_TRY(hipMemcpy(hw.data(), w, hw.size() * sizeof(float), hipMemcpyDeviceToHost));
     for (int c = 0; c < C; ++c)
@@ -4941,9 +4805,9 @@ extern "C" int lds_test_w2vbert_dwconv(const float* x, const float* w, const flo
     HIP_TRY(hipMemcpy(wp, hp.data(), hp.size() * sizeof(float), hipMemcpyHostToDevice));
     const int *vl = nullptr, *nl = nullptr;
     if (in_rows || out_rows) {
-        if (!in_rows || !out_rows) return fail(LDS_EINVAL, "in_rows and out_rows come together");
+        if (!in_rows || !out_rows) return set_error(LDS_EINVAL, "in_rows and out_rows come together");
         for (int b = 0; b < B; ++b)
-            if (out_rows[b] < 1 || out_rows[b] > T || in_rows[b] < 1 || in_rows[b] > out_rows[b]) return fail(LDS_EINVAL, "rows[%d] = (%d, %d) outside 1 .. %d", b, in_rows[b], out_rows[b], T);
+            if (out_rows[b] < 1 || out_rows[b] > T || in_rows[b] < 1 || in_rows[b] > out_rows[b]) return set_error(LDS_EINVAL, "rows[%d] = (%d, %d) outside 1 .. %d", b, in_rows[b], out_rows[b], T);
         LDS_TRY(upload_clip_ints(in_rows, B, dl, st));
         LDS_TRY(upload_clip_ints(out_rows, B, dl + 64, st));
         vl = dl; nl = dl + 64;
@@ -4959,7 +4823,7 @@ extern "C" int lds_test_w2vbert_dwconv(const float* x, const float* w, const flo
 // pointer.  wavlm_buckets touches no device.
 extern "C" int lds_test_wavlm_attention(const float* qkv, const float* gate, const float* toep, const int32_t* lengths, float* out, int B, int C, int T,
                                         int heads, int n_ctx, void* stream) {
-    if (!qkv || !gate || !toep || !out || B < 1 || B > 64 || T < 1 || heads < 1 || C != heads * 64 || n_ctx < T || n_ctx > 1500) return fail(LDS_EINVAL, "bad argument");
+    if (!qkv || !gate || !toep || !out || B < 1 || B > 64 || T < 1 || heads < 1 || C != heads * 64 || n_ctx < T || n_ctx > 1500) return set_error(LDS_EINVAL, "bad argument");
     hipStream_t st = (hipStream_t)stream;
     TmpDev tmp;
     float* qkp = tmp.f((size_t)B * 2 * C * T);       // plain [B][2C][T]
@@ -4968,11 +4832,11 @@ extern "C" int lds_test_wavlm_attention(const float* qkv, const float* gate, con
     float* kqk = tmp.f((size_t)B * 2 * C * (T + 2));
     float* ko = tmp.f((size_t)B * C * (T + 2));
     int* dl = (int*)tmp.f(64);
-    if (!qkp || !vpl || !vt || !kqk || !ko || !dl) return fail(LDS_ENOMEM, "alloc");
+    if (!qkp || !vpl || !vt || !kqk || !ko || !dl) return set_error(LDS_ENOMEM, "alloc");
     const int* ln = nullptr;
     if (lengths) {
         for (int b = 0; b < B; ++b)
-            if (lengths[b] < 1 || lengths[b] > T) return fail(LDS_EINVAL, "lengths[%d] = %d outside 1 .. %d", b, lengths[b], T);
+            if (lengths[b] < 1 || lengths[b] > T) return set_error(LDS_EINVAL, "lengths[%d] = %d outside 1 .. %d", b, lengths[b], T);
         LDS_TRY(upload_clip_ints(lengths, B, dl, st));
         ln = dl;
     }
@@ -4991,7 +4855,7 @@ extern "C" int lds_test_wavlm_attention(const float* qkv, const float* gate, con
     return LDS_OK;
 }
 extern "C" int lds_test_wavlm_buckets(int num_buckets, int max_distance, int n, int32_t* out) {
-    if (!out || n < 1 || n > (1 << 20)) return fail(LDS_EINVAL, "bad argument");
+    if (!out || n < 1 || n > (1 << 20)) return set_error(LDS_EINVAL, "bad argument");
     LDS_TRY(wavlm_bucket_check(num_buckets, max_distance));
     for (int d = -(n - 1); d < n; ++d) out[d + n - 1] = wavlm_bucket(d, num_buckets, max_distance);
     return LDS_OK;

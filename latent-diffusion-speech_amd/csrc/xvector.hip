@@ -15,10 +15,10 @@
 #include "../../include/lds.h"
 #include "../../include/lds_test.h"
 #include "kernels.h"
+#include "host.h"
 
 #include <math.h>
 
-#include <map>
 #include <string>
 #include <vector>
 
@@ -243,23 +243,15 @@ __global__ void __launch_bounds__(64) xv_cosine_kernel(const float* __restrict__
 struct lds_xvector {
     lds_xvector_cfg cfg;
     int n_labels = 0;
-    std::vector<void*> own;
+    Owner own;
     float *proj_w = nullptr, *proj_b = nullptr, *fe_w = nullptr, *fe_b = nullptr, *cl_w = nullptr, *cl_b = nullptr;
     float *tdnn_w[8] = {}, *tdnn_b[8] = {};
-    ~lds_xvector() {
-        for (void* p : own) (void)hipFree(p);
-    }
 };
 
 namespace {
 
 using lds::set_error;
 constexpr int kXvMaxT = 32768;      // rows per clip: every byte offset of a clip's slab stays below 2^31 at the widest layer
-
-int xv_launched(const char* fn) {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? LDS_OK : set_error(LDS_EHIP, "%s: %s", fn, hipGetErrorString(e));
-}
 
 int xv_check_layer(const char* fn, int Cin, int Cout, int ks, int dil) {
     if (Cin < lds::kXvBK || Cin > 4096 || Cin % lds::kXvBK)
@@ -271,20 +263,13 @@ int xv_check_layer(const char* fn, int Cin, int Cout, int ks, int dil) {
 }
 
 int xv_check_bt(const char* fn, int B, int T) {
-    if (B < 1 || B > 64) return set_error(LDS_EINVAL, "%s: B %d outside 1 .. 64", fn, B);
-    if (T < 1 || T > kXvMaxT) return set_error(LDS_EINVAL, "%s: T %d outside 1 .. %d", fn, T, kXvMaxT);
-    return LDS_OK;
+    LDS_TRY(range_check(fn, "B", B, 1, 64));
+    return range_check(fn, "T", T, 1, kXvMaxT);
 }
 
 int xv_lens(const char* fn, int B, int T, const int32_t* n_frames, lds::XvLens& lens) {
-    if (!n_frames) return set_error(LDS_EINVAL, "%s: null n_frames", fn);
     lens.B = B; lens.T = T;
-    for (int i = 0; i < 64; ++i) lens.v[i] = 0;
-    for (int b = 0; b < B; ++b) {
-        if (n_frames[b] < 0 || n_frames[b] > T) return set_error(LDS_EINVAL, "%s: n_frames[%d] = %d outside 0 .. %d", fn, b, n_frames[b], T);
-        lens.v[b] = n_frames[b];
-    }
-    return LDS_OK;
+    return clip_lens_fill(fn, "n_frames", B, T, n_frames, lens.v);
 }
 
 // one layer over the clips' own frames: into Y, or (part != NULL) into the pooling partials
@@ -306,7 +291,6 @@ void xv_join(const float2* part, float* stats, int C, int span, const lds::XvLen
 }
 
 size_t xv_part_bytes(int B, int T, int C) { return (size_t)B * 2 * ((T + lds::kXvB - 1) / lds::kXvB) * C * sizeof(float2); }
-size_t xv_round(size_t n) { return (n + 255) & ~(size_t)255; }
 
 struct XvPlan { size_t o_a, o_b, o_part, o_stats, bytes; };
 
@@ -321,13 +305,12 @@ XvPlan xv_plan(const lds_xvector* h, int B, int T) {
     int wide = c.tdnn_dim[0];
     for (int i = 0; i + 1 < c.n_tdnn; ++i) wide = wide > c.tdnn_dim[i] ? wide : c.tdnn_dim[i];
     XvPlan p;
-    size_t o = 0;
-    auto take = [&](size_t n) { const size_t at = o; o += xv_round(n); return at; };
-    p.o_a = take((size_t)B * T * wide * 4);
-    p.o_b = take((size_t)B * T * wide * 4);
-    p.o_part = take(xv_part_bytes(B, T, c.tdnn_dim[c.n_tdnn - 1]));
-    p.o_stats = take((size_t)B * 2 * c.tdnn_dim[c.n_tdnn - 1] * 4);
-    p.bytes = o;
+    Slots S;
+    p.o_a = S.take((size_t)B * T * wide * 4);
+    p.o_b = S.take((size_t)B * T * wide * 4);
+    p.o_part = S.take(xv_part_bytes(B, T, c.tdnn_dim[c.n_tdnn - 1]));
+    p.o_stats = S.take((size_t)B * 2 * c.tdnn_dim[c.n_tdnn - 1] * 4);
+    p.bytes = S.o;
     return p;
 }
 
@@ -348,50 +331,32 @@ extern "C" int lds_xvector_create(const lds_xvector_cfg* cfg, int n, const char*
     const char* fn = "lds_xvector_create";
     if (!cfg || !names || !ptrs || !numel || !out || n < 0) return set_error(LDS_EINVAL, "%s: null argument", fn);
     if (int rc = xv_cfg_check(cfg)) return rc;
-    std::map<std::string, std::pair<const float*, int64_t>> m;
-    for (int i = 0; i < n; ++i)
-        if (names[i] && ptrs[i]) m[names[i]] = {ptrs[i], numel[i]};
     lds_xvector* h = new lds_xvector();
     h->cfg = *cfg;
-    std::string missing;
-    bool oom = false;
-    // numel < 0: any positive size (returned through *got)
-    auto get = [&](const std::string& k, int64_t want, int64_t* got) -> float* {
-        auto it = m.find(k);
-        if (it == m.end() || (want >= 0 ? it->second.second != want : it->second.second < 1)) {
-            if (missing.empty()) missing = k + (it == m.end() ? " (absent)" : " (wrong size)");
-            return nullptr;
-        }
-        if (got) *got = it->second.second;
-        void* d = nullptr;
-        const size_t bytes = (size_t)it->second.second * sizeof(float);
-        if (hipMalloc(&d, bytes) != hipSuccess) { oom = true; return nullptr; }
-        h->own.push_back(d);
-        if (hipMemcpy(d, it->second.first, bytes, hipMemcpyHostToDevice) != hipSuccess) { oom = true; return nullptr; }
-        return (float*)d;
-    };
+    WeightLoader W(h->own, n, names, ptrs, numel);
     const int C0 = cfg->tdnn_dim[0], CL = cfg->tdnn_dim[cfg->n_tdnn - 1], E = cfg->xvector_dim;
-    h->proj_w = get("projector.weight", (int64_t)C0 * cfg->d_in, nullptr);
-    h->proj_b = get("projector.bias", C0, nullptr);
+    h->proj_w = W.vec("projector.weight", (int64_t)C0 * cfg->d_in);
+    h->proj_b = W.vec("projector.bias", C0);
+    bool ok = h->proj_w && h->proj_b;
     for (int i = 0; i < cfg->n_tdnn; ++i) {
         const int Cin = i ? cfg->tdnn_dim[i - 1] : C0;
         const std::string p = "tdnn." + std::to_string(i) + ".kernel.";
-        h->tdnn_w[i] = get(p + "weight", (int64_t)cfg->tdnn_dim[i] * cfg->tdnn_kernel[i] * Cin, nullptr);
-        h->tdnn_b[i] = get(p + "bias", cfg->tdnn_dim[i], nullptr);
+        h->tdnn_w[i] = W.vec(p + "weight", (int64_t)cfg->tdnn_dim[i] * cfg->tdnn_kernel[i] * Cin);
+        h->tdnn_b[i] = W.vec(p + "bias", cfg->tdnn_dim[i]);
+        ok = ok && h->tdnn_w[i] && h->tdnn_b[i];
     }
-    h->fe_w = get("feature_extractor.weight", (int64_t)E * 2 * CL, nullptr);
-    h->fe_b = get("feature_extractor.bias", E, nullptr);
-    int64_t nl = 0;
-    h->cl_b = get("classifier.bias", -1, &nl);
-    h->cl_w = get("classifier.weight", nl * E, nullptr);
+    h->fe_w = W.vec("feature_extractor.weight", (int64_t)E * 2 * CL);
+    h->fe_b = W.vec("feature_extractor.bias", E);
+    int64_t nl = 0;      // the classifier's width is the checkpoint's
+    h->cl_b = W.vec("classifier.bias", -1, &nl);
+    h->cl_w = W.vec("classifier.weight", nl * E);
     h->n_labels = (int)nl;
-    if (oom || !missing.empty()) {
+    ok = ok && h->fe_w && h->fe_b && h->cl_b && h->cl_w;
+    if (!ok && W.T.missing.empty()) {
         delete h;
-        if (oom) return set_error(LDS_ENOMEM, "%s: device allocation or upload failed", fn);
-        return set_error(LDS_EMISSING, "xvector weight tensor %s", missing.c_str());
+        return set_error(LDS_ENOMEM, "%s: device allocation or upload failed", fn);
     }
-    *out = h;
-    return LDS_OK;
+    return W.finish(ok, fn, h, out, "xvector weight tensor");
 }
 
 extern "C" void lds_xvector_destroy(lds_xvector* h) { delete h; }
@@ -444,7 +409,7 @@ extern "C" int lds_xvector_embed(lds_xvector* h, const float* X, const int32_t* 
     if (logits && lds::launch_small_linear(h->cl_w, h->cl_b, emb, c.xvector_dim, lds::IN_PLAIN, nullptr, logits, h->n_labels, 0, h->n_labels, c.xvector_dim, B, s) !=
                       hipSuccess)
         return set_error(LDS_EHIP, "%s: the classifier launch failed", fn);
-    return xv_launched(fn);
+    return launched(fn);
 }
 
 extern "C" int lds_xvector_cosine(const float* a, int N, const float* b, int M, int dim, float* out, void* stream) {
@@ -453,7 +418,7 @@ extern "C" int lds_xvector_cosine(const float* a, int N, const float* b, int M, 
     if (dim < 1 || dim > 65536) return set_error(LDS_EINVAL, "%s: dim %d outside 1 .. 65536", fn, dim);
     if (!a || !b || !out) return set_error(LDS_EINVAL, "%s: null pointer", fn);
     hipLaunchKernelGGL(lds::xv_cosine_kernel, dim3(M, N), dim3(64), 0, (hipStream_t)stream, a, b, dim, M, out);
-    return xv_launched(fn);
+    return launched(fn);
 }
 
 extern "C" int lds_test_xvector_tdnn(const float* X, int B, int T, const int32_t* n_frames, const float* W, const float* bias, int Cin, int Cout, int ks, int dil,
@@ -465,7 +430,7 @@ extern "C" int lds_test_xvector_tdnn(const float* X, int B, int T, const int32_t
     if (int rc = xv_lens(fn, B, T, n_frames, lens)) return rc;
     if (!X || !W || !bias || !Y) return set_error(LDS_EINVAL, "%s: null pointer", fn);
     xv_layer(X, W, bias, Cin, Cout, ks, dil, relu ? 1 : 0, Y, nullptr, lens, (hipStream_t)stream);
-    return xv_launched(fn);
+    return launched(fn);
 }
 
 extern "C" int lds_test_xvector_pool_workspace_bytes(int B, int T, int Cout, size_t* out) {
@@ -473,7 +438,7 @@ extern "C" int lds_test_xvector_pool_workspace_bytes(int B, int T, int Cout, siz
     if (!out) return set_error(LDS_EINVAL, "%s: null out", fn);
     if (int rc = xv_check_bt(fn, B, T)) return rc;
     if (Cout < 4 || Cout > 4096 || Cout % 4) return set_error(LDS_EINVAL, "%s: Cout %d must be a multiple of 4 in 4 .. 4096", fn, Cout);
-    *out = xv_round(xv_part_bytes(B, T, Cout));
+    *out = Slots::round(xv_part_bytes(B, T, Cout));
     return LDS_OK;
 }
 
@@ -489,11 +454,11 @@ extern "C" int lds_test_xvector_pool(const float* X, int B, int T, const int32_t
             return set_error(LDS_EINVAL, "%s: n_frames[%d] = %d gives %d pooled frames; the unbiased standard deviation needs 2", fn, b, lens.v[b],
                              lens.v[b] - (ks - 1) * dil > 0 ? lens.v[b] - (ks - 1) * dil : 0);
     if (!X || !W || !bias || !stats || !ws) return set_error(LDS_EINVAL, "%s: null pointer", fn);
-    const size_t need = xv_round(xv_part_bytes(B, T, Cout));
+    const size_t need = Slots::round(xv_part_bytes(B, T, Cout));
     if (ws_bytes < need) return set_error(LDS_ENOMEM, "%s: workspace %zu < %zu bytes", fn, ws_bytes, need);
     hipStream_t s = (hipStream_t)stream;
     xv_layer(X, W, bias, Cin, Cout, ks, dil, 1, nullptr, (float2*)ws, lens, s);
     xv_join((const float2*)ws, stats, Cout, (ks - 1) * dil, lens, s);
     if (Y) xv_layer(X, W, bias, Cin, Cout, ks, dil, 1, Y, nullptr, lens, s);
-    return xv_launched(fn);
+    return launched(fn);
 }
