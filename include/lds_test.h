@@ -320,6 +320,28 @@ int lds_test_wino_conv_lvl(const float* x1, const float* x2, int C1, int C2, int
  * exact-fp32 mode, 0 = never.  Host only; returns the value, not a status. */
 int lds_test_wino_min_T(int Ci, int Co);
 
+/* ---- conv2 + the 1x1 shortcut of a resnet as one conv_wino launch over Cm + Cin / 2 channels (csrc/model.hip run_wconv_pair) ----------------
+ * lds_test_wino_pair_pack (host only): g [Co][Cm][3], S [Co][Cin] -> U [4][Co][Cm + Cin/2]: lds_test_wino_pack's taps of g, then per tap the
+ * Cin / 2 extension columns S_A, S_B / 2, S_B / 2, -S_A (S_A / S_B: the first / second half of S's columns), computed in double, rounded once.
+ * lds_test_wino_pair: out = conv_k3(SiLU(GroupNorm2(h) (* (1 + scale) + shift)); w2) + conv_1x1([x1 ; x2]; ws) + b2 + bs as run_resnet runs a
+ * routed pair: conv1's GroupNorm pass over [x1 ; x2] (gamma1 / beta1, SiLU) with the side output, conv2's pass over h (gn_wpair), the launch.
+ * h dev [B,Cm,T]; x1 / x2 dev [B,C1,T] / [B,C2,T] (x2 may be NULL); gamma / beta host; scale_shift dev [B, 2 Cm] or NULL; w2 [Cm,Cm,3], ws
+ * [Cm,C1+C2], b2 / bs [Cm] host.  lengths (LEVEL-0, host, or NULL), lvl, poison, cfg as lds_test_wino_conv_lvl.  out dev [B,Cm,T]; vplanes (or
+ * NULL) dev [B][Cin/8][2][4][P][4]: conv1's planes, bit for bit lds_test_wino_conv's; pplanes (or NULL) dev [B][(Cm + Cin/2)/8][2][4][P][4]: the
+ * launch's planes (conv2's blocks, then the shortcut's); gnpart (or NULL) as lds_test_wino_conv.  Every buffer starts as NaN.
+ * lds_bench_wino_pair: the direct tail (conv1's pass, gn_stream, conv_dma_pair) against the new one (conv1's pass with the side output,
+ * gn_wpair, conv_wino_pair), alternating as lds_bench_wino.
+ * lds_test_wino_pair_min_T: the routing table (csrc/model.hip wino_pair_min_T), 0 = never; a pair is routed only where conv1 is as well. */
+int lds_test_wino_pair_pack(const float* g, const float* S, int Co, int Cm, int Cin, float* U);
+int lds_test_wino_pair(const float* h, const float* x1, const float* x2, int Cm, int C1, int C2, int T, const float* gamma1, const float* beta1,
+                       const float* gamma2, const float* beta2, const float* scale_shift, int groups, const float* w2, const float* b2, const float* ws,
+                       const float* bs, const int32_t* lengths, int poison, int cfg, int lvl, float* out, float* vplanes, float* pplanes, float* gnpart, int B,
+                       void* stream);
+int lds_bench_wino_pair(const float* h, const float* x1, const float* x2, int Cm, int C1, int C2, int T, const float* gamma1, const float* beta1,
+                        const float* gamma2, const float* beta2, const float* scale_shift, int groups, const float* w2, const float* b2, const float* ws,
+                        const float* bs, int cfg, int B, int iters, int reps, float* ms_direct, float* ms_wino, char* cfg_out, size_t cfg_cap, void* stream);
+int lds_test_wino_pair_min_T(int Cin, int Cm);
+
 /* ---- x-vector head, one layer at a time (csrc/xvector.hip; limits as lds_xvector_*) -----------------------------------------------------------
  * lds_test_xvector_tdnn: X dev [B][T][Cin], n_frames host [B] (0 .. T), W dev [Cout][ks Cin], bias dev [Cout] -> Y dev [B][T][Cout]: rows below
  * T_out = n_frames[b] - (ks - 1) d hold the layer (relu 0 / 1), the rows from there to T zeros.  ks 1 without relu is the projector.

@@ -6,6 +6,8 @@
 //   V0 = d[2i] - d[2i+2], V1 = d[2i+1] + d[2i+2], V2 = d[2i+2] - d[2i+1], V3 = d[2i+1] - d[2i+3]    (k4p_ops.hip gn_wino_kernel)
 //   Mj = Uj . Vj   (a Ci-deep GEMM over T / 2 columns each);   Y[2i] = M0 + M1 + M2,   Y[2i+1] = M1 - M2 - M3
 // Four column-products per output pair instead of six: two thirds of the MFMAs of the direct form.
+// A resnet's conv2 + 1x1 shortcut runs through the same kernel as one reduction over Cm + Cin / 2 channels: the shortcut's taps and planes are
+// appended along K so that they enter through the join above (model.hip wino_pair_taps / run_wconv_pair); nothing here knows.
 //
 // The kernel is built from conv_dma's parts.  A workgroup owns 32 output rows x 32 pairs (64 frames); wave j accumulates Mj, a 32 x 32
 // tile in two chains, over the whole Ci.  Both operand tiles of a K-step -- the four taps' weight rows and the four planes' pair columns --

@@ -377,15 +377,18 @@ hipError_t launch_gn_stream(const float* x1, const float* x2, int C1, int C2, in
 // no exchange across waves), forms d at the four frames -- zero outside [0, Tv) by selects on the computed values, so whatever the pad frames or the frames beyond an
 // utterance's length hold never reaches a plane -- and stores one 16-byte entry into each plane:
 //   V0 = d[2i] - d[2i+2], V1 = d[2i+1] + d[2i+2], V2 = d[2i+2] - d[2i+1], V3 = d[2i+1] - d[2i+3]      y: [B][C/8][2][4][P][4], P = ceil(T / 2)
-template <int E>
-__global__ void __launch_bounds__(256) gn_wino_kernel(const float* __restrict__ x1, const float* __restrict__ x2, int C1, int C2, int T,
-                                                      int cg16, unsigned gm, unsigned gsh, float inv_nT, float eps,
-                                                      const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                      const float* __restrict__ ss, int ss_stride, int ss_off, int silu,
-                                                      const float2* __restrict__ gp1, const float2* __restrict__ gp2, float* __restrict__ y,
-                                                      const int* __restrict__ lens, int lvl) {
-    asm volatile("" : "+s"(x1), "+s"(x2), "+s"(C1), "+s"(C2), "+s"(T), "+s"(cg16), "+s"(gm), "+s"(gsh), "+s"(inv_nT), "+s"(eps), "+s"(gamma), "+s"(beta),
-                      "+s"(ss), "+s"(ss_stride), "+s"(ss_off), "+s"(silu), "+s"(gp1), "+s"(gp2), "+s"(y), "+s"(lens), "+s"(lvl));
+//
+// PAIR (the conv2 + shortcut launch of a resnet, model.hip run_wconv_pair): the output's batch stride is the caller's -- the planes are the
+// first C / 8 blocks of a longer plane tensor -- and, where `side` is given, the pass also writes the shortcut's operand planes from the RAW
+// entries it already holds at frames 2i and 2i+1 (x_e, x_o; zero from the utterance's length on, by select): block q of the first half of the
+// C / 8 blocks writes planes 0 and 3 of side block q (x_e, x_o), block q of the second half planes 1 and 2 of side block q - C / 16
+// (x_e + x_o, x_e - x_o: one fp32 operation each).  Without PAIR the body is gn_wino_kernel's as it was.
+template <int E, bool PAIR>
+static __device__ __forceinline__ void gn_wino_body(const float* __restrict__ x1, const float* __restrict__ x2, int C1, int C2, int T, int cg16, unsigned gm,
+                                                    unsigned gsh, float inv_nT, float eps, const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                    const float* __restrict__ ss, int ss_stride, int ss_off, int silu, const float2* __restrict__ gp1,
+                                                    const float2* __restrict__ gp2, float* __restrict__ y, const int* __restrict__ lens, int lvl,
+                                                    long long y_bstride, float* __restrict__ side, long long side_bstride) {
     const int q = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, lane = tid & 63;
     const int C = C1 + C2, Tp = T + 2, nq1 = C1 >> 3, nq = C >> 3, Pn = (T + 1) >> 1;
     const float* sp = ss ? ss + (long long)b * ss_stride + ss_off + q * 8 : gamma + q * 8;
@@ -398,9 +401,15 @@ __global__ void __launch_bounds__(256) gn_wino_kernel(const float* __restrict__ 
         Tv = n < T ? n : T;
     }
     const float* xb = (q < nq1) ? x1 + (((long long)b * nq1 + q) * 2) * Tp * 4 : x2 + (((long long)b * (C2 >> 3) + (q - nq1)) * 2) * Tp * 4;
-    float* yb = y + (((long long)b * nq + q) * 2) * 4 * Pn * 4;
+    float* yb = PAIR ? y + (long long)b * y_bstride + (long long)q * 2 * 4 * Pn * 4 : y + (((long long)b * nq + q) * 2) * 4 * Pn * 4;
     const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(xb), 0, 2 * Tp * 16, 0x00020000);
     const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(yb, 0, 2 * 4 * Pn * 16, 0x00020000);
+    // the side block of this block (a launch without side output gets a buffer of zero bytes: its stores are dropped, and none is issued)
+    const bool side_a = q < (nq >> 1);
+    __amdgpu_buffer_rsrc_t rs = ry;
+    if constexpr (PAIR)
+        rs = __builtin_amdgcn_make_buffer_rsrc(side ? side + (long long)b * side_bstride + (long long)(side_a ? q : q - (nq >> 1)) * 2 * 4 * Pn * 4 : side, 0,
+                                               side ? 2 * 4 * Pn * 16 : 0, 0x00020000);
     const int total = 2 * Pn;                         // work items of this block: (row hh, pair i) -> idx = hh * Pn + i
     const int g = (int)dma_magic_div((unsigned)q, gm, gsh);
     const int nT = (T + 31) >> 5, P = cg16 * nT, nk1 = C1 >> 4;
@@ -498,10 +507,46 @@ __global__ void __launch_bounds__(256) gn_wino_kernel(const float* __restrict__ 
 #pragma unroll
                 for (int j = 0; j < 4; ++j)
                     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, pl[j]), ry, ((hh * 4 + j) * Pn + pi) * 16, 0, 16);
+                if constexpr (PAIR) {
+                    if (side) {
+                        f32x4 xe, xo;
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) {
+                            xe[j] = (2 * pi < Tv) ? v[i][1][j] : 0.f;
+                            xo[j] = (2 * pi + 1 < Tv) ? v[i][2][j] : 0.f;
+                        }
+                        const f32x4 sa = side_a ? xe : xe + xo, sb = side_a ? xo : xe - xo;
+                        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, sa), rs, ((hh * 4 + (side_a ? 0 : 1)) * Pn + pi) * 16, 0, 16);
+                        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, sb), rs, ((hh * 4 + (side_a ? 3 : 2)) * Pn + pi) * 16, 0, 16);
+                    }
+                }
             }
         }
     }
 }
+
+#define GN_WINO_PARAMS                                                                                                                               \
+    const float *__restrict__ x1, const float *__restrict__ x2, int C1, int C2, int T, int cg16, unsigned gm, unsigned gsh, float inv_nT, float eps, \
+        const float *__restrict__ gamma, const float *__restrict__ beta, const float *__restrict__ ss, int ss_stride, int ss_off, int silu,         \
+        const float2 *__restrict__ gp1, const float2 *__restrict__ gp2, float *__restrict__ y, const int *__restrict__ lens, int lvl
+#define GN_WINO_PIN                                                                                                                                        \
+    asm volatile("" : "+s"(x1), "+s"(x2), "+s"(C1), "+s"(C2), "+s"(T), "+s"(cg16), "+s"(gm), "+s"(gsh), "+s"(inv_nT), "+s"(eps), "+s"(gamma), "+s"(beta), \
+                      "+s"(ss), "+s"(ss_stride), "+s"(ss_off), "+s"(silu), "+s"(gp1), "+s"(gp2), "+s"(y), "+s"(lens), "+s"(lvl))
+#define GN_WINO_PASS x1, x2, C1, C2, T, cg16, gm, gsh, inv_nT, eps, gamma, beta, ss, ss_stride, ss_off, silu, gp1, gp2, y, lens, lvl
+template <int E>
+__global__ void __launch_bounds__(256) gn_wino_kernel(GN_WINO_PARAMS) {
+    GN_WINO_PIN;
+    gn_wino_body<E, false>(GN_WINO_PASS, 0, nullptr, 0);
+}
+template <int E>
+__global__ void __launch_bounds__(256) gn_wino_pair_kernel(GN_WINO_PARAMS, long long y_bstride, float* __restrict__ side, long long side_bstride) {
+    GN_WINO_PIN;
+    asm volatile("" : "+s"(y_bstride), "+s"(side), "+s"(side_bstride));
+    gn_wino_body<E, true>(GN_WINO_PASS, y_bstride, side, side_bstride);
+}
+#undef GN_WINO_PARAMS
+#undef GN_WINO_PIN
+#undef GN_WINO_PASS
 
 hipError_t launch_gn_wino(const float* x1, const float* x2, int C1, int C2, int T, int groups, float eps, const float* gamma, const float* beta,
                           const float* ss, int ss_stride, int ss_off, int silu, const float2* gp1, const float2* gp2, float* y, int B, hipStream_t s,
@@ -524,6 +569,35 @@ hipError_t launch_gn_wino(const float* x1, const float* x2, int C1, int C2, int 
     } else if (need <= 1) hipLaunchKernelGGL(gn_wino_kernel<1>, grid, blk, 0, s, GN_ARGS);
     else if (need <= 2) hipLaunchKernelGGL(gn_wino_kernel<2>, grid, blk, 0, s, GN_ARGS);
     else hipLaunchKernelGGL(gn_wino_kernel<4>, grid, blk, 0, s, GN_ARGS);
+#undef GN_ARGS
+    return hipGetLastError();
+}
+
+hipError_t launch_gn_wino_pair(const float* x1, const float* x2, int C1, int C2, int T, int groups, float eps, const float* gamma, const float* beta,
+                               const float* ss, int ss_stride, int ss_off, int silu, const float2* gp1, const float2* gp2, float* y, long long y_bstride,
+                               float* side, long long side_bstride, int B, hipStream_t s, const int* lens, int lvl) {
+    const int C = C1 + C2;
+    if ((C1 & 15) || (C2 & 15) || groups <= 0 || C % groups || (C / groups) % 16 || !gp1 || (C2 && !gp2) || !y) return hipErrorInvalidValue;
+    const int Pn = (T + 1) / 2;
+    if (y_bstride < (long long)C * 4 * Pn || (side && side_bstride < (long long)(C / 2) * 4 * Pn)) return hipErrorInvalidValue;
+    // conv1's pass keeps its name (one gn_wino per conv_wino) and counts the two side stores per item; conv2's pass is gn_wpair
+    ProfScope ps(s, side ? "gn_wino" : "gn_wpair", 0.0, 4.0 * B * (double)C * (T + 4.0 * Pn + (side ? 2.0 * Pn : 0.0)), true);
+    const dim3 grid(C / 8, B), blk(256);
+    const int need = (2 * Pn + 255) / 256;
+    const int cg16 = (C / groups) >> 4;
+    const DmaMagic gmg = dma_magic((unsigned)(2 * cg16));
+    const float inv_nT = 1.0f / (float)((T + 31) >> 5);
+#define GN_ARGS                                                                                                                                  \
+    x1, x2 ? x2 : x1, C1, C2, T, cg16, gmg.m, gmg.s, inv_nT, eps, gamma, beta, ss, ss_stride, ss_off, silu, gp1, gp2 ? gp2 : gp1, y, lens, lvl, \
+        y_bstride, side, side_bstride
+    hipEvent_t e0, e1;
+    if (prof_attach_events(&e0, &e1)) {
+        if (need <= 1) hipExtLaunchKernelGGL(gn_wino_pair_kernel<1>, grid, blk, 0, s, e0, e1, 0, GN_ARGS);
+        else if (need <= 2) hipExtLaunchKernelGGL(gn_wino_pair_kernel<2>, grid, blk, 0, s, e0, e1, 0, GN_ARGS);
+        else hipExtLaunchKernelGGL(gn_wino_pair_kernel<4>, grid, blk, 0, s, e0, e1, 0, GN_ARGS);
+    } else if (need <= 1) hipLaunchKernelGGL(gn_wino_pair_kernel<1>, grid, blk, 0, s, GN_ARGS);
+    else if (need <= 2) hipLaunchKernelGGL(gn_wino_pair_kernel<2>, grid, blk, 0, s, GN_ARGS);
+    else hipLaunchKernelGGL(gn_wino_pair_kernel<4>, grid, blk, 0, s, GN_ARGS);
 #undef GN_ARGS
     return hipGetLastError();
 }

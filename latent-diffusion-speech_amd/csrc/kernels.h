@@ -220,6 +220,16 @@ const char* conv_wino_last_config();
 hipError_t launch_gn_wino(const float* x1, const float* x2, int C1, int C2, int T, int groups, float eps, const float* gamma, const float* beta,
                           const float* scale_shift, int ss_stride, int ss_off, int silu, const float2* gp1, const float2* gp2, float* y, int B,
                           hipStream_t s, const int* lens = nullptr, int lvl = 0);
+// The two passes in front of a resnet's conv2 + shortcut launch in the Winograd form (model.hip run_wconv_pair).  That launch reduces over
+// Cm + Cin / 2 channels: conv2's planes in the first Cm / 8 blocks of a plane tensor [B][(Cm + Cin/2)/8][2][4][P][4], the shortcut's operand
+// planes in the last Cin / 16 blocks -- for the first half A of the raw block input's 8-channel blocks plane 0 = x_e, plane 3 = x_o (x_e[i] =
+// x[2i], x_o[i] = x[2i+1], zero from the utterance's length on), for the second half B plane 1 = x_e + x_o, plane 2 = x_e - x_o.
+//   side == null (profiler name gn_wpair): launch_gn_wino's pass with the batch stride `y_bstride` (floats) on the output: conv2's planes.
+//   side != null (gn_wino): launch_gn_wino's pass, y as there with y_bstride = (C1 + C2) * 4 * P, and the shortcut's planes beside it: block q
+//   of [x1 ; x2] writes two planes of side block q mod (C / 16), `side` = the first side block of batch element 0, side_bstride in floats.
+hipError_t launch_gn_wino_pair(const float* x1, const float* x2, int C1, int C2, int T, int groups, float eps, const float* gamma, const float* beta,
+                               const float* scale_shift, int ss_stride, int ss_off, int silu, const float2* gp1, const float2* gp2, float* y,
+                               long long y_bstride, float* side, long long side_bstride, int B, hipStream_t s, const int* lens = nullptr, int lvl = 0);
 
 // ---------------------------------------------------------------------------------------------
 // conv_bf3: the same operator on the bf16 matrix pipe with fp32-equivalent split operands (conv_bf3.hip, k8b3.h).  Same argument

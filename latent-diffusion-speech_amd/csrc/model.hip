@@ -267,6 +267,38 @@ static bool pack_wino(Owner& o, const float* w, int Co, int Ci, ConvW& out) {
     out.wu = o.upload(p);
     return out.wu != nullptr;
 }
+// conv2 + the 1x1 shortcut of a resnet as ONE Winograd reduction over Cm + Cin / 2 channels.  conv_wino joins Y[2i] = M0 + M1 + M2
+// and Y[2i+1] = M1 - M2 - M3, so an addend on M0 reaches the even frame, one on M3 (negated) the odd frame, and a pair (A on M1, B on M2)
+// puts A + B into the even and A - B into the odd frame.  With x_e[i] = x[2i], x_o[i] = x[2i+1] of the raw block input and its channels
+// split into a first half A and a second half B, the shortcut S rides as
+//   tap 0: S_A . x_e(A)     tap 1: S_B / 2 . (x_e(B) + x_o(B))     tap 2: S_B / 2 . (x_e(B) - x_o(B))     tap 3: -S_A . x_o(A)
+// two products per output pair like the direct form, but Cin / 2 deep on every one of the four waves.
+// g [Co][Cm][3], S [Co][Cin] -> U [4][Co][Cm + Cin/2]: wino_taps(g), then the extension; S_B halved in double and rounded once (exact)
+static void wino_pair_taps(const float* g, const float* S, int Co, int Cm, int Cin, std::vector<float>& U) {
+    std::vector<float> U3;
+    wino_taps(g, Co, Cm, U3);
+    const int half = Cin / 2, Ck = Cm + half;
+    U.assign((size_t)4 * Co * Ck, 0.f);
+    for (int j = 0; j < 4; ++j)
+        for (int co = 0; co < Co; ++co) {
+            float* row = &U[((size_t)j * Co + co) * Ck];
+            memcpy(row, &U3[((size_t)j * Co + co) * Cm], sizeof(float) * Cm);
+            for (int e = 0; e < half; ++e) {
+                const double sa = S[(size_t)co * Cin + e], sb = S[(size_t)co * Cin + half + e];
+                row[Cm + e] = (float)(j == 0 ? sa : j == 3 ? -sa : sb * 0.5);
+            }
+        }
+}
+static float* pack_wino_pair(Owner& o, const float* w2, const float* ws, int Co, int Cm, int Cin, int Mp) {
+    std::vector<float> U;
+    wino_pair_taps(w2, ws, Co, Cm, Cin, U);
+    const int Ck = Cm + Cin / 2;
+    std::vector<float> p((size_t)4 * Ck * Mp, 0.f);
+    for (int j = 0; j < 4; ++j)
+        for (int co = 0; co < Co; ++co)
+            for (int ci = 0; ci < Ck; ++ci) p[widx(j, ci, co, Ck, Mp)] = U[((size_t)j * Co + co) * Ck + ci];
+    return o.upload(p);
+}
 
 // GEGLU projection (reference attention.py:280-301): rows [0,4C) are the value half, [4C,8C) the gate.
 // Interleave them in 32-row groups so one wave's two MFMA row tiles hold value and gate of the same channels.
@@ -698,6 +730,26 @@ static bool wino_routed(int Ci, int Co, int T) {
 static bool wino_routed_any_T(int Ci, int Co) { return wino_min_T(Ci, Co) > 0; }      // (load time: T is not known yet)
 // A resnet's k 3 convolution over the planes `v` that launch_gn_wino wrote (W.wu: its packed taps).  The profiler's record carries the
 // algorithmic FLOP of the convolution it replaces, 2 B T Co Ci 3 -- the figure every other family reports -- not the two thirds it executes.
+// (`family`: the record's name; `Ci_name`: the input channels of the operator it stands for; a.Ci is the depth the kernel reduces over)
+static int run_wconv_args(WinoConvArgs& a, const char* family, int Ci_name, double flops, double bytes, hipStream_t st, int cfg) {
+    hipError_t e;
+    {
+        ProfScope ps(st, family, flops, bytes, true);
+        e = launch_conv_wino(a, cfg, st);
+        if (ps.on) {
+            std::string cfgs(conv_wino_last_config());
+            std::string nm = std::string(family) + "<" + cfgs.substr(0, cfgs.find(" grid")) + ">";
+            if (g_prof_level.load(std::memory_order_relaxed) >= 2) {
+                char sh[96];
+                snprintf(sh, sizeof(sh), " Ci%d Co%d K3 To%d%s", Ci_name, a.Co, a.T, a.res ? " +res" : "");
+                nm += sh;
+            }
+            ps.rename(nm);
+        }
+    }
+    if (e != hipSuccess) return set_error(LDS_EHIP, "%s launch failed (%s): Co %d Ci %d T %d cfg %d", family, hipGetErrorString(e), a.Co, a.Ci, a.T, cfg);
+    return LDS_OK;
+}
 static int run_wconv(const ConvW& W, const float* v, int T, const float* res, float2* gnpart_out, float* out, int B, hipStream_t st, int lvl, int cfg = 0) {
     if (!W.wu || W.K != 3) return set_error(LDS_EINVAL, "wconv: the Winograd taps were not packed for this layer");
     WinoConvArgs a{};
@@ -706,23 +758,38 @@ static int run_wconv(const ConvW& W, const float* v, int T, const float* res, fl
     a.B = B; a.Ci = W.Ci; a.Mp = W.Mp; a.Co = W.Co; a.T = T;
     const double flops = 2.0 * B * (double)T * (double)W.Co * (double)W.Ci * 3.0;
     const double bytes = 4.0 * ((double)B * W.Ci * 4.0 * ((T + 1) / 2) + 4.0 * W.Ci * W.Co + (double)B * W.Co * T * (res ? 2.0 : 1.0));
-    hipError_t e;
-    {
-        ProfScope ps(st, "conv_wino", flops, bytes, true);
-        e = launch_conv_wino(a, cfg, st);
-        if (ps.on) {
-            std::string cfgs(conv_wino_last_config());
-            std::string nm = "conv_wino<" + cfgs.substr(0, cfgs.find(" grid")) + ">";
-            if (g_prof_level.load(std::memory_order_relaxed) >= 2) {
-                char sh[96];
-                snprintf(sh, sizeof(sh), " Ci%d Co%d K3 To%d%s", W.Ci, W.Co, T, res ? " +res" : "");
-                nm += sh;
-            }
-            ps.rename(nm);
-        }
-    }
-    if (e != hipSuccess) return set_error(LDS_EHIP, "conv_wino launch failed (%s): Co %d Ci %d T %d cfg %d", hipGetErrorString(e), W.Co, W.Ci, T, cfg);
-    return LDS_OK;
+    return run_wconv_args(a, "conv_wino", W.Ci, flops, bytes, st, cfg);
+}
+// Which conv2 + shortcut pairs run as one conv_wino launch over Cm + Cin / 2 channels (pack_wino_pair) in exact-fp32 mode: (Cin, Cm) of the
+// UNet's resnets with a shortcut and the shortest T at which tools/bench_wino.py --pair measured the new form (conv1's pass with the side
+// output + gn_wpair + conv_wino_pair) faster than the direct one (conv1's pass + gn_stream + conv_dma_pair) at the nominal batch of 16 by
+// more than the larger of the two spreads (profiles/r30_wino_pair_shapes.json).  Like wino_min_T it never sees the batch or
+// the lengths; a pair is routed only where conv1 is (its pass writes the shortcut's planes).
+static int wino_pair_min_T(int Cin, int Cm) {
+    static const int kTable[][3] = {
+        {256, 384, 256}, {384, 512, 128}, {1024, 512, 64}, {896, 512, 128}, {896, 384, 256}, {768, 384, 256}, {640, 384, 256}, {512, 256, 512},
+    };      // (640 -> 256 at 512 frames measured 0.69 us faster with a spread of 0.85 us: it stays direct)
+    for (const auto& s : kTable)
+        if (s[0] == Cin && s[1] == Cm) return s[2];
+    return 0;
+}
+static bool wino_pair_routed(int Cin, int Cm, int T) {
+    const int Tmin = wino_pair_min_T(Cin, Cm);
+    return Tmin > 0 && T >= Tmin && wino_routed(Cin, Cm, T);
+}
+static size_t wino_pair_plane_floats(int Cin, int Cm, int T) { return (size_t)(Cm + Cin / 2) * 4 * (size_t)((T + 1) / 2); }      // per utterance
+// conv2 + shortcut over the pair planes `v` ([B][(Cm + Cin/2)/8][2][4][P][4]: launch_gn_wino_pair's two passes) with the taps of pack_wino_pair.
+// The record carries the algorithmic FLOP of the pair it replaces, 2 B T Co (3 Cm + Cin), and Ci = Cin in its name.
+static int run_wconv_pair(const float* wu_pair, int Cin, int Cm, int Mp, const float* v, int T, const float* bias_pair, float2* gnpart_out, float* out, int B,
+                          hipStream_t st, int lvl, int cfg = 0) {
+    if (!wu_pair) return set_error(LDS_EINVAL, "wconv pair: the pair's Winograd taps were not packed for this resnet");
+    WinoConvArgs a{};
+    a.v = v; a.u = wu_pair; a.bias = bias_pair; a.res = nullptr; a.out = out; a.gnpart_out = gnpart_out;
+    a.lens = tl_lens; a.lvl = lvl;
+    a.B = B; a.Ci = Cm + Cin / 2; a.Mp = Mp; a.Co = Cm; a.T = T;
+    const double flops = 2.0 * B * (double)T * (double)Cm * (3.0 * Cm + (double)Cin);
+    const double bytes = 4.0 * ((double)B * a.Ci * 4.0 * ((T + 1) / 2) + 4.0 * a.Ci * Cm + (double)B * Cm * T);
+    return run_wconv_args(a, "conv_wino_pair", Cin, flops, bytes, st, cfg);
 }
 
 // The UNet's plan is the same in both GEMM modes; these pick the kernel family.  In LDS_GEMM_SPLIT_BF16 mode every activation buffer
@@ -748,6 +815,7 @@ struct ResnetW {
     float *g1 = nullptr, *b1 = nullptr, *g2 = nullptr, *b2 = nullptr;
     ConvW conv1, conv2, sc;
     float* bias_pair = nullptr;      // conv2.bias + conv_shortcut.bias per packed row (the fused conv2 + shortcut launch)
+    float* wu_pair = nullptr;        // conv2 + shortcut as one Winograd reduction, [4][cout + cin/2][Mp] packed (pack_wino_pair), where the pair is routed
     bool has_sc = false;
     int temb_off = 0;
 };
@@ -823,6 +891,10 @@ static bool load_resnet(lds_unet* u, Tensors& T, const std::string& p, int cin, 
         for (int co = 0; co < cout; ++co) bp[co] = c2b[co] + bs[co];
         r.bias_pair = o.upload(bp);
         if (!r.bias_pair) return false;
+        if (wino_pair_min_T(cin, cout) > 0 && wino_routed_any_T(cin, cout)) {
+            r.wu_pair = pack_wino_pair(o, w2, ws, cout, cout, cin, r.conv2.Mp);
+            if (!r.wu_pair) return false;
+        }
     }
     r.temb_off = (int)tpb.size();
     tpw.insert(tpw.end(), tw, tw + (size_t)2 * cout * u->temb);
@@ -1108,7 +1180,7 @@ struct UnetWs {
     float* xin;
     float *xk, *ck, *cinc;      // sampler runs: the sample alone in K4P, the condition alone, conv_in's condition half (+ bias), computed once per run
     std::vector<float*> skips;
-    float *cur[2], *r, *h1, *sc, *ta, *tb, *upt, *gno, *qk, *v, *att, *ff;
+    float *cur[2], *r, *h1, *sc, *ta, *tb, *upt, *gno, *wpl, *qk, *v, *att, *ff;
     int ss_stride = 0;
     // GroupNorm partial statistics of an activation buffer (written by its producer's epilogue, read by gn_stream)
     std::map<const float*, float2*> gpart;
@@ -1173,11 +1245,15 @@ static void plan_ws(const lds_unet* u, Arena& A, int B, int T, UnetWs& w) {
     // a resnet convolution routed to conv_wino reads the four Winograd planes from `gno`, 4 C ceil(T / 2) floats per utterance (twice the
     // direct K4P tensor).  Only the exact-fp32 default mode routes, but the slot is sized alike in every mode: a handle's workspace then
     // never shrinks when it is switched to a split mode or to latency mode.
+    // `wpl`: the planes of a routed conv2 + shortcut pair (run_wconv_pair).  Not `gno`: conv1's pass writes the shortcut's planes while
+    // conv1's own planes live there.  Sized alike in every mode, as `gno` is.
+    size_t maxwpl = 0;
     {
         auto planes = [&](const ResnetW& r, int Tl) {
             const size_t P = (size_t)(Tl + 1) / 2;
             if (r.conv1.wu && wino_routed(r.cin, r.cout, Tl)) maxgn = std::max(maxgn, 4 * (size_t)r.cin * P);
             if (r.conv2.wu && wino_routed(r.cout, r.cout, Tl)) maxgn = std::max(maxgn, 4 * (size_t)r.cout * P);
+            if (r.wu_pair && wino_pair_routed(r.cin, r.cout, Tl)) maxwpl = std::max(maxwpl, wino_pair_plane_floats(r.cin, r.cout, Tl));
         };
         for (int i = 0; i < nb; ++i) {
             for (const ResnetW& r : u->down[i].res) planes(r, Ts[i]);
@@ -1195,6 +1271,7 @@ static void plan_ws(const lds_unet* u, Arena& A, int B, int T, UnetWs& w) {
     w.r = scratch("r"); w.h1 = scratch("h1"); w.sc = A.f(B * maxct, "sc");
     w.ta = A.f(B * maxct, "ta"); w.tb = A.f(B * maxct, "tb"); w.upt = A.f(B * maxct, "upt");
     w.gno = A.f(B * maxgn, "gno");
+    w.wpl = maxwpl ? A.f(B * maxwpl, "wpl") : nullptr;
     w.qk = A.f(B * maxatt * 2, "qk"); w.v = A.f(B * (maxatt + 2048), "v"); w.att = A.f(B * maxatt, "att"); w.ff = A.f(B * maxatt * 4, "ff");
     w.lnp = (float2*)A.f(B * (maxatt / 32 + 64) * 2, "lnp");
     w.lens_dev = (int*)A.f(64, "lens");
@@ -1251,7 +1328,16 @@ static int run_resnet(const lds_unet* u, const ResnetW& r, const UnetWs& w, cons
     // exact-fp32 mode, shapes of wino_routed's table: the GroupNorm pass writes the Winograd planes instead of the K4P tensor and conv_wino
     // reads them (the debug trace records K4P tensors: a traced run keeps the direct path)
     const bool wino_ok = !bf3 && !u->latency_mode && !g_trace_on.load(std::memory_order_relaxed);
-    if (wino_ok && r.conv1.wu && wino_routed(C1 + C2, r.cout, T)) {
+    // ... and a routed conv2 + shortcut pair reads `wpl`: conv1's pass writes the shortcut's planes into its last cin / 16 blocks on the way
+    const bool wino1 = wino_ok && r.conv1.wu && wino_routed(C1 + C2, r.cout, T);
+    const bool wpair = wino1 && r.has_sc && r.wu_pair && w.wpl && wino_pair_routed(C1 + C2, r.cout, T);
+    const long long wpl_stride = (long long)wino_pair_plane_floats(C1 + C2, r.cout, T);
+    if (wpair) {
+        const int Pn = (T + 1) / 2;
+        HIP_TRY(launch_gn_wino_pair(x1, x2, C1, C2, T, u->G, 1e-5f, r.g1, r.b1, nullptr, 0, 0, 1, w.gp(x1), x2 ? w.gp(x2) : nullptr, w.gno, (long long)(C1 + C2) * 4 * Pn,
+                                    w.wpl + (size_t)r.cout * 4 * Pn, wpl_stride, B, st, tl_lens, lvl));
+        LDS_TRY(run_wconv(r.conv1, w.gno, T, nullptr, w.gp(w.h1), w.h1, B, st, lvl));
+    } else if (wino1) {
         HIP_TRY(launch_gn_wino(x1, x2, C1, C2, T, u->G, 1e-5f, r.g1, r.b1, nullptr, 0, 0, 1, w.gp(x1), x2 ? w.gp(x2) : nullptr, w.gno, B, st, tl_lens, lvl));
         LDS_TRY(run_wconv(r.conv1, w.gno, T, nullptr, w.gp(w.h1), w.h1, B, st, lvl));
     } else {
@@ -1266,6 +1352,11 @@ static int run_resnet(const lds_unet* u, const ResnetW& r, const UnetWs& w, cons
     if (wino_ok && !r.has_sc && C2 == 0 && r.conv2.wu && wino_routed(r.cout, r.cout, T)) {
         HIP_TRY(launch_gn_wino(w.h1, nullptr, r.cout, 0, T, u->G, 1e-5f, r.g2, r.b2, w.tproj, w.ss_stride, r.temb_off, 1, w.gp(w.h1), nullptr, w.gno, B, st, tl_lens, lvl));
         return run_wconv(r.conv2, w.gno, T, x1, w.gp(out), out, B, st, lvl);
+    }
+    if (wpair) {
+        HIP_TRY(launch_gn_wino_pair(w.h1, nullptr, r.cout, 0, T, u->G, 1e-5f, r.g2, r.b2, w.tproj, w.ss_stride, r.temb_off, 1, w.gp(w.h1), nullptr, w.wpl, wpl_stride,
+                                    nullptr, 0, B, st, tl_lens, lvl));
+        return run_wconv_pair(r.wu_pair, C1 + C2, r.cout, r.conv2.Mp, w.wpl, T, r.bias_pair, w.gp(out), out, B, st, lvl);
     }
     HIP_TRY(gn_any(bf3, w.h1, nullptr, r.cout, 0, T, u->G, 1e-5f, r.g2, r.b2, w.tproj, w.ss_stride, r.temb_off, 1, w.gp(w.h1), nullptr, w.gno, B, st, lvl));
     TRACE_ACT("gn2", w.gno, r.cout, T);
@@ -4630,6 +4721,166 @@ extern "C" int lds_bench_wino(const float* x1, const float* x2, int C1, int C2, 
         HIP_TRY(hipEventElapsedTime(&d, ev[0], ev[1]));
         HIP_TRY(hipEventElapsedTime(&w, ev[1], ev[2]));
         ms_direct[r] = d / iters; ms_wino[r] = w / iters;
+    }
+    for (auto& e : ev) (void)hipEventDestroy(e);
+    HIP_TRY(hipStreamSynchronize(st));
+    return rc;
+}
+
+// ---- conv2 + shortcut as one conv_wino launch (include/lds_test.h) ----
+extern "C" int lds_test_wino_pair_pack(const float* g, const float* S, int Co, int Cm, int Cin, float* U) {
+    if (!g || !S || !U || Co < 1 || Cm < 1 || Cin < 2 || (Cin & 1)) return set_error(LDS_EINVAL, "bad argument");
+    std::vector<float> u;
+    wino_pair_taps(g, S, Co, Cm, Cin, u);
+    memcpy(U, u.data(), u.size() * sizeof(float));
+    return LDS_OK;
+}
+extern "C" int lds_test_wino_pair_min_T(int Cin, int Cm) { return wino_pair_min_T(Cin, Cm); }
+struct lds_wino_pair_test {      // (the entries' arguments, gathered)
+    const float *h, *x1, *x2; int Cm, C1, C2, T;
+    const float *gamma1, *beta1, *gamma2, *beta2, *scale_shift; int groups;
+    const float *w2, *b2, *ws, *bs;
+    const int32_t* lengths; int poison, cfg, lvl;
+};
+// the tail of a resnet with a shortcut from conv1's GroupNorm pass on (run_resnet): K4P sources with their partials, both weight forms
+struct WinoPairTestState {
+    Owner own; TmpDev tmp; ConvW W2, Ws;
+    float *wu_pair = nullptr, *bias_pair = nullptr, *gamma1 = nullptr, *beta1 = nullptr, *gamma2 = nullptr, *beta2 = nullptr;
+    float *kh = nullptr, *k1 = nullptr, *k2 = nullptr, *v1 = nullptr, *wpl = nullptr, *gno = nullptr, *ko = nullptr;
+    float2 *gph = nullptr, *gp1 = nullptr, *gp2 = nullptr;
+    int *lens = nullptr, *lens_lvl = nullptr;
+    int Cin = 0, P = 0;
+    size_t v1_floats = 0, wpl_floats = 0, out_floats = 0;
+};
+static int wino_pair_test_setup(const lds_wino_pair_test* a, int B, hipStream_t st, WinoPairTestState& s) {
+    if (!a || !a->h || !a->x1 || !a->w2 || !a->b2 || !a->ws || !a->bs || !a->gamma1 || !a->beta1 || !a->gamma2 || !a->beta2 || B < 1 || B > 64 || a->T < 1 ||
+        (a->C2 > 0) != (a->x2 != nullptr) || a->C1 < 16 || (a->C1 & 15) || a->C2 < 0 || (a->C2 & 15) || a->Cm < 16 || (a->Cm & 15) || a->groups < 1 ||
+        (a->C1 + a->C2) % a->groups || ((a->C1 + a->C2) / a->groups) % 16 || a->Cm % a->groups || (a->Cm / a->groups) % 16 || a->cfg < 0 || a->lvl < 0 || a->lvl > 30)
+        return set_error(LDS_EINVAL, "bad argument");
+    const int Cin = a->C1 + a->C2, Cm = a->Cm, T = a->T, nT = (T + 31) / 32;
+    s.Cin = Cin; s.P = (T + 1) / 2;
+    int32_t reduced[64];
+    for (int b = 0; b < B && a->lengths; ++b) {
+        int n = a->lengths[b];
+        for (int i = 0; i < a->lvl && n >= 1; ++i) n = (n - 1) / 2 + 1;
+        if (n < 1 || n > T) return set_error(LDS_EINVAL, "lengths[%d] = %d (%d at level %d) outside 1 .. %d", b, a->lengths[b], n, a->lvl, T);
+        reduced[b] = n;
+    }
+    if (!pack_conv(s.own, a->w2, nullptr, Cm, Cm, 3, s.W2) || !pack_conv(s.own, a->ws, nullptr, Cm, Cin, 1, s.Ws)) return set_error(LDS_ENOMEM, "upload failed");
+    s.wu_pair = pack_wino_pair(s.own, a->w2, a->ws, Cm, Cm, Cin, s.W2.Mp);
+    std::vector<float> bp(s.W2.Mp, 0.f);
+    for (int co = 0; co < Cm; ++co) bp[co] = a->b2[co] + a->bs[co];
+    s.bias_pair = s.own.upload(bp);
+    s.gamma1 = up_vec(s.own, a->gamma1, Cin); s.beta1 = up_vec(s.own, a->beta1, Cin);
+    s.gamma2 = up_vec(s.own, a->gamma2, Cm); s.beta2 = up_vec(s.own, a->beta2, Cm);
+    LDS_TRY(test_upload_lens(s.tmp, a->lengths, B, s.lens, st));
+    LDS_TRY(test_upload_lens(s.tmp, a->lengths ? reduced : nullptr, B, s.lens_lvl, st));
+    s.v1_floats = (size_t)B * Cin * 4 * s.P; s.wpl_floats = (size_t)B * wino_pair_plane_floats(Cin, Cm, T); s.out_floats = (size_t)B * Cm * (T + 2);
+    s.kh = s.tmp.f(s.out_floats);
+    s.k1 = s.tmp.f((size_t)B * a->C1 * (T + 2));
+    s.k2 = a->C2 ? s.tmp.f((size_t)B * a->C2 * (T + 2)) : nullptr;
+    s.gph = (float2*)s.tmp.f((size_t)B * (Cm / 16) * nT * 2);
+    s.gp1 = (float2*)s.tmp.f((size_t)B * (a->C1 / 16) * nT * 2);
+    s.gp2 = a->C2 ? (float2*)s.tmp.f((size_t)B * (a->C2 / 16) * nT * 2) : nullptr;
+    s.v1 = s.tmp.f(s.v1_floats);
+    s.wpl = s.tmp.f(s.wpl_floats);
+    s.gno = s.tmp.f(s.out_floats);      // (the direct path's K4P tensor in lds_bench_wino_pair)
+    s.ko = s.tmp.f(s.out_floats);
+    if (!s.wu_pair || !s.bias_pair || !s.gamma1 || !s.beta1 || !s.gamma2 || !s.beta2 || !s.kh || !s.k1 || (a->C2 && (!s.k2 || !s.gp2)) || !s.gph || !s.gp1 || !s.v1 ||
+        !s.wpl || !s.gno || !s.ko)
+        return set_error(LDS_ENOMEM, "alloc");
+    HIP_TRY(hipMemsetAsync(s.gph, 0xff, sizeof(float2) * (size_t)B * (Cm / 16) * nT, st));      // (NaN: a partial beyond a length is never read)
+    HIP_TRY(hipMemsetAsync(s.gp1, 0xff, sizeof(float2) * (size_t)B * (a->C1 / 16) * nT, st));
+    if (a->C2) HIP_TRY(hipMemsetAsync(s.gp2, 0xff, sizeof(float2) * (size_t)B * (a->C2 / 16) * nT, st));
+    HIP_TRY(launch_to_k4p(a->h, s.kh, B, Cm, T, Cm, 0, st, s.lens_lvl));
+    HIP_TRY(launch_to_k4p(a->x1, s.k1, B, a->C1, T, a->C1, 0, st, s.lens_lvl));
+    if (a->C2) HIP_TRY(launch_to_k4p(a->x2, s.k2, B, a->C2, T, a->C2, 0, st, s.lens_lvl));
+    if (a->poison) {      // NaN / Inf in the sources' pad frames and beyond the lengths: nothing of it may reach a plane
+        HIP_TRY(launch_k4p_poison(s.kh, B, Cm, T, s.lens_lvl, st));
+        HIP_TRY(launch_k4p_poison(s.k1, B, a->C1, T, s.lens_lvl, st));
+        if (a->C2) HIP_TRY(launch_k4p_poison(s.k2, B, a->C2, T, s.lens_lvl, st));
+    }
+    HIP_TRY(launch_gn_partials(s.kh, Cm, T, s.gph, B, st, s.lens_lvl, 0));
+    HIP_TRY(launch_gn_partials(s.k1, a->C1, T, s.gp1, B, st, s.lens_lvl, 0));
+    if (a->C2) HIP_TRY(launch_gn_partials(s.k2, a->C2, T, s.gp2, B, st, s.lens_lvl, 0));
+    return LDS_OK;
+}
+// conv1's pass with the side output, conv2's pass, the pair launch: run_resnet's three launches around conv1
+static int wino_pair_test_run(const lds_wino_pair_test* a, WinoPairTestState& s, float2* gnpart, int B, hipStream_t st) {
+    const long long stride = (long long)wino_pair_plane_floats(s.Cin, a->Cm, a->T);
+    HIP_TRY(launch_gn_wino_pair(s.k1, s.k2, a->C1, a->C2, a->T, a->groups, 1e-5f, s.gamma1, s.beta1, nullptr, 0, 0, 1, s.gp1, s.gp2, s.v1, (long long)s.Cin * 4 * s.P,
+                                s.wpl + (size_t)a->Cm * 4 * s.P, stride, B, st, s.lens, a->lvl));
+    HIP_TRY(launch_gn_wino_pair(s.kh, nullptr, a->Cm, 0, a->T, a->groups, 1e-5f, s.gamma2, s.beta2, a->scale_shift, 2 * a->Cm, 0, 1, s.gph, nullptr, s.wpl, stride,
+                                nullptr, 0, B, st, s.lens, a->lvl));
+    return run_wconv_pair(s.wu_pair, s.Cin, a->Cm, s.W2.Mp, s.wpl, a->T, s.bias_pair, gnpart, s.ko, B, st, a->lvl, a->cfg);
+}
+extern "C" int lds_test_wino_pair(const float* h, const float* x1, const float* x2, int Cm, int C1, int C2, int T, const float* gamma1, const float* beta1,
+                                  const float* gamma2, const float* beta2, const float* scale_shift, int groups, const float* w2, const float* b2, const float* ws,
+                                  const float* bs, const int32_t* lengths, int poison, int cfg, int lvl, float* out, float* vplanes, float* pplanes, float* gnpart,
+                                  int B, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    if (!out) return set_error(LDS_EINVAL, "bad argument");
+    const lds_wino_pair_test args{h, x1, x2, Cm, C1, C2, T, gamma1, beta1, gamma2, beta2, scale_shift, groups, w2, b2, ws, bs, lengths, poison, cfg, lvl};
+    WinoPairTestState s;
+    LDS_TRY(wino_pair_test_setup(&args, B, st, s));
+    // NaN fill: every plane entry, every output frame (pads included) and every partial of a block inside a length must be written
+    HIP_TRY(hipMemsetAsync(s.v1, 0xff, sizeof(float) * s.v1_floats, st));
+    HIP_TRY(hipMemsetAsync(s.wpl, 0xff, sizeof(float) * s.wpl_floats, st));
+    HIP_TRY(hipMemsetAsync(s.ko, 0xff, sizeof(float) * s.out_floats, st));
+    if (gnpart) HIP_TRY(hipMemsetAsync(gnpart, 0xff, sizeof(float) * (size_t)B * (Cm / 16) * ((T + 31) / 32) * 2, st));
+    int rc;
+    {
+        LensScope ls(s.lens);
+        rc = wino_pair_test_run(&args, s, (float2*)gnpart, B, st);
+    }
+    if (rc == LDS_OK) {
+        HIP_TRY(tap_take(s.ko, s.out_floats, st));
+        HIP_TRY(launch_from_k4p(s.ko, out, B, Cm, T, st));
+        if (vplanes) HIP_TRY(hipMemcpyAsync(vplanes, s.v1, sizeof(float) * s.v1_floats, hipMemcpyDeviceToDevice, st));
+        if (pplanes) HIP_TRY(hipMemcpyAsync(pplanes, s.wpl, sizeof(float) * s.wpl_floats, hipMemcpyDeviceToDevice, st));
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    return rc;
+}
+// the direct tail (gn_wino on the block input, gn_stream, conv_dma_pair) against the new one (wino_pair_test_run) on one shape, alternating as
+// lds_bench_wino does: conv1's pass is in both blocks, so the side output's cost is in the comparison
+extern "C" int lds_bench_wino_pair(const float* h, const float* x1, const float* x2, int Cm, int C1, int C2, int T, const float* gamma1, const float* beta1,
+                                   const float* gamma2, const float* beta2, const float* scale_shift, int groups, const float* w2, const float* b2, const float* ws,
+                                   const float* bs, int cfg, int B, int iters, int reps, float* ms_direct, float* ms_wino, char* cfg_out, size_t cfg_cap,
+                                   void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    if (!ms_direct || !ms_wino || iters < 1 || reps < 1) return set_error(LDS_EINVAL, "bad argument");
+    const lds_wino_pair_test args{h, x1, x2, Cm, C1, C2, T, gamma1, beta1, gamma2, beta2, scale_shift, groups, w2, b2, ws, bs, nullptr, 0, cfg, 0};
+    const lds_wino_pair_test* a = &args;
+    WinoPairTestState s;
+    LDS_TRY(wino_pair_test_setup(a, B, st, s));
+    float2* gnpart = (float2*)s.tmp.f((size_t)B * (Cm / 16) * ((T + 31) / 32) * 2);
+    if (!gnpart) return set_error(LDS_ENOMEM, "alloc");
+    auto direct = [&]() -> int {
+        HIP_TRY(launch_gn_wino(s.k1, s.k2, C1, C2, T, groups, 1e-5f, s.gamma1, s.beta1, nullptr, 0, 0, 1, s.gp1, s.gp2, s.v1, B, st));
+        HIP_TRY(launch_gn_stream(s.kh, nullptr, Cm, 0, T, groups, 1e-5f, s.gamma2, s.beta2, scale_shift, 2 * Cm, 0, 1, s.gph, nullptr, s.gno, B, st));
+        const int rc = run_dconv_pair(s.W2, s.gno, s.Ws, s.k1, C1, s.k2, C2, T, s.bias_pair, gnpart, s.ko, B, st);
+        return rc == 1 ? set_error(LDS_EINVAL, "bench wino pair: no fused direct variant for these shapes") : rc;
+    };
+    LDS_TRY(direct());
+    std::string cfgs = std::string("direct ") + conv_dma_last_config();
+    LDS_TRY(wino_pair_test_run(a, s, gnpart, B, st));
+    cfgs += std::string(" | wino ") + conv_wino_last_config();
+    if (cfg_out && cfg_cap) snprintf(cfg_out, cfg_cap, "%s", cfgs.c_str());
+    hipEvent_t ev[3];
+    for (auto& e : ev) HIP_TRY(hipEventCreate(&e));
+    int rc = LDS_OK;
+    for (int r = -1; r < reps && rc == LDS_OK; ++r) {      // (r = -1: one alternation that is not reported -- the first block of a shape runs into the clock's ramp)
+        HIP_TRY(hipEventRecord(ev[0], st));
+        for (int i = 0; i < iters && rc == LDS_OK; ++i) rc = direct();
+        HIP_TRY(hipEventRecord(ev[1], st));
+        for (int i = 0; i < iters && rc == LDS_OK; ++i) rc = wino_pair_test_run(a, s, gnpart, B, st);
+        HIP_TRY(hipEventRecord(ev[2], st));
+        HIP_TRY(hipEventSynchronize(ev[2]));
+        float d = 0.f, w = 0.f;
+        HIP_TRY(hipEventElapsedTime(&d, ev[0], ev[1]));
+        HIP_TRY(hipEventElapsedTime(&w, ev[1], ev[2]));
+        if (r >= 0) { ms_direct[r] = d / iters; ms_wino[r] = w / iters; }
     }
     for (auto& e : ev) (void)hipEventDestroy(e);
     HIP_TRY(hipStreamSynchronize(st));

@@ -275,6 +275,10 @@ lds_test_wino_conv               i:ppiiipppiippippiipppip
 lds_bench_wino                   i:ppiiipppiippipiiiipppzp
 lds_test_wino_conv_lvl           i:ppiiipppiippippiiipppip
 lds_test_wino_min_T              i:ii
+lds_test_wino_pair_pack          i:ppiiip
+lds_test_wino_pair               i:pppiiiipppppipppppiiippppip
+lds_bench_wino_pair              i:pppiiiipppppippppiiiipppzp
+lds_test_wino_pair_min_T         i:ii
 """
 SIGNATURES = dict(ln.split() for ln in (_PUBLIC + _TEST).splitlines() if ln)
 EXPORTS = [ln.split()[0] for ln in _PUBLIC.splitlines() if ln]
