@@ -593,6 +593,77 @@ int  lds_llama_score_workspace_bytes(const lds_llama* h, int B, int S, size_t* o
 int  lds_llama_score(lds_llama* h, const int64_t* input_ids, const int32_t* ids_len, const int64_t* labels, int B, int S, float* logprobs, int32_t* ranks,
                      float* loss, int32_t* n_counted, float* logits_out, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- speech to text: Whisper's text decoder on the native audio encoder (OpenAI whisper/model.py TextDecoder; the reference's
+ *      encoder/whisper/model.py:85-110 ResidualAttentionBlock(cross_attention=True) and :150-154 Whisper.logits / Whisper.forward, which
+ *      end in a `self.decoder` that it never builds; csrc/whisper_dec.hip; tests/whisper_decoder_numpy.py is the float64 restatement) ---------
+ * cfg: large-v3 is {51866, 448, 1280, 20, 32, 1500}.  Limits (LDS_EINVAL): n_state a multiple of 64 (<= 8192) with n_state / n_head == 64,
+ * 1 <= n_layer <= 64, 2 <= n_text_ctx <= 448, 1 <= n_audio_ctx <= 1500, 2 <= n_vocab <= 2^20.
+ * names: OpenAI Whisper's own checkpoint keys, fp32 host arrays in that layout: "decoder.token_embedding.weight" [n_vocab][n_state],
+ * "decoder.positional_embedding" [n_text_ctx][n_state], "decoder.blocks.N.{attn,cross_attn}.{query,value,out}.{weight,bias}",
+ * "decoder.blocks.N.{attn,cross_attn}.key.weight" (no bias), "decoder.blocks.N.{attn_ln,cross_attn_ln,mlp_ln}.{weight,bias}",
+ * "decoder.blocks.N.mlp.{0,2}.{weight,bias}", "decoder.ln.{weight,bias}"; a missing tensor gives LDS_EMISSING naming it.  The head is the
+ * token embedding transposed (tied): the handle keeps the embedding twice, [n_vocab][n_state] for the look-up and [n_state][n_vocab] for
+ * the head's column walk, n_vocab * n_state * 4 bytes each (266 MB each at large-v3 and 3.89 GB for the whole handle, both in units of 10^6 / 10^9 bytes).
+ *
+ * One workspace serves the three calls; lds_whisper_decoder_workspace_bytes(h, B, T, S) sizes it for B rows, T encoder frames and S text
+ * positions (a scoring pass's S, a decode's cap).  Its first part depends on B and T alone and holds what lds_whisper_decoder_cross leaves
+ * for the other two: the clips' frame counts and every layer's cross-attention keys and values, 2 * n_layer * B * T * n_state * 4 bytes
+ * (491 MB per 30 s clip at large-v3).  So: cross once per batch of clips, then any number of logits / generate calls with the SAME
+ * workspace, B and T.  The rest of the workspace's contents on entry do not matter to any call.  A small workspace gives LDS_ENOMEM with
+ * the size needed in the message; a bad argument returns before anything is enqueued.
+ *
+ * Exact fp32; one fixed-order accumulation per output that does not depend on the batch size; no floating-point atomics, so a repeat gives
+ * the same bits; a row of a batch equals that row run alone (B = 1, its own n_frames and prompt), tokens and log-probs bit for bit; a
+ * prefill row and a decode step go through the same kernels, so generate's logits_out equals logits on the produced sequence bit for bit.
+ * Whisper's d^-0.25 scaling of q and of k is applied once to their product (0.125 at d = 64, exact).
+ * Not built (LDS_EINVAL): sampling and temperature fallback, beam search, timestamp rules (ApplyTimestampRules), word alignment from
+ * alignment_heads, long-form windows, fp16, and a no-repeat n-gram ban (lm.hip's bit set spans 8192 columns, not this vocabulary). */
+typedef struct lds_whisper_decoder lds_whisper_decoder;
+typedef struct lds_whisper_decoder_cfg { int n_vocab, n_text_ctx, n_state, n_head, n_layer, n_audio_ctx; } lds_whisper_decoder_cfg;
+int  lds_whisper_decoder_create(const lds_whisper_decoder_cfg* cfg, int n_tensors, const char* const* names, const float* const* host_ptrs,
+                                const int64_t* numel, lds_whisper_decoder** out);
+void lds_whisper_decoder_destroy(lds_whisper_decoder* h);
+/* B 1 .. 64, T 1 .. n_audio_ctx, S 2 .. n_text_ctx */
+int  lds_whisper_decoder_workspace_bytes(const lds_whisper_decoder* h, int B, int T, int S, size_t* out);
+/* units dev [B][T][n_state], the encoder's output (lds_whisper_encode's layout); n_frames host int32 [B] (1 <= n_frames[b] <= T) or NULL
+ * (T everywhere).  Every layer's cross key and value rows, once per call, into the workspace.  Nothing at or beyond n_frames[b] is read
+ * (NaN included), and keys stop at n_frames[b] in every later step.  Takes any workspace of lds_whisper_decoder_workspace_bytes(h, B, T, S >= 2).
+ * n_frames is read during the call only; nothing synchronises. */
+int  lds_whisper_decoder_cross(lds_whisper_decoder* h, const float* units, const int32_t* n_frames, int B, int T, void* ws, size_t ws_bytes,
+                               void* stream);
+/* Whisper.logits: tokens dev int64 [B][S] (ids clamped to the vocabulary), tok_len dev int32 [B] or NULL (S everywhere; rows at and beyond
+ * tok_len[b] are computed from id 0 and mean nothing) -> logits dev [B][S][n_vocab] or NULL, from ONE causal pass over all B * S rows.
+ * Optionally logprobs / ranks dev [B][S-1], loss / n_counted dev [1] (all four or none) with exactly lds_lm_score's definitions over the
+ * whole vocabulary, labels dev int64 [B][S] or NULL (= tokens): position t predicts labels[b][t + 1], counted when t + 1 < tok_len[b] and
+ * the label lies in [0, n_vocab).  With logits NULL the rows go through a buffer of 64 rows and B * S * n_vocab floats are never stored.
+ * 2 <= S <= n_text_ctx.  Nothing synchronises. */
+int  lds_whisper_decoder_logits(lds_whisper_decoder* h, const int64_t* tokens, const int32_t* tok_len, const int64_t* labels, int B, int S, int T,
+                                float* logits, float* logprobs, int32_t* ranks, float* loss, int32_t* n_counted, void* ws, size_t ws_bytes,
+                                void* stream);
+/* Greedy decode.  suppress / begin_suppress: dev int32 lists; a listed id gets -inf at every step / at each row's first generated step only
+ * (HF's SuppressTokensLogitsProcessor / SuppressTokensAtBeginLogitsProcessor); ids outside the vocabulary are ignored.  num_beams must be
+ * 1, temperature 0 and no_repeat_ngram_size 0 (above). */
+typedef struct lds_whisper_decode_opts {
+    int max_new_tokens, eos, pad, no_repeat_ngram_size;
+    const int32_t* suppress;
+    const int32_t* begin_suppress;
+    int n_suppress, n_begin_suppress;
+    int num_beams;
+    float temperature;
+} lds_whisper_decode_opts;
+/* prompt dev int64 [B][P] with host int32 prompt_len[B] (1 .. P): <|startoftranscript|><|lang|><|transcribe|><|notimestamps|>, behind an
+ * optional <|startofprev|> prefix.  The prompt's positions but the last go through one causal prefill into the self-attention caches, then
+ * come cached steps.  cap (P < cap <= n_text_ctx): the sequences' capacity; row b stops at EOS, after max_new_tokens ids or at position
+ * cap, whichever comes first.
+ * -> tokens dev int64 [B][cap]: the prompt, then the generated ids, EOS kept, PAD after it;  token_logprob dev [B][max_new_tokens]: the
+ * chosen id's log-softmax over the unsuppressed columns (max and sum in a fixed order), 0 behind a row's end;  sum_logprob dev [B] or NULL;
+ * logits_out dev [max_new_tokens][B][n_vocab] or NULL: the raw logits of every step run (before the suppress lists; a finished row's are
+ * computed and mean nothing);  *n_tokens_host: the longest row's length, prompt included.
+ * Synchronises: before the first launch (prompt_len), at the EOS poll every 8 steps and at the end. */
+int  lds_whisper_decoder_generate(lds_whisper_decoder* h, const int64_t* prompt, const int32_t* prompt_len, int B, int P, int T, int cap,
+                                  const lds_whisper_decode_opts* opts, int64_t* tokens, float* token_logprob, float* sum_logprob, float* logits_out,
+                                  int* n_tokens_host, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- k-means semantic tokenizer: units -> tokens and the codebook fit (reference cluster/__init__.py:13-23 get_cluster_result /
  *      get_cluster_center_result, cluster/kmeans.py:10-50 _kpp, :108-131 euc_sim / max_sim, :184-198 the Lloyd step; called from
  *      17_preprocess_train_cluster.py and 19_preprocess_token.py) -------------------------------------------------------------------

@@ -367,6 +367,13 @@ int lds_debug_trace(int on);
 int lds_debug_trace_count(void);
 int lds_debug_trace_get(int i, char* name, size_t name_cap, const void** data, size_t* bytes);
 
+/* The Whisper decoder's vocabulary head alone (csrc/whisper_dec.hip: the linear's head epilogue + wd_choose_kernel).  x dev [N][K] (N <= 64,
+ * 32 <= K <= 8192), ln_g / ln_b dev [K] (the final LayerNorm), et dev [K][V] (the token embedding transposed), suppress dev int32
+ * [n_suppress] or NULL -> token dev int64 [N] (arg-max over the unsuppressed columns, ties to the lowest id), logprob dev [N] (its
+ * log-softmax over them), lse dev [N], logits dev [N][V] or NULL (raw).  Synchronises. */
+int lds_test_whisper_head(const float* x, const float* ln_g, const float* ln_b, const float* et, int N, int K, int V, const int32_t* suppress,
+                          int n_suppress, int64_t* token, float* logprob, float* lse, float* logits, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -458,6 +458,90 @@ def whisper_init_state(n_mels, n_audio_state, n_audio_layer, seed=0, init_weight
     return {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in st.items()}
 
 
+# ---- Whisper text decoder (OpenAI whisper/model.py TextDecoder; the reference's model.py:85-110 holds its blocks) -----------------------
+def whisper_decoder_param_shapes(n_vocab, n_text_ctx, n_text_state, n_text_layer):
+    """OpenAI's `decoder.*` state_dict key -> shape, in the module order of TextDecoder (`key` has no bias)"""
+    d = OrderedDict()
+    c = int(n_text_state)
+    d["decoder.positional_embedding"] = (int(n_text_ctx), c)
+    d["decoder.token_embedding.weight"] = (int(n_vocab), c)
+    for i in range(int(n_text_layer)):
+        p = f"decoder.blocks.{i}."
+        for a in ("attn", "cross_attn"):
+            d[p + a + ".query.weight"] = (c, c)
+            d[p + a + ".query.bias"] = (c,)
+            d[p + a + ".key.weight"] = (c, c)
+            d[p + a + ".value.weight"] = (c, c)
+            d[p + a + ".value.bias"] = (c,)
+            d[p + a + ".out.weight"] = (c, c)
+            d[p + a + ".out.bias"] = (c,)
+            d[p + a + "_ln.weight"] = (c,)
+            d[p + a + "_ln.bias"] = (c,)
+        d[p + "mlp.0.weight"] = (4 * c, c)
+        d[p + "mlp.0.bias"] = (4 * c,)
+        d[p + "mlp.2.weight"] = (c, 4 * c)
+        d[p + "mlp.2.bias"] = (c,)
+        d[p + "mlp_ln.weight"] = (c,)
+        d[p + "mlp_ln.bias"] = (c,)
+    d["decoder.ln.weight"] = (c,)
+    d["decoder.ln.bias"] = (c,)
+    return d
+
+
+def whisper_decoder_init_state(n_vocab, n_text_ctx, n_text_state, n_text_layer, seed=0, init_weights=None):
+    """Build-owned seeded weights for the text decoder.  Matrices at 3x the familiar 1/sqrt(fan_in) scale and unit-range embeddings: the
+    blocks then move the residual stream enough, and the tied head spreads the logits enough, that a seeded greedy path is not razor-thin
+    (the fixture recipe records every path's smallest top-2 gap and refuses a seed below 1e-3 x absmax)."""
+    if init_weights is None:
+        from . import init_weights
+    import numpy as np
+    shapes = whisper_decoder_param_shapes(n_vocab, n_text_ctx, n_text_state, n_text_layer)
+    st = {}
+    for k, sh in shapes.items():
+        if "_ln." in k or ".ln." in k:
+            st[k] = init_weights.uniform(k, sh, seed, 0.8, 1.2) if k.endswith(".weight") else init_weights.uniform(k, sh, seed, -0.1, 0.1)
+        elif k.endswith("embedding.weight") or k.endswith("positional_embedding"):
+            st[k] = init_weights.uniform(k, sh, seed, -1.0, 1.0)
+        elif k.endswith(".bias"):
+            st[k] = init_weights.uniform(k, sh, seed, -0.05, 0.05)
+        else:
+            b = 3.0 / float(np.sqrt(sh[1]))
+            st[k] = init_weights.uniform(k, sh, seed, -b, b)
+    return {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in st.items()}
+
+
+# openai-whisper's tokenizer.LANGUAGES in its order (the language tokens follow <|startoftranscript|> in this order); large-v3 added "yue"
+WHISPER_LANGUAGES = ("en zh de es ru ko fr ja pt tr pl ca nl ar sv it id hi fi vi he uk el ms cs ro da hu ta no th ur hr bg lt la mi ml cy sk te fa lv bn "
+                     "sr az sl kn et mk br eu is hy ne mn bs kk sq sw gl mr pa si km sn yo so af oc ka be tg sd gu am yi lo uz fo ht ps tk nn mt sa lb my "
+                     "bo tl mg as tt haw ln ha ba jw su yue").split()
+
+
+def whisper_special_tokens(n_vocab, **override):
+    """The special-token ids of a multilingual Whisper vocabulary, derived as openai-whisper's get_encoding lays them out behind the 50,257
+    byte-pair tokens: <|endoftext|>, <|startoftranscript|>, the n_vocab - 51766 language tokens, <|translate|>, <|transcribe|>,
+    <|startoflm|>, <|startofprev|>, <|nospeech|>, <|notimestamps|>, then the 1501 timestamps <|0.00|> .. <|30.00|>.
+    UNVERIFIED: written from memory of openai-whisper, with no tokenizer file at hand to confirm it against (for 51,866 it gives eot 50257,
+    sot 50258, languages from 50259, translate 50359, transcribe 50360, startoflm 50361, startofprev 50362, nospeech 50363, notimestamps
+    50364, timestamps from 50365).  Every id can be overridden by keyword; check them against the tokenizer that came with the checkpoint.
+    Returns a dict: eot, sot, translate, transcribe, startoflm, startofprev, nospeech, notimestamps, timestamp_begin, num_languages,
+    languages (code -> id)."""
+    n_vocab = int(n_vocab)
+    if n_vocab < 51865:
+        raise ValueError(f"whisper_special_tokens derives multilingual vocabularies (n_vocab >= 51865); for {n_vocab} pass every id yourself")
+    nl = n_vocab - 51765 - 1
+    if nl > len(WHISPER_LANGUAGES):
+        raise ValueError(f"n_vocab {n_vocab} implies {nl} languages; the table knows {len(WHISPER_LANGUAGES)}")
+    eot = 50257
+    t = dict(eot=eot, sot=eot + 1, translate=eot + 2 + nl, transcribe=eot + 3 + nl, startoflm=eot + 4 + nl, startofprev=eot + 5 + nl,
+             nospeech=eot + 6 + nl, notimestamps=eot + 7 + nl, timestamp_begin=eot + 8 + nl, num_languages=nl)
+    t["languages"] = {code: eot + 2 + i for i, code in enumerate(WHISPER_LANGUAGES[:nl])}
+    unknown = set(override) - set(t)
+    if unknown:
+        raise TypeError(f"unknown special token(s) {sorted(unknown)}")
+    t.update(override)
+    return t
+
+
 def whisper_mel_filters(n_mels, sr=16000, n_fft=400):
     """The filter bank of the reference's assets/mel_filters.npz ([n_mels][201], float32), computed: librosa.filters.mel(sr=16000,
     n_fft=400, n_mels=n_mels) -- Slaney's scale (linear below 1 kHz, logarithmic above), triangles normalised to unit area -- evaluated

@@ -41,6 +41,17 @@ class WhisperCfg(C.Structure):
     _fields_ = [("n_mels", C.c_int), ("n_state", C.c_int), ("n_head", C.c_int), ("n_layer", C.c_int), ("n_ctx", C.c_int)]
 
 
+class WhisperDecoderCfg(C.Structure):
+    _fields_ = [("n_vocab", C.c_int), ("n_text_ctx", C.c_int), ("n_state", C.c_int), ("n_head", C.c_int), ("n_layer", C.c_int),
+                ("n_audio_ctx", C.c_int)]
+
+
+class WhisperDecodeOpts(C.Structure):
+    _fields_ = [("max_new_tokens", C.c_int), ("eos", C.c_int), ("pad", C.c_int), ("no_repeat_ngram_size", C.c_int), ("suppress", C.c_void_p),
+                ("begin_suppress", C.c_void_p), ("n_suppress", C.c_int), ("n_begin_suppress", C.c_int), ("num_beams", C.c_int),
+                ("temperature", C.c_float)]
+
+
 EARLY_STOPPING = {True: 1, False: 0, "never": 2}
 
 
@@ -149,6 +160,12 @@ lds_llama_beam_workspace_bytes   i:piiiip
 lds_llama_generate_beam          i:pppiiippppzp
 lds_llama_score_workspace_bytes  i:piip
 lds_llama_score                  i:ppppiippppppzp
+lds_whisper_decoder_create       i:pipppp
+lds_whisper_decoder_destroy      v:p
+lds_whisper_decoder_workspace_bytes i:piiip
+lds_whisper_decoder_cross        i:pppiipzp
+lds_whisper_decoder_logits       i:ppppiiippppppzp
+lds_whisper_decoder_generate     i:pppiiiipppppppzp
 lds_kmeans_workspace_bytes       i:qiip
 lds_kmeans_prepare               i:piipp
 lds_kmeans_prepare_metric        i:piiipp
@@ -247,6 +264,7 @@ lds_test_lm_beam_step            i:piiiiiifiippppppppppppppppp
 lds_test_llama_beam_step         i:piiiiiifiiipppppppppppppppppppp
 lds_test_llama_beam_attn         i:pppppiiiiiiiipp
 lds_test_llama_generate_beam_poll i:pppiiippppzpi
+lds_test_whisper_head            i:ppppiiipippppp
 lds_test_dconv_pair              i:pppppppiiiiiipiiipppzp
 lds_test_dconv_ex                i:pppipzp
 lds_test_dma_magic_div           i:uup
@@ -1340,6 +1358,144 @@ class Llama(_Handle):
         check(lib().lds_llama_score(self.h, _dev(ids, torch.int64), _dev_or_null(ids_len, torch.int32), _dev_or_null(lab, torch.int64), B, S, _dev(lp),
                                     _dev(ranks), _dev(loss), _dev(n), _dev_or_null(logits), _dev(ws), ws.numel(), _stream()))
         return lp, ranks, loss, n, logits
+
+
+class WhisperDecoder(_Handle):
+    """Whisper's text decoder (lds_whisper_decoder_*): cross keys / values once per batch of clips, then teacher-forced logits / scores or
+    the greedy cached decode over them."""
+    KIND = "whisper_decoder"
+
+    def __init__(self, n_vocab, n_text_ctx, n_state, n_head, n_layer, n_audio_ctx, state):
+        """state: OpenAI Whisper's checkpoint keys ("decoder.token_embedding.weight", ...) -> fp32 CPU tensors / arrays"""
+        c = WhisperDecoderCfg(int(n_vocab), int(n_text_ctx), int(n_state), int(n_head), int(n_layer), int(n_audio_ctx))
+        self._create_weights(c, state)
+        self.n_vocab, self.n_text_ctx, self.n_state, self.n_audio_ctx = int(n_vocab), int(n_text_ctx), int(n_state), int(n_audio_ctx)
+        self._cross = None      # (device, stream, B, T) of the batch whose cross keys / values the workspace holds
+
+    def workspace_bytes(self, B, T, S):
+        return _bytes("lds_whisper_decoder_workspace_bytes", self.h, int(B), int(T), int(S))
+
+    def _ws(self, device, B, T, S):
+        """the current stream's buffer, large enough for S positions.  A buffer that had to grow has lost the cross part: it is recomputed
+        from the units of the last `cross` call."""
+        import torch
+        key = (str(device), int(torch.cuda.current_stream(device).cuda_stream), B, T)
+        if self._cross is None or self._cross[0] != key:
+            raise RuntimeError("WhisperDecoder: call cross(units, n_frames) for this batch (and on this stream) first")
+        ws = self.ws.get(self.workspace_bytes(B, T, S), device)
+        if ws.data_ptr() != self._cross[1]:
+            self._run_cross(ws, *self._cross[2:])
+        return ws
+
+    def _run_cross(self, ws, units, nf):
+        B, T, _ = units.shape
+        check(lib().lds_whisper_decoder_cross(self.h, _dev(units, _f32()), _host(nf), B, T, _dev(ws), ws.numel(), _stream()))
+        self._cross = (self._cross[0], ws.data_ptr(), units, nf)
+
+    def cross(self, units, n_frames=None, S=None):
+        """units fp32 [B,T,n_state] on the device (the audio encoder's output), n_frames B host ints (1 .. T) or None.  S: the text positions
+        the later calls will need (default n_text_ctx), so that the buffer does not have to grow behind the cross part."""
+        import torch
+        if units.dim() != 3 or units.shape[2] != self.n_state:
+            raise ValueError(f"units must be [B, T, {self.n_state}], got {tuple(units.shape)}")
+        B, T = int(units.shape[0]), int(units.shape[1])
+        nf = None if n_frames is None else _host_lengths(n_frames, B, 1, T, 64, "decoder")
+        units = units.contiguous()
+        ws = self.ws.get(self.workspace_bytes(B, T, self.n_text_ctx if S is None else int(S)), units.device)
+        self._cross = ((str(units.device), int(torch.cuda.current_stream(units.device).cuda_stream), B, T), None, None, None)
+        self._run_cross(ws, units, nf)
+
+    def logits(self, tokens, tok_len=None, labels=None, return_logits=True, score=False):
+        """tokens int64 [B,S] on the device, tok_len int32 [B] on the device or None.  Returns logits [B,S,n_vocab] (return_logits), or with
+        score=True the tuple (logprobs [B,S-1], ranks int32 [B,S-1], loss [], n_counted int32 [], logits or None)."""
+        import torch
+        if tokens.dim() != 2:
+            raise ValueError(f"tokens must be [B, S], got {tuple(tokens.shape)}")
+        B, S = (int(v) for v in tokens.shape)
+        if labels is not None and tuple(labels.shape) != (B, S):
+            raise ValueError(f"labels must have tokens' shape {(B, S)}, got {tuple(labels.shape)}")
+        if self._cross is None:
+            raise RuntimeError("WhisperDecoder: call cross(units, n_frames) first")
+        T = self._cross[0][3]
+        if self._cross[0][2] != B:
+            raise ValueError(f"tokens hold {B} rows, the cross keys {self._cross[0][2]}")
+        dev = tokens.device
+        ids = tokens.contiguous()
+        lab = labels.contiguous() if labels is not None else None
+        lg = torch.empty(B, S, self.n_vocab, dtype=torch.float32, device=dev) if return_logits else None
+        lp = ranks = loss = n = None
+        if score:
+            lp = torch.empty(B, S - 1, dtype=torch.float32, device=dev)
+            ranks = torch.empty(B, S - 1, dtype=torch.int32, device=dev)
+            loss = torch.empty((), dtype=torch.float32, device=dev)
+            n = torch.empty((), dtype=torch.int32, device=dev)
+        ws = self._ws(dev, B, T, S)
+        check(lib().lds_whisper_decoder_logits(self.h, _dev(ids, torch.int64), _dev_or_null(tok_len, torch.int32), _dev_or_null(lab, torch.int64), B, S, T,
+                                               _dev_or_null(lg), _dev_or_null(lp), _dev_or_null(ranks), _dev_or_null(loss), _dev_or_null(n), _dev(ws),
+                                               ws.numel(), _stream()))
+        return (lp, ranks, loss, n, lg) if score else lg
+
+    def generate(self, prompt, prompt_len, max_new_tokens, eos, pad, suppress=None, begin_suppress=None, return_logits=False, cap=None,
+                 no_repeat_ngram_size=0, num_beams=1, temperature=0.0):
+        """Greedy decode.  prompt int64 [B,P] on the device, prompt_len B host ints (1 .. P); suppress / begin_suppress: id lists or None.
+        cap: the sequences' capacity (default min(max(prompt_len) + max_new_tokens, n_text_ctx)).  Returns (tokens [B,n] with the prompt in
+        front, EOS kept, PAD after it; token_logprob [B,max_new_tokens]; sum_logprob [B]; logits [steps,B,n_vocab] or None)."""
+        import torch
+        if prompt.dim() != 2:
+            raise ValueError(f"prompt must be [B, P], got {tuple(prompt.shape)}")
+        B, P = (int(v) for v in prompt.shape)
+        if self._cross is None:
+            raise RuntimeError("WhisperDecoder: call cross(units, n_frames) first")
+        T = self._cross[0][3]
+        if self._cross[0][2] != B:
+            raise ValueError(f"prompt holds {B} rows, the cross keys {self._cross[0][2]}")
+        pl = _host_lengths(prompt_len, B, 1, P)
+        max_new = int(max_new_tokens)
+        if cap is None:
+            cap = min(int(pl.max()) + max(max_new, 1), self.n_text_ctx)
+        cap = int(cap)
+        dev = prompt.device
+        lists = [None if v is None or len(v) == 0 else torch.as_tensor(list(v), dtype=torch.int32).to(dev) for v in (suppress, begin_suppress)]
+        o = WhisperDecodeOpts(max_new, int(eos), int(pad), int(no_repeat_ngram_size), lists[0].data_ptr() if lists[0] is not None else None,
+                              lists[1].data_ptr() if lists[1] is not None else None, 0 if lists[0] is None else lists[0].numel(),
+                              0 if lists[1] is None else lists[1].numel(), int(num_beams), float(temperature))
+        ids = prompt.contiguous()
+        tokens = torch.empty(B, max(cap, 1), dtype=torch.int64, device=dev)
+        tlp = torch.empty(B, max(max_new, 1), dtype=torch.float32, device=dev)
+        slp = torch.empty(B, dtype=torch.float32, device=dev)
+        lg = torch.empty(max(max_new, 1), B, self.n_vocab, dtype=torch.float32, device=dev) if return_logits else None
+        n = C.c_int()
+        # (the shape refusals come from the library, before anything is enqueued; the workspace is sized only for shapes it takes)
+        ok = 1 <= B <= 64 and 2 <= cap <= self.n_text_ctx
+        ws = self._ws(dev, B, T, cap) if ok else torch.empty(256, dtype=torch.uint8, device=dev)
+        check(lib().lds_whisper_decoder_generate(self.h, _dev(ids, torch.int64), _host(pl), B, P, T, cap, C.byref(o), _dev(tokens), _dev(tlp), _dev(slp),
+                                                 _dev_or_null(lg), C.byref(n), _dev(ws), ws.numel(), _stream()))
+        toks = tokens[:, : n.value].contiguous()
+        steps = max(1, n.value - int(pl.min()))
+        return toks, tlp, slp, (lg[:steps] if lg is not None else None)
+
+
+def _f32():
+    import torch
+    return torch.float32
+
+
+def whisper_head_test(x, ln_g, ln_b, et, suppress=None, return_logits=False):
+    """lds_test_whisper_head: x [N,K], ln_g / ln_b [K], et [K,V] fp32 on the device, suppress an id list or None ->
+    (token int64 [N], logprob [N], lse [N], logits [N,V] or None)"""
+    import torch
+    N, K = (int(v) for v in x.shape)
+    V = int(et.shape[1])
+    dev = x.device
+    sup = None if suppress is None or len(suppress) == 0 else torch.as_tensor(list(suppress), dtype=torch.int32).to(dev)
+    tok = torch.empty(N, dtype=torch.int64, device=dev)
+    lp = torch.empty(N, dtype=torch.float32, device=dev)
+    lse = torch.empty(N, dtype=torch.float32, device=dev)
+    lg = torch.empty(N, V, dtype=torch.float32, device=dev) if return_logits else None
+    check(lib().lds_test_whisper_head(_dev(x.contiguous(), torch.float32), _dev(ln_g.contiguous(), torch.float32), _dev(ln_b.contiguous(), torch.float32),
+                                      _dev(et.contiguous(), torch.float32), N, K, V, _dev_or_null(sup, torch.int32), 0 if sup is None else sup.numel(),
+                                      _dev(tok), _dev(lp), _dev(lse), _dev_or_null(lg), _stream()))
+    return tok, lp, lse, lg
 
 
 # ---- k-means semantic tokenizer (lds_kmeans_*): thin wrappers; X [N, D] and C [K, D] contiguous fp32 device tensors ----
